@@ -2,6 +2,8 @@
 """Headline benchmark: 256x256 images/sec/GPU, 8-step MaskGIT decode with vit-s-vqgan tokens.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR     (+ the last timed step's outputs as DIR/*.npy)
+    python bench.py --full ...              (+ self-check, host / power figures, roofline, extras, cpu_baseline)
     python bench.py --gpus N ...            (no WORLD_SIZE in the environment: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -14,9 +16,17 @@ reference does per generate() (generate.py:165; nothing is skipped).  Images sta
 Multi-GPU: weak scaling, every rank decodes its own 64 images (RNG keyed by global image index), no
 collective in the data path, one RCCL gather of the finished images to rank 0 inside the timed region.
 
-Before the timed region the exact timed configuration (bf16, hipGraph replay, concurrent micro-batch lanes)
-is checked once against the eager single-stream loop: ids and every decoded image must be bit-identical,
-otherwise no value is printed ("self_check").
+A plain run does only what the headline needs: set-up (workspace sizing + graph capture), warm-up, the timed
+steps, the optional output dump, the JSON line.  Everything else is measured with --full, off by default:
+before the timed region the exact timed configuration (bf16, hipGraph replay, concurrent micro-batch lanes)
+is checked once against the eager single-stream loop -- ids and every decoded image must be bit-identical,
+otherwise no value is printed ("self_check") --, and after it come the host-CPU and power figures, the
+per-kernel roofline, the secondary workloads ("extra") and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0's share) as DIR/<name>.npy in float32 /
+float64, at most 64 MB in all: arrays above a size cap are replaced by a fixed, seeded sample of their elements
+(DUMP_* below).  Weights, inputs and sampling seeds depend only on the arguments, so two builds can be compared
+output for output.
 
 One JSON line is printed by rank 0; see DESIGN.md for how `roofline` and `cpu_baseline` are derived.
 """
@@ -288,10 +298,71 @@ def make_step(workload, model, device, rank, decode_every_step=True):
                                      streams=lanes_arg(s), join=False, wait_current=False, guidance_scale=guidance)
         ids, imgs = pipe.generate_ids(ctx, B, T, 1.0, 5, flags, seed=1000 + i, image_base=rank * B, use_graph=USE_GRAPH,
                                       streams=lanes_arg(s), wait_current=False, guidance_scale=guidance)
+        if step.keep_last:                                  # --dump-outputs: the whole result of the call, not only the last image
+            step.last = (ids, imgs)
         return imgs[-1]
     step.joins = True
     step.ctx, step.flags = ctx, flags
+    step.keep_last, step.last = False, None
     return step
+
+
+# --dump-outputs: an array of at most DUMP_FULL_ELEMS elements is written whole (the headline's last images, B = 64 at 256 px:
+# 48 MiB of float32), a larger one as DUMP_SAMPLE_ELEMS elements at fixed, seeded positions; every decoded image of the step
+# contributes DUMP_STEP_SAMPLE elements at the same positions.  The worst case of the workloads above stays under DUMP_MAX_BYTES.
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_FULL_ELEMS = 64 * 3 * 256 * 256
+DUMP_SAMPLE_ELEMS = 1 << 22
+DUMP_STEP_SAMPLE = 1 << 16
+DUMP_SEED = 20240
+
+
+def sample_positions(numel, n, device):
+    """n sorted flat positions in [0, numel) drawn from a fixed seed (every position when n >= numel): the same positions for
+    the same shape in every run"""
+    import torch
+    if n >= numel:
+        return torch.arange(numel, device=device)
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    return torch.randint(0, numel, (n,), generator=g).sort().values.to(device)
+
+
+def step_outputs(workload, step, last):
+    """{name: (tensor, numpy dtype)} of what the last timed step returned to its caller; `last` is the timed loop's record of
+    that step: the reconstruction (vit-s-recon), the per-lane results [(ids, imgs, stream), ...] of a free-running step, or
+    the last image of a joined one, whose whole (ids, imgs) the step kept in step.last.  Lanes are joined in image order
+    (ids [B, N], imgs [n_decoded, B, C, H, W])."""
+    import torch
+    if WORKLOADS[workload][0] is None:
+        return {"reconstruction": (last, "float32")}
+    if isinstance(last, list):
+        ids = torch.cat([p[0] for p in last], dim=0)
+        imgs = torch.cat([p[1] for p in last], dim=1)
+    else:
+        ids, imgs = step.last
+    flat = imgs.reshape(imgs.shape[0], -1)
+    pos = sample_positions(flat.shape[1], DUMP_STEP_SAMPLE, flat.device)
+    return {"ids": (ids, "float64"),                                # token ids after the last MaskGIT step (exact in float64)
+            "images": (imgs[-1], "float32"),                        # the step's last decoded images: what step() returns
+            "decoded_images_sample": (flat[:, pos], "float32")}     # every decoded image of the step, at the same positions
+
+
+def dump_outputs(outdir, outputs):
+    """write {name: (tensor, dtype)} as outdir/<name>.npy (sampled above DUMP_FULL_ELEMS) -> {name: shape written}"""
+    import numpy as np
+    arrays = {}
+    for name, (x, dtype) in outputs.items():
+        x = x.detach()
+        if x.numel() > DUMP_FULL_ELEMS:
+            x = x.reshape(-1)[sample_positions(x.numel(), DUMP_SAMPLE_ELEMS, x.device)]
+        arrays[name] = np.ascontiguousarray(x.float().cpu().numpy() if dtype == "float32" else x.double().cpu().numpy())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def self_check(workload, model, step, device, rank):
@@ -754,10 +825,15 @@ def main():
     ap.add_argument("--workload", default=DEFAULT_WORKLOAD, choices=sorted(WORKLOADS))
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--final-decode-only", action="store_true", help="decode only the last step's image (not the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads measured after the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the self-check, host / power figures, roofline, secondary workloads and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary workloads measured after the headline")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     force_dist = os.environ.get("PM_BENCH_FORCE_DIST") == "1"
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or force_dist):
@@ -852,22 +928,27 @@ def main():
     for i in range(2):
         step(-1 - i)
     torch.cuda.synchronize(device)
-    log("self-check of the timed configuration against the eager single-stream loop")
-    ok, detail = self_check(args.workload, model, step, device, rank)
-    if dist is not None:
-        flag = torch.tensor([1 if ok else 0], device=device)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        ok = bool(flag.item())
-    if not ok:
-        log("SELF-CHECK FAILED: " + detail)
+    full = args.full
+    detail = None
+    if full:
+        log("self-check of the timed configuration against the eager single-stream loop")
+        ok, detail = self_check(args.workload, model, step, device, rank)
         if dist is not None:
-            dist.destroy_process_group()
-        flush_c_stdout()
-        if rank == 0:
-            print(json.dumps({"metric": "256x256 images/sec, 8-step MaskGIT decode (vit-s-vqgan), whole job", "value": None,
-                              "self_check": "FAILED: timed configuration differs from the eager single-stream loop", "n_gpus": world}),
-                  flush=True)
-        return 1
+            flag = torch.tensor([1 if ok else 0], device=device)
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            ok = bool(flag.item())
+        if not ok:
+            log("SELF-CHECK FAILED: " + detail)
+            if dist is not None:
+                dist.destroy_process_group()
+            flush_c_stdout()
+            if rank == 0:
+                print(json.dumps({"metric": "256x256 images/sec, 8-step MaskGIT decode (vit-s-vqgan), whole job", "value": None,
+                                  "self_check": "FAILED: timed configuration differs from the eager single-stream loop", "n_gpus": world}),
+                      flush=True)
+            return 1
+    dump = args.dump_outputs if rank == 0 else None
+    step.keep_last = bool(dump)
     log("warm-up")
     free_running = getattr(step, "joins", False) and STREAMS > 1
     for i in range(args.warmup):
@@ -877,15 +958,17 @@ def main():
             gather(step(i))
     drain_gathers()
     log("timed region")
-    if args.dtype == "bf16":
+    if args.dtype == "bf16" and full:
         from paintmind_amd import ops as _ops
         _ops.attention_fallbacks(reset=True, device=device)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize(device)
-    power = PowerSampler(local_rank).start() if rank == 0 else None
-    ru0 = resource.getrusage(resource.RUSAGE_SELF)      # process-wide: the main thread, lane threads, the HIP runtime's helpers
-    th0 = thread_cpu_seconds()
+    # --full only: power sampling and host-CPU accounting around the timed steps
+    power = PowerSampler(local_rank).start() if rank == 0 and full else None
+    ru0 = resource.getrusage(resource.RUSAGE_SELF) if full else None   # process-wide: the main thread, lane threads, the HIP runtime's helpers
+    th0 = thread_cpu_seconds() if full else None
+    last = None                                         # what the latest step returned (kept for --dump-outputs)
     t0 = time.perf_counter()
     # The host stays at most PACE steps ahead of the GPU: before step i is enqueued it waits until step i - PACE has finished,
     # and it waits QUIETLY (event.query() + a 1 ms sleep: on this ROCm a hipEventSynchronize spins even on a blocking event
@@ -911,25 +994,28 @@ def main():
                 ev.record(st)
                 evs.append(ev)
             paced.append(evs)
+            last = parts
         else:
-            gather(step(args.warmup + i))
+            last = gather(step(args.warmup + i))
             ev = torch.cuda.Event()
             ev.record()
             paced.append([ev])
     host_enqueue = time.perf_counter() - t0             # wall time until the last step is enqueued: INCLUDES the time the launch
-    ru1 = resource.getrusage(resource.RUSAGE_SELF)      # calls block on a full hardware queue (back-pressure, not host work)
+    ru1 = resource.getrusage(resource.RUSAGE_SELF) if full else None   # calls block on a full hardware queue (back-pressure, not host work)
     for evs in paced:
         wait_quietly(evs)                               # the remaining <= PACE steps, without spinning
     drain_gathers()
     torch.cuda.synchronize(device)
     own_elapsed = time.perf_counter() - t0              # this rank's own K steps (before waiting for the slowest rank)
-    ru2 = resource.getrusage(resource.RUSAGE_SELF)
-    th1 = thread_cpu_seconds()
-    power_summary = power.summary() if power is not None else None
-    by_thread = sorted(((th1[t][1] - th0.get(t, (None, 0.0))[1], "main" if t == os.getpid() else th1[t][0]) for t in th1), reverse=True)
-    main_cpu = th1.get(os.getpid(), (None, 0.0))[1] - th0.get(os.getpid(), (None, 0.0))[1]
-    cpu_enqueue = (ru1.ru_utime + ru1.ru_stime) - (ru0.ru_utime + ru0.ru_stime)
-    cpu_total = (ru2.ru_utime + ru2.ru_stime) - (ru0.ru_utime + ru0.ru_stime)   # incl. the closing synchronize (a spin or a sleep)
+    cpu_enqueue = cpu_total = 0.0
+    if full:
+        ru2 = resource.getrusage(resource.RUSAGE_SELF)
+        th1 = thread_cpu_seconds()
+        power_summary = power.summary() if power is not None else None
+        by_thread = sorted(((th1[t][1] - th0.get(t, (None, 0.0))[1], "main" if t == os.getpid() else th1[t][0]) for t in th1), reverse=True)
+        main_cpu = th1.get(os.getpid(), (None, 0.0))[1] - th0.get(os.getpid(), (None, 0.0))[1]
+        cpu_enqueue = (ru1.ru_utime + ru1.ru_stime) - (ru0.ru_utime + ru0.ru_stime)
+        cpu_total = (ru2.ru_utime + ru2.ru_stime) - (ru0.ru_utime + ru0.ru_stime)   # incl. the closing synchronize (a spin or a sleep)
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
@@ -946,6 +1032,7 @@ def main():
         per_rank_cpu = [(float(x[1].item()), float(x[2].item())) for x in allt]
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
+    dumped = dump_outputs(dump, step_outputs(args.workload, step, last)) if dump else None   # before anything else runs on the device
 
     result = {
         "metric": "256x256 images/sec, 8-step MaskGIT decode (vit-s-vqgan), whole job", "value": round(value, 3),
@@ -960,36 +1047,45 @@ def main():
                    "dispatch_mode": "AMD_DIRECT_DISPATCH=" + os.environ.get("AMD_DIRECT_DISPATCH", "1 (default)"),
                    "rank_mode": bool(_RANK_MODE)},
         "images_per_s_per_gpu": round(value / world, 3),
-        # workgroups of the bf16 attention kernel that left its fixed-reference fast path in the timed steps (rank 0)
-        "attention_fallbacks": _ops.attention_fallbacks(reset=True, device=device) if args.dtype == "bf16" else None,
-        "self_check": "ok", "self_check_detail": detail,
+        "full": full,
         "rccl_ranks": dist.get_world_size() if dist is not None else 0,
         "per_rank_images_per_s": [round(B * args.steps / e, 3) for e in per_rank],
-        # HOST COST of one step, measured (getrusage for the process, /proc/self/task for the threads), over the K timed steps
-        # including the closing synchronize.  host_main_thread_cpu_ms_per_step: the thread that enqueues (graph replays of the
-        # lanes, parameter copies, event records, pacing) -- the path's own host work.  host_cpu_ms_per_step: the whole
-        # process; the difference is the HIP runtime's helper threads, one of which busy-polls for as long as GPU work is
-        # outstanding (a full core whatever the wait policy).  host_enqueue_wall_ms_per_step: wall time until the last step is
-        # enqueued; it INCLUDES the pacing sleeps (the host stays <= PACE steps ahead), so it approaches ms_per_step.
-        "host_main_thread_cpu_ms_per_step": round(main_cpu / args.steps * 1e3, 3),
-        "host_cpu_ms_per_step": round(cpu_total / args.steps * 1e3, 3),
-        "host_cpu_fraction_of_one_core": round(cpu_total / max(own_elapsed, 1e-9), 4),
-        "host_enqueue_wall_ms_per_step": round(host_enqueue / args.steps * 1e3, 3),
-        "host_cpu_ms_per_step_by_thread": [{"thread": nm, "cpu_ms_per_step": round(sec / args.steps * 1e3, 2)} for sec, nm in by_thread[:4] if sec > 0],
-        "power": power_summary,
-        # energy of one step = mean package power in the timed region x its duration: at the 1.35-1.40 kW cap the step is
-        # energy-limited, and joules -- flops at ~0.9 pJ, HBM bytes at ~0.13 nJ, idle ~240 W -- is the currency
-        # for deciding which lever is worth building; joules_per_image is the per-GPU figure of merit next to images/s
-        "joules_per_step": round(power_summary["package_watts_mean"] * ms_per_step / 1e3, 1) if power_summary else None,
-        "joules_per_image": round(power_summary["package_watts_mean"] * ms_per_step / 1e3 / B, 3) if power_summary else None,
-        "per_rank_host_cpu_ms_per_step": [round(c[1] / args.steps * 1e3, 3) for c in per_rank_cpu],
         # the path's only collective: finished images of one step -> rank 0 (0 without a process group)
         "gather_bytes_per_step_per_rank": (B * 3 * 256 * 256 * 4 if cfg0 is None else B * 3 * img_px * img_px * 4) if dist is not None else 0,
     }
+    if dumped is not None:
+        result["dumped_outputs"] = dumped
+    if not full:
+        result["self_check"] = "not run (--full checks the timed configuration against the eager single-stream loop)"
+    else:
+        result.update({
+            # workgroups of the bf16 attention kernel that left its fixed-reference fast path in the timed steps (rank 0)
+            "attention_fallbacks": _ops.attention_fallbacks(reset=True, device=device) if args.dtype == "bf16" else None,
+            "self_check": "ok", "self_check_detail": detail,
+            # HOST COST of one step, measured (getrusage for the process, /proc/self/task for the threads), over the K timed steps
+            # including the closing synchronize.  host_main_thread_cpu_ms_per_step: the thread that enqueues (graph replays of the
+            # lanes, parameter copies, event records, pacing) -- the path's own host work.  host_cpu_ms_per_step: the whole
+            # process; the difference is the HIP runtime's helper threads, one of which busy-polls for as long as GPU work is
+            # outstanding (a full core whatever the wait policy).  host_enqueue_wall_ms_per_step: wall time until the last step is
+            # enqueued; it INCLUDES the pacing sleeps (the host stays <= PACE steps ahead), so it approaches ms_per_step.
+            "host_main_thread_cpu_ms_per_step": round(main_cpu / args.steps * 1e3, 3),
+            "host_cpu_ms_per_step": round(cpu_total / args.steps * 1e3, 3),
+            "host_cpu_fraction_of_one_core": round(cpu_total / max(own_elapsed, 1e-9), 4),
+            "host_enqueue_wall_ms_per_step": round(host_enqueue / args.steps * 1e3, 3),
+            "host_cpu_ms_per_step_by_thread": [{"thread": nm, "cpu_ms_per_step": round(sec / args.steps * 1e3, 2)}
+                                               for sec, nm in by_thread[:4] if sec > 0],
+            "power": power_summary,
+            # energy of one step = mean package power in the timed region x its duration: at the 1.35-1.40 kW cap the step is
+            # energy-limited, and joules -- flops at ~0.9 pJ, HBM bytes at ~0.13 nJ, idle ~240 W -- is the
+            # currency for deciding which lever is worth building; joules_per_image is the per-GPU figure of merit next to images/s
+            "joules_per_step": round(power_summary["package_watts_mean"] * ms_per_step / 1e3, 1) if power_summary else None,
+            "joules_per_image": round(power_summary["package_watts_mean"] * ms_per_step / 1e3 / B, 3) if power_summary else None,
+            "per_rank_host_cpu_ms_per_step": [round(c[1] / args.steps * 1e3, 3) for c in per_rank_cpu],
+        })
 
     log(f"timed region done: {ms_per_step:.1f} ms/step")
     pipeline = WORKLOADS[args.workload][0] is not None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and full and not args.no_roofline:
         # per-family kernel time of ONE more step, bracketed by hipEvents on the launch stream
         kinds = {}
         gf, af, sample_bytes = work_per_step(args.workload, decode_every_step=not args.final_decode_only, kinds=kinds)
@@ -1092,12 +1188,12 @@ def main():
             result["kernel_families"]["sample"]["read_GBps"] = round(sample_bytes / (ms_s * 1e-3) / 1e9, 1)
         result["end_to_end_tflops_per_gpu"] = round((gf + af) / (ms_per_step * 1e-3) / 1e12, 2)
     extra = {}
-    if rank == 0 and world == 1 and pipeline and not args.final_decode_only:
+    if rank == 0 and full and world == 1 and pipeline and not args.final_decode_only:
         # secondary number (NOT the headline): same loop, but only the image of the last step is decoded
         alt = make_step(args.workload, model, device, rank, decode_every_step=False)
         dt = time_steps(alt, device, 2, 1, 3, STREAMS > 1)
         extra["final_decode_only_images_per_s"] = round(B / dt, 2)
-    if rank == 0 and world == 1 and pipeline and not args.final_decode_only and not args.no_extra:
+    if rank == 0 and full and world == 1 and pipeline and not args.final_decode_only and not args.no_extra:
         log("drop-in Pipeline.generate() with default arguments")
         try:
             dg = dropin_generate(args.workload, model, device, max(2, min(args.steps, 5)))
@@ -1107,12 +1203,12 @@ def main():
             extra["dropin_generate"] = dg
         except Exception as e:
             extra["dropin_generate"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and pipeline and not args.no_extra and args.workload == DEFAULT_WORKLOAD:
+    if rank == 0 and full and world == 1 and pipeline and not args.no_extra and args.workload == DEFAULT_WORKLOAD:
         try:
             extra["small_batch_latency"] = small_batch_latency(args.workload, model, device)
         except Exception as e:
             extra["small_batch_latency"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_extra and args.workload == DEFAULT_WORKLOAD and args.dtype == "bf16":
+    if rank == 0 and full and world == 1 and not args.no_extra and args.workload == DEFAULT_WORKLOAD and args.dtype == "bf16":
         del step, model
         torch.cuda.empty_cache()
         for name, dt_name, k in EXTRA_WORKLOADS:
@@ -1124,7 +1220,7 @@ def main():
                 extra[key] = {"error": f"{type(e).__name__}: {e}"}
     if extra:
         result["extra"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.workload)
     if dist is not None:
         dist.barrier()

@@ -78,3 +78,61 @@ def test_rank_processes_run_eagerly_without_the_polling_helper_thread():
     assert run(WORLD_SIZE="8", PM_BENCH_RANK_GRAPH="1") == ["unset", "True"]
     assert run(AMD_DIRECT_DISPATCH="0") == ["0", "False"]           # whoever sets the mode gets the eager loop
     assert run(PM_BENCH_FORCE_DIST="1") == ["0", "False"]           # one GPU, one RCCL rank: exactly the program a rank runs
+
+
+def test_steps_must_be_positive():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "launch-selftest", "--steps", "0"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_joins_lanes_in_image_order(tmp_path):
+    """--dump-outputs writes what the last step returned: lanes concatenated in image order, ids exact in float64, images in
+    float32, every decoded image sampled at the same positions"""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    parts = [(torch.randint(0, 8192, (n, 16), generator=g), torch.rand(3, n, 3, 8, 8, generator=g), None) for n in (3, 2)]
+    shapes = bench.dump_outputs(str(tmp_path), bench.step_outputs(bench.DEFAULT_WORKLOAD, None, parts))
+    assert shapes == {"ids": [5, 16], "images": [5, 3, 8, 8], "decoded_images_sample": [3, 960]}     # small: every position
+    ids, imgs = np.load(tmp_path / "ids.npy"), np.load(tmp_path / "images.npy")
+    assert ids.dtype == np.float64 and imgs.dtype == np.float32
+    assert np.array_equal(ids, torch.cat([p[0] for p in parts]).numpy())
+    assert np.array_equal(imgs, torch.cat([p[1][-1] for p in parts]).numpy())
+    every = torch.cat([p[1] for p in parts], dim=1).reshape(3, -1)
+    assert np.array_equal(np.load(tmp_path / "decoded_images_sample.npy"), every.numpy())
+
+    class Joined:                                   # a joined step keeps its whole (ids, imgs) in step.last
+        last = (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts], dim=1))
+    again = bench.dump_outputs(str(tmp_path / "joined"), bench.step_outputs(bench.DEFAULT_WORKLOAD, Joined, imgs))
+    assert again == shapes and np.array_equal(np.load(tmp_path / "joined" / "images.npy"), imgs)
+
+
+def test_dump_outputs_samples_large_arrays_reproducibly(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_FULL_ELEMS", 100)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_ELEMS", 40)
+    x = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    a = bench.dump_outputs(str(tmp_path / "a"), {"reconstruction": (x, "float32")})
+    b = bench.dump_outputs(str(tmp_path / "b"), {"reconstruction": (x, "float32")})
+    assert a == b == {"reconstruction": [40]}
+    sa, sb = np.load(tmp_path / "a" / "reconstruction.npy"), np.load(tmp_path / "b" / "reconstruction.npy")
+    assert np.array_equal(sa, sb) and np.all(np.diff(sa) >= 0) and sa.max() < 1000
+
+
+def test_dump_outputs_fit_the_budget_for_every_workload():
+    """the largest dump any workload can write (full-size arrays, sampled where above the cap) stays within DUMP_MAX_BYTES"""
+    import bench
+    for wl, (cfg_name, B, T, L) in bench.WORKLOADS.items():
+        if wl == "launch-selftest":
+            continue
+        enc = bench.stage1_cfg(cfg_name)["enc"]
+        px = enc["image_size"]
+        images = B * 3 * px * px
+        nbytes = 4 * (images if images <= bench.DUMP_FULL_ELEMS else bench.DUMP_SAMPLE_ELEMS)
+        if cfg_name is not None:
+            nbytes += 8 * B * (px // enc["patch_size"]) ** 2 + 4 * T * bench.DUMP_STEP_SAMPLE
+        assert nbytes <= bench.DUMP_MAX_BYTES, (wl, nbytes)

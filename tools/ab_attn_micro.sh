@@ -11,7 +11,7 @@ for round in 1 2; do
     echo "== $(basename $src)"
     python tools/xattn_bench.py 2>&1 | grep -E "Nkv=(1024|77)\b"
     python tools/attn_only.py 2>&1 | grep -E "^B=64"
-    python bench.py --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); f = d['kernel_families']
 print('bench', d['value'], d['ms_per_step'], d['self_check'], 'attention', f['attention']['ms'])"

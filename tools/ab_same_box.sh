@@ -10,7 +10,7 @@ for round in 1 2; do
   for src in "$@"; do
     cp "$src" "$target"
     bash paintmind_amd/csrc/build.sh > /dev/null 2>&1 || { echo "build failed for $src"; continue; }
-    python bench.py --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
+    python bench.py --full --no-cpu-baseline --no-extra 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); f = d['kernel_families']
 print('$(basename $src)', d['value'], d['ms_per_step'], d['self_check'], 'gemm', f['gemm']['ms'], 'attention', f['attention']['ms'], 'ln', f['layernorm']['ms'])"

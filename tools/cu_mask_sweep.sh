@@ -4,7 +4,7 @@
 set -u
 run() {
   echo -n "$* : "
-  env "$@" python tools/cu_mask_lanes.py --no-cpu-baseline --no-extra --no-roofline 2>/dev/null | tail -1 | python -c "
+  env "$@" python tools/cu_mask_lanes.py --full --no-cpu-baseline --no-extra --no-roofline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['self_check'])"
 }

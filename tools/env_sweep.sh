@@ -1,6 +1,6 @@
 #!/bin/bash
 # development: same-box sweep of the run-time tile-walk knobs (single-stream default workload, GEMM family ms)
-run() { PM_BENCH_STREAMS=1 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+run() { PM_BENCH_STREAMS=1 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('$1', d['value'], 'gemm', d['kernel_families']['gemm']['ms'])"; }
 run "default(chunk256=6,chunk2b=12)"

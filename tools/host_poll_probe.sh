@@ -4,7 +4,7 @@
 #   gpurun -- 'bash tools/host_poll_probe.sh'
 run() {
   label=$1; shift
-  env "$@" python bench.py --steps 10 --no-cpu-baseline --no-extra --no-roofline 2>/dev/null | tail -1 | python -c "
+  env "$@" python bench.py --steps 10 --full --no-cpu-baseline --no-extra --no-roofline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 th = ', '.join(f\"{t['thread']} {t['cpu_ms_per_step']}\" for t in d.get('host_cpu_ms_per_step_by_thread', []))

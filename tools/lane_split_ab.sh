@@ -2,11 +2,9 @@
 # Same-box A/B of the micro-batch lane split and the decode-overlap row limit, through both timing harnesses of bench.py
 # (gpurun -- 'bash tools/lane_split_ab.sh'): "main" = the paced headline loop (python bench.py --workload W), "extra" = the
 # free-running loop the secondary workloads are timed with (bench.extra_workload).  PM_BENCH_LANE_SPLIT="" = the library's default.
-main() { wl=$1; cfg=$2; ov=$3; PMHIP_DECODE_OVERLAP_MAX_ROWS=$ov PM_BENCH_STREAMS=2 PM_BENCH_LANE_SPLIT=$cfg python bench.py --workload $wl --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline --no-extra --no-roofline > gpurun_out/ls.json 2>/dev/null; python - <<PY
-import json
-d=json.loads(open("gpurun_out/ls.json").read().strip().splitlines()[-1])
-print("main  $wl split=[$cfg] overlap_rows=$ov", d["value"], d["ms_per_step"], d["self_check"])
-PY
+main() { wl=$1; cfg=$2; ov=$3; PMHIP_DECODE_OVERLAP_MAX_ROWS=$ov PM_BENCH_STREAMS=2 PM_BENCH_LANE_SPLIT=$cfg python bench.py --workload $wl --steps ${STEPS:-6} --warmup 2 --full --no-cpu-baseline --no-extra --no-roofline 2>/dev/null | tail -1 | python -c "
+import sys, json
+d = json.loads(sys.stdin.read()); print('main  $wl split=[$cfg] overlap_rows=$ov', d['value'], d['ms_per_step'], d['self_check'])"
 }
 extra() { wl=$1; cfg=$2; ov=$3; PMHIP_DECODE_OVERLAP_MAX_ROWS=$ov PM_BENCH_STREAMS=2 PM_BENCH_LANE_SPLIT=$cfg python - <<PY 2>/dev/null
 import torch, bench
