@@ -445,7 +445,7 @@ int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return
  * what a handle latched: bit 0 LayerNorm fold (PMHIP_LN_UNFOLD unset), bit 1 bf16 hi/lo stream (PMHIP_HILO != 0), bit 2 row
- * statistics from the producers (PMHIP_LN_STATS != 0), bit 3 centred hi plane (PMHIP_HILO_CENTER != 0), bit 4
+ * statistics from the producers (always set: its switch is gone), bit 3 centred hi plane (PMHIP_HILO_CENTER != 0), bit 4
  * PMHIP_BLOCKING_WAIT, bit 5 (pmhip_s2_switches only; process-wide) AMD_DIRECT_DISPATCH=0: PMHIP_GENERATE_GRAPH requests run
  * the eager loop; -1 for a NULL handle.  A tool that A/Bs a switch asserts the mode it believes it measures. */
 int pmhip_s2_switches(const pmhip_s2* h);

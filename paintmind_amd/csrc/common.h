@@ -314,7 +314,7 @@ __device__ __forceinline__ float2 softmax_block_stat(float a, float b, float c, 
 // DEVELOPMENT KNOBS: tuning values and the switches of finished A/Bs (tools/*.sh sweep them).  They are read from the environment
 // only in a development build (PM_EXTRA_FLAGS=-DPM_DEV_KNOBS bash paintmind_amd/csrc/build.sh); the product library carries the
 // defaults as constants -- no configuration that no test runs (round-5 review, W6).  The switches the tests DO exercise stay
-// runtime: PMHIP_HILO, PMHIP_LN_UNFOLD, PMHIP_LN_STATS, PMHIP_HILO_CENTER, PMHIP_FOLD_MAX_ROWS (engine.hip Switches).
+// runtime: PMHIP_HILO, PMHIP_LN_UNFOLD, PMHIP_HILO_CENTER, PMHIP_FOLD_MAX_ROWS (engine.hip Switches).
 static inline int pm_dev_knob(const char* name, int dflt) {
 #ifdef PM_DEV_KNOBS
     const char* e = getenv(name);
@@ -327,3 +327,12 @@ static inline int pm_dev_knob(const char* name, int dflt) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t dtype_size(int dtype) { return dtype == PMHIP_BF16 ? 2 : 4; }
+
+// Can a LayerNorm over K columns be folded into the GEMM out[M,N] = A[M,K] (row stride lda) . W[N,K]^T (row stride ldw)?  THE
+// predicate: the engine's decision (M = one image's rows: folded or not must not depend on the batch), the GEMM entry points'
+// check and pmhip_lnfold_supported all ask it.  M, N whole 256x256 tiles, K whole pairs of K-tiles, and both operands within the
+// 32-bit byte offsets the 256x256 kernel addresses them with.
+inline bool pm_lnfold_shape_ok(int M, int N, int K, int lda, int ldw) {
+    return M % 256 == 0 && N % 256 == 0 && K % 128 == 0 && K >= 128 && (unsigned long long)M * lda * 2 < (1ull << 31) &&
+           (unsigned long long)N * ldw * 2 < (1ull << 31);
+}

@@ -186,6 +186,59 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     int L = 0, Lp = 0;
 };
 
+// The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
+// the fp32 stream + LayerNorm kernel of rounds 1-2): 1.3 % faster on the default workload (same box: 476.5 vs 470.6 images/s),
+// as accurate (DESIGN.md section 4d).  It was opt-in while 3-11 of 1800 generate() calls under concurrent lanes were not
+// bit-identical; that was a gfx950 packed-FP32 operand-select hazard in the folded epilogue (DESIGN.md section 4e), fixed in
+// gemm_common.h and gated by tests/test_isa_hazards.py.
+// The PMHIP_* switches are read ONCE, when a handle is created (a handle's graphs, workspace and fold decisions all depend on
+// them; a getenv on the hot path is also a data race with a caller that edits the environment from another thread).
+struct Switches {
+    int overlap_rows = 65536;   // PMHIP_DECODE_OVERLAP_MAX_ROWS: largest B * tokens whose decode loop defers each step's ViT decode
+                                // to a side stream beside the next step's tower (0 = never)
+    bool hilo = true;       // PMHIP_HILO=0: the fp32 stream + LayerNorm kernel of rounds 1-2
+    bool fold = true;       // PMHIP_LN_UNFOLD=1: the hi/lo pair, but the separate LayerNorm kernel
+    static Switches from_env() {
+        Switches w;
+        const char* e = getenv("PMHIP_HILO");
+        w.hilo = !(e && atoi(e) == 0);
+        e = getenv("PMHIP_LN_UNFOLD");
+        w.fold = !(e && atoi(e) != 0);
+        e = getenv("PMHIP_FOLD_MAX_ROWS");
+        w.fold_rows_cap = e ? atoi(e) : 0;
+        e = getenv("PMHIP_HILO_CENTER");
+        w.center = !(e && atoi(e) == 0);
+        e = getenv("PMHIP_BLOCKING_WAIT");
+        w.blocking_wait = e && atoi(e) != 0;
+        e = getenv("PMHIP_DECODE_OVERLAP_MAX_ROWS");
+        if (e) w.overlap_rows = atoi(e);
+        w.logits_stats = pm_dev_knob("PMHIP_LOGITS_STATS", 1) != 0;
+        return w;
+    }
+    int fold_rows_cap = 0;  // PMHIP_FOLD_MAX_ROWS (development / tests): cap on the rows one folded launch takes, see fold_rows()
+    bool center = true;     // PMHIP_HILO_CENTER=0: the residual producers do not centre the hi plane (A/B, tests)
+    bool logits_stats = true;     // PMHIP_LOGITS_STATS=0 (development builds, profiles/r06_d): the logits GEMM leaves no block statistics, the sampling kernel derives
+                                  // them from the rows it then has to read in full (same ids and scores, bit for bit)
+    bool blocking_wait = false;   // PMHIP_BLOCKING_WAIT=1: host waits between decode-loop segments sleep instead of spinning
+    // bit 2 (the producers leave row statistics for the fold) is constant: the switch that cleared it is gone, the bit keeps its place
+    int key() const { return (hilo ? 2 : 0) + (fold ? 1 : 0) + 4 + (center ? 8 : 0); }
+};
+
+// LayerNorm fold: where the per-row coefficients (TowerBufs::coef) of the CURRENT hi plane stand.  Every transition is written here:
+//   produced()  a residual GEMM wrote a new hi plane (and, with_parts, left its partial row statistics behind)  -> kStale
+//   requested() a folded LayerNorm is about to consume the plane: true = nobody can derive the coefficients from parts, the caller
+//               runs the pass over the plane now (-> kWritten); false = left to the first folded consumer (-> kDeferred)
+//   consumed()  a folded consumer is being launched: it writes the coefficients from parts or finds them written  -> kWritten
+// A reader of coef -- the centred producer, residual_gemm -- takes them unless kStale and refuses to run on kDeferred (round-5
+// advisor: the invariant was implicit).
+struct FoldState {
+    enum { kStale, kDeferred, kWritten } coef = kStale;
+    bool parts = false;     // TowerBufs::parts describe the current hi plane
+    void produced(bool with_parts) { coef = kStale; parts = with_parts; }
+    bool requested() { coef = parts ? kDeferred : kWritten; return !parts; }
+    void consumed() { coef = kWritten; }
+};
+
 struct TowerBufs {
     float* x = nullptr;     // residual stream, fp32 [M, dim]                      (fp32-verify mode)
     void* xh = nullptr;     // residual stream as a bf16 pair: x = hi + lo, [M, dim] each   (bf16-perf mode).  The hi plane IS
@@ -197,18 +250,14 @@ struct TowerBufs {
     float* split = nullptr; // dim_head != 64 only: f32 scratch of the plain head-split path [M, 3*inner]
     float* coef = nullptr;  // LayerNorm fold: per-row (rstd, -rstd * mean) of the hi plane
     float* parts = nullptr; // ... and the partial row statistics the last residual GEMM left behind, [M, dim/64, 2]
-    bool parts_valid = false;   // parts describe the CURRENT hi plane (set by residual_gemm, see tower_coef)
-    // centred hi plane (gemm_common.h, GemmParams::center_coef): the producers subtract the row mean the last LayerNorm saw
-    bool center = false;        // mode on (fold on and not PMHIP_HILO_CENTER=0)
-    bool coef_valid = false;    // coef holds the statistics of the CURRENT hi plane (set by tower_coef, cleared by a producer)
-    bool coef_deferred = false; // ... but nobody has WRITTEN them yet: tower_coef left that to the first folded consumer, which
-                                // materialises them from `parts` (fold_desc hands it the parts and clears this flag).  A reader of
-                                // coef -- the centred producer -- refuses to run while it is set (round-5 advisor: the invariant was implicit)
+    FoldState st;           // where coef and parts stand
     float* shift = nullptr;     // per-row running sum of the subtracted means: only where the absolute x is needed again (ViT encoder)
+    const Switches* sw = nullptr;   // the handle's
     bool hilo = false;      // bf16 mode
-    int fold_rows_cap = 0;  // Switches::fold_rows_cap
-    bool stats = true;      // producers leave row statistics (PMHIP_LN_STATS=0: the coefficient pass over the plane, A/B tests)
     bool fold = false;      // hilo and folding not disabled (PMHIP_LN_UNFOLD=1 forces the separate LayerNorm kernel: A/B tests)
+    // centred hi plane (gemm_common.h, GemmParams::center_coef): the producers subtract the row mean the last LayerNorm saw
+    // (fold on and not PMHIP_HILO_CENTER=0)
+    bool center() const { return fold && sw->center; }
 };
 
 // where a residual GEMM takes its addend from: fp32 rows (verify mode), or a pair of bf16 planes (bf16 mode)
@@ -230,46 +279,6 @@ int check_dim_head(const char* who, const pmhip_tower_cfg& tc) {
                "%s: heads=%d dim_head=%d: dim_head must be a multiple of 16 in [16,128] and heads*dim_head a multiple of 64", who, tc.heads, dh);
     return PMHIP_OK;
 }
-
-// The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
-// the fp32 stream + LayerNorm kernel of rounds 1-2): 1.3 % faster on the default workload (same box: 476.5 vs 470.6 images/s),
-// as accurate (DESIGN.md section 4d).  It was opt-in while 3-11 of 1800 generate() calls under concurrent lanes were not
-// bit-identical; that was a gfx950 packed-FP32 operand-select hazard in the folded epilogue (DESIGN.md section 4e), fixed in
-// gemm_common.h and gated by tests/test_isa_hazards.py.
-// The PMHIP_* switches are read ONCE, when a handle is created (a handle's graphs, workspace and fold decisions all depend on
-// them; a getenv on the hot path is also a data race with a caller that edits the environment from another thread).
-struct Switches {
-    int overlap_rows = 65536;   // PMHIP_DECODE_OVERLAP_MAX_ROWS: largest B * tokens whose decode loop defers each step's ViT decode
-                                // to a side stream beside the next step's tower (0 = never)
-    bool hilo = true;       // PMHIP_HILO=0: the fp32 stream + LayerNorm kernel of rounds 1-2
-    bool fold = true;       // PMHIP_LN_UNFOLD=1: the hi/lo pair, but the separate LayerNorm kernel
-    bool stats = true;      // PMHIP_LN_STATS=0: fold coefficients by a pass over the hi plane
-    static Switches from_env() {
-        Switches w;
-        const char* e = getenv("PMHIP_HILO");
-        w.hilo = !(e && atoi(e) == 0);
-        e = getenv("PMHIP_LN_UNFOLD");
-        w.fold = !(e && atoi(e) != 0);
-        e = getenv("PMHIP_LN_STATS");
-        w.stats = !(e && atoi(e) == 0);
-        e = getenv("PMHIP_FOLD_MAX_ROWS");
-        w.fold_rows_cap = e ? atoi(e) : 0;
-        e = getenv("PMHIP_HILO_CENTER");
-        w.center = !(e && atoi(e) == 0);
-        e = getenv("PMHIP_BLOCKING_WAIT");
-        w.blocking_wait = e && atoi(e) != 0;
-        e = getenv("PMHIP_DECODE_OVERLAP_MAX_ROWS");
-        if (e) w.overlap_rows = atoi(e);
-        w.logits_stats = pm_dev_knob("PMHIP_LOGITS_STATS", 1) != 0;
-        return w;
-    }
-    int fold_rows_cap = 0;  // PMHIP_FOLD_MAX_ROWS (development / tests): cap on the rows one folded launch takes, see fold_rows()
-    bool center = true;     // PMHIP_HILO_CENTER=0: the residual producers do not centre the hi plane (A/B, tests)
-    bool logits_stats = true;     // PMHIP_LOGITS_STATS=0 (development builds, profiles/r06_d): the logits GEMM leaves no block statistics, the sampling kernel derives
-                                  // them from the rows it then has to read in full (same ids and scores, bit for bit)
-    bool blocking_wait = false;   // PMHIP_BLOCKING_WAIT=1: host waits between decode-loop segments sleep instead of spinning
-    int key() const { return (hilo ? 2 : 0) + (fold ? 1 : 0) + (stats ? 4 : 0) + (center ? 8 : 0); }
-};
 
 // widest residual stream the hi/lo row operators (pmhip_split_hilo, pmhip_layernorm_hilo, pmhip_layernorm_to_hilo, pmhip_ln_coef,
 // pmhip_join_hilo: one wave per row, the row in registers) serve; wider bf16 towers keep the fp32 stream + pmhip_layernorm
@@ -296,14 +305,11 @@ int alloc_tower(Workspace& ws, const Switches& sw, const char* tag, int dtype, c
     WS(ws, (t + ".hid").c_str(), M * tc.hidden_pad * es, b.hid);
     WS(ws, (t + ".coef").c_str(), M * 2 * 4, b.coef);
     WS(ws, (t + ".parts").c_str(), M * (size_t)round_up(tc.dim, 64) / 64 * 2 * 4, b.parts);
-    b.parts_valid = false;
     b.split = nullptr;
     if (dh != 64) WS(ws, (t + ".split").c_str(), M * 3 * inner * 4, b.split);
+    b.sw = &sw;
     b.fold = b.hilo && dh == 64 && sw.fold;
-    b.stats = sw.stats;
-    b.fold_rows_cap = sw.fold_rows_cap;
-    b.center = b.fold && sw.center;
-    b.coef_valid = false;
+    b.st = FoldState{};
     b.shift = nullptr;
     return PMHIP_OK;
 }
@@ -319,41 +325,19 @@ ResSrc res_self(const TowerBufs& b, int dim) {
 int residual_gemm(int dtype, TowerBufs& b, const void* A, int lda, const void* W, int ldw, const float* bias, const ResSrc& r,
                   int M, int N, int K, hipStream_t s, float bias_mean = 0.f) {
     if (b.hilo) {
+        const bool self = r.hi == b.xh && r.rows == 0;                 // x += ... (not the GEMM that opens the stream)
+        const float* cc = (b.center() && self && b.st.coef != FoldState::kStale) ? b.coef : nullptr;
+        PM_REQUIRE(!cc || b.st.coef != FoldState::kDeferred,
+                   "residual_gemm: the fold coefficients of this LayerNorm were left to a folded consumer that never ran");
+        const int shift_mode = !b.shift ? 0 : (self ? (cc ? 2 : 0) : 1);
         // with the LayerNorm folded into the consumers the producer's epilogue also leaves the row statistics of the new hi plane
         // (16 bytes per 64 columns): the coefficient pass over the plane (pmhip_ln_coef, 14 us per launch at the bench shape)
-        // becomes a combination of 8-16 partials per row.  PMHIP_LN_STATS=0: the pass (A/B).
-        b.parts_valid = b.fold && N % 64 == 0 && N <= 1024 && b.stats;   // pmhip_ln_coef_parts combines <= 16 parts
-        const bool self = r.hi == b.xh && r.rows == 0;                 // x += ... (not the GEMM that opens the stream)
-        const float* cc = (b.center && self && b.coef_valid) ? b.coef : nullptr;
-        PM_REQUIRE(!cc || !b.coef_deferred, "residual_gemm: the fold coefficients of this LayerNorm were left to a folded consumer that never ran");
-        const int shift_mode = !b.shift ? 0 : (self ? (cc ? 2 : 0) : 1);
-        b.coef_valid = false;                                          // the hi plane changes
-        if (cc || b.shift)
-            return pmhip_gemm_hilo_center(A, lda, W, ldw, bias, r.hi, r.lo, r.ld, r.rows, b.xh, b.xl, N, M, N, K, b.parts_valid ? b.parts : nullptr,
-                                          cc, bias_mean, b.shift, shift_mode, s);
-        if (b.parts_valid) return pmhip_gemm_hilo_stats(A, lda, W, ldw, bias, r.hi, r.lo, r.ld, r.rows, b.xh, b.xl, N, M, N, K, b.parts, s);
-        return pmhip_gemm_hilo(A, lda, W, ldw, bias, r.hi, r.lo, r.ld, r.rows, b.xh, b.xl, N, M, N, K, s);
+        // becomes a combination of 8-16 partials per row.
+        b.st.produced(b.fold && N % 64 == 0 && N <= 1024);             // pmhip_ln_coef_parts combines <= 16 parts
+        return pmhip_gemm_hilo_center(A, lda, W, ldw, bias, r.hi, r.lo, r.ld, r.rows, b.xh, b.xl, N, M, N, K, b.st.parts ? b.parts : nullptr,
+                                      cc, bias_mean, b.shift, shift_mode, s);
     }
     return pmhip_gemm(dtype, A, lda, W, ldw, bias, r.f32, r.ld, r.rows, b.x, N, PMHIP_F32, M, N, K, s);
-}
-
-// (rstd, -rstd * mean) of the rows of the current hi plane into b.coef.  Where the last residual GEMM left partial row statistics
-// behind, the folded consumer itself produces coef from them (pmhip_lnfold::parts: in its own prologue for a small launch, by
-// pmhip_ln_coef_parts in front of it otherwise) and nothing is launched here; else the pass over the plane.
-int tower_coef(TowerBufs& b, int M, int dim, hipStream_t s) {
-    b.coef_valid = true;
-    b.coef_deferred = b.parts_valid;
-    if (b.parts_valid) return PMHIP_OK;
-    return pmhip_ln_coef(b.xh, 1e-5f, b.coef, M, dim, s);
-}
-// the fold descriptor of the rows [m0, ...) of the tower
-// the ONLY place a fold descriptor is built: a consumer handed a descriptor without `parts` would read coefficients nobody wrote
-pmhip_lnfold fold_desc(TowerBufs& b, int m0, int dim, const float* c, const float* d) {
-    pmhip_lnfold ln{};
-    ln.coef = b.coef + (size_t)m0 * 2; ln.c = c; ln.d = d;
-    if (b.parts_valid) { ln.parts = b.parts + (size_t)m0 * (dim / 64) * 2; ln.nparts = dim / 64; ln.eps = 1e-5f; }
-    b.coef_deferred = false;                                  // the consumer about to be launched writes coef (from parts) or finds it written
-    return ln;
 }
 
 // LN(x) of the tower's residual stream into b.y (the unfolded path)
@@ -368,39 +352,49 @@ int tower_layernorm(int dtype, TowerBufs& b, const float* g, const float* be, in
 // The 256x256 kernel addresses its operands with 32-bit byte offsets (set_lnfold in gemm.hip refuses M * lda * 2 >= 2^31): the
 // weight and ONE image's rows must fit -- a larger batch is cut into launches of whole images by fold_rows(), so the decision
 // stays a function of the shape and the result stays bit-identical for every batch size.
-bool fold_shape_ok(int tokens, int n_out, int dim) {
-    return tokens % 256 == 0 && n_out % 256 == 0 && dim % 128 == 0 && dim >= 128 && (unsigned long long)n_out * dim * 2 < (1ull << 31) &&
-           (unsigned long long)tokens * dim * 2 < (1ull << 31);
-}
+bool fold_shape_ok(int tokens, int n_out, int dim) { return pm_lnfold_shape_ok(tokens, n_out, dim, dim, dim); }
 
 // rows one folded launch may take: whole images, below the 32-bit byte-offset limit
 int fold_rows(const TowerBufs& b, int M, int tokens, int dim) {
     long long rows = ((1ll << 31) - 1) / ((long long)dim * 2);
-    if (b.fold_rows_cap > 0 && b.fold_rows_cap < rows) rows = b.fold_rows_cap;
+    if (b.sw->fold_rows_cap > 0 && b.sw->fold_rows_cap < rows) rows = b.sw->fold_rows_cap;
     long long imgs = rows / tokens;
     if (imgs < 1) imgs = 1;
     return (int)std::min<long long>(M, imgs * tokens);
+}
+
+// A folded consumer of LN(x) over the whole tower (c, d: its fold vectors), in launches of whole images: launch(m0, rows, a, ln) runs
+// the GEMM of the rows [m0, m0 + rows), a = those rows of the hi plane.  The (rstd, -rstd * mean) of the rows go to b.coef: where the
+// last residual GEMM left partial row statistics behind, the consumer itself produces them (pmhip_lnfold::parts: in its own prologue
+// for a small launch, by pmhip_ln_coef_parts in front of it otherwise) and nothing is launched for them here; else the pass over
+// the plane.  The ONLY place a fold descriptor is built: a consumer handed a descriptor without `parts` would read coefficients
+// nobody wrote.
+template <typename Launch>
+int folded_consumer(TowerBufs& b, int M, int tokens, int dim, const float* c, const float* d, hipStream_t s, Launch&& launch) {
+    if (b.st.requested()) PM_TRY(pmhip_ln_coef(b.xh, 1e-5f, b.coef, M, dim, s));
+    const int step = fold_rows(b, M, tokens, dim);
+    for (int m0 = 0; m0 < M; m0 += step) {
+        pmhip_lnfold ln{};
+        ln.coef = b.coef + (size_t)m0 * 2; ln.c = c; ln.d = d;
+        if (b.st.parts) { ln.parts = b.parts + (size_t)m0 * (dim / 64) * 2; ln.nparts = dim / 64; ln.eps = 1e-5f; }
+        b.st.consumed();
+        PM_TRY(launch(m0, std::min(step, M - m0), reinterpret_cast<const unsigned char*>(b.xh) + (size_t)m0 * dim * 2, &ln));
+    }
+    return PMHIP_OK;
 }
 
 // LN(x) -> head-split projection: folded when the shape is served, else LayerNorm + GEMM
 int ln_heads(int dtype, TowerBufs& b, const float* g, const float* be, const void* W, const void* Wf, const float* fc, const float* fd,
              int M, int dim, int heads, int dh, int tokens, int Np, int nparts, const int* kinds, void* const* outs, float q_scale,
              hipStream_t s) {
-    if (b.fold && Wf && fold_shape_ok(tokens, nparts * heads * 64, dim)) {
-        PM_TRY(tower_coef(b, M, dim, s));
-        const int step = fold_rows(b, M, tokens, dim);
-        for (int m0 = 0; m0 < M; m0 += step) {
-            const int rows = std::min(step, M - m0);
+    if (b.fold && Wf && fold_shape_ok(tokens, nparts * heads * 64, dim))
+        return folded_consumer(b, M, tokens, dim, fc, fd, s, [&](int m0, int rows, const void* a, const pmhip_lnfold* ln) {
             const size_t b0 = (size_t)(m0 / tokens);
             void* o[3] = {nullptr, nullptr, nullptr};
             for (int i = 0; i < nparts; ++i)
                 o[i] = reinterpret_cast<unsigned char*>(outs[i]) + b0 * heads * (kinds[i] == PMHIP_PART_Q ? tokens : Np) * 64 * dtype_size(dtype);
-            const pmhip_lnfold ln = fold_desc(b, m0, dim, fc, fd);
-            PM_TRY(pmhip_gemm_heads_ln(dtype, reinterpret_cast<const unsigned char*>(b.xh) + (size_t)m0 * dim * 2, dim, Wf, dim, rows, dim, heads,
-                                       tokens, Np, nparts, kinds, o, q_scale, &ln, s));
-        }
-        return PMHIP_OK;
-    }
+            return pmhip_gemm_heads_ln(dtype, a, dim, Wf, dim, rows, dim, heads, tokens, Np, nparts, kinds, o, q_scale, ln, s);
+        });
     PM_TRY(tower_layernorm(dtype, b, g, be, M, dim, s));
     return pmhip_gemm_heads_dh(dtype, b.y, dim, W, dim, M, dim, heads, dh, tokens, Np, nparts, kinds, outs, q_scale, b.split, s);
 }
@@ -443,14 +437,11 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
 
     // x = ffnet(norm(x)) + x
     if (b.fold && L.w12p_f && fold_shape_ok(tokens, 2 * tc.hidden_pad, dim)) {
-        PM_TRY(tower_coef(b, M, dim, s));
-        const int step = fold_rows(b, M, tokens, dim);
-        for (int m0 = 0; m0 < M; m0 += step) {
-            const pmhip_lnfold ln = fold_desc(b, m0, dim, L.w12_c, L.w12_d);
-            PM_TRY(pmhip_gemm_swiglu_ln(dtype, reinterpret_cast<const unsigned char*>(b.xh) + (size_t)m0 * dim * 2, dim, L.w12p_f, L.b12p,
+        PM_TRY(folded_consumer(b, M, tokens, dim, L.w12_c, L.w12_d, s, [&](int m0, int rows, const void* a, const pmhip_lnfold* ln) {
+            return pmhip_gemm_swiglu_ln(dtype, a, dim, L.w12p_f, L.b12p,
                                         reinterpret_cast<unsigned char*>(b.hid) + (size_t)m0 * tc.hidden_pad * dtype_size(dtype), tc.hidden_pad,
-                                        std::min(step, M - m0), tc.hidden_pad, dim, &ln, s));
-        }
+                                        rows, tc.hidden_pad, dim, ln, s);
+        }));
     } else {
         PM_TRY(tower_layernorm(dtype, b, L.ln2_g, L.ln2_b, M, dim, s));
         PM_TRY(pmhip_gemm_swiglu(dtype, b.y, dim, L.w12p, L.b12p, b.hid, tc.hidden_pad, M, tc.hidden_pad, dim, s));
@@ -541,7 +532,7 @@ int vq_encoder(pmhip_vqgan* h, const float* img, int B, TowerBufs& tb, hipStream
                       PMHIP_F32, M, dim, h->patch_k, s));
     if (tb.hilo) PM_TRY(pmhip_layernorm_to_hilo(x0, h->w.pre_g, h->w.pre_b, 1e-5f, tb.xh, tb.xl, M, dim, s));
     else PM_TRY(pmhip_layernorm(x0, h->w.pre_g, h->w.pre_b, 1e-5f, tb.x, PMHIP_F32, M, dim, s));
-    if (tb.center) {
+    if (tb.center()) {
         // prev_quant (vqmodel.py:23) consumes the ABSOLUTE residual stream, so this tower keeps the running shift of its centred
         // hi plane and folds it back in at the end (the decoder and the stage-2 tower end in a LayerNorm, which never sees it)
         WS(h->ws, "enc.shift", (size_t)M * 4, tb.shift);
@@ -792,21 +783,14 @@ int s2_tower(pmhip_s2* h, const void* tp, int B, float* logits, hipStream_t s, b
     PM_TRY(residual_gemm(h->dtype, tb, tp, 64, h->w.tokproj_w, 64, h->w.tokproj_b, pos, M, dim, 64, s));
     for (int l = 0; l < c.tower.depth; ++l)
         PM_TRY(layer_forward(h->dtype, h->layers[l], c.tower, tb, B, c.tokens, true, use_cross ? &h->cross[l] : nullptr, s));
-    if (tb.fold && h->w.logits_wf && fold_shape_ok(c.tokens, c.n_embed, dim)) {
-        PM_TRY(tower_coef(tb, M, dim, s));
-        const int step = fold_rows(tb, M, c.tokens, dim);
-        for (int m0 = 0; m0 < M; m0 += step) {
-            const pmhip_lnfold ln = fold_desc(tb, m0, dim, h->w.logits_c, h->w.logits_d);   // the final norm folded into to_logits
-            const void* a = reinterpret_cast<const unsigned char*>(tb.xh) + (size_t)m0 * dim * 2;
+    if (tb.fold && h->w.logits_wf && fold_shape_ok(c.tokens, c.n_embed, dim))   // the final norm folded into to_logits
+        return folded_consumer(tb, M, c.tokens, dim, h->w.logits_c, h->w.logits_d, s, [&](int m0, int rows, const void* a, const pmhip_lnfold* ln) {
+            float* out = logits + (size_t)m0 * c.n_embed;
             if (block_stats)
-                PM_TRY(pmhip_gemm_softmax_stats(h->dtype, a, dim, h->w.logits_wf, dim, h->w.logits_b, logits + (size_t)m0 * c.n_embed, c.n_embed,
-                                                std::min(step, M - m0), c.n_embed, dim, &ln, block_stats + (size_t)m0 * (c.n_embed / 64) * 2, s));
-            else
-                PM_TRY(pmhip_gemm_ln(h->dtype, a, dim, h->w.logits_wf, dim, h->w.logits_b, logits + (size_t)m0 * c.n_embed, c.n_embed, PMHIP_F32,
-                                     std::min(step, M - m0), c.n_embed, dim, &ln, s));
-        }
-        return PMHIP_OK;
-    }
+                return pmhip_gemm_softmax_stats(h->dtype, a, dim, h->w.logits_wf, dim, h->w.logits_b, out, c.n_embed, rows, c.n_embed, dim, ln,
+                                                block_stats + (size_t)m0 * (c.n_embed / 64) * 2, s);
+            return pmhip_gemm_ln(h->dtype, a, dim, h->w.logits_wf, dim, h->w.logits_b, out, c.n_embed, PMHIP_F32, rows, c.n_embed, dim, ln, s);
+        });
     PM_TRY(tower_layernorm(h->dtype, tb, h->w.norm_g, h->w.norm_b, M, dim, s));
     if (block_stats)
         return pmhip_gemm_softmax_stats(h->dtype, tb.y, dim, h->w.logits_w, dim, h->w.logits_b, logits, c.n_embed, M, c.n_embed, dim, nullptr,
@@ -821,18 +805,25 @@ int s2_tower(pmhip_s2* h, const void* tp, int B, float* logits, hipStream_t s, b
 // The step in two halves, so that a caller can put something between the tower and the sampling (the small-batch loop joins the
 // previous step's decode there).  step_tower: ids2tokens + the tower(s) -> logits.  step_tail: sampling, the optional decode,
 // the optional copies, re-masking.
+// the buffers the two halves share: the logits, and the softmax statistics of their 64-column blocks for the sampling kernel (NULL:
+// it derives them)
+int step_bufs(pmhip_s2* s2, int M, float*& logits, float*& lstats, hipStream_t s) {
+    const auto& c = s2->cfg;
+    WS(s2->ws, "s2.logits", (size_t)M * c.n_embed * 4, logits);
+    lstats = nullptr;
+    if (c.n_embed % 64 == 0 && s2->sw.logits_stats) WS(s2->ws, "s2.lstats", (size_t)M * (c.n_embed / 64) * 8, lstats);
+    return PMHIP_OK;
+}
+
 int step_tower(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s, const float* guidance) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
-    void* tp; float* logits;
+    void* tp; float* logits; float* lstats;
     WS(s2->ws, "s2.tok", (size_t)M * 64 * dtype_size(s2->dtype), tp);
-    WS(s2->ws, "s2.logits", (size_t)M * c.n_embed * 4, logits);
+    PM_TRY(step_bufs(s2, M, logits, lstats, s));
     // ids2tokens: lookup in cat(raw codebook, mask_token) (generate.py:148-157)
     PM_TRY(pmhip_embed_rows(s2->w.tok_table, ids, tp, s2->dtype, 64, M, c.n_embed + 1, c.embed_dim, s));
-    // softmax statistics of the logits' 64-column blocks for the sampling kernel: from the logits GEMM, or -- guided -- from the
-    // combination, which produces the logits that are sampled
-    float* lstats = nullptr;
-    if (c.n_embed % 64 == 0 && s2->sw.logits_stats) WS(s2->ws, "s2.lstats", (size_t)M * (c.n_embed / 64) * 8, lstats);
+    // the statistics come from the logits GEMM, or -- guided -- from the combination, which produces the logits that are sampled
     PM_TRY(s2_tower(s2, tp, B, logits, s, true, guidance ? nullptr : lstats));
     if (guidance) {
         float* uncond;
@@ -857,12 +848,10 @@ int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, int topk, floa
               const PmGenParams* gp) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
-    float* logits; int64_t* pred; float* score;
-    WS(s2->ws, "s2.logits", (size_t)M * c.n_embed * 4, logits);
+    float* logits; float* lstats; int64_t* pred; float* score;
+    PM_TRY(step_bufs(s2, M, logits, lstats, s));             // step_tower filled them
     WS(s2->ws, "s2.pred", (size_t)M * 8, pred);
     WS(s2->ws, "s2.score", (size_t)M * 4, score);
-    float* lstats = nullptr;                                 // step_tower filled them (same condition, same workspace entry)
-    if (c.n_embed % 64 == 0 && s2->sw.logits_stats) WS(s2->ws, "s2.lstats", (size_t)M * (c.n_embed / 64) * 8, lstats);
     PM_TRY(pm_sample_rows(logits, c.n_embed, lstats, ids, (int64_t)c.n_embed, topk, temperature, noise, seed, step,
                           image_base * (uint64_t)c.tokens, pred, ids, score, M, c.n_embed, gp, s));
     if (img_out) PM_TRY(decode_pred(s2, vq, B, img_out, s));

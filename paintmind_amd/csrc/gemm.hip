@@ -249,20 +249,25 @@ __global__ __launch_bounds__(WM * 128) void gemm_nt_kernel(const GemmParams p) {
     wave_epilogue<EPI, OutT, MI, RPRE ? MI * 4 : 1, false, -1, NoHook, STAGES != 4>(p, acc, eraw, m0 + wm * (MI * 16), n0 + wn * 64, lane, rpre);
 }
 
-int env_int(const char* name, int dflt);
+int tiles128(const GemmParams& p) { return ceil_div(p.M, BM) * ceil_div(p.N, BN); }
+
+// The development switches below (common.h pm_dev_knob: development builds only) are process-wide: read once, in the thread-safe
+// initialiser of a function-local static (the first GEMMs of a process are launched from several lane threads at the same time).
+
 // at most one workgroup per CU: nothing overlaps the K loop's DMA latency but the loop itself -> the four-stage form
 // (128 KiB of LDS, one workgroup per CU).  PMHIP_GEMM128_DEEP_MAX_TILES (development): 0 = never.
-bool deep128(int tiles, int K) {
-    static const int deep_max = env_int("PMHIP_GEMM128_DEEP_MAX_TILES", 256);
-    return tiles <= deep_max && K >= 4 * 64;
+bool deep128(const GemmParams& p) {
+    static const int deep_max = pm_dev_knob("PMHIP_GEMM128_DEEP_MAX_TILES", 256);
+    return tiles128(p) <= deep_max && p.K >= 4 * 64;
 }
 
+// deep: the four-stage form (bf16 only; the caller's deep128() answer)
 template <typename T, int EPI, typename OutT, bool FOLD = false>
-int launch(const GemmParams& p, hipStream_t s) {
-    const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
+int launch(const GemmParams& p, bool deep, hipStream_t s) {
+    const int tiles = tiles128(p);
     PmTimer tm(gemm_family(p, EPI), s);
     if constexpr (sizeof(T) == 2) {
-        if (deep128(tiles, p.K)) {
+        if (deep) {
             hipLaunchKernelGGL((gemm_nt_kernel<T, EPI, OutT, FOLD, 4, 4>), dim3(tiles), dim3(512), 0, s, p);
             PM_HIP(hipGetLastError());
             return PMHIP_OK;
@@ -273,20 +278,16 @@ int launch(const GemmParams& p, hipStream_t s) {
     return PMHIP_OK;
 }
 
-// process-wide development switches: read once, in the thread-safe initialiser of a function-local static (the first GEMMs of
-// a process are launched from several lane threads at the same time)
-int env_int(const char* name, int dflt) { return pm_dev_knob(name, dflt); }      // development builds only (common.h)
-
 // A folded GEMM (set_lnfold: M, N multiples of 256) runs on the 128x128 kernel while the 256x256 tiling would leave at least half
 // of the CUs without a workgroup: 4x the workgroups, a quarter of the serial K loop each, bit-identical results.
 // PMHIP_FOLD128_MAX_TILES (development): largest 256x256 tile count that still takes the small kernel (0 = never).
 bool fold_small(const GemmParams& p) {
-    static const int max_tiles = env_int("PMHIP_FOLD128_MAX_TILES", 128);
+    static const int max_tiles = pm_dev_knob("PMHIP_FOLD128_MAX_TILES", 128);
     return (p.M / 256) * (p.N / 256) <= max_tiles;
 }
 
 bool use256(const GemmParams& p, int dtype, int epi, int out_dtype) {
-    static const int g_use256 = env_int("PMHIP_GEMM256", 1);      // PMHIP_GEMM256=0 disables the 256x256 kernel
+    static const int g_use256 = pm_dev_knob("PMHIP_GEMM256", 1);      // PMHIP_GEMM256=0 disables the 256x256 kernel
     return g_use256 && pm_gemm256_supported(p, dtype, epi, out_dtype);
 }
 
@@ -294,7 +295,7 @@ bool use256(const GemmParams& p, int dtype, int epi, int out_dtype) {
 // K = inner): they are HBM-bound (fp32 residual in, fp32 out) and it streams them at ~4.5 TB/s where the 128x128
 // kernel reaches 3.6.  Everything else measured equal or slower than gemm256.hip (tools/gemm_bench.py).
 bool use2b(const GemmParams& p, int dtype, int epi, int out_dtype) {
-    static const int g_use2b = env_int("PMHIP_GEMM2B", 1);   // 0 = never, 1 = where it wins (default), 2 = wherever it is supported (development)
+    static const int g_use2b = pm_dev_knob("PMHIP_GEMM2B", 1);   // 0 = never, 1 = where it wins (default), 2 = wherever it is supported (development)
     if (!g_use2b || !pm_gemm2b_supported(p, dtype, epi, out_dtype)) return false;
     if (g_use2b >= 2) return true;
     return epi == EPI_STD && p.residual && !pm_gemm256_supported(p, dtype, epi, out_dtype);
@@ -309,33 +310,49 @@ int check_common(const GemmParams& p, int dtype) {
     return PMHIP_OK;
 }
 
-}  // namespace
-
-namespace {
-
 // LayerNorm fold (gemm_common.h): checks shared by the three consumer entry points; fills the consumer fields
-int set_lnfold(GemmParams& p, const pmhip_lnfold* ln, int dtype, int epi, int out_dtype, pmhip_stream stream) {
-    if (!ln) return PMHIP_OK;
+int set_lnfold(GemmParams& p, const pmhip_lnfold* ln, int dtype) {
     PM_REQUIRE(ln->coef && ln->c && ln->d, "gemm_ln: null fold pointer");
     PM_REQUIRE(dtype == PMHIP_BF16, "gemm_ln: the LayerNorm fold exists in bf16 mode only");
     PM_REQUIRE(p.K % 128 == 0, "gemm_ln: K=%d must be a multiple of 128", p.K);
     p.ln_c = ln->c; p.ln_d = ln->d; p.ln_coef = ln->coef;
     // any tile count: whether a LayerNorm is folded must not depend on the batch size (see pmhip_lnfold_supported)
-    PM_REQUIRE(p.M % 256 == 0 && p.N % 256 == 0 && (unsigned long long)p.M * p.lda * 2 < (1ull << 31) &&
-               (unsigned long long)p.N * p.ldw * 2 < (1ull << 31),
+    PM_REQUIRE(pm_lnfold_shape_ok(p.M, p.N, p.K, p.lda, p.ldw),
                "gemm_ln: shape M=%d N=%d K=%d is not served by the 256x256 kernel (M, N multiples of 256)", p.M, p.N, p.K);
-    if (ln->parts) {
-        // coef is an OUTPUT too: computed from the producer's partial statistics -- by the GEMM's own prologue where the small
-        // kernel takes the launch (one launch less per LayerNorm: 424 launches of 5 us per 8-step generate of one image), by
-        // pmhip_ln_coef_parts in front of it otherwise.  Same bits either way (common.h, lnp_*).
-        PM_REQUIRE(ln->nparts > 0 && ln->nparts <= 16 && ln->nparts * 64 == p.K, "gemm_ln: nparts=%d does not describe K=%d columns", ln->nparts, p.K);
-        if (fold_small(p) && deep128(ceil_div(p.M, BM) * ceil_div(p.N, BN), p.K)) {
-            p.ln_parts = ln->parts; p.ln_nparts = ln->nparts; p.ln_eps = ln->eps; p.ln_coef_out = const_cast<float*>(ln->coef);
-        } else {
-            PM_TRY(pmhip_ln_coef_parts(ln->parts, ln->nparts, ln->eps, const_cast<float*>(ln->coef), p.M, stream));
-        }
-    }
+    PM_REQUIRE(!ln->parts || (ln->nparts > 0 && ln->nparts <= 16 && ln->nparts * 64 == p.K), "gemm_ln: nparts=%d does not describe K=%d columns",
+               ln->nparts, p.K);
     return PMHIP_OK;
+}
+
+// the 128x128 kernel in bf16: only the plain epilogue has an f32 result
+template <int EPI, bool FOLD>
+int launch_bf16(const GemmParams& p, int out_dtype, bool deep, hipStream_t s) {
+    if constexpr (EPI == EPI_STD)
+        if (out_dtype == PMHIP_F32) return launch<bf16_t, EPI, float, FOLD>(p, deep, s);
+    return launch<bf16_t, EPI, bf16_t, FOLD>(p, deep, s);
+}
+
+// THE kernel selection: every entry point ends here once its GemmParams are filled and checked.  ln: the LayerNorm to fold, or NULL.
+template <int EPI>
+int dispatch(GemmParams& p, int dtype, int out_dtype, const pmhip_lnfold* ln, pmhip_stream stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (ln) {
+        PM_TRY(set_lnfold(p, ln, dtype));
+        const bool small = fold_small(p), deep = small && deep128(p);
+        if (ln->parts) {
+            // coef is an OUTPUT too: computed from the producer's partial statistics -- by the GEMM's own prologue where the small
+            // kernel takes the launch in its four-stage form (one launch less per LayerNorm: 424 launches of 5 us per 8-step generate
+            // of one image), by pmhip_ln_coef_parts in front of it otherwise.  Same bits either way (common.h, lnp_*).
+            if (deep) { p.ln_parts = ln->parts; p.ln_nparts = ln->nparts; p.ln_eps = ln->eps; p.ln_coef_out = const_cast<float*>(ln->coef); }
+            else PM_TRY(pmhip_ln_coef_parts(ln->parts, ln->nparts, ln->eps, const_cast<float*>(ln->coef), p.M, stream));
+        }
+        if (small) return launch_bf16<EPI, true>(p, out_dtype, deep, s);
+        return pm_gemm256_launch(p, EPI, out_dtype, s);
+    }
+    if (use2b(p, dtype, EPI, out_dtype)) return pm_gemm2b_launch(p, EPI, out_dtype, s);
+    if (use256(p, dtype, EPI, out_dtype)) return pm_gemm256_launch(p, EPI, out_dtype, s);
+    if (dtype == PMHIP_F32) return launch<float, EPI, float>(p, false, s);
+    return launch_bf16<EPI, false>(p, out_dtype, deep128(p), s);
 }
 
 int gemm_impl(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias,
@@ -355,15 +372,7 @@ int gemm_impl(int dtype, const void* A, int lda, const void* W, int ldw, const f
     PM_REQUIRE(!residual || out_dtype == PMHIP_F32, "gemm: a residual needs an f32 output (the residual stream is f32)");
     PM_REQUIRE(out_dtype == PMHIP_F32 || out_dtype == dtype, "gemm: out dtype must be f32 or the compute dtype");
     PM_REQUIRE(out_dtype == PMHIP_F32 || ldo % 8 == 0, "gemm: bf16 output needs ldo to be a multiple of 8");
-    PM_TRY(set_lnfold(p, ln, dtype, EPI_STD, out_dtype, stream));
-    hipStream_t s = (hipStream_t)stream;
-    if (ln && fold_small(p)) return out_dtype == PMHIP_F32 ? launch<bf16_t, EPI_STD, float, true>(p, s) : launch<bf16_t, EPI_STD, bf16_t, true>(p, s);
-    if (ln) return pm_gemm256_launch(p, EPI_STD, out_dtype, s);
-    if (use2b(p, dtype, EPI_STD, out_dtype)) return pm_gemm2b_launch(p, EPI_STD, out_dtype, s);
-    if (use256(p, dtype, EPI_STD, out_dtype)) return pm_gemm256_launch(p, EPI_STD, out_dtype, s);
-    if (dtype == PMHIP_F32) return launch<float, EPI_STD, float>(p, s);
-    if (out_dtype == PMHIP_F32) return launch<bf16_t, EPI_STD, float>(p, s);
-    return launch<bf16_t, EPI_STD, bf16_t>(p, s);
+    return dispatch<EPI_STD>(p, dtype, out_dtype, ln, stream);
 }
 
 }  // namespace
@@ -394,10 +403,7 @@ static int gemm_hilo_impl(const void* A, int lda, const void* W, int ldw, const 
     PM_REQUIRE(res_hi && res_lo && out_hi && out_lo, "gemm_hilo: null plane");
     PM_REQUIRE(N % 8 == 0 && ldo % 8 == 0 && ldr % 8 == 0, "gemm_hilo: N=%d, ldo=%d, ldr=%d must be multiples of 8", N, ldo, ldr);
     PM_REQUIRE(!row_stats || N % 64 == 0, "gemm_hilo_stats: N=%d must be a multiple of 64", N);
-    hipStream_t s = (hipStream_t)stream;
-    if (use2b(p, PMHIP_BF16, EPI_STD, PMHIP_BF16)) return pm_gemm2b_launch(p, EPI_STD, PMHIP_BF16, s);
-    if (use256(p, PMHIP_BF16, EPI_STD, PMHIP_BF16)) return pm_gemm256_launch(p, EPI_STD, PMHIP_BF16, s);
-    return launch<bf16_t, EPI_STD, bf16_t>(p, s);
+    return dispatch<EPI_STD>(p, PMHIP_BF16, PMHIP_BF16, nullptr, stream);
 }
 
 extern "C" int pmhip_gemm_hilo(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res_hi,
@@ -438,8 +444,7 @@ extern "C" int pmhip_gemm_softmax_stats(int dtype, const void* A, int lda, const
 }
 
 extern "C" int pmhip_lnfold_supported(int dtype, int epi_kind, int M, int N, int K) {
-    return dtype == PMHIP_BF16 && K % 128 == 0 && K >= 128 && epi_kind >= 0 && epi_kind <= 2 && M % 256 == 0 && N % 256 == 0 &&
-           (unsigned long long)M * K * 2 < (1ull << 31) && (unsigned long long)N * K * 2 < (1ull << 31) ? 1 : 0;
+    return dtype == PMHIP_BF16 && epi_kind >= 0 && epi_kind <= 2 && pm_lnfold_shape_ok(M, N, K, K, K) ? 1 : 0;
 }
 
 static int gemm_swiglu_impl(int dtype, const void* A, int lda, const void* W12p, const float* b12p,
@@ -451,14 +456,7 @@ static int gemm_swiglu_impl(int dtype, const void* A, int lda, const void* W12p,
     PM_TRY(check_common(p, dtype));
     PM_REQUIRE(Hp % 64 == 0, "gemm_swiglu: padded hidden width %d must be a multiple of 64", Hp);
     PM_REQUIRE(b12p && out && ldo % 8 == 0, "gemm_swiglu: bias/out required, ldo multiple of 8");
-    PM_TRY(set_lnfold(p, ln, dtype, EPI_SWIGLU, dtype, stream));
-    hipStream_t s = (hipStream_t)stream;
-    if (ln && fold_small(p)) return launch<bf16_t, EPI_SWIGLU, bf16_t, true>(p, s);
-    if (ln) return pm_gemm256_launch(p, EPI_SWIGLU, dtype, s);
-    if (use2b(p, dtype, EPI_SWIGLU, dtype)) return pm_gemm2b_launch(p, EPI_SWIGLU, dtype, s);
-    if (use256(p, dtype, EPI_SWIGLU, dtype)) return pm_gemm256_launch(p, EPI_SWIGLU, dtype, s);
-    if (dtype == PMHIP_F32) return launch<float, EPI_SWIGLU, float>(p, s);
-    return launch<bf16_t, EPI_SWIGLU, bf16_t>(p, s);
+    return dispatch<EPI_SWIGLU>(p, dtype, dtype, ln, stream);
 }
 
 extern "C" int pmhip_gemm_swiglu(int dtype, const void* A, int lda, const void* W12p, const float* b12p,
@@ -490,14 +488,7 @@ static int gemm_heads_impl(int dtype, const void* A, int lda, const void* W, int
         PM_REQUIRE(p.kinds[i] >= 0 && p.kinds[i] <= 2, "gemm_heads: bad part kind");
     }
     PM_TRY(check_common(p, dtype));
-    PM_TRY(set_lnfold(p, ln, dtype, EPI_HEADS, dtype, stream));
-    hipStream_t s = (hipStream_t)stream;
-    if (ln && fold_small(p)) return launch<bf16_t, EPI_HEADS, bf16_t, true>(p, s);
-    if (ln) return pm_gemm256_launch(p, EPI_HEADS, dtype, s);
-    if (use2b(p, dtype, EPI_HEADS, dtype)) return pm_gemm2b_launch(p, EPI_HEADS, dtype, s);
-    if (use256(p, dtype, EPI_HEADS, dtype)) return pm_gemm256_launch(p, EPI_HEADS, dtype, s);
-    if (dtype == PMHIP_F32) return launch<float, EPI_HEADS, float>(p, s);
-    return launch<bf16_t, EPI_HEADS, bf16_t>(p, s);
+    return dispatch<EPI_HEADS>(p, dtype, dtype, ln, stream);
 }
 
 extern "C" int pmhip_gemm_heads(int dtype, const void* A, int lda, const void* W, int ldw, int M, int K,

@@ -415,8 +415,6 @@ __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict
 
 }  // namespace
 
-static int sample_env_int(const char* name, int dflt) { return pm_dev_knob(name, dflt); }     // development builds only (common.h)
-
 int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id, int topk,
                    float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base, int64_t* pred_out,
                    int64_t* ids_out, float* score_out, int M, int V, const PmGenParams* gp, pmhip_stream stream) {
@@ -429,7 +427,7 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const
     PmTimer tm(FAM_SAMPLE, s);
     // Which kernel runs depends on (V, topk) ONLY -- never on whether statistics were handed in: the two differ in the last bits
     // of the confidence (a different summation order of the softmax denominator).
-    static const int g_tiles = sample_env_int("PMHIP_SAMPLE_TILES", 1);     // 0: the one-read row kernel everywhere (A/B)
+    static const int g_tiles = pm_dev_knob("PMHIP_SAMPLE_TILES", 1);     // 0: the one-read row kernel everywhere (A/B)
     if (g_tiles && topk <= KT_MAX && V % 64 == 0) {
         const float2* st = reinterpret_cast<const float2*>(block_stats);
 #define PM_TILES(NB2)                                                                                                         \
@@ -485,7 +483,7 @@ int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, 
     while (np2 < N) np2 <<= 1;
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_SAMPLE, s);
-    static const int g_reg = sample_env_int("PMHIP_REMASK_REG", 1);      // 0: the all-LDS sort (A/B)
+    static const int g_reg = pm_dev_knob("PMHIP_REMASK_REG", 1);      // 0: the all-LDS sort (A/B)
 #define PM_REMASK(E) hipLaunchKernelGGL(remask_reg_kernel<E>, dim3(B), dim3(THREADS), 0, s, ids, scores, num_mask, mask_id, N, gp, step)
     if (!g_reg) hipLaunchKernelGGL(remask_kernel, dim3(B), dim3(THREADS), (size_t)np2 * 8, s, ids, scores, num_mask, mask_id, N, np2, gp, step);
     else if (np2 <= 256) PM_REMASK(1);
