@@ -295,15 +295,19 @@ __device__ __forceinline__ float2 ln_coef_row(const float2 (&pa)[8], const float
 //   layout: the 16 lanes of a DPP row, lane j holding columns 4j .. 4j+3; every lane of the row returns the block's pair
 // ------------------------------------------------------------------------------------------------
 constexpr float PM_LOG2E = 1.4426950408889634f;
+// e^(x - m) for x <= m.  The difference is taken FIRST: x = m gives exactly 1, and the rounding error of the exponent scales with
+// |x - m|, not with |m|.  (fma(x, log2 e, -rn(m log2 e)) carries the rounding error of m log2 e, up to 2^-19 for |m| in 22..44: a
+// row with one dominant class got p = 1 -+ 1.3e-6 instead of 1 and a confidence score below 0 or above it by that much.)
+__device__ __forceinline__ float softmax_exp_below(float x, float m) {
+    return __builtin_amdgcn_exp2f(__fmul_rn(__fsub_rn(x, m), PM_LOG2E));
+}
 __device__ __forceinline__ float2 softmax_block_stat(float a, float b, float c, float d) {
     float m = fmaxf(fmaxf(a, b), fmaxf(c, d));
     m = fmaxf(m, dpp_mov<0xB1>(m));
     m = fmaxf(m, dpp_mov<0x4E>(m));
     m = fmaxf(m, dpp_mov<0x141>(m));
     m = fmaxf(m, dpp_mov<0x140>(m));
-    const float nm = __fmul_rn(m, -PM_LOG2E);
-    float s = __fadd_rn(__fadd_rn(__builtin_amdgcn_exp2f(__fmaf_rn(a, PM_LOG2E, nm)), __builtin_amdgcn_exp2f(__fmaf_rn(b, PM_LOG2E, nm))),
-                        __fadd_rn(__builtin_amdgcn_exp2f(__fmaf_rn(c, PM_LOG2E, nm)), __builtin_amdgcn_exp2f(__fmaf_rn(d, PM_LOG2E, nm))));
+    float s = __fadd_rn(__fadd_rn(softmax_exp_below(a, m), softmax_exp_below(b, m)), __fadd_rn(softmax_exp_below(c, m), softmax_exp_below(d, m)));
     s = __fadd_rn(s, dpp_mov<0xB1>(s));
     s = __fadd_rn(s, dpp_mov<0x4E>(s));
     s = __fadd_rn(s, dpp_mov<0x141>(s));

@@ -226,10 +226,9 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
 #pragma unroll
     for (int j = 1; j < NB2; ++j) mx = fmaxf(mx, st[j].x);
     mx = wave_max(mx);
-    const float nmx = __fmul_rn(mx, -PM_LOG2E);
     float se = 0.f;
 #pragma unroll
-    for (int j = 0; j < NB2; ++j) se = __fmaf_rn(st[j].y, __builtin_amdgcn_exp2f(__fmaf_rn(st[j].x, PM_LOG2E, nmx)), se);
+    for (int j = 0; j < NB2; ++j) se = __fmaf_rn(st[j].y, softmax_exp_below(st[j].x, mx), se);
     se = wave_sum(se);
 
     // ---- the k blocks with the largest maxima, (max desc, block asc): they hold the k first elements of (value desc, column asc)
@@ -299,7 +298,7 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
         const int64_t pred = win.i;
         const int64_t cur = ids_in[row];
         const bool is_mask = (cur == mask_id);
-        const float p = __fdiv_rn(__builtin_amdgcn_exp2f(__fmaf_rn(raw, PM_LOG2E, nmx)), se);
+        const float p = __fdiv_rn(softmax_exp_below(raw, mx), se);    // raw <= mx and se >= 1 (the maximum's own term): p in [0, 1]
         if (pred_out) pred_out[row] = pred;
         ids_out[row] = is_mask ? pred : cur;
         if (score_out) score_out[row] = is_mask ? (1.0f - p) : -1e5f;

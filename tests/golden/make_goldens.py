@@ -6,6 +6,27 @@ F1  tiny_vqgan.npz / tiny_pipeline.npz / tiny_forward.npz : tiny configs, weight
 F2  full_vqgan.npz / full_vqgan_b512.npz / full_stage2.npz / full_stage2_d768.npz / full_stage2_d1024.npz : full-size configs; weights are NOT stored -- both sides
     re-create them with torch.manual_seed(seed) + create_model (bit-identical init, checked by sha256)
 F3  api.json                            : API-behaviour facts (shapes, dtypes, list lengths, errors)
+F4  full_stage2_chain.npz : the reference's own 8-step decode loop (generate.py:189-194; B = 1, T = 8, topk = 1, all-mask start) at full
+    size on the full_stage2 model with transformer.to_logits.weight *= 16 -- a power of two: exact in fp32 and bf16, both sides still
+    re-create identical weights from the seed (sha256 of the SCALED state dict) and every upstream error is scaled by exactly 16.
+    Unscaled, the seed-0 model's logits are flat (std 0.34, row entropy 8.95 of 9.01 nats) and the re-mask is decided by ties;
+    scaled, they look trained (std 5.5, entropies below) and every confidence score of a step is distinct.  Per step t: ids_in /
+    ids_out / num_mask / argmax of the fp32 reference, and of a float64 copy of the model on the same input ids gap64 (top-2 logit
+    gap), score64 (1 - p[argmax], -1e5 at unmasked positions), lse64, logits64_sub; dlogit = max |logits32 - logits64| and dscore =
+    max over masked positions |score32 - score64| of the reference itself; decidable = gap64 >= W * 2 * dlogit and, at masked
+    positions, |score64 - cut64| >= W * 2 * dscore, with cut64 the num_mask-th largest score64 and W = 8: the reference's own
+    fp32-vs-float64 deviation times a margin for another fp32 summation order.  The generator asserts <= 8 undecidable positions per
+    step and float64 decision == fp32 ids_out at every decidable one.  Its table (torch 2.10, CPU):
+        step  num_mask  mean row entropy  dlogit    dscore    undecidable (W = 8)   (W = 32)
+        0     1004      1.36              2.45e-05  4.65e-06  1                     3
+        1      946      1.56              1.91e-05  3.13e-06  4                     4
+        2      851      1.07              1.84e-05  5.14e-06  1                     3
+        3      724      2.03              1.89e-05  3.56e-06  1                     3
+        4      568      2.26              1.98e-05  3.59e-06  1                     2
+        5      391      0.16              1.98e-05  1.20e-06  3                     4
+        6      199      0.81              1.78e-05  2.37e-06  2                     4
+        7        1      2.82              2.23e-05  3.07e-06  3                     4
+    (the cut-off element itself is always undecidable; the float64 decision equals the fp32 one at ALL 8 x 1024 positions)
 """
 import hashlib
 import json
@@ -281,8 +302,7 @@ def full_vqgan():
     return {"full_vqgan_weights_sha256": sha}
 
 
-def full_stage2():
-    """BASELINE cfg 3: vit-s-vqgan + 12L/d512, context=None, one sample step at B=1, topk=1."""
+def _build_full_stage2_pipe():
     cfg = {k: v for k, v in my_cfg["bench-uncond-12L-d512"].items() if k not in ("text_model", "context_dim")}
     ref_cfg["bench-uncond-12L-d512"] = cfg
     import paintmind.generate as G
@@ -298,6 +318,12 @@ def full_stage2():
         pipe = RefPipeline(ref.Config(cfg), stage1_pretrained=False).eval()
     finally:
         G.CondTransformer = real_ct
+    return pipe
+
+
+def full_stage2():
+    """BASELINE cfg 3: vit-s-vqgan + 12L/d512, context=None, one sample step at B=1, topk=1."""
+    pipe = _build_full_stage2_pipe()
     sha = sd_sha(pipe)
     N, V = 1024, 8192
     ids0 = torch.randint(0, V, (1, N), generator=torch.Generator().manual_seed(200))
@@ -311,6 +337,70 @@ def full_stage2():
          logits_top2gap=(top2[..., 0] - top2[..., 1]).numpy(), ids1=ids1.numpy().astype(np.int16),
          img1_sub=img1[:, :, ::4, ::4].numpy(), weights_sha=np.frombuffer(bytes.fromhex(sha), dtype=np.uint8))
     return {"full_stage2_weights_sha256": sha}
+
+
+CHAIN_LOGIT_SCALE = 16
+CHAIN_W = 8
+
+
+def full_stage2_chain():
+    """The reference's own 8-step decode loop (generate.py:189-194) at full size, B = 1, topk = 1, on the full_stage2 model with
+    to_logits.weight multiplied by 16 (see F4 in the module docstring), plus a float64 copy of the model evaluated on the fp32
+    chain's input ids of every step, which says which positions fp32 rounding can decide."""
+    import copy
+    pipe = _build_full_stage2_pipe()
+    pipe.transformer.to_logits.weight.data *= CHAIN_LOGIT_SCALE
+    sha = sd_sha(pipe)
+    pipe64 = copy.deepcopy(pipe).double()
+    N, V, T, W = pipe.num_tokens, pipe.mask_token_id, 8, CHAIN_W
+    assert (N, V) == (1024, 8192)
+    out = {}
+    ids = torch.full((1, N), V, dtype=torch.long)
+    table = []
+    for t in range(T):
+        masked_r = ref_generate.mask_schedule((t + 1) / T)
+        cur_temp = 1.0 * (1 - t / T)
+        num_mask = max(int((masked_r * N).item()), 1)               # generate.py:175
+        ids_in = ids
+        is_mask = ids_in == V
+        ids, img = pipe.sample(ids_in, mask_ratio=masked_r, text=None, topk=1, temperature=cur_temp)
+        assert int((ids == V).sum()) == num_mask
+        logits32 = pipe.tokens2logits(pipe.ids2tokens(ids_in), None)
+        logits64 = pipe64.tokens2logits(pipe64.ids2tokens(ids_in), None)
+        assert logits32.dtype == torch.float32 and logits64.dtype == torch.float64
+        arg32, arg64 = logits32.argmax(-1), logits64.argmax(-1)
+        score32 = 1 - logits32.softmax(-1).gather(2, arg32[..., None])[..., 0]
+        score64 = (1 - logits64.softmax(-1).gather(2, arg64[..., None])[..., 0]).masked_fill(~is_mask, -1e5)   # generate.py:173
+        top2 = torch.topk(logits64, 2, dim=-1).values
+        gap64 = top2[..., 0] - top2[..., 1]
+        dlogit = (logits32.double() - logits64).abs().max().item()
+        dscore = (score32.double() - score64)[is_mask].abs().max().item()
+        top = score64.topk(num_mask, dim=-1)
+        cut64 = top.values[0, -1].item()
+        decidable = (gap64 >= W * 2 * dlogit) & (~is_mask | ((score64 - cut64).abs() >= W * 2 * dscore))
+        # the float64 decision: arg-max merge + topk(score64, num_mask)
+        ids64 = torch.where(is_mask, arg64, ids_in).scatter(1, top.indices, V)
+        und = int((~decidable).sum())
+        bad = int(((ids64 != ids) & decidable).sum())
+        ent = -(logits32.log_softmax(-1) * logits32.softmax(-1)).sum(-1).mean().item()
+        table.append(f"step {t}: num_mask {num_mask:4d}  entropy {ent:5.2f}  dlogit {dlogit:.2e}  dscore {dscore:.2e}  "
+                     f"undecidable {und}  fp64!=fp32 at decidable {bad}  fp64!=fp32 anywhere {int((ids64 != ids).sum())}")
+        print(table[-1], flush=True)
+        assert und <= 8, (t, und)
+        assert bad == 0, (t, bad)
+        out[f"ids_in{t}"], out[f"ids_out{t}"] = ids_in.numpy().astype(np.int16), ids.numpy().astype(np.int16)
+        out[f"num_mask{t}"] = np.int64(num_mask)
+        out[f"argmax{t}"] = arg32.numpy().astype(np.int16)
+        out[f"gap64{t}"], out[f"score64{t}"], out[f"lse64{t}"] = gap64.numpy(), score64.numpy(), torch.logsumexp(logits64, -1).numpy()
+        # float64 values kept as float32: eight float64 slices alone are 1 MiB, the most a committed file may have.  The rounding
+        # (<= 2e-6 at |logit| < 32) is far inside the 16 x TOL the tests compare at, but it is about a tenth of dlogit: the
+        # "deviation / dlogit" ratio the GPU test prints carries that much of it
+        out[f"logits64_sub{t}"] = logits64[:, ::8, ::64].numpy().astype(np.float32)
+        out[f"dlogit{t}"], out[f"dscore{t}"] = np.float64(dlogit), np.float64(dscore)
+        out[f"decidable{t}"] = decidable.numpy()
+    save("full_stage2_chain.npz", **out, img_last_sub=img[:, :, ::4, ::4].numpy(), logit_scale=np.int64(CHAIN_LOGIT_SCALE),
+         window_margin=np.int64(W), weights_sha=np.frombuffer(bytes.fromhex(sha), dtype=np.uint8))
+    return {"full_stage2_chain_weights_sha256": sha}
 
 
 def full_vqgan_b512():
@@ -389,7 +479,7 @@ def full_stage2_text(key, out_name, img_stride):
 
 if __name__ == "__main__":
     which = sys.argv[1:] or ["tiny_vqgan", "tiny_pipeline", "tiny_forward", "full_vqgan", "full_stage2", "full_stage2_d768",
-                             "full_stage2_d1024", "full_vqgan_b512"]
+                             "full_stage2_d1024", "full_vqgan_b512", "full_stage2_chain"]
     api_path = os.path.join(HERE, "api.json")
     api = json.load(open(api_path)) if os.path.exists(api_path) else {}
     api["torch_version"] = torch.__version__
@@ -405,6 +495,8 @@ if __name__ == "__main__":
         api.update(full_stage2())
     if "full_vqgan_b512" in which:
         api.update(full_vqgan_b512())
+    if "full_stage2_chain" in which:
+        api.update(full_stage2_chain())
     if "full_stage2_d768" in which:
         api.update(full_stage2_text("bench-text-24L-d768", "full_stage2_d768.npz", 4))
     if "full_stage2_d1024" in which:

@@ -384,3 +384,100 @@ def test_small_batches_run_small_batch_kernels_and_give_the_large_batch_bits(pip
                 assert torch.equal(imgs, imgs40[:, :nb]), (nb, rep)
     finally:
         pipe.set_compute_dtype(torch.float32)
+
+
+# ---- bf16 (the timed mode) on trained-like logits: the eight states of tests/golden/full_stage2_chain.npz ---------------------
+# MEASURED on MI355X, 2026-10-17, this change on top of bab015c (profiles/bf16_chain_steps.txt), bf16 against the fp32-verify path of
+# the same build: the eight fixture states plus the same eight steps with the unmasked positions refilled by torch.manual_seed(1..4)
+# random tokens, five fillings in all; mean / sample sigma over the five:
+#   top-1 agreement over 8 x 1024 rows        0.98936 / 0.0038   (fixture states 0.98889)
+#   mean |score_bf16 - score_fp32|            0.004354 / 0.00080 (0.003581)     non-flipped masked rows
+#   max  |score_bf16 - score_fp32|            0.02343 / 0.00723  (0.03215)
+#   re-masked-set overlap, steps 0..6         0.99801 / 0, 0.99493 / 0.00293, 0.99224 / 0.00213, 0.98757 / 0.00618, 0.99296 / 0.00413,
+#                                             0.98926 / 0.00554, 0.98593 / 0.00550
+#   step 7 (num_mask = 1: a set of ONE, overlap is 0 or 1)   0.8 / 0.447 -- 0 on the fixture state: no bar can be set from this
+# bf16 logits max error per step 0.18-0.23 (16 x the 0.011 of the unscaled model); no bf16 score was exactly 0 or 1 at any step and
+# step 5 (entropy 0.16) is no outlier: nothing collapses on low-entropy rows.  Bars: two sigma on the safe side of the mean.
+BF16_CHAIN_TOP1_AGREE = 0.9817
+BF16_CHAIN_SCORE_MEAN_DEV = 0.00596
+BF16_CHAIN_SCORE_MAX_DEV = 0.0379
+BF16_CHAIN_REMASK_OVERLAP = [0.9980, 0.9890, 0.9879, 0.9752, 0.9847, 0.9781, 0.9749, 0.0]
+
+
+@pytest.fixture(scope="module")
+def chain_pipe():
+    from gpu_common import scaled_chain_pipeline
+    return scaled_chain_pipeline()
+
+
+def _bf16_chain_step(pipe, ids_in, temp, nm):
+    """one decode step on `ids_in` [1, N] in fp32-verify and in bf16 (folded final LayerNorm, the logits GEMM's block statistics,
+    sample_tiles_kernel: the path bench.py times), topk = 1 -> per mode (logits, ids, pred, score) as numpy"""
+    out = {}
+    try:
+        for dtype in (torch.float32, torch.bfloat16):
+            pipe.set_compute_dtype(dtype)
+            eng = pipe.engine()
+            assert eng.dtype == dtype
+            logits = pipe.tokens2logits(pipe.ids2tokens(ids_in), None)
+            ids1, _, pred, score = eng.sample(pipe.vqgan.engine(), ids_in.clone(), None, 1, temp, nm, want_img=False, want_aux=True)
+            out[dtype] = (logits[0], n(ids1)[0], n(pred)[0], n(score)[0])
+    finally:
+        pipe.set_compute_dtype(torch.float32)
+    return out[torch.float32], out[torch.bfloat16]
+
+
+def _bf16_chain_stats(pipe, d, fill_seed=None, verbose=True):
+    """The eight chain states through both modes, with the hard assertions that need no measurement, -> the measured figures:
+    (top-1 agreement over the 8 x 1024 rows, mean and max |score_bf16 - score_fp32| over non-flipped masked rows, [re-masked-set overlap
+    per step]).  fill_seed: replace the tokens at the unmasked positions by torch.manual_seed(fill_seed)-seeded random ones (the
+    spread the bars are set from); None: the fixture's states."""
+    V, T = pipe.mask_token_id, 8
+    flips_all, rows_all, devs, overlaps = 0, 0, [], []
+    for step in range(T):
+        ids_np = d[f"ids_in{step}"].astype(np.int64)
+        nm = int(d[f"num_mask{step}"])
+        if fill_seed is not None:
+            torch.manual_seed(fill_seed)
+            fill = torch.randint(0, V, ids_np.shape).numpy()
+            ids_np = np.where(ids_np == V, V, fill)
+        (l32, ids32, pred32, s32), (l16, ids16, pred16, s16) = _bf16_chain_step(pipe, t(ids_np), 1.0 * (1 - step / T), nm)
+        masked = ids_np[0] == V
+        err = float((l16 - l32).abs().max())
+        top2 = torch.topk(l32, 2, dim=-1).values
+        gap = n(top2[:, 0] - top2[:, 1])
+        flips = pred16 != pred32
+        # a flip needs the two candidates closer than the two errors combined, and at most the rows inside that noise may flip
+        assert np.all(gap[flips] < 2 * err), (step, gap[flips], err)
+        assert int(flips.sum()) <= int((gap < 2 * err).sum())
+        assert (ids32 == V).sum() == (ids16 == V).sum() == nm
+        assert np.isfinite(s16[masked]).all() and (s16[masked] >= 0).all() and (s16[masked] <= 1).all(), step
+        assert np.array_equal(s16[~masked], np.full((~masked).sum(), -1e5, np.float32))
+        ok = masked & ~flips
+        dev_ = np.abs(s16.astype(np.float64) - s32)[ok]
+        overlap = float(((ids16 == V) & (ids32 == V)).sum()) / nm
+        sat = int(((s16[masked] == 0) | (s16[masked] == 1)).sum()), int(((s32[masked] == 0) | (s32[masked] == 1)).sum())
+        if verbose:
+            print(f"bf16 chain step {step}: logits max err {err:.4f}, {int(flips.sum())} flips ({int((gap < 2 * err).sum())} rows with gap < 2 err), "
+                  f"score dev mean {dev_.mean():.2e} max {dev_.max():.2e}, re-mask overlap {overlap:.4f} of {nm}, "
+                  f"scores exactly 0 or 1: bf16 {sat[0]} fp32 {sat[1]} of {int(masked.sum())}")
+        flips_all += int(flips.sum())
+        rows_all += flips.size
+        devs.append(dev_)
+        overlaps.append(overlap)
+    devs = np.concatenate(devs)
+    return 1.0 - flips_all / rows_all, float(devs.mean()), float(devs.max()), overlaps
+
+
+def test_bf16_decode_steps_on_trained_like_logits(chain_pipe):
+    """bf16 mode against fp32-verify of the same build on low-entropy, trained-like logits (row entropies 0.2-2.8 nats; the other
+    bf16 tests run the flat logits of the random-weight model, std 0.3): the eight states of the reference's own decode chain.
+    Hard: a prediction differs only where the fp32 top-2 gap is inside twice the step's measured logits error; both modes leave
+    exactly num_mask mask ids; every bf16 score of a masked row is finite and in [0, 1].  Measured bars: see the constants."""
+    pipe, d = chain_pipe
+    agree, dev_mean, dev_max, overlaps = _bf16_chain_stats(pipe, d)
+    print(f"bf16 chain, 8 x 1024 rows: top-1 agreement {agree:.5f}, score |dev| mean {dev_mean:.3e} max {dev_max:.3e}, "
+          f"re-mask overlap per step {[round(o, 4) for o in overlaps]}")
+    assert agree >= BF16_CHAIN_TOP1_AGREE, agree
+    assert dev_mean <= BF16_CHAIN_SCORE_MEAN_DEV and dev_max <= BF16_CHAIN_SCORE_MAX_DEV, (dev_mean, dev_max)
+    assert all(o >= bar for o, bar in zip(overlaps, BF16_CHAIN_REMASK_OVERLAP)), overlaps

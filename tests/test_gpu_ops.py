@@ -724,6 +724,105 @@ def test_logits_gemm_leaves_the_block_statistics_of_what_it_stores(M, fold):
         assert torch.equal(a_, b_)
 
 
+def _low_entropy_rows(V, M=96):
+    """96 rows of what a trained MaskGIT emits (and the edges the block-statistics softmax has there), fp32:
+    rows 0-7    one class 30 above every other of the row: sum exp(x - max) = 1 + < 8191 e^-30 = 1 + < 8e-10, which rounds to 1.0 in
+                fp32 whatever the summation order, so p = 1.0 and the score is EXACTLY 0 (in the numpy oracle as well);
+    rows 8-15   every 64-column block but two sits 110-130 below the row maximum: exp of anything more than 103.98 below it is 0 in
+                fp32, such a block's sum of exp must enter the normaliser as 0;
+    row 16      the maximum is the last column of the last block;   row 17  the two largest values are equal, in different blocks;
+    the rest    Gaussian rows of std 5.5 (row entropies 0.1-3 nats)."""
+    rng = np.random.default_rng(V + 7)
+    x = (rng.standard_normal((M, V)) * 5.5).astype(np.float32)
+    nblk = V // 64
+    for r in range(8):
+        c = int(rng.integers(0, V))
+        if r == 0:
+            c = V - 1
+        x[r, c] = -np.inf
+        x[r, c] = np.float32(x[r].max() + 30.0)
+    for r in range(8, 16):
+        keep = rng.choice(nblk, 2, replace=False)
+        low = np.ones(nblk, bool)
+        low[keep] = False
+        blocks = x[r].reshape(nblk, 64)
+        top = blocks[keep].max()
+        blocks[low] = (top - 120.0 + np.clip(blocks[low] - blocks[low].mean(), -10.0, 10.0)).astype(np.float32)
+        assert blocks[low].max() < top - 104.0
+    x[16, V - 1] = x[16].max() + np.float32(1.5)
+    a, b = 5, nblk - 3
+    x[17, a * 64 + 9] = x[17, b * 64 + 40] = x[17].max() + np.float32(0.75)
+    return x
+
+
+@pytest.mark.parametrize("V", [1024, 8192])
+@pytest.mark.parametrize("topk", [1, 5, 8])
+@pytest.mark.parametrize("temp", [1.0, 0.125])
+def test_sample_rows_on_low_entropy_rows(V, topk, temp):
+    """The sampling kernels on peaky, trained-like rows (_low_entropy_rows): the other sampler tests draw Gaussian logits of std 2-3,
+    where no probability is near 1 and no block's exp underflows.  Dense call, block statistics handed in and Philox noise agree bit
+    for bit; predictions and merged ids are the oracle's; scores within the file's 2e-6 of the oracle AND of a float64 softmax
+    computed here, and exactly 0 where p rounds to 1.0.  Then the re-mask on those scores (equal scores of 0 included).
+    (Before softmax_exp_below took the difference first, a block's sum of exp was off by up to 5.3e-6 relative on these rows and the
+    score of a p = 1 row by up to 2.6e-6, either sign; observed now: max |score - float64| 1.8e-7.)"""
+    M = 96
+    logits = _low_entropy_rows(V, M)
+    ids = RNG.integers(0, V, M).astype(np.int64)
+    ids[np.arange(M) % 5 < 3] = V
+    ids[:18] = V                                                  # every special row is a masked one: its score is looked at
+    masked = ids == V
+    noise = RNG.random((M, V)).astype(np.float32)
+    x = t(logits)
+    same, stats = ops.guidance_combine(x, x, 1.0, with_stats=True)
+    assert torch.equal(same, x)
+    blocks = logits.reshape(M, V // 64, 64).astype(np.float64)
+    assert np.array_equal(n(stats[..., 0]), blocks.max(-1))
+    assert np.isfinite(n(stats[..., 1])).all()
+    assert np.max(np.abs(n(stats[..., 1]) / np.exp(blocks - blocks.max(-1, keepdims=True)).sum(-1) - 1)) < 2e-6
+    dense = ops.sample_rows(x, t(ids), V, topk, temp, noise=t(noise))
+    sparse = ops.sample_rows(x, t(ids), V, topk, temp, noise=t(noise), block_stats=stats)
+    for a, b in zip(dense, sparse):
+        assert torch.equal(a, b)
+    l64 = logits.astype(np.float64)
+    p64 = np.exp(l64 - l64.max(-1, keepdims=True))
+    p64 /= p64.sum(-1, keepdims=True)
+
+    def check(got, noise_np):
+        pred_r, merged_r, score_r = O.sample_rows(logits, ids, V, topk, temp, noise_np)
+        pred, merged, score = n(got[0]), n(got[1]), n(got[2])
+        assert np.array_equal(pred, pred_r) and np.array_equal(merged, merged_r)
+        assert np.isfinite(score).all() and np.array_equal(score[~masked], np.full((~masked).sum(), -1e5, np.float32))
+        s64 = 1.0 - p64[np.arange(M), pred_r]
+        e_o, e_64 = np.abs(score - score_r)[masked].max(), np.abs(score - s64)[masked].max()
+        print(f"V={V} topk={topk} temp={temp}: score max |gpu - oracle| {e_o:.2e}, max |gpu - float64| {e_64:.2e}, "
+              f"range [{score[masked].min():.3g}, {score[masked].max():.3g}]")
+        assert e_o < 2e-6 and e_64 < 2e-6
+        assert (score[masked] >= 0).all() and (score[masked] <= 1).all()
+        # p rounds to 1.0: whichever candidate the noise picks in rows 0-7, the arg-max itself has score exactly 0
+        top = pred_r[:8] == logits[:8].argmax(-1)
+        assert np.array_equal(score_r[:8][top], np.zeros(top.sum(), np.float32))
+        assert np.array_equal(score[:8][top], np.zeros(top.sum(), np.float32))
+        if topk == 1:
+            assert top.all() and pred[16] == V - 1 and pred[17] == 5 * 64 + 9      # equal values: the lower column
+        return score
+
+    score = check(dense, noise)
+    seed, step, base = 0x0FEDCBA987654321, 5, 4096
+    d2 = ops.sample_rows(x, t(ids), V, topk, temp, seed=seed, step=step, row_base=base)
+    s2 = ops.sample_rows(x, t(ids), V, topk, temp, seed=seed, step=step, row_base=base, block_stats=stats)
+    for a, b in zip(d2, s2):
+        assert torch.equal(a, b)
+    cols = np.broadcast_to(np.arange(V), (M, V))
+    rows = np.broadcast_to((base + np.arange(M))[:, None], (M, V))
+    check(d2, O.philox_uniform(seed, step, rows, cols))
+    # the re-mask on these scores, as one image of 96 positions: 1, some, and every masked position
+    for m in (1, 37, int(masked.sum())):
+        assert m <= masked.sum()
+        out = n(ops.remask(dense[1].reshape(1, M).clone(), dense[2].reshape(1, M), m, V))
+        assert np.array_equal(out, O.remask(n(dense[1]).reshape(1, M), score.reshape(1, M), m, V))
+        assert (out == V).sum() == m and np.array_equal(out[0][~masked], ids[~masked])
+
+
 def test_sample_rows_philox_matches_numpy_philox_and_is_shard_invariant():
     M, V, topk = 64, 8192, 5
     logits = rnd(M, V, scale=2.0)

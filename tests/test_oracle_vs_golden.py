@@ -5,7 +5,7 @@ import pytest
 
 from oracle import paintmind_oracle as O
 from oracle import vq_ref
-from util import load_golden, maxabs, vq_cfg, s2_cfg
+from util import load_golden, maxabs, state_dict_sha, vq_cfg, s2_cfg
 
 
 @pytest.fixture(scope="module")
@@ -167,7 +167,6 @@ def test_north_star_size_models_weights_and_oracle_against_the_reference(key, na
     (24L/d1024, context_proj 768 -> 1024), against the REFERENCE's own output at that size (make_goldens.py full_stage2_text):
     the seeded init reproduces the reference's weights bit for bit (sha256), and the torch port of the oracle -- what the GPU
     tests of these configs compare with at larger batches -- reproduces its logits."""
-    import hashlib
     import torch
     import paintmind_amd as pm
     from paintmind_amd.generate import Pipeline
@@ -176,12 +175,8 @@ def test_north_star_size_models_weights_and_oracle_against_the_reference(key, na
     _, d = load_golden(name + ".npz")
     torch.manual_seed(0)
     pipe = Pipeline(pm.Config(pm.ver2cfg[key]), stage1_pretrained=False).eval()
-    h = hashlib.sha256()
     sd = {k: v for k, v in pipe.state_dict().items() if not k.startswith("text_model")}
-    for k, v in sd.items():
-        h.update(k.encode())
-        h.update(v.numpy().tobytes())
-    assert h.hexdigest() == api_facts()[name + "_weights_sha256"] == bytes(d["weights_sha"]).hex()
+    assert state_dict_sha(sd) == api_facts()[name + "_weights_sha256"] == bytes(d["weights_sha"]).hex()
     ids0 = torch.from_numpy(d["ids0"].astype(np.int64))
     table = torch.cat([sd["vqgan.quantize.embedding.weight"], sd["mask_token"]])
     with torch.no_grad():
@@ -195,7 +190,6 @@ def test_north_star_size_models_weights_and_oracle_against_the_reference(key, na
 def test_vit_b_512_weights_and_oracle_against_the_reference():
     """cfg 5's assumed stage 1 (vit-b-vqgan-512): seeded weights sha-identical to the reference's, and the torch port of the oracle
     reproduces the reference's tokens and reconstruction (tests/golden/full_vqgan_b512.npz)."""
-    import hashlib
     import torch
     import paintmind_amd as pm
     from oracle import torch_port as TP
@@ -203,11 +197,7 @@ def test_vit_b_512_weights_and_oracle_against_the_reference():
     _, d = load_golden("full_vqgan_b512.npz")
     torch.manual_seed(0)
     m = pm.create_model(arch="vqgan", version="vit-b-vqgan-512", pretrained=False).eval()
-    h = hashlib.sha256()
-    for k, v in m.state_dict().items():
-        h.update(k.encode())
-        h.update(v.numpy().tobytes())
-    assert h.hexdigest() == api_facts()["full_vqgan_b512_weights_sha256"] == bytes(d["weights_sha"]).hex()
+    assert state_dict_sha(m.state_dict()) == api_facts()["full_vqgan_b512_weights_sha256"] == bytes(d["weights_sha"]).hex()
     sd = dict(m.state_dict())
     x = torch.rand(1, 3, 512, 512, generator=torch.Generator().manual_seed(101)) * 2 - 1
     with torch.no_grad():
@@ -247,3 +237,44 @@ def test_pipeline_forward_loss_golden(tp, tf):
         for j in range(2):
             loss, _ = O.pipeline_forward(tf["img"], ctx, float(tf[f"fw_{tag}{j}_ratio"]), tf[f"fw_{tag}{j}_noise"], p, cfg, s2)
             assert abs(float(loss) - float(tf[f"fw_{tag}{j}_loss"])) < 2e-5
+
+
+# ---- the reference's own 8-step decode chain at full size, on trained-like logits (make_goldens.py full_stage2_chain) ----
+def test_full_size_decode_chain():
+    """The 12L/d512 model of full_stage2.npz with to_logits.weight times 16 (exact in fp32: logits of std 5.5, row entropies 0.2-2.8
+    nats, every confidence score distinct), the reference's 8-step loop from the all-mask start (generate.py:189-194, B = 1, topk = 1).
+    The seeded init times 16 reproduces the reference's scaled weights bit for bit (sha256: "same weights on both sides", pinned
+    where no GPU is needed); then the numpy oracle, teacher-forced on the reference's input ids of step 0 (all mask id), step 5 (the
+    lowest-entropy step) and step 7 (num_mask = max(int(r * 1024), 1) = 1), must take the reference's decision at every position
+    the fixture calls decidable: top-2 logit gap and distance from the re-mask cut-off both at least 8 x 2 x the reference's own
+    fp32-vs-fp64 deviation.  At most 8 of the 1024 positions of a step are not (asserted by the generator)."""
+    import torch
+    import paintmind_amd as pm
+    from paintmind_amd.generate import Pipeline
+    from util import api_facts
+    _, d = load_golden("full_stage2_chain.npz")
+    key = "bench-uncond-12L-d512"
+    torch.manual_seed(0)
+    pipe = Pipeline(pm.Config(pm.ver2cfg[key]), stage1_pretrained=False).eval()
+    pipe.transformer.to_logits.weight.data *= int(d["logit_scale"])
+    sd = {k: v for k, v in pipe.state_dict().items() if not k.startswith("text_model")}
+    assert state_dict_sha(sd) == api_facts()["full_stage2_chain_weights_sha256"] == bytes(d["weights_sha"]).hex()
+    assert [int(d[f"num_mask{t}"]) for t in range(8)] == api_facts()["mask_counts_T8_N1024"]
+    p = {k: v.numpy() for k, v in sd.items()}
+    vcfg, scfg = vq_cfg("vit-s-vqgan"), s2_cfg(key)
+    V = vcfg["n_embed"]
+    noise = np.full((1, 1024, V), 0.5, np.float32)
+    for t in (0, 5, 7):
+        ids_in, want = d[f"ids_in{t}"].astype(np.int64), d[f"ids_out{t}"].astype(np.int64)
+        dec = d[f"decidable{t}"]
+        assert dec.shape == (1, 1024) and (~dec).sum() <= 8
+        if t == 0:
+            assert (ids_in == V).all()
+        ids, _, aux = O.sample_step(ids_in, O.mask_schedule((t + 1) / 8), None, 1, 1.0 * (1 - t / 8), noise, p, vcfg, scfg, decode=False)
+        mism = ids != want
+        flips = aux["pred"] != d[f"argmax{t}"]
+        print(f"decode chain step {t}: oracle vs reference: {int(mism.sum())} id mismatches ({int((mism & dec).sum())} at decidable "
+              f"positions), {int(flips.sum())} arg-max flips, {int((~dec).sum())} undecidable positions")
+        assert aux["num_mask"] == int(d[f"num_mask{t}"]) == int((ids == V).sum()) == int((want == V).sum())
+        assert not (mism & dec).any(), np.nonzero(mism & dec)
+        assert not (flips & dec).any(), np.nonzero(flips & dec)

@@ -40,3 +40,16 @@ def maxabs(a, b):
 def to_torch_sd(params):
     import torch
     return {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in params.items()}
+
+
+def state_dict_sha(sd, skip=("text_model",)):
+    """sha256 over (key, raw tensor bytes) of a state dict in its own order, text tower left out: the definition of "same weights
+    on both sides" that tests/golden/make_goldens.py (sd_sha) records for the full-size fixtures"""
+    import hashlib
+    h = hashlib.sha256()
+    for k, v in sd.items():
+        if k.startswith(skip):
+            continue
+        h.update(k.encode())
+        h.update(v.detach().cpu().numpy().tobytes())
+    return h.hexdigest()
