@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PMHIP_ABI_VERSION 10
+#define PMHIP_ABI_VERSION 11
 
 enum { PMHIP_OK = 0, PMHIP_EINVAL = 1, PMHIP_EHIP = 2, PMHIP_ENOMEM = 3, PMHIP_ESTATE = 4 };
 enum { PMHIP_F32 = 0, PMHIP_BF16 = 1 };
@@ -283,6 +283,30 @@ int pmhip_sample_rows_stats(const float* logits, int ldl, const float* block_sta
 int pmhip_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N,
                  pmhip_stream stream);
 
+/* ABI 11: per-IMAGE decode state.  One record per image of a batch, in DEVICE memory for the two operators below (the model-level
+ * entry pmhip_pipeline_step_slots takes host records and stages them).  Every value the scalar entries above take once per call
+ * -- seed, step, temperature, top-k, mask count, global image index -- is taken per image, so requests that differ share a batch. */
+typedef struct pmhip_slot {      /* one per image of the batch, 32 bytes */
+    uint64_t seed;               /* Philox key */
+    uint64_t image_index;        /* global image index: the row counter is image_index * tokens + position */
+    float    temperature;        /* this step's temperature, as the caller derived it */
+    int32_t  topk;               /* 1..8 */
+    int32_t  num_mask;           /* this step's num_token_masked, >= 1 */
+    uint32_t step;               /* Philox counter word; bit 31 set = slot idle */
+} pmhip_slot;
+
+/* pmhip_sample_rows / pmhip_sample_rows_stats with the scalars of row r taken from slots[r / tokens] (M = B * tokens rows, slots a
+ * DEVICE array [B]): the same kernel body, arithmetic and order -- image b's rows equal, bit for bit, the scalar entry called on
+ * that image alone with its slot's values and row_base = image_index * tokens.  Philox noise only.  An idle slot (bit 31 of step)
+ * draws nothing: ids_out = ids_in, pred = ids_in, score = -1e5.  Served: the block-statistics kernel only, i.e. V % 64 == 0 and
+ * every topk in 1..8 (what every decode-loop launch uses); block_stats may be NULL (derived from the stored rows). */
+int pmhip_sample_rows_slots(const float* logits, int ldl, const float* block_stats /* or NULL */,
+                            const int64_t* ids_in, int64_t mask_id, const pmhip_slot* slots, int tokens,
+                            int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream);
+/* pmhip_remask with num_mask = slots[b].num_mask; the row of an idle slot is left untouched.  Same keys, order and threshold. */
+int pmhip_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id,
+                       int B, int N, pmhip_stream stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Model level.  Weight tables are filled by the host packer (paintmind_amd/engine.py) from the
  * reference's state_dict layout.
@@ -441,6 +465,24 @@ int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, 
                                    uint64_t image_base, float* imgs_out, int use_graph,
                                    pmhip_stream stream, float* imgs_host, size_t host_stride,
                                    pmhip_stream copy_stream, float guidance_scale);
+
+/* ABI 11: one MaskGIT step (pmhip_pipeline_sample without the image) in which every image carries its own decode state:
+ * slots_host[B] (HOST records, validated here: an active slot needs 1 <= topk <= 8 and num_mask >= 1) replace topk, temperature,
+ * num_mask, seed, step and image_base.  The records travel through a pinned ring to device memory, from where the sampling and
+ * re-masking kernels read them; the tower never mixes rows, so image b's pred / score / ids equal, bit for bit, those of the
+ * scalar step run at the same B with slot b's values (idle slots still run through the tower; their ids stay as they are).
+ * flags: PMHIP_SLOTS_KEEP_CONTEXT -- `context` is ignored and the cross K/V the previous slots call on this handle prepared are
+ * reused (PMHIP_ESTATE when nothing was prepared, when another entry point prepared a context since, or when B or L differ).
+ * PMHIP_SLOTS_GRAPH -- the step (tower + sampling + re-masking, a linear chain) is captured once per (B, L or no context) and
+ * replayed: first call eager, second captures.  Every per-image value is read from device memory, so one graph serves every
+ * schedule and every mix of requests.  The request is ignored exactly when PMHIP_GENERATE_GRAPH is (timing on,
+ * AMD_DIRECT_DISPATCH=0): eager, same bits.  Context preparation always runs outside the graph.  n_embed % 64 == 0.
+ * pred_out [B,N] / score_out [B,N] may be NULL. */
+#define PMHIP_SLOTS_GRAPH        1   /* replay a captured step */
+#define PMHIP_SLOTS_KEEP_CONTEXT 2   /* reuse the cross K/V the previous slots call on this handle prepared */
+int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                              const pmhip_slot* slots_host, int flags,
+                              int64_t* pred_out, float* score_out, pmhip_stream stream);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

@@ -10,9 +10,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpaintmind_hip.so")
 
 PMHIP_OK = 0
+PMHIP_EINVAL, PMHIP_EHIP, PMHIP_ENOMEM, PMHIP_ESTATE = 1, 2, 3, 4
 F32, BF16 = 0, 1
 PART_Q, PART_K, PART_V = 0, 1, 2
-ABI_VERSION = 10
+ABI_VERSION = 11
+SLOTS_GRAPH, SLOTS_KEEP_CONTEXT = 1, 2
+SLOT_IDLE = 0x80000000             # bit 31 of Slot.step
 
 vp = C.c_void_p
 i32 = C.c_int
@@ -64,6 +67,11 @@ class LnFold(C.Structure):
     _fields_ = [("coef", vp), ("c", vp), ("d", vp), ("parts", vp), ("nparts", i32), ("eps", f32)]
 
 
+class Slot(C.Structure):
+    """mirror of pmhip_slot: the decode state of one image of a batch (32 bytes)"""
+    _fields_ = [("seed", u64), ("image_index", u64), ("temperature", f32), ("topk", i32), ("num_mask", i32), ("step", u32)]
+
+
 # name -> (restype, argtypes); every symbol include/pmhip.h declares
 PROTOTYPES = {
     "pmhip_abi_version": (i32, []),
@@ -110,6 +118,9 @@ PROTOTYPES = {
     "pmhip_sample_rows": (i32, [vp, i32, vp, i64, i32, f32, vp, u64, u32, u64, vp, vp, vp, i32, i32, vp]),
     "pmhip_sample_rows_stats": (i32, [vp, i32, vp, vp, i64, i32, f32, vp, u64, u32, u64, vp, vp, vp, i32, i32, vp]),
     "pmhip_remask": (i32, [vp, vp, i32, i64, i32, i32, vp]),
+    "pmhip_sample_rows_slots": (i32, [vp, i32, vp, vp, i64, vp, i32, vp, vp, vp, i32, i32, vp]),
+    "pmhip_remask_slots": (i32, [vp, vp, vp, i64, i32, i32, vp]),
+    "pmhip_pipeline_step_slots": (i32, [vp, vp, vp, i32, i32, C.POINTER(Slot), i32, vp, vp, vp]),
     "pmhip_vqgan_create": (i32, [C.POINTER(vp), i32, i32, C.POINTER(VqganCfg), C.POINTER(VqganWeights)]),
     "pmhip_vqgan_destroy": (None, [vp]),
     "pmhip_vqgan_encode": (i32, [vp, vp, i32, vp, vp, vp, vp]),
@@ -164,4 +175,6 @@ def load():
 def check(rc, what=""):
     if rc != PMHIP_OK:
         msg = load().pmhip_last_error()
-        raise PmhipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+        err = PmhipError(f"{what} failed (code {rc}): {msg.decode() if msg else '?'}")
+        err.code = rc                     # a PMHIP_E* value
+        raise err

@@ -80,6 +80,17 @@ int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, 
               pmhip_stream stream);
 
 // ---------------------------------------------------------------------------------------------
+// per-IMAGE decode state (include/pmhip.h, pmhip_slot): device memory, one record per image of the batch.  The slots forms of the
+// sampling tail read every per-call value from it, so a captured step serves every schedule and every mix of requests.
+// ---------------------------------------------------------------------------------------------
+static_assert(sizeof(pmhip_slot) == 32, "pmhip_slot is 32 bytes: two 16-byte words per image");
+constexpr uint32_t PM_SLOT_IDLE = 0x80000000u;              // bit 31 of pmhip_slot::step
+int pm_sample_rows_slots(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
+                         const pmhip_slot* slots, int tokens, int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V,
+                         pmhip_stream stream);
+int pm_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id, int B, int N, pmhip_stream stream);
+
+// ---------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float bf16_to_f32(bf16_t h) { return __uint_as_float(((uint32_t)h) << 16); }

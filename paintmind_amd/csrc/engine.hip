@@ -685,6 +685,14 @@ struct pmhip_s2 {
     PmGenParams* params_host = nullptr;
     hipEvent_t params_done[kParamSlots] = {};
     int params_next = 0;
+    // per-image decode state (pmhip_pipeline_step_slots): the host records travel through a pinned ring of their own (kParamSlots
+    // entries of slots_cap records; an entry is reused only after the copy that read it has completed), and the handle remembers
+    // which context the last slots call prepared (slots_ctx_L: 0 = prepared without a context, -1 = nothing a slots call may reuse)
+    pmhip_slot* slots_host = nullptr;
+    int slots_cap = 0;
+    hipEvent_t slots_done[kParamSlots] = {};
+    int slots_next = 0;
+    int slots_ctx_B = 0, slots_ctx_L = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
     // its previous record may still be queued); last D2H complete -> next call
     std::vector<hipEvent_t> img_ready;
@@ -697,6 +705,9 @@ struct pmhip_s2 {
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (params_host) (void)hipHostFree(params_host);
+        if (slots_host) (void)hipHostFree(slots_host);
+        for (auto e : slots_done)
+            if (e) (void)hipEventDestroy(e);
         for (auto e : params_done)
             if (e) (void)hipEventDestroy(e);
         for (auto e : img_ready)
@@ -737,6 +748,7 @@ int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStrea
     const auto& c = h->cfg;
     const int dim = c.tower.dim, heads = c.tower.heads, dh = dh_of(c.tower), inner = heads * dh;
     const size_t es = dtype_size(h->dtype);
+    h->slots_ctx_L = -1;                                      // whatever a slots call prepared is about to be replaced
     if (!context) {
         for (auto& ck : h->cross) ck = CrossKV{};
         return PMHIP_OK;
@@ -858,6 +870,20 @@ int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, int topk, floa
     if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
     if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
     return pm_remask(ids, score, num_mask, (int64_t)c.n_embed, B, c.tokens, gp, (int)step, s);
+}
+
+// step_tail with every per-image value read from the device records `slots` [B] (no image: the caller decodes finished rows only)
+int step_tail_slots(pmhip_s2* s2, int64_t* ids, int B, const pmhip_slot* slots, int64_t* pred_out, float* score_out, hipStream_t s) {
+    const auto& c = s2->cfg;
+    const int M = B * c.tokens;
+    float* logits; float* lstats; int64_t* pred; float* score;
+    PM_TRY(step_bufs(s2, M, logits, lstats, s));             // step_tower filled them
+    WS(s2->ws, "s2.pred", (size_t)M * 8, pred);
+    WS(s2->ws, "s2.score", (size_t)M * 4, score);
+    PM_TRY(pm_sample_rows_slots(logits, c.n_embed, lstats, ids, (int64_t)c.n_embed, slots, c.tokens, pred, ids, score, M, c.n_embed, s));
+    if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
+    if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
+    return pm_remask_slots(ids, score, slots, (int64_t)c.n_embed, B, c.tokens, s);
 }
 
 int sample_step(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, int topk, float temperature, int num_mask,
@@ -1155,6 +1181,118 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               size_t host_stride, pmhip_stream copy_stream, float guidance_scale) {
     return pipeline_generate(s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
                              use_graph, stream, imgs_host, host_stride, copy_stream, &guidance_scale);
+}
+
+// One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged
+// through the pinned ring into the workspace, and read from there by the sampling and re-masking kernels; with the graph flag the
+// step -- tower, sampling, re-masking: one linear chain -- is captured once per (B, context length) on handle-owned ids and
+// replayed, whatever the records say.
+extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
+                                         int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    PM_REQUIRE(s2 && ids && slots_host && B > 0, "pipeline_step_slots: bad arguments (null handle, ids or slots, or B <= 0)");
+    const auto& c = s2->cfg;
+    PM_REQUIRE(c.n_embed % 64 == 0, "pipeline_step_slots: n_embed=%d must be a multiple of 64", c.n_embed);
+    for (int b = 0; b < B; ++b) {
+        const pmhip_slot& sl = slots_host[b];
+        if (sl.step & PM_SLOT_IDLE) continue;
+        PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "pipeline_step_slots: slot %d: topk=%d must be in [1, 8]", b, sl.topk);
+        PM_REQUIRE(sl.num_mask >= 1, "pipeline_step_slots: slot %d: num_mask=%d must be >= 1", b, sl.num_mask);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (flags & PMHIP_SLOTS_KEEP_CONTEXT) {
+        if (s2->slots_ctx_L < 0 || s2->slots_ctx_B != B || s2->slots_ctx_L != L) {
+            pm_set_error("pipeline_step_slots: keep-context asked for B=%d L=%d, but %s", B, L,
+                         s2->slots_ctx_L < 0 ? "no slots call has prepared a context on this handle (or another entry point replaced it)"
+                                             : "the prepared context has another B or L");
+            return PMHIP_ESTATE;
+        }
+    } else {
+        PM_TRY(s2_prepare_context(s2, context, L, B, s));     // eager, outside any graph
+        s2->slots_ctx_B = B;
+        s2->slots_ctx_L = context ? L : 0;
+    }
+    const int Lc = s2->slots_ctx_L;
+
+    // the records: pinned ring entry -> device
+    if (B > s2->slots_cap) {
+        for (auto e : s2->slots_done)
+            if (e) PM_HIP(hipEventSynchronize(e));            // copies still reading the old ring
+        if (s2->slots_host) { PM_HIP(hipHostFree(s2->slots_host)); s2->slots_host = nullptr; s2->slots_cap = 0; }
+        PM_HIP(hipHostMalloc((void**)&s2->slots_host, sizeof(pmhip_slot) * (size_t)B * pmhip_s2::kParamSlots, hipHostMallocDefault));
+        s2->slots_cap = B;
+        for (auto& e : s2->slots_done)
+            if (!e) PM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    pmhip_slot* dslots;
+    WS(s2->ws, "slots.dev", sizeof(pmhip_slot) * (size_t)B, dslots);
+    {
+        const int e = s2->slots_next;
+        s2->slots_next = (e + 1) % pmhip_s2::kParamSlots;
+        PM_HIP(hipEventSynchronize(s2->slots_done[e]));       // the copy that last read this entry (no-op when never recorded)
+        pmhip_slot* hp = s2->slots_host + (size_t)e * s2->slots_cap;
+        memcpy(hp, slots_host, sizeof(pmhip_slot) * (size_t)B);
+        void* hp_dev = nullptr;                               // the pinned entry through its device alias
+        PM_HIP(hipHostGetDevicePointer(&hp_dev, hp, 0));
+        PM_TRY(copy16_async(dslots, hp_dev, sizeof(pmhip_slot) * (size_t)B, s));
+        PM_HIP(hipEventRecord(s2->slots_done[e], s));
+    }
+
+    // ignored exactly when pipeline_generate ignores its graph request (same bits either way)
+    const bool graph = (flags & PMHIP_SLOTS_GRAPH) && !g_pm_timing_on.load() && !direct_dispatch_off();
+    if (!graph) {
+        PM_TRY(step_tower(s2, ids, B, s, nullptr));
+        return step_tail_slots(s2, ids, B, dslots, pred_out, score_out, s);
+    }
+
+    const size_t ids_bytes = (size_t)B * c.tokens * 8;
+    int64_t* gids;
+    WS(s2->ws, "slots.ids", ids_bytes, gids);
+    PM_TRY(copy16_async(gids, ids, ids_bytes, s));
+    GraphEntry& ge = s2->graphs["slotsB" + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key())];
+    auto run_step = [&](hipStream_t on) -> int {
+        PM_TRY(step_tower(s2, gids, B, on, nullptr));
+        return step_tail_slots(s2, gids, B, dslots, nullptr, nullptr, on);
+    };
+    if (!ge.warmed) {
+        PM_TRY(run_step(s));                                  // eager once: sizes every workspace buffer
+        ge.warmed = true;
+    } else {
+        if (!ge.segs.empty() && ge.s2_gen != s2->ws.gen) {    // a workspace buffer was reallocated since the capture
+            PM_HIP(hipStreamSynchronize(s));
+            ge.destroy();
+        }
+        if (ge.segs.empty()) {
+            if (!s2->capture_stream) PM_HIP(hipStreamCreateWithFlags(&s2->capture_stream, hipStreamNonBlocking));
+            hipStream_t cap = s2->capture_stream;
+            hipGraph_t g = nullptr;
+            hipGraphExec_t exec = nullptr;
+            s2->ws.frozen = true;
+            hipError_t rc = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
+            int step_rc = PMHIP_OK;
+            if (rc == hipSuccess) {
+                step_rc = run_step(cap);                      // records only: nothing executes during capture
+                rc = hipStreamEndCapture(cap, &g);
+            }
+            s2->ws.frozen = false;
+            if (step_rc == PMHIP_OK && rc == hipSuccess) rc = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+            if (g) (void)hipGraphDestroy(g);
+            if (step_rc != PMHIP_OK) return step_rc;
+            PM_HIP(rc);
+            ge.segs.push_back(exec);
+            ge.s2_gen = s2->ws.gen;
+        }
+        PM_HIP(hipGraphLaunch(ge.segs[0], s));
+    }
+    PM_TRY(copy16_async(ids, gids, ids_bytes, s));
+    if (pred_out || score_out) {
+        const size_t M = (size_t)B * c.tokens;
+        int64_t* pred; float* score;
+        WS(s2->ws, "s2.pred", M * 8, pred);
+        WS(s2->ws, "s2.score", M * 4, score);
+        if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, M * 8, hipMemcpyDeviceToDevice, s));
+        if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, M * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return PMHIP_OK;
 }
 
 // the PMHIP_* switches a handle latched when it was created (bit 0 fold, 1 hilo, 2 stats, 3 center, 4 blocking_wait)

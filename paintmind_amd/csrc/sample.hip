@@ -170,17 +170,38 @@ constexpr int KT_MAX = 8;                                  // top-k served by sa
 
 // NB2 = blocks per lane (block b is kept by lane b % 64).  DENSE: no statistics were handed in -- one pass over the stored row
 // computes them (lane l, group g: columns (g*64 + l)*4 .. +3, i.e. block g*4 + l/16 in the layout softmax_block_stat defines).
-template <int NB2, bool DENSE>
+// SLOTS (pmhip_sample_rows_slots): the per-call scalars of row r come from slots[r / tokens] -- one wave owns a row, so they are
+// wave-uniform like the kernel arguments they replace -- and everything below the prologue is the code of the scalar form.  The
+// scalar instantiations compile the prologue away: they gain neither a load nor a branch.
+template <int NB2, bool DENSE, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
     const float* __restrict__ logits, int ldl, const float2* __restrict__ stats, const int64_t* __restrict__ ids_in, int64_t mask_id,
     int topk, float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
-    const PmGenParams* __restrict__ gp) {
+    const PmGenParams* __restrict__ gp, const pmhip_slot* __restrict__ slots, int tokens) {
     __shared__ float2 sh[DENSE ? THREADS / 64 : 1][DENSE ? NB2 * 64 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * (THREADS / 64) + wave;
     if (row >= M) return;                                  // whole wave exits together (no workgroup barrier below)
-    if (gp) {
+    if constexpr (SLOTS) {
+        const int img = __builtin_amdgcn_readfirstlane(row / tokens);
+        const pmhip_slot sl = slots[img];
+        step = __builtin_amdgcn_readfirstlane(sl.step);
+        if (step & PM_SLOT_IDLE) {                         // wave-uniform: nothing is drawn, the row keeps its id
+            if (lane == 0) {
+                const int64_t cur = ids_in[row];
+                if (pred_out) pred_out[row] = cur;
+                ids_out[row] = cur;
+                if (score_out) score_out[row] = -1e5f;
+            }
+            return;
+        }
+        topk = __builtin_amdgcn_readfirstlane(sl.topk);
+        temperature = sl.temperature;
+        seed = sl.seed;
+        // row_base + row below = image_index * tokens + position (modulo 2^64, like the sum itself)
+        row_base = sl.image_index * (uint64_t)tokens - (uint64_t)img * (uint64_t)tokens;
+    } else if (gp) {
         temperature = gp->temps[step];
         seed = gp->seed;
         row_base = gp->row_base;
@@ -348,13 +369,18 @@ __global__ __launch_bounds__(THREADS) void remask_kernel(int64_t* __restrict__ i
 // compare-exchange with distance j is in-thread for j < E, a wave shuffle for j < 64*E and goes through LDS (two barriers) only
 // beyond that: 3 of the 55 stages at N = 1024 (the all-LDS kernel above: one barrier per stage, 40 us per launch on B <= 64
 // workgroups -- latency, not work).  Same keys, same total order, same threshold test.
-template <int E>
+// SLOTS (pmhip_remask_slots): num_mask = slots[image].num_mask; the workgroup of an idle slot leaves (before any barrier).
+template <int E, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
                                                              int num_mask, int64_t mask_id, int N, const PmGenParams* __restrict__ gp,
-                                                             int step) {
+                                                             int step, const pmhip_slot* __restrict__ slots) {
     constexpr int NP = THREADS * E;
     __shared__ unsigned long long xs[NP];
-    if (gp) num_mask = gp->nmask[step];
+    if constexpr (SLOTS) {
+        const pmhip_slot sl = slots[blockIdx.x];
+        if (sl.step & PM_SLOT_IDLE) return;
+        num_mask = sl.num_mask;
+    } else if (gp) num_mask = gp->nmask[step];
     const int tid = threadIdx.x, base = tid * E;
     const float* sc = scores + (size_t)blockIdx.x * N;
     unsigned long long key[E], mine[E];
@@ -432,9 +458,9 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const
 #define PM_TILES(NB2)                                                                                                         \
     do {                                                                                                                      \
         if (st) hipLaunchKernelGGL((sample_tiles_kernel<NB2, false>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, topk, \
-                                   temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp);          \
+                                   temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, nullptr, 0); \
         else hipLaunchKernelGGL((sample_tiles_kernel<NB2, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, topk,   \
-                                temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp);             \
+                                temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, nullptr, 0); \
     } while (0)
         if (V <= 4096) PM_TILES(1);
         else if (V <= 8192) PM_TILES(2);
@@ -474,6 +500,39 @@ extern "C" int pmhip_sample_rows_stats(const float* logits, int ldl, const float
                           score_out, M, V, nullptr, stream);
 }
 
+// the per-image form: the block-statistics kernel only (what every decode-loop launch runs), every scalar from slots[row / tokens]
+int pm_sample_rows_slots(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
+                         const pmhip_slot* slots, int tokens, int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V,
+                         pmhip_stream stream) {
+    PM_REQUIRE(logits && ids_in && ids_out && slots, "sample_rows_slots: null pointer");
+    PM_REQUIRE(M > 0 && V > 0 && ldl % 4 == 0 && ldl >= V, "sample_rows_slots: bad shape M=%d V=%d ldl=%d", M, V, ldl);
+    PM_REQUIRE(V % 64 == 0 && V <= 16384, "sample_rows_slots: V=%d must be a multiple of 64, at most 16384", V);
+    PM_REQUIRE(tokens > 0 && M % tokens == 0, "sample_rows_slots: M=%d is not a whole number of images of %d tokens", M, tokens);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(ceil_div(M, THREADS / 64)), block(THREADS);
+    PmTimer tm(FAM_SAMPLE, s);
+    const float2* st = reinterpret_cast<const float2*>(block_stats);
+#define PM_TILES(NB2)                                                                                                          \
+    do {                                                                                                                       \
+        if (st) hipLaunchKernelGGL((sample_tiles_kernel<NB2, false, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, 0, 0.f, \
+                                   nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens);              \
+        else hipLaunchKernelGGL((sample_tiles_kernel<NB2, true, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, 0, 0.f, \
+                                nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens);                 \
+    } while (0)
+    if (V <= 4096) PM_TILES(1);
+    else if (V <= 8192) PM_TILES(2);
+    else PM_TILES(4);
+#undef PM_TILES
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
+}
+
+extern "C" int pmhip_sample_rows_slots(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
+                                       const pmhip_slot* slots, int tokens, int64_t* pred_out, int64_t* ids_out, float* score_out,
+                                       int M, int V, pmhip_stream stream) {
+    return pm_sample_rows_slots(logits, ldl, block_stats, ids_in, mask_id, slots, tokens, pred_out, ids_out, score_out, M, V, stream);
+}
+
 int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N, const PmGenParams* gp, int step,
               pmhip_stream stream) {
     PM_REQUIRE(ids && scores, "remask: null pointer");
@@ -483,7 +542,7 @@ int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, 
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_SAMPLE, s);
     static const int g_reg = pm_dev_knob("PMHIP_REMASK_REG", 1);      // 0: the all-LDS sort (A/B)
-#define PM_REMASK(E) hipLaunchKernelGGL(remask_reg_kernel<E>, dim3(B), dim3(THREADS), 0, s, ids, scores, num_mask, mask_id, N, gp, step)
+#define PM_REMASK(E) hipLaunchKernelGGL(remask_reg_kernel<E>, dim3(B), dim3(THREADS), 0, s, ids, scores, num_mask, mask_id, N, gp, step, nullptr)
     if (!g_reg) hipLaunchKernelGGL(remask_kernel, dim3(B), dim3(THREADS), (size_t)np2 * 8, s, ids, scores, num_mask, mask_id, N, np2, gp, step);
     else if (np2 <= 256) PM_REMASK(1);
     else if (np2 <= 512) PM_REMASK(2);
@@ -498,4 +557,27 @@ int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, 
 extern "C" int pmhip_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N,
                             pmhip_stream stream) {
     return pm_remask(ids, scores, num_mask, mask_id, B, N, nullptr, 0, stream);
+}
+
+int pm_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id, int B, int N, pmhip_stream stream) {
+    PM_REQUIRE(ids && scores && slots, "remask_slots: null pointer");
+    PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "remask_slots: bad shape B=%d N=%d (N <= 4096)", B, N);
+    int np2 = 1;
+    while (np2 < N) np2 <<= 1;
+    hipStream_t s = (hipStream_t)stream;
+    PmTimer tm(FAM_SAMPLE, s);
+#define PM_REMASK(E) hipLaunchKernelGGL((remask_reg_kernel<E, true>), dim3(B), dim3(THREADS), 0, s, ids, scores, 0, mask_id, N, nullptr, 0, slots)
+    if (np2 <= 256) PM_REMASK(1);
+    else if (np2 <= 512) PM_REMASK(2);
+    else if (np2 <= 1024) PM_REMASK(4);
+    else if (np2 <= 2048) PM_REMASK(8);
+    else PM_REMASK(16);
+#undef PM_REMASK
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
+}
+
+extern "C" int pmhip_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id, int B, int N,
+                                  pmhip_stream stream) {
+    return pm_remask_slots(ids, scores, slots, mask_id, B, N, stream);
 }

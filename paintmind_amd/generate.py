@@ -346,6 +346,21 @@ class Pipeline(nn.Module):
         """the HIP stream of one lane (a hook: tools/cu_mask_lanes.py replaces it with CU-masked streams for an experiment)"""
         return torch.cuda.Stream(device=device)
 
+    def _start_ids(self, B, ids0, device):
+        """the ids a decode loop starts from: all-mask, or a CONTIGUOUS int64 copy of ids0 [B, N] on `device` (the native calls
+        read B * N consecutive ids; clone() alone would keep a view's strides)"""
+        if ids0 is None:
+            return torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long, device=device)
+        if tuple(ids0.shape) != (B, self.num_tokens):
+            raise ValueError(f"start ids have shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
+        return ids0.to(device, torch.long).clone(memory_format=torch.contiguous_format)
+
+    def decode_session(self, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True):
+        """a DecodeSession over this pipeline (paintmind_amd/serve.py): `slots` images decode together, each with its own
+        timesteps / temperature / top-k / seed, and new requests are admitted into free slots between steps"""
+        from .serve import DecodeSession
+        return DecodeSession(self, slots=slots, conditional=conditional, use_graph=use_graph, record_steps=record_steps, decode=decode)
+
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
                      join=True, wait_current=True, host=None, guidance_scale=None, ids0=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
@@ -361,6 +376,8 @@ class Pipeline(nn.Module):
         the host buffer (every lane fills its rows, each image as soon as it is complete, on its own copy stream); no
         device image tensor is returned.
         ids0 (streams = 1 only): start from these ids [B, N] int64 instead of the all-mask state (the region loops of inpaint / outpaint)."""
+        if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
+            raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
         temps, nmask = self._schedule(timesteps, temperature)
         if isinstance(streams, (list, tuple)):           # explicit micro-batch sizes, e.g. (32, 16, 16)
@@ -381,8 +398,7 @@ class Pipeline(nn.Module):
         if ids0 is not None and streams != 1:
             raise ValueError("generate_ids: ids0 needs streams=1")
         if streams == 1:
-            ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long, device=eng.device) if ids0 is None \
-                else ids0.to(eng.device, torch.long).clone()
+            ids = self._start_ids(B, ids0, eng.device)
             return eng.generate(self.vqgan.engine(), ids, context, temps, nmask, decode_flags, topk, seed=seed,
                                 image_base=image_base, use_graph=use_graph,
                                 host=None if host is None else (host[0], 0, host[1][0]), want_device_imgs=host is None,

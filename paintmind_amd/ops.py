@@ -493,6 +493,58 @@ def remask(ids, scores, num_mask, mask_id):
     return ids
 
 
+def pack_slots(records, device=None):
+    """[(seed, image_index, temperature, topk, num_mask, step) or None (idle), ...] -> the pmhip_slot array as a uint8 tensor
+    [B, 32] (on `device` when given): what sample_rows_slots / remask_slots read."""
+    arr = (_lib.Slot * len(records))()
+    for i, r in enumerate(records):
+        if r is None:
+            arr[i].step = _lib.SLOT_IDLE
+            continue
+        seed, image_index, temperature, topk, num_mask, step = r
+        arr[i] = _lib.Slot(int(seed) & (2 ** 64 - 1), int(image_index) & (2 ** 64 - 1), float(temperature), int(topk), int(num_mask), int(step))
+    t = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).reshape(len(records), C.sizeof(_lib.Slot))
+    return t if device is None else t.to(device)
+
+
+def _check_slots(slots, B, dev):
+    if (slots.dtype != torch.uint8 or not slots.is_contiguous() or slots.device != dev
+            or tuple(slots.shape) != (B, C.sizeof(_lib.Slot))):
+        raise ValueError(f"slots must be a contiguous uint8 [{B}, {C.sizeof(_lib.Slot)}] tensor (pack_slots) on the operands' device")
+
+
+def sample_rows_slots(logits, ids, mask_id, slots, tokens, block_stats=None):
+    """sample_rows with the scalars of row r taken from slots[r // tokens] (pack_slots): logits fp32 [B*tokens, V], ids int64
+    [B*tokens] -> (pred, merged ids, score).  Image b equals sample_rows on its rows alone with its slot's values and
+    row_base = image_index * tokens, bit for bit; an idle slot keeps its ids (pred = ids, score = -1e5).  V % 64 == 0, topk <= 8."""
+    dev = _dev(logits, ids, slots, block_stats)
+    lib = _lib.load()
+    M, V = logits.shape
+    if tokens <= 0 or M % tokens:
+        raise ValueError(f"sample_rows_slots: {M} rows are not a whole number of images of {tokens} tokens")
+    _check_slots(slots, M // tokens, dev)
+    if block_stats is not None and (block_stats.dtype != torch.float32 or tuple(block_stats.shape) != (M, V // 64, 2) or V % 64):
+        raise ValueError("sample_rows_slots: block_stats must be a contiguous fp32 [M, V/64, 2] tensor on the logits' device")
+    pred = torch.empty(M, device=dev, dtype=torch.int64)
+    ids_out = torch.empty(M, device=dev, dtype=torch.int64)
+    score = torch.empty(M, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        check(lib.pmhip_sample_rows_slots(_p(logits), logits.stride(0), _p(block_stats), _p(ids), int(mask_id), _p(slots), int(tokens),
+                                          _p(pred), _p(ids_out), _p(score), M, V, stream_ptr(dev)), "pmhip_sample_rows_slots")
+    return pred, ids_out, score
+
+
+def remask_slots(ids, scores, slots, mask_id):
+    """remask with num_mask = slot b's, in place on ids int64 [B,N]; the row of an idle slot is left untouched."""
+    dev = _dev(ids, scores, slots)
+    lib = _lib.load()
+    B, N = ids.shape
+    _check_slots(slots, B, dev)
+    with torch.cuda.device(dev):
+        check(lib.pmhip_remask_slots(_p(ids), _p(scores), _p(slots), int(mask_id), B, N, stream_ptr(dev)), "pmhip_remask_slots")
+    return ids
+
+
 def random_mask(z, noise, mask_token, len_keep):
     """z fp32 [B,N,E], noise fp32 [B,N], mask_token fp32 [E] -> (x [B,N,E], mask [B,N] with 1 = masked)."""
     dev = _dev(z, noise, mask_token)
