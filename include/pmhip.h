@@ -428,6 +428,18 @@ int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const flo
  * defers a step's ViT decode to a side stream.  The deferral exists on the GRAPH path only (fork / join inside the captured
  * segments, for B * tokens <= 65536: one lane alone leaves the chip partly idle: +15 % at B = 8, +1.5 % at B = 64); the eager
  * loop decodes in line -- results are the same either way.
+ * PMHIP_GENERATE_FROM_MASK (4; added within ABI 11 -- a new flag bit and one new entry point, nothing existing changes meaning, so
+ * the version number stays): the loop starts from the all-mask state.  The library fills its working ids with the
+ * mask id (n_embed) itself -- the content of `ids` on entry is ignored, `ids` is still written on return -- so a caller cannot
+ * claim the state falsely.  With context == NULL (and hence no guidance) step 0 then runs NO tower: the input of that pass is the
+ * same for every image and every call, so its logits are a function of the weights alone, which a handle never changes.  The
+ * handle keeps the step-0 logits (and block statistics) of ONE image -- tokens x n_embed fp32 + tokens x n_embed/64 x 2 fp32:
+ * 32 MiB + 1 MiB at vit-s sizes -- computed by the first flagged loop (its ordinary step-0 tower; image 0's rows are kept) and
+ * sampled from by every later one, at any B, T, top-k, temperature and seed, eager or replayed (row r reads row r % tokens; ids,
+ * Philox counters and scores stay per row).  Rows of different images never mix and the kernels are batch-invariant, so the
+ * result is the unflagged loop's bit for bit (tests/test_gpu_step0.py); pmhip_s2_step0_shared counts fills and hits.  With a
+ * context the flag only fills the ids.  While per-kernel timing is on the shortcut is OFF, like the graph request: bench.py
+ * divides the work of ALL T tower passes by the measured family times, which a skipped pass would overstate by T / (T - 1).
  * imgs_host != NULL replaces the reference's `imgs.append(img.cpu())` (generate.py:195-196): decoded
  * image d is copied to imgs_host + d * host_stride (floats; the caller's PINNED buffer, so that a
  * lane can fill its rows of a [n_decoded, B_total, C, H, W] tensor) on copy_stream as soon as it is
@@ -439,6 +451,7 @@ int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const flo
  * copy_stream NULL: the copies are enqueued on `stream`. */
 #define PMHIP_GENERATE_GRAPH 1
 #define PMHIP_GENERATE_CONCURRENT_LANES 2
+#define PMHIP_GENERATE_FROM_MASK 4
 int pmhip_pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context,
                             int L, int B, int T, const float* temps_host, const int* nmask_host,
                             const unsigned char* decode_host, int topk, uint64_t seed,
@@ -492,6 +505,9 @@ int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, 
  * the eager loop; -1 for a NULL handle.  A tool that A/Bs a switch asserts the mode it believes it measures. */
 int pmhip_s2_switches(const pmhip_s2* h);
 int pmhip_vqgan_switches(const pmhip_vqgan* h);
+/* The shared step 0 (PMHIP_GENERATE_FROM_MASK): *fills = how often this handle computed it (0 or 1), *hits = how many loops
+ * sampled their step 0 from it without running a tower.  Either pointer may be NULL. */
+int pmhip_s2_step0_shared(const pmhip_s2* h, int* fills, int* hits);
 
 /* Per-kernel timing hook used by bench.py: when enabled, every kernel launch of the named family
  * is bracketed by hipEvents on its own stream and accumulated (count, total ms). */
@@ -500,7 +516,8 @@ int pmhip_timing_reset(void);
 /* family: "gemm" (all GEMM launches = the sum of "gemm_plain", "gemm_heads", "gemm_swiglu", "gemm_resid", "gemm_resid2b": bias-only /
  * head-split q|k|v / SwiGLU w12 / residual producers on the one-workgroup kernels / on the two-workgroups-per-CU kernel),
  * "attention", "layernorm", "sample", "vq", "rowops"; returns PMHIP_EINVAL if unknown.  The accumulators are process-wide and
- * guarded by a mutex; while timing is on pmhip_pipeline_generate runs eagerly (no graph replay). */
+ * guarded by a mutex; while timing is on pmhip_pipeline_generate runs eagerly (no graph replay) and runs the tower of EVERY
+ * step (no shared step 0, see PMHIP_GENERATE_FROM_MASK). */
 int pmhip_timing_get(const char* family, int* launches, double* total_ms);
 
 #ifdef __cplusplus

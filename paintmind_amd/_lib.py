@@ -14,6 +14,7 @@ PMHIP_EINVAL, PMHIP_EHIP, PMHIP_ENOMEM, PMHIP_ESTATE = 1, 2, 3, 4
 F32, BF16 = 0, 1
 PART_Q, PART_K, PART_V = 0, 1, 2
 ABI_VERSION = 11
+GENERATE_GRAPH, GENERATE_CONCURRENT_LANES, GENERATE_FROM_MASK = 1, 2, 4
 SLOTS_GRAPH, SLOTS_KEEP_CONTEXT = 1, 2
 SLOT_IDLE = 0x80000000             # bit 31 of Slot.step
 
@@ -139,6 +140,7 @@ PROTOTYPES = {
                                              C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, f32]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
+    "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

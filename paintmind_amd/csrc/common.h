@@ -73,9 +73,10 @@ struct PmGenParams {
     int nmask[PM_MAX_STEPS];
 };
 // block_stats: NULL, or the (max, sum of exp) pairs of the row's 64-column blocks, [M][V/64][2] (softmax_block_stat below)
+// period: 0, or the number of logits (and statistics) rows there are -- row r then samples from row r % period
 int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id, int topk,
                    float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base, int64_t* pred_out,
-                   int64_t* ids_out, float* score_out, int M, int V, const PmGenParams* gp, pmhip_stream stream);
+                   int64_t* ids_out, float* score_out, int M, int V, const PmGenParams* gp, int period, pmhip_stream stream);
 int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N, const PmGenParams* gp, int step,
               pmhip_stream stream);
 

@@ -178,6 +178,16 @@ int copy16_async(void* dst, const void* src, size_t bytes, hipStream_t s) {
     PM_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, s));
     return PMHIP_OK;
 }
+// ids[0 .. n) = value, stream-ordered (the all-mask start of a decode loop)
+__global__ void fill_ids_kernel(int64_t* __restrict__ ids, int64_t value, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) ids[i] = value;
+}
+int fill_ids_async(int64_t* ids, int64_t value, size_t n, hipStream_t s) {
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(fill_ids_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, s, ids, value, n);
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
+}
 constexpr float kLog2e = 1.4426950408889634f;
 
 struct CrossKV {            // cached cross-attention K / V^T of a static context, per layer
@@ -698,6 +708,13 @@ struct pmhip_s2 {
     std::vector<hipEvent_t> img_ready;
     hipEvent_t host_copied = nullptr;
     bool host_copy_pending = false;
+    // the shared step 0 of unconditional loops that start from the all-mask state (PMHIP_GENERATE_FROM_MASK): the logits and block
+    // statistics of ONE all-mask image (workspace "s0.logits" / "s0.lstats", fixed size) are a function of the weights alone,
+    // which this handle never changes; filled by the first such loop, sampled from by every later one at any B
+    bool s0_valid = false;
+    int s0_fills = 0, s0_hits = 0;
+    hipStream_t s0_stream = nullptr;            // the stream that filled the buffers: a loop on another stream waits for s0_ready
+    hipEvent_t s0_ready = nullptr;
     ~pmhip_s2() {
         for (auto& kv : graphs) kv.second.destroy();
         if (capture_stream) (void)hipStreamDestroy(capture_stream);
@@ -713,6 +730,7 @@ struct pmhip_s2 {
         for (auto e : img_ready)
             if (e) (void)hipEventDestroy(e);
         if (host_copied) (void)hipEventDestroy(host_copied);
+        if (s0_ready) (void)hipEventDestroy(s0_ready);
     }
 };
 
@@ -827,6 +845,15 @@ int step_bufs(pmhip_s2* s2, int M, float*& logits, float*& lstats, hipStream_t s
     return PMHIP_OK;
 }
 
+// the same two buffers for ONE image, kept: the shared step 0 (pmhip_s2::s0_valid)
+int step0_bufs(pmhip_s2* s2, float*& logits, float*& lstats, hipStream_t s) {
+    const auto& c = s2->cfg;
+    WS(s2->ws, "s0.logits", (size_t)c.tokens * c.n_embed * 4, logits);
+    lstats = nullptr;
+    if (c.n_embed % 64 == 0 && s2->sw.logits_stats) WS(s2->ws, "s0.lstats", (size_t)c.tokens * (c.n_embed / 64) * 8, lstats);
+    return PMHIP_OK;
+}
+
 int step_tower(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s, const float* guidance) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
@@ -857,15 +884,16 @@ int decode_pred(pmhip_s2* s2, pmhip_vqgan* vq, int B, float* img_out, hipStream_
 
 int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, int topk, float temperature, int num_mask, const float* noise,
               uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out, float* score_out, hipStream_t s,
-              const PmGenParams* gp) {
+              const PmGenParams* gp, bool shared0 = false) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
     float* logits; float* lstats; int64_t* pred; float* score;
-    PM_TRY(step_bufs(s2, M, logits, lstats, s));             // step_tower filled them
+    if (shared0) PM_TRY(step0_bufs(s2, logits, lstats, s));  // every image samples from the one all-mask image's rows
+    else PM_TRY(step_bufs(s2, M, logits, lstats, s));        // step_tower filled them
     WS(s2->ws, "s2.pred", (size_t)M * 8, pred);
     WS(s2->ws, "s2.score", (size_t)M * 4, score);
     PM_TRY(pm_sample_rows(logits, c.n_embed, lstats, ids, (int64_t)c.n_embed, topk, temperature, noise, seed, step,
-                          image_base * (uint64_t)c.tokens, pred, ids, score, M, c.n_embed, gp, s));
+                          image_base * (uint64_t)c.tokens, pred, ids, score, M, c.n_embed, gp, shared0 ? c.tokens : 0, s));
     if (img_out) PM_TRY(decode_pred(s2, vq, B, img_out, s));
     if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
     if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
@@ -891,6 +919,29 @@ int sample_step(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, int topk, fl
                 float* score_out, hipStream_t s, const PmGenParams* gp = nullptr, const float* guidance = nullptr) {
     PM_TRY(step_tower(s2, ids, B, s, guidance));
     return step_tail(s2, vq, ids, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out, score_out, s, gp);
+}
+
+// The tower half of step 0 of an unconditional loop from the all-mask state (ids: B all-mask images).  Its input is the same for
+// every image and every call -- tok_table[mask] -> token_proj + pos -> the layers -> to_logits, no context -- rows of different
+// images never mix, and the kernels are batch-invariant bit for bit, so image 0's logits ARE every image's, at any B.  The first
+// such loop on a handle runs the ordinary tower and keeps image 0's rows; every later one runs nothing here, and step_tail
+// (shared0) samples all B images from the kept rows.
+int step0_tower_once(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s) {
+    if (s2->s0_valid) return PMHIP_OK;
+    PM_REQUIRE(!s2->ws.frozen, "pipeline_generate: the shared step-0 logits are missing during a graph capture");
+    const auto& c = s2->cfg;
+    float* logits; float* lstats; float* l0; float* st0;
+    PM_TRY(step0_bufs(s2, l0, st0, s));
+    PM_TRY(step_tower(s2, ids, B, s, nullptr));
+    PM_TRY(step_bufs(s2, B * c.tokens, logits, lstats, s));
+    PM_TRY(copy16_async(l0, logits, (size_t)c.tokens * c.n_embed * 4, s));
+    if (st0) PM_TRY(copy16_async(st0, lstats, (size_t)c.tokens * (c.n_embed / 64) * 8, s));
+    if (!s2->s0_ready) PM_HIP(hipEventCreateWithFlags(&s2->s0_ready, hipEventDisableTiming));
+    PM_HIP(hipEventRecord(s2->s0_ready, s));
+    s2->s0_stream = s;
+    s2->s0_valid = true;
+    ++s2->s0_fills;
+    return PMHIP_OK;
 }
 
 }  // namespace
@@ -957,6 +1008,21 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
     // code involved -- so the loop stays eager in that mode whatever the caller asked for (same results, bit for bit)
     // pmhip_s2_switches reports the downgrade (bit 5) so that a caller can tell which mode ran
     const bool graph = (use_graph & PMHIP_GENERATE_GRAPH) && !g_pm_timing_on.load() && T <= PM_MAX_STEPS && !direct_dispatch_off();
+    // PMHIP_GENERATE_FROM_MASK: the loop starts from the all-mask state -- the library writes that state itself, so the claim
+    // cannot be false -- and, without a context, step 0 samples from the handle's shared step-0 logits instead of running the tower
+    // (step0_tower_once).  Not while per-kernel timing is on: the timed pass accounts for the work of all T tower passes.
+    const bool from_mask = (use_graph & PMHIP_GENERATE_FROM_MASK) != 0;
+    const bool share0 = from_mask && !context && !guidance && !g_pm_timing_on.load();
+    const size_t n_ids = (size_t)B * s2->cfg.tokens;
+    if (share0 && s2->s0_valid) {
+        ++s2->s0_hits;
+        if (s != s2->s0_stream) PM_HIP(hipStreamWaitEvent(s, s2->s0_ready, 0));
+    }
+    // the tower half of step t
+    auto tower = [&](const int64_t* from, int t, hipStream_t on) -> int {
+        if (share0 && t == 0) return step0_tower_once(s2, from, B, on);
+        return step_tower(s2, from, B, on, guidance);
+    };
 
     if (imgs_host) {
         // PMHIP_BLOCKING_WAIT=1 (read when the handle is created): the lane's host thread SLEEPS in hipEventSynchronize while its
@@ -1010,11 +1076,13 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
 
     if (!graph) {
         int d = 0;
+        if (from_mask) PM_TRY(fill_ids_async(ids, (int64_t)s2->cfg.n_embed, n_ids, s));
         for (int t = 0; t < T; ++t) {
             const bool dec = decode_host && decode_host[t];
             float* img = !dec ? nullptr : (gimgs ? gimgs : imgs_out) + (size_t)d * img_elems;
-            PM_TRY(sample_step(s2, vq, ids, B, topk, temps_host[t], nmask_host[t], nullptr, seed, (uint32_t)t, image_base, img,
-                               nullptr, nullptr, s, nullptr, guidance));
+            PM_TRY(tower(ids, t, s));
+            PM_TRY(step_tail(s2, vq, ids, B, topk, temps_host[t], nmask_host[t], nullptr, seed, (uint32_t)t, image_base, img,
+                             nullptr, nullptr, s, nullptr, share0 && t == 0));
             PM_TRY(flush_pending());                           // the previous image, now that one more step is queued behind it
             if (dec) PM_TRY(deliver(d++, img));
         }
@@ -1025,7 +1093,7 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
     // one), whose kernels read the per-call scalars (temperatures, mask counts, seed, row base) from a device parameter
     // block and whose ids / image pointers are handle-owned buffers, so the same executable graphs serve every call with
     // this structure; between two segments the finished image starts its way to the host.
-    const size_t ids_bytes = (size_t)B * s2->cfg.tokens * 8;
+    const size_t ids_bytes = n_ids * 8;
     int64_t* gids; PmGenParams* gparams;
     WS(s2->ws, "gen.ids", ids_bytes, gids);
     WS(s2->ws, "gen.params", sizeof(PmGenParams), gparams);
@@ -1046,7 +1114,8 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
         PM_TRY(copy16_async(gparams, hp_dev, sizeof hp, s));
     }
     PM_HIP(hipEventRecord(s2->params_done[slot], s));
-    PM_TRY(copy16_async(gids, ids, ids_bytes, s));
+    if (from_mask) PM_TRY(fill_ids_async(gids, (int64_t)s2->cfg.n_embed, n_ids, s));
+    else PM_TRY(copy16_async(gids, ids, ids_bytes, s));
 
     std::string key = "B" + std::to_string(B) + "T" + std::to_string(T) + "k" + std::to_string(topk) + "L" +
                       std::to_string(context ? L : 0) + "v" + std::to_string(vq ? vq->uid : 0) + "f" +
@@ -1083,6 +1152,7 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
         if (pend >= 0) units.push_back({T, T, pend, pend, false});
     }
     key += overlap ? "o1" : "o0";
+    if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
     GraphEntry& ge = s2->graphs[key];
     if (overlap && !s2->side_stream) {
         PM_HIP(hipStreamCreateWithFlags(&s2->side_stream, hipStreamNonBlocking));
@@ -1105,10 +1175,11 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
             }
         }
         for (int t = u.t0; t < u.t1; ++t) {
-            PM_TRY(step_tower(s2, gids, B, on, guidance));
+            PM_TRY(tower(gids, t, on));
             if (need_join) { PM_HIP(hipStreamWaitEvent(on, s2->ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
             float* img = (u.decode_inline && decode_host && decode_host[t]) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
-            PM_TRY(step_tail(s2, vq, gids, B, topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, img, nullptr, nullptr, on, gparams));
+            PM_TRY(step_tail(s2, vq, gids, B, topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, img, nullptr, nullptr, on, gparams,
+                             share0 && t == 0));
         }
         return PMHIP_OK;
     };
@@ -1292,6 +1363,14 @@ extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float
         if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, M * 8, hipMemcpyDeviceToDevice, s));
         if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, M * 4, hipMemcpyDeviceToDevice, s));
     }
+    return PMHIP_OK;
+}
+
+// how often the shared step 0 was computed (0 or 1 per handle) and how many loops sampled from it without running a tower
+extern "C" int pmhip_s2_step0_shared(const pmhip_s2* h, int* fills, int* hits) {
+    PM_REQUIRE(h, "s2_step0_shared: null handle");
+    if (fills) *fills = h->s0_fills;
+    if (hits) *hits = h->s0_hits;
     return PMHIP_OK;
 }
 

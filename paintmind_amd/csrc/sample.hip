@@ -68,12 +68,15 @@ __device__ __forceinline__ float gumbel_from_uniform(float u) {
 // Row layout in registers: lane l holds float4 group g (g = 0..NV4-1) = columns (g*64 + l)*4 .. +3,
 // so a lane's columns increase with g and groups are disjoint contiguous column ranges: ordering
 // candidates by (value desc, first column of their group asc) equals (value desc, column asc).
-template <int NV4>
+// PERIOD: logits row r is read from row r % period (every image of a batch samples from ONE image's logits -- the shared step 0 of
+// an unconditional loop, engine.hip); ids, predictions, scores, the noise and the Philox counters stay per row.  The other
+// instantiation never looks at `period`.
+template <int NV4, bool PERIOD = false>
 __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
     const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, int64_t mask_id, int topk,
     float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
-    const PmGenParams* __restrict__ gp) {
+    const PmGenParams* __restrict__ gp, int period) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
     if (row >= M) return;                                  // whole wave exits together
@@ -82,7 +85,8 @@ __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
         seed = gp->seed;
         row_base = gp->row_base;
     }
-    const float* lrow = logits + (size_t)row * ldl;
+    const int lr = PERIOD ? row % period : row;
+    const float* lrow = logits + (size_t)lr * ldl;
 
     float4 x[NV4];
 #pragma unroll
@@ -173,12 +177,13 @@ constexpr int KT_MAX = 8;                                  // top-k served by sa
 // SLOTS (pmhip_sample_rows_slots): the per-call scalars of row r come from slots[r / tokens] -- one wave owns a row, so they are
 // wave-uniform like the kernel arguments they replace -- and everything below the prologue is the code of the scalar form.  The
 // scalar instantiations compile the prologue away: they gain neither a load nor a branch.
-template <int NB2, bool DENSE, bool SLOTS = false>
+// PERIOD: as in sample_rows_kernel -- the logits AND the statistics of row r are those of row r % period.
+template <int NB2, bool DENSE, bool SLOTS = false, bool PERIOD = false>
 __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
     const float* __restrict__ logits, int ldl, const float2* __restrict__ stats, const int64_t* __restrict__ ids_in, int64_t mask_id,
     int topk, float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
-    const PmGenParams* __restrict__ gp, const pmhip_slot* __restrict__ slots, int tokens) {
+    const PmGenParams* __restrict__ gp, const pmhip_slot* __restrict__ slots, int tokens, int period) {
     __shared__ float2 sh[DENSE ? THREADS / 64 : 1][DENSE ? NB2 * 64 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * (THREADS / 64) + wave;
@@ -206,7 +211,8 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
         seed = gp->seed;
         row_base = gp->row_base;
     }
-    const float* lrow = logits + (size_t)row * ldl;
+    const int lr = PERIOD ? row % period : row;
+    const float* lrow = logits + (size_t)lr * ldl;
     const int nblk = V >> 6;
 
     float2 st[NB2];
@@ -235,7 +241,7 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
             st[j] = b < nblk ? sh[wave][b] : make_float2(-INFINITY, 0.f);
         }
     } else {
-        const float2* srow = stats + (size_t)row * nblk;
+        const float2* srow = stats + (size_t)lr * nblk;
 #pragma unroll
         for (int j = 0; j < NB2; ++j) {
             const int b = lane + 64 * j;
@@ -442,8 +448,9 @@ __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict
 
 int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id, int topk,
                    float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base, int64_t* pred_out,
-                   int64_t* ids_out, float* score_out, int M, int V, const PmGenParams* gp, pmhip_stream stream) {
+                   int64_t* ids_out, float* score_out, int M, int V, const PmGenParams* gp, int period, pmhip_stream stream) {
     PM_REQUIRE(logits && ids_in && ids_out, "sample_rows: null pointer");
+    PM_REQUIRE(period >= 0, "sample_rows: negative logits row period %d", period);
     PM_REQUIRE(M > 0 && V > 0 && V % 4 == 0 && ldl % 4 == 0 && ldl >= V, "sample_rows: bad shape M=%d V=%d ldl=%d", M, V, ldl);
     PM_REQUIRE(topk >= 1 && topk <= 64 && topk <= V, "sample_rows: topk=%d must be in [1, min(64,V)]", topk);
     PM_REQUIRE(V <= 16384, "sample_rows: V=%d > 16384 unsupported", V);
@@ -455,28 +462,38 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const
     static const int g_tiles = pm_dev_knob("PMHIP_SAMPLE_TILES", 1);     // 0: the one-read row kernel everywhere (A/B)
     if (g_tiles && topk <= KT_MAX && V % 64 == 0) {
         const float2* st = reinterpret_cast<const float2*>(block_stats);
+#define PM_TILES_AS(NB2, DENSE, PER)                                                                                         \
+    hipLaunchKernelGGL((sample_tiles_kernel<NB2, DENSE, false, PER>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, topk, \
+                       temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, nullptr, 0, period)
 #define PM_TILES(NB2)                                                                                                         \
     do {                                                                                                                      \
-        if (st) hipLaunchKernelGGL((sample_tiles_kernel<NB2, false>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, topk, \
-                                   temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, nullptr, 0); \
-        else hipLaunchKernelGGL((sample_tiles_kernel<NB2, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, topk,   \
-                                temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, nullptr, 0); \
+        if (st && period) PM_TILES_AS(NB2, false, true);                                                                      \
+        else if (st) PM_TILES_AS(NB2, false, false);                                                                          \
+        else if (period) PM_TILES_AS(NB2, true, true);                                                                        \
+        else PM_TILES_AS(NB2, true, false);                                                                                   \
     } while (0)
         if (V <= 4096) PM_TILES(1);
         else if (V <= 8192) PM_TILES(2);
         else PM_TILES(4);
 #undef PM_TILES
+#undef PM_TILES_AS
         PM_HIP(hipGetLastError());
         return PMHIP_OK;
     }
-#define PM_SAMPLE(NV4)                                                                                              \
-    hipLaunchKernelGGL((sample_rows_kernel<NV4>), grid, block, 0, s, logits, ldl, ids_in, mask_id, topk, temperature, \
-                       noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp)
+#define PM_SAMPLE_AS(NV4, PER)                                                                                           \
+    hipLaunchKernelGGL((sample_rows_kernel<NV4, PER>), grid, block, 0, s, logits, ldl, ids_in, mask_id, topk, temperature, \
+                       noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, period)
+#define PM_SAMPLE(NV4)                    \
+    do {                                  \
+        if (period) PM_SAMPLE_AS(NV4, true); \
+        else PM_SAMPLE_AS(NV4, false);    \
+    } while (0)
     if (V <= 256) PM_SAMPLE(1);
     else if (V <= 1024) PM_SAMPLE(4);
     else if (V <= 8192) PM_SAMPLE(32);
     else PM_SAMPLE(64);
 #undef PM_SAMPLE
+#undef PM_SAMPLE_AS
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
 }
@@ -486,7 +503,7 @@ extern "C" int pmhip_sample_rows(const float* logits, int ldl, const int64_t* id
                                  uint64_t row_base, int64_t* pred_out, int64_t* ids_out, float* score_out, int M,
                                  int V, pmhip_stream stream) {
     return pm_sample_rows(logits, ldl, nullptr, ids_in, mask_id, topk, temperature, noise, seed, step, row_base, pred_out, ids_out,
-                          score_out, M, V, nullptr, stream);
+                          score_out, M, V, nullptr, 0, stream);
 }
 
 // the same step with the block statistics pmhip_gemm_softmax_stats (or pmhip_guidance_combine_stats) left behind: [M][V/64][2]
@@ -497,7 +514,7 @@ extern "C" int pmhip_sample_rows_stats(const float* logits, int ldl, const float
     PM_REQUIRE(block_stats, "sample_rows_stats: null statistics");
     PM_REQUIRE(V % 64 == 0, "sample_rows_stats: V=%d must be a multiple of 64", V);
     return pm_sample_rows(logits, ldl, block_stats, ids_in, mask_id, topk, temperature, noise, seed, step, row_base, pred_out, ids_out,
-                          score_out, M, V, nullptr, stream);
+                          score_out, M, V, nullptr, 0, stream);
 }
 
 // the per-image form: the block-statistics kernel only (what every decode-loop launch runs), every scalar from slots[row / tokens]
@@ -515,9 +532,9 @@ int pm_sample_rows_slots(const float* logits, int ldl, const float* block_stats,
 #define PM_TILES(NB2)                                                                                                          \
     do {                                                                                                                       \
         if (st) hipLaunchKernelGGL((sample_tiles_kernel<NB2, false, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, 0, 0.f, \
-                                   nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens);              \
+                                   nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens, 0);              \
         else hipLaunchKernelGGL((sample_tiles_kernel<NB2, true, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, 0, 0.f, \
-                                nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens);                 \
+                                nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens, 0);                 \
     } while (0)
     if (V <= 4096) PM_TILES(1);
     else if (V <= 8192) PM_TILES(2);

@@ -212,6 +212,13 @@ class S2Engine:
         """the PMHIP_* switches this handle latched when it was created (they are not re-read: include/pmhip.h)"""
         return _switch_dict(self.lib.pmhip_s2_switches(self.handle))
 
+    def step0_shared(self):
+        """(fills, hits) of this handle's shared step-0 logits (pmhip_s2_step0_shared): computed 0 or 1 times, sampled from by
+        `hits` later unconditional loops that ran no step-0 tower"""
+        fills, hits = C.c_int(0), C.c_int(0)
+        check(self.lib.pmhip_s2_step0_shared(self.handle, C.byref(fills), C.byref(hits)), "pmhip_s2_step0_shared")
+        return fills.value, hits.value
+
     def __init__(self, transformer, codebook, mask_token, dtype):
         self.lib = _lib.load()
         dev = next(transformer.parameters()).device
@@ -337,14 +344,16 @@ class S2Engine:
         return ids, pred, score
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
-                 host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False):
+                 host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
 
         host = (pinned float32 tensor [n_decoded, B_total, C, H, W], first row of this batch, copy stream): every decoded
         image is copied into its rows on the copy stream as soon as it is complete (the reference's `img.cpu()`,
         generate.py:195-196); the caller synchronises that stream.
         concurrent_lanes: other micro-batches run beside this call on other streams (PMHIP_GENERATE_CONCURRENT_LANES: the loop
-        then does not put a small batch's decode on a side stream of its own)."""
+        then does not put a small batch's decode on a side stream of its own).
+        from_mask: the loop starts from the all-mask state (PMHIP_GENERATE_FROM_MASK): the native call writes that state itself --
+        what `ids` holds on entry is ignored -- and an unconditional loop samples its step 0 from the handle's shared logits."""
         B = ids.shape[0]
         T = len(temps)
         context, L = self._ctx(context)
@@ -366,7 +375,9 @@ class S2Engine:
         nmask_c = (C.c_int * T)(*[int(n) for n in nmask])
         dec_c = (C.c_ubyte * T)(*[1 if f else 0 for f in decode_flags])
         args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, T,
-                temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), (1 if use_graph else 0) | (2 if concurrent_lanes else 0),
+                temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs),
+                (_lib.GENERATE_GRAPH if use_graph else 0) | (_lib.GENERATE_CONCURRENT_LANES if concurrent_lanes else 0) |
+                (_lib.GENERATE_FROM_MASK if from_mask else 0),
                 stream_ptr(self.device), host_ptr, host_stride, copy_stream)
         with torch.cuda.device(self.device):
             if guidance_scale is None:

@@ -375,7 +375,10 @@ class Pipeline(nn.Module):
         host = (pinned [n_decoded, B, C, H, W] float32 tensor, [copy stream per lane]): the decoded images go straight to
         the host buffer (every lane fills its rows, each image as soon as it is complete, on its own copy stream); no
         device image tensor is returned.
-        ids0 (streams = 1 only): start from these ids [B, N] int64 instead of the all-mask state (the region loops of inpaint / outpaint)."""
+        ids0 (streams = 1 only): start from these ids [B, N] int64 instead of the all-mask state (the region loops of inpaint / outpaint).
+        Without ids0 the native loop is told that it starts from the all-mask state (from_mask): an unconditional loop then samples
+        its step 0 from logits the handle computed once (include/pmhip.h, PMHIP_GENERATE_FROM_MASK) -- same result, bit for bit,
+        as passing an explicit all-mask ids0, which keeps the full path."""
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
@@ -402,7 +405,7 @@ class Pipeline(nn.Module):
             return eng.generate(self.vqgan.engine(), ids, context, temps, nmask, decode_flags, topk, seed=seed,
                                 image_base=image_base, use_graph=use_graph,
                                 host=None if host is None else (host[0], 0, host[1][0]), want_device_imgs=host is None,
-                                guidance_scale=guidance_scale)
+                                guidance_scale=guidance_scale, from_mask=ids0 is None)
         from .dist import shard_range
         cur = torch.cuda.current_stream(eng.device)
         if wait_current:
@@ -418,7 +421,8 @@ class Pipeline(nn.Module):
                 c = None if context is None else context[lo:hi].contiguous()
                 ids, imgs = e.generate(v, ids, c, temps, nmask, decode_flags, topk, seed=seed, image_base=image_base + lo,
                                        use_graph=use_graph, host=None if host is None else (host[0], lo, host[1][i]),
-                                       want_device_imgs=host is None, guidance_scale=guidance_scale, concurrent_lanes=True)
+                                       want_device_imgs=host is None, guidance_scale=guidance_scale, concurrent_lanes=True,
+                                       from_mask=True)          # lanes exist for ids0 None only (checked above)
             return ids, imgs, st
 
         lanes = self._lanes(streams)
