@@ -17,6 +17,27 @@
  *   - matrices are row-major; "T" below is the handle's compute dtype (PMHIP_F32 or PMHIP_BF16);
  *     weights are stored [out_features, in_features] exactly like torch.nn.Linear
  *   - GEMM reduction widths (K) must be multiples of 64 elements; the host packer zero-pads
+ *
+ * Memory contract (tests/test_gpu_abi_memory.py holds every operator to it)
+ *   - leading dimensions (lda, ldw, ldr, ldo, ldl) count ELEMENTS between the starts of consecutive rows and may be wider than
+ *     the row: the gap is never written and what it holds (NaN included) never reaches a result.  Lower bounds, checked
+ *     (PMHIP_EINVAL, the message names the argument):
+ *         lda >= K, ldw >= K          every GEMM entry point (and both multiples of 8)
+ *         ldo >= N, ldr >= N          pmhip_gemm / _ln / _softmax_stats (ldr only with a residual), pmhip_gemm_hilo / _stats / _center
+ *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
+ *         ldo >= heads * dim_head     pmhip_attention / _dh
+ *         ldl >= V                    pmhip_sample_rows / _stats / _slots, pmhip_masked_ce
+ *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
+ *     N * ldw stay below 2^30 elements; beyond that another kernel may serve the call).
+ *   - an output of [M, N] is written in exactly its M x N elements, however ragged M and N are against a kernel's tile; arrays
+ *     without a leading dimension (row_stats, block_stats, coef, shift, pred, ids, score, ...) in exactly their stated extent
+ *   - in place is allowed where an entry point says so, and only there:
+ *         pmhip_gemm_hilo / _stats / _center   out_hi == res_hi and out_lo == res_lo with ldo == ldr, the residual being the
+ *                                              stream itself (res_rows <= 0 or >= M: no row modulo)
+ *         pmhip_gemm with an f32 residual      out == residual with ldo == ldr, res_rows covering all M rows
+ *         pmhip_unshift_hilo, pmhip_remask(_slots), pmhip_guidance_combine(_stats), pmhip_sample_rows* (ids_out == ids_in)
+ *     Every element is read by the workgroup that writes it, before it writes it; the result equals the out-of-place call's bit
+ *     for bit.  Any other overlap between an output and an input is undefined.
  */
 #ifndef PMHIP_H
 #define PMHIP_H
@@ -51,7 +72,8 @@ int pmhip_device_info(int device, int* cu_count, int* lds_bytes, char* arch, int
  * (modules/attention.py:46-49,59; stage1/vqmodel.py:23,28; stage1/layers.py:149;
  * stage2/transformer.py:81,85,91).  A, W are `dtype`; bias/residual fp32 or NULL; out is
  * `out_dtype`.  res_rows lets one [tokens, N] table (a position embedding,
- * stage1/layers.py:108,146, stage2/transformer.py:82) be added to every image. */
+ * stage1/layers.py:108,146, stage2/transformer.py:82) be added to every image.  lda, ldw >= K; ldo >= N; with a residual
+ * ldr >= N, and out may BE the residual (ldo == ldr, res_rows <= 0 or >= M): the fp32 stream updated in place. */
 int pmhip_gemm(int dtype, const void* A, int lda, const void* W, int ldw, const float* bias,
                const float* residual, int ldr, int res_rows, void* out, int ldo, int out_dtype,
                int M, int N, int K, pmhip_stream stream);
@@ -64,7 +86,9 @@ int pmhip_gemm_swiglu(int dtype, const void* A, int lda, const void* W12p, const
 
 /* Head-split projection (modules/attention.py:46-52): A[M,K] . W[nparts*inner,K]^T, no bias,
  * written per part as  Q -> [B,H,tokens,64] * q_scale ;  K -> [B,H,tokens_pad,64] ;
- * V -> transposed [B,H,64,tokens_pad].  M = B*tokens, inner = heads*64 (dim_head is 64). */
+ * V -> transposed [B,H,64,tokens_pad].  M = B*tokens, inner = heads*64 (dim_head is 64).
+ * The padding [tokens, tokens_pad) of K (rows) and V^T (columns) is left UNTOUCHED by every kernel that serves this entry point
+ * (and by pmhip_gemm_heads_ln / _dh): what the caller put there stays there.  pmhip_attention never uses it (NaN included). */
 int pmhip_gemm_heads(int dtype, const void* A, int lda, const void* W, int ldw, int M, int K,
                      int heads, int tokens, int tokens_pad, int nparts, const int* part_kinds_host,
                      void* const* part_outs_host, float q_scale, pmhip_stream stream);
@@ -82,7 +106,8 @@ int pmhip_gemm_heads(int dtype, const void* A, int lda, const void* W, int ldw, 
  * pmhip_ln_coef, which reads the hi plane only.  Deterministic: no atomics. */
 
 /* (hi, lo) <- split(A[M,K] . W[N,K]^T + bias + (res_hi + res_lo)[m % res_rows]); bf16 operands.  In place when the output
- * planes are the residual planes.  N, ldr, ldo multiples of 8. */
+ * planes are the residual planes (out_hi == res_hi, out_lo == res_lo, ldo == ldr, no row modulo; see the memory contract above).
+ * N, ldr, ldo multiples of 8; ldr >= N, ldo >= N. */
 int pmhip_gemm_hilo(const void* A, int lda, const void* W, int ldw, const float* bias, const void* res_hi,
                     const void* res_lo, int ldr, int res_rows, void* out_hi, void* out_lo, int ldo, int M, int N,
                     int K, pmhip_stream stream);

@@ -506,6 +506,7 @@ extern "C" int pmhip_attention(int dtype, const void* Q, const void* K, const vo
     PM_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0, "attention: empty problem");
     PM_REQUIRE(Nkv_pad % KT == 0 && Nkv_pad >= Nkv, "attention: Nkv_pad=%d must be a multiple of 64 >= Nkv=%d", Nkv_pad, Nkv);
     PM_REQUIRE(ldo % 4 == 0 && (dtype == PMHIP_F32 || ldo % 8 == 0), "attention: ldo must be a multiple of 4 (f32) / 8 (bf16: 16-byte row stores)");
+    PM_REQUIRE(ldo >= heads * DH, "attention: ldo=%d is smaller than heads*64=%d (rows of out would overlap)", ldo, heads * DH);
     hipStream_t s = (hipStream_t)stream;
     dim3 block(THREADS);
     PmTimer tm(FAM_ATTENTION, s);

@@ -152,6 +152,7 @@ extern "C" int pmhip_attention_dh(int dtype, const void* Q, const void* K, const
     PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "attention_dh: bad dtype %d", dtype);
     PM_REQUIRE(Q && K && Vt && out, "attention_dh: null pointer");
     PM_REQUIRE(B > 0 && Nq > 0 && Nkv > 0 && Nkv_pad >= Nkv, "attention_dh: empty problem");
+    PM_REQUIRE(ldo >= heads * dim_head, "attention_dh: ldo=%d is smaller than heads*dim_head=%d (rows of out would overlap)", ldo, heads * dim_head);
     PM_REQUIRE((long long)B * heads <= 65535, "attention_dh: B*heads=%lld exceeds the grid's y range", (long long)B * heads);
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_ATTENTION, s);

@@ -306,6 +306,8 @@ int check_common(const GemmParams& p, int dtype) {
     PM_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
     PM_REQUIRE(p.K % 64 == 0, "gemm: K=%d must be a multiple of 64 (pad on the host)", p.K);
     PM_REQUIRE(p.lda % 8 == 0 && p.ldw % 8 == 0, "gemm: lda/ldw must be multiples of 8 elements");
+    PM_REQUIRE(p.lda >= p.K, "gemm: lda=%d is smaller than K=%d (rows of A would overlap)", p.lda, p.K);
+    PM_REQUIRE(p.ldw >= p.K, "gemm: ldw=%d is smaller than K=%d (rows of W would overlap)", p.ldw, p.K);
     PM_REQUIRE(p.A && p.W, "gemm: null operand");
     return PMHIP_OK;
 }
@@ -368,7 +370,9 @@ int gemm_impl(int dtype, const void* A, int lda, const void* W, int ldw, const f
     PM_TRY(check_common(p, dtype));
     PM_REQUIRE(out, "gemm: null out");
     PM_REQUIRE(N % 4 == 0 && ldo % 4 == 0, "gemm: N=%d and ldo=%d must be multiples of 4", N, ldo);
+    PM_REQUIRE(ldo >= N, "gemm: ldo=%d is smaller than N=%d (rows of out would overlap)", ldo, N);
     PM_REQUIRE(!residual || ldr % 4 == 0, "gemm: ldr must be a multiple of 4");
+    PM_REQUIRE(!residual || ldr >= N, "gemm: ldr=%d is smaller than N=%d (rows of the residual would overlap)", ldr, N);
     PM_REQUIRE(!residual || out_dtype == PMHIP_F32, "gemm: a residual needs an f32 output (the residual stream is f32)");
     PM_REQUIRE(out_dtype == PMHIP_F32 || out_dtype == dtype, "gemm: out dtype must be f32 or the compute dtype");
     PM_REQUIRE(out_dtype == PMHIP_F32 || ldo % 8 == 0, "gemm: bf16 output needs ldo to be a multiple of 8");
@@ -402,6 +406,8 @@ static int gemm_hilo_impl(const void* A, int lda, const void* W, int ldw, const 
     PM_TRY(check_common(p, PMHIP_BF16));
     PM_REQUIRE(res_hi && res_lo && out_hi && out_lo, "gemm_hilo: null plane");
     PM_REQUIRE(N % 8 == 0 && ldo % 8 == 0 && ldr % 8 == 0, "gemm_hilo: N=%d, ldo=%d, ldr=%d must be multiples of 8", N, ldo, ldr);
+    PM_REQUIRE(ldo >= N, "gemm_hilo: ldo=%d is smaller than N=%d (rows of the output planes would overlap)", ldo, N);
+    PM_REQUIRE(ldr >= N, "gemm_hilo: ldr=%d is smaller than N=%d (rows of the residual planes would overlap)", ldr, N);
     PM_REQUIRE(!row_stats || N % 64 == 0, "gemm_hilo_stats: N=%d must be a multiple of 64", N);
     return dispatch<EPI_STD>(p, PMHIP_BF16, PMHIP_BF16, nullptr, stream);
 }
@@ -456,6 +462,7 @@ static int gemm_swiglu_impl(int dtype, const void* A, int lda, const void* W12p,
     PM_TRY(check_common(p, dtype));
     PM_REQUIRE(Hp % 64 == 0, "gemm_swiglu: padded hidden width %d must be a multiple of 64", Hp);
     PM_REQUIRE(b12p && out && ldo % 8 == 0, "gemm_swiglu: bias/out required, ldo multiple of 8");
+    PM_REQUIRE(ldo >= Hp, "gemm_swiglu: ldo=%d is smaller than Hp=%d (rows of out would overlap)", ldo, Hp);
     return dispatch<EPI_SWIGLU>(p, dtype, dtype, ln, stream);
 }
 

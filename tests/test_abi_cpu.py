@@ -35,6 +35,43 @@ def test_errors_are_reported_not_thrown():
     assert rc == 1
 
 
+def test_undersized_leading_dimensions_are_rejected():
+    """A leading dimension smaller than the row it strides over would make rows overlap silently: every entry point that takes one
+    answers PMHIP_EINVAL and names the argument.  The checks return before anything is launched, so dummy pointers do."""
+    import ctypes as C
+    lib = _lib.load()
+    p = C.c_void_p(256)
+    F32, BF16 = _lib.F32, _lib.BF16
+
+    def rejected(rc, name):
+        msg = lib.pmhip_last_error()
+        assert rc == _lib.PMHIP_EINVAL and name.encode() in msg and b"smaller" in msg, (rc, msg)
+
+    # check_common: lda / ldw against K, through every entry point that ends there
+    rejected(lib.pmhip_gemm(F32, p, 64, p, 128, None, None, 0, 0, p, 128, F32, 128, 128, 128, None), "lda")
+    rejected(lib.pmhip_gemm(F32, p, 128, p, 64, None, None, 0, 0, p, 128, F32, 128, 128, 128, None), "ldw")
+    rejected(lib.pmhip_gemm_swiglu(BF16, p, 64, p, p, p, 64, 128, 64, 128, None), "lda")
+    kinds, outs = (C.c_int * 1)(_lib.PART_Q), (C.c_void_p * 1)(256)
+    rejected(lib.pmhip_gemm_heads(BF16, p, 128, p, 64, 128, 128, 2, 128, 128, 1, kinds, outs, 1.0, None), "ldw")
+    rejected(lib.pmhip_gemm_hilo(p, 64, p, 128, None, p, p, 128, 0, p, p, 128, 128, 128, 128, None), "lda")
+    # the plain GEMM: ldo, and ldr only with a residual
+    rejected(lib.pmhip_gemm(F32, p, 128, p, 128, None, None, 0, 0, p, 64, F32, 128, 128, 128, None), "ldo")
+    rejected(lib.pmhip_gemm(F32, p, 128, p, 128, None, p, 64, 0, p, 128, F32, 128, 128, 128, None), "ldr")
+    rejected(lib.pmhip_gemm_softmax_stats(F32, p, 128, p, 128, None, p, 64, 128, 128, 128, None, p, None), "ldo")
+    # the pair producers
+    rejected(lib.pmhip_gemm_hilo(p, 128, p, 128, None, p, p, 128, 0, p, p, 64, 128, 128, 128, None), "ldo")
+    rejected(lib.pmhip_gemm_hilo(p, 128, p, 128, None, p, p, 64, 0, p, p, 128, 128, 128, 128, None), "ldr")
+    rejected(lib.pmhip_gemm_hilo_stats(p, 128, p, 128, None, p, p, 128, 0, p, p, 64, 128, 128, 128, p, None), "ldo")
+    rejected(lib.pmhip_gemm_hilo_center(p, 128, p, 128, None, p, p, 64, 0, p, p, 128, 128, 128, 128, None, None, 0.0, None, 0, None),
+             "ldr")
+    # SwiGLU: ldo against the padded hidden width
+    rejected(lib.pmhip_gemm_swiglu(BF16, p, 128, p, p, p, 64, 128, 128, 128, None), "ldo")
+    # attention: ldo against heads * dim_head
+    rejected(lib.pmhip_attention(BF16, p, p, p, p, 64, 1, 2, 64, 64, 64, 1, None), "ldo")
+    rejected(lib.pmhip_attention_dh(BF16, p, p, p, p, 64, 1, 4, 32, 64, 64, 64, 1, None), "ldo")
+    rejected(lib.pmhip_attention_dh(BF16, p, p, p, p, 64, 1, 2, 64, 64, 64, 64, 1, None), "ldo")      # forwards to pmhip_attention
+
+
 def test_hip_operators_have_no_cpu_fallback():
     """The HIP operators never compute on the CPU: a CPU tensor handed to one raises.  (A MODULE that lives on the CPU is a
     different matter: it runs this package's own plain-torch branch, like the reference runs on whatever device the module is

@@ -155,7 +155,8 @@ def test_gemm_hilo_row_statistics_and_coefficients(M, N, K):
                                          (2048, 512, 64, 1024),         # 128x128 kernel, position-embedding addend (row modulo)
                                          (200, 768, 192, 0)])           # ragged M
 def test_gemm_hilo_residual_stream(M, N, K, rows):
-    """(hi, lo) <- split(A W^T + bias + (hi + lo)): every kernel route, against float64; in place like the engine uses it"""
+    """(hi, lo) <- split(A W^T + bias + (hi + lo)): every kernel route, against float64.  Fresh output planes here; in place, the
+    way the engine runs it, is tests/test_gpu_abi_memory.py::test_gemm_hilo_pair (bit-identical to this form, on every route)."""
     bf = torch.bfloat16
     a, w, b0 = bf16_round(rnd(M, K)), bf16_round(rnd(N, K, scale=K ** -0.5)), rnd(N)
     R = rows or M
