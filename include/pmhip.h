@@ -36,6 +36,7 @@
  *                                              stream itself (res_rows <= 0 or >= M: no row modulo)
  *         pmhip_gemm with an f32 residual      out == residual with ldo == ldr, res_rows covering all M rows
  *         pmhip_unshift_hilo, pmhip_remask(_slots), pmhip_guidance_combine(_stats), pmhip_sample_rows* (ids_out == ids_in)
+ *         pmhip_guidance_combine_slots         out == cond (or uncond)
  *     Every element is read by the workgroup that writes it, before it writes it; the result equals the out-of-place call's bit
  *     for bit.  Any other overlap between an output and an input is undefined.
  */
@@ -332,6 +333,20 @@ int pmhip_sample_rows_slots(const float* logits, int ldl, const float* block_sta
 int pmhip_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id,
                        int B, int N, pmhip_stream stream);
 
+/* Per-image GUIDANCE: a record parallel to pmhip_slot, which stays 32 bytes; the ABI version stays 11 (new entries only). */
+typedef struct pmhip_slot_guide { float scale; uint32_t on; } pmhip_slot_guide;   /* 8 bytes, one per image; on = 0: not guided */
+
+/* pmhip_guidance_combine(_stats) per image: cond / uncond / out fp32 [M, V] with contiguous rows, M = B * tokens, guides and slots
+ * DEVICE arrays [B].  For an image that is active (bit 31 of slots[b].step clear) and has guides[b].on != 0, every row becomes
+ * fmaf(scale_b, cond - uncond, uncond) and -- block_stats [M][V/64][2] given -- its block statistics are written: the same
+ * per-element and per-block arithmetic in the same lane layout, so those rows equal, bit for bit, pmhip_guidance_combine(_stats)
+ * called on that image alone with its scale.  The rows of an idle or unguided image are NEITHER READ NOR WRITTEN, in `out` and in
+ * `block_stats`: in place on the cond tower's logits and statistics they stay the unguided step's inputs.  out may alias cond (or
+ * uncond).  V % 64 == 0, M % tokens == 0; null pointers and bad shapes are PMHIP_EINVAL before anything is launched. */
+int pmhip_guidance_combine_slots(const float* cond, const float* uncond, const pmhip_slot_guide* guides,
+                                 const pmhip_slot* slots, int tokens, float* out, float* block_stats /* or NULL */,
+                                 int M, int V, pmhip_stream stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Model level.  Weight tables are filled by the host packer (paintmind_amd/engine.py) from the
  * reference's state_dict layout.
@@ -522,6 +537,20 @@ int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, 
                               const pmhip_slot* slots_host, int flags,
                               int64_t* pred_out, float* score_out, pmhip_stream stream);
 
+/* The same step with per-image GUIDANCE: guides_host[B] (HOST records, may be NULL) travel beside the slot records through the
+ * same pinned ring.  An active slot with on != 0 samples from uncond + scale * (cond - uncond) like pmhip_pipeline_sample_guided
+ * with its own scale; it needs a finite scale and a context (L > 0, also under PMHIP_SLOTS_KEEP_CONTEXT), otherwise PMHIP_EINVAL
+ * ("guidance needs a context") and nothing runs.  guides_host == NULL, or no ACTIVE slot guided: exactly
+ * pmhip_pipeline_step_slots -- one tower pass, the same graph.  Otherwise a linear chain: the tower with the context (the logits
+ * GEMM leaves the block statistics), the tower without it, pmhip_guidance_combine_slots in place on the first tower's logits and
+ * statistics, the slots sampling tail.  An unguided slot beside a guided one keeps the first tower's rows untouched, so it
+ * computes what it computes in pmhip_pipeline_step_slots, bit for bit; it still runs through the second tower (no compaction).
+ * PMHIP_SLOTS_GRAPH: that chain is captured once per (B, L) under a key of its own; the scales are read from device memory, so
+ * one graph serves every mix of scales.  Ignored when pmhip_pipeline_step_slots ignores it. */
+int pmhip_pipeline_step_slots_guided(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                     const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, int flags,
+                                     int64_t* pred_out, float* score_out, pmhip_stream stream);
+
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return
  * what a handle latched: bit 0 LayerNorm fold (PMHIP_LN_UNFOLD unset), bit 1 bf16 hi/lo stream (PMHIP_HILO != 0), bit 2 row
@@ -533,6 +562,9 @@ int pmhip_vqgan_switches(const pmhip_vqgan* h);
 /* The shared step 0 (PMHIP_GENERATE_FROM_MASK): *fills = how often this handle computed it (0 or 1), *hits = how many loops
  * sampled their step 0 from it without running a tower.  Either pointer may be NULL. */
 int pmhip_s2_step0_shared(const pmhip_s2* h, int* fills, int* hits);
+/* Slots steps this handle ran (both slots entries), by tower passes: *one_pass without guidance, *two_pass with at least one
+ * active guided slot.  Either pointer may be NULL. */
+int pmhip_s2_slots_steps(const pmhip_s2* h, int* one_pass, int* two_pass);
 
 /* Per-kernel timing hook used by bench.py: when enabled, every kernel launch of the named family
  * is bracketed by hipEvents on its own stream and accumulated (count, total ms). */

@@ -73,6 +73,11 @@ class Slot(C.Structure):
     _fields_ = [("seed", u64), ("image_index", u64), ("temperature", f32), ("topk", i32), ("num_mask", i32), ("step", u32)]
 
 
+class SlotGuide(C.Structure):
+    """mirror of pmhip_slot_guide: the guidance of one image of a batch (8 bytes; on = 0: not guided)"""
+    _fields_ = [("scale", f32), ("on", u32)]
+
+
 # name -> (restype, argtypes); every symbol include/pmhip.h declares
 PROTOTYPES = {
     "pmhip_abi_version": (i32, []),
@@ -122,6 +127,8 @@ PROTOTYPES = {
     "pmhip_sample_rows_slots": (i32, [vp, i32, vp, vp, i64, vp, i32, vp, vp, vp, i32, i32, vp]),
     "pmhip_remask_slots": (i32, [vp, vp, vp, i64, i32, i32, vp]),
     "pmhip_pipeline_step_slots": (i32, [vp, vp, vp, i32, i32, C.POINTER(Slot), i32, vp, vp, vp]),
+    "pmhip_guidance_combine_slots": (i32, [vp, vp, vp, vp, i32, vp, vp, i32, i32, vp]),
+    "pmhip_pipeline_step_slots_guided": (i32, [vp, vp, vp, i32, i32, C.POINTER(Slot), C.POINTER(SlotGuide), i32, vp, vp, vp]),
     "pmhip_vqgan_create": (i32, [C.POINTER(vp), i32, i32, C.POINTER(VqganCfg), C.POINTER(VqganWeights)]),
     "pmhip_vqgan_destroy": (None, [vp]),
     "pmhip_vqgan_encode": (i32, [vp, vp, i32, vp, vp, vp, vp]),
@@ -141,6 +148,7 @@ PROTOTYPES = {
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+    "pmhip_s2_slots_steps": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

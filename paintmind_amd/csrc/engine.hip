@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <atomic>
 #include <map>
 #include <memory>
@@ -698,8 +699,12 @@ struct pmhip_s2 {
     // per-image decode state (pmhip_pipeline_step_slots): the host records travel through a pinned ring of their own (kParamSlots
     // entries of slots_cap records; an entry is reused only after the copy that read it has completed), and the handle remembers
     // which context the last slots call prepared (slots_ctx_L: 0 = prepared without a context, -1 = nothing a slots call may reuse)
+    // (a call with guidance stages its pmhip_slot_guide records through the same ring: entry e of guides_host travels with entry e of
+    // slots_host and is guarded by the same event; slots_one_pass / slots_two_pass count the steps by tower passes)
     pmhip_slot* slots_host = nullptr;
+    pmhip_slot_guide* guides_host = nullptr;
     int slots_cap = 0;
+    int slots_one_pass = 0, slots_two_pass = 0;
     hipEvent_t slots_done[kParamSlots] = {};
     int slots_next = 0;
     int slots_ctx_B = 0, slots_ctx_L = -1;
@@ -723,6 +728,7 @@ struct pmhip_s2 {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (params_host) (void)hipHostFree(params_host);
         if (slots_host) (void)hipHostFree(slots_host);
+        if (guides_host) (void)hipHostFree(guides_host);
         for (auto e : slots_done)
             if (e) (void)hipEventDestroy(e);
         for (auto e : params_done)
@@ -872,6 +878,23 @@ int step_tower(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s, const flo
         else PM_TRY(pmhip_guidance_combine(logits, uncond, *guidance, logits, (size_t)M * c.n_embed, s));
     }
     return PMHIP_OK;
+}
+
+// step_tower with per-image guidance (pmhip_pipeline_step_slots_guided): BOTH towers for the whole batch, the first one with the
+// logits GEMM's block statistics (the same logits as without them, bit for bit: tests/test_gpu_abi_memory.py), then the combination
+// in place on the rows of the guided images only -- an unguided image keeps the first tower's logits and statistics, i.e. exactly
+// what step_tower leaves for it
+int step_tower_guided_slots(pmhip_s2* s2, const int64_t* ids, int B, const pmhip_slot* slots, const pmhip_slot_guide* guides, hipStream_t s) {
+    const auto& c = s2->cfg;
+    const int M = B * c.tokens;
+    void* tp; float* logits; float* lstats; float* uncond;
+    WS(s2->ws, "s2.tok", (size_t)M * 64 * dtype_size(s2->dtype), tp);
+    PM_TRY(step_bufs(s2, M, logits, lstats, s));
+    WS(s2->ws, "s2.logits_u", (size_t)M * c.n_embed * 4, uncond);
+    PM_TRY(pmhip_embed_rows(s2->w.tok_table, ids, tp, s2->dtype, 64, M, c.n_embed + 1, c.embed_dim, s));
+    PM_TRY(s2_tower(s2, tp, B, logits, s, true, lstats));
+    PM_TRY(s2_tower(s2, tp, B, uncond, s, false));
+    return pmhip_guidance_combine_slots(logits, uncond, guides, slots, c.tokens, logits, lstats, M, c.n_embed, s);
 }
 
 // the image of the predictions the last step_tail left in the handle's `s2.pred` (decoded from pred at ALL positions, generate.py:165)
@@ -1258,21 +1281,31 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
 // through the pinned ring into the workspace, and read from there by the sampling and re-masking kernels; with the graph flag the
 // step -- tower, sampling, re-masking: one linear chain -- is captured once per (B, context length) on handle-owned ids and
 // replayed, whatever the records say.
-extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
-                                         int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    PM_REQUIRE(s2 && ids && slots_host && B > 0, "pipeline_step_slots: bad arguments (null handle, ids or slots, or B <= 0)");
+// guides_host (pmhip_pipeline_step_slots_guided; NULL otherwise): per-image guidance.  The host decides "two tower passes or one"
+// per STEP -- two exactly when an active slot is guided -- and the two-pass chain (step_tower_guided_slots + the same tail) has a
+// graph of its own; which rows the combination touches is decided on the device, from the staged records.
+static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
+                           const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
     const auto& c = s2->cfg;
-    PM_REQUIRE(c.n_embed % 64 == 0, "pipeline_step_slots: n_embed=%d must be a multiple of 64", c.n_embed);
+    PM_REQUIRE(c.n_embed % 64 == 0, "%s: n_embed=%d must be a multiple of 64", who, c.n_embed);
+    bool two_pass = false;
     for (int b = 0; b < B; ++b) {
         const pmhip_slot& sl = slots_host[b];
         if (sl.step & PM_SLOT_IDLE) continue;
-        PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "pipeline_step_slots: slot %d: topk=%d must be in [1, 8]", b, sl.topk);
-        PM_REQUIRE(sl.num_mask >= 1, "pipeline_step_slots: slot %d: num_mask=%d must be >= 1", b, sl.num_mask);
+        PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "%s: slot %d: topk=%d must be in [1, 8]", who, b, sl.topk);
+        PM_REQUIRE(sl.num_mask >= 1, "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
+        if (guides_host && guides_host[b].on) {
+            PM_REQUIRE(std::isfinite(guides_host[b].scale), "%s: slot %d: the guidance scale must be finite", who, b);
+            PM_REQUIRE(L > 0 && (context || (flags & PMHIP_SLOTS_KEEP_CONTEXT)),
+                       "%s: slot %d: guidance needs a context (context NULL IS the unconditional branch)", who, b);
+            two_pass = true;
+        }
     }
     hipStream_t s = (hipStream_t)stream;
     if (flags & PMHIP_SLOTS_KEEP_CONTEXT) {
         if (s2->slots_ctx_L < 0 || s2->slots_ctx_B != B || s2->slots_ctx_L != L) {
-            pm_set_error("pipeline_step_slots: keep-context asked for B=%d L=%d, but %s", B, L,
+            pm_set_error("%s: keep-context asked for B=%d L=%d, but %s", who, B, L,
                          s2->slots_ctx_L < 0 ? "no slots call has prepared a context on this handle (or another entry point replaced it)"
                                              : "the prepared context has another B or L");
             return PMHIP_ESTATE;
@@ -1289,13 +1322,17 @@ extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float
         for (auto e : s2->slots_done)
             if (e) PM_HIP(hipEventSynchronize(e));            // copies still reading the old ring
         if (s2->slots_host) { PM_HIP(hipHostFree(s2->slots_host)); s2->slots_host = nullptr; s2->slots_cap = 0; }
+        if (s2->guides_host) { PM_HIP(hipHostFree(s2->guides_host)); s2->guides_host = nullptr; }
         PM_HIP(hipHostMalloc((void**)&s2->slots_host, sizeof(pmhip_slot) * (size_t)B * pmhip_s2::kParamSlots, hipHostMallocDefault));
+        PM_HIP(hipHostMalloc((void**)&s2->guides_host, sizeof(pmhip_slot_guide) * (size_t)B * pmhip_s2::kParamSlots, hipHostMallocDefault));
         s2->slots_cap = B;
         for (auto& e : s2->slots_done)
             if (!e) PM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     pmhip_slot* dslots;
+    pmhip_slot_guide* dguides = nullptr;
     WS(s2->ws, "slots.dev", sizeof(pmhip_slot) * (size_t)B, dslots);
+    if (two_pass) WS(s2->ws, "slots.guides", sizeof(pmhip_slot_guide) * (size_t)B, dguides);
     {
         const int e = s2->slots_next;
         s2->slots_next = (e + 1) % pmhip_s2::kParamSlots;
@@ -1305,13 +1342,23 @@ extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float
         void* hp_dev = nullptr;                               // the pinned entry through its device alias
         PM_HIP(hipHostGetDevicePointer(&hp_dev, hp, 0));
         PM_TRY(copy16_async(dslots, hp_dev, sizeof(pmhip_slot) * (size_t)B, s));
+        if (two_pass) {
+            pmhip_slot_guide* gp = s2->guides_host + (size_t)e * s2->slots_cap;
+            memcpy(gp, guides_host, sizeof(pmhip_slot_guide) * (size_t)B);
+            PM_HIP(hipHostGetDevicePointer(&hp_dev, gp, 0));
+            PM_TRY(copy16_async(dguides, hp_dev, sizeof(pmhip_slot_guide) * (size_t)B, s));
+        }
         PM_HIP(hipEventRecord(s2->slots_done[e], s));
     }
+    ++(two_pass ? s2->slots_two_pass : s2->slots_one_pass);
+    auto tower = [&](const int64_t* from, hipStream_t on) -> int {
+        return two_pass ? step_tower_guided_slots(s2, from, B, dslots, dguides, on) : step_tower(s2, from, B, on, nullptr);
+    };
 
     // ignored exactly when pipeline_generate ignores its graph request (same bits either way)
     const bool graph = (flags & PMHIP_SLOTS_GRAPH) && !g_pm_timing_on.load() && !direct_dispatch_off();
     if (!graph) {
-        PM_TRY(step_tower(s2, ids, B, s, nullptr));
+        PM_TRY(tower(ids, s));
         return step_tail_slots(s2, ids, B, dslots, pred_out, score_out, s);
     }
 
@@ -1319,9 +1366,9 @@ extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float
     int64_t* gids;
     WS(s2->ws, "slots.ids", ids_bytes, gids);
     PM_TRY(copy16_async(gids, ids, ids_bytes, s));
-    GraphEntry& ge = s2->graphs["slotsB" + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key())];
+    GraphEntry& ge = s2->graphs[(two_pass ? "slotsguidedB" : "slotsB") + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key())];
     auto run_step = [&](hipStream_t on) -> int {
-        PM_TRY(step_tower(s2, gids, B, on, nullptr));
+        PM_TRY(tower(gids, on));
         return step_tail_slots(s2, gids, B, dslots, nullptr, nullptr, on);
     };
     if (!ge.warmed) {
@@ -1363,6 +1410,25 @@ extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float
         if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, M * 8, hipMemcpyDeviceToDevice, s));
         if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, M * 4, hipMemcpyDeviceToDevice, s));
     }
+    return PMHIP_OK;
+}
+
+extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
+                                         int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    return step_slots_impl("pipeline_step_slots", s2, ids, context, L, B, slots_host, nullptr, flags, pred_out, score_out, stream);
+}
+
+extern "C" int pmhip_pipeline_step_slots_guided(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
+                                                const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out,
+                                                pmhip_stream stream) {
+    return step_slots_impl("pipeline_step_slots_guided", s2, ids, context, L, B, slots_host, guides_host, flags, pred_out, score_out, stream);
+}
+
+// slots steps by tower passes: one (no active slot guided) / two
+extern "C" int pmhip_s2_slots_steps(const pmhip_s2* h, int* one_pass, int* two_pass) {
+    PM_REQUIRE(h, "s2_slots_steps: null handle");
+    if (one_pass) *one_pass = h->slots_one_pass;
+    if (two_pass) *two_pass = h->slots_two_pass;
     return PMHIP_OK;
 }
 

@@ -1,6 +1,8 @@
 // HBM-bound row kernels: LayerNorm, patchify / un-patchify(+clamp), pad-convert, embedding gather.
 // All are one pass over their input with 16-byte accesses; one wave owns one row where a
 // reduction is involved (no LDS, no barriers).
+#include <algorithm>
+
 #include "common.h"
 
 namespace {
@@ -201,6 +203,37 @@ __global__ __launch_bounds__(THREADS) void guidance_kernel(const float* cond, co
         if constexpr (STATS) {                             // n4 % 16 == 0: the 16 lanes of a block run the same iterations
             const float2 st = softmax_block_stat(r.x, r.y, r.z, r.w);
             if ((threadIdx.x & 15) == 0) block_stats[i >> 4] = st;
+        }
+    }
+}
+
+// guidance_kernel per IMAGE (pmhip_guidance_combine_slots): image b = blockIdx.y combines with guides[b].scale when its slot is
+// active and guides[b].on is set, and is neither read nor written otherwise -- the workgroups of such an image leave at once, so
+// what the cond tower's GEMM left there (logits and statistics) stays the unguided step's input.  The image is a workgroup-level
+// value: the skip is uniform over the workgroup, and the blocks of gridDim.x grid-stride over the image's n4 float4s -- n4 % 16
+// == 0 (V % 64 == 0), so the 16 lanes of a 64-column block run the same iterations and softmax_block_stat's DPP rows are always
+// full.  Element and block arithmetic, and the 16-lanes-per-block layout, are guidance_kernel's: a guided image's rows equal that
+// kernel's on the image alone, bit for bit.  (no __restrict__ on the planes: out aliases cond in the engine)
+template <bool STATS>
+__global__ __launch_bounds__(THREADS) void guidance_slots_kernel(const float* cond, const float* uncond,
+                                                                 const pmhip_slot_guide* __restrict__ guides,
+                                                                 const pmhip_slot* __restrict__ slots, float* out, size_t n4,
+                                                                 float2* block_stats) {
+    const pmhip_slot_guide g = guides[blockIdx.y];
+    if ((slots[blockIdx.y].step & PM_SLOT_IDLE) || g.on == 0) return;
+    const size_t base = (size_t)blockIdx.y * n4;
+    const float4* c4 = reinterpret_cast<const float4*>(cond) + base;
+    const float4* u4 = reinterpret_cast<const float4*>(uncond) + base;
+    float4* o4 = reinterpret_cast<float4*>(out) + base;
+    const float scale = g.scale;
+    for (size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x; i < n4; i += (size_t)gridDim.x * THREADS) {
+        const float4 c = c4[i], u = u4[i];
+        const float4 r = make_float4(fmaf(scale, c.x - u.x, u.x), fmaf(scale, c.y - u.y, u.y), fmaf(scale, c.z - u.z, u.z),
+                                     fmaf(scale, c.w - u.w, u.w));
+        o4[i] = r;
+        if constexpr (STATS) {
+            const float2 st = softmax_block_stat(r.x, r.y, r.z, r.w);
+            if ((threadIdx.x & 15) == 0) block_stats[(base + i) >> 4] = st;
         }
     }
 }
@@ -545,4 +578,30 @@ extern "C" int pmhip_guidance_combine_stats(const float* cond, const float* unco
                                             pmhip_stream stream) {
     PM_REQUIRE(block_stats, "guidance_combine_stats: null statistics buffer");
     return guidance_impl(cond, uncond, scale, out, n, block_stats, stream);
+}
+
+// the same per image: guides / slots are DEVICE arrays [M / tokens]; an idle or unguided image is neither read nor written
+extern "C" int pmhip_guidance_combine_slots(const float* cond, const float* uncond, const pmhip_slot_guide* guides, const pmhip_slot* slots,
+                                            int tokens, float* out, float* block_stats, int M, int V, pmhip_stream stream) {
+    PM_REQUIRE(cond && uncond, "guidance_combine_slots: null cond or uncond pointer");
+    PM_REQUIRE(guides, "guidance_combine_slots: null guides pointer");
+    PM_REQUIRE(slots, "guidance_combine_slots: null slots pointer");
+    PM_REQUIRE(out, "guidance_combine_slots: null out pointer");
+    PM_REQUIRE(M > 0 && V > 0 && V % 64 == 0, "guidance_combine_slots: bad shape M=%d V=%d (V must be a multiple of 64)", M, V);
+    PM_REQUIRE(tokens > 0 && M % tokens == 0, "guidance_combine_slots: M=%d is not a whole number of images of tokens=%d", M, tokens);
+    const int B = M / tokens;
+    PM_REQUIRE(B <= 65535, "guidance_combine_slots: M / tokens = %d images, at most 65535", B);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n4 = (size_t)tokens * (V / 4);
+    // as many workgroups as guidance_kernel gets for the whole plane, shared out over the images
+    const int chunks = std::min(grid_for(n4), std::max(1, (256 * 8 + B - 1) / B));
+    PmTimer tm(FAM_ROWOPS, s);
+    if (block_stats)
+        hipLaunchKernelGGL(guidance_slots_kernel<true>, dim3(chunks, B), dim3(THREADS), 0, s, cond, uncond, guides, slots, out, n4,
+                           reinterpret_cast<float2*>(block_stats));
+    else
+        hipLaunchKernelGGL(guidance_slots_kernel<false>, dim3(chunks, B), dim3(THREADS), 0, s, cond, uncond, guides, slots, out, n4,
+                           (float2*)nullptr);
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
 }

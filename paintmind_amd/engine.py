@@ -320,14 +320,25 @@ class S2Engine:
                       "pmhip_pipeline_sample_guided")
         return ids, img, pred, score
 
-    def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True):
+    def slots_steps(self):
+        """(one_pass, two_pass): the slots steps this handle ran, by tower passes (pmhip_s2_slots_steps) -- two passes exactly when
+        an active slot of the step was guided"""
+        one, two = C.c_int(0), C.c_int(0)
+        check(self.lib.pmhip_s2_slots_steps(self.handle, C.byref(one), C.byref(two)), "pmhip_s2_slots_steps")
+        return one.value, two.value
+
+    def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
-        length; the cross K/V the previous step_slots call prepared are reused.  -> (ids, pred [B,N], score [B,N])"""
+        length; the cross K/V the previous step_slots call prepared are reused.  guides: a ctypes array of _lib.SlotGuide beside
+        `slots` (HOST records: scale, on) -- an active slot with on != 0 samples from uncond + scale * (cond - uncond), and a step
+        with such a slot runs the tower twice (pmhip_pipeline_step_slots_guided).  -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
             raise ValueError(f"step_slots: {len(slots)} slot records for a batch of {B}")
+        if guides is not None and len(guides) != B:
+            raise ValueError(f"step_slots: {len(guides)} guide records for a batch of {B}")
         if not (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.shape[1] == self.tokens):
             raise ValueError(f"step_slots: ids must be a contiguous int64 [B, {self.tokens}] tensor on the device")
         if keep_context:
@@ -339,8 +350,12 @@ class S2Engine:
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
         flags = (_lib.SLOTS_GRAPH if use_graph else 0) | (_lib.SLOTS_KEEP_CONTEXT if keep_context else 0)
         with torch.cuda.device(self.device):
-            check(self.lib.pmhip_pipeline_step_slots(self.handle, _p(ids), _p(context), L, B, slots, flags, _p(pred), _p(score),
-                                                     stream_ptr(self.device)), "pmhip_pipeline_step_slots")
+            if guides is None:
+                check(self.lib.pmhip_pipeline_step_slots(self.handle, _p(ids), _p(context), L, B, slots, flags, _p(pred), _p(score),
+                                                         stream_ptr(self.device)), "pmhip_pipeline_step_slots")
+            else:
+                check(self.lib.pmhip_pipeline_step_slots_guided(self.handle, _p(ids), _p(context), L, B, slots, guides, flags, _p(pred),
+                                                                _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_guided")
         return ids, pred, score
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,

@@ -545,6 +545,49 @@ def remask_slots(ids, scores, slots, mask_id):
     return ids
 
 
+def pack_slot_guides(scales, device=None):
+    """[guidance scale or None (not guided), ...] -> the pmhip_slot_guide array as a uint8 tensor [B, 8] (on `device` when given):
+    what guidance_combine_slots reads, one record beside every pack_slots record."""
+    arr = (_lib.SlotGuide * len(scales))()
+    for i, sc in enumerate(scales):
+        if sc is not None:
+            arr[i] = _lib.SlotGuide(float(sc), 1)
+    t = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).reshape(len(scales), C.sizeof(_lib.SlotGuide))
+    return t if device is None else t.to(device)
+
+
+def guidance_combine_slots(cond, uncond, guides, slots, tokens, out=None, block_stats=None):
+    """guidance_combine with the scale of row r taken from guides[r // tokens] (pack_slot_guides): cond, uncond fp32
+    [B*tokens, V] -> `out` (default: a new tensor; may be cond), and `block_stats` fp32 [B*tokens, V/64, 2] when given.  The rows
+    of an image that is guided and whose slot (pack_slots) is active equal guidance_combine(with_stats=True) on that image alone,
+    bit for bit; the rows of every other image are neither read nor written: `out` and `block_stats` keep what they held.
+    V % 64 == 0."""
+    dev = _dev(cond, uncond, guides, slots, out, block_stats)
+    lib = _lib.load()
+    if cond.dim() != 2 or cond.shape != uncond.shape or cond.dtype != torch.float32 or uncond.dtype != torch.float32:
+        raise ValueError("guidance_combine_slots needs two fp32 [M, V] tensors of one shape")
+    M, V = cond.shape
+    if tokens <= 0 or M % tokens:
+        raise ValueError(f"guidance_combine_slots: {M} rows are not a whole number of images of {tokens} tokens")
+    B = M // tokens
+    _check_slots(slots, B, dev)
+    if (guides.dtype != torch.uint8 or not guides.is_contiguous() or guides.device != dev
+            or tuple(guides.shape) != (B, C.sizeof(_lib.SlotGuide))):
+        raise ValueError(f"guides must be a contiguous uint8 [{B}, {C.sizeof(_lib.SlotGuide)}] tensor (pack_slot_guides) on the operands' device")
+    out = torch.empty_like(cond) if out is None else out
+    if out.shape != cond.shape or out.dtype != torch.float32 or out.device != cond.device:
+        raise ValueError("guidance_combine_slots: `out` must be an fp32 tensor of the inputs' shape on their device")
+    if not (cond.is_contiguous() and uncond.is_contiguous() and out.is_contiguous()):
+        raise ValueError("guidance_combine_slots needs contiguous tensors (rows of V consecutive elements)")
+    if block_stats is not None and (block_stats.dtype != torch.float32 or not block_stats.is_contiguous()
+                                    or tuple(block_stats.shape) != (M, V // 64, 2) or V % 64):
+        raise ValueError("guidance_combine_slots: block_stats must be a contiguous fp32 [M, V/64, 2] tensor on the inputs' device")
+    with torch.cuda.device(dev):
+        check(lib.pmhip_guidance_combine_slots(_p(cond), _p(uncond), _p(guides), _p(slots), int(tokens), _p(out), _p(block_stats), M, V,
+                                               stream_ptr(dev)), "pmhip_guidance_combine_slots")
+    return out if block_stats is None else (out, block_stats)
+
+
 def random_mask(z, noise, mask_token, len_keep):
     """z fp32 [B,N,E], noise fp32 [B,N], mask_token fp32 [E] -> (x [B,N,E], mask [B,N] with 1 = masked)."""
     dev = _dev(z, noise, mask_token)

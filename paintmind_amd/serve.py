@@ -6,16 +6,24 @@ rows, and the sampling tail reads every per-image value from a device record, so
 whatever shares the batch with it.  The contract ("Decode sessions"): a request (T, temperature, topk, seed, image
 index k, context c) that sits in slot j of an S-slot session produces, bit for bit, the per-step predictions, scores and final
 ids of row j of ``Pipeline.generate_ids(context with c in row j, B=S, T, temperature, topk, ..., seed, image_base=k - j,
-streams=1)``; its image is ``vqgan.decode_from_indice`` of the last step's predictions.
+streams=1, guidance_scale=s)``; its image is ``vqgan.decode_from_indice`` of the last step's predictions.
+
+Guidance is per request (``submit(guidance_scale=s)``, conditional sessions only): the native step
+(pmhip_pipeline_step_slots_guided) reads a scale per slot from a second device record, runs the tower twice in a step in which
+at least one active slot is guided, and combines the two towers' logits on the rows of the guided slots only, so requests with
+different scales, and unguided ones, share a batch and each computes what it would compute alone.
 
 Limits: a session is all-conditional or all-unconditional (``context=None`` selects attn2's inputs for the whole batch), every
-context of a session has the same length, top-k <= 8 (the block-statistics sampling kernel), no guidance, and idle slots still run
-through the tower (no compaction).
+context of a session has the same length, top-k <= 8 (the block-statistics sampling kernel), and idle slots still run through
+the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the second tower pass: the
+unconditional pass runs at the session's batch size.  The guided loop's step-0 cache ("Not built") stays
+not built.
 
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
-``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed)``.
+``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed, guidance_scale=s)``.
 """
 import collections
+import math
 import os
 
 import torch
@@ -28,8 +36,9 @@ Finished = collections.namedtuple("Finished", ["handle", "image", "ids"])
 class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
-    def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0):
+    def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None):
         self.number, self.text, self.context = number, text, context
+        self.guidance_scale = guidance_scale        # None: not guided
         self.timesteps, self.temperature, self.topk, self.seed, self.image_index = timesteps, temperature, topk, seed, image_index
         self.temps, self.nmask = temps, nmask
         self.ids0 = ids0
@@ -41,7 +50,7 @@ class Request:
 
     def __repr__(self):
         return (f"Request(#{self.number}, T={self.timesteps}, temperature={self.temperature}, topk={self.topk}, seed={self.seed}, "
-                f"image_index={self.image_index}, slot={self.slot}, admitted={self.admitted}, retired={self.retired})")
+                f"image_index={self.image_index}, guidance_scale={self.guidance_scale}, slot={self.slot}, admitted={self.admitted}, retired={self.retired})")
 
 
 class DecodeSession:
@@ -68,12 +77,22 @@ class DecodeSession:
         self._ctx = None                    # GPU, conditional: [S, L, context_dim] fp32
         self._ctx_dirty = True              # a slot's context changed since the cross K/V were prepared
         self._records = (_lib.Slot * self.size)()
+        self._guides = (_lib.SlotGuide * self.size)() if self.conditional else None
 
     # -- requests -----------------------------------------------------------------------------------
-    def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None):
+    def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
+               guidance_scale=None):
         """queue one request (any time, also between steps) -> its Request.  `context` [L, D] may be given instead of `text`
-        (a conditional session runs the pipeline's text model on `text` otherwise); `ids0` [N]: start ids instead of all-mask."""
+        (a conditional session runs the pipeline's text model on `text` otherwise); `ids0` [N]: start ids instead of all-mask;
+        `guidance_scale` (None = not guided): this request samples from uncond + scale * (cond - uncond), like
+        ``Pipeline.generate(guidance_scale=)``."""
         timesteps, topk = int(timesteps), int(topk)
+        if guidance_scale is not None:
+            if not self.conditional:
+                raise ValueError("guidance_scale needs a text condition (an unconditional session IS the unconditional branch)")
+            guidance_scale = float(guidance_scale)
+            if not math.isfinite(guidance_scale):
+                raise ValueError("guidance_scale must be finite")
         if timesteps < 1:
             raise ValueError("timesteps must be >= 1")
         if not self._cpu and not 1 <= topk <= 8:
@@ -100,7 +119,7 @@ class DecodeSession:
         if ids0 is not None:
             ids0 = self.pipe._start_ids(1, ids0.reshape(1, -1), ids0.device)
         temps, nmask = self.pipe._schedule(timesteps, temperature)
-        r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0)
+        r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale)
         self._submitted += 1
         self.queue.append(r)
         return r
@@ -155,7 +174,7 @@ class DecodeSession:
                 continue
             t = r.done
             ctx = None if r.context is None else r.context[None]
-            ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t)
+            ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t, r.guidance_scale)
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
@@ -186,6 +205,9 @@ class DecodeSession:
         retiring = []
         for j, r in enumerate(self.occupied):
             rec = self._records[j]
+            if self._guides is not None:
+                on = r is not None and r.guidance_scale is not None
+                self._guides[j].scale, self._guides[j].on = (r.guidance_scale if on else 0.0), int(on)
             if r is None:
                 rec.step = _lib.SLOT_IDLE
                 continue
@@ -198,12 +220,14 @@ class DecodeSession:
         ctx = self._ctx if self.conditional else None
         keep = not self._ctx_dirty
         try:
-            _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep, want_aux=want_aux)
+            _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep, want_aux=want_aux,
+                                            guides=self._guides)
         except _lib.PmhipError as e:
             # another call on this handle (pipe.generate, a rebuilt engine ...) replaced the prepared context: prepare it again
             if not (keep and getattr(e, "code", None) == _lib.PMHIP_ESTATE):
                 raise
-            _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=False, want_aux=want_aux)
+            _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=False, want_aux=want_aux,
+                                            guides=self._guides)
         self._ctx_dirty = False
         for r in self.occupied:
             if r is not None:

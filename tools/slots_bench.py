@@ -6,6 +6,14 @@
            loop can do (sort by T, one generate_ids per homogeneous group of at most S).  Images/s and the mean request latency
            in decode steps (session: the tick a request retires at + 1; sorted groups: the steps run up to the end of its group).
 
+  guided   per-request guidance, --part kernel | session | all:
+           kernel   guidance_slots_kernel<true> (every image guided, then every second one) against guidance_kernel<true> on the
+                    same planes (--rows x --classes, in place at scale 1 so that the values stay put), alternating, --launches
+                    each, timed with events; run it under ``rocprofv3 --kernel-trace --stats --`` for the per-kernel figures.
+           session  S conditional requests (T steps, scale --scale) admitted together: the guided session against
+                    generate_ids(guidance_scale=, use_graph=True, streams=1); then the same with every second request unguided
+                    against one generate_ids per homogeneous group (S/2 guided, S/2 unguided).
+
 The arms alternate inside one process, --rounds times; nothing is decoded (ids only).  --arms generate runs on a commit that has
 no sessions: point --root at such a checkout to time the scalar loop of another commit on the same box.
 """
@@ -20,18 +28,26 @@ import time
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="checkout whose paintmind_amd is timed")
-    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed"])
+    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed", "guided"])
     ap.add_argument("--arms", default="session,generate")
-    ap.add_argument("--workload", default="bench-uncond-12L-d512")
+    ap.add_argument("--workload", default=None, help="default: bench-uncond-12L-d512; guided: bench-text-24L-d768")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--slots", type=int, default=64)
-    ap.add_argument("--timesteps", type=int, default=8)
+    ap.add_argument("--timesteps", type=int, default=None, help="default: 8; guided: 12")
+    ap.add_argument("--part", default="all", choices=["kernel", "session", "all"], help="guided: which half to run")
+    ap.add_argument("--scale", type=float, default=3.0)
+    ap.add_argument("--rows", type=int, default=65536, help="guided kernel: rows of the planes (a multiple of --tokens)")
+    ap.add_argument("--classes", type=int, default=8192)
+    ap.add_argument("--tokens", type=int, default=1024)
+    ap.add_argument("--launches", type=int, default=6)
     ap.add_argument("--requests", type=int, default=256)
     ap.add_argument("--mix", default="8,12,18")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=6, help="uniform: batches per timed window")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.workload = a.workload or ("bench-text-24L-d768" if a.mode == "guided" else "bench-uncond-12L-d512")
+    a.timesteps = a.timesteps or (12 if a.mode == "guided" else 8)
     sys.path.insert(0, a.root)
     import torch
     import paintmind_amd as pm
@@ -40,6 +56,14 @@ def main():
     assert torch.cuda.is_available(), "slots_bench needs a ROCm device"
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
+    if a.mode == "guided":
+        out = {"mode": "guided", "root": os.path.abspath(a.root), "dtype": a.dtype}
+        if a.part in ("kernel", "all"):
+            out["kernel"] = guided_kernel(a, dev)
+        if a.part in ("session", "all"):
+            out["session"] = guided_session(a, dev)
+        emit(out, a.out)
+        return
     pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
     pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
     S, arms = a.slots, a.arms.split(",")
@@ -96,11 +120,91 @@ def main():
            "requests": len(ts), "reps": reps, "groups": groups if a.mode == "mixed" else None,
            "images_per_s": res,
            "mean_latency_steps": {arm: info[arm][0] for arm in arms}, "steps_run": {arm: info[arm][1] for arm in arms}}
+    emit(out, a.out)
+
+
+def emit(out, path):
     line = json.dumps(out)
     print(line)
-    if a.out:
-        with open(a.out, "a") as f:
+    if path:
+        with open(path, "a") as f:
             f.write(line + "\n")
+
+
+def guided_kernel(a, dev):
+    """ms per launch: the flat combination, the per-image one with every image guided, with every second image guided"""
+    import torch
+    from paintmind_amd import ops
+    M, V, N = a.rows, a.classes, a.tokens
+    B = M // N
+    g = torch.Generator(device=dev).manual_seed(1)
+    cond = torch.randn(M, V, device=dev, generator=g)
+    unc = torch.randn(M, V, device=dev, generator=g)
+    stats = torch.empty(M, V // 64, 2, device=dev)
+    slots = ops.pack_slots([(1, b, 1.0, 5, 1, 0) for b in range(B)], dev)
+    every = ops.pack_slot_guides([1.0] * B, dev)
+    half = ops.pack_slot_guides([1.0 if b % 2 == 0 else None for b in range(B)], dev)
+    arms = {"guidance_kernel": lambda: ops.guidance_combine(cond, unc, 1.0, out=cond, with_stats=True),
+            "guidance_slots_kernel": lambda: ops.guidance_combine_slots(cond, unc, every, slots, N, out=cond, block_stats=stats),
+            "guidance_slots_kernel_half": lambda: ops.guidance_combine_slots(cond, unc, half, slots, N, out=cond, block_stats=stats)}
+    for f in arms.values():
+        f()
+    torch.cuda.synchronize(dev)
+    ms = {k: [] for k in arms}
+    for _ in range(a.launches):
+        for k, f in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    return {"rows": M, "classes": V, "tokens": N, "images": B, "guided_row_bytes": 3 * V * 4, "ms": ms}
+
+
+def guided_session(a, dev):
+    import torch
+    import paintmind_amd as pm
+    from paintmind_amd.generate import Pipeline
+    pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
+    pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    S, T, scale = a.slots, a.timesteps, a.scale
+    ctx = torch.randn(S, 77, pipe.engine().context_dim, device=dev, generator=torch.Generator(device=dev).manual_seed(2))
+    sync = lambda: torch.cuda.synchronize(dev)
+
+    def run_generate(groups, seed):
+        at = 0
+        for B, sc in groups:
+            pipe.generate_ids(ctx[at:at + B].contiguous(), B, T, 1.0, 5, [False] * T, seed, use_graph=True, streams=1, guidance_scale=sc)
+            at += B
+
+    def run_session(scales, seed):
+        s = pipe.decode_session(slots=S, conditional=True, use_graph=True, decode=False)
+        for i, sc in enumerate(scales):
+            s.submit(context=ctx[i], timesteps=T, temperature=1.0, topk=5, seed=seed + i, guidance_scale=sc)
+        assert len(s.drain()) == S and s.tick == T
+
+    mixed = [scale] * (S // 2) + [None] * (S - S // 2)
+    work = {"session_guided": lambda sd: run_session([scale] * S, sd),
+            "generate_guided": lambda sd: run_generate([(S, scale)], sd),
+            "session_half_guided": lambda sd: run_session(mixed, sd),
+            "generate_two_groups": lambda sd: run_generate([(S // 2, scale), (S - S // 2, None)], sd)}
+    for f in work.values():                            # eager pass, capture pass, replay
+        for w in range(3):
+            f(w)
+    sync()
+    res = {arm: [] for arm in work}
+    for rnd in range(a.rounds):
+        for arm, f in work.items():
+            sync()
+            t0 = time.perf_counter()
+            for rep in range(a.reps):
+                f(100 * rnd + rep)
+            sync()
+            res[arm].append(S * a.reps / (time.perf_counter() - t0))
+    one, two = pipe.engine().slots_steps()
+    return {"workload": a.workload, "slots": S, "timesteps": T, "scale": scale, "reps": a.reps, "images_per_s": res,
+            "slots_steps": {"one_pass": one, "two_pass": two}}
 
 
 if __name__ == "__main__":
