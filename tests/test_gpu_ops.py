@@ -413,10 +413,25 @@ def test_heads_projection_and_attention(dtype, B, heads, Nq, Nkv):
 @pytest.mark.parametrize("pattern", ["rising", "falling", "spikes", "huge_jumps", "very_negative"])
 @pytest.mark.parametrize("Nkv", [416, 448])
 def test_attention_running_max_rescale_paths(dtype, pattern, Nkv):
+    """The mode the product runs: use_exp2 = (dtype is bf16).  See _running_max_rescale_paths."""
+    _running_max_rescale_paths(dtype, pattern, Nkv, dtype == torch.bfloat16)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("pattern", ["rising", "falling", "spikes", "huge_jumps", "very_negative"])
+@pytest.mark.parametrize("Nkv", [416, 448])
+def test_attention_running_max_rescale_paths_in_the_other_mode(dtype, pattern, Nkv):
+    """use_exp2 = (dtype is f32): attention_kernel<float, true, 2> and attention_bf16_kernel<false, QF>."""
+    _running_max_rescale_paths(dtype, pattern, Nkv, dtype == torch.float32)
+
+
+def _running_max_rescale_paths(dtype, pattern, Nkv, use_exp2):
     """Scores whose maximum keeps growing along the key axis, including jumps far beyond the exp2 range (the bf16 kernel's
     fixed-reference fast path overflows and the workgroup must notice and take its exact path), shrinking, with isolated
     spikes, and all very negative.  Nkv = 416: 6.5 tiles, ragged last tile, odd number of half-tiles (fast steps, then exact
-    steps); 448: whole tiles only (every half-tile through the fast step)."""
+    steps); 448: whole tiles only (every half-tile through the fast step).  Both dtypes run both modes: the product only ever
+    passes use_exp2 = (dtype is bf16), the other two forms (expf in the bf16 kernel, the deferred rescale of the f32 kernel) are
+    public all the same."""
     B, H, Nq = 1, 2, 256
     rng = np.random.default_rng(7)
     q = rng.standard_normal((B, H, Nq, 64)).astype(np.float32)
@@ -440,13 +455,19 @@ def test_attention_running_max_rescale_paths(dtype, pattern, Nkv):
     k = k + boost[None, None, :, None] * mean_dir
     scale = 0.125
     fast = dtype == torch.bfloat16
-    if fast:                                              # the kernel sees q pre-scaled by scale*log2(e), rounded ONCE
-        k, v = bf16_round(k), bf16_round(v)
-        qs = bf16_round(q * (scale * ops.LOG2E))
-        s = (qs.astype(np.float64) @ k.astype(np.float64).transpose(0, 1, 3, 2)) * np.log(2.0)
-    else:
-        qs = q * np.float32(scale)
-        s = qs.astype(np.float64) @ k.astype(np.float64).transpose(0, 1, 3, 2)
+    qs = q * np.float32(scale * ops.LOG2E if use_exp2 else scale)     # the kernel sees q pre-scaled (by scale*log2(e) in exp2 mode) ...
+    if fast:                                              # ... and rounded ONCE
+        k, v, qs = bf16_round(k), bf16_round(v), bf16_round(qs)
+    s = (qs.astype(np.float64) @ k.astype(np.float64).transpose(0, 1, 3, 2)) * (np.log(2.0) if use_exp2 else 1.0)    # nats
+    # the fast path accumulates l = sum_j e^(s_j - m_ref), m_ref = the maximum over the first 32 keys, over the keys of its fast steps
+    # (Nkv = 448: all of them; 416: the first 352 -- steady_end = 10 fast half-tiles, and the first exact step still takes its
+    # half-tile at m_ref; the exact steps behind it raise the maximum)
+    nfast = 352 if Nkv == 416 else Nkv
+    m_ref = s[..., :32].max(-1, keepdims=True)
+    m_end = np.maximum(m_ref, s[..., nfast:].max(-1, keepdims=True)) if nfast < Nkv else m_ref
+    l_fast = np.exp(np.minimum(s[..., :nfast] - m_ref, 700.0)).sum(-1)
+    l_ref = np.exp(np.minimum(s - m_ref, 700.0)).sum(-1)
+    l_end = np.exp(np.minimum(s - m_end, 700.0)).sum(-1)
     s -= s.max(-1, keepdims=True)
     pr = np.exp(s)
     pr /= pr.sum(-1, keepdims=True)
@@ -458,17 +479,73 @@ def test_attention_running_max_rescale_paths(dtype, pattern, Nkv):
     vtp[:, :, :, :Nkv] = v.transpose(0, 1, 3, 2)
     if fast:
         ops.attention_fallbacks(reset=True)
-    out = n(ops.attention(t(qs, dtype), t(kp, dtype), t(vtp, dtype), Nkv, use_exp2=fast))
+    out = n(ops.attention(t(qs, dtype), t(kp, dtype), t(vtp, dtype), Nkv, use_exp2=use_exp2))
     assert np.isfinite(out).all()
     # scores of ~1e4 carry an fp32 ulp of ~1e-3 themselves: any fp32 softmax is only that accurate against float64
     tol32 = 2e-3 if pattern == "huge_jumps" else 5e-5
     assert rel_err(out, ref) < (tol32 if dtype == torch.float32 else 4e-2), rel_err(out, ref)
-    if fast:
+    if fast and use_exp2:
         # the exact path ran where, and only where, the scores leave the fast path's range: huge_jumps climbs by hundreds of
         # octaves per 50 keys in every workgroup (2 heads x 4 blocks of 64 queries at this size); the other patterns stay within
         # 2^64 of the first keys' maximum
         fb = ops.attention_fallbacks(reset=True)
         assert (fb == 8) if pattern == "huge_jumps" else (fb == 0), fb
+    elif fast:
+        # the same vote on l = sum_j e^(s_j - m_ref) in nats, bracketed from the float64 scores as in the peaky-heads test below: a
+        # 16-query tile MUST vote where the l of its fast steps leaves f32 (it stays inf / NaN) or what is left at the end, relative
+        # to the maximum the exact steps raised, is 2^64.5 or more; it MAY vote where the whole row's l reaches 2^63.5.  This launch
+        # runs 64 queries per workgroup, and the counter counts workgroups.
+        fb = ops.attention_fallbacks(reset=True)
+        wg = lambda cond: int(cond.reshape(B, H, Nq // 64, 64).any(-1).sum())
+        must, may = wg((np.log2(l_fast) > 128.5) | (np.log2(l_end) > 64.5)), wg(np.log2(l_ref) > 63.5)
+        print(f"{pattern} Nkv={Nkv} bf16 exp: workgroups re-run {fb} (must {must}, may {may})")
+        assert must <= fb <= may, (fb, must, may)
+
+
+def _staircase_scores(incr, Nq, Nkv, rng):
+    """q, k (f32, [1, 2, ., 64]) whose scores are a_i * g_j + noise: g climbs by incr[h] at the start of half-tile h (32 keys), a_i
+    in [0.95, 1.05]"""
+    u = rng.standard_normal(64).astype(np.float32)
+    u /= np.linalg.norm(u)
+    perp = lambda x: x - (x @ u)[..., None] * u
+    a = rng.uniform(0.95, 1.05, (1, 2, Nq, 1)).astype(np.float32)
+    q = a * u + perp(rng.standard_normal((1, 2, Nq, 64)).astype(np.float32)) * 0.02
+    gsteps = np.cumsum(incr)[np.arange(Nkv) // 32].astype(np.float32)
+    k = gsteps[None, None, :, None] * u + perp(rng.standard_normal((1, 2, Nkv, 64)).astype(np.float32)) * 0.3
+    return q.astype(np.float32), k.astype(np.float32)
+
+
+@pytest.mark.parametrize("pattern", ["deferred", "over_the_limit"])
+def test_attention_f32_exp2_deferred_rescale(pattern):
+    """attention_kernel<float, true, 2> leaves the running maximum where it is while a half-tile exceeds it by at most 2^8
+    (kDefer: P up to 256) and rescales once the excess is larger.  'deferred': the maximum of every query grows by 3 to 7 octaves
+    at every half-tile, so it is left behind for one or two half-tiles and then caught up, again and again; 'over_the_limit':
+    single steps of 9 to 30 octaves between flat stretches.  Both are asserted on the float64 scores, and the output is held to
+    the element-wise f32 bound of tests/attention_probes.py.  Nq = 200: a full and a ragged block of 128 queries; Nkv = 416: 13
+    half-tiles, ragged last tile."""
+    import attention_probes as P
+    Nq, Nkv = 200, 416
+    rng = np.random.default_rng(23)
+    nh = (Nkv + 31) // 32
+    if pattern == "deferred":
+        incr = rng.uniform(3.6, 6.2, nh)
+    else:
+        incr = np.where(np.arange(nh) % 3 == 1, rng.uniform(9.5, 28.0, nh), 0.0)
+    incr[0] = 0.0
+    q, k = _staircase_scores(incr, Nq, Nkv, rng)
+    v = rng.standard_normal((1, 2, Nkv, 64)).astype(np.float32)
+    ref, A, s = P.reference(q, k, v, True)
+    hmax = np.stack([s[..., 32 * h:32 * h + 32].max(-1) for h in range(nh)], -1)            # [1, 2, Nq, nh]
+    growth = hmax[..., 1:] - np.maximum.accumulate(hmax, -1)[..., :-1]
+    if pattern == "deferred":
+        assert growth.min() > 3.0 and growth.max() < 7.0, (growth.min(), growth.max())
+    else:
+        assert (growth.max(-1) > 9.0).all() and ((growth > 8.0) | (growth < 1.0)).all(), (growth.min(), growth.max())
+    kp, vtp = P.pad_kv(k, v, 448)
+    out = P.from_out_layout(n(ops.attention(t(q), t(kp), t(vtp), Nkv, use_exp2=True)), 1, 2, Nq, 64)
+    ratio, msg = P.check_bound(out, ref, P.bound("f32", ref, A, P.score_error(q, k, s, True), Nkv), s, f"f32 exp2 {pattern}")
+    print(f"f32 exp2 {pattern}: largest err / B {ratio:.3f}")
+    assert msg is None, msg
 
 
 @pytest.mark.parametrize("dominance", [0.0, 10.0, 20.0, 45.0])
@@ -576,7 +653,8 @@ def test_attention_result_does_not_depend_on_the_batch_or_the_workgroup_size(Nkv
     vt = bf16_round(rng.standard_normal((B, H, 64, Np)).astype(np.float32))
     k[0, 3, min(200, Nkv - 3)] = bf16_round(q[0, 3, 77] * 4000.0)   # one head of image 0 overflows for the queries aligned with q[77]
     run = lambda sl: n(ops.attention(t(q[sl], torch.bfloat16), t(k[sl], torch.bfloat16), t(vt[sl], torch.bfloat16), Nkv, use_exp2=True))
-    fast = Nkv > 128                                            # (a context of one or two tiles never enters the fast path: nothing can overflow)
+    fast = Nkv > 128                                            # (77: steady_end <= 0, no fast step, nothing can overflow.  A context of two WHOLE
+                                                                #  tiles, Nkv = 128, does take one pair of fast steps; no such Nkv is run here)
     ops.attention_fallbacks(reset=True)
     full = run(slice(0, B)).reshape(B, N, H * 64)               # 32 * 8 * 2 = 512 workgroups of 256 queries
     assert (ops.attention_fallbacks(reset=True) >= 1) == fast and np.isfinite(full).all()
