@@ -209,6 +209,11 @@ struct Switches {
                                 // to a side stream beside the next step's tower (0 = never)
     bool hilo = true;       // PMHIP_HILO=0: the fp32 stream + LayerNorm kernel of rounds 1-2
     bool fold = true;       // PMHIP_LN_UNFOLD=1: the hi/lo pair, but the separate LayerNorm kernel
+    int fold_rows_cap = 0;  // PMHIP_FOLD_MAX_ROWS (development / tests): cap on the rows one folded launch takes, see fold_rows()
+    bool center = true;     // PMHIP_HILO_CENTER=0: the residual producers do not centre the hi plane (A/B, tests)
+    bool logits_stats = true;     // PMHIP_LOGITS_STATS=0 (development builds, profiles/r06_d): the logits GEMM leaves no block statistics, the sampling kernel derives
+                                  // them from the rows it then has to read in full (same ids and scores, bit for bit)
+    bool blocking_wait = false;   // PMHIP_BLOCKING_WAIT=1: host waits between decode-loop segments sleep instead of spinning
     static Switches from_env() {
         Switches w;
         const char* e = getenv("PMHIP_HILO");
@@ -226,11 +231,6 @@ struct Switches {
         w.logits_stats = pm_dev_knob("PMHIP_LOGITS_STATS", 1) != 0;
         return w;
     }
-    int fold_rows_cap = 0;  // PMHIP_FOLD_MAX_ROWS (development / tests): cap on the rows one folded launch takes, see fold_rows()
-    bool center = true;     // PMHIP_HILO_CENTER=0: the residual producers do not centre the hi plane (A/B, tests)
-    bool logits_stats = true;     // PMHIP_LOGITS_STATS=0 (development builds, profiles/r06_d): the logits GEMM leaves no block statistics, the sampling kernel derives
-                                  // them from the rows it then has to read in full (same ids and scores, bit for bit)
-    bool blocking_wait = false;   // PMHIP_BLOCKING_WAIT=1: host waits between decode-loop segments sleep instead of spinning
     // bit 2 (the producers leave row statistics for the fold) is constant: the switch that cleared it is gone, the bit keeps its place
     int key() const { return (hilo ? 2 : 0) + (fold ? 1 : 0) + 4 + (center ? 8 : 0); }
 };
@@ -664,16 +664,84 @@ extern "C" int pmhip_vqgan_decoder_forward(pmhip_vqgan* h, const float* x, int B
 // ------------------------------------------------------------------------------------------------
 // stage 2: CondTransformer + MaskGIT loop
 // ------------------------------------------------------------------------------------------------
+namespace {
+
+// A HIP event or stream that is created at most once, on first use, and destroyed with its owner.
+template <typename H, hipError_t (*Create)(H*, unsigned), hipError_t (*Destroy)(H)>
+struct HipOwned {
+    H h = nullptr;
+    HipOwned() = default;
+    HipOwned(HipOwned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    HipOwned(const HipOwned&) = delete;
+    HipOwned& operator=(const HipOwned&) = delete;
+    ~HipOwned() { if (h) (void)Destroy(h); }
+    int get(unsigned flags, H& out) {           // the flags of the FIRST call are the handle's
+        if (!h) PM_HIP(Create(&h, flags));
+        out = h;
+        return PMHIP_OK;
+    }
+};
+using OwnedEvent = HipOwned<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+using OwnedStream = HipOwned<hipStream_t, hipStreamCreateWithFlags, hipStreamDestroy>;
+
+// Per-call host records travel through PINNED host memory (a pageable source makes hipMemcpyAsync stage synchronously): a ring of
+// kParamSlots entries, each reused only after the last copy that read it has completed.  Per call: acquire(), stage() once per
+// destination, commit().
+struct PinnedRing {
+    static constexpr int kParamSlots = 4;
+    unsigned char* host = nullptr;
+    size_t entry_bytes = 0;
+    OwnedEvent done[kParamSlots];
+    int cur = kParamSlots - 1;                                // the entry of the last acquire()
+    ~PinnedRing() { if (host) (void)hipHostFree(host); }
+    // at least `bytes` per entry (kept a multiple of 16: copy16_async takes its widest path from every entry)
+    int reserve(size_t bytes) {
+        if (bytes <= entry_bytes) return PMHIP_OK;
+        for (auto& e : done)
+            if (e.h) PM_HIP(hipEventSynchronize(e.h));        // copies still reading the old ring
+        if (host) { PM_HIP(hipHostFree(host)); host = nullptr; entry_bytes = 0; }
+        const size_t want = (bytes + 15) & ~(size_t)15;
+        PM_HIP(hipHostMalloc(&host, want * kParamSlots));
+        entry_bytes = want;
+        return PMHIP_OK;
+    }
+    int acquire() {
+        cur = (cur + 1) % kParamSlots;
+        hipEvent_t e;
+        PM_TRY(done[cur].get(hipEventDisableTiming, e));
+        PM_HIP(hipEventSynchronize(e));                       // the copy that last read this entry (no-op when never recorded)
+        return PMHIP_OK;
+    }
+    // src[0 .. bytes) -> the entry at `offset` -> dst, by a kernel on `s` that reads the entry through its device alias
+    int stage(void* dst, size_t offset, const void* src, size_t bytes, hipStream_t s) {
+        unsigned char* at = host + (size_t)cur * entry_bytes + offset;
+        memcpy(at, src, bytes);
+        void* alias = nullptr;
+        PM_HIP(hipHostGetDevicePointer(&alias, at, 0));
+        return copy16_async(dst, alias, bytes, s);
+    }
+    int commit(hipStream_t s) {                               // after the last stage() of the entry
+        PM_HIP(hipEventRecord(done[cur].h, s));
+        return PMHIP_OK;
+    }
+};
+
 struct GraphEntry {
     bool warmed = false;            // one eager pass has sized every workspace buffer
     std::vector<hipGraphExec_t> segs;   // one executable graph per segment (a segment ends with a decoded step)
     uint64_t s2_gen = 0, vq_gen = 0;   // workspace generations the graphs' baked-in pointers belong to
+    GraphEntry() = default;
+    GraphEntry(const GraphEntry&) = delete;
+    GraphEntry& operator=(const GraphEntry&) = delete;
+    ~GraphEntry() { destroy(); }
     void destroy() {
         for (auto e : segs)
             if (e) (void)hipGraphExecDestroy(e);
         segs.clear();
     }
 };
+
+}  // namespace
 
 struct pmhip_s2 {
     int device = 0, dtype = 0;
@@ -685,33 +753,23 @@ struct pmhip_s2 {
     Switches sw = Switches::from_env();
     bool pos_split = false;         // bf16 mode: position embedding split into hi / lo planes (ws "pos.*")
     std::map<std::string, GraphEntry> graphs;   // captured decode loops, keyed by shape / schedule structure
-    hipStream_t capture_stream = nullptr;       // capture never happens on the caller's stream (it may be the NULL stream)
+    OwnedStream capture_stream;                 // capture_graph
     // small batches: the ViT decode of step t runs on a side stream BESIDE the tower of step t + 1 (fork / join by events, inside
     // the captured graphs too)
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // per-call scalars travel through PINNED host slots (a pageable source makes hipMemcpyAsync stage synchronously);
-    // a slot is reused only after the copy that read it has completed
-    static constexpr int kParamSlots = 4;
-    PmGenParams* params_host = nullptr;
-    hipEvent_t params_done[kParamSlots] = {};
-    int params_next = 0;
-    // per-image decode state (pmhip_pipeline_step_slots): the host records travel through a pinned ring of their own (kParamSlots
-    // entries of slots_cap records; an entry is reused only after the copy that read it has completed), and the handle remembers
-    // which context the last slots call prepared (slots_ctx_L: 0 = prepared without a context, -1 = nothing a slots call may reuse)
-    // (a call with guidance stages its pmhip_slot_guide records through the same ring: entry e of guides_host travels with entry e of
-    // slots_host and is guarded by the same event; slots_one_pass / slots_two_pass count the steps by tower passes)
-    pmhip_slot* slots_host = nullptr;
-    pmhip_slot_guide* guides_host = nullptr;
-    int slots_cap = 0;
+    OwnedStream side_stream;
+    OwnedEvent ev_fork, ev_join;
+    PinnedRing params_ring;         // pipeline_generate: one PmGenParams per call
+    // per-image decode state (pmhip_pipeline_step_slots): an entry of the ring holds B pmhip_slot records and, behind them, the B
+    // pmhip_slot_guide records of a call with guidance (they travel under the entry's one event); the handle remembers which
+    // context the last slots call prepared (slots_ctx_L: 0 = prepared without a context, -1 = nothing a slots call may reuse);
+    // slots_one_pass / slots_two_pass count the steps by tower passes
+    PinnedRing slots_ring;
     int slots_one_pass = 0, slots_two_pass = 0;
-    hipEvent_t slots_done[kParamSlots] = {};
-    int slots_next = 0;
     int slots_ctx_B = 0, slots_ctx_L = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
     // its previous record may still be queued); last D2H complete -> next call
-    std::vector<hipEvent_t> img_ready;
-    hipEvent_t host_copied = nullptr;
+    std::vector<OwnedEvent> img_ready;
+    OwnedEvent host_copied;
     bool host_copy_pending = false;
     // the shared step 0 of unconditional loops that start from the all-mask state (PMHIP_GENERATE_FROM_MASK): the logits and block
     // statistics of ONE all-mask image (workspace "s0.logits" / "s0.lstats", fixed size) are a function of the weights alone,
@@ -719,25 +777,7 @@ struct pmhip_s2 {
     bool s0_valid = false;
     int s0_fills = 0, s0_hits = 0;
     hipStream_t s0_stream = nullptr;            // the stream that filled the buffers: a loop on another stream waits for s0_ready
-    hipEvent_t s0_ready = nullptr;
-    ~pmhip_s2() {
-        for (auto& kv : graphs) kv.second.destroy();
-        if (capture_stream) (void)hipStreamDestroy(capture_stream);
-        if (side_stream) (void)hipStreamDestroy(side_stream);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-        if (params_host) (void)hipHostFree(params_host);
-        if (slots_host) (void)hipHostFree(slots_host);
-        if (guides_host) (void)hipHostFree(guides_host);
-        for (auto e : slots_done)
-            if (e) (void)hipEventDestroy(e);
-        for (auto e : params_done)
-            if (e) (void)hipEventDestroy(e);
-        for (auto e : img_ready)
-            if (e) (void)hipEventDestroy(e);
-        if (host_copied) (void)hipEventDestroy(host_copied);
-        if (s0_ready) (void)hipEventDestroy(s0_ready);
-    }
+    OwnedEvent s0_ready;
 };
 
 extern "C" int pmhip_s2_create(pmhip_s2** out, int device, int dtype, const pmhip_s2_cfg* cfg, const pmhip_s2_weights* w) {
@@ -841,107 +881,112 @@ int s2_tower(pmhip_s2* h, const void* tp, int B, float* logits, hipStream_t s, b
 // The step in two halves, so that a caller can put something between the tower and the sampling (the small-batch loop joins the
 // previous step's decode there).  step_tower: ids2tokens + the tower(s) -> logits.  step_tail: sampling, the optional decode,
 // the optional copies, re-masking.
-// the buffers the two halves share: the logits, and the softmax statistics of their 64-column blocks for the sampling kernel (NULL:
-// it derives them)
-int step_bufs(pmhip_s2* s2, int M, float*& logits, float*& lstats, hipStream_t s) {
-    const auto& c = s2->cfg;
-    WS(s2->ws, "s2.logits", (size_t)M * c.n_embed * 4, logits);
-    lstats = nullptr;
-    if (c.n_embed % 64 == 0 && s2->sw.logits_stats) WS(s2->ws, "s2.lstats", (size_t)M * (c.n_embed / 64) * 8, lstats);
+// the buffers the two halves share: the logits, the softmax statistics of their 64-column blocks for the sampling kernel (NULL:
+// it derives them), and the predictions and scores the sampling leaves for the decode, the copies and the re-masking
+struct StepBufs {
+    float* logits = nullptr; float* lstats = nullptr;
+    int64_t* pred = nullptr; float* score = nullptr;
+};
+
+int pred_bufs(pmhip_s2* s2, size_t M, StepBufs& b, hipStream_t s) {
+    WS(s2->ws, "s2.pred", M * 8, b.pred);
+    WS(s2->ws, "s2.score", M * 4, b.score);
     return PMHIP_OK;
 }
 
-// the same two buffers for ONE image, kept: the shared step 0 (pmhip_s2::s0_valid)
-int step0_bufs(pmhip_s2* s2, float*& logits, float*& lstats, hipStream_t s) {
+// shared0: the logits and statistics are those of ONE image, kept: the shared step 0 (pmhip_s2::s0_valid)
+int step_bufs(pmhip_s2* s2, int M, bool shared0, StepBufs& b, hipStream_t s) {
     const auto& c = s2->cfg;
-    WS(s2->ws, "s0.logits", (size_t)c.tokens * c.n_embed * 4, logits);
-    lstats = nullptr;
-    if (c.n_embed % 64 == 0 && s2->sw.logits_stats) WS(s2->ws, "s0.lstats", (size_t)c.tokens * (c.n_embed / 64) * 8, lstats);
+    const size_t rows = shared0 ? c.tokens : M;
+    WS(s2->ws, shared0 ? "s0.logits" : "s2.logits", rows * c.n_embed * 4, b.logits);
+    b.lstats = nullptr;
+    if (c.n_embed % 64 == 0 && s2->sw.logits_stats) WS(s2->ws, shared0 ? "s0.lstats" : "s2.lstats", rows * (c.n_embed / 64) * 8, b.lstats);
+    return pred_bufs(s2, (size_t)M, b, s);
+}
+
+// the tower's input rows, T [M,64]
+int tok_buf(pmhip_s2* s2, int M, void*& tp, hipStream_t s) {
+    WS(s2->ws, "s2.tok", (size_t)M * 64 * dtype_size(s2->dtype), tp);
     return PMHIP_OK;
 }
 
-int step_tower(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s, const float* guidance) {
+// ids2tokens: lookup in cat(raw codebook, mask_token) (generate.py:148-157)
+int step_tokens(pmhip_s2* s2, const int64_t* ids, int M, void*& tp, hipStream_t s) {
+    PM_TRY(tok_buf(s2, M, tp, s));
+    return pmhip_embed_rows(s2->w.tok_table, ids, tp, s2->dtype, 64, M, s2->cfg.n_embed + 1, s2->cfg.embed_dim, s);
+}
+
+// the optional copies of a step's predictions and scores
+int copy_aux(const StepBufs& b, size_t M, int64_t* pred_out, float* score_out, hipStream_t s) {
+    if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, b.pred, M * 8, hipMemcpyDeviceToDevice, s));
+    if (score_out) PM_HIP(hipMemcpyAsync(score_out, b.score, M * 4, hipMemcpyDeviceToDevice, s));
+    return PMHIP_OK;
+}
+
+// guides != nullptr (with the device records `slots`): per-image guidance (pmhip_pipeline_step_slots_guided).  BOTH towers for the
+// whole batch, the first one with the logits GEMM's block statistics (the same logits as without them, bit for bit:
+// tests/test_gpu_abi_memory.py), then the combination in place on the rows of the guided images only -- an unguided image keeps
+// the first tower's logits and statistics, i.e. exactly what the one-pass step leaves for it
+int step_tower(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s, const float* guidance, const pmhip_slot* slots = nullptr,
+               const pmhip_slot_guide* guides = nullptr) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
-    void* tp; float* logits; float* lstats;
-    WS(s2->ws, "s2.tok", (size_t)M * 64 * dtype_size(s2->dtype), tp);
-    PM_TRY(step_bufs(s2, M, logits, lstats, s));
-    // ids2tokens: lookup in cat(raw codebook, mask_token) (generate.py:148-157)
-    PM_TRY(pmhip_embed_rows(s2->w.tok_table, ids, tp, s2->dtype, 64, M, c.n_embed + 1, c.embed_dim, s));
-    // the statistics come from the logits GEMM, or -- guided -- from the combination, which produces the logits that are sampled
-    PM_TRY(s2_tower(s2, tp, B, logits, s, true, guidance ? nullptr : lstats));
-    if (guidance) {
-        float* uncond;
-        WS(s2->ws, "s2.logits_u", (size_t)M * c.n_embed * 4, uncond);
-        PM_TRY(s2_tower(s2, tp, B, uncond, s, false));
-        if (lstats) PM_TRY(pmhip_guidance_combine_stats(logits, uncond, *guidance, logits, (size_t)M * c.n_embed, lstats, s));
-        else PM_TRY(pmhip_guidance_combine(logits, uncond, *guidance, logits, (size_t)M * c.n_embed, s));
-    }
-    return PMHIP_OK;
-}
-
-// step_tower with per-image guidance (pmhip_pipeline_step_slots_guided): BOTH towers for the whole batch, the first one with the
-// logits GEMM's block statistics (the same logits as without them, bit for bit: tests/test_gpu_abi_memory.py), then the combination
-// in place on the rows of the guided images only -- an unguided image keeps the first tower's logits and statistics, i.e. exactly
-// what step_tower leaves for it
-int step_tower_guided_slots(pmhip_s2* s2, const int64_t* ids, int B, const pmhip_slot* slots, const pmhip_slot_guide* guides, hipStream_t s) {
-    const auto& c = s2->cfg;
-    const int M = B * c.tokens;
-    void* tp; float* logits; float* lstats; float* uncond;
-    WS(s2->ws, "s2.tok", (size_t)M * 64 * dtype_size(s2->dtype), tp);
-    PM_TRY(step_bufs(s2, M, logits, lstats, s));
+    void* tp; StepBufs b;
+    PM_TRY(step_tokens(s2, ids, M, tp, s));
+    PM_TRY(step_bufs(s2, M, false, b, s));
+    // the statistics come from the logits GEMM, or -- one scale for the batch -- from the combination, which produces the logits
+    // that are sampled
+    PM_TRY(s2_tower(s2, tp, B, b.logits, s, true, guidance ? nullptr : b.lstats));
+    if (!guidance && !guides) return PMHIP_OK;
+    float* uncond;
     WS(s2->ws, "s2.logits_u", (size_t)M * c.n_embed * 4, uncond);
-    PM_TRY(pmhip_embed_rows(s2->w.tok_table, ids, tp, s2->dtype, 64, M, c.n_embed + 1, c.embed_dim, s));
-    PM_TRY(s2_tower(s2, tp, B, logits, s, true, lstats));
     PM_TRY(s2_tower(s2, tp, B, uncond, s, false));
-    return pmhip_guidance_combine_slots(logits, uncond, guides, slots, c.tokens, logits, lstats, M, c.n_embed, s);
+    if (guides) return pmhip_guidance_combine_slots(b.logits, uncond, guides, slots, c.tokens, b.logits, b.lstats, M, c.n_embed, s);
+    if (b.lstats) return pmhip_guidance_combine_stats(b.logits, uncond, *guidance, b.logits, (size_t)M * c.n_embed, b.lstats, s);
+    return pmhip_guidance_combine(b.logits, uncond, *guidance, b.logits, (size_t)M * c.n_embed, s);
 }
 
 // the image of the predictions the last step_tail left in the handle's `s2.pred` (decoded from pred at ALL positions, generate.py:165)
 int decode_pred(pmhip_s2* s2, pmhip_vqgan* vq, int B, float* img_out, hipStream_t s) {
     PM_REQUIRE(vq, "pipeline_sample: img_out requested without a vqgan handle");
-    int64_t* pred;
-    WS(s2->ws, "s2.pred", (size_t)B * s2->cfg.tokens * 8, pred);
-    return vq_decode_indices(vq, pred, B, img_out, s);
+    StepBufs b;
+    PM_TRY(pred_bufs(s2, (size_t)B * s2->cfg.tokens, b, s));
+    return vq_decode_indices(vq, b.pred, B, img_out, s);
 }
 
-int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, int topk, float temperature, int num_mask, const float* noise,
-              uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out, float* score_out, hipStream_t s,
-              const PmGenParams* gp, bool shared0 = false) {
+// what a step samples and re-masks by: one set of values for the batch (gp != nullptr: temperature, mask count, seed and row base
+// come from the device parameter block instead; shared0: every image samples from the one all-mask image's rows) ...
+struct StepScalars {
+    int topk = 0; float temperature = 0.f; int num_mask = 0;
+    const float* noise = nullptr;
+    uint64_t seed = 0; uint32_t step = 0; uint64_t image_base = 0;
+    const PmGenParams* gp = nullptr;
+    bool shared0 = false;
+};
+
+// ... or, slots != nullptr, every per-image value read from the device records `slots` [B] (sc is not looked at)
+int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, const StepScalars& sc, const pmhip_slot* slots, float* img_out,
+              int64_t* pred_out, float* score_out, hipStream_t s) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
-    float* logits; float* lstats; int64_t* pred; float* score;
-    if (shared0) PM_TRY(step0_bufs(s2, logits, lstats, s));  // every image samples from the one all-mask image's rows
-    else PM_TRY(step_bufs(s2, M, logits, lstats, s));        // step_tower filled them
-    WS(s2->ws, "s2.pred", (size_t)M * 8, pred);
-    WS(s2->ws, "s2.score", (size_t)M * 4, score);
-    PM_TRY(pm_sample_rows(logits, c.n_embed, lstats, ids, (int64_t)c.n_embed, topk, temperature, noise, seed, step,
-                          image_base * (uint64_t)c.tokens, pred, ids, score, M, c.n_embed, gp, shared0 ? c.tokens : 0, s));
+    const bool shared0 = !slots && sc.shared0;
+    StepBufs b;
+    PM_TRY(step_bufs(s2, M, shared0, b, s));                  // step_tower (or the shared step 0) filled the logits
+    if (slots)
+        PM_TRY(pm_sample_rows_slots(b.logits, c.n_embed, b.lstats, ids, (int64_t)c.n_embed, slots, c.tokens, b.pred, ids, b.score, M, c.n_embed, s));
+    else
+        PM_TRY(pm_sample_rows(b.logits, c.n_embed, b.lstats, ids, (int64_t)c.n_embed, sc.topk, sc.temperature, sc.noise, sc.seed, sc.step,
+                              sc.image_base * (uint64_t)c.tokens, b.pred, ids, b.score, M, c.n_embed, sc.gp, shared0 ? c.tokens : 0, s));
     if (img_out) PM_TRY(decode_pred(s2, vq, B, img_out, s));
-    if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
-    if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
-    return pm_remask(ids, score, num_mask, (int64_t)c.n_embed, B, c.tokens, gp, (int)step, s);
+    PM_TRY(copy_aux(b, (size_t)M, pred_out, score_out, s));
+    if (slots) return pm_remask_slots(ids, b.score, slots, (int64_t)c.n_embed, B, c.tokens, s);
+    return pm_remask(ids, b.score, sc.num_mask, (int64_t)c.n_embed, B, c.tokens, sc.gp, (int)sc.step, s);
 }
 
-// step_tail with every per-image value read from the device records `slots` [B] (no image: the caller decodes finished rows only)
-int step_tail_slots(pmhip_s2* s2, int64_t* ids, int B, const pmhip_slot* slots, int64_t* pred_out, float* score_out, hipStream_t s) {
-    const auto& c = s2->cfg;
-    const int M = B * c.tokens;
-    float* logits; float* lstats; int64_t* pred; float* score;
-    PM_TRY(step_bufs(s2, M, logits, lstats, s));             // step_tower filled them
-    WS(s2->ws, "s2.pred", (size_t)M * 8, pred);
-    WS(s2->ws, "s2.score", (size_t)M * 4, score);
-    PM_TRY(pm_sample_rows_slots(logits, c.n_embed, lstats, ids, (int64_t)c.n_embed, slots, c.tokens, pred, ids, score, M, c.n_embed, s));
-    if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, (size_t)M * 8, hipMemcpyDeviceToDevice, s));
-    if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, (size_t)M * 4, hipMemcpyDeviceToDevice, s));
-    return pm_remask_slots(ids, score, slots, (int64_t)c.n_embed, B, c.tokens, s);
-}
-
-int sample_step(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, int topk, float temperature, int num_mask,
-                const float* noise, uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
-                float* score_out, hipStream_t s, const PmGenParams* gp = nullptr, const float* guidance = nullptr) {
+int sample_step(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, const StepScalars& sc, float* img_out, int64_t* pred_out,
+                float* score_out, hipStream_t s, const float* guidance = nullptr) {
     PM_TRY(step_tower(s2, ids, B, s, guidance));
-    return step_tail(s2, vq, ids, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out, score_out, s, gp);
+    return step_tail(s2, vq, ids, B, sc, nullptr, img_out, pred_out, score_out, s);
 }
 
 // The tower half of step 0 of an unconditional loop from the all-mask state (ids: B all-mask images).  Its input is the same for
@@ -953,17 +998,83 @@ int step0_tower_once(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s) {
     if (s2->s0_valid) return PMHIP_OK;
     PM_REQUIRE(!s2->ws.frozen, "pipeline_generate: the shared step-0 logits are missing during a graph capture");
     const auto& c = s2->cfg;
-    float* logits; float* lstats; float* l0; float* st0;
-    PM_TRY(step0_bufs(s2, l0, st0, s));
+    StepBufs kept, b;
+    PM_TRY(step_bufs(s2, B * c.tokens, true, kept, s));
     PM_TRY(step_tower(s2, ids, B, s, nullptr));
-    PM_TRY(step_bufs(s2, B * c.tokens, logits, lstats, s));
-    PM_TRY(copy16_async(l0, logits, (size_t)c.tokens * c.n_embed * 4, s));
-    if (st0) PM_TRY(copy16_async(st0, lstats, (size_t)c.tokens * (c.n_embed / 64) * 8, s));
-    if (!s2->s0_ready) PM_HIP(hipEventCreateWithFlags(&s2->s0_ready, hipEventDisableTiming));
-    PM_HIP(hipEventRecord(s2->s0_ready, s));
+    PM_TRY(step_bufs(s2, B * c.tokens, false, b, s));
+    PM_TRY(copy16_async(kept.logits, b.logits, (size_t)c.tokens * c.n_embed * 4, s));
+    if (kept.lstats) PM_TRY(copy16_async(kept.lstats, b.lstats, (size_t)c.tokens * (c.n_embed / 64) * 8, s));
+    hipEvent_t ready;
+    PM_TRY(s2->s0_ready.get(hipEventDisableTiming, ready));
+    PM_HIP(hipEventRecord(ready, s));
     s2->s0_stream = s;
     s2->s0_valid = true;
     ++s2->s0_fills;
+    return PMHIP_OK;
+}
+
+// One executable graph of what record(stream) launches, captured on the handle's own stream (never the caller's: it may be the
+// NULL stream) with both workspaces frozen; a library error from the recorded launches takes precedence over the HIP error.
+template <typename Record>
+int capture_graph(pmhip_s2* s2, pmhip_vqgan* vq, hipGraphExec_t* exec, Record&& record) {
+    hipStream_t cap;
+    PM_TRY(s2->capture_stream.get(hipStreamNonBlocking, cap));
+    hipGraph_t g = nullptr;
+    hipError_t rc;
+    int unit_rc = PMHIP_OK;
+    {
+        struct Freeze {                                       // growing a workspace during the capture would be a bug
+            Workspace& a; Workspace* b;
+            Freeze(Workspace& a_, Workspace* b_) : a(a_), b(b_) { a.frozen = true; if (b) b->frozen = true; }
+            ~Freeze() { a.frozen = false; if (b) b->frozen = false; }
+        } freeze(s2->ws, vq ? &vq->ws : nullptr);
+        rc = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
+        if (rc == hipSuccess) {
+            unit_rc = record(cap);                            // records only: nothing executes during capture
+            rc = hipStreamEndCapture(cap, &g);
+        }
+    }
+    if (unit_rc == PMHIP_OK && rc == hipSuccess) rc = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+    if (g) (void)hipGraphDestroy(g);
+    PM_TRY(unit_rc);
+    PM_HIP(rc);
+    return PMHIP_OK;
+}
+
+// The graphs of one captured loop (ge: its entry in s2->graphs): n_units executable graphs, unit i = what run_unit(stream, i)
+// launches.  The first call for an entry runs the units eagerly, which sizes every workspace buffer; the second captures them;
+// every later one replays.  after(i) runs behind unit i, however it was run.  vq: the vqgan handle whose buffers the units use
+// (NULL: none).
+template <typename RunUnit, typename After>
+int run_graphs(pmhip_s2* s2, pmhip_vqgan* vq, GraphEntry& ge, size_t n_units, hipStream_t s, RunUnit&& run_unit, After&& after) {
+    if (!ge.warmed) {
+        for (size_t i = 0; i < n_units; ++i) {                // eager once: sizes every workspace buffer
+            PM_TRY(run_unit(s, i));
+            PM_TRY(after(i));
+        }
+        ge.warmed = true;
+        return PMHIP_OK;
+    }
+    // a workspace buffer of either handle was reallocated since the capture (a later call with a larger batch, a
+    // longer context, a direct encode/decode on the shared vqgan handle ...): the graphs' pointers are stale
+    if (!ge.segs.empty() && (ge.s2_gen != s2->ws.gen || (vq && ge.vq_gen != vq->ws.gen))) {
+        PM_HIP(hipStreamSynchronize(s));                      // an earlier replay may still be running
+        ge.destroy();
+    }
+    if (ge.segs.empty()) {
+        for (size_t i = 0; i < n_units; ++i) {
+            hipGraphExec_t exec = nullptr;
+            const int rc = capture_graph(s2, vq, &exec, [&](hipStream_t cap) { return run_unit(cap, i); });
+            if (rc != PMHIP_OK) { ge.destroy(); return rc; }
+            ge.segs.push_back(exec);
+        }
+        ge.s2_gen = s2->ws.gen;
+        ge.vq_gen = vq ? vq->ws.gen : 0;
+    }
+    for (size_t i = 0; i < n_units; ++i) {
+        PM_HIP(hipGraphLaunch(ge.segs[i], s));
+        PM_TRY(after(i));
+    }
     return PMHIP_OK;
 }
 
@@ -976,7 +1087,7 @@ extern "C" int pmhip_s2_forward(pmhip_s2* h, const float* tokens, const float* c
     const int M = B * h->cfg.tokens;
     PM_TRY(s2_prepare_context(h, context, L, B, s));
     void* tp;
-    WS(h->ws, "s2.tok", (size_t)M * 64 * dtype_size(h->dtype), tp);
+    PM_TRY(tok_buf(h, M, tp, s));
     PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
     return s2_tower(h, tp, B, logits_out, s);
 }
@@ -988,7 +1099,7 @@ extern "C" int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids
     PM_REQUIRE(s2 && ids && B > 0, "pipeline_sample: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     PM_TRY(s2_prepare_context(s2, context, L, B, s));
-    return sample_step(s2, vq, ids, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+    return sample_step(s2, vq, ids, B, StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out,
                        score_out, s);
 }
 
@@ -1000,8 +1111,8 @@ extern "C" int pmhip_pipeline_sample_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64
     PM_REQUIRE(context && L > 0, "pipeline_sample_guided: guidance needs a context (context NULL IS the unconditional branch)");
     hipStream_t s = (hipStream_t)stream;
     PM_TRY(s2_prepare_context(s2, context, L, B, s));
-    return sample_step(s2, vq, ids, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
-                       score_out, s, nullptr, &guidance_scale);
+    return sample_step(s2, vq, ids, B, StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out,
+                       score_out, s, &guidance_scale);
 }
 
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
@@ -1010,106 +1121,146 @@ static bool direct_dispatch_off() {
     return off;
 }
 
-static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
-                             int T, const float* temps_host, const int* nmask_host,
-                             const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
-                             float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
-                             size_t host_stride, pmhip_stream copy_stream, const float* guidance) {
-    PM_REQUIRE(s2 && ids && B > 0 && T > 0 && temps_host && nmask_host, "pipeline_generate: bad arguments");
-    PM_REQUIRE(!guidance || (context && L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
-    hipStream_t s = (hipStream_t)stream;
-    hipStream_t cs = copy_stream ? (hipStream_t)copy_stream : s;
-    PM_TRY(s2_prepare_context(s2, context, L, B, s));         // context projection + cross K/V: once per loop, eager
-    size_t img_elems = 0;
-    if (vq) img_elems = (size_t)B * vq->cfg.channels * vq->cfg.image_size * vq->cfg.image_size;
-    int n_dec = 0;
-    for (int t = 0; t < T; ++t) n_dec += (decode_host && decode_host[t]) ? 1 : 0;
-    PM_REQUIRE(n_dec == 0 || (vq && (imgs_out || imgs_host)), "pipeline_generate: decode requested without vqgan / an image destination");
-    PM_REQUIRE(!imgs_host || host_stride >= img_elems, "pipeline_generate: host_stride smaller than one image batch");
-    // AMD_DIRECT_DISPATCH=0 (the runtime mode without the busy-polling helper thread): hipGraph replay is broken there on ROCm 7.2
-    // -- tools/hwtests/graph_dispatch_mode.hip, 39 of 40 replays of a chain of dependent kernels wrong with none of this library's
-    // code involved -- so the loop stays eager in that mode whatever the caller asked for (same results, bit for bit)
-    // pmhip_s2_switches reports the downgrade (bit 5) so that a caller can tell which mode ran
-    const bool graph = (use_graph & PMHIP_GENERATE_GRAPH) && !g_pm_timing_on.load() && T <= PM_MAX_STEPS && !direct_dispatch_off();
-    // PMHIP_GENERATE_FROM_MASK: the loop starts from the all-mask state -- the library writes that state itself, so the claim
-    // cannot be false -- and, without a context, step 0 samples from the handle's shared step-0 logits instead of running the tower
-    // (step0_tower_once).  Not while per-kernel timing is on: the timed pass accounts for the work of all T tower passes.
-    const bool from_mask = (use_graph & PMHIP_GENERATE_FROM_MASK) != 0;
-    const bool share0 = from_mask && !context && !guidance && !g_pm_timing_on.load();
-    const size_t n_ids = (size_t)B * s2->cfg.tokens;
-    if (share0 && s2->s0_valid) {
-        ++s2->s0_hits;
-        if (s != s2->s0_stream) PM_HIP(hipStreamWaitEvent(s, s2->s0_ready, 0));
-    }
-    // the tower half of step t
-    auto tower = [&](const int64_t* from, int t, hipStream_t on) -> int {
-        if (share0 && t == 0) return step0_tower_once(s2, from, B, on);
-        return step_tower(s2, from, B, on, guidance);
-    };
+namespace {
 
-    if (imgs_host) {
-        // PMHIP_BLOCKING_WAIT=1 (read when the handle is created): the lane's host thread SLEEPS in hipEventSynchronize while its
-        // segment runs instead of spinning -- frees a core per lane on a host that is short of them, at 0.6 ms of wake-up latency
-        // per saved image (measured: the drop-in generate() 151 vs 141 ms per call), hence off by default
-        const unsigned evflags = hipEventDisableTiming | (s2->sw.blocking_wait ? hipEventBlockingSync : 0u);
-        if (!s2->host_copied) PM_HIP(hipEventCreateWithFlags(&s2->host_copied, evflags));
-        while ((int)s2->img_ready.size() < n_dec) {
-            hipEvent_t e;
-            PM_HIP(hipEventCreateWithFlags(&e, evflags));
-            s2->img_ready.push_back(e);
-        }
+// the arguments of pmhip_pipeline_generate(_guided), include/pmhip.h
+struct GenCall {
+    pmhip_s2* s2; pmhip_vqgan* vq; int64_t* ids; const float* context; int L, B, T;
+    const float* temps_host; const int* nmask_host; const unsigned char* decode_host;
+    int topk; uint64_t seed, image_base; float* imgs_out; int use_graph; pmhip_stream stream;
+    float* imgs_host; size_t host_stride; pmhip_stream copy_stream;
+    const float* guidance = nullptr;
+    bool decodes(int t) const { return decode_host && decode_host[t]; }
+};
+
+// A unit = one executable graph.  Normally a unit is a SEGMENT [t0, t1) (t1 - 1 is a decoded step, or the end of the loop) whose
+// last step decodes in place and whose image is complete when the unit is.  Small batches (B * tokens <= overlap_rows: every
+// kernel is a few dozen workgroups on 256 CUs and the loop is one long dependent chain) DEFER the decode instead: the ViT decode
+// of a segment's last step opens the NEXT unit on a side stream, beside that unit's first tower pass (which only needs the ids),
+// and is joined before the first sampling kernel overwrites the predictions it reads; a last unit without steps decodes the
+// final image.  Same kernels, same inputs: bit-identical images, one unit later.
+struct Unit { int t0, t1, decode_first, delivers; bool decode_inline; };
+
+std::vector<Unit> plan_units(const GenCall& c, bool overlap) {
+    std::vector<Unit> units;
+    int d = 0, pend = -1;
+    for (int t = 0, t0 = 0; t < c.T; ++t) {
+        const bool dec = c.decodes(t);
+        if (!dec && t != c.T - 1) continue;
+        if (overlap) { units.push_back({t0, t + 1, pend, pend, false}); pend = dec ? d++ : -1; }
+        else units.push_back({t0, t + 1, -1, dec ? d++ : -1, true});
+        t0 = t + 1;
     }
-    // images are produced into a handle-owned buffer when a graph bakes the pointer in or when the caller only wants the
-    // host copy; that buffer must not be overwritten while the previous call's last device-to-host copy still reads it
-    float* gimgs = nullptr;
-    if (n_dec && (graph || !imgs_out)) {
-        WS(s2->ws, "gen.imgs", (size_t)n_dec * img_elems * 4 + 16, gimgs);
-        if (s2->host_copy_pending) { PM_HIP(hipStreamWaitEvent(s, s2->host_copied, 0)); s2->host_copy_pending = false; }
-    }
-    // Image d is complete on `s` after the step that decodes it.  Device destination: a copy on `s`.  Host destination: the
-    // copy must run on the copy stream UNDER the following steps, but it is not made to wait there by a cross-stream event:
-    // a barrier packet parked at the head of the copy queue until a whole segment has run starves the other lane's queue
-    // on this part (measured: two lanes with such waits run one after the other, 164 vs 138 ms per call).  Instead the HOST
-    // paces the loop, like the reference's blocking `img.cpu()` per saved step (generate.py:195-196): once the next
-    // segment is queued it waits for image d's event and enqueues a copy that can start at once.  The caller runs
-    // concurrent lanes from one thread each (the ctypes call drops the GIL).
+    if (pend >= 0) units.push_back({c.T, c.T, pend, pend, false});
+    return units;
+}
+
+// Image d is complete on `s` after the step that decodes it.  Device destination: a copy on `s`.  Host destination: the
+// copy must run on the copy stream UNDER the following steps, but it is not made to wait there by a cross-stream event:
+// a barrier packet parked at the head of the copy queue until a whole segment has run starves the other lane's queue
+// on this part (measured: two lanes with such waits run one after the other, 164 vs 138 ms per call).  Instead the HOST
+// paces the loop, like the reference's blocking `img.cpu()` per saved step (generate.py:195-196): once the next
+// segment is queued it waits for image d's event and enqueues a copy that can start at once.  The caller runs
+// concurrent lanes from one thread each (the ctypes call drops the GIL).
+// Per unit or step, in this order: run it, flush(), deliver().
+struct HostDelivery {
+    const GenCall& c;
+    hipStream_t s, cs;
+    size_t img_elems;
+    int n_dec;
+    bool handle_buffer;                                       // the images are produced into the handle's "gen.imgs"
     int pending = -1;                                         // decoded image whose host copy has not been enqueued yet
     const float* pending_src = nullptr;
-    auto flush_pending = [&]() -> int {
+    int flush() {
         if (pending < 0) return PMHIP_OK;
-        if (cs != s) PM_HIP(hipEventSynchronize(s2->img_ready[pending]));
-        PM_HIP(hipMemcpyAsync(imgs_host + (size_t)pending * host_stride, pending_src, img_elems * 4, hipMemcpyDeviceToHost, cs));
-        if (pending == n_dec - 1 && gimgs) {
-            PM_HIP(hipEventRecord(s2->host_copied, cs));
-            s2->host_copy_pending = cs != s;
+        if (cs != s) PM_HIP(hipEventSynchronize(c.s2->img_ready[pending].h));
+        PM_HIP(hipMemcpyAsync(c.imgs_host + (size_t)pending * c.host_stride, pending_src, img_elems * 4, hipMemcpyDeviceToHost, cs));
+        if (pending == n_dec - 1 && handle_buffer) {
+            PM_HIP(hipEventRecord(c.s2->host_copied.h, cs));
+            c.s2->host_copy_pending = cs != s;
         }
         pending = -1;
         return PMHIP_OK;
-    };
-    auto deliver = [&](int d, const float* src) -> int {
-        if (imgs_out && src != imgs_out + (size_t)d * img_elems)
-            PM_HIP(hipMemcpyAsync(imgs_out + (size_t)d * img_elems, src, img_elems * 4, hipMemcpyDeviceToDevice, s));
-        if (imgs_host) {
-            if (cs != s) PM_HIP(hipEventRecord(s2->img_ready[d], s));
+    }
+    int deliver(int d, const float* src) {
+        if (c.imgs_out && src != c.imgs_out + (size_t)d * img_elems)
+            PM_HIP(hipMemcpyAsync(c.imgs_out + (size_t)d * img_elems, src, img_elems * 4, hipMemcpyDeviceToDevice, s));
+        if (c.imgs_host) {
+            if (cs != s) PM_HIP(hipEventRecord(c.s2->img_ready[d].h, s));
             pending = d;
             pending_src = src;
         }
         return PMHIP_OK;
+    }
+};
+
+int pipeline_generate(const GenCall& c) {
+    pmhip_s2* s2 = c.s2; pmhip_vqgan* vq = c.vq;
+    const int B = c.B, T = c.T;
+    PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && c.nmask_host, "pipeline_generate: bad arguments");
+    PM_REQUIRE(!c.guidance || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
+    hipStream_t s = (hipStream_t)c.stream;
+    hipStream_t cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
+    PM_TRY(s2_prepare_context(s2, c.context, c.L, B, s));     // context projection + cross K/V: once per loop, eager
+    size_t img_elems = 0;
+    if (vq) img_elems = (size_t)B * vq->cfg.channels * vq->cfg.image_size * vq->cfg.image_size;
+    int n_dec = 0;
+    for (int t = 0; t < T; ++t) n_dec += c.decodes(t) ? 1 : 0;
+    PM_REQUIRE(n_dec == 0 || (vq && (c.imgs_out || c.imgs_host)), "pipeline_generate: decode requested without vqgan / an image destination");
+    PM_REQUIRE(!c.imgs_host || c.host_stride >= img_elems, "pipeline_generate: host_stride smaller than one image batch");
+    // AMD_DIRECT_DISPATCH=0 (the runtime mode without the busy-polling helper thread): hipGraph replay is broken there on ROCm 7.2
+    // -- tools/hwtests/graph_dispatch_mode.hip, 39 of 40 replays of a chain of dependent kernels wrong with none of this library's
+    // code involved -- so the loop stays eager in that mode whatever the caller asked for (same results, bit for bit)
+    // pmhip_s2_switches reports the downgrade (bit 5) so that a caller can tell which mode ran
+    const bool graph = (c.use_graph & PMHIP_GENERATE_GRAPH) && !g_pm_timing_on.load() && T <= PM_MAX_STEPS && !direct_dispatch_off();
+    // PMHIP_GENERATE_FROM_MASK: the loop starts from the all-mask state -- the library writes that state itself, so the claim
+    // cannot be false -- and, without a context, step 0 samples from the handle's shared step-0 logits instead of running the tower
+    // (step0_tower_once).  Not while per-kernel timing is on: the timed pass accounts for the work of all T tower passes.
+    const bool from_mask = (c.use_graph & PMHIP_GENERATE_FROM_MASK) != 0;
+    const bool share0 = from_mask && !c.context && !c.guidance && !g_pm_timing_on.load();
+    const size_t n_ids = (size_t)B * s2->cfg.tokens;
+    if (share0 && s2->s0_valid) {
+        ++s2->s0_hits;
+        if (s != s2->s0_stream) PM_HIP(hipStreamWaitEvent(s, s2->s0_ready.h, 0));
+    }
+    // the tower half of step t
+    auto tower = [&](const int64_t* from, int t, hipStream_t on) -> int {
+        if (share0 && t == 0) return step0_tower_once(s2, from, B, on);
+        return step_tower(s2, from, B, on, c.guidance);
     };
+
+    if (c.imgs_host) {
+        // PMHIP_BLOCKING_WAIT=1 (read when the handle is created): the lane's host thread SLEEPS in hipEventSynchronize while its
+        // segment runs instead of spinning -- frees a core per lane on a host that is short of them, at 0.6 ms of wake-up latency
+        // per saved image (measured: the drop-in generate() 151 vs 141 ms per call), hence off by default
+        const unsigned evflags = hipEventDisableTiming | (s2->sw.blocking_wait ? hipEventBlockingSync : 0u);
+        hipEvent_t e;
+        PM_TRY(s2->host_copied.get(evflags, e));
+        if ((int)s2->img_ready.size() < n_dec) s2->img_ready.resize(n_dec);
+        for (int d = 0; d < n_dec; ++d) PM_TRY(s2->img_ready[d].get(evflags, e));
+    }
+    // images are produced into a handle-owned buffer when a graph bakes the pointer in or when the caller only wants the
+    // host copy; that buffer must not be overwritten while the previous call's last device-to-host copy still reads it
+    float* gimgs = nullptr;
+    if (n_dec && (graph || !c.imgs_out)) {
+        WS(s2->ws, "gen.imgs", (size_t)n_dec * img_elems * 4 + 16, gimgs);
+        if (s2->host_copy_pending) { PM_HIP(hipStreamWaitEvent(s, s2->host_copied.h, 0)); s2->host_copy_pending = false; }
+    }
+    HostDelivery out{c, s, cs, img_elems, n_dec, gimgs != nullptr};
 
     if (!graph) {
         int d = 0;
-        if (from_mask) PM_TRY(fill_ids_async(ids, (int64_t)s2->cfg.n_embed, n_ids, s));
+        if (from_mask) PM_TRY(fill_ids_async(c.ids, (int64_t)s2->cfg.n_embed, n_ids, s));
         for (int t = 0; t < T; ++t) {
-            const bool dec = decode_host && decode_host[t];
-            float* img = !dec ? nullptr : (gimgs ? gimgs : imgs_out) + (size_t)d * img_elems;
-            PM_TRY(tower(ids, t, s));
-            PM_TRY(step_tail(s2, vq, ids, B, topk, temps_host[t], nmask_host[t], nullptr, seed, (uint32_t)t, image_base, img,
-                             nullptr, nullptr, s, nullptr, share0 && t == 0));
-            PM_TRY(flush_pending());                           // the previous image, now that one more step is queued behind it
-            if (dec) PM_TRY(deliver(d++, img));
+            const bool dec = c.decodes(t);
+            float* img = !dec ? nullptr : (gimgs ? gimgs : c.imgs_out) + (size_t)d * img_elems;
+            StepScalars sc{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0};
+            PM_TRY(tower(c.ids, t, s));
+            PM_TRY(step_tail(s2, vq, c.ids, B, sc, nullptr, img, nullptr, nullptr, s));
+            PM_TRY(out.flush());                               // the previous image, now that one more step is queued behind it
+            if (dec) PM_TRY(out.deliver(d++, img));
         }
-        return flush_pending();
+        return out.flush();
     }
 
     // ---- hipGraph path.  The T-step loop is a chain of graphs, one per SEGMENT (the steps up to and including a decoded
@@ -1120,78 +1271,54 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
     int64_t* gids; PmGenParams* gparams;
     WS(s2->ws, "gen.ids", ids_bytes, gids);
     WS(s2->ws, "gen.params", sizeof(PmGenParams), gparams);
-    if (!s2->params_host) {
-        PM_HIP(hipHostMalloc((void**)&s2->params_host, sizeof(PmGenParams) * pmhip_s2::kParamSlots, hipHostMallocDefault));
-        for (auto& e : s2->params_done) PM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const int slot = s2->params_next;
-    s2->params_next = (slot + 1) % pmhip_s2::kParamSlots;
-    PM_HIP(hipEventSynchronize(s2->params_done[slot]));       // the copy that last read this slot (no-op when never recorded)
-    PmGenParams& hp = s2->params_host[slot];
-    hp.seed = seed;
-    hp.row_base = image_base * (uint64_t)s2->cfg.tokens;
-    for (int t = 0; t < T; ++t) { hp.temps[t] = temps_host[t]; hp.nmask[t] = nmask_host[t]; }
     {
-        void* hp_dev = nullptr;                               // the pinned slot through its device alias
-        PM_HIP(hipHostGetDevicePointer(&hp_dev, &hp, 0));
-        PM_TRY(copy16_async(gparams, hp_dev, sizeof hp, s));
+        PmGenParams hp;
+        hp.seed = c.seed;
+        hp.row_base = c.image_base * (uint64_t)s2->cfg.tokens;
+        for (int t = 0; t < T; ++t) { hp.temps[t] = c.temps_host[t]; hp.nmask[t] = c.nmask_host[t]; }
+        PM_TRY(s2->params_ring.reserve(sizeof hp));
+        PM_TRY(s2->params_ring.acquire());
+        PM_TRY(s2->params_ring.stage(gparams, 0, &hp, sizeof hp, s));
+        PM_TRY(s2->params_ring.commit(s));
     }
-    PM_HIP(hipEventRecord(s2->params_done[slot], s));
     if (from_mask) PM_TRY(fill_ids_async(gids, (int64_t)s2->cfg.n_embed, n_ids, s));
-    else PM_TRY(copy16_async(gids, ids, ids_bytes, s));
+    else PM_TRY(copy16_async(gids, c.ids, ids_bytes, s));
 
-    std::string key = "B" + std::to_string(B) + "T" + std::to_string(T) + "k" + std::to_string(topk) + "L" +
-                      std::to_string(context ? L : 0) + "v" + std::to_string(vq ? vq->uid : 0) + "f" +
+    std::string key = "B" + std::to_string(B) + "T" + std::to_string(T) + "k" + std::to_string(c.topk) + "L" +
+                      std::to_string(c.context ? c.L : 0) + "v" + std::to_string(vq ? vq->uid : 0) + "f" +
                       std::to_string(s2->sw.key() * 16 + (vq ? vq->sw.key() : 0));
-    if (guidance) {                                           // the scale is a kernel argument of the captured combine: one graph per value
+    if (c.guidance) {                                         // the scale is a kernel argument of the captured combine: one graph per value
         unsigned bits;
-        memcpy(&bits, guidance, 4);
+        memcpy(&bits, c.guidance, 4);
         key += "g" + std::to_string(bits);
     }
     key += "d";
-    for (int t = 0; t < T; ++t) key += (decode_host && decode_host[t]) ? '1' : '0';
-
-    // A unit = one executable graph.  Normally a unit is a SEGMENT [t0, t1) (t1 - 1 is a decoded step, or the end of the loop) whose
-    // last step decodes in place and whose image is complete when the unit is.  Small batches (B * tokens <= overlap_rows: every
-    // kernel is a few dozen workgroups on 256 CUs and the loop is one long dependent chain) DEFER the decode instead: the ViT decode
-    // of a segment's last step opens the NEXT unit on a side stream, beside that unit's first tower pass (which only needs the ids),
-    // and is joined before the first sampling kernel overwrites the predictions it reads; a last unit without steps decodes the
-    // final image.  Same kernels, same inputs: bit-identical images, one unit later.
-    struct Unit { int t0, t1, decode_first, delivers; bool decode_inline; };
-    // (not when the caller runs other lanes beside this one -- PMHIP_GENERATE_CONCURRENT_LANES: the chip is full then, and a third
-    // and fourth stream of kernels costs 5-17 % at 15-16 images per lane, profiles/r05_g_*)
+    for (int t = 0; t < T; ++t) key += c.decodes(t) ? '1' : '0';
+    // (no deferred decode when the caller runs other lanes beside this one -- PMHIP_GENERATE_CONCURRENT_LANES: the chip is full
+    // then, and a third and fourth stream of kernels costs 5-17 % at 15-16 images per lane, profiles/r05_g_*)
     const bool overlap = vq && n_dec > 0 && s2->sw.overlap_rows > 0 && (long long)B * s2->cfg.tokens <= s2->sw.overlap_rows &&
-                         !(use_graph & PMHIP_GENERATE_CONCURRENT_LANES);
-    std::vector<Unit> units;
-    {
-        int d = 0, pend = -1;
-        for (int t = 0, t0 = 0; t < T; ++t) {
-            const bool dec = decode_host && decode_host[t];
-            if (!dec && t != T - 1) continue;
-            if (overlap) { units.push_back({t0, t + 1, pend, pend, false}); pend = dec ? d++ : -1; }
-            else units.push_back({t0, t + 1, -1, dec ? d++ : -1, true});
-            t0 = t + 1;
-        }
-        if (pend >= 0) units.push_back({T, T, pend, pend, false});
-    }
+                         !(c.use_graph & PMHIP_GENERATE_CONCURRENT_LANES);
+    const std::vector<Unit> units = plan_units(c, overlap);
     key += overlap ? "o1" : "o0";
     if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
-    GraphEntry& ge = s2->graphs[key];
-    if (overlap && !s2->side_stream) {
-        PM_HIP(hipStreamCreateWithFlags(&s2->side_stream, hipStreamNonBlocking));
-        PM_HIP(hipEventCreateWithFlags(&s2->ev_fork, hipEventDisableTiming));
-        PM_HIP(hipEventCreateWithFlags(&s2->ev_join, hipEventDisableTiming));
+    hipStream_t side = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    if (overlap) {
+        PM_TRY(s2->side_stream.get(hipStreamNonBlocking, side));
+        PM_TRY(s2->ev_fork.get(hipEventDisableTiming, ev_fork));
+        PM_TRY(s2->ev_join.get(hipEventDisableTiming, ev_join));
     }
 
-    auto run_unit = [&](hipStream_t on, const Unit& u) -> int {
+    auto run_unit = [&](hipStream_t on, size_t i) -> int {
+        const Unit& u = units[i];
         bool need_join = false;
         if (u.decode_first >= 0) {
             float* img = gimgs + (size_t)u.decode_first * img_elems;
             if (u.t1 > u.t0) {                                // fork: the pending decode runs beside this unit's first tower pass
-                PM_HIP(hipEventRecord(s2->ev_fork, on));
-                PM_HIP(hipStreamWaitEvent(s2->side_stream, s2->ev_fork, 0));
-                PM_TRY(decode_pred(s2, vq, B, img, s2->side_stream));
-                PM_HIP(hipEventRecord(s2->ev_join, s2->side_stream));
+                PM_HIP(hipEventRecord(ev_fork, on));
+                PM_HIP(hipStreamWaitEvent(side, ev_fork, 0));
+                PM_TRY(decode_pred(s2, vq, B, img, side));
+                PM_HIP(hipEventRecord(ev_join, side));
                 need_join = true;
             } else {
                 PM_TRY(decode_pred(s2, vq, B, img, on));
@@ -1199,73 +1326,31 @@ static int pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const 
         }
         for (int t = u.t0; t < u.t1; ++t) {
             PM_TRY(tower(gids, t, on));
-            if (need_join) { PM_HIP(hipStreamWaitEvent(on, s2->ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
-            float* img = (u.decode_inline && decode_host && decode_host[t]) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
-            PM_TRY(step_tail(s2, vq, gids, B, topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, img, nullptr, nullptr, on, gparams,
-                             share0 && t == 0));
+            if (need_join) { PM_HIP(hipStreamWaitEvent(on, ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
+            float* img = (u.decode_inline && c.decodes(t)) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
+            StepScalars sc{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0};
+            PM_TRY(step_tail(s2, vq, gids, B, sc, nullptr, img, nullptr, nullptr, on));
         }
         return PMHIP_OK;
     };
-
-    if (!ge.warmed) {
-        for (const Unit& u : units) {                          // eager once: sizes every workspace buffer
-            PM_TRY(run_unit(s, u));
-            PM_TRY(flush_pending());
-            if (u.delivers >= 0) PM_TRY(deliver(u.delivers, gimgs + (size_t)u.delivers * img_elems));
-        }
-        ge.warmed = true;
-    } else {
-        // a workspace buffer of either handle was reallocated since the capture (a later call with a larger batch, a
-        // longer context, a direct encode/decode on the shared vqgan handle ...): the graphs' pointers are stale
-        if (!ge.segs.empty() && (ge.s2_gen != s2->ws.gen || (vq && ge.vq_gen != vq->ws.gen))) {
-            PM_HIP(hipStreamSynchronize(s));                  // an earlier replay may still be running
-            ge.destroy();
-        }
-        if (ge.segs.empty()) {
-            if (!s2->capture_stream) PM_HIP(hipStreamCreateWithFlags(&s2->capture_stream, hipStreamNonBlocking));
-            hipStream_t cap = s2->capture_stream;
-            for (const Unit& u : units) {
-                hipGraph_t g = nullptr;
-                hipGraphExec_t exec = nullptr;
-                s2->ws.frozen = true;
-                if (vq) vq->ws.frozen = true;
-                hipError_t rc = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
-                int step_rc = PMHIP_OK;
-                if (rc == hipSuccess) {
-                    step_rc = run_unit(cap, u);              // records only: nothing executes during capture
-                    rc = hipStreamEndCapture(cap, &g);
-                }
-                s2->ws.frozen = false;
-                if (vq) vq->ws.frozen = false;
-                if (step_rc == PMHIP_OK && rc == hipSuccess) rc = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-                if (g) (void)hipGraphDestroy(g);
-                if (step_rc != PMHIP_OK || rc != hipSuccess) {
-                    ge.destroy();
-                    if (step_rc != PMHIP_OK) return step_rc;
-                    PM_HIP(rc);
-                }
-                ge.segs.push_back(exec);
-            }
-            ge.s2_gen = s2->ws.gen;
-            ge.vq_gen = vq ? vq->ws.gen : 0;
-        }
-        for (size_t i = 0; i < units.size(); ++i) {
-            PM_HIP(hipGraphLaunch(ge.segs[i], s));
-            PM_TRY(flush_pending());
-            if (units[i].delivers >= 0) PM_TRY(deliver(units[i].delivers, gimgs + (size_t)units[i].delivers * img_elems));
-        }
-    }
-    PM_TRY(copy16_async(ids, gids, ids_bytes, s));
-    return flush_pending();
+    PM_TRY(run_graphs(s2, vq, s2->graphs[key], units.size(), s, run_unit, [&](size_t i) -> int {
+        PM_TRY(out.flush());
+        if (units[i].delivers >= 0) PM_TRY(out.deliver(units[i].delivers, gimgs + (size_t)units[i].delivers * img_elems));
+        return PMHIP_OK;
+    }));
+    PM_TRY(copy16_async(c.ids, gids, ids_bytes, s));
+    return out.flush();
 }
+
+}  // namespace
 
 extern "C" int pmhip_pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                        int T, const float* temps_host, const int* nmask_host,
                                        const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                        float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
                                        size_t host_stride, pmhip_stream copy_stream) {
-    return pipeline_generate(s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-                             use_graph, stream, imgs_host, host_stride, copy_stream, nullptr);
+    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
+                                     use_graph, stream, imgs_host, host_stride, copy_stream});
 }
 
 extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1273,8 +1358,8 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                               float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
                                               size_t host_stride, pmhip_stream copy_stream, float guidance_scale) {
-    return pipeline_generate(s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-                             use_graph, stream, imgs_host, host_stride, copy_stream, &guidance_scale);
+    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
+                                     use_graph, stream, imgs_host, host_stride, copy_stream, &guidance_scale});
 }
 
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged
@@ -1282,8 +1367,8 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
 // step -- tower, sampling, re-masking: one linear chain -- is captured once per (B, context length) on handle-owned ids and
 // replayed, whatever the records say.
 // guides_host (pmhip_pipeline_step_slots_guided; NULL otherwise): per-image guidance.  The host decides "two tower passes or one"
-// per STEP -- two exactly when an active slot is guided -- and the two-pass chain (step_tower_guided_slots + the same tail) has a
-// graph of its own; which rows the combination touches is decided on the device, from the staged records.
+// per STEP -- two exactly when an active slot is guided -- and the two-pass chain (step_tower with the guide records + the same
+// tail) has a graph of its own; which rows the combination touches is decided on the device, from the staged records.
 static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
                            const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
@@ -1317,100 +1402,38 @@ static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const fl
     }
     const int Lc = s2->slots_ctx_L;
 
-    // the records: pinned ring entry -> device
-    if (B > s2->slots_cap) {
-        for (auto e : s2->slots_done)
-            if (e) PM_HIP(hipEventSynchronize(e));            // copies still reading the old ring
-        if (s2->slots_host) { PM_HIP(hipHostFree(s2->slots_host)); s2->slots_host = nullptr; s2->slots_cap = 0; }
-        if (s2->guides_host) { PM_HIP(hipHostFree(s2->guides_host)); s2->guides_host = nullptr; }
-        PM_HIP(hipHostMalloc((void**)&s2->slots_host, sizeof(pmhip_slot) * (size_t)B * pmhip_s2::kParamSlots, hipHostMallocDefault));
-        PM_HIP(hipHostMalloc((void**)&s2->guides_host, sizeof(pmhip_slot_guide) * (size_t)B * pmhip_s2::kParamSlots, hipHostMallocDefault));
-        s2->slots_cap = B;
-        for (auto& e : s2->slots_done)
-            if (!e) PM_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    // the records: pinned ring entry -> device (the guide records sit behind the B slot records: 32 B bytes, a multiple of 16)
+    const size_t slot_bytes = sizeof(pmhip_slot) * (size_t)B, guide_bytes = sizeof(pmhip_slot_guide) * (size_t)B;
     pmhip_slot* dslots;
     pmhip_slot_guide* dguides = nullptr;
-    WS(s2->ws, "slots.dev", sizeof(pmhip_slot) * (size_t)B, dslots);
-    if (two_pass) WS(s2->ws, "slots.guides", sizeof(pmhip_slot_guide) * (size_t)B, dguides);
-    {
-        const int e = s2->slots_next;
-        s2->slots_next = (e + 1) % pmhip_s2::kParamSlots;
-        PM_HIP(hipEventSynchronize(s2->slots_done[e]));       // the copy that last read this entry (no-op when never recorded)
-        pmhip_slot* hp = s2->slots_host + (size_t)e * s2->slots_cap;
-        memcpy(hp, slots_host, sizeof(pmhip_slot) * (size_t)B);
-        void* hp_dev = nullptr;                               // the pinned entry through its device alias
-        PM_HIP(hipHostGetDevicePointer(&hp_dev, hp, 0));
-        PM_TRY(copy16_async(dslots, hp_dev, sizeof(pmhip_slot) * (size_t)B, s));
-        if (two_pass) {
-            pmhip_slot_guide* gp = s2->guides_host + (size_t)e * s2->slots_cap;
-            memcpy(gp, guides_host, sizeof(pmhip_slot_guide) * (size_t)B);
-            PM_HIP(hipHostGetDevicePointer(&hp_dev, gp, 0));
-            PM_TRY(copy16_async(dguides, hp_dev, sizeof(pmhip_slot_guide) * (size_t)B, s));
-        }
-        PM_HIP(hipEventRecord(s2->slots_done[e], s));
-    }
+    WS(s2->ws, "slots.dev", slot_bytes, dslots);
+    if (two_pass) WS(s2->ws, "slots.guides", guide_bytes, dguides);
+    PM_TRY(s2->slots_ring.reserve(slot_bytes + guide_bytes));
+    PM_TRY(s2->slots_ring.acquire());
+    PM_TRY(s2->slots_ring.stage(dslots, 0, slots_host, slot_bytes, s));
+    if (two_pass) PM_TRY(s2->slots_ring.stage(dguides, slot_bytes, guides_host, guide_bytes, s));
+    PM_TRY(s2->slots_ring.commit(s));
     ++(two_pass ? s2->slots_two_pass : s2->slots_one_pass);
-    auto tower = [&](const int64_t* from, hipStream_t on) -> int {
-        return two_pass ? step_tower_guided_slots(s2, from, B, dslots, dguides, on) : step_tower(s2, from, B, on, nullptr);
+    auto run_step = [&](int64_t* on_ids, int64_t* pred, float* score, hipStream_t on) -> int {
+        PM_TRY(step_tower(s2, on_ids, B, on, nullptr, dslots, dguides));
+        return step_tail(s2, nullptr, on_ids, B, StepScalars{}, dslots, nullptr, pred, score, on);
     };
 
     // ignored exactly when pipeline_generate ignores its graph request (same bits either way)
     const bool graph = (flags & PMHIP_SLOTS_GRAPH) && !g_pm_timing_on.load() && !direct_dispatch_off();
-    if (!graph) {
-        PM_TRY(tower(ids, s));
-        return step_tail_slots(s2, ids, B, dslots, pred_out, score_out, s);
-    }
+    if (!graph) return run_step(ids, pred_out, score_out, s);
 
     const size_t ids_bytes = (size_t)B * c.tokens * 8;
     int64_t* gids;
     WS(s2->ws, "slots.ids", ids_bytes, gids);
     PM_TRY(copy16_async(gids, ids, ids_bytes, s));
     GraphEntry& ge = s2->graphs[(two_pass ? "slotsguidedB" : "slotsB") + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key())];
-    auto run_step = [&](hipStream_t on) -> int {
-        PM_TRY(tower(gids, on));
-        return step_tail_slots(s2, gids, B, dslots, nullptr, nullptr, on);
-    };
-    if (!ge.warmed) {
-        PM_TRY(run_step(s));                                  // eager once: sizes every workspace buffer
-        ge.warmed = true;
-    } else {
-        if (!ge.segs.empty() && ge.s2_gen != s2->ws.gen) {    // a workspace buffer was reallocated since the capture
-            PM_HIP(hipStreamSynchronize(s));
-            ge.destroy();
-        }
-        if (ge.segs.empty()) {
-            if (!s2->capture_stream) PM_HIP(hipStreamCreateWithFlags(&s2->capture_stream, hipStreamNonBlocking));
-            hipStream_t cap = s2->capture_stream;
-            hipGraph_t g = nullptr;
-            hipGraphExec_t exec = nullptr;
-            s2->ws.frozen = true;
-            hipError_t rc = hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal);
-            int step_rc = PMHIP_OK;
-            if (rc == hipSuccess) {
-                step_rc = run_step(cap);                      // records only: nothing executes during capture
-                rc = hipStreamEndCapture(cap, &g);
-            }
-            s2->ws.frozen = false;
-            if (step_rc == PMHIP_OK && rc == hipSuccess) rc = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-            if (g) (void)hipGraphDestroy(g);
-            if (step_rc != PMHIP_OK) return step_rc;
-            PM_HIP(rc);
-            ge.segs.push_back(exec);
-            ge.s2_gen = s2->ws.gen;
-        }
-        PM_HIP(hipGraphLaunch(ge.segs[0], s));
-    }
+    PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
+                      [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
-    if (pred_out || score_out) {
-        const size_t M = (size_t)B * c.tokens;
-        int64_t* pred; float* score;
-        WS(s2->ws, "s2.pred", M * 8, pred);
-        WS(s2->ws, "s2.score", M * 4, score);
-        if (pred_out) PM_HIP(hipMemcpyAsync(pred_out, pred, M * 8, hipMemcpyDeviceToDevice, s));
-        if (score_out) PM_HIP(hipMemcpyAsync(score_out, score, M * 4, hipMemcpyDeviceToDevice, s));
-    }
-    return PMHIP_OK;
+    StepBufs b;
+    PM_TRY(pred_bufs(s2, (size_t)B * c.tokens, b, s));
+    return copy_aux(b, (size_t)B * c.tokens, pred_out, score_out, s);
 }
 
 extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,

@@ -282,6 +282,60 @@ def test_an_unguided_session_is_the_plain_slots_step(tiny_pipe, use_graph):
                 assert torch.equal(p1, p2) and torch.equal(s1, s2)
 
 
+def _same_session_runs(got, want):
+    for (pa, fa, _), (pb, fb, _) in zip(got, want):
+        assert pa == pb and fa.handle.slot == fb.handle.slot and len(fa.handle.trace) == len(fb.handle.trace)
+        assert torch.equal(fa.ids, fb.ids) and torch.equal(fa.image, fb.image)
+        for (p1, s1), (p2, s2) in zip(fa.handle.trace, fb.handle.trace):
+            assert torch.equal(p1, p2) and torch.equal(s1, s2)
+    assert len(got) == len(want)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_session_and_generate_graphs_share_one_handle_through_workspace_growth(tiny_pipe, dtype):
+    """The slots step and Pipeline.generate capture into ONE handle's graph cache, on its one capture stream, and every graph
+    bakes workspace pointers in: a guided step that allocates "s2.logits_u" / "slots.guides", and a session of twice the slots
+    that grows every "s2.*" buffer, leave the graphs captured before them stale.  Each run -- first eager, then captured, then
+    replayed, then re-captured after the growth -- must give the bits of its eager (use_graph=False) run."""
+    pipe = tiny_pipe
+    contexts = list(pipe.text_model([f"p{i}" for i in range(7)]).to(dev()))
+    texts = ["a", "b", "c"]
+    # (T, temperature, topk, seed, image index, scale): 4 steps of 3 slots = eager, capture, replay, replay
+    plain3 = {0: [(4, 1.0, 5, 301, 3, None), (4, 0.7, 2, 302, 4, None), (4, 1.2, 8, 303, 5, None)]}
+    plain6 = {0: [(3, 1.0, 5, 310 + i, 6 + i, None) for i in range(6)]}
+
+    def generate(use_graph):
+        imgs, ids = pipe.generate(texts, timesteps=4, topk=3, save_interval=2, seed=21, return_ids=True, use_graph=use_graph, streams=1)
+        return [im.clone() for im in imgs], ids.clone()
+
+    def runs(use_graph):
+        out = {"a": run_session(pipe, 3, use_graph, plain3, contexts)[0],
+               "b": run_session(pipe, 3, use_graph, TINY_PLAN, contexts)[0],
+               "c": [generate(use_graph) for _ in range(3)],
+               "d": run_session(pipe, 6, use_graph, plain6, contexts)[0]}
+        if use_graph:                                                  # every graph captured so far now holds stale pointers
+            out["e"] = (run_session(pipe, 3, True, plain3, contexts)[0], run_session(pipe, 3, True, TINY_PLAN, contexts)[0],
+                        [generate(True) for _ in range(3)])
+        return out
+
+    try:
+        pipe.set_compute_dtype(dtype)
+        want = runs(False)
+        assert all(torch.equal(i1, i2) for i1, i2 in zip(want["c"][0][0], want["c"][1][0])) and torch.equal(want["c"][0][1], want["c"][1][1])
+        pipe.invalidate_engines()                                      # one fresh engine pair: nothing sized, nothing captured
+        got = runs(True)
+        for a, b, c in ((got["a"], got["b"], got["c"]), got["e"]):
+            _same_session_runs(a, want["a"])
+            _same_session_runs(b, want["b"])
+            for imgs, ids in c:
+                assert torch.equal(ids, want["c"][0][1]) and len(imgs) == len(want["c"][0][0]) == 2
+                assert all(torch.equal(i1, i2) for i1, i2 in zip(imgs, want["c"][0][0]))
+        _same_session_runs(got["d"], want["d"])
+    finally:
+        pipe.set_compute_dtype(torch.float32)
+        pipe.invalidate_engines()
+
+
 def _records(*recs):
     arr = (_lib.Slot * len(recs))()
     for i, r in enumerate(recs):
