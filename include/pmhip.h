@@ -25,7 +25,7 @@
  *         lda >= K, ldw >= K          every GEMM entry point (and both multiples of 8)
  *         ldo >= N, ldr >= N          pmhip_gemm / _ln / _softmax_stats (ldr only with a residual), pmhip_gemm_hilo / _stats / _center
  *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
- *         ldo >= heads * dim_head     pmhip_attention / _dh
+ *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens
  *         ldl >= V                    pmhip_sample_rows / _stats / _slots, pmhip_masked_ce
  *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
  *     N * ldw stay below 2^30 elements; beyond that another kernel may serve the call).
@@ -208,6 +208,18 @@ int pmhip_gemm_heads_dh(int dtype, const void* A, int lda, const void* W, int ld
                         void* const* part_outs_host, float q_scale, float* scratch, pmhip_stream stream);
 int pmhip_attention_dh(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                        int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, pmhip_stream stream);
+
+/* pmhip_attention_dh with a key count per IMAGE (a key-padding mask; new entry within ABI 11, nothing existing changes meaning):
+ * kv_lens = DEVICE int32 [B]; image b attends to the keys [0, n_b) with n_b = min(max(kv_lens[b], 1), Nkv) -- the clamp is the
+ * kernel's, an operator cannot validate device memory, and it keeps every read inside Nkv_pad.  Nkv stays the launch-wide upper
+ * bound and Nkv_pad the layout: bases and row strides are those of pmhip_attention_dh.  Contract: the rows of image b equal, bit
+ * for bit, pmhip_attention_dh called on that image alone with Nkv = n_b -- the same kernel body with the key count read once per
+ * workgroup -- so K rows and V^T columns [n_b, Nkv_pad) of image b never reach a result, NaN included.  Any dim_head the _dh
+ * entry serves (64 runs the tuned kernels); the workgroup shape of the bf16 kernel is chosen from B, heads and Nq only, never
+ * from the lengths.  With every kv_lens[b] == Nkv the result is pmhip_attention_dh's.  kv_lens NULL is PMHIP_EINVAL. */
+int pmhip_attention_lens(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                         int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens,
+                         pmhip_stream stream);
 
 /* torch.nn.LayerNorm over the last dim, eps inside the sqrt (stage1/layers.py:49,51,89,128;
  * stage2/transformer.py:37,39,41,62).  x fp32 [M,D] -> out (`out_dtype`). */
@@ -550,6 +562,39 @@ int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, 
 int pmhip_pipeline_step_slots_guided(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
                                      const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, int flags,
                                      int64_t* pred_out, float* score_out, pmhip_stream stream);
+
+/* Per-image CONTEXT LENGTHS (new entries within ABI 11, following pmhip_slot_guide: nothing existing changes meaning).  The model-
+ * level entries above attend to all L rows of every image's context, padding included (the reference's behaviour with its T5
+ * embedder: padding="max_length", no mask).  The *_lens entries take ctx_lens_host, a HOST int32 [B]: image b's cross-attention
+ * sees the context rows [0, len_b) only.  Contract: rows [len_b, L) of image b's context never reach a result, NaN included, and
+ * image b computes what it computes at the same B with any other lengths beside it.  ctx_lens_host == NULL: every image uses L --
+ * exactly the entry without the suffix, the same kernels and the same graphs.
+ *   - the lengths are validated before anything is launched: 1 <= len_b <= L, else PMHIP_EINVAL with a message naming the image;
+ *     lengths without a context are PMHIP_EINVAL
+ *   - they travel like the slot records: pinned ring -> copy kernel -> a handle-owned device array, from where the cross-attention
+ *     launch (pmhip_attention_lens) reads them.  Captured graphs bake in that array, not the lengths: one graph per (B, L) serves
+ *     every mix of lengths (a key of its own beside the unmasked graph's, since the kernel form differs)
+ *   - the context projection and the cross K/V still cover all B * L rows; self-attention launches and the unconditional pass of a
+ *     guided step never see lengths
+ *   - PMHIP_SLOTS_KEEP_CONTEXT keeps the cross K/V only: every slots call brings its own lengths (or NULL), so a step in which only
+ *     the lengths changed needs no new context
+ * guided != 0: the entry is the _guided one with guidance_scale; guided == 0: guidance_scale is ignored.
+ * pmhip_pipeline_step_slots_lens is pmhip_pipeline_step_slots_guided (guides_host may be NULL) with lengths. */
+int pmhip_s2_forward_lens(pmhip_s2* h, const float* tokens, const float* context, int L, int B,
+                          const int32_t* ctx_lens_host, float* logits_out, pmhip_stream stream);
+int pmhip_pipeline_sample_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                               const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                               uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                               float* score_out, int guided, float guidance_scale, pmhip_stream stream);
+int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                 const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                 const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                 float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                 pmhip_stream copy_stream, int guided, float guidance_scale);
+int pmhip_pipeline_step_slots_lens(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                   const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
+                                   const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out,
+                                   pmhip_stream stream);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

@@ -108,6 +108,7 @@ PROTOTYPES = {
     "pmhip_gemm_heads_dh": (i32, [i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32),
                                   C.POINTER(vp), f32, vp, vp]),
     "pmhip_attention_dh": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "pmhip_attention_lens": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "pmhip_layernorm": (i32, [vp, vp, vp, f32, vp, i32, i32, i32, vp]),
     "pmhip_patchify": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "pmhip_unpatchify_clamp": (i32, [vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
@@ -145,6 +146,11 @@ PROTOTYPES = {
     "pmhip_pipeline_sample_guided": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, f32, vp]),
     "pmhip_pipeline_generate_guided": (i32, [vp, vp, vp, vp, i32, i32, i32, C.POINTER(f32), C.POINTER(i32),
                                              C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, f32]),
+    "pmhip_s2_forward_lens": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), vp, vp]),
+    "pmhip_pipeline_sample_lens": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, i32, f32, vp]),
+    "pmhip_pipeline_generate_lens": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
+                                           C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32]),
+    "pmhip_pipeline_step_slots_lens": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), i32, vp, vp, vp]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),

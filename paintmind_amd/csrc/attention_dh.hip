@@ -46,47 +46,33 @@ __device__ __forceinline__ float quad_sum(float v) {
     return v;
 }
 
-// DPL = dims per lane = dh / 4
-template <typename T, int DPL, bool EXP2>
-__global__ __launch_bounds__(256) void attention_dh_kernel(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ Vt,
-                                                          T* __restrict__ out, int ldo, int heads, int Nq, int Nkv, int Nkp) {
-    constexpr int DH = DPL * 4;
-    const int bh = blockIdx.y, b = bh / heads, h = bh % heads;
-    const int qi = blockIdx.x * 64 + (threadIdx.x >> 2), part = threadIdx.x & 3;
-    const int qr = qi < Nq ? qi : Nq - 1;                       // rows past the end compute a copy and do not store
-    float q[DPL], o[DPL];
-    const T* qp = Q + ((size_t)bh * Nq + qr) * DH + part * DPL;
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) { q[i] = to_f32<T>(qp[i]); o[i] = 0.f; }
-    const T* kp = K + (size_t)bh * Nkp * DH + part * DPL;
-    const T* vp = Vt + ((size_t)bh * DH + part * DPL) * Nkp;
-    float m = -INFINITY, l = 0.f;
-    for (int j = 0; j < Nkv; ++j) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) s = fmaf(q[i], to_f32<T>(kp[(size_t)j * DH + i]), s);
-        s = quad_sum(s);
-        const float mn = fmaxf(m, s);
-        const float a = EXP2 ? exp2f(m - mn) : expf(m - mn);
-        const float pj = EXP2 ? exp2f(s - mn) : expf(s - mn);
-        l = fmaf(l, a, pj);
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) o[i] = fmaf(o[i], a, pj * to_f32<T>(vp[(size_t)i * Nkp + j]));
-        m = mn;
-    }
-    if (qi < Nq) {
-        const float inv = 1.f / l;
-        T* op = out + ((size_t)b * Nq + qi) * ldo + h * DH + part * DPL;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) op[i] = from_f32<T>(o[i] * inv);
-    }
-}
+// DPL = dims per lane = dh / 4.  The kernel, in its two forms (attention_dh_body.h)
+#define PM_ATTN_KERNEL attention_dh_kernel
+#define PM_ATTN_LENS_PARAM
+#include "attention_dh_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+// the per-image form: Nkv_b = clamp(lens[b], 1, Nkv)
+#define PM_ATTN_KERNEL attention_dh_lens_kernel
+#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens
+#define PM_ATTN_LENS 1
+#include "attention_dh_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_LENS
 
 template <typename T, int DPL>
 void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-               int use_exp2, hipStream_t s) {
+               int use_exp2, const int* lens, hipStream_t s) {
     dim3 grid((Nq + 63) / 64, B * heads), block(256);
-    if (use_exp2)
+    if (lens) {
+        if (use_exp2)
+            hipLaunchKernelGGL((attention_dh_lens_kernel<T, DPL, true>), grid, block, 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
+                               ldo, heads, Nq, Nkv, Nkp, lens);
+        else
+            hipLaunchKernelGGL((attention_dh_lens_kernel<T, DPL, false>), grid, block, 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
+                               ldo, heads, Nq, Nkv, Nkp, lens);
+    } else if (use_exp2)
         hipLaunchKernelGGL((attention_dh_kernel<T, DPL, true>), grid, block, 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo,
                            heads, Nq, Nkv, Nkp);
     else
@@ -96,9 +82,9 @@ void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo,
 
 template <typename T>
 int dispatch_dh(int dh, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-                int use_exp2, hipStream_t s) {
+                int use_exp2, const int* lens, hipStream_t s) {
     switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, s); break;
+#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, s); break;
         PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
 #undef PM_DH_CASE
         default: PM_REQUIRE(false, "attention_dh: dim_head=%d not served", dh);
@@ -145,17 +131,34 @@ extern "C" int pmhip_gemm_heads_dh(int dtype, const void* A, int lda, const void
     return PMHIP_OK;
 }
 
+int pm_attention64(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                   int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
+
+// pmhip_attention_dh (lens NULL) and pmhip_attention_lens
+static int attention_any(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                         int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s) {
+    if (dim_head == 64) return pm_attention64(who, dtype, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+    PM_TRY(check_dh(who, heads, dim_head));
+    PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "%s: bad dtype %d", who, dtype);
+    PM_REQUIRE(Q && K && Vt && out, "%s: null pointer", who);
+    PM_REQUIRE(B > 0 && Nq > 0 && Nkv > 0 && Nkv_pad >= Nkv, "%s: empty problem", who);
+    PM_REQUIRE(ldo >= heads * dim_head, "%s: ldo=%d is smaller than heads*dim_head=%d (rows of out would overlap)", who, ldo, heads * dim_head);
+    PM_REQUIRE((long long)B * heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)B * heads);
+    PmTimer tm(FAM_ATTENTION, s);
+    if (dtype == PMHIP_F32) return dispatch_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+    return dispatch_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+}
+
 extern "C" int pmhip_attention_dh(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                                   int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, pmhip_stream stream) {
-    if (dim_head == 64) return pmhip_attention(dtype, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
-    PM_TRY(check_dh("attention_dh", heads, dim_head));
-    PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "attention_dh: bad dtype %d", dtype);
-    PM_REQUIRE(Q && K && Vt && out, "attention_dh: null pointer");
-    PM_REQUIRE(B > 0 && Nq > 0 && Nkv > 0 && Nkv_pad >= Nkv, "attention_dh: empty problem");
-    PM_REQUIRE(ldo >= heads * dim_head, "attention_dh: ldo=%d is smaller than heads*dim_head=%d (rows of out would overlap)", ldo, heads * dim_head);
-    PM_REQUIRE((long long)B * heads <= 65535, "attention_dh: B*heads=%lld exceeds the grid's y range", (long long)B * heads);
-    hipStream_t s = (hipStream_t)stream;
-    PmTimer tm(FAM_ATTENTION, s);
-    if (dtype == PMHIP_F32) return dispatch_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, s);
-    return dispatch_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, s);
+    return attention_any(dim_head == 64 ? "attention" : "attention_dh", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad,
+                         use_exp2, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int pmhip_attention_lens(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                                    int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens,
+                                    pmhip_stream stream) {
+    PM_REQUIRE(kv_lens, "attention_lens: kv_lens is NULL (pmhip_attention_dh is the entry without per-image key counts)");
+    return attention_any("attention_lens", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, kv_lens,
+                         (hipStream_t)stream);
 }

@@ -195,6 +195,7 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     const void* k = nullptr;
     const void* vt = nullptr;
     int L = 0, Lp = 0;
+    const int32_t* lens = nullptr;   // device [B]: per-image key counts of THIS call (NULL: every image attends to all L rows)
 };
 
 // The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
@@ -436,7 +437,12 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
             void* outs[1] = {b.q};
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 1, kind_q,
                             outs, q_scale, s));
-            PM_TRY(pmhip_attention_dh(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast, s));
+            // the one launch that sees per-image context lengths (self-attention and the unconditional pass never do)
+            if (cross->lens)
+                PM_TRY(pmhip_attention_lens(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
+                                            cross->lens, s));
+            else
+                PM_TRY(pmhip_attention_dh(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast, s));
         } else {
             void* outs[3] = {b.q, b.k, b.vt};
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 3, kinds_qkv,
@@ -764,6 +770,7 @@ struct pmhip_s2 {
     // context the last slots call prepared (slots_ctx_L: 0 = prepared without a context, -1 = nothing a slots call may reuse);
     // slots_one_pass / slots_two_pass count the steps by tower passes
     PinnedRing slots_ring;
+    PinnedRing lens_ring;           // per-image context lengths of a call (ctx_lens_host): B int32 -> workspace "ctx.lens"
     int slots_one_pass = 0, slots_two_pass = 0;
     int slots_ctx_B = 0, slots_ctx_L = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
@@ -839,8 +846,38 @@ int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStrea
         void* outs[2] = {kv + per * (2 * l), kv + per * (2 * l + 1)};
         const unsigned char* wkv = reinterpret_cast<const unsigned char*>(h->layers[l].wqkv2) + (size_t)inner * dim * es;
         PM_TRY(pmhip_gemm_heads_dh(h->dtype, cp, dim, wkv, dim, Mc, dim, heads, dh, L, Lp, 2, kinds, outs, 1.0f, split, s));
-        h->cross[l].k = outs[0]; h->cross[l].vt = outs[1]; h->cross[l].L = L; h->cross[l].Lp = Lp;
+        h->cross[l].k = outs[0]; h->cross[l].vt = outs[1]; h->cross[l].L = L; h->cross[l].Lp = Lp; h->cross[l].lens = nullptr;
     }
+    return PMHIP_OK;
+}
+
+// Per-image context lengths (ctx_lens_host of the *_lens entries), checked BEFORE anything is launched: 1 <= len <= L.  They need
+// a context: without one attn2 is a second self-attention, which never sees lengths.
+int check_ctx_lens(const char* who, const int32_t* lens_host, bool have_context, int L, int B) {
+    if (!lens_host) return PMHIP_OK;
+    PM_REQUIRE(have_context && L > 0, "%s: ctx_lens_host given without a context", who);
+    for (int b = 0; b < B; ++b)
+        PM_REQUIRE(lens_host[b] >= 1 && lens_host[b] <= L, "%s: image %d: context length %d must be in [1, L=%d]", who, b, (int)lens_host[b], L);
+    return PMHIP_OK;
+}
+
+// The checked lengths travel like the slot records and PmGenParams: pinned ring entry -> copy kernel -> the handle's device array
+// -> every layer's CrossKV, from where the cross-attention launch of layer_forward hands them to pmhip_attention_lens.  Called by
+// every model-level entry AFTER the context is prepared or kept (lens_host NULL: the lengths of an earlier call are dropped), and
+// always outside a graph: a captured graph bakes in the device array, never a length.
+int s2_set_ctx_lens(pmhip_s2* h, const int32_t* lens_host, int L, int B, hipStream_t s) {
+    int32_t* dlens = nullptr;
+    if (lens_host) {
+        const int Bp = round_up(B, 4);                        // 16-byte multiples: the copy kernel's widest path
+        WS(h->ws, "ctx.lens", (size_t)Bp * 4, dlens);
+        std::vector<int32_t> padded((size_t)Bp, L);
+        std::copy(lens_host, lens_host + B, padded.begin());
+        PM_TRY(h->lens_ring.reserve((size_t)Bp * 4));
+        PM_TRY(h->lens_ring.acquire());
+        PM_TRY(h->lens_ring.stage(dlens, 0, padded.data(), (size_t)Bp * 4, s));
+        PM_TRY(h->lens_ring.commit(s));
+    }
+    for (auto& ck : h->cross) ck.lens = ck.k ? dlens : nullptr;
     return PMHIP_OK;
 }
 
@@ -1080,39 +1117,67 @@ int run_graphs(pmhip_s2* s2, pmhip_vqgan* vq, GraphEntry& ge, size_t n_units, hi
 
 }  // namespace
 
-extern "C" int pmhip_s2_forward(pmhip_s2* h, const float* tokens, const float* context, int L, int B, float* logits_out,
-                                pmhip_stream stream) {
-    PM_REQUIRE(h && tokens && logits_out && B > 0, "s2_forward: bad arguments");
+static int s2_forward_impl(const char* who, pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                           float* logits_out, pmhip_stream stream) {
+    PM_REQUIRE(h && tokens && logits_out && B > 0, "%s: bad arguments", who);
+    PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
     hipStream_t s = (hipStream_t)stream;
     const int M = B * h->cfg.tokens;
     PM_TRY(s2_prepare_context(h, context, L, B, s));
+    PM_TRY(s2_set_ctx_lens(h, ctx_lens_host, L, B, s));
     void* tp;
     PM_TRY(tok_buf(h, M, tp, s));
     PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
     return s2_tower(h, tp, B, logits_out, s);
 }
 
+extern "C" int pmhip_s2_forward(pmhip_s2* h, const float* tokens, const float* context, int L, int B, float* logits_out,
+                                pmhip_stream stream) {
+    return s2_forward_impl("s2_forward", h, tokens, context, L, B, nullptr, logits_out, stream);
+}
+
+extern "C" int pmhip_s2_forward_lens(pmhip_s2* h, const float* tokens, const float* context, int L, int B,
+                                     const int32_t* ctx_lens_host, float* logits_out, pmhip_stream stream) {
+    return s2_forward_impl("s2_forward_lens", h, tokens, context, L, B, ctx_lens_host, logits_out, stream);
+}
+
+static int pipeline_sample_impl(const char* who, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                const int32_t* ctx_lens_host, const StepScalars& sc, float* img_out, int64_t* pred_out, float* score_out,
+                                const float* guidance, pmhip_stream stream) {
+    PM_REQUIRE(s2 && ids && B > 0, "%s: bad arguments", who);
+    PM_REQUIRE(!guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
+    PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
+    hipStream_t s = (hipStream_t)stream;
+    PM_TRY(s2_prepare_context(s2, context, L, B, s));
+    PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
+    return sample_step(s2, vq, ids, B, sc, img_out, pred_out, score_out, s, guidance);
+}
+
 extern "C" int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                      int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                      uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                      float* score_out, pmhip_stream stream) {
-    PM_REQUIRE(s2 && ids && B > 0, "pipeline_sample: bad arguments");
-    hipStream_t s = (hipStream_t)stream;
-    PM_TRY(s2_prepare_context(s2, context, L, B, s));
-    return sample_step(s2, vq, ids, B, StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out,
-                       score_out, s);
+    return pipeline_sample_impl("pipeline_sample", s2, vq, ids, context, L, B, nullptr,
+                                StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out, nullptr,
+                                stream);
 }
 
 extern "C" int pmhip_pipeline_sample_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                             int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                             uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                             float* score_out, float guidance_scale, pmhip_stream stream) {
-    PM_REQUIRE(s2 && ids && B > 0, "pipeline_sample_guided: bad arguments");
-    PM_REQUIRE(context && L > 0, "pipeline_sample_guided: guidance needs a context (context NULL IS the unconditional branch)");
-    hipStream_t s = (hipStream_t)stream;
-    PM_TRY(s2_prepare_context(s2, context, L, B, s));
-    return sample_step(s2, vq, ids, B, StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out,
-                       score_out, s, &guidance_scale);
+    return pipeline_sample_impl("pipeline_sample_guided", s2, vq, ids, context, L, B, nullptr,
+                                StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out,
+                                &guidance_scale, stream);
+}
+
+extern "C" int pmhip_pipeline_sample_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                          const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                          uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                          float* score_out, int guided, float guidance_scale, pmhip_stream stream) {
+    return pipeline_sample_impl("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host,
+                                StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out,
+                                guided ? &guidance_scale : nullptr, stream);
 }
 
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
@@ -1130,6 +1195,8 @@ struct GenCall {
     int topk; uint64_t seed, image_base; float* imgs_out; int use_graph; pmhip_stream stream;
     float* imgs_host; size_t host_stride; pmhip_stream copy_stream;
     const float* guidance = nullptr;
+    const int32_t* ctx_lens = nullptr;      // host [B] or NULL (pmhip_pipeline_generate_lens)
+    const char* who = "pipeline_generate";
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
 
@@ -1199,9 +1266,11 @@ int pipeline_generate(const GenCall& c) {
     const int B = c.B, T = c.T;
     PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && c.nmask_host, "pipeline_generate: bad arguments");
     PM_REQUIRE(!c.guidance || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
+    PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
     hipStream_t s = (hipStream_t)c.stream;
     hipStream_t cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
     PM_TRY(s2_prepare_context(s2, c.context, c.L, B, s));     // context projection + cross K/V: once per loop, eager
+    PM_TRY(s2_set_ctx_lens(s2, c.ctx_lens, c.L, B, s));       // the lengths: device memory the (captured) cross-attention launches read
     size_t img_elems = 0;
     if (vq) img_elems = (size_t)B * vq->cfg.channels * vq->cfg.image_size * vq->cfg.image_size;
     int n_dec = 0;
@@ -1301,6 +1370,7 @@ int pipeline_generate(const GenCall& c) {
     const std::vector<Unit> units = plan_units(c, overlap);
     key += overlap ? "o1" : "o0";
     if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
+    if (c.ctx_lens) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     if (overlap) {
@@ -1362,6 +1432,16 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
                                      use_graph, stream, imgs_host, host_stride, copy_stream, &guidance_scale});
 }
 
+extern "C" int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                            const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                            const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                            float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                            pmhip_stream copy_stream, int guided, float guidance_scale) {
+    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
+                                     use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
+                                     "pipeline_generate_lens"});
+}
+
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged
 // through the pinned ring into the workspace, and read from there by the sampling and re-masking kernels; with the graph flag the
 // step -- tower, sampling, re-masking: one linear chain -- is captured once per (B, context length) on handle-owned ids and
@@ -1369,9 +1449,13 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
 // guides_host (pmhip_pipeline_step_slots_guided; NULL otherwise): per-image guidance.  The host decides "two tower passes or one"
 // per STEP -- two exactly when an active slot is guided -- and the two-pass chain (step_tower with the guide records + the same
 // tail) has a graph of its own; which rows the combination touches is decided on the device, from the staged records.
+// ctx_lens_host (pmhip_pipeline_step_slots_lens; NULL otherwise): per-image context lengths, staged by EVERY call -- also under
+// PMHIP_SLOTS_KEEP_CONTEXT, where the kept cross K/V serve whatever lengths this call brings.
 static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
-                           const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
+                           const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream,
+                           const int32_t* ctx_lens_host = nullptr) {
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
+    PM_TRY(check_ctx_lens(who, ctx_lens_host, context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0), L, B));
     const auto& c = s2->cfg;
     PM_REQUIRE(c.n_embed % 64 == 0, "%s: n_embed=%d must be a multiple of 64", who, c.n_embed);
     bool two_pass = false;
@@ -1401,6 +1485,8 @@ static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const fl
         s2->slots_ctx_L = context ? L : 0;
     }
     const int Lc = s2->slots_ctx_L;
+    PM_REQUIRE(!ctx_lens_host || Lc > 0, "%s: ctx_lens_host given, but the kept context was prepared without one", who);
+    PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
 
     // the records: pinned ring entry -> device (the guide records sit behind the B slot records: 32 B bytes, a multiple of 16)
     const size_t slot_bytes = sizeof(pmhip_slot) * (size_t)B, guide_bytes = sizeof(pmhip_slot_guide) * (size_t)B;
@@ -1427,7 +1513,8 @@ static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const fl
     int64_t* gids;
     WS(s2->ws, "slots.ids", ids_bytes, gids);
     PM_TRY(copy16_async(gids, ids, ids_bytes, s));
-    GraphEntry& ge = s2->graphs[(two_pass ? "slotsguidedB" : "slotsB") + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key())];
+    GraphEntry& ge = s2->graphs[(two_pass ? "slotsguidedB" : "slotsB") + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
+                                (ctx_lens_host ? "n" : "")];
     PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
@@ -1445,6 +1532,13 @@ extern "C" int pmhip_pipeline_step_slots_guided(pmhip_s2* s2, int64_t* ids, cons
                                                 const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out,
                                                 pmhip_stream stream) {
     return step_slots_impl("pipeline_step_slots_guided", s2, ids, context, L, B, slots_host, guides_host, flags, pred_out, score_out, stream);
+}
+
+extern "C" int pmhip_pipeline_step_slots_lens(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                              const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, int flags,
+                                              int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    return step_slots_impl("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, guides_host, flags, pred_out, score_out, stream,
+                           ctx_lens_host);
 }
 
 // slots steps by tower passes: one (no active slot guided) / two

@@ -92,6 +92,12 @@ def generate_sharded(pipe, text, seed, group=None, dst=0, timesteps=18, save_int
         tm.base_index = lo                                   # synthetic text features are keyed by global index
     on = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
     stacked = None
+    if kwargs.get("context_lens") is not None:               # explicit per-image context lengths: every rank takes its slice
+        cl = kwargs["context_lens"]
+        cl = cl.reshape(-1).tolist() if isinstance(cl, torch.Tensor) else list(cl)
+        if len(cl) != len(text):
+            raise ValueError(f"context_lens: {len(cl)} lengths for {len(text)} prompts")
+        kwargs = dict(kwargs, context_lens=cl[lo:hi])
     if hi > lo:
         imgs = pipe.generate(text[lo:hi], timesteps=timesteps, save_interval=save_interval, seed=seed, image_base=lo,
                              keep_on_device=True, **kwargs)

@@ -288,22 +288,41 @@ class S2Engine:
             raise ValueError(f"context width {context.shape[-1]} != context_dim {self.context_dim}")
         return context, context.shape[1]
 
-    def forward(self, tokens, context=None):
+    @staticmethod
+    def _lens(context_lens, context, B, L):
+        """context_lens (list / CPU tensor / device tensor / None) -> a ctypes int32 [B] for ctx_lens_host, or None; checked here
+        (1 <= len <= L, one per image) and again by the native entry"""
+        if context_lens is None:
+            return None
+        if context is None and L == 0:
+            raise ValueError("context_lens needs a context (context None IS the unconditional branch)")
+        vals = ops.host_lens(context_lens, B, L)
+        return (C.c_int * B)(*vals)
+
+    def forward(self, tokens, context=None, context_lens=None):
         tokens = tokens.to(self.device, torch.float32).contiguous()
         B = tokens.shape[0]
         context, L = self._ctx(context)
+        lens = self._lens(context_lens, context, B, L)
         logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            check(self.lib.pmhip_s2_forward(self.handle, _p(tokens), _p(context), L, B, _p(logits), stream_ptr(self.device)),
-                  "pmhip_s2_forward")
+            if lens is None:
+                check(self.lib.pmhip_s2_forward(self.handle, _p(tokens), _p(context), L, B, _p(logits), stream_ptr(self.device)),
+                      "pmhip_s2_forward")
+            else:
+                check(self.lib.pmhip_s2_forward_lens(self.handle, _p(tokens), _p(context), L, B, lens, _p(logits),
+                                                     stream_ptr(self.device)), "pmhip_s2_forward_lens")
         return logits
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
-               want_img=True, want_aux=False, guidance_scale=None):
+               want_img=True, want_aux=False, guidance_scale=None, context_lens=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
-        guidance_scale (None = the reference's step): sample from uncond + scale * (cond - uncond), two tower passes."""
+        guidance_scale (None = the reference's step): sample from uncond + scale * (cond - uncond), two tower passes.
+        context_lens (None = every image attends to its whole context): image b's cross-attention sees context rows
+        [0, context_lens[b]) only (pmhip_pipeline_sample_lens)."""
         B = ids.shape[0]
         context, L = self._ctx(context)
+        lens = self._lens(context_lens, context, B, L)
         img = vq_engine._new_img(B) if want_img else None
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
@@ -313,7 +332,11 @@ class S2Engine:
                 int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img),
                 _p(pred), _p(score))
         with torch.cuda.device(self.device):
-            if guidance_scale is None:
+            if lens is not None:
+                check(self.lib.pmhip_pipeline_sample_lens(*args[:6], lens, *args[6:], int(guidance_scale is not None),
+                                                          float(guidance_scale or 0.0), stream_ptr(self.device)),
+                      "pmhip_pipeline_sample_lens")
+            elif guidance_scale is None:
                 check(self.lib.pmhip_pipeline_sample(*args, stream_ptr(self.device)), "pmhip_pipeline_sample")
             else:
                 check(self.lib.pmhip_pipeline_sample_guided(*args, float(guidance_scale), stream_ptr(self.device)),
@@ -327,13 +350,15 @@ class S2Engine:
         check(self.lib.pmhip_s2_slots_steps(self.handle, C.byref(one), C.byref(two)), "pmhip_s2_slots_steps")
         return one.value, two.value
 
-    def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None):
+    def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
         length; the cross K/V the previous step_slots call prepared are reused.  guides: a ctypes array of _lib.SlotGuide beside
         `slots` (HOST records: scale, on) -- an active slot with on != 0 samples from uncond + scale * (cond - uncond), and a step
-        with such a slot runs the tower twice (pmhip_pipeline_step_slots_guided).  -> (ids, pred [B,N], score [B,N])"""
+        with such a slot runs the tower twice (pmhip_pipeline_step_slots_guided).  context_lens: per-slot context lengths of THIS
+        step (pmhip_pipeline_step_slots_lens; also with keep_context, which keeps the cross K/V only).
+        -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
             raise ValueError(f"step_slots: {len(slots)} slot records for a batch of {B}")
@@ -346,11 +371,15 @@ class S2Engine:
             context = None
         else:
             context, L = self._ctx(context)
+        lens = self._lens(context_lens, context, B, L)
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
         flags = (_lib.SLOTS_GRAPH if use_graph else 0) | (_lib.SLOTS_KEEP_CONTEXT if keep_context else 0)
         with torch.cuda.device(self.device):
-            if guides is None:
+            if lens is not None:
+                check(self.lib.pmhip_pipeline_step_slots_lens(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, flags, _p(pred),
+                                                              _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_lens")
+            elif guides is None:
                 check(self.lib.pmhip_pipeline_step_slots(self.handle, _p(ids), _p(context), L, B, slots, flags, _p(pred), _p(score),
                                                          stream_ptr(self.device)), "pmhip_pipeline_step_slots")
             else:
@@ -359,7 +388,7 @@ class S2Engine:
         return ids, pred, score
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
-                 host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False):
+                 host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
 
         host = (pinned float32 tensor [n_decoded, B_total, C, H, W], first row of this batch, copy stream): every decoded
@@ -368,10 +397,12 @@ class S2Engine:
         concurrent_lanes: other micro-batches run beside this call on other streams (PMHIP_GENERATE_CONCURRENT_LANES: the loop
         then does not put a small batch's decode on a side stream of its own).
         from_mask: the loop starts from the all-mask state (PMHIP_GENERATE_FROM_MASK): the native call writes that state itself --
-        what `ids` holds on entry is ignored -- and an unconditional loop samples its step 0 from the handle's shared logits."""
+        what `ids` holds on entry is ignored -- and an unconditional loop samples its step 0 from the handle's shared logits.
+        context_lens: per-image context lengths (pmhip_pipeline_generate_lens); the captured graphs read them from device memory."""
         B = ids.shape[0]
         T = len(temps)
         context, L = self._ctx(context)
+        lens = self._lens(context_lens, context, B, L)
         n_dec = int(sum(1 for f in decode_flags if f))
         imgs = None
         if n_dec and (want_device_imgs or host is None):
@@ -395,7 +426,10 @@ class S2Engine:
                 (_lib.GENERATE_FROM_MASK if from_mask else 0),
                 stream_ptr(self.device), host_ptr, host_stride, copy_stream)
         with torch.cuda.device(self.device):
-            if guidance_scale is None:
+            if lens is not None:
+                check(self.lib.pmhip_pipeline_generate_lens(*args[:6], lens, *args[6:], int(guidance_scale is not None),
+                                                            float(guidance_scale or 0.0)), "pmhip_pipeline_generate_lens")
+            elif guidance_scale is None:
                 check(self.lib.pmhip_pipeline_generate(*args), "pmhip_pipeline_generate")
             else:
                 check(self.lib.pmhip_pipeline_generate_guided(*args, float(guidance_scale)), "pmhip_pipeline_generate_guided")

@@ -221,10 +221,22 @@ class Pipeline(nn.Module):
     def _on_cpu(self):
         return self.mask_token.device.type == "cpu"
 
-    def tokens2logits(self, token, text=None):
+    def _lens(self, context_lens, context, B):
+        """context_lens (a list, a CPU tensor or a device tensor; None passes through) -> a checked list of B ints on the host,
+        brought there ONCE per call: 1 <= len <= L, one per image"""
+        if context_lens is None:
+            return None
+        if context is None:
+            raise ValueError("context_lens needs a text condition (text=None IS the unconditional branch)")
+        return ops.host_lens(context_lens, B, context.shape[1])
+
+    def tokens2logits(self, token, text=None, context_lens=None):
+        """context_lens (extension; None = the reference's behaviour, every row of the context is attended to): one length per
+        image -- rows [len_b, L) of image b's context never reach its logits, NaN included."""
+        lens = self._lens(context_lens, text, token.shape[0])
         if self._on_cpu():
-            return self.transformer(token, text)             # plain-torch operators of this package (no HIP engine on the CPU)
-        return self.engine().forward(token, text)
+            return self.transformer(token, text, lens)       # plain-torch operators of this package (no HIP engine on the CPU)
+        return self.engine().forward(token, text, context_lens=lens)
 
     @torch.no_grad()
     def ids2tokens(self, ids):
@@ -237,7 +249,7 @@ class Pipeline(nn.Module):
 
     @torch.no_grad()
     def sample(self, ids, mask_ratio, text=None, topk=1, temperature=1, noise=None, seed=None, step=0, image_base=0,
-               guidance_scale=None):
+               guidance_scale=None, context_lens=None):
         """One MaskGIT step (generate.py:159-181) -> (ids', img).
 
         ``noise``: optional uniform(0,1) tensor shaped like the logits (B,N,V) -- the parity hook for the
@@ -250,21 +262,25 @@ class Pipeline(nn.Module):
         ``uncond + guidance_scale * (cond - uncond)`` with ``uncond = transformer(tokens, None)``, the path the reference
         trains by dropping the text 10 % of the time (utils/trainer.py:379,387-388) but never uses when sampling.  Both
         forwards share the step's token lookup; everything after the logits is the reference's step unchanged.
+
+        ``context_lens`` (extension; None = the reference's behaviour): one context length per image, see ``tokens2logits``.
+        The unconditional forward of a guided step takes no context and so no lengths.
         """
         nm = num_token_masked(mask_ratio, self.num_tokens)
         if guidance_scale is not None and text is None:
             raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
+        lens = self._lens(context_lens, text, ids.shape[0])
         if self._on_cpu():
-            return self._sample_cpu(ids, nm, text, topk, temperature, noise, seed, guidance_scale)
+            return self._sample_cpu(ids, nm, text, topk, temperature, noise, seed, guidance_scale, lens)
         if seed is None:
             seed = _draw_seed()
         eng = self.engine()
         ids = ids.to(eng.device, torch.int64).clone().contiguous()
         ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, topk, temperature, nm, noise=noise, seed=seed, step=step,
-                                    image_base=image_base, want_img=True, guidance_scale=guidance_scale)
+                                    image_base=image_base, want_img=True, guidance_scale=guidance_scale, context_lens=lens)
         return ids, img
 
-    def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale):
+    def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale, context_lens=None):
         """the guided step composed from the operator-level C ABI (two pmhip_s2_forward + pmhip_guidance_combine +
         pmhip_sample_rows + decode + pmhip_remask): the same kernels, in the same order, as pmhip_pipeline_sample_guided.
         Not on any product path: the bit-identity reference of tests/test_gpu_model.py for the native guided step / loop."""
@@ -272,7 +288,7 @@ class Pipeline(nn.Module):
         ids = ids.to(eng.device, torch.int64).clone().contiguous()
         B, N = ids.shape
         tok = self.ids2tokens(ids)
-        cond = eng.forward(tok, text)
+        cond = eng.forward(tok, text, context_lens=context_lens)
         uncond = eng.forward(tok, None)
         logits = ops.guidance_combine(cond, uncond, scale, out=cond)
         if noise is not None:
@@ -283,12 +299,12 @@ class Pipeline(nn.Module):
         ids = ops.remask(merged.reshape(B, N), score.reshape(B, N), nm, self.mask_token_id)
         return ids, img
 
-    def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None):
+    def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None):
         """generate.py:159-181 in plain torch for a pipeline that lives on the CPU.  The noise is drawn from the torch CPU
         generator like the reference's (`seed` re-seeds a private generator; `noise` overrides it); ties in top-k / argmax
         follow torch."""
         tok = self.ids2tokens(ids)
-        logits = self.tokens2logits(tok, text)
+        logits = self.tokens2logits(tok, text, context_lens)
         if guidance_scale is not None:
             uncond = self.tokens2logits(tok, None)
             logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(guidance_scale)))
@@ -307,14 +323,15 @@ class Pipeline(nn.Module):
         ids = ids.scatter(1, scores.topk(nm, dim=-1).indices, self.mask_token_id)
         return ids, img
 
-    def _generate_cpu(self, text, context, timesteps, temperature, topk, save_interval, seed, return_ids):
+    def _generate_cpu(self, text, context, timesteps, temperature, topk, save_interval, seed, return_ids, context_lens=None):
         B = len(text)
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
         imgs = []
         for step in range(timesteps):
             masked_r = mask_schedule((step + 1) / timesteps)
             ids, img = self._sample_cpu(ids, num_token_masked(masked_r, self.num_tokens), context, topk,
-                                        temperature * (1 - step / timesteps), None, None if seed is None else seed + step)
+                                        temperature * (1 - step / timesteps), None, None if seed is None else seed + step,
+                                        None, context_lens)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
@@ -355,14 +372,15 @@ class Pipeline(nn.Module):
             raise ValueError(f"start ids have shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         return ids0.to(device, torch.long).clone(memory_format=torch.contiguous_format)
 
-    def decode_session(self, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True):
+    def decode_session(self, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True, max_context_len=None):
         """a DecodeSession over this pipeline (paintmind_amd/serve.py): `slots` images decode together, each with its own
-        timesteps / temperature / top-k / seed, and new requests are admitted into free slots between steps"""
+        timesteps / temperature / top-k / seed / context length, and new requests are admitted into free slots between steps"""
         from .serve import DecodeSession
-        return DecodeSession(self, slots=slots, conditional=conditional, use_graph=use_graph, record_steps=record_steps, decode=decode)
+        return DecodeSession(self, slots=slots, conditional=conditional, use_graph=use_graph, record_steps=record_steps, decode=decode,
+                             max_context_len=max_context_len)
 
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
-                     join=True, wait_current=True, host=None, guidance_scale=None, ids0=None):
+                     join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
 
         streams > 1 (or a tuple of micro-batch sizes): the batch is cut into contiguous micro-batches that run CONCURRENTLY on separate HIP
@@ -378,7 +396,10 @@ class Pipeline(nn.Module):
         ids0 (streams = 1 only): start from these ids [B, N] int64 instead of the all-mask state (the region loops of inpaint / outpaint).
         Without ids0 the native loop is told that it starts from the all-mask state (from_mask): an unconditional loop then samples
         its step 0 from logits the handle computed once (include/pmhip.h, PMHIP_GENERATE_FROM_MASK) -- same result, bit for bit,
-        as passing an explicit all-mask ids0, which keeps the full path."""
+        as passing an explicit all-mask ids0, which keeps the full path.
+        context_lens (None: every image attends to all L rows of its context): one context length per image; image b's cross-attention
+        sees rows [0, context_lens[b]) only.  Every lane takes the slice of its micro-batch."""
+        lens = self._lens(context_lens, context, B)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
@@ -405,7 +426,7 @@ class Pipeline(nn.Module):
             return eng.generate(self.vqgan.engine(), ids, context, temps, nmask, decode_flags, topk, seed=seed,
                                 image_base=image_base, use_graph=use_graph,
                                 host=None if host is None else (host[0], 0, host[1][0]), want_device_imgs=host is None,
-                                guidance_scale=guidance_scale, from_mask=ids0 is None)
+                                guidance_scale=guidance_scale, from_mask=ids0 is None, context_lens=lens)
         from .dist import shard_range
         cur = torch.cuda.current_stream(eng.device)
         if wait_current:
@@ -422,7 +443,8 @@ class Pipeline(nn.Module):
                 ids, imgs = e.generate(v, ids, c, temps, nmask, decode_flags, topk, seed=seed, image_base=image_base + lo,
                                        use_graph=use_graph, host=None if host is None else (host[0], lo, host[1][i]),
                                        want_device_imgs=host is None, guidance_scale=guidance_scale, concurrent_lanes=True,
-                                       from_mask=True)          # lanes exist for ids0 None only (checked above)
+                                       from_mask=True,          # lanes exist for ids0 None only (checked above)
+                                       context_lens=None if lens is None else lens[lo:hi])
             return ids, imgs, st
 
         lanes = self._lanes(streams)
@@ -462,7 +484,8 @@ class Pipeline(nn.Module):
         return ids, imgs
 
     def generate(self, text, timesteps=18, temperature=1.0, topk=5, save_interval=2, seed=None, image_base=0,
-                 return_ids=False, keep_on_device=False, use_graph=None, streams=None, guidance_scale=None):
+                 return_ids=False, keep_on_device=False, use_graph=None, streams=None, guidance_scale=None, mask_padding=False,
+                 context_lens=None):
         """Full decode loop (generate.py:183-198): list of (B,3,H,W) CPU tensors for steps % save_interval == 0.
 
         The call is the fast path by default: the loop replays captured hipGraphs (first call eager, second call captures),
@@ -482,15 +505,24 @@ class Pipeline(nn.Module):
         The returned tensors are views of ONE pinned host buffer [n_saved, B, C, H, W] that the package reuses once no
         tensor (or numpy alias) of an earlier call is alive: keeping one image keeps the whole buffer page-locked, and an
         asynchronous `.to('cuda', non_blocking=True)` of a returned image must be synchronised before the LAST reference to
-        the list is dropped.  `.clone()` a result to own ordinary pageable memory, as the reference's `img.cpu()` returns."""
+        the list is dropped.  `.clone()` a result to own ordinary pageable memory, as the reference's `img.cpu()` returns.
+
+        mask_padding (extension; False = the reference's behaviour: every row of the padded context is attended to, padding
+        included): the text model is asked for the prompts' token counts (``text_model(text, return_lens=True)``) and every image's
+        cross-attention sees its own tokens only.  context_lens gives the lengths explicitly instead (one per prompt)."""
         B = len(text)
-        context = self.text_model(text)
+        if mask_padding and context_lens is None:
+            context, context_lens = self.text_model(text, return_lens=True)
+        else:
+            context = self.text_model(text)
         if guidance_scale is not None and context is None:
             raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
+        lens = self._lens(context_lens, context, B)
         if self._on_cpu():
             if guidance_scale is not None:
-                return self._generate_guided_cpu(context, B, timesteps, temperature, topk, save_interval, seed, return_ids, guidance_scale)
-            return self._generate_cpu(text, context, timesteps, temperature, topk, save_interval, seed, return_ids)
+                return self._generate_guided_cpu(context, B, timesteps, temperature, topk, save_interval, seed, return_ids, guidance_scale,
+                                                 lens)
+            return self._generate_cpu(text, context, timesteps, temperature, topk, save_interval, seed, return_ids, lens)
         eng = self.engine()
         if seed is None:
             seed = _draw_seed()
@@ -512,7 +544,7 @@ class Pipeline(nn.Module):
         n_dec = sum(flags)
         if keep_on_device or n_dec == 0:
             ids, imgs = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
-                                          use_graph=use_graph, streams=streams, guidance_scale=guidance_scale)
+                                          use_graph=use_graph, streams=streams, guidance_scale=guidance_scale, context_lens=lens)
             out = [] if imgs is None else list(imgs)
             return (out, ids) if return_ids else out
         vq = self.vqgan.engine()
@@ -526,7 +558,8 @@ class Pipeline(nn.Module):
             cs.append(torch.cuda.Stream(device=eng.device))
         try:
             ids, _ = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
-                                       use_graph=use_graph, streams=streams, host=(host, cs), guidance_scale=guidance_scale)
+                                       use_graph=use_graph, streams=streams, host=(host, cs), guidance_scale=guidance_scale,
+                                       context_lens=lens)
         except BaseException:
             # a lane failed: whatever the other lanes queued may still be writing into `host`; drain it, and never hand
             # this buffer out again
@@ -546,7 +579,7 @@ class Pipeline(nn.Module):
         return (out, ids) if return_ids else out
 
     @torch.no_grad()
-    def _generate_guided_cpu(self, context, B, timesteps, temperature, topk, save_interval, seed, return_ids, scale):
+    def _generate_guided_cpu(self, context, B, timesteps, temperature, topk, save_interval, seed, return_ids, scale, context_lens=None):
         """generate.py:183-198 with guided steps (see `sample`) for a pipeline that lives on the CPU; same return structure.
         (On the GPU the guided loop is the native one: pmhip_pipeline_generate_guided, graph-captured and lane-able.)"""
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
@@ -554,7 +587,7 @@ class Pipeline(nn.Module):
         for step in range(timesteps):
             nm = num_token_masked(mask_schedule((step + 1) / timesteps), self.num_tokens)
             ids, img = self._sample_cpu(ids, nm, context, topk, temperature * (1 - step / timesteps), None,
-                                        None if seed is None else seed + step, scale)
+                                        None if seed is None else seed + step, scale, context_lens)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs

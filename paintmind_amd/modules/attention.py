@@ -55,15 +55,21 @@ class CrossAttention(nn.Module):
             self._pack = (stamp, pk)
         return self._pack[1]
 
-    def forward(self, x, context=None):
-        return self.run(x, context, residual=None)
+    def forward(self, x, context=None, context_lens=None):
+        return self.run(x, context, residual=None, context_lens=context_lens)
 
-    def run(self, x, context=None, residual=None):
-        """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x."""
+    def run(self, x, context=None, residual=None, context_lens=None):
+        """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x.
+        context_lens (extension; None = the reference's behaviour, no mask): one length per image -- image b attends to rows
+        [0, context_lens[b]) of its context only; the rows beyond never reach the result, NaN included."""
         if self.training and self.to_out[1].p > 0:
             raise RuntimeError("paintmind_amd attention is inference-only (dropout>0 in training mode)")
+        if context_lens is not None:
+            if context is None:
+                raise ValueError("context_lens needs a context (self-attention takes no key-padding mask)")
+            context_lens = ops.host_lens(context_lens, x.shape[0], context.shape[1])
         if not x.is_cuda:
-            return self._run_cpu(x, context, residual)
+            return self._run_cpu(x, context, residual, context_lens)
         B, N, D = x.shape
         dtype = x.dtype
         pk = self.packed(dtype)
@@ -81,23 +87,33 @@ class CrossAttention(nn.Module):
             (q,) = ops.gemm_heads(a, pk["wq"], self.heads, N, [ops.PART_Q], q_scale, self.dim_head)
             k, vt = ops.gemm_heads(c, pk["wkv"], self.heads, L, [ops.PART_K, ops.PART_V], 1.0, self.dim_head)
             n_kv = L
-        o = ops.attention(q, k, vt, n_kv, use_exp2=fast)
+        kv_lens = None if context_lens is None else torch.tensor(context_lens, dtype=torch.int32, device=x.device)
+        o = ops.attention(q, k, vt, n_kv, use_exp2=fast, kv_lens=kv_lens)
         res = residual.reshape(B * N, D) if residual is not None else None
         out_dtype = torch.float32 if residual is not None else dtype
         out = ops.gemm(o, pk["wo"], bias=pk["bo"], residual=res, out_dtype=out_dtype)
         return out.reshape(B, N, D)
 
 
-    def _run_cpu(self, x, context, residual):
+    def _run_cpu(self, x, context, residual, context_lens=None):
         """Parameters on the CPU: the same operator in plain torch (reference modules/attention.py:43-59; BASELINE config 1
-        runs the model there).  q is scaled BEFORE the product (:52), no mask, softmax over the keys, head split 'b n (h d)'."""
+        runs the model there).  q is scaled BEFORE the product (:52), no mask, softmax over the keys, head split 'b n (h d)'.
+        context_lens (a checked list, or None): scores of the keys at or beyond an image's length become -inf (whatever they
+        were, NaN included) and the V rows there are ZEROED -- a probability of 0 alone would not do, 0 * NaN is NaN in P @ V."""
         B, N, _ = x.shape
         c = x if context is None else context
+        if context_lens is not None and len(set(context_lens)) == 1:
+            c, context_lens = c[:, :context_lens[0]], None       # one length for the batch (B = 1 always): cut the padding off
         h, d = self.heads, self.dim_head
         q = (F.linear(x, self.to_q.weight) * self.scale).reshape(B, N, h, d).permute(0, 2, 1, 3)
         k = F.linear(c, self.to_k.weight).reshape(B, c.shape[1], h, d).permute(0, 2, 1, 3)
         v = F.linear(c, self.to_v.weight).reshape(B, c.shape[1], h, d).permute(0, 2, 1, 3)
-        p = torch.softmax(q @ k.transpose(-1, -2), dim=-1)
+        s = q @ k.transpose(-1, -2)
+        if context_lens is not None:
+            pad = torch.arange(c.shape[1])[None, :] >= torch.tensor(context_lens)[:, None]           # [B, L]
+            s = s.masked_fill(pad[:, None, None, :], float("-inf"))
+            v = v.masked_fill(pad[:, None, :, None], 0.0)
+        p = torch.softmax(s, dim=-1)
         o = (p @ v).permute(0, 2, 1, 3).reshape(B, N, h * d)
         out = F.linear(o, self.to_out[0].weight, self.to_out[0].bias)
         return out if residual is None else out + residual

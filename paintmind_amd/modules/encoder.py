@@ -18,6 +18,17 @@ def _module_device(module):
     return next(module.parameters()).device
 
 
+def _pad_id(tokenizer):
+    pad = getattr(tokenizer, "pad_token_id", None)
+    return 0 if pad is None else int(pad)                  # T5's pad token is id 0
+
+
+def _count_tokens(mask):
+    """[B, L] non-pad mask -> int32 [B] on the host: the non-pad token count of every prompt, at least 1 (an empty prompt still
+    attends to one row: a softmax over nothing has no value)"""
+    return mask.to(torch.int64).sum(-1).clamp_(min=1).to(torch.int32).cpu()
+
+
 class T5TextEmbedder(nn.Module):
     """Flan-T5 encoder (reference encoder.py:18-42): tokens padded / truncated to max_length -> last_hidden_state."""
 
@@ -41,11 +52,19 @@ class T5TextEmbedder(nn.Module):
             param.requires_grad = False
 
     @torch.no_grad()
-    def forward(self, text):
+    def forward(self, text, return_lens=False):
+        """-> context (B, max_length, d_model), every position as in the reference (no mask is passed to the encoder).
+        return_lens: -> (context, lens), lens[b] = the number of non-pad tokens of prompt b (the end-of-sequence token counts;
+        at least 1), for ``Pipeline.generate(mask_padding=True)`` / ``context_lens=``."""
         enc = self.tokenizer(text, truncation=True, max_length=self.max_length, return_length=True,
                              return_overflowing_tokens=False, padding="max_length", return_tensors="pt")
-        tokens = enc["input_ids"].to(_module_device(self.transformer))
-        return self.transformer(input_ids=tokens).last_hidden_state
+        ids = enc["input_ids"]
+        tokens = ids.to(_module_device(self.transformer))
+        context = self.transformer(input_ids=tokens).last_hidden_state
+        if not return_lens:
+            return context
+        mask = enc["attention_mask"] if "attention_mask" in enc else ids != _pad_id(self.tokenizer)
+        return context, _count_tokens(torch.as_tensor(mask))
 
     def encode(self, text):
         return self(text)
@@ -90,9 +109,12 @@ class CLIPTextEmbedder(nn.Module):
             param.requires_grad = False
 
     @torch.no_grad()
-    def forward(self, text):
+    def forward(self, text, return_lens=False):
+        """return_lens: -> (context, lens), lens[b] = the number of non-pad tokens of prompt b (open_clip pads with 0; the
+        start and end tokens count), for ``Pipeline.generate(mask_padding=True)`` / ``context_lens=``."""
         tokens = self.tokenize(text)
-        return self.encode_with_transformer(tokens.to(_module_device(self.model)))
+        context = self.encode_with_transformer(tokens.to(_module_device(self.model)))
+        return (context, _count_tokens(tokens != 0)) if return_lens else context
 
     def encode_with_transformer(self, tokens):
         m = self.model
@@ -117,8 +139,8 @@ class NullTextEmbedder(nn.Module):
     """Unconditional generation through the drop-in API: the context is None, so attn2 runs as a second self-attention
     (reference modules/attention.py:47).  BASELINE.json configs[2] is this path."""
 
-    def forward(self, text):
-        return None
+    def forward(self, text, return_lens=False):
+        return (None, None) if return_lens else None
 
 
 class SyntheticTextEmbedder(nn.Module):
@@ -134,7 +156,10 @@ class SyntheticTextEmbedder(nn.Module):
         self.base_index = 0
         self.register_buffer("_anchor", torch.zeros(1), persistent=False)
 
-    def forward(self, text):
+    def forward(self, text, return_lens=False):
+        """return_lens: every row is a feature (there is no tokenizer and no padding): lens = max_length for every prompt"""
+        if return_lens:
+            return self.forward(text), torch.full((len(text),), self.max_length, dtype=torch.int32)
         rows = []
         for i in range(len(text)):
             g = torch.Generator().manual_seed(self.seed * 1000003 + self.base_index + i)

@@ -49,6 +49,22 @@ def round_up(v, m):
     return (v + m - 1) // m * m
 
 
+def host_lens(lens, B, L, what="context_lens"):
+    """per-image lengths (a list, a CPU tensor or a device tensor; None passes through) -> a list of B ints on the host, each in
+    [1, L]: brought to the host ONCE per call, checked before anything is launched"""
+    if lens is None:
+        return None
+    vals = lens.detach().reshape(-1).tolist() if isinstance(lens, torch.Tensor) else list(lens)
+    if len(vals) != B:
+        raise ValueError(f"{what}: {len(vals)} lengths for a batch of {B}")
+    out = []
+    for b, v in enumerate(vals):
+        if int(v) != v or not 1 <= int(v) <= L:
+            raise ValueError(f"{what}: image {b}: length {v} must be an integer in [1, {L}]")
+        out.append(int(v))
+    return out
+
+
 def swiglu_hidden(hidden_features):
     """hidden width rule of SwiGLUFFNFused (reference modules/mlp.py:53)."""
     return (int(hidden_features * 2 / 3) + 7) // 8 * 8
@@ -321,15 +337,22 @@ def attention_fallbacks(reset=False, device=None):
     return int(n.value)
 
 
-def attention(q, k, vt, n_kv, use_exp2=False):
-    """q [B,H,Nq,dh], k [B,H,Nkp,dh], vt [B,H,dh,Nkp] -> [B*Nq, H*dh]  (dh 64: tuned MFMA kernel; else pmhip_attention_dh)."""
-    dev = _dev(q, k, vt)
+def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None):
+    """q [B,H,Nq,dh], k [B,H,Nkp,dh], vt [B,H,dh,Nkp] -> [B*Nq, H*dh]  (dh 64: tuned MFMA kernel; else pmhip_attention_dh).
+    kv_lens (None: every image attends to n_kv keys): int32 [B] on the device, image b attends to its first kv_lens[b] keys
+    (clamped to [1, n_kv] by the kernel) -- pmhip_attention_lens."""
+    dev = _dev(q, k, vt, kv_lens)
     lib = _lib.load()
     B, H, Nq, dh = q.shape
     nkp = k.shape[2]
     out = torch.empty(B * Nq, H * dh, device=dev, dtype=q.dtype)
+    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
+        raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
     with torch.cuda.device(dev):
-        if dh == 64:
+        if kv_lens is not None:
+            check(lib.pmhip_attention_lens(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * dh, B, H, dh, Nq, n_kv, nkp,
+                                           int(use_exp2), _p(kv_lens), stream_ptr(dev)), "pmhip_attention_lens")
+        elif dh == 64:
             check(lib.pmhip_attention(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * 64, B, H, Nq, n_kv, nkp,
                                       int(use_exp2), stream_ptr(dev)), "pmhip_attention")
         else:

@@ -8,13 +8,21 @@ index k, context c) that sits in slot j of an S-slot session produces, bit for b
 ids of row j of ``Pipeline.generate_ids(context with c in row j, B=S, T, temperature, topk, ..., seed, image_base=k - j,
 streams=1, guidance_scale=s)``; its image is ``vqgan.decode_from_indice`` of the last step's predictions.
 
+Contexts of different lengths share a session: a request's ``context`` is ``[L_r, D]`` with its own ``L_r``.  The session keeps its
+contexts in one ``[S, capacity, D]`` tensor -- ``max_context_len`` rows, or, when that is None, as many as the longest context
+admitted so far (growing re-prepares the cross K/V) -- and hands the native step one length per slot
+(pmhip_pipeline_step_slots_lens), so a request never attends to the rows behind its own.  The contract above then reads
+``generate_ids(context padded to the capacity, context_lens with L_r in row j, ...)`` (a step taken at capacity C is the scalar
+step at capacity C: a request that lives through a growth follows the capacity step by step).  A step in which every occupied slot fills
+the capacity takes the entry without lengths: the same result, on the kernels every earlier version ran.
+
 Guidance is per request (``submit(guidance_scale=s)``, conditional sessions only): the native step
 (pmhip_pipeline_step_slots_guided) reads a scale per slot from a second device record, runs the tower twice in a step in which
 at least one active slot is guided, and combines the two towers' logits on the rows of the guided slots only, so requests with
 different scales, and unguided ones, share a batch and each computes what it would compute alone.
 
 Limits: a session is all-conditional or all-unconditional (``context=None`` selects attn2's inputs for the whole batch), every
-context of a session has the same length, top-k <= 8 (the block-statistics sampling kernel), and idle slots still run through
+context of a session has the same width D, top-k <= 8 (the block-statistics sampling kernel), and idle slots still run through
 the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the second tower pass: the
 unconditional pass runs at the session's batch size.  The guided loop's step-0 cache ("Not built") stays
 not built.
@@ -57,9 +65,12 @@ class DecodeSession:
     """``pipe.decode_session(slots=64, conditional=True, use_graph=True)``; see the module docstring.
     use_graph=None follows PMHIP_GENERATE_GRAPH like ``Pipeline.generate``."""
 
-    def __init__(self, pipe, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True):
+    def __init__(self, pipe, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True, max_context_len=None):
         if slots < 1:
             raise ValueError("a decode session needs at least one slot")
+        if max_context_len is not None and int(max_context_len) < 1:
+            raise ValueError("max_context_len must be >= 1 (or None: the capacity grows with the contexts admitted)")
+        self.max_context_len = None if max_context_len is None else int(max_context_len)
         self.pipe, self.size, self.conditional = pipe, int(slots), bool(conditional)
         if use_graph is None:
             use_graph = os.environ.get("PMHIP_GENERATE_GRAPH", "1") != "0"
@@ -74,16 +85,18 @@ class DecodeSession:
         self._cpu = pipe._on_cpu()
         self._ids = None                    # GPU: [S, N] int64, one row per slot; CPU: one [1, N] tensor per slot
         self._rows = [None] * self.size
-        self._ctx = None                    # GPU, conditional: [S, L, context_dim] fp32
+        self._ctx = None                    # GPU, conditional: [S, capacity, context_dim] fp32, a slot's rows behind its length are 0
         self._ctx_dirty = True              # a slot's context changed since the cross K/V were prepared
+        self._lens = [1] * self.size        # GPU, conditional: context rows of every slot (an idle slot keeps a valid value)
         self._records = (_lib.Slot * self.size)()
         self._guides = (_lib.SlotGuide * self.size)() if self.conditional else None
 
     # -- requests -----------------------------------------------------------------------------------
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
                guidance_scale=None):
-        """queue one request (any time, also between steps) -> its Request.  `context` [L, D] may be given instead of `text`
-        (a conditional session runs the pipeline's text model on `text` otherwise); `ids0` [N]: start ids instead of all-mask;
+        """queue one request (any time, also between steps) -> its Request.  `context` [L_r, D] may be given instead of `text`
+        (a conditional session runs the pipeline's text model on `text` otherwise), with its OWN length L_r: the request attends
+        to exactly these rows; `ids0` [N]: start ids instead of all-mask;
         `guidance_scale` (None = not guided): this request samples from uncond + scale * (cond - uncond), like
         ``Pipeline.generate(guidance_scale=)``."""
         timesteps, topk = int(timesteps), int(topk)
@@ -106,8 +119,10 @@ class DecodeSession:
                     raise ValueError("the pipeline's text model gives no context: open the session with conditional=False")
                 context = context[0]
             context = context.detach().to(torch.float32)
-            if context.dim() != 2:
-                raise ValueError(f"a request's context is [L, D], got {tuple(context.shape)}")
+            if context.dim() != 2 or context.shape[0] < 1:
+                raise ValueError(f"a request's context is [L, D] with L >= 1, got {tuple(context.shape)}")
+            if self.max_context_len is not None and context.shape[0] > self.max_context_len:
+                raise ValueError(f"a context of {context.shape[0]} rows does not fit the session's max_context_len={self.max_context_len}")
         elif context is not None:
             raise ValueError("an unconditional session takes no context")
         if seed is None:
@@ -194,11 +209,18 @@ class DecodeSession:
             self._ids[r.slot] = mask_id if r.ids0 is None else r.ids0[0].to(eng.device)
             if self.conditional:
                 c = r.context.to(eng.device)
+                Lr = c.shape[0]
                 if self._ctx is None:
-                    self._ctx = torch.zeros(self.size, c.shape[0], c.shape[1], device=eng.device, dtype=torch.float32)
-                if tuple(c.shape) != tuple(self._ctx.shape[1:]):
-                    raise ValueError(f"every context of a session has the same shape: {tuple(c.shape)} != {tuple(self._ctx.shape[1:])}")
-                self._ctx[r.slot] = c
+                    self._ctx = torch.zeros(self.size, self.max_context_len or Lr, c.shape[1], device=eng.device, dtype=torch.float32)
+                if c.shape[1] != self._ctx.shape[2]:
+                    raise ValueError(f"every context of a session has the same width: {c.shape[1]} != {self._ctx.shape[2]}")
+                if Lr > self._ctx.shape[1]:              # max_context_len None (submit checked the other case): the capacity grows
+                    grown = torch.zeros(self.size, Lr, c.shape[1], device=eng.device, dtype=torch.float32)
+                    grown[:, :self._ctx.shape[1]] = self._ctx
+                    self._ctx = grown
+                self._ctx[r.slot, :Lr] = c
+                self._ctx[r.slot, Lr:] = 0
+                self._lens[r.slot] = Lr
                 self._ctx_dirty = True
         if self.active == 0:
             return []
@@ -219,15 +241,19 @@ class DecodeSession:
         want_aux = (bool(retiring) and self.decode) or self.record_steps
         ctx = self._ctx if self.conditional else None
         keep = not self._ctx_dirty
+        # one length per slot -- unless every occupied slot fills the capacity, which IS the step without lengths
+        lens = None
+        if self.conditional and any(r is not None and self._lens[j] != ctx.shape[1] for j, r in enumerate(self.occupied)):
+            lens = [min(n, ctx.shape[1]) for n in self._lens]
         try:
             _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep, want_aux=want_aux,
-                                            guides=self._guides)
+                                            guides=self._guides, context_lens=lens)
         except _lib.PmhipError as e:
             # another call on this handle (pipe.generate, a rebuilt engine ...) replaced the prepared context: prepare it again
             if not (keep and getattr(e, "code", None) == _lib.PMHIP_ESTATE):
                 raise
             _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=False, want_aux=want_aux,
-                                            guides=self._guides)
+                                            guides=self._guides, context_lens=lens)
         self._ctx_dirty = False
         for r in self.occupied:
             if r is not None:

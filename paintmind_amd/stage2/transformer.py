@@ -21,13 +21,15 @@ class Layer(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ffnet = SwiGLUFFNFused(in_features=dim, hidden_features=mlp_dim)
 
-    def forward(self, x, context=None):
-        """self-attn, cross-attn (a 2nd self-attn when context is None), SwiGLU (transformer.py:44-49)."""
+    def forward(self, x, context=None, context_lens=None):
+        """self-attn, cross-attn (a 2nd self-attn when context is None), SwiGLU (transformer.py:44-49).
+        context_lens: per-image context lengths for the cross-attention only (modules/attention.py)."""
         B, N, D = x.shape
         T = compute_dtype_of(self)
         x = x.contiguous()
         x = self.attn1.run(_norm(x.reshape(B * N, D), self.norm1, T).reshape(B, N, D), None, residual=x)
-        x = self.attn2.run(_norm(x.reshape(B * N, D), self.norm2, T).reshape(B, N, D), context, residual=x)
+        x = self.attn2.run(_norm(x.reshape(B * N, D), self.norm2, T).reshape(B, N, D), context, residual=x,
+                           context_lens=context_lens if context is not None else None)
         return self.ffnet.run(_norm(x.reshape(B * N, D), self.norm3, T).reshape(B, N, D), residual=x)
 
 
@@ -45,8 +47,14 @@ class CondTransformer(nn.Module):
         self.to_logits = nn.Linear(dim, num_classes)
         _xavier_like_reference(self)
 
-    def forward(self, x, context=None):
-        """operator-level composition of transformer.py:80-93 (Pipeline uses the native engine instead)."""
+    def forward(self, x, context=None, context_lens=None):
+        """operator-level composition of transformer.py:80-93 (Pipeline uses the native engine instead).
+        context_lens (extension; None = the reference's behaviour): image b's cross-attention sees rows [0, context_lens[b]) of
+        its context only.  The context projection still covers every row: it is row-local, so padding stays in the padding."""
+        if context_lens is not None:
+            if context is None:
+                raise ValueError("context_lens needs a context (context None IS the unconditional branch)")
+            context_lens = ops.host_lens(context_lens, x.shape[0], context.shape[1])
         T = compute_dtype_of(self)
         B, N, E = x.shape
         dim = self.token_proj.out_features
@@ -57,7 +65,7 @@ class CondTransformer(nn.Module):
             if context is not None:
                 context = self.context_proj(context.float())
             for layer in self.layers:
-                h = layer(h, context)
+                h = layer(h, context, context_lens)
             return self.to_logits(self.norm(h))
         a = ops.convert_pad(x.contiguous().float().reshape(B * N, E), 64, T)
         pos = self.position_embedding.detach()[0].contiguous()
@@ -70,7 +78,7 @@ class CondTransformer(nn.Module):
                 c = ops.gemm(c, packing.pad_cols(self.context_proj.weight, c.shape[1], T))
             context = c.reshape(B, L, dim)
         for layer in self.layers:
-            h = layer(h, context)
+            h = layer(h, context, context_lens)
         y = _norm(h.reshape(B * N, dim), self.norm, T)
         logits = ops.gemm(y, packing.cast(self.to_logits.weight, T), bias=self.to_logits.bias.detach().float(),
                           out_dtype=torch.float32)

@@ -79,6 +79,7 @@ PmTimer::~PmTimer() {}
 namespace old {
 #include "../../paintmind_amd/csrc/attention.hip"
 int pm_attention_bf16(const void*, const void*, const void*, void*, int, int, int, int, int, int, int, hipStream_t) { return -1; }
+int pm_attention_bf16_lens(const void*, const void*, const void*, void*, int, int, int, int, int, int, int, const int*, hipStream_t) { return -1; }
 int run(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad, int use_exp2, hipStream_t s) {
     return pmhip_attention(PMHIP_BF16, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, s);
 }
