@@ -72,13 +72,6 @@ struct PmGenParams {
     float temps[PM_MAX_STEPS];
     int nmask[PM_MAX_STEPS];
 };
-// block_stats: NULL, or the (max, sum of exp) pairs of the row's 64-column blocks, [M][V/64][2] (softmax_block_stat below)
-// period: 0, or the number of logits (and statistics) rows there are -- row r then samples from row r % period
-int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id, int topk,
-                   float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base, int64_t* pred_out,
-                   int64_t* ids_out, float* score_out, int M, int V, const PmGenParams* gp, int period, pmhip_stream stream);
-int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N, const PmGenParams* gp, int step,
-              pmhip_stream stream);
 
 // ---------------------------------------------------------------------------------------------
 // per-IMAGE decode state (include/pmhip.h, pmhip_slot): device memory, one record per image of the batch.  The slots forms of the
@@ -86,10 +79,31 @@ int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, 
 // ---------------------------------------------------------------------------------------------
 static_assert(sizeof(pmhip_slot) == 32, "pmhip_slot is 32 bytes: two 16-byte words per image");
 constexpr uint32_t PM_SLOT_IDLE = 0x80000000u;              // bit 31 of pmhip_slot::step
-int pm_sample_rows_slots(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
-                         const pmhip_slot* slots, int tokens, int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V,
-                         pmhip_stream stream);
-int pm_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id, int B, int N, pmhip_stream stream);
+
+// ---------------------------------------------------------------------------------------------
+// Where a launch of the sampling tail takes its step values from -- exactly one of
+//   BATCH   the scalars below, one set for every row;
+//   PARAMS  a replayed graph: temperature, mask count, seed and row base from the device block gp, indexed by `step`; top-k and
+//           the step stay kernel arguments (they are part of the graph);
+//   SLOTS   per image: the device records slots [M / tokens] (the block-statistics kernel only: V % 64 == 0, top-k <= 8).
+// ---------------------------------------------------------------------------------------------
+struct PmStepSource {
+    enum Kind { BATCH, PARAMS, SLOTS } kind;
+    int topk; float temperature; int num_mask; uint64_t seed; uint32_t step; uint64_t row_base;
+    const PmGenParams* gp;
+    const pmhip_slot* slots; int tokens;
+    static PmStepSource batch(int topk, float temperature, int num_mask, uint64_t seed, uint32_t step, uint64_t row_base) {
+        return {BATCH, topk, temperature, num_mask, seed, step, row_base, nullptr, nullptr, 0};
+    }
+    static PmStepSource params(const PmGenParams* gp, int topk, uint32_t step) { return {PARAMS, topk, 0.f, 0, 0, step, 0, gp, nullptr, 0}; }
+    static PmStepSource per_image(const pmhip_slot* slots, int tokens) { return {SLOTS, 0, 0.f, 0, 0, 0, 0, nullptr, slots, tokens}; }
+};
+// block_stats: NULL, or the (max, sum of exp) pairs of the row's 64-column blocks, [M][V/64][2] (softmax_block_stat below)
+// period: 0, or the number of logits (and statistics) rows there are -- row r then samples from row r % period
+int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int period, const int64_t* ids_in, int64_t mask_id,
+                   const float* noise, int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, const PmStepSource& src,
+                   pmhip_stream stream);
+int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, const PmStepSource& src, pmhip_stream stream);
 
 // ---------------------------------------------------------------------------------------------
 // device helpers

@@ -913,7 +913,7 @@ int s2_tower(pmhip_s2* h, const void* tp, int B, float* logits, hipStream_t s, b
 }
 
 // Pipeline.sample after the context is prepared (generate.py:161-179)
-// guidance != nullptr: the step's logits are uncond + *guidance * (cond - uncond), uncond = the same tower without the context
+// Step::guidance != nullptr: the step's logits are uncond + *guidance * (cond - uncond), uncond = the same tower without the context
 // (the branch the reference trains by dropping the text, utils/trainer.py:379,387-388); everything after the logits is unchanged
 // The step in two halves, so that a caller can put something between the tower and the sampling (the small-batch loop joins the
 // previous step's decode there).  step_tower: ids2tokens + the tower(s) -> logits.  step_tail: sampling, the optional decode,
@@ -960,12 +960,32 @@ int copy_aux(const StepBufs& b, size_t M, int64_t* pred_out, float* score_out, h
     return PMHIP_OK;
 }
 
-// guides != nullptr (with the device records `slots`): per-image guidance (pmhip_pipeline_step_slots_guided).  BOTH towers for the
-// whole batch, the first one with the logits GEMM's block statistics (the same logits as without them, bit for bit:
-// tests/test_gpu_abi_memory.py), then the combination in place on the rows of the guided images only -- an unguided image keeps
-// the first tower's logits and statistics, i.e. exactly what the one-pass step leaves for it
-int step_tower(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s, const float* guidance, const pmhip_slot* slots = nullptr,
-               const pmhip_slot_guide* guides = nullptr) {
+// ONE description of a step, taken by both halves: where the values it samples, re-masks and guides by come from.  Exactly one
+// of (the three sources of common.h PmStepSource, which source() maps them onto)
+//   the batch scalars: one set of values for the batch;
+//   gp: temperature, mask count, seed and row base from the device parameter block of a replayed loop (top-k and step stay);
+//   slots: every per-image value from the device records slots [B], with guides [B] where an active slot is guided.
+// shared0: every image samples from the one all-mask image's kept rows (step0_tower_once); guidance: the batch's scale (above).
+struct Step {
+    int topk = 0; float temperature = 0.f; int num_mask = 0;
+    const float* noise = nullptr;
+    uint64_t seed = 0; uint32_t step = 0; uint64_t image_base = 0;
+    const PmGenParams* gp = nullptr;
+    bool shared0 = false;
+    const float* guidance = nullptr;
+    const pmhip_slot* slots = nullptr; const pmhip_slot_guide* guides = nullptr;
+    PmStepSource source(int tokens) const {
+        if (slots) return PmStepSource::per_image(slots, tokens);
+        if (gp) return PmStepSource::params(gp, topk, step);
+        return PmStepSource::batch(topk, temperature, num_mask, seed, step, image_base * (uint64_t)tokens);
+    }
+};
+
+// guides: per-image guidance (pmhip_pipeline_step_slots_guided).  BOTH towers for the whole batch, the first one with the logits
+// GEMM's block statistics (the same logits as without them, bit for bit: tests/test_gpu_abi_memory.py), then the combination in
+// place on the rows of the guided images only -- an unguided image keeps the first tower's logits and statistics, i.e. exactly
+// what the one-pass step leaves for it
+int step_tower(pmhip_s2* s2, const int64_t* ids, int B, const Step& st, hipStream_t s) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
     void* tp; StepBufs b;
@@ -973,14 +993,14 @@ int step_tower(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s, const flo
     PM_TRY(step_bufs(s2, M, false, b, s));
     // the statistics come from the logits GEMM, or -- one scale for the batch -- from the combination, which produces the logits
     // that are sampled
-    PM_TRY(s2_tower(s2, tp, B, b.logits, s, true, guidance ? nullptr : b.lstats));
-    if (!guidance && !guides) return PMHIP_OK;
+    PM_TRY(s2_tower(s2, tp, B, b.logits, s, true, st.guidance ? nullptr : b.lstats));
+    if (!st.guidance && !st.guides) return PMHIP_OK;
     float* uncond;
     WS(s2->ws, "s2.logits_u", (size_t)M * c.n_embed * 4, uncond);
     PM_TRY(s2_tower(s2, tp, B, uncond, s, false));
-    if (guides) return pmhip_guidance_combine_slots(b.logits, uncond, guides, slots, c.tokens, b.logits, b.lstats, M, c.n_embed, s);
-    if (b.lstats) return pmhip_guidance_combine_stats(b.logits, uncond, *guidance, b.logits, (size_t)M * c.n_embed, b.lstats, s);
-    return pmhip_guidance_combine(b.logits, uncond, *guidance, b.logits, (size_t)M * c.n_embed, s);
+    if (st.guides) return pmhip_guidance_combine_slots(b.logits, uncond, st.guides, st.slots, c.tokens, b.logits, b.lstats, M, c.n_embed, s);
+    if (b.lstats) return pmhip_guidance_combine_stats(b.logits, uncond, *st.guidance, b.logits, (size_t)M * c.n_embed, b.lstats, s);
+    return pmhip_guidance_combine(b.logits, uncond, *st.guidance, b.logits, (size_t)M * c.n_embed, s);
 }
 
 // the image of the predictions the last step_tail left in the handle's `s2.pred` (decoded from pred at ALL positions, generate.py:165)
@@ -991,39 +1011,25 @@ int decode_pred(pmhip_s2* s2, pmhip_vqgan* vq, int B, float* img_out, hipStream_
     return vq_decode_indices(vq, b.pred, B, img_out, s);
 }
 
-// what a step samples and re-masks by: one set of values for the batch (gp != nullptr: temperature, mask count, seed and row base
-// come from the device parameter block instead; shared0: every image samples from the one all-mask image's rows) ...
-struct StepScalars {
-    int topk = 0; float temperature = 0.f; int num_mask = 0;
-    const float* noise = nullptr;
-    uint64_t seed = 0; uint32_t step = 0; uint64_t image_base = 0;
-    const PmGenParams* gp = nullptr;
-    bool shared0 = false;
-};
-
-// ... or, slots != nullptr, every per-image value read from the device records `slots` [B] (sc is not looked at)
-int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, const StepScalars& sc, const pmhip_slot* slots, float* img_out,
-              int64_t* pred_out, float* score_out, hipStream_t s) {
+// sampling, the optional decode, the optional copies, re-masking
+int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, const Step& st, float* img_out, int64_t* pred_out, float* score_out,
+              hipStream_t s) {
     const auto& c = s2->cfg;
     const int M = B * c.tokens;
-    const bool shared0 = !slots && sc.shared0;
+    const PmStepSource src = st.source(c.tokens);
     StepBufs b;
-    PM_TRY(step_bufs(s2, M, shared0, b, s));                  // step_tower (or the shared step 0) filled the logits
-    if (slots)
-        PM_TRY(pm_sample_rows_slots(b.logits, c.n_embed, b.lstats, ids, (int64_t)c.n_embed, slots, c.tokens, b.pred, ids, b.score, M, c.n_embed, s));
-    else
-        PM_TRY(pm_sample_rows(b.logits, c.n_embed, b.lstats, ids, (int64_t)c.n_embed, sc.topk, sc.temperature, sc.noise, sc.seed, sc.step,
-                              sc.image_base * (uint64_t)c.tokens, b.pred, ids, b.score, M, c.n_embed, sc.gp, shared0 ? c.tokens : 0, s));
+    PM_TRY(step_bufs(s2, M, st.shared0, b, s));               // step_tower (or the shared step 0) filled the logits
+    PM_TRY(pm_sample_rows(b.logits, c.n_embed, b.lstats, st.shared0 ? c.tokens : 0, ids, (int64_t)c.n_embed, st.noise, b.pred, ids, b.score,
+                          M, c.n_embed, src, s));
     if (img_out) PM_TRY(decode_pred(s2, vq, B, img_out, s));
     PM_TRY(copy_aux(b, (size_t)M, pred_out, score_out, s));
-    if (slots) return pm_remask_slots(ids, b.score, slots, (int64_t)c.n_embed, B, c.tokens, s);
-    return pm_remask(ids, b.score, sc.num_mask, (int64_t)c.n_embed, B, c.tokens, sc.gp, (int)sc.step, s);
+    return pm_remask(ids, b.score, (int64_t)c.n_embed, B, c.tokens, src, s);
 }
 
-int sample_step(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, const StepScalars& sc, float* img_out, int64_t* pred_out,
-                float* score_out, hipStream_t s, const float* guidance = nullptr) {
-    PM_TRY(step_tower(s2, ids, B, s, guidance));
-    return step_tail(s2, vq, ids, B, sc, nullptr, img_out, pred_out, score_out, s);
+int sample_step(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, const Step& st, float* img_out, int64_t* pred_out, float* score_out,
+                hipStream_t s) {
+    PM_TRY(step_tower(s2, ids, B, st, s));
+    return step_tail(s2, vq, ids, B, st, img_out, pred_out, score_out, s);
 }
 
 // The tower half of step 0 of an unconditional loop from the all-mask state (ids: B all-mask images).  Its input is the same for
@@ -1037,7 +1043,7 @@ int step0_tower_once(pmhip_s2* s2, const int64_t* ids, int B, hipStream_t s) {
     const auto& c = s2->cfg;
     StepBufs kept, b;
     PM_TRY(step_bufs(s2, B * c.tokens, true, kept, s));
-    PM_TRY(step_tower(s2, ids, B, s, nullptr));
+    PM_TRY(step_tower(s2, ids, B, Step{}, s));
     PM_TRY(step_bufs(s2, B * c.tokens, false, b, s));
     PM_TRY(copy16_async(kept.logits, b.logits, (size_t)c.tokens * c.n_embed * 4, s));
     if (kept.lstats) PM_TRY(copy16_async(kept.lstats, b.lstats, (size_t)c.tokens * (c.n_embed / 64) * 8, s));
@@ -1142,15 +1148,15 @@ extern "C" int pmhip_s2_forward_lens(pmhip_s2* h, const float* tokens, const flo
 }
 
 static int pipeline_sample_impl(const char* who, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
-                                const int32_t* ctx_lens_host, const StepScalars& sc, float* img_out, int64_t* pred_out, float* score_out,
-                                const float* guidance, pmhip_stream stream) {
+                                const int32_t* ctx_lens_host, const Step& st, float* img_out, int64_t* pred_out, float* score_out,
+                                pmhip_stream stream) {
     PM_REQUIRE(s2 && ids && B > 0, "%s: bad arguments", who);
-    PM_REQUIRE(!guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
+    PM_REQUIRE(!st.guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
     hipStream_t s = (hipStream_t)stream;
     PM_TRY(s2_prepare_context(s2, context, L, B, s));
     PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
-    return sample_step(s2, vq, ids, B, sc, img_out, pred_out, score_out, s, guidance);
+    return sample_step(s2, vq, ids, B, st, img_out, pred_out, score_out, s);
 }
 
 extern "C" int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1158,8 +1164,7 @@ extern "C" int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids
                                      uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                      float* score_out, pmhip_stream stream) {
     return pipeline_sample_impl("pipeline_sample", s2, vq, ids, context, L, B, nullptr,
-                                StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out, nullptr,
-                                stream);
+                                Step{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out, stream);
 }
 
 extern "C" int pmhip_pipeline_sample_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1167,8 +1172,8 @@ extern "C" int pmhip_pipeline_sample_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64
                                             uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                             float* score_out, float guidance_scale, pmhip_stream stream) {
     return pipeline_sample_impl("pipeline_sample_guided", s2, vq, ids, context, L, B, nullptr,
-                                StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out,
-                                &guidance_scale, stream);
+                                Step{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, &guidance_scale}, img_out,
+                                pred_out, score_out, stream);
 }
 
 extern "C" int pmhip_pipeline_sample_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1176,8 +1181,8 @@ extern "C" int pmhip_pipeline_sample_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t
                                           uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                           float* score_out, int guided, float guidance_scale, pmhip_stream stream) {
     return pipeline_sample_impl("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host,
-                                StepScalars{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out,
-                                guided ? &guidance_scale : nullptr, stream);
+                                Step{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr},
+                                img_out, pred_out, score_out, stream);
 }
 
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
@@ -1292,10 +1297,9 @@ int pipeline_generate(const GenCall& c) {
         ++s2->s0_hits;
         if (s != s2->s0_stream) PM_HIP(hipStreamWaitEvent(s, s2->s0_ready.h, 0));
     }
-    // the tower half of step t
-    auto tower = [&](const int64_t* from, int t, hipStream_t on) -> int {
-        if (share0 && t == 0) return step0_tower_once(s2, from, B, on);
-        return step_tower(s2, from, B, on, c.guidance);
+    // the tower half of a step
+    auto tower = [&](const int64_t* from, const Step& st, hipStream_t on) -> int {
+        return st.shared0 ? step0_tower_once(s2, from, B, on) : step_tower(s2, from, B, st, on);
     };
 
     if (c.imgs_host) {
@@ -1323,9 +1327,9 @@ int pipeline_generate(const GenCall& c) {
         for (int t = 0; t < T; ++t) {
             const bool dec = c.decodes(t);
             float* img = !dec ? nullptr : (gimgs ? gimgs : c.imgs_out) + (size_t)d * img_elems;
-            StepScalars sc{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0};
-            PM_TRY(tower(c.ids, t, s));
-            PM_TRY(step_tail(s2, vq, c.ids, B, sc, nullptr, img, nullptr, nullptr, s));
+            const Step st{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0, c.guidance};
+            PM_TRY(tower(c.ids, st, s));
+            PM_TRY(step_tail(s2, vq, c.ids, B, st, img, nullptr, nullptr, s));
             PM_TRY(out.flush());                               // the previous image, now that one more step is queued behind it
             if (dec) PM_TRY(out.deliver(d++, img));
         }
@@ -1395,11 +1399,11 @@ int pipeline_generate(const GenCall& c) {
             }
         }
         for (int t = u.t0; t < u.t1; ++t) {
-            PM_TRY(tower(gids, t, on));
+            const Step st{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0, c.guidance};
+            PM_TRY(tower(gids, st, on));
             if (need_join) { PM_HIP(hipStreamWaitEvent(on, ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
             float* img = (u.decode_inline && c.decodes(t)) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
-            StepScalars sc{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0};
-            PM_TRY(step_tail(s2, vq, gids, B, sc, nullptr, img, nullptr, nullptr, on));
+            PM_TRY(step_tail(s2, vq, gids, B, st, img, nullptr, nullptr, on));
         }
         return PMHIP_OK;
     };
@@ -1500,9 +1504,11 @@ static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const fl
     if (two_pass) PM_TRY(s2->slots_ring.stage(dguides, slot_bytes, guides_host, guide_bytes, s));
     PM_TRY(s2->slots_ring.commit(s));
     ++(two_pass ? s2->slots_two_pass : s2->slots_one_pass);
+    Step st;
+    st.slots = dslots;
+    st.guides = dguides;
     auto run_step = [&](int64_t* on_ids, int64_t* pred, float* score, hipStream_t on) -> int {
-        PM_TRY(step_tower(s2, on_ids, B, on, nullptr, dslots, dguides));
-        return step_tail(s2, nullptr, on_ids, B, StepScalars{}, dslots, nullptr, pred, score, on);
+        return sample_step(s2, nullptr, on_ids, B, st, nullptr, pred, score, on);
     };
 
     // ignored exactly when pipeline_generate ignores its graph request (same bits either way)

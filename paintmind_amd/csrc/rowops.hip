@@ -192,28 +192,37 @@ __global__ __launch_bounds__(THREADS) void add_rows_kernel(const float* __restri
 // (no __restrict__: out is documented to alias cond or uncond; every element is read and then written by the same lane)
 // STATS: additionally the softmax statistics of every 64-element block of the result (16 consecutive lanes hold one block, four
 // consecutive elements each -- the layout of common.h softmax_block_stat): what the logits GEMM leaves behind for an unguided step.
+// guidance_body: THE loop of both kernels below.  The workgroups of gridDim.x grid-stride over the n4 float4s of the three views;
+// the statistics of float4 i's block go to block_stats[(stat_base + i) / 16].  n4 % 16 == 0 where STATS is set: the 16 lanes of
+// a block run the same iterations, so softmax_block_stat's DPP rows are always full.
+template <bool STATS>
+__device__ __forceinline__ void guidance_body(const float4* c4, const float4* u4, float4* o4, float2* block_stats, size_t n4, float scale,
+                                              size_t stat_base) {
+    for (size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x; i < n4; i += (size_t)gridDim.x * THREADS) {
+        const float4 c = c4[i], u = u4[i];
+        const float4 r = make_float4(fmaf(scale, c.x - u.x, u.x), fmaf(scale, c.y - u.y, u.y), fmaf(scale, c.z - u.z, u.z),
+                                     fmaf(scale, c.w - u.w, u.w));
+        o4[i] = r;
+        if constexpr (STATS) {
+            const float2 st = softmax_block_stat(r.x, r.y, r.z, r.w);
+            if ((threadIdx.x & 15) == 0) block_stats[(stat_base + i) >> 4] = st;
+        }
+    }
+}
+
 template <bool STATS>
 __global__ __launch_bounds__(THREADS) void guidance_kernel(const float* cond, const float* uncond, float scale, float* out, size_t n4,
                                                            float2* block_stats) {
-    for (size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x; i < n4; i += (size_t)gridDim.x * THREADS) {
-        const float4 c = reinterpret_cast<const float4*>(cond)[i], u = reinterpret_cast<const float4*>(uncond)[i];
-        const float4 r = make_float4(fmaf(scale, c.x - u.x, u.x), fmaf(scale, c.y - u.y, u.y), fmaf(scale, c.z - u.z, u.z),
-                                     fmaf(scale, c.w - u.w, u.w));
-        reinterpret_cast<float4*>(out)[i] = r;
-        if constexpr (STATS) {                             // n4 % 16 == 0: the 16 lanes of a block run the same iterations
-            const float2 st = softmax_block_stat(r.x, r.y, r.z, r.w);
-            if ((threadIdx.x & 15) == 0) block_stats[i >> 4] = st;
-        }
-    }
+    guidance_body<STATS>(reinterpret_cast<const float4*>(cond), reinterpret_cast<const float4*>(uncond), reinterpret_cast<float4*>(out),
+                         block_stats, n4, scale, 0);
 }
 
 // guidance_kernel per IMAGE (pmhip_guidance_combine_slots): image b = blockIdx.y combines with guides[b].scale when its slot is
 // active and guides[b].on is set, and is neither read nor written otherwise -- the workgroups of such an image leave at once, so
 // what the cond tower's GEMM left there (logits and statistics) stays the unguided step's input.  The image is a workgroup-level
-// value: the skip is uniform over the workgroup, and the blocks of gridDim.x grid-stride over the image's n4 float4s -- n4 % 16
-// == 0 (V % 64 == 0), so the 16 lanes of a 64-column block run the same iterations and softmax_block_stat's DPP rows are always
-// full.  Element and block arithmetic, and the 16-lanes-per-block layout, are guidance_kernel's: a guided image's rows equal that
-// kernel's on the image alone, bit for bit.  (no __restrict__ on the planes: out aliases cond in the engine)
+// value: the skip is uniform over the workgroup, and the body runs on the image's n4 float4s (n4 % 16 == 0: V % 64 == 0), so a
+// guided image's rows equal guidance_kernel's on the image alone, bit for bit.  (no __restrict__ on the planes: out aliases cond
+// in the engine)
 template <bool STATS>
 __global__ __launch_bounds__(THREADS) void guidance_slots_kernel(const float* cond, const float* uncond,
                                                                  const pmhip_slot_guide* __restrict__ guides,
@@ -222,20 +231,8 @@ __global__ __launch_bounds__(THREADS) void guidance_slots_kernel(const float* co
     const pmhip_slot_guide g = guides[blockIdx.y];
     if ((slots[blockIdx.y].step & PM_SLOT_IDLE) || g.on == 0) return;
     const size_t base = (size_t)blockIdx.y * n4;
-    const float4* c4 = reinterpret_cast<const float4*>(cond) + base;
-    const float4* u4 = reinterpret_cast<const float4*>(uncond) + base;
-    float4* o4 = reinterpret_cast<float4*>(out) + base;
-    const float scale = g.scale;
-    for (size_t i = (size_t)blockIdx.x * THREADS + threadIdx.x; i < n4; i += (size_t)gridDim.x * THREADS) {
-        const float4 c = c4[i], u = u4[i];
-        const float4 r = make_float4(fmaf(scale, c.x - u.x, u.x), fmaf(scale, c.y - u.y, u.y), fmaf(scale, c.z - u.z, u.z),
-                                     fmaf(scale, c.w - u.w, u.w));
-        o4[i] = r;
-        if constexpr (STATS) {
-            const float2 st = softmax_block_stat(r.x, r.y, r.z, r.w);
-            if ((threadIdx.x & 15) == 0) block_stats[(base + i) >> 4] = st;
-        }
-    }
+    guidance_body<STATS>(reinterpret_cast<const float4*>(cond) + base, reinterpret_cast<const float4*>(uncond) + base,
+                         reinterpret_cast<float4*>(out) + base, block_stats, n4, g.scale, base);
 }
 
 inline int grid_for(size_t total) {

@@ -15,9 +15,16 @@
 // arithmetic (common.h softmax_block_stat), so which kernel produced them never shows in the result.
 //
 // remask: per image, the num_mask highest scores get the mask id (generate.py:175-179); bitonic sort
-// of 64-bit (score, reversed index) keys gives the exact (score desc, index asc) order (round 5: the keys stay in registers,
-// remask_reg_kernel; the all-LDS sort is kept behind PMHIP_REMASK_REG=0).
+// of 64-bit (score, reversed index) keys (remask_key) gives the exact (score desc, index asc) order; the keys stay in registers
+// (remask_reg_kernel, round 5; the all-LDS sort of rounds 1-4 is gone).
+//
+// The two sampling kernels differ in how they find the k candidates and in how they round the confidence.  Everything else is ONE
+// piece of device code: where a row's step values come from (row_step: the kernel arguments, the PmGenParams block of a replayed
+// graph, or the pmhip_slot record of the row's image -- common.h PmStepSource), the draw among the candidates (draw_among) and the
+// store of the row's outcome (store_outcome).  The host side has one launcher per kernel family (pm_sample_rows, pm_remask): one
+// copy of the checks, one place that picks the instantiation.
 #include <stdlib.h>
+#include <type_traits>
 
 #include "common.h"
 
@@ -65,6 +72,80 @@ __device__ __forceinline__ float gumbel_from_uniform(float u) {
     return -logf(fmaxf(inner, 1e-20f));
 }
 
+// ---- a row's step values.  Exactly one source (common.h PmStepSource): the kernel arguments as they are; gp != nullptr (graph
+// replay): temperature, seed and row base from the device block, the step indexing it; SLOTS: everything from slots[row / tokens]
+// -- one wave owns a row, so the values are wave-uniform like the kernel arguments they replace.  SLOTS is a compile-time choice:
+// the scalar instantiations gain neither a load nor a branch.  `v` brings the kernel arguments; idle: the slot holds no request.
+struct RowStep { int topk; float temperature; uint64_t seed; uint32_t step; uint64_t row_base; bool idle; };
+
+template <bool SLOTS>
+__device__ __forceinline__ RowStep row_step(RowStep v, int row, const PmGenParams* __restrict__ gp, const pmhip_slot* __restrict__ slots,
+                                            int tokens) {
+    if constexpr (SLOTS) {
+        const int img = __builtin_amdgcn_readfirstlane(row / tokens);
+        const pmhip_slot sl = slots[img];
+        v.step = __builtin_amdgcn_readfirstlane(sl.step);
+        v.idle = (v.step & PM_SLOT_IDLE) != 0;
+        v.topk = __builtin_amdgcn_readfirstlane(sl.topk);
+        v.temperature = sl.temperature;
+        v.seed = sl.seed;
+        // row_base + row = image_index * tokens + position (modulo 2^64, like the sum itself)
+        v.row_base = sl.image_index * (uint64_t)tokens - (uint64_t)img * (uint64_t)tokens;
+    } else if (gp) {
+        v.temperature = gp->temps[v.step];
+        v.seed = gp->seed;
+        v.row_base = gp->row_base;
+    }
+    return v;
+}
+
+// its sibling for the re-masking kernel (one workgroup per image): how many positions image `img` masks; false: an idle slot
+template <bool SLOTS>
+__device__ __forceinline__ bool image_num_mask(int& num_mask, int img, const PmGenParams* __restrict__ gp, int step,
+                                               const pmhip_slot* __restrict__ slots) {
+    if constexpr (SLOTS) {
+        const pmhip_slot sl = slots[img];
+        if (sl.step & PM_SLOT_IDLE) return false;
+        num_mask = sl.num_mask;
+    } else if (gp) num_mask = gp->nmask[step];
+    return true;
+}
+
+// ---- the draw: gumbel arg-max among the k candidates (lane r brings candidate r in `mine`: raw logit and column).  Noise is only
+// needed at the candidates: given, or Philox at (global row, column, step) under the seed.  Every lane returns the sampled column
+// and its RAW logit.
+__device__ __forceinline__ Cand draw_among(Cand mine, int lane, int row, int V, const RowStep& st, const float* __restrict__ noise) {
+    Cand pert{-INFINITY, 0x7fffffff};
+    if (lane < st.topk && mine.i < V) {
+        float u;
+        if (noise) {
+            u = noise[(size_t)row * V + mine.i];
+        } else {
+            const uint64_t grow = st.row_base + (uint64_t)row;
+            const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), (uint32_t)mine.i, st.step),
+                                            make_uint2((uint32_t)st.seed, (uint32_t)(st.seed >> 32)));
+            u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
+        }
+        pert.v = mine.v / fmaxf(st.temperature, 1e-10f) + gumbel_from_uniform(u);
+        pert.i = mine.i;
+    }
+    const Cand win = wave_best(pert);
+    const unsigned long long owner = __ballot(lane < st.topk && mine.i == win.i);
+    const int src = owner ? __ffsll((long long)owner) - 1 : 0;
+    return Cand{__uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mine.v), src)), win.i};   // src is wave-uniform
+}
+
+// ---- the store of a row's outcome, by one lane: the prediction, the id merged into the masked positions, and the score -- 1 - p
+// where the position took the prediction, -1e5 where its id was given.  drawn = false (an idle slot): the row keeps its id.
+__device__ __forceinline__ void store_outcome(int row, bool drawn, int64_t pred, float p, const int64_t* ids_in, int64_t mask_id,
+                                              int64_t* pred_out, int64_t* ids_out, float* score_out) {
+    const int64_t cur = ids_in[row];
+    const bool take = drawn && cur == mask_id;
+    if (pred_out) pred_out[row] = drawn ? pred : cur;
+    ids_out[row] = take ? pred : cur;
+    if (score_out) score_out[row] = take ? (1.0f - p) : -1e5f;
+}
+
 // Row layout in registers: lane l holds float4 group g (g = 0..NV4-1) = columns (g*64 + l)*4 .. +3,
 // so a lane's columns increase with g and groups are disjoint contiguous column ranges: ordering
 // candidates by (value desc, first column of their group asc) equals (value desc, column asc).
@@ -80,11 +161,7 @@ __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
     if (row >= M) return;                                  // whole wave exits together
-    if (gp) {                                              // graph replay: per-call scalars live in device memory
-        temperature = gp->temps[step];
-        seed = gp->seed;
-        row_base = gp->row_base;
-    }
+    const RowStep rs = row_step<false>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, nullptr, 0);
     const int lr = PERIOD ? row % period : row;
     const float* lrow = logits + (size_t)lr * ldl;
 
@@ -137,35 +214,12 @@ __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
         col = __builtin_amdgcn_readlane(col, wl);                         // wl is wave-uniform
         if (lane == r) { mine.v = c.v; mine.i = col; }
     }
-    // ---- gumbel arg-max among the candidates (lane r evaluates candidate r)
-    Cand pert{-INFINITY, 0x7fffffff};
-    if (lane < topk && mine.i < V) {
-        float u;
-        if (noise) {
-            u = noise[(size_t)row * V + mine.i];
-        } else {
-            const uint64_t grow = row_base + (uint64_t)row;
-            const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), (uint32_t)mine.i, step),
-                                            make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-            u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
-        }
-        pert.v = mine.v / fmaxf(temperature, 1e-10f) + gumbel_from_uniform(u);
-        pert.i = mine.i;
-    }
-    const Cand win = wave_best(pert);
-    const unsigned long long owner = __ballot(lane < topk && mine.i == win.i);
-    const int src = owner ? __ffsll((long long)owner) - 1 : 0;
-    const float raw = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mine.v), src));   // src is wave-uniform
-
-    if (lane == 0) {
-        const int64_t pred = win.i;
-        const int64_t cur = ids_in[row];
-        const bool is_mask = (cur == mask_id);
-        const float p = expf(raw - mx) / se;
-        if (pred_out) pred_out[row] = pred;
-        ids_out[row] = is_mask ? pred : cur;
-        if (score_out) score_out[row] = is_mask ? (1.0f - p) : -1e5f;
-    }
+    // ---- the draw, and the confidence of the UNfiltered softmax at the sampled id.  The confidence is each kernel's own: here expf
+    // and a plain division, over a denominator summed in lane order; in sample_tiles_kernel explicitly rounded operations over a
+    // denominator summed block by block, so that the blocks' statistics can come from whoever computed them.  The two differ in
+    // the last bits of the score, which is why the choice of the kernel depends on (V, top-k) only.
+    const Cand win = draw_among(mine, lane, row, V, rs, noise);
+    if (lane == 0) store_outcome(row, true, win.i, expf(win.v - mx) / se, ids_in, mask_id, pred_out, ids_out, score_out);
 }
 
 
@@ -174,9 +228,8 @@ constexpr int KT_MAX = 8;                                  // top-k served by sa
 
 // NB2 = blocks per lane (block b is kept by lane b % 64).  DENSE: no statistics were handed in -- one pass over the stored row
 // computes them (lane l, group g: columns (g*64 + l)*4 .. +3, i.e. block g*4 + l/16 in the layout softmax_block_stat defines).
-// SLOTS (pmhip_sample_rows_slots): the per-call scalars of row r come from slots[r / tokens] -- one wave owns a row, so they are
-// wave-uniform like the kernel arguments they replace -- and everything below the prologue is the code of the scalar form.  The
-// scalar instantiations compile the prologue away: they gain neither a load nor a branch.
+// SLOTS (pmhip_sample_rows_slots): the step values of row r come from slots[r / tokens] (row_step); everything below the prologue
+// is the code of the scalar form.
 // PERIOD: as in sample_rows_kernel -- the logits AND the statistics of row r are those of row r % period.
 template <int NB2, bool DENSE, bool SLOTS = false, bool PERIOD = false>
 __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
@@ -188,29 +241,12 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * (THREADS / 64) + wave;
     if (row >= M) return;                                  // whole wave exits together (no workgroup barrier below)
-    if constexpr (SLOTS) {
-        const int img = __builtin_amdgcn_readfirstlane(row / tokens);
-        const pmhip_slot sl = slots[img];
-        step = __builtin_amdgcn_readfirstlane(sl.step);
-        if (step & PM_SLOT_IDLE) {                         // wave-uniform: nothing is drawn, the row keeps its id
-            if (lane == 0) {
-                const int64_t cur = ids_in[row];
-                if (pred_out) pred_out[row] = cur;
-                ids_out[row] = cur;
-                if (score_out) score_out[row] = -1e5f;
-            }
-            return;
-        }
-        topk = __builtin_amdgcn_readfirstlane(sl.topk);
-        temperature = sl.temperature;
-        seed = sl.seed;
-        // row_base + row below = image_index * tokens + position (modulo 2^64, like the sum itself)
-        row_base = sl.image_index * (uint64_t)tokens - (uint64_t)img * (uint64_t)tokens;
-    } else if (gp) {
-        temperature = gp->temps[step];
-        seed = gp->seed;
-        row_base = gp->row_base;
+    const RowStep rs = row_step<SLOTS>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, slots, tokens);
+    if (SLOTS && rs.idle) {                                // wave-uniform: nothing is drawn, the row keeps its id
+        if (lane == 0) store_outcome(row, false, 0, 0.f, ids_in, mask_id, pred_out, ids_out, score_out);
+        return;
     }
+    topk = rs.topk;
     const int lr = PERIOD ? row % period : row;
     const float* lrow = logits + (size_t)lr * ldl;
     const int nblk = V >> 6;
@@ -301,35 +337,11 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
             if (lane == r) mine = c;
         }
     }
-    // ---- gumbel arg-max among the candidates (lane r evaluates candidate r)
-    Cand pert{-INFINITY, 0x7fffffff};
-    if (lane < topk && mine.i < V) {
-        float u;
-        if (noise) {
-            u = noise[(size_t)row * V + mine.i];
-        } else {
-            const uint64_t grow = row_base + (uint64_t)row;
-            const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), (uint32_t)mine.i, step),
-                                            make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));
-            u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
-        }
-        pert.v = mine.v / fmaxf(temperature, 1e-10f) + gumbel_from_uniform(u);
-        pert.i = mine.i;
-    }
-    const Cand win = wave_best(pert);
-    const unsigned long long owner = __ballot(lane < topk && mine.i == win.i);
-    const int src = owner ? __ffsll((long long)owner) - 1 : 0;
-    const float raw = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(mine.v), src));   // src is wave-uniform
-
-    if (lane == 0) {
-        const int64_t pred = win.i;
-        const int64_t cur = ids_in[row];
-        const bool is_mask = (cur == mask_id);
-        const float p = __fdiv_rn(softmax_exp_below(raw, mx), se);    // raw <= mx and se >= 1 (the maximum's own term): p in [0, 1]
-        if (pred_out) pred_out[row] = pred;
-        ids_out[row] = is_mask ? pred : cur;
-        if (score_out) score_out[row] = is_mask ? (1.0f - p) : -1e5f;
-    }
+    // ---- the draw, and the confidence (this kernel's own rounding: see sample_rows_kernel).  raw <= mx and se >= 1 (the
+    // maximum's own term): p in [0, 1]
+    const Cand win = draw_among(mine, lane, row, V, rs, noise);
+    if (lane == 0)
+        store_outcome(row, true, win.i, __fdiv_rn(softmax_exp_below(win.v, mx), se), ids_in, mask_id, pred_out, ids_out, score_out);
 }
 
 __device__ __forceinline__ uint32_t orderable(float f) {
@@ -337,44 +349,15 @@ __device__ __forceinline__ uint32_t orderable(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ __launch_bounds__(THREADS) void remask_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
-                                                         int num_mask, int64_t mask_id, int N, int Npow2,
-                                                         const PmGenParams* __restrict__ gp, int step) {
-    if (gp) num_mask = gp->nmask[step];
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* key = reinterpret_cast<unsigned long long*>(smem);
-    const int b = blockIdx.x;
-    const float* sc = scores + (size_t)b * N;
-    for (int i = threadIdx.x; i < Npow2; i += THREADS)
-        key[i] = i < N ? (((unsigned long long)orderable(sc[i]) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i)) : 0ull;
-    __syncthreads();
-    // bitonic sort, descending
-    for (int k = 2; k <= Npow2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < Npow2; i += THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const unsigned long long a = key[i], c = key[ixj];
-                    const bool desc = ((i & k) == 0);
-                    if (desc ? (a < c) : (a > c)) { key[i] = c; key[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    const int nm = num_mask < 1 ? 1 : (num_mask > N ? N : num_mask);
-    const unsigned long long thr = key[nm - 1];
-    for (int i = threadIdx.x; i < N; i += THREADS) {
-        const unsigned long long k = ((unsigned long long)orderable(sc[i]) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i);
-        if (k >= thr) ids[(size_t)b * N + i] = mask_id;
-    }
+// the sort key: (score desc, index asc) as one descending 64-bit order
+__device__ __forceinline__ unsigned long long remask_key(float score, int i) {
+    return ((unsigned long long)orderable(score) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i);
 }
 
-
-// Round 5: the same selection with the sort in registers.  Thread t keeps the E consecutive elements t*E .. t*E+E-1; a bitonic
+// The selection with the sort in registers (round 5).  Thread t keeps the E consecutive elements t*E .. t*E+E-1; a bitonic
 // compare-exchange with distance j is in-thread for j < E, a wave shuffle for j < 64*E and goes through LDS (two barriers) only
-// beyond that: 3 of the 55 stages at N = 1024 (the all-LDS kernel above: one barrier per stage, 40 us per launch on B <= 64
-// workgroups -- latency, not work).  Same keys, same total order, same threshold test.
+// beyond that: 3 of the 55 stages at N = 1024 (the all-LDS sort of rounds 1-4 had one barrier per stage, 40 us per launch on B <= 64
+// workgroups -- latency, not work).
 // SLOTS (pmhip_remask_slots): num_mask = slots[image].num_mask; the workgroup of an idle slot leaves (before any barrier).
 template <int E, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
@@ -382,18 +365,14 @@ __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict
                                                              int step, const pmhip_slot* __restrict__ slots) {
     constexpr int NP = THREADS * E;
     __shared__ unsigned long long xs[NP];
-    if constexpr (SLOTS) {
-        const pmhip_slot sl = slots[blockIdx.x];
-        if (sl.step & PM_SLOT_IDLE) return;
-        num_mask = sl.num_mask;
-    } else if (gp) num_mask = gp->nmask[step];
+    if (!image_num_mask<SLOTS>(num_mask, blockIdx.x, gp, step, slots)) return;
     const int tid = threadIdx.x, base = tid * E;
     const float* sc = scores + (size_t)blockIdx.x * N;
     unsigned long long key[E], mine[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const int i = base + e;
-        key[e] = i < N ? (((unsigned long long)orderable(sc[i]) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i)) : 0ull;
+        key[e] = i < N ? remask_key(sc[i], i) : 0ull;
         mine[e] = key[e];
     }
 #pragma unroll
@@ -444,56 +423,54 @@ __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict
         if (base + e < N && mine[e] >= thr) ids[(size_t)blockIdx.x * N + base + e] = mask_id;
 }
 
+// a run-time size class or flag as a compile-time constant: f(std::integral_constant<int, V>) for the one V of Vs that equals v
+template <int... Vs, typename F>
+void pick(int v, F&& f) {
+    ((v == Vs ? f(std::integral_constant<int, Vs>{}) : (void)0), ...);
+}
+
 }  // namespace
 
-int pm_sample_rows(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id, int topk,
-                   float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base, int64_t* pred_out,
-                   int64_t* ids_out, float* score_out, int M, int V, const PmGenParams* gp, int period, pmhip_stream stream) {
-    PM_REQUIRE(logits && ids_in && ids_out, "sample_rows: null pointer");
-    PM_REQUIRE(period >= 0, "sample_rows: negative logits row period %d", period);
-    PM_REQUIRE(M > 0 && V > 0 && V % 4 == 0 && ldl % 4 == 0 && ldl >= V, "sample_rows: bad shape M=%d V=%d ldl=%d", M, V, ldl);
-    PM_REQUIRE(topk >= 1 && topk <= 64 && topk <= V, "sample_rows: topk=%d must be in [1, min(64,V)]", topk);
-    PM_REQUIRE(V <= 16384, "sample_rows: V=%d > 16384 unsupported", V);
+int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int period, const int64_t* ids_in, int64_t mask_id,
+                   const float* noise, int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, const PmStepSource& src,
+                   pmhip_stream stream) {
+    const bool slots = src.kind == PmStepSource::SLOTS;
+    const char* who = slots ? "sample_rows_slots" : "sample_rows";
+    PM_REQUIRE(logits && ids_in && ids_out && (!slots || src.slots) && (src.kind != PmStepSource::PARAMS || src.gp), "%s: null pointer", who);
+    PM_REQUIRE(period >= 0 && !(slots && period), "%s: bad logits row period %d", who, period);
+    PM_REQUIRE(M > 0 && V > 0 && V % 4 == 0 && ldl % 4 == 0 && ldl >= V, "%s: bad shape M=%d V=%d ldl=%d", who, M, V, ldl);
+    if (slots) {                                           // the block-statistics kernel only: what every decode-loop launch runs
+        PM_REQUIRE(V % 64 == 0 && V <= 16384, "sample_rows_slots: V=%d must be a multiple of 64, at most 16384", V);
+        PM_REQUIRE(src.tokens > 0 && M % src.tokens == 0, "sample_rows_slots: M=%d is not a whole number of images of %d tokens", M, src.tokens);
+    } else {
+        PM_REQUIRE(src.topk >= 1 && src.topk <= 64 && src.topk <= V, "sample_rows: topk=%d must be in [1, min(64,V)]", src.topk);
+        PM_REQUIRE(V <= 16384, "sample_rows: V=%d > 16384 unsupported", V);
+    }
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(ceil_div(M, THREADS / 64)), block(THREADS);
     PmTimer tm(FAM_SAMPLE, s);
     // Which kernel runs depends on (V, topk) ONLY -- never on whether statistics were handed in: the two differ in the last bits
-    // of the confidence (a different summation order of the softmax denominator).
+    // of the confidence (sample_rows_kernel).  The records of a slots launch carry top-k <= 8 (checked where they are staged).
     static const int g_tiles = pm_dev_knob("PMHIP_SAMPLE_TILES", 1);     // 0: the one-read row kernel everywhere (A/B)
-    if (g_tiles && topk <= KT_MAX && V % 64 == 0) {
+    if (slots || (g_tiles && src.topk <= KT_MAX && V % 64 == 0)) {
         const float2* st = reinterpret_cast<const float2*>(block_stats);
-#define PM_TILES_AS(NB2, DENSE, PER)                                                                                         \
-    hipLaunchKernelGGL((sample_tiles_kernel<NB2, DENSE, false, PER>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, topk, \
-                       temperature, noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, nullptr, 0, period)
-#define PM_TILES(NB2)                                                                                                         \
-    do {                                                                                                                      \
-        if (st && period) PM_TILES_AS(NB2, false, true);                                                                      \
-        else if (st) PM_TILES_AS(NB2, false, false);                                                                          \
-        else if (period) PM_TILES_AS(NB2, true, true);                                                                        \
-        else PM_TILES_AS(NB2, true, false);                                                                                   \
-    } while (0)
-        if (V <= 4096) PM_TILES(1);
-        else if (V <= 8192) PM_TILES(2);
-        else PM_TILES(4);
-#undef PM_TILES
-#undef PM_TILES_AS
-        PM_HIP(hipGetLastError());
-        return PMHIP_OK;
+        pick<1, 2, 4>(V <= 4096 ? 1 : V <= 8192 ? 2 : 4, [&](auto NB2) {
+            pick<0, 1>(st == nullptr, [&](auto DENSE) {
+                pick<0, 1, 2>(slots ? 2 : period ? 1 : 0, [&](auto FORM) {      // scalar, period or slots: never two of them
+                    hipLaunchKernelGGL((sample_tiles_kernel<NB2(), DENSE() == 1, FORM() == 2, FORM() == 1>), grid, block, 0, s, logits, ldl, st,
+                                       ids_in, mask_id, src.topk, src.temperature, noise, src.seed, src.step, src.row_base, pred_out, ids_out,
+                                       score_out, M, V, src.gp, src.slots, src.tokens, period);
+                });
+            });
+        });
+    } else {
+        pick<1, 4, 32, 64>(V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64, [&](auto NV4) {
+            pick<0, 1>(period != 0, [&](auto PER) {
+                hipLaunchKernelGGL((sample_rows_kernel<NV4(), PER() == 1>), grid, block, 0, s, logits, ldl, ids_in, mask_id, src.topk,
+                                   src.temperature, noise, src.seed, src.step, src.row_base, pred_out, ids_out, score_out, M, V, src.gp, period);
+            });
+        });
     }
-#define PM_SAMPLE_AS(NV4, PER)                                                                                           \
-    hipLaunchKernelGGL((sample_rows_kernel<NV4, PER>), grid, block, 0, s, logits, ldl, ids_in, mask_id, topk, temperature, \
-                       noise, seed, step, row_base, pred_out, ids_out, score_out, M, V, gp, period)
-#define PM_SAMPLE(NV4)                    \
-    do {                                  \
-        if (period) PM_SAMPLE_AS(NV4, true); \
-        else PM_SAMPLE_AS(NV4, false);    \
-    } while (0)
-    if (V <= 256) PM_SAMPLE(1);
-    else if (V <= 1024) PM_SAMPLE(4);
-    else if (V <= 8192) PM_SAMPLE(32);
-    else PM_SAMPLE(64);
-#undef PM_SAMPLE
-#undef PM_SAMPLE_AS
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
 }
@@ -502,8 +479,8 @@ extern "C" int pmhip_sample_rows(const float* logits, int ldl, const int64_t* id
                                  float temperature, const float* noise, uint64_t seed, uint32_t step,
                                  uint64_t row_base, int64_t* pred_out, int64_t* ids_out, float* score_out, int M,
                                  int V, pmhip_stream stream) {
-    return pm_sample_rows(logits, ldl, nullptr, ids_in, mask_id, topk, temperature, noise, seed, step, row_base, pred_out, ids_out,
-                          score_out, M, V, nullptr, 0, stream);
+    return pm_sample_rows(logits, ldl, nullptr, 0, ids_in, mask_id, noise, pred_out, ids_out, score_out, M, V,
+                          PmStepSource::batch(topk, temperature, 0, seed, step, row_base), stream);
 }
 
 // the same step with the block statistics pmhip_gemm_softmax_stats (or pmhip_guidance_combine_stats) left behind: [M][V/64][2]
@@ -513,88 +490,43 @@ extern "C" int pmhip_sample_rows_stats(const float* logits, int ldl, const float
                                        pmhip_stream stream) {
     PM_REQUIRE(block_stats, "sample_rows_stats: null statistics");
     PM_REQUIRE(V % 64 == 0, "sample_rows_stats: V=%d must be a multiple of 64", V);
-    return pm_sample_rows(logits, ldl, block_stats, ids_in, mask_id, topk, temperature, noise, seed, step, row_base, pred_out, ids_out,
-                          score_out, M, V, nullptr, 0, stream);
+    return pm_sample_rows(logits, ldl, block_stats, 0, ids_in, mask_id, noise, pred_out, ids_out, score_out, M, V,
+                          PmStepSource::batch(topk, temperature, 0, seed, step, row_base), stream);
 }
 
-// the per-image form: the block-statistics kernel only (what every decode-loop launch runs), every scalar from slots[row / tokens]
-int pm_sample_rows_slots(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
-                         const pmhip_slot* slots, int tokens, int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V,
-                         pmhip_stream stream) {
-    PM_REQUIRE(logits && ids_in && ids_out && slots, "sample_rows_slots: null pointer");
-    PM_REQUIRE(M > 0 && V > 0 && ldl % 4 == 0 && ldl >= V, "sample_rows_slots: bad shape M=%d V=%d ldl=%d", M, V, ldl);
-    PM_REQUIRE(V % 64 == 0 && V <= 16384, "sample_rows_slots: V=%d must be a multiple of 64, at most 16384", V);
-    PM_REQUIRE(tokens > 0 && M % tokens == 0, "sample_rows_slots: M=%d is not a whole number of images of %d tokens", M, tokens);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid(ceil_div(M, THREADS / 64)), block(THREADS);
-    PmTimer tm(FAM_SAMPLE, s);
-    const float2* st = reinterpret_cast<const float2*>(block_stats);
-#define PM_TILES(NB2)                                                                                                          \
-    do {                                                                                                                       \
-        if (st) hipLaunchKernelGGL((sample_tiles_kernel<NB2, false, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, 0, 0.f, \
-                                   nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens, 0);              \
-        else hipLaunchKernelGGL((sample_tiles_kernel<NB2, true, true>), grid, block, 0, s, logits, ldl, st, ids_in, mask_id, 0, 0.f, \
-                                nullptr, 0, 0, 0, pred_out, ids_out, score_out, M, V, nullptr, slots, tokens, 0);                 \
-    } while (0)
-    if (V <= 4096) PM_TILES(1);
-    else if (V <= 8192) PM_TILES(2);
-    else PM_TILES(4);
-#undef PM_TILES
-    PM_HIP(hipGetLastError());
-    return PMHIP_OK;
-}
-
+// the per-image form: every step value from slots[row / tokens]
 extern "C" int pmhip_sample_rows_slots(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
                                        const pmhip_slot* slots, int tokens, int64_t* pred_out, int64_t* ids_out, float* score_out,
                                        int M, int V, pmhip_stream stream) {
-    return pm_sample_rows_slots(logits, ldl, block_stats, ids_in, mask_id, slots, tokens, pred_out, ids_out, score_out, M, V, stream);
+    return pm_sample_rows(logits, ldl, block_stats, 0, ids_in, mask_id, nullptr, pred_out, ids_out, score_out, M, V,
+                          PmStepSource::per_image(slots, tokens), stream);
 }
 
-int pm_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N, const PmGenParams* gp, int step,
-              pmhip_stream stream) {
-    PM_REQUIRE(ids && scores, "remask: null pointer");
-    PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "remask: bad shape B=%d N=%d (N <= 4096)", B, N);
-    int np2 = 1;
-    while (np2 < N) np2 <<= 1;
+int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, const PmStepSource& src, pmhip_stream stream) {
+    const bool slots = src.kind == PmStepSource::SLOTS;
+    const char* who = slots ? "remask_slots" : "remask";
+    PM_REQUIRE(ids && scores && (!slots || src.slots) && (src.kind != PmStepSource::PARAMS || src.gp), "%s: null pointer", who);
+    PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "%s: bad shape B=%d N=%d (N <= 4096)", who, B, N);
+    int per_thread = 1;                                    // E: the power of two with THREADS * E >= N
+    while (THREADS * per_thread < N) per_thread <<= 1;
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_SAMPLE, s);
-    static const int g_reg = pm_dev_knob("PMHIP_REMASK_REG", 1);      // 0: the all-LDS sort (A/B)
-#define PM_REMASK(E) hipLaunchKernelGGL(remask_reg_kernel<E>, dim3(B), dim3(THREADS), 0, s, ids, scores, num_mask, mask_id, N, gp, step, nullptr)
-    if (!g_reg) hipLaunchKernelGGL(remask_kernel, dim3(B), dim3(THREADS), (size_t)np2 * 8, s, ids, scores, num_mask, mask_id, N, np2, gp, step);
-    else if (np2 <= 256) PM_REMASK(1);
-    else if (np2 <= 512) PM_REMASK(2);
-    else if (np2 <= 1024) PM_REMASK(4);
-    else if (np2 <= 2048) PM_REMASK(8);
-    else PM_REMASK(16);
-#undef PM_REMASK
+    pick<1, 2, 4, 8, 16>(per_thread, [&](auto E) {
+        pick<0, 1>(slots, [&](auto SLOTS) {
+            hipLaunchKernelGGL((remask_reg_kernel<E(), SLOTS() == 1>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.num_mask, mask_id, N,
+                               src.gp, (int)src.step, src.slots);
+        });
+    });
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
 }
 
 extern "C" int pmhip_remask(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N,
                             pmhip_stream stream) {
-    return pm_remask(ids, scores, num_mask, mask_id, B, N, nullptr, 0, stream);
-}
-
-int pm_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id, int B, int N, pmhip_stream stream) {
-    PM_REQUIRE(ids && scores && slots, "remask_slots: null pointer");
-    PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "remask_slots: bad shape B=%d N=%d (N <= 4096)", B, N);
-    int np2 = 1;
-    while (np2 < N) np2 <<= 1;
-    hipStream_t s = (hipStream_t)stream;
-    PmTimer tm(FAM_SAMPLE, s);
-#define PM_REMASK(E) hipLaunchKernelGGL((remask_reg_kernel<E, true>), dim3(B), dim3(THREADS), 0, s, ids, scores, 0, mask_id, N, nullptr, 0, slots)
-    if (np2 <= 256) PM_REMASK(1);
-    else if (np2 <= 512) PM_REMASK(2);
-    else if (np2 <= 1024) PM_REMASK(4);
-    else if (np2 <= 2048) PM_REMASK(8);
-    else PM_REMASK(16);
-#undef PM_REMASK
-    PM_HIP(hipGetLastError());
-    return PMHIP_OK;
+    return pm_remask(ids, scores, mask_id, B, N, PmStepSource::batch(0, 0.f, num_mask, 0, 0, 0), stream);
 }
 
 extern "C" int pmhip_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id, int B, int N,
                                   pmhip_stream stream) {
-    return pm_remask_slots(ids, scores, slots, mask_id, B, N, stream);
+    return pm_remask(ids, scores, mask_id, B, N, PmStepSource::per_image(slots, N), stream);
 }

@@ -1,0 +1,158 @@
+"""Bit digest of the decode tail: sampling, re-masking, guidance combination and the tiny pipeline's decode loops.
+
+  python tools/decode_tail_digest.py --root <built checkout> [--out file.jsonl]
+
+One JSON line per case with a sha256 of every output tensor; inputs come from fixed numpy seeds.  The tests compare scores with a
+tolerance; this is for "bit for bit what another commit computes": run it on two built checkouts on one box and diff the files
+(profiles/decode_tail_digest_*.jsonl).  Only the public Python surface (ops, Pipeline) is used, so any commit that has decode
+sessions with per-request guidance can be the other side.
+"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="checkout whose paintmind_amd is run")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    sys.path.insert(0, a.root)
+    sys.path.insert(0, os.path.join(a.root, "tests"))
+    import numpy as np
+    import torch
+    import paintmind_amd as pm
+    from paintmind_amd import ops
+    from paintmind_amd.generate import Pipeline
+    from util import load_golden, to_torch_sd
+
+    assert torch.cuda.is_available(), "decode_tail_digest needs a ROCm device"
+    print("library under test:", pm.__file__, file=sys.stderr)
+    dev = torch.device("cuda:0")
+    out = open(a.out, "w") if a.out else None
+
+    def sha(x):
+        return hashlib.sha256(np.ascontiguousarray(x.detach().cpu().numpy()).tobytes()).hexdigest()
+
+    def emit(case, **tensors):
+        line = json.dumps({"case": case, **{k: sha(v) for k, v in tensors.items()}})
+        print(line)
+        if out:
+            out.write(line + "\n")
+
+    def t(x):
+        return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+    def logits_of(rng, M, V, quantised):
+        x = (rng.standard_normal((M, V)) * 2.0).astype(np.float32)
+        return np.round(x * 2) / 2 if quantised else x             # half-integers: many ties
+
+    def ids_of(rng, M, V):
+        ids = rng.integers(0, V, M).astype(np.int64)
+        ids[rng.random(M) < 0.6] = V
+        return ids
+
+    def stats_of(x):
+        return ops.guidance_combine(x, x, 1.0, with_stats=True)[1]
+
+    # ---- sample_rows: M = 37 (a partly empty last workgroup), one block / ragged V / the NB2 = 1, 2, 4 boundaries
+    M, seed, base, number = 37, 0xFEDCBA9876543210, 2 ** 40 + 12345, 0
+    for V in (64, 1000, 4160, 8192, 8256):
+        rng = np.random.default_rng(V)
+        planes = [t(logits_of(rng, M, V, q)) for q in (False, True)]
+        stats = [stats_of(x) if V % 64 == 0 else None for x in planes]
+        ids, noise = t(ids_of(rng, M, V)), t(rng.random((M, V)).astype(np.float32))
+        for topk in (1, 5, 8, 9, min(64, V)):
+            for temp in (0.0, 0.7):
+                q = number % 2
+                number += 1
+                x = planes[q]
+                for name, st in (("dense", None), ("stats", stats[q])):
+                    if name == "stats" and st is None:
+                        continue
+                    pred, merged, score = ops.sample_rows(x, ids, V, topk, temp, seed=seed, step=5, row_base=base, block_stats=st)
+                    emit(f"sample_rows V={V} k={topk} T={temp} ties={q} philox {name}", pred=pred, ids=merged, score=score)
+                    if temp:
+                        pred, merged, score = ops.sample_rows(x, ids, V, topk, temp, noise=noise, block_stats=st)
+                        emit(f"sample_rows V={V} k={topk} T={temp} ties={q} noise {name}", pred=pred, ids=merged, score=score)
+
+    # ---- the slots forms: the record set of tests/test_gpu_slots.py::_operator_slots at N = 16
+    N = 16
+    recs = [(0x0123456789ABCDEF, 7, 0.0, 1, 1, 0), (77, 2 ** 33 + 5, 0.8, 8, N, 3), None,
+            (0xFEDCBA9876543210, 4096, 1.3, 5, max(N // 2, 1), 17), (5, 1, 0.5, 3, 3, 1)]
+    for V in (64, 8192):
+        rng = np.random.default_rng(1000 * V + N)
+        x, ids = t(logits_of(rng, 5 * N, V, False)), t(ids_of(rng, 5 * N, V))
+        slots = ops.pack_slots(recs, dev)
+        for name, st in (("dense", None), ("stats", stats_of(x))):
+            pred, merged, score = ops.sample_rows_slots(x, ids, V, slots, N, block_stats=st)
+            emit(f"sample_rows_slots V={V} {name}", pred=pred, ids=merged, score=score)
+        emit(f"remask_slots V={V}", ids=ops.remask_slots(merged.reshape(5, N).clone(), score.reshape(5, N), slots, V))
+
+    # ---- remask: every elements-per-thread class, tied scores
+    for N in (16, 100, 300, 1024, 2048, 4096):
+        rng = np.random.default_rng(N)
+        scores = t((rng.integers(0, 8, (3, N)) / 8.0).astype(np.float32))
+        ids = t(rng.integers(0, 64, (3, N)).astype(np.int64))
+        for nm in (1, N // 2, N):
+            emit(f"remask N={N} num_mask={nm}", ids=ops.remask(ids.clone(), scores, nm, 64))
+
+    # ---- guidance: flat (with and without statistics, in place and not) and per image (guided, unguided, idle)
+    rng = np.random.default_rng(7)
+    tokens, V = 16, 192
+    cond, unc = t(rng.standard_normal((3 * tokens, V)).astype(np.float32)), t(rng.standard_normal((3 * tokens, V)).astype(np.float32))
+    emit("guidance_combine", out=ops.guidance_combine(cond, unc, 2.5))
+    c2 = cond.clone()
+    emit("guidance_combine into cond", out=ops.guidance_combine(c2, unc, 2.5, out=c2))
+    o, st = ops.guidance_combine(cond, unc, 2.5, with_stats=True)
+    emit("guidance_combine stats", out=o, stats=st)
+    c2 = cond.clone()
+    o, st = ops.guidance_combine(c2, unc, 2.5, out=c2, with_stats=True)
+    emit("guidance_combine stats into cond", out=o, stats=st)
+    slots = ops.pack_slots([(1, 0, 1.0, 5, 1, 0), (2, 1, 1.0, 5, 1, 0), None], dev)
+    guides = ops.pack_slot_guides([1.75, None, 3.0], dev)
+    emit("guidance_combine_slots", out=ops.guidance_combine_slots(cond, unc, guides, slots, tokens, out=torch.zeros_like(cond)))
+    c2, st = cond.clone(), torch.zeros(3 * tokens, V // 64, 2, device=dev)
+    o, st = ops.guidance_combine_slots(c2, unc, guides, slots, tokens, out=c2, block_stats=st)
+    emit("guidance_combine_slots stats into cond", out=o, stats=st)
+
+    # ---- the tiny pipeline of tests/test_gpu_step0.py::make_tiny: final ids and images of its loops
+    p, _ = load_golden("tiny_pipeline.npz")
+    pipe = Pipeline(pm.Config(pm.ver2cfg["tiny-pipeline"]), stage1_pretrained=False)
+    pipe.load_state_dict(to_torch_sd(p), strict=False)
+    pipe = pipe.to(dev).eval()
+    B, T, flags = 3, 4, [False, True, False, True]
+    rng = np.random.default_rng(11)
+    Nt, mask = pipe.num_tokens, pipe.mask_token_id
+    ctx = t(rng.standard_normal((4, 5, pipe.engine().context_dim)).astype(np.float32))
+    start = rng.integers(0, mask, (B, Nt)).astype(np.int64)
+    start[rng.random((B, Nt)) < 0.7] = mask
+    for dtype in (torch.float32, torch.bfloat16):
+        pipe.set_compute_dtype(dtype)
+        pipe.invalidate_engines()
+        tag = "fp32" if dtype == torch.float32 else "bf16"
+        for topk in (3, 16):
+            for src, ids0 in (("mask", None), ("ids", t(start))):
+                for guided, kw in (("", {}), (" guided", {"guidance_scale": 2.0})):
+                    context = ctx[:B].contiguous() if guided else None
+                    for graph, calls in ((False, 1), (True, 3)):            # graph: the eager warm pass, the capture, one replay
+                        for call in range(calls):
+                            ids, imgs = pipe.generate_ids(context, B, T, 0.9, topk, flags, seed=1234, image_base=2 ** 33, use_graph=graph,
+                                                          streams=1, ids0=None if ids0 is None else ids0.clone(), **kw)
+                            emit(f"generate_ids {tag} k={topk} from={src}{guided} graph={int(graph)} call={call}", ids=ids, imgs=imgs)
+        # a decode session of four requests, two of them guided
+        for graph in (False, True):
+            s = pipe.decode_session(slots=4, conditional=True, use_graph=graph)
+            for i, (steps, temp, topk, scale) in enumerate([(3, 1.0, 5, 2.0), (4, 0.7, 3, None), (2, 1.3, 8, 1.5), (4, 0.0, 1, None)]):
+                s.submit(context=ctx[i], timesteps=steps, temperature=temp, topk=topk, seed=100 + i, image_index=2 ** 33 + i, guidance_scale=scale)
+            for f in sorted(s.drain(), key=lambda f: f.handle.number):
+                emit(f"session {tag} graph={int(graph)} request={f.handle.number}", ids=f.ids, image=f.image)
+    pipe.set_compute_dtype(torch.float32)
+    if out:
+        out.close()
+
+
+if __name__ == "__main__":
+    main()
