@@ -35,7 +35,7 @@
  *         pmhip_gemm_hilo / _stats / _center   out_hi == res_hi and out_lo == res_lo with ldo == ldr, the residual being the
  *                                              stream itself (res_rows <= 0 or >= M: no row modulo)
  *         pmhip_gemm with an f32 residual      out == residual with ldo == ldr, res_rows covering all M rows
- *         pmhip_unshift_hilo, pmhip_remask(_slots), pmhip_guidance_combine(_stats), pmhip_sample_rows* (ids_out == ids_in)
+ *         pmhip_unshift_hilo, pmhip_remask(_slots), pmhip_remask_choice(_slots), pmhip_guidance_combine(_stats), pmhip_sample_rows* (ids_out == ids_in)
  *         pmhip_guidance_combine_slots         out == cond (or uncond)
  *     Every element is read by the workgroup that writes it, before it writes it; the result equals the out-of-place call's bit
  *     for bit.  Any other overlap between an output and an input is undefined.
@@ -345,6 +345,29 @@ int pmhip_sample_rows_slots(const float* logits, int ldl, const float* block_sta
 int pmhip_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id,
                        int B, int N, pmhip_stream stream);
 
+/* CHOICE TEMPERATURE (new entries within ABI 11): MaskGIT's perturbed re-masking.  pmhip_remask with the
+ * key of image b, position i, score s = scores[b,i] replaced by, each line one fp32 operation, round to nearest:
+ *   choice_t == 0:  s                           (pmhip_remask, bit for bit)
+ *   s < 0:          s                           (a given id, score -1e5: no noise is drawn; given ids sort below every taken one
+ *                                                and are re-masked only when num_mask exceeds the taken positions, in index order)
+ *   otherwise:      ph = 1 - s;  conf = logf(fmaxf(ph, 2^-24));  g = -log(-log(u)) with both logs clamped at 1e-20 (the token
+ *                   draw's gumbel);  key = -fmaf(choice_t, g, conf)
+ * Order (key desc, index asc), threshold element num_mask - 1, every position at or above it masked: as pmhip_remask.
+ * u: noise[b*N + i] (fp32 uniform(0,1), the parity hook) or, noise == NULL, Philox4x32-10 under `seed` at the counter
+ * (grow_lo, grow_hi, 0xFFFFFFFF, step), grow = row_base + b*N + i, u = (x >> 8) * 2^-24.  No class column is 0xFFFFFFFF
+ * (V <= 16384): the stream is disjoint from pmhip_sample_rows' under the same seed, step and rows.
+ * choice_t is the STEP's value (a loop over T steps uses choice_temperature * (1 - (step+1)/T), 0 on the last step): finite,
+ * 0 <= choice_t <= 1000 (every noisy key then stays above -1e5), else PMHIP_EINVAL before anything is launched. */
+int pmhip_remask_choice(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N, float choice_t,
+                        const float* noise /* [B,N] or NULL */, uint64_t seed, uint32_t step, uint64_t row_base,
+                        pmhip_stream stream);
+/* The per-image form: num_mask, seed, step and image_index (grow = image_index * N + i) from slots[b], choice_t from
+ * choice_t_dev[b], a DEVICE float [B] parallel to the slot records (pmhip_slot stays 32 bytes).  Image b equals
+ * pmhip_remask_choice on its row alone with these values and row_base = image_index * N; an image with choice 0 takes the
+ * plain key; the row of an idle slot is left untouched.  Philox noise only. */
+int pmhip_remask_choice_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, const float* choice_t_dev,
+                              int64_t mask_id, int B, int N, pmhip_stream stream);
+
 /* Per-image GUIDANCE: a record parallel to pmhip_slot, which stays 32 bytes; the ABI version stays 11 (new entries only). */
 typedef struct pmhip_slot_guide { float scale; uint32_t on; } pmhip_slot_guide;   /* 8 bytes, one per image; on = 0: not guided */
 
@@ -595,6 +618,33 @@ int pmhip_pipeline_step_slots_lens(pmhip_s2* s2, int64_t* ids, const float* cont
                                    const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
                                    const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out,
                                    pmhip_stream stream);
+
+/* CHOICE TEMPERATURE at the model level (new entries within ABI 11): the *_lens entries with the re-masking launch replaced by
+ * its choice form (pmhip_remask_choice above); nothing else of the step changes, so it composes with guidance, context lengths,
+ * lanes, PMHIP_GENERATE_FROM_MASK and PMHIP_SLOTS_KEEP_CONTEXT.  A NULL or all-zero choice argument runs exactly the *_lens
+ * entry: the same kernels and the same captured graphs.  Values are validated before anything is launched (finite, in [0, 1000]).
+ *   - pmhip_pipeline_sample_choice: choice_t is this step's value; choice_noise [B,N] (or NULL: Philox under seed / step /
+ *     image_base, column word 0xFFFFFFFF) the uniforms of the re-masking keys
+ *   - pmhip_pipeline_generate_choice: ctemps_host [T], one value per step.  With the graph flag the loop is captured under a key of
+ *     its own and its re-masking launches read the values from the device parameter block: one graph serves every schedule
+ *   - pmhip_pipeline_step_slots_choice: choice_host [B], one value per slot (idle slots are not looked at).  The values travel in the
+ *     ring entry of the slot and guide records to a handle-owned device array; a step with a non-zero value has a graph key of
+ *     its own, and one graph serves every mix of values */
+int pmhip_pipeline_sample_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                 const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                 uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                 float* score_out, int guided, float guidance_scale, float choice_t,
+                                 const float* choice_noise /* [B,N] or NULL */, pmhip_stream stream);
+int pmhip_pipeline_generate_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                   const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                   const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                   float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                   pmhip_stream copy_stream, int guided, float guidance_scale,
+                                   const float* ctemps_host /* [T] or NULL */);
+int pmhip_pipeline_step_slots_choice(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                     const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
+                                     const pmhip_slot_guide* guides_host, const float* choice_host /* [B] or NULL */, int flags,
+                                     int64_t* pred_out, float* score_out, pmhip_stream stream);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

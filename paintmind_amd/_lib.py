@@ -17,6 +17,7 @@ ABI_VERSION = 11
 GENERATE_GRAPH, GENERATE_CONCURRENT_LANES, GENERATE_FROM_MASK = 1, 2, 4
 SLOTS_GRAPH, SLOTS_KEEP_CONTEXT = 1, 2
 SLOT_IDLE = 0x80000000             # bit 31 of Slot.step
+CHOICE_T_MAX = 1000.0              # largest choice temperature of a step (include/pmhip.h, pmhip_remask_choice)
 
 vp = C.c_void_p
 i32 = C.c_int
@@ -151,6 +152,14 @@ PROTOTYPES = {
     "pmhip_pipeline_generate_lens": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
                                            C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32]),
     "pmhip_pipeline_step_slots_lens": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), i32, vp, vp, vp]),
+    "pmhip_remask_choice": (i32, [vp, vp, i32, i64, i32, i32, f32, vp, u64, u32, u64, vp]),
+    "pmhip_remask_choice_slots": (i32, [vp, vp, vp, vp, i64, i32, i32, vp]),
+    "pmhip_pipeline_sample_choice": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, i32, f32,
+                                           f32, vp, vp]),
+    "pmhip_pipeline_generate_choice": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
+                                             C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32)]),
+    "pmhip_pipeline_step_slots_choice": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
+                                               i32, vp, vp, vp]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),

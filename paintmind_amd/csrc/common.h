@@ -1,6 +1,7 @@
 // Shared device/host helpers for libpaintmind_hip.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
@@ -71,7 +72,9 @@ struct PmGenParams {
     unsigned long long row_base;
     float temps[PM_MAX_STEPS];
     int nmask[PM_MAX_STEPS];
+    float ctemps[PM_MAX_STEPS];     // choice temperatures (the choice form of the re-masking kernel); appended: nothing above moves
 };
+static_assert(offsetof(PmGenParams, ctemps) == 16 + 8 * PM_MAX_STEPS, "PmGenParams: the fields in front of ctemps keep their offsets");
 
 // ---------------------------------------------------------------------------------------------
 // per-IMAGE decode state (include/pmhip.h, pmhip_slot): device memory, one record per image of the batch.  The slots forms of the
@@ -97,7 +100,18 @@ struct PmStepSource {
     }
     static PmStepSource params(const PmGenParams* gp, int topk, uint32_t step) { return {PARAMS, topk, 0.f, 0, 0, step, 0, gp, nullptr, 0}; }
     static PmStepSource per_image(const pmhip_slot* slots, int tokens) { return {SLOTS, 0, 0.f, 0, 0, 0, 0, nullptr, slots, tokens}; }
+    // The choice temperature of the re-masking step (pm_remask only), by the same three sources: BATCH the
+    // scalar choice_t with optional given uniforms [B,N]; PARAMS gp->ctemps[step]; SLOTS the device array choice_dev [B].  Off
+    // (the default): the plain re-masking kernel, as before.
+    float choice_t = 0.f; const float* choice_noise = nullptr; const float* choice_dev = nullptr; bool choice_params = false;
+    bool choice_on() const { return kind == BATCH ? (choice_t != 0.f || choice_noise) : kind == PARAMS ? choice_params : choice_dev != nullptr; }
+    PmStepSource with_choice(float t, const float* noise) const { PmStepSource r = *this; r.choice_t = t; r.choice_noise = noise; return r; }
+    PmStepSource with_choice_params() const { PmStepSource r = *this; r.choice_params = true; return r; }
+    PmStepSource with_choice_dev(const float* dev) const { PmStepSource r = *this; r.choice_dev = dev; return r; }
 };
+// a step's choice temperature: finite, 0 <= t <= 1000 (the bound keeps every noisy key above the -1e5 of a given id)
+constexpr float PM_CHOICE_T_MAX = 1000.f;
+int pm_check_choice_t(const char* who, float t);
 // block_stats: NULL, or the (max, sum of exp) pairs of the row's 64-column blocks, [M][V/64][2] (softmax_block_stat below)
 // period: 0, or the number of logits (and statistics) rows there are -- row r then samples from row r % period
 int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int period, const int64_t* ids_in, int64_t mask_id,

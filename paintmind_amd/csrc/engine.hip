@@ -974,10 +974,14 @@ struct Step {
     bool shared0 = false;
     const float* guidance = nullptr;
     const pmhip_slot* slots = nullptr; const pmhip_slot_guide* guides = nullptr;
+    // the re-masking step's choice temperature, by the same three sources: the scalar choice_t (with optional
+    // given uniforms choice_noise [B,N]); choice_params: gp->ctemps[step]; choice_dev: a device float [B] beside the slot records.
+    // None of them set: the plain re-masking launch.
+    float choice_t = 0.f; const float* choice_noise = nullptr; bool choice_params = false; const float* choice_dev = nullptr;
     PmStepSource source(int tokens) const {
-        if (slots) return PmStepSource::per_image(slots, tokens);
-        if (gp) return PmStepSource::params(gp, topk, step);
-        return PmStepSource::batch(topk, temperature, num_mask, seed, step, image_base * (uint64_t)tokens);
+        if (slots) { const PmStepSource p = PmStepSource::per_image(slots, tokens); return choice_dev ? p.with_choice_dev(choice_dev) : p; }
+        if (gp) { const PmStepSource p = PmStepSource::params(gp, topk, step); return choice_params ? p.with_choice_params() : p; }
+        return PmStepSource::batch(topk, temperature, num_mask, seed, step, image_base * (uint64_t)tokens).with_choice(choice_t, choice_noise);
     }
 };
 
@@ -1185,6 +1189,19 @@ extern "C" int pmhip_pipeline_sample_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t
                                 img_out, pred_out, score_out, stream);
 }
 
+// choice_t == 0 (and no given uniforms to ignore): exactly pmhip_pipeline_sample_lens
+extern "C" int pmhip_pipeline_sample_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                            const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                            uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                            float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
+                                            pmhip_stream stream) {
+    PM_TRY(pm_check_choice_t("pipeline_sample_choice", choice_t));
+    Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
+    if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }
+    return pipeline_sample_impl(choice_t != 0.f ? "pipeline_sample_choice" : "pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, st,
+                                img_out, pred_out, score_out, stream);
+}
+
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
 static bool direct_dispatch_off() {
     static const bool off = [] { const char* e = getenv("AMD_DIRECT_DISPATCH"); return e && atoi(e) == 0; }();
@@ -1202,6 +1219,7 @@ struct GenCall {
     const float* guidance = nullptr;
     const int32_t* ctx_lens = nullptr;      // host [B] or NULL (pmhip_pipeline_generate_lens)
     const char* who = "pipeline_generate";
+    const float* ctemps = nullptr;          // host [T] or NULL: the steps' choice temperatures (pmhip_pipeline_generate_choice)
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
 
@@ -1272,6 +1290,12 @@ int pipeline_generate(const GenCall& c) {
     PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && c.nmask_host, "pipeline_generate: bad arguments");
     PM_REQUIRE(!c.guidance || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
     PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
+    // the choice temperatures, checked before anything is launched; all zero IS the loop without them (same kernels, same graphs)
+    bool choice = false;
+    for (int t = 0; c.ctemps && t < T; ++t) {
+        PM_TRY(pm_check_choice_t(c.who, c.ctemps[t]));
+        choice = choice || c.ctemps[t] != 0.f;
+    }
     hipStream_t s = (hipStream_t)c.stream;
     hipStream_t cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
     PM_TRY(s2_prepare_context(s2, c.context, c.L, B, s));     // context projection + cross K/V: once per loop, eager
@@ -1327,7 +1351,8 @@ int pipeline_generate(const GenCall& c) {
         for (int t = 0; t < T; ++t) {
             const bool dec = c.decodes(t);
             float* img = !dec ? nullptr : (gimgs ? gimgs : c.imgs_out) + (size_t)d * img_elems;
-            const Step st{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0, c.guidance};
+            Step st{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0, c.guidance};
+            if (choice) st.choice_t = c.ctemps[t];             // 0 (the last step of an annealed loop): the plain launch, the same keys
             PM_TRY(tower(c.ids, st, s));
             PM_TRY(step_tail(s2, vq, c.ids, B, st, img, nullptr, nullptr, s));
             PM_TRY(out.flush());                               // the previous image, now that one more step is queued behind it
@@ -1348,10 +1373,12 @@ int pipeline_generate(const GenCall& c) {
         PmGenParams hp;
         hp.seed = c.seed;
         hp.row_base = c.image_base * (uint64_t)s2->cfg.tokens;
-        for (int t = 0; t < T; ++t) { hp.temps[t] = c.temps_host[t]; hp.nmask[t] = c.nmask_host[t]; }
+        for (int t = 0; t < T; ++t) { hp.temps[t] = c.temps_host[t]; hp.nmask[t] = c.nmask_host[t]; hp.ctemps[t] = choice ? c.ctemps[t] : 0.f; }
+        // a loop without choice temperatures stages what it always staged: the block up to ctemps, which none of its kernels reads
+        const size_t hp_bytes = choice ? sizeof hp : offsetof(PmGenParams, ctemps);
         PM_TRY(s2->params_ring.reserve(sizeof hp));
         PM_TRY(s2->params_ring.acquire());
-        PM_TRY(s2->params_ring.stage(gparams, 0, &hp, sizeof hp, s));
+        PM_TRY(s2->params_ring.stage(gparams, 0, &hp, hp_bytes, s));
         PM_TRY(s2->params_ring.commit(s));
     }
     if (from_mask) PM_TRY(fill_ids_async(gids, (int64_t)s2->cfg.n_embed, n_ids, s));
@@ -1375,6 +1402,7 @@ int pipeline_generate(const GenCall& c) {
     key += overlap ? "o1" : "o0";
     if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
     if (c.ctx_lens) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
+    if (choice) key += "c";                                   // the choice form of the re-masking kernel; the temperatures are not in the key
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     if (overlap) {
@@ -1399,7 +1427,8 @@ int pipeline_generate(const GenCall& c) {
             }
         }
         for (int t = u.t0; t < u.t1; ++t) {
-            const Step st{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0, c.guidance};
+            Step st{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0, c.guidance};
+            st.choice_params = choice;
             PM_TRY(tower(gids, st, on));
             if (need_join) { PM_HIP(hipStreamWaitEvent(on, ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
             float* img = (u.decode_inline && c.decodes(t)) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
@@ -1446,6 +1475,18 @@ extern "C" int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64
                                      "pipeline_generate_lens"});
 }
 
+extern "C" int pmhip_pipeline_generate_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                              const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                              const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                              float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                              pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host) {
+    GenCall c{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
+              use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
+              ctemps_host ? "pipeline_generate_choice" : "pipeline_generate_lens"};
+    c.ctemps = ctemps_host;
+    return pipeline_generate(c);
+}
+
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged
 // through the pinned ring into the workspace, and read from there by the sampling and re-masking kernels; with the graph flag the
 // step -- tower, sampling, re-masking: one linear chain -- is captured once per (B, context length) on handle-owned ids and
@@ -1457,15 +1498,19 @@ extern "C" int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64
 // PMHIP_SLOTS_KEEP_CONTEXT, where the kept cross K/V serve whatever lengths this call brings.
 static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
                            const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream,
-                           const int32_t* ctx_lens_host = nullptr) {
+                           const int32_t* ctx_lens_host = nullptr, const float* choice_host = nullptr) {
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0), L, B));
     const auto& c = s2->cfg;
     PM_REQUIRE(c.n_embed % 64 == 0, "%s: n_embed=%d must be a multiple of 64", who, c.n_embed);
-    bool two_pass = false;
+    bool two_pass = false, choice = false;      // choice: an active slot has a choice temperature other than 0 (else: the step without)
     for (int b = 0; b < B; ++b) {
         const pmhip_slot& sl = slots_host[b];
         if (sl.step & PM_SLOT_IDLE) continue;
+        if (choice_host) {
+            PM_TRY(pm_check_choice_t(who, choice_host[b]));
+            choice = choice || choice_host[b] != 0.f;
+        }
         PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "%s: slot %d: topk=%d must be in [1, 8]", who, b, sl.topk);
         PM_REQUIRE(sl.num_mask >= 1, "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
         if (guides_host && guides_host[b].on) {
@@ -1498,15 +1543,25 @@ static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const fl
     pmhip_slot_guide* dguides = nullptr;
     WS(s2->ws, "slots.dev", slot_bytes, dslots);
     if (two_pass) WS(s2->ws, "slots.guides", guide_bytes, dguides);
-    PM_TRY(s2->slots_ring.reserve(slot_bytes + guide_bytes));
+    // ... and behind those, on a 16-byte boundary, the B choice temperatures (padded to whole 16-byte words; an idle slot's is 0)
+    const size_t choice_at = (slot_bytes + guide_bytes + 15) & ~(size_t)15, choice_bytes = (size_t)round_up(B, 4) * 4;
+    float* dchoice = nullptr;
+    if (choice) WS(s2->ws, "slots.choice", choice_bytes, dchoice);
+    PM_TRY(s2->slots_ring.reserve(choice_at + choice_bytes));
     PM_TRY(s2->slots_ring.acquire());
     PM_TRY(s2->slots_ring.stage(dslots, 0, slots_host, slot_bytes, s));
     if (two_pass) PM_TRY(s2->slots_ring.stage(dguides, slot_bytes, guides_host, guide_bytes, s));
+    if (choice) {
+        std::vector<float> padded(choice_bytes / 4, 0.f);
+        for (int b = 0; b < B; ++b) padded[b] = (slots_host[b].step & PM_SLOT_IDLE) ? 0.f : choice_host[b];
+        PM_TRY(s2->slots_ring.stage(dchoice, choice_at, padded.data(), choice_bytes, s));
+    }
     PM_TRY(s2->slots_ring.commit(s));
     ++(two_pass ? s2->slots_two_pass : s2->slots_one_pass);
     Step st;
     st.slots = dslots;
     st.guides = dguides;
+    st.choice_dev = dchoice;
     auto run_step = [&](int64_t* on_ids, int64_t* pred, float* score, hipStream_t on) -> int {
         return sample_step(s2, nullptr, on_ids, B, st, nullptr, pred, score, on);
     };
@@ -1520,7 +1575,7 @@ static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const fl
     WS(s2->ws, "slots.ids", ids_bytes, gids);
     PM_TRY(copy16_async(gids, ids, ids_bytes, s));
     GraphEntry& ge = s2->graphs[(two_pass ? "slotsguidedB" : "slotsB") + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
-                                (ctx_lens_host ? "n" : "")];
+                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "")];
     PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
@@ -1545,6 +1600,14 @@ extern "C" int pmhip_pipeline_step_slots_lens(pmhip_s2* s2, int64_t* ids, const 
                                               int64_t* pred_out, float* score_out, pmhip_stream stream) {
     return step_slots_impl("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, guides_host, flags, pred_out, score_out, stream,
                            ctx_lens_host);
+}
+
+// choice_host NULL, or 0 for every active slot: exactly pmhip_pipeline_step_slots_lens
+extern "C" int pmhip_pipeline_step_slots_choice(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                                const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
+                                                int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    return step_slots_impl(choice_host ? "pipeline_step_slots_choice" : "pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, guides_host,
+                           flags, pred_out, score_out, stream, ctx_lens_host, choice_host);
 }
 
 // slots steps by tower passes: one (no active slot guided) / two

@@ -24,6 +24,7 @@
 // store of the row's outcome (store_outcome).  The host side has one launcher per kernel family (pm_sample_rows, pm_remask): one
 // copy of the checks, one place that picks the instantiation.
 #include <stdlib.h>
+#include <cmath>
 #include <type_traits>
 
 #include "common.h"
@@ -108,6 +109,33 @@ __device__ __forceinline__ bool image_num_mask(int& num_mask, int img, const PmG
         if (sl.step & PM_SLOT_IDLE) return false;
         num_mask = sl.num_mask;
     } else if (gp) num_mask = gp->nmask[step];
+    return true;
+}
+
+// and the values the CHOICE form of the re-masking kernel adds: the step's choice temperature t and the
+// Philox stream of the image -- element i draws at counter (base + i, 0xFFFFFFFF, step) under the seed.  BATCH: the kernel
+// arguments in `v`, base = row_base + img * N; PARAMS: t = gp->ctemps[step], seed and row base from the block; SLOTS: t =
+// choice[img] (a device float [B] beside the slot records), seed, step and image index from the slot.  false: an idle slot.
+struct ImageChoice { int num_mask; float t; uint64_t seed; uint32_t step; uint64_t base; };
+
+template <bool SLOTS>
+__device__ __forceinline__ bool image_choice(ImageChoice& v, int img, int N, const PmGenParams* __restrict__ gp,
+                                             const pmhip_slot* __restrict__ slots, const float* __restrict__ choice) {
+    if (!image_num_mask<SLOTS>(v.num_mask, img, gp, (int)v.step, slots)) return false;
+    if constexpr (SLOTS) {
+        const pmhip_slot sl = slots[img];
+        v.t = choice[img];
+        v.seed = sl.seed;
+        v.step = sl.step;
+        v.base = sl.image_index * (uint64_t)N;
+    } else {
+        if (gp) {
+            v.t = gp->ctemps[v.step];
+            v.seed = gp->seed;
+            v.base = gp->row_base;
+        }
+        v.base += (uint64_t)img * (uint64_t)N;
+    }
     return true;
 }
 
@@ -359,6 +387,7 @@ __device__ __forceinline__ unsigned long long remask_key(float score, int i) {
 // beyond that: 3 of the 55 stages at N = 1024 (the all-LDS sort of rounds 1-4 had one barrier per stage, 40 us per launch on B <= 64
 // workgroups -- latency, not work).
 // SLOTS (pmhip_remask_slots): num_mask = slots[image].num_mask; the workgroup of an idle slot leaves (before any barrier).
+// The network, the threshold and the store are remask_select.h: one copy for this kernel and the choice form below it.
 template <int E, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
                                                              int num_mask, int64_t mask_id, int N, const PmGenParams* __restrict__ gp,
@@ -375,52 +404,62 @@ __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict
         key[e] = i < N ? remask_key(sc[i], i) : 0ull;
         mine[e] = key[e];
     }
-#pragma unroll
-    for (int k = 2; k <= NP; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            if (j < E) {                                   // both elements in this thread
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if ((e & j) == 0) {
-                        const bool desc = ((base + e) & k) == 0;
-                        const unsigned long long a = key[e], b = key[e | j];
-                        const bool swap = desc ? (a < b) : (a > b);
-                        key[e] = swap ? b : a;
-                        key[e | j] = swap ? a : b;
-                    }
-                }
-            } else {
-                unsigned long long other[E];
-                if (j < 64 * E) {                          // the partner thread is in this wave
-#pragma unroll
-                    for (int e = 0; e < E; ++e) other[e] = __shfl_xor(key[e], j / E, 64);
+#include "remask_select.h"
+}
+
+// The CHOICE form (pmhip_remask_choice, pmhip_remask_choice_slots): MaskGIT's perturbed confidence.  With the
+// image's choice temperature t (image_choice) an element with score s sorts by
+//   s                                                           t == 0 (the plain key, bit for bit), or s < 0 (a given id: no draw)
+//   -fmaf(t, gumbel(u), logf(fmaxf(1 - s, 2^-24)))              otherwise
+// u: noise[img * N + i], or Philox at (base + i, 0xFFFFFFFF, step) -- a column word no class column has (V <= 16384), so the
+// stream never meets the token draw's.  t <= 1000 keeps every noisy key above the -1e5 of a given id; t is uniform over the
+// workgroup.  Everything behind the keys is remask_select.h, as in remask_reg_kernel.
+template <int E, bool SLOTS>
+__global__ __launch_bounds__(THREADS) void remask_choice_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores, int num_mask,
+                                                                int64_t mask_id, int N, const PmGenParams* __restrict__ gp, int step,
+                                                                const pmhip_slot* __restrict__ slots, float choice_t,
+                                                                const float* __restrict__ choice, const float* __restrict__ noise,
+                                                                uint64_t seed, uint64_t row_base) {
+    constexpr int NP = THREADS * E;
+    __shared__ unsigned long long xs[NP];
+    ImageChoice ic{num_mask, choice_t, seed, (uint32_t)step, row_base};
+    if (!image_choice<SLOTS>(ic, blockIdx.x, N, gp, slots, choice)) return;
+    num_mask = ic.num_mask;
+    const int tid = threadIdx.x, base = tid * E;
+    const float* sc = scores + (size_t)blockIdx.x * N;
+    // one element at a time (a Philox and three logf each: unrolled E = 16 times they would not fit the registers), through the
+    // thread's own E words of xs, which nobody else touches before the first barrier
+#pragma unroll 1
+    for (int e = 0; e < E; ++e) {
+        const int i = base + e;
+        unsigned long long k = 0ull;
+        if (i < N) {
+            float s = sc[i];
+            if (ic.t != 0.f && !(s < 0.f)) {
+                float u;
+                if (noise) {
+                    u = noise[(size_t)blockIdx.x * N + i];
                 } else {
-#pragma unroll
-                    for (int e = 0; e < E; ++e) xs[base + e] = key[e];
-                    __syncthreads();
-#pragma unroll
-                    for (int e = 0; e < E; ++e) other[e] = xs[(base + e) ^ j];
-                    __syncthreads();
+                    const uint64_t grow = ic.base + (uint64_t)i;
+                    const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), 0xFFFFFFFFu, ic.step),
+                                                    make_uint2((uint32_t)ic.seed, (uint32_t)(ic.seed >> 32)));
+                    u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
                 }
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const int i = base + e;
-                    const bool want_max = ((i & j) == 0) == ((i & k) == 0);   // descending block: the lower index keeps the larger key
-                    const unsigned long long a = key[e], b = other[e];
-                    key[e] = want_max ? (a > b ? a : b) : (a < b ? a : b);
-                }
+                const float ph = 1.0f - s;
+                const float conf = logf(fmaxf(ph, 0x1p-24f));
+                s = -fmaf(ic.t, gumbel_from_uniform(u), conf);
             }
+            k = remask_key(s, i);
         }
+        xs[i] = k;
     }
+    unsigned long long key[E], mine[E];
 #pragma unroll
-    for (int e = 0; e < E; ++e) xs[base + e] = key[e];
-    __syncthreads();
-    const int nm = num_mask < 1 ? 1 : (num_mask > N ? N : num_mask);
-    const unsigned long long thr = xs[nm - 1];
-#pragma unroll
-    for (int e = 0; e < E; ++e)
-        if (base + e < N && mine[e] >= thr) ids[(size_t)blockIdx.x * N + base + e] = mask_id;
+    for (int e = 0; e < E; ++e) {
+        key[e] = xs[base + e];
+        mine[e] = key[e];
+    }
+#include "remask_select.h"
 }
 
 // a run-time size class or flag as a compile-time constant: f(std::integral_constant<int, V>) for the one V of Vs that equals v
@@ -502,9 +541,16 @@ extern "C" int pmhip_sample_rows_slots(const float* logits, int ldl, const float
                           PmStepSource::per_image(slots, tokens), stream);
 }
 
+int pm_check_choice_t(const char* who, float t) {
+    PM_REQUIRE(std::isfinite(t) && t >= 0.f && t <= PM_CHOICE_T_MAX, "%s: the choice temperature %g must be finite and in [0, %g]", who, (double)t,
+               (double)PM_CHOICE_T_MAX);
+    return PMHIP_OK;
+}
+
 int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, const PmStepSource& src, pmhip_stream stream) {
     const bool slots = src.kind == PmStepSource::SLOTS;
-    const char* who = slots ? "remask_slots" : "remask";
+    const bool choice = src.choice_on();
+    const char* who = slots ? (choice ? "remask_choice_slots" : "remask_slots") : (choice ? "remask_choice" : "remask");
     PM_REQUIRE(ids && scores && (!slots || src.slots) && (src.kind != PmStepSource::PARAMS || src.gp), "%s: null pointer", who);
     PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "%s: bad shape B=%d N=%d (N <= 4096)", who, B, N);
     int per_thread = 1;                                    // E: the power of two with THREADS * E >= N
@@ -513,8 +559,12 @@ int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, 
     PmTimer tm(FAM_SAMPLE, s);
     pick<1, 2, 4, 8, 16>(per_thread, [&](auto E) {
         pick<0, 1>(slots, [&](auto SLOTS) {
-            hipLaunchKernelGGL((remask_reg_kernel<E(), SLOTS() == 1>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.num_mask, mask_id, N,
-                               src.gp, (int)src.step, src.slots);
+            if (choice)
+                hipLaunchKernelGGL((remask_choice_kernel<E(), SLOTS() == 1>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.num_mask, mask_id,
+                                   N, src.gp, (int)src.step, src.slots, src.choice_t, src.choice_dev, src.choice_noise, src.seed, src.row_base);
+            else
+                hipLaunchKernelGGL((remask_reg_kernel<E(), SLOTS() == 1>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.num_mask, mask_id, N,
+                                   src.gp, (int)src.step, src.slots);
         });
     });
     PM_HIP(hipGetLastError());
@@ -529,4 +579,18 @@ extern "C" int pmhip_remask(int64_t* ids, const float* scores, int num_mask, int
 extern "C" int pmhip_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id, int B, int N,
                                   pmhip_stream stream) {
     return pm_remask(ids, scores, mask_id, B, N, PmStepSource::per_image(slots, N), stream);
+}
+
+// the choice forms: the checks that concern the choice arguments, then the one launcher (choice_t == 0 without given noise IS
+// pmhip_remask: the plain kernel)
+extern "C" int pmhip_remask_choice(int64_t* ids, const float* scores, int num_mask, int64_t mask_id, int B, int N, float choice_t,
+                                   const float* noise, uint64_t seed, uint32_t step, uint64_t row_base, pmhip_stream stream) {
+    PM_TRY(pm_check_choice_t("remask_choice", choice_t));
+    return pm_remask(ids, scores, mask_id, B, N, PmStepSource::batch(0, 0.f, num_mask, seed, step, row_base).with_choice(choice_t, noise), stream);
+}
+
+extern "C" int pmhip_remask_choice_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, const float* choice_t_dev,
+                                         int64_t mask_id, int B, int N, pmhip_stream stream) {
+    PM_REQUIRE(choice_t_dev, "remask_choice_slots: null pointer");
+    return pm_remask(ids, scores, mask_id, B, N, PmStepSource::per_image(slots, N).with_choice_dev(choice_t_dev), stream);
 }

@@ -315,12 +315,15 @@ class S2Engine:
         return logits
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
-               want_img=True, want_aux=False, guidance_scale=None, context_lens=None):
+               want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
         guidance_scale (None = the reference's step): sample from uncond + scale * (cond - uncond), two tower passes.
         context_lens (None = every image attends to its whole context): image b's cross-attention sees context rows
-        [0, context_lens[b]) only (pmhip_pipeline_sample_lens)."""
+        [0, context_lens[b]) only (pmhip_pipeline_sample_lens).
+        choice_temperature (None or 0 = the reference's step): THIS step's choice temperature -- the re-masking sorts by MaskGIT's
+        perturbed confidence (pmhip_pipeline_sample_choice); choice_noise fp32 [B,N]: its uniforms (default: Philox)."""
         B = ids.shape[0]
+        ct = ops.choice_t(choice_temperature)
         context, L = self._ctx(context)
         lens = self._lens(context_lens, context, B, L)
         img = vq_engine._new_img(B) if want_img else None
@@ -331,8 +334,16 @@ class S2Engine:
         args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B,
                 int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img),
                 _p(pred), _p(score))
+        if choice_noise is not None:
+            choice_noise = choice_noise.to(self.device, torch.float32).contiguous()
+            if tuple(choice_noise.shape) != (B, self.tokens):
+                raise ValueError(f"choice_noise must be [B, {self.tokens}]")
         with torch.cuda.device(self.device):
-            if lens is not None:
+            if ct != 0.0:
+                check(self.lib.pmhip_pipeline_sample_choice(*args[:6], lens, *args[6:], int(guidance_scale is not None),
+                                                            float(guidance_scale or 0.0), ct, _p(choice_noise), stream_ptr(self.device)),
+                      "pmhip_pipeline_sample_choice")
+            elif lens is not None:
                 check(self.lib.pmhip_pipeline_sample_lens(*args[:6], lens, *args[6:], int(guidance_scale is not None),
                                                           float(guidance_scale or 0.0), stream_ptr(self.device)),
                       "pmhip_pipeline_sample_lens")
@@ -350,14 +361,17 @@ class S2Engine:
         check(self.lib.pmhip_s2_slots_steps(self.handle, C.byref(one), C.byref(two)), "pmhip_s2_slots_steps")
         return one.value, two.value
 
-    def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None):
+    def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None,
+                   choice=None):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
         length; the cross K/V the previous step_slots call prepared are reused.  guides: a ctypes array of _lib.SlotGuide beside
         `slots` (HOST records: scale, on) -- an active slot with on != 0 samples from uncond + scale * (cond - uncond), and a step
         with such a slot runs the tower twice (pmhip_pipeline_step_slots_guided).  context_lens: per-slot context lengths of THIS
-        step (pmhip_pipeline_step_slots_lens; also with keep_context, which keeps the cross K/V only).
+        step (pmhip_pipeline_step_slots_lens; also with keep_context, which keeps the cross K/V only).  choice: one choice
+        temperature per slot for THIS step (a list of B floats, 0 = the plain re-masking; pmhip_pipeline_step_slots_choice); None
+        or all zero is the step without.
         -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
@@ -375,8 +389,16 @@ class S2Engine:
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
         flags = (_lib.SLOTS_GRAPH if use_graph else 0) | (_lib.SLOTS_KEEP_CONTEXT if keep_context else 0)
+        if choice is not None:
+            if len(choice) != B:
+                raise ValueError(f"step_slots: {len(choice)} choice temperatures for a batch of {B}")
+            vals = [ops.choice_t(v, f"step_slots: slot {b}: choice temperature") for b, v in enumerate(choice)]
+            choice = (C.c_float * B)(*vals) if any(vals) else None
         with torch.cuda.device(self.device):
-            if lens is not None:
+            if choice is not None:
+                check(self.lib.pmhip_pipeline_step_slots_choice(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, flags,
+                                                                _p(pred), _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_choice")
+            elif lens is not None:
                 check(self.lib.pmhip_pipeline_step_slots_lens(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, flags, _p(pred),
                                                               _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_lens")
             elif guides is None:
@@ -388,7 +410,8 @@ class S2Engine:
         return ids, pred, score
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
-                 host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None):
+                 host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
+                 choice_temps=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
 
         host = (pinned float32 tensor [n_decoded, B_total, C, H, W], first row of this batch, copy stream): every decoded
@@ -398,9 +421,15 @@ class S2Engine:
         then does not put a small batch's decode on a side stream of its own).
         from_mask: the loop starts from the all-mask state (PMHIP_GENERATE_FROM_MASK): the native call writes that state itself --
         what `ids` holds on entry is ignored -- and an unconditional loop samples its step 0 from the handle's shared logits.
-        context_lens: per-image context lengths (pmhip_pipeline_generate_lens); the captured graphs read them from device memory."""
+        context_lens: per-image context lengths (pmhip_pipeline_generate_lens); the captured graphs read them from device memory.
+        choice_temps: one choice temperature per step (pmhip_pipeline_generate_choice); None or all zero is the loop without."""
         B = ids.shape[0]
         T = len(temps)
+        if choice_temps is not None:
+            if len(choice_temps) != T:
+                raise ValueError(f"generate: {len(choice_temps)} choice temperatures for {T} steps")
+            vals = [ops.choice_t(v, f"generate: step {i}: choice temperature") for i, v in enumerate(choice_temps)]
+            choice_temps = (C.c_float * T)(*vals) if any(vals) else None
         context, L = self._ctx(context)
         lens = self._lens(context_lens, context, B, L)
         n_dec = int(sum(1 for f in decode_flags if f))
@@ -426,7 +455,10 @@ class S2Engine:
                 (_lib.GENERATE_FROM_MASK if from_mask else 0),
                 stream_ptr(self.device), host_ptr, host_stride, copy_stream)
         with torch.cuda.device(self.device):
-            if lens is not None:
+            if choice_temps is not None:
+                check(self.lib.pmhip_pipeline_generate_choice(*args[:6], lens, *args[6:], int(guidance_scale is not None),
+                                                              float(guidance_scale or 0.0), choice_temps), "pmhip_pipeline_generate_choice")
+            elif lens is not None:
                 check(self.lib.pmhip_pipeline_generate_lens(*args[:6], lens, *args[6:], int(guidance_scale is not None),
                                                             float(guidance_scale or 0.0)), "pmhip_pipeline_generate_lens")
             elif guidance_scale is None:

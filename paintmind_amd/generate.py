@@ -43,6 +43,24 @@ def num_token_masked(mask_ratio, num_tokens):
     return max(int(r), 1)
 
 
+def choice_schedule(timesteps, choice_temperature):
+    """MaskGIT's annealed choice temperature: step s of T re-masks with t_s = choice_temperature * (1 - (s + 1) / T), evaluated in
+    double precision and rounded to fp32 once (what the kernels take); the last step's value is exactly 0.  None or 0 -> None (the
+    reference's deterministic re-masking).  The base value obeys the bound of every step's: finite, in [0, 1000]."""
+    base = ops.choice_t(choice_temperature)
+    if base == 0.0:
+        return None
+    return [float(np.float32(base * (1.0 - (step + 1) / timesteps))) for step in range(timesteps)]
+
+
+def choice_keys(scores, t, u):
+    """the re-masking keys of the plain-torch branch, fp32: a given position (score < 0) keeps its score, a taken one gets
+    -(log(max(1 - score, 2^-24)) + t * gumbel(u)) -- DESIGN.md section 4m; the largest keys are re-masked"""
+    conf = torch.log((1.0 - scores).clamp(min=2.0 ** -24))
+    gumbel = -torch.log((-torch.log(u.clamp(min=1e-20))).clamp(min=1e-20))
+    return torch.where(scores < 0, scores, -(conf + torch.tensor(t, dtype=scores.dtype) * gumbel))
+
+
 class _PinnedPool:
     """Pinned host buffers for the images generate() returns.  Page-locking a fresh 400 MB allocation costs ~35 ms (more
     than the copies themselves), so buffers are kept and handed out again -- but only once nothing the caller received
@@ -249,7 +267,7 @@ class Pipeline(nn.Module):
 
     @torch.no_grad()
     def sample(self, ids, mask_ratio, text=None, topk=1, temperature=1, noise=None, seed=None, step=0, image_base=0,
-               guidance_scale=None, context_lens=None):
+               guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None):
         """One MaskGIT step (generate.py:159-181) -> (ids', img).
 
         ``noise``: optional uniform(0,1) tensor shaped like the logits (B,N,V) -- the parity hook for the
@@ -265,19 +283,27 @@ class Pipeline(nn.Module):
 
         ``context_lens`` (extension; None = the reference's behaviour): one context length per image, see ``tokens2logits``.
         The unconditional forward of a guided step takes no context and so no lengths.
+
+        ``choice_temperature`` (extension; None or 0 = the reference's behaviour): THIS step's choice temperature, like
+        ``temperature`` the step's own value.  The re-masking then picks the ``num_mask`` positions by MaskGIT's perturbed
+        confidence ``log p + choice_temperature * gumbel`` instead of by ``1 - p`` alone; a position whose id was given is
+        never preferred to one the step took.  ``choice_noise``: optional uniform(0,1) tensor (B,N), the parity hook for
+        that gumbel noise; without it the Philox stream of the step, at a counter word no class column uses.
         """
         nm = num_token_masked(mask_ratio, self.num_tokens)
+        ct = ops.choice_t(choice_temperature)
         if guidance_scale is not None and text is None:
             raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
         lens = self._lens(context_lens, text, ids.shape[0])
         if self._on_cpu():
-            return self._sample_cpu(ids, nm, text, topk, temperature, noise, seed, guidance_scale, lens)
+            return self._sample_cpu(ids, nm, text, topk, temperature, noise, seed, guidance_scale, lens, ct, choice_noise)
         if seed is None:
             seed = _draw_seed()
         eng = self.engine()
         ids = ids.to(eng.device, torch.int64).clone().contiguous()
         ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, topk, temperature, nm, noise=noise, seed=seed, step=step,
-                                    image_base=image_base, want_img=True, guidance_scale=guidance_scale, context_lens=lens)
+                                    image_base=image_base, want_img=True, guidance_scale=guidance_scale, context_lens=lens,
+                                    choice_temperature=ct, choice_noise=choice_noise)
         return ids, img
 
     def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale, context_lens=None):
@@ -299,10 +325,12 @@ class Pipeline(nn.Module):
         ids = ops.remask(merged.reshape(B, N), score.reshape(B, N), nm, self.mask_token_id)
         return ids, img
 
-    def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None):
+    def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None, choice_t=0.0,
+                    choice_noise=None):
         """generate.py:159-181 in plain torch for a pipeline that lives on the CPU.  The noise is drawn from the torch CPU
         generator like the reference's (`seed` re-seeds a private generator; `noise` overrides it); ties in top-k / argmax
-        follow torch."""
+        follow torch.  choice_t != 0: the re-masking sorts by choice_keys; its uniforms are `choice_noise`, or drawn behind the
+        token noise from the same generator."""
         tok = self.ids2tokens(ids)
         logits = self.tokens2logits(tok, text, context_lens)
         if guidance_scale is not None:
@@ -310,8 +338,8 @@ class Pipeline(nn.Module):
             logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(guidance_scale)))
         val, ind = logits.topk(topk, dim=-1)
         filtered = torch.full_like(logits, float("-inf")).scatter_(2, ind, val)
+        g = None if seed is None else torch.Generator().manual_seed(int(seed) & (2 ** 63 - 1))
         if noise is None:
-            g = None if seed is None else torch.Generator().manual_seed(int(seed) & (2 ** 63 - 1))
             noise = torch.rand(logits.shape, generator=g)
         gumbel = -torch.log((-torch.log(noise.clamp(min=1e-20))).clamp(min=1e-20))
         pred = (filtered / max(temperature, 1e-10) + gumbel).argmax(dim=-1)
@@ -320,18 +348,24 @@ class Pipeline(nn.Module):
         ids = torch.where(is_mask, pred, ids)
         scores = 1 - logits.softmax(dim=-1).gather(2, pred[..., None])[..., 0]
         scores = scores.masked_fill(~is_mask, -1e5)
+        if choice_t:
+            if choice_noise is None:
+                choice_noise = torch.rand(scores.shape, generator=g)
+            scores = choice_keys(scores, choice_t, choice_noise.to(scores.dtype))
         ids = ids.scatter(1, scores.topk(nm, dim=-1).indices, self.mask_token_id)
         return ids, img
 
-    def _generate_cpu(self, text, context, timesteps, temperature, topk, save_interval, seed, return_ids, context_lens=None):
+    def _generate_cpu(self, text, context, timesteps, temperature, topk, save_interval, seed, return_ids, context_lens=None,
+                      choice_temperature=None):
         B = len(text)
+        ctemps = choice_schedule(timesteps, choice_temperature)
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
         imgs = []
         for step in range(timesteps):
             masked_r = mask_schedule((step + 1) / timesteps)
             ids, img = self._sample_cpu(ids, num_token_masked(masked_r, self.num_tokens), context, topk,
                                         temperature * (1 - step / timesteps), None, None if seed is None else seed + step,
-                                        None, context_lens)
+                                        None, context_lens, ctemps[step] if ctemps else 0.0)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
@@ -380,7 +414,7 @@ class Pipeline(nn.Module):
                              max_context_len=max_context_len)
 
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
-                     join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None):
+                     join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
 
         streams > 1 (or a tuple of micro-batch sizes): the batch is cut into contiguous micro-batches that run CONCURRENTLY on separate HIP
@@ -398,8 +432,11 @@ class Pipeline(nn.Module):
         its step 0 from logits the handle computed once (include/pmhip.h, PMHIP_GENERATE_FROM_MASK) -- same result, bit for bit,
         as passing an explicit all-mask ids0, which keeps the full path.
         context_lens (None: every image attends to all L rows of its context): one context length per image; image b's cross-attention
-        sees rows [0, context_lens[b]) only.  Every lane takes the slice of its micro-batch."""
+        sees rows [0, context_lens[b]) only.  Every lane takes the slice of its micro-batch.
+        choice_temperature (None or 0: the reference's deterministic re-masking): MaskGIT's base choice temperature, annealed over the
+        loop (choice_schedule); the noise is keyed by the global image index like the token draw's, so lanes change nothing."""
         lens = self._lens(context_lens, context, B)
+        ctemps = choice_schedule(timesteps, choice_temperature)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
@@ -426,7 +463,7 @@ class Pipeline(nn.Module):
             return eng.generate(self.vqgan.engine(), ids, context, temps, nmask, decode_flags, topk, seed=seed,
                                 image_base=image_base, use_graph=use_graph,
                                 host=None if host is None else (host[0], 0, host[1][0]), want_device_imgs=host is None,
-                                guidance_scale=guidance_scale, from_mask=ids0 is None, context_lens=lens)
+                                guidance_scale=guidance_scale, from_mask=ids0 is None, context_lens=lens, choice_temps=ctemps)
         from .dist import shard_range
         cur = torch.cuda.current_stream(eng.device)
         if wait_current:
@@ -444,7 +481,7 @@ class Pipeline(nn.Module):
                                        use_graph=use_graph, host=None if host is None else (host[0], lo, host[1][i]),
                                        want_device_imgs=host is None, guidance_scale=guidance_scale, concurrent_lanes=True,
                                        from_mask=True,          # lanes exist for ids0 None only (checked above)
-                                       context_lens=None if lens is None else lens[lo:hi])
+                                       context_lens=None if lens is None else lens[lo:hi], choice_temps=ctemps)
             return ids, imgs, st
 
         lanes = self._lanes(streams)
@@ -485,7 +522,7 @@ class Pipeline(nn.Module):
 
     def generate(self, text, timesteps=18, temperature=1.0, topk=5, save_interval=2, seed=None, image_base=0,
                  return_ids=False, keep_on_device=False, use_graph=None, streams=None, guidance_scale=None, mask_padding=False,
-                 context_lens=None):
+                 context_lens=None, choice_temperature=None):
         """Full decode loop (generate.py:183-198): list of (B,3,H,W) CPU tensors for steps % save_interval == 0.
 
         The call is the fast path by default: the loop replays captured hipGraphs (first call eager, second call captures),
@@ -509,8 +546,13 @@ class Pipeline(nn.Module):
 
         mask_padding (extension; False = the reference's behaviour: every row of the padded context is attended to, padding
         included): the text model is asked for the prompts' token counts (``text_model(text, return_lens=True)``) and every image's
-        cross-attention sees its own tokens only.  context_lens gives the lengths explicitly instead (one per prompt)."""
+        cross-attention sees its own tokens only.  context_lens gives the lengths explicitly instead (one per prompt).
+
+        choice_temperature (extension; None or 0 = the reference's behaviour: the least confident tokens are re-masked, a
+        deterministic choice): MaskGIT's choice temperature (its default is 4.5).  Step s of T re-masks by ``log p +
+        choice_temperature * (1 - (s + 1) / T) * gumbel``; the last step's noise is exactly zero."""
         B = len(text)
+        choice_schedule(timesteps, choice_temperature)        # the value is checked before anything runs
         if mask_padding and context_lens is None:
             context, context_lens = self.text_model(text, return_lens=True)
         else:
@@ -521,8 +563,8 @@ class Pipeline(nn.Module):
         if self._on_cpu():
             if guidance_scale is not None:
                 return self._generate_guided_cpu(context, B, timesteps, temperature, topk, save_interval, seed, return_ids, guidance_scale,
-                                                 lens)
-            return self._generate_cpu(text, context, timesteps, temperature, topk, save_interval, seed, return_ids, lens)
+                                                 lens, choice_temperature)
+            return self._generate_cpu(text, context, timesteps, temperature, topk, save_interval, seed, return_ids, lens, choice_temperature)
         eng = self.engine()
         if seed is None:
             seed = _draw_seed()
@@ -544,7 +586,8 @@ class Pipeline(nn.Module):
         n_dec = sum(flags)
         if keep_on_device or n_dec == 0:
             ids, imgs = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
-                                          use_graph=use_graph, streams=streams, guidance_scale=guidance_scale, context_lens=lens)
+                                          use_graph=use_graph, streams=streams, guidance_scale=guidance_scale, context_lens=lens,
+                                          choice_temperature=choice_temperature)
             out = [] if imgs is None else list(imgs)
             return (out, ids) if return_ids else out
         vq = self.vqgan.engine()
@@ -559,7 +602,7 @@ class Pipeline(nn.Module):
         try:
             ids, _ = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
                                        use_graph=use_graph, streams=streams, host=(host, cs), guidance_scale=guidance_scale,
-                                       context_lens=lens)
+                                       context_lens=lens, choice_temperature=choice_temperature)
         except BaseException:
             # a lane failed: whatever the other lanes queued may still be writing into `host`; drain it, and never hand
             # this buffer out again
@@ -579,20 +622,24 @@ class Pipeline(nn.Module):
         return (out, ids) if return_ids else out
 
     @torch.no_grad()
-    def _generate_guided_cpu(self, context, B, timesteps, temperature, topk, save_interval, seed, return_ids, scale, context_lens=None):
+    def _generate_guided_cpu(self, context, B, timesteps, temperature, topk, save_interval, seed, return_ids, scale, context_lens=None,
+                             choice_temperature=None):
         """generate.py:183-198 with guided steps (see `sample`) for a pipeline that lives on the CPU; same return structure.
         (On the GPU the guided loop is the native one: pmhip_pipeline_generate_guided, graph-captured and lane-able.)"""
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
         imgs = []
+        ctemps = choice_schedule(timesteps, choice_temperature)
         for step in range(timesteps):
             nm = num_token_masked(mask_schedule((step + 1) / timesteps), self.num_tokens)
             ids, img = self._sample_cpu(ids, nm, context, topk, temperature * (1 - step / timesteps), None,
-                                        None if seed is None else seed + step, scale, context_lens)
+                                        None if seed is None else seed + step, scale, context_lens, ctemps[step] if ctemps else 0.0)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
 
-    def _region_loop(self, img, coord, text, timesteps, topk, temperature, keep_inside, seed=None, return_ids=False):
+    def _region_loop(self, img, coord, text, timesteps, topk, temperature, keep_inside, seed=None, return_ids=False,
+                     choice_temperature=None):
+        choice_schedule(timesteps, choice_temperature)        # the value is checked before anything runs
         if seed is None:
             seed = _draw_seed()                 # one stream per call; the step index separates the steps
         z, ids, text = self.to_latent(img, text)
@@ -611,28 +658,31 @@ class Pipeline(nn.Module):
             # these start ids, decoding only the last step -- bit-identical to the per-step composition below (tests/test_gpu_model.py)
             use_graph = os.environ.get("PMHIP_GENERATE_GRAPH", "1") != "0"
             ids, imgs = self.generate_ids(text, ids.shape[0], timesteps, temperature, topk, [False] * (timesteps - 1) + [True], seed,
-                                          use_graph=use_graph, streams=1, ids0=ids)
+                                          use_graph=use_graph, streams=1, ids0=ids, choice_temperature=choice_temperature)
             return (imgs[0], ids) if return_ids else imgs[0]
-        return self._region_steps(ids, text, timesteps, topk, temperature, seed, return_ids)
+        return self._region_steps(ids, text, timesteps, topk, temperature, seed, return_ids, choice_temperature)
 
-    def _region_steps(self, ids, text, timesteps, topk, temperature, seed, return_ids=False):
+    def _region_steps(self, ids, text, timesteps, topk, temperature, seed, return_ids=False, choice_temperature=None):
         """the region loop as the reference writes it: one sample() per step (generate.py:211-216,230-235)"""
         out = None
+        ctemps = choice_schedule(timesteps, choice_temperature)
         for step in range(timesteps):
             progress = (step + 1) / timesteps
             masked_r = mask_schedule(progress)
             cur_temp = temperature * (1 - step / timesteps)
-            ids, out = self.sample(ids, mask_ratio=masked_r, text=text, topk=topk, temperature=cur_temp, seed=seed, step=step)
+            ids, out = self.sample(ids, mask_ratio=masked_r, text=text, topk=topk, temperature=cur_temp, seed=seed, step=step,
+                                   choice_temperature=ctemps[step] if ctemps else None)
         return (out, ids) if return_ids else out
 
     @torch.no_grad()
-    def inpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False):
-        """re-generate the rectangle coord=(x,y,h,w) in pixels (generate.py:200-217)."""
+    def inpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None):
+        """re-generate the rectangle coord=(x,y,h,w) in pixels (generate.py:200-217).  choice_temperature: as in ``generate`` (the
+        kept region's ids are given: the noise never prefers one of them to a position the loop took)."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=False, seed=seed,
-                                 return_ids=return_ids)
+                                 return_ids=return_ids, choice_temperature=choice_temperature)
 
     @torch.no_grad()
-    def outpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False):
-        """keep the rectangle, re-generate everything else (generate.py:219-236)."""
+    def outpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None):
+        """keep the rectangle, re-generate everything else (generate.py:219-236).  choice_temperature: as in ``inpaint``."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=True, seed=seed,
-                                 return_ids=return_ids)
+                                 return_ids=return_ids, choice_temperature=choice_temperature)

@@ -506,13 +506,31 @@ def sample_rows(logits, ids, mask_id, topk, temperature, noise=None, seed=0, ste
     return pred, ids_out, score
 
 
-def remask(ids, scores, num_mask, mask_id):
-    """in place on ids int64 [B,N]."""
-    dev = _dev(ids, scores)
+def choice_t(value, what="choice_temperature"):
+    """a step's choice temperature (None = 0) -> a float, checked as the native entries check it: finite, 0 <= t <= CHOICE_T_MAX"""
+    t = 0.0 if value is None else float(value)
+    if not (math.isfinite(t) and 0.0 <= t <= _lib.CHOICE_T_MAX):
+        raise ValueError(f"{what}: {value} must be finite and in [0, {_lib.CHOICE_T_MAX:g}]")
+    return t
+
+
+def remask(ids, scores, num_mask, mask_id, choice_temperature=0.0, noise=None, seed=0, step=0, row_base=0):
+    """in place on ids int64 [B,N].
+    choice_temperature (this step's value; 0 = the plain re-masking): MaskGIT's perturbed confidence -- a taken position sorts by
+    -(log(max(1 - score, 2^-24)) + t * gumbel(u)), a given one (score < 0) by its score (pmhip_remask_choice).  u: `noise` fp32
+    [B,N] uniform(0,1), or Philox under (seed, step, row_base + b*N + i) at the column word 0xFFFFFFFF."""
+    dev = _dev(ids, scores, noise)
     lib = _lib.load()
     B, N = ids.shape
+    t = choice_t(choice_temperature)
+    if noise is not None and (noise.dtype != torch.float32 or tuple(noise.shape) != (B, N)):
+        raise ValueError(f"remask: noise must be a contiguous fp32 [{B}, {N}] tensor on the operands' device")
     with torch.cuda.device(dev):
-        check(lib.pmhip_remask(_p(ids), _p(scores), int(num_mask), int(mask_id), B, N, stream_ptr(dev)), "pmhip_remask")
+        if t == 0.0 and noise is None:
+            check(lib.pmhip_remask(_p(ids), _p(scores), int(num_mask), int(mask_id), B, N, stream_ptr(dev)), "pmhip_remask")
+        else:
+            check(lib.pmhip_remask_choice(_p(ids), _p(scores), int(num_mask), int(mask_id), B, N, t, _p(noise), int(seed), int(step),
+                                          int(row_base), stream_ptr(dev)), "pmhip_remask_choice")
     return ids
 
 
@@ -557,14 +575,22 @@ def sample_rows_slots(logits, ids, mask_id, slots, tokens, block_stats=None):
     return pred, ids_out, score
 
 
-def remask_slots(ids, scores, slots, mask_id):
-    """remask with num_mask = slot b's, in place on ids int64 [B,N]; the row of an idle slot is left untouched."""
-    dev = _dev(ids, scores, slots)
+def remask_slots(ids, scores, slots, mask_id, choice=None):
+    """remask with num_mask = slot b's, in place on ids int64 [B,N]; the row of an idle slot is left untouched.
+    choice (None = the plain re-masking): fp32 [B] on the device, image b's choice temperature of this step (0: the plain key);
+    seed, step and image index of the Philox stream come from the slot (pmhip_remask_choice_slots)."""
+    dev = _dev(ids, scores, slots, choice)
     lib = _lib.load()
     B, N = ids.shape
     _check_slots(slots, B, dev)
     with torch.cuda.device(dev):
-        check(lib.pmhip_remask_slots(_p(ids), _p(scores), _p(slots), int(mask_id), B, N, stream_ptr(dev)), "pmhip_remask_slots")
+        if choice is None:
+            check(lib.pmhip_remask_slots(_p(ids), _p(scores), _p(slots), int(mask_id), B, N, stream_ptr(dev)), "pmhip_remask_slots")
+        else:
+            if choice.dtype != torch.float32 or tuple(choice.shape) != (B,):
+                raise ValueError(f"remask_slots: choice must be a contiguous fp32 [{B}] tensor on the operands' device")
+            check(lib.pmhip_remask_choice_slots(_p(ids), _p(scores), _p(slots), _p(choice), int(mask_id), B, N, stream_ptr(dev)),
+                  "pmhip_remask_choice_slots")
     return ids
 
 

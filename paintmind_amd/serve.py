@@ -24,7 +24,12 @@ different scales, and unguided ones, share a batch and each computes what it wou
 Limits: a session is all-conditional or all-unconditional (``context=None`` selects attn2's inputs for the whole batch), every
 context of a session has the same width D, top-k <= 8 (the block-statistics sampling kernel), and idle slots still run through
 the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the second tower pass: the
-unconditional pass runs at the session's batch size.  The guided loop's step-0 cache ("Not built") stays
+unconditional pass runs at the session's batch size.
+
+A choice temperature is per request too (``submit(choice_temperature=c)``): the request keeps MaskGIT's annealed value of each of
+its steps beside its temperatures and mask counts, the native step (pmhip_pipeline_step_slots_choice) reads one value per slot
+from a device array, and the contract reads ``generate_ids(..., choice_temperature=c)``.  A step in which no occupied slot has a
+non-zero value is the step without: the same entry, kernels and graph as before.  The guided loop's step-0 cache ("Not built") stays
 not built.
 
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
@@ -44,8 +49,10 @@ Finished = collections.namedtuple("Finished", ["handle", "image", "ids"])
 class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
-    def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None):
+    def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None,
+                 ctemps=None):
         self.number, self.text, self.context = number, text, context
+        self.ctemps = ctemps                        # None: no choice temperature; else the annealed value of every step
         self.guidance_scale = guidance_scale        # None: not guided
         self.timesteps, self.temperature, self.topk, self.seed, self.image_index = timesteps, temperature, topk, seed, image_index
         self.temps, self.nmask = temps, nmask
@@ -93,12 +100,13 @@ class DecodeSession:
 
     # -- requests -----------------------------------------------------------------------------------
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
-               guidance_scale=None):
+               guidance_scale=None, choice_temperature=None):
         """queue one request (any time, also between steps) -> its Request.  `context` [L_r, D] may be given instead of `text`
         (a conditional session runs the pipeline's text model on `text` otherwise), with its OWN length L_r: the request attends
         to exactly these rows; `ids0` [N]: start ids instead of all-mask;
         `guidance_scale` (None = not guided): this request samples from uncond + scale * (cond - uncond), like
-        ``Pipeline.generate(guidance_scale=)``."""
+        ``Pipeline.generate(guidance_scale=)``; `choice_temperature` (None or 0 = the deterministic re-masking): MaskGIT's base
+        choice temperature, annealed over this request's own steps like ``Pipeline.generate(choice_temperature=)``."""
         timesteps, topk = int(timesteps), int(topk)
         if guidance_scale is not None:
             if not self.conditional:
@@ -134,7 +142,10 @@ class DecodeSession:
         if ids0 is not None:
             ids0 = self.pipe._start_ids(1, ids0.reshape(1, -1), ids0.device)
         temps, nmask = self.pipe._schedule(timesteps, temperature)
-        r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale)
+        from .generate import choice_schedule
+        ctemps = choice_schedule(timesteps, choice_temperature)
+        r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale,
+                    ctemps)
         self._submitted += 1
         self.queue.append(r)
         return r
@@ -189,7 +200,8 @@ class DecodeSession:
                 continue
             t = r.done
             ctx = None if r.context is None else r.context[None]
-            ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t, r.guidance_scale)
+            ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t, r.guidance_scale,
+                                        None, r.ctemps[t] if r.ctemps else 0.0)
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
@@ -225,6 +237,9 @@ class DecodeSession:
         if self.active == 0:
             return []
         retiring = []
+        # this step's choice temperature of every slot; None when no occupied slot has a non-zero one: the step without
+        choice = [r.ctemps[r.done] if r is not None and r.ctemps else 0.0 for r in self.occupied]
+        choice = choice if any(choice) else None
         for j, r in enumerate(self.occupied):
             rec = self._records[j]
             if self._guides is not None:
@@ -247,13 +262,13 @@ class DecodeSession:
             lens = [min(n, ctx.shape[1]) for n in self._lens]
         try:
             _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep, want_aux=want_aux,
-                                            guides=self._guides, context_lens=lens)
+                                            guides=self._guides, context_lens=lens, choice=choice)
         except _lib.PmhipError as e:
             # another call on this handle (pipe.generate, a rebuilt engine ...) replaced the prepared context: prepare it again
             if not (keep and getattr(e, "code", None) == _lib.PMHIP_ESTATE):
                 raise
             _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=False, want_aux=want_aux,
-                                            guides=self._guides, context_lens=lens)
+                                            guides=self._guides, context_lens=lens, choice=choice)
         self._ctx_dirty = False
         for r in self.occupied:
             if r is not None:
