@@ -298,7 +298,11 @@ int pmhip_masked_ce(const float* logits, int ldl, const int64_t* labels, const f
  * reference's torch.zeros_like(t).uniform_(0,1), generate.py:41).
  * Outputs: pred[M] (all positions, what the image is decoded from, generate.py:165),
  * ids_out[M] = where(ids_in==mask_id, pred, ids_in), score[M] = is_mask ? 1-p[pred] : -1e5.
- * ids_out may alias ids_in.  Ties: (value desc, index asc). 1 <= topk <= 64. */
+ * ids_out may alias ids_in.  Ties: (value desc, index asc).  1 <= topk <= V (V <= 16384); topk = V is the sampler without a
+ * filter.  Which kernel runs depends on (V, topk) only: up to 8 with V % 64 == 0 the block-statistics kernel, up to 64 the row
+ * kernel with one candidate per lane, above 64 (within ABI 11: a wider accepted range, nothing that was accepted changes by a
+ * bit) the selection kernel, which keeps exactly the first topk elements of that order.  The noise of a (row, column) pair does
+ * not depend on topk.  -inf logits are legal (they sort last); NaN is unspecified. */
 int pmhip_sample_rows(const float* logits, int ldl, const int64_t* ids_in, int64_t mask_id,
                       int topk, float temperature, const float* noise, uint64_t seed,
                       uint32_t step, uint64_t row_base, int64_t* pred_out, int64_t* ids_out,
@@ -309,7 +313,8 @@ int pmhip_sample_rows(const float* logits, int ldl, const int64_t* ids_in, int64
  * For topk <= 8 the kernel reads the statistics (8 bytes per block) and the topk blocks with the largest maxima -- they contain
  * the topk largest elements -- instead of the whole row: 1 KiB + topk x 256 B instead of 32 KiB at V = 8192.
  * Same result, bit for bit, as pmhip_sample_rows on the same logits: for topk <= 8 and V % 64 == 0 that entry runs the same
- * kernel and derives the statistics from the stored row with the same arithmetic.  (topk > 8: the statistics are ignored.)
+ * kernel and derives the statistics from the stored row with the same arithmetic.  (topk > 8: the statistics are ignored; the
+ * range is pmhip_sample_rows': 1 <= topk <= V, the selection kernel above 64.)
  * V % 64 == 0.  Reference: generate.py:163-173, as above. */
 int pmhip_sample_rows_stats(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
                             int topk, float temperature, const float* noise, uint64_t seed, uint32_t step,
@@ -483,7 +488,10 @@ int pmhip_s2_forward(pmhip_s2* h, const float* tokens, const float* context, int
                      float* logits_out, pmhip_stream stream);
 
 /* Pipeline.sample (generate.py:159-181), one MaskGIT step on ids int64 [B,N] in place.
- * img_out may be NULL (skip the ViT decode of generate.py:165); pred_out/score_out may be NULL. */
+ * img_out may be NULL (skip the ViT decode of generate.py:165); pred_out/score_out may be NULL.
+ * topk, here and in every pmhip_pipeline_* entry below that takes one as an argument (sample / generate, their _guided, _lens and
+ * _choice forms): 1 <= topk <= n_embed, as pmhip_sample_rows serves it; topk = n_embed samples without a filter.  The slots
+ * entries keep 1..8 per record (pmhip_pipeline_step_slots). */
 int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L,
                           int B, int topk, float temperature, int num_mask, const float* noise,
                           uint64_t seed, uint32_t step, uint64_t image_base, float* img_out,
@@ -555,7 +563,8 @@ int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, 
                                    pmhip_stream copy_stream, float guidance_scale);
 
 /* ABI 11: one MaskGIT step (pmhip_pipeline_sample without the image) in which every image carries its own decode state:
- * slots_host[B] (HOST records, validated here: an active slot needs 1 <= topk <= 8 and num_mask >= 1) replace topk, temperature,
+ * slots_host[B] (HOST records, validated here: an active slot needs 1 <= topk <= 8 and num_mask >= 1 -- the wider range of the
+ * scalar entries stops here: a batch that mixes records at and above 8 would need a second sampling launch chosen per step) replace topk, temperature,
  * num_mask, seed, step and image_base.  The records travel through a pinned ring to device memory, from where the sampling and
  * re-masking kernels read them; the tower never mixes rows, so image b's pred / score / ids equal, bit for bit, those of the
  * scalar step run at the same B with slot b's values (idle slots still run through the tower; their ids stay as they are).

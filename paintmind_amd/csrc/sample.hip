@@ -8,6 +8,9 @@
 // (noise is only needed at those k positions: every other position is -inf in the reference), the
 // confidence of the unfiltered softmax at the sampled id, and the merge into the masked positions.
 //
+// sample_wide (top-k above 64, up to V: DESIGN.md section 4n): the same wave, row and normaliser; the kept set comes from a bitwise
+// selection of the k-th value over the resident row instead of k rounds, and every lane draws among its own kept elements.
+//
 // sample_tiles (round 5, top-k <= 8 and V a multiple of 64: every launch of the decode loop): the same step from the softmax
 // statistics of the row's 64-column blocks -- (max, sum of exp) per block, 8 bytes, left behind by the logits GEMM's epilogue
 // (gemm_common.h, GemmParams::block_stats) -- and the k blocks with the largest maxima, which contain the k largest elements:
@@ -18,11 +21,11 @@
 // of 64-bit (score, reversed index) keys (remask_key) gives the exact (score desc, index asc) order; the keys stay in registers
 // (remask_reg_kernel, round 5; the all-LDS sort of rounds 1-4 is gone).
 //
-// The two sampling kernels differ in how they find the k candidates and in how they round the confidence.  Everything else is ONE
-// piece of device code: where a row's step values come from (row_step: the kernel arguments, the PmGenParams block of a replayed
-// graph, or the pmhip_slot record of the row's image -- common.h PmStepSource), the draw among the candidates (draw_among) and the
-// store of the row's outcome (store_outcome).  The host side has one launcher per kernel family (pm_sample_rows, pm_remask): one
-// copy of the checks, one place that picks the instantiation.
+// The sampling kernels differ in how they find the k candidates and (the tiles kernel) in how they round the confidence.  Everything
+// else is ONE piece of device code: where a row's step values come from (row_step: the kernel arguments, the PmGenParams block of a
+// replayed graph, or the pmhip_slot record of the row's image -- common.h PmStepSource), an element's noise and perturbed value
+// (perturbed), the draw among up to 64 candidates (draw_among) and the store of the row's outcome (store_outcome).  The host side
+// has one launcher per kernel family (pm_sample_rows, pm_remask): one copy of the checks, one place that picks the instantiation.
 #include <stdlib.h>
 #include <cmath>
 #include <type_traits>
@@ -40,6 +43,12 @@ __device__ __forceinline__ bool before(float av, int ai, float bv, int bi) {
     return (av > bv) || (av == bv && ai < bi);
 }
 
+// a float as an unsigned word of the same order (NaN aside): the keys of the re-masking sort and of the wide top-k's selection
+__device__ __forceinline__ uint32_t orderable(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 // wave-wide arg-max under `before`: a butterfly on the VALU only (DPP inside a row of 16 lanes, then the row / half swaps;
 // nothing goes through the LDS pipe -- DESIGN.md section 4a).  Every lane ends with the same winner: the order is total.
 __device__ __forceinline__ Cand wave_best(Cand c) {
@@ -53,6 +62,18 @@ __device__ __forceinline__ Cand wave_best(Cand c) {
     PM_STEP(__uint_as_float(other32(__float_as_uint(c.v), lane)), (int)other32((unsigned)c.i, lane))
 #undef PM_STEP
     return c;
+}
+
+// wave-wide integer sum, the butterfly of wave_sum (common.h) on counts: every lane ends with the total
+__device__ __forceinline__ int wave_count(int v) {
+    v += dpp_mov<0xB1>(v);
+    v += dpp_mov<0x4E>(v);
+    v += dpp_mov<0x141>(v);
+    v += dpp_mov<0x140>(v);
+    auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+    v = (int)(a[0] + a[1]);
+    auto b = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+    return (int)(b[0] + b[1]);
 }
 
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
@@ -139,22 +160,29 @@ __device__ __forceinline__ bool image_choice(ImageChoice& v, int img, int N, con
     return true;
 }
 
+// ---- the perturbed value of one kept element (raw logit v at column col < V): v / max(T, 1e-10) + gumbel(u), u = noise[row][col]
+// when noise is given, else Philox at (global row, column, step) under the seed, word .x, its top 24 bits.  u is a function of
+// (row, column) and the step's values alone: which elements are kept, and how many, never moves the noise of one of them.
+__device__ __forceinline__ float perturbed(float v, int col, int row, int V, const RowStep& st, const float* __restrict__ noise) {
+    float u;
+    if (noise) {
+        u = noise[(size_t)row * V + col];
+    } else {
+        const uint64_t grow = st.row_base + (uint64_t)row;
+        const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), (uint32_t)col, st.step),
+                                        make_uint2((uint32_t)st.seed, (uint32_t)(st.seed >> 32)));
+        u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
+    }
+    return v / fmaxf(st.temperature, 1e-10f) + gumbel_from_uniform(u);
+}
+
 // ---- the draw: gumbel arg-max among the k candidates (lane r brings candidate r in `mine`: raw logit and column).  Noise is only
 // needed at the candidates: given, or Philox at (global row, column, step) under the seed.  Every lane returns the sampled column
 // and its RAW logit.
 __device__ __forceinline__ Cand draw_among(Cand mine, int lane, int row, int V, const RowStep& st, const float* __restrict__ noise) {
     Cand pert{-INFINITY, 0x7fffffff};
     if (lane < st.topk && mine.i < V) {
-        float u;
-        if (noise) {
-            u = noise[(size_t)row * V + mine.i];
-        } else {
-            const uint64_t grow = st.row_base + (uint64_t)row;
-            const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), (uint32_t)mine.i, st.step),
-                                            make_uint2((uint32_t)st.seed, (uint32_t)(st.seed >> 32)));
-            u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
-        }
-        pert.v = mine.v / fmaxf(st.temperature, 1e-10f) + gumbel_from_uniform(u);
+        pert.v = perturbed(mine.v, mine.i, row, V, st, noise);
         pert.i = mine.i;
     }
     const Cand win = wave_best(pert);
@@ -250,9 +278,145 @@ __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
     if (lane == 0) store_outcome(row, true, win.i, expf(win.v - mx) / se, ids_in, mask_id, pred_out, ids_out, score_out);
 }
 
+// ---- the wide form: 64 < top-k <= V.  Same wave, same resident row, same normaliser -- expression for
+// expression, so the confidence of a drawn id has the bits sample_rows_kernel gives it -- but the kept set is found by selection
+// instead of k rounds of arg-max, and every lane draws among its own kept elements instead of lane r among candidate r:
+//   1. the row's values become their orderable() keys in place (-0 counts as +0, like `before`; a column >= V gets key 0, below
+//      every value's);
+//   2. tau = the k-th largest key, one bit per round from the top: a per-lane count of keys >= the trial value, one wave_count;
+//   3. with g keys above tau, the k - g lowest COLUMNS among the keys equal to tau are kept: when there are more such keys than
+//      that, the same search over the column bits finds the last kept column c (otherwise all of them are kept);
+//   4. kept = key > tau, or key == tau and column <= c: exactly the first k elements of (value desc, column asc), one bit per
+//      element in the lane's mask words.  top-k == V skips 2 and 3 (wave-uniform): tau = 0 and c = V - 1 keep every column < V;
+//   5. each lane walks its mask from the lowest column up, reads the element's raw logit back (the row is in the cache it was just
+//      loaded through), perturbs it (perturbed: the noise of a (row, column) does not depend on k) and keeps its best under
+//      `before`; one wave_best finishes the draw, and the winner's lane hands over the raw logit.
+// The walk is a loop of as many turns as the fullest lane has kept elements -- about k / 64 when the kept set is spread over
+// the lanes -- with ONE copy of the Philox and the logarithms; the rounds of 2 and 3 are counted, never data-dependent.
+template <int NV4, bool PERIOD = false>
+__global__ __launch_bounds__(THREADS) void sample_wide_kernel(
+    const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, int64_t mask_id, int topk,
+    float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
+    int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
+    const PmGenParams* __restrict__ gp, int period) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+    if (row >= M) return;                                  // whole wave exits together
+    const RowStep rs = row_step<false>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, nullptr, 0);
+    const int lr = PERIOD ? row % period : row;
+    const float* lrow = logits + (size_t)lr * ldl;
+
+    float4 x[NV4];
+#pragma unroll
+    for (int g = 0; g < NV4; ++g) {
+        const int col = (g * 64 + lane) * 4;
+        x[g] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        if (col < V) x[g] = *reinterpret_cast<const float4*>(lrow + col);
+    }
+    // ---- softmax normaliser of the UNfiltered row: sample_rows_kernel's expressions, in its order
+    float mx = -INFINITY;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g) mx = fmaxf(mx, fmaxf(fmaxf(x[g].x, x[g].y), fmaxf(x[g].z, x[g].w)));
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g)
+        se += (__expf(x[g].x - mx) + __expf(x[g].y - mx)) + (__expf(x[g].z - mx) + __expf(x[g].w - mx));
+    se = wave_sum(se);
+
+    // ---- 1. keys in place of the values
+    uint32_t key[NV4][4];
+#pragma unroll
+    for (int g = 0; g < NV4; ++g) {
+        const bool in = (g * 64 + lane) * 4 < V;
+        key[g][0] = in ? orderable(x[g].x + 0.f) : 0u;
+        key[g][1] = in ? orderable(x[g].y + 0.f) : 0u;
+        key[g][2] = in ? orderable(x[g].z + 0.f) : 0u;
+        key[g][3] = in ? orderable(x[g].w + 0.f) : 0u;
+    }
+    // kept: key > tau, or key == tau and column <= last.  As they stand: every column < V (its key is above 0), none beyond.
+    // An element's column is (g * 64 + lane) * 4 + e = lane * 4 + (g * 256 + e): a bound on it is compared with the constant
+    // part after one subtraction per lane, so no column sits in a register.
+    uint32_t tau = 0u;
+    int last = V - 1;
+    if (topk < V) {                                        // wave-uniform
+        // ---- 2. the k-th largest key: the largest t with #(key >= t) >= k
+#pragma unroll 1
+        for (uint32_t bit = 0x80000000u; bit; bit >>= 1) {
+            const uint32_t trial = tau | bit;
+            int n = 0;
+#pragma unroll
+            for (int g = 0; g < NV4; ++g)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) n += key[g][e] >= trial;
+            if (__builtin_amdgcn_readfirstlane(wave_count(n)) >= topk) tau = trial;
+        }
+        int above = 0, equal = 0;
+#pragma unroll
+        for (int g = 0; g < NV4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                above += key[g][e] > tau;
+                equal += key[g][e] == tau;
+            }
+        const int need = topk - __builtin_amdgcn_readfirstlane(wave_count(above));     // >= 1: tau is the k-th largest
+        // ---- 3. the plateau straddles position k: the need-th lowest column of it = the largest c with #(equal, column < c) < need
+        if (need < __builtin_amdgcn_readfirstlane(wave_count(equal))) {
+            int c = 0;
+#pragma unroll 1
+            for (int bit = NV4 * 128; bit; bit >>= 1) {
+                const int trial = c | bit, mine = trial - lane * 4;
+                int n = 0;
+#pragma unroll
+                for (int g = 0; g < NV4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) n += key[g][e] == tau && g * 256 + e < mine;
+                if (__builtin_amdgcn_readfirstlane(wave_count(n)) < need) c = trial;
+            }
+            last = min(c, V - 1);
+        }
+    }
+    // ---- 4. the kept set, one bit per element: bit s = g * 4 + e of the lane's words, so a lane's columns rise with s
+    constexpr int NW = (NV4 * 4 + 31) / 32;
+    uint32_t kept[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) kept[w] = 0u;
+    const int mine_last = last - lane * 4;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int s = g * 4 + e;
+            const bool keep = key[g][e] > tau || (key[g][e] == tau && g * 256 + e <= mine_last);   // last < V: no column beyond
+            kept[s >> 5] |= (keep ? 1u : 0u) << (s & 31);
+        }
+    // ---- 5. the draw: every lane among its own kept elements, lowest column first
+    Cand best{-INFINITY, 0x7fffffff};
+    float raw = -INFINITY;
+    for (;;) {
+        int s = -1;
+#pragma unroll
+        for (int w = NW - 1; w >= 0; --w)
+            if (kept[w]) s = w * 32 + __ffs((int)kept[w]) - 1;
+        if (s < 0) break;
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+            if ((s >> 5) == w) kept[w] &= kept[w] - 1u;
+        const int col = (((s >> 2) * 64 + lane) << 2) + (s & 3);          // < V: step 4 kept no other
+        const float v = lrow[col];
+        const float pv = perturbed(v, col, row, V, rs, noise);
+        if (before(pv, col, best.v, best.i)) { best.v = pv; best.i = col; raw = v; }
+    }
+    const Cand win = wave_best(best);
+    const int owner = __builtin_amdgcn_readfirstlane((win.i >> 2) & 63);   // the lane that holds the winner's column
+    raw = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(raw), owner));
+    if (lane == 0) store_outcome(row, true, win.i, expf(raw - mx) / se, ids_in, mask_id, pred_out, ids_out, score_out);
+}
+
 
 // ---- the step from block statistics -----------------------------------------------------------------------------------------
 constexpr int KT_MAX = 8;                                  // top-k served by sample_tiles_kernel
+constexpr int K_LANES = 64;                                // top-k served by sample_rows_kernel: one candidate per lane
 
 // NB2 = blocks per lane (block b is kept by lane b % 64).  DENSE: no statistics were handed in -- one pass over the stored row
 // computes them (lane l, group g: columns (g*64 + l)*4 .. +3, i.e. block g*4 + l/16 in the layout softmax_block_stat defines).
@@ -372,11 +536,6 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
         store_outcome(row, true, win.i, __fdiv_rn(softmax_exp_below(win.v, mx), se), ids_in, mask_id, pred_out, ids_out, score_out);
 }
 
-__device__ __forceinline__ uint32_t orderable(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // the sort key: (score desc, index asc) as one descending 64-bit order
 __device__ __forceinline__ unsigned long long remask_key(float score, int i) {
     return ((unsigned long long)orderable(score) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i);
@@ -482,14 +641,15 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int p
         PM_REQUIRE(V % 64 == 0 && V <= 16384, "sample_rows_slots: V=%d must be a multiple of 64, at most 16384", V);
         PM_REQUIRE(src.tokens > 0 && M % src.tokens == 0, "sample_rows_slots: M=%d is not a whole number of images of %d tokens", M, src.tokens);
     } else {
-        PM_REQUIRE(src.topk >= 1 && src.topk <= 64 && src.topk <= V, "sample_rows: topk=%d must be in [1, min(64,V)]", src.topk);
+        PM_REQUIRE(src.topk >= 1 && src.topk <= V, "sample_rows: topk=%d must be in [1, V=%d]", src.topk, V);
         PM_REQUIRE(V <= 16384, "sample_rows: V=%d > 16384 unsupported", V);
     }
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(ceil_div(M, THREADS / 64)), block(THREADS);
     PmTimer tm(FAM_SAMPLE, s);
     // Which kernel runs depends on (V, topk) ONLY -- never on whether statistics were handed in: the two differ in the last bits
-    // of the confidence (sample_rows_kernel).  The records of a slots launch carry top-k <= 8 (checked where they are staged).
+    // of the confidence (sample_rows_kernel); above top-k = 8 statistics are ignored.  The records of a slots launch carry
+    // top-k <= 8 (checked where they are staged).
     static const int g_tiles = pm_dev_knob("PMHIP_SAMPLE_TILES", 1);     // 0: the one-read row kernel everywhere (A/B)
     if (slots || (g_tiles && src.topk <= KT_MAX && V % 64 == 0)) {
         const float2* st = reinterpret_cast<const float2*>(block_stats);
@@ -503,10 +663,14 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int p
             });
         });
     } else {
+        // the row kernels: candidate r in lane r up to top-k = 64 (K_LANES), the selection above it
         pick<1, 4, 32, 64>(V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64, [&](auto NV4) {
             pick<0, 1>(period != 0, [&](auto PER) {
-                hipLaunchKernelGGL((sample_rows_kernel<NV4(), PER() == 1>), grid, block, 0, s, logits, ldl, ids_in, mask_id, src.topk,
-                                   src.temperature, noise, src.seed, src.step, src.row_base, pred_out, ids_out, score_out, M, V, src.gp, period);
+                pick<0, 1>(src.topk > K_LANES, [&](auto WIDE) {
+                    auto kernel = WIDE() == 1 ? sample_wide_kernel<NV4(), PER() == 1> : sample_rows_kernel<NV4(), PER() == 1>;
+                    hipLaunchKernelGGL(kernel, grid, block, 0, s, logits, ldl, ids_in, mask_id, src.topk, src.temperature, noise, src.seed,
+                                       src.step, src.row_base, pred_out, ids_out, score_out, M, V, src.gp, period);
+                });
             });
         });
     }

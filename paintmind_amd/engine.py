@@ -317,6 +317,7 @@ class S2Engine:
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
                want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
+        topk: an integer in 1..n_embed (Pipeline resolves its topk=None to n_embed before it gets here).
         guidance_scale (None = the reference's step): sample from uncond + scale * (cond - uncond), two tower passes.
         context_lens (None = every image attends to its whole context): image b's cross-attention sees context rows
         [0, context_lens[b]) only (pmhip_pipeline_sample_lens).
@@ -413,6 +414,8 @@ class S2Engine:
                  host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
                  choice_temps=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
+
+        topk: an integer in 1..n_embed, the same for every step; part of the key of a captured graph.
 
         host = (pinned float32 tensor [n_decoded, B_total, C, H, W], first row of this batch, copy stream): every decoded
         image is copied into its rows on the copy stream as soon as it is complete (the reference's `img.cpu()`,

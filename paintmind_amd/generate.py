@@ -239,6 +239,11 @@ class Pipeline(nn.Module):
     def _on_cpu(self):
         return self.mask_token.device.type == "cpu"
 
+    def _topk(self, topk):
+        """topk=None is 'no filter' (the plain MaskGIT / Muse sampler): every class is kept, topk = n_embed -- on the CPU and
+        on the GPU branch alike.  An integer passes through unchecked: the step itself refuses what is out of 1..n_embed."""
+        return self.mask_token_id if topk is None else topk
+
     def _lens(self, context_lens, context, B):
         """context_lens (a list, a CPU tensor or a device tensor; None passes through) -> a checked list of B ints on the host,
         brought there ONCE per call: 1 <= len <= L, one per image"""
@@ -270,6 +275,9 @@ class Pipeline(nn.Module):
                guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None):
         """One MaskGIT step (generate.py:159-181) -> (ids', img).
 
+        ``topk``: 1..n_embed like the reference's ``top_k(logits, k)``, on the GPU as on the CPU (above
+        64 the selection kernel); ``None`` = no filter, i.e. n_embed.
+
         ``noise``: optional uniform(0,1) tensor shaped like the logits (B,N,V) -- the parity hook for the
         reference's ``torch.zeros_like(t).uniform_(0,1)``; without it a counter-based Philox stream keyed
         by (seed, step, image_base + image index, position, class) is used.  ``seed=None`` draws a fresh
@@ -292,6 +300,7 @@ class Pipeline(nn.Module):
         """
         nm = num_token_masked(mask_ratio, self.num_tokens)
         ct = ops.choice_t(choice_temperature)
+        topk = self._topk(topk)
         if guidance_scale is not None and text is None:
             raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
         lens = self._lens(context_lens, text, ids.shape[0])
@@ -359,6 +368,7 @@ class Pipeline(nn.Module):
                       choice_temperature=None):
         B = len(text)
         ctemps = choice_schedule(timesteps, choice_temperature)
+        topk = self._topk(topk)
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
         imgs = []
         for step in range(timesteps):
@@ -434,9 +444,11 @@ class Pipeline(nn.Module):
         context_lens (None: every image attends to all L rows of its context): one context length per image; image b's cross-attention
         sees rows [0, context_lens[b]) only.  Every lane takes the slice of its micro-batch.
         choice_temperature (None or 0: the reference's deterministic re-masking): MaskGIT's base choice temperature, annealed over the
-        loop (choice_schedule); the noise is keyed by the global image index like the token draw's, so lanes change nothing."""
+        loop (choice_schedule); the noise is keyed by the global image index like the token draw's, so lanes change nothing.
+        topk: 1..n_embed, or None = no filter (n_embed); part of the key of a captured graph."""
         lens = self._lens(context_lens, context, B)
         ctemps = choice_schedule(timesteps, choice_temperature)
+        topk = self._topk(topk)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
@@ -548,6 +560,9 @@ class Pipeline(nn.Module):
         included): the text model is asked for the prompts' token counts (``text_model(text, return_lens=True)``) and every image's
         cross-attention sees its own tokens only.  context_lens gives the lengths explicitly instead (one per prompt).
 
+        topk: any value in 1..n_embed, as in the reference, on the GPU as on the CPU; None = no top-k filter at all (the sampler of
+        the MaskGIT / Muse papers), i.e. n_embed.
+
         choice_temperature (extension; None or 0 = the reference's behaviour: the least confident tokens are re-masked, a
         deterministic choice): MaskGIT's choice temperature (its default is 4.5).  Step s of T re-masks by ``log p +
         choice_temperature * (1 - (s + 1) / T) * gumbel``; the last step's noise is exactly zero."""
@@ -629,6 +644,7 @@ class Pipeline(nn.Module):
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
         imgs = []
         ctemps = choice_schedule(timesteps, choice_temperature)
+        topk = self._topk(topk)
         for step in range(timesteps):
             nm = num_token_masked(mask_schedule((step + 1) / timesteps), self.num_tokens)
             ids, img = self._sample_cpu(ids, nm, context, topk, temperature * (1 - step / timesteps), None,
@@ -677,12 +693,13 @@ class Pipeline(nn.Module):
     @torch.no_grad()
     def inpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None):
         """re-generate the rectangle coord=(x,y,h,w) in pixels (generate.py:200-217).  choice_temperature: as in ``generate`` (the
-        kept region's ids are given: the noise never prefers one of them to a position the loop took)."""
+        kept region's ids are given: the noise never prefers one of them to a position the loop took).  topk: 1..n_embed, or
+        None = no filter, as in ``generate``."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=False, seed=seed,
                                  return_ids=return_ids, choice_temperature=choice_temperature)
 
     @torch.no_grad()
     def outpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None):
-        """keep the rectangle, re-generate everything else (generate.py:219-236).  choice_temperature: as in ``inpaint``."""
+        """keep the rectangle, re-generate everything else (generate.py:219-236).  choice_temperature, topk: as in ``inpaint``."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=True, seed=seed,
                                  return_ids=return_ids, choice_temperature=choice_temperature)

@@ -482,6 +482,8 @@ def vq_quantize(z, en, sq, beta=0.25):
 
 def sample_rows(logits, ids, mask_id, topk, temperature, noise=None, seed=0, step=0, row_base=0, block_stats=None):
     """logits fp32 [M,V], ids int64 [M] -> (pred [M], merged ids [M], score [M]).
+    topk: 1..V.  Which kernel serves it depends on (V, topk) only: up to 8 (V % 64 == 0) the block-statistics kernel, up to 64 the
+    row kernel with one candidate per lane, above 64 the selection kernel; block_stats are ignored above 8.
     block_stats fp32 [M, V/64, 2] (gemm_softmax_stats / guidance_combine(with_stats=True)): the kernel reads them and the top-k
     blocks of a row instead of the row; same bits as without."""
     dev = _dev(logits, ids, noise)

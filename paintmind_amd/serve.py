@@ -22,7 +22,9 @@ at least one active slot is guided, and combines the two towers' logits on the r
 different scales, and unguided ones, share a batch and each computes what it would compute alone.
 
 Limits: a session is all-conditional or all-unconditional (``context=None`` selects attn2's inputs for the whole batch), every
-context of a session has the same width D, top-k <= 8 (the block-statistics sampling kernel), and idle slots still run through
+context of a session has the same width D, top-k <= 8 (the block-statistics sampling kernel: ``Pipeline.generate`` takes any
+top-k up to n_embed, and ``None`` for no filter, DESIGN.md section 4n, but a session does not -- a batch that mixes requests at
+and above 8 needs a second sampling launch chosen step by step, which is not built), and idle slots still run through
 the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the second tower pass: the
 unconditional pass runs at the session's batch size.
 
