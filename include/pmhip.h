@@ -26,7 +26,7 @@
  *         ldo >= N, ldr >= N          pmhip_gemm / _ln / _softmax_stats (ldr only with a residual), pmhip_gemm_hilo / _stats / _center
  *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
  *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens
- *         ldl >= V                    pmhip_sample_rows / _stats / _slots, pmhip_masked_ce
+ *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus, pmhip_masked_ce
  *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
  *     N * ldw stay below 2^30 elements; beyond that another kernel may serve the call).
  *   - an output of [M, N] is written in exactly its M x N elements, however ragged M and N are against a kernel's tile; arrays
@@ -307,6 +307,19 @@ int pmhip_sample_rows(const float* logits, int ldl, const int64_t* ids_in, int64
                       int topk, float temperature, const float* noise, uint64_t seed,
                       uint32_t step, uint64_t row_base, int64_t* pred_out, int64_t* ids_out,
                       float* score_out, int M, int V, pmhip_stream stream);
+
+/* The same step with a NUCLEUS (top-p) filter behind the top-k (new entries within ABI 11).  0 < top_p <= 1, finite (else
+ * PMHIP_EINVAL); top_p == 1 is pmhip_sample_rows: the same kernel, the same bits.  Below 1, with K the first topk elements of
+ * (value desc, column asc), w_i = exp(x_i - max), Z = sum of w over K and P = top_p * Z: element i of K is kept iff the mass of
+ * the elements of K whose weight is strictly above w_i is below P.  A plateau of equal weights is kept or dropped whole, the
+ * row's maximum is always kept, a weight that underflows to 0 never is.  The filter reads the RAW logits, as the top-k does: the
+ * temperature acts in the draw only, and the confidence stays the unfiltered softmax of the drawn id.  The noise of a (row,
+ * column) pair depends neither on topk nor on top_p.  One kernel serves every topk in 1..V (block statistics play no part);
+ * which kernel runs depends on (V, topk, top_p < 1) only.  Sums are fp32 in a fixed order: an element whose mass above it lies
+ * within 1e-4 Z of P may fall on either side of what exact arithmetic gives (tests/nucleus_ref.py). */
+int pmhip_sample_rows_nucleus(const float* logits, int ldl, const int64_t* ids_in, int64_t mask_id, int topk, float top_p,
+                              float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base,
+                              int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream);
 
 /* The same step for a caller that holds the SOFTMAX STATISTICS of the rows' 64-column blocks (round 5): block_stats [M][V/64][2] =
  * (max, sum_j 2^((x_j - max) log2 e)) per block, as pmhip_gemm_softmax_stats / pmhip_guidance_combine_stats leave them behind.
@@ -654,6 +667,24 @@ int pmhip_pipeline_step_slots_choice(pmhip_s2* s2, int64_t* ids, const float* co
                                      const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
                                      const pmhip_slot_guide* guides_host, const float* choice_host /* [B] or NULL */, int flags,
                                      int64_t* pred_out, float* score_out, pmhip_stream stream);
+
+/* NUCLEUS FILTER at the model level (new entries within ABI 11): the *_choice entries with `top_p`, the token draw's nucleus mass
+ * (pmhip_sample_rows_nucleus above: 0 < top_p <= 1, validated before anything is launched), one value for the batch and, in the
+ * loop, for every step.  top_p == 1 runs exactly the *_choice entry: the same kernels and the same captured graphs.  Below 1 the
+ * sampling launch is the nucleus kernel and nothing else of the step changes, so it composes with guidance, context lengths,
+ * choice temperatures, lanes and PMHIP_GENERATE_FROM_MASK; with the graph flag top_p is a kernel argument of the captured loop,
+ * like topk: one graph per value.  The slots entries have no top_p: a pmhip_slot record carries none. */
+int pmhip_pipeline_sample_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                  const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                  uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                  float* score_out, int guided, float guidance_scale, float choice_t,
+                                  const float* choice_noise /* [B,N] or NULL */, float top_p, pmhip_stream stream);
+int pmhip_pipeline_generate_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                    const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                    const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                    float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                    pmhip_stream copy_stream, int guided, float guidance_scale,
+                                    const float* ctemps_host /* [T] or NULL */, float top_p);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

@@ -160,6 +160,12 @@ PROTOTYPES = {
                                              C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32)]),
     "pmhip_pipeline_step_slots_choice": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
                                                i32, vp, vp, vp]),
+    "pmhip_sample_rows_nucleus": (i32, [vp, i32, vp, i64, i32, f32, f32, vp, u64, u32, u64, vp, vp, vp, i32, i32, vp]),
+    "pmhip_pipeline_sample_nucleus": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, i32, f32,
+                                            f32, vp, f32, vp]),
+    "pmhip_pipeline_generate_nucleus": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
+                                              C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
+                                              f32]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),

@@ -88,7 +88,7 @@ constexpr uint32_t PM_SLOT_IDLE = 0x80000000u;              // bit 31 of pmhip_s
 //   BATCH   the scalars below, one set for every row;
 //   PARAMS  a replayed graph: temperature, mask count, seed and row base from the device block gp, indexed by `step`; top-k and
 //           the step stay kernel arguments (they are part of the graph);
-//   SLOTS   per image: the device records slots [M / tokens] (the block-statistics kernel only: V % 64 == 0, top-k <= 8).
+//   SLOTS   per image: the device records slots [M / tokens] (the block-statistics kernel only: V % 64 == 0, top-k <= 8, no top_p).
 // ---------------------------------------------------------------------------------------------
 struct PmStepSource {
     enum Kind { BATCH, PARAMS, SLOTS } kind;
@@ -108,7 +108,14 @@ struct PmStepSource {
     PmStepSource with_choice(float t, const float* noise) const { PmStepSource r = *this; r.choice_t = t; r.choice_noise = noise; return r; }
     PmStepSource with_choice_params() const { PmStepSource r = *this; r.choice_params = true; return r; }
     PmStepSource with_choice_dev(const float* dev) const { PmStepSource r = *this; r.choice_dev = dev; return r; }
+    // The nucleus filter of the token draw (pm_sample_rows only): of the top-k elements, those whose mass
+    // strictly above them is below top_p of the top-k's mass.  BATCH and PARAMS only -- a kernel argument, like top-k; a SLOTS
+    // source with top_p < 1 is refused.  1 (the default): no filter, the kernels that ran before.
+    float top_p = 1.f;
+    PmStepSource with_top_p(float p) const { PmStepSource r = *this; r.top_p = p; return r; }
 };
+// a step's nucleus mass: finite, 0 < top_p <= 1
+int pm_check_top_p(const char* who, float p);
 // a step's choice temperature: finite, 0 <= t <= 1000 (the bound keeps every noisy key above the -1e5 of a given id)
 constexpr float PM_CHOICE_T_MAX = 1000.f;
 int pm_check_choice_t(const char* who, float t);

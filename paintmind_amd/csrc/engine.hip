@@ -978,10 +978,13 @@ struct Step {
     // given uniforms choice_noise [B,N]); choice_params: gp->ctemps[step]; choice_dev: a device float [B] beside the slot records.
     // None of them set: the plain re-masking launch.
     float choice_t = 0.f; const float* choice_noise = nullptr; bool choice_params = false; const float* choice_dev = nullptr;
+    // the token draw's nucleus mass: the batch's value, with the scalars and with gp alike (a kernel argument
+    // of a captured step, like top-k); a slots step has none.  1: no filter.
+    float top_p = 1.f;
     PmStepSource source(int tokens) const {
-        if (slots) { const PmStepSource p = PmStepSource::per_image(slots, tokens); return choice_dev ? p.with_choice_dev(choice_dev) : p; }
-        if (gp) { const PmStepSource p = PmStepSource::params(gp, topk, step); return choice_params ? p.with_choice_params() : p; }
-        return PmStepSource::batch(topk, temperature, num_mask, seed, step, image_base * (uint64_t)tokens).with_choice(choice_t, choice_noise);
+        if (slots) { const PmStepSource p = PmStepSource::per_image(slots, tokens); return (choice_dev ? p.with_choice_dev(choice_dev) : p).with_top_p(top_p); }
+        if (gp) { const PmStepSource p = PmStepSource::params(gp, topk, step); return (choice_params ? p.with_choice_params() : p).with_top_p(top_p); }
+        return PmStepSource::batch(topk, temperature, num_mask, seed, step, image_base * (uint64_t)tokens).with_choice(choice_t, choice_noise).with_top_p(top_p);
     }
 };
 
@@ -1202,6 +1205,23 @@ extern "C" int pmhip_pipeline_sample_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64
                                 img_out, pred_out, score_out, stream);
 }
 
+// top_p == 1: exactly pmhip_pipeline_sample_choice
+extern "C" int pmhip_pipeline_sample_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                             const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                             uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                             float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
+                                             float top_p, pmhip_stream stream) {
+    PM_TRY(pm_check_top_p("pipeline_sample_nucleus", top_p));
+    if (top_p == 1.f)
+        return pmhip_pipeline_sample_choice(s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step, image_base,
+                                            img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, stream);
+    PM_TRY(pm_check_choice_t("pipeline_sample_nucleus", choice_t));
+    Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
+    if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }
+    st.top_p = top_p;
+    return pipeline_sample_impl("pipeline_sample_nucleus", s2, vq, ids, context, L, B, ctx_lens_host, st, img_out, pred_out, score_out, stream);
+}
+
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
 static bool direct_dispatch_off() {
     static const bool off = [] { const char* e = getenv("AMD_DIRECT_DISPATCH"); return e && atoi(e) == 0; }();
@@ -1220,6 +1240,7 @@ struct GenCall {
     const int32_t* ctx_lens = nullptr;      // host [B] or NULL (pmhip_pipeline_generate_lens)
     const char* who = "pipeline_generate";
     const float* ctemps = nullptr;          // host [T] or NULL: the steps' choice temperatures (pmhip_pipeline_generate_choice)
+    float top_p = 1.f;                      // every step's nucleus mass (pmhip_pipeline_generate_nucleus); 1: no filter
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
 
@@ -1290,6 +1311,7 @@ int pipeline_generate(const GenCall& c) {
     PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && c.nmask_host, "pipeline_generate: bad arguments");
     PM_REQUIRE(!c.guidance || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
     PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
+    PM_TRY(pm_check_top_p(c.who, c.top_p));
     // the choice temperatures, checked before anything is launched; all zero IS the loop without them (same kernels, same graphs)
     bool choice = false;
     for (int t = 0; c.ctemps && t < T; ++t) {
@@ -1353,6 +1375,7 @@ int pipeline_generate(const GenCall& c) {
             float* img = !dec ? nullptr : (gimgs ? gimgs : c.imgs_out) + (size_t)d * img_elems;
             Step st{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0, c.guidance};
             if (choice) st.choice_t = c.ctemps[t];             // 0 (the last step of an annealed loop): the plain launch, the same keys
+            st.top_p = c.top_p;
             PM_TRY(tower(c.ids, st, s));
             PM_TRY(step_tail(s2, vq, c.ids, B, st, img, nullptr, nullptr, s));
             PM_TRY(out.flush());                               // the previous image, now that one more step is queued behind it
@@ -1403,6 +1426,11 @@ int pipeline_generate(const GenCall& c) {
     if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
     if (c.ctx_lens) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
     if (choice) key += "c";                                   // the choice form of the re-masking kernel; the temperatures are not in the key
+    if (c.top_p < 1.f) {                                      // the nucleus kernel, the mass its argument in the captured graph: one graph per value
+        unsigned bits;
+        memcpy(&bits, &c.top_p, 4);
+        key += "p" + std::to_string(bits);
+    }
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     if (overlap) {
@@ -1429,6 +1457,7 @@ int pipeline_generate(const GenCall& c) {
         for (int t = u.t0; t < u.t1; ++t) {
             Step st{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0, c.guidance};
             st.choice_params = choice;
+            st.top_p = c.top_p;
             PM_TRY(tower(gids, st, on));
             if (need_join) { PM_HIP(hipStreamWaitEvent(on, ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
             float* img = (u.decode_inline && c.decodes(t)) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
@@ -1484,6 +1513,26 @@ extern "C" int pmhip_pipeline_generate_choice(pmhip_s2* s2, pmhip_vqgan* vq, int
               use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
               ctemps_host ? "pipeline_generate_choice" : "pipeline_generate_lens"};
     c.ctemps = ctemps_host;
+    return pipeline_generate(c);
+}
+
+// top_p == 1: exactly pmhip_pipeline_generate_choice
+extern "C" int pmhip_pipeline_generate_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                               const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                               const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                               float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                               pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
+                                               float top_p) {
+    PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
+    if (top_p == 1.f)
+        return pmhip_pipeline_generate_choice(s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host, topk, seed,
+                                              image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                              guidance_scale, ctemps_host);
+    GenCall c{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
+              use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
+              "pipeline_generate_nucleus"};
+    c.ctemps = ctemps_host;
+    c.top_p = top_p;
     return pipeline_generate(c);
 }
 

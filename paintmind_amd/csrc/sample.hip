@@ -11,6 +11,9 @@
 // sample_wide (top-k above 64, up to V: DESIGN.md section 4n): the same wave, row and normaliser; the kept set comes from a bitwise
 // selection of the k-th value over the resident row instead of k rounds, and every lane draws among its own kept elements.
 //
+// sample_nucleus (top_p < 1, any top-k: DESIGN.md section 4o): the wide form's selection, then the kept elements' softmax weights
+// in place of the keys and a bitwise search for the weight at which the mass from the top reaches top_p of the kept mass.
+//
 // sample_tiles (round 5, top-k <= 8 and V a multiple of 64: every launch of the decode loop): the same step from the softmax
 // statistics of the row's 64-column blocks -- (max, sum of exp) per block, 8 bytes, left behind by the logits GEMM's epilogue
 // (gemm_common.h, GemmParams::block_stats) -- and the k blocks with the largest maxima, which contain the k largest elements:
@@ -299,83 +302,7 @@ __global__ __launch_bounds__(THREADS) void sample_wide_kernel(
     float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
     const PmGenParams* __restrict__ gp, int period) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
-    if (row >= M) return;                                  // whole wave exits together
-    const RowStep rs = row_step<false>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, nullptr, 0);
-    const int lr = PERIOD ? row % period : row;
-    const float* lrow = logits + (size_t)lr * ldl;
-
-    float4 x[NV4];
-#pragma unroll
-    for (int g = 0; g < NV4; ++g) {
-        const int col = (g * 64 + lane) * 4;
-        x[g] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        if (col < V) x[g] = *reinterpret_cast<const float4*>(lrow + col);
-    }
-    // ---- softmax normaliser of the UNfiltered row: sample_rows_kernel's expressions, in its order
-    float mx = -INFINITY;
-#pragma unroll
-    for (int g = 0; g < NV4; ++g) mx = fmaxf(mx, fmaxf(fmaxf(x[g].x, x[g].y), fmaxf(x[g].z, x[g].w)));
-    mx = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int g = 0; g < NV4; ++g)
-        se += (__expf(x[g].x - mx) + __expf(x[g].y - mx)) + (__expf(x[g].z - mx) + __expf(x[g].w - mx));
-    se = wave_sum(se);
-
-    // ---- 1. keys in place of the values
-    uint32_t key[NV4][4];
-#pragma unroll
-    for (int g = 0; g < NV4; ++g) {
-        const bool in = (g * 64 + lane) * 4 < V;
-        key[g][0] = in ? orderable(x[g].x + 0.f) : 0u;
-        key[g][1] = in ? orderable(x[g].y + 0.f) : 0u;
-        key[g][2] = in ? orderable(x[g].z + 0.f) : 0u;
-        key[g][3] = in ? orderable(x[g].w + 0.f) : 0u;
-    }
-    // kept: key > tau, or key == tau and column <= last.  As they stand: every column < V (its key is above 0), none beyond.
-    // An element's column is (g * 64 + lane) * 4 + e = lane * 4 + (g * 256 + e): a bound on it is compared with the constant
-    // part after one subtraction per lane, so no column sits in a register.
-    uint32_t tau = 0u;
-    int last = V - 1;
-    if (topk < V) {                                        // wave-uniform
-        // ---- 2. the k-th largest key: the largest t with #(key >= t) >= k
-#pragma unroll 1
-        for (uint32_t bit = 0x80000000u; bit; bit >>= 1) {
-            const uint32_t trial = tau | bit;
-            int n = 0;
-#pragma unroll
-            for (int g = 0; g < NV4; ++g)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) n += key[g][e] >= trial;
-            if (__builtin_amdgcn_readfirstlane(wave_count(n)) >= topk) tau = trial;
-        }
-        int above = 0, equal = 0;
-#pragma unroll
-        for (int g = 0; g < NV4; ++g)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                above += key[g][e] > tau;
-                equal += key[g][e] == tau;
-            }
-        const int need = topk - __builtin_amdgcn_readfirstlane(wave_count(above));     // >= 1: tau is the k-th largest
-        // ---- 3. the plateau straddles position k: the need-th lowest column of it = the largest c with #(equal, column < c) < need
-        if (need < __builtin_amdgcn_readfirstlane(wave_count(equal))) {
-            int c = 0;
-#pragma unroll 1
-            for (int bit = NV4 * 128; bit; bit >>= 1) {
-                const int trial = c | bit, mine = trial - lane * 4;
-                int n = 0;
-#pragma unroll
-                for (int g = 0; g < NV4; ++g)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) n += key[g][e] == tau && g * 256 + e < mine;
-                if (__builtin_amdgcn_readfirstlane(wave_count(n)) < need) c = trial;
-            }
-            last = min(c, V - 1);
-        }
-    }
+#include "sample_select_prologue.h"
     // ---- 4. the kept set, one bit per element: bit s = g * 4 + e of the lane's words, so a lane's columns rise with s
     constexpr int NW = (NV4 * 4 + 31) / 32;
     uint32_t kept[NW];
@@ -390,27 +317,70 @@ __global__ __launch_bounds__(THREADS) void sample_wide_kernel(
             const bool keep = key[g][e] > tau || (key[g][e] == tau && g * 256 + e <= mine_last);   // last < V: no column beyond
             kept[s >> 5] |= (keep ? 1u : 0u) << (s & 31);
         }
-    // ---- 5. the draw: every lane among its own kept elements, lowest column first
-    Cand best{-INFINITY, 0x7fffffff};
-    float raw = -INFINITY;
-    for (;;) {
-        int s = -1;
+#include "sample_select_draw.h"
+}
+
+// ---- the nucleus form: top_p < 1, every top-k in 1..V.  The wide kernel's wave, row, normaliser, top-k
+// selection and draw; between the selection and the draw the kept set K shrinks to its nucleus:
+//   a. every resident key becomes the element's weight w = __expf(x - max) for an element of K, 0 outside it and beyond V, held
+//      as the bit pattern of a non-negative float -- whose unsigned order is the float order;
+//   b. G(t) = the sum of the weights whose pattern is >= t: per lane in the fixed order of (g, e), then one wave_sum.  A sum of
+//      non-negative terms, rounded to nearest in a fixed order, does not grow when terms are replaced by 0: G never increases in t,
+//      as computed.  Z = G(1) (every positive weight) and P = top_p * Z, so G(1) >= P;
+//   c. t* = the largest t with G(t) >= P, one bit per round over the 31 value bits -- counted rounds, never data-dependent;
+//   d. kept = pattern >= t*: an element is kept iff the mass strictly above its weight, G(the next pattern), is below P; a
+//      plateau of equal weights is kept or dropped whole, the row's maximum (mass 0 above it) always stays, a weight that
+//      underflowed to 0 never does (t* >= 1).
+// The filter reads the raw logits; the temperature acts in the draw only and the confidence stays the unfiltered softmax's.
+template <int NV4, bool PERIOD = false>
+__global__ __launch_bounds__(THREADS) void sample_nucleus_kernel(
+    const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, int64_t mask_id, int topk, float top_p,
+    float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
+    int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
+    const PmGenParams* __restrict__ gp, int period) {
+#include "sample_select_prologue.h"
+    // ---- a. weights in place of the keys (the value back from its key: orderable() undone)
+    const int mine_last = last - lane * 4;
+    uint32_t wt[NV4][4];
 #pragma unroll
-        for (int w = NW - 1; w >= 0; --w)
-            if (kept[w]) s = w * 32 + __ffs((int)kept[w]) - 1;
-        if (s < 0) break;
+    for (int g = 0; g < NV4; ++g)
 #pragma unroll
-        for (int w = 0; w < NW; ++w)
-            if ((s >> 5) == w) kept[w] &= kept[w] - 1u;
-        const int col = (((s >> 2) * 64 + lane) << 2) + (s & 3);          // < V: step 4 kept no other
-        const float v = lrow[col];
-        const float pv = perturbed(v, col, row, V, rs, noise);
-        if (before(pv, col, best.v, best.i)) { best.v = pv; best.i = col; raw = v; }
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t k = key[g][e];
+            const float v = __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
+            const bool in_k = k > tau || (k == tau && g * 256 + e <= mine_last);             // last < V: no column beyond
+            wt[g][e] = in_k ? __float_as_uint(__expf(v - mx)) : 0u;
+        }
+    // ---- b., c. the mass threshold
+    auto mass_from = [&](uint32_t t) -> float {
+        float m = 0.f;
+#pragma unroll
+        for (int g = 0; g < NV4; ++g)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m += wt[g][e] >= t ? __uint_as_float(wt[g][e]) : 0.f;
+        return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(wave_sum(m))));
+    };
+    const float P = top_p * mass_from(1u);
+    uint32_t ts = 0u;
+#pragma unroll 1
+    for (uint32_t bit = 0x40000000u; bit; bit >>= 1) {
+        const uint32_t trial = ts | bit;
+        if (mass_from(trial) >= P) ts = trial;
     }
-    const Cand win = wave_best(best);
-    const int owner = __builtin_amdgcn_readfirstlane((win.i >> 2) & 63);   // the lane that holds the winner's column
-    raw = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(raw), owner));
-    if (lane == 0) store_outcome(row, true, win.i, expf(raw - mx) / se, ids_in, mask_id, pred_out, ids_out, score_out);
+    ts = max(ts, 1u);                                      // (a row whose sums are NaN finds nothing: still no zero weight, no column >= V)
+    // ---- d. the kept set, one bit per element
+    constexpr int NW = (NV4 * 4 + 31) / 32;
+    uint32_t kept[NW];
+#pragma unroll
+    for (int q = 0; q < NW; ++q) kept[q] = 0u;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int s = g * 4 + e;
+            kept[s >> 5] |= (wt[g][e] >= ts ? 1u : 0u) << (s & 31);
+        }
+#include "sample_select_draw.h"
 }
 
 
@@ -636,6 +606,9 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int p
     const char* who = slots ? "sample_rows_slots" : "sample_rows";
     PM_REQUIRE(logits && ids_in && ids_out && (!slots || src.slots) && (src.kind != PmStepSource::PARAMS || src.gp), "%s: null pointer", who);
     PM_REQUIRE(period >= 0 && !(slots && period), "%s: bad logits row period %d", who, period);
+    PM_TRY(pm_check_top_p(who, src.top_p));
+    const bool nucleus = src.top_p < 1.f;
+    PM_REQUIRE(!(slots && nucleus), "%s: top_p=%g: the per-image records carry no top_p (the nucleus filter is the batch forms')", who, (double)src.top_p);
     PM_REQUIRE(M > 0 && V > 0 && V % 4 == 0 && ldl % 4 == 0 && ldl >= V, "%s: bad shape M=%d V=%d ldl=%d", who, M, V, ldl);
     if (slots) {                                           // the block-statistics kernel only: what every decode-loop launch runs
         PM_REQUIRE(V % 64 == 0 && V <= 16384, "sample_rows_slots: V=%d must be a multiple of 64, at most 16384", V);
@@ -650,8 +623,17 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int p
     // Which kernel runs depends on (V, topk) ONLY -- never on whether statistics were handed in: the two differ in the last bits
     // of the confidence (sample_rows_kernel); above top-k = 8 statistics are ignored.  The records of a slots launch carry
     // top-k <= 8 (checked where they are staged).
+    // top_p < 1: the nucleus kernel for EVERY top-k -- the choice is a function of (V, topk, top_p < 1).
     static const int g_tiles = pm_dev_knob("PMHIP_SAMPLE_TILES", 1);     // 0: the one-read row kernel everywhere (A/B)
-    if (slots || (g_tiles && src.topk <= KT_MAX && V % 64 == 0)) {
+    if (nucleus) {
+        pick<1, 4, 32, 64>(V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64, [&](auto NV4) {
+            pick<0, 1>(period != 0, [&](auto PER) {
+                hipLaunchKernelGGL((sample_nucleus_kernel<NV4(), PER() == 1>), grid, block, 0, s, logits, ldl, ids_in, mask_id, src.topk,
+                                   src.top_p, src.temperature, noise, src.seed, src.step, src.row_base, pred_out, ids_out, score_out, M, V,
+                                   src.gp, period);
+            });
+        });
+    } else if (slots || (g_tiles && src.topk <= KT_MAX && V % 64 == 0)) {
         const float2* st = reinterpret_cast<const float2*>(block_stats);
         pick<1, 2, 4>(V <= 4096 ? 1 : V <= 8192 ? 2 : 4, [&](auto NB2) {
             pick<0, 1>(st == nullptr, [&](auto DENSE) {
@@ -686,6 +668,14 @@ extern "C" int pmhip_sample_rows(const float* logits, int ldl, const int64_t* id
                           PmStepSource::batch(topk, temperature, 0, seed, step, row_base), stream);
 }
 
+// the same step with a nucleus filter behind the top-k (top_p == 1: exactly pmhip_sample_rows)
+extern "C" int pmhip_sample_rows_nucleus(const float* logits, int ldl, const int64_t* ids_in, int64_t mask_id, int topk, float top_p,
+                                         float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base,
+                                         int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream) {
+    return pm_sample_rows(logits, ldl, nullptr, 0, ids_in, mask_id, noise, pred_out, ids_out, score_out, M, V,
+                          PmStepSource::batch(topk, temperature, 0, seed, step, row_base).with_top_p(top_p), stream);
+}
+
 // the same step with the block statistics pmhip_gemm_softmax_stats (or pmhip_guidance_combine_stats) left behind: [M][V/64][2]
 extern "C" int pmhip_sample_rows_stats(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
                                        int topk, float temperature, const float* noise, uint64_t seed, uint32_t step,
@@ -703,6 +693,11 @@ extern "C" int pmhip_sample_rows_slots(const float* logits, int ldl, const float
                                        int M, int V, pmhip_stream stream) {
     return pm_sample_rows(logits, ldl, block_stats, 0, ids_in, mask_id, nullptr, pred_out, ids_out, score_out, M, V,
                           PmStepSource::per_image(slots, tokens), stream);
+}
+
+int pm_check_top_p(const char* who, float p) {
+    PM_REQUIRE(std::isfinite(p) && p > 0.f && p <= 1.f, "%s: top_p=%g must be finite and in (0, 1]", who, (double)p);
+    return PMHIP_OK;
 }
 
 int pm_check_choice_t(const char* who, float t) {

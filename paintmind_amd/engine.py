@@ -315,16 +315,20 @@ class S2Engine:
         return logits
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
-               want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None):
+               want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None,
+               top_p=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
         topk: an integer in 1..n_embed (Pipeline resolves its topk=None to n_embed before it gets here).
         guidance_scale (None = the reference's step): sample from uncond + scale * (cond - uncond), two tower passes.
         context_lens (None = every image attends to its whole context): image b's cross-attention sees context rows
         [0, context_lens[b]) only (pmhip_pipeline_sample_lens).
         choice_temperature (None or 0 = the reference's step): THIS step's choice temperature -- the re-masking sorts by MaskGIT's
-        perturbed confidence (pmhip_pipeline_sample_choice); choice_noise fp32 [B,N]: its uniforms (default: Philox)."""
+        perturbed confidence (pmhip_pipeline_sample_choice); choice_noise fp32 [B,N]: its uniforms (default: Philox).
+        top_p (None or 1 = no nucleus filter: the calls above): the token draw's nucleus mass, 0 < top_p <= 1
+        (pmhip_pipeline_sample_nucleus)."""
         B = ids.shape[0]
         ct = ops.choice_t(choice_temperature)
+        nucleus = ops.nucleus_p(top_p)
         context, L = self._ctx(context)
         lens = self._lens(context_lens, context, B, L)
         img = vq_engine._new_img(B) if want_img else None
@@ -340,7 +344,11 @@ class S2Engine:
             if tuple(choice_noise.shape) != (B, self.tokens):
                 raise ValueError(f"choice_noise must be [B, {self.tokens}]")
         with torch.cuda.device(self.device):
-            if ct != 0.0:
+            if nucleus < 1.0:
+                check(self.lib.pmhip_pipeline_sample_nucleus(*args[:6], lens, *args[6:], int(guidance_scale is not None),
+                                                             float(guidance_scale or 0.0), ct, _p(choice_noise), nucleus,
+                                                             stream_ptr(self.device)), "pmhip_pipeline_sample_nucleus")
+            elif ct != 0.0:
                 check(self.lib.pmhip_pipeline_sample_choice(*args[:6], lens, *args[6:], int(guidance_scale is not None),
                                                             float(guidance_scale or 0.0), ct, _p(choice_noise), stream_ptr(self.device)),
                       "pmhip_pipeline_sample_choice")
@@ -412,7 +420,7 @@ class S2Engine:
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
                  host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
-                 choice_temps=None):
+                 choice_temps=None, top_p=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
 
         topk: an integer in 1..n_embed, the same for every step; part of the key of a captured graph.
@@ -425,9 +433,12 @@ class S2Engine:
         from_mask: the loop starts from the all-mask state (PMHIP_GENERATE_FROM_MASK): the native call writes that state itself --
         what `ids` holds on entry is ignored -- and an unconditional loop samples its step 0 from the handle's shared logits.
         context_lens: per-image context lengths (pmhip_pipeline_generate_lens); the captured graphs read them from device memory.
-        choice_temps: one choice temperature per step (pmhip_pipeline_generate_choice); None or all zero is the loop without."""
+        choice_temps: one choice temperature per step (pmhip_pipeline_generate_choice); None or all zero is the loop without.
+        top_p (None or 1 = no nucleus filter: the calls above): every step's nucleus mass, 0 < top_p <= 1
+        (pmhip_pipeline_generate_nucleus); below 1 part of the key of a captured graph, like topk."""
         B = ids.shape[0]
         T = len(temps)
+        nucleus = ops.nucleus_p(top_p)
         if choice_temps is not None:
             if len(choice_temps) != T:
                 raise ValueError(f"generate: {len(choice_temps)} choice temperatures for {T} steps")
@@ -458,7 +469,11 @@ class S2Engine:
                 (_lib.GENERATE_FROM_MASK if from_mask else 0),
                 stream_ptr(self.device), host_ptr, host_stride, copy_stream)
         with torch.cuda.device(self.device):
-            if choice_temps is not None:
+            if nucleus < 1.0:
+                check(self.lib.pmhip_pipeline_generate_nucleus(*args[:6], lens, *args[6:], int(guidance_scale is not None),
+                                                               float(guidance_scale or 0.0), choice_temps, nucleus),
+                      "pmhip_pipeline_generate_nucleus")
+            elif choice_temps is not None:
                 check(self.lib.pmhip_pipeline_generate_choice(*args[:6], lens, *args[6:], int(guidance_scale is not None),
                                                               float(guidance_scale or 0.0), choice_temps), "pmhip_pipeline_generate_choice")
             elif lens is not None:

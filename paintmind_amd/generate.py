@@ -61,6 +61,20 @@ def choice_keys(scores, t, u):
     return torch.where(scores < 0, scores, -(conf + torch.tensor(t, dtype=scores.dtype) * gumbel))
 
 
+def nucleus_keep(val, top_p):
+    """the nucleus rule of the plain-torch branch on the top-k VALUES val [..., k], sorted descending as
+    torch.topk returns them -> bool [..., k]: with w = exp(val - max), Z = sum w and P = top_p * Z an element is kept iff the
+    mass of the elements whose weight is strictly above its own is below P -- a plateau of equal weights whole or not at all, the
+    maximum always, a weight of 0 never.  float64: the kernels' fp32 sums decide elements within 1e-4 Z of P on their own."""
+    w = torch.exp((val - val[..., :1]).double())
+    c = w.cumsum(-1)
+    before = c - w                                          # the mass in front of every element
+    start = torch.ones_like(w, dtype=torch.bool)
+    start[..., 1:] = w[..., 1:] != w[..., :-1]
+    above = torch.where(start, before, torch.zeros_like(before)).cummax(-1).values     # ... in front of its plateau
+    return (above < top_p * c[..., -1:]) & (w > 0)
+
+
 class _PinnedPool:
     """Pinned host buffers for the images generate() returns.  Page-locking a fresh 400 MB allocation costs ~35 ms (more
     than the copies themselves), so buffers are kept and handed out again -- but only once nothing the caller received
@@ -272,8 +286,12 @@ class Pipeline(nn.Module):
 
     @torch.no_grad()
     def sample(self, ids, mask_ratio, text=None, topk=1, temperature=1, noise=None, seed=None, step=0, image_base=0,
-               guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None):
+               guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None, top_p=None):
         """One MaskGIT step (generate.py:159-181) -> (ids', img).
+
+        ``top_p`` (extension; None or 1.0 = no nucleus filter, the step as without the keyword): 0 < top_p <= 1.  Behind the
+        top-k, only the elements whose probability mass strictly above them is below ``top_p`` of the top-k's mass are drawn
+        from.  Like ``topk`` it reads the raw logits: the temperature acts in the draw only.
 
         ``topk``: 1..n_embed like the reference's ``top_k(logits, k)``, on the GPU as on the CPU (above
         64 the selection kernel); ``None`` = no filter, i.e. n_embed.
@@ -300,19 +318,20 @@ class Pipeline(nn.Module):
         """
         nm = num_token_masked(mask_ratio, self.num_tokens)
         ct = ops.choice_t(choice_temperature)
+        top_p = ops.nucleus_p(top_p)
         topk = self._topk(topk)
         if guidance_scale is not None and text is None:
             raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
         lens = self._lens(context_lens, text, ids.shape[0])
         if self._on_cpu():
-            return self._sample_cpu(ids, nm, text, topk, temperature, noise, seed, guidance_scale, lens, ct, choice_noise)
+            return self._sample_cpu(ids, nm, text, topk, temperature, noise, seed, guidance_scale, lens, ct, choice_noise, top_p)
         if seed is None:
             seed = _draw_seed()
         eng = self.engine()
         ids = ids.to(eng.device, torch.int64).clone().contiguous()
         ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, topk, temperature, nm, noise=noise, seed=seed, step=step,
                                     image_base=image_base, want_img=True, guidance_scale=guidance_scale, context_lens=lens,
-                                    choice_temperature=ct, choice_noise=choice_noise)
+                                    choice_temperature=ct, choice_noise=choice_noise, top_p=top_p)
         return ids, img
 
     def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale, context_lens=None):
@@ -335,17 +354,19 @@ class Pipeline(nn.Module):
         return ids, img
 
     def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None, choice_t=0.0,
-                    choice_noise=None):
+                    choice_noise=None, top_p=1.0):
         """generate.py:159-181 in plain torch for a pipeline that lives on the CPU.  The noise is drawn from the torch CPU
         generator like the reference's (`seed` re-seeds a private generator; `noise` overrides it); ties in top-k / argmax
         follow torch.  choice_t != 0: the re-masking sorts by choice_keys; its uniforms are `choice_noise`, or drawn behind the
-        token noise from the same generator."""
+        token noise from the same generator.  top_p < 1: of the top-k values only those nucleus_keep keeps."""
         tok = self.ids2tokens(ids)
         logits = self.tokens2logits(tok, text, context_lens)
         if guidance_scale is not None:
             uncond = self.tokens2logits(tok, None)
             logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(guidance_scale)))
         val, ind = logits.topk(topk, dim=-1)
+        if top_p < 1.0:
+            val = val.masked_fill(~nucleus_keep(val, top_p), float("-inf"))
         filtered = torch.full_like(logits, float("-inf")).scatter_(2, ind, val)
         g = None if seed is None else torch.Generator().manual_seed(int(seed) & (2 ** 63 - 1))
         if noise is None:
@@ -365,7 +386,7 @@ class Pipeline(nn.Module):
         return ids, img
 
     def _generate_cpu(self, text, context, timesteps, temperature, topk, save_interval, seed, return_ids, context_lens=None,
-                      choice_temperature=None):
+                      choice_temperature=None, top_p=1.0):
         B = len(text)
         ctemps = choice_schedule(timesteps, choice_temperature)
         topk = self._topk(topk)
@@ -375,7 +396,7 @@ class Pipeline(nn.Module):
             masked_r = mask_schedule((step + 1) / timesteps)
             ids, img = self._sample_cpu(ids, num_token_masked(masked_r, self.num_tokens), context, topk,
                                         temperature * (1 - step / timesteps), None, None if seed is None else seed + step,
-                                        None, context_lens, ctemps[step] if ctemps else 0.0)
+                                        None, context_lens, ctemps[step] if ctemps else 0.0, None, top_p)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
@@ -424,7 +445,8 @@ class Pipeline(nn.Module):
                              max_context_len=max_context_len)
 
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
-                     join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None):
+                     join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None,
+                     top_p=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
 
         streams > 1 (or a tuple of micro-batch sizes): the batch is cut into contiguous micro-batches that run CONCURRENTLY on separate HIP
@@ -445,9 +467,12 @@ class Pipeline(nn.Module):
         sees rows [0, context_lens[b]) only.  Every lane takes the slice of its micro-batch.
         choice_temperature (None or 0: the reference's deterministic re-masking): MaskGIT's base choice temperature, annealed over the
         loop (choice_schedule); the noise is keyed by the global image index like the token draw's, so lanes change nothing.
-        topk: 1..n_embed, or None = no filter (n_embed); part of the key of a captured graph."""
+        topk: 1..n_embed, or None = no filter (n_embed); part of the key of a captured graph.
+        top_p (None or 1.0: no nucleus filter): every step's nucleus mass, 0 < top_p <= 1 (see ``sample``); one value for the batch,
+        so every lane takes it as it is; below 1 part of the key of a captured graph."""
         lens = self._lens(context_lens, context, B)
         ctemps = choice_schedule(timesteps, choice_temperature)
+        top_p = ops.nucleus_p(top_p)
         topk = self._topk(topk)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
@@ -475,7 +500,8 @@ class Pipeline(nn.Module):
             return eng.generate(self.vqgan.engine(), ids, context, temps, nmask, decode_flags, topk, seed=seed,
                                 image_base=image_base, use_graph=use_graph,
                                 host=None if host is None else (host[0], 0, host[1][0]), want_device_imgs=host is None,
-                                guidance_scale=guidance_scale, from_mask=ids0 is None, context_lens=lens, choice_temps=ctemps)
+                                guidance_scale=guidance_scale, from_mask=ids0 is None, context_lens=lens, choice_temps=ctemps,
+                                top_p=top_p)
         from .dist import shard_range
         cur = torch.cuda.current_stream(eng.device)
         if wait_current:
@@ -493,7 +519,7 @@ class Pipeline(nn.Module):
                                        use_graph=use_graph, host=None if host is None else (host[0], lo, host[1][i]),
                                        want_device_imgs=host is None, guidance_scale=guidance_scale, concurrent_lanes=True,
                                        from_mask=True,          # lanes exist for ids0 None only (checked above)
-                                       context_lens=None if lens is None else lens[lo:hi], choice_temps=ctemps)
+                                       context_lens=None if lens is None else lens[lo:hi], choice_temps=ctemps, top_p=top_p)
             return ids, imgs, st
 
         lanes = self._lanes(streams)
@@ -534,7 +560,7 @@ class Pipeline(nn.Module):
 
     def generate(self, text, timesteps=18, temperature=1.0, topk=5, save_interval=2, seed=None, image_base=0,
                  return_ids=False, keep_on_device=False, use_graph=None, streams=None, guidance_scale=None, mask_padding=False,
-                 context_lens=None, choice_temperature=None):
+                 context_lens=None, choice_temperature=None, top_p=None):
         """Full decode loop (generate.py:183-198): list of (B,3,H,W) CPU tensors for steps % save_interval == 0.
 
         The call is the fast path by default: the loop replays captured hipGraphs (first call eager, second call captures),
@@ -565,9 +591,15 @@ class Pipeline(nn.Module):
 
         choice_temperature (extension; None or 0 = the reference's behaviour: the least confident tokens are re-masked, a
         deterministic choice): MaskGIT's choice temperature (its default is 4.5).  Step s of T re-masks by ``log p +
-        choice_temperature * (1 - (s + 1) / T) * gumbel``; the last step's noise is exactly zero."""
+        choice_temperature * (1 - (s + 1) / T) * gumbel``; the last step's noise is exactly zero.
+
+        top_p (extension; None or 1.0 = no nucleus filter): 0 < top_p <= 1, the same for every step -- behind the top-k, the
+        tokens are drawn from the smallest set of classes that holds ``top_p`` of the top-k's probability mass (``sample`` has
+        the exact rule).  A mass cut follows the model from its flat early steps to its peaked late ones, which no fixed
+        ``topk`` can; with ``topk=None`` it is the only filter."""
         B = len(text)
         choice_schedule(timesteps, choice_temperature)        # the value is checked before anything runs
+        top_p = ops.nucleus_p(top_p)
         if mask_padding and context_lens is None:
             context, context_lens = self.text_model(text, return_lens=True)
         else:
@@ -578,8 +610,9 @@ class Pipeline(nn.Module):
         if self._on_cpu():
             if guidance_scale is not None:
                 return self._generate_guided_cpu(context, B, timesteps, temperature, topk, save_interval, seed, return_ids, guidance_scale,
-                                                 lens, choice_temperature)
-            return self._generate_cpu(text, context, timesteps, temperature, topk, save_interval, seed, return_ids, lens, choice_temperature)
+                                                 lens, choice_temperature, top_p)
+            return self._generate_cpu(text, context, timesteps, temperature, topk, save_interval, seed, return_ids, lens, choice_temperature,
+                                      top_p)
         eng = self.engine()
         if seed is None:
             seed = _draw_seed()
@@ -602,7 +635,7 @@ class Pipeline(nn.Module):
         if keep_on_device or n_dec == 0:
             ids, imgs = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
                                           use_graph=use_graph, streams=streams, guidance_scale=guidance_scale, context_lens=lens,
-                                          choice_temperature=choice_temperature)
+                                          choice_temperature=choice_temperature, top_p=top_p)
             out = [] if imgs is None else list(imgs)
             return (out, ids) if return_ids else out
         vq = self.vqgan.engine()
@@ -617,7 +650,7 @@ class Pipeline(nn.Module):
         try:
             ids, _ = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
                                        use_graph=use_graph, streams=streams, host=(host, cs), guidance_scale=guidance_scale,
-                                       context_lens=lens, choice_temperature=choice_temperature)
+                                       context_lens=lens, choice_temperature=choice_temperature, top_p=top_p)
         except BaseException:
             # a lane failed: whatever the other lanes queued may still be writing into `host`; drain it, and never hand
             # this buffer out again
@@ -638,7 +671,7 @@ class Pipeline(nn.Module):
 
     @torch.no_grad()
     def _generate_guided_cpu(self, context, B, timesteps, temperature, topk, save_interval, seed, return_ids, scale, context_lens=None,
-                             choice_temperature=None):
+                             choice_temperature=None, top_p=1.0):
         """generate.py:183-198 with guided steps (see `sample`) for a pipeline that lives on the CPU; same return structure.
         (On the GPU the guided loop is the native one: pmhip_pipeline_generate_guided, graph-captured and lane-able.)"""
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
@@ -648,14 +681,16 @@ class Pipeline(nn.Module):
         for step in range(timesteps):
             nm = num_token_masked(mask_schedule((step + 1) / timesteps), self.num_tokens)
             ids, img = self._sample_cpu(ids, nm, context, topk, temperature * (1 - step / timesteps), None,
-                                        None if seed is None else seed + step, scale, context_lens, ctemps[step] if ctemps else 0.0)
+                                        None if seed is None else seed + step, scale, context_lens, ctemps[step] if ctemps else 0.0,
+                                        None, top_p)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
 
     def _region_loop(self, img, coord, text, timesteps, topk, temperature, keep_inside, seed=None, return_ids=False,
-                     choice_temperature=None):
+                     choice_temperature=None, top_p=None):
         choice_schedule(timesteps, choice_temperature)        # the value is checked before anything runs
+        top_p = ops.nucleus_p(top_p)
         if seed is None:
             seed = _draw_seed()                 # one stream per call; the step index separates the steps
         z, ids, text = self.to_latent(img, text)
@@ -674,11 +709,11 @@ class Pipeline(nn.Module):
             # these start ids, decoding only the last step -- bit-identical to the per-step composition below (tests/test_gpu_model.py)
             use_graph = os.environ.get("PMHIP_GENERATE_GRAPH", "1") != "0"
             ids, imgs = self.generate_ids(text, ids.shape[0], timesteps, temperature, topk, [False] * (timesteps - 1) + [True], seed,
-                                          use_graph=use_graph, streams=1, ids0=ids, choice_temperature=choice_temperature)
+                                          use_graph=use_graph, streams=1, ids0=ids, choice_temperature=choice_temperature, top_p=top_p)
             return (imgs[0], ids) if return_ids else imgs[0]
-        return self._region_steps(ids, text, timesteps, topk, temperature, seed, return_ids, choice_temperature)
+        return self._region_steps(ids, text, timesteps, topk, temperature, seed, return_ids, choice_temperature, top_p)
 
-    def _region_steps(self, ids, text, timesteps, topk, temperature, seed, return_ids=False, choice_temperature=None):
+    def _region_steps(self, ids, text, timesteps, topk, temperature, seed, return_ids=False, choice_temperature=None, top_p=None):
         """the region loop as the reference writes it: one sample() per step (generate.py:211-216,230-235)"""
         out = None
         ctemps = choice_schedule(timesteps, choice_temperature)
@@ -687,19 +722,21 @@ class Pipeline(nn.Module):
             masked_r = mask_schedule(progress)
             cur_temp = temperature * (1 - step / timesteps)
             ids, out = self.sample(ids, mask_ratio=masked_r, text=text, topk=topk, temperature=cur_temp, seed=seed, step=step,
-                                   choice_temperature=ctemps[step] if ctemps else None)
+                                   choice_temperature=ctemps[step] if ctemps else None, top_p=top_p)
         return (out, ids) if return_ids else out
 
     @torch.no_grad()
-    def inpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None):
+    def inpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None,
+                top_p=None):
         """re-generate the rectangle coord=(x,y,h,w) in pixels (generate.py:200-217).  choice_temperature: as in ``generate`` (the
         kept region's ids are given: the noise never prefers one of them to a position the loop took).  topk: 1..n_embed, or
-        None = no filter, as in ``generate``."""
+        None = no filter, as in ``generate``.  top_p: the nucleus mass, as in ``generate``."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=False, seed=seed,
-                                 return_ids=return_ids, choice_temperature=choice_temperature)
+                                 return_ids=return_ids, choice_temperature=choice_temperature, top_p=top_p)
 
     @torch.no_grad()
-    def outpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None):
-        """keep the rectangle, re-generate everything else (generate.py:219-236).  choice_temperature, topk: as in ``inpaint``."""
+    def outpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None,
+                 top_p=None):
+        """keep the rectangle, re-generate everything else (generate.py:219-236).  choice_temperature, topk, top_p: as in ``inpaint``."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=True, seed=seed,
-                                 return_ids=return_ids, choice_temperature=choice_temperature)
+                                 return_ids=return_ids, choice_temperature=choice_temperature, top_p=top_p)

@@ -480,18 +480,36 @@ def vq_quantize(z, en, sq, beta=0.25):
     return z_out, idx, loss
 
 
-def sample_rows(logits, ids, mask_id, topk, temperature, noise=None, seed=0, step=0, row_base=0, block_stats=None):
+def nucleus_p(value, what="top_p"):
+    """a nucleus mass (None = 1 = no filter) -> a float, checked as the native entries check it: finite, 0 < top_p <= 1"""
+    p = 1.0 if value is None else float(value)
+    if not (math.isfinite(p) and 0.0 < p <= 1.0):
+        raise ValueError(f"{what}: {value} must be finite and in (0, 1]")
+    return p
+
+
+def sample_rows(logits, ids, mask_id, topk, temperature, noise=None, seed=0, step=0, row_base=0, block_stats=None, top_p=None):
     """logits fp32 [M,V], ids int64 [M] -> (pred [M], merged ids [M], score [M]).
+    top_p: None or 1.0 = no nucleus filter (the kernels below, as without the keyword); 0 < top_p < 1, finite (else ValueError):
+    of the top-k elements only those whose mass strictly above them is below top_p of the top-k's mass are drawn from -- the
+    nucleus kernel for every topk (pmhip_sample_rows_nucleus), block_stats ignored.
     topk: 1..V.  Which kernel serves it depends on (V, topk) only: up to 8 (V % 64 == 0) the block-statistics kernel, up to 64 the
     row kernel with one candidate per lane, above 64 the selection kernel; block_stats are ignored above 8.
     block_stats fp32 [M, V/64, 2] (gemm_softmax_stats / guidance_combine(with_stats=True)): the kernel reads them and the top-k
     blocks of a row instead of the row; same bits as without."""
+    nucleus = nucleus_p(top_p)
     dev = _dev(logits, ids, noise)
     lib = _lib.load()
     M, V = logits.shape
     pred = torch.empty(M, device=dev, dtype=torch.int64)
     ids_out = torch.empty(M, device=dev, dtype=torch.int64)
     score = torch.empty(M, device=dev, dtype=torch.float32)
+    if nucleus < 1.0:
+        with torch.cuda.device(dev):
+            check(lib.pmhip_sample_rows_nucleus(_p(logits), logits.stride(0), _p(ids), int(mask_id), int(topk), nucleus, float(temperature),
+                                                _p(noise), int(seed), int(step), int(row_base), _p(pred), _p(ids_out), _p(score),
+                                                M, V, stream_ptr(dev)), "pmhip_sample_rows_nucleus")
+        return pred, ids_out, score
     if block_stats is not None:
         if (block_stats.dtype != torch.float32 or not block_stats.is_contiguous() or block_stats.device != logits.device
                 or tuple(block_stats.shape) != (M, V // 64, 2) or V % 64):
