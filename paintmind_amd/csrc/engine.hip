@@ -1154,9 +1154,20 @@ extern "C" int pmhip_s2_forward_lens(pmhip_s2* h, const float* tokens, const flo
     return s2_forward_impl("s2_forward_lens", h, tokens, context, L, B, ctx_lens_host, logits_out, stream);
 }
 
-static int pipeline_sample_impl(const char* who, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
-                                const int32_t* ctx_lens_host, const Step& st, float* img_out, int64_t* pred_out, float* score_out,
-                                pmhip_stream stream) {
+// The sample family's one builder: the argument list of pmhip_pipeline_sample_nucleus, the widest entry, -> the Step and the name
+// the messages carry.  A narrower entry passes the neutral values (include/pmhip.h) and `narrow`, the name its messages carry when
+// neither a nucleus mass nor a choice temperature is in play: its own, or the *_lens entry's for the two entries above that one.
+static int pipeline_sample_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
+                                uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out, float* score_out, int guided,
+                                float guidance_scale, float choice_t, const float* choice_noise, float top_p, pmhip_stream stream) {
+    PM_TRY(pm_check_top_p("pipeline_sample_nucleus", top_p));
+    const char* wide = top_p != 1.f ? "pipeline_sample_nucleus" : "pipeline_sample_choice";
+    PM_TRY(pm_check_choice_t(wide, choice_t));
+    const char* who = top_p != 1.f || choice_t != 0.f ? wide : narrow;
+    Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
+    if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }     // 0: no given uniforms to ignore
+    st.top_p = top_p;
     PM_REQUIRE(s2 && ids && B > 0, "%s: bad arguments", who);
     PM_REQUIRE(!st.guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
@@ -1170,39 +1181,34 @@ extern "C" int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids
                                      int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                      uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                      float* score_out, pmhip_stream stream) {
-    return pipeline_sample_impl("pipeline_sample", s2, vq, ids, context, L, B, nullptr,
-                                Step{topk, temperature, num_mask, noise, seed, step, image_base}, img_out, pred_out, score_out, stream);
+    return pipeline_sample_call("pipeline_sample", s2, vq, ids, context, L, B, nullptr, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, 0, 0.f, 0.f, nullptr, 1.f, stream);
 }
 
 extern "C" int pmhip_pipeline_sample_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                             int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                             uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                             float* score_out, float guidance_scale, pmhip_stream stream) {
-    return pipeline_sample_impl("pipeline_sample_guided", s2, vq, ids, context, L, B, nullptr,
-                                Step{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, &guidance_scale}, img_out,
-                                pred_out, score_out, stream);
+    return pipeline_sample_call("pipeline_sample_guided", s2, vq, ids, context, L, B, nullptr, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, 1, guidance_scale, 0.f, nullptr, 1.f, stream);
 }
 
 extern "C" int pmhip_pipeline_sample_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                           const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
                                           uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                           float* score_out, int guided, float guidance_scale, pmhip_stream stream) {
-    return pipeline_sample_impl("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host,
-                                Step{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr},
-                                img_out, pred_out, score_out, stream);
+    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, guided, guidance_scale, 0.f, nullptr, 1.f, stream);
 }
 
-// choice_t == 0 (and no given uniforms to ignore): exactly pmhip_pipeline_sample_lens
+// choice_t == 0: exactly pmhip_pipeline_sample_lens
 extern "C" int pmhip_pipeline_sample_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                             const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
                                             uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                             float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
                                             pmhip_stream stream) {
-    PM_TRY(pm_check_choice_t("pipeline_sample_choice", choice_t));
-    Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
-    if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }
-    return pipeline_sample_impl(choice_t != 0.f ? "pipeline_sample_choice" : "pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, st,
-                                img_out, pred_out, score_out, stream);
+    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, 1.f, stream);
 }
 
 // top_p == 1: exactly pmhip_pipeline_sample_choice
@@ -1211,15 +1217,8 @@ extern "C" int pmhip_pipeline_sample_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int6
                                              uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                              float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
                                              float top_p, pmhip_stream stream) {
-    PM_TRY(pm_check_top_p("pipeline_sample_nucleus", top_p));
-    if (top_p == 1.f)
-        return pmhip_pipeline_sample_choice(s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step, image_base,
-                                            img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, stream);
-    PM_TRY(pm_check_choice_t("pipeline_sample_nucleus", choice_t));
-    Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
-    if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }
-    st.top_p = top_p;
-    return pipeline_sample_impl("pipeline_sample_nucleus", s2, vq, ids, context, L, B, ctx_lens_host, st, img_out, pred_out, score_out, stream);
+    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream);
 }
 
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
@@ -1230,7 +1229,7 @@ static bool direct_dispatch_off() {
 
 namespace {
 
-// the arguments of pmhip_pipeline_generate(_guided), include/pmhip.h
+// the arguments of pmhip_pipeline_generate_nucleus, include/pmhip.h, as pipeline_generate_call (below) fills them in
 struct GenCall {
     pmhip_s2* s2; pmhip_vqgan* vq; int64_t* ids; const float* context; int L, B, T;
     const float* temps_host; const int* nmask_host; const unsigned char* decode_host;
@@ -1311,7 +1310,6 @@ int pipeline_generate(const GenCall& c) {
     PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && c.nmask_host, "pipeline_generate: bad arguments");
     PM_REQUIRE(!c.guidance || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
     PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
-    PM_TRY(pm_check_top_p(c.who, c.top_p));
     // the choice temperatures, checked before anything is launched; all zero IS the loop without them (same kernels, same graphs)
     bool choice = false;
     for (int t = 0; c.ctemps && t < T; ++t) {
@@ -1476,13 +1474,28 @@ int pipeline_generate(const GenCall& c) {
 
 }  // namespace
 
+// The generate family's one builder: the argument list of pmhip_pipeline_generate_nucleus, the widest entry, -> the GenCall and the
+// name its messages carry.  A narrower entry passes the neutral values (include/pmhip.h) and `narrow`, the name in use when neither
+// a nucleus mass nor choice temperatures are in play: its own, or the *_lens entry's for the two entries above that one.
+static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                  const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                  const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base, float* imgs_out,
+                                  int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride, pmhip_stream copy_stream,
+                                  int guided, float guidance_scale, const float* ctemps_host, float top_p) {
+    PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
+    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
+                                     use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
+                                     top_p != 1.f ? "pipeline_generate_nucleus" : ctemps_host ? "pipeline_generate_choice" : narrow,
+                                     ctemps_host, top_p});
+}
+
 extern "C" int pmhip_pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                        int T, const float* temps_host, const int* nmask_host,
                                        const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                        float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
                                        size_t host_stride, pmhip_stream copy_stream) {
-    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-                                     use_graph, stream, imgs_host, host_stride, copy_stream});
+    return pipeline_generate_call("pipeline_generate", s2, vq, ids, context, L, B, nullptr, T, temps_host, nmask_host, decode_host, topk, seed,
+                                  image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, 0, 0.f, nullptr, 1.f);
 }
 
 extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1490,8 +1503,8 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                               float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
                                               size_t host_stride, pmhip_stream copy_stream, float guidance_scale) {
-    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-                                     use_graph, stream, imgs_host, host_stride, copy_stream, &guidance_scale});
+    return pipeline_generate_call("pipeline_generate", s2, vq, ids, context, L, B, nullptr, T, temps_host, nmask_host, decode_host, topk, seed,
+                                  image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, 1, guidance_scale, nullptr, 1.f);
 }
 
 extern "C" int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1499,9 +1512,9 @@ extern "C" int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64
                                             const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                             float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
                                             pmhip_stream copy_stream, int guided, float guidance_scale) {
-    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-                                     use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
-                                     "pipeline_generate_lens"});
+    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
+                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                  guidance_scale, nullptr, 1.f);
 }
 
 extern "C" int pmhip_pipeline_generate_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1509,11 +1522,9 @@ extern "C" int pmhip_pipeline_generate_choice(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                               float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
                                               pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host) {
-    GenCall c{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-              use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
-              ctemps_host ? "pipeline_generate_choice" : "pipeline_generate_lens"};
-    c.ctemps = ctemps_host;
-    return pipeline_generate(c);
+    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
+                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                  guidance_scale, ctemps_host, 1.f);
 }
 
 // top_p == 1: exactly pmhip_pipeline_generate_choice
@@ -1523,17 +1534,9 @@ extern "C" int pmhip_pipeline_generate_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, in
                                                float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
                                                pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
                                                float top_p) {
-    PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
-    if (top_p == 1.f)
-        return pmhip_pipeline_generate_choice(s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host, topk, seed,
-                                              image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                              guidance_scale, ctemps_host);
-    GenCall c{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-              use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
-              "pipeline_generate_nucleus"};
-    c.ctemps = ctemps_host;
-    c.top_p = top_p;
-    return pipeline_generate(c);
+    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
+                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                  guidance_scale, ctemps_host, top_p);
 }
 
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged
@@ -1545,9 +1548,12 @@ extern "C" int pmhip_pipeline_generate_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, in
 // tail) has a graph of its own; which rows the combination touches is decided on the device, from the staged records.
 // ctx_lens_host (pmhip_pipeline_step_slots_lens; NULL otherwise): per-image context lengths, staged by EVERY call -- also under
 // PMHIP_SLOTS_KEEP_CONTEXT, where the kept cross K/V serve whatever lengths this call brings.
-static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
-                           const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream,
-                           const int32_t* ctx_lens_host = nullptr, const float* choice_host = nullptr) {
+// The slots family's one builder: the argument list of pmhip_pipeline_step_slots_choice, the widest entry, -> the Step and the name
+// the messages carry: `narrow` (a narrower entry's own name, or the *_lens entry's for the widest) unless choice temperatures came.
+static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                           const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host, int flags,
+                           int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    const char* who = choice_host ? "pipeline_step_slots_choice" : narrow;
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0), L, B));
     const auto& c = s2->cfg;
@@ -1635,28 +1641,29 @@ static int step_slots_impl(const char* who, pmhip_s2* s2, int64_t* ids, const fl
 
 extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
                                          int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_impl("pipeline_step_slots", s2, ids, context, L, B, slots_host, nullptr, flags, pred_out, score_out, stream);
+    return step_slots_call("pipeline_step_slots", s2, ids, context, L, B, nullptr, slots_host, nullptr, nullptr, flags, pred_out, score_out, stream);
 }
 
 extern "C" int pmhip_pipeline_step_slots_guided(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
                                                 const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out,
                                                 pmhip_stream stream) {
-    return step_slots_impl("pipeline_step_slots_guided", s2, ids, context, L, B, slots_host, guides_host, flags, pred_out, score_out, stream);
+    return step_slots_call("pipeline_step_slots_guided", s2, ids, context, L, B, nullptr, slots_host, guides_host, nullptr, flags, pred_out,
+                           score_out, stream);
 }
 
 extern "C" int pmhip_pipeline_step_slots_lens(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                                               const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, int flags,
                                               int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_impl("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, guides_host, flags, pred_out, score_out, stream,
-                           ctx_lens_host);
+    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, nullptr, flags, pred_out,
+                           score_out, stream);
 }
 
 // choice_host NULL, or 0 for every active slot: exactly pmhip_pipeline_step_slots_lens
 extern "C" int pmhip_pipeline_step_slots_choice(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                                                 const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
                                                 int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_impl(choice_host ? "pipeline_step_slots_choice" : "pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, guides_host,
-                           flags, pred_out, score_out, stream, ctx_lens_host, choice_host);
+    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
+                           score_out, stream);
 }
 
 // slots steps by tower passes: one (no active slot guided) / two

@@ -306,12 +306,8 @@ class S2Engine:
         lens = self._lens(context_lens, context, B, L)
         logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            if lens is None:
-                check(self.lib.pmhip_s2_forward(self.handle, _p(tokens), _p(context), L, B, _p(logits), stream_ptr(self.device)),
-                      "pmhip_s2_forward")
-            else:
-                check(self.lib.pmhip_s2_forward_lens(self.handle, _p(tokens), _p(context), L, B, lens, _p(logits),
-                                                     stream_ptr(self.device)), "pmhip_s2_forward_lens")
+            check(self.lib.pmhip_s2_forward_lens(self.handle, _p(tokens), _p(context), L, B, lens, _p(logits), stream_ptr(self.device)),
+                  "pmhip_s2_forward_lens")
         return logits
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
@@ -336,31 +332,18 @@ class S2Engine:
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
         if noise is not None:
             noise = noise.to(self.device, torch.float32).contiguous()
-        args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B,
-                int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img),
-                _p(pred), _p(score))
         if choice_noise is not None:
             choice_noise = choice_noise.to(self.device, torch.float32).contiguous()
             if tuple(choice_noise.shape) != (B, self.tokens):
                 raise ValueError(f"choice_noise must be [B, {self.tokens}]")
+        # always the widest entry: an absent option travels as the value with which the header promises the narrower entry's
+        # computation (NULL lengths, guided = 0, choice_t = 0, top_p = 1)
         with torch.cuda.device(self.device):
-            if nucleus < 1.0:
-                check(self.lib.pmhip_pipeline_sample_nucleus(*args[:6], lens, *args[6:], int(guidance_scale is not None),
-                                                             float(guidance_scale or 0.0), ct, _p(choice_noise), nucleus,
-                                                             stream_ptr(self.device)), "pmhip_pipeline_sample_nucleus")
-            elif ct != 0.0:
-                check(self.lib.pmhip_pipeline_sample_choice(*args[:6], lens, *args[6:], int(guidance_scale is not None),
-                                                            float(guidance_scale or 0.0), ct, _p(choice_noise), stream_ptr(self.device)),
-                      "pmhip_pipeline_sample_choice")
-            elif lens is not None:
-                check(self.lib.pmhip_pipeline_sample_lens(*args[:6], lens, *args[6:], int(guidance_scale is not None),
-                                                          float(guidance_scale or 0.0), stream_ptr(self.device)),
-                      "pmhip_pipeline_sample_lens")
-            elif guidance_scale is None:
-                check(self.lib.pmhip_pipeline_sample(*args, stream_ptr(self.device)), "pmhip_pipeline_sample")
-            else:
-                check(self.lib.pmhip_pipeline_sample_guided(*args, float(guidance_scale), stream_ptr(self.device)),
-                      "pmhip_pipeline_sample_guided")
+            check(self.lib.pmhip_pipeline_sample_nucleus(
+                self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens,
+                int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img), _p(pred),
+                _p(score), int(guidance_scale is not None), float(guidance_scale or 0.0), ct, _p(choice_noise if ct else None), nucleus,
+                stream_ptr(self.device)), "pmhip_pipeline_sample_nucleus")
         return ids, img, pred, score
 
     def slots_steps(self):
@@ -403,19 +386,9 @@ class S2Engine:
                 raise ValueError(f"step_slots: {len(choice)} choice temperatures for a batch of {B}")
             vals = [ops.choice_t(v, f"step_slots: slot {b}: choice temperature") for b, v in enumerate(choice)]
             choice = (C.c_float * B)(*vals) if any(vals) else None
-        with torch.cuda.device(self.device):
-            if choice is not None:
-                check(self.lib.pmhip_pipeline_step_slots_choice(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, flags,
-                                                                _p(pred), _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_choice")
-            elif lens is not None:
-                check(self.lib.pmhip_pipeline_step_slots_lens(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, flags, _p(pred),
-                                                              _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_lens")
-            elif guides is None:
-                check(self.lib.pmhip_pipeline_step_slots(self.handle, _p(ids), _p(context), L, B, slots, flags, _p(pred), _p(score),
-                                                         stream_ptr(self.device)), "pmhip_pipeline_step_slots")
-            else:
-                check(self.lib.pmhip_pipeline_step_slots_guided(self.handle, _p(ids), _p(context), L, B, slots, guides, flags, _p(pred),
-                                                                _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_guided")
+        with torch.cuda.device(self.device):      # always the widest entry; NULL lengths, guides or choice: the step without them
+            check(self.lib.pmhip_pipeline_step_slots_choice(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, flags,
+                                                            _p(pred), _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_choice")
         return ids, pred, score
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
@@ -463,24 +436,12 @@ class S2Engine:
         temps_c = (C.c_float * T)(*[float(t) for t in temps])
         nmask_c = (C.c_int * T)(*[int(n) for n in nmask])
         dec_c = (C.c_ubyte * T)(*[1 if f else 0 for f in decode_flags])
-        args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, T,
-                temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs),
-                (_lib.GENERATE_GRAPH if use_graph else 0) | (_lib.GENERATE_CONCURRENT_LANES if concurrent_lanes else 0) |
-                (_lib.GENERATE_FROM_MASK if from_mask else 0),
-                stream_ptr(self.device), host_ptr, host_stride, copy_stream)
-        with torch.cuda.device(self.device):
-            if nucleus < 1.0:
-                check(self.lib.pmhip_pipeline_generate_nucleus(*args[:6], lens, *args[6:], int(guidance_scale is not None),
-                                                               float(guidance_scale or 0.0), choice_temps, nucleus),
-                      "pmhip_pipeline_generate_nucleus")
-            elif choice_temps is not None:
-                check(self.lib.pmhip_pipeline_generate_choice(*args[:6], lens, *args[6:], int(guidance_scale is not None),
-                                                              float(guidance_scale or 0.0), choice_temps), "pmhip_pipeline_generate_choice")
-            elif lens is not None:
-                check(self.lib.pmhip_pipeline_generate_lens(*args[:6], lens, *args[6:], int(guidance_scale is not None),
-                                                            float(guidance_scale or 0.0)), "pmhip_pipeline_generate_lens")
-            elif guidance_scale is None:
-                check(self.lib.pmhip_pipeline_generate(*args), "pmhip_pipeline_generate")
-            else:
-                check(self.lib.pmhip_pipeline_generate_guided(*args, float(guidance_scale)), "pmhip_pipeline_generate_guided")
+        flags = ((_lib.GENERATE_GRAPH if use_graph else 0) | (_lib.GENERATE_CONCURRENT_LANES if concurrent_lanes else 0) |
+                 (_lib.GENERATE_FROM_MASK if from_mask else 0))
+        with torch.cuda.device(self.device):      # always the widest entry, absent options as the header's neutral values (see sample)
+            check(self.lib.pmhip_pipeline_generate_nucleus(
+                self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
+                temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
+                host_stride, copy_stream, int(guidance_scale is not None), float(guidance_scale or 0.0), choice_temps, nucleus),
+                "pmhip_pipeline_generate_nucleus")
         return ids, imgs

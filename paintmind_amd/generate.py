@@ -11,6 +11,7 @@ The masked-token objective (forward / loss / random_masking, generate.py:78-146)
 import math
 import concurrent.futures
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -51,6 +52,30 @@ def choice_schedule(timesteps, choice_temperature):
     if base == 0.0:
         return None
     return [float(np.float32(base * (1.0 - (step + 1) / timesteps))) for step in range(timesteps)]
+
+
+def loop_schedule(timesteps, temperature, num_tokens, choice_temperature=None):
+    """the per-step values of a decode loop (generate.py:187-190) -> (temps [T], nmask [T], ctemps [T] or None), evaluated in
+    float64 like the reference: step s samples at temperature * (1 - s / T), re-masks num_token_masked(cosine((s + 1) / T)) tokens
+    and does so with choice_schedule's value.  Every loop of this package -- native, CPU, region, session -- reads its steps here."""
+    temps = [temperature * (1 - step / timesteps) for step in range(timesteps)]
+    nmask = [num_token_masked(mask_schedule((step + 1) / timesteps), num_tokens) for step in range(timesteps)]
+    return temps, nmask, choice_schedule(timesteps, choice_temperature)
+
+
+class _Options(NamedTuple):
+    """the sampler options of one public call, checked once (Pipeline._options): topk an integer (None resolved to n_embed), top_p a
+    float (1.0 = no nucleus filter), guidance_scale a number or None, lens the per-image context lengths as a host list or None,
+    choice_temperature the base value as a float (0.0 = the deterministic re-masking)"""
+    topk: int
+    top_p: float
+    guidance_scale: Optional[float]
+    lens: Optional[list]
+    choice_temperature: float
+
+    def lane(self, lo, hi):
+        """the options of the micro-batch of images [lo, hi): everything is per batch except the lengths"""
+        return self if self.lens is None else self._replace(lens=self.lens[lo:hi])
 
 
 def choice_keys(scores, t, u):
@@ -267,6 +292,18 @@ class Pipeline(nn.Module):
             raise ValueError("context_lens needs a text condition (text=None IS the unconditional branch)")
         return ops.host_lens(context_lens, B, context.shape[1])
 
+    def _options(self, topk, top_p, guidance_scale, context_lens, choice_temperature, context, B):
+        """the keywords of a public call -> its _Options, every value checked here and nowhere behind: the choice temperature and
+        the nucleus mass (their ranges), guidance and context lengths (both need the context [B, L, D] they are about).  A caller
+        that holds the record already passes it as `topk` and leaves the other keywords at None: it comes back as it is."""
+        if isinstance(topk, _Options):
+            return topk
+        base = ops.choice_t(choice_temperature)
+        top_p = ops.nucleus_p(top_p)
+        if guidance_scale is not None and context is None:
+            raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
+        return _Options(self._topk(topk), top_p, guidance_scale, self._lens(context_lens, context, B), base)
+
     def tokens2logits(self, token, text=None, context_lens=None):
         """context_lens (extension; None = the reference's behaviour, every row of the context is attended to): one length per
         image -- rows [len_b, L) of image b's context never reach its logits, NaN included."""
@@ -317,21 +354,22 @@ class Pipeline(nn.Module):
         that gumbel noise; without it the Philox stream of the step, at a counter word no class column uses.
         """
         nm = num_token_masked(mask_ratio, self.num_tokens)
-        ct = ops.choice_t(choice_temperature)
-        top_p = ops.nucleus_p(top_p)
-        topk = self._topk(topk)
-        if guidance_scale is not None and text is None:
-            raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
-        lens = self._lens(context_lens, text, ids.shape[0])
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, text, ids.shape[0])
+        return self._step(ids, nm, text, opts, temperature, opts.choice_temperature, noise, seed, step, image_base, choice_noise)
+
+    @torch.no_grad()
+    def _step(self, ids, nm, text, opts, temperature, choice_t, noise=None, seed=None, step=0, image_base=0, choice_noise=None):
+        """``sample`` behind its checks: one step that re-masks nm tokens, with the step's own temperature and choice temperature"""
         if self._on_cpu():
-            return self._sample_cpu(ids, nm, text, topk, temperature, noise, seed, guidance_scale, lens, ct, choice_noise, top_p)
+            return self._sample_cpu(ids, nm, text, opts.topk, temperature, noise, seed, opts.guidance_scale, opts.lens, choice_t,
+                                    choice_noise, opts.top_p)
         if seed is None:
             seed = _draw_seed()
         eng = self.engine()
         ids = ids.to(eng.device, torch.int64).clone().contiguous()
-        ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, topk, temperature, nm, noise=noise, seed=seed, step=step,
-                                    image_base=image_base, want_img=True, guidance_scale=guidance_scale, context_lens=lens,
-                                    choice_temperature=ct, choice_noise=choice_noise, top_p=top_p)
+        ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, opts.topk, temperature, nm, noise=noise, seed=seed, step=step,
+                                    image_base=image_base, want_img=True, guidance_scale=opts.guidance_scale, context_lens=opts.lens,
+                                    choice_temperature=choice_t, choice_noise=choice_noise, top_p=opts.top_p)
         return ids, img
 
     def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale, context_lens=None):
@@ -385,30 +423,22 @@ class Pipeline(nn.Module):
         ids = ids.scatter(1, scores.topk(nm, dim=-1).indices, self.mask_token_id)
         return ids, img
 
-    def _generate_cpu(self, text, context, timesteps, temperature, topk, save_interval, seed, return_ids, context_lens=None,
-                      choice_temperature=None, top_p=1.0):
-        B = len(text)
-        ctemps = choice_schedule(timesteps, choice_temperature)
-        topk = self._topk(topk)
+    @torch.no_grad()
+    def _generate_cpu(self, context, B, timesteps, temperature, opts, save_interval, seed, return_ids):
+        """generate.py:183-198, with plain or guided steps (see `sample`), for a pipeline that lives on the CPU.  (On the GPU the
+        loop is the native one, graph-captured and lane-able.)"""
+        temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
         imgs = []
         for step in range(timesteps):
-            masked_r = mask_schedule((step + 1) / timesteps)
-            ids, img = self._sample_cpu(ids, num_token_masked(masked_r, self.num_tokens), context, topk,
-                                        temperature * (1 - step / timesteps), None, None if seed is None else seed + step,
-                                        None, context_lens, ctemps[step] if ctemps else 0.0, None, top_p)
+            ids, img = self._sample_cpu(ids, nmask[step], context, opts.topk, temps[step], None, None if seed is None else seed + step,
+                                        opts.guidance_scale, opts.lens, ctemps[step] if ctemps else 0.0, None, opts.top_p)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
 
     def _schedule(self, timesteps, temperature):
-        temps, nmask = [], []
-        for step in range(timesteps):
-            progress = (step + 1) / timesteps
-            masked_r = mask_schedule(progress)
-            temps.append(temperature * (1 - step / timesteps))
-            nmask.append(num_token_masked(masked_r, self.num_tokens))
-        return temps, nmask
+        return loop_schedule(timesteps, temperature, self.num_tokens)[:2]
 
     @torch.no_grad()
     def _lanes(self, k):
@@ -470,14 +500,16 @@ class Pipeline(nn.Module):
         topk: 1..n_embed, or None = no filter (n_embed); part of the key of a captured graph.
         top_p (None or 1.0: no nucleus filter): every step's nucleus mass, 0 < top_p <= 1 (see ``sample``); one value for the batch,
         so every lane takes it as it is; below 1 part of the key of a captured graph."""
-        lens = self._lens(context_lens, context, B)
-        ctemps = choice_schedule(timesteps, choice_temperature)
-        top_p = ops.nucleus_p(top_p)
-        topk = self._topk(topk)
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
-        temps, nmask = self._schedule(timesteps, temperature)
+        temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
+
+        def run(e, v, ids, c, o, **kw):                   # the native loop of one engine pair: the whole batch, or one lane's images
+            return e.generate(v, ids, c, temps, nmask, decode_flags, o.topk, seed=seed, use_graph=use_graph, want_device_imgs=host is None,
+                              guidance_scale=o.guidance_scale, context_lens=o.lens, choice_temps=ctemps, top_p=o.top_p, **kw)
+
         if isinstance(streams, (list, tuple)):           # explicit micro-batch sizes, e.g. (32, 16, 16)
             sizes = [int(x) for x in streams]
             if sum(sizes) != B or min(sizes) < 1:
@@ -497,11 +529,8 @@ class Pipeline(nn.Module):
             raise ValueError("generate_ids: ids0 needs streams=1")
         if streams == 1:
             ids = self._start_ids(B, ids0, eng.device)
-            return eng.generate(self.vqgan.engine(), ids, context, temps, nmask, decode_flags, topk, seed=seed,
-                                image_base=image_base, use_graph=use_graph,
-                                host=None if host is None else (host[0], 0, host[1][0]), want_device_imgs=host is None,
-                                guidance_scale=guidance_scale, from_mask=ids0 is None, context_lens=lens, choice_temps=ctemps,
-                                top_p=top_p)
+            return run(eng, self.vqgan.engine(), ids, context, opts, image_base=image_base, from_mask=ids0 is None,
+                       host=None if host is None else (host[0], 0, host[1][0]))
         from .dist import shard_range
         cur = torch.cuda.current_stream(eng.device)
         if wait_current:
@@ -515,11 +544,9 @@ class Pipeline(nn.Module):
             with torch.cuda.device(eng.device), torch.cuda.stream(st):
                 ids = torch.full((hi - lo, self.num_tokens), self.mask_token_id, dtype=torch.long, device=eng.device)
                 c = None if context is None else context[lo:hi].contiguous()
-                ids, imgs = e.generate(v, ids, c, temps, nmask, decode_flags, topk, seed=seed, image_base=image_base + lo,
-                                       use_graph=use_graph, host=None if host is None else (host[0], lo, host[1][i]),
-                                       want_device_imgs=host is None, guidance_scale=guidance_scale, concurrent_lanes=True,
-                                       from_mask=True,          # lanes exist for ids0 None only (checked above)
-                                       context_lens=None if lens is None else lens[lo:hi], choice_temps=ctemps, top_p=top_p)
+                ids, imgs = run(e, v, ids, c, opts.lane(lo, hi), image_base=image_base + lo, concurrent_lanes=True,
+                                from_mask=True,                  # lanes exist for ids0 None only (checked above)
+                                host=None if host is None else (host[0], lo, host[1][i]))
             return ids, imgs, st
 
         lanes = self._lanes(streams)
@@ -598,21 +625,13 @@ class Pipeline(nn.Module):
         the exact rule).  A mass cut follows the model from its flat early steps to its peaked late ones, which no fixed
         ``topk`` can; with ``topk=None`` it is the only filter."""
         B = len(text)
-        choice_schedule(timesteps, choice_temperature)        # the value is checked before anything runs
-        top_p = ops.nucleus_p(top_p)
         if mask_padding and context_lens is None:
             context, context_lens = self.text_model(text, return_lens=True)
         else:
             context = self.text_model(text)
-        if guidance_scale is not None and context is None:
-            raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
-        lens = self._lens(context_lens, context, B)
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B)
         if self._on_cpu():
-            if guidance_scale is not None:
-                return self._generate_guided_cpu(context, B, timesteps, temperature, topk, save_interval, seed, return_ids, guidance_scale,
-                                                 lens, choice_temperature, top_p)
-            return self._generate_cpu(text, context, timesteps, temperature, topk, save_interval, seed, return_ids, lens, choice_temperature,
-                                      top_p)
+            return self._generate_cpu(context, B, timesteps, temperature, opts, save_interval, seed, return_ids)
         eng = self.engine()
         if seed is None:
             seed = _draw_seed()
@@ -633,9 +652,8 @@ class Pipeline(nn.Module):
             context = context.to(eng.device)
         n_dec = sum(flags)
         if keep_on_device or n_dec == 0:
-            ids, imgs = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
-                                          use_graph=use_graph, streams=streams, guidance_scale=guidance_scale, context_lens=lens,
-                                          choice_temperature=choice_temperature, top_p=top_p)
+            ids, imgs = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base,
+                                          use_graph=use_graph, streams=streams)
             out = [] if imgs is None else list(imgs)
             return (out, ids) if return_ids else out
         vq = self.vqgan.engine()
@@ -648,9 +666,8 @@ class Pipeline(nn.Module):
         while len(cs) < n_lanes:
             cs.append(torch.cuda.Stream(device=eng.device))
         try:
-            ids, _ = self.generate_ids(context, B, timesteps, temperature, topk, flags, seed, image_base=image_base,
-                                       use_graph=use_graph, streams=streams, host=(host, cs), guidance_scale=guidance_scale,
-                                       context_lens=lens, choice_temperature=choice_temperature, top_p=top_p)
+            ids, _ = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base,
+                                       use_graph=use_graph, streams=streams, host=(host, cs))
         except BaseException:
             # a lane failed: whatever the other lanes queued may still be writing into `host`; drain it, and never hand
             # this buffer out again
@@ -669,28 +686,10 @@ class Pipeline(nn.Module):
         out = list(host)                                     # views of one pinned buffer; it is reused once all of them are gone
         return (out, ids) if return_ids else out
 
-    @torch.no_grad()
-    def _generate_guided_cpu(self, context, B, timesteps, temperature, topk, save_interval, seed, return_ids, scale, context_lens=None,
-                             choice_temperature=None, top_p=1.0):
-        """generate.py:183-198 with guided steps (see `sample`) for a pipeline that lives on the CPU; same return structure.
-        (On the GPU the guided loop is the native one: pmhip_pipeline_generate_guided, graph-captured and lane-able.)"""
-        ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
-        imgs = []
-        ctemps = choice_schedule(timesteps, choice_temperature)
-        topk = self._topk(topk)
-        for step in range(timesteps):
-            nm = num_token_masked(mask_schedule((step + 1) / timesteps), self.num_tokens)
-            ids, img = self._sample_cpu(ids, nm, context, topk, temperature * (1 - step / timesteps), None,
-                                        None if seed is None else seed + step, scale, context_lens, ctemps[step] if ctemps else 0.0,
-                                        None, top_p)
-            if step % save_interval == 0:
-                imgs.append(img)
-        return (imgs, ids) if return_ids else imgs
-
     def _region_loop(self, img, coord, text, timesteps, topk, temperature, keep_inside, seed=None, return_ids=False,
                      choice_temperature=None, top_p=None):
-        choice_schedule(timesteps, choice_temperature)        # the value is checked before anything runs
-        top_p = ops.nucleus_p(top_p)
+        # the values are checked before anything runs (a region loop has neither guidance nor context lengths: no context needed)
+        opts = self._options(topk, top_p, None, None, choice_temperature, None, 0)
         if seed is None:
             seed = _draw_seed()                 # one stream per call; the step index separates the steps
         z, ids, text = self.to_latent(img, text)
@@ -708,21 +707,18 @@ class Pipeline(nn.Module):
             # more than the reference's default single step: the native decode loop (graph replay by default, like generate()) from
             # these start ids, decoding only the last step -- bit-identical to the per-step composition below (tests/test_gpu_model.py)
             use_graph = os.environ.get("PMHIP_GENERATE_GRAPH", "1") != "0"
-            ids, imgs = self.generate_ids(text, ids.shape[0], timesteps, temperature, topk, [False] * (timesteps - 1) + [True], seed,
-                                          use_graph=use_graph, streams=1, ids0=ids, choice_temperature=choice_temperature, top_p=top_p)
+            ids, imgs = self.generate_ids(text, ids.shape[0], timesteps, temperature, opts, [False] * (timesteps - 1) + [True], seed,
+                                          use_graph=use_graph, streams=1, ids0=ids)
             return (imgs[0], ids) if return_ids else imgs[0]
-        return self._region_steps(ids, text, timesteps, topk, temperature, seed, return_ids, choice_temperature, top_p)
+        return self._region_steps(ids, text, timesteps, opts, temperature, seed, return_ids)
 
     def _region_steps(self, ids, text, timesteps, topk, temperature, seed, return_ids=False, choice_temperature=None, top_p=None):
-        """the region loop as the reference writes it: one sample() per step (generate.py:211-216,230-235)"""
+        """the region loop as the reference writes it: one step of ``sample`` per step (generate.py:211-216,230-235)"""
         out = None
-        ctemps = choice_schedule(timesteps, choice_temperature)
+        opts = self._options(topk, top_p, None, None, choice_temperature, text, ids.shape[0])
+        temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
         for step in range(timesteps):
-            progress = (step + 1) / timesteps
-            masked_r = mask_schedule(progress)
-            cur_temp = temperature * (1 - step / timesteps)
-            ids, out = self.sample(ids, mask_ratio=masked_r, text=text, topk=topk, temperature=cur_temp, seed=seed, step=step,
-                                   choice_temperature=ctemps[step] if ctemps else None, top_p=top_p)
+            ids, out = self._step(ids, nmask[step], text, opts, temps[step], ctemps[step] if ctemps else 0.0, seed=seed, step=step)
         return (out, ids) if return_ids else out
 
     @torch.no_grad()

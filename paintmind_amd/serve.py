@@ -14,7 +14,7 @@ admitted so far (growing re-prepares the cross K/V) -- and hands the native step
 (pmhip_pipeline_step_slots_lens), so a request never attends to the rows behind its own.  The contract above then reads
 ``generate_ids(context padded to the capacity, context_lens with L_r in row j, ...)`` (a step taken at capacity C is the scalar
 step at capacity C: a request that lives through a growth follows the capacity step by step).  A step in which every occupied slot fills
-the capacity takes the entry without lengths: the same result, on the kernels every earlier version ran.
+the capacity passes no lengths, which IS the step without them: the same result, on the kernels every earlier version ran.
 
 Guidance is per request (``submit(guidance_scale=s)``, conditional sessions only): the native step
 (pmhip_pipeline_step_slots_guided) reads a scale per slot from a second device record, runs the tower twice in a step in which
@@ -31,7 +31,7 @@ unconditional pass runs at the session's batch size.
 A choice temperature is per request too (``submit(choice_temperature=c)``): the request keeps MaskGIT's annealed value of each of
 its steps beside its temperatures and mask counts, the native step (pmhip_pipeline_step_slots_choice) reads one value per slot
 from a device array, and the contract reads ``generate_ids(..., choice_temperature=c)``.  A step in which no occupied slot has a
-non-zero value is the step without: the same entry, kernels and graph as before.  The guided loop's step-0 cache ("Not built") stays
+non-zero value passes none, which IS the step without: the same kernels and graph as before.  The guided loop's step-0 cache ("Not built") stays
 not built.
 
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
@@ -143,9 +143,8 @@ class DecodeSession:
             self._next_index += 1
         if ids0 is not None:
             ids0 = self.pipe._start_ids(1, ids0.reshape(1, -1), ids0.device)
-        temps, nmask = self.pipe._schedule(timesteps, temperature)
-        from .generate import choice_schedule
-        ctemps = choice_schedule(timesteps, choice_temperature)
+        from .generate import loop_schedule
+        temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.pipe.num_tokens, choice_temperature)
         r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale,
                     ctemps)
         self._submitted += 1
@@ -262,15 +261,17 @@ class DecodeSession:
         lens = None
         if self.conditional and any(r is not None and self._lens[j] != ctx.shape[1] for j, r in enumerate(self.occupied)):
             lens = [min(n, ctx.shape[1]) for n in self._lens]
+
+        def run(keep_context):
+            return eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep_context, want_aux=want_aux,
+                                  guides=self._guides, context_lens=lens, choice=choice)
         try:
-            _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep, want_aux=want_aux,
-                                            guides=self._guides, context_lens=lens, choice=choice)
+            _, pred, score = run(keep)
         except _lib.PmhipError as e:
             # another call on this handle (pipe.generate, a rebuilt engine ...) replaced the prepared context: prepare it again
             if not (keep and getattr(e, "code", None) == _lib.PMHIP_ESTATE):
                 raise
-            _, pred, score = eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=False, want_aux=want_aux,
-                                            guides=self._guides, context_lens=lens, choice=choice)
+            _, pred, score = run(False)
         self._ctx_dirty = False
         for r in self.occupied:
             if r is not None:

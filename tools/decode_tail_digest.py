@@ -4,8 +4,8 @@
 
 One JSON line per case with a sha256 of every output tensor; inputs come from fixed numpy seeds.  The tests compare scores with a
 tolerance; this is for "bit for bit what another commit computes": run it on two built checkouts on one box and diff the files
-(profiles/decode_tail_digest_*.jsonl).  Only the public Python surface (ops, Pipeline) is used, so any commit that has decode
-sessions with per-request guidance can be the other side.
+(profiles/decode_tail_digest_*.jsonl).  Only the public Python surface (ops, Pipeline) is used, so any commit that has the
+nucleus filter (and so wide top-k, choice temperatures, context lengths and per-request guidance) can be the other side.
 """
 import argparse
 import hashlib
@@ -78,6 +78,20 @@ def main():
                         pred, merged, score = ops.sample_rows(x, ids, V, topk, temp, noise=noise, block_stats=st)
                         emit(f"sample_rows V={V} k={topk} T={temp} ties={q} noise {name}", pred=pred, ids=merged, score=score)
 
+    # ---- sample_rows above 64 (the selection kernel, up to the whole row) and behind the nucleus filter (with topk = 5 and topk = V)
+    for V in (1000, 8192):
+        rng = np.random.default_rng(3 * V)
+        planes = [t(logits_of(rng, M, V, q)) for q in (False, True)]
+        ids, noise = t(ids_of(rng, M, V)), t(rng.random((M, V)).astype(np.float32))
+        for q, x in enumerate(planes):
+            for temp in (0.0, 0.7):
+                for topk, top_p in ((65, None), (V, None), (5, 0.5), (5, 0.9), (V, 0.5), (V, 0.9)):
+                    pred, merged, score = ops.sample_rows(x, ids, V, topk, temp, seed=seed, step=5, row_base=base, top_p=top_p)
+                    emit(f"sample_rows V={V} k={topk} p={top_p} T={temp} ties={q} philox", pred=pred, ids=merged, score=score)
+                    if temp:
+                        pred, merged, score = ops.sample_rows(x, ids, V, topk, temp, noise=noise, top_p=top_p)
+                        emit(f"sample_rows V={V} k={topk} p={top_p} T={temp} ties={q} noise", pred=pred, ids=merged, score=score)
+
     # ---- the slots forms: the record set of tests/test_gpu_slots.py::_operator_slots at N = 16
     N = 16
     recs = [(0x0123456789ABCDEF, 7, 0.0, 1, 1, 0), (77, 2 ** 33 + 5, 0.8, 8, N, 3), None,
@@ -90,6 +104,8 @@ def main():
             pred, merged, score = ops.sample_rows_slots(x, ids, V, slots, N, block_stats=st)
             emit(f"sample_rows_slots V={V} {name}", pred=pred, ids=merged, score=score)
         emit(f"remask_slots V={V}", ids=ops.remask_slots(merged.reshape(5, N).clone(), score.reshape(5, N), slots, V))
+        choice = t(np.array([4.5, 0.0, 2.0, 1.5, 0.25], dtype=np.float32))
+        emit(f"remask_slots V={V} choice", ids=ops.remask_slots(merged.reshape(5, N).clone(), score.reshape(5, N), slots, V, choice=choice))
 
     # ---- remask: every elements-per-thread class, tied scores
     for N in (16, 100, 300, 1024, 2048, 4096):
@@ -98,6 +114,10 @@ def main():
         ids = t(rng.integers(0, 64, (3, N)).astype(np.int64))
         for nm in (1, N // 2, N):
             emit(f"remask N={N} num_mask={nm}", ids=ops.remask(ids.clone(), scores, nm, 64))
+            emit(f"remask N={N} num_mask={nm} choice philox",
+                 ids=ops.remask(ids.clone(), scores, nm, 64, choice_temperature=4.5, seed=seed, step=2, row_base=base))
+        emit(f"remask N={N} num_mask={N // 2} choice noise",
+             ids=ops.remask(ids.clone(), scores, N // 2, 64, choice_temperature=4.5, noise=t(rng.random((3, N)).astype(np.float32))))
 
     # ---- guidance: flat (with and without statistics, in place and not) and per image (guided, unguided, idle)
     rng = np.random.default_rng(7)
@@ -142,6 +162,43 @@ def main():
                             ids, imgs = pipe.generate_ids(context, B, T, 0.9, topk, flags, seed=1234, image_base=2 ** 33, use_graph=graph,
                                                           streams=1, ids0=None if ids0 is None else ids0.clone(), **kw)
                             emit(f"generate_ids {tag} k={topk} from={src}{guided} graph={int(graph)} call={call}", ids=ids, imgs=imgs)
+        # the sampler options that came after the loops above: no top-k filter (topk = V), the nucleus filter behind topk = 5 and behind
+        # none, the choice temperature, context lengths under guidance, and all of them in one call, also cut into two lanes
+        full, lens = ctx[:B].contiguous(), [5, 2, 1]
+        option_cases = [("k=V", dict(topk=None))]
+        option_cases += [(f"k={k} p={p}", dict(topk=k, top_p=p)) for p in (0.5, 0.9) for k in (5, None)]
+        option_cases += [("choice", dict(topk=5, choice_temperature=4.5)),
+                         ("lens guided", dict(topk=5, context_lens=lens, guidance_scale=2.0)),
+                         ("all", dict(topk=None, top_p=0.9, choice_temperature=4.5, context_lens=lens, guidance_scale=2.0))]
+        for name, kw in option_cases:
+            topk = kw.pop("topk")
+            for graph, calls in ((False, 1), (True, 3)):
+                for call in range(calls):
+                    ids, imgs = pipe.generate_ids(full, B, T, 0.9, topk, flags, seed=1234, image_base=2 ** 33, use_graph=graph, streams=1, **kw)
+                    emit(f"generate_ids {tag} {name} graph={int(graph)} call={call}", ids=ids, imgs=imgs)
+            ids, imgs = pipe.generate_ids(full, B, T, 0.9, topk, flags, seed=1234, image_base=2 ** 33, use_graph=False, streams=2, **kw)
+            emit(f"generate_ids {tag} {name} lanes=2", ids=ids, imgs=imgs)
+            ids, img = pipe.sample(t(start), 0.5, text=full, topk=topk, temperature=0.8, seed=77, step=1, image_base=2 ** 33, **kw)
+            emit(f"sample {tag} {name}", ids=ids, img=img)
+        # the public loops: generate() through its host buffer and lanes, inpaint with three steps (the native loop from given ids)
+        prompts = ["a", "b", "c"]
+        imgs, ids = pipe.generate(prompts, timesteps=T, temperature=0.9, topk=None, save_interval=2, seed=5, image_base=2 ** 33, return_ids=True,
+                                  streams=2, guidance_scale=2.0, context_lens=[70, 8, 1], choice_temperature=4.5, top_p=0.9)
+        emit(f"generate {tag} all lanes=2", ids=ids, **{f"img{i}": im for i, im in enumerate(imgs)})
+        picture = t((np.random.default_rng(13).random((2, 3, pipe.image_size, pipe.image_size)) * 2 - 1).astype(np.float32))
+        half = pipe.image_size // 2
+        for name, kw in (("choice", dict(choice_temperature=4.5)), ("choice p=0.9 k=V", dict(choice_temperature=4.5, top_p=0.9, topk=None))):
+            img, ids = pipe.inpaint(picture, (0, 0, half, half), text=prompts[:2], timesteps=3, temperature=0.9, seed=9, return_ids=True,
+                                    **dict(dict(topk=5), **kw))
+            emit(f"inpaint {tag} T=3 {name}", ids=ids, img=img)
+        # a decode session of three requests, each with its own choice temperature
+        for graph in (False, True):
+            s = pipe.decode_session(slots=3, conditional=True, use_graph=graph)
+            for i, (steps, temp, topk, scale, choice) in enumerate([(3, 1.0, 5, None, 4.5), (4, 0.7, 3, 1.5, 1.0), (2, 1.3, 8, None, 0.25)]):
+                s.submit(context=ctx[i, :5 - i], timesteps=steps, temperature=temp, topk=topk, seed=200 + i, image_index=2 ** 33 + i,
+                         guidance_scale=scale, choice_temperature=choice)
+            for f in sorted(s.drain(), key=lambda f: f.handle.number):
+                emit(f"session choice {tag} graph={int(graph)} request={f.handle.number}", ids=f.ids, image=f.image)
         # a decode session of four requests, two of them guided
         for graph in (False, True):
             s = pipe.decode_session(slots=4, conditional=True, use_graph=graph)
