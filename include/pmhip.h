@@ -254,6 +254,14 @@ int pmhip_guidance_combine(const float* cond, const float* uncond, float scale, 
  * pmhip_sample_rows_stats: rows must be contiguous and a multiple of 64 long (n % 64 == 0). */
 int pmhip_guidance_combine_stats(const float* cond, const float* uncond, float scale, float* out, size_t n, float* block_stats,
                                  pmhip_stream stream);
+/* The same two with the scale in DEVICE memory (new entry within ABI 11): the kernel loads scale_dev[0] once, wave-uniformly, in
+ * front of its loop and then runs the loop of the entries above -- for the same value the logits and, with block_stats != NULL,
+ * the statistics equal theirs bit for bit, in place (out == cond or uncond) as out of place.  block_stats NULL: the logits only.
+ * Shape rules and NULL refusals are those of the scalar entries, given before anything is launched.  The VALUE cannot be checked
+ * here: whoever wrote it to scale_dev checked it (the decode loop stages finite scales only).  A captured decode loop bakes in the
+ * address, not the scale: this is what lets one graph serve every guidance schedule (pmhip_pipeline_generate_negative). */
+int pmhip_guidance_combine_dev(const float* cond, const float* uncond, const float* scale_dev, float* out, size_t n,
+                               float* block_stats /* or NULL */, pmhip_stream stream);
 
 /* Row gather out[m,:] = table[ids[m],:] (nn.Embedding: stage1/quantize.py:41, generate.py:148-157),
  * table fp32 [V,E], ids int64, out `out_dtype` [M,Kpad] zero-padded. */
@@ -685,6 +693,43 @@ int pmhip_pipeline_generate_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids,
                                     float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
                                     pmhip_stream copy_stream, int guided, float guidance_scale,
                                     const float* ctemps_host /* [T] or NULL */, float top_p);
+
+/* NEGATIVE PROMPT and GUIDANCE SCHEDULE at the model level (new entries within ABI 11): the *_nucleus entries with
+ *   - neg_context fp32 [B, Ln, context_dim] (device), Ln >= 1, and neg_lens_host, a HOST int32 [B] or NULL: the second tower of a
+ *     guided step attends to THIS context instead of running without one -- the step samples from neg + scale * (cond - neg).
+ *     The handle keeps a second set of cross K/V for it (workspace, device length array and ring staging of its own), prepared
+ *     once per call like the context's; Ln need not equal L.  The lengths obey the *_lens contract: rows [len_b, Ln) of image b's
+ *     negative context never reach a result, NaN included
+ *   - (generate only) gscales_host, a HOST float [T] or NULL: step t combines with gscales_host[t]; the scalar guidance_scale is
+ *     then ignored.  The scales travel with the temperatures in the device parameter block, and every combine launch of such a
+ *     loop -- eager, captured or replayed -- is pmhip_guidance_combine_dev on the address of its step's scale: the loop has a graph
+ *     key of its own and ONE graph serves every schedule.  T <= 128 with a schedule
+ * neg_context == NULL (and gscales_host == NULL) runs exactly the *_nucleus entry: the same kernels and the same captured graphs;
+ * in particular the scalar-scale loop keeps its one graph per guidance_scale value.  A negative context adds a component with
+ * Ln (and whether lengths came) to the graph key.  The step with a negative context equals the operator-level composition
+ * pmhip_s2_forward_lens(context) + pmhip_s2_forward_lens(neg_context) + pmhip_guidance_combine + sampling bit for bit; a loop
+ * whose schedule is one value T times equals the scalar-scale loop bit for bit; with neg_context the same rows and lengths as
+ * context the result is the UNGUIDED step's for every scale (cond - neg is exactly 0).  A step whose scale is 0 still runs both
+ * towers.  Everything composes with context lengths, choice temperatures, the nucleus filter, lanes and the deferred decode
+ * like the entries these extend.
+ * Validated before anything is launched (PMHIP_EINVAL, ids untouched): a negative context or a schedule needs guided != 0 and a
+ * context; Ln >= 1; 1 <= neg_len_b <= Ln (the message names the image); neg_lens_host without neg_context; every scale finite.
+ * A later call through any model-level entry that brings no negative context drops the set: nothing runs against a stale one. */
+int pmhip_pipeline_sample_negative(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                   const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                   uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                   float* score_out, int guided, float guidance_scale, float choice_t,
+                                   const float* choice_noise /* [B,N] or NULL */, float top_p,
+                                   const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                   const int32_t* neg_lens_host /* [B] or NULL */, pmhip_stream stream);
+int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                     const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                     const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                     float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                     pmhip_stream copy_stream, int guided, float guidance_scale,
+                                     const float* ctemps_host /* [T] or NULL */, float top_p,
+                                     const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                     const int32_t* neg_lens_host /* [B] or NULL */, const float* gscales_host /* [T] or NULL */);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

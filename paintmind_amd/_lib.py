@@ -166,6 +166,12 @@ PROTOTYPES = {
     "pmhip_pipeline_generate_nucleus": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
                                               C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
                                               f32]),
+    "pmhip_guidance_combine_dev": (i32, [vp, vp, vp, vp, C.c_size_t, vp, vp]),
+    "pmhip_pipeline_sample_negative": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, i32, f32,
+                                             f32, vp, f32, vp, i32, C.POINTER(i32), vp]),
+    "pmhip_pipeline_generate_negative": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
+                                               C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
+                                               f32, vp, i32, C.POINTER(i32), C.POINTER(f32)]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),

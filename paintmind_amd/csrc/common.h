@@ -73,8 +73,10 @@ struct PmGenParams {
     float temps[PM_MAX_STEPS];
     int nmask[PM_MAX_STEPS];
     float ctemps[PM_MAX_STEPS];     // choice temperatures (the choice form of the re-masking kernel); appended: nothing above moves
+    float gscales[PM_MAX_STEPS];    // guidance scales of a scheduled loop (pmhip_guidance_combine_dev reads &gscales[t]); appended
 };
 static_assert(offsetof(PmGenParams, ctemps) == 16 + 8 * PM_MAX_STEPS, "PmGenParams: the fields in front of ctemps keep their offsets");
+static_assert(offsetof(PmGenParams, gscales) == 16 + 12 * PM_MAX_STEPS, "PmGenParams: the fields in front of gscales keep their offsets");
 
 // ---------------------------------------------------------------------------------------------
 // per-IMAGE decode state (include/pmhip.h, pmhip_slot): device memory, one record per image of the batch.  The slots forms of the

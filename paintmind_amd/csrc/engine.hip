@@ -755,6 +755,7 @@ struct pmhip_s2 {
     pmhip_s2_weights w{};
     std::vector<pmhip_layer_weights> layers;
     std::vector<CrossKV> cross;     // per layer, valid after prepare_context
+    std::vector<CrossKV> cross_neg; // per layer: the NEGATIVE context's set (pmhip_pipeline_*_negative), empty K/V when the last call brought none
     Workspace ws;
     Switches sw = Switches::from_env();
     bool pos_split = false;         // bf16 mode: position embedding split into hi / lo planes (ws "pos.*")
@@ -771,6 +772,7 @@ struct pmhip_s2 {
     // slots_one_pass / slots_two_pass count the steps by tower passes
     PinnedRing slots_ring;
     PinnedRing lens_ring;           // per-image context lengths of a call (ctx_lens_host): B int32 -> workspace "ctx.lens"
+    PinnedRing neg_lens_ring;       // ... and of its negative context (neg_lens_host): B int32 -> workspace "neg.lens"
     int slots_one_pass = 0, slots_two_pass = 0;
     int slots_ctx_B = 0, slots_ctx_L = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
@@ -801,6 +803,7 @@ extern "C" int pmhip_s2_create(pmhip_s2** out, int device, int dtype, const pmhi
     h->layers.assign(w->layers, w->layers + cfg->tower.depth);
     h->w.layers = h->layers.data();
     h->cross.resize(cfg->tower.depth);
+    h->cross_neg.resize(cfg->tower.depth);
     *out = h.release();
     return PMHIP_OK;
 }
@@ -813,24 +816,43 @@ extern "C" void pmhip_s2_destroy(pmhip_s2* h) {
 
 namespace {
 
+// Which cross K/V a tower's attn2 layers attend to: none (the unconditional branch: a second self-attention), the context's, or
+// the negative context's.  The two sets are the same thing twice -- workspace buffers, a device length array and ring staging of
+// their own -- so s2_prepare_context and s2_set_ctx_lens are written once and act on the set they are told.
+enum CrossSet { kCrossNone = 0, kCrossContext, kCrossNegative };
+struct CrossSetRef {
+    std::vector<CrossKV>& kv;
+    PinnedRing& ring;
+    const char *in, *proj, *kvbuf, *split, *lens;           // workspace names
+};
+CrossSetRef cross_set(pmhip_s2* h, CrossSet set) {
+    if (set == kCrossNegative) return {h->cross_neg, h->neg_lens_ring, "neg.in", "neg.proj", "neg.kv", "neg.split", "neg.lens"};
+    return {h->cross, h->lens_ring, "ctx.in", "ctx.proj", "ctx.kv", "ctx.split", "ctx.lens"};
+}
+
 // context_proj (transformer.py:84-85) and every layer's attn2 to_k / to_v of the projected context
 // (attention.py:48-49).  The context is static over a decode loop, so this runs once per loop.
-int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStream_t s) {
+// Every model-level entry prepares (or drops) the context's set first; that drops the negative set too, so a call that brings no
+// negative context can never run against a stale one.  An entry with a negative context prepares that set right behind.
+int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStream_t s, CrossSet set = kCrossContext) {
     const auto& c = h->cfg;
     const int dim = c.tower.dim, heads = c.tower.heads, dh = dh_of(c.tower), inner = heads * dh;
     const size_t es = dtype_size(h->dtype);
+    const CrossSetRef cs = cross_set(h, set);
     h->slots_ctx_L = -1;                                      // whatever a slots call prepared is about to be replaced
+    if (set == kCrossContext)
+        for (auto& ck : h->cross_neg) ck = CrossKV{};
     if (!context) {
-        for (auto& ck : h->cross) ck = CrossKV{};
+        for (auto& ck : cs.kv) ck = CrossKV{};
         return PMHIP_OK;
     }
     PM_REQUIRE(L > 0, "s2: context given with L=%d", L);
     const int Mc = B * L, Lp = round_up(L, 64);
     void* cT; void* cp = nullptr;
-    WS(h->ws, "ctx.in", (size_t)Mc * c.context_dim_pad * es, cT);
+    WS(h->ws, cs.in, (size_t)Mc * c.context_dim_pad * es, cT);
     PM_TRY(pmhip_convert_pad(context, c.context_dim, cT, h->dtype, c.context_dim_pad, Mc, s));
     if (h->w.ctxproj_w) {
-        WS(h->ws, "ctx.proj", (size_t)Mc * dim * es, cp);
+        WS(h->ws, cs.proj, (size_t)Mc * dim * es, cp);
         PM_TRY(pmhip_gemm(h->dtype, cT, c.context_dim_pad, h->w.ctxproj_w, c.context_dim_pad, nullptr, nullptr, 0, 0, cp, dim,
                           h->dtype, Mc, dim, c.context_dim_pad, s));
     } else {
@@ -838,15 +860,15 @@ int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStrea
     }
     const size_t per = (size_t)B * heads * Lp * dh * es;
     unsigned char* kv;
-    WS(h->ws, "ctx.kv", per * 2 * c.tower.depth, kv);
+    WS(h->ws, cs.kvbuf, per * 2 * c.tower.depth, kv);
     float* split = nullptr;
-    if (dh != 64) WS(h->ws, "ctx.split", (size_t)Mc * 2 * inner * 4, split);
+    if (dh != 64) WS(h->ws, cs.split, (size_t)Mc * 2 * inner * 4, split);
     const int kinds[2] = {PMHIP_PART_K, PMHIP_PART_V};
     for (int l = 0; l < c.tower.depth; ++l) {
         void* outs[2] = {kv + per * (2 * l), kv + per * (2 * l + 1)};
         const unsigned char* wkv = reinterpret_cast<const unsigned char*>(h->layers[l].wqkv2) + (size_t)inner * dim * es;
         PM_TRY(pmhip_gemm_heads_dh(h->dtype, cp, dim, wkv, dim, Mc, dim, heads, dh, L, Lp, 2, kinds, outs, 1.0f, split, s));
-        h->cross[l].k = outs[0]; h->cross[l].vt = outs[1]; h->cross[l].L = L; h->cross[l].Lp = Lp; h->cross[l].lens = nullptr;
+        cs.kv[l].k = outs[0]; cs.kv[l].vt = outs[1]; cs.kv[l].L = L; cs.kv[l].Lp = Lp; cs.kv[l].lens = nullptr;
     }
     return PMHIP_OK;
 }
@@ -865,28 +887,45 @@ int check_ctx_lens(const char* who, const int32_t* lens_host, bool have_context,
 // -> every layer's CrossKV, from where the cross-attention launch of layer_forward hands them to pmhip_attention_lens.  Called by
 // every model-level entry AFTER the context is prepared or kept (lens_host NULL: the lengths of an earlier call are dropped), and
 // always outside a graph: a captured graph bakes in the device array, never a length.
-int s2_set_ctx_lens(pmhip_s2* h, const int32_t* lens_host, int L, int B, hipStream_t s) {
+int s2_set_ctx_lens(pmhip_s2* h, const int32_t* lens_host, int L, int B, hipStream_t s, CrossSet set = kCrossContext) {
+    const CrossSetRef cs = cross_set(h, set);
     int32_t* dlens = nullptr;
     if (lens_host) {
         const int Bp = round_up(B, 4);                        // 16-byte multiples: the copy kernel's widest path
-        WS(h->ws, "ctx.lens", (size_t)Bp * 4, dlens);
+        WS(h->ws, cs.lens, (size_t)Bp * 4, dlens);
         std::vector<int32_t> padded((size_t)Bp, L);
         std::copy(lens_host, lens_host + B, padded.begin());
-        PM_TRY(h->lens_ring.reserve((size_t)Bp * 4));
-        PM_TRY(h->lens_ring.acquire());
-        PM_TRY(h->lens_ring.stage(dlens, 0, padded.data(), (size_t)Bp * 4, s));
-        PM_TRY(h->lens_ring.commit(s));
+        PM_TRY(cs.ring.reserve((size_t)Bp * 4));
+        PM_TRY(cs.ring.acquire());
+        PM_TRY(cs.ring.stage(dlens, 0, padded.data(), (size_t)Bp * 4, s));
+        PM_TRY(cs.ring.commit(s));
     }
-    for (auto& ck : h->cross) ck.lens = ck.k ? dlens : nullptr;
+    for (auto& ck : cs.kv) ck.lens = ck.k ? dlens : nullptr;
+    return PMHIP_OK;
+}
+
+// The negative context of the *_negative entries, checked BEFORE anything is launched (who: the entry family).  It and a guidance
+// schedule need guidance and a context; Ln >= 1; 1 <= neg_len_b <= Ln; lengths need the negative context they are about.
+int check_negative(const char* who, const float* neg_context, int Ln, const int32_t* neg_lens_host, bool schedule, bool guided,
+                   bool have_context, int B) {
+    PM_REQUIRE(neg_context || !neg_lens_host, "%s: neg_lens_host given without a negative context", who);
+    if (!neg_context && !schedule) return PMHIP_OK;
+    PM_REQUIRE(guided && have_context, "%s: a negative context or a guidance schedule needs guidance (guided != 0) and a context", who);
+    if (!neg_context) return PMHIP_OK;
+    PM_REQUIRE(Ln >= 1, "%s: negative context given with Ln=%d", who, Ln);
+    for (int b = 0; neg_lens_host && b < B; ++b)
+        PM_REQUIRE(neg_lens_host[b] >= 1 && neg_lens_host[b] <= Ln, "%s: image %d: negative context length %d must be in [1, Ln=%d]", who, b,
+                   (int)neg_lens_host[b], Ln);
     return PMHIP_OK;
 }
 
 // token rows (T [M,64]) -> logits fp32 [M,V]  (transformer.py:81-82,87-91)
-// use_cross = false: the unconditional branch (context None: every attn2 is a second self-attention, attention.py:47) although a
-// context has been prepared -- the second forward of a guided step
+// set = kCrossNone: the unconditional branch (context None: every attn2 is a second self-attention, attention.py:47) although a
+// context has been prepared -- the second forward of a guided step; kCrossNegative: that forward against the negative context
 // block_stats (optional, n_embed % 64 == 0): the softmax statistics of the logits' 64-column blocks, [M][n_embed/64][2], written by
 // the logits GEMM's epilogue for the sampling kernel (gemm_common.h GemmParams::block_stats)
-int s2_tower(pmhip_s2* h, const void* tp, int B, float* logits, hipStream_t s, bool use_cross = true, float* block_stats = nullptr) {
+int s2_tower(pmhip_s2* h, const void* tp, int B, float* logits, hipStream_t s, CrossSet set = kCrossContext, float* block_stats = nullptr) {
+    const std::vector<CrossKV>* cross = set == kCrossNone ? nullptr : set == kCrossNegative ? &h->cross_neg : &h->cross;
     const auto& c = h->cfg;
     const int M = B * c.tokens, dim = c.tower.dim;
     TowerBufs tb;
@@ -895,7 +934,7 @@ int s2_tower(pmhip_s2* h, const void* tp, int B, float* logits, hipStream_t s, b
     PM_TRY(pos_source(h->ws, "pos", tb.hilo, h->w.pos, c.tokens, dim, h->pos_split, pos, s));
     PM_TRY(residual_gemm(h->dtype, tb, tp, 64, h->w.tokproj_w, 64, h->w.tokproj_b, pos, M, dim, 64, s));
     for (int l = 0; l < c.tower.depth; ++l)
-        PM_TRY(layer_forward(h->dtype, h->layers[l], c.tower, tb, B, c.tokens, true, use_cross ? &h->cross[l] : nullptr, s));
+        PM_TRY(layer_forward(h->dtype, h->layers[l], c.tower, tb, B, c.tokens, true, cross ? &(*cross)[l] : nullptr, s));
     if (tb.fold && h->w.logits_wf && fold_shape_ok(c.tokens, c.n_embed, dim))   // the final norm folded into to_logits
         return folded_consumer(tb, M, c.tokens, dim, h->w.logits_c, h->w.logits_d, s, [&](int m0, int rows, const void* a, const pmhip_lnfold* ln) {
             float* out = logits + (size_t)m0 * c.n_embed;
@@ -974,6 +1013,9 @@ struct Step {
     bool shared0 = false;
     const float* guidance = nullptr;
     const pmhip_slot* slots = nullptr; const pmhip_slot_guide* guides = nullptr;
+    // guidance_dev: the batch's scale in DEVICE memory (a scheduled loop: &gp->gscales[step]) instead of *guidance; negative: the
+    // second tower of a batch-guided step attends to the negative context's set instead of running without one
+    const float* guidance_dev = nullptr; bool negative = false;
     // the re-masking step's choice temperature, by the same three sources: the scalar choice_t (with optional
     // given uniforms choice_noise [B,N]); choice_params: gp->ctemps[step]; choice_dev: a device float [B] beside the slot records.
     // None of them set: the plain re-masking launch.
@@ -1000,11 +1042,13 @@ int step_tower(pmhip_s2* s2, const int64_t* ids, int B, const Step& st, hipStrea
     PM_TRY(step_bufs(s2, M, false, b, s));
     // the statistics come from the logits GEMM, or -- one scale for the batch -- from the combination, which produces the logits
     // that are sampled
-    PM_TRY(s2_tower(s2, tp, B, b.logits, s, true, st.guidance ? nullptr : b.lstats));
-    if (!st.guidance && !st.guides) return PMHIP_OK;
+    const bool batch_guided = st.guidance || st.guidance_dev;
+    PM_TRY(s2_tower(s2, tp, B, b.logits, s, kCrossContext, batch_guided ? nullptr : b.lstats));
+    if (!batch_guided && !st.guides) return PMHIP_OK;
     float* uncond;
     WS(s2->ws, "s2.logits_u", (size_t)M * c.n_embed * 4, uncond);
-    PM_TRY(s2_tower(s2, tp, B, uncond, s, false));
+    PM_TRY(s2_tower(s2, tp, B, uncond, s, st.negative ? kCrossNegative : kCrossNone));
+    if (st.guidance_dev) return pmhip_guidance_combine_dev(b.logits, uncond, st.guidance_dev, b.logits, (size_t)M * c.n_embed, b.lstats, s);
     if (st.guides) return pmhip_guidance_combine_slots(b.logits, uncond, st.guides, st.slots, c.tokens, b.logits, b.lstats, M, c.n_embed, s);
     if (b.lstats) return pmhip_guidance_combine_stats(b.logits, uncond, *st.guidance, b.logits, (size_t)M * c.n_embed, b.lstats, s);
     return pmhip_guidance_combine(b.logits, uncond, *st.guidance, b.logits, (size_t)M * c.n_embed, s);
@@ -1160,20 +1204,27 @@ extern "C" int pmhip_s2_forward_lens(pmhip_s2* h, const float* tokens, const flo
 static int pipeline_sample_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                 const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                 uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out, float* score_out, int guided,
-                                float guidance_scale, float choice_t, const float* choice_noise, float top_p, pmhip_stream stream) {
+                                float guidance_scale, float choice_t, const float* choice_noise, float top_p, pmhip_stream stream,
+                                const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr) {
     PM_TRY(pm_check_top_p("pipeline_sample_nucleus", top_p));
     const char* wide = top_p != 1.f ? "pipeline_sample_nucleus" : "pipeline_sample_choice";
     PM_TRY(pm_check_choice_t(wide, choice_t));
-    const char* who = top_p != 1.f || choice_t != 0.f ? wide : narrow;
+    PM_TRY(check_negative("pipeline_sample_negative", neg_context, Ln, neg_lens_host, false, guided != 0, context && L > 0, B));
+    const char* who = neg_context ? "pipeline_sample_negative" : top_p != 1.f || choice_t != 0.f ? wide : narrow;
     Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
     if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }     // 0: no given uniforms to ignore
     st.top_p = top_p;
+    st.negative = neg_context != nullptr;
     PM_REQUIRE(s2 && ids && B > 0, "%s: bad arguments", who);
     PM_REQUIRE(!st.guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
     hipStream_t s = (hipStream_t)stream;
-    PM_TRY(s2_prepare_context(s2, context, L, B, s));
+    PM_TRY(s2_prepare_context(s2, context, L, B, s));         // (drops the negative set of an earlier call)
     PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
+    if (neg_context) {
+        PM_TRY(s2_prepare_context(s2, neg_context, Ln, B, s, kCrossNegative));
+        PM_TRY(s2_set_ctx_lens(s2, neg_lens_host, Ln, B, s, kCrossNegative));
+    }
     return sample_step(s2, vq, ids, B, st, img_out, pred_out, score_out, s);
 }
 
@@ -1221,6 +1272,18 @@ extern "C" int pmhip_pipeline_sample_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int6
                                 image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream);
 }
 
+// neg_context == NULL: exactly pmhip_pipeline_sample_nucleus
+extern "C" int pmhip_pipeline_sample_negative(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                              const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                              uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                              float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
+                                              float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                              pmhip_stream stream) {
+    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream,
+                                neg_context, Ln, neg_lens_host);
+}
+
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
 static bool direct_dispatch_off() {
     static const bool off = [] { const char* e = getenv("AMD_DIRECT_DISPATCH"); return e && atoi(e) == 0; }();
@@ -1240,6 +1303,11 @@ struct GenCall {
     const char* who = "pipeline_generate";
     const float* ctemps = nullptr;          // host [T] or NULL: the steps' choice temperatures (pmhip_pipeline_generate_choice)
     float top_p = 1.f;                      // every step's nucleus mass (pmhip_pipeline_generate_nucleus); 1: no filter
+    // pmhip_pipeline_generate_negative: the negative context [B, Ln, context_dim] with its host lengths [B] (or NULL), and the
+    // steps' guidance scales, host [T] (then `guidance` is NULL: the scalar is ignored)
+    const float* neg_context = nullptr; int Ln = 0; const int32_t* neg_lens = nullptr;
+    const float* gscales = nullptr;
+    bool guided() const { return guidance || gscales; }
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
 
@@ -1308,8 +1376,9 @@ int pipeline_generate(const GenCall& c) {
     pmhip_s2* s2 = c.s2; pmhip_vqgan* vq = c.vq;
     const int B = c.B, T = c.T;
     PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && c.nmask_host, "pipeline_generate: bad arguments");
-    PM_REQUIRE(!c.guidance || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
+    PM_REQUIRE(!c.guided() || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
     PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
+    const bool sched = c.gscales != nullptr, neg = c.neg_context != nullptr;
     // the choice temperatures, checked before anything is launched; all zero IS the loop without them (same kernels, same graphs)
     bool choice = false;
     for (int t = 0; c.ctemps && t < T; ++t) {
@@ -1320,6 +1389,10 @@ int pipeline_generate(const GenCall& c) {
     hipStream_t cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
     PM_TRY(s2_prepare_context(s2, c.context, c.L, B, s));     // context projection + cross K/V: once per loop, eager
     PM_TRY(s2_set_ctx_lens(s2, c.ctx_lens, c.L, B, s));       // the lengths: device memory the (captured) cross-attention launches read
+    if (neg) {                                                // the negative set: one more preparation per loop, eager like the first
+        PM_TRY(s2_prepare_context(s2, c.neg_context, c.Ln, B, s, kCrossNegative));
+        PM_TRY(s2_set_ctx_lens(s2, c.neg_lens, c.Ln, B, s, kCrossNegative));
+    }
     size_t img_elems = 0;
     if (vq) img_elems = (size_t)B * vq->cfg.channels * vq->cfg.image_size * vq->cfg.image_size;
     int n_dec = 0;
@@ -1365,8 +1438,31 @@ int pipeline_generate(const GenCall& c) {
     }
     HostDelivery out{c, s, cs, img_elems, n_dec, gimgs != nullptr};
 
+    // The device parameter block: what the kernels of a replayed loop read their per-call values from, and -- eager or replayed --
+    // where the combine launches of a loop with a guidance schedule read their scales (one kernel form for eager, capture and replay).
+    PmGenParams* gparams = nullptr;
+    auto stage_params = [&]() -> int {
+        WS(s2->ws, "gen.params", sizeof(PmGenParams), gparams);
+        PmGenParams hp;
+        hp.seed = c.seed;
+        hp.row_base = c.image_base * (uint64_t)s2->cfg.tokens;
+        for (int t = 0; t < T; ++t) {
+            hp.temps[t] = c.temps_host[t]; hp.nmask[t] = c.nmask_host[t]; hp.ctemps[t] = choice ? c.ctemps[t] : 0.f;
+            hp.gscales[t] = sched ? c.gscales[t] : 0.f;
+        }
+        // a loop stages what it always staged: without choice temperatures the block up to ctemps, without a guidance schedule the
+        // block up to gscales -- none of its kernels reads what lies behind
+        const size_t hp_bytes = sched ? sizeof hp : choice ? offsetof(PmGenParams, gscales) : offsetof(PmGenParams, ctemps);
+        PM_TRY(s2->params_ring.reserve(sizeof hp));
+        PM_TRY(s2->params_ring.acquire());
+        PM_TRY(s2->params_ring.stage(gparams, 0, &hp, hp_bytes, s));
+        PM_TRY(s2->params_ring.commit(s));
+        return PMHIP_OK;
+    };
+
     if (!graph) {
         int d = 0;
+        if (sched) PM_TRY(stage_params());
         if (from_mask) PM_TRY(fill_ids_async(c.ids, (int64_t)s2->cfg.n_embed, n_ids, s));
         for (int t = 0; t < T; ++t) {
             const bool dec = c.decodes(t);
@@ -1374,6 +1470,8 @@ int pipeline_generate(const GenCall& c) {
             Step st{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0, c.guidance};
             if (choice) st.choice_t = c.ctemps[t];             // 0 (the last step of an annealed loop): the plain launch, the same keys
             st.top_p = c.top_p;
+            st.negative = neg;
+            if (sched) st.guidance_dev = &gparams->gscales[t];
             PM_TRY(tower(c.ids, st, s));
             PM_TRY(step_tail(s2, vq, c.ids, B, st, img, nullptr, nullptr, s));
             PM_TRY(out.flush());                               // the previous image, now that one more step is queued behind it
@@ -1387,21 +1485,9 @@ int pipeline_generate(const GenCall& c) {
     // block and whose ids / image pointers are handle-owned buffers, so the same executable graphs serve every call with
     // this structure; between two segments the finished image starts its way to the host.
     const size_t ids_bytes = n_ids * 8;
-    int64_t* gids; PmGenParams* gparams;
+    int64_t* gids;
     WS(s2->ws, "gen.ids", ids_bytes, gids);
-    WS(s2->ws, "gen.params", sizeof(PmGenParams), gparams);
-    {
-        PmGenParams hp;
-        hp.seed = c.seed;
-        hp.row_base = c.image_base * (uint64_t)s2->cfg.tokens;
-        for (int t = 0; t < T; ++t) { hp.temps[t] = c.temps_host[t]; hp.nmask[t] = c.nmask_host[t]; hp.ctemps[t] = choice ? c.ctemps[t] : 0.f; }
-        // a loop without choice temperatures stages what it always staged: the block up to ctemps, which none of its kernels reads
-        const size_t hp_bytes = choice ? sizeof hp : offsetof(PmGenParams, ctemps);
-        PM_TRY(s2->params_ring.reserve(sizeof hp));
-        PM_TRY(s2->params_ring.acquire());
-        PM_TRY(s2->params_ring.stage(gparams, 0, &hp, hp_bytes, s));
-        PM_TRY(s2->params_ring.commit(s));
-    }
+    PM_TRY(stage_params());
     if (from_mask) PM_TRY(fill_ids_async(gids, (int64_t)s2->cfg.n_embed, n_ids, s));
     else PM_TRY(copy16_async(gids, c.ids, ids_bytes, s));
 
@@ -1412,7 +1498,11 @@ int pipeline_generate(const GenCall& c) {
         unsigned bits;
         memcpy(&bits, c.guidance, 4);
         key += "g" + std::to_string(bits);
+    } else if (sched) {                                       // the combine reads &gparams->gscales[t]: an address, so one graph serves every schedule
+        key += "gs";
     }
+    // the second tower attends to the negative set: Ln shapes its cross-attention launches, lengths pick their per-image form
+    if (neg) key += "N" + std::to_string(c.Ln) + (c.neg_lens ? "l" : "");
     key += "d";
     for (int t = 0; t < T; ++t) key += c.decodes(t) ? '1' : '0';
     // (no deferred decode when the caller runs other lanes beside this one -- PMHIP_GENERATE_CONCURRENT_LANES: the chip is full
@@ -1456,6 +1546,8 @@ int pipeline_generate(const GenCall& c) {
             Step st{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0, c.guidance};
             st.choice_params = choice;
             st.top_p = c.top_p;
+            st.negative = neg;
+            if (sched) st.guidance_dev = &gparams->gscales[t];
             PM_TRY(tower(gids, st, on));
             if (need_join) { PM_HIP(hipStreamWaitEvent(on, ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
             float* img = (u.decode_inline && c.decodes(t)) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
@@ -1481,12 +1573,23 @@ static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan*
                                   const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
                                   const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base, float* imgs_out,
                                   int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride, pmhip_stream copy_stream,
-                                  int guided, float guidance_scale, const float* ctemps_host, float top_p) {
+                                  int guided, float guidance_scale, const float* ctemps_host, float top_p,
+                                  const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
+                                  const float* gscales_host = nullptr) {
     PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
-    return pipeline_generate(GenCall{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-                                     use_graph, stream, imgs_host, host_stride, copy_stream, guided ? &guidance_scale : nullptr, ctx_lens_host,
-                                     top_p != 1.f ? "pipeline_generate_nucleus" : ctemps_host ? "pipeline_generate_choice" : narrow,
-                                     ctemps_host, top_p});
+    const char* neg_who = "pipeline_generate_negative";
+    PM_TRY(check_negative(neg_who, neg_context, Ln, neg_lens_host, gscales_host != nullptr, guided != 0, context && L > 0, B));
+    if (gscales_host) {
+        PM_REQUIRE(T <= PM_MAX_STEPS, "%s: a guidance schedule serves at most %d steps, T=%d", neg_who, PM_MAX_STEPS, T);
+        for (int t = 0; t < T; ++t) PM_REQUIRE(std::isfinite(gscales_host[t]), "%s: step %d: the guidance scale must be finite", neg_who, t);
+    }
+    GenCall c{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
+              use_graph, stream, imgs_host, host_stride, copy_stream, guided && !gscales_host ? &guidance_scale : nullptr, ctx_lens_host,
+              neg_context || gscales_host ? neg_who : top_p != 1.f ? "pipeline_generate_nucleus" : ctemps_host ? "pipeline_generate_choice" : narrow,
+              ctemps_host, top_p};
+    c.neg_context = neg_context; c.Ln = Ln; c.neg_lens = neg_lens_host;
+    c.gscales = gscales_host;
+    return pipeline_generate(c);
 }
 
 extern "C" int pmhip_pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -1537,6 +1640,19 @@ extern "C" int pmhip_pipeline_generate_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, in
     return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
                                   topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
                                   guidance_scale, ctemps_host, top_p);
+}
+
+// neg_context == NULL and gscales_host == NULL: exactly pmhip_pipeline_generate_nucleus
+extern "C" int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                                const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                                const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                                float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                                pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
+                                                float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                                const float* gscales_host) {
+    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
+                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host);
 }
 
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged

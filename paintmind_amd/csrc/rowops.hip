@@ -217,6 +217,17 @@ __global__ __launch_bounds__(THREADS) void guidance_kernel(const float* cond, co
                          block_stats, n4, scale, 0);
 }
 
+// guidance_kernel with the scale in DEVICE memory (pmhip_guidance_combine_dev): one wave-uniform load of scale_dev[0] in front of
+// the loop, then the same body -- for the same value the same bits as guidance_kernel, logits and statistics.  A captured decode
+// loop bakes in the address, not the value: one graph serves every guidance schedule.
+template <bool STATS>
+__global__ __launch_bounds__(THREADS) void guidance_dev_kernel(const float* cond, const float* uncond, const float* __restrict__ scale_dev,
+                                                               float* out, size_t n4, float2* block_stats) {
+    const float scale = scale_dev[0];
+    guidance_body<STATS>(reinterpret_cast<const float4*>(cond), reinterpret_cast<const float4*>(uncond), reinterpret_cast<float4*>(out),
+                         block_stats, n4, scale, 0);
+}
+
 // guidance_kernel per IMAGE (pmhip_guidance_combine_slots): image b = blockIdx.y combines with guides[b].scale when its slot is
 // active and guides[b].on is set, and is neither read nor written otherwise -- the workgroups of such an image leave at once, so
 // what the cond tower's GEMM left there (logits and statistics) stays the unguided step's input.  The image is a workgroup-level
@@ -550,13 +561,21 @@ extern "C" int pmhip_add_rows(const float* x, const float* table, int table_rows
     return PMHIP_OK;
 }
 
-static int guidance_impl(const float* cond, const float* uncond, float scale, float* out, size_t n, float* block_stats, pmhip_stream stream) {
+// scale_dev != NULL: the scale is scale_dev[0] in device memory (pmhip_guidance_combine_dev) and `scale` is not looked at
+static int guidance_impl(const float* cond, const float* uncond, float scale, const float* scale_dev, float* out, size_t n,
+                         float* block_stats, pmhip_stream stream) {
     PM_REQUIRE(cond && uncond && out, "guidance_combine: null pointer");
     PM_REQUIRE(n > 0 && n % 4 == 0, "guidance_combine: n must be a positive multiple of 4");
     PM_REQUIRE(!block_stats || n % 64 == 0, "guidance_combine_stats: n must be a multiple of 64 (rows of whole 64-column blocks)");
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_ROWOPS, s);
-    if (block_stats)
+    if (scale_dev && block_stats)
+        hipLaunchKernelGGL(guidance_dev_kernel<true>, dim3(grid_for(n / 4)), dim3(THREADS), 0, s, cond, uncond, scale_dev, out, n / 4,
+                           reinterpret_cast<float2*>(block_stats));
+    else if (scale_dev)
+        hipLaunchKernelGGL(guidance_dev_kernel<false>, dim3(grid_for(n / 4)), dim3(THREADS), 0, s, cond, uncond, scale_dev, out, n / 4,
+                           (float2*)nullptr);
+    else if (block_stats)
         hipLaunchKernelGGL(guidance_kernel<true>, dim3(grid_for(n / 4)), dim3(THREADS), 0, s, cond, uncond, scale, out, n / 4,
                            reinterpret_cast<float2*>(block_stats));
     else
@@ -566,7 +585,7 @@ static int guidance_impl(const float* cond, const float* uncond, float scale, fl
 }
 
 extern "C" int pmhip_guidance_combine(const float* cond, const float* uncond, float scale, float* out, size_t n, pmhip_stream stream) {
-    return guidance_impl(cond, uncond, scale, out, n, nullptr, stream);
+    return guidance_impl(cond, uncond, scale, nullptr, out, n, nullptr, stream);
 }
 
 // the same, plus block_stats [n / 64][2]: softmax statistics of the combined logits for pmhip_sample_rows_stats (contiguous rows
@@ -574,7 +593,15 @@ extern "C" int pmhip_guidance_combine(const float* cond, const float* uncond, fl
 extern "C" int pmhip_guidance_combine_stats(const float* cond, const float* uncond, float scale, float* out, size_t n, float* block_stats,
                                             pmhip_stream stream) {
     PM_REQUIRE(block_stats, "guidance_combine_stats: null statistics buffer");
-    return guidance_impl(cond, uncond, scale, out, n, block_stats, stream);
+    return guidance_impl(cond, uncond, scale, nullptr, out, n, block_stats, stream);
+}
+
+// the same two with the scale read by the kernel from scale_dev[0] (device memory; whoever wrote it there checked the value);
+// block_stats NULL: the logits only
+extern "C" int pmhip_guidance_combine_dev(const float* cond, const float* uncond, const float* scale_dev, float* out, size_t n,
+                                          float* block_stats, pmhip_stream stream) {
+    PM_REQUIRE(scale_dev, "guidance_combine_dev: null scale pointer");
+    return guidance_impl(cond, uncond, 0.f, scale_dev, out, n, block_stats, stream);
 }
 
 // the same per image: guides / slots are DEVICE arrays [M / tokens]; an idle or unguided image is neither read nor written

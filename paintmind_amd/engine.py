@@ -312,8 +312,11 @@ class S2Engine:
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
                want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None,
-               top_p=None):
+               top_p=None, negative_context=None, negative_lens=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
+        negative_context fp32 [B, Ln, context_dim] (None = the calls below, as without the keyword): the second tower of the guided
+        step attends to it instead of running without a context (pmhip_pipeline_sample_negative); negative_lens: its per-image
+        lengths, like context_lens.  Needs guidance_scale.
         topk: an integer in 1..n_embed (Pipeline resolves its topk=None to n_embed before it gets here).
         guidance_scale (None = the reference's step): sample from uncond + scale * (cond - uncond), two tower passes.
         context_lens (None = every image attends to its whole context): image b's cross-attention sees context rows
@@ -336,15 +339,31 @@ class S2Engine:
             choice_noise = choice_noise.to(self.device, torch.float32).contiguous()
             if tuple(choice_noise.shape) != (B, self.tokens):
                 raise ValueError(f"choice_noise must be [B, {self.tokens}]")
+        neg, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
         # always the widest entry: an absent option travels as the value with which the header promises the narrower entry's
         # computation (NULL lengths, guided = 0, choice_t = 0, top_p = 1)
-        with torch.cuda.device(self.device):
-            check(self.lib.pmhip_pipeline_sample_nucleus(
-                self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens,
+        args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens,
                 int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img), _p(pred),
-                _p(score), int(guidance_scale is not None), float(guidance_scale or 0.0), ct, _p(choice_noise if ct else None), nucleus,
-                stream_ptr(self.device)), "pmhip_pipeline_sample_nucleus")
+                _p(score), int(guidance_scale is not None), float(guidance_scale or 0.0), ct, _p(choice_noise if ct else None), nucleus)
+        with torch.cuda.device(self.device):
+            if neg is None:                       # without a negative context the native call is the one made before there was one
+                check(self.lib.pmhip_pipeline_sample_nucleus(*args, stream_ptr(self.device)), "pmhip_pipeline_sample_nucleus")
+            else:
+                check(self.lib.pmhip_pipeline_sample_negative(*args, _p(neg), Ln, neg_lens, stream_ptr(self.device)),
+                      "pmhip_pipeline_sample_negative")
         return ids, img, pred, score
+
+    def _negative(self, negative_context, negative_lens, B):
+        """(negative_context, negative_lens) -> (the context on the device or None, Ln, a ctypes int32 [B] or None)"""
+        if negative_context is None:
+            if negative_lens is not None:
+                raise ValueError("negative_lens needs a negative context")
+            return None, 0, None
+        neg, Ln = self._ctx(negative_context)
+        if neg.shape[0] != B:
+            raise ValueError(f"negative context for {neg.shape[0]} images, batch of {B}")
+        vals = ops.host_lens(negative_lens, B, Ln, "negative_lens")
+        return neg, Ln, None if vals is None else (C.c_int * B)(*vals)
 
     def slots_steps(self):
         """(one_pass, two_pass): the slots steps this handle ran, by tower passes (pmhip_s2_slots_steps) -- two passes exactly when
@@ -393,8 +412,13 @@ class S2Engine:
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
                  host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
-                 choice_temps=None, top_p=None):
+                 choice_temps=None, top_p=None, negative_context=None, negative_lens=None, guidance_scales=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
+
+        negative_context / negative_lens: as in ``sample``.  guidance_scales: one finite scale per step (a list of T floats) instead of
+        the one guidance_scale, which is then ignored -- the captured loop reads them from device memory: one graph serves every
+        schedule.  Without any of the three the native call is the one made before they existed; with any of them it is ONE call to
+        pmhip_pipeline_generate_negative, absent ones at their neutral values (NULL).
 
         topk: an integer in 1..n_embed, the same for every step; part of the key of a captured graph.
 
@@ -438,10 +462,17 @@ class S2Engine:
         dec_c = (C.c_ubyte * T)(*[1 if f else 0 for f in decode_flags])
         flags = ((_lib.GENERATE_GRAPH if use_graph else 0) | (_lib.GENERATE_CONCURRENT_LANES if concurrent_lanes else 0) |
                  (_lib.GENERATE_FROM_MASK if from_mask else 0))
+        neg, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
+        gscales = None
+        if guidance_scales is not None:
+            gscales = (C.c_float * T)(*ops.guidance_scales(guidance_scales, T, "generate: guidance_scales"))
+        guided = guidance_scale is not None or gscales is not None
         with torch.cuda.device(self.device):      # always the widest entry, absent options as the header's neutral values (see sample)
-            check(self.lib.pmhip_pipeline_generate_nucleus(
-                self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
-                temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
-                host_stride, copy_stream, int(guidance_scale is not None), float(guidance_scale or 0.0), choice_temps, nucleus),
-                "pmhip_pipeline_generate_nucleus")
+            args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
+                    temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
+                    host_stride, copy_stream, int(guided), float(guidance_scale or 0.0), choice_temps, nucleus)
+            if neg is None and gscales is None:
+                check(self.lib.pmhip_pipeline_generate_nucleus(*args), "pmhip_pipeline_generate_nucleus")
+            else:
+                check(self.lib.pmhip_pipeline_generate_negative(*args, _p(neg), Ln, neg_lens, gscales), "pmhip_pipeline_generate_negative")
         return ids, imgs

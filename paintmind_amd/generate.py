@@ -54,6 +54,13 @@ def choice_schedule(timesteps, choice_temperature):
     return [float(np.float32(base * (1.0 - (step + 1) / timesteps))) for step in range(timesteps)]
 
 
+def linear_guidance(timesteps, scale):
+    """a guidance schedule that rises linearly to `scale`: step s of T guides with scale * (s + 1) / T -- low early for diversity,
+    high late for fidelity, as Muse describes it (without naming endpoints: any list of T finite floats is a schedule for
+    ``Pipeline.generate(guidance_scale=[...])``, this is one choice)"""
+    return [scale * (step + 1) / timesteps for step in range(timesteps)]
+
+
 def loop_schedule(timesteps, temperature, num_tokens, choice_temperature=None):
     """the per-step values of a decode loop (generate.py:187-190) -> (temps [T], nmask [T], ctemps [T] or None), evaluated in
     float64 like the reference: step s samples at temperature * (1 - s / T), re-masks num_token_masked(cosine((s + 1) / T)) tokens
@@ -66,16 +73,29 @@ def loop_schedule(timesteps, temperature, num_tokens, choice_temperature=None):
 class _Options(NamedTuple):
     """the sampler options of one public call, checked once (Pipeline._options): topk an integer (None resolved to n_embed), top_p a
     float (1.0 = no nucleus filter), guidance_scale a number or None, lens the per-image context lengths as a host list or None,
-    choice_temperature the base value as a float (0.0 = the deterministic re-masking)"""
+    choice_temperature the base value as a float (0.0 = the deterministic re-masking), negative the negative context [B, Ln, D] or
+    None with negative_lens its per-image lengths as a host list or None, guidance_scales the loop's per-step scales as a list of
+    floats or None (then guidance_scale is every step's)"""
     topk: int
     top_p: float
     guidance_scale: Optional[float]
     lens: Optional[list]
     choice_temperature: float
+    negative: Optional[torch.Tensor] = None
+    negative_lens: Optional[list] = None
+    guidance_scales: Optional[list] = None
 
     def lane(self, lo, hi):
-        """the options of the micro-batch of images [lo, hi): everything is per batch except the lengths"""
-        return self if self.lens is None else self._replace(lens=self.lens[lo:hi])
+        """the options of the micro-batch of images [lo, hi): everything is per batch except the lengths and the negative context"""
+        if self.lens is None and self.negative is None:
+            return self
+        return self._replace(lens=None if self.lens is None else self.lens[lo:hi],
+                             negative=None if self.negative is None else self.negative[lo:hi].contiguous(),
+                             negative_lens=None if self.negative_lens is None else self.negative_lens[lo:hi])
+
+    def step_scale(self, step):
+        """the guidance scale of step `step` of a loop (None: no guidance)"""
+        return self.guidance_scale if self.guidance_scales is None else self.guidance_scales[step]
 
 
 def choice_keys(scores, t, u):
@@ -292,17 +312,36 @@ class Pipeline(nn.Module):
             raise ValueError("context_lens needs a text condition (text=None IS the unconditional branch)")
         return ops.host_lens(context_lens, B, context.shape[1])
 
-    def _options(self, topk, top_p, guidance_scale, context_lens, choice_temperature, context, B):
+    def _options(self, topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative=None, negative_lens=None,
+                 timesteps=None):
         """the keywords of a public call -> its _Options, every value checked here and nowhere behind: the choice temperature and
-        the nucleus mass (their ranges), guidance and context lengths (both need the context [B, L, D] they are about).  A caller
-        that holds the record already passes it as `topk` and leaves the other keywords at None: it comes back as it is."""
+        the nucleus mass (their ranges), guidance and context lengths (both need the context [B, L, D] they are about), the
+        negative context [B, Ln, D] (needs guidance) and its lengths (need it).  guidance_scale: a number, or -- in a loop, which
+        says so by its `timesteps` -- a sequence of that many finite numbers, one per step.  A caller that holds the record
+        already passes it as `topk` and leaves the other keywords at None: it comes back as it is."""
         if isinstance(topk, _Options):
             return topk
         base = ops.choice_t(choice_temperature)
         top_p = ops.nucleus_p(top_p)
         if guidance_scale is not None and context is None:
             raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
-        return _Options(self._topk(topk), top_p, guidance_scale, self._lens(context_lens, context, B), base)
+        scales = None
+        if isinstance(guidance_scale, (list, tuple, np.ndarray, torch.Tensor)) and np.ndim(guidance_scale) > 0:
+            if timesteps is None:
+                raise ValueError("guidance_scale: one step takes one scale (a sequence is a loop's schedule)")
+            scales, guidance_scale = ops.guidance_scales(guidance_scale, timesteps), None
+        if negative_lens is not None and negative is None:
+            raise ValueError("negative_context_lens needs a negative text")
+        if negative is not None:
+            if context is None:
+                raise ValueError("negative_text needs a text condition (text=None IS the unconditional branch)")
+            if guidance_scale is None and scales is None:
+                raise ValueError("negative_text needs guidance_scale (the step moves away from it by that much)")
+            if negative.dim() != 3 or negative.shape[0] != B or negative.shape[2] != context.shape[2]:
+                raise ValueError(f"negative_text must be a context tensor [{B}, Ln, {context.shape[2]}], got {tuple(negative.shape)}")
+            negative_lens = ops.host_lens(negative_lens, B, negative.shape[1], "negative_context_lens")
+        return _Options(self._topk(topk), top_p, guidance_scale, self._lens(context_lens, context, B), base, negative, negative_lens,
+                        scales)
 
     def tokens2logits(self, token, text=None, context_lens=None):
         """context_lens (extension; None = the reference's behaviour, every row of the context is attended to): one length per
@@ -323,8 +362,14 @@ class Pipeline(nn.Module):
 
     @torch.no_grad()
     def sample(self, ids, mask_ratio, text=None, topk=1, temperature=1, noise=None, seed=None, step=0, image_base=0,
-               guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None, top_p=None):
+               guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None, top_p=None, negative_text=None,
+               negative_context_lens=None):
         """One MaskGIT step (generate.py:159-181) -> (ids', img).
+
+        ``negative_text`` (extension; None = the step as without the keyword): a NEGATIVE prompt -- like ``text`` a context tensor
+        (B, Ln, D) here; Ln need not equal L.  The second forward of the guided step then sees this context instead of none, and
+        the step's logits are ``neg + guidance_scale * (cond - neg)``: the image moves away from it (Muse's negative prompting).
+        Needs ``guidance_scale`` and ``text``.  ``negative_context_lens``: one length per image for it, like ``context_lens``.
 
         ``top_p`` (extension; None or 1.0 = no nucleus filter, the step as without the keyword): 0 < top_p <= 1.  Behind the
         top-k, only the elements whose probability mass strictly above them is below ``top_p`` of the top-k's mass are drawn
@@ -354,7 +399,8 @@ class Pipeline(nn.Module):
         that gumbel noise; without it the Philox stream of the step, at a counter word no class column uses.
         """
         nm = num_token_masked(mask_ratio, self.num_tokens)
-        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, text, ids.shape[0])
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, text, ids.shape[0], negative_text,
+                             negative_context_lens)
         return self._step(ids, nm, text, opts, temperature, opts.choice_temperature, noise, seed, step, image_base, choice_noise)
 
     @torch.no_grad()
@@ -362,14 +408,15 @@ class Pipeline(nn.Module):
         """``sample`` behind its checks: one step that re-masks nm tokens, with the step's own temperature and choice temperature"""
         if self._on_cpu():
             return self._sample_cpu(ids, nm, text, opts.topk, temperature, noise, seed, opts.guidance_scale, opts.lens, choice_t,
-                                    choice_noise, opts.top_p)
+                                    choice_noise, opts.top_p, opts.negative, opts.negative_lens)
         if seed is None:
             seed = _draw_seed()
         eng = self.engine()
         ids = ids.to(eng.device, torch.int64).clone().contiguous()
         ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, opts.topk, temperature, nm, noise=noise, seed=seed, step=step,
                                     image_base=image_base, want_img=True, guidance_scale=opts.guidance_scale, context_lens=opts.lens,
-                                    choice_temperature=choice_t, choice_noise=choice_noise, top_p=opts.top_p)
+                                    choice_temperature=choice_t, choice_noise=choice_noise, top_p=opts.top_p,
+                                    negative_context=opts.negative, negative_lens=opts.negative_lens)
         return ids, img
 
     def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale, context_lens=None):
@@ -392,15 +439,16 @@ class Pipeline(nn.Module):
         return ids, img
 
     def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None, choice_t=0.0,
-                    choice_noise=None, top_p=1.0):
+                    choice_noise=None, top_p=1.0, negative=None, negative_lens=None):
         """generate.py:159-181 in plain torch for a pipeline that lives on the CPU.  The noise is drawn from the torch CPU
         generator like the reference's (`seed` re-seeds a private generator; `noise` overrides it); ties in top-k / argmax
         follow torch.  choice_t != 0: the re-masking sorts by choice_keys; its uniforms are `choice_noise`, or drawn behind the
-        token noise from the same generator.  top_p < 1: of the top-k values only those nucleus_keep keeps."""
+        token noise from the same generator.  top_p < 1: of the top-k values only those nucleus_keep keeps.  negative: the second
+        forward of a guided step takes this context (with negative_lens) instead of none."""
         tok = self.ids2tokens(ids)
         logits = self.tokens2logits(tok, text, context_lens)
         if guidance_scale is not None:
-            uncond = self.tokens2logits(tok, None)
+            uncond = self.tokens2logits(tok, negative, negative_lens)
             logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(guidance_scale)))
         val, ind = logits.topk(topk, dim=-1)
         if top_p < 1.0:
@@ -432,7 +480,8 @@ class Pipeline(nn.Module):
         imgs = []
         for step in range(timesteps):
             ids, img = self._sample_cpu(ids, nmask[step], context, opts.topk, temps[step], None, None if seed is None else seed + step,
-                                        opts.guidance_scale, opts.lens, ctemps[step] if ctemps else 0.0, None, opts.top_p)
+                                        opts.step_scale(step), opts.lens, ctemps[step] if ctemps else 0.0, None, opts.top_p, opts.negative,
+                                        opts.negative_lens)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
@@ -476,8 +525,13 @@ class Pipeline(nn.Module):
 
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
                      join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None,
-                     top_p=None):
+                     top_p=None, negative_context=None, negative_lens=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
+
+        guidance_scale: a number, or a sequence of `timesteps` finite numbers, one per step (``generate`` has the meaning); the captured
+        loop reads a schedule from device memory, so one graph serves every schedule.
+        negative_context [B, Ln, D] (None: the second pass of a guided step runs without a context) with negative_lens, its per-image
+        lengths: the negative prompt of ``generate``.  Every lane takes the rows of its micro-batch.
 
         streams > 1 (or a tuple of micro-batch sizes): the batch is cut into contiguous micro-batches that run CONCURRENTLY on separate HIP
         streams (own native handle + workspace each, same weights): memory-bound kernels of one micro-batch overlap
@@ -500,13 +554,16 @@ class Pipeline(nn.Module):
         topk: 1..n_embed, or None = no filter (n_embed); part of the key of a captured graph.
         top_p (None or 1.0: no nucleus filter): every step's nucleus mass, 0 < top_p <= 1 (see ``sample``); one value for the batch,
         so every lane takes it as it is; below 1 part of the key of a captured graph."""
-        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B)
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative_context, negative_lens,
+                             timesteps)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
 
         def run(e, v, ids, c, o, **kw):                   # the native loop of one engine pair: the whole batch, or one lane's images
+            if o.negative is not None or o.guidance_scales is not None:
+                kw.update(negative_context=o.negative, negative_lens=o.negative_lens, guidance_scales=o.guidance_scales)
             return e.generate(v, ids, c, temps, nmask, decode_flags, o.topk, seed=seed, use_graph=use_graph, want_device_imgs=host is None,
                               guidance_scale=o.guidance_scale, context_lens=o.lens, choice_temps=ctemps, top_p=o.top_p, **kw)
 
@@ -587,8 +644,17 @@ class Pipeline(nn.Module):
 
     def generate(self, text, timesteps=18, temperature=1.0, topk=5, save_interval=2, seed=None, image_base=0,
                  return_ids=False, keep_on_device=False, use_graph=None, streams=None, guidance_scale=None, mask_padding=False,
-                 context_lens=None, choice_temperature=None, top_p=None):
+                 context_lens=None, choice_temperature=None, top_p=None, negative_text=None, negative_context_lens=None):
         """Full decode loop (generate.py:183-198): list of (B,3,H,W) CPU tensors for steps % save_interval == 0.
+
+        guidance_scale (extension; None = the reference's loop): a number -- every step samples from ``uncond + guidance_scale *
+        (cond - uncond)`` (see ``sample``) -- or a sequence of ``timesteps`` finite numbers, step s guiding with its own: Muse
+        raises the scale over the steps, low early for diversity and high late for fidelity (``linear_guidance(timesteps, scale)``
+        is one such list).  One captured graph serves every schedule; a scalar keeps its path and its graph per value.
+
+        negative_text (extension; needs guidance_scale): a NEGATIVE prompt, one string for every image or a list of B strings, run
+        through the text model like ``text``.  The second pass of every step sees it instead of no text, so the images move away
+        from it.  With ``mask_padding=True`` its lengths come from the text model too; negative_context_lens gives them explicitly.
 
         The call is the fast path by default: the loop replays captured hipGraphs (first call eager, second call captures),
         in bf16 mode a batch of at least LANES_MIN_WORK (B * tokens * width: 33 images for d512, 22 for d768, 17 for d1024) runs
@@ -629,7 +695,17 @@ class Pipeline(nn.Module):
             context, context_lens = self.text_model(text, return_lens=True)
         else:
             context = self.text_model(text)
-        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B)
+        negative = None
+        if negative_text is not None:
+            prompts = [negative_text] * B if isinstance(negative_text, str) else list(negative_text)
+            if len(prompts) != B:
+                raise ValueError(f"negative_text: {len(prompts)} prompts for a batch of {B}")
+            if mask_padding and negative_context_lens is None:
+                negative, negative_context_lens = self.text_model(prompts, return_lens=True)
+            else:
+                negative = self.text_model(prompts)
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative, negative_context_lens,
+                             timesteps)
         if self._on_cpu():
             return self._generate_cpu(context, B, timesteps, temperature, opts, save_interval, seed, return_ids)
         eng = self.engine()
@@ -650,6 +726,8 @@ class Pipeline(nn.Module):
         flags = [step % save_interval == 0 for step in range(timesteps)]
         if context is not None:
             context = context.to(eng.device)
+        if opts.negative is not None:
+            opts = opts._replace(negative=opts.negative.to(eng.device))
         n_dec = sum(flags)
         if keep_on_device or n_dec == 0:
             ids, imgs = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base,

@@ -441,6 +441,46 @@ def guidance_combine(cond, uncond, scale, out=None, with_stats=False):
     return out
 
 
+def guidance_combine_dev(cond, uncond, scale_dev, out=None, with_stats=False):
+    """guidance_combine with the scale read by the kernel from `scale_dev`, an fp32 tensor of one element on the operands' device
+    (pmhip_guidance_combine_dev): for the same value the same bits as guidance_combine, logits and statistics.  The value is not
+    checked: whoever wrote it checked it."""
+    dev = _dev(cond, uncond, scale_dev)
+    if cond.shape != uncond.shape or cond.dtype != torch.float32 or uncond.dtype != torch.float32:
+        raise ValueError("guidance_combine_dev needs two fp32 tensors of one shape")
+    if scale_dev.dtype != torch.float32 or scale_dev.numel() != 1:
+        raise ValueError("guidance_combine_dev: scale_dev must be an fp32 tensor of one element on the operands' device")
+    out = torch.empty(cond.shape, device=dev, dtype=torch.float32) if out is None else out
+    if out.shape != cond.shape or out.dtype != torch.float32 or out.device != cond.device:
+        raise ValueError("guidance_combine_dev: `out` must be an fp32 tensor of the inputs' shape on their device")
+    if not (cond.is_contiguous() and uncond.is_contiguous() and out.is_contiguous()):
+        raise ValueError("guidance_combine_dev needs contiguous tensors (the kernel walks them as flat arrays)")
+    if cond.numel() % 4:
+        raise ValueError("guidance_combine_dev: the element count must be a multiple of 4")
+    stats = None
+    if with_stats:
+        if cond.shape[-1] % 64:
+            raise ValueError("guidance_combine_dev(with_stats=True): rows must be a multiple of 64 long")
+        stats = torch.empty(cond.shape[:-1] + (cond.shape[-1] // 64, 2), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_guidance_combine_dev(_p(cond), _p(uncond), _p(scale_dev), _p(out), cond.numel(), _p(stats),
+                                                     stream_ptr(dev)), "pmhip_guidance_combine_dev")
+    return (out, stats) if with_stats else out
+
+
+def guidance_scales(value, timesteps, what="guidance_scale"):
+    """a guidance schedule (a sequence of `timesteps` numbers, one per step) -> a list of floats, checked as the native entry checks
+    it: every scale finite"""
+    vals = value.detach().reshape(-1).tolist() if isinstance(value, torch.Tensor) else list(value)
+    if len(vals) != timesteps:
+        raise ValueError(f"{what}: {len(vals)} scales for {timesteps} steps")
+    out = [float(v) for v in vals]
+    for i, v in enumerate(out):
+        if not math.isfinite(v):
+            raise ValueError(f"{what}: step {i}: the scale {v} must be finite")
+    return out
+
+
 def embed_rows(table, ids, kpad, out_dtype):
     dev = _dev(table, ids)
     lib = _lib.load()

@@ -26,7 +26,7 @@ context of a session has the same width D, top-k <= 8 (the block-statistics samp
 top-k up to n_embed, and ``None`` for no filter, DESIGN.md section 4n, but a session does not -- a batch that mixes requests at
 and above 8 needs a second sampling launch chosen step by step, which is not built), and idle slots still run through
 the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the second tower pass: the
-unconditional pass runs at the session's batch size.
+unconditional pass runs at the session's batch size.  Requests carry no negative prompt and no guidance schedule (``Pipeline.generate`` has both).
 
 A choice temperature is per request too (``submit(choice_temperature=c)``): the request keeps MaskGIT's annealed value of each of
 its steps beside its temperatures and mask counts, the native step (pmhip_pipeline_step_slots_choice) reads one value per slot
