@@ -36,6 +36,7 @@
  *                                              stream itself (res_rows <= 0 or >= M: no row modulo)
  *         pmhip_gemm with an f32 residual      out == residual with ldo == ldr, res_rows covering all M rows
  *         pmhip_unshift_hilo, pmhip_remask(_slots), pmhip_remask_choice(_slots), pmhip_guidance_combine(_stats), pmhip_sample_rows* (ids_out == ids_in)
+ *         pmhip_remask_counts, pmhip_remask_choice_counts, pmhip_mask_tokens (ids), pmhip_composite (out == gen or orig)
  *         pmhip_guidance_combine_slots         out == cond (or uncond)
  *     Every element is read by the workgroup that writes it, before it writes it; the result equals the out-of-place call's bit
  *     for bit.  Any other overlap between an output and an input is undefined.
@@ -393,6 +394,29 @@ int pmhip_remask_choice(int64_t* ids, const float* scores, int num_mask, int64_t
  * plain key; the row of an idle slot is left untouched.  Philox noise only. */
 int pmhip_remask_choice_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, const float* choice_t_dev,
                               int64_t mask_id, int B, int N, pmhip_stream stream);
+/* A COUNT PER IMAGE (new entries within ABI 11): counts_dev is a DEVICE int32 [B].  The row of image b
+ * equals, bit for bit, pmhip_remask (pmhip_remask_choice) called on that row alone with num_mask = counts_dev[b] and the noise at
+ * row_base + b * N.  counts_dev[b] == 0 leaves row b untouched -- its workgroup leaves like an idle slot's; the entries above keep
+ * their clamp to 1 -- and so does a negative entry; a count above N masks the row.  In place like pmhip_remask.  Null pointers,
+ * bad shapes and a bad choice_t are PMHIP_EINVAL before anything is launched. */
+int pmhip_remask_counts(int64_t* ids, const float* scores, const int32_t* counts_dev /* [B] */, int64_t mask_id, int B, int N,
+                        pmhip_stream stream);
+int pmhip_remask_choice_counts(int64_t* ids, const float* scores, const int32_t* counts_dev /* [B] */, int64_t mask_id, int B, int N,
+                               float choice_t, const float* noise /* [B,N] or NULL */, uint64_t seed, uint32_t step, uint64_t row_base,
+                               pmhip_stream stream);
+
+/* Pixel-side operators of the edit call.
+ * pmhip_mask_tokens: pixel_mask uint8 [B,H,W], ids int64 [B, (H/patch) * (W/patch)] IN PLACE, counts_out int32 [B].  Token (r, c)
+ * of image b is regenerated iff ANY pixel of its patch x patch block is non-zero: its id becomes mask_id; counts_out[b] = how many
+ * tokens of image b are.  Every other id is left as it is; counts_out is written in exactly its B elements.
+ * patch >= 1, H % patch == 0, W % patch == 0.
+ * pmhip_composite: gen / orig / out fp32 [B,C,H,W], pixel_mask uint8 [B,H,W] broadcast over C: out = mask != 0 ? gen : orig,
+ * element-wise.  out may alias gen (or orig): every element is read by the thread that writes it.
+ * Null pointers and bad shapes are PMHIP_EINVAL before anything is launched. */
+int pmhip_mask_tokens(const uint8_t* pixel_mask, int patch, int64_t* ids, int64_t mask_id, int32_t* counts_out, int B, int H, int W,
+                      pmhip_stream stream);
+int pmhip_composite(const float* gen, const float* orig, const uint8_t* pixel_mask, float* out, int B, int C, int H, int W,
+                    pmhip_stream stream);
 
 /* Per-image GUIDANCE: a record parallel to pmhip_slot, which stays 32 bytes; the ABI version stays 11 (new entries only). */
 typedef struct pmhip_slot_guide { float scale; uint32_t on; } pmhip_slot_guide;   /* 8 bytes, one per image; on = 0: not guided */
@@ -730,6 +754,27 @@ int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids
                                      const float* ctemps_host /* [T] or NULL */, float top_p,
                                      const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
                                      const int32_t* neg_lens_host /* [B] or NULL */, const float* gscales_host /* [T] or NULL */);
+
+/* THE EDIT LOOP (new entry within ABI 11): pmhip_pipeline_generate_negative with three changes.
+ *   - nmask_img_host, a HOST int32 [T][B], replaces nmask_host: step t re-masks nmask_img_host[t * B + b] positions of image b
+ *     (the counts form of the re-masking kernel, its choice form when a choice temperature is active); 0 leaves the image's ids
+ *     as the step merged them.  The table travels through pinned memory into a handle-owned device table at a fixed address:
+ *     a captured loop bakes in the address, never the counts, so one graph per (B, L, T, topk, top_p, ...) serves every set of masks
+ *   - a decoded step decodes the MERGED ids -- where(ids == mask, pred, ids), taken before that step's re-masking -- instead of
+ *     the predictions at all positions: a position whose id the caller gave decodes from that id
+ *   - the loop starts from the caller's ids: PMHIP_GENERATE_FROM_MASK is refused, there is no shared step 0
+ * Everything else -- tower, statistics, sampler choice, guidance (scalar or per step), negative context, context lengths, choice
+ * temperatures, eager or captured under a graph key of its own -- is that entry's.
+ * Validated before anything is launched (PMHIP_EINVAL, ids untouched): what that entry validates, and every table entry in
+ * 0 .. tokens (the message names step and image). */
+int pmhip_pipeline_generate_edit(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                 const int32_t* ctx_lens_host, int T, const float* temps_host,
+                                 const int32_t* nmask_img_host /* [T][B] */, const unsigned char* decode_host, int topk, uint64_t seed,
+                                 uint64_t image_base, float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
+                                 size_t host_stride, pmhip_stream copy_stream, int guided, float guidance_scale,
+                                 const float* ctemps_host /* [T] or NULL */, float top_p,
+                                 const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                 const int32_t* neg_lens_host /* [B] or NULL */, const float* gscales_host /* [T] or NULL */);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

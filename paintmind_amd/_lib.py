@@ -172,6 +172,14 @@ PROTOTYPES = {
     "pmhip_pipeline_generate_negative": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
                                                C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
                                                f32, vp, i32, C.POINTER(i32), C.POINTER(f32)]),
+    # the edit call: a re-masking count per image, the pixel-side operators, the edit loop
+    "pmhip_remask_counts": (i32, [vp, vp, vp, i64, i32, i32, vp]),
+    "pmhip_remask_choice_counts": (i32, [vp, vp, vp, i64, i32, i32, f32, vp, u64, u32, u64, vp]),
+    "pmhip_mask_tokens": (i32, [vp, i32, vp, i64, vp, i32, i32, i32, vp]),
+    "pmhip_composite": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "pmhip_pipeline_generate_edit": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
+                                           C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
+                                           f32, vp, i32, C.POINTER(i32), C.POINTER(f32)]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),

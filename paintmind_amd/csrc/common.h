@@ -115,6 +115,11 @@ struct PmStepSource {
     // source with top_p < 1 is refused.  1 (the default): no filter, the kernels that ran before.
     float top_p = 1.f;
     PmStepSource with_top_p(float p) const { PmStepSource r = *this; r.top_p = p; return r; }
+    // The re-masking count PER IMAGE (pm_remask only): a device int32 [B] beside a BATCH or PARAMS source --
+    // image b re-masks counts[b] positions instead of num_mask / gp->nmask[step], 0 leaving its row untouched; the choice values keep
+    // coming from the source's kind.  NULL (the default): the kernels that ran before.  Appended: nothing above moves.
+    const int32_t* counts = nullptr;
+    PmStepSource with_counts(const int32_t* dev) const { PmStepSource r = *this; r.counts = dev; return r; }
 };
 // a step's nucleus mass: finite, 0 < top_p <= 1
 int pm_check_top_p(const char* who, float p);

@@ -773,6 +773,7 @@ struct pmhip_s2 {
     PinnedRing slots_ring;
     PinnedRing lens_ring;           // per-image context lengths of a call (ctx_lens_host): B int32 -> workspace "ctx.lens"
     PinnedRing neg_lens_ring;       // ... and of its negative context (neg_lens_host): B int32 -> workspace "neg.lens"
+    PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
     int slots_one_pass = 0, slots_two_pass = 0;
     int slots_ctx_B = 0, slots_ctx_L = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
@@ -1023,7 +1024,11 @@ struct Step {
     // the token draw's nucleus mass: the batch's value, with the scalars and with gp alike (a kernel argument
     // of a captured step, like top-k); a slots step has none.  1: no filter.
     float top_p = 1.f;
-    PmStepSource source(int tokens) const {
+    // the edit loop: counts = the step's re-masking counts, a device int32 [B] beside the scalars or gp (NULL:
+    // one count for the batch); decode_merged: the step's image -- inline or deferred -- is decoded from the MERGED ids
+    const int32_t* counts = nullptr; bool decode_merged = false;
+    PmStepSource source(int tokens) const { return source_of(tokens).with_counts(counts); }
+    PmStepSource source_of(int tokens) const {
         if (slots) { const PmStepSource p = PmStepSource::per_image(slots, tokens); return (choice_dev ? p.with_choice_dev(choice_dev) : p).with_top_p(top_p); }
         if (gp) { const PmStepSource p = PmStepSource::params(gp, topk, step); return (choice_params ? p.with_choice_params() : p).with_top_p(top_p); }
         return PmStepSource::batch(topk, temperature, num_mask, seed, step, image_base * (uint64_t)tokens).with_choice(choice_t, choice_noise).with_top_p(top_p);
@@ -1072,6 +1077,9 @@ int step_tail(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, int B, const Step& st
     PM_TRY(step_bufs(s2, M, st.shared0, b, s));               // step_tower (or the shared step 0) filled the logits
     PM_TRY(pm_sample_rows(b.logits, c.n_embed, b.lstats, st.shared0 ? c.tokens : 0, ids, (int64_t)c.n_embed, st.noise, b.pred, ids, b.score,
                           M, c.n_embed, src, s));
+    // the edit loop: the buffer the decode reads takes the merged ids (the sampler wrote them as ids_out) before the re-masking
+    // launch below touches them -- the decode itself may run here or, deferred, beside the next step's tower
+    if (st.decode_merged) PM_TRY(copy16_async(b.pred, ids, (size_t)M * 8, s));
     if (img_out) PM_TRY(decode_pred(s2, vq, B, img_out, s));
     PM_TRY(copy_aux(b, (size_t)M, pred_out, score_out, s));
     return pm_remask(ids, b.score, (int64_t)c.n_embed, B, c.tokens, src, s);
@@ -1307,6 +1315,9 @@ struct GenCall {
     // steps' guidance scales, host [T] (then `guidance` is NULL: the scalar is ignored)
     const float* neg_context = nullptr; int Ln = 0; const int32_t* neg_lens = nullptr;
     const float* gscales = nullptr;
+    // pmhip_pipeline_generate_edit: the re-masking counts per step and image, host [T][B], instead of nmask_host (then NULL); a
+    // decoded step of such a loop decodes the merged ids
+    const int32_t* nmask_img = nullptr;
     bool guided() const { return guidance || gscales; }
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
@@ -1375,7 +1386,16 @@ struct HostDelivery {
 int pipeline_generate(const GenCall& c) {
     pmhip_s2* s2 = c.s2; pmhip_vqgan* vq = c.vq;
     const int B = c.B, T = c.T;
-    PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && c.nmask_host, "pipeline_generate: bad arguments");
+    const bool edit = c.nmask_img != nullptr;
+    PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && (c.nmask_host || edit), "pipeline_generate: bad arguments");
+    if (edit) {                                               // checked before anything is launched
+        PM_REQUIRE(!(c.use_graph & PMHIP_GENERATE_FROM_MASK), "%s: an edit starts from the caller's ids, the from-mask flag is refused", c.who);
+        for (int t = 0; t < T; ++t)
+            for (int b = 0; b < B; ++b)
+                PM_REQUIRE(c.nmask_img[(size_t)t * B + b] >= 0 && c.nmask_img[(size_t)t * B + b] <= s2->cfg.tokens,
+                           "%s: step %d, image %d: the re-masking count %d must be in [0, %d]", c.who, t, b, c.nmask_img[(size_t)t * B + b],
+                           s2->cfg.tokens);
+    }
     PM_REQUIRE(!c.guided() || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
     PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
     const bool sched = c.gscales != nullptr, neg = c.neg_context != nullptr;
@@ -1447,7 +1467,7 @@ int pipeline_generate(const GenCall& c) {
         hp.seed = c.seed;
         hp.row_base = c.image_base * (uint64_t)s2->cfg.tokens;
         for (int t = 0; t < T; ++t) {
-            hp.temps[t] = c.temps_host[t]; hp.nmask[t] = c.nmask_host[t]; hp.ctemps[t] = choice ? c.ctemps[t] : 0.f;
+            hp.temps[t] = c.temps_host[t]; hp.nmask[t] = edit ? 0 : c.nmask_host[t]; hp.ctemps[t] = choice ? c.ctemps[t] : 0.f;
             hp.gscales[t] = sched ? c.gscales[t] : 0.f;
         }
         // a loop stages what it always staged: without choice temperatures the block up to ctemps, without a guidance schedule the
@@ -1460,14 +1480,32 @@ int pipeline_generate(const GenCall& c) {
         return PMHIP_OK;
     };
 
+    // The edit loop's count table, T * B int32 at a fixed address: step t's re-masking launch -- eager, captured or replayed -- reads
+    // its B counts at gcounts + t * B, so a graph bakes in the address and never the counts.  Refreshed per call like the block above.
+    int32_t* gcounts = nullptr;
+    auto stage_counts = [&]() -> int {
+        const size_t bytes = ((size_t)T * B * 4 + 15) & ~(size_t)15;
+        WS(s2->ws, "gen.counts", bytes, gcounts);
+        std::vector<int32_t> padded(bytes / 4, 0);
+        std::copy(c.nmask_img, c.nmask_img + (size_t)T * B, padded.begin());
+        PM_TRY(s2->counts_ring.reserve(bytes));
+        PM_TRY(s2->counts_ring.acquire());
+        PM_TRY(s2->counts_ring.stage(gcounts, 0, padded.data(), bytes, s));
+        PM_TRY(s2->counts_ring.commit(s));
+        return PMHIP_OK;
+    };
+
     if (!graph) {
         int d = 0;
         if (sched) PM_TRY(stage_params());
+        if (edit) PM_TRY(stage_counts());
         if (from_mask) PM_TRY(fill_ids_async(c.ids, (int64_t)s2->cfg.n_embed, n_ids, s));
         for (int t = 0; t < T; ++t) {
             const bool dec = c.decodes(t);
             float* img = !dec ? nullptr : (gimgs ? gimgs : c.imgs_out) + (size_t)d * img_elems;
-            Step st{c.topk, c.temps_host[t], c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0, c.guidance};
+            Step st{c.topk, c.temps_host[t], edit ? 0 : c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0,
+                    c.guidance};
+            if (edit) { st.counts = gcounts + (size_t)t * B; st.decode_merged = dec; }
             if (choice) st.choice_t = c.ctemps[t];             // 0 (the last step of an annealed loop): the plain launch, the same keys
             st.top_p = c.top_p;
             st.negative = neg;
@@ -1488,6 +1526,7 @@ int pipeline_generate(const GenCall& c) {
     int64_t* gids;
     WS(s2->ws, "gen.ids", ids_bytes, gids);
     PM_TRY(stage_params());
+    if (edit) PM_TRY(stage_counts());
     if (from_mask) PM_TRY(fill_ids_async(gids, (int64_t)s2->cfg.n_embed, n_ids, s));
     else PM_TRY(copy16_async(gids, c.ids, ids_bytes, s));
 
@@ -1513,6 +1552,7 @@ int pipeline_generate(const GenCall& c) {
     key += overlap ? "o1" : "o0";
     if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
     if (c.ctx_lens) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
+    if (edit) key += "e";                                     // the counts form of the re-masking kernel and the merged decode; the counts are not in the key
     if (choice) key += "c";                                   // the choice form of the re-masking kernel; the temperatures are not in the key
     if (c.top_p < 1.f) {                                      // the nucleus kernel, the mass its argument in the captured graph: one graph per value
         unsigned bits;
@@ -1548,6 +1588,7 @@ int pipeline_generate(const GenCall& c) {
             st.top_p = c.top_p;
             st.negative = neg;
             if (sched) st.guidance_dev = &gparams->gscales[t];
+            if (edit) { st.counts = gcounts + (size_t)t * B; st.decode_merged = c.decodes(t); }
             PM_TRY(tower(gids, st, on));
             if (need_join) { PM_HIP(hipStreamWaitEvent(on, ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
             float* img = (u.decode_inline && c.decodes(t)) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
@@ -1575,9 +1616,9 @@ static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan*
                                   int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride, pmhip_stream copy_stream,
                                   int guided, float guidance_scale, const float* ctemps_host, float top_p,
                                   const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
-                                  const float* gscales_host = nullptr) {
+                                  const float* gscales_host = nullptr, const int32_t* nmask_img_host = nullptr) {
     PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
-    const char* neg_who = "pipeline_generate_negative";
+    const char* neg_who = nmask_img_host ? narrow : "pipeline_generate_negative";
     PM_TRY(check_negative(neg_who, neg_context, Ln, neg_lens_host, gscales_host != nullptr, guided != 0, context && L > 0, B));
     if (gscales_host) {
         PM_REQUIRE(T <= PM_MAX_STEPS, "%s: a guidance schedule serves at most %d steps, T=%d", neg_who, PM_MAX_STEPS, T);
@@ -1585,10 +1626,11 @@ static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan*
     }
     GenCall c{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
               use_graph, stream, imgs_host, host_stride, copy_stream, guided && !gscales_host ? &guidance_scale : nullptr, ctx_lens_host,
-              neg_context || gscales_host ? neg_who : top_p != 1.f ? "pipeline_generate_nucleus" : ctemps_host ? "pipeline_generate_choice" : narrow,
+              nmask_img_host || neg_context || gscales_host ? neg_who : top_p != 1.f ? "pipeline_generate_nucleus" : ctemps_host ? "pipeline_generate_choice" : narrow,
               ctemps_host, top_p};
     c.neg_context = neg_context; c.Ln = Ln; c.neg_lens = neg_lens_host;
     c.gscales = gscales_host;
+    c.nmask_img = nmask_img_host;
     return pipeline_generate(c);
 }
 
@@ -1803,3 +1845,18 @@ extern "C" int pmhip_s2_switches(const pmhip_s2* h) {
     return h ? h->sw.key() + (h->sw.blocking_wait ? 16 : 0) + (direct_dispatch_off() ? 32 : 0) : -1;
 }
 extern "C" int pmhip_vqgan_switches(const pmhip_vqgan* h) { return h ? h->sw.key() + (h->sw.blocking_wait ? 16 : 0) : -1; }
+
+// the edit loop (include/pmhip.h): pmhip_pipeline_generate_negative with a re-masking count per step and image, a decode of the
+// merged ids, and the caller's ids as the start
+extern "C" int pmhip_pipeline_generate_edit(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                            const int32_t* ctx_lens_host, int T, const float* temps_host, const int32_t* nmask_img_host,
+                                            const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                            float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                            pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
+                                            float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                            const float* gscales_host) {
+    PM_REQUIRE(nmask_img_host, "pipeline_generate_edit: null count table");
+    return pipeline_generate_call("pipeline_generate_edit", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nullptr, decode_host,
+                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host, nmask_img_host);
+}

@@ -246,6 +246,50 @@ __global__ __launch_bounds__(THREADS) void guidance_slots_kernel(const float* co
                          reinterpret_cast<float4*>(out) + base, block_stats, n4, g.scale, base);
 }
 
+// The pixel side of an edit.  mask_tokens: one workgroup per image; a thread owns the tokens tid, tid + THREADS,
+// ... of the image's gh x gw grid, reads the patch x patch pixels of each and, when any is non-zero, writes mask_id over the token's
+// id; the workgroup's count of such tokens (wave shuffles, then THREADS / 64 words of LDS) goes to counts_out[image]: no atomics,
+// every count written exactly once.
+__global__ __launch_bounds__(THREADS) void mask_tokens_kernel(const uint8_t* __restrict__ pixel_mask, int patch, int64_t* __restrict__ ids,
+                                                              int64_t mask_id, int32_t* __restrict__ counts_out, int H, int W) {
+    __shared__ int wave_count[THREADS / 64];
+    const int gw = W / patch, ntok = (H / patch) * gw;
+    const uint8_t* pm = pixel_mask + (size_t)blockIdx.x * H * W;
+    int64_t* row = ids + (size_t)blockIdx.x * ntok;
+    int count = 0;
+    for (int t = threadIdx.x; t < ntok; t += THREADS) {
+        const uint8_t* p0 = pm + (size_t)(t / gw) * patch * W + (size_t)(t % gw) * patch;
+        bool lit = false;
+        for (int y = 0; y < patch; ++y)
+            for (int x = 0; x < patch; ++x) lit = lit || p0[(size_t)y * W + x] != 0;
+        if (lit) {
+            row[t] = mask_id;
+            ++count;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o, 64);
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < THREADS / 64; ++w) total += wave_count[w];
+        counts_out[blockIdx.x] = total;
+    }
+}
+
+// composite: out = mask ? gen : orig over [B,C,H,W], the mask [B,H,W] broadcast over C (no __restrict__ on the planes: out is
+// documented to alias gen or orig; every element is read and then written by the same lane)
+__global__ __launch_bounds__(THREADS) void composite_kernel(const float* gen, const float* orig, const uint8_t* __restrict__ pixel_mask,
+                                                            float* out, size_t total, size_t chw, size_t hw) {
+    for (size_t idx = (size_t)blockIdx.x * THREADS + threadIdx.x; idx < total; idx += (size_t)gridDim.x * THREADS) {
+        const size_t b = idx / chw, p = idx % hw;
+        const float g = gen[idx], o = orig[idx];
+        out[idx] = pixel_mask[b * hw + p] != 0 ? g : o;
+    }
+}
+
 inline int grid_for(size_t total) {
     size_t blocks = (total + THREADS - 1) / THREADS;
     if (blocks > 256 * 8) blocks = 256 * 8;       // grid-stride the rest
@@ -626,6 +670,32 @@ extern "C" int pmhip_guidance_combine_slots(const float* cond, const float* unco
     else
         hipLaunchKernelGGL(guidance_slots_kernel<false>, dim3(chunks, B), dim3(THREADS), 0, s, cond, uncond, guides, slots, out, n4,
                            (float2*)nullptr);
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
+}
+
+// pixel mask -> token mask (include/pmhip.h): a token is regenerated iff any pixel of its patch is non-zero
+extern "C" int pmhip_mask_tokens(const uint8_t* pixel_mask, int patch, int64_t* ids, int64_t mask_id, int32_t* counts_out, int B, int H,
+                                 int W, pmhip_stream stream) {
+    PM_REQUIRE(pixel_mask && ids && counts_out, "mask_tokens: null pointer");
+    PM_REQUIRE(B > 0 && H > 0 && W > 0 && patch > 0 && H % patch == 0 && W % patch == 0,
+               "mask_tokens: bad shape B=%d H=%d W=%d patch=%d (H and W must be multiples of patch)", B, H, W, patch);
+    hipStream_t s = (hipStream_t)stream;
+    PmTimer tm(FAM_ROWOPS, s);
+    hipLaunchKernelGGL(mask_tokens_kernel, dim3(B), dim3(THREADS), 0, s, pixel_mask, patch, ids, mask_id, counts_out, H, W);
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
+}
+
+// out = pixel_mask ? gen : orig, the mask broadcast over the channels; out may alias gen (or orig)
+extern "C" int pmhip_composite(const float* gen, const float* orig, const uint8_t* pixel_mask, float* out, int B, int C, int H, int W,
+                               pmhip_stream stream) {
+    PM_REQUIRE(gen && orig && pixel_mask && out, "composite: null pointer");
+    PM_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "composite: bad shape B=%d C=%d H=%d W=%d", B, C, H, W);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t hw = (size_t)H * W, chw = hw * C, total = chw * B;
+    PmTimer tm(FAM_ROWOPS, s);
+    hipLaunchKernelGGL(composite_kernel, dim3(grid_for(total)), dim3(THREADS), 0, s, gen, orig, pixel_mask, out, total, chw, hw);
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
 }

@@ -536,6 +536,29 @@ __global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict
 #include "remask_select.h"
 }
 
+// COUNTS (pmhip_remask_counts): num_mask = counts[image], a device int32 per image -- the third source of the
+// count beside the arguments / gp and the slot records, a kernel of its own so that theirs keep their arguments and their code.  The
+// workgroup of an image whose count is 0 leaves like an idle slot's (before any barrier), its row untouched: remask_select.h's
+// clamp to 1 is the other sources'.
+template <int E>
+__global__ __launch_bounds__(THREADS) void remask_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
+                                                                const int32_t* __restrict__ counts, int64_t mask_id, int N) {
+    constexpr int NP = THREADS * E;
+    __shared__ unsigned long long xs[NP];
+    const int num_mask = counts[blockIdx.x];
+    if (num_mask <= 0) return;
+    const int tid = threadIdx.x, base = tid * E;
+    const float* sc = scores + (size_t)blockIdx.x * N;
+    unsigned long long key[E], mine[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = base + e;
+        key[e] = i < N ? remask_key(sc[i], i) : 0ull;
+        mine[e] = key[e];
+    }
+#include "remask_select.h"
+}
+
 // The CHOICE form (pmhip_remask_choice, pmhip_remask_choice_slots): MaskGIT's perturbed confidence.  With the
 // image's choice temperature t (image_choice) an element with score s sorts by
 //   s                                                           t == 0 (the plain key, bit for bit), or s < 0 (a given id: no draw)
@@ -556,38 +579,25 @@ __global__ __launch_bounds__(THREADS) void remask_choice_kernel(int64_t* __restr
     num_mask = ic.num_mask;
     const int tid = threadIdx.x, base = tid * E;
     const float* sc = scores + (size_t)blockIdx.x * N;
-    // one element at a time (a Philox and three logf each: unrolled E = 16 times they would not fit the registers), through the
-    // thread's own E words of xs, which nobody else touches before the first barrier
-#pragma unroll 1
-    for (int e = 0; e < E; ++e) {
-        const int i = base + e;
-        unsigned long long k = 0ull;
-        if (i < N) {
-            float s = sc[i];
-            if (ic.t != 0.f && !(s < 0.f)) {
-                float u;
-                if (noise) {
-                    u = noise[(size_t)blockIdx.x * N + i];
-                } else {
-                    const uint64_t grow = ic.base + (uint64_t)i;
-                    const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), 0xFFFFFFFFu, ic.step),
-                                                    make_uint2((uint32_t)ic.seed, (uint32_t)(ic.seed >> 32)));
-                    u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
-                }
-                const float ph = 1.0f - s;
-                const float conf = logf(fmaxf(ph, 0x1p-24f));
-                s = -fmaf(ic.t, gumbel_from_uniform(u), conf);
-            }
-            k = remask_key(s, i);
-        }
-        xs[i] = k;
-    }
-    unsigned long long key[E], mine[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        key[e] = xs[base + e];
-        mine[e] = key[e];
-    }
+#include "remask_choice_keys.h"
+#include "remask_select.h"
+}
+
+// the counts form of the choice kernel: counts[image] positions, the choice values as in the scalar form (the arguments, or gp)
+template <int E>
+__global__ __launch_bounds__(THREADS) void remask_choice_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
+                                                                       const int32_t* __restrict__ counts, int64_t mask_id, int N,
+                                                                       const PmGenParams* __restrict__ gp, int step, float choice_t,
+                                                                       const float* __restrict__ noise, uint64_t seed, uint64_t row_base) {
+    constexpr int NP = THREADS * E;
+    __shared__ unsigned long long xs[NP];
+    const int num_mask = counts[blockIdx.x];
+    if (num_mask <= 0) return;
+    ImageChoice ic{num_mask, choice_t, seed, (uint32_t)step, row_base};
+    image_choice<false>(ic, blockIdx.x, N, gp, nullptr, nullptr);      // t, seed, step and the image's noise base; the count stays the table's
+    const int tid = threadIdx.x, base = tid * E;
+    const float* sc = scores + (size_t)blockIdx.x * N;
+#include "remask_choice_keys.h"
 #include "remask_select.h"
 }
 
@@ -708,15 +718,26 @@ int pm_check_choice_t(const char* who, float t) {
 
 int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, const PmStepSource& src, pmhip_stream stream) {
     const bool slots = src.kind == PmStepSource::SLOTS;
+    const bool counts = src.counts != nullptr;             // the count of image b from counts[b]; everything else from the source's kind
     const bool choice = src.choice_on();
-    const char* who = slots ? (choice ? "remask_choice_slots" : "remask_slots") : (choice ? "remask_choice" : "remask");
+    const char* who = counts ? (choice ? "remask_choice_counts" : "remask_counts")
+                             : slots ? (choice ? "remask_choice_slots" : "remask_slots") : (choice ? "remask_choice" : "remask");
     PM_REQUIRE(ids && scores && (!slots || src.slots) && (src.kind != PmStepSource::PARAMS || src.gp), "%s: null pointer", who);
+    PM_REQUIRE(!(slots && counts), "%s: a count table beside slot records", who);
     PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "%s: bad shape B=%d N=%d (N <= 4096)", who, B, N);
     int per_thread = 1;                                    // E: the power of two with THREADS * E >= N
     while (THREADS * per_thread < N) per_thread <<= 1;
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_SAMPLE, s);
     pick<1, 2, 4, 8, 16>(per_thread, [&](auto E) {
+        if (counts) {
+            if (choice)
+                hipLaunchKernelGGL((remask_choice_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.counts, mask_id, N, src.gp,
+                                   (int)src.step, src.choice_t, src.choice_noise, src.seed, src.row_base);
+            else
+                hipLaunchKernelGGL((remask_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.counts, mask_id, N);
+            return;
+        }
         pick<0, 1>(slots, [&](auto SLOTS) {
             if (choice)
                 hipLaunchKernelGGL((remask_choice_kernel<E(), SLOTS() == 1>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.num_mask, mask_id,
@@ -752,4 +773,21 @@ extern "C" int pmhip_remask_choice_slots(int64_t* ids, const float* scores, cons
                                          int64_t mask_id, int B, int N, pmhip_stream stream) {
     PM_REQUIRE(choice_t_dev, "remask_choice_slots: null pointer");
     return pm_remask(ids, scores, mask_id, B, N, PmStepSource::per_image(slots, N).with_choice_dev(choice_t_dev), stream);
+}
+
+// the counts forms: image b re-masks counts_dev[b] positions, 0 leaving its row untouched; row b is
+// pmhip_remask / pmhip_remask_choice on that row alone with num_mask = counts_dev[b] (noise at row_base + b * N), bit for bit
+extern "C" int pmhip_remask_counts(int64_t* ids, const float* scores, const int32_t* counts_dev, int64_t mask_id, int B, int N,
+                                   pmhip_stream stream) {
+    PM_REQUIRE(counts_dev, "remask_counts: null pointer");
+    return pm_remask(ids, scores, mask_id, B, N, PmStepSource::batch(0, 0.f, 0, 0, 0, 0).with_counts(counts_dev), stream);
+}
+
+extern "C" int pmhip_remask_choice_counts(int64_t* ids, const float* scores, const int32_t* counts_dev, int64_t mask_id, int B, int N,
+                                          float choice_t, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base,
+                                          pmhip_stream stream) {
+    PM_REQUIRE(counts_dev, "remask_choice_counts: null pointer");
+    PM_TRY(pm_check_choice_t("remask_choice_counts", choice_t));
+    return pm_remask(ids, scores, mask_id, B, N,
+                     PmStepSource::batch(0, 0.f, 0, seed, step, row_base).with_choice(choice_t, noise).with_counts(counts_dev), stream);
 }

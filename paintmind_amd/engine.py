@@ -412,8 +412,13 @@ class S2Engine:
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
                  host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
-                 choice_temps=None, top_p=None, negative_context=None, negative_lens=None, guidance_scales=None):
+                 choice_temps=None, top_p=None, negative_context=None, negative_lens=None, guidance_scales=None, nmask_img=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
+
+        nmask_img (None = the loops below): the EDIT loop (pmhip_pipeline_generate_edit) -- T rows of B integers, step t re-masking
+        nmask_img[t][b] positions of image b (0: none) instead of nmask[t] of every image; a decoded step then decodes the merged
+        ids, not the predictions at all positions, and the loop starts from `ids` (from_mask is refused).  `nmask` is ignored.
+        The captured loop reads the table from device memory: one graph serves every set of masks.
 
         negative_context / negative_lens: as in ``sample``.  guidance_scales: one finite scale per step (a list of T floats) instead of
         the one guidance_scale, which is then ignored -- the captured loop reads them from device memory: one graph serves every
@@ -458,7 +463,15 @@ class S2Engine:
             host_stride = buf.shape[1] * per_img
             copy_stream = C.c_void_p(cstream.cuda_stream)
         temps_c = (C.c_float * T)(*[float(t) for t in temps])
-        nmask_c = (C.c_int * T)(*[int(n) for n in nmask])
+        if nmask_img is not None:
+            rows = [[int(n) for n in row] for row in nmask_img]
+            if len(rows) != T or any(len(row) != B for row in rows):
+                raise ValueError(f"generate: nmask_img must hold {T} rows of {B} counts")
+            if from_mask:
+                raise ValueError("generate: an edit loop starts from its ids (from_mask)")
+            nmask_c = (C.c_int * (T * B))(*[n for row in rows for n in row])
+        else:
+            nmask_c = (C.c_int * T)(*[int(n) for n in nmask])
         dec_c = (C.c_ubyte * T)(*[1 if f else 0 for f in decode_flags])
         flags = ((_lib.GENERATE_GRAPH if use_graph else 0) | (_lib.GENERATE_CONCURRENT_LANES if concurrent_lanes else 0) |
                  (_lib.GENERATE_FROM_MASK if from_mask else 0))
@@ -471,7 +484,9 @@ class S2Engine:
             args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
                     temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
                     host_stride, copy_stream, int(guided), float(guidance_scale or 0.0), choice_temps, nucleus)
-            if neg is None and gscales is None:
+            if nmask_img is not None:
+                check(self.lib.pmhip_pipeline_generate_edit(*args, _p(neg), Ln, neg_lens, gscales), "pmhip_pipeline_generate_edit")
+            elif neg is None and gscales is None:
                 check(self.lib.pmhip_pipeline_generate_nucleus(*args), "pmhip_pipeline_generate_nucleus")
             else:
                 check(self.lib.pmhip_pipeline_generate_negative(*args, _p(neg), Ln, neg_lens, gscales), "pmhip_pipeline_generate_negative")

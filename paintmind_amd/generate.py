@@ -44,6 +44,20 @@ def num_token_masked(mask_ratio, num_tokens):
     return max(int(r), 1)
 
 
+def edit_schedule(m, timesteps):
+    """the re-masking counts of an EDIT of m tokens over T steps (``Pipeline.edit``) -> a list of T ints.
+    MaskGIT's rule, counted over the region: with c_0 = m, step s < T - 1 re-masks
+    n_s = max(0, min(max(int(cosine((s + 1) / T) * m), 1), c_s - 1)) and c_{s+1} = n_s; the last step re-masks 0.  At least one
+    token is committed per step, nothing is left at the end, and -- n_s being below the c_s positions step s took -- a given id is
+    never re-masked.  The cosine is ``mask_schedule``'s, float64."""
+    out, c = [], int(m)
+    for step in range(timesteps - 1):
+        n = max(0, min(max(int(mask_schedule((step + 1) / timesteps) * m), 1), c - 1))
+        out.append(n)
+        c = n
+    return out + [0]
+
+
 def choice_schedule(timesteps, choice_temperature):
     """MaskGIT's annealed choice temperature: step s of T re-masks with t_s = choice_temperature * (1 - (s + 1) / T), evaluated in
     double precision and rounded to fp32 once (what the kernels take); the last step's value is exactly 0.  None or 0 -> None (the
@@ -439,12 +453,14 @@ class Pipeline(nn.Module):
         return ids, img
 
     def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None, choice_t=0.0,
-                    choice_noise=None, top_p=1.0, negative=None, negative_lens=None):
+                    choice_noise=None, top_p=1.0, negative=None, negative_lens=None, counts=None):
         """generate.py:159-181 in plain torch for a pipeline that lives on the CPU.  The noise is drawn from the torch CPU
         generator like the reference's (`seed` re-seeds a private generator; `noise` overrides it); ties in top-k / argmax
         follow torch.  choice_t != 0: the re-masking sorts by choice_keys; its uniforms are `choice_noise`, or drawn behind the
         token noise from the same generator.  top_p < 1: of the top-k values only those nucleus_keep keeps.  negative: the second
-        forward of a guided step takes this context (with negative_lens) instead of none."""
+        forward of a guided step takes this context (with negative_lens) instead of none.  counts (a list of B ints; None = the
+        reference's step): the EDIT step -- image b re-masks counts[b] positions (0: none) instead of nm, and no image is decoded
+        (``edit`` decodes the merged ids of its last step itself)."""
         tok = self.ids2tokens(ids)
         logits = self.tokens2logits(tok, text, context_lens)
         if guidance_scale is not None:
@@ -459,7 +475,7 @@ class Pipeline(nn.Module):
             noise = torch.rand(logits.shape, generator=g)
         gumbel = -torch.log((-torch.log(noise.clamp(min=1e-20))).clamp(min=1e-20))
         pred = (filtered / max(temperature, 1e-10) + gumbel).argmax(dim=-1)
-        img = self.vqgan.decode_from_indice(pred)            # decoded from the predictions at ALL positions (:165)
+        img = None if counts is not None else self.vqgan.decode_from_indice(pred)   # decoded from the predictions at ALL positions (:165)
         is_mask = ids == self.mask_token_id
         ids = torch.where(is_mask, pred, ids)
         scores = 1 - logits.softmax(dim=-1).gather(2, pred[..., None])[..., 0]
@@ -468,6 +484,11 @@ class Pipeline(nn.Module):
             if choice_noise is None:
                 choice_noise = torch.rand(scores.shape, generator=g)
             scores = choice_keys(scores, choice_t, choice_noise.to(scores.dtype))
+        if counts is not None:
+            for b, n in enumerate(counts):
+                if n > 0:
+                    ids[b, scores[b].topk(n).indices] = self.mask_token_id
+            return ids, img
         ids = ids.scatter(1, scores.topk(nm, dim=-1).indices, self.mask_token_id)
         return ids, img
 
@@ -799,18 +820,147 @@ class Pipeline(nn.Module):
             ids, out = self._step(ids, nmask[step], text, opts, temps[step], ctemps[step] if ctemps else 0.0, seed=seed, step=step)
         return (out, ids) if return_ids else out
 
+    def _edit_masks(self, img, mask, token_mask):
+        """the masks of an ``edit`` call, checked -> (token mask bool [B, g, g] or None, pixel mask uint8 [B, H, W]); with a token
+        mask the pixel mask is that of its patches"""
+        if (mask is None) == (token_mask is None):
+            raise ValueError("edit: give exactly one of mask (pixels) and token_mask (tokens)")
+        if img.dim() != 4:
+            raise ValueError(f"edit: img must be [B, C, H, W], got {tuple(img.shape)}")
+        B, _, H, W = img.shape
+        if H != self.image_size or W != self.image_size:
+            raise ValueError(f"edit: img must be {self.image_size} x {self.image_size}, got {H} x {W}")
+        p = self.patch_size
+        g = self.image_size // p
+        if token_mask is not None:
+            tm = torch.as_tensor(token_mask)
+            if tm.dtype != torch.bool or tuple(tm.shape) not in ((B, g, g), (g, g)):
+                raise ValueError(f"edit: token_mask must be a bool [{B}, {g}, {g}] or [{g}, {g}] tensor, got {tm.dtype} {tuple(tm.shape)}")
+            tm = tm.to(img.device).expand(B, g, g)
+            return tm, tm.repeat_interleave(p, 1).repeat_interleave(p, 2).to(torch.uint8).contiguous()
+        pm = torch.as_tensor(mask)
+        if tuple(pm.shape) == (B, 1, H, W):
+            pm = pm[:, 0]
+        if tuple(pm.shape) not in ((B, H, W), (H, W)):
+            raise ValueError(f"edit: mask must be [{B}, {H}, {W}], [{B}, 1, {H}, {W}] or [{H}, {W}], got {tuple(pm.shape)}")
+        return None, (pm.to(img.device) != 0).expand(B, H, W).to(torch.uint8).contiguous()
+
+    def edit_ids(self, ids, counts, context, timesteps, temperature, opts, seed, image_base=0, use_graph=False):
+        """the EDIT loop on device tensors (pmhip_pipeline_generate_edit): ids int64 [B, N] with the mask id where a token is
+        regenerated, counts = how many per image (a list of B ints), opts the call's ``_Options``.  Step t re-masks
+        ``edit_schedule(counts[b], timesteps)[t]`` positions of image b; the last step is decoded, from the merged ids.
+        -> (final ids [B, N], image [B, C, H, W]); ``ids`` is left as it is."""
+        eng = self.engine()
+        B = ids.shape[0]
+        temps, _, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
+        per_image = [edit_schedule(m, timesteps) for m in counts]
+        table = [[per_image[b][t] for b in range(B)] for t in range(timesteps)]
+        kw = {}
+        if opts.negative is not None or opts.guidance_scales is not None:
+            kw.update(negative_context=opts.negative, negative_lens=opts.negative_lens, guidance_scales=opts.guidance_scales)
+        ids = self._start_ids(B, ids, eng.device)
+        ids, imgs = eng.generate(self.vqgan.engine(), ids, context, temps, None, [False] * (timesteps - 1) + [True], opts.topk, seed=seed,
+                                 image_base=image_base, use_graph=use_graph, guidance_scale=opts.guidance_scale, context_lens=opts.lens,
+                                 choice_temps=ctemps, top_p=opts.top_p, nmask_img=table, **kw)
+        return ids, imgs[0]
+
+    @torch.no_grad()
+    def edit(self, img, mask=None, text=None, timesteps=8, temperature=1.0, topk=5, seed=None, image_base=0, token_mask=None,
+             guidance_scale=None, negative_text=None, mask_padding=False, context_lens=None, choice_temperature=None, top_p=None,
+             preserve="tokens", return_ids=False):
+        """Regenerate a free-form region of ``img`` [B, C, H, W] in [-1, 1] and KEEP the rest: the region-preserving call beside the
+        reference-shaped ``inpaint`` / ``outpaint``.
+
+        ``mask``: a bool / uint8 / float tensor [B, H, W], [B, 1, H, W] or [H, W] (every image), non-zero = regenerate; a token is
+        regenerated iff ANY pixel of its patch is.  ``token_mask``: a bool [B, g, g] or [g, g] tensor over the token grid instead.
+        Exactly one of the two.  Every image has its own mask, area and schedule: step s of image b re-masks
+        ``edit_schedule(m_b, timesteps)[s]`` of ITS m_b tokens, so a kept token is never re-masked, the last step leaves no mask
+        id behind, and the image is decoded from the merged ids -- a kept token decodes from its own id.  An image whose mask is
+        empty comes back as ``decode(encode(img))``.
+
+        ``text``: the prompts (what ``inpaint`` takes).  ``guidance_scale`` (a number or one per step), ``negative_text``,
+        ``mask_padding`` / ``context_lens``, ``topk`` (None included), ``top_p``, ``choice_temperature``, ``temperature``, ``seed``,
+        ``image_base``: as in ``generate``.
+
+        ``preserve``: "tokens" returns the decode as it is (a kept token's pixels are the decoder's reconstruction of them);
+        "pixels" puts the ORIGINAL pixels back outside the pixel mask (with ``token_mask``: outside its patches).
+
+        -> the image batch on the pipeline's device, like ``inpaint``; with ``return_ids`` (image, final ids)."""
+        if preserve not in ("tokens", "pixels"):
+            raise ValueError(f"edit: preserve must be 'tokens' or 'pixels', got {preserve!r}")
+        tm, pm = self._edit_masks(img, mask, token_mask)
+        B = img.shape[0]
+        negative = negative_lens = None
+        if exists(text):
+            if mask_padding and context_lens is None:
+                context, context_lens = self.text_model(text, return_lens=True)
+            else:
+                context = self.text_model(text)
+            if negative_text is not None:
+                prompts = [negative_text] * B if isinstance(negative_text, str) else list(negative_text)
+                if len(prompts) != B:
+                    raise ValueError(f"negative_text: {len(prompts)} prompts for a batch of {B}")
+                if mask_padding:
+                    negative, negative_lens = self.text_model(prompts, return_lens=True)
+                else:
+                    negative = self.text_model(prompts)
+        else:
+            context = None
+            if negative_text is not None:
+                raise ValueError("negative_text needs a text condition (text=None IS the unconditional branch)")
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative, negative_lens, timesteps)
+        _, ids, _ = self.to_latent(img)
+        ids = ids.reshape(B, self.num_tokens)
+        if self._on_cpu():
+            if tm is None:
+                p = self.patch_size
+                tm = pm.reshape(B, pm.shape[1] // p, p, pm.shape[2] // p, p).amax(dim=(2, 4)) != 0
+            ids = torch.where(tm.reshape(B, -1), torch.full_like(ids, self.mask_token_id), ids)
+            counts = tm.reshape(B, -1).sum(1).tolist()
+            temps, _, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
+            per_image = [edit_schedule(m, timesteps) for m in counts]
+            for step in range(timesteps):
+                ids, _ = self._sample_cpu(ids, 0, context, opts.topk, temps[step], None, None if seed is None else seed + step,
+                                          opts.step_scale(step), opts.lens, ctemps[step] if ctemps else 0.0, None, opts.top_p,
+                                          opts.negative, opts.negative_lens, counts=[sched[step] for sched in per_image])
+            out = self.vqgan.decode_from_indice(ids)
+            if preserve == "pixels":
+                out = torch.where(pm[:, None] != 0, out, img.to(out.dtype))
+            return (out, ids) if return_ids else out
+        eng = self.engine()
+        if seed is None:
+            seed = _draw_seed()
+        ids = ids.to(eng.device, torch.long).clone(memory_format=torch.contiguous_format)
+        if tm is None:
+            ids, counts = ops.mask_tokens(pm.to(eng.device), self.patch_size, ids, self.mask_token_id)
+            counts = counts.tolist()                           # the one device-to-host copy of the call: B counts
+        else:
+            ids = torch.where(tm.reshape(B, -1).to(eng.device), torch.full_like(ids, self.mask_token_id), ids)
+            counts = tm.reshape(B, -1).sum(1).tolist()
+        if context is not None:
+            context = context.to(eng.device)
+        if opts.negative is not None:
+            opts = opts._replace(negative=opts.negative.to(eng.device))
+        use_graph = os.environ.get("PMHIP_GENERATE_GRAPH", "1") != "0"
+        ids, out = self.edit_ids(ids, counts, context, timesteps, temperature, opts, seed, image_base=image_base, use_graph=use_graph)
+        if preserve == "pixels":
+            out = ops.composite(out, img.to(eng.device, torch.float32).contiguous(), pm.to(eng.device), out=out)
+        return (out, ids) if return_ids else out
+
     @torch.no_grad()
     def inpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None,
                 top_p=None):
         """re-generate the rectangle coord=(x,y,h,w) in pixels (generate.py:200-217).  choice_temperature: as in ``generate`` (the
         kept region's ids are given: the noise never prefers one of them to a position the loop took).  topk: 1..n_embed, or
-        None = no filter, as in ``generate``.  top_p: the nucleus mass, as in ``generate``."""
+        None = no filter, as in ``generate``.  top_p: the nucleus mass, as in ``generate``.
+        This reproduces the reference's loop, which re-masks and re-predicts the kept region; ``edit`` is the region-preserving call."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=False, seed=seed,
                                  return_ids=return_ids, choice_temperature=choice_temperature, top_p=top_p)
 
     @torch.no_grad()
     def outpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None,
                  top_p=None):
-        """keep the rectangle, re-generate everything else (generate.py:219-236).  choice_temperature, topk, top_p: as in ``inpaint``."""
+        """keep the rectangle, re-generate everything else (generate.py:219-236).  choice_temperature, topk, top_p: as in ``inpaint``.
+        This reproduces the reference's loop, which re-masks and re-predicts the kept region; ``edit`` is the region-preserving call."""
         return self._region_loop(img, coord, text, timesteps, topk, temperature, keep_inside=True, seed=seed,
                                  return_ids=return_ids, choice_temperature=choice_temperature, top_p=top_p)

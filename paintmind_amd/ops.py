@@ -594,6 +594,64 @@ def remask(ids, scores, num_mask, mask_id, choice_temperature=0.0, noise=None, s
     return ids
 
 
+def remask_counts(ids, scores, counts, mask_id, choice_temperature=0.0, noise=None, seed=0, step=0, row_base=0):
+    """remask with a count PER IMAGE, in place on ids int64 [B,N]: counts int32 [B] on the device; row b equals remask on that
+    row alone with num_mask = counts[b] (noise at row_base + b * N), and a count of 0 leaves the row untouched
+    (pmhip_remask_counts / pmhip_remask_choice_counts).  The other keywords: as in ``remask``."""
+    dev = _dev(ids, scores, counts, noise)
+    lib = _lib.load()
+    B, N = ids.shape
+    t = choice_t(choice_temperature)
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (B,) or not counts.is_contiguous():
+        raise ValueError(f"remask_counts: counts must be a contiguous int32 [{B}] tensor on the operands' device")
+    if noise is not None and (noise.dtype != torch.float32 or tuple(noise.shape) != (B, N)):
+        raise ValueError(f"remask_counts: noise must be a contiguous fp32 [{B}, {N}] tensor on the operands' device")
+    with torch.cuda.device(dev):
+        if t == 0.0 and noise is None:
+            check(lib.pmhip_remask_counts(_p(ids), _p(scores), _p(counts), int(mask_id), B, N, stream_ptr(dev)), "pmhip_remask_counts")
+        else:
+            check(lib.pmhip_remask_choice_counts(_p(ids), _p(scores), _p(counts), int(mask_id), B, N, t, _p(noise), int(seed), int(step),
+                                                 int(row_base), stream_ptr(dev)), "pmhip_remask_choice_counts")
+    return ids
+
+
+def mask_tokens(pixel_mask, patch, ids, mask_id):
+    """pixel mask -> token mask, in place on ids int64 [B, (H/patch) * (W/patch)]: pixel_mask uint8 [B,H,W]; a token whose patch
+    holds ANY non-zero pixel gets mask_id.  -> (ids, counts int32 [B]: how many tokens of each image did)."""
+    dev = _dev(pixel_mask, ids)
+    if pixel_mask.dtype != torch.uint8 or pixel_mask.dim() != 3 or not pixel_mask.is_contiguous():
+        raise ValueError("mask_tokens: pixel_mask must be a contiguous uint8 [B, H, W] tensor")
+    B, H, W = pixel_mask.shape
+    if patch <= 0 or H % patch or W % patch:
+        raise ValueError(f"mask_tokens: H={H} and W={W} must be multiples of patch={patch}")
+    if ids.dtype != torch.int64 or tuple(ids.shape) != (B, (H // patch) * (W // patch)) or not ids.is_contiguous():
+        raise ValueError(f"mask_tokens: ids must be a contiguous int64 [{B}, {(H // patch) * (W // patch)}] tensor")
+    counts = torch.empty(B, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_mask_tokens(_p(pixel_mask), int(patch), _p(ids), int(mask_id), _p(counts), B, H, W, stream_ptr(dev)),
+              "pmhip_mask_tokens")
+    return ids, counts
+
+
+def composite(gen, orig, pixel_mask, out=None):
+    """where(pixel_mask != 0, gen, orig): gen, orig fp32 [B,C,H,W], pixel_mask uint8 [B,H,W] broadcast over C; `out` (default: a
+    new tensor) may be gen."""
+    dev = _dev(gen, orig, pixel_mask)
+    if gen.dim() != 4 or gen.shape != orig.shape or gen.dtype != torch.float32 or orig.dtype != torch.float32:
+        raise ValueError("composite needs two fp32 [B, C, H, W] tensors of one shape")
+    B, Cn, H, W = gen.shape
+    if pixel_mask.dtype != torch.uint8 or tuple(pixel_mask.shape) != (B, H, W):
+        raise ValueError(f"composite: pixel_mask must be a uint8 [{B}, {H}, {W}] tensor")
+    out = torch.empty_like(gen) if out is None else out
+    if out.shape != gen.shape or out.dtype != torch.float32 or out.device != gen.device:
+        raise ValueError("composite: `out` must be an fp32 tensor of the inputs' shape on their device")
+    if not (gen.is_contiguous() and orig.is_contiguous() and pixel_mask.is_contiguous() and out.is_contiguous()):
+        raise ValueError("composite needs contiguous tensors (the kernel walks them as flat arrays)")
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_composite(_p(gen), _p(orig), _p(pixel_mask), _p(out), B, Cn, H, W, stream_ptr(dev)), "pmhip_composite")
+    return out
+
+
 def pack_slots(records, device=None):
     """[(seed, image_index, temperature, topk, num_mask, step) or None (idle), ...] -> the pmhip_slot array as a uint8 tensor
     [B, 32] (on `device` when given): what sample_rows_slots / remask_slots read."""
