@@ -133,25 +133,21 @@ template <int QF>
 static void launch_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
                       int use_exp2, const int* lens, hipStream_t s) {
     const int nqb = ceil_div(Nq, 4 * QF * 16);
-    dim3 grid(nqb * B * heads), block(THREADS);
-    if (lens) {
-        if (use_exp2)
-            hipLaunchKernelGGL((attention_bf16_lens_kernel<true, QF>), grid, block, 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt,
-                               (bf16_t*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb, lens);
-        else
-            hipLaunchKernelGGL((attention_bf16_lens_kernel<false, QF>), grid, block, 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt,
-                               (bf16_t*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb, lens);
-    } else if (use_exp2)
-        hipLaunchKernelGGL((attention_bf16_kernel<true, QF>), grid, block, 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt,
-                           (bf16_t*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb);
-    else
-        hipLaunchKernelGGL((attention_bf16_kernel<false, QF>), grid, block, 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt,
-                           (bf16_t*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb);
+    auto launch = [&](auto plain, auto per_image) {
+        pm_launch_lens(plain, per_image, dim3(nqb * B * heads), dim3(THREADS), s, lens, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt,
+                       (bf16_t*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb);
+    };
+    if (use_exp2) launch(attention_bf16_kernel<true, QF>, attention_bf16_lens_kernel<true, QF>);
+    else launch(attention_bf16_kernel<false, QF>, attention_bf16_lens_kernel<false, QF>);
 }
 
-// The largest workgroup that still gives the chip two workgroups per CU (256 CUs on this part: 512) is taken; the result of an
-// image does not depend on the choice, and the choice looks at B, heads and Nq only -- never at `lens`.
-static int dispatch_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+}  // namespace
+
+// bf16, dim_head = 64 leg of the attention entry points (attention_dh.hip): arguments already validated there; lens = device
+// int32 [B], the per-image key counts, or NULL.  The largest workgroup that still gives the chip two workgroups per CU (256 CUs on
+// this part: 512) is taken; the result of an image does not depend on the choice, and the choice looks at B, heads and Nq only --
+// never at `lens`.
+void pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
                        int Nkv_pad, int use_exp2, const int* lens, hipStream_t s) {
 #ifdef PM_ATTN_FORCE_QF
     constexpr int kFill = 0;
@@ -164,18 +160,4 @@ static int dispatch_qf(const void* Q, const void* K, const void* Vt, void* out, 
     if (force == 4 || (!force && bh * ceil_div(Nq, 256) >= kFill)) launch_qf<4>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
     else if (force == 2 || (!force && bh * ceil_div(Nq, 128) >= kFill)) launch_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
     else launch_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
-    return PMHIP_OK;
-}
-
-}  // namespace
-
-// bf16 leg of pmhip_attention (attention.hip): arguments already validated there
-int pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                      int Nkv_pad, int use_exp2, hipStream_t s) {
-    return dispatch_qf(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, nullptr, s);
-}
-// bf16 leg of pmhip_attention_lens: lens = device int32 [B], the per-image key counts
-int pm_attention_bf16_lens(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                           int Nkv_pad, int use_exp2, const int* lens, hipStream_t s) {
-    return dispatch_qf(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
 }

@@ -8,6 +8,9 @@
 //                dims of q and of the output; the score is a quad reduction (two DPP steps).  All lanes of a workgroup
 //                walk the keys in the same order, so K / V^T addresses are wave-uniform per quad position and come out of
 //                L1/L2 as broadcasts.  The score matrix is never materialised.
+//
+// The attention entry points of the C ABI (pmhip_attention, pmhip_attention_dh, pmhip_attention_lens) are at the end of this file:
+// one argument check for the family, then the launcher of attention.hip, attention_bf16.hip or this file.
 #include "common.h"
 
 namespace {
@@ -64,32 +67,24 @@ __device__ __forceinline__ float quad_sum(float v) {
 template <typename T, int DPL>
 void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
                int use_exp2, const int* lens, hipStream_t s) {
-    dim3 grid((Nq + 63) / 64, B * heads), block(256);
-    if (lens) {
-        if (use_exp2)
-            hipLaunchKernelGGL((attention_dh_lens_kernel<T, DPL, true>), grid, block, 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
-                               ldo, heads, Nq, Nkv, Nkp, lens);
-        else
-            hipLaunchKernelGGL((attention_dh_lens_kernel<T, DPL, false>), grid, block, 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
-                               ldo, heads, Nq, Nkv, Nkp, lens);
-    } else if (use_exp2)
-        hipLaunchKernelGGL((attention_dh_kernel<T, DPL, true>), grid, block, 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo,
-                           heads, Nq, Nkv, Nkp);
-    else
-        hipLaunchKernelGGL((attention_dh_kernel<T, DPL, false>), grid, block, 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo,
-                           heads, Nq, Nkv, Nkp);
+    auto launch = [&](auto plain, auto per_image) {
+        pm_launch_lens(plain, per_image, dim3((Nq + 63) / 64, B * heads), dim3(256), s, lens, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
+                       ldo, heads, Nq, Nkv, Nkp);
+    };
+    if (use_exp2) launch(attention_dh_kernel<T, DPL, true>, attention_dh_lens_kernel<T, DPL, true>);
+    else launch(attention_dh_kernel<T, DPL, false>, attention_dh_lens_kernel<T, DPL, false>);
 }
 
+// the launcher of this file's kernels: dim_head != 64, already passed through check_dh
 template <typename T>
-int dispatch_dh(int dh, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-                int use_exp2, const int* lens, hipStream_t s) {
+int pm_attention_dh(int dh, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
+                    int use_exp2, const int* lens, hipStream_t s) {
     switch (dh / 4) {
 #define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, s); break;
         PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
 #undef PM_DH_CASE
         default: PM_REQUIRE(false, "attention_dh: dim_head=%d not served", dh);
     }
-    PM_HIP(hipGetLastError());
     return PMHIP_OK;
 }
 
@@ -131,22 +126,45 @@ extern "C" int pmhip_gemm_heads_dh(int dtype, const void* A, int lda, const void
     return PMHIP_OK;
 }
 
-int pm_attention64(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
-                   int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
+// the dim_head = 64 launchers (attention.hip, attention_bf16.hip)
+void pm_attention_f32(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                      int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
+void pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                       int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
 
-// pmhip_attention_dh (lens NULL) and pmhip_attention_lens
+// Every attention entry point ends here: the arguments are checked once, then one launcher per kernel file.  lens = device
+// int32 [B], the per-image key counts, or NULL (one key count for the launch).
 static int attention_any(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                          int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s) {
-    if (dim_head == 64) return pm_attention64(who, dtype, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
-    PM_TRY(check_dh(who, heads, dim_head));
+    const bool tuned = dim_head == 64;               // the MFMA kernels; otherwise this file's plain path
+    if (!tuned) PM_TRY(check_dh(who, heads, dim_head));
     PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "%s: bad dtype %d", who, dtype);
     PM_REQUIRE(Q && K && Vt && out, "%s: null pointer", who);
-    PM_REQUIRE(B > 0 && Nq > 0 && Nkv > 0 && Nkv_pad >= Nkv, "%s: empty problem", who);
+    PM_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0, "%s: empty problem", who);
+    if (tuned) {
+        PM_REQUIRE(Nkv_pad % 64 == 0 && Nkv_pad >= Nkv, "%s: Nkv_pad=%d must be a multiple of 64 >= Nkv=%d", who, Nkv_pad, Nkv);
+        PM_REQUIRE(ldo % 4 == 0 && (dtype == PMHIP_F32 || ldo % 8 == 0), "%s: ldo must be a multiple of 4 (f32) / 8 (bf16: 16-byte row stores)", who);
+    } else {
+        PM_REQUIRE(Nkv_pad >= Nkv, "%s: Nkv_pad=%d must be >= Nkv=%d", who, Nkv_pad, Nkv);
+    }
     PM_REQUIRE(ldo >= heads * dim_head, "%s: ldo=%d is smaller than heads*dim_head=%d (rows of out would overlap)", who, ldo, heads * dim_head);
-    PM_REQUIRE((long long)B * heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)B * heads);
+    if (!tuned) PM_REQUIRE((long long)B * heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)B * heads);
     PmTimer tm(FAM_ATTENTION, s);
-    if (dtype == PMHIP_F32) return dispatch_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
-    return dispatch_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+    if (!tuned) {
+        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s));
+        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s));
+    } else if (dtype == PMHIP_F32) {
+        pm_attention_f32(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+    } else {
+        pm_attention_bf16(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+    }
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
+}
+
+extern "C" int pmhip_attention(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq,
+                               int Nkv, int Nkv_pad, int use_exp2, pmhip_stream stream) {
+    return attention_any("attention", dtype, Q, K, Vt, out, ldo, B, heads, 64, Nq, Nkv, Nkv_pad, use_exp2, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int pmhip_attention_dh(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,

@@ -386,6 +386,14 @@ static inline int pm_dev_knob(const char* name, int dflt) {
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t dtype_size(int dtype) { return dtype == PMHIP_BF16 ? 2 : 4; }
 
+// The attention kernels come in two forms: `plain` takes one key count for the launch, `per_image` takes the same
+// arguments plus `lens` (device int32 [B]).  lens == NULL launches the plain form.
+template <typename Plain, typename PerImage, typename... Args>
+static inline void pm_launch_lens(Plain plain, PerImage per_image, dim3 grid, dim3 block, hipStream_t s, const int* lens, Args... args) {
+    if (lens) hipLaunchKernelGGL(per_image, grid, block, 0, s, args..., lens);
+    else hipLaunchKernelGGL(plain, grid, block, 0, s, args...);
+}
+
 // Can a LayerNorm over K columns be folded into the GEMM out[M,N] = A[M,K] (row stride lda) . W[N,K]^T (row stride ldw)?  THE
 // predicate: the engine's decision (M = one image's rows: folded or not must not depend on the batch), the GEMM entry points'
 // check and pmhip_lnfold_supported all ask it.  M, N whole 256x256 tiles, K whole pairs of K-tiles, and both operands within the

@@ -6,7 +6,7 @@ factor on top of it), the selector probe must come out bit for bit, and tests/te
 these checks reject a single dropped, added, exchanged or shifted key.  K rows and V^T columns in [Nkv, Nkv_pad) hold NaN.
 
 Both modes of both dtypes run: use_exp2 = 0 in bf16 (attention_bf16_kernel<false, QF>: expf on the fast path, the overflow vote in
-nats) and use_exp2 = 1 in f32 (attention_kernel<float, true, 2>: the deferred running-max rescale) have no caller in the
+nats) and use_exp2 = 1 in f32 (attention_kernel<true, 2>: the deferred running-max rescale) have no caller in the
 product, which always passes use_exp2 = (dtype is bf16), but are public forms of pmhip_attention / pmhip_attention_dh.
 """
 import numpy as np
@@ -78,6 +78,21 @@ def test_edge_walk_on_the_smallest_launch(dtype, exp2):
             if fb:
                 failures.append(f"Nkv={nkv}: {fb} workgroups fell back to the exact path, none is due")
     print(f"edge walk {kind} {'exp2' if exp2 else 'exp'}: largest err / B", {k: round(v, 3) for k, v in worst.items()})
+    assert not failures, f"{len(failures)} failures:\n" + "\n".join(failures[:12])
+
+
+@MODES
+@pytest.mark.parametrize("nkv", [65, 193])
+def test_f32_grouped_grid_map_and_second_query_block(nkv, exp2):
+    """The f32 cases of the edge walk run B * H = 6 and Nq = 80: the plain grid map and one workgroup per (batch, head).  Here
+    B = 2, H = 4 (B * H % 8 == 0: attention_kernel's XCD-grouped map) and Nq = 144 (a full block of 128 queries and a ragged one
+    of 16), at Nkv = 65 (a ragged second tile) and 193 (four tiles: the 3-stage K / V^T ring wraps), both gauss families, held
+    to the same f32 bound."""
+    worst, failures = {}, []
+    for name, sigma in (("gauss0.3", 0.3), ("gauss4", 4.0)):
+        d = P.gauss((2, 4), 144, nkv, sigma)
+        _held_to_bound("f32", name, d, _attend(d, F32, exp2), exp2, worst, failures)
+    print(f"f32 grouped map Nkv={nkv} {'exp2' if exp2 else 'exp'}: largest err / B", {k: round(v, 3) for k, v in worst.items()})
     assert not failures, f"{len(failures)} failures:\n" + "\n".join(failures[:12])
 
 

@@ -1,8 +1,8 @@
 #!/bin/bash
-# Same-box comparison of variants of attention.hip on the attention micro-benchmark (tools/attn_only.py):
+# Same-box comparison of variants of attention_bf16.hip (the kernel tools/attn_only.py times) on that micro-benchmark:
 #   gpurun -- 'bash tools/ab_attn.sh variantA variantB [...]'      (two rounds; the original is restored at the end)
 set -u
-target=paintmind_amd/csrc/attention.hip
+target=paintmind_amd/csrc/attention_bf16.hip
 cp "$target" /tmp/ab_original
 for round in 1 2; do
   for src in "$@"; do

@@ -77,7 +77,12 @@ namespace g4_skeleton {
 }
 #undef ABL
 
-typedef int (*fn_t)(const void*, const void*, const void*, void*, int, int, int, int, int, int, int, hipStream_t);
+// the launcher of csrc/attention_bf16.hip (lens = NULL here: one key count for the launch); the round-3/4 file has the older form
+typedef void (*fn_t)(const void*, const void*, const void*, void*, int, int, int, int, int, int, int, const int*, hipStream_t);
+static void gen3_run(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
+                     int use_exp2, const int*, hipStream_t s) {
+    gen3::pm_attention_bf16(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, s);
+}
 struct V { const char* name; fn_t fn; bool exact; double us; };
 
 int main(int argc, char** argv) {
@@ -92,7 +97,7 @@ int main(int argc, char** argv) {
     void *q, *k, *v, *o, *oref;
     hipMalloc(&q, n * 2); hipMalloc(&k, n * 2); hipMalloc(&v, n * 2); hipMalloc(&o, n * 2); hipMalloc(&oref, n * 2);
     hipMemcpy(q, hq.data(), n * 2, hipMemcpyHostToDevice); hipMemcpy(k, hk.data(), n * 2, hipMemcpyHostToDevice); hipMemcpy(v, hv.data(), n * 2, hipMemcpyHostToDevice);
-    V vs[] = {{"gen3 (round 4)", gen3::pm_attention_bf16, true, 0}, {"gen4", gen4::pm_attention_bf16, true, 0},
+    V vs[] = {{"gen3 (round 4)", gen3_run, true, 0}, {"gen4", gen4::pm_attention_bf16, true, 0},
               {"gen4 256 queries / WG", g4_qf4::pm_attention_bf16, true, 0}, {"gen4 128 queries / WG", g4_qf2::pm_attention_bf16, true, 0},
               {"gen4  64 queries / WG", g4_qf1::pm_attention_bf16, true, 0},
               {"gen4 old K swizzle", g4_kswz0::pm_attention_bf16, true, 0},
@@ -102,8 +107,8 @@ int main(int argc, char** argv) {
               {"gen4 no reads/DMA/barrier", g4_nomove::pm_attention_bf16, false, 0}, {"gen4 MFMA + pack only", g4_skeleton::pm_attention_bf16, false, 0}};
     // element-wise comparison of the exact variants (bf16 outputs)
     std::vector<unsigned short> ha(n), hb(n);
-    gen3::pm_attention_bf16(q, k, v, oref, H * 64, B, H, N, N, N, 1, 0);
-    gen4::pm_attention_bf16(q, k, v, o, H * 64, B, H, N, N, N, 1, 0);
+    gen3_run(q, k, v, oref, H * 64, B, H, N, N, N, 1, nullptr, 0);
+    gen4::pm_attention_bf16(q, k, v, o, H * 64, B, H, N, N, N, 1, nullptr, 0);
     hipDeviceSynchronize();
     hipMemcpy(ha.data(), oref, n * 2, hipMemcpyDeviceToHost); hipMemcpy(hb.data(), o, n * 2, hipMemcpyDeviceToHost);
     double maxd = 0, maxv = 0; size_t ndiff = 0;
@@ -119,7 +124,7 @@ int main(int argc, char** argv) {
         const char* names[3] = {"256", "128", "64"};
         for (int i = 0; i < 3; ++i) {
             hipMemset(oref, 0xff, n * 2);
-            qfs[i](q, k, v, oref, H * 64, B, H, N, N, N, 1, 0);
+            qfs[i](q, k, v, oref, H * 64, B, H, N, N, N, 1, nullptr, 0);
             hipDeviceSynchronize();
             hipMemcpy(ha.data(), oref, n * 2, hipMemcpyDeviceToHost);
             size_t nd = 0;
@@ -130,10 +135,10 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int round = 0; round < rounds; ++round)
         for (auto& x : vs) {
-            for (int i = 0; i < 3; ++i) x.fn(q, k, v, o, H * 64, B, H, N, N, N, 1, 0);
+            for (int i = 0; i < 3; ++i) x.fn(q, k, v, o, H * 64, B, H, N, N, N, 1, nullptr, 0);
             hipEventRecord(e0, 0);
             const int reps = 10;
-            for (int i = 0; i < reps; ++i) x.fn(q, k, v, o, H * 64, B, H, N, N, N, 1, 0);
+            for (int i = 0; i < reps; ++i) x.fn(q, k, v, o, H * 64, B, H, N, N, N, 1, nullptr, 0);
             hipEventRecord(e1, 0); hipEventSynchronize(e1);
             float ms; hipEventElapsedTime(&ms, e0, e1);
             const double us = ms * 1e3 / reps;
