@@ -14,6 +14,10 @@
 //
 //   per K-tile t:   wait DMA | barrier | DMA A(t+1) -> other A buffer | W fragments -> registers | barrier |
 //                   DMA W(t+1) | 2 x { 8 A fragments, 32 MFMAs }
+//
+// Same MFMA chain per output element as the 128x128 kernel of gemm.hip (K-tiles in order, the two k-halves of a K-tile in
+// order) and the same epilogue: a launch here is BIT-IDENTICAL to 128x128 launches over its rows, planes, row statistics and
+// shift alike (tests/test_gpu_gemm_probes.py::test_2b_producer_equals_128_launches).
 #include <stdlib.h>
 
 #include "gemm_common.h"
