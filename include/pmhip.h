@@ -37,7 +37,7 @@
  *         pmhip_gemm with an f32 residual      out == residual with ldo == ldr, res_rows covering all M rows
  *         pmhip_unshift_hilo, pmhip_remask(_slots), pmhip_remask_choice(_slots), pmhip_guidance_combine(_stats), pmhip_sample_rows* (ids_out == ids_in)
  *         pmhip_remask_counts, pmhip_remask_choice_counts, pmhip_mask_tokens (ids), pmhip_composite (out == gen or orig)
- *         pmhip_guidance_combine_slots         out == cond (or uncond)
+ *         pmhip_guidance_combine_slots(_which) out == cond (or uncond / other)
  *     Every element is read by the workgroup that writes it, before it writes it; the result equals the out-of-place call's bit
  *     for bit.  Any other overlap between an output and an input is undefined.
  */
@@ -420,6 +420,12 @@ int pmhip_composite(const float* gen, const float* orig, const uint8_t* pixel_ma
 
 /* Per-image GUIDANCE: a record parallel to pmhip_slot, which stays 32 bytes; the ABI version stays 11 (new entries only). */
 typedef struct pmhip_slot_guide { float scale; uint32_t on; } pmhip_slot_guide;   /* 8 bytes, one per image; on = 0: not guided */
+/* `on` names what the image is guided AGAINST: 1 the pass without a context, 2 the negative context's pass
+ * (pmhip_pipeline_step_slots_negative, pmhip_guidance_combine_slots_which).  The entries that predate the second kind
+ * (pmhip_guidance_combine_slots, the pmhip_pipeline_step_slots_guided / _lens / _choice entries) keep reading any non-zero value as 1. */
+#define PMHIP_GUIDE_OFF      0u
+#define PMHIP_GUIDE_UNCOND   1u
+#define PMHIP_GUIDE_NEGATIVE 2u
 
 /* pmhip_guidance_combine(_stats) per image: cond / uncond / out fp32 [M, V] with contiguous rows, M = B * tokens, guides and slots
  * DEVICE arrays [B].  For an image that is active (bit 31 of slots[b].step clear) and has guides[b].on != 0, every row becomes
@@ -431,6 +437,16 @@ typedef struct pmhip_slot_guide { float scale; uint32_t on; } pmhip_slot_guide; 
 int pmhip_guidance_combine_slots(const float* cond, const float* uncond, const pmhip_slot_guide* guides,
                                  const pmhip_slot* slots, int tokens, float* out, float* block_stats /* or NULL */,
                                  int M, int V, pmhip_stream stream);
+/* The same for the images of ONE kind (a new entry within ABI 11): image b is combined iff it is active and guides[b].on == which
+ * (which = 1 or 2, else PMHIP_EINVAL); its rows of `out` (and of `block_stats` when given) become
+ * fmaf(scale_b, cond - other, other).  Every other image -- idle, unguided, or of the other kind -- is NEITHER READ NOR WRITTEN.
+ * The selector is a workgroup-uniform compare in front of the same loop, so a combined image's rows equal, bit for bit,
+ * pmhip_guidance_combine(_stats) called on that image alone; which = 1 over records whose `on` is 0 or 1 equals
+ * pmhip_guidance_combine_slots.  Two launches with which = 1 and 2 and two different `other` planes touch disjoint images: this
+ * is how a decode step guides some slots against no text and others against their negative text. */
+int pmhip_guidance_combine_slots_which(const float* cond, const float* other, const pmhip_slot_guide* guides,
+                                       const pmhip_slot* slots, int which, int tokens, float* out,
+                                       float* block_stats /* or NULL */, int M, int V, pmhip_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Model level.  Weight tables are filled by the host packer (paintmind_amd/engine.py) from the
@@ -776,6 +792,35 @@ int pmhip_pipeline_generate_edit(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, co
                                  const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
                                  const int32_t* neg_lens_host /* [B] or NULL */, const float* gscales_host /* [T] or NULL */);
 
+/* NEGATIVE PROMPT PER SLOT (new entries within ABI 11): pmhip_pipeline_step_slots_choice with a negative
+ * context neg_context fp32 [B, Ln, context_dim] (device, or NULL) and neg_lens_host, a HOST int32 [B] or NULL.  Through THIS entry
+ * guides_host[b].on names what slot b is guided against: 0 not guided, 1 the pass without a context, 2 the negative context --
+ * slot b then samples from neg_b + scale_b * (cond_b - neg_b), like pmhip_pipeline_sample_negative on that image.  The host
+ * decides the tower passes of the step from the ACTIVE slots:
+ *   1. the tower with the context, always (its logits GEMM leaves the block statistics);
+ *   2. the tower without a context iff a slot has on == 1, then pmhip_guidance_combine_slots_which(which = 1) in place;
+ *   3. the tower against the negative set iff a slot has on == 2, then the same with which = 2.
+ * Passes 2 and 3 write the same second logits plane one after the other -- a linear chain, no third plane -- and the two combines
+ * touch disjoint images, so an unguided slot keeps the first tower's rows and every slot computes, bit for bit, what it computes
+ * alone.  A step without pass 3 runs the launches and the captured graph of pmhip_pipeline_step_slots_choice; one with it has a
+ * graph key that adds the pass set, Ln and whether negative lengths came.
+ * The negative K/V are prepared eagerly, outside any graph, in the handle's second set (as for pmhip_pipeline_sample_negative).
+ * flags: PMHIP_SLOTS_KEEP_NEGATIVE -- neg_context is ignored and the negative K/V the PREVIOUS slots call on this handle prepared
+ * (or kept) are reused, also across the preparation of a new context; PMHIP_ESTATE when there are none (no slots call prepared
+ * any, the previous one neither brought nor kept them, another entry point ran since) or when B or Ln differ.  A call that
+ * neither brings nor keeps a negative context drops the set.  Lengths are staged by every call that brings them, also under the
+ * keep flag; NULL: every slot attends to all Ln rows.
+ * Validated before anything is staged or launched (PMHIP_EINVAL, ids untouched): on in {0, 1, 2}; on == 2 needs a negative set,
+ * given or kept, and a context; Ln >= 1; 1 <= neg_len_b <= Ln for every b (the message names the slot); neg_lens_host without a
+ * negative set; every scale of a guided slot finite. */
+#define PMHIP_SLOTS_KEEP_NEGATIVE 4  /* reuse the negative cross K/V the previous slots call on this handle prepared */
+int pmhip_pipeline_step_slots_negative(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                       const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
+                                       const pmhip_slot_guide* guides_host, const float* choice_host /* [B] or NULL */,
+                                       const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                       const int32_t* neg_lens_host /* [B] or NULL */, int flags,
+                                       int64_t* pred_out, float* score_out, pmhip_stream stream);
+
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return
  * what a handle latched: bit 0 LayerNorm fold (PMHIP_LN_UNFOLD unset), bit 1 bf16 hi/lo stream (PMHIP_HILO != 0), bit 2 row
@@ -790,6 +835,9 @@ int pmhip_s2_step0_shared(const pmhip_s2* h, int* fills, int* hits);
 /* Slots steps this handle ran (both slots entries), by tower passes: *one_pass without guidance, *two_pass with at least one
  * active guided slot.  Either pointer may be NULL. */
 int pmhip_s2_slots_steps(const pmhip_s2* h, int* one_pass, int* two_pass);
+/* The same with the steps of THREE passes (slots guided against no context and against a negative context in one step,
+ * pmhip_pipeline_step_slots_negative); *two_pass stays the steps of exactly two.  Any pointer may be NULL. */
+int pmhip_s2_slots_passes(const pmhip_s2* h, int* one_pass, int* two_pass, int* three_pass);
 
 /* Per-kernel timing hook used by bench.py: when enabled, every kernel launch of the named family
  * is bracketed by hipEvents on its own stream and accumulated (count, total ms). */

@@ -15,7 +15,8 @@ F32, BF16 = 0, 1
 PART_Q, PART_K, PART_V = 0, 1, 2
 ABI_VERSION = 11
 GENERATE_GRAPH, GENERATE_CONCURRENT_LANES, GENERATE_FROM_MASK = 1, 2, 4
-SLOTS_GRAPH, SLOTS_KEEP_CONTEXT = 1, 2
+SLOTS_GRAPH, SLOTS_KEEP_CONTEXT, SLOTS_KEEP_NEGATIVE = 1, 2, 4
+GUIDE_OFF, GUIDE_UNCOND, GUIDE_NEGATIVE = 0, 1, 2   # SlotGuide.on: what a slot is guided against
 SLOT_IDLE = 0x80000000             # bit 31 of Slot.step
 CHOICE_T_MAX = 1000.0              # largest choice temperature of a step (include/pmhip.h, pmhip_remask_choice)
 
@@ -75,7 +76,8 @@ class Slot(C.Structure):
 
 
 class SlotGuide(C.Structure):
-    """mirror of pmhip_slot_guide: the guidance of one image of a batch (8 bytes; on = 0: not guided)"""
+    """mirror of pmhip_slot_guide: the guidance of one image of a batch (8 bytes; on = 0: not guided, 1: against the pass without a
+    context, 2: against the negative context)"""
     _fields_ = [("scale", f32), ("on", u32)]
 
 
@@ -184,6 +186,11 @@ PROTOTYPES = {
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "pmhip_s2_slots_steps": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+    # a negative prompt per slot: the combine of one kind of slot, the widest slots entry, its counters
+    "pmhip_guidance_combine_slots_which": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp]),
+    "pmhip_pipeline_step_slots_negative": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
+                                                 vp, i32, C.POINTER(i32), i32, vp, vp, vp]),
+    "pmhip_s2_slots_passes": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

@@ -769,13 +769,15 @@ struct pmhip_s2 {
     // per-image decode state (pmhip_pipeline_step_slots): an entry of the ring holds B pmhip_slot records and, behind them, the B
     // pmhip_slot_guide records of a call with guidance (they travel under the entry's one event); the handle remembers which
     // context the last slots call prepared (slots_ctx_L: 0 = prepared without a context, -1 = nothing a slots call may reuse);
-    // slots_one_pass / slots_two_pass count the steps by tower passes
+    // slots_one_pass / slots_two_pass / slots_three_pass count the steps by tower passes.  The negative set a slots call prepared
+    // (pmhip_pipeline_step_slots_negative) is remembered the same way: slots_neg_Ln = -1: none a slots call may reuse
     PinnedRing slots_ring;
     PinnedRing lens_ring;           // per-image context lengths of a call (ctx_lens_host): B int32 -> workspace "ctx.lens"
     PinnedRing neg_lens_ring;       // ... and of its negative context (neg_lens_host): B int32 -> workspace "neg.lens"
     PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
-    int slots_one_pass = 0, slots_two_pass = 0;
+    int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
     int slots_ctx_B = 0, slots_ctx_L = -1;
+    int slots_neg_B = 0, slots_neg_Ln = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
     // its previous record may still be queued); last D2H complete -> next call
     std::vector<OwnedEvent> img_ready;
@@ -841,6 +843,7 @@ int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStrea
     const size_t es = dtype_size(h->dtype);
     const CrossSetRef cs = cross_set(h, set);
     h->slots_ctx_L = -1;                                      // whatever a slots call prepared is about to be replaced
+    h->slots_neg_Ln = -1;                                     // (a slots call sets both again behind its own preparation)
     if (set == kCrossContext)
         for (auto& ck : h->cross_neg) ck = CrossKV{};
     if (!context) {
@@ -1017,6 +1020,9 @@ struct Step {
     // guidance_dev: the batch's scale in DEVICE memory (a scheduled loop: &gp->gscales[step]) instead of *guidance; negative: the
     // second tower of a batch-guided step attends to the negative context's set instead of running without one
     const float* guidance_dev = nullptr; bool negative = false;
+    // a slots step with guide records whose `on` names a kind (pmhip_pipeline_step_slots_negative): slots_neg: an active slot is
+    // guided against the negative context (on == 2), slots_uncond: one against the pass without a context (on == 1) beside it
+    bool slots_uncond = false, slots_neg = false;
     // the re-masking step's choice temperature, by the same three sources: the scalar choice_t (with optional
     // given uniforms choice_noise [B,N]); choice_params: gp->ctemps[step]; choice_dev: a device float [B] beside the slot records.
     // None of them set: the plain re-masking launch.
@@ -1052,6 +1058,16 @@ int step_tower(pmhip_s2* s2, const int64_t* ids, int B, const Step& st, hipStrea
     if (!batch_guided && !st.guides) return PMHIP_OK;
     float* uncond;
     WS(s2->ws, "s2.logits_u", (size_t)M * c.n_embed * 4, uncond);
+    if (st.guides && st.slots_neg) {
+        // up to two more passes, one after the other into the same plane; each combine touches the images of its kind only, so
+        // the two write disjoint rows and an unguided image keeps the first tower's
+        if (st.slots_uncond) {
+            PM_TRY(s2_tower(s2, tp, B, uncond, s, kCrossNone));
+            PM_TRY(pmhip_guidance_combine_slots_which(b.logits, uncond, st.guides, st.slots, 1, c.tokens, b.logits, b.lstats, M, c.n_embed, s));
+        }
+        PM_TRY(s2_tower(s2, tp, B, uncond, s, kCrossNegative));
+        return pmhip_guidance_combine_slots_which(b.logits, uncond, st.guides, st.slots, 2, c.tokens, b.logits, b.lstats, M, c.n_embed, s);
+    }
     PM_TRY(s2_tower(s2, tp, B, uncond, s, st.negative ? kCrossNegative : kCrossNone));
     if (st.guidance_dev) return pmhip_guidance_combine_dev(b.logits, uncond, st.guidance_dev, b.logits, (size_t)M * c.n_embed, b.lstats, s);
     if (st.guides) return pmhip_guidance_combine_slots(b.logits, uncond, st.guides, st.slots, c.tokens, b.logits, b.lstats, M, c.n_embed, s);
@@ -1708,15 +1724,29 @@ extern "C" int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, i
 // PMHIP_SLOTS_KEEP_CONTEXT, where the kept cross K/V serve whatever lengths this call brings.
 // The slots family's one builder: the argument list of pmhip_pipeline_step_slots_choice, the widest entry, -> the Step and the name
 // the messages carry: `narrow` (a narrower entry's own name, or the *_lens entry's for the widest) unless choice temperatures came.
+// neg_context / Ln / neg_lens_host (pmhip_pipeline_step_slots_negative, `kinds` set; NULL / 0 / NULL and PMHIP_SLOTS_KEEP_NEGATIVE
+// clear from the four narrower entries): guides_host[b].on then names what slot b is guided against -- 1 the pass without a
+// context, 2 the negative context's K/V -- and the host decides the passes per step: the conditional tower, the tower without a
+// context iff an active slot has on == 1, the tower against the negative set iff one has on == 2, each of the two followed by the
+// combine of its kind.  The negative set is prepared eagerly like the context's, or kept from the previous slots call.
 static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                            const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host, int flags,
-                           int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    const char* who = choice_host ? "pipeline_step_slots_choice" : narrow;
+                           int64_t* pred_out, float* score_out, pmhip_stream stream, bool kinds = false, const float* neg_context = nullptr,
+                           int Ln = 0, const int32_t* neg_lens_host = nullptr) {
+    const bool keep_neg = kinds && (flags & PMHIP_SLOTS_KEEP_NEGATIVE) != 0;
+    const bool neg_set = neg_context || keep_neg;             // this call has a negative set, given or kept
+    const char* who = (neg_set || neg_lens_host) ? "pipeline_step_slots_negative" : choice_host ? "pipeline_step_slots_choice" : narrow;
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0), L, B));
     const auto& c = s2->cfg;
     PM_REQUIRE(c.n_embed % 64 == 0, "%s: n_embed=%d must be a multiple of 64", who, c.n_embed);
+    PM_REQUIRE(neg_set || !neg_lens_host, "%s: neg_lens_host given without a negative context", who);
+    PM_REQUIRE(!neg_set || Ln >= 1, "%s: negative context given with Ln=%d", who, Ln);
+    for (int b = 0; neg_lens_host && b < B; ++b)
+        PM_REQUIRE(neg_lens_host[b] >= 1 && neg_lens_host[b] <= Ln, "%s: slot %d: negative context length %d must be in [1, Ln=%d]", who, b,
+                   (int)neg_lens_host[b], Ln);
     bool two_pass = false, choice = false;      // choice: an active slot has a choice temperature other than 0 (else: the step without)
+    bool pass_neg = false, pass_uncond = false;               // an active slot guided against the negative set / against no context
     for (int b = 0; b < B; ++b) {
         const pmhip_slot& sl = slots_host[b];
         if (sl.step & PM_SLOT_IDLE) continue;
@@ -1727,13 +1757,27 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
         PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "%s: slot %d: topk=%d must be in [1, 8]", who, b, sl.topk);
         PM_REQUIRE(sl.num_mask >= 1, "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
         if (guides_host && guides_host[b].on) {
+            PM_REQUIRE(!kinds || guides_host[b].on <= 2, "%s: slot %d: on=%u must be 0, 1 or 2", who, b, guides_host[b].on);
             PM_REQUIRE(std::isfinite(guides_host[b].scale), "%s: slot %d: the guidance scale must be finite", who, b);
             PM_REQUIRE(L > 0 && (context || (flags & PMHIP_SLOTS_KEEP_CONTEXT)),
                        "%s: slot %d: guidance needs a context (context NULL IS the unconditional branch)", who, b);
+            const bool against_neg = kinds && guides_host[b].on == 2;
+            PM_REQUIRE(!against_neg || neg_set, "%s: slot %d: on=2 needs a negative context, given or kept", who, b);
+            (against_neg ? pass_neg : pass_uncond) = true;
             two_pass = true;
         }
     }
     hipStream_t s = (hipStream_t)stream;
+    if (keep_neg && (s2->slots_neg_Ln < 0 || s2->slots_neg_B != B || s2->slots_neg_Ln != Ln)) {
+        pm_set_error("%s: keep-negative asked for B=%d Ln=%d, but %s", who, B, Ln,
+                     s2->slots_neg_Ln < 0 ? "no slots call has prepared a negative context on this handle (or another entry point replaced it)"
+                                          : "the prepared negative context has another B or Ln");
+        return PMHIP_ESTATE;
+    }
+    // a kept negative set outlives the preparation of a new context (which drops the handle's negative set: s2_prepare_context);
+    // its K/V live in workspace buffers of their own, which only a negative preparation touches
+    std::vector<CrossKV> kept_neg;
+    if (keep_neg) kept_neg = s2->cross_neg;
     if (flags & PMHIP_SLOTS_KEEP_CONTEXT) {
         if (s2->slots_ctx_L < 0 || s2->slots_ctx_B != B || s2->slots_ctx_L != L) {
             pm_set_error("%s: keep-context asked for B=%d L=%d, but %s", who, B, L,
@@ -1749,6 +1793,19 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     const int Lc = s2->slots_ctx_L;
     PM_REQUIRE(!ctx_lens_host || Lc > 0, "%s: ctx_lens_host given, but the kept context was prepared without one", who);
     PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
+    // the negative set: prepared (eager, outside any graph), kept, or -- a call that neither brings nor keeps one -- dropped
+    if (keep_neg) {
+        s2->cross_neg = kept_neg;                             // (neg_context is ignored, like context under PMHIP_SLOTS_KEEP_CONTEXT)
+    } else if (neg_context) {
+        const int ctx_B = s2->slots_ctx_B, ctx_L = s2->slots_ctx_L;
+        PM_TRY(s2_prepare_context(s2, neg_context, Ln, B, s, kCrossNegative));
+        s2->slots_ctx_B = ctx_B; s2->slots_ctx_L = ctx_L;     // (the preparation of either set forgets what slots calls prepared)
+    } else {
+        for (auto& ck : s2->cross_neg) ck = CrossKV{};
+    }
+    s2->slots_neg_B = B;
+    s2->slots_neg_Ln = neg_set ? Ln : -1;
+    if (neg_set) PM_TRY(s2_set_ctx_lens(s2, neg_lens_host, Ln, B, s, kCrossNegative));   // every call brings its own lengths (or NULL)
 
     // the records: pinned ring entry -> device (the guide records sit behind the B slot records: 32 B bytes, a multiple of 16)
     const size_t slot_bytes = sizeof(pmhip_slot) * (size_t)B, guide_bytes = sizeof(pmhip_slot_guide) * (size_t)B;
@@ -1770,10 +1827,12 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
         PM_TRY(s2->slots_ring.stage(dchoice, choice_at, padded.data(), choice_bytes, s));
     }
     PM_TRY(s2->slots_ring.commit(s));
-    ++(two_pass ? s2->slots_two_pass : s2->slots_one_pass);
+    ++(pass_neg && pass_uncond ? s2->slots_three_pass : two_pass ? s2->slots_two_pass : s2->slots_one_pass);
     Step st;
     st.slots = dslots;
     st.guides = dguides;
+    st.slots_neg = pass_neg;
+    st.slots_uncond = pass_uncond;
     st.choice_dev = dchoice;
     auto run_step = [&](int64_t* on_ids, int64_t* pred, float* score, hipStream_t on) -> int {
         return sample_step(s2, nullptr, on_ids, B, st, nullptr, pred, score, on);
@@ -1787,8 +1846,12 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     int64_t* gids;
     WS(s2->ws, "slots.ids", ids_bytes, gids);
     PM_TRY(copy16_async(gids, ids, ids_bytes, s));
-    GraphEntry& ge = s2->graphs[(two_pass ? "slotsguidedB" : "slotsB") + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
-                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "")];
+    // the key names the pass set; a step without a pass against the negative set keeps the key it had before there was one, and
+    // one with it adds Ln and whether negative lengths came (the kernel form of that tower's cross-attention)
+    const char* passes = pass_neg ? (pass_uncond ? "slotsthreeB" : "slotsnegB") : two_pass ? "slotsguidedB" : "slotsB";
+    const std::string neg_key = pass_neg ? "N" + std::to_string(Ln) + (neg_lens_host ? "n" : "") : "";
+    GraphEntry& ge = s2->graphs[passes + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
+                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key];
     PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
@@ -1824,11 +1887,29 @@ extern "C" int pmhip_pipeline_step_slots_choice(pmhip_s2* s2, int64_t* ids, cons
                            score_out, stream);
 }
 
-// slots steps by tower passes: one (no active slot guided) / two
+// neg_context NULL, PMHIP_SLOTS_KEEP_NEGATIVE clear and no active slot with on == 2: exactly pmhip_pipeline_step_slots_choice
+extern "C" int pmhip_pipeline_step_slots_negative(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                                  const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
+                                                  const float* neg_context, int Ln, const int32_t* neg_lens_host, int flags,
+                                                  int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
+                           score_out, stream, true, neg_context, Ln, neg_lens_host);
+}
+
+// slots steps by tower passes: one (no active slot guided) / exactly two
 extern "C" int pmhip_s2_slots_steps(const pmhip_s2* h, int* one_pass, int* two_pass) {
     PM_REQUIRE(h, "s2_slots_steps: null handle");
     if (one_pass) *one_pass = h->slots_one_pass;
     if (two_pass) *two_pass = h->slots_two_pass;
+    return PMHIP_OK;
+}
+
+// ... and three: active slots guided against no context and against the negative set in one step
+extern "C" int pmhip_s2_slots_passes(const pmhip_s2* h, int* one_pass, int* two_pass, int* three_pass) {
+    PM_REQUIRE(h, "s2_slots_passes: null handle");
+    if (one_pass) *one_pass = h->slots_one_pass;
+    if (two_pass) *two_pass = h->slots_two_pass;
+    if (three_pass) *three_pass = h->slots_three_pass;
     return PMHIP_OK;
 }
 

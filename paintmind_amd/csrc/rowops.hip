@@ -246,6 +246,23 @@ __global__ __launch_bounds__(THREADS) void guidance_slots_kernel(const float* co
                          reinterpret_cast<float4*>(out) + base, block_stats, n4, g.scale, base);
 }
 
+// guidance_slots_kernel for the images of ONE kind (pmhip_guidance_combine_slots_which): guides[b].on names what image b is guided
+// against (1: the pass without a context, 2: the negative context's), and only an active image with on == which is combined.  The
+// selector is a compare of two workgroup-uniform values in front of the same body, so a combined image's rows are guidance_kernel's
+// on that image alone, bit for bit, and the extents of every other image stay untouched: two launches with which = 1 and 2 and
+// two different `uncond` planes touch disjoint images.
+template <bool STATS>
+__global__ __launch_bounds__(THREADS) void guidance_slots_which_kernel(const float* cond, const float* other,
+                                                                       const pmhip_slot_guide* __restrict__ guides,
+                                                                       const pmhip_slot* __restrict__ slots, uint32_t which, float* out,
+                                                                       size_t n4, float2* block_stats) {
+    const pmhip_slot_guide g = guides[blockIdx.y];
+    if ((slots[blockIdx.y].step & PM_SLOT_IDLE) || g.on != which) return;
+    const size_t base = (size_t)blockIdx.y * n4;
+    guidance_body<STATS>(reinterpret_cast<const float4*>(cond) + base, reinterpret_cast<const float4*>(other) + base,
+                         reinterpret_cast<float4*>(out) + base, block_stats, n4, g.scale, base);
+}
+
 // The pixel side of an edit.  mask_tokens: one workgroup per image; a thread owns the tokens tid, tid + THREADS,
 // ... of the image's gh x gw grid, reads the patch x patch pixels of each and, when any is non-zero, writes mask_id over the token's
 // id; the workgroup's count of such tokens (wave shuffles, then THREADS / 64 words of LDS) goes to counts_out[image]: no atomics,
@@ -649,8 +666,9 @@ extern "C" int pmhip_guidance_combine_dev(const float* cond, const float* uncond
 }
 
 // the same per image: guides / slots are DEVICE arrays [M / tokens]; an idle or unguided image is neither read nor written
-extern "C" int pmhip_guidance_combine_slots(const float* cond, const float* uncond, const pmhip_slot_guide* guides, const pmhip_slot* slots,
-                                            int tokens, float* out, float* block_stats, int M, int V, pmhip_stream stream) {
+// which == 0: every active image with a non-zero `on` (pmhip_guidance_combine_slots); 1 or 2: the images of that kind only
+static int guidance_slots_impl(const float* cond, const float* uncond, const pmhip_slot_guide* guides, const pmhip_slot* slots, uint32_t which,
+                               int tokens, float* out, float* block_stats, int M, int V, pmhip_stream stream) {
     PM_REQUIRE(cond && uncond, "guidance_combine_slots: null cond or uncond pointer");
     PM_REQUIRE(guides, "guidance_combine_slots: null guides pointer");
     PM_REQUIRE(slots, "guidance_combine_slots: null slots pointer");
@@ -664,7 +682,13 @@ extern "C" int pmhip_guidance_combine_slots(const float* cond, const float* unco
     // as many workgroups as guidance_kernel gets for the whole plane, shared out over the images
     const int chunks = std::min(grid_for(n4), std::max(1, (256 * 8 + B - 1) / B));
     PmTimer tm(FAM_ROWOPS, s);
-    if (block_stats)
+    if (which && block_stats)
+        hipLaunchKernelGGL(guidance_slots_which_kernel<true>, dim3(chunks, B), dim3(THREADS), 0, s, cond, uncond, guides, slots, which, out, n4,
+                           reinterpret_cast<float2*>(block_stats));
+    else if (which)
+        hipLaunchKernelGGL(guidance_slots_which_kernel<false>, dim3(chunks, B), dim3(THREADS), 0, s, cond, uncond, guides, slots, which, out, n4,
+                           (float2*)nullptr);
+    else if (block_stats)
         hipLaunchKernelGGL(guidance_slots_kernel<true>, dim3(chunks, B), dim3(THREADS), 0, s, cond, uncond, guides, slots, out, n4,
                            reinterpret_cast<float2*>(block_stats));
     else
@@ -672,6 +696,19 @@ extern "C" int pmhip_guidance_combine_slots(const float* cond, const float* unco
                            (float2*)nullptr);
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
+}
+
+extern "C" int pmhip_guidance_combine_slots(const float* cond, const float* uncond, const pmhip_slot_guide* guides, const pmhip_slot* slots,
+                                            int tokens, float* out, float* block_stats, int M, int V, pmhip_stream stream) {
+    return guidance_slots_impl(cond, uncond, guides, slots, 0, tokens, out, block_stats, M, V, stream);
+}
+
+// only the active images with guides[b].on == which (1: against the pass without a context, 2: against the negative context)
+extern "C" int pmhip_guidance_combine_slots_which(const float* cond, const float* other, const pmhip_slot_guide* guides,
+                                                  const pmhip_slot* slots, int which, int tokens, float* out, float* block_stats, int M, int V,
+                                                  pmhip_stream stream) {
+    PM_REQUIRE(which == 1 || which == 2, "guidance_combine_slots_which: which=%d must be 1 or 2", which);
+    return guidance_slots_impl(cond, other, guides, slots, (uint32_t)which, tokens, out, block_stats, M, V, stream);
 }
 
 // pixel mask -> token mask (include/pmhip.h): a token is regenerated iff any pixel of its patch is non-zero

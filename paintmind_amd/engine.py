@@ -372,8 +372,16 @@ class S2Engine:
         check(self.lib.pmhip_s2_slots_steps(self.handle, C.byref(one), C.byref(two)), "pmhip_s2_slots_steps")
         return one.value, two.value
 
+    def slots_passes(self):
+        """(one_pass, two_pass, three_pass): the slots steps this handle ran, by tower passes (pmhip_s2_slots_passes) -- the
+        conditional pass, plus one without a context when an active slot had on == 1, plus one against the negative context when
+        one had on == 2"""
+        one, two, three = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self.lib.pmhip_s2_slots_passes(self.handle, C.byref(one), C.byref(two), C.byref(three)), "pmhip_s2_slots_passes")
+        return one.value, two.value, three.value
+
     def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None,
-                   choice=None):
+                   choice=None, negative_context=None, negative_lens=None, keep_negative=False):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
@@ -383,6 +391,10 @@ class S2Engine:
         step (pmhip_pipeline_step_slots_lens; also with keep_context, which keeps the cross K/V only).  choice: one choice
         temperature per slot for THIS step (a list of B floats, 0 = the plain re-masking; pmhip_pipeline_step_slots_choice); None
         or all zero is the step without.
+        negative_context fp32 [B, Ln, context_dim]: a slot whose guide record has on == 2 is guided against ITS rows of it instead of
+        the pass without a context (on == 1); negative_lens: per-slot lengths of it for THIS step, like context_lens.
+        keep_negative: like keep_context for the negative K/V -- `negative_context` only says how long it is.  A step without an
+        active on == 2 slot runs what it ran before there was a negative context (pmhip_pipeline_step_slots_negative).
         -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
@@ -400,14 +412,34 @@ class S2Engine:
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
         flags = (_lib.SLOTS_GRAPH if use_graph else 0) | (_lib.SLOTS_KEEP_CONTEXT if keep_context else 0)
+        if keep_negative:
+            if negative_context is None:
+                raise ValueError("step_slots: keep_negative needs the negative context it keeps (for its length)")
+            if negative_context.dim() != 3 or negative_context.shape[0] != B:
+                raise ValueError(f"step_slots: negative context {tuple(negative_context.shape)}, batch of {B}")
+            neg, Ln = None, negative_context.shape[1]
+            vals = ops.host_lens(negative_lens, B, Ln, "negative_lens")
+            neg_lens = None if vals is None else (C.c_int * B)(*vals)
+            flags |= _lib.SLOTS_KEEP_NEGATIVE
+        else:
+            neg, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
         if choice is not None:
             if len(choice) != B:
                 raise ValueError(f"step_slots: {len(choice)} choice temperatures for a batch of {B}")
             vals = [ops.choice_t(v, f"step_slots: slot {b}: choice temperature") for b, v in enumerate(choice)]
             choice = (C.c_float * B)(*vals) if any(vals) else None
-        with torch.cuda.device(self.device):      # always the widest entry; NULL lengths, guides or choice: the step without them
-            check(self.lib.pmhip_pipeline_step_slots_choice(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, flags,
-                                                            _p(pred), _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_choice")
+        # the widest entry of the family as it was before a slot could carry a negative prompt (NULL lengths, guides or choice: the
+        # step without them) -- unless this step has something only the entry with a negative context reads: that context, kept or
+        # given, or a guide record whose `on` names a kind beyond 1 (which that entry validates)
+        kinds = guides is not None and any(g.on > _lib.GUIDE_UNCOND for g in guides)
+        with torch.cuda.device(self.device):
+            if neg is None and not keep_negative and not kinds:
+                check(self.lib.pmhip_pipeline_step_slots_choice(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, flags,
+                                                                _p(pred), _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_choice")
+            else:
+                check(self.lib.pmhip_pipeline_step_slots_negative(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
+                                                                  Ln, neg_lens, flags, _p(pred), _p(score), stream_ptr(self.device)),
+                      "pmhip_pipeline_step_slots_negative")
         return ids, pred, score
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,

@@ -712,24 +712,32 @@ def remask_slots(ids, scores, slots, mask_id, choice=None):
     return ids
 
 
-def pack_slot_guides(scales, device=None):
+def pack_slot_guides(scales, device=None, kinds=None):
     """[guidance scale or None (not guided), ...] -> the pmhip_slot_guide array as a uint8 tensor [B, 8] (on `device` when given):
-    what guidance_combine_slots reads, one record beside every pack_slots record."""
+    what guidance_combine_slots reads, one record beside every pack_slots record.  kinds (None: 1 for every guided image): the
+    record's `on` per guided image -- 1 guided against the pass without a context, 2 against the negative context."""
     arr = (_lib.SlotGuide * len(scales))()
+    if kinds is not None and len(kinds) != len(scales):
+        raise ValueError(f"pack_slot_guides: {len(kinds)} kinds for {len(scales)} scales")
     for i, sc in enumerate(scales):
         if sc is not None:
-            arr[i] = _lib.SlotGuide(float(sc), 1)
+            arr[i] = _lib.SlotGuide(float(sc), 1 if kinds is None else int(kinds[i]))
     t = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).reshape(len(scales), C.sizeof(_lib.SlotGuide))
     return t if device is None else t.to(device)
 
 
-def guidance_combine_slots(cond, uncond, guides, slots, tokens, out=None, block_stats=None):
+def guidance_combine_slots(cond, uncond, guides, slots, tokens, out=None, block_stats=None, which=None):
     """guidance_combine with the scale of row r taken from guides[r // tokens] (pack_slot_guides): cond, uncond fp32
     [B*tokens, V] -> `out` (default: a new tensor; may be cond), and `block_stats` fp32 [B*tokens, V/64, 2] when given.  The rows
     of an image that is guided and whose slot (pack_slots) is active equal guidance_combine(with_stats=True) on that image alone,
     bit for bit; the rows of every other image are neither read nor written: `out` and `block_stats` keep what they held.
-    V % 64 == 0."""
+    V % 64 == 0.
+    which (None: every active image whose record has a non-zero `on`): 1 or 2 -- only the active images whose `on` EQUALS it are
+    combined (pmhip_guidance_combine_slots_which), `uncond` then being the plane of that kind: the pass without a context for 1,
+    the pass against the negative context for 2."""
     dev = _dev(cond, uncond, guides, slots, out, block_stats)
+    if which is not None and which not in (1, 2):
+        raise ValueError(f"guidance_combine_slots: which={which!r} must be None, 1 or 2")
     lib = _lib.load()
     if cond.dim() != 2 or cond.shape != uncond.shape or cond.dtype != torch.float32 or uncond.dtype != torch.float32:
         raise ValueError("guidance_combine_slots needs two fp32 [M, V] tensors of one shape")
@@ -750,8 +758,12 @@ def guidance_combine_slots(cond, uncond, guides, slots, tokens, out=None, block_
                                     or tuple(block_stats.shape) != (M, V // 64, 2) or V % 64):
         raise ValueError("guidance_combine_slots: block_stats must be a contiguous fp32 [M, V/64, 2] tensor on the inputs' device")
     with torch.cuda.device(dev):
-        check(lib.pmhip_guidance_combine_slots(_p(cond), _p(uncond), _p(guides), _p(slots), int(tokens), _p(out), _p(block_stats), M, V,
-                                               stream_ptr(dev)), "pmhip_guidance_combine_slots")
+        if which is None:
+            check(lib.pmhip_guidance_combine_slots(_p(cond), _p(uncond), _p(guides), _p(slots), int(tokens), _p(out), _p(block_stats), M, V,
+                                                   stream_ptr(dev)), "pmhip_guidance_combine_slots")
+        else:
+            check(lib.pmhip_guidance_combine_slots_which(_p(cond), _p(uncond), _p(guides), _p(slots), int(which), int(tokens), _p(out),
+                                                         _p(block_stats), M, V, stream_ptr(dev)), "pmhip_guidance_combine_slots_which")
     return out if block_stats is None else (out, block_stats)
 
 

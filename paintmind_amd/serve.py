@@ -26,7 +26,19 @@ context of a session has the same width D, top-k <= 8 (the block-statistics samp
 top-k up to n_embed, and ``None`` for no filter, DESIGN.md section 4n, but a session does not -- a batch that mixes requests at
 and above 8 needs a second sampling launch chosen step by step, which is not built), and idle slots still run through
 the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the second tower pass: the
-unconditional pass runs at the session's batch size.  Requests carry no negative prompt and no guidance schedule (``Pipeline.generate`` has both).
+unconditional pass runs at the session's batch size.
+
+A negative prompt and a guidance schedule are per request as well (``submit(negative_text=..., guidance_scale=[s_0, ..., s_T-1])``,
+what ``Pipeline.generate`` takes for a whole batch).  A request's negative context is ``[Ln_r, D]`` with its own length; the session
+keeps them in a second ``[S, capacity_n, D]`` tensor with the rules of the contexts (``max_negative_len``, or growing with the
+longest one admitted; growth or admission re-prepares the negative K/V; a step in which every occupied slot with a negative
+prompt fills the capacity passes no lengths).  The guide record of a slot says what it is guided against -- nothing, the pass
+without a context, or the negative context -- and the native step (pmhip_pipeline_step_slots_negative) runs, beside the
+conditional pass, the pass without a context iff an occupied slot needs it and the pass against the negative K/V iff one needs
+that: up to three tower passes, each combine touching only the slots of its kind.  A schedule is written into the slot's guide
+record step by step.  The contract reads ``generate_ids(..., guidance_scale=s or the schedule, negative_context=[S, capacity_n, D]
+with the request's rows in row j, negative_lens with Ln_r in row j)``.  A session without such a request runs the steps it ran
+before there were any.
 
 A choice temperature is per request too (``submit(choice_temperature=c)``): the request keeps MaskGIT's annealed value of each of
 its steps beside its temperatures and mask counts, the native step (pmhip_pipeline_step_slots_choice) reads one value per slot
@@ -35,7 +47,8 @@ non-zero value passes none, which IS the step without: the same kernels and grap
 not built.
 
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
-``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed, guidance_scale=s)``.
+``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed, guidance_scale=s,
+negative_text=n)``.
 """
 import collections
 import math
@@ -43,7 +56,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 
 Finished = collections.namedtuple("Finished", ["handle", "image", "ids"])
 
@@ -52,8 +65,10 @@ class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
     def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None,
-                 ctemps=None):
+                 ctemps=None, negative=None, scales=None):
         self.number, self.text, self.context = number, text, context
+        self.negative = negative                    # None: no negative prompt; else its context [Ln_r, D]
+        self.scales = scales                        # None: one scale (guidance_scale); else the scale of every step
         self.ctemps = ctemps                        # None: no choice temperature; else the annealed value of every step
         self.guidance_scale = guidance_scale        # None: not guided
         self.timesteps, self.temperature, self.topk, self.seed, self.image_index = timesteps, temperature, topk, seed, image_index
@@ -74,9 +89,13 @@ class DecodeSession:
     """``pipe.decode_session(slots=64, conditional=True, use_graph=True)``; see the module docstring.
     use_graph=None follows PMHIP_GENERATE_GRAPH like ``Pipeline.generate``."""
 
-    def __init__(self, pipe, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True, max_context_len=None):
+    def __init__(self, pipe, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True, max_context_len=None,
+                 max_negative_len=None):
         if slots < 1:
             raise ValueError("a decode session needs at least one slot")
+        if max_negative_len is not None and int(max_negative_len) < 1:
+            raise ValueError("max_negative_len must be >= 1 (or None: the capacity grows with the negative contexts admitted)")
+        self.max_negative_len = None if max_negative_len is None else int(max_negative_len)
         if max_context_len is not None and int(max_context_len) < 1:
             raise ValueError("max_context_len must be >= 1 (or None: the capacity grows with the contexts admitted)")
         self.max_context_len = None if max_context_len is None else int(max_context_len)
@@ -97,27 +116,54 @@ class DecodeSession:
         self._ctx = None                    # GPU, conditional: [S, capacity, context_dim] fp32, a slot's rows behind its length are 0
         self._ctx_dirty = True              # a slot's context changed since the cross K/V were prepared
         self._lens = [1] * self.size        # GPU, conditional: context rows of every slot (an idle slot keeps a valid value)
+        self._neg = None                    # GPU: [S, capacity_n, context_dim] fp32 once a request with a negative prompt was admitted
+        self._neg_dirty = True              # a slot's negative context changed since the negative K/V were prepared
+        self._neg_lens = [1] * self.size    # GPU: negative rows of every slot (a slot without a negative prompt keeps a valid value)
         self._records = (_lib.Slot * self.size)()
         self._guides = (_lib.SlotGuide * self.size)() if self.conditional else None
 
     # -- requests -----------------------------------------------------------------------------------
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
-               guidance_scale=None, choice_temperature=None):
+               guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None):
         """queue one request (any time, also between steps) -> its Request.  `context` [L_r, D] may be given instead of `text`
         (a conditional session runs the pipeline's text model on `text` otherwise), with its OWN length L_r: the request attends
         to exactly these rows; `ids0` [N]: start ids instead of all-mask;
         `guidance_scale` (None = not guided): this request samples from uncond + scale * (cond - uncond), like
         ``Pipeline.generate(guidance_scale=)``; `choice_temperature` (None or 0 = the deterministic re-masking): MaskGIT's base
-        choice temperature, annealed over this request's own steps like ``Pipeline.generate(choice_temperature=)``."""
+        choice temperature, annealed over this request's own steps like ``Pipeline.generate(choice_temperature=)``.
+        `guidance_scale` may also be a sequence of `timesteps` finite numbers, one per step of THIS request (a guidance schedule).
+        `negative_text` / `negative_context` [Ln_r, D] (needs guidance_scale): a negative prompt -- the request samples from
+        neg + scale * (cond - neg), like ``Pipeline.generate(negative_text=)``; the text goes through the pipeline's text model like
+        `text`, the context has its own length like `context`."""
         timesteps, topk = int(timesteps), int(topk)
+        if timesteps < 1:
+            raise ValueError("timesteps must be >= 1")
+        scales = None
         if guidance_scale is not None:
             if not self.conditional:
                 raise ValueError("guidance_scale needs a text condition (an unconditional session IS the unconditional branch)")
-            guidance_scale = float(guidance_scale)
-            if not math.isfinite(guidance_scale):
-                raise ValueError("guidance_scale must be finite")
-        if timesteps < 1:
-            raise ValueError("timesteps must be >= 1")
+            if isinstance(guidance_scale, (list, tuple, torch.Tensor)) or (hasattr(guidance_scale, "ndim") and guidance_scale.ndim > 0):
+                scales = ops.guidance_scales(guidance_scale, timesteps)
+            else:
+                guidance_scale = float(guidance_scale)
+                if not math.isfinite(guidance_scale):
+                    raise ValueError("guidance_scale must be finite")
+        negative = None
+        if negative_text is not None or negative_context is not None:
+            if not self.conditional:
+                raise ValueError("a negative prompt needs a text condition (an unconditional session IS the unconditional branch)")
+            if guidance_scale is None:
+                raise ValueError("a negative prompt needs guidance_scale (the step moves away from it by that much)")
+            if negative_context is None:
+                negative_context = self.pipe.text_model([negative_text])
+                if negative_context is None:
+                    raise ValueError("the pipeline's text model gives no context for the negative prompt")
+                negative_context = negative_context[0]
+            negative = negative_context.detach().to(torch.float32)
+            if negative.dim() != 2 or negative.shape[0] < 1:
+                raise ValueError(f"a request's negative context is [Ln, D] with Ln >= 1, got {tuple(negative.shape)}")
+            if self.max_negative_len is not None and negative.shape[0] > self.max_negative_len:
+                raise ValueError(f"a negative context of {negative.shape[0]} rows does not fit the session's max_negative_len={self.max_negative_len}")
         if not self._cpu and not 1 <= topk <= 8:
             raise ValueError(f"a decode session serves topk in 1..8, got {topk}")
         if self.conditional:
@@ -133,6 +179,8 @@ class DecodeSession:
                 raise ValueError(f"a request's context is [L, D] with L >= 1, got {tuple(context.shape)}")
             if self.max_context_len is not None and context.shape[0] > self.max_context_len:
                 raise ValueError(f"a context of {context.shape[0]} rows does not fit the session's max_context_len={self.max_context_len}")
+            if negative is not None and negative.shape[1] != context.shape[1]:
+                raise ValueError(f"a negative context has the context's width: {negative.shape[1]} != {context.shape[1]}")
         elif context is not None:
             raise ValueError("an unconditional session takes no context")
         if seed is None:
@@ -146,7 +194,7 @@ class DecodeSession:
         from .generate import loop_schedule
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.pipe.num_tokens, choice_temperature)
         r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale,
-                    ctemps)
+                    ctemps, negative, scales)
         self._submitted += 1
         self.queue.append(r)
         return r
@@ -201,8 +249,10 @@ class DecodeSession:
                 continue
             t = r.done
             ctx = None if r.context is None else r.context[None]
-            ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t, r.guidance_scale,
-                                        None, r.ctemps[t] if r.ctemps else 0.0)
+            neg = None if r.negative is None else r.negative[None]
+            ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t,
+                                        r.scales[t] if r.scales else r.guidance_scale, None, r.ctemps[t] if r.ctemps else 0.0,
+                                        negative=neg, negative_lens=None)
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
@@ -218,6 +268,7 @@ class DecodeSession:
         if self._ids is None or self._ids.device != eng.device:
             self._ids = pipe._start_ids(self.size, None, eng.device)
             self._ctx, self._ctx_dirty = None, True
+            self._neg, self._neg_dirty = None, True
         for r in admitted:
             self._ids[r.slot] = mask_id if r.ids0 is None else r.ids0[0].to(eng.device)
             if self.conditional:
@@ -235,6 +286,19 @@ class DecodeSession:
                 self._ctx[r.slot, Lr:] = 0
                 self._lens[r.slot] = Lr
                 self._ctx_dirty = True
+            if r.negative is not None:                   # the same bookkeeping for the negative contexts
+                n = r.negative.to(eng.device)
+                Ln = n.shape[0]
+                if self._neg is None:
+                    self._neg = torch.zeros(self.size, self.max_negative_len or Ln, n.shape[1], device=eng.device, dtype=torch.float32)
+                if Ln > self._neg.shape[1]:
+                    grown = torch.zeros(self.size, Ln, n.shape[1], device=eng.device, dtype=torch.float32)
+                    grown[:, :self._neg.shape[1]] = self._neg
+                    self._neg = grown
+                self._neg[r.slot, :Ln] = n
+                self._neg[r.slot, Ln:] = 0
+                self._neg_lens[r.slot] = Ln
+                self._neg_dirty = True
         if self.active == 0:
             return []
         retiring = []
@@ -244,8 +308,11 @@ class DecodeSession:
         for j, r in enumerate(self.occupied):
             rec = self._records[j]
             if self._guides is not None:
+                # what the slot is guided against (nothing / no context / its negative context) and THIS step's scale
                 on = r is not None and r.guidance_scale is not None
-                self._guides[j].scale, self._guides[j].on = (r.guidance_scale if on else 0.0), int(on)
+                kind = _lib.GUIDE_OFF if not on else _lib.GUIDE_UNCOND if r.negative is None else _lib.GUIDE_NEGATIVE
+                scale = 0.0 if not on else r.scales[r.done] if r.scales else r.guidance_scale
+                self._guides[j].scale, self._guides[j].on = scale, kind
             if r is None:
                 rec.step = _lib.SLOT_IDLE
                 continue
@@ -262,17 +329,26 @@ class DecodeSession:
         if self.conditional and any(r is not None and self._lens[j] != ctx.shape[1] for j, r in enumerate(self.occupied)):
             lens = [min(n, ctx.shape[1]) for n in self._lens]
 
-        def run(keep_context):
+        # the negative contexts: once a request brought one, every step hands the tensor over (or keeps its K/V), so that the set
+        # outlives the steps in which no occupied slot uses it; lengths like the contexts', over the slots that have a negative prompt
+        neg, neg_lens = self._neg, None
+        keep_neg = neg is not None and not self._neg_dirty
+        if neg is not None and any(r is not None and r.negative is not None and self._neg_lens[j] != neg.shape[1]
+                                   for j, r in enumerate(self.occupied)):
+            neg_lens = [min(n, neg.shape[1]) for n in self._neg_lens]
+
+        def run(keep_context, keep_negative):
             return eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep_context, want_aux=want_aux,
-                                  guides=self._guides, context_lens=lens, choice=choice)
+                                  guides=self._guides, context_lens=lens, choice=choice, negative_context=neg, negative_lens=neg_lens,
+                                  keep_negative=keep_negative)
         try:
-            _, pred, score = run(keep)
+            _, pred, score = run(keep, keep_neg)
         except _lib.PmhipError as e:
-            # another call on this handle (pipe.generate, a rebuilt engine ...) replaced the prepared context: prepare it again
-            if not (keep and getattr(e, "code", None) == _lib.PMHIP_ESTATE):
+            # another call on this handle (pipe.generate, a rebuilt engine ...) replaced the prepared contexts: prepare them again
+            if not ((keep or keep_neg) and getattr(e, "code", None) == _lib.PMHIP_ESTATE):
                 raise
-            _, pred, score = run(False)
-        self._ctx_dirty = False
+            _, pred, score = run(False, False)
+        self._ctx_dirty = self._neg_dirty = False
         for r in self.occupied:
             if r is not None:
                 r.done += 1

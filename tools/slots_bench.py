@@ -14,6 +14,11 @@
                     generate_ids(guidance_scale=, use_graph=True, streams=1); then the same with every second request unguided
                     against one generate_ids per homogeneous group (S/2 guided, S/2 unguided).
 
+  negative a negative prompt per request: milliseconds per session step by tower passes -- S conditional
+           requests (T steps, a [77, D] context each) admitted together, all unguided (one pass), all guided without a negative
+           prompt (two), all guided against a --neg-rows negative context (two, the second against the negative K/V), half and
+           half (three).  --arms picks among one,two_uncond,two_negative,three: a commit without the feature runs the first two.
+
 The arms alternate inside one process, --rounds times; nothing is decoded (ids only).  --arms generate runs on a commit that has
 no sessions: point --root at such a checkout to time the scalar loop of another commit on the same box.
 """
@@ -28,7 +33,7 @@ import time
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="checkout whose paintmind_amd is timed")
-    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed", "guided"])
+    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed", "guided", "negative"])
     ap.add_argument("--arms", default="session,generate")
     ap.add_argument("--workload", default=None, help="default: bench-uncond-12L-d512; guided: bench-text-24L-d768")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
@@ -36,6 +41,7 @@ def main():
     ap.add_argument("--timesteps", type=int, default=None, help="default: 8; guided: 12")
     ap.add_argument("--part", default="all", choices=["kernel", "session", "all"], help="guided: which half to run")
     ap.add_argument("--scale", type=float, default=3.0)
+    ap.add_argument("--neg-rows", type=int, default=77, help="negative: rows of every request's negative context")
     ap.add_argument("--rows", type=int, default=65536, help="guided kernel: rows of the planes (a multiple of --tokens)")
     ap.add_argument("--classes", type=int, default=8192)
     ap.add_argument("--tokens", type=int, default=1024)
@@ -48,6 +54,8 @@ def main():
     a = ap.parse_args()
     a.workload = a.workload or ("bench-text-24L-d768" if a.mode == "guided" else "bench-uncond-12L-d512")
     a.timesteps = a.timesteps or (12 if a.mode == "guided" else 8)
+    if a.mode == "negative" and a.arms == "session,generate":
+        a.arms = "one,two_uncond,two_negative,three"
     sys.path.insert(0, a.root)
     import torch
     import paintmind_amd as pm
@@ -63,6 +71,9 @@ def main():
         if a.part in ("session", "all"):
             out["session"] = guided_session(a, dev)
         emit(out, a.out)
+        return
+    if a.mode == "negative":
+        emit(negative_session(a, dev), a.out)
         return
     pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
     pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
@@ -205,6 +216,52 @@ def guided_session(a, dev):
     one, two = pipe.engine().slots_steps()
     return {"workload": a.workload, "slots": S, "timesteps": T, "scale": scale, "reps": a.reps, "images_per_s": res,
             "slots_steps": {"one_pass": one, "two_pass": two}}
+
+
+def negative_session(a, dev):
+    """ms per session step (graph replay, nothing decoded) by the tower passes the step runs"""
+    import torch
+    import paintmind_amd as pm
+    from paintmind_amd.generate import Pipeline
+    pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
+    pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    S, T, scale = a.slots, a.timesteps, a.scale
+    D = pipe.engine().context_dim
+    g = torch.Generator(device=dev).manual_seed(2)
+    ctx = torch.randn(S, 77, D, device=dev, generator=g)
+    neg = torch.randn(S, a.neg_rows, D, device=dev, generator=g)
+    # per arm: (guided, with a negative prompt) of request i
+    kinds = {"one": lambda i: (False, False), "two_uncond": lambda i: (True, False), "two_negative": lambda i: (True, True),
+             "three": lambda i: (True, i % 2 == 1)}
+    arms = a.arms.split(",")
+
+    def run(arm, seed):
+        s = pipe.decode_session(slots=S, conditional=True, use_graph=True, decode=False)
+        for i in range(S):
+            guided, negative = kinds[arm](i)
+            kw = dict(negative_context=neg[i]) if negative else {}
+            s.submit(context=ctx[i], timesteps=T, temperature=1.0, topk=5, seed=seed + i, guidance_scale=scale if guided else None, **kw)
+        assert len(s.drain()) == S and s.tick == T
+
+    for arm in arms:                                   # eager pass, capture pass, replay
+        for w in range(3):
+            run(arm, w)
+    torch.cuda.synchronize(dev)
+    ms = {arm: [] for arm in arms}
+    for rnd in range(a.rounds):
+        for arm in arms:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for rep in range(a.reps):
+                run(arm, 100 * rnd + rep)
+            torch.cuda.synchronize(dev)
+            ms[arm].append(1e3 * (time.perf_counter() - t0) / (a.reps * T))
+    out = {"mode": "negative", "root": os.path.abspath(a.root), "workload": a.workload, "dtype": a.dtype, "slots": S, "timesteps": T,
+           "context_rows": 77, "negative_rows": a.neg_rows, "scale": scale, "reps": a.reps, "ms_per_step": ms}
+    eng = pipe.engine()
+    if hasattr(eng, "slots_passes"):
+        out["slots_passes"] = dict(zip(("one", "two", "three"), eng.slots_passes()))
+    return out
 
 
 if __name__ == "__main__":
