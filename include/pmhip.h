@@ -355,7 +355,7 @@ typedef struct pmhip_slot {      /* one per image of the batch, 32 bytes */
     uint64_t seed;               /* Philox key */
     uint64_t image_index;        /* global image index: the row counter is image_index * tokens + position */
     float    temperature;        /* this step's temperature, as the caller derived it */
-    int32_t  topk;               /* 1..8 */
+    int32_t  topk;               /* 1..8 (1..V through the *_filter entries) */
     int32_t  num_mask;           /* this step's num_token_masked, >= 1 */
     uint32_t step;               /* Philox counter word; bit 31 set = slot idle */
 } pmhip_slot;
@@ -368,6 +368,20 @@ typedef struct pmhip_slot {      /* one per image of the batch, 32 bytes */
 int pmhip_sample_rows_slots(const float* logits, int ldl, const float* block_stats /* or NULL */,
                             const int64_t* ids_in, int64_t mask_id, const pmhip_slot* slots, int tokens,
                             int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream);
+/* THE SAMPLER FILTERS PER IMAGE (a new entry within ABI 11): pmhip_sample_rows_slots with slots[b].topk
+ * anywhere in 1..V (V: no filter) and a nucleus mass per image, top_p_dev a DEVICE float [B] beside the records (NULL: every slot
+ * 1; an idle slot's value is not looked at).  Which kernel serves a row is the rule of the scalar entries, per slot: top_p < 1 the
+ * nucleus kernel, else topk <= 8 the block-statistics kernel, <= 64 the row kernel, above it the selection kernel.  Four launches
+ * in that fixed order (block statistics, row, selection, nucleus), each serving the rows of its class only -- every row of
+ * pred_out / ids_out / score_out is written by exactly one of them, an idle slot's by the first (ids_out = ids_in, pred = ids_in,
+ * score = -1e5) -- so image b's rows equal, bit for bit, pmhip_sample_rows, pmhip_sample_rows_stats or pmhip_sample_rows_nucleus
+ * called on that image alone with its slot's values and row_base = image_index * tokens.  Shapes as pmhip_sample_rows_slots: V %
+ * 64 == 0, V <= 16384, M % tokens == 0, ldl >= V, ids_out == ids_in allowed; block_stats (read by the first launch only) may be
+ * NULL.  The records are device memory and are not validated here: a caller keeps 1 <= topk <= V and 0 < top_p <= 1. */
+int pmhip_sample_rows_slots_filter(const float* logits, int ldl, const float* block_stats /* or NULL */,
+                                   const int64_t* ids_in, int64_t mask_id, const pmhip_slot* slots /* DEVICE [B] */,
+                                   const float* top_p_dev /* DEVICE [B], or NULL: every slot 1 */, int tokens,
+                                   int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream);
 /* pmhip_remask with num_mask = slots[b].num_mask; the row of an idle slot is left untouched.  Same keys, order and threshold. */
 int pmhip_remask_slots(int64_t* ids, const float* scores, const pmhip_slot* slots, int64_t mask_id,
                        int B, int N, pmhip_stream stream);
@@ -552,7 +566,7 @@ int pmhip_s2_forward(pmhip_s2* h, const float* tokens, const float* context, int
  * img_out may be NULL (skip the ViT decode of generate.py:165); pred_out/score_out may be NULL.
  * topk, here and in every pmhip_pipeline_* entry below that takes one as an argument (sample / generate, their _guided, _lens and
  * _choice forms): 1 <= topk <= n_embed, as pmhip_sample_rows serves it; topk = n_embed samples without a filter.  The slots
- * entries keep 1..8 per record (pmhip_pipeline_step_slots). */
+ * entries keep 1..8 per record (pmhip_pipeline_step_slots); pmhip_pipeline_step_slots_filter serves 1..n_embed per slot. */
 int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L,
                           int B, int topk, float temperature, int num_mask, const float* noise,
                           uint64_t seed, uint32_t step, uint64_t image_base, float* img_out,
@@ -721,7 +735,8 @@ int pmhip_pipeline_step_slots_choice(pmhip_s2* s2, int64_t* ids, const float* co
  * loop, for every step.  top_p == 1 runs exactly the *_choice entry: the same kernels and the same captured graphs.  Below 1 the
  * sampling launch is the nucleus kernel and nothing else of the step changes, so it composes with guidance, context lengths,
  * choice temperatures, lanes and PMHIP_GENERATE_FROM_MASK; with the graph flag top_p is a kernel argument of the captured loop,
- * like topk: one graph per value.  The slots entries have no top_p: a pmhip_slot record carries none. */
+ * like topk: one graph per value.  The slots entries have no top_p: a pmhip_slot record carries none
+ * (pmhip_pipeline_step_slots_filter takes one per slot beside the records). */
 int pmhip_pipeline_sample_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                   const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
                                   uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
@@ -820,6 +835,28 @@ int pmhip_pipeline_step_slots_negative(pmhip_s2* s2, int64_t* ids, const float* 
                                        const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
                                        const int32_t* neg_lens_host /* [B] or NULL */, int flags,
                                        int64_t* pred_out, float* score_out, pmhip_stream stream);
+
+/* THE SAMPLER FILTERS PER SLOT (new entries within ABI 11): pmhip_pipeline_step_slots_negative, the widest
+ * slots entry, with the wider sampler.  Through THIS entry an active slot may carry 1 <= topk <= n_embed (n_embed: no filter) and
+ * a nucleus mass top_p_host[b], finite and in (0, 1] (top_p_host a HOST float [B], or NULL: every slot 1); idle slots are not
+ * looked at.  Validated before anything is staged or launched (PMHIP_EINVAL, ids untouched; the message names the slot).  The five
+ * entries above keep their 1..8 per record.
+ * When every active slot is served by the block-statistics kernel (top_p == 1 and topk <= 8) the call runs exactly
+ * pmhip_pipeline_step_slots_negative: the same launches, the same graph key, the same captured graph.  Otherwise the sampling
+ * tail is the four launches of pmhip_sample_rows_slots_filter; the tower passes, the combines, the re-masking and the choice
+ * temperature stay as they are.  top_p travels in the pinned-ring entry of the records, behind the choice temperatures (an idle
+ * slot's is 1), into a handle-owned device array; with PMHIP_SLOTS_GRAPH the chain form has one further graph key, and as every
+ * record value and top_p are read from device memory, that one graph serves every mix of classes and values.  A slot computes,
+ * bit for bit, what pmhip_pipeline_sample / _nucleus computes for that image alone with its values. */
+int pmhip_pipeline_step_slots_filter(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                     const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
+                                     const pmhip_slot_guide* guides_host, const float* choice_host /* [B] or NULL */,
+                                     const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                     const int32_t* neg_lens_host /* [B] or NULL */, const float* top_p_host /* [B] or NULL */,
+                                     int flags, int64_t* pred_out, float* score_out, pmhip_stream stream);
+/* Steps pmhip_pipeline_step_slots_filter ran on this handle, by the form of the sampling tail: *tiles_only the one
+ * block-statistics launch (every active slot at topk <= 8 without a nucleus), *chain the four launches.  Either may be NULL. */
+int pmhip_s2_slots_filter_steps(const pmhip_s2* h, int* tiles_only, int* chain);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

@@ -191,6 +191,12 @@ PROTOTYPES = {
     "pmhip_pipeline_step_slots_negative": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
                                                  vp, i32, C.POINTER(i32), i32, vp, vp, vp]),
     "pmhip_s2_slots_passes": (i32, [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+    # the sampler filters per slot: the operator with a launch per class, the slots entry that takes top-k up
+    # to n_embed and a nucleus mass per slot, its counters
+    "pmhip_sample_rows_slots_filter": (i32, [vp, i32, vp, vp, i64, vp, vp, i32, vp, vp, vp, i32, i32, vp]),
+    "pmhip_pipeline_step_slots_filter": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
+                                               vp, i32, C.POINTER(i32), C.POINTER(f32), i32, vp, vp, vp]),
+    "pmhip_s2_slots_filter_steps": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

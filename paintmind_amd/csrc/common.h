@@ -90,7 +90,8 @@ constexpr uint32_t PM_SLOT_IDLE = 0x80000000u;              // bit 31 of pmhip_s
 //   BATCH   the scalars below, one set for every row;
 //   PARAMS  a replayed graph: temperature, mask count, seed and row base from the device block gp, indexed by `step`; top-k and
 //           the step stay kernel arguments (they are part of the graph);
-//   SLOTS   per image: the device records slots [M / tokens] (the block-statistics kernel only: V % 64 == 0, top-k <= 8, no top_p).
+//   SLOTS   per image: the device records slots [M / tokens] (V % 64 == 0; the block-statistics kernel only, top-k <= 8 and no top_p --
+//           unless with_filters() asks for the launch per class).
 // ---------------------------------------------------------------------------------------------
 struct PmStepSource {
     enum Kind { BATCH, PARAMS, SLOTS } kind;
@@ -120,7 +121,23 @@ struct PmStepSource {
     // coming from the source's kind.  NULL (the default): the kernels that ran before.  Appended: nothing above moves.
     const int32_t* counts = nullptr;
     PmStepSource with_counts(const int32_t* dev) const { PmStepSource r = *this; r.counts = dev; return r; }
+    // The sampler filters PER IMAGE (pm_sample_rows only, a SLOTS source): every slot's top-k in 1..V and its
+    // nucleus mass from top_p_dev, a device float [B] beside the records (NULL: every slot 1) -- the launcher then issues one launch
+    // per class of pm_sample_class, each serving the rows of its class.  Off (the default): the one block-statistics launch, top-k
+    // <= 8, as before.  Appended: nothing above moves.
+    const float* top_p_dev = nullptr; bool filters = false;
+    PmStepSource with_filters(const float* dev) const { PmStepSource r = *this; r.top_p_dev = dev; r.filters = true; return r; }
 };
+// Which sampling kernel serves a row: a function of (top-k, top_p < 1) ONLY -- the kernels differ in the last bits of the
+// confidence, so a request's rows run on the kernel its own scalar run picks, whatever shares the batch.
+// The scalar launcher and the per-image kernels both ask here.  (A scalar launch whose V is no multiple of 64 serves class T on
+// the row kernel: pm_sample_rows.)
+constexpr int KT_MAX = 8;                                  // top-k served by sample_tiles_kernel
+constexpr int K_LANES = 64;                                // top-k served by sample_rows_kernel: one candidate per lane
+enum PmSampleClass { PM_CLASS_TILES = 0, PM_CLASS_ROWS = 1, PM_CLASS_WIDE = 2, PM_CLASS_NUCLEUS = 3 };
+__host__ __device__ inline int pm_sample_class(int topk, bool nucleus) {
+    return nucleus ? PM_CLASS_NUCLEUS : topk <= KT_MAX ? PM_CLASS_TILES : topk <= K_LANES ? PM_CLASS_ROWS : PM_CLASS_WIDE;
+}
 // a step's nucleus mass: finite, 0 < top_p <= 1
 int pm_check_top_p(const char* who, float p);
 // a step's choice temperature: finite, 0 <= t <= 1000 (the bound keeps every noisy key above the -1e5 of a given id)

@@ -776,6 +776,7 @@ struct pmhip_s2 {
     PinnedRing neg_lens_ring;       // ... and of its negative context (neg_lens_host): B int32 -> workspace "neg.lens"
     PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
     int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
+    int slots_filter_tiles = 0, slots_filter_chain = 0;   // steps of pmhip_pipeline_step_slots_filter by the form of their sampling tail
     int slots_ctx_B = 0, slots_ctx_L = -1;
     int slots_neg_B = 0, slots_neg_Ln = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
@@ -1030,12 +1031,18 @@ struct Step {
     // the token draw's nucleus mass: the batch's value, with the scalars and with gp alike (a kernel argument
     // of a captured step, like top-k); a slots step has none.  1: no filter.
     float top_p = 1.f;
+    // the sampler filters per slot (pmhip_pipeline_step_slots_filter): the sampling tail of a slots step is
+    // the launch per class, every slot's nucleus mass from the device array top_p_dev [B].  Off: the one block-statistics launch.
+    bool filters = false; const float* top_p_dev = nullptr;
     // the edit loop: counts = the step's re-masking counts, a device int32 [B] beside the scalars or gp (NULL:
     // one count for the batch); decode_merged: the step's image -- inline or deferred -- is decoded from the MERGED ids
     const int32_t* counts = nullptr; bool decode_merged = false;
     PmStepSource source(int tokens) const { return source_of(tokens).with_counts(counts); }
     PmStepSource source_of(int tokens) const {
-        if (slots) { const PmStepSource p = PmStepSource::per_image(slots, tokens); return (choice_dev ? p.with_choice_dev(choice_dev) : p).with_top_p(top_p); }
+        if (slots) {
+            const PmStepSource p = PmStepSource::per_image(slots, tokens), q = (choice_dev ? p.with_choice_dev(choice_dev) : p).with_top_p(top_p);
+            return filters ? q.with_filters(top_p_dev) : q;
+        }
         if (gp) { const PmStepSource p = PmStepSource::params(gp, topk, step); return (choice_params ? p.with_choice_params() : p).with_top_p(top_p); }
         return PmStepSource::batch(topk, temperature, num_mask, seed, step, image_base * (uint64_t)tokens).with_choice(choice_t, choice_noise).with_top_p(top_p);
     }
@@ -1729,13 +1736,18 @@ extern "C" int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, i
 // context, 2 the negative context's K/V -- and the host decides the passes per step: the conditional tower, the tower without a
 // context iff an active slot has on == 1, the tower against the negative set iff one has on == 2, each of the two followed by the
 // combine of its kind.  The negative set is prepared eagerly like the context's, or kept from the previous slots call.
+// filters / top_p_host (pmhip_pipeline_step_slots_filter; false / NULL from the five older entries): an active
+// slot may carry top-k up to n_embed and a nucleus mass.  The host decides the form of the sampling tail per STEP: the one
+// block-statistics launch of the older entries (their launches, graph key and graph) unless an active slot is of another class
+// (common.h pm_sample_class) -- then the launch per class, with the masses staged behind the choice temperatures.
 static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                            const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host, int flags,
                            int64_t* pred_out, float* score_out, pmhip_stream stream, bool kinds = false, const float* neg_context = nullptr,
-                           int Ln = 0, const int32_t* neg_lens_host = nullptr) {
+                           int Ln = 0, const int32_t* neg_lens_host = nullptr, bool filters = false, const float* top_p_host = nullptr) {
     const bool keep_neg = kinds && (flags & PMHIP_SLOTS_KEEP_NEGATIVE) != 0;
     const bool neg_set = neg_context || keep_neg;             // this call has a negative set, given or kept
-    const char* who = (neg_set || neg_lens_host) ? "pipeline_step_slots_negative" : choice_host ? "pipeline_step_slots_choice" : narrow;
+    const char* who = filters ? "pipeline_step_slots_filter"
+                              : (neg_set || neg_lens_host) ? "pipeline_step_slots_negative" : choice_host ? "pipeline_step_slots_choice" : narrow;
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0), L, B));
     const auto& c = s2->cfg;
@@ -1747,6 +1759,7 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
                    (int)neg_lens_host[b], Ln);
     bool two_pass = false, choice = false;      // choice: an active slot has a choice temperature other than 0 (else: the step without)
     bool pass_neg = false, pass_uncond = false;               // an active slot guided against the negative set / against no context
+    bool chain = false;                                       // filters: an active slot is of another class than the block-statistics kernel's
     for (int b = 0; b < B; ++b) {
         const pmhip_slot& sl = slots_host[b];
         if (sl.step & PM_SLOT_IDLE) continue;
@@ -1754,7 +1767,14 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
             PM_TRY(pm_check_choice_t(who, choice_host[b]));
             choice = choice || choice_host[b] != 0.f;
         }
-        PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "%s: slot %d: topk=%d must be in [1, 8]", who, b, sl.topk);
+        if (filters) {
+            PM_REQUIRE(sl.topk >= 1 && sl.topk <= c.n_embed, "%s: slot %d: topk=%d must be in [1, n_embed=%d]", who, b, sl.topk, c.n_embed);
+            const float p = top_p_host ? top_p_host[b] : 1.f;
+            PM_TRY(pm_check_top_p((std::string(who) + ": slot " + std::to_string(b)).c_str(), p));
+            chain = chain || pm_sample_class(sl.topk, p < 1.f) != PM_CLASS_TILES;
+        } else {
+            PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "%s: slot %d: topk=%d must be in [1, 8]", who, b, sl.topk);
+        }
         PM_REQUIRE(sl.num_mask >= 1, "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
         if (guides_host && guides_host[b].on) {
             PM_REQUIRE(!kinds || guides_host[b].on <= 2, "%s: slot %d: on=%u must be 0, 1 or 2", who, b, guides_host[b].on);
@@ -1817,7 +1837,12 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     const size_t choice_at = (slot_bytes + guide_bytes + 15) & ~(size_t)15, choice_bytes = (size_t)round_up(B, 4) * 4;
     float* dchoice = nullptr;
     if (choice) WS(s2->ws, "slots.choice", choice_bytes, dchoice);
-    PM_TRY(s2->slots_ring.reserve(choice_at + choice_bytes));
+    // ... and behind those (choice_bytes is whole 16-byte words) the B nucleus masses of a step whose tail is the launch per class,
+    // padded the same way; an idle slot's is 1
+    const size_t top_p_at = choice_at + choice_bytes, top_p_bytes = choice_bytes;
+    float* dtop_p = nullptr;
+    if (chain) WS(s2->ws, "slots.top_p", top_p_bytes, dtop_p);
+    PM_TRY(s2->slots_ring.reserve(top_p_at + top_p_bytes));
     PM_TRY(s2->slots_ring.acquire());
     PM_TRY(s2->slots_ring.stage(dslots, 0, slots_host, slot_bytes, s));
     if (two_pass) PM_TRY(s2->slots_ring.stage(dguides, slot_bytes, guides_host, guide_bytes, s));
@@ -1826,7 +1851,13 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
         for (int b = 0; b < B; ++b) padded[b] = (slots_host[b].step & PM_SLOT_IDLE) ? 0.f : choice_host[b];
         PM_TRY(s2->slots_ring.stage(dchoice, choice_at, padded.data(), choice_bytes, s));
     }
+    if (chain) {
+        std::vector<float> padded(top_p_bytes / 4, 1.f);
+        for (int b = 0; b < B; ++b) padded[b] = ((slots_host[b].step & PM_SLOT_IDLE) || !top_p_host) ? 1.f : top_p_host[b];
+        PM_TRY(s2->slots_ring.stage(dtop_p, top_p_at, padded.data(), top_p_bytes, s));
+    }
     PM_TRY(s2->slots_ring.commit(s));
+    if (filters) ++(chain ? s2->slots_filter_chain : s2->slots_filter_tiles);
     ++(pass_neg && pass_uncond ? s2->slots_three_pass : two_pass ? s2->slots_two_pass : s2->slots_one_pass);
     Step st;
     st.slots = dslots;
@@ -1834,6 +1865,8 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     st.slots_neg = pass_neg;
     st.slots_uncond = pass_uncond;
     st.choice_dev = dchoice;
+    st.filters = chain;                                       // every active slot of class T: the step of the entries without filters
+    st.top_p_dev = dtop_p;
     auto run_step = [&](int64_t* on_ids, int64_t* pred, float* score, hipStream_t on) -> int {
         return sample_step(s2, nullptr, on_ids, B, st, nullptr, pred, score, on);
     };
@@ -1851,7 +1884,7 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     const char* passes = pass_neg ? (pass_uncond ? "slotsthreeB" : "slotsnegB") : two_pass ? "slotsguidedB" : "slotsB";
     const std::string neg_key = pass_neg ? "N" + std::to_string(Ln) + (neg_lens_host ? "n" : "") : "";
     GraphEntry& ge = s2->graphs[passes + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
-                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key];
+                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "")];
     PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
@@ -1894,6 +1927,23 @@ extern "C" int pmhip_pipeline_step_slots_negative(pmhip_s2* s2, int64_t* ids, co
                                                   int64_t* pred_out, float* score_out, pmhip_stream stream) {
     return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
                            score_out, stream, true, neg_context, Ln, neg_lens_host);
+}
+
+// top_p_host NULL and every active slot at topk <= 8: exactly pmhip_pipeline_step_slots_negative
+extern "C" int pmhip_pipeline_step_slots_filter(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                                const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
+                                                const float* neg_context, int Ln, const int32_t* neg_lens_host, const float* top_p_host,
+                                                int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
+                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host);
+}
+
+// steps of that entry by the form of their sampling tail
+extern "C" int pmhip_s2_slots_filter_steps(const pmhip_s2* h, int* tiles_only, int* chain) {
+    PM_REQUIRE(h, "s2_slots_filter_steps: null handle");
+    if (tiles_only) *tiles_only = h->slots_filter_tiles;
+    if (chain) *chain = h->slots_filter_chain;
+    return PMHIP_OK;
 }
 
 // slots steps by tower passes: one (no active slot guided) / exactly two

@@ -29,6 +29,10 @@
 // replayed graph, or the pmhip_slot record of the row's image -- common.h PmStepSource), an element's noise and perturbed value
 // (perturbed), the draw among up to 64 candidates (draw_among) and the store of the row's outcome (store_outcome).  The host side
 // has one launcher per kernel family (pm_sample_rows, pm_remask): one copy of the checks, one place that picks the instantiation.
+//
+// Which of the four sampling kernels serves a row is pm_sample_class (common.h), a function of (top-k, top_p < 1).  A batch-scalar
+// launch asks it once; a per-image launch with filters is four launches, one per class, in which every
+// kernel's SLOTS form asks it per slot and serves the rows of its own class only (slot_in_class).
 #include <stdlib.h>
 #include <cmath>
 #include <type_traits>
@@ -124,6 +128,18 @@ __device__ __forceinline__ RowStep row_step(RowStep v, int row, const PmGenParam
     return v;
 }
 
+// ---- the class test of a per-image launch with filters (PmStepSource::with_filters).  The launcher issues
+// one launch per class of pm_sample_class, and every row belongs to exactly one of them: the wave of a row whose slot is of another
+// class returns before it touches any output, and so does the wave of an idle slot's row -- except in the block-statistics launch
+// (class T), which writes the idle rows.  The slot's nucleus mass comes back in `top_p`: top_p_dev[image] (NULL: 1), wave-uniform
+// like the record's values.  Only instantiated forms with SLOTS call this: the scalar forms gain nothing.
+__device__ __forceinline__ bool slot_in_class(int cls, const RowStep& rs, int row, int tokens, const float* __restrict__ top_p_dev,
+                                              float& top_p) {
+    top_p = 1.f;
+    if (top_p_dev) top_p = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(top_p_dev[row / tokens])));
+    return !rs.idle && pm_sample_class(rs.topk, top_p < 1.f) == cls;
+}
+
 // its sibling for the re-masking kernel (one workgroup per image): how many positions image `img` masks; false: an idle slot
 template <bool SLOTS>
 __device__ __forceinline__ bool image_num_mask(int& num_mask, int img, const PmGenParams* __restrict__ gp, int step,
@@ -211,16 +227,25 @@ __device__ __forceinline__ void store_outcome(int row, bool drawn, int64_t pred,
 // PERIOD: logits row r is read from row r % period (every image of a batch samples from ONE image's logits -- the shared step 0 of
 // an unconditional loop, engine.hip); ids, predictions, scores, the noise and the Philox counters stay per row.  The other
 // instantiation never looks at `period`.
-template <int NV4, bool PERIOD = false>
+// SLOTS (a launch of class R for pmhip_sample_rows_slots_filter; no PERIOD form): the step values of row r come from slots[r /
+// tokens] (row_step), and only the rows whose slot is of this kernel's class are served (slot_in_class); everything below the
+// prologue is the code of the scalar form.
+template <int NV4, bool PERIOD = false, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
     const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, int64_t mask_id, int topk,
     float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
-    const PmGenParams* __restrict__ gp, int period) {
+    const PmGenParams* __restrict__ gp, int period, const pmhip_slot* __restrict__ slots, int tokens,
+    const float* __restrict__ top_p_dev) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
     if (row >= M) return;                                  // whole wave exits together
-    const RowStep rs = row_step<false>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, nullptr, 0);
+    const RowStep rs = row_step<SLOTS>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, slots, tokens);
+    if constexpr (SLOTS) {                                 // wave-uniform, like the kernel argument it replaces
+        float mass;
+        if (!slot_in_class(PM_CLASS_ROWS, rs, row, tokens, top_p_dev, mass)) return;
+        topk = rs.topk;
+    }
     const int lr = PERIOD ? row % period : row;
     const float* lrow = logits + (size_t)lr * ldl;
 
@@ -296,12 +321,16 @@ __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
 //      `before`; one wave_best finishes the draw, and the winner's lane hands over the raw logit.
 // The walk is a loop of as many turns as the fullest lane has kept elements -- about k / 64 when the kept set is spread over
 // the lanes -- with ONE copy of the Philox and the logarithms; the rounds of 2 and 3 are counted, never data-dependent.
-template <int NV4, bool PERIOD = false>
+// SLOTS: as in sample_rows_kernel -- a launch of class W.
+template <int NV4, bool PERIOD = false, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void sample_wide_kernel(
     const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, int64_t mask_id, int topk,
     float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
-    const PmGenParams* __restrict__ gp, int period) {
+    const PmGenParams* __restrict__ gp, int period, const pmhip_slot* __restrict__ slots, int tokens,
+    const float* __restrict__ top_p_dev) {
+    constexpr int CLS = PM_CLASS_WIDE;
+    float top_p;                                           // (the class test's: this kernel has no use for the mass itself)
 #include "sample_select_prologue.h"
     // ---- 4. the kept set, one bit per element: bit s = g * 4 + e of the lane's words, so a lane's columns rise with s
     constexpr int NW = (NV4 * 4 + 31) / 32;
@@ -332,12 +361,15 @@ __global__ __launch_bounds__(THREADS) void sample_wide_kernel(
 //      plateau of equal weights is kept or dropped whole, the row's maximum (mass 0 above it) always stays, a weight that
 //      underflowed to 0 never does (t* >= 1).
 // The filter reads the raw logits; the temperature acts in the draw only and the confidence stays the unfiltered softmax's.
-template <int NV4, bool PERIOD = false>
+// SLOTS: as in sample_rows_kernel -- a launch of class N; top_p is the slot's, top_p_dev[image].
+template <int NV4, bool PERIOD = false, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void sample_nucleus_kernel(
     const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, int64_t mask_id, int topk, float top_p,
     float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
-    const PmGenParams* __restrict__ gp, int period) {
+    const PmGenParams* __restrict__ gp, int period, const pmhip_slot* __restrict__ slots, int tokens,
+    const float* __restrict__ top_p_dev) {
+    constexpr int CLS = PM_CLASS_NUCLEUS;
 #include "sample_select_prologue.h"
     // ---- a. weights in place of the keys (the value back from its key: orderable() undone)
     const int mine_last = last - lane * 4;
@@ -385,20 +417,21 @@ __global__ __launch_bounds__(THREADS) void sample_nucleus_kernel(
 
 
 // ---- the step from block statistics -----------------------------------------------------------------------------------------
-constexpr int KT_MAX = 8;                                  // top-k served by sample_tiles_kernel
-constexpr int K_LANES = 64;                                // top-k served by sample_rows_kernel: one candidate per lane
-
+// (KT_MAX = 8, the top-k this kernel serves, and K_LANES sit beside pm_sample_class in common.h)
 // NB2 = blocks per lane (block b is kept by lane b % 64).  DENSE: no statistics were handed in -- one pass over the stored row
 // computes them (lane l, group g: columns (g*64 + l)*4 .. +3, i.e. block g*4 + l/16 in the layout softmax_block_stat defines).
 // SLOTS (pmhip_sample_rows_slots): the step values of row r come from slots[r / tokens] (row_step); everything below the prologue
 // is the code of the scalar form.
 // PERIOD: as in sample_rows_kernel -- the logits AND the statistics of row r are those of row r % period.
-template <int NB2, bool DENSE, bool SLOTS = false, bool PERIOD = false>
+// FILTER (with SLOTS; pmhip_sample_rows_slots_filter): the launch of class T beside those of the row kernels -- it writes the idle
+// rows, as the SLOTS form does, and of the others those whose slot is of class T (slot_in_class).
+template <int NB2, bool DENSE, bool SLOTS = false, bool PERIOD = false, bool FILTER = false>
 __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
     const float* __restrict__ logits, int ldl, const float2* __restrict__ stats, const int64_t* __restrict__ ids_in, int64_t mask_id,
     int topk, float temperature, const float* __restrict__ noise, uint64_t seed, uint32_t step, uint64_t row_base,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
-    const PmGenParams* __restrict__ gp, const pmhip_slot* __restrict__ slots, int tokens, int period) {
+    const PmGenParams* __restrict__ gp, const pmhip_slot* __restrict__ slots, int tokens, int period,
+    const float* __restrict__ top_p_dev) {
     __shared__ float2 sh[DENSE ? THREADS / 64 : 1][DENSE ? NB2 * 64 : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int row = blockIdx.x * (THREADS / 64) + wave;
@@ -407,6 +440,10 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
     if (SLOTS && rs.idle) {                                // wave-uniform: nothing is drawn, the row keeps its id
         if (lane == 0) store_outcome(row, false, 0, 0.f, ids_in, mask_id, pred_out, ids_out, score_out);
         return;
+    }
+    if constexpr (SLOTS && FILTER) {
+        float mass;
+        if (!slot_in_class(PM_CLASS_TILES, rs, row, tokens, top_p_dev, mass)) return;
     }
     topk = rs.topk;
     const int lr = PERIOD ? row % period : row;
@@ -632,39 +669,60 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int p
     PmTimer tm(FAM_SAMPLE, s);
     // Which kernel runs depends on (V, topk) ONLY -- never on whether statistics were handed in: the two differ in the last bits
     // of the confidence (sample_rows_kernel); above top-k = 8 statistics are ignored.  The records of a slots launch carry
-    // top-k <= 8 (checked where they are staged).
-    // top_p < 1: the nucleus kernel for EVERY top-k -- the choice is a function of (V, topk, top_p < 1).
+    // top-k <= 8 (checked where they are staged) -- unless the source asks for the filters: then every class gets its launch.
+    // top_p < 1: the nucleus kernel for EVERY top-k -- the choice is a function of (V, topk, top_p < 1),
+    // pm_sample_class; a scalar launch of class T whose V is no multiple of 64 (or with the dev switch off) runs on the row kernel.
     static const int g_tiles = pm_dev_knob("PMHIP_SAMPLE_TILES", 1);     // 0: the one-read row kernel everywhere (A/B)
-    if (nucleus) {
-        pick<1, 4, 32, 64>(V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64, [&](auto NV4) {
-            pick<0, 1>(period != 0, [&](auto PER) {
-                hipLaunchKernelGGL((sample_nucleus_kernel<NV4(), PER() == 1>), grid, block, 0, s, logits, ldl, ids_in, mask_id, src.topk,
-                                   src.top_p, src.temperature, noise, src.seed, src.step, src.row_base, pred_out, ids_out, score_out, M, V,
-                                   src.gp, period);
-            });
-        });
-    } else if (slots || (g_tiles && src.topk <= KT_MAX && V % 64 == 0)) {
-        const float2* st = reinterpret_cast<const float2*>(block_stats);
-        pick<1, 2, 4>(V <= 4096 ? 1 : V <= 8192 ? 2 : 4, [&](auto NB2) {
-            pick<0, 1>(st == nullptr, [&](auto DENSE) {
-                pick<0, 1, 2>(slots ? 2 : period ? 1 : 0, [&](auto FORM) {      // scalar, period or slots: never two of them
-                    hipLaunchKernelGGL((sample_tiles_kernel<NB2(), DENSE() == 1, FORM() == 2, FORM() == 1>), grid, block, 0, s, logits, ldl, st,
-                                       ids_in, mask_id, src.topk, src.temperature, noise, src.seed, src.step, src.row_base, pred_out, ids_out,
-                                       score_out, M, V, src.gp, src.slots, src.tokens, period);
+    const bool filters = slots && src.filters;
+    // one launch of class `cls`; PER_IMAGE: the form that serves the rows of its class only (a filters source)
+    auto launch = [&](int cls, auto PER_IMAGE) {
+        constexpr bool PI = decltype(PER_IMAGE)::value == 1;
+        const int nv4 = V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64;
+        if (cls == PM_CLASS_NUCLEUS) {
+            pick<1, 4, 32, 64>(nv4, [&](auto NV4) {
+                pick<0, 1>(!PI && period != 0, [&](auto PER) {
+                    if constexpr (!(PI && PER() == 1))
+                        hipLaunchKernelGGL((sample_nucleus_kernel<NV4(), PER() == 1, PI>), grid, block, 0, s, logits, ldl, ids_in, mask_id,
+                                           src.topk, src.top_p, src.temperature, noise, src.seed, src.step, src.row_base, pred_out, ids_out,
+                                           score_out, M, V, src.gp, period, src.slots, src.tokens, src.top_p_dev);
                 });
             });
-        });
+        } else if (cls == PM_CLASS_TILES) {
+            const float2* st = reinterpret_cast<const float2*>(block_stats);
+            pick<1, 2, 4>(V <= 4096 ? 1 : V <= 8192 ? 2 : 4, [&](auto NB2) {
+                pick<0, 1>(st == nullptr, [&](auto DENSE) {
+                    // scalar, period, slots, or slots as one class among four: never two of them
+                    pick<0, 1, 2, 3>(PI ? 3 : slots ? 2 : period ? 1 : 0, [&](auto FORM) {
+                        if constexpr (PI == (FORM() == 3))
+                            hipLaunchKernelGGL((sample_tiles_kernel<NB2(), DENSE() == 1, FORM() >= 2, FORM() == 1, FORM() == 3>), grid, block, 0, s,
+                                               logits, ldl, st, ids_in, mask_id, src.topk, src.temperature, noise, src.seed, src.step, src.row_base,
+                                               pred_out, ids_out, score_out, M, V, src.gp, src.slots, src.tokens, period, src.top_p_dev);
+                    });
+                });
+            });
+        } else {
+            // the row kernels: candidate r in lane r up to top-k = 64 (K_LANES), the selection above it
+            pick<1, 4, 32, 64>(nv4, [&](auto NV4) {
+                pick<0, 1>(!PI && period != 0, [&](auto PER) {
+                    pick<0, 1>(cls == PM_CLASS_WIDE, [&](auto WIDE) {
+                        if constexpr (!(PI && PER() == 1)) {
+                            auto kernel = WIDE() == 1 ? sample_wide_kernel<NV4(), PER() == 1, PI> : sample_rows_kernel<NV4(), PER() == 1, PI>;
+                            hipLaunchKernelGGL(kernel, grid, block, 0, s, logits, ldl, ids_in, mask_id, src.topk, src.temperature, noise, src.seed,
+                                               src.step, src.row_base, pred_out, ids_out, score_out, M, V, src.gp, period, src.slots, src.tokens,
+                                               src.top_p_dev);
+                        }
+                    });
+                });
+            });
+        }
+    };
+    if (filters) {
+        // T, R, W, N in this order on the stream: every row is written by exactly one of them (slot_in_class), the idle rows by T
+        for (int cls : {PM_CLASS_TILES, PM_CLASS_ROWS, PM_CLASS_WIDE, PM_CLASS_NUCLEUS}) launch(cls, std::integral_constant<int, 1>{});
     } else {
-        // the row kernels: candidate r in lane r up to top-k = 64 (K_LANES), the selection above it
-        pick<1, 4, 32, 64>(V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64, [&](auto NV4) {
-            pick<0, 1>(period != 0, [&](auto PER) {
-                pick<0, 1>(src.topk > K_LANES, [&](auto WIDE) {
-                    auto kernel = WIDE() == 1 ? sample_wide_kernel<NV4(), PER() == 1> : sample_rows_kernel<NV4(), PER() == 1>;
-                    hipLaunchKernelGGL(kernel, grid, block, 0, s, logits, ldl, ids_in, mask_id, src.topk, src.temperature, noise, src.seed,
-                                       src.step, src.row_base, pred_out, ids_out, score_out, M, V, src.gp, period);
-                });
-            });
-        });
+        int cls = slots ? (int)PM_CLASS_TILES : pm_sample_class(src.topk, nucleus);
+        if (cls == PM_CLASS_TILES && !slots && !(g_tiles && V % 64 == 0)) cls = PM_CLASS_ROWS;
+        launch(cls, std::integral_constant<int, 0>{});
     }
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
@@ -703,6 +761,15 @@ extern "C" int pmhip_sample_rows_slots(const float* logits, int ldl, const float
                                        int M, int V, pmhip_stream stream) {
     return pm_sample_rows(logits, ldl, block_stats, 0, ids_in, mask_id, nullptr, pred_out, ids_out, score_out, M, V,
                           PmStepSource::per_image(slots, tokens), stream);
+}
+
+// ... with the sampler filters per image: top-k in 1..V from the record, the nucleus mass from top_p_dev [B] (NULL: every slot 1);
+// one launch per class of pm_sample_class
+extern "C" int pmhip_sample_rows_slots_filter(const float* logits, int ldl, const float* block_stats, const int64_t* ids_in, int64_t mask_id,
+                                              const pmhip_slot* slots, const float* top_p_dev, int tokens, int64_t* pred_out,
+                                              int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream) {
+    return pm_sample_rows(logits, ldl, block_stats, 0, ids_in, mask_id, nullptr, pred_out, ids_out, score_out, M, V,
+                          PmStepSource::per_image(slots, tokens).with_filters(top_p_dev), stream);
 }
 
 int pm_check_top_p(const char* who, float p) {

@@ -1,12 +1,18 @@
 // The prologue the selection kernels of sample.hip share (sample_wide_kernel, sample_nucleus_kernel; DESIGN.md sections 4n, 4o),
 // included into the kernel body like remask_select.h: one copy of the text, and each kernel compiles as if it were written out.
-// In scope: the kernel's parameters (logits, ldl, topk, temperature, seed, step, row_base, M, V, gp, period) and NV4, PERIOD.
+// In scope: the kernel's parameters (logits, ldl, topk, temperature, seed, step, row_base, M, V, gp, period, slots, tokens,
+// top_p_dev) and NV4, PERIOD, SLOTS; for the SLOTS form also CLS, the kernel's class (common.h pm_sample_class), and a float top_p
+// that takes the slot's nucleus mass: topk and top_p then are the slot's, wave-uniform like the arguments they replace.
 // Leaves behind: lane, row, rs, lrow, the normaliser (mx, se), the row's keys key[NV4][4] and (tau, last) -- an element is among
 // the first top-k of (value desc, column asc) iff key > tau, or key == tau and its column <= last; no column >= V is.
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
     if (row >= M) return;                                  // whole wave exits together
-    const RowStep rs = row_step<false>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, nullptr, 0);
+    const RowStep rs = row_step<SLOTS>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, slots, tokens);
+    if constexpr (SLOTS) {                                 // a per-image launch: the rows of class CLS only; top-k and top_p are the slot's
+        if (!slot_in_class(CLS, rs, row, tokens, top_p_dev, top_p)) return;
+        topk = rs.topk;
+    }
     const int lr = PERIOD ? row % period : row;
     const float* lrow = logits + (size_t)lr * ldl;
 

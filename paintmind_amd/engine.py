@@ -380,8 +380,15 @@ class S2Engine:
         check(self.lib.pmhip_s2_slots_passes(self.handle, C.byref(one), C.byref(two), C.byref(three)), "pmhip_s2_slots_passes")
         return one.value, two.value, three.value
 
+    def slots_filter_steps(self):
+        """(tiles_only, chain): the steps pmhip_pipeline_step_slots_filter ran on this handle, by the form of their sampling tail --
+        the one block-statistics launch (every active slot at topk <= 8 without a nucleus) or the launch per class"""
+        tiles, chain = C.c_int(0), C.c_int(0)
+        check(self.lib.pmhip_s2_slots_filter_steps(self.handle, C.byref(tiles), C.byref(chain)), "pmhip_s2_slots_filter_steps")
+        return tiles.value, chain.value
+
     def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None,
-                   choice=None, negative_context=None, negative_lens=None, keep_negative=False):
+                   choice=None, negative_context=None, negative_lens=None, keep_negative=False, top_p=None):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
@@ -395,6 +402,10 @@ class S2Engine:
         the pass without a context (on == 1); negative_lens: per-slot lengths of it for THIS step, like context_lens.
         keep_negative: like keep_context for the negative K/V -- `negative_context` only says how long it is.  A step without an
         active on == 2 slot runs what it ran before there was a negative context (pmhip_pipeline_step_slots_negative).
+        top_p (None: the routing and the limits above): one nucleus mass per slot for THIS step (a sequence of B values, finite and
+        in (0, 1], None = 1), which routes the step to pmhip_pipeline_step_slots_filter -- also when every value is 1: an active
+        slot may then carry topk in 1..n_embed, and a step whose active slots all have topk <= 8 and top_p == 1 runs the launches
+        and the graph of the entries above.
         -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
@@ -432,8 +443,18 @@ class S2Engine:
         # step without them) -- unless this step has something only the entry with a negative context reads: that context, kept or
         # given, or a guide record whose `on` names a kind beyond 1 (which that entry validates)
         kinds = guides is not None and any(g.on > _lib.GUIDE_UNCOND for g in guides)
+        if top_p is not None:
+            if len(top_p) != B:
+                raise ValueError(f"step_slots: {len(top_p)} nucleus masses for a batch of {B}")
+            # checked like ops.sample_rows checks its top_p; an idle slot's value is not looked at (it travels as 1)
+            top_p = (C.c_float * B)(*[1.0 if slots[b].step & _lib.SLOT_IDLE else ops.nucleus_p(v, f"step_slots: slot {b}: top_p")
+                                      for b, v in enumerate(top_p)])
         with torch.cuda.device(self.device):
-            if neg is None and not keep_negative and not kinds:
+            if top_p is not None:
+                check(self.lib.pmhip_pipeline_step_slots_filter(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
+                                                                Ln, neg_lens, top_p, flags, _p(pred), _p(score), stream_ptr(self.device)),
+                      "pmhip_pipeline_step_slots_filter")
+            elif neg is None and not keep_negative and not kinds:
                 check(self.lib.pmhip_pipeline_step_slots_choice(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, flags,
                                                                 _p(pred), _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_choice")
             else:

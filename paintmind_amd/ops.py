@@ -672,11 +672,14 @@ def _check_slots(slots, B, dev):
         raise ValueError(f"slots must be a contiguous uint8 [{B}, {C.sizeof(_lib.Slot)}] tensor (pack_slots) on the operands' device")
 
 
-def sample_rows_slots(logits, ids, mask_id, slots, tokens, block_stats=None):
+def sample_rows_slots(logits, ids, mask_id, slots, tokens, block_stats=None, top_p=None, filters=False):
     """sample_rows with the scalars of row r taken from slots[r // tokens] (pack_slots): logits fp32 [B*tokens, V], ids int64
     [B*tokens] -> (pred, merged ids, score).  Image b equals sample_rows on its rows alone with its slot's values and
-    row_base = image_index * tokens, bit for bit; an idle slot keeps its ids (pred = ids, score = -1e5).  V % 64 == 0, topk <= 8."""
-    dev = _dev(logits, ids, slots, block_stats)
+    row_base = image_index * tokens, bit for bit; an idle slot keeps its ids (pred = ids, score = -1e5).  V % 64 == 0, topk <= 8.
+    filters=True (pmhip_sample_rows_slots_filter): a slot's topk may be anywhere in 1..V and `top_p`, fp32 [B]
+    on the device (None: every slot 1), gives every slot its nucleus mass -- image b then equals sample_rows(..., topk, top_p=) on
+    its rows, on the kernel that call picks (block_stats are read for the slots at topk <= 8 without a nucleus only)."""
+    dev = _dev(logits, ids, slots, block_stats, top_p)
     lib = _lib.load()
     M, V = logits.shape
     if tokens <= 0 or M % tokens:
@@ -684,12 +687,22 @@ def sample_rows_slots(logits, ids, mask_id, slots, tokens, block_stats=None):
     _check_slots(slots, M // tokens, dev)
     if block_stats is not None and (block_stats.dtype != torch.float32 or tuple(block_stats.shape) != (M, V // 64, 2) or V % 64):
         raise ValueError("sample_rows_slots: block_stats must be a contiguous fp32 [M, V/64, 2] tensor on the logits' device")
+    if top_p is not None:
+        if not filters:
+            raise ValueError("sample_rows_slots: top_p needs filters=True (the entry without filters has no nucleus)")
+        if top_p.dtype != torch.float32 or tuple(top_p.shape) != (M // tokens,) or not top_p.is_contiguous():
+            raise ValueError(f"sample_rows_slots: top_p must be a contiguous fp32 [{M // tokens}] tensor on the operands' device")
     pred = torch.empty(M, device=dev, dtype=torch.int64)
     ids_out = torch.empty(M, device=dev, dtype=torch.int64)
     score = torch.empty(M, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        check(lib.pmhip_sample_rows_slots(_p(logits), logits.stride(0), _p(block_stats), _p(ids), int(mask_id), _p(slots), int(tokens),
-                                          _p(pred), _p(ids_out), _p(score), M, V, stream_ptr(dev)), "pmhip_sample_rows_slots")
+        if filters:
+            check(lib.pmhip_sample_rows_slots_filter(_p(logits), logits.stride(0), _p(block_stats), _p(ids), int(mask_id), _p(slots), _p(top_p),
+                                                     int(tokens), _p(pred), _p(ids_out), _p(score), M, V, stream_ptr(dev)),
+                  "pmhip_sample_rows_slots_filter")
+        else:
+            check(lib.pmhip_sample_rows_slots(_p(logits), logits.stride(0), _p(block_stats), _p(ids), int(mask_id), _p(slots), int(tokens),
+                                              _p(pred), _p(ids_out), _p(score), M, V, stream_ptr(dev)), "pmhip_sample_rows_slots")
     return pred, ids_out, score
 
 

@@ -23,10 +23,10 @@ different scales, and unguided ones, share a batch and each computes what it wou
 
 Limits: a session is all-conditional or all-unconditional (``context=None`` selects attn2's inputs for the whole batch), every
 context of a session has the same width D, top-k <= 8 (the block-statistics sampling kernel: ``Pipeline.generate`` takes any
-top-k up to n_embed, and ``None`` for no filter, DESIGN.md section 4n, but a session does not -- a batch that mixes requests at
-and above 8 needs a second sampling launch chosen step by step, which is not built), and idle slots still run through
-the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the second tower pass: the
-unconditional pass runs at the session's batch size.
+top-k up to n_embed, and ``None`` for no filter, DESIGN.md section 4n, but this session does not -- a batch that mixes requests at
+and above 8 needs further sampling launches chosen step by step: ``decode_session(filters=True)``, the FilterSession below), and
+idle slots still run through the tower (no compaction).  For the same reason an unguided slot beside a guided one still pays the
+second tower pass: the unconditional pass runs at the session's batch size.
 
 A negative prompt and a guidance schedule are per request as well (``submit(negative_text=..., guidance_scale=[s_0, ..., s_T-1])``,
 what ``Pipeline.generate`` takes for a whole batch).  A request's negative context is ``[Ln_r, D]`` with its own length; the session
@@ -46,9 +46,18 @@ from a device array, and the contract reads ``generate_ids(..., choice_temperatu
 non-zero value passes none, which IS the step without: the same kernels and graph as before.  The guided loop's step-0 cache ("Not built") stays
 not built.
 
+The sampler filters are per request in a FilterSession (``pipe.decode_session(..., filters=True)``):
+``submit(topk=k, top_p=p)`` with k anywhere in 1..n_embed (``None``: no filter) and a nucleus mass p in (0, 1] (``None``: none),
+what ``Pipeline.generate`` takes for a whole batch.  Which sampling kernel serves a row depends on its request's (topk, top_p < 1)
+alone, so the native step (pmhip_pipeline_step_slots_filter) issues one sampling launch per kernel class, each serving the rows of
+its class, and a step in which every occupied slot has top-k <= 8 and no nucleus runs the launches and the graph of the session
+above.  The contract sentence extends unchanged: a request (T, temperature, topk, top_p, seed, k, ...) in slot j of an S-slot
+session produces, bit for bit, the per-step predictions, scores and final ids of row j of ``generate_ids(..., B=S, topk=topk,
+top_p=top_p, ..., image_base=k - j, streams=1)``.
+
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
 ``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed, guidance_scale=s,
-negative_text=n)``.
+negative_text=n)`` -- in a FilterSession with ``topk=, top_p=`` as well.
 """
 import collections
 import math
@@ -65,7 +74,8 @@ class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
     def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None,
-                 ctemps=None, negative=None, scales=None):
+                 ctemps=None, negative=None, scales=None, top_p=1.0):
+        self.top_p = top_p                          # the nucleus mass (1: none; a FilterSession's requests may carry another)
         self.number, self.text, self.context = number, text, context
         self.negative = negative                    # None: no negative prompt; else its context [Ln_r, D]
         self.scales = scales                        # None: one scale (guidance_scale); else the scale of every step
@@ -135,7 +145,22 @@ class DecodeSession:
         `negative_text` / `negative_context` [Ln_r, D] (needs guidance_scale): a negative prompt -- the request samples from
         neg + scale * (cond - neg), like ``Pipeline.generate(negative_text=)``; the text goes through the pipeline's text model like
         `text`, the context has its own length like `context`."""
-        timesteps, topk = int(timesteps), int(topk)
+        return self._submit(text, timesteps, temperature, topk, None, seed, image_index, context, ids0, guidance_scale, choice_temperature,
+                            negative_text, negative_context)
+
+    def _filters(self, topk, top_p):
+        """a request's sampler filters as this session serves them -> (topk, top_p): top-k in 1..8 where the native slots step runs
+        (the block-statistics kernel), no nucleus"""
+        topk = int(topk)
+        if not self._cpu and not 1 <= topk <= 8:
+            raise ValueError(f"a decode session serves topk in 1..8, got {topk}")
+        return topk, 1.0
+
+    def _submit(self, text, timesteps, temperature, topk, top_p, seed, image_index, context, ids0, guidance_scale, choice_temperature,
+                negative_text, negative_context):
+        """submit() behind its keywords; (topk, top_p) go through _filters, the session's own range of them"""
+        topk, top_p = self._filters(topk, top_p)
+        timesteps = int(timesteps)
         if timesteps < 1:
             raise ValueError("timesteps must be >= 1")
         scales = None
@@ -164,8 +189,6 @@ class DecodeSession:
                 raise ValueError(f"a request's negative context is [Ln, D] with Ln >= 1, got {tuple(negative.shape)}")
             if self.max_negative_len is not None and negative.shape[0] > self.max_negative_len:
                 raise ValueError(f"a negative context of {negative.shape[0]} rows does not fit the session's max_negative_len={self.max_negative_len}")
-        if not self._cpu and not 1 <= topk <= 8:
-            raise ValueError(f"a decode session serves topk in 1..8, got {topk}")
         if self.conditional:
             if context is None:
                 if text is None:
@@ -194,7 +217,7 @@ class DecodeSession:
         from .generate import loop_schedule
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.pipe.num_tokens, choice_temperature)
         r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale,
-                    ctemps, negative, scales)
+                    ctemps, negative, scales, top_p)
         self._submitted += 1
         self.queue.append(r)
         return r
@@ -239,6 +262,10 @@ class DecodeSession:
         r.retired = self.tick
         self.occupied[r.slot] = None
 
+    def _step_filters(self):
+        """what this step's native call takes beyond DecodeSession's: nothing"""
+        return {}
+
     def _step_cpu(self, admitted):
         pipe = self.pipe
         for r in admitted:
@@ -252,7 +279,7 @@ class DecodeSession:
             neg = None if r.negative is None else r.negative[None]
             ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t,
                                         r.scales[t] if r.scales else r.guidance_scale, None, r.ctemps[t] if r.ctemps else 0.0,
-                                        negative=neg, negative_lens=None)
+                                        top_p=r.top_p, negative=neg, negative_lens=None)
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
@@ -340,7 +367,7 @@ class DecodeSession:
         def run(keep_context, keep_negative):
             return eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep_context, want_aux=want_aux,
                                   guides=self._guides, context_lens=lens, choice=choice, negative_context=neg, negative_lens=neg_lens,
-                                  keep_negative=keep_negative)
+                                  keep_negative=keep_negative, **self._step_filters())
         try:
             _, pred, score = run(keep, keep_neg)
         except _lib.PmhipError as e:
@@ -365,3 +392,28 @@ class DecodeSession:
             out.append(Finished(r, imgs[i] if self.decode else None, ids[i]))
             self._retire(r)
         return out
+
+
+class FilterSession(DecodeSession):
+    """``pipe.decode_session(..., filters=True)``: a DecodeSession whose requests carry the sampler filters of ``Pipeline.generate``
+    -- top-k anywhere in 1..n_embed (None: no filter) and a nucleus mass top_p -- see the module docstring.  Everything else a
+    request can carry works as in DecodeSession, through the same code."""
+
+    def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
+               guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None, top_p=None):
+        """DecodeSession.submit with `topk` in 1..n_embed, or None for no filter (stored as n_embed), and `top_p` (None or 1 = no
+        nucleus filter; else finite, 0 < top_p < 1): of the request's top-k classes only those whose mass strictly above them is
+        below top_p of the top-k's mass are drawn from, like ``Pipeline.generate(top_p=)``.  Out of range: ValueError, here."""
+        return self._submit(text, timesteps, temperature, topk, top_p, seed, image_index, context, ids0, guidance_scale, choice_temperature,
+                            negative_text, negative_context)
+
+    def _filters(self, topk, top_p):
+        V = self.pipe.mask_token_id                 # n_embed
+        topk = V if topk is None else int(topk)
+        if not 1 <= topk <= V:
+            raise ValueError(f"topk must be in 1..n_embed={V} (or None: no filter), got {topk}")
+        return topk, ops.nucleus_p(top_p)
+
+    def _step_filters(self):
+        # one nucleus mass per slot, also when every one is 1: the step that takes top-k up to n_embed
+        return {"top_p": [1.0 if r is None else r.top_p for r in self.occupied]}
