@@ -37,6 +37,7 @@
  *         pmhip_gemm with an f32 residual      out == residual with ldo == ldr, res_rows covering all M rows
  *         pmhip_unshift_hilo, pmhip_remask(_slots), pmhip_remask_choice(_slots), pmhip_guidance_combine(_stats), pmhip_sample_rows* (ids_out == ids_in)
  *         pmhip_remask_counts, pmhip_remask_choice_counts, pmhip_mask_tokens (ids), pmhip_composite (out == gen or orig)
+ *         pmhip_remask_slots_counts, pmhip_remask_choice_slots_counts
  *         pmhip_guidance_combine_slots(_which) out == cond (or uncond / other)
  *     Every element is read by the workgroup that writes it, before it writes it; the result equals the out-of-place call's bit
  *     for bit.  Any other overlap between an output and an input is undefined.
@@ -418,6 +419,19 @@ int pmhip_remask_counts(int64_t* ids, const float* scores, const int32_t* counts
 int pmhip_remask_choice_counts(int64_t* ids, const float* scores, const int32_t* counts_dev /* [B] */, int64_t mask_id, int B, int N,
                                float choice_t, const float* noise /* [B,N] or NULL */, uint64_t seed, uint32_t step, uint64_t row_base,
                                pmhip_stream stream);
+/* SLOT RECORDS WITH A COUNT PER SLOT (new entries within ABI 11): the per-image forms above with counts_dev,
+ * a DEVICE int32 [B] parallel to the slot records (pmhip_slot stays 32 bytes).  Row b equals, bit for bit,
+ *   counts_dev[b] <  0:  pmhip_remask_slots / pmhip_remask_choice_slots on that row -- the record's num_mask with its clamp to 1;
+ *   counts_dev[b] >  0:  pmhip_remask_counts / pmhip_remask_choice_counts on that row ALONE (B = 1) with num_mask = counts_dev[b],
+ *                        the slot's seed and step, choice_t = choice_t_dev[b] and row_base = image_index * N; above N: the row;
+ *   counts_dev[b] == 0, or the slot is idle:  its input -- the workgroup leaves before it touches the row; the count of an idle
+ *                        slot is not looked at.
+ * In place like pmhip_remask.  Null pointers and bad shapes are PMHIP_EINVAL before anything is launched.  The records and the
+ * counts are device memory and are not validated here. */
+int pmhip_remask_slots_counts(int64_t* ids, const float* scores, const pmhip_slot* slots, const int32_t* counts_dev /* [B] */,
+                              int64_t mask_id, int B, int N, pmhip_stream stream);
+int pmhip_remask_choice_slots_counts(int64_t* ids, const float* scores, const pmhip_slot* slots, const float* choice_t_dev,
+                                     const int32_t* counts_dev /* [B] */, int64_t mask_id, int B, int N, pmhip_stream stream);
 
 /* Pixel-side operators of the edit call.
  * pmhip_mask_tokens: pixel_mask uint8 [B,H,W], ids int64 [B, (H/patch) * (W/patch)] IN PLACE, counts_out int32 [B].  Token (r, c)
@@ -857,6 +871,31 @@ int pmhip_pipeline_step_slots_filter(pmhip_s2* s2, int64_t* ids, const float* co
 /* Steps pmhip_pipeline_step_slots_filter ran on this handle, by the form of the sampling tail: *tiles_only the one
  * block-statistics launch (every active slot at topk <= 8 without a nucleus), *chain the four launches.  Either may be NULL. */
 int pmhip_s2_slots_filter_steps(const pmhip_s2* h, int* tiles_only, int* chain);
+
+/* EDIT REQUESTS IN A SLOTS STEP (new entries within ABI 11): pmhip_pipeline_step_slots_filter with a
+ * re-masking count per slot, counts_host a HOST int32 [B] or NULL.  counts_host[b] == -1: slot b re-masks its record's num_mask,
+ * as through every entry above; 0 <= counts_host[b] <= tokens: it re-masks exactly that many positions, 0 leaving its row as the
+ * sampler merged it (its record's num_mask is then not read and may be anything).  That is what an edit needs: with the counts
+ * of an edit schedule a given id is never re-masked and no mask id is left behind.  Idle slots are not looked at.
+ * Every active slot's entry is validated in -1..tokens before anything is staged or launched (PMHIP_EINVAL, ids untouched; the
+ * message names the slot).
+ * counts_host NULL, or no active slot with an entry >= 0: the call runs exactly pmhip_pipeline_step_slots_filter -- the same
+ * launches, the same graph key, the same captured graph.  Otherwise the counts travel in the pinned-ring entry of the records,
+ * behind the nucleus masses (an idle slot's is 0), into a handle-owned device array, and the re-masking launch is
+ * pmhip_remask_slots_counts or its choice form; the tower passes, the combines and the sampling tail stay as they are.  With
+ * PMHIP_SLOTS_GRAPH this form has one further graph key, and as the counts are read from device memory that one graph serves
+ * every set of counts. */
+int pmhip_pipeline_step_slots_edit(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                   const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
+                                   const pmhip_slot_guide* guides_host, const float* choice_host /* [B] or NULL */,
+                                   const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                   const int32_t* neg_lens_host /* [B] or NULL */, const float* top_p_host /* [B] or NULL */,
+                                   const int32_t* counts_host /* [B] or NULL */, int flags, int64_t* pred_out, float* score_out,
+                                   pmhip_stream stream);
+/* Steps pmhip_pipeline_step_slots_edit ran on this handle with the re-masking form that takes a count per slot (the others ran
+ * the step of the entry above).  The pointer may be NULL.  Every step of this entry is also counted by
+ * pmhip_s2_slots_filter_steps, by the form of its sampling tail. */
+int pmhip_s2_slots_edit_steps(const pmhip_s2* h, int* steps);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

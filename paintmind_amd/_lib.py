@@ -197,6 +197,11 @@ PROTOTYPES = {
     "pmhip_pipeline_step_slots_filter": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
                                                vp, i32, C.POINTER(i32), C.POINTER(f32), i32, vp, vp, vp]),
     "pmhip_s2_slots_filter_steps": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+    "pmhip_remask_slots_counts": (i32, [vp, vp, vp, vp, i64, i32, i32, vp]),
+    "pmhip_remask_choice_slots_counts": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "pmhip_pipeline_step_slots_edit": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
+                                             vp, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(i32), i32, vp, vp, vp]),
+    "pmhip_s2_slots_edit_steps": (i32, [vp, C.POINTER(i32)]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

@@ -777,6 +777,7 @@ struct pmhip_s2 {
     PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
     int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
     int slots_filter_tiles = 0, slots_filter_chain = 0;   // steps of pmhip_pipeline_step_slots_filter by the form of their sampling tail
+    int slots_edit_steps = 0;                             // steps of pmhip_pipeline_step_slots_edit that re-masked by a count per slot
     int slots_ctx_B = 0, slots_ctx_L = -1;
     int slots_neg_B = 0, slots_neg_Ln = -1;
     // device image d complete -> copy stream (one event per image of a call: an event is never re-recorded while a wait on
@@ -1740,13 +1741,17 @@ extern "C" int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, i
 // slot may carry top-k up to n_embed and a nucleus mass.  The host decides the form of the sampling tail per STEP: the one
 // block-statistics launch of the older entries (their launches, graph key and graph) unless an active slot is of another class
 // (common.h pm_sample_class) -- then the launch per class, with the masses staged behind the choice temperatures.
+// counts_host (pmhip_pipeline_step_slots_edit; NULL from the six older entries): a re-masking count per slot,
+// -1 = the record's num_mask.  A step in which no active slot has a count >= 0 is the step without counts (launches, graph key and
+// graph); otherwise the counts are staged behind the masses and the re-masking launch is the form with a count per slot.
 static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                            const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host, int flags,
                            int64_t* pred_out, float* score_out, pmhip_stream stream, bool kinds = false, const float* neg_context = nullptr,
-                           int Ln = 0, const int32_t* neg_lens_host = nullptr, bool filters = false, const float* top_p_host = nullptr) {
+                           int Ln = 0, const int32_t* neg_lens_host = nullptr, bool filters = false, const float* top_p_host = nullptr,
+                           const int32_t* counts_host = nullptr) {
     const bool keep_neg = kinds && (flags & PMHIP_SLOTS_KEEP_NEGATIVE) != 0;
     const bool neg_set = neg_context || keep_neg;             // this call has a negative set, given or kept
-    const char* who = filters ? "pipeline_step_slots_filter"
+    const char* who = counts_host ? "pipeline_step_slots_edit" : filters ? "pipeline_step_slots_filter"
                               : (neg_set || neg_lens_host) ? "pipeline_step_slots_negative" : choice_host ? "pipeline_step_slots_choice" : narrow;
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0), L, B));
@@ -1760,6 +1765,7 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     bool two_pass = false, choice = false;      // choice: an active slot has a choice temperature other than 0 (else: the step without)
     bool pass_neg = false, pass_uncond = false;               // an active slot guided against the negative set / against no context
     bool chain = false;                                       // filters: an active slot is of another class than the block-statistics kernel's
+    bool edit = false;                                        // counts_host: an active slot brings a count of its own (>= 0)
     for (int b = 0; b < B; ++b) {
         const pmhip_slot& sl = slots_host[b];
         if (sl.step & PM_SLOT_IDLE) continue;
@@ -1775,7 +1781,13 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
         } else {
             PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "%s: slot %d: topk=%d must be in [1, 8]", who, b, sl.topk);
         }
-        PM_REQUIRE(sl.num_mask >= 1, "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
+        if (counts_host) {
+            PM_REQUIRE(counts_host[b] >= -1 && counts_host[b] <= c.tokens, "%s: slot %d: count %d must be in [-1, tokens=%d]", who, b,
+                       (int)counts_host[b], c.tokens);
+            edit = edit || counts_host[b] >= 0;
+        }
+        // (a slot with a count of its own never reads the record's)
+        PM_REQUIRE(sl.num_mask >= 1 || (counts_host && counts_host[b] >= 0), "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
         if (guides_host && guides_host[b].on) {
             PM_REQUIRE(!kinds || guides_host[b].on <= 2, "%s: slot %d: on=%u must be 0, 1 or 2", who, b, guides_host[b].on);
             PM_REQUIRE(std::isfinite(guides_host[b].scale), "%s: slot %d: the guidance scale must be finite", who, b);
@@ -1842,7 +1854,12 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     const size_t top_p_at = choice_at + choice_bytes, top_p_bytes = choice_bytes;
     float* dtop_p = nullptr;
     if (chain) WS(s2->ws, "slots.top_p", top_p_bytes, dtop_p);
-    PM_TRY(s2->slots_ring.reserve(top_p_at + top_p_bytes));
+    // ... and behind those the B re-masking counts of a step in which an active slot brings its own, padded the
+    // same way; an idle slot's is 0
+    const size_t counts_at = top_p_at + top_p_bytes, counts_bytes = choice_bytes;
+    int32_t* dcounts = nullptr;
+    if (edit) WS(s2->ws, "slots.counts", counts_bytes, dcounts);
+    PM_TRY(s2->slots_ring.reserve(counts_at + counts_bytes));
     PM_TRY(s2->slots_ring.acquire());
     PM_TRY(s2->slots_ring.stage(dslots, 0, slots_host, slot_bytes, s));
     if (two_pass) PM_TRY(s2->slots_ring.stage(dguides, slot_bytes, guides_host, guide_bytes, s));
@@ -1856,7 +1873,13 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
         for (int b = 0; b < B; ++b) padded[b] = ((slots_host[b].step & PM_SLOT_IDLE) || !top_p_host) ? 1.f : top_p_host[b];
         PM_TRY(s2->slots_ring.stage(dtop_p, top_p_at, padded.data(), top_p_bytes, s));
     }
+    if (edit) {
+        std::vector<int32_t> padded(counts_bytes / 4, 0);
+        for (int b = 0; b < B; ++b) padded[b] = (slots_host[b].step & PM_SLOT_IDLE) ? 0 : counts_host[b];
+        PM_TRY(s2->slots_ring.stage(dcounts, counts_at, padded.data(), counts_bytes, s));
+    }
     PM_TRY(s2->slots_ring.commit(s));
+    if (edit) ++s2->slots_edit_steps;
     if (filters) ++(chain ? s2->slots_filter_chain : s2->slots_filter_tiles);
     ++(pass_neg && pass_uncond ? s2->slots_three_pass : two_pass ? s2->slots_two_pass : s2->slots_one_pass);
     Step st;
@@ -1867,6 +1890,7 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     st.choice_dev = dchoice;
     st.filters = chain;                                       // every active slot of class T: the step of the entries without filters
     st.top_p_dev = dtop_p;
+    st.counts = dcounts;                                      // NULL: the re-masking launch of the entries without counts
     auto run_step = [&](int64_t* on_ids, int64_t* pred, float* score, hipStream_t on) -> int {
         return sample_step(s2, nullptr, on_ids, B, st, nullptr, pred, score, on);
     };
@@ -1884,7 +1908,7 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     const char* passes = pass_neg ? (pass_uncond ? "slotsthreeB" : "slotsnegB") : two_pass ? "slotsguidedB" : "slotsB";
     const std::string neg_key = pass_neg ? "N" + std::to_string(Ln) + (neg_lens_host ? "n" : "") : "";
     GraphEntry& ge = s2->graphs[passes + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
-                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "")];
+                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "") + (edit ? "E" : "")];
     PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
@@ -1938,7 +1962,23 @@ extern "C" int pmhip_pipeline_step_slots_filter(pmhip_s2* s2, int64_t* ids, cons
                            score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host);
 }
 
-// steps of that entry by the form of their sampling tail
+// every active slot at -1 (or counts_host NULL): exactly pmhip_pipeline_step_slots_filter
+extern "C" int pmhip_pipeline_step_slots_edit(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                              const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
+                                              const float* neg_context, int Ln, const int32_t* neg_lens_host, const float* top_p_host,
+                                              const int32_t* counts_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
+    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
+                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host, counts_host);
+}
+
+// steps of that entry whose re-masking launch was the form with a count per slot
+extern "C" int pmhip_s2_slots_edit_steps(const pmhip_s2* h, int* steps) {
+    PM_REQUIRE(h, "s2_slots_edit_steps: null handle");
+    if (steps) *steps = h->slots_edit_steps;
+    return PMHIP_OK;
+}
+
+// steps of pmhip_pipeline_step_slots_filter (and of the edit entry, which is that entry with counts) by the form of their sampling tail
 extern "C" int pmhip_s2_slots_filter_steps(const pmhip_s2* h, int* tiles_only, int* chain) {
     PM_REQUIRE(h, "s2_slots_filter_steps: null handle");
     if (tiles_only) *tiles_only = h->slots_filter_tiles;

@@ -638,6 +638,56 @@ __global__ __launch_bounds__(THREADS) void remask_choice_counts_kernel(int64_t* 
 #include "remask_select.h"
 }
 
+// SLOTS WITH A COUNT PER SLOT (pmhip_remask_slots_counts): the step values from the record as in the SLOTS
+// forms above, and beside the records a device int32 per slot, c = counts[image]:
+//   c < 0   the record's num_mask with remask_select.h's clamp to 1 -- remask_reg_kernel<E, true> on this row;
+//   c == 0  the workgroup leaves like an idle slot's (before any barrier), its row untouched;
+//   c > 0   exactly c positions (remask_counts_kernel on this row; above N: the row).
+// Kernels of their own, like the counts forms: the instantiations above keep their arguments and their code.
+template <int E>
+__global__ __launch_bounds__(THREADS) void remask_slots_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
+                                                                      const pmhip_slot* __restrict__ slots,
+                                                                      const int32_t* __restrict__ counts, int64_t mask_id, int N) {
+    constexpr int NP = THREADS * E;
+    __shared__ unsigned long long xs[NP];
+    int num_mask = 0;
+    if (!image_num_mask<true>(num_mask, blockIdx.x, nullptr, 0, slots)) return;
+    const int c = counts[blockIdx.x];
+    if (c == 0) return;
+    if (c > 0) num_mask = c;
+    const int tid = threadIdx.x, base = tid * E;
+    const float* sc = scores + (size_t)blockIdx.x * N;
+    unsigned long long key[E], mine[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        const int i = base + e;
+        key[e] = i < N ? remask_key(sc[i], i) : 0ull;
+        mine[e] = key[e];
+    }
+#include "remask_select.h"
+}
+
+// its choice form (pmhip_remask_choice_slots_counts): t from choice[image], seed, step and image_index * N from the record
+// (image_choice<true>), Philox noise only; the count as above
+template <int E>
+__global__ __launch_bounds__(THREADS) void remask_choice_slots_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
+                                                                             const pmhip_slot* __restrict__ slots,
+                                                                             const float* __restrict__ choice,
+                                                                             const int32_t* __restrict__ counts, int64_t mask_id, int N) {
+    constexpr int NP = THREADS * E;
+    __shared__ unsigned long long xs[NP];
+    ImageChoice ic{0, 0.f, 0ull, 0u, 0ull};
+    if (!image_choice<true>(ic, blockIdx.x, N, nullptr, slots, choice)) return;
+    const int c = counts[blockIdx.x];
+    if (c == 0) return;
+    const int num_mask = c > 0 ? c : ic.num_mask;
+    const float* noise = nullptr;
+    const int tid = threadIdx.x, base = tid * E;
+    const float* sc = scores + (size_t)blockIdx.x * N;
+#include "remask_choice_keys.h"
+#include "remask_select.h"
+}
+
 // a run-time size class or flag as a compile-time constant: f(std::integral_constant<int, V>) for the one V of Vs that equals v
 template <int... Vs, typename F>
 void pick(int v, F&& f) {
@@ -787,16 +837,24 @@ int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, 
     const bool slots = src.kind == PmStepSource::SLOTS;
     const bool counts = src.counts != nullptr;             // the count of image b from counts[b]; everything else from the source's kind
     const bool choice = src.choice_on();
-    const char* who = counts ? (choice ? "remask_choice_counts" : "remask_counts")
-                             : slots ? (choice ? "remask_choice_slots" : "remask_slots") : (choice ? "remask_choice" : "remask");
+    const char* who = slots && counts ? (choice ? "remask_choice_slots_counts" : "remask_slots_counts")
+                      : counts        ? (choice ? "remask_choice_counts" : "remask_counts")
+                      : slots         ? (choice ? "remask_choice_slots" : "remask_slots") : (choice ? "remask_choice" : "remask");
     PM_REQUIRE(ids && scores && (!slots || src.slots) && (src.kind != PmStepSource::PARAMS || src.gp), "%s: null pointer", who);
-    PM_REQUIRE(!(slots && counts), "%s: a count table beside slot records", who);
     PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "%s: bad shape B=%d N=%d (N <= 4096)", who, B, N);
     int per_thread = 1;                                    // E: the power of two with THREADS * E >= N
     while (THREADS * per_thread < N) per_thread <<= 1;
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_SAMPLE, s);
     pick<1, 2, 4, 8, 16>(per_thread, [&](auto E) {
+        if (slots && counts) {                             // a count per slot beside the records
+            if (choice)
+                hipLaunchKernelGGL((remask_choice_slots_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.slots, src.choice_dev,
+                                   src.counts, mask_id, N);
+            else
+                hipLaunchKernelGGL((remask_slots_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.slots, src.counts, mask_id, N);
+            return;
+        }
         if (counts) {
             if (choice)
                 hipLaunchKernelGGL((remask_choice_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.counts, mask_id, N, src.gp,
@@ -840,6 +898,20 @@ extern "C" int pmhip_remask_choice_slots(int64_t* ids, const float* scores, cons
                                          int64_t mask_id, int B, int N, pmhip_stream stream) {
     PM_REQUIRE(choice_t_dev, "remask_choice_slots: null pointer");
     return pm_remask(ids, scores, mask_id, B, N, PmStepSource::per_image(slots, N).with_choice_dev(choice_t_dev), stream);
+}
+
+// the slot forms with a count per slot: counts_dev[b] < 0 the record's num_mask (the entries above on that
+// row), 0 the row untouched, > 0 exactly that many (the counts entries below on that row, with the slot's seed, step and image index)
+extern "C" int pmhip_remask_slots_counts(int64_t* ids, const float* scores, const pmhip_slot* slots, const int32_t* counts_dev,
+                                         int64_t mask_id, int B, int N, pmhip_stream stream) {
+    PM_REQUIRE(slots && counts_dev, "remask_slots_counts: null pointer");
+    return pm_remask(ids, scores, mask_id, B, N, PmStepSource::per_image(slots, N).with_counts(counts_dev), stream);
+}
+
+extern "C" int pmhip_remask_choice_slots_counts(int64_t* ids, const float* scores, const pmhip_slot* slots, const float* choice_t_dev,
+                                                const int32_t* counts_dev, int64_t mask_id, int B, int N, pmhip_stream stream) {
+    PM_REQUIRE(slots && choice_t_dev && counts_dev, "remask_choice_slots_counts: null pointer");
+    return pm_remask(ids, scores, mask_id, B, N, PmStepSource::per_image(slots, N).with_choice_dev(choice_t_dev).with_counts(counts_dev), stream);
 }
 
 // the counts forms: image b re-masks counts_dev[b] positions, 0 leaving its row untouched; row b is

@@ -387,8 +387,14 @@ class S2Engine:
         check(self.lib.pmhip_s2_slots_filter_steps(self.handle, C.byref(tiles), C.byref(chain)), "pmhip_s2_slots_filter_steps")
         return tiles.value, chain.value
 
+    def slots_edit_steps(self):
+        """the steps pmhip_pipeline_step_slots_edit ran on this handle with the re-masking form that takes a count per slot"""
+        steps = C.c_int(0)
+        check(self.lib.pmhip_s2_slots_edit_steps(self.handle, C.byref(steps)), "pmhip_s2_slots_edit_steps")
+        return steps.value
+
     def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None,
-                   choice=None, negative_context=None, negative_lens=None, keep_negative=False, top_p=None):
+                   choice=None, negative_context=None, negative_lens=None, keep_negative=False, top_p=None, counts=None):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
@@ -406,6 +412,10 @@ class S2Engine:
         in (0, 1], None = 1), which routes the step to pmhip_pipeline_step_slots_filter -- also when every value is 1: an active
         slot may then carry topk in 1..n_embed, and a step whose active slots all have topk <= 8 and top_p == 1 runs the launches
         and the graph of the entries above.
+        counts (None: the steps above): one re-masking count per slot for THIS step (a sequence of B integers in -1..tokens), which
+        routes the step to pmhip_pipeline_step_slots_edit with the limits of the `top_p` route: -1 = the record's num_mask, c >= 0 =
+        exactly c positions, 0 leaving the row as the sampler merged it (an edit request: DESIGN.md section 4t).  A step in which
+        every active slot is at -1 runs the launches and the graph of the `top_p` route.
         -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
@@ -449,8 +459,20 @@ class S2Engine:
             # checked like ops.sample_rows checks its top_p; an idle slot's value is not looked at (it travels as 1)
             top_p = (C.c_float * B)(*[1.0 if slots[b].step & _lib.SLOT_IDLE else ops.nucleus_p(v, f"step_slots: slot {b}: top_p")
                                       for b, v in enumerate(top_p)])
+        if counts is not None:
+            if len(counts) != B:
+                raise ValueError(f"step_slots: {len(counts)} re-masking counts for a batch of {B}")
+            vals = [0 if slots[b].step & _lib.SLOT_IDLE else int(v) for b, v in enumerate(counts)]
+            for b, v in enumerate(vals):
+                if not -1 <= v <= self.tokens:
+                    raise ValueError(f"step_slots: slot {b}: count {v} must be in -1..{self.tokens}")
+            counts = (C.c_int * B)(*vals)
         with torch.cuda.device(self.device):
-            if top_p is not None:
+            if counts is not None:
+                check(self.lib.pmhip_pipeline_step_slots_edit(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
+                                                              Ln, neg_lens, top_p, counts, flags, _p(pred), _p(score), stream_ptr(self.device)),
+                      "pmhip_pipeline_step_slots_edit")
+            elif top_p is not None:
                 check(self.lib.pmhip_pipeline_step_slots_filter(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
                                                                 Ln, neg_lens, top_p, flags, _p(pred), _p(score), stream_ptr(self.device)),
                       "pmhip_pipeline_step_slots_filter")

@@ -725,6 +725,29 @@ def remask_slots(ids, scores, slots, mask_id, choice=None):
     return ids
 
 
+def remask_slots_counts(ids, scores, slots, counts, mask_id, choice=None):
+    """remask_slots with a count PER SLOT, in place on ids int64 [B,N]: counts int32 [B] on the device.  counts[b] < 0: slot b's
+    num_mask, as remask_slots does it; 0: the row untouched; > 0: exactly that many positions, as remask_counts does it on that row
+    alone with the slot's seed, step and row_base = image_index * N; the row of an idle slot is left untouched whatever its count.
+    choice: as in ``remask_slots`` (pmhip_remask_slots_counts / pmhip_remask_choice_slots_counts)."""
+    dev = _dev(ids, scores, slots, counts, choice)
+    lib = _lib.load()
+    B, N = ids.shape
+    _check_slots(slots, B, dev)
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (B,) or not counts.is_contiguous():
+        raise ValueError(f"remask_slots_counts: counts must be a contiguous int32 [{B}] tensor on the operands' device")
+    with torch.cuda.device(dev):
+        if choice is None:
+            check(lib.pmhip_remask_slots_counts(_p(ids), _p(scores), _p(slots), _p(counts), int(mask_id), B, N, stream_ptr(dev)),
+                  "pmhip_remask_slots_counts")
+        else:
+            if choice.dtype != torch.float32 or tuple(choice.shape) != (B,):
+                raise ValueError(f"remask_slots_counts: choice must be a contiguous fp32 [{B}] tensor on the operands' device")
+            check(lib.pmhip_remask_choice_slots_counts(_p(ids), _p(scores), _p(slots), _p(choice), _p(counts), int(mask_id), B, N,
+                                                       stream_ptr(dev)), "pmhip_remask_choice_slots_counts")
+    return ids
+
+
 def pack_slot_guides(scales, device=None, kinds=None):
     """[guidance scale or None (not guided), ...] -> the pmhip_slot_guide array as a uint8 tensor [B, 8] (on `device` when given):
     what guidance_combine_slots reads, one record beside every pack_slots record.  kinds (None: 1 for every guided image): the

@@ -55,9 +55,23 @@ above.  The contract sentence extends unchanged: a request (T, temperature, topk
 session produces, bit for bit, the per-step predictions, scores and final ids of row j of ``generate_ids(..., B=S, topk=topk,
 top_p=top_p, ..., image_base=k - j, streams=1)``.
 
+Edit requests: ``submit(ids0=x, keep_given=True)`` regenerates the m positions of x that hold the mask id
+and KEEPS the rest -- ``Pipeline.edit`` for one request -- and ``submit(image=[C,H,W], mask=[H,W] | token_mask=[g,g],
+preserve="tokens" | "pixels")`` builds x from an image at submit (``to_latent`` at B = 1 and the mask operator of ``Pipeline.edit``).
+The request's re-masking counts are ``edit_schedule(m, T)`` instead of ``loop_schedule``'s, m counted once at submit, so a given id
+is never re-masked and no mask id is left at the end; its temperatures and choice temperatures are unchanged.  The native step
+(pmhip_pipeline_step_slots_edit) takes one count per slot beside the records -- the request's own for an edit, -1 (the record's)
+for a generation, 0 leaving the row as the sampler merged it -- and ``Finished.image`` of an edit is decoded from its merged ids,
+in the one decode call of the step (``preserve="pixels"`` then composites the original pixels back outside the pixel mask).  The
+contract reads: an edit request in slot j produces, bit for bit, the per-step predictions and scores and the final ids of row j of
+``Pipeline.edit_ids(ids with x in row j, counts with m in row j, ..., B=S, image_base=k - j, use_graph=False)``, whatever shares the
+batch with it; every other keyword of a request composes unchanged, and a step in which no occupied slot is an edit request passes
+no counts, which IS the step without: the same kernels and graph as before.
+
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
 ``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed, guidance_scale=s,
-negative_text=n)`` -- in a FilterSession with ``topk=, top_p=`` as well.
+negative_text=n)`` -- in a FilterSession with ``topk=, top_p=`` as well -- and an edit request equals ``pipe.edit(img[None], ...,
+seed=seed)``.
 """
 import collections
 import math
@@ -74,7 +88,9 @@ class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
     def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None,
-                 ctemps=None, negative=None, scales=None, top_p=1.0):
+                 ctemps=None, negative=None, scales=None, top_p=1.0, edit=False, orig=None, pixel_mask=None):
+        self.edit = edit                            # an edit request: nmask is edit_schedule's over its masked start ids, given ids stay
+        self.orig, self.pixel_mask = orig, pixel_mask   # preserve="pixels": the image [C,H,W] and the pixel mask uint8 [H,W] to composite by
         self.top_p = top_p                          # the nucleus mass (1: none; a FilterSession's requests may carry another)
         self.number, self.text, self.context = number, text, context
         self.negative = negative                    # None: no negative prompt; else its context [Ln_r, D]
@@ -134,7 +150,8 @@ class DecodeSession:
 
     # -- requests -----------------------------------------------------------------------------------
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
-               guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None):
+               guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None, keep_given=False, image=None,
+               mask=None, token_mask=None, preserve="tokens"):
         """queue one request (any time, also between steps) -> its Request.  `context` [L_r, D] may be given instead of `text`
         (a conditional session runs the pipeline's text model on `text` otherwise), with its OWN length L_r: the request attends
         to exactly these rows; `ids0` [N]: start ids instead of all-mask;
@@ -144,9 +161,15 @@ class DecodeSession:
         `guidance_scale` may also be a sequence of `timesteps` finite numbers, one per step of THIS request (a guidance schedule).
         `negative_text` / `negative_context` [Ln_r, D] (needs guidance_scale): a negative prompt -- the request samples from
         neg + scale * (cond - neg), like ``Pipeline.generate(negative_text=)``; the text goes through the pipeline's text model like
-        `text`, the context has its own length like `context`."""
+        `text`, the context has its own length like `context`.
+        `keep_given` (with `ids0`): an EDIT request over the m positions of `ids0` that hold the mask id -- its re-masking counts are
+        ``edit_schedule(m, timesteps)``, so a given id is never re-masked, no mask id is left at the end, and the image is decoded
+        from the merged ids (``Pipeline.edit`` for one request).
+        `image` [C,H,W] with exactly one of `mask` [H,W] (pixels, non-zero = regenerate) / `token_mask` bool [g,g]: the same edit
+        from an image -- it is encoded and masked here, at submit -- and `preserve` ("tokens" | "pixels"): "pixels" puts the original
+        pixels back outside the pixel mask, as in ``Pipeline.edit``."""
         return self._submit(text, timesteps, temperature, topk, None, seed, image_index, context, ids0, guidance_scale, choice_temperature,
-                            negative_text, negative_context)
+                            negative_text, negative_context, keep_given, image, mask, token_mask, preserve)
 
     def _filters(self, topk, top_p):
         """a request's sampler filters as this session serves them -> (topk, top_p): top-k in 1..8 where the native slots step runs
@@ -156,10 +179,46 @@ class DecodeSession:
             raise ValueError(f"a decode session serves topk in 1..8, got {topk}")
         return topk, 1.0
 
+    def _edit_start(self, ids0, keep_given, image, mask, token_mask, preserve):
+        """the edit keywords of submit(), checked -> (ids0, edit, orig, pixel mask): an image is encoded (B = 1) and masked here, by
+        the operators and the checks of ``Pipeline.edit``; orig / pixel mask only where preserve asks for the pixels"""
+        pipe = self.pipe
+        if preserve not in ("tokens", "pixels"):
+            raise ValueError(f"preserve must be 'tokens' or 'pixels', got {preserve!r}")
+        if image is None:
+            if mask is not None or token_mask is not None:
+                raise ValueError("a mask needs the image it is about (image=)")
+            if preserve == "pixels":
+                raise ValueError("preserve='pixels' needs the image whose pixels are kept (image=)")
+            if keep_given and ids0 is None:
+                raise ValueError("keep_given needs the start ids whose given positions are kept (ids0=)")
+            return ids0, bool(keep_given), None, None
+        if ids0 is not None:
+            raise ValueError("give the start of an edit as image= (with a mask) or as ids0=, not both")
+        if image.dim() != 3:
+            raise ValueError(f"a request's image is [C, H, W], got {tuple(image.shape)}")
+        device = "cpu" if self._cpu else pipe.engine().device
+        img = image[None].to(device)
+        tm, pm = pipe._edit_masks(img, mask, token_mask)
+        with torch.no_grad():
+            ids = pipe.to_latent(img)[1].reshape(1, pipe.num_tokens)
+        if tm is None and not self._cpu:
+            ids = ids.to(device, torch.long).clone(memory_format=torch.contiguous_format)
+            ids, _ = ops.mask_tokens(pm, pipe.patch_size, ids, pipe.mask_token_id)
+        else:
+            if tm is None:
+                p = pipe.patch_size
+                tm = pm.reshape(1, pm.shape[1] // p, p, pm.shape[2] // p, p).amax(dim=(2, 4)) != 0
+            ids = torch.where(tm.reshape(1, -1).to(ids.device), torch.full_like(ids, pipe.mask_token_id), ids)
+        if preserve == "pixels":
+            return ids[0], True, img[0], pm[0]
+        return ids[0], True, None, None
+
     def _submit(self, text, timesteps, temperature, topk, top_p, seed, image_index, context, ids0, guidance_scale, choice_temperature,
-                negative_text, negative_context):
+                negative_text, negative_context, keep_given=False, image=None, mask=None, token_mask=None, preserve="tokens"):
         """submit() behind its keywords; (topk, top_p) go through _filters, the session's own range of them"""
         topk, top_p = self._filters(topk, top_p)
+        ids0, edit, orig, pixel_mask = self._edit_start(ids0, keep_given, image, mask, token_mask, preserve)
         timesteps = int(timesteps)
         if timesteps < 1:
             raise ValueError("timesteps must be >= 1")
@@ -214,10 +273,12 @@ class DecodeSession:
             self._next_index += 1
         if ids0 is not None:
             ids0 = self.pipe._start_ids(1, ids0.reshape(1, -1), ids0.device)
-        from .generate import loop_schedule
+        from .generate import edit_schedule, loop_schedule
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.pipe.num_tokens, choice_temperature)
+        if edit:                                    # m is counted once, here: the schedule over the region instead of the image
+            nmask = edit_schedule(int((ids0 == self.pipe.mask_token_id).sum()), timesteps)
         r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale,
-                    ctemps, negative, scales, top_p)
+                    ctemps, negative, scales, top_p, edit, orig, pixel_mask)
         self._submitted += 1
         self.queue.append(r)
         return r
@@ -277,12 +338,17 @@ class DecodeSession:
             t = r.done
             ctx = None if r.context is None else r.context[None]
             neg = None if r.negative is None else r.negative[None]
-            ids, img = pipe._sample_cpu(self._rows[j], r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t,
+            # an edit request: the step with a count per image, as Pipeline.edit's CPU branch takes it
+            ids, img = pipe._sample_cpu(self._rows[j], 0 if r.edit else r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t,
                                         r.scales[t] if r.scales else r.guidance_scale, None, r.ctemps[t] if r.ctemps else 0.0,
-                                        top_p=r.top_p, negative=neg, negative_lens=None)
+                                        top_p=r.top_p, negative=neg, negative_lens=None, **({"counts": [r.nmask[t]]} if r.edit else {}))
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
+                if r.edit and self.decode:          # from the merged ids; the original pixels back outside the mask
+                    img = pipe.vqgan.decode_from_indice(ids)
+                    if r.orig is not None:
+                        img = torch.where(r.pixel_mask[None, None] != 0, img, r.orig[None].to(img.dtype))
                 out.append(Finished(r, img[0] if self.decode else None, ids[0].clone()))
                 self._rows[j] = None
                 self._retire(r)
@@ -345,10 +411,15 @@ class DecodeSession:
                 continue
             t = r.done
             rec.seed, rec.image_index = r.seed & (2 ** 64 - 1), r.image_index & (2 ** 64 - 1)
-            rec.temperature, rec.topk, rec.num_mask, rec.step = r.temps[t], r.topk, r.nmask[t], t
+            rec.temperature, rec.topk, rec.num_mask, rec.step = r.temps[t], r.topk, max(r.nmask[t], 1), t
             if t + 1 == r.timesteps:
                 retiring.append(r)
-        want_aux = (bool(retiring) and self.decode) or self.record_steps
+        # this step's re-masking count of every slot: an edit request's own, -1 (the record's) otherwise; None when no occupied slot
+        # is an edit request: the step without
+        counts = None
+        if any(r is not None and r.edit for r in self.occupied):
+            counts = [r.nmask[r.done] if r is not None and r.edit else -1 for r in self.occupied]
+        want_aux = (any(not r.edit for r in retiring) and self.decode) or self.record_steps
         ctx = self._ctx if self.conditional else None
         keep = not self._ctx_dirty
         # one length per slot -- unless every occupied slot fills the capacity, which IS the step without lengths
@@ -367,7 +438,7 @@ class DecodeSession:
         def run(keep_context, keep_negative):
             return eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep_context, want_aux=want_aux,
                                   guides=self._guides, context_lens=lens, choice=choice, negative_context=neg, negative_lens=neg_lens,
-                                  keep_negative=keep_negative, **self._step_filters())
+                                  keep_negative=keep_negative, counts=counts, **self._step_filters())
         try:
             _, pred, score = run(keep, keep_neg)
         except _lib.PmhipError as e:
@@ -383,13 +454,24 @@ class DecodeSession:
                     r.trace.append((pred[r.slot].clone(), score[r.slot].clone()))
         if not retiring:
             return []
-        # ONE decode call for the rows that finished: the image comes from the predictions at ALL positions of the last step
+        # ONE decode call for the rows that finished: the image comes from the predictions at ALL positions of the last step -- for
+        # an edit request from its merged ids (its last count is 0: no mask id is left in them)
         rows = torch.tensor([r.slot for r in retiring], device=eng.device)
-        imgs = pipe.vqgan.engine().decode_indices(pred.index_select(0, rows)) if self.decode else None
         ids = self._ids.index_select(0, rows)
+        imgs = None
+        if self.decode:
+            edits = [r.edit for r in retiring]
+            src = ids if all(edits) else pred.index_select(0, rows)
+            if any(edits) and not all(edits):
+                src = torch.where(torch.tensor(edits, device=eng.device)[:, None], ids, src)
+            imgs = pipe.vqgan.engine().decode_indices(src)
         out = []
         for i, r in enumerate(retiring):
-            out.append(Finished(r, imgs[i] if self.decode else None, ids[i]))
+            img = imgs[i] if self.decode else None
+            if img is not None and r.orig is not None:
+                img = ops.composite(img[None].contiguous(), r.orig[None].to(eng.device, torch.float32).contiguous(),
+                                    r.pixel_mask[None].to(eng.device).contiguous())[0]
+            out.append(Finished(r, img, ids[i]))
             self._retire(r)
         return out
 
@@ -400,12 +482,13 @@ class FilterSession(DecodeSession):
     request can carry works as in DecodeSession, through the same code."""
 
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
-               guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None, top_p=None):
+               guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None, top_p=None, keep_given=False,
+               image=None, mask=None, token_mask=None, preserve="tokens"):
         """DecodeSession.submit with `topk` in 1..n_embed, or None for no filter (stored as n_embed), and `top_p` (None or 1 = no
         nucleus filter; else finite, 0 < top_p < 1): of the request's top-k classes only those whose mass strictly above them is
         below top_p of the top-k's mass are drawn from, like ``Pipeline.generate(top_p=)``.  Out of range: ValueError, here."""
         return self._submit(text, timesteps, temperature, topk, top_p, seed, image_index, context, ids0, guidance_scale, choice_temperature,
-                            negative_text, negative_context)
+                            negative_text, negative_context, keep_given, image, mask, token_mask, preserve)
 
     def _filters(self, topk, top_p):
         V = self.pipe.mask_token_id                 # n_embed
