@@ -223,6 +223,28 @@ int pmhip_attention_lens(int dtype, const void* Q, const void* K, const void* Vt
                          int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens,
                          pmhip_stream stream);
 
+/* pmhip_attention_dh with a key SET per QUERY (regional prompts; new entry within ABI 11, nothing existing changes meaning):
+ *   key_seg    DEVICE uint8  [B, Nkv]: the segment 0..31 of image b's key k, or 255 = padding
+ *   query_mask DEVICE uint32 [B, Nq] : bit s set = query q of image b attends to segment s
+ * Key k takes part in query q's softmax iff key_seg[b,k] < 32 && (query_mask[b,q] >> key_seg[b,k]) & 1; every other key has weight
+ * exactly 0 for that query.  Bases, strides, Nkv and Nkv_pad are those of pmhip_attention_dh; keys [Nkv, Nkv_pad) are padding.
+ * Contract:
+ *   - every query allows at least one key.  The model-level entries validate that where they own the arrays; this operator cannot
+ *     validate device memory: a query with no allowed key yields a finite, unspecified row (zeros today), never a fault and never
+ *     a read outside Nkv_pad or outside the two arrays
+ *   - K rows and V^T columns with key_seg == 255 never reach a result, NaN included (their V^T columns are zeroed on chip; a
+ *     probability of 0 alone would not do, 0 * NaN is NaN)
+ *   - K rows and V^T columns with a segment 0..31 must be finite: a key allowed to some queries and denied to others contributes
+ *     0 times a finite value where it is denied; a denied key never raises a query's running maximum, whatever its score
+ *   - image b's rows do not depend on what else is in the batch
+ *   - the padding value subsumes the per-image length: there is no kv_lens beside it
+ * Any dim_head the _dh entry serves.  dim_head 64 runs the tuned kernels with the running maximum raised at every 32-key half-tile
+ * (no lagged-max fast path, so pmhip_attention_fallbacks never counts these launches); the bf16 kernel runs 128 or 64 queries per
+ * workgroup, chosen from B, heads and Nq only.  key_seg or query_mask NULL is PMHIP_EINVAL. */
+int pmhip_attention_segments(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                             int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
+                             const uint32_t* query_mask, pmhip_stream stream);
+
 /* torch.nn.LayerNorm over the last dim, eps inside the sqrt (stage1/layers.py:49,51,89,128;
  * stage2/transformer.py:37,39,41,62).  x fp32 [M,D] -> out (`out_dtype`). */
 int pmhip_layernorm(const float* x, const float* gamma, const float* beta, float eps, void* out,
@@ -914,6 +936,45 @@ int pmhip_s2_slots_steps(const pmhip_s2* h, int* one_pass, int* two_pass);
 /* The same with the steps of THREE passes (slots guided against no context and against a negative context in one step,
  * pmhip_pipeline_step_slots_negative); *two_pass stays the steps of exactly two.  Any pointer may be NULL. */
 int pmhip_s2_slots_passes(const pmhip_s2* h, int* one_pass, int* two_pass, int* three_pass);
+
+/* REGIONAL PROMPTS (new entries within ABI 11, following the *_lens entries: nothing existing changes meaning; DESIGN.md section
+ * 4u).  Different text for different parts of the picture: the context of image b is a concatenation of prompts, every row of it
+ * belongs to a SEGMENT, and every token of the grid attends to a set of segments.
+ *   ctx_seg_host  HOST uint8  [B, L]     : the segment 0..31 of context row k of image b, or 255 = padding
+ *   tok_seg_host  HOST uint32 [B, tokens]: bit s set = the token attends to the rows of segment s
+ * Row k takes part in token t's cross-attention iff ctx_seg[b,k] < 32 && (tok_seg[b,t] >> ctx_seg[b,k]) & 1; rows marked 255 never
+ * reach a result, NaN included; image b computes what it computes at the same B with any other layout beside it.  Both NULL: the
+ * call IS the entry it extends -- pmhip_s2_forward, pmhip_pipeline_sample_negative, pmhip_pipeline_generate_negative -- same
+ * kernels, same graphs (so every narrower entry is reachable through these with neutral values, as the header promises for those).
+ *   - validated before anything is launched, else PMHIP_EINVAL: both arrays or neither; every segment id in 0..31 or 255 (the
+ *     message names the image and the row); every token allows at least one segment that is PRESENT in its image (the message
+ *     names the image and the token); segments without a context are refused, and so are segments beside ctx_lens_host -- the
+ *     padding value subsumes the length
+ *   - they travel like the lengths: pinned ring -> copy kernel -> a handle-owned device array, from where the ONE launch that
+ *     changes, the cross-attention of the pass with the context, reads them (pmhip_attention_segments).  Self-attention launches,
+ *     the pass without a context of a guided step and a negative context's pass never see segments
+ *   - captured graphs bake in that array, not its contents: one graph per (B, L) serves every layout of regions, under a key of
+ *     its own beside the unmasked and the per-image graphs
+ * The other arguments are those of the entry each extends. */
+/* The handle's graph cache (new entry within ABI 11): *entries = the keys it holds -- one per (entry family, B, L, kernel forms,
+ * ...) that was asked for with a graph flag --, *captured = how many of them hold captured graphs.  A test asserts with it that a
+ * second layout of regions, lengths or scales replays the graph of the first.  Either pointer may be NULL. */
+int pmhip_s2_graph_count(const pmhip_s2* h, int* entries, int* captured);
+int pmhip_s2_forward_segments(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const uint8_t* ctx_seg_host,
+                              const uint32_t* tok_seg_host, float* logits_out, pmhip_stream stream);
+int pmhip_pipeline_sample_segments(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                   const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                   uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                   float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
+                                   float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                   const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, pmhip_stream stream);
+int pmhip_pipeline_generate_segments(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                     const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                     const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                     float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                     pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
+                                     float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                     const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host);
 
 /* Per-kernel timing hook used by bench.py: when enabled, every kernel launch of the named family
  * is bracketed by hipEvents on its own stream and accumulated (count, total ms). */

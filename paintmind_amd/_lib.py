@@ -182,6 +182,16 @@ PROTOTYPES = {
     "pmhip_pipeline_generate_edit": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
                                            C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
                                            f32, vp, i32, C.POINTER(i32), C.POINTER(f32)]),
+    # regional prompts: the operator with a key set per query, and the model-level entries that take the
+    # segment of every context row (host uint8 [B, L]) and the segments of every token (host uint32 [B, tokens])
+    "pmhip_attention_segments": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "pmhip_s2_graph_count": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),
+    "pmhip_s2_forward_segments": (i32, [vp, vp, vp, i32, i32, C.POINTER(C.c_ubyte), C.POINTER(u32), vp, vp]),
+    "pmhip_pipeline_sample_segments": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, i32, f32,
+                                             f32, vp, f32, vp, i32, C.POINTER(i32), C.POINTER(C.c_ubyte), C.POINTER(u32), vp]),
+    "pmhip_pipeline_generate_segments": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
+                                               C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
+                                               f32, vp, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), C.POINTER(u32)]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),

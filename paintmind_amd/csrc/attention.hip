@@ -86,15 +86,29 @@ __device__ __forceinline__ void zero_ragged_v(unsigned char* Vl, int kv0, int Nk
 #undef PM_ATTN_KERNEL
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_LENS
+// the per-query form: key k takes part in query q's softmax iff key_seg[b,k] < 32 and bit key_seg[b,k] of query_mask[b,q] is set
+#define PM_ATTN_KERNEL attention_seg_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
+#define PM_ATTN_SEG 1
+#include "attention_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
 
 }  // namespace
 
 // fp32, dim_head = 64 leg of the attention entry points (attention_dh.hip): arguments already validated there;
-// lens = device int32 [B], the per-image key counts, or NULL
+// lens = device int32 [B], the per-image key counts, or NULL; seg = the per-query key sets, or NULL (never both)
 void pm_attention_f32(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                      int Nkv_pad, int use_exp2, const int* lens, hipStream_t s) {
+                      int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s) {
     constexpr int QF = 2;
     const int nqb = ceil_div(Nq, 4 * QF * 16);
+    if (seg) {
+        auto k = use_exp2 ? attention_seg_kernel<true, QF> : attention_seg_kernel<false, QF>;
+        hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
+                           Nq, Nkv, Nkv_pad, nqb, seg->key_seg, seg->query_mask);
+        return;
+    }
     auto launch = [&](auto plain, auto per_image) {
         pm_launch_lens(plain, per_image, dim3(nqb * B * heads), dim3(THREADS), s, lens, (const float*)Q, (const float*)K, (const float*)Vt,
                        (float*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb);

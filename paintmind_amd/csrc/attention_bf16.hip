@@ -124,6 +124,14 @@ __device__ __forceinline__ f32x4_t mma(const v4u_t& rows, const v4u_t& cols, con
 #undef PM_ATTN_KERNEL
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_LENS
+// the per-query form: key k takes part in query q's softmax iff key_seg[b,k] < 32 and bit key_seg[b,k] of query_mask[b,q] is set
+#define PM_ATTN_KERNEL attention_bf16_seg_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
+#define PM_ATTN_SEG 1
+#include "attention_bf16_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
 
 #undef DSRX
 #undef LGKM4
@@ -139,6 +147,15 @@ static void launch_qf(const void* Q, const void* K, const void* Vt, void* out, i
     };
     if (use_exp2) launch(attention_bf16_kernel<true, QF>, attention_bf16_lens_kernel<true, QF>);
     else launch(attention_bf16_kernel<false, QF>, attention_bf16_lens_kernel<false, QF>);
+}
+
+template <int QF>
+static void launch_seg_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
+                          int use_exp2, const PmAttnSeg& seg, hipStream_t s) {
+    const int nqb = ceil_div(Nq, 4 * QF * 16);
+    auto k = use_exp2 ? attention_bf16_seg_kernel<true, QF> : attention_bf16_seg_kernel<false, QF>;
+    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
+                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask);
 }
 
 }  // namespace
@@ -160,4 +177,14 @@ void pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, 
     if (force == 4 || (!force && bh * ceil_div(Nq, 256) >= kFill)) launch_qf<4>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
     else if (force == 2 || (!force && bh * ceil_div(Nq, 128) >= kFill)) launch_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
     else launch_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+}
+
+// The per-query form, a launcher of its own so that the one above keeps its signature (tools/hwtests build this file
+// under several names and call it through one function-pointer type).  128 or 64 queries per workgroup only: the 256-query form
+// with the masks does not fit in 256 VGPRs without more scratch than its twins, so it is not built.  Same rule otherwise -- B,
+// heads and Nq decide, never the masks -- and the forms are bit-identical per 16-query tile.
+void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                           int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s) {
+    if ((long long)B * heads * ceil_div(Nq, 128) >= 512) launch_seg_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
+    else launch_seg_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
 }

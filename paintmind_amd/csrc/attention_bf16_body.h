@@ -1,10 +1,15 @@
-// The bf16 attention kernel of attention_bf16.hip, which includes this file TWICE (no include guard on purpose):
+// The bf16 attention kernel of attention_bf16.hip, which includes this file THREE TIMES (no include guard on purpose):
 //   PM_ATTN_KERNEL = attention_bf16_kernel,      PM_ATTN_LENS_PARAM empty          one key count for the launch (Nkv)
 //   PM_ATTN_KERNEL = attention_bf16_lens_kernel, PM_ATTN_LENS_PARAM = ", lens"     PM_ATTN_LENS defined: the key count is per IMAGE --
 //       lens[b] (device int32 [B]), read once per workgroup into a scalar and clamped to [1, Nkv]; Nkv stays the launch-wide
 //       upper bound and Nkv_pad the layout, so every base and row stride is unchanged and every read stays inside Nkv_pad.
 //       Everything below the clamp -- tile counts, the ragged-tile K mask, the V^T zeroing, steady_end / all_steady -- uses the
 //       per-image value, so image b computes what it computes alone with Nkv = lens[b].
+//   PM_ATTN_KERNEL = attention_bf16_seg_kernel,  PM_ATTN_LENS_PARAM = ", key_seg, query_mask"   PM_ATTN_SEG defined: the key SET is per
+//       QUERY.  key_seg[b, k] (device uint8 [B, Nkv]) is the segment 0..31 of a key or 255 for padding,
+//       query_mask[b, q] (device uint32 [B, Nq]) the segments a query attends to.  Every half-tile takes the exact path: the mask
+//       sits where the ragged-tile mask sets scores to -inf, the V^T columns of padding keys are zeroed in every tile, and the
+//       running max of a query that has not met an allowed key yet stays "none" (negm 0, l 0) instead of -inf.
 // A compile-time variant by TEXT, not by a template parameter or an inlined body function: the first form is then the kernel the
 // library had before the second existed, token for token -- same symbol, same instruction stream, same registers (a shared
 // __device__ body, even force-inlined, was measured to move the schedule of every instantiation).
@@ -38,6 +43,18 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
     {                                                        // workgroup-uniform: this image's key count
         const int n = __builtin_amdgcn_readfirstlane(lens[b]);
         Nkv = n < 1 ? 1 : (n > Nkv ? Nkv : n);
+    }
+#endif
+#ifdef PM_ATTN_SEG
+    const unsigned char* segb = key_seg + (size_t)b * Nkv;  // this image's key segments
+    // segment of key `key` of this image; keys at or beyond Nkv are padding
+    auto seg_of = [&](int key) -> unsigned { return key < Nkv ? (unsigned)segb[key] : 255u; };
+    unsigned qmask[QF];                                      // the segments this lane's query of tile qf attends to
+#pragma unroll
+    for (int qf = 0; qf < QF; ++qf) {
+        int q = q0 + qf * 16 + l15;
+        q = q < Nq ? q : Nq - 1;
+        qmask[qf] = query_mask[(size_t)b * Nq + q];
     }
 #endif
 
@@ -135,6 +152,18 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
     auto rescale = [&](auto ragged_c, auto first_c, f32x4_t (&sc)[2][QF], int hh) {
         constexpr bool first = decltype(first_c)::value;
         const int kv0 = (hh >> 1) * KT, pc = hh & 1;
+#ifdef PM_ATTN_SEG
+        // every half-tile: a key takes part in a query's softmax iff its segment is one the query attends to (padding, 255, never)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned sg = seg_of(kv0 + 32 * pc + 8 * g + 4 * kk + r);
+#pragma unroll
+                for (int qf = 0; qf < QF; ++qf)
+                    if (!((sg < 32u) & ((qmask[qf] >> (sg & 31u)) & 1u))) sc[kk][qf][r] = -INFINITY;
+            }
+#else
         if (decltype(ragged_c)::value && kv0 + KT > Nkv) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
@@ -147,15 +176,27 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
                     }
                 }
         }
+#endif
 #pragma unroll
         for (int qf = 0; qf < QF; ++qf) {
             float m = vmax3(sc[0][qf][0], sc[0][qf][1], sc[0][qf][2]);
             m = vmax3(m, sc[0][qf][3], sc[1][qf][0]);
             m = vmax3(m, sc[1][qf][1], sc[1][qf][2]);
             m = vmax2(m, sc[1][qf][3]);                      // this lane's 8 keys, relative to mb
+#ifdef PM_ATTN_SEG
+            // A query that has met no allowed key yet has l = 0 (the key at a running max contributes exactly 1) and keeps negm = 0:
+            // its accumulators start from 0 as in the first half-tile, and there is no old max to rescale from.  While that
+            // lasts nothing is moved: -inf scores stay -inf, and no exp(-inf - (-inf)) is ever formed.
+            const bool none = first || lacc[qf][0] == 0.f;
+            const float mold = none ? -INFINITY : -negm[qf][0];
+            const float mb = none ? 0.f : mold;
+            const float mnew = vmax3(mold, group4_max(m) + mb, -1e30f);
+            if (mnew <= -1e30f) continue;                    // every key of this half-tile denied, and none allowed before it
+#else
             const float mold = first ? -INFINITY : -negm[qf][0];
             const float mb = first ? 0.f : mold;             // what the accumulators started from
             const float mnew = vmax3(mold, group4_max(m) + mb, -1e30f);   // column max over the 4 lane groups
+#endif
             const float delta = mb - mnew;                   // scores hold s - mb: move them to s - mnew
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
@@ -194,6 +235,26 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
             __builtin_amdgcn_s_barrier();
         }
         if (tn + AHEAD < ntiles && !(ABL & 4)) stage_tiles(tn + AHEAD);
+#ifdef PM_ATTN_SEG
+        if (decltype(ragged_c)::value) {                         // every tile: zero the V^T columns of padding keys (255, or >= Nkv)
+            unsigned char* Vl = lds + (tn % RING) * STAGE_BYTES + TILE_BYTES;
+            for (int idx = tid; idx < KT * 8; idx += THREADS) {
+                const int row = idx / 8, ls = idx % 8;
+                uint4* p = reinterpret_cast<uint4*>(Vl + row * 128 + ((ls ^ (row & 7)) << 4));
+                uint4 v = *p;
+                const int k0 = tn * KT + ls * 8;                 // first key of this 8-key chunk
+                unsigned keep[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) keep[e] = seg_of(k0 + e) == 255u ? 0u : 0xffffu;
+                v.x &= keep[0] | (keep[1] << 16);
+                v.y &= keep[2] | (keep[3] << 16);
+                v.z &= keep[4] | (keep[5] << 16);
+                v.w &= keep[6] | (keep[7] << 16);
+                *p = v;
+            }
+            __syncthreads();
+        }
+#else
         if (decltype(ragged_c)::value && tn * KT + KT > Nkv) {   // ragged last tile: zero the V^T columns of keys >= Nkv
             unsigned char* Vl = lds + (tn % RING) * STAGE_BYTES + TILE_BYTES;
             for (int idx = tid; idx < KT * 8; idx += THREADS) {
@@ -209,6 +270,7 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
             }
             __syncthreads();
         }
+#endif
     };
 
     f32x4_t sA[2][QF];                   // S^T of ONE half-tile (single-buffered: group g of a step overwrites the tile it has consumed)
@@ -324,7 +386,11 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
     // produce is consumed.
     const bool all_steady = (Nkv % KT) == 0 && ntiles >= 3;
     const int steady_end = all_steady ? nhalves - 1 : min(nhalves - 3, nh_full - 2);   // one bound: the loop's shape is unchanged
+#ifdef PM_ATTN_SEG
+    bool exact = true;                                       // the lagged-max fast path was built for unmasked tiles
+#else
     bool exact = steady_end <= 0;                            // workgroup-uniform: no fast step at all, or second attempt
+#endif
     unsigned redo_mask = ~0u;                                // tiles the exact attempt stores (all, unless it is a second attempt)
 
     // O = O^T / l, head-major inside the output row, for the 16-query tiles in `mask`.  The wave's output rows go through the
@@ -334,7 +400,11 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
         unsigned char* obuf = lds + wave * (QF * 16 * RS);
 #pragma unroll
         for (int qf = 0; qf < QF; ++qf) {
+#ifdef PM_ATTN_SEG
+            const float inv = lacc[qf][0] > 0.f ? 1.0f / lacc[qf][0] : 0.f;      // (a query with no allowed key: a finite row)
+#else
             const float inv = 1.0f / lacc[qf][0];
+#endif
 #pragma unroll
             for (int df = 0; df < 4; ++df)
                 *reinterpret_cast<uint2*>(obuf + (qf * 16 + l15) * RS + (df * 16 + g * 4) * 2) =
@@ -380,6 +450,7 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
         if (nhalves > 1) k_issue(kf, 1);
 
         int hs = 0;
+#ifndef PM_ATTN_SEG
         if (!exact) {
             v_issue(vf, 0);
             exp_pack1(sA, 0);
@@ -391,6 +462,9 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
             LGKM4(0, vf[0], vf[1], vf[2], vf[3]);
             // hand-over to the exact steps: sA = S^T(hs) with tiles 1..3 untouched (tile 0 is exponentiated again, same bits), K(hs+1) in kf
         }
+#else
+        (void)step; (void)N; (void)steady_end;               // the fast path is not part of this form
+#endif
 #ifdef PM_ATTN_COUNT
         if (lane == 0) { atomicAdd(&g_attn_counters[1], (unsigned long long)hs); atomicAdd(&g_attn_counters[2], (unsigned long long)(nhalves - hs)); }
 #endif

@@ -1,6 +1,9 @@
-// The fp32-verify attention kernel of attention.hip, which includes this file TWICE (no include guard on purpose), exactly as
+// The fp32-verify attention kernel of attention.hip, which includes this file THREE TIMES (no include guard on purpose), exactly as
 // attention_bf16.hip includes attention_bf16_body.h -- see there: PM_ATTN_KERNEL names the kernel, PM_ATTN_LENS_PARAM is empty or
 // ", const int* lens", and with PM_ATTN_LENS the key count is lens[b], read once per workgroup and clamped to [1, Nkv].
+// A THIRD inclusion with PM_ATTN_SEG (attention_seg_kernel; parameters key_seg, query_mask) is the per-query key set of DESIGN.md 4u:
+// scores of denied keys become -inf in every half-tile, the V^T columns of padding keys (segment 255) are zeroed in every tile, the
+// running max is raised at every half-tile (no deferred rescale), and a query that has met no allowed key yet keeps negm = 0.
 template <bool EXP2, int QF>
 __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __restrict__ Q, const float* __restrict__ Kp,
                                                             const float* __restrict__ Vt, float* __restrict__ out,
@@ -34,6 +37,17 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
     {                                                        // workgroup-uniform: this image's key count
         const int n = __builtin_amdgcn_readfirstlane(lens[b]);
         Nkv = n < 1 ? 1 : (n > Nkv ? Nkv : n);
+    }
+#endif
+#ifdef PM_ATTN_SEG
+    const unsigned char* segb = key_seg + (size_t)b * Nkv;  // this image's key segments; keys at or beyond Nkv are padding
+    auto seg_of = [&](int key) -> unsigned { return key < Nkv ? (unsigned)segb[key] : 255u; };
+    unsigned qmask[QF];                                      // the segments this lane's query of tile qf attends to
+#pragma unroll
+    for (int qf = 0; qf < QF; ++qf) {
+        int q = q0 + qf * 16 + l15;
+        q = q < Nq ? q : Nq - 1;
+        qmask[qf] = query_mask[(size_t)b * Nq + q];
     }
 #endif
 
@@ -92,6 +106,17 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
     // (1) row max of half-tile hh and the rare rescale branch
     auto rowmax_rescale = [&](f32x4_t (&sc)[2][QF], int hh) {
         const int t = hh >> 1, pc = hh & 1, kv0 = t * KT;
+#ifdef PM_ATTN_SEG
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const unsigned sg = seg_of(kv0 + 16 * (2 * pc + kk) + 4 * g + r);
+#pragma unroll
+                for (int qf = 0; qf < QF; ++qf)
+                    if (!((sg < 32u) & ((qmask[qf] >> (sg & 31u)) & 1u))) sc[kk][qf][r] = -INFINITY;
+            }
+#else
         if (kv0 + KT > Nkv) {                                // ragged last tile: mask keys beyond Nkv
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk)
@@ -104,9 +129,15 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
                     }
                 }
         }
+#endif
         float tmax[QF];                                      // max of (s - mb), mb = what the accumulators started from
         const bool first = (hh == 0);
+#ifdef PM_ATTN_SEG
+        bool grow = true;                                    // exact at every half-tile: the deferred rescale assumes a max that exists
+        (void)first;
+#else
         bool grow = first;
+#endif
 #pragma unroll
         for (int qf = 0; qf < QF; ++qf) {
             float m = vmax3(sc[0][qf][0], sc[0][qf][1], sc[0][qf][2]);
@@ -119,8 +150,16 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
         if (__any(grow)) {                                   // wave-uniform: rescale everything at the old max exactly once
 #pragma unroll
             for (int qf = 0; qf < QF; ++qf) {
+#ifdef PM_ATTN_SEG
+                // mrun = -inf: no allowed key met yet -- negm is 0 (the accumulators started from 0), l = O = 0.  While that lasts
+                // nothing is moved, so no exp(-inf - (-inf)) is formed and -inf scores stay -inf.
+                const float mb = mrun[qf] == -INFINITY ? 0.f : mrun[qf];
+                const float mnew = vmax2(mrun[qf], group4_max(tmax[qf]) + mb);
+                if (mnew == -INFINITY) continue;
+#else
                 const float mb = first ? 0.f : mrun[qf];
                 const float mnew = vmax3(mrun[qf], group4_max(tmax[qf]) + mb, -1e30f);   // column max over the 4 lane groups
+#endif
                 const float alpha = EXP2 ? __builtin_amdgcn_exp2f(mrun[qf] - mnew) : expf(mrun[qf] - mnew);
                 const float delta = mb - mnew;               // scores already hold s - mb: move them to s - mnew
 #pragma unroll
@@ -184,10 +223,28 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if (tn + 1 < ntiles) stage_tiles(lds + ((tn + 1) % 3) * STAGE_BYTES, Kbh, Vbh, v_row_bytes, tn + 1, wave_u, lane);
+#ifdef PM_ATTN_SEG
+        {                                                    // every tile: zero the V^T columns of padding keys (255, or >= Nkv)
+            unsigned char* Vl = lds + (tn % 3) * STAGE_BYTES + TILE_BYTES;
+            for (int idx = tid; idx < KT * SLOTS; idx += THREADS) {
+                const int row = idx / SLOTS, lslot = idx % SLOTS;
+                uint4* p = reinterpret_cast<uint4*>(Vl + row * ROWB + ((lslot ^ (row & (SLOTS - 1))) << 4));
+                uint4 v = *p;
+                const int k0 = tn * KT + lslot * 4;
+                if (seg_of(k0 + 0) == 255u) v.x = 0u;
+                if (seg_of(k0 + 1) == 255u) v.y = 0u;
+                if (seg_of(k0 + 2) == 255u) v.z = 0u;
+                if (seg_of(k0 + 3) == 255u) v.w = 0u;
+                *p = v;
+            }
+            __syncthreads();
+        }
+#else
         if (tn * KT + KT > Nkv) {
             zero_ragged_v(lds + (tn % 3) * STAGE_BYTES + TILE_BYTES, tn * KT, Nkv, tid);
             __syncthreads();
         }
+#endif
     };
 
     stage_tiles(lds, Kbh, Vbh, v_row_bytes, 0, wave_u, lane);
@@ -227,7 +284,12 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
     float inv[QF];
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {      // cross-lane steps first, outside any divergent region
+#ifdef PM_ATTN_SEG
+        const float lsum = group4_sum(lrun[qf]);
+        inv[qf] = lsum > 0.f ? 1.0f / lsum : 0.f;            // (a query with no allowed key: a finite row)
+#else
         inv[qf] = 1.0f / group4_sum(lrun[qf]);
+#endif
     }
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {

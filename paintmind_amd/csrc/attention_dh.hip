@@ -9,7 +9,7 @@
 //                walk the keys in the same order, so K / V^T addresses are wave-uniform per quad position and come out of
 //                L1/L2 as broadcasts.  The score matrix is never materialised.
 //
-// The attention entry points of the C ABI (pmhip_attention, pmhip_attention_dh, pmhip_attention_lens) are at the end of this file:
+// The attention entry points of the C ABI (pmhip_attention, pmhip_attention_dh, pmhip_attention_lens, pmhip_attention_segments) are at the end of this file:
 // one argument check for the family, then the launcher of attention.hip, attention_bf16.hip or this file.
 #include "common.h"
 
@@ -63,10 +63,24 @@ __device__ __forceinline__ float quad_sum(float v) {
 #undef PM_ATTN_KERNEL
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_LENS
+// the per-query form: key k takes part in query q's softmax iff key_seg[b,k] < 32 and bit key_seg[b,k] of query_mask[b,q] is set
+#define PM_ATTN_KERNEL attention_dh_seg_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
+#define PM_ATTN_SEG 1
+#include "attention_dh_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
 
 template <typename T, int DPL>
 void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-               int use_exp2, const int* lens, hipStream_t s) {
+               int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s) {
+    if (seg) {
+        auto k = use_exp2 ? attention_dh_seg_kernel<T, DPL, true> : attention_dh_seg_kernel<T, DPL, false>;
+        hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
+                           Nkv, Nkp, seg->key_seg, seg->query_mask);
+        return;
+    }
     auto launch = [&](auto plain, auto per_image) {
         pm_launch_lens(plain, per_image, dim3((Nq + 63) / 64, B * heads), dim3(256), s, lens, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
                        ldo, heads, Nq, Nkv, Nkp);
@@ -78,9 +92,9 @@ void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo,
 // the launcher of this file's kernels: dim_head != 64, already passed through check_dh
 template <typename T>
 int pm_attention_dh(int dh, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-                    int use_exp2, const int* lens, hipStream_t s) {
+                    int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s) {
     switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, s); break;
+#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, seg, s); break;
         PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
 #undef PM_DH_CASE
         default: PM_REQUIRE(false, "attention_dh: dim_head=%d not served", dh);
@@ -128,14 +142,17 @@ extern "C" int pmhip_gemm_heads_dh(int dtype, const void* A, int lda, const void
 
 // the dim_head = 64 launchers (attention.hip, attention_bf16.hip)
 void pm_attention_f32(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                      int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
+                      int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s);
 void pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
                        int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
+void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                           int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s);
 
 // Every attention entry point ends here: the arguments are checked once, then one launcher per kernel file.  lens = device
-// int32 [B], the per-image key counts, or NULL (one key count for the launch).
+// int32 [B], the per-image key counts, or NULL (one key count for the launch); seg = the per-query key sets (device arrays), or NULL.
 static int attention_any(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
-                         int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s) {
+                         int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s,
+                         const PmAttnSeg* seg = nullptr) {
     const bool tuned = dim_head == 64;               // the MFMA kernels; otherwise this file's plain path
     if (!tuned) PM_TRY(check_dh(who, heads, dim_head));
     PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "%s: bad dtype %d", who, dtype);
@@ -151,12 +168,13 @@ static int attention_any(const char* who, int dtype, const void* Q, const void* 
     if (!tuned) PM_REQUIRE((long long)B * heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)B * heads);
     PmTimer tm(FAM_ATTENTION, s);
     if (!tuned) {
-        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s));
-        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s));
+        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, s));
+        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, s));
     } else if (dtype == PMHIP_F32) {
-        pm_attention_f32(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+        pm_attention_f32(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, s);
     } else {
-        pm_attention_bf16(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+        if (seg) pm_attention_bf16_seg(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, s);
+        else pm_attention_bf16(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
     }
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
@@ -179,4 +197,13 @@ extern "C" int pmhip_attention_lens(int dtype, const void* Q, const void* K, con
     PM_REQUIRE(kv_lens, "attention_lens: kv_lens is NULL (pmhip_attention_dh is the entry without per-image key counts)");
     return attention_any("attention_lens", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, kv_lens,
                          (hipStream_t)stream);
+}
+
+extern "C" int pmhip_attention_segments(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                                        int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
+                                        const uint32_t* query_mask, pmhip_stream stream) {
+    PM_REQUIRE(key_seg && query_mask, "attention_segments: key_seg / query_mask is NULL (pmhip_attention_dh is the entry without key sets)");
+    const PmAttnSeg seg{key_seg, query_mask};
+    return attention_any("attention_segments", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
+                         (hipStream_t)stream, &seg);
 }

@@ -1,6 +1,8 @@
-// The plain-path attention kernel of attention_dh.hip (DPL = dims per lane = dh / 4), which includes this file TWICE (no include
+// The plain-path attention kernel of attention_dh.hip (DPL = dims per lane = dh / 4), which includes this file THREE TIMES (no include
 // guard on purpose), exactly as attention_bf16.hip includes attention_bf16_body.h -- see there: PM_ATTN_KERNEL names the kernel,
 // PM_ATTN_LENS_PARAM is empty or ", const int* lens", and with PM_ATTN_LENS the loop bound is lens[b], clamped to [1, Nkv].
+// A THIRD inclusion with PM_ATTN_SEG (attention_dh_seg_kernel; parameters key_seg, query_mask) is the per-query key set of DESIGN.md
+// 4u: a key whose segment the query does not attend to (or padding, 255) is skipped -- its score and its V column are read by no update.
 template <typename T, int DPL, bool EXP2>
 __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ Vt,
                                                           T* __restrict__ out, int ldo, int heads, int Nq, int Nkv, int Nkp PM_ATTN_LENS_PARAM) {
@@ -21,11 +23,19 @@ __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, c
     const T* kp = K + (size_t)bh * Nkp * DH + part * DPL;
     const T* vp = Vt + ((size_t)bh * DH + part * DPL) * Nkp;
     float m = -INFINITY, l = 0.f;
+#ifdef PM_ATTN_SEG
+    const unsigned char* segb = key_seg + (size_t)b * Nkv;
+    const unsigned qm = query_mask[(size_t)b * Nq + qr];
+#endif
     for (int j = 0; j < Nkv; ++j) {
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < DPL; ++i) s = fmaf(q[i], to_f32<T>(kp[(size_t)j * DH + i]), s);
         s = quad_sum(s);
+#ifdef PM_ATTN_SEG
+        const unsigned sg = segb[j];                            // (the four lanes of a query agree: the quad stays whole)
+        if (!((sg < 32u) & ((qm >> (sg & 31u)) & 1u))) continue;
+#endif
         const float mn = fmaxf(m, s);
         const float a = EXP2 ? exp2f(m - mn) : expf(m - mn);
         const float pj = EXP2 ? exp2f(s - mn) : expf(s - mn);
@@ -35,7 +45,11 @@ __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, c
         m = mn;
     }
     if (qi < Nq) {
+#ifdef PM_ATTN_SEG
+        const float inv = l > 0.f ? 1.f / l : 0.f;              // (a query with no allowed key: a finite row)
+#else
         const float inv = 1.f / l;
+#endif
         T* op = out + ((size_t)b * Nq + qi) * ldo + h * DH + part * DPL;
 #pragma unroll
         for (int i = 0; i < DPL; ++i) op[i] = from_f32<T>(o[i] * inv);

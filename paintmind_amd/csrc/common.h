@@ -413,6 +413,13 @@ static inline void pm_launch_lens(Plain plain, PerImage per_image, dim3 grid, di
     else hipLaunchKernelGGL(plain, grid, block, 0, s, args...);
 }
 
+// The third form: a key SET per query.  key_seg device uint8 [B, Nkv] (segment 0..31 of a key, 255 = padding),
+// query_mask device uint32 [B, Nq] (bit s: the query attends to segment s).  The launchers take a pointer to this, NULL for none.
+struct PmAttnSeg {
+    const unsigned char* key_seg;
+    const unsigned* query_mask;
+};
+
 // Can a LayerNorm over K columns be folded into the GEMM out[M,N] = A[M,K] (row stride lda) . W[N,K]^T (row stride ldw)?  THE
 // predicate: the engine's decision (M = one image's rows: folded or not must not depend on the batch), the GEMM entry points'
 // check and pmhip_lnfold_supported all ask it.  M, N whole 256x256 tiles, K whole pairs of K-tiles, and both operands within the

@@ -196,6 +196,10 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     const void* vt = nullptr;
     int L = 0, Lp = 0;
     const int32_t* lens = nullptr;   // device [B]: per-image key counts of THIS call (NULL: every image attends to all L rows)
+    // regional prompts, THIS call's or NULL: device uint8 [B, L], the segment of every context row (255 = padding),
+    // and device uint32 [B, tokens], the segments every token attends to.  Never beside `lens`.
+    const uint8_t* key_seg = nullptr;
+    const uint32_t* query_mask = nullptr;
 };
 
 // The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
@@ -438,7 +442,10 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 1, kind_q,
                             outs, q_scale, s));
             // the one launch that sees per-image context lengths (self-attention and the unconditional pass never do)
-            if (cross->lens)
+            if (cross->key_seg)
+                PM_TRY(pmhip_attention_segments(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
+                                                cross->key_seg, cross->query_mask, s));
+            else if (cross->lens)
                 PM_TRY(pmhip_attention_lens(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
                                             cross->lens, s));
             else
@@ -774,6 +781,7 @@ struct pmhip_s2 {
     PinnedRing slots_ring;
     PinnedRing lens_ring;           // per-image context lengths of a call (ctx_lens_host): B int32 -> workspace "ctx.lens"
     PinnedRing neg_lens_ring;       // ... and of its negative context (neg_lens_host): B int32 -> workspace "neg.lens"
+    PinnedRing seg_ring;            // regional prompts: B * tokens uint32 token masks, then B * L uint8 row segments -> workspace "ctx.seg"
     PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
     int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
     int slots_filter_tiles = 0, slots_filter_chain = 0;   // steps of pmhip_pipeline_step_slots_filter by the form of their sampling tail
@@ -875,6 +883,7 @@ int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStrea
         const unsigned char* wkv = reinterpret_cast<const unsigned char*>(h->layers[l].wqkv2) + (size_t)inner * dim * es;
         PM_TRY(pmhip_gemm_heads_dh(h->dtype, cp, dim, wkv, dim, Mc, dim, heads, dh, L, Lp, 2, kinds, outs, 1.0f, split, s));
         cs.kv[l].k = outs[0]; cs.kv[l].vt = outs[1]; cs.kv[l].L = L; cs.kv[l].Lp = Lp; cs.kv[l].lens = nullptr;
+        cs.kv[l].key_seg = nullptr; cs.kv[l].query_mask = nullptr;
     }
     return PMHIP_OK;
 }
@@ -906,7 +915,57 @@ int s2_set_ctx_lens(pmhip_s2* h, const int32_t* lens_host, int L, int B, hipStre
         PM_TRY(cs.ring.stage(dlens, 0, padded.data(), (size_t)Bp * 4, s));
         PM_TRY(cs.ring.commit(s));
     }
-    for (auto& ck : cs.kv) ck.lens = ck.k ? dlens : nullptr;
+    for (auto& ck : cs.kv) {
+        ck.lens = ck.k ? dlens : nullptr;
+        ck.key_seg = nullptr; ck.query_mask = nullptr;        // the segments of an earlier call are dropped with its lengths
+    }
+    return PMHIP_OK;
+}
+
+// Regional prompts (the *_segments entries), checked BEFORE anything is launched.  ctx_seg_host uint8 [B, L]: the segment 0..31 of
+// every context row, 255 = padding; tok_seg_host uint32 [B, tokens]: bit s = the token attends to segment s.  Both or neither; they
+// need a context (without one attn2 is a second self-attention, which never sees segments) and exclude ctx_lens_host, which the
+// padding value subsumes.  Every token must allow a segment that is PRESENT in its image: an empty softmax has no value.
+int check_segments(const char* who, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const int32_t* ctx_lens_host, bool have_context,
+                   int L, int B, const pmhip_s2* h) {
+    PM_REQUIRE(!ctx_seg_host == !tok_seg_host, "%s: ctx_seg_host and tok_seg_host come together (one of them is NULL)", who);
+    if (!ctx_seg_host) return PMHIP_OK;
+    PM_REQUIRE(have_context && L > 0, "%s: segments given without a context", who);
+    PM_REQUIRE(!ctx_lens_host, "%s: segments and ctx_lens_host exclude each other (mark padding rows with segment 255)", who);
+    const int tokens = h->cfg.tokens;                         // (the handle is read only once the arrays are known to be there)
+    for (int b = 0; b < B; ++b) {
+        uint32_t present = 0;
+        for (int k = 0; k < L; ++k) {
+            const int sg = ctx_seg_host[(size_t)b * L + k];
+            PM_REQUIRE(sg < 32 || sg == 255, "%s: image %d: context row %d: segment %d must be in 0..31, or 255 for padding", who, b, k, sg);
+            if (sg < 32) present |= 1u << sg;
+        }
+        for (int t = 0; t < tokens; ++t)
+            PM_REQUIRE(tok_seg_host[(size_t)b * tokens + t] & present,
+                       "%s: image %d: token %d allows no segment that is present in its context (mask 0x%08x, present 0x%08x)", who, b, t,
+                       (unsigned)tok_seg_host[(size_t)b * tokens + t], (unsigned)present);
+    }
+    return PMHIP_OK;
+}
+
+// The checked segments travel like the lengths: one pinned ring entry (token masks, then row segments, each padded to 16 bytes) ->
+// copy kernel -> the handle's device array "ctx.seg" -> every layer's CrossKV of the context's set, from where the cross-attention
+// launch of layer_forward hands them to pmhip_attention_segments.  Called right behind s2_set_ctx_lens (which drops the segments of
+// an earlier call), always outside a graph: a captured graph bakes in the device array, never a layout of regions.
+int s2_set_segments(pmhip_s2* h, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, int L, int B, hipStream_t s) {
+    if (!ctx_seg_host) return PMHIP_OK;
+    const size_t qbytes = ((size_t)B * h->cfg.tokens * 4 + 15) & ~(size_t)15, kbytes = ((size_t)B * L + 15) & ~(size_t)15;
+    unsigned char* dseg;
+    WS(h->ws, "ctx.seg", qbytes + kbytes, dseg);
+    std::vector<unsigned char> packed(qbytes + kbytes, 255);
+    memcpy(packed.data(), tok_seg_host, (size_t)B * h->cfg.tokens * 4);
+    memcpy(packed.data() + qbytes, ctx_seg_host, (size_t)B * L);
+    PM_TRY(h->seg_ring.reserve(qbytes + kbytes));
+    PM_TRY(h->seg_ring.acquire());
+    PM_TRY(h->seg_ring.stage(dseg, 0, packed.data(), qbytes + kbytes, s));
+    PM_TRY(h->seg_ring.commit(s));
+    for (auto& ck : h->cross)
+        if (ck.k) { ck.query_mask = reinterpret_cast<const uint32_t*>(dseg); ck.key_seg = dseg + qbytes; }
     return PMHIP_OK;
 }
 
@@ -1207,13 +1266,16 @@ int run_graphs(pmhip_s2* s2, pmhip_vqgan* vq, GraphEntry& ge, size_t n_units, hi
 }  // namespace
 
 static int s2_forward_impl(const char* who, pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
-                           float* logits_out, pmhip_stream stream) {
+                           float* logits_out, pmhip_stream stream, const uint8_t* ctx_seg_host = nullptr,
+                           const uint32_t* tok_seg_host = nullptr) {
     PM_REQUIRE(h && tokens && logits_out && B > 0, "%s: bad arguments", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
+    PM_TRY(check_segments(who, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, h));
     hipStream_t s = (hipStream_t)stream;
     const int M = B * h->cfg.tokens;
     PM_TRY(s2_prepare_context(h, context, L, B, s));
     PM_TRY(s2_set_ctx_lens(h, ctx_lens_host, L, B, s));
+    PM_TRY(s2_set_segments(h, ctx_seg_host, tok_seg_host, L, B, s));
     void* tp;
     PM_TRY(tok_buf(h, M, tp, s));
     PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
@@ -1230,6 +1292,23 @@ extern "C" int pmhip_s2_forward_lens(pmhip_s2* h, const float* tokens, const flo
     return s2_forward_impl("s2_forward_lens", h, tokens, context, L, B, ctx_lens_host, logits_out, stream);
 }
 
+// the handle's graph cache: keys it holds, and how many of them hold captured graphs (the first call under a key runs eagerly)
+extern "C" int pmhip_s2_graph_count(const pmhip_s2* h, int* entries, int* captured) {
+    PM_REQUIRE(h, "s2_graph_count: NULL handle");
+    int n = 0;
+    for (const auto& kv : h->graphs) n += kv.second.segs.empty() ? 0 : 1;
+    if (entries) *entries = (int)h->graphs.size();
+    if (captured) *captured = n;
+    return PMHIP_OK;
+}
+
+// ctx_seg_host == NULL and tok_seg_host == NULL: exactly pmhip_s2_forward
+extern "C" int pmhip_s2_forward_segments(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const uint8_t* ctx_seg_host,
+                                         const uint32_t* tok_seg_host, float* logits_out, pmhip_stream stream) {
+    return s2_forward_impl(ctx_seg_host || tok_seg_host ? "s2_forward_segments" : "s2_forward", h, tokens, context, L, B, nullptr, logits_out,
+                           stream, ctx_seg_host, tok_seg_host);
+}
+
 // The sample family's one builder: the argument list of pmhip_pipeline_sample_nucleus, the widest entry, -> the Step and the name
 // the messages carry.  A narrower entry passes the neutral values (include/pmhip.h) and `narrow`, the name its messages carry when
 // neither a nucleus mass nor a choice temperature is in play: its own, or the *_lens entry's for the two entries above that one.
@@ -1237,12 +1316,14 @@ static int pipeline_sample_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* v
                                 const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                 uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out, float* score_out, int guided,
                                 float guidance_scale, float choice_t, const float* choice_noise, float top_p, pmhip_stream stream,
-                                const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr) {
+                                const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
+                                const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr) {
     PM_TRY(pm_check_top_p("pipeline_sample_nucleus", top_p));
     const char* wide = top_p != 1.f ? "pipeline_sample_nucleus" : "pipeline_sample_choice";
     PM_TRY(pm_check_choice_t(wide, choice_t));
     PM_TRY(check_negative("pipeline_sample_negative", neg_context, Ln, neg_lens_host, false, guided != 0, context && L > 0, B));
-    const char* who = neg_context ? "pipeline_sample_negative" : top_p != 1.f || choice_t != 0.f ? wide : narrow;
+    const char* who = ctx_seg_host || tok_seg_host ? "pipeline_sample_segments"
+                      : neg_context ? "pipeline_sample_negative" : top_p != 1.f || choice_t != 0.f ? wide : narrow;
     Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
     if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }     // 0: no given uniforms to ignore
     st.top_p = top_p;
@@ -1250,9 +1331,11 @@ static int pipeline_sample_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* v
     PM_REQUIRE(s2 && ids && B > 0, "%s: bad arguments", who);
     PM_REQUIRE(!st.guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
+    PM_TRY(check_segments(who, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, s2));
     hipStream_t s = (hipStream_t)stream;
     PM_TRY(s2_prepare_context(s2, context, L, B, s));         // (drops the negative set of an earlier call)
     PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
+    PM_TRY(s2_set_segments(s2, ctx_seg_host, tok_seg_host, L, B, s));   // the context's set only: the other passes never see segments
     if (neg_context) {
         PM_TRY(s2_prepare_context(s2, neg_context, Ln, B, s, kCrossNegative));
         PM_TRY(s2_set_ctx_lens(s2, neg_lens_host, Ln, B, s, kCrossNegative));
@@ -1316,6 +1399,18 @@ extern "C" int pmhip_pipeline_sample_negative(pmhip_s2* s2, pmhip_vqgan* vq, int
                                 neg_context, Ln, neg_lens_host);
 }
 
+// ctx_seg_host == NULL and tok_seg_host == NULL: exactly pmhip_pipeline_sample_negative
+extern "C" int pmhip_pipeline_sample_segments(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                              const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                              uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                              float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
+                                              float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                              const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, pmhip_stream stream) {
+    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream,
+                                neg_context, Ln, neg_lens_host, ctx_seg_host, tok_seg_host);
+}
+
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
 static bool direct_dispatch_off() {
     static const bool off = [] { const char* e = getenv("AMD_DIRECT_DISPATCH"); return e && atoi(e) == 0; }();
@@ -1342,6 +1437,8 @@ struct GenCall {
     // pmhip_pipeline_generate_edit: the re-masking counts per step and image, host [T][B], instead of nmask_host (then NULL); a
     // decoded step of such a loop decodes the merged ids
     const int32_t* nmask_img = nullptr;
+    // pmhip_pipeline_generate_segments: regional prompts, host uint8 [B, L] and uint32 [B, tokens], or both NULL
+    const uint8_t* ctx_seg = nullptr; const uint32_t* tok_seg = nullptr;
     bool guided() const { return guidance || gscales; }
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
@@ -1422,6 +1519,7 @@ int pipeline_generate(const GenCall& c) {
     }
     PM_REQUIRE(!c.guided() || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
     PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
+    PM_TRY(check_segments(c.who, c.ctx_seg, c.tok_seg, c.ctx_lens, c.context != nullptr, c.L, B, s2));
     const bool sched = c.gscales != nullptr, neg = c.neg_context != nullptr;
     // the choice temperatures, checked before anything is launched; all zero IS the loop without them (same kernels, same graphs)
     bool choice = false;
@@ -1433,6 +1531,7 @@ int pipeline_generate(const GenCall& c) {
     hipStream_t cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
     PM_TRY(s2_prepare_context(s2, c.context, c.L, B, s));     // context projection + cross K/V: once per loop, eager
     PM_TRY(s2_set_ctx_lens(s2, c.ctx_lens, c.L, B, s));       // the lengths: device memory the (captured) cross-attention launches read
+    PM_TRY(s2_set_segments(s2, c.ctx_seg, c.tok_seg, c.L, B, s));   // ... and the segments, likewise (the context's set only)
     if (neg) {                                                // the negative set: one more preparation per loop, eager like the first
         PM_TRY(s2_prepare_context(s2, c.neg_context, c.Ln, B, s, kCrossNegative));
         PM_TRY(s2_set_ctx_lens(s2, c.neg_lens, c.Ln, B, s, kCrossNegative));
@@ -1576,6 +1675,7 @@ int pipeline_generate(const GenCall& c) {
     key += overlap ? "o1" : "o0";
     if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
     if (c.ctx_lens) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
+    if (c.ctx_seg) key += "s";                                // the per-query form of the cross-attention kernel; the layout of regions is not in the key
     if (edit) key += "e";                                     // the counts form of the re-masking kernel and the merged decode; the counts are not in the key
     if (choice) key += "c";                                   // the choice form of the re-masking kernel; the temperatures are not in the key
     if (c.top_p < 1.f) {                                      // the nucleus kernel, the mass its argument in the captured graph: one graph per value
@@ -1640,7 +1740,8 @@ static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan*
                                   int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride, pmhip_stream copy_stream,
                                   int guided, float guidance_scale, const float* ctemps_host, float top_p,
                                   const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
-                                  const float* gscales_host = nullptr, const int32_t* nmask_img_host = nullptr) {
+                                  const float* gscales_host = nullptr, const int32_t* nmask_img_host = nullptr,
+                                  const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr) {
     PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
     const char* neg_who = nmask_img_host ? narrow : "pipeline_generate_negative";
     PM_TRY(check_negative(neg_who, neg_context, Ln, neg_lens_host, gscales_host != nullptr, guided != 0, context && L > 0, B));
@@ -1655,6 +1756,8 @@ static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan*
     c.neg_context = neg_context; c.Ln = Ln; c.neg_lens = neg_lens_host;
     c.gscales = gscales_host;
     c.nmask_img = nmask_img_host;
+    c.ctx_seg = ctx_seg_host; c.tok_seg = tok_seg_host;
+    if (ctx_seg_host || tok_seg_host) c.who = "pipeline_generate_segments";
     return pipeline_generate(c);
 }
 
@@ -1719,6 +1822,20 @@ extern "C" int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, i
     return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
                                   topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
                                   guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host);
+}
+
+// ctx_seg_host == NULL and tok_seg_host == NULL: exactly pmhip_pipeline_generate_negative
+extern "C" int pmhip_pipeline_generate_segments(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                                const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                                const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                                float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                                pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
+                                                float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                                const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host) {
+    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
+                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host, nullptr, ctx_seg_host,
+                                  tok_seg_host);
 }
 
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged

@@ -212,6 +212,13 @@ class S2Engine:
         """the PMHIP_* switches this handle latched when it was created (they are not re-read: include/pmhip.h)"""
         return _switch_dict(self.lib.pmhip_s2_switches(self.handle))
 
+    def graph_count(self):
+        """(entries, captured) of this handle's graph cache (pmhip_s2_graph_count): the keys it holds, and how many of them hold
+        captured graphs"""
+        entries, captured = C.c_int(0), C.c_int(0)
+        check(self.lib.pmhip_s2_graph_count(self.handle, C.byref(entries), C.byref(captured)), "pmhip_s2_graph_count")
+        return entries.value, captured.value
+
     def step0_shared(self):
         """(fills, hits) of this handle's shared step-0 logits (pmhip_s2_step0_shared): computed 0 or 1 times, sampled from by
         `hits` later unconditional loops that ran no step-0 tower"""
@@ -299,21 +306,43 @@ class S2Engine:
         vals = ops.host_lens(context_lens, B, L)
         return (C.c_int * B)(*vals)
 
-    def forward(self, tokens, context=None, context_lens=None):
+    def _segments(self, context_segments, token_segments, context, context_lens, B, L):
+        """regional prompts: context_segments [B, L] (the segment 0..31 of every context row, -1 / 255 =
+        padding) and token_segments [B, tokens] (bit masks) -> (ctypes uint8 [B * L], ctypes uint32 [B * tokens]) for ctx_seg_host /
+        tok_seg_host, or None; checked here (``ops.host_segments``) and again by the native entry"""
+        if context_segments is None and token_segments is None:
+            return None
+        if context is None and L == 0:
+            raise ValueError("context_segments / token_segments need a context (context None IS the unconditional branch)")
+        if context_lens is not None:
+            raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
+        cs, ts = ops.host_segments(context_segments, token_segments, B, L, self.tokens)
+        return (np.ctypeslib.as_ctypes(cs.reshape(-1)), np.ctypeslib.as_ctypes(ts.reshape(-1)))
+
+    def forward(self, tokens, context=None, context_lens=None, context_segments=None, token_segments=None):
+        """context_segments / token_segments (None = the call as without them): regional prompts, see ``_segments``
+        (pmhip_s2_forward_segments)."""
         tokens = tokens.to(self.device, torch.float32).contiguous()
         B = tokens.shape[0]
         context, L = self._ctx(context)
         lens = self._lens(context_lens, context, B, L)
+        seg = self._segments(context_segments, token_segments, context, context_lens, B, L)
         logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
+            if seg is not None:
+                check(self.lib.pmhip_s2_forward_segments(self.handle, _p(tokens), _p(context), L, B, seg[0], seg[1], _p(logits),
+                                                         stream_ptr(self.device)), "pmhip_s2_forward_segments")
+                return logits
             check(self.lib.pmhip_s2_forward_lens(self.handle, _p(tokens), _p(context), L, B, lens, _p(logits), stream_ptr(self.device)),
                   "pmhip_s2_forward_lens")
         return logits
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
                want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None,
-               top_p=None, negative_context=None, negative_lens=None):
+               top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
+        context_segments / token_segments (None = the calls below): regional prompts, see ``_segments``; only the pass with the
+        context sees them (pmhip_pipeline_sample_segments).
         negative_context fp32 [B, Ln, context_dim] (None = the calls below, as without the keyword): the second tower of the guided
         step attends to it instead of running without a context (pmhip_pipeline_sample_negative); negative_lens: its per-image
         lengths, like context_lens.  Needs guidance_scale.
@@ -330,6 +359,7 @@ class S2Engine:
         nucleus = ops.nucleus_p(top_p)
         context, L = self._ctx(context)
         lens = self._lens(context_lens, context, B, L)
+        seg = self._segments(context_segments, token_segments, context, context_lens, B, L)
         img = vq_engine._new_img(B) if want_img else None
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
@@ -346,7 +376,10 @@ class S2Engine:
                 int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img), _p(pred),
                 _p(score), int(guidance_scale is not None), float(guidance_scale or 0.0), ct, _p(choice_noise if ct else None), nucleus)
         with torch.cuda.device(self.device):
-            if neg is None:                       # without a negative context the native call is the one made before there was one
+            if seg is not None:
+                check(self.lib.pmhip_pipeline_sample_segments(*args, _p(neg), Ln, neg_lens, seg[0], seg[1], stream_ptr(self.device)),
+                      "pmhip_pipeline_sample_segments")
+            elif neg is None:                     # without a negative context the native call is the one made before there was one
                 check(self.lib.pmhip_pipeline_sample_nucleus(*args, stream_ptr(self.device)), "pmhip_pipeline_sample_nucleus")
             else:
                 check(self.lib.pmhip_pipeline_sample_negative(*args, _p(neg), Ln, neg_lens, stream_ptr(self.device)),
@@ -487,8 +520,12 @@ class S2Engine:
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
                  host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
-                 choice_temps=None, top_p=None, negative_context=None, negative_lens=None, guidance_scales=None, nmask_img=None):
+                 choice_temps=None, top_p=None, negative_context=None, negative_lens=None, guidance_scales=None, nmask_img=None,
+                 context_segments=None, token_segments=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
+
+        context_segments / token_segments (None = the loops below): regional prompts, see ``_segments``
+        (pmhip_pipeline_generate_segments); the captured loop reads them from device memory: one graph serves every layout.
 
         nmask_img (None = the loops below): the EDIT loop (pmhip_pipeline_generate_edit) -- T rows of B integers, step t re-masking
         nmask_img[t][b] positions of image b (0: none) instead of nmask[t] of every image; a decoded step then decodes the merged
@@ -523,6 +560,9 @@ class S2Engine:
             choice_temps = (C.c_float * T)(*vals) if any(vals) else None
         context, L = self._ctx(context)
         lens = self._lens(context_lens, context, B, L)
+        seg = self._segments(context_segments, token_segments, context, context_lens, B, L)
+        if seg is not None and nmask_img is not None:
+            raise ValueError("generate: the edit loop takes no regional prompts")
         n_dec = int(sum(1 for f in decode_flags if f))
         imgs = None
         if n_dec and (want_device_imgs or host is None):
@@ -559,7 +599,10 @@ class S2Engine:
             args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
                     temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
                     host_stride, copy_stream, int(guided), float(guidance_scale or 0.0), choice_temps, nucleus)
-            if nmask_img is not None:
+            if seg is not None:
+                check(self.lib.pmhip_pipeline_generate_segments(*args, _p(neg), Ln, neg_lens, gscales, seg[0], seg[1]),
+                      "pmhip_pipeline_generate_segments")
+            elif nmask_img is not None:
                 check(self.lib.pmhip_pipeline_generate_edit(*args, _p(neg), Ln, neg_lens, gscales), "pmhip_pipeline_generate_edit")
             elif neg is None and gscales is None:
                 check(self.lib.pmhip_pipeline_generate_nucleus(*args), "pmhip_pipeline_generate_nucleus")

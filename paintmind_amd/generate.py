@@ -84,6 +84,54 @@ def loop_schedule(timesteps, temperature, num_tokens, choice_temperature=None):
     return temps, nmask, choice_schedule(timesteps, choice_temperature)
 
 
+def region_token_mask(mask, image_size, patch_size):
+    """one region's mask -> bool [g * g] over the token grid (g = image_size // patch_size): a bool [g, g] token mask as it is, or
+    a pixel mask [H, W] (non-zero = inside), of which a token is part iff ANY pixel of its patch is -- the rule of ``Pipeline.edit``"""
+    m = torch.as_tensor(mask).cpu()
+    g = image_size // patch_size
+    if tuple(m.shape) == (g, g) and (m.dtype == torch.bool or g == image_size):
+        return (m != 0).reshape(-1)
+    if tuple(m.shape) != (image_size, image_size):
+        raise ValueError(f"regions: a mask must be a bool [{g}, {g}] token mask or a [{image_size}, {image_size}] pixel mask, got "
+                         f"{m.dtype} {tuple(m.shape)}")
+    return ((m != 0).reshape(g, patch_size, g, patch_size).to(torch.uint8).amax(dim=(1, 3)) != 0).reshape(-1)
+
+
+MAX_REGIONS = 31           # segments 1..31 beside the global prompt's segment 0: one bit each of a token's 32-bit mask
+
+
+def region_layout(contexts, masks, image_size, patch_size):
+    """The concatenated context of regional prompts and its two arrays.  contexts: per image a list of [L_r, D] tensors, the global
+    prompt's rows first, then every region's; masks: per image the regions' masks (one fewer than contexts).
+    -> (context fp32 [B, Lmax, D], zero-filled behind an image's rows; numpy uint8 [B, Lmax], the segment of every row, 255 = padding;
+    numpy uint32 [B, N], bit 0 | bit r for every region r the token is part of)"""
+    B = len(contexts)
+    g = image_size // patch_size
+    totals = [sum(c.shape[0] for c in cs) for cs in contexts]
+    Lmax, D = max(totals), contexts[0][0].shape[1]
+    context = torch.zeros(B, Lmax, D, dtype=torch.float32)
+    ctx_seg = np.full((B, Lmax), 255, np.uint8)
+    tok_seg = np.ones((B, g * g), np.uint32)
+    for b in range(B):
+        if len(masks[b]) != len(contexts[b]) - 1:
+            raise ValueError(f"regions: image {b}: {len(masks[b])} masks for {len(contexts[b]) - 1} region prompts")
+        if len(masks[b]) > MAX_REGIONS:
+            raise ValueError(f"regions: image {b}: {len(masks[b])} regions, at most {MAX_REGIONS} per image")
+        at = 0
+        for r, c in enumerate(contexts[b]):
+            context[b, at:at + c.shape[0]] = c.detach().to("cpu", torch.float32)
+            ctx_seg[b, at:at + c.shape[0]] = r
+            at += c.shape[0]
+        for r, m in enumerate(masks[b], start=1):
+            tok_seg[b] |= region_token_mask(m, image_size, patch_size).numpy().astype(np.uint32) << np.uint32(r)
+    return context, ctx_seg, tok_seg
+
+
+def _seg_kw(segments, lo=None, hi=None):
+    """the regional prompts' checked arrays (or None) as the keywords the engine and the modules take, of images [lo, hi)"""
+    return {} if segments is None else dict(context_segments=segments[0][lo:hi], token_segments=segments[1][lo:hi])
+
+
 class _Options(NamedTuple):
     """the sampler options of one public call, checked once (Pipeline._options): topk an integer (None resolved to n_embed), top_p a
     float (1.0 = no nucleus filter), guidance_scale a number or None, lens the per-image context lengths as a host list or None,
@@ -357,13 +405,32 @@ class Pipeline(nn.Module):
         return _Options(self._topk(topk), top_p, guidance_scale, self._lens(context_lens, context, B), base, negative, negative_lens,
                         scales)
 
-    def tokens2logits(self, token, text=None, context_lens=None):
+    def _segments(self, context_segments, token_segments, context, context_lens, B):
+        """context_segments [B, L] / token_segments [B, N] (lists, arrays or tensors; both None pass through) -> the two checked
+        host arrays of ``ops.host_segments`` (numpy uint8 [B, L], numpy uint32 [B, N]), brought to the host ONCE per call.  They
+        travel beside the call's ``_Options``, not in it: they need the context and exclude context_lens."""
+        if context_segments is None and token_segments is None:
+            return None
+        if context is None:
+            raise ValueError("context_segments / token_segments need a text condition (text=None IS the unconditional branch)")
+        if context_lens is not None:
+            raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
+        return ops.host_segments(context_segments, token_segments, B, context.shape[1], self.num_tokens)
+
+    def tokens2logits(self, token, text=None, context_lens=None, context_segments=None, token_segments=None):
         """context_lens (extension; None = the reference's behaviour, every row of the context is attended to): one length per
-        image -- rows [len_b, L) of image b's context never reach its logits, NaN included."""
+        image -- rows [len_b, L) of image b's context never reach its logits, NaN included.
+
+        context_segments [B, L] ints + token_segments [B, N] int bitmasks (extension, REGIONAL PROMPTS; never
+        beside context_lens): row k of image b's context belongs to segment context_segments[b, k] in 0..31 (-1 or 255: padding,
+        which never reaches the logits, NaN included), and token t attends to exactly the rows whose segment is a set bit of
+        token_segments[b, t].  Every token must allow a segment that is present in its image.  ``generate(regions=)`` builds both
+        from prompts and masks."""
         lens = self._lens(context_lens, text, token.shape[0])
+        kw = _seg_kw(self._segments(context_segments, token_segments, text, context_lens, token.shape[0]))
         if self._on_cpu():
-            return self.transformer(token, text, lens)       # plain-torch operators of this package (no HIP engine on the CPU)
-        return self.engine().forward(token, text, context_lens=lens)
+            return self.transformer(token, text, lens, **kw)   # plain-torch operators of this package (no HIP engine on the CPU)
+        return self.engine().forward(token, text, context_lens=lens, **kw)
 
     @torch.no_grad()
     def ids2tokens(self, ids):
@@ -377,8 +444,12 @@ class Pipeline(nn.Module):
     @torch.no_grad()
     def sample(self, ids, mask_ratio, text=None, topk=1, temperature=1, noise=None, seed=None, step=0, image_base=0,
                guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None, top_p=None, negative_text=None,
-               negative_context_lens=None):
+               negative_context_lens=None, context_segments=None, token_segments=None):
         """One MaskGIT step (generate.py:159-181) -> (ids', img).
+
+        ``context_segments`` / ``token_segments`` (extension; None = the step as without them): regional prompts, see
+        ``tokens2logits``.  Only the forward with ``text`` sees them: the second forward of a guided step -- without a context or with
+        the negative one -- never does.
 
         ``negative_text`` (extension; None = the step as without the keyword): a NEGATIVE prompt -- like ``text`` a context tensor
         (B, Ln, D) here; Ln need not equal L.  The second forward of the guided step then sees this context instead of none, and
@@ -415,14 +486,17 @@ class Pipeline(nn.Module):
         nm = num_token_masked(mask_ratio, self.num_tokens)
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, text, ids.shape[0], negative_text,
                              negative_context_lens)
-        return self._step(ids, nm, text, opts, temperature, opts.choice_temperature, noise, seed, step, image_base, choice_noise)
+        segments = self._segments(context_segments, token_segments, text, context_lens, ids.shape[0])
+        return self._step(ids, nm, text, opts, temperature, opts.choice_temperature, noise, seed, step, image_base, choice_noise, segments)
 
     @torch.no_grad()
-    def _step(self, ids, nm, text, opts, temperature, choice_t, noise=None, seed=None, step=0, image_base=0, choice_noise=None):
-        """``sample`` behind its checks: one step that re-masks nm tokens, with the step's own temperature and choice temperature"""
+    def _step(self, ids, nm, text, opts, temperature, choice_t, noise=None, seed=None, step=0, image_base=0, choice_noise=None,
+              segments=None):
+        """``sample`` behind its checks: one step that re-masks nm tokens, with the step's own temperature and choice temperature;
+        segments: the regional prompts' checked arrays (``_segments``) or None"""
         if self._on_cpu():
             return self._sample_cpu(ids, nm, text, opts.topk, temperature, noise, seed, opts.guidance_scale, opts.lens, choice_t,
-                                    choice_noise, opts.top_p, opts.negative, opts.negative_lens)
+                                    choice_noise, opts.top_p, opts.negative, opts.negative_lens, segments=segments)
         if seed is None:
             seed = _draw_seed()
         eng = self.engine()
@@ -430,7 +504,7 @@ class Pipeline(nn.Module):
         ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, opts.topk, temperature, nm, noise=noise, seed=seed, step=step,
                                     image_base=image_base, want_img=True, guidance_scale=opts.guidance_scale, context_lens=opts.lens,
                                     choice_temperature=choice_t, choice_noise=choice_noise, top_p=opts.top_p,
-                                    negative_context=opts.negative, negative_lens=opts.negative_lens)
+                                    negative_context=opts.negative, negative_lens=opts.negative_lens, **_seg_kw(segments))
         return ids, img
 
     def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale, context_lens=None):
@@ -453,7 +527,7 @@ class Pipeline(nn.Module):
         return ids, img
 
     def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None, choice_t=0.0,
-                    choice_noise=None, top_p=1.0, negative=None, negative_lens=None, counts=None):
+                    choice_noise=None, top_p=1.0, negative=None, negative_lens=None, counts=None, segments=None):
         """generate.py:159-181 in plain torch for a pipeline that lives on the CPU.  The noise is drawn from the torch CPU
         generator like the reference's (`seed` re-seeds a private generator; `noise` overrides it); ties in top-k / argmax
         follow torch.  choice_t != 0: the re-masking sorts by choice_keys; its uniforms are `choice_noise`, or drawn behind the
@@ -462,7 +536,7 @@ class Pipeline(nn.Module):
         reference's step): the EDIT step -- image b re-masks counts[b] positions (0: none) instead of nm, and no image is decoded
         (``edit`` decodes the merged ids of its last step itself)."""
         tok = self.ids2tokens(ids)
-        logits = self.tokens2logits(tok, text, context_lens)
+        logits = self.tokens2logits(tok, text, context_lens, *(segments or ()))
         if guidance_scale is not None:
             uncond = self.tokens2logits(tok, negative, negative_lens)
             logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(guidance_scale)))
@@ -493,7 +567,7 @@ class Pipeline(nn.Module):
         return ids, img
 
     @torch.no_grad()
-    def _generate_cpu(self, context, B, timesteps, temperature, opts, save_interval, seed, return_ids):
+    def _generate_cpu(self, context, B, timesteps, temperature, opts, save_interval, seed, return_ids, segments=None):
         """generate.py:183-198, with plain or guided steps (see `sample`), for a pipeline that lives on the CPU.  (On the GPU the
         loop is the native one, graph-captured and lane-able.)"""
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
@@ -502,7 +576,7 @@ class Pipeline(nn.Module):
         for step in range(timesteps):
             ids, img = self._sample_cpu(ids, nmask[step], context, opts.topk, temps[step], None, None if seed is None else seed + step,
                                         opts.step_scale(step), opts.lens, ctemps[step] if ctemps else 0.0, None, opts.top_p, opts.negative,
-                                        opts.negative_lens)
+                                        opts.negative_lens, segments=segments)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
@@ -552,9 +626,11 @@ class Pipeline(nn.Module):
 
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
                      join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None,
-                     top_p=None, negative_context=None, negative_lens=None):
+                     top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
 
+        context_segments [B, L] / token_segments [B, N] (None: the loop as without them): regional prompts, see ``tokens2logits``.  Every
+        lane takes the rows of its micro-batch; the captured loop reads them from device memory, so one graph serves every layout.
         guidance_scale: a number, or a sequence of `timesteps` finite numbers, one per step (``generate`` has the meaning); the captured
         loop reads a schedule from device memory, so one graph serves every schedule.
         negative_context [B, Ln, D] (None: the second pass of a guided step runs without a context) with negative_lens, its per-image
@@ -583,14 +659,16 @@ class Pipeline(nn.Module):
         so every lane takes it as it is; below 1 part of the key of a captured graph."""
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative_context, negative_lens,
                              timesteps)
+        segments = self._segments(context_segments, token_segments, context, context_lens, B)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
 
-        def run(e, v, ids, c, o, **kw):                   # the native loop of one engine pair: the whole batch, or one lane's images
+        def run(e, v, ids, c, o, lo=None, hi=None, **kw):  # the native loop of one engine pair: the whole batch, or one lane's images [lo, hi)
             if o.negative is not None or o.guidance_scales is not None:
                 kw.update(negative_context=o.negative, negative_lens=o.negative_lens, guidance_scales=o.guidance_scales)
+            kw.update(_seg_kw(segments, lo, hi))
             return e.generate(v, ids, c, temps, nmask, decode_flags, o.topk, seed=seed, use_graph=use_graph, want_device_imgs=host is None,
                               guidance_scale=o.guidance_scale, context_lens=o.lens, choice_temps=ctemps, top_p=o.top_p, **kw)
 
@@ -628,7 +706,7 @@ class Pipeline(nn.Module):
             with torch.cuda.device(eng.device), torch.cuda.stream(st):
                 ids = torch.full((hi - lo, self.num_tokens), self.mask_token_id, dtype=torch.long, device=eng.device)
                 c = None if context is None else context[lo:hi].contiguous()
-                ids, imgs = run(e, v, ids, c, opts.lane(lo, hi), image_base=image_base + lo, concurrent_lanes=True,
+                ids, imgs = run(e, v, ids, c, opts.lane(lo, hi), lo, hi, image_base=image_base + lo, concurrent_lanes=True,
                                 from_mask=True,                  # lanes exist for ids0 None only (checked above)
                                 host=None if host is None else (host[0], lo, host[1][i]))
             return ids, imgs, st
@@ -671,8 +749,20 @@ class Pipeline(nn.Module):
 
     def generate(self, text, timesteps=18, temperature=1.0, topk=5, save_interval=2, seed=None, image_base=0,
                  return_ids=False, keep_on_device=False, use_graph=None, streams=None, guidance_scale=None, mask_padding=False,
-                 context_lens=None, choice_temperature=None, top_p=None, negative_text=None, negative_context_lens=None):
+                 context_lens=None, choice_temperature=None, top_p=None, negative_text=None, negative_context_lens=None, regions=None,
+                 context_segments=None, token_segments=None):
         """Full decode loop (generate.py:183-198): list of (B,3,H,W) CPU tensors for steps % save_interval == 0.
+
+        regions (extension; None = the loop as without it): REGIONAL PROMPTS, different text for different parts of the picture -- a
+        list of B lists of ``(prompt, mask)``.  ``mask`` is a pixel mask [H, W] (non-zero = inside) or a bool token mask [g, g]; a
+        token belongs to a region iff any pixel of its patch is set (the rule of ``edit``); regions may overlap, and a token in no
+        region sees the global prompt only.  ``text`` stays the GLOBAL prompt, which every token attends to.  Image b's context is
+        the concatenation [global | region 1 | region 2 | ...] (with ``mask_padding=True`` every prompt contributes its non-pad rows
+        only), zero-padded to the longest image's total; its cross-attention lets a token see the global rows and the rows of the
+        regions it is part of, nothing else.  At most 31 regions per image.  Guidance, ``negative_text``, ``topk``, ``top_p`` and
+        ``choice_temperature`` compose unchanged: the pass without the text and the negative prompt's pass carry no regions.
+        context_segments / token_segments give the two arrays explicitly instead (``tokens2logits``), for a ``text`` that is already
+        the concatenation; neither goes with context_lens.
 
         guidance_scale (extension; None = the reference's loop): a number -- every step samples from ``uncond + guidance_scale *
         (cond - uncond)`` (see ``sample``) -- or a sequence of ``timesteps`` finite numbers, step s guiding with its own: Muse
@@ -718,7 +808,11 @@ class Pipeline(nn.Module):
         the exact rule).  A mass cut follows the model from its flat early steps to its peaked late ones, which no fixed
         ``topk`` can; with ``topk=None`` it is the only filter."""
         B = len(text)
-        if mask_padding and context_lens is None:
+        if regions is not None:
+            if context_lens is not None or context_segments is not None or token_segments is not None:
+                raise ValueError("regions builds the context's segments itself: no context_lens, context_segments or token_segments beside it")
+            context, context_segments, token_segments = self._region_context(text, regions, mask_padding)
+        elif mask_padding and context_lens is None and context_segments is None:
             context, context_lens = self.text_model(text, return_lens=True)
         else:
             context = self.text_model(text)
@@ -733,8 +827,10 @@ class Pipeline(nn.Module):
                 negative = self.text_model(prompts)
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative, negative_context_lens,
                              timesteps)
+        segments = self._segments(context_segments, token_segments, context, context_lens, B)
         if self._on_cpu():
-            return self._generate_cpu(context, B, timesteps, temperature, opts, save_interval, seed, return_ids)
+            return self._generate_cpu(context, B, timesteps, temperature, opts, save_interval, seed, return_ids, segments)
+        seg_kw = _seg_kw(segments)
         eng = self.engine()
         if seed is None:
             seed = _draw_seed()
@@ -758,7 +854,7 @@ class Pipeline(nn.Module):
         n_dec = sum(flags)
         if keep_on_device or n_dec == 0:
             ids, imgs = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base,
-                                          use_graph=use_graph, streams=streams)
+                                          use_graph=use_graph, streams=streams, **seg_kw)
             out = [] if imgs is None else list(imgs)
             return (out, ids) if return_ids else out
         vq = self.vqgan.engine()
@@ -772,7 +868,7 @@ class Pipeline(nn.Module):
             cs.append(torch.cuda.Stream(device=eng.device))
         try:
             ids, _ = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base,
-                                       use_graph=use_graph, streams=streams, host=(host, cs))
+                                       use_graph=use_graph, streams=streams, host=(host, cs), **seg_kw)
         except BaseException:
             # a lane failed: whatever the other lanes queued may still be writing into `host`; drain it, and never hand
             # this buffer out again
@@ -790,6 +886,35 @@ class Pipeline(nn.Module):
                     pass
         out = list(host)                                     # views of one pinned buffer; it is reused once all of them are gone
         return (out, ids) if return_ids else out
+
+    def _region_context(self, text, regions, mask_padding):
+        """``generate(text, regions=)`` -> (context [B, Lmax, D], context_segments, token_segments): every prompt of every image goes
+        through the text model in ONE call; with mask_padding a prompt contributes its non-pad rows only (``region_layout``)"""
+        B = len(text)
+        if len(regions) != B:
+            raise ValueError(f"regions: {len(regions)} lists for a batch of {B}")
+        regions = [list(r) for r in regions]
+        for b, r in enumerate(regions):
+            if len(r) > MAX_REGIONS:
+                raise ValueError(f"regions: image {b}: {len(r)} regions, at most {MAX_REGIONS} per image")
+            for item in r:
+                if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], str)):
+                    raise ValueError(f"regions: image {b}: every region is a (prompt, mask) pair")
+        prompts = [p for b in range(B) for p in [text[b]] + [item[0] for item in regions[b]]]
+        if mask_padding:
+            ctx, lens = self.text_model(prompts, return_lens=True)
+            lens = ops.host_lens(lens, len(prompts), ctx.shape[1], "regions: prompt lengths")
+        else:
+            ctx = self.text_model(prompts)
+            lens = [ctx.shape[1]] * len(prompts)
+        if ctx is None:
+            raise ValueError("regions needs a text model (this pipeline is unconditional)")
+        contexts, at = [], 0
+        for b in range(B):
+            n = 1 + len(regions[b])
+            contexts.append([ctx[at + i, :lens[at + i]] for i in range(n)])
+            at += n
+        return region_layout(contexts, [[item[1] for item in r] for r in regions], self.image_size, self.patch_size)
 
     def _region_loop(self, img, coord, text, timesteps, topk, temperature, keep_inside, seed=None, return_ids=False,
                      choice_temperature=None, top_p=None):

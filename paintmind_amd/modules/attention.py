@@ -9,6 +9,7 @@ done by libpaintmind_hip.so: fused q|k|v projection with head-split epilogue, fl
 softmax(QK^T)V that never materialises the score matrix, and an out-projection with fused bias
 (+ residual when called from a Layer).
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -55,21 +56,34 @@ class CrossAttention(nn.Module):
             self._pack = (stamp, pk)
         return self._pack[1]
 
-    def forward(self, x, context=None, context_lens=None):
-        return self.run(x, context, residual=None, context_lens=context_lens)
+    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None):
+        return self.run(x, context, residual=None, context_lens=context_lens, context_segments=context_segments,
+                        token_segments=token_segments)
 
-    def run(self, x, context=None, residual=None, context_lens=None):
+    def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None):
         """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x.
         context_lens (extension; None = the reference's behaviour, no mask): one length per image -- image b attends to rows
-        [0, context_lens[b]) of its context only; the rows beyond never reach the result, NaN included."""
+        [0, context_lens[b]) of its context only; the rows beyond never reach the result, NaN included.
+        context_segments [B, L] + token_segments [B, N] (extension, regional prompts; never beside context_lens): row k of image
+        b's context belongs to segment context_segments[b, k] (0..31; -1 or 255 = padding, which never reaches the result), and
+        token t attends to the rows whose segment is a set bit of token_segments[b, t].  Every token must allow a present segment."""
         if self.training and self.to_out[1].p > 0:
             raise RuntimeError("paintmind_amd attention is inference-only (dropout>0 in training mode)")
         if context_lens is not None:
             if context is None:
                 raise ValueError("context_lens needs a context (self-attention takes no key-padding mask)")
             context_lens = ops.host_lens(context_lens, x.shape[0], context.shape[1])
+        segments = None
+        if context_segments is not None or token_segments is not None:
+            if context is None:
+                raise ValueError("context_segments / token_segments need a context (self-attention takes no mask)")
+            if context_lens is not None:
+                raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
+            segments = context_segments, token_segments
+            if not (isinstance(context_segments, np.ndarray) and context_segments.dtype == np.uint8):      # (checked already otherwise)
+                segments = ops.host_segments(context_segments, token_segments, x.shape[0], context.shape[1], x.shape[1])
         if not x.is_cuda:
-            return self._run_cpu(x, context, residual, context_lens)
+            return self._run_cpu(x, context, residual, context_lens, segments)
         B, N, D = x.shape
         dtype = x.dtype
         pk = self.packed(dtype)
@@ -88,18 +102,24 @@ class CrossAttention(nn.Module):
             k, vt = ops.gemm_heads(c, pk["wkv"], self.heads, L, [ops.PART_K, ops.PART_V], 1.0, self.dim_head)
             n_kv = L
         kv_lens = None if context_lens is None else torch.tensor(context_lens, dtype=torch.int32, device=x.device)
-        o = ops.attention(q, k, vt, n_kv, use_exp2=fast, kv_lens=kv_lens)
+        if segments is not None:
+            o = ops.attention(q, k, vt, n_kv, use_exp2=fast, key_segments=torch.from_numpy(segments[0]).to(x.device),
+                              query_segments=torch.from_numpy(segments[1].view(np.int32)).to(x.device))
+        else:
+            o = ops.attention(q, k, vt, n_kv, use_exp2=fast, kv_lens=kv_lens)
         res = residual.reshape(B * N, D) if residual is not None else None
         out_dtype = torch.float32 if residual is not None else dtype
         out = ops.gemm(o, pk["wo"], bias=pk["bo"], residual=res, out_dtype=out_dtype)
         return out.reshape(B, N, D)
 
 
-    def _run_cpu(self, x, context, residual, context_lens=None):
+    def _run_cpu(self, x, context, residual, context_lens=None, segments=None):
         """Parameters on the CPU: the same operator in plain torch (reference modules/attention.py:43-59; BASELINE config 1
         runs the model there).  q is scaled BEFORE the product (:52), no mask, softmax over the keys, head split 'b n (h d)'.
         context_lens (a checked list, or None): scores of the keys at or beyond an image's length become -inf (whatever they
-        were, NaN included) and the V rows there are ZEROED -- a probability of 0 alone would not do, 0 * NaN is NaN in P @ V."""
+        were, NaN included) and the V rows there are ZEROED -- a probability of 0 alone would not do, 0 * NaN is NaN in P @ V.
+        segments (checked numpy arrays (uint8 [B, L], uint32 [B, N]), or None): the same per QUERY -- scores of the rows a token
+        does not attend to become -inf, and the V rows of padding (segment 255) are zeroed."""
         B, N, _ = x.shape
         c = x if context is None else context
         if context_lens is not None and len(set(context_lens)) == 1:
@@ -113,6 +133,10 @@ class CrossAttention(nn.Module):
             pad = torch.arange(c.shape[1])[None, :] >= torch.tensor(context_lens)[:, None]           # [B, L]
             s = s.masked_fill(pad[:, None, None, :], float("-inf"))
             v = v.masked_fill(pad[:, None, :, None], 0.0)
+        if segments is not None:
+            allowed = torch.from_numpy(ops.segments_allowed(*segments))                               # [B, N, L]
+            s = s.masked_fill(~allowed[:, None], float("-inf"))
+            v = v.masked_fill(torch.from_numpy(segments[0] == 255)[:, None, :, None], 0.0)
         p = torch.softmax(s, dim=-1)
         o = (p @ v).permute(0, 2, 1, 3).reshape(B, N, h * d)
         out = F.linear(o, self.to_out[0].weight, self.to_out[0].bias)

@@ -6,6 +6,7 @@ function asserts its operands live on a ROCm device; nothing falls back to ATen.
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -63,6 +64,48 @@ def host_lens(lens, B, L, what="context_lens"):
             raise ValueError(f"{what}: image {b}: length {v} must be an integer in [1, {L}]")
         out.append(int(v))
     return out
+
+
+def host_segments(context_segments, token_segments, B, L, N):
+    """regional prompts: context_segments [B, L] ints (the segment 0..31 of every context row; -1 or 255 =
+    padding) and token_segments [B, N] int bitmasks (bit s = the token attends to segment s), as lists, numpy arrays, CPU or device
+    tensors; both None pass through as None.  -> (numpy uint8 [B, L] with 255 for padding, numpy uint32 [B, N]) on the host, brought
+    there ONCE per call and checked before anything is launched: ids in range, every token allows a segment present in its image."""
+    if context_segments is None and token_segments is None:
+        return None
+    if context_segments is None or token_segments is None:
+        raise ValueError("context_segments and token_segments come together")
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    cs, ts = to_np(context_segments), to_np(token_segments)
+    if cs.shape != (B, L) or cs.dtype.kind not in "iu":
+        raise ValueError(f"context_segments must be integers of shape ({B}, {L}), got {cs.dtype} {cs.shape}")
+    if ts.shape != (B, N) or ts.dtype.kind not in "iu":
+        raise ValueError(f"token_segments must be integer bitmasks of shape ({B}, {N}), got {ts.dtype} {ts.shape}")
+    cs, ts = cs.astype(np.int64), ts.astype(np.int64)
+    cs = np.where(cs == -1, 255, cs)
+    bad = np.argwhere(((cs < 0) | (cs > 31)) & (cs != 255))
+    if len(bad):
+        b, k = bad[0]
+        raise ValueError(f"context_segments: image {b}: context row {k}: segment {int(cs[b, k])} must be in 0..31, or -1 / 255 for padding")
+    bad = np.argwhere((ts < 0) | (ts >= 2 ** 32))
+    if len(bad):
+        b, t = bad[0]
+        raise ValueError(f"token_segments: image {b}: token {t}: mask {int(ts[b, t])} must be a 32-bit mask")
+    present = np.zeros(B, np.int64)
+    for b in range(B):
+        present[b] = np.bitwise_or.reduce(np.int64(1) << cs[b][cs[b] < 32]) if (cs[b] < 32).any() else 0
+    bad = np.argwhere((ts & present[:, None]) == 0)
+    if len(bad):
+        b, t = bad[0]
+        raise ValueError(f"token_segments: image {b}: token {t} allows no segment that is present in its context "
+                         f"(mask {int(ts[b, t]):#x}, present {int(present[b]):#x})")
+    return np.ascontiguousarray(cs.astype(np.uint8)), np.ascontiguousarray(ts.astype(np.uint32))
+
+
+def segments_allowed(key_seg, query_mask):
+    """numpy uint8 [B, L], uint32 [B, N] -> bool [B, N, L]: row k takes part in token t's softmax (the rule of pmhip_attention_segments)"""
+    ks = key_seg.astype(np.int64)[:, None, :]
+    return (ks < 32) & (((query_mask.astype(np.int64)[:, :, None] >> np.minimum(ks, 31)) & 1) != 0)
 
 
 def swiglu_hidden(hidden_features):
@@ -337,19 +380,38 @@ def attention_fallbacks(reset=False, device=None):
     return int(n.value)
 
 
-def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None):
+def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None):
     """q [B,H,Nq,dh], k [B,H,Nkp,dh], vt [B,H,dh,Nkp] -> [B*Nq, H*dh]  (dh 64: tuned MFMA kernel; else pmhip_attention_dh).
     kv_lens (None: every image attends to n_kv keys): int32 [B] on the device, image b attends to its first kv_lens[b] keys
-    (clamped to [1, n_kv] by the kernel) -- pmhip_attention_lens."""
-    dev = _dev(q, k, vt, kv_lens)
+    (clamped to [1, n_kv] by the kernel) -- pmhip_attention_lens.
+    key_segments uint8 [B, n_kv] + query_segments int32 / uint32 [B, Nq] (bit masks), both on the device and never beside kv_lens:
+    key j takes part in query i's softmax iff key_segments[b, j] < 32 and bit key_segments[b, j] of query_segments[b, i] is set; 255
+    marks padding, whose K rows and V^T columns never reach a result -- pmhip_attention_segments.  Every query must allow a key."""
+    dev = _dev(q, k, vt, kv_lens, key_segments, query_segments)
     lib = _lib.load()
     B, H, Nq, dh = q.shape
     nkp = k.shape[2]
     out = torch.empty(B * Nq, H * dh, device=dev, dtype=q.dtype)
     if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
         raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
-    with torch.cuda.device(dev):
+    if (key_segments is None) != (query_segments is None):
+        raise ValueError("key_segments and query_segments come together")
+    if key_segments is not None:
         if kv_lens is not None:
+            raise ValueError("key_segments / query_segments and kv_lens exclude each other (mark padding keys with segment 255)")
+        if key_segments.dtype != torch.uint8 or tuple(key_segments.shape) != (B, n_kv) or not key_segments.is_contiguous():
+            raise ValueError(f"key_segments must be a contiguous uint8 tensor of shape ({B}, {n_kv}), got {key_segments.dtype} "
+                             f"{tuple(key_segments.shape)}")
+        if query_segments.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(query_segments.shape) != (B, Nq) or \
+                not query_segments.is_contiguous():
+            raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
+                             f"{tuple(query_segments.shape)}")
+    with torch.cuda.device(dev):
+        if key_segments is not None:
+            check(lib.pmhip_attention_segments(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * dh, B, H, dh, Nq, n_kv, nkp,
+                                               int(use_exp2), _p(key_segments), _p(query_segments), stream_ptr(dev)),
+                  "pmhip_attention_segments")
+        elif kv_lens is not None:
             check(lib.pmhip_attention_lens(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * dh, B, H, dh, Nq, n_kv, nkp,
                                            int(use_exp2), _p(kv_lens), stream_ptr(dev)), "pmhip_attention_lens")
         elif dh == 64:

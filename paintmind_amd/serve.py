@@ -84,6 +84,11 @@ from . import _lib, ops
 Finished = collections.namedtuple("Finished", ["handle", "image", "ids"])
 
 
+def _no_regions(regions):
+    if regions is not None:
+        raise ValueError("a decode session serves no regional prompts (regions=): Pipeline.generate(regions=) does")
+
+
 class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
@@ -151,7 +156,7 @@ class DecodeSession:
     # -- requests -----------------------------------------------------------------------------------
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
                guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None, keep_given=False, image=None,
-               mask=None, token_mask=None, preserve="tokens"):
+               mask=None, token_mask=None, preserve="tokens", regions=None):
         """queue one request (any time, also between steps) -> its Request.  `context` [L_r, D] may be given instead of `text`
         (a conditional session runs the pipeline's text model on `text` otherwise), with its OWN length L_r: the request attends
         to exactly these rows; `ids0` [N]: start ids instead of all-mask;
@@ -167,7 +172,9 @@ class DecodeSession:
         from the merged ids (``Pipeline.edit`` for one request).
         `image` [C,H,W] with exactly one of `mask` [H,W] (pixels, non-zero = regenerate) / `token_mask` bool [g,g]: the same edit
         from an image -- it is encoded and masked here, at submit -- and `preserve` ("tokens" | "pixels"): "pixels" puts the original
-        pixels back outside the pixel mask, as in ``Pipeline.edit``."""
+        pixels back outside the pixel mask, as in ``Pipeline.edit``.
+        `regions`: refused -- regional prompts are served by ``Pipeline.generate(regions=)`` only."""
+        _no_regions(regions)
         return self._submit(text, timesteps, temperature, topk, None, seed, image_index, context, ids0, guidance_scale, choice_temperature,
                             negative_text, negative_context, keep_given, image, mask, token_mask, preserve)
 
@@ -483,10 +490,11 @@ class FilterSession(DecodeSession):
 
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
                guidance_scale=None, choice_temperature=None, negative_text=None, negative_context=None, top_p=None, keep_given=False,
-               image=None, mask=None, token_mask=None, preserve="tokens"):
+               image=None, mask=None, token_mask=None, preserve="tokens", regions=None):
         """DecodeSession.submit with `topk` in 1..n_embed, or None for no filter (stored as n_embed), and `top_p` (None or 1 = no
         nucleus filter; else finite, 0 < top_p < 1): of the request's top-k classes only those whose mass strictly above them is
         below top_p of the top-k's mass are drawn from, like ``Pipeline.generate(top_p=)``.  Out of range: ValueError, here."""
+        _no_regions(regions)
         return self._submit(text, timesteps, temperature, topk, top_p, seed, image_index, context, ids0, guidance_scale, choice_temperature,
                             negative_text, negative_context, keep_given, image, mask, token_mask, preserve)
 

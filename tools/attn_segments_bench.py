@@ -1,0 +1,45 @@
+"""Segmented cross-attention against the per-image-length form and the unmasked entry at a regional-prompts shape (default
+B=64, H=12, Nq=1024, Nkv=231 = a global prompt and two regions of 77 rows, dh=64): microseconds per launch by hipEvents, bf16
+(exp2) and fp32.  A measurement for DESIGN.md section 4u, no gate.  Layout of the masks: rows [0,77) segment 0 (global), [77,154)
+segment 1, [154,231) segment 2; the left half of a 32 x 32 token grid attends to segments 0 and 1, the right half to 0 and 2."""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from paintmind_amd import ops
+
+dev = torch.device("cuda:0")
+B, H, NQ, NKV = (int(x) for x in (sys.argv[1:5] if len(sys.argv) > 4 else (64, 12, 1024, 231)))
+NKP = -(-NKV // 64) * 64
+g = torch.Generator().manual_seed(0)
+ks = (torch.arange(NKV) // -(-NKV // 3)).to(torch.uint8)[None].expand(B, NKV).contiguous().to(dev)
+side = int(NQ ** 0.5) or 1
+right = ((torch.arange(NQ) % side) >= side // 2).to(torch.int32)
+qm = (1 | (2 << right))[None].expand(B, NQ).contiguous().to(dev)
+lens = torch.full((B,), NKV, dtype=torch.int32, device=dev)
+
+
+def timed(fn, reps=50):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3
+
+
+for dtype, exp2 in ((torch.bfloat16, True), (torch.float32, False)):
+    q = ((torch.rand(B, H, NQ, 64, generator=g) * 2 - 1) * 0.5).to(dev).to(dtype)
+    k = (torch.rand(B, H, NKP, 64, generator=g) * 2 - 1).to(dev).to(dtype)
+    vt = (torch.rand(B, H, 64, NKP, generator=g) * 2 - 1).to(dev).to(dtype)
+    plain = timed(lambda: ops.attention(q, k, vt, NKV, use_exp2=exp2))
+    per_image = timed(lambda: ops.attention(q, k, vt, NKV, use_exp2=exp2, kv_lens=lens))
+    seg = timed(lambda: ops.attention(q, k, vt, NKV, use_exp2=exp2, key_segments=ks, query_segments=qm))
+    print(f"{dtype} B={B} H={H} Nq={NQ} Nkv={NKV}: unmasked {plain:.1f} us, lens {per_image:.1f} us, segments {seg:.1f} us "
+          f"({seg / per_image:.2f} x lens)")
