@@ -245,6 +245,22 @@ int pmhip_attention_segments(int dtype, const void* Q, const void* K, const void
                              int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
                              const uint32_t* query_mask, pmhip_stream stream);
 
+/* pmhip_attention_lens or pmhip_attention_segments for SOME images of the batch (regional prompts per slot; new entry within ABI
+ * 11, nothing existing changes meaning):
+ *   pick DEVICE uint8 [B]: the kind of every image;  want: the kind this launch serves (0..255)
+ * Exactly one of kv_lens, or the pair key_seg + query_mask, is non-NULL and selects the form; the other arguments are those of the
+ * entry it selects.  A workgroup of an image with pick[b] != want returns at once: it reads nothing of that image's Q, K, V^T,
+ * length or segments (NaN there reaches nothing) and leaves EVERY byte of that image's rows of `out` as it found it.  An image
+ * with pick[b] == want gets, bit for bit, the rows pmhip_attention_lens / pmhip_attention_segments writes for it on the same
+ * inputs: same kernel text, same launch geometry, and the workgroup size chosen from B, heads and Nq only -- never from `pick` --,
+ * so what an image computes does not depend on which images a launch serves.  Two launches, one per kind, fill one buffer.
+ * A skipped image never counts in pmhip_attention_fallbacks; a served one of the kv_lens form takes the lagged-max fast path and
+ * its exact re-run exactly as in pmhip_attention_lens.  pick NULL, both forms or none, or one of key_seg / query_mask without
+ * the other: PMHIP_EINVAL. */
+int pmhip_attention_pick(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                         int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens, const uint8_t* key_seg,
+                         const uint32_t* query_mask, const uint8_t* pick, int want, pmhip_stream stream);
+
 /* torch.nn.LayerNorm over the last dim, eps inside the sqrt (stage1/layers.py:49,51,89,128;
  * stage2/transformer.py:37,39,41,62).  x fp32 [M,D] -> out (`out_dtype`). */
 int pmhip_layernorm(const float* x, const float* gamma, const float* beta, float eps, void* out,
@@ -918,6 +934,40 @@ int pmhip_pipeline_step_slots_edit(pmhip_s2* s2, int64_t* ids, const float* cont
  * the step of the entry above).  The pointer may be NULL.  Every step of this entry is also counted by
  * pmhip_s2_slots_filter_steps, by the form of its sampling tail. */
 int pmhip_s2_slots_edit_steps(const pmhip_s2* h, int* steps);
+
+/* REGIONAL PROMPTS IN A SLOTS STEP (new entries within ABI 11): pmhip_pipeline_step_slots_edit with three
+ * HOST arrays in front of `flags`, all NULL or none:
+ *   ctx_seg_host  uint8  [B, L]     : the segment 0..31 of context row k of slot b, or 255 = padding
+ *   tok_seg_host  uint32 [B, tokens]: bit s set = the token attends to the rows of segment s
+ *   region_host   uint8  [B]        : 1 = slot b is regional, 0 = it is not
+ * An active slot with region_host[b] == 1 runs the cross-attention of the pass WITH the context under its key sets, exactly as
+ * pmhip_pipeline_sample_segments does for that image; its ctx_lens_host[b] is not used (the padding value subsumes the length).
+ * An active slot with region_host[b] == 0 runs under ctx_lens_host[b] (L where ctx_lens_host is NULL), as through the entry above,
+ * and its rows of the two segment arrays are not looked at.  Idle slots count as 0.  The pass without a context and the pass
+ * against the negative context never see segments.  Either kind of slot computes the same bits whatever shares the batch.
+ * Validated before anything is staged or launched (PMHIP_EINVAL, ids untouched), for ACTIVE slots: region_host[b] in {0, 1};
+ * for a regional slot the rules of the *_segments entries -- every segment id in 0..31 or 255 (the message names the slot and
+ * the row), every token allows a segment that is PRESENT in its slot (the message names the slot and the token), a context is
+ * required, given or kept; every other slot keeps the length check of the entry above.
+ * The arrays NULL, or no ACTIVE slot regional: the call runs exactly pmhip_pipeline_step_slots_edit -- the same launches, the
+ * same graph key, the same captured graph.  Otherwise every layer's cross-attention of the pass with the context is two launches
+ * of pmhip_attention_pick into the same buffer, first the per-image-length form with want = 0, then the per-query form with want
+ * = 1; the arrays and the flags travel like the lengths (pinned ring entry -> copy kernel -> handle-owned device arrays), and
+ * everything else of the step is unchanged.  PMHIP_SLOTS_KEEP_CONTEXT keeps the cross K/V only: every call brings its own
+ * arrays, as with the lengths.  With PMHIP_SLOTS_GRAPH this form has one further graph key, and as the captured graph bakes in
+ * the device arrays, not their contents, one graph per (B, L, pass set, ...) serves every mix of regional and plain slots and
+ * every layout. */
+int pmhip_pipeline_step_slots_regions(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                      const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
+                                      const pmhip_slot_guide* guides_host, const float* choice_host /* [B] or NULL */,
+                                      const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                      const int32_t* neg_lens_host /* [B] or NULL */, const float* top_p_host /* [B] or NULL */,
+                                      const int32_t* counts_host /* [B] or NULL */, const uint8_t* ctx_seg_host,
+                                      const uint32_t* tok_seg_host, const uint8_t* region_host, int flags, int64_t* pred_out,
+                                      float* score_out, pmhip_stream stream);
+/* Steps pmhip_pipeline_step_slots_regions ran on this handle with the two-launch cross-attention (an active slot was regional;
+ * the others ran the step of the entry above).  The pointer may be NULL. */
+int pmhip_s2_slots_region_steps(const pmhip_s2* h, int* steps);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

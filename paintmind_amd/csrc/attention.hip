@@ -94,6 +94,24 @@ __device__ __forceinline__ void zero_ragged_v(unsigned char* Vl, int kv0, int Nk
 #undef PM_ATTN_KERNEL
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
+// the picked forms: the per-image and the per-query form again, each with `pick` (device uint8 [B]) and `want` --
+// a workgroup whose image has pick[b] != want returns at once, every other one runs its twin's text
+#define PM_ATTN_KERNEL attention_lens_pick_kernel
+#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_LENS 1
+#define PM_ATTN_PICK 1
+#include "attention_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_LENS
+#define PM_ATTN_KERNEL attention_seg_pick_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_SEG 1
+#include "attention_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_PICK
 
 }  // namespace
 
@@ -115,4 +133,21 @@ void pm_attention_f32(const void* Q, const void* K, const void* Vt, void* out, i
     };
     if (use_exp2) launch(attention_kernel<true, QF>, attention_lens_kernel<true, QF>);
     else launch(attention_kernel<false, QF>, attention_lens_kernel<false, QF>);
+}
+
+// The picked forms, a launcher of their own so that the one above keeps its text: exactly one of lens / seg is given,
+// the grid and the workgroup are those of the twin.
+void pm_attention_f32_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                           int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s) {
+    constexpr int QF = 2;
+    const int nqb = ceil_div(Nq, 4 * QF * 16);
+    if (seg) {
+        auto k = use_exp2 ? attention_seg_pick_kernel<true, QF> : attention_seg_pick_kernel<false, QF>;
+        hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
+                           Nq, Nkv, Nkv_pad, nqb, seg->key_seg, seg->query_mask, pk.pick, pk.want);
+        return;
+    }
+    auto k = use_exp2 ? attention_lens_pick_kernel<true, QF> : attention_lens_pick_kernel<false, QF>;
+    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
+                       Nq, Nkv, Nkv_pad, nqb, lens, pk.pick, pk.want);
 }

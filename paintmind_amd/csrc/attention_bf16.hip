@@ -132,6 +132,24 @@ __device__ __forceinline__ f32x4_t mma(const v4u_t& rows, const v4u_t& cols, con
 #undef PM_ATTN_KERNEL
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
+// the picked forms: the per-image and the per-query form again, each with `pick` (device uint8 [B]) and `want` --
+// a workgroup whose image has pick[b] != want returns at once, every other one runs its twin's text
+#define PM_ATTN_KERNEL attention_bf16_lens_pick_kernel
+#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_LENS 1
+#define PM_ATTN_PICK 1
+#include "attention_bf16_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_LENS
+#define PM_ATTN_KERNEL attention_bf16_seg_pick_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_SEG 1
+#include "attention_bf16_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_PICK
 
 #undef DSRX
 #undef LGKM4
@@ -156,6 +174,24 @@ static void launch_seg_qf(const void* Q, const void* K, const void* Vt, void* ou
     auto k = use_exp2 ? attention_bf16_seg_kernel<true, QF> : attention_bf16_seg_kernel<false, QF>;
     hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
                        Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask);
+}
+
+// the picked forms: exactly one of lens / seg, the geometry of the twin
+template <int QF>
+static void launch_pick_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
+                           int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s) {
+    const int nqb = ceil_div(Nq, 4 * QF * 16);
+    if constexpr (QF <= 2) {
+        if (seg) {
+            auto k = use_exp2 ? attention_bf16_seg_pick_kernel<true, QF> : attention_bf16_seg_pick_kernel<false, QF>;
+            hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo,
+                               heads, Nq, Nkv, Nkv_pad, nqb, seg->key_seg, seg->query_mask, pk.pick, pk.want);
+            return;
+        }
+    }
+    auto k = use_exp2 ? attention_bf16_lens_pick_kernel<true, QF> : attention_bf16_lens_pick_kernel<false, QF>;
+    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
+                       Nq, Nkv, Nkv_pad, nqb, lens, pk.pick, pk.want);
 }
 
 }  // namespace
@@ -187,4 +223,15 @@ void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* o
                            int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s) {
     if ((long long)B * heads * ceil_div(Nq, 128) >= 512) launch_seg_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
     else launch_seg_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
+}
+
+// The picked forms: the rule of the twin, from B, heads and Nq only -- never from `pick` --, so an image's bits do not
+// depend on which images a launch serves.  lens: 256 / 128 / 64 queries per workgroup as pm_attention_bf16 (PM_ATTN_FORCE_QF builds
+// do not reach this launcher); seg: 128 / 64 as pm_attention_bf16_seg.
+void pm_attention_bf16_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                            int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s) {
+    const long long bh = (long long)B * heads;
+    if (!seg && bh * ceil_div(Nq, 256) >= 512) launch_pick_qf<4>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
+    else if (bh * ceil_div(Nq, 128) >= 512) launch_pick_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
+    else launch_pick_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
 }

@@ -1,4 +1,4 @@
-// The bf16 attention kernel of attention_bf16.hip, which includes this file THREE TIMES (no include guard on purpose):
+// The bf16 attention kernel of attention_bf16.hip, which includes this file FIVE TIMES (no include guard on purpose):
 //   PM_ATTN_KERNEL = attention_bf16_kernel,      PM_ATTN_LENS_PARAM empty          one key count for the launch (Nkv)
 //   PM_ATTN_KERNEL = attention_bf16_lens_kernel, PM_ATTN_LENS_PARAM = ", lens"     PM_ATTN_LENS defined: the key count is per IMAGE --
 //       lens[b] (device int32 [B]), read once per workgroup into a scalar and clamped to [1, Nkv]; Nkv stays the launch-wide
@@ -10,6 +10,10 @@
 //       query_mask[b, q] (device uint32 [B, Nq]) the segments a query attends to.  Every half-tile takes the exact path: the mask
 //       sits where the ragged-tile mask sets scores to -inf, the V^T columns of padding keys are zeroed in every tile, and the
 //       running max of a query that has not met an allowed key yet stays "none" (negm 0, l 0) instead of -inf.
+//   PM_ATTN_KERNEL = attention_bf16_lens_pick_kernel / attention_bf16_seg_pick_kernel: the second and the third form again with
+//       PM_ATTN_PICK defined and two more parameters ", pick, want" (DESIGN.md section 4v).  pick (device uint8 [B]) names the kind
+//       of every image; a workgroup whose image has pick[b] != want returns at once and leaves the image's output rows as they
+//       are, every other workgroup runs its twin's text.  Two launches, one per kind, fill one output buffer.
 // A compile-time variant by TEXT, not by a template parameter or an inlined body function: the first form is then the kernel the
 // library had before the second existed, token for token -- same symbol, same instruction stream, same registers (a shared
 // __device__ body, even force-inlined, was measured to move the schedule of every instantiation).
@@ -39,6 +43,11 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
     }
     const int b = bh / heads, h = bh % heads;
     const int q0 = qblk * (4 * QF * 16) + wave * (QF * 16);
+#ifdef PM_ATTN_PICK
+    // the picked form: a workgroup whose image is not the launch's kind is done here, before any LDS write, DMA
+    // request, barrier or store -- workgroup-uniform (b is, and the flag goes through a scalar), so no wave is left at a barrier
+    if (__builtin_amdgcn_readfirstlane((int)pick[b]) != want) return;
+#endif
 #ifdef PM_ATTN_LENS
     {                                                        // workgroup-uniform: this image's key count
         const int n = __builtin_amdgcn_readfirstlane(lens[b]);

@@ -4,6 +4,8 @@
 // A THIRD inclusion with PM_ATTN_SEG (attention_seg_kernel; parameters key_seg, query_mask) is the per-query key set of DESIGN.md 4u:
 // scores of denied keys become -inf in every half-tile, the V^T columns of padding keys (segment 255) are zeroed in every tile, the
 // running max is raised at every half-tile (no deferred rescale), and a query that has met no allowed key yet keeps negm = 0.
+// A FOURTH and a FIFTH inclusion with PM_ATTN_PICK beside PM_ATTN_LENS / PM_ATTN_SEG (attention_lens_pick_kernel, attention_seg_pick_kernel;
+// two more parameters pick, want) are the picked forms of DESIGN.md 4v: a workgroup whose image has pick[b] != want returns at once.
 template <bool EXP2, int QF>
 __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __restrict__ Q, const float* __restrict__ Kp,
                                                             const float* __restrict__ Vt, float* __restrict__ out,
@@ -33,6 +35,11 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
     }
     const int b = bh / heads, h = bh % heads;
     const int q0 = qblk * (4 * QF * 16) + wave * (QF * 16);
+#ifdef PM_ATTN_PICK
+    // the picked form: a workgroup whose image is not the launch's kind is done here, before any LDS write, DMA
+    // request, barrier or store -- workgroup-uniform (b is, and the flag goes through a scalar), so no wave is left at a barrier
+    if (__builtin_amdgcn_readfirstlane((int)pick[b]) != want) return;
+#endif
 #ifdef PM_ATTN_LENS
     {                                                        // workgroup-uniform: this image's key count
         const int n = __builtin_amdgcn_readfirstlane(lens[b]);

@@ -9,7 +9,7 @@
 //                walk the keys in the same order, so K / V^T addresses are wave-uniform per quad position and come out of
 //                L1/L2 as broadcasts.  The score matrix is never materialised.
 //
-// The attention entry points of the C ABI (pmhip_attention, pmhip_attention_dh, pmhip_attention_lens, pmhip_attention_segments) are at the end of this file:
+// The attention entry points of the C ABI (pmhip_attention, pmhip_attention_dh, pmhip_attention_lens, pmhip_attention_segments, pmhip_attention_pick) are at the end of this file:
 // one argument check for the family, then the launcher of attention.hip, attention_bf16.hip or this file.
 #include "common.h"
 
@@ -71,10 +71,41 @@ __device__ __forceinline__ float quad_sum(float v) {
 #undef PM_ATTN_KERNEL
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
+// the picked forms: the per-image and the per-query form again, each with `pick` (device uint8 [B]) and `want` --
+// a workgroup whose image has pick[b] != want returns at once, every other one runs its twin's text
+#define PM_ATTN_KERNEL attention_dh_lens_pick_kernel
+#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_LENS 1
+#define PM_ATTN_PICK 1
+#include "attention_dh_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_LENS
+#define PM_ATTN_KERNEL attention_dh_seg_pick_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_SEG 1
+#include "attention_dh_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_PICK
 
 template <typename T, int DPL>
 void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-               int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s) {
+               int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, hipStream_t s) {
+    if (pk) {                                          // the picked forms: exactly one of lens / seg, the geometry of the twin
+        const dim3 grid((Nq + 63) / 64, B * heads);
+        if (seg) {
+            auto k = use_exp2 ? attention_dh_seg_pick_kernel<T, DPL, true> : attention_dh_seg_pick_kernel<T, DPL, false>;
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq, Nkv, Nkp, seg->key_seg,
+                               seg->query_mask, pk->pick, pk->want);
+        } else {
+            auto k = use_exp2 ? attention_dh_lens_pick_kernel<T, DPL, true> : attention_dh_lens_pick_kernel<T, DPL, false>;
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq, Nkv, Nkp, lens, pk->pick,
+                               pk->want);
+        }
+        return;
+    }
     if (seg) {
         auto k = use_exp2 ? attention_dh_seg_kernel<T, DPL, true> : attention_dh_seg_kernel<T, DPL, false>;
         hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
@@ -92,9 +123,9 @@ void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo,
 // the launcher of this file's kernels: dim_head != 64, already passed through check_dh
 template <typename T>
 int pm_attention_dh(int dh, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-                    int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s) {
+                    int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, hipStream_t s) {
     switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, seg, s); break;
+#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, seg, pk, s); break;
         PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
 #undef PM_DH_CASE
         default: PM_REQUIRE(false, "attention_dh: dim_head=%d not served", dh);
@@ -147,12 +178,17 @@ void pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, 
                        int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
 void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
                            int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s);
+void pm_attention_f32_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                           int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s);
+void pm_attention_bf16_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                            int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s);
 
 // Every attention entry point ends here: the arguments are checked once, then one launcher per kernel file.  lens = device
-// int32 [B], the per-image key counts, or NULL (one key count for the launch); seg = the per-query key sets (device arrays), or NULL.
+// int32 [B], the per-image key counts, or NULL (one key count for the launch); seg = the per-query key sets (device arrays), or NULL;
+// pk = the picked forms (exactly one of lens / seg beside it), or NULL.
 static int attention_any(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                          int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s,
-                         const PmAttnSeg* seg = nullptr) {
+                         const PmAttnSeg* seg = nullptr, const PmAttnPick* pk = nullptr) {
     const bool tuned = dim_head == 64;               // the MFMA kernels; otherwise this file's plain path
     if (!tuned) PM_TRY(check_dh(who, heads, dim_head));
     PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "%s: bad dtype %d", who, dtype);
@@ -168,8 +204,11 @@ static int attention_any(const char* who, int dtype, const void* Q, const void* 
     if (!tuned) PM_REQUIRE((long long)B * heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)B * heads);
     PmTimer tm(FAM_ATTENTION, s);
     if (!tuned) {
-        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, s));
-        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, s));
+        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s));
+        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s));
+    } else if (pk) {
+        if (dtype == PMHIP_F32) pm_attention_f32_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, *pk, s);
+        else pm_attention_bf16_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, *pk, s);
     } else if (dtype == PMHIP_F32) {
         pm_attention_f32(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, s);
     } else {
@@ -206,4 +245,18 @@ extern "C" int pmhip_attention_segments(int dtype, const void* Q, const void* K,
     const PmAttnSeg seg{key_seg, query_mask};
     return attention_any("attention_segments", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
                          (hipStream_t)stream, &seg);
+}
+
+extern "C" int pmhip_attention_pick(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                                    int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens,
+                                    const uint8_t* key_seg, const uint32_t* query_mask, const uint8_t* pick, int want,
+                                    pmhip_stream stream) {
+    PM_REQUIRE(pick, "attention_pick: pick is NULL (pmhip_attention_lens / pmhip_attention_segments are the entries that serve every image)");
+    PM_REQUIRE(!key_seg == !query_mask, "attention_pick: key_seg and query_mask go together");
+    PM_REQUIRE(!kv_lens != !key_seg, "attention_pick: exactly one of kv_lens and the pair key_seg + query_mask selects the form");
+    PM_REQUIRE(want >= 0 && want <= 255, "attention_pick: want=%d is no value of a uint8 pick", want);
+    const PmAttnSeg seg{key_seg, query_mask};
+    const PmAttnPick pk{pick, want};
+    return attention_any("attention_pick", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, kv_lens,
+                         (hipStream_t)stream, key_seg ? &seg : nullptr, &pk);
 }

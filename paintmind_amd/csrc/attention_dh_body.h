@@ -3,11 +3,18 @@
 // PM_ATTN_LENS_PARAM is empty or ", const int* lens", and with PM_ATTN_LENS the loop bound is lens[b], clamped to [1, Nkv].
 // A THIRD inclusion with PM_ATTN_SEG (attention_dh_seg_kernel; parameters key_seg, query_mask) is the per-query key set of DESIGN.md
 // 4u: a key whose segment the query does not attend to (or padding, 255) is skipped -- its score and its V column are read by no update.
+// A FOURTH and a FIFTH inclusion with PM_ATTN_PICK beside PM_ATTN_LENS / PM_ATTN_SEG (attention_dh_lens_pick_kernel,
+// attention_dh_seg_pick_kernel; two more parameters pick, want) are the picked forms of DESIGN.md 4v.
 template <typename T, int DPL, bool EXP2>
 __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ Vt,
                                                           T* __restrict__ out, int ldo, int heads, int Nq, int Nkv, int Nkp PM_ATTN_LENS_PARAM) {
     constexpr int DH = DPL * 4;
     const int bh = blockIdx.y, b = bh / heads, h = bh % heads;
+#ifdef PM_ATTN_PICK
+    // the picked form: a workgroup whose image is not the launch's kind is done here, before any load of the image's
+    // rows and any store (workgroup-uniform: b is, and the flag goes through a scalar)
+    if (__builtin_amdgcn_readfirstlane((int)pick[b]) != want) return;
+#endif
 #ifdef PM_ATTN_LENS
     {                                                           // workgroup-uniform: this image's key count
         const int n = __builtin_amdgcn_readfirstlane(lens[b]);

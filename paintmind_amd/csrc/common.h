@@ -420,6 +420,13 @@ struct PmAttnSeg {
     const unsigned* query_mask;
 };
 
+// The picked forms: pick device uint8 [B], the kind of every image; a launch serves the images with pick[b] == want
+// and leaves the output rows of the others untouched.
+struct PmAttnPick {
+    const unsigned char* pick;
+    int want;
+};
+
 // Can a LayerNorm over K columns be folded into the GEMM out[M,N] = A[M,K] (row stride lda) . W[N,K]^T (row stride ldw)?  THE
 // predicate: the engine's decision (M = one image's rows: folded or not must not depend on the batch), the GEMM entry points'
 // check and pmhip_lnfold_supported all ask it.  M, N whole 256x256 tiles, K whole pairs of K-tiles, and both operands within the

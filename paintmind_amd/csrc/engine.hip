@@ -197,9 +197,12 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     int L = 0, Lp = 0;
     const int32_t* lens = nullptr;   // device [B]: per-image key counts of THIS call (NULL: every image attends to all L rows)
     // regional prompts, THIS call's or NULL: device uint8 [B, L], the segment of every context row (255 = padding),
-    // and device uint32 [B, tokens], the segments every token attends to.  Never beside `lens`.
+    // and device uint32 [B, tokens], the segments every token attends to.  Never beside `lens`, except with `pick`.
     const uint8_t* key_seg = nullptr;
     const uint32_t* query_mask = nullptr;
+    // a slots step with regional and plain slots side by side, THIS call's or NULL: device uint8 [B], 1 = the image
+    // runs under its key sets, 0 = under its length.  Only then `lens` and the segments stand side by side: two picked launches.
+    const uint8_t* pick = nullptr;
 };
 
 // The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
@@ -442,7 +445,14 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 1, kind_q,
                             outs, q_scale, s));
             // the one launch that sees per-image context lengths (self-attention and the unconditional pass never do)
-            if (cross->key_seg)
+            if (cross->pick) {
+                // two launches into one buffer: the plain images under their lengths, then the regional ones under
+                // their key sets; each launch leaves the other kind's rows as they are
+                PM_TRY(pmhip_attention_pick(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
+                                            cross->lens, nullptr, nullptr, cross->pick, 0, s));
+                PM_TRY(pmhip_attention_pick(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
+                                            nullptr, cross->key_seg, cross->query_mask, cross->pick, 1, s));
+            } else if (cross->key_seg)
                 PM_TRY(pmhip_attention_segments(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
                                                 cross->key_seg, cross->query_mask, s));
             else if (cross->lens)
@@ -785,6 +795,7 @@ struct pmhip_s2 {
     PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
     int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
     int slots_filter_tiles = 0, slots_filter_chain = 0;   // steps of pmhip_pipeline_step_slots_filter by the form of their sampling tail
+    int slots_region_steps = 0;                           // steps of pmhip_pipeline_step_slots_regions that ran the two-launch cross-attention
     int slots_edit_steps = 0;                             // steps of pmhip_pipeline_step_slots_edit that re-masked by a count per slot
     int slots_ctx_B = 0, slots_ctx_L = -1;
     int slots_neg_B = 0, slots_neg_Ln = -1;
@@ -883,7 +894,7 @@ int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStrea
         const unsigned char* wkv = reinterpret_cast<const unsigned char*>(h->layers[l].wqkv2) + (size_t)inner * dim * es;
         PM_TRY(pmhip_gemm_heads_dh(h->dtype, cp, dim, wkv, dim, Mc, dim, heads, dh, L, Lp, 2, kinds, outs, 1.0f, split, s));
         cs.kv[l].k = outs[0]; cs.kv[l].vt = outs[1]; cs.kv[l].L = L; cs.kv[l].Lp = Lp; cs.kv[l].lens = nullptr;
-        cs.kv[l].key_seg = nullptr; cs.kv[l].query_mask = nullptr;
+        cs.kv[l].key_seg = nullptr; cs.kv[l].query_mask = nullptr; cs.kv[l].pick = nullptr;
     }
     return PMHIP_OK;
 }
@@ -918,7 +929,24 @@ int s2_set_ctx_lens(pmhip_s2* h, const int32_t* lens_host, int L, int B, hipStre
     for (auto& ck : cs.kv) {
         ck.lens = ck.k ? dlens : nullptr;
         ck.key_seg = nullptr; ck.query_mask = nullptr;        // the segments of an earlier call are dropped with its lengths
+        ck.pick = nullptr;
     }
+    return PMHIP_OK;
+}
+
+// One image's rows of the two arrays: every id in 0..31 or 255, every token allowing a segment that is present.  `noun` is what the
+// messages call b: "image" in the *_segments entries, "slot" in a slots step (pmhip_pipeline_step_slots_regions).
+int check_segments_of(const char* who, const char* noun, int b, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, int L, int tokens) {
+    uint32_t present = 0;
+    for (int k = 0; k < L; ++k) {
+        const int sg = ctx_seg_host[(size_t)b * L + k];
+        PM_REQUIRE(sg < 32 || sg == 255, "%s: %s %d: context row %d: segment %d must be in 0..31, or 255 for padding", who, noun, b, k, sg);
+        if (sg < 32) present |= 1u << sg;
+    }
+    for (int t = 0; t < tokens; ++t)
+        PM_REQUIRE(tok_seg_host[(size_t)b * tokens + t] & present,
+                   "%s: %s %d: token %d allows no segment that is present in its context (mask 0x%08x, present 0x%08x)", who, noun, b, t,
+                   (unsigned)tok_seg_host[(size_t)b * tokens + t], (unsigned)present);
     return PMHIP_OK;
 }
 
@@ -933,18 +961,7 @@ int check_segments(const char* who, const uint8_t* ctx_seg_host, const uint32_t*
     PM_REQUIRE(have_context && L > 0, "%s: segments given without a context", who);
     PM_REQUIRE(!ctx_lens_host, "%s: segments and ctx_lens_host exclude each other (mark padding rows with segment 255)", who);
     const int tokens = h->cfg.tokens;                         // (the handle is read only once the arrays are known to be there)
-    for (int b = 0; b < B; ++b) {
-        uint32_t present = 0;
-        for (int k = 0; k < L; ++k) {
-            const int sg = ctx_seg_host[(size_t)b * L + k];
-            PM_REQUIRE(sg < 32 || sg == 255, "%s: image %d: context row %d: segment %d must be in 0..31, or 255 for padding", who, b, k, sg);
-            if (sg < 32) present |= 1u << sg;
-        }
-        for (int t = 0; t < tokens; ++t)
-            PM_REQUIRE(tok_seg_host[(size_t)b * tokens + t] & present,
-                       "%s: image %d: token %d allows no segment that is present in its context (mask 0x%08x, present 0x%08x)", who, b, t,
-                       (unsigned)tok_seg_host[(size_t)b * tokens + t], (unsigned)present);
-    }
+    for (int b = 0; b < B; ++b) PM_TRY(check_segments_of(who, "image", b, ctx_seg_host, tok_seg_host, L, tokens));
     return PMHIP_OK;
 }
 
@@ -952,20 +969,31 @@ int check_segments(const char* who, const uint8_t* ctx_seg_host, const uint32_t*
 // copy kernel -> the handle's device array "ctx.seg" -> every layer's CrossKV of the context's set, from where the cross-attention
 // launch of layer_forward hands them to pmhip_attention_segments.  Called right behind s2_set_ctx_lens (which drops the segments of
 // an earlier call), always outside a graph: a captured graph bakes in the device array, never a layout of regions.
-int s2_set_segments(pmhip_s2* h, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, int L, int B, hipStream_t s) {
+// region_host (a slots step of pmhip_pipeline_step_slots_regions; NULL otherwise): the B flags ride in the same ring entry, behind the
+// row segments, into a device array of their own ("ctx.pick"), and the CrossKV keep the lengths s2_set_ctx_lens has just set.
+int s2_set_segments(pmhip_s2* h, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, int L, int B, hipStream_t s,
+                    const uint8_t* region_host = nullptr) {
     if (!ctx_seg_host) return PMHIP_OK;
     const size_t qbytes = ((size_t)B * h->cfg.tokens * 4 + 15) & ~(size_t)15, kbytes = ((size_t)B * L + 15) & ~(size_t)15;
+    const size_t pbytes = region_host ? ((size_t)B + 15) & ~(size_t)15 : 0;
     unsigned char* dseg;
+    unsigned char* dpick = nullptr;
     WS(h->ws, "ctx.seg", qbytes + kbytes, dseg);
+    if (region_host) WS(h->ws, "ctx.pick", pbytes, dpick);
     std::vector<unsigned char> packed(qbytes + kbytes, 255);
     memcpy(packed.data(), tok_seg_host, (size_t)B * h->cfg.tokens * 4);
     memcpy(packed.data() + qbytes, ctx_seg_host, (size_t)B * L);
-    PM_TRY(h->seg_ring.reserve(qbytes + kbytes));
+    PM_TRY(h->seg_ring.reserve(qbytes + kbytes + pbytes));
     PM_TRY(h->seg_ring.acquire());
     PM_TRY(h->seg_ring.stage(dseg, 0, packed.data(), qbytes + kbytes, s));
+    if (region_host) {
+        std::vector<unsigned char> flags(pbytes, 0);
+        memcpy(flags.data(), region_host, (size_t)B);
+        PM_TRY(h->seg_ring.stage(dpick, qbytes + kbytes, flags.data(), pbytes, s));
+    }
     PM_TRY(h->seg_ring.commit(s));
     for (auto& ck : h->cross)
-        if (ck.k) { ck.query_mask = reinterpret_cast<const uint32_t*>(dseg); ck.key_seg = dseg + qbytes; }
+        if (ck.k) { ck.query_mask = reinterpret_cast<const uint32_t*>(dseg); ck.key_seg = dseg + qbytes; ck.pick = dpick; }
     return PMHIP_OK;
 }
 
@@ -1865,13 +1893,40 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
                            const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host, int flags,
                            int64_t* pred_out, float* score_out, pmhip_stream stream, bool kinds = false, const float* neg_context = nullptr,
                            int Ln = 0, const int32_t* neg_lens_host = nullptr, bool filters = false, const float* top_p_host = nullptr,
-                           const int32_t* counts_host = nullptr) {
+                           const int32_t* counts_host = nullptr, const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr,
+                           const uint8_t* region_host = nullptr) {
     const bool keep_neg = kinds && (flags & PMHIP_SLOTS_KEEP_NEGATIVE) != 0;
     const bool neg_set = neg_context || keep_neg;             // this call has a negative set, given or kept
-    const char* who = counts_host ? "pipeline_step_slots_edit" : filters ? "pipeline_step_slots_filter"
+    const char* who = (ctx_seg_host || tok_seg_host || region_host) ? "pipeline_step_slots_regions"
+                      : counts_host ? "pipeline_step_slots_edit" : filters ? "pipeline_step_slots_filter"
                               : (neg_set || neg_lens_host) ? "pipeline_step_slots_negative" : choice_host ? "pipeline_step_slots_choice" : narrow;
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
-    PM_TRY(check_ctx_lens(who, ctx_lens_host, context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0), L, B));
+    const bool have_context = context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0);
+    // regional slots (pmhip_pipeline_step_slots_regions): the three arrays together or none, the rules of
+    // check_segments for the ACTIVE slots that are flagged, the length check for every other slot
+    bool regions = false;                                     // an active slot is regional: the two-launch cross-attention
+    PM_REQUIRE((!ctx_seg_host == !tok_seg_host) && (!ctx_seg_host == !region_host),
+               "%s: ctx_seg_host, tok_seg_host and region_host come together (one of them is NULL)", who);
+    if (region_host) {
+        for (int b = 0; b < B; ++b) {
+            if (slots_host[b].step & PM_SLOT_IDLE) continue;
+            PM_REQUIRE(region_host[b] <= 1, "%s: slot %d: region_host=%d must be 0 or 1", who, b, (int)region_host[b]);
+            regions = regions || region_host[b] == 1;
+        }
+    }
+    auto regional = [&](int b) { return regions && !(slots_host[b].step & PM_SLOT_IDLE) && region_host[b] == 1; };
+    if (!regions) {
+        PM_TRY(check_ctx_lens(who, ctx_lens_host, have_context, L, B));
+    } else {
+        PM_REQUIRE(have_context && L > 0, "%s: regional slots given without a context", who);
+        for (int b = 0; b < B; ++b) {
+            if (regional(b))
+                PM_TRY(check_segments_of(who, "slot", b, ctx_seg_host, tok_seg_host, L, s2->cfg.tokens));
+            else
+                PM_REQUIRE(!ctx_lens_host || (ctx_lens_host[b] >= 1 && ctx_lens_host[b] <= L), "%s: image %d: context length %d must be in [1, L=%d]",
+                           who, b, (int)ctx_lens_host[b], L);
+        }
+    }
     const auto& c = s2->cfg;
     PM_REQUIRE(c.n_embed % 64 == 0, "%s: n_embed=%d must be a multiple of 64", who, c.n_embed);
     PM_REQUIRE(neg_set || !neg_lens_host, "%s: neg_lens_host given without a negative context", who);
@@ -1941,7 +1996,29 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     }
     const int Lc = s2->slots_ctx_L;
     PM_REQUIRE(!ctx_lens_host || Lc > 0, "%s: ctx_lens_host given, but the kept context was prepared without one", who);
-    PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
+    PM_REQUIRE(!regions || Lc > 0, "%s: regional slots given, but the kept context was prepared without one", who);
+    if (!regions) {
+        PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
+    } else {
+        // The lengths the want = 0 launch reads (L where none came; a regional or idle slot's is never read by a workgroup that
+        // goes on), then the arrays with the rows of the slots that are not regional made neutral: they are not looked at here
+        // and by no kernel -- one segment, every token attending to it.
+        std::vector<int32_t> lens((size_t)B, L);
+        std::vector<uint8_t> kseg((size_t)B * L, 0), flag((size_t)B, 0);
+        std::vector<uint32_t> tseg((size_t)B * c.tokens, 1u);
+        for (int b = 0; b < B; ++b) {
+            if (!regional(b)) {
+                if (ctx_lens_host) lens[b] = ctx_lens_host[b];
+                continue;
+            }
+            flag[b] = 1;
+            memcpy(kseg.data() + (size_t)b * L, ctx_seg_host + (size_t)b * L, (size_t)L);
+            memcpy(tseg.data() + (size_t)b * c.tokens, tok_seg_host + (size_t)b * c.tokens, (size_t)c.tokens * 4);
+        }
+        PM_TRY(s2_set_ctx_lens(s2, lens.data(), L, B, s));
+        PM_TRY(s2_set_segments(s2, kseg.data(), tseg.data(), L, B, s, flag.data()));
+        ++s2->slots_region_steps;
+    }
     // the negative set: prepared (eager, outside any graph), kept, or -- a call that neither brings nor keeps one -- dropped
     if (keep_neg) {
         s2->cross_neg = kept_neg;                             // (neg_context is ignored, like context under PMHIP_SLOTS_KEEP_CONTEXT)
@@ -2025,7 +2102,7 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     const char* passes = pass_neg ? (pass_uncond ? "slotsthreeB" : "slotsnegB") : two_pass ? "slotsguidedB" : "slotsB";
     const std::string neg_key = pass_neg ? "N" + std::to_string(Ln) + (neg_lens_host ? "n" : "") : "";
     GraphEntry& ge = s2->graphs[passes + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
-                                (ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "") + (edit ? "E" : "")];
+                                (regions ? "R" : ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "") + (edit ? "E" : "")];
     PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
@@ -2086,6 +2163,25 @@ extern "C" int pmhip_pipeline_step_slots_edit(pmhip_s2* s2, int64_t* ids, const 
                                               const int32_t* counts_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
     return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
                            score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host, counts_host);
+}
+
+// no active slot with region_host == 1 (or the three arrays NULL): exactly pmhip_pipeline_step_slots_edit
+extern "C" int pmhip_pipeline_step_slots_regions(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                                 const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
+                                                 const float* neg_context, int Ln, const int32_t* neg_lens_host, const float* top_p_host,
+                                                 const int32_t* counts_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
+                                                 const uint8_t* region_host, int flags, int64_t* pred_out, float* score_out,
+                                                 pmhip_stream stream) {
+    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
+                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host, counts_host, ctx_seg_host, tok_seg_host,
+                           region_host);
+}
+
+// steps of that entry that ran the two-launch cross-attention (an active slot was regional)
+extern "C" int pmhip_s2_slots_region_steps(const pmhip_s2* h, int* steps) {
+    PM_REQUIRE(h, "s2_slots_region_steps: null handle");
+    if (steps) *steps = h->slots_region_steps;
+    return PMHIP_OK;
 }
 
 // steps of that entry whose re-masking launch was the form with a count per slot

@@ -420,6 +420,13 @@ class S2Engine:
         check(self.lib.pmhip_s2_slots_filter_steps(self.handle, C.byref(tiles), C.byref(chain)), "pmhip_s2_slots_filter_steps")
         return tiles.value, chain.value
 
+    def slots_region_steps(self):
+        """the steps pmhip_pipeline_step_slots_regions ran on this handle with the two-launch cross-attention (an active slot was
+        regional)"""
+        steps = C.c_int(0)
+        check(self.lib.pmhip_s2_slots_region_steps(self.handle, C.byref(steps)), "pmhip_s2_slots_region_steps")
+        return steps.value
+
     def slots_edit_steps(self):
         """the steps pmhip_pipeline_step_slots_edit ran on this handle with the re-masking form that takes a count per slot"""
         steps = C.c_int(0)
@@ -427,7 +434,8 @@ class S2Engine:
         return steps.value
 
     def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None,
-                   choice=None, negative_context=None, negative_lens=None, keep_negative=False, top_p=None, counts=None):
+                   choice=None, negative_context=None, negative_lens=None, keep_negative=False, top_p=None, counts=None,
+                   segments=None):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
@@ -449,6 +457,12 @@ class S2Engine:
         routes the step to pmhip_pipeline_step_slots_edit with the limits of the `top_p` route: -1 = the record's num_mask, c >= 0 =
         exactly c positions, 0 leaving the row as the sampler merged it (an edit request: DESIGN.md section 4t).  A step in which
         every active slot is at -1 runs the launches and the graph of the `top_p` route.
+        segments (None: the steps above): ``(ctx_seg uint8 [B, L], tok_seg uint32 [B, tokens], flags uint8 [B])``, host arrays, which
+        route the step to pmhip_pipeline_step_slots_regions with the limits of the `top_p` route: an active
+        slot with flags[b] == 1 runs the cross-attention of the pass with the context under its key sets -- ctx_seg[b, k] the
+        segment 0..31 of context row k or 255 for padding, tok_seg[b, t] the segments token t attends to --, every other slot under
+        its context length; the native entry validates them (a context is required).  A step in which no active slot is flagged
+        runs the launches and the graph of the `counts` route.
         -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
@@ -500,8 +514,18 @@ class S2Engine:
                 if not -1 <= v <= self.tokens:
                     raise ValueError(f"step_slots: slot {b}: count {v} must be in -1..{self.tokens}")
             counts = (C.c_int * B)(*vals)
+        if segments is not None:
+            cs, ts, fl = (np.ascontiguousarray(a, dtype=t) for a, t in zip(segments, (np.uint8, np.uint32, np.uint8)))
+            if cs.shape != (B, L) or ts.shape != (B, self.tokens) or fl.shape != (B,):
+                raise ValueError(f"step_slots: segments {cs.shape}, {ts.shape}, {fl.shape}: expected ({B}, {L}), ({B}, {self.tokens}), ({B},)")
+            segments = tuple(a.ctypes.data_as(C.POINTER(t)) for a, t in ((cs, C.c_ubyte), (ts, C.c_uint32), (fl, C.c_ubyte)))
         with torch.cuda.device(self.device):
-            if counts is not None:
+            if segments is not None:
+                check(self.lib.pmhip_pipeline_step_slots_regions(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
+                                                                 Ln, neg_lens, top_p, counts, segments[0], segments[1], segments[2], flags,
+                                                                 _p(pred), _p(score), stream_ptr(self.device)),
+                      "pmhip_pipeline_step_slots_regions")
+            elif counts is not None:
                 check(self.lib.pmhip_pipeline_step_slots_edit(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
                                                               Ln, neg_lens, top_p, counts, flags, _p(pred), _p(score), stream_ptr(self.device)),
                       "pmhip_pipeline_step_slots_edit")

@@ -423,6 +423,45 @@ def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, q
     return out
 
 
+def attention_pick(q, k, vt, n_kv, pick, want, out, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None):
+    """``attention`` for SOME images of the batch, into a caller-supplied `out` (pmhip_attention_pick).
+    pick uint8 [B] on the device names the kind of every image, `want` the kind this call serves: the rows of an image with
+    pick[b] == want become, bit for bit, what ``attention`` with the same kv_lens / key_segments + query_segments writes for it,
+    the rows of every other image stay as they are -- so two calls, one per kind, fill one buffer.  Exactly one of kv_lens and the
+    pair key_segments + query_segments selects the form.  out: [B*Nq, H*dh] of q's dtype with unit column stride; its row stride is
+    the leading dimension (a window of a larger buffer will do).  -> out"""
+    dev = _dev(q, k, vt, pick, kv_lens, key_segments, query_segments)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dim() == 2):
+        raise ValueError("out must be a 2-D tensor on the operands' device")
+    lib = _lib.load()
+    B, H, Nq, dh = q.shape
+    nkp = k.shape[2]
+    if pick.dtype != torch.uint8 or tuple(pick.shape) != (B,):
+        raise ValueError(f"pick must be a uint8 tensor of shape ({B},), got {pick.dtype} {tuple(pick.shape)}")
+    if out.dtype != q.dtype or tuple(out.shape) != (B * Nq, H * dh) or out.stride(1) != 1 or out.stride(0) < H * dh:
+        raise ValueError(f"out must be a {q.dtype} [{B * Nq}, {H * dh}] tensor with unit column stride, got {out.dtype} {tuple(out.shape)} "
+                         f"strides {tuple(out.stride())}")
+    if (key_segments is None) != (query_segments is None):
+        raise ValueError("key_segments and query_segments come together")
+    if (kv_lens is None) == (key_segments is None):
+        raise ValueError("exactly one of kv_lens and the pair key_segments + query_segments selects the form")
+    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
+        raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
+    if key_segments is not None:
+        if key_segments.dtype != torch.uint8 or tuple(key_segments.shape) != (B, n_kv) or not key_segments.is_contiguous():
+            raise ValueError(f"key_segments must be a contiguous uint8 tensor of shape ({B}, {n_kv}), got {key_segments.dtype} "
+                             f"{tuple(key_segments.shape)}")
+        if query_segments.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(query_segments.shape) != (B, Nq) or \
+                not query_segments.is_contiguous():
+            raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
+                             f"{tuple(query_segments.shape)}")
+    with torch.cuda.device(dev):
+        check(lib.pmhip_attention_pick(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), out.stride(0), B, H, dh, Nq, n_kv, nkp, int(use_exp2),
+                                       _p(kv_lens), _p(key_segments), _p(query_segments), _p(pick), int(want), stream_ptr(dev)),
+              "pmhip_attention_pick")
+    return out
+
+
 def layernorm(x, gamma, beta, eps=1e-5, out_dtype=torch.float32):
     dev = _dev(x, gamma, beta)
     lib = _lib.load()

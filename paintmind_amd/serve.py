@@ -68,15 +68,35 @@ contract reads: an edit request in slot j produces, bit for bit, the per-step pr
 batch with it; every other keyword of a request composes unchanged, and a step in which no occupied slot is an edit request passes
 no counts, which IS the step without: the same kernels and graph as before.
 
+Regional prompts are per request in a session opened with ``pipe.decode_session(..., regions=True)`` (it is an
+option of the session, not a class of its own, so it composes with ``filters=True``; without it ``regions=`` is refused as
+before).  ``submit(text=..., regions=[(prompt, mask), ...])`` takes ONE image's list of what ``Pipeline.generate(regions=)`` takes
+per image: ``prompt`` a string (or a ``[L_r, D]`` tensor when ``context=`` is given instead of ``text=``), ``mask`` a pixel mask
+``[H, W]`` or a bool token mask ``[g, g]``, at most ``MAX_REGIONS`` regions.  The request's context is the concatenation [global |
+region 1 | ...], built at submit by the code of ``generate`` at B = 1; its length is the total, and the capacity rules above
+(``max_context_len``, growth, re-preparing the K/V) apply to the total.  The native step (pmhip_pipeline_step_slots_regions) takes,
+beside everything above, a segment row and a token-mask row per slot and a flag per slot: every layer's cross-attention of the
+pass with the context is then two launches into one buffer, the per-image-length kernel serving the plain slots and the
+per-query kernel serving the regional ones, each returning at once on the other kind's images.  The contract: a regional request
+in slot j of an S-slot session produces, bit for bit, the per-step predictions, the scores and the final ids of row j of
+``generate_ids(context [S, capacity, D] with its rows in row j, context_segments / token_segments with its layout in row j and a
+one-segment layout in the other rows, B=S, ..., image_base=k - j, streams=1)``; a request WITHOUT regions in the same session still
+equals row j of ``generate_ids(..., context_lens=...)``, as in the default session; both hold whatever shares the batch.  A step
+passes the arrays only while an occupied slot is regional: a session without such a request runs the steps it ran before.
+Guidance or a schedule, a negative prompt, a choice temperature, the filters and the seed compose unchanged (the pass without a
+context and the negative prompt's pass never see regions).  An edit request (``keep_given``, ``image=``) with ``regions=`` is
+refused -- there is no scalar edit with regions to be identical to -- and so is ``regions=`` in an unconditional session.
+
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
 ``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed, guidance_scale=s,
 negative_text=n)`` -- in a FilterSession with ``topk=, top_p=`` as well -- and an edit request equals ``pipe.edit(img[None], ...,
-seed=seed)``.
+seed=seed)``; a regional request equals ``pipe.generate([text], regions=[regions], ..., seed=seed)``.
 """
 import collections
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -93,7 +113,9 @@ class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
     def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None,
-                 ctemps=None, negative=None, scales=None, top_p=1.0, edit=False, orig=None, pixel_mask=None):
+                 ctemps=None, negative=None, scales=None, top_p=1.0, edit=False, orig=None, pixel_mask=None, segments=None):
+        # a regional request: (numpy uint8 [L_r], the segment of every row of its context; numpy uint32 [N], the segments of every token)
+        self.segments = segments
         self.edit = edit                            # an edit request: nmask is edit_schedule's over its masked start ids, given ids stay
         self.orig, self.pixel_mask = orig, pixel_mask   # preserve="pixels": the image [C,H,W] and the pixel mask uint8 [H,W] to composite by
         self.top_p = top_p                          # the nucleus mass (1: none; a FilterSession's requests may carry another)
@@ -121,7 +143,8 @@ class DecodeSession:
     use_graph=None follows PMHIP_GENERATE_GRAPH like ``Pipeline.generate``."""
 
     def __init__(self, pipe, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True, max_context_len=None,
-                 max_negative_len=None):
+                 max_negative_len=None, regions=False):
+        self.regions = bool(regions)        # submit(regions=) is served (DESIGN.md section 4v); False: refused, as before there was the option
         if slots < 1:
             raise ValueError("a decode session needs at least one slot")
         if max_negative_len is not None and int(max_negative_len) < 1:
@@ -173,10 +196,12 @@ class DecodeSession:
         `image` [C,H,W] with exactly one of `mask` [H,W] (pixels, non-zero = regenerate) / `token_mask` bool [g,g]: the same edit
         from an image -- it is encoded and masked here, at submit -- and `preserve` ("tokens" | "pixels"): "pixels" puts the original
         pixels back outside the pixel mask, as in ``Pipeline.edit``.
-        `regions`: refused -- regional prompts are served by ``Pipeline.generate(regions=)`` only."""
-        _no_regions(regions)
+        `regions`: refused -- unless the session was opened with ``regions=True``: then ONE image's list ``[(prompt, mask), ...]`` of
+        ``Pipeline.generate(regions=)``, `text` (or `context`) staying the global prompt (the module docstring has the rules)."""
+        if not self.regions:
+            _no_regions(regions)
         return self._submit(text, timesteps, temperature, topk, None, seed, image_index, context, ids0, guidance_scale, choice_temperature,
-                            negative_text, negative_context, keep_given, image, mask, token_mask, preserve)
+                            negative_text, negative_context, keep_given, image, mask, token_mask, preserve, regions)
 
     def _filters(self, topk, top_p):
         """a request's sampler filters as this session serves them -> (topk, top_p): top-k in 1..8 where the native slots step runs
@@ -185,6 +210,48 @@ class DecodeSession:
         if not self._cpu and not 1 <= topk <= 8:
             raise ValueError(f"a decode session serves topk in 1..8, got {topk}")
         return topk, 1.0
+
+    def _region_request(self, text, context, regions):
+        """submit(regions=) -> (the request's context [L_total, D]: global | region 1 | ..., (its segment row uint8 [L_total], its
+        token masks uint32 [N])), by the code of ``Pipeline.generate(regions=)`` at B = 1"""
+        from .generate import MAX_REGIONS, region_layout
+        pipe = self.pipe
+        regions = list(regions)
+        if len(regions) > MAX_REGIONS:
+            raise ValueError(f"regions: {len(regions)} regions, at most {MAX_REGIONS} per request")
+        if context is None:
+            if text is None:
+                raise ValueError("a conditional session needs a text (or a context) for every request")
+            ctx, cs, ts = pipe._region_context([text], [regions], False)
+        else:
+            for item in regions:
+                if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], torch.Tensor) and item[0].dim() == 2
+                        and item[0].shape[0] >= 1 and item[0].shape[1] == context.shape[-1]):
+                    raise ValueError("regions: beside context= every region is a (context [L_r, D], mask) pair of the context's width")
+            if context.dim() != 2 or context.shape[0] < 1:
+                raise ValueError(f"a request's context is [L, D] with L >= 1, got {tuple(context.shape)}")
+            ctx, cs, ts = region_layout([[context] + [item[0] for item in regions]], [[item[1] for item in regions]], pipe.image_size,
+                                        pipe.patch_size)
+        return ctx[0], (cs[0], ts[0])
+
+    def _segment_arrays(self, capacity):
+        """this step's (ctx_seg uint8 [S, capacity], tok_seg uint32 [S, N], flags uint8 [S]) for the native step, or None when no
+        occupied slot is regional (the step without).  A regional slot's rows are its layout, 255 behind its total; every other
+        slot's rows are the one-segment layout (the native step does not look at them)."""
+        if not any(r is not None and r.segments is not None for r in self.occupied):
+            return None
+        cs = np.zeros((self.size, capacity), np.uint8)
+        ts = np.ones((self.size, self.pipe.num_tokens), np.uint32)
+        flags = np.zeros(self.size, np.uint8)
+        for j, r in enumerate(self.occupied):
+            if r is None:
+                continue
+            cs[j, r.context.shape[0]:] = 255
+            if r.segments is not None:
+                cs[j, :r.context.shape[0]] = r.segments[0]
+                ts[j] = r.segments[1]
+                flags[j] = 1
+        return cs, ts, flags
 
     def _edit_start(self, ids0, keep_given, image, mask, token_mask, preserve):
         """the edit keywords of submit(), checked -> (ids0, edit, orig, pixel mask): an image is encoded (B = 1) and masked here, by
@@ -222,9 +289,16 @@ class DecodeSession:
         return ids[0], True, None, None
 
     def _submit(self, text, timesteps, temperature, topk, top_p, seed, image_index, context, ids0, guidance_scale, choice_temperature,
-                negative_text, negative_context, keep_given=False, image=None, mask=None, token_mask=None, preserve="tokens"):
+                negative_text, negative_context, keep_given=False, image=None, mask=None, token_mask=None, preserve="tokens", regions=None):
         """submit() behind its keywords; (topk, top_p) go through _filters, the session's own range of them"""
         topk, top_p = self._filters(topk, top_p)
+        segments = None
+        if regions is not None:
+            if not self.conditional:
+                raise ValueError("regions need a text condition (an unconditional session IS the unconditional branch)")
+            if keep_given or image is not None:
+                raise ValueError("an edit request (keep_given, image=) takes no regions: Pipeline.edit has none to be identical to")
+            context, segments = self._region_request(text, context, regions)
         ids0, edit, orig, pixel_mask = self._edit_start(ids0, keep_given, image, mask, token_mask, preserve)
         timesteps = int(timesteps)
         if timesteps < 1:
@@ -285,7 +359,7 @@ class DecodeSession:
         if edit:                                    # m is counted once, here: the schedule over the region instead of the image
             nmask = edit_schedule(int((ids0 == self.pipe.mask_token_id).sum()), timesteps)
         r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale,
-                    ctemps, negative, scales, top_p, edit, orig, pixel_mask)
+                    ctemps, negative, scales, top_p, edit, orig, pixel_mask, segments)
         self._submitted += 1
         self.queue.append(r)
         return r
@@ -348,7 +422,8 @@ class DecodeSession:
             # an edit request: the step with a count per image, as Pipeline.edit's CPU branch takes it
             ids, img = pipe._sample_cpu(self._rows[j], 0 if r.edit else r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t,
                                         r.scales[t] if r.scales else r.guidance_scale, None, r.ctemps[t] if r.ctemps else 0.0,
-                                        top_p=r.top_p, negative=neg, negative_lens=None, **({"counts": [r.nmask[t]]} if r.edit else {}))
+                                        top_p=r.top_p, negative=neg, negative_lens=None, **({"counts": [r.nmask[t]]} if r.edit else {}),
+                                        **({"segments": (r.segments[0][None], r.segments[1][None])} if r.segments is not None else {}))
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
@@ -442,10 +517,14 @@ class DecodeSession:
                                    for j, r in enumerate(self.occupied)):
             neg_lens = [min(n, neg.shape[1]) for n in self._neg_lens]
 
+        # the regional slots' arrays -- None when no occupied slot is regional: the step without
+        segments = self._segment_arrays(ctx.shape[1]) if self.regions and self.conditional else None
+        seg_kw = {} if segments is None else {"segments": segments}
+
         def run(keep_context, keep_negative):
             return eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep_context, want_aux=want_aux,
                                   guides=self._guides, context_lens=lens, choice=choice, negative_context=neg, negative_lens=neg_lens,
-                                  keep_negative=keep_negative, counts=counts, **self._step_filters())
+                                  keep_negative=keep_negative, counts=counts, **seg_kw, **self._step_filters())
         try:
             _, pred, score = run(keep, keep_neg)
         except _lib.PmhipError as e:
@@ -494,9 +573,10 @@ class FilterSession(DecodeSession):
         """DecodeSession.submit with `topk` in 1..n_embed, or None for no filter (stored as n_embed), and `top_p` (None or 1 = no
         nucleus filter; else finite, 0 < top_p < 1): of the request's top-k classes only those whose mass strictly above them is
         below top_p of the top-k's mass are drawn from, like ``Pipeline.generate(top_p=)``.  Out of range: ValueError, here."""
-        _no_regions(regions)
+        if not self.regions:
+            _no_regions(regions)
         return self._submit(text, timesteps, temperature, topk, top_p, seed, image_index, context, ids0, guidance_scale, choice_temperature,
-                            negative_text, negative_context, keep_given, image, mask, token_mask, preserve)
+                            negative_text, negative_context, keep_given, image, mask, token_mask, preserve, regions)
 
     def _filters(self, topk, top_p):
         V = self.pipe.mask_token_id                 # n_embed

@@ -1,7 +1,9 @@
 """Segmented cross-attention against the per-image-length form and the unmasked entry at a regional-prompts shape (default
 B=64, H=12, Nq=1024, Nkv=231 = a global prompt and two regions of 77 rows, dh=64): microseconds per launch by hipEvents, bf16
 (exp2) and fp32.  A measurement for DESIGN.md section 4u, no gate.  Layout of the masks: rows [0,77) segment 0 (global), [77,154)
-segment 1, [154,231) segment 2; the left half of a 32 x 32 token grid attends to segments 0 and 1, the right half to 0 and 2."""
+segment 1, [154,231) segment 2; the left half of a 32 x 32 token grid attends to segments 0 and 1, the right half to 0 and 2.
+Behind them the picked forms of DESIGN.md section 4v (pmhip_attention_pick): each form with every image served, every second one and
+none -- the last is what a launch costs whose workgroups all return at once -- and the pair of launches of a half-regional batch."""
 import os
 import sys
 
@@ -43,3 +45,16 @@ for dtype, exp2 in ((torch.bfloat16, True), (torch.float32, False)):
     seg = timed(lambda: ops.attention(q, k, vt, NKV, use_exp2=exp2, key_segments=ks, query_segments=qm))
     print(f"{dtype} B={B} H={H} Nq={NQ} Nkv={NKV}: unmasked {plain:.1f} us, lens {per_image:.1f} us, segments {seg:.1f} us "
           f"({seg / per_image:.2f} x lens)")
+    if hasattr(ops, "attention_pick"):
+        out = torch.empty(B * NQ, H * 64, device=dev, dtype=dtype)
+        picks = {"all": torch.zeros(B, dtype=torch.uint8, device=dev), "half": (torch.arange(B) % 2).to(torch.uint8).to(dev),
+                 "none": torch.ones(B, dtype=torch.uint8, device=dev)}
+        lens_pick = {n: timed(lambda: ops.attention_pick(q, k, vt, NKV, p, 0, out, use_exp2=exp2, kv_lens=lens)) for n, p in picks.items()}
+        seg_pick = {n: timed(lambda: ops.attention_pick(q, k, vt, NKV, 1 - p, 1, out, use_exp2=exp2, key_segments=ks, query_segments=qm))
+                    for n, p in picks.items()}
+
+        def pair():
+            ops.attention_pick(q, k, vt, NKV, picks["half"], 0, out, use_exp2=exp2, kv_lens=lens)
+            ops.attention_pick(q, k, vt, NKV, picks["half"], 1, out, use_exp2=exp2, key_segments=ks, query_segments=qm)
+        fmt = lambda d: ", ".join(f"{n} served {v:.1f} us" for n, v in d.items())
+        print(f"    picked lens form: {fmt(lens_pick)}; picked segments form: {fmt(seg_pick)}; both launches, half and half: {timed(pair):.1f} us")

@@ -19,6 +19,12 @@
            prompt (two), all guided against a --neg-rows negative context (two, the second against the negative K/V), half and
            half (three).  --arms picks among one,two_uncond,two_negative,three: a commit without the feature runs the first two.
 
+  regions  regional prompts per request: milliseconds per session step, hipEvents around every step of a
+           session of S conditional requests (T steps, a [77, D] global context each) admitted together behind two warm-up sessions
+           (eager, capture), the admission step left out -- none regional (the steps of a session without the option), every second
+           one, all of them (two region prompts of 77 rows each over halves of the grid: a total of 231 rows, the capacity).
+           --arms picks among none,half,all; a commit without the feature runs ``--arms none`` (point --root at it).
+
 The arms alternate inside one process, --rounds times; nothing is decoded (ids only).  --arms generate runs on a commit that has
 no sessions: point --root at such a checkout to time the scalar loop of another commit on the same box.
 """
@@ -33,7 +39,7 @@ import time
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="checkout whose paintmind_amd is timed")
-    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed", "guided", "negative"])
+    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed", "guided", "negative", "regions"])
     ap.add_argument("--arms", default="session,generate")
     ap.add_argument("--workload", default=None, help="default: bench-uncond-12L-d512; guided: bench-text-24L-d768")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
@@ -74,6 +80,11 @@ def main():
         return
     if a.mode == "negative":
         emit(negative_session(a, dev), a.out)
+        return
+    if a.mode == "regions":
+        if a.arms == "session,generate":
+            a.arms = "none,half,all"
+        emit(regions_session(a, dev), a.out)
         return
     pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
     pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
@@ -261,6 +272,57 @@ def negative_session(a, dev):
     eng = pipe.engine()
     if hasattr(eng, "slots_passes"):
         out["slots_passes"] = dict(zip(("one", "two", "three"), eng.slots_passes()))
+    return out
+
+
+def regions_session(a, dev):
+    """ms per session step (graph replay, nothing decoded), by how many of the S requests carry regional prompts"""
+    import torch
+    import paintmind_amd as pm
+    from paintmind_amd.generate import Pipeline
+    pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
+    pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    S, T = a.slots, max(a.timesteps, 21)
+    D, g = pipe.engine().context_dim, pipe.image_size // pipe.patch_size
+    gen = torch.Generator().manual_seed(2)
+    ctx = torch.randn(S, 3, 77, D, generator=gen)
+    left = torch.zeros(g, g, dtype=torch.bool)
+    left[:, :g // 2] = True
+    share = {"none": lambda i: False, "half": lambda i: i % 2 == 1, "all": lambda i: True}
+    arms = a.arms.split(",")
+
+    def run(arm, seed, timed):
+        kw = dict(regions=True) if arm != "none" else {}
+        s = pipe.decode_session(slots=S, conditional=True, use_graph=True, decode=False, max_context_len=231, **kw)
+        for i in range(S):
+            rk = dict(regions=[(ctx[i, 1], left), (ctx[i, 2], ~left)]) if share[arm](i) else {}
+            s.submit(context=ctx[i, 0], timesteps=T, temperature=1.0, topk=5, seed=seed + i, **rk)
+        ms = []
+        for step in range(T):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            s.step()
+            e1.record()
+            if timed and step > 0:
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+        assert s.idle()
+        return ms
+
+    for arm in arms:                                   # eager pass, capture pass
+        for w in range(2):
+            run(arm, w, False)
+    torch.cuda.synchronize(dev)
+    ms = {arm: [] for arm in arms}
+    for rnd in range(a.rounds):
+        for arm in arms:
+            ms[arm] += run(arm, 100 * rnd, True)
+    stat = lambda v: {"steps": len(v), "median": sorted(v)[len(v) // 2], "mean": sum(v) / len(v), "min": min(v)}
+    out = {"mode": "regions", "root": os.path.abspath(a.root), "workload": a.workload, "dtype": a.dtype, "slots": S, "timesteps": T,
+           "global_rows": 77, "region_rows": [77, 77], "capacity": 231, "ms_per_step": {arm: stat(v) for arm, v in ms.items()}}
+    eng = pipe.engine()
+    if hasattr(eng, "slots_region_steps"):
+        out["slots_region_steps"] = eng.slots_region_steps()
     return out
 
 
