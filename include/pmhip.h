@@ -272,7 +272,8 @@ int pmhip_patchify(const float* img, void* out, int out_dtype, int B, int C, int
                    pmhip_stream stream);
 
 /* 'b (h w) (p1 p2 c) -> b c (h p1) (w p2)' then clamp(lo,hi) (stage1/layers.py:150;
- * stage1/vqmodel.py:30).  y fp32 [B*(H/P)*(W/P), P*P*C] -> img fp32 [B,C,H,W]. */
+ * stage1/vqmodel.py:30).  y fp32 [B*(H/P)*(W/P), P*P*C] -> img fp32 [B,C,H,W].  The clamp is torch.clamp's: a NaN stays a
+ * NaN (lo = -inf, hi = +inf copies every value). */
 int pmhip_unpatchify_clamp(const float* y, float* img, int B, int C, int H, int W, int P, float lo,
                            float hi, pmhip_stream stream);
 
@@ -327,7 +328,8 @@ int pmhip_vq_quantize(const float* z, const float* en, const float* sq, float be
  * position i of sample b is KEPT iff fewer than len_keep positions of the sample have smaller noise
  * (ties: smaller index first, i.e. the order of a stable ascending argsort); masked positions get
  * mask_token.  z, x_out fp32 [B,N,E]; noise, mask_out fp32 [B,N] (mask: 0 keep, 1 masked);
- * len_keep = N - max(int(N*mask_ratio),1) is computed by the caller (generate.py:86-87). */
+ * len_keep = N - max(int(N*mask_ratio),1) is computed by the caller (generate.py:86-87).  0 <= len_keep <= N, N <= 16384
+ * (a sample's noise and flags sit in 8 N bytes of dynamic LDS, up to 128 of a CU's 160 KiB). */
 int pmhip_random_mask(const float* z, const float* noise, const float* mask_token, int len_keep,
                       float* x_out, float* mask_out, int B, int N, int E, pmhip_stream stream);
 

@@ -112,6 +112,10 @@ __global__ __launch_bounds__(THREADS) void patchify_kernel(const float* __restri
     }
 }
 
+// torch.clamp: a NaN stays a NaN (fminf / fmaxf return their other operand: a NaN pixel would come out as `lo`); both
+// comparisons are false for a NaN, so it falls through
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
 // un-patchify + clamp: img[b,c,ph*P+i,pw*P+j] = clamp(y[(b,ph,pw), (i*P+j)*C + c]); thread = 4 j
 __global__ __launch_bounds__(THREADS) void unpatchify_kernel(const float* __restrict__ y, float* __restrict__ img, int B,
                                                              int C, int H, int W, int P, float lo, float hi) {
@@ -127,10 +131,10 @@ __global__ __launch_bounds__(THREADS) void unpatchify_kernel(const float* __rest
         const int ph = yy / P, i = yy % P, pw = xx / P, j = xx % P;
         const float* src = y + (((size_t)b * Hp + ph) * Wp + pw) * K + (size_t)(i * P + j) * C + c;
         float4 v;
-        v.x = fminf(fmaxf(src[0], lo), hi);
-        v.y = fminf(fmaxf(src[C], lo), hi);
-        v.z = fminf(fmaxf(src[2 * C], lo), hi);
-        v.w = fminf(fmaxf(src[3 * C], lo), hi);
+        v.x = clamp_keep_nan(src[0], lo, hi);
+        v.y = clamp_keep_nan(src[C], lo, hi);
+        v.z = clamp_keep_nan(src[2 * C], lo, hi);
+        v.w = clamp_keep_nan(src[3 * C], lo, hi);
         *reinterpret_cast<float4*>(img + (((size_t)b * C + c) * H + yy) * W + xx) = v;
     }
 }
