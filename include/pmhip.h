@@ -245,6 +245,34 @@ int pmhip_attention_segments(int dtype, const void* Q, const void* K, const void
                              int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
                              const uint32_t* query_mask, pmhip_stream stream);
 
+/* pmhip_attention_segments with a WEIGHT per key (prompt weights; new entries within ABI 11, nothing existing changes meaning;
+ * DESIGN.md section 4w):
+ *   key_bias DEVICE f32 [B, Nkv]: log(w[b,k]) in the kernel's score unit -- octaves when use_exp2, nats otherwise --, or -inf for
+ *            w == 0.  pmhip_key_bias writes it from the weights.
+ * Over the keys its segments allow, query q's probabilities are p[q,k] = w[k] exp(s[q,k]) / sum_j w[j] exp(s[q,j]): the bias is added
+ * to the score (one f32 addition, in every 32-key half-tile, before the maximum is taken: the running maximum is a maximum over
+ * s + bias).  An integer weight n is the key appearing n times.  key_seg, query_mask and every other argument are those of
+ * pmhip_attention_segments.  Contract:
+ *   - a key with bias -inf is a key with key_seg == 255, bit for bit: it never reaches a result, NaN in its K row and V^T column
+ *     included, and never raises a running maximum; a key takes part in a query's softmax iff its segment is allowed AND its bias
+ *     is above -inf
+ *   - every bias == 0 gives pmhip_attention_segments's rows, bit for bit
+ *   - every query allows at least one key with a bias above -inf (else: a finite, unspecified row, as there)
+ *   - K rows and V^T columns of keys with a segment 0..31 and a bias above -inf must be finite; the biases are -inf or finite, and
+ *     |bias| <= 20 octaves is what the model-level entries validate and the tests cover
+ *   - image b's rows do not depend on what else is in the batch; there is no kv_lens beside the arrays
+ * Any dim_head the _dh entry serves.  dim_head 64 runs the tuned kernels, every half-tile on the exact path as in the segmented form
+ * (pmhip_attention_fallbacks never counts these launches); the bf16 kernel runs 128 or 64 queries per workgroup, chosen from B,
+ * heads and Nq only, never from the arrays, bit-identical per 16-query tile.  There is no picked variant.  key_seg, query_mask or
+ * key_bias NULL is PMHIP_EINVAL. */
+int pmhip_attention_weighted(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                             int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
+                             const uint32_t* query_mask, const float* key_bias, pmhip_stream stream);
+/* weights DEVICE f32 [n] -> bias DEVICE f32 [n]: 0 -> -inf, 1 -> exactly 0.0f, otherwise log2f(w), times ln 2 (one f32
+ * multiplication) when use_exp2 == 0.  One asynchronous launch on `stream`, usable inside a captured graph; the two arrays do not overlap.
+ * The range of w (0, or [2^-20, 2^20]) is the caller's to validate: this entry cannot read device memory on the host. */
+int pmhip_key_bias(const float* weights, float* bias, int n, int use_exp2, pmhip_stream stream);
+
 /* pmhip_attention_lens or pmhip_attention_segments for SOME images of the batch (regional prompts per slot; new entry within ABI
  * 11, nothing existing changes meaning):
  *   pick DEVICE uint8 [B]: the kind of every image;  want: the kind this launch serves (0..255)
@@ -1027,6 +1055,43 @@ int pmhip_pipeline_generate_segments(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids
                                      pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
                                      float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                      const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host);
+
+/* PROMPT WEIGHTS (new entries within ABI 11, following the *_segments entries: nothing existing changes meaning; DESIGN.md section
+ * 4w).  Emphasis: how much a context row counts.
+ *   ctx_w_host  HOST f32 [B, L]: the weight w >= 0 of context row k of image b
+ * Over the rows a token's segments allow, p[t,k] = w[k] exp(s[t,k]) / sum_j w[j] exp(s[t,j]); w == 1 is the unweighted row, an integer
+ * n the row appearing n times, and w == 0 a row marked 255: it never reaches a result, NaN included.  NULL: the call IS the
+ * *_segments entry -- same kernels, same graphs.
+ *   - weights stand beside the two segment arrays, beside ctx_lens_host (where the entry has one), or alone.  Without segment arrays
+ *     the engine stages neutral ones: segment 0 for the rows below the image's length, 255 behind, every token mask all ones.
+ *     Weights beside explicit segments AND ctx_lens_host stay refused, as for segments
+ *   - validated before anything is launched, else PMHIP_EINVAL: every weight finite and either 0 or in [2^-20, 2^20] (the message
+ *     names the image and the row) -- outside that a weight is no emphasis any more, inside it log w stays clear of denormals and
+ *     20 octaves on a score overflow nothing the exact path's running maximum does not already handle --; a context present; every
+ *     token allows at least one row with w > 0 (the message names the image and the token)
+ *   - they travel like the segments: pinned ring -> copy kernel -> pmhip_key_bias -> a handle-owned device array, from where the ONE
+ *     launch that changes, the cross-attention of the pass with the context, reads them (pmhip_attention_weighted).  The pass
+ *     without a context of a guided step and a negative context's pass never see weights
+ *   - captured graphs bake in that array, not its contents: one graph per (B, L) serves every set of weights (and every layout of
+ *     regions beside them), under one further key of the handle's graph cache (pmhip_s2_graph_count)
+ * The other arguments are those of the entry each extends. */
+int pmhip_s2_forward_weights(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const uint8_t* ctx_seg_host,
+                             const uint32_t* tok_seg_host, const float* ctx_w_host, float* logits_out, pmhip_stream stream);
+int pmhip_pipeline_sample_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                  const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                  uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                  float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
+                                  float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                  const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const float* ctx_w_host,
+                                  pmhip_stream stream);
+int pmhip_pipeline_generate_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                    const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                    const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                    float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                    pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
+                                    float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                    const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
+                                    const float* ctx_w_host);
 
 /* Per-kernel timing hook used by bench.py: when enabled, every kernel launch of the named family
  * is bracketed by hipEvents on its own stream and accumulated (count, total ms). */

@@ -192,6 +192,17 @@ PROTOTYPES = {
     "pmhip_pipeline_generate_segments": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
                                                C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
                                                f32, vp, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), C.POINTER(u32)]),
+    # prompt weights: the operator with a bias per key, the weights -> bias kernel, and the model-level entries
+    # that take the weight of every context row (host f32 [B, L])
+    "pmhip_attention_weighted": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "pmhip_key_bias": (i32, [vp, vp, i32, i32, vp]),
+    "pmhip_s2_forward_weights": (i32, [vp, vp, vp, i32, i32, C.POINTER(C.c_ubyte), C.POINTER(u32), C.POINTER(f32), vp, vp]),
+    "pmhip_pipeline_sample_weights": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, i32, f32,
+                                            f32, vp, f32, vp, i32, C.POINTER(i32), C.POINTER(C.c_ubyte), C.POINTER(u32), C.POINTER(f32), vp]),
+    "pmhip_pipeline_generate_weights": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),
+                                              C.POINTER(C.c_ubyte), i32, u64, u64, vp, i32, vp, vp, C.c_size_t, vp, i32, f32, C.POINTER(f32),
+                                              f32, vp, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_ubyte), C.POINTER(u32),
+                                              C.POINTER(f32)]),
     "pmhip_s2_switches": (i32, [vp]),
     "pmhip_vqgan_switches": (i32, [vp]),
     "pmhip_s2_step0_shared": (i32, [vp, C.POINTER(i32), C.POINTER(i32)]),

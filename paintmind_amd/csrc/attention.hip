@@ -112,6 +112,17 @@ __device__ __forceinline__ void zero_ragged_v(unsigned char* Vl, int kv0, int Nk
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
 #undef PM_ATTN_PICK
+// the weighted form: the per-query form plus key_bias (device f32 [B, Nkv]), log(weight) of every key in the
+// kernel's score unit; -inf = the key is padding
+#define PM_ATTN_KERNEL attention_seg_bias_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias
+#define PM_ATTN_SEG 1
+#define PM_ATTN_BIAS 1
+#include "attention_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_BIAS
 
 }  // namespace
 
@@ -133,6 +144,17 @@ void pm_attention_f32(const void* Q, const void* K, const void* Vt, void* out, i
     };
     if (use_exp2) launch(attention_kernel<true, QF>, attention_lens_kernel<true, QF>);
     else launch(attention_kernel<false, QF>, attention_lens_kernel<false, QF>);
+}
+
+// The weighted form, a launcher of its own so that the one above keeps its text: the grid and the workgroup of the
+// segmented twin.
+void pm_attention_f32_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                               int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s) {
+    constexpr int QF = 2;
+    const int nqb = ceil_div(Nq, 4 * QF * 16);
+    auto k = use_exp2 ? attention_seg_bias_kernel<true, QF> : attention_seg_bias_kernel<false, QF>;
+    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
+                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias);
 }
 
 // The picked forms, a launcher of their own so that the one above keeps its text: exactly one of lens / seg is given,

@@ -150,6 +150,17 @@ __device__ __forceinline__ f32x4_t mma(const v4u_t& rows, const v4u_t& cols, con
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
 #undef PM_ATTN_PICK
+// the weighted form: the per-query form plus key_bias (device f32 [B, Nkv]), log(weight) of every key in the
+// kernel's score unit, added to an allowed key's score before the maximum is taken; -inf = the key is padding
+#define PM_ATTN_KERNEL attention_bf16_seg_bias_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias
+#define PM_ATTN_SEG 1
+#define PM_ATTN_BIAS 1
+#include "attention_bf16_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_BIAS
 
 #undef DSRX
 #undef LGKM4
@@ -174,6 +185,16 @@ static void launch_seg_qf(const void* Q, const void* K, const void* Vt, void* ou
     auto k = use_exp2 ? attention_bf16_seg_kernel<true, QF> : attention_bf16_seg_kernel<false, QF>;
     hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
                        Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask);
+}
+
+// the weighted form: the geometry of the segmented twin
+template <int QF>
+static void launch_seg_bias_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
+                               int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s) {
+    const int nqb = ceil_div(Nq, 4 * QF * 16);
+    auto k = use_exp2 ? attention_bf16_seg_bias_kernel<true, QF> : attention_bf16_seg_bias_kernel<false, QF>;
+    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
+                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias);
 }
 
 // the picked forms: exactly one of lens / seg, the geometry of the twin
@@ -223,6 +244,15 @@ void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* o
                            int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s) {
     if ((long long)B * heads * ceil_div(Nq, 128) >= 512) launch_seg_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
     else launch_seg_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
+}
+
+// The weighted form: the rule of pm_attention_bf16_seg, word for word -- B, heads and Nq decide between 128 and 64
+// queries per workgroup, never the arrays --, and the forms are bit-identical per 16-query tile.
+void pm_attention_bf16_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                                int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s) {
+    if ((long long)B * heads * ceil_div(Nq, 128) >= 512)
+        launch_seg_bias_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, s);
+    else launch_seg_bias_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, s);
 }
 
 // The picked forms: the rule of the twin, from B, heads and Nq only -- never from `pick` --, so an image's bits do not

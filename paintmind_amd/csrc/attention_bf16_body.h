@@ -1,4 +1,4 @@
-// The bf16 attention kernel of attention_bf16.hip, which includes this file FIVE TIMES (no include guard on purpose):
+// The bf16 attention kernel of attention_bf16.hip, which includes this file SIX TIMES (no include guard on purpose):
 //   PM_ATTN_KERNEL = attention_bf16_kernel,      PM_ATTN_LENS_PARAM empty          one key count for the launch (Nkv)
 //   PM_ATTN_KERNEL = attention_bf16_lens_kernel, PM_ATTN_LENS_PARAM = ", lens"     PM_ATTN_LENS defined: the key count is per IMAGE --
 //       lens[b] (device int32 [B]), read once per workgroup into a scalar and clamped to [1, Nkv]; Nkv stays the launch-wide
@@ -14,6 +14,11 @@
 //       PM_ATTN_PICK defined and two more parameters ", pick, want" (DESIGN.md section 4v).  pick (device uint8 [B]) names the kind
 //       of every image; a workgroup whose image has pick[b] != want returns at once and leaves the image's output rows as they
 //       are, every other workgroup runs its twin's text.  Two launches, one per kind, fill one output buffer.
+//   PM_ATTN_KERNEL = attention_bf16_seg_bias_kernel: the third form again with PM_ATTN_BIAS defined and one more parameter
+//       ", key_bias" (DESIGN.md section 4w).  key_bias[b, k] (device f32 [B, Nkv]) is log(weight) of a key in the kernel's score
+//       unit -- octaves when EXP2, nats otherwise --, added to the key's score in every half-tile BEFORE the maximum is taken, so
+//       the running max is a max over s + bias; -inf means excluded and makes the key padding (255) in seg_of, for the scores and
+//       for the V^T zeroing alike.  No picked variant.
 // A compile-time variant by TEXT, not by a template parameter or an inlined body function: the first form is then the kernel the
 // library had before the second existed, token for token -- same symbol, same instruction stream, same registers (a shared
 // __device__ body, even force-inlined, was measured to move the schedule of every instantiation).
@@ -56,8 +61,14 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
 #endif
 #ifdef PM_ATTN_SEG
     const unsigned char* segb = key_seg + (size_t)b * Nkv;  // this image's key segments
+#ifdef PM_ATTN_BIAS
+    const float* biasb = key_bias + (size_t)b * Nkv;         // this image's key biases; -inf = the key is padding
+    auto seg_of = [&](int key) -> unsigned { return key < Nkv && biasb[key] != -INFINITY ? (unsigned)segb[key] : 255u; };
+    auto bias_of = [&](int key) -> float { return key < Nkv ? biasb[key] : 0.f; };
+#else
     // segment of key `key` of this image; keys at or beyond Nkv are padding
     auto seg_of = [&](int key) -> unsigned { return key < Nkv ? (unsigned)segb[key] : 255u; };
+#endif
     unsigned qmask[QF];                                      // the segments this lane's query of tile qf attends to
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {
@@ -161,7 +172,22 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __res
     auto rescale = [&](auto ragged_c, auto first_c, f32x4_t (&sc)[2][QF], int hh) {
         constexpr bool first = decltype(first_c)::value;
         const int kv0 = (hh >> 1) * KT, pc = hh & 1;
-#ifdef PM_ATTN_SEG
+#if defined(PM_ATTN_SEG) && defined(PM_ATTN_BIAS)
+        // every half-tile: an allowed key's score becomes s + bias (one f32 add, before the maximum below), a denied one -inf
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = kv0 + 32 * pc + 8 * g + 4 * kk + r;
+                const unsigned sg = seg_of(key);
+                const float kb = bias_of(key);
+#pragma unroll
+                for (int qf = 0; qf < QF; ++qf) {
+                    if (!((sg < 32u) & ((qmask[qf] >> (sg & 31u)) & 1u))) sc[kk][qf][r] = -INFINITY;
+                    else sc[kk][qf][r] += kb;
+                }
+            }
+#elif defined(PM_ATTN_SEG)
         // every half-tile: a key takes part in a query's softmax iff its segment is one the query attends to (padding, 255, never)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)

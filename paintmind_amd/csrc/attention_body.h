@@ -6,6 +6,9 @@
 // running max is raised at every half-tile (no deferred rescale), and a query that has met no allowed key yet keeps negm = 0.
 // A FOURTH and a FIFTH inclusion with PM_ATTN_PICK beside PM_ATTN_LENS / PM_ATTN_SEG (attention_lens_pick_kernel, attention_seg_pick_kernel;
 // two more parameters pick, want) are the picked forms of DESIGN.md 4v: a workgroup whose image has pick[b] != want returns at once.
+// A SIXTH inclusion with PM_ATTN_BIAS beside PM_ATTN_SEG (attention_seg_bias_kernel; one more parameter key_bias, device f32 [B, Nkv])
+// is the weighted form of DESIGN.md 4w: key_bias[b, k] = log(weight) in the kernel's score unit is added to an allowed key's score
+// before the maximum is taken; -inf makes the key padding (255), for the scores and for the V^T zeroing alike.
 template <bool EXP2, int QF>
 __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __restrict__ Q, const float* __restrict__ Kp,
                                                             const float* __restrict__ Vt, float* __restrict__ out,
@@ -48,7 +51,13 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
 #endif
 #ifdef PM_ATTN_SEG
     const unsigned char* segb = key_seg + (size_t)b * Nkv;  // this image's key segments; keys at or beyond Nkv are padding
+#ifdef PM_ATTN_BIAS
+    const float* biasb = key_bias + (size_t)b * Nkv;         // this image's key biases; -inf = the key is padding
+    auto seg_of = [&](int key) -> unsigned { return key < Nkv && biasb[key] != -INFINITY ? (unsigned)segb[key] : 255u; };
+    auto bias_of = [&](int key) -> float { return key < Nkv ? biasb[key] : 0.f; };
+#else
     auto seg_of = [&](int key) -> unsigned { return key < Nkv ? (unsigned)segb[key] : 255u; };
+#endif
     unsigned qmask[QF];                                      // the segments this lane's query of tile qf attends to
 #pragma unroll
     for (int qf = 0; qf < QF; ++qf) {
@@ -113,7 +122,21 @@ __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __rest
     // (1) row max of half-tile hh and the rare rescale branch
     auto rowmax_rescale = [&](f32x4_t (&sc)[2][QF], int hh) {
         const int t = hh >> 1, pc = hh & 1, kv0 = t * KT;
-#ifdef PM_ATTN_SEG
+#if defined(PM_ATTN_SEG) && defined(PM_ATTN_BIAS)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int key = kv0 + 16 * (2 * pc + kk) + 4 * g + r;
+                const unsigned sg = seg_of(key);
+                const float kb = bias_of(key);                   // an allowed key's score becomes s + bias: one f32 add, before the maximum
+#pragma unroll
+                for (int qf = 0; qf < QF; ++qf) {
+                    if (!((sg < 32u) & ((qmask[qf] >> (sg & 31u)) & 1u))) sc[kk][qf][r] = -INFINITY;
+                    else sc[kk][qf][r] += kb;
+                }
+            }
+#elif defined(PM_ATTN_SEG)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll

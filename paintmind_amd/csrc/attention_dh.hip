@@ -89,10 +89,39 @@ __device__ __forceinline__ float quad_sum(float v) {
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
 #undef PM_ATTN_PICK
+// the weighted form: the per-query form plus key_bias (device f32 [B, Nkv]), log(weight) of every key in the
+// kernel's score unit; -inf = the key is skipped like padding
+#define PM_ATTN_KERNEL attention_dh_seg_bias_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias
+#define PM_ATTN_SEG 1
+#define PM_ATTN_BIAS 1
+#include "attention_dh_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_BIAS
+
+// weights -> key_bias: 0 -> -inf (excluded), 1 -> exactly 0, otherwise log2(w), times ln 2 when the scores are nats
+__global__ __launch_bounds__(256) void key_bias_kernel(const float* __restrict__ w, float* __restrict__ bias, int n, int use_exp2) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float x = w[i];
+    float r;
+    if (x == 0.f) r = -INFINITY;
+    else if (x == 1.f) r = 0.f;
+    else r = use_exp2 ? log2f(x) : log2f(x) * 0.693147180559945309f;
+    bias[i] = r;
+}
 
 template <typename T, int DPL>
 void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-               int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, hipStream_t s) {
+               int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, const float* bias, hipStream_t s) {
+    if (bias) {                                        // the weighted form: seg beside it, never pk
+        auto k = use_exp2 ? attention_dh_seg_bias_kernel<T, DPL, true> : attention_dh_seg_bias_kernel<T, DPL, false>;
+        hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
+                           Nkv, Nkp, seg->key_seg, seg->query_mask, bias);
+        return;
+    }
     if (pk) {                                          // the picked forms: exactly one of lens / seg, the geometry of the twin
         const dim3 grid((Nq + 63) / 64, B * heads);
         if (seg) {
@@ -123,9 +152,9 @@ void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo,
 // the launcher of this file's kernels: dim_head != 64, already passed through check_dh
 template <typename T>
 int pm_attention_dh(int dh, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-                    int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, hipStream_t s) {
+                    int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, const float* bias, hipStream_t s) {
     switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, seg, pk, s); break;
+#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, seg, pk, bias, s); break;
         PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
 #undef PM_DH_CASE
         default: PM_REQUIRE(false, "attention_dh: dim_head=%d not served", dh);
@@ -180,15 +209,19 @@ void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* o
                            int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s);
 void pm_attention_f32_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
                            int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s);
+void pm_attention_f32_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                               int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s);
+void pm_attention_bf16_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                                int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s);
 void pm_attention_bf16_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
                             int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s);
 
 // Every attention entry point ends here: the arguments are checked once, then one launcher per kernel file.  lens = device
 // int32 [B], the per-image key counts, or NULL (one key count for the launch); seg = the per-query key sets (device arrays), or NULL;
-// pk = the picked forms (exactly one of lens / seg beside it), or NULL.
+// pk = the picked forms (exactly one of lens / seg beside it), or NULL; bias = the weighted form (seg beside it, no pk), or NULL.
 static int attention_any(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                          int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s,
-                         const PmAttnSeg* seg = nullptr, const PmAttnPick* pk = nullptr) {
+                         const PmAttnSeg* seg = nullptr, const PmAttnPick* pk = nullptr, const float* bias = nullptr) {
     const bool tuned = dim_head == 64;               // the MFMA kernels; otherwise this file's plain path
     if (!tuned) PM_TRY(check_dh(who, heads, dim_head));
     PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "%s: bad dtype %d", who, dtype);
@@ -204,8 +237,11 @@ static int attention_any(const char* who, int dtype, const void* Q, const void* 
     if (!tuned) PM_REQUIRE((long long)B * heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)B * heads);
     PmTimer tm(FAM_ATTENTION, s);
     if (!tuned) {
-        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s));
-        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s));
+        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, bias, s));
+        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, bias, s));
+    } else if (bias) {
+        if (dtype == PMHIP_F32) pm_attention_f32_seg_bias(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, s);
+        else pm_attention_bf16_seg_bias(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, s);
     } else if (pk) {
         if (dtype == PMHIP_F32) pm_attention_f32_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, *pk, s);
         else pm_attention_bf16_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, *pk, s);
@@ -245,6 +281,25 @@ extern "C" int pmhip_attention_segments(int dtype, const void* Q, const void* K,
     const PmAttnSeg seg{key_seg, query_mask};
     return attention_any("attention_segments", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
                          (hipStream_t)stream, &seg);
+}
+
+extern "C" int pmhip_attention_weighted(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                                        int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
+                                        const uint32_t* query_mask, const float* key_bias, pmhip_stream stream) {
+    PM_REQUIRE(key_seg && query_mask && key_bias,
+               "attention_weighted: key_seg / query_mask / key_bias is NULL (pmhip_attention_segments is the entry without weights)");
+    const PmAttnSeg seg{key_seg, query_mask};
+    return attention_any("attention_weighted", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
+                         (hipStream_t)stream, &seg, nullptr, key_bias);
+}
+
+extern "C" int pmhip_key_bias(const float* weights, float* bias, int n, int use_exp2, pmhip_stream stream) {
+    PM_REQUIRE(weights && bias, "key_bias: null pointer");
+    PM_REQUIRE(n > 0, "key_bias: n=%d must be positive", n);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(key_bias_kernel, dim3((n + 255) / 256), dim3(256), 0, s, weights, bias, n, use_exp2);
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
 }
 
 extern "C" int pmhip_attention_pick(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,

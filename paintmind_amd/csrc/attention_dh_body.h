@@ -5,6 +5,9 @@
 // 4u: a key whose segment the query does not attend to (or padding, 255) is skipped -- its score and its V column are read by no update.
 // A FOURTH and a FIFTH inclusion with PM_ATTN_PICK beside PM_ATTN_LENS / PM_ATTN_SEG (attention_dh_lens_pick_kernel,
 // attention_dh_seg_pick_kernel; two more parameters pick, want) are the picked forms of DESIGN.md 4v.
+// A SIXTH inclusion with PM_ATTN_BIAS beside PM_ATTN_SEG (attention_dh_seg_bias_kernel; one more parameter key_bias, device f32
+// [B, Nkv]) is the weighted form of DESIGN.md 4w: an allowed key's score becomes s + key_bias[b, k] before it meets the running
+// maximum, and a key whose bias is -inf is skipped like padding.
 template <typename T, int DPL, bool EXP2>
 __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ Vt,
                                                           T* __restrict__ out, int ldo, int heads, int Nq, int Nkv, int Nkp PM_ATTN_LENS_PARAM) {
@@ -34,6 +37,9 @@ __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, c
     const unsigned char* segb = key_seg + (size_t)b * Nkv;
     const unsigned qm = query_mask[(size_t)b * Nq + qr];
 #endif
+#ifdef PM_ATTN_BIAS
+    const float* biasb = key_bias + (size_t)b * Nkv;
+#endif
     for (int j = 0; j < Nkv; ++j) {
         float s = 0.f;
 #pragma unroll
@@ -42,6 +48,11 @@ __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, c
 #ifdef PM_ATTN_SEG
         const unsigned sg = segb[j];                            // (the four lanes of a query agree: the quad stays whole)
         if (!((sg < 32u) & ((qm >> (sg & 31u)) & 1u))) continue;
+#endif
+#ifdef PM_ATTN_BIAS
+        const float kb = biasb[j];                              // (wave-uniform address: the quad stays whole here too)
+        if (kb == -INFINITY) continue;
+        s += kb;
 #endif
         const float mn = fmaxf(m, s);
         const float a = EXP2 ? exp2f(m - mn) : expf(m - mn);

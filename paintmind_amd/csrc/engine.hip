@@ -203,6 +203,9 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     // a slots step with regional and plain slots side by side, THIS call's or NULL: device uint8 [B], 1 = the image
     // runs under its key sets, 0 = under its length.  Only then `lens` and the segments stand side by side: two picked launches.
     const uint8_t* pick = nullptr;
+    // prompt weights, THIS call's or NULL: device f32 [B, L], log(weight) of every context row in the score unit of
+    // the handle's dtype (-inf = excluded).  Always beside key_seg / query_mask (the caller's or the neutral ones), never beside pick.
+    const float* key_bias = nullptr;
 };
 
 // The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
@@ -452,7 +455,10 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
                                             cross->lens, nullptr, nullptr, cross->pick, 0, s));
                 PM_TRY(pmhip_attention_pick(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
                                             nullptr, cross->key_seg, cross->query_mask, cross->pick, 1, s));
-            } else if (cross->key_seg)
+            } else if (cross->key_bias)
+                PM_TRY(pmhip_attention_weighted(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
+                                                cross->key_seg, cross->query_mask, cross->key_bias, s));
+            else if (cross->key_seg)
                 PM_TRY(pmhip_attention_segments(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
                                                 cross->key_seg, cross->query_mask, s));
             else if (cross->lens)
@@ -791,6 +797,7 @@ struct pmhip_s2 {
     PinnedRing slots_ring;
     PinnedRing lens_ring;           // per-image context lengths of a call (ctx_lens_host): B int32 -> workspace "ctx.lens"
     PinnedRing neg_lens_ring;       // ... and of its negative context (neg_lens_host): B int32 -> workspace "neg.lens"
+    PinnedRing w_ring;              // prompt weights: B * L f32 -> workspace "ctx.w", from where pmhip_key_bias fills "ctx.bias"
     PinnedRing seg_ring;            // regional prompts: B * tokens uint32 token masks, then B * L uint8 row segments -> workspace "ctx.seg"
     PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
     int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
@@ -894,7 +901,7 @@ int s2_prepare_context(pmhip_s2* h, const float* context, int L, int B, hipStrea
         const unsigned char* wkv = reinterpret_cast<const unsigned char*>(h->layers[l].wqkv2) + (size_t)inner * dim * es;
         PM_TRY(pmhip_gemm_heads_dh(h->dtype, cp, dim, wkv, dim, Mc, dim, heads, dh, L, Lp, 2, kinds, outs, 1.0f, split, s));
         cs.kv[l].k = outs[0]; cs.kv[l].vt = outs[1]; cs.kv[l].L = L; cs.kv[l].Lp = Lp; cs.kv[l].lens = nullptr;
-        cs.kv[l].key_seg = nullptr; cs.kv[l].query_mask = nullptr; cs.kv[l].pick = nullptr;
+        cs.kv[l].key_seg = nullptr; cs.kv[l].query_mask = nullptr; cs.kv[l].pick = nullptr; cs.kv[l].key_bias = nullptr;
     }
     return PMHIP_OK;
 }
@@ -930,6 +937,7 @@ int s2_set_ctx_lens(pmhip_s2* h, const int32_t* lens_host, int L, int B, hipStre
         ck.lens = ck.k ? dlens : nullptr;
         ck.key_seg = nullptr; ck.query_mask = nullptr;        // the segments of an earlier call are dropped with its lengths
         ck.pick = nullptr;
+        ck.key_bias = nullptr;                                // ... and so are its weights
     }
     return PMHIP_OK;
 }
@@ -994,6 +1002,75 @@ int s2_set_segments(pmhip_s2* h, const uint8_t* ctx_seg_host, const uint32_t* to
     PM_TRY(h->seg_ring.commit(s));
     for (auto& ck : h->cross)
         if (ck.k) { ck.query_mask = reinterpret_cast<const uint32_t*>(dseg); ck.key_seg = dseg + qbytes; ck.pick = dpick; }
+    return PMHIP_OK;
+}
+
+// Prompt weights (the *_weights entries), checked BEFORE anything is launched, behind check_ctx_lens and check_segments.
+// ctx_w_host f32 [B, L]: the weight of every context row, 0 or in [2^-20, 2^20].  They need a context; they stand beside the pair of
+// segment arrays, beside ctx_lens_host, or alone -- without segment arrays the engine stages NEUTRAL ones: segment 0 for the rows
+// below the image's length, 255 behind, every token mask all ones.  Every token must allow a row with w > 0.
+struct CtxWeights {
+    const float* w = nullptr;                                 // the caller's array, or NULL: no weights, everything below is the caller's
+    std::vector<uint8_t> kseg;                                // the neutral arrays, when the caller gave none
+    std::vector<uint32_t> tseg;
+    const uint8_t* seg = nullptr;                             // what s2_set_segments stages
+    const uint32_t* tok = nullptr;
+    const int32_t* lens = nullptr;                            // what s2_set_ctx_lens stages: the caller's lengths, or NULL under weights
+};
+int check_weights(const char* who, const float* ctx_w_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const int32_t* ctx_lens_host,
+                  bool have_context, int L, int B, const pmhip_s2* h, CtxWeights& out) {
+    out.w = ctx_w_host; out.seg = ctx_seg_host; out.tok = tok_seg_host; out.lens = ctx_lens_host;
+    if (!ctx_w_host) return PMHIP_OK;
+    PM_REQUIRE(have_context && L > 0, "%s: weights given without a context", who);
+    const int tokens = h->cfg.tokens;
+    for (int b = 0; b < B; ++b)
+        for (int k = 0; k < L; ++k) {
+            const float w = ctx_w_host[(size_t)b * L + k];
+            PM_REQUIRE(std::isfinite(w) && (w == 0.f || (w >= 0x1p-20f && w <= 0x1p20f)),
+                       "%s: image %d: context row %d: weight %g must be 0 or in [2^-20, 2^20]", who, b, k, (double)w);
+        }
+    if (!ctx_seg_host) {                                      // (check_segments has seen to it that both are NULL then)
+        out.kseg.assign((size_t)B * L, 0);
+        out.tseg.assign((size_t)B * tokens, 0xffffffffu);
+        for (int b = 0; ctx_lens_host && b < B; ++b)
+            for (int k = ctx_lens_host[b]; k < L; ++k) out.kseg[(size_t)b * L + k] = 255;
+        out.seg = out.kseg.data(); out.tok = out.tseg.data();
+    }
+    out.lens = nullptr;                                       // the padding value subsumes the length
+    for (int b = 0; b < B; ++b) {
+        uint32_t present = 0;                                 // segments with a row of weight > 0
+        for (int k = 0; k < L; ++k) {
+            const int sg = out.seg[(size_t)b * L + k];
+            if (sg < 32 && ctx_w_host[(size_t)b * L + k] > 0.f) present |= 1u << sg;
+        }
+        for (int t = 0; t < tokens; ++t)
+            PM_REQUIRE(out.tok[(size_t)b * tokens + t] & present,
+                       "%s: image %d: token %d allows no context row with a weight above 0 (mask 0x%08x, segments with such a row 0x%08x)", who, b,
+                       t, (unsigned)out.tok[(size_t)b * tokens + t], (unsigned)present);
+    }
+    return PMHIP_OK;
+}
+
+// The checked weights travel like the segments: pinned ring entry -> copy kernel -> the handle's device array "ctx.w" -> the conversion
+// kernel (pmhip_key_bias, in the score unit of the handle's dtype) -> the handle's device array "ctx.bias" -> every layer's CrossKV of
+// the context's set, from where the cross-attention launch of layer_forward hands it to pmhip_attention_weighted.  Called right behind
+// s2_set_segments, always outside a graph: a captured graph bakes in the bias array, never a weight.
+int s2_set_weights(pmhip_s2* h, const float* ctx_w_host, int L, int B, hipStream_t s) {
+    if (!ctx_w_host) return PMHIP_OK;
+    const size_t n = (size_t)B * L, bytes = (n * 4 + 15) & ~(size_t)15;
+    float* dw;
+    float* dbias;
+    WS(h->ws, "ctx.w", bytes, dw);
+    WS(h->ws, "ctx.bias", bytes, dbias);
+    std::vector<float> padded(bytes / 4, 0.f);
+    std::copy(ctx_w_host, ctx_w_host + n, padded.begin());
+    PM_TRY(h->w_ring.reserve(bytes));
+    PM_TRY(h->w_ring.acquire());
+    PM_TRY(h->w_ring.stage(dw, 0, padded.data(), bytes, s));
+    PM_TRY(h->w_ring.commit(s));
+    PM_TRY(pmhip_key_bias(dw, dbias, (int)n, h->dtype == PMHIP_BF16, s));
+    for (auto& ck : h->cross)
+        if (ck.k) ck.key_bias = dbias;
     return PMHIP_OK;
 }
 
@@ -1295,15 +1372,18 @@ int run_graphs(pmhip_s2* s2, pmhip_vqgan* vq, GraphEntry& ge, size_t n_units, hi
 
 static int s2_forward_impl(const char* who, pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
                            float* logits_out, pmhip_stream stream, const uint8_t* ctx_seg_host = nullptr,
-                           const uint32_t* tok_seg_host = nullptr) {
+                           const uint32_t* tok_seg_host = nullptr, const float* ctx_w_host = nullptr) {
     PM_REQUIRE(h && tokens && logits_out && B > 0, "%s: bad arguments", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
     PM_TRY(check_segments(who, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, h));
+    CtxWeights cw;
+    PM_TRY(check_weights(who, ctx_w_host, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, h, cw));
     hipStream_t s = (hipStream_t)stream;
     const int M = B * h->cfg.tokens;
     PM_TRY(s2_prepare_context(h, context, L, B, s));
-    PM_TRY(s2_set_ctx_lens(h, ctx_lens_host, L, B, s));
-    PM_TRY(s2_set_segments(h, ctx_seg_host, tok_seg_host, L, B, s));
+    PM_TRY(s2_set_ctx_lens(h, cw.lens, L, B, s));
+    PM_TRY(s2_set_segments(h, cw.seg, cw.tok, L, B, s));
+    PM_TRY(s2_set_weights(h, cw.w, L, B, s));
     void* tp;
     PM_TRY(tok_buf(h, M, tp, s));
     PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
@@ -1337,6 +1417,13 @@ extern "C" int pmhip_s2_forward_segments(pmhip_s2* h, const float* tokens, const
                            stream, ctx_seg_host, tok_seg_host);
 }
 
+// ctx_w_host == NULL: exactly pmhip_s2_forward_segments
+extern "C" int pmhip_s2_forward_weights(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const uint8_t* ctx_seg_host,
+                                        const uint32_t* tok_seg_host, const float* ctx_w_host, float* logits_out, pmhip_stream stream) {
+    const char* who = ctx_w_host ? "s2_forward_weights" : ctx_seg_host || tok_seg_host ? "s2_forward_segments" : "s2_forward";
+    return s2_forward_impl(who, h, tokens, context, L, B, nullptr, logits_out, stream, ctx_seg_host, tok_seg_host, ctx_w_host);
+}
+
 // The sample family's one builder: the argument list of pmhip_pipeline_sample_nucleus, the widest entry, -> the Step and the name
 // the messages carry.  A narrower entry passes the neutral values (include/pmhip.h) and `narrow`, the name its messages carry when
 // neither a nucleus mass nor a choice temperature is in play: its own, or the *_lens entry's for the two entries above that one.
@@ -1345,12 +1432,13 @@ static int pipeline_sample_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* v
                                 uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out, float* score_out, int guided,
                                 float guidance_scale, float choice_t, const float* choice_noise, float top_p, pmhip_stream stream,
                                 const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
-                                const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr) {
+                                const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr,
+                                const float* ctx_w_host = nullptr) {
     PM_TRY(pm_check_top_p("pipeline_sample_nucleus", top_p));
     const char* wide = top_p != 1.f ? "pipeline_sample_nucleus" : "pipeline_sample_choice";
     PM_TRY(pm_check_choice_t(wide, choice_t));
     PM_TRY(check_negative("pipeline_sample_negative", neg_context, Ln, neg_lens_host, false, guided != 0, context && L > 0, B));
-    const char* who = ctx_seg_host || tok_seg_host ? "pipeline_sample_segments"
+    const char* who = ctx_w_host ? "pipeline_sample_weights" : ctx_seg_host || tok_seg_host ? "pipeline_sample_segments"
                       : neg_context ? "pipeline_sample_negative" : top_p != 1.f || choice_t != 0.f ? wide : narrow;
     Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
     if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }     // 0: no given uniforms to ignore
@@ -1360,10 +1448,13 @@ static int pipeline_sample_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* v
     PM_REQUIRE(!st.guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
     PM_TRY(check_segments(who, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, s2));
+    CtxWeights cw;
+    PM_TRY(check_weights(who, ctx_w_host, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, s2, cw));
     hipStream_t s = (hipStream_t)stream;
     PM_TRY(s2_prepare_context(s2, context, L, B, s));         // (drops the negative set of an earlier call)
-    PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
-    PM_TRY(s2_set_segments(s2, ctx_seg_host, tok_seg_host, L, B, s));   // the context's set only: the other passes never see segments
+    PM_TRY(s2_set_ctx_lens(s2, cw.lens, L, B, s));
+    PM_TRY(s2_set_segments(s2, cw.seg, cw.tok, L, B, s));     // the context's set only: the other passes never see segments
+    PM_TRY(s2_set_weights(s2, cw.w, L, B, s));                // ... or weights
     if (neg_context) {
         PM_TRY(s2_prepare_context(s2, neg_context, Ln, B, s, kCrossNegative));
         PM_TRY(s2_set_ctx_lens(s2, neg_lens_host, Ln, B, s, kCrossNegative));
@@ -1439,6 +1530,19 @@ extern "C" int pmhip_pipeline_sample_segments(pmhip_s2* s2, pmhip_vqgan* vq, int
                                 neg_context, Ln, neg_lens_host, ctx_seg_host, tok_seg_host);
 }
 
+// ctx_w_host == NULL: exactly pmhip_pipeline_sample_segments
+extern "C" int pmhip_pipeline_sample_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                             const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
+                                             uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
+                                             float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
+                                             float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                             const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const float* ctx_w_host,
+                                             pmhip_stream stream) {
+    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
+                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream,
+                                neg_context, Ln, neg_lens_host, ctx_seg_host, tok_seg_host, ctx_w_host);
+}
+
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
 static bool direct_dispatch_off() {
     static const bool off = [] { const char* e = getenv("AMD_DIRECT_DISPATCH"); return e && atoi(e) == 0; }();
@@ -1467,6 +1571,8 @@ struct GenCall {
     const int32_t* nmask_img = nullptr;
     // pmhip_pipeline_generate_segments: regional prompts, host uint8 [B, L] and uint32 [B, tokens], or both NULL
     const uint8_t* ctx_seg = nullptr; const uint32_t* tok_seg = nullptr;
+    // pmhip_pipeline_generate_weights: prompt weights, host f32 [B, L], or NULL
+    const float* ctx_w = nullptr;
     bool guided() const { return guidance || gscales; }
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
@@ -1548,6 +1654,8 @@ int pipeline_generate(const GenCall& c) {
     PM_REQUIRE(!c.guided() || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
     PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
     PM_TRY(check_segments(c.who, c.ctx_seg, c.tok_seg, c.ctx_lens, c.context != nullptr, c.L, B, s2));
+    CtxWeights cw;
+    PM_TRY(check_weights(c.who, c.ctx_w, c.ctx_seg, c.tok_seg, c.ctx_lens, c.context != nullptr, c.L, B, s2, cw));
     const bool sched = c.gscales != nullptr, neg = c.neg_context != nullptr;
     // the choice temperatures, checked before anything is launched; all zero IS the loop without them (same kernels, same graphs)
     bool choice = false;
@@ -1558,8 +1666,9 @@ int pipeline_generate(const GenCall& c) {
     hipStream_t s = (hipStream_t)c.stream;
     hipStream_t cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
     PM_TRY(s2_prepare_context(s2, c.context, c.L, B, s));     // context projection + cross K/V: once per loop, eager
-    PM_TRY(s2_set_ctx_lens(s2, c.ctx_lens, c.L, B, s));       // the lengths: device memory the (captured) cross-attention launches read
-    PM_TRY(s2_set_segments(s2, c.ctx_seg, c.tok_seg, c.L, B, s));   // ... and the segments, likewise (the context's set only)
+    PM_TRY(s2_set_ctx_lens(s2, cw.lens, c.L, B, s));          // the lengths: device memory the (captured) cross-attention launches read
+    PM_TRY(s2_set_segments(s2, cw.seg, cw.tok, c.L, B, s));   // ... and the segments, likewise (the context's set only)
+    PM_TRY(s2_set_weights(s2, cw.w, c.L, B, s));              // ... and the weights' bias array
     if (neg) {                                                // the negative set: one more preparation per loop, eager like the first
         PM_TRY(s2_prepare_context(s2, c.neg_context, c.Ln, B, s, kCrossNegative));
         PM_TRY(s2_set_ctx_lens(s2, c.neg_lens, c.Ln, B, s, kCrossNegative));
@@ -1702,8 +1811,9 @@ int pipeline_generate(const GenCall& c) {
     const std::vector<Unit> units = plan_units(c, overlap);
     key += overlap ? "o1" : "o0";
     if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
-    if (c.ctx_lens) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
+    if (c.ctx_lens && !c.ctx_w) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
     if (c.ctx_seg) key += "s";                                // the per-query form of the cross-attention kernel; the layout of regions is not in the key
+    if (c.ctx_w) key += "w";                                  // the weighted form of the cross-attention kernel; neither the weights nor the layout are in the key
     if (edit) key += "e";                                     // the counts form of the re-masking kernel and the merged decode; the counts are not in the key
     if (choice) key += "c";                                   // the choice form of the re-masking kernel; the temperatures are not in the key
     if (c.top_p < 1.f) {                                      // the nucleus kernel, the mass its argument in the captured graph: one graph per value
@@ -1769,7 +1879,8 @@ static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan*
                                   int guided, float guidance_scale, const float* ctemps_host, float top_p,
                                   const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
                                   const float* gscales_host = nullptr, const int32_t* nmask_img_host = nullptr,
-                                  const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr) {
+                                  const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr,
+                                  const float* ctx_w_host = nullptr) {
     PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
     const char* neg_who = nmask_img_host ? narrow : "pipeline_generate_negative";
     PM_TRY(check_negative(neg_who, neg_context, Ln, neg_lens_host, gscales_host != nullptr, guided != 0, context && L > 0, B));
@@ -1786,6 +1897,8 @@ static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan*
     c.nmask_img = nmask_img_host;
     c.ctx_seg = ctx_seg_host; c.tok_seg = tok_seg_host;
     if (ctx_seg_host || tok_seg_host) c.who = "pipeline_generate_segments";
+    c.ctx_w = ctx_w_host;
+    if (ctx_w_host) c.who = "pipeline_generate_weights";
     return pipeline_generate(c);
 }
 
@@ -1864,6 +1977,21 @@ extern "C" int pmhip_pipeline_generate_segments(pmhip_s2* s2, pmhip_vqgan* vq, i
                                   topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
                                   guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host, nullptr, ctx_seg_host,
                                   tok_seg_host);
+}
+
+// ctx_w_host == NULL: exactly pmhip_pipeline_generate_segments
+extern "C" int pmhip_pipeline_generate_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
+                                               const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
+                                               const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
+                                               float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
+                                               pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
+                                               float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
+                                               const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
+                                               const float* ctx_w_host) {
+    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
+                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
+                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host, nullptr, ctx_seg_host,
+                                  tok_seg_host, ctx_w_host);
 }
 
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged

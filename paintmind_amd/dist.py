@@ -98,7 +98,8 @@ def generate_sharded(pipe, text, seed, group=None, dst=0, timesteps=18, save_int
         if len(cl) != len(text):
             raise ValueError(f"context_lens: {len(cl)} lengths for {len(text)} prompts")
         kwargs = dict(kwargs, context_lens=cl[lo:hi])
-    for name in ("regions", "context_segments", "token_segments"):   # regional prompts: every rank takes the rows of its images
+    # regional prompts and prompt weights: every rank takes the rows of its images
+    for name in ("regions", "context_segments", "token_segments", "context_weights"):
         if kwargs.get(name) is not None:
             if len(kwargs[name]) != len(text):
                 raise ValueError(f"{name}: {len(kwargs[name])} entries for {len(text)} prompts")

@@ -319,16 +319,36 @@ class S2Engine:
         cs, ts = ops.host_segments(context_segments, token_segments, B, L, self.tokens)
         return (np.ctypeslib.as_ctypes(cs.reshape(-1)), np.ctypeslib.as_ctypes(ts.reshape(-1)))
 
-    def forward(self, tokens, context=None, context_lens=None, context_segments=None, token_segments=None):
+    def _weights(self, context_weights, context_segments, token_segments, context, context_lens, B, L, native_lens=True):
+        """prompt weights: context_weights [B, L] (None = the call as without them) -> (seg, w) with
+        seg = the pair of ``_segments`` or (None, None) and w a ctypes float32 [B * L] for ctx_w_host, or None; checked here
+        (``ops.host_weights``) and again by the native entry.  Without segment arrays the native entry stages the neutral ones from
+        ctx_lens_host; an entry without that argument (native_lens False) gets them from here when there are lengths."""
+        if context_weights is None:
+            return None
+        if context is None and L == 0:
+            raise ValueError("context_weights need a context (context None IS the unconditional branch)")
+        cs, ts, w = ops.host_weights(context_weights, B, L, self.tokens, context_segments, token_segments, context_lens)
+        given = context_segments is not None or (context_lens is not None and not native_lens)
+        seg = (np.ctypeslib.as_ctypes(cs.reshape(-1)), np.ctypeslib.as_ctypes(ts.reshape(-1))) if given else (None, None)
+        return seg, np.ctypeslib.as_ctypes(w.reshape(-1))
+
+    def forward(self, tokens, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """context_segments / token_segments (None = the call as without them): regional prompts, see ``_segments``
-        (pmhip_s2_forward_segments)."""
+        (pmhip_s2_forward_segments).  context_weights (None = the call as without them): prompt weights, see ``_weights``
+        (pmhip_s2_forward_weights)."""
         tokens = tokens.to(self.device, torch.float32).contiguous()
         B = tokens.shape[0]
         context, L = self._ctx(context)
+        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L, native_lens=False)
         lens = self._lens(context_lens, context, B, L)
-        seg = self._segments(context_segments, token_segments, context, context_lens, B, L)
+        seg = None if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L)
         logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
+            if wts is not None:
+                check(self.lib.pmhip_s2_forward_weights(self.handle, _p(tokens), _p(context), L, B, wts[0][0], wts[0][1], wts[1], _p(logits),
+                                                        stream_ptr(self.device)), "pmhip_s2_forward_weights")
+                return logits
             if seg is not None:
                 check(self.lib.pmhip_s2_forward_segments(self.handle, _p(tokens), _p(context), L, B, seg[0], seg[1], _p(logits),
                                                          stream_ptr(self.device)), "pmhip_s2_forward_segments")
@@ -339,8 +359,10 @@ class S2Engine:
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
                want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None,
-               top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None):
+               top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
+        context_weights (None = the calls below): prompt weights, see ``_weights``; only the pass with the context sees them
+        (pmhip_pipeline_sample_weights).
         context_segments / token_segments (None = the calls below): regional prompts, see ``_segments``; only the pass with the
         context sees them (pmhip_pipeline_sample_segments).
         negative_context fp32 [B, Ln, context_dim] (None = the calls below, as without the keyword): the second tower of the guided
@@ -358,8 +380,9 @@ class S2Engine:
         ct = ops.choice_t(choice_temperature)
         nucleus = ops.nucleus_p(top_p)
         context, L = self._ctx(context)
+        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L)
         lens = self._lens(context_lens, context, B, L)
-        seg = self._segments(context_segments, token_segments, context, context_lens, B, L)
+        seg = None if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L)
         img = vq_engine._new_img(B) if want_img else None
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
@@ -376,7 +399,10 @@ class S2Engine:
                 int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img), _p(pred),
                 _p(score), int(guidance_scale is not None), float(guidance_scale or 0.0), ct, _p(choice_noise if ct else None), nucleus)
         with torch.cuda.device(self.device):
-            if seg is not None:
+            if wts is not None:
+                check(self.lib.pmhip_pipeline_sample_weights(*args, _p(neg), Ln, neg_lens, wts[0][0], wts[0][1], wts[1], stream_ptr(self.device)),
+                      "pmhip_pipeline_sample_weights")
+            elif seg is not None:
                 check(self.lib.pmhip_pipeline_sample_segments(*args, _p(neg), Ln, neg_lens, seg[0], seg[1], stream_ptr(self.device)),
                       "pmhip_pipeline_sample_segments")
             elif neg is None:                     # without a negative context the native call is the one made before there was one
@@ -545,8 +571,11 @@ class S2Engine:
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
                  host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
                  choice_temps=None, top_p=None, negative_context=None, negative_lens=None, guidance_scales=None, nmask_img=None,
-                 context_segments=None, token_segments=None):
+                 context_segments=None, token_segments=None, context_weights=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
+
+        context_weights (None = the loops below): prompt weights, see ``_weights`` (pmhip_pipeline_generate_weights); the captured
+        loop reads their bias array from device memory: one graph serves every set of weights.
 
         context_segments / token_segments (None = the loops below): regional prompts, see ``_segments``
         (pmhip_pipeline_generate_segments); the captured loop reads them from device memory: one graph serves every layout.
@@ -583,10 +612,13 @@ class S2Engine:
             vals = [ops.choice_t(v, f"generate: step {i}: choice temperature") for i, v in enumerate(choice_temps)]
             choice_temps = (C.c_float * T)(*vals) if any(vals) else None
         context, L = self._ctx(context)
+        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L)
         lens = self._lens(context_lens, context, B, L)
-        seg = self._segments(context_segments, token_segments, context, context_lens, B, L)
+        seg = None if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L)
         if seg is not None and nmask_img is not None:
             raise ValueError("generate: the edit loop takes no regional prompts")
+        if wts is not None and nmask_img is not None:
+            raise ValueError("generate: the edit loop takes no prompt weights")
         n_dec = int(sum(1 for f in decode_flags if f))
         imgs = None
         if n_dec and (want_device_imgs or host is None):
@@ -623,7 +655,10 @@ class S2Engine:
             args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
                     temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
                     host_stride, copy_stream, int(guided), float(guidance_scale or 0.0), choice_temps, nucleus)
-            if seg is not None:
+            if wts is not None:
+                check(self.lib.pmhip_pipeline_generate_weights(*args, _p(neg), Ln, neg_lens, gscales, wts[0][0], wts[0][1], wts[1]),
+                      "pmhip_pipeline_generate_weights")
+            elif seg is not None:
                 check(self.lib.pmhip_pipeline_generate_segments(*args, _p(neg), Ln, neg_lens, gscales, seg[0], seg[1]),
                       "pmhip_pipeline_generate_segments")
             elif nmask_img is not None:

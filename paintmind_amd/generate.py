@@ -128,8 +128,14 @@ def region_layout(contexts, masks, image_size, patch_size):
 
 
 def _seg_kw(segments, lo=None, hi=None):
-    """the regional prompts' checked arrays (or None) as the keywords the engine and the modules take, of images [lo, hi)"""
-    return {} if segments is None else dict(context_segments=segments[0][lo:hi], token_segments=segments[1][lo:hi])
+    """the regional prompts' checked arrays (or None) as the keywords the engine and the modules take, of images [lo, hi); a third
+    array is the prompt weights that travel with them"""
+    if segments is None:
+        return {}
+    kw = dict(context_segments=segments[0][lo:hi], token_segments=segments[1][lo:hi])
+    if len(segments) == 3:
+        kw["context_weights"] = segments[2][lo:hi]
+    return kw
 
 
 class _Options(NamedTuple):
@@ -405,10 +411,16 @@ class Pipeline(nn.Module):
         return _Options(self._topk(topk), top_p, guidance_scale, self._lens(context_lens, context, B), base, negative, negative_lens,
                         scales)
 
-    def _segments(self, context_segments, token_segments, context, context_lens, B):
+    def _segments(self, context_segments, token_segments, context, context_lens, B, context_weights=None):
         """context_segments [B, L] / token_segments [B, N] (lists, arrays or tensors; both None pass through) -> the two checked
         host arrays of ``ops.host_segments`` (numpy uint8 [B, L], numpy uint32 [B, N]), brought to the host ONCE per call.  They
-        travel beside the call's ``_Options``, not in it: they need the context and exclude context_lens."""
+        travel beside the call's ``_Options``, not in it: they need the context and exclude context_lens.
+        context_weights [B, L] (None: as above): -> the three checked host arrays of ``ops.host_weights``; without segment arrays
+        the first two are the neutral ones, which carry context_lens -- the caller drops the lengths from its ``_Options``."""
+        if context_weights is not None:
+            if context is None:
+                raise ValueError("context_weights need a text condition (text=None IS the unconditional branch)")
+            return ops.host_weights(context_weights, B, context.shape[1], self.num_tokens, context_segments, token_segments, context_lens)
         if context_segments is None and token_segments is None:
             return None
         if context is None:
@@ -417,7 +429,7 @@ class Pipeline(nn.Module):
             raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
         return ops.host_segments(context_segments, token_segments, B, context.shape[1], self.num_tokens)
 
-    def tokens2logits(self, token, text=None, context_lens=None, context_segments=None, token_segments=None):
+    def tokens2logits(self, token, text=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """context_lens (extension; None = the reference's behaviour, every row of the context is attended to): one length per
         image -- rows [len_b, L) of image b's context never reach its logits, NaN included.
 
@@ -425,9 +437,17 @@ class Pipeline(nn.Module):
         beside context_lens): row k of image b's context belongs to segment context_segments[b, k] in 0..31 (-1 or 255: padding,
         which never reaches the logits, NaN included), and token t attends to exactly the rows whose segment is a set bit of
         token_segments[b, t].  Every token must allow a segment that is present in its image.  ``generate(regions=)`` builds both
-        from prompts and masks."""
+        from prompts and masks.
+
+        context_weights [B, L] (extension, PROMPT WEIGHTS; beside the two segment arrays, beside context_lens,
+        or alone): how much a context row counts -- over the rows a token attends to, p = w exp(s) / sum w exp(s).  1 is the row as
+        without weights, an integer n the row repeated n times, 0 a padding row; otherwise 2^-20 <= w <= 2^20.  Every token must
+        allow a row with a weight above 0.  ``generate(prompt_weights=True)`` reads them from ``(words:1.3)`` in the prompts."""
         lens = self._lens(context_lens, text, token.shape[0])
-        kw = _seg_kw(self._segments(context_segments, token_segments, text, context_lens, token.shape[0]))
+        segments = self._segments(context_segments, token_segments, text, lens, token.shape[0], context_weights)
+        kw = _seg_kw(segments)
+        if context_weights is not None:
+            lens = None                                           # (the neutral segments carry them)
         if self._on_cpu():
             return self.transformer(token, text, lens, **kw)   # plain-torch operators of this package (no HIP engine on the CPU)
         return self.engine().forward(token, text, context_lens=lens, **kw)
@@ -444,8 +464,11 @@ class Pipeline(nn.Module):
     @torch.no_grad()
     def sample(self, ids, mask_ratio, text=None, topk=1, temperature=1, noise=None, seed=None, step=0, image_base=0,
                guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None, top_p=None, negative_text=None,
-               negative_context_lens=None, context_segments=None, token_segments=None):
+               negative_context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """One MaskGIT step (generate.py:159-181) -> (ids', img).
+
+        ``context_weights`` (extension; None = the step as without them): prompt weights, see ``tokens2logits``.  Like the segments,
+        only the forward with ``text`` sees them.
 
         ``context_segments`` / ``token_segments`` (extension; None = the step as without them): regional prompts, see
         ``tokens2logits``.  Only the forward with ``text`` sees them: the second forward of a guided step -- without a context or with
@@ -486,7 +509,9 @@ class Pipeline(nn.Module):
         nm = num_token_masked(mask_ratio, self.num_tokens)
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, text, ids.shape[0], negative_text,
                              negative_context_lens)
-        segments = self._segments(context_segments, token_segments, text, context_lens, ids.shape[0])
+        segments = self._segments(context_segments, token_segments, text, opts.lens, ids.shape[0], context_weights)
+        if context_weights is not None:
+            opts = opts._replace(lens=None)
         return self._step(ids, nm, text, opts, temperature, opts.choice_temperature, noise, seed, step, image_base, choice_noise, segments)
 
     @torch.no_grad()
@@ -628,8 +653,12 @@ class Pipeline(nn.Module):
 
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
                      join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None,
-                     top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None):
+                     top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None,
+                     context_weights=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
+
+        context_weights [B, L] (None: the loop as without them): prompt weights, see ``tokens2logits``.  Every lane takes the rows of
+        its micro-batch; the captured loop reads their bias array from device memory, so one graph serves every set of weights.
 
         context_segments [B, L] / token_segments [B, N] (None: the loop as without them): regional prompts, see ``tokens2logits``.  Every
         lane takes the rows of its micro-batch; the captured loop reads them from device memory, so one graph serves every layout.
@@ -661,7 +690,9 @@ class Pipeline(nn.Module):
         so every lane takes it as it is; below 1 part of the key of a captured graph."""
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative_context, negative_lens,
                              timesteps)
-        segments = self._segments(context_segments, token_segments, context, context_lens, B)
+        segments = self._segments(context_segments, token_segments, context, opts.lens, B, context_weights)
+        if context_weights is not None:
+            opts = opts._replace(lens=None)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
@@ -752,8 +783,17 @@ class Pipeline(nn.Module):
     def generate(self, text, timesteps=18, temperature=1.0, topk=5, save_interval=2, seed=None, image_base=0,
                  return_ids=False, keep_on_device=False, use_graph=None, streams=None, guidance_scale=None, mask_padding=False,
                  context_lens=None, choice_temperature=None, top_p=None, negative_text=None, negative_context_lens=None, regions=None,
-                 context_segments=None, token_segments=None):
+                 context_segments=None, token_segments=None, context_weights=None, prompt_weights=False):
         """Full decode loop (generate.py:183-198): list of (B,3,H,W) CPU tensors for steps % save_interval == 0.
+
+        PROMPT WEIGHTS (extension).  prompt_weights=True: the prompts -- ``text`` and the prompts of
+        ``regions`` -- carry emphasis syntax, ``a (red:1.4) barn, (blurry:0.5)`` (``paintmind_amd.prompt.parse_weighted``), and the
+        text model is called with ``weighted=True``: every context row gets the weight of the words it came from, and the
+        cross-attention counts it that much (``tokens2logits`` has the rule).  With ``mask_padding=True`` the padding rows are
+        masked as without weights; otherwise they are attended to as before, at weight 1.  context_weights [B, L] gives the weights
+        explicitly instead, for a ``text`` that is already a context; not beside ``regions`` or ``prompt_weights``.  An item of
+        ``regions`` may be ``(prompt, mask, weight)``: the number multiplies the weight of that region's rows ("this region's
+        prompt, but weaker").  The pass without the text and a negative prompt's pass never see weights.
 
         regions (extension; None = the loop as without it): REGIONAL PROMPTS, different text for different parts of the picture -- a
         list of B lists of ``(prompt, mask)``.  ``mask`` is a pixel mask [H, W] (non-zero = inside) or a bool token mask [g, g]; a
@@ -810,10 +850,20 @@ class Pipeline(nn.Module):
         the exact rule).  A mass cut follows the model from its flat early steps to its peaked late ones, which no fixed
         ``topk`` can; with ``topk=None`` it is the only filter."""
         B = len(text)
+        if prompt_weights and context_weights is not None:
+            raise ValueError("prompt_weights=True reads the weights from the prompts: no context_weights beside it")
         if regions is not None:
             if context_lens is not None or context_segments is not None or token_segments is not None:
                 raise ValueError("regions builds the context's segments itself: no context_lens, context_segments or token_segments beside it")
-            context, context_segments, token_segments = self._region_context(text, regions, mask_padding)
+            if context_weights is not None:
+                raise ValueError("regions builds the context itself: no context_weights beside it (give a region a weight as its third element)")
+            context, context_segments, token_segments, context_weights = self._region_context_weighted(text, regions, mask_padding, prompt_weights)
+        elif prompt_weights:
+            context, lens, context_weights = self.text_model(list(text), weighted=True)
+            if context is None:
+                raise ValueError("prompt_weights needs a text model (this pipeline is unconditional)")
+            if mask_padding and context_lens is None and context_segments is None:
+                context_lens = lens
         elif mask_padding and context_lens is None and context_segments is None:
             context, context_lens = self.text_model(text, return_lens=True)
         else:
@@ -829,7 +879,9 @@ class Pipeline(nn.Module):
                 negative = self.text_model(prompts)
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative, negative_context_lens,
                              timesteps)
-        segments = self._segments(context_segments, token_segments, context, context_lens, B)
+        segments = self._segments(context_segments, token_segments, context, opts.lens, B, context_weights)
+        if context_weights is not None:
+            opts = opts._replace(lens=None)
         if self._on_cpu():
             return self._generate_cpu(context, B, timesteps, temperature, opts, save_interval, seed, return_ids, segments)
         seg_kw = _seg_kw(segments)
@@ -890,8 +942,15 @@ class Pipeline(nn.Module):
         return (out, ids) if return_ids else out
 
     def _region_context(self, text, regions, mask_padding):
-        """``generate(text, regions=)`` -> (context [B, Lmax, D], context_segments, token_segments): every prompt of every image goes
-        through the text model in ONE call; with mask_padding a prompt contributes its non-pad rows only (``region_layout``)"""
+        """``generate(text, regions=)`` without prompt weights -> (context [B, Lmax, D], context_segments, token_segments); see
+        ``_region_context_weighted``, whose first three results these are"""
+        return self._region_context_weighted(text, regions, mask_padding)[:3]
+
+    def _region_context_weighted(self, text, regions, mask_padding, prompt_weights=False):
+        """``generate(text, regions=)`` -> (context [B, Lmax, D], context_segments, token_segments, context_weights): every prompt of
+        every image goes through the text model in ONE call; with mask_padding a prompt contributes its non-pad rows only
+        (``region_layout``).  context_weights (numpy float32 [B, Lmax]) is None unless a region carries a weight -- ``(prompt, mask,
+        weight)`` -- or prompt_weights asks the text model for the weights of the words; a region's number multiplies its rows'."""
         B = len(text)
         if len(regions) != B:
             raise ValueError(f"regions: {len(regions)} lists for a batch of {B}")
@@ -900,10 +959,18 @@ class Pipeline(nn.Module):
             if len(r) > MAX_REGIONS:
                 raise ValueError(f"regions: image {b}: {len(r)} regions, at most {MAX_REGIONS} per image")
             for item in r:
-                if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], str)):
+                if not (isinstance(item, (tuple, list)) and len(item) in (2, 3) and isinstance(item[0], str)):
+                    raise ValueError(f"regions: image {b}: every region is a (prompt, mask) pair")
+                if len(item) == 3 and (isinstance(item[2], bool) or not isinstance(item[2], (int, float))):
                     raise ValueError(f"regions: image {b}: every region is a (prompt, mask) pair")
         prompts = [p for b in range(B) for p in [text[b]] + [item[0] for item in regions[b]]]
-        if mask_padding:
+        weighted = prompt_weights or any(len(item) == 3 for r in regions for item in r)
+        rows_w = None
+        if prompt_weights:
+            ctx, lens, rows_w = self.text_model(prompts, weighted=True)
+            lens = ops.host_lens(lens, len(prompts), ctx.shape[1], "regions: prompt lengths") if mask_padding and ctx is not None else \
+                ([ctx.shape[1]] * len(prompts) if ctx is not None else None)
+        elif mask_padding:
             ctx, lens = self.text_model(prompts, return_lens=True)
             lens = ops.host_lens(lens, len(prompts), ctx.shape[1], "regions: prompt lengths")
         else:
@@ -916,7 +983,22 @@ class Pipeline(nn.Module):
             n = 1 + len(regions[b])
             contexts.append([ctx[at + i, :lens[at + i]] for i in range(n)])
             at += n
-        return region_layout(contexts, [[item[1] for item in r] for r in regions], self.image_size, self.patch_size)
+        context, ctx_seg, tok_seg = region_layout(contexts, [[item[1] for item in r] for r in regions], self.image_size, self.patch_size)
+        if not weighted:
+            return context, ctx_seg, tok_seg, None
+        ctx_w = np.ones(ctx_seg.shape, np.float32)                # (rows behind an image's last prompt are padding: any weight will do)
+        at = 0
+        for b in range(B):
+            col = 0
+            for i in range(1 + len(regions[b])):
+                n = lens[at + i]
+                w = np.ones(n, np.float32) if rows_w is None else np.asarray(rows_w[at + i, :n], np.float32)
+                if i > 0 and len(regions[b][i - 1]) == 3:
+                    w = w * np.float32(regions[b][i - 1][2])
+                ctx_w[b, col:col + n] = w
+                col += n
+            at += 1 + len(regions[b])
+        return context, ctx_seg, tok_seg, ctx_w
 
     def _region_loop(self, img, coord, text, timesteps, topk, temperature, keep_inside, seed=None, return_ids=False,
                      choice_temperature=None, top_p=None):

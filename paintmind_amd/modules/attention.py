@@ -56,17 +56,19 @@ class CrossAttention(nn.Module):
             self._pack = (stamp, pk)
         return self._pack[1]
 
-    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None):
+    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         return self.run(x, context, residual=None, context_lens=context_lens, context_segments=context_segments,
-                        token_segments=token_segments)
+                        token_segments=token_segments, context_weights=context_weights)
 
-    def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None):
+    def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x.
         context_lens (extension; None = the reference's behaviour, no mask): one length per image -- image b attends to rows
         [0, context_lens[b]) of its context only; the rows beyond never reach the result, NaN included.
         context_segments [B, L] + token_segments [B, N] (extension, regional prompts; never beside context_lens): row k of image
         b's context belongs to segment context_segments[b, k] (0..31; -1 or 255 = padding, which never reaches the result), and
-        token t attends to the rows whose segment is a set bit of token_segments[b, t].  Every token must allow a present segment."""
+        token t attends to the rows whose segment is a set bit of token_segments[b, t].  Every token must allow a present segment.
+        context_weights [B, L] (extension, prompt weights; beside the segment arrays, beside context_lens, or alone): over the rows
+        a token attends to, p = w exp(s) / sum w exp(s).  A weight of 0 makes the row padding; otherwise 2^-20 <= w <= 2^20."""
         if self.training and self.to_out[1].p > 0:
             raise RuntimeError("paintmind_amd attention is inference-only (dropout>0 in training mode)")
         if context_lens is not None:
@@ -82,8 +84,16 @@ class CrossAttention(nn.Module):
             segments = context_segments, token_segments
             if not (isinstance(context_segments, np.ndarray) and context_segments.dtype == np.uint8):      # (checked already otherwise)
                 segments = ops.host_segments(context_segments, token_segments, x.shape[0], context.shape[1], x.shape[1])
+        weights = None
+        if context_weights is not None:
+            if context is None:
+                raise ValueError("context_weights need a context (self-attention takes no weights)")
+            cs, ts, weights = ops.host_weights(context_weights, x.shape[0], context.shape[1], x.shape[1],
+                                               None if segments is None else segments[0], None if segments is None else segments[1],
+                                               context_lens)
+            segments, context_lens = (cs, ts), None               # (without segment arrays: the neutral ones, which carry the lengths)
         if not x.is_cuda:
-            return self._run_cpu(x, context, residual, context_lens, segments)
+            return self._run_cpu(x, context, residual, context_lens, segments, weights)
         B, N, D = x.shape
         dtype = x.dtype
         pk = self.packed(dtype)
@@ -104,7 +114,8 @@ class CrossAttention(nn.Module):
         kv_lens = None if context_lens is None else torch.tensor(context_lens, dtype=torch.int32, device=x.device)
         if segments is not None:
             o = ops.attention(q, k, vt, n_kv, use_exp2=fast, key_segments=torch.from_numpy(segments[0]).to(x.device),
-                              query_segments=torch.from_numpy(segments[1].view(np.int32)).to(x.device))
+                              query_segments=torch.from_numpy(segments[1].view(np.int32)).to(x.device),
+                              key_weights=None if weights is None else torch.from_numpy(weights).to(x.device))
         else:
             o = ops.attention(q, k, vt, n_kv, use_exp2=fast, kv_lens=kv_lens)
         res = residual.reshape(B * N, D) if residual is not None else None
@@ -113,13 +124,15 @@ class CrossAttention(nn.Module):
         return out.reshape(B, N, D)
 
 
-    def _run_cpu(self, x, context, residual, context_lens=None, segments=None):
+    def _run_cpu(self, x, context, residual, context_lens=None, segments=None, weights=None):
         """Parameters on the CPU: the same operator in plain torch (reference modules/attention.py:43-59; BASELINE config 1
         runs the model there).  q is scaled BEFORE the product (:52), no mask, softmax over the keys, head split 'b n (h d)'.
         context_lens (a checked list, or None): scores of the keys at or beyond an image's length become -inf (whatever they
         were, NaN included) and the V rows there are ZEROED -- a probability of 0 alone would not do, 0 * NaN is NaN in P @ V.
         segments (checked numpy arrays (uint8 [B, L], uint32 [B, N]), or None): the same per QUERY -- scores of the rows a token
-        does not attend to become -inf, and the V rows of padding (segment 255) are zeroed."""
+        does not attend to become -inf, and the V rows of padding (segment 255) are zeroed.
+        weights (checked numpy float32 [B, L] beside segments, or None): log w is added to the scores of the rows with w > 0; a row
+        with w == 0 is padding."""
         B, N, _ = x.shape
         c = x if context is None else context
         if context_lens is not None and len(set(context_lens)) == 1:
@@ -137,6 +150,12 @@ class CrossAttention(nn.Module):
             allowed = torch.from_numpy(ops.segments_allowed(*segments))                               # [B, N, L]
             s = s.masked_fill(~allowed[:, None], float("-inf"))
             v = v.masked_fill(torch.from_numpy(segments[0] == 255)[:, None, :, None], 0.0)
+        if weights is not None:
+            w = torch.from_numpy(weights)
+            off = (w == 0)
+            s = s + torch.log(torch.where(off, torch.ones_like(w), w))[:, None, None, :].to(s.dtype)
+            s = s.masked_fill(off[:, None, None, :], float("-inf"))
+            v = v.masked_fill(off[:, None, :, None], 0.0)
         p = torch.softmax(s, dim=-1)
         o = (p @ v).permute(0, 2, 1, 3).reshape(B, N, h * d)
         out = F.linear(o, self.to_out[0].weight, self.to_out[0].bias)

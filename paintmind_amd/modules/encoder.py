@@ -52,10 +52,14 @@ class T5TextEmbedder(nn.Module):
             param.requires_grad = False
 
     @torch.no_grad()
-    def forward(self, text, return_lens=False):
+    def forward(self, text, return_lens=False, weighted=False):
         """-> context (B, max_length, d_model), every position as in the reference (no mask is passed to the encoder).
         return_lens: -> (context, lens), lens[b] = the number of non-pad tokens of prompt b (the end-of-sequence token counts;
-        at least 1), for ``Pipeline.generate(mask_padding=True)`` / ``context_lens=``."""
+        at least 1), for ``Pipeline.generate(mask_padding=True)`` / ``context_lens=``.
+        weighted: the prompts carry emphasis syntax (``paintmind_amd.prompt``) -> (context, lens, weights), weights float32
+        [B, max_length] on the host, one per context row: see ``_forward_weighted``."""
+        if weighted:
+            return self._forward_weighted(text)
         enc = self.tokenizer(text, truncation=True, max_length=self.max_length, return_length=True,
                              return_overflowing_tokens=False, padding="max_length", return_tensors="pt")
         ids = enc["input_ids"]
@@ -65,6 +69,34 @@ class T5TextEmbedder(nn.Module):
             return context
         mask = enc["attention_mask"] if "attention_mask" in enc else ids != _pad_id(self.tokenizer)
         return context, _count_tokens(torch.as_tensor(mask))
+
+    def _forward_weighted(self, text):
+        """Every prompt is parsed (``prompt.parse_weighted``), its fragments are tokenised one by one WITHOUT special tokens, the ids
+        are concatenated, closed with the end-of-sequence id and truncated (the end-of-sequence id stays last) or padded to
+        max_length; the context is ONE tower call on those ids -- the words see each other as in an unweighted prompt, only the
+        syntax is gone.  Row j of prompt b carries the weight of the fragment its token came from; the end-of-sequence row and the
+        padding rows carry 1."""
+        from ..prompt import parse_weighted
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        eos = 1 if eos is None else int(eos)                   # T5's end-of-sequence token is id 1
+        pad = _pad_id(self.tokenizer)
+        B, L = len(text), self.max_length
+        ids = torch.full((B, L), pad, dtype=torch.long)
+        weights = torch.ones(B, L, dtype=torch.float32)
+        lens = torch.zeros(B, dtype=torch.int32)
+        for b, prompt in enumerate(text):
+            row, wrow = [], []
+            for frag, w in parse_weighted(prompt):
+                piece = self.tokenizer(frag, add_special_tokens=False)["input_ids"]
+                piece = [int(t) for t in (piece.reshape(-1).tolist() if hasattr(piece, "reshape") else piece)]
+                row += piece
+                wrow += [float(w)] * len(piece)
+            row, wrow = row[:L - 1] + [eos], wrow[:L - 1] + [1.0]
+            ids[b, :len(row)] = torch.tensor(row, dtype=torch.long)
+            weights[b, :len(row)] = torch.tensor(wrow, dtype=torch.float32)
+            lens[b] = len(row)
+        context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
+        return context, lens, weights
 
     def encode(self, text):
         return self(text)
@@ -109,9 +141,12 @@ class CLIPTextEmbedder(nn.Module):
             param.requires_grad = False
 
     @torch.no_grad()
-    def forward(self, text, return_lens=False):
+    def forward(self, text, return_lens=False, weighted=False):
         """return_lens: -> (context, lens), lens[b] = the number of non-pad tokens of prompt b (open_clip pads with 0; the
-        start and end tokens count), for ``Pipeline.generate(mask_padding=True)`` / ``context_lens=``."""
+        start and end tokens count), for ``Pipeline.generate(mask_padding=True)`` / ``context_lens=``.
+        weighted: not served -- the byte-pair tokenizer of this tower is not written for fragments."""
+        if weighted:
+            raise NotImplementedError("CLIPTextEmbedder serves no prompt weights (weighted=True): T5TextEmbedder does")
         tokens = self.tokenize(text)
         context = self.encode_with_transformer(tokens.to(_module_device(self.model)))
         return (context, _count_tokens(tokens != 0)) if return_lens else context
@@ -139,7 +174,9 @@ class NullTextEmbedder(nn.Module):
     """Unconditional generation through the drop-in API: the context is None, so attn2 runs as a second self-attention
     (reference modules/attention.py:47).  BASELINE.json configs[2] is this path."""
 
-    def forward(self, text, return_lens=False):
+    def forward(self, text, return_lens=False, weighted=False):
+        if weighted:
+            return None, None, None
         return (None, None) if return_lens else None
 
 
@@ -156,8 +193,13 @@ class SyntheticTextEmbedder(nn.Module):
         self.base_index = 0
         self.register_buffer("_anchor", torch.zeros(1), persistent=False)
 
-    def forward(self, text, return_lens=False):
-        """return_lens: every row is a feature (there is no tokenizer and no padding): lens = max_length for every prompt"""
+    def forward(self, text, return_lens=False, weighted=False):
+        """return_lens: every row is a feature (there is no tokenizer and no padding): lens = max_length for every prompt.
+        weighted: the emphasis syntax is parsed (so a malformed prompt is refused) and dropped; -> (context, lens, weights of 1)"""
+        if weighted:
+            from ..prompt import strip_weights
+            context, lens = self.forward([strip_weights(t) for t in text], return_lens=True)
+            return context, lens, torch.ones(len(text), self.max_length, dtype=torch.float32)
         if return_lens:
             return self.forward(text), torch.full((len(text),), self.max_length, dtype=torch.int32)
         rows = []

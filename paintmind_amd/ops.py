@@ -102,6 +102,42 @@ def host_segments(context_segments, token_segments, B, L, N):
     return np.ascontiguousarray(cs.astype(np.uint8)), np.ascontiguousarray(ts.astype(np.uint32))
 
 
+W_MIN, W_MAX = 2.0 ** -20, 2.0 ** 20      # the range of a non-zero prompt weight (include/pmhip.h, PROMPT WEIGHTS)
+
+
+def host_weights(context_weights, B, L, N, context_segments=None, token_segments=None, context_lens=None):
+    """prompt weights: context_weights [B, L] (the weight >= 0 of every context row; 0 = the row is padding),
+    as a list, a numpy array, a CPU or a device tensor; None passes through as None.  Beside it the pair of segment arrays
+    (``host_segments``), or per-image lengths (``host_lens``), or nothing: without segment arrays the NEUTRAL ones are built here --
+    segment 0 for the rows below the image's length, 255 behind, every token mask all ones.
+    -> (numpy uint8 [B, L], numpy uint32 [B, N], numpy float32 [B, L]) on the host, brought there ONCE per call and checked before
+    anything is launched: every weight finite and 0 or in [2^-20, 2^20], every token allows a row with a weight above 0."""
+    if context_weights is None:
+        return None
+    w = context_weights.detach().cpu().numpy() if isinstance(context_weights, torch.Tensor) else np.asarray(context_weights)
+    if w.shape != (B, L) or w.dtype.kind not in "fiu":
+        raise ValueError(f"context_weights must be numbers of shape ({B}, {L}), got {w.dtype} {w.shape}")
+    w = np.ascontiguousarray(w.astype(np.float32))
+    bad = np.argwhere(~(np.isfinite(w) & ((w == 0) | ((w >= W_MIN) & (w <= W_MAX)))))
+    if len(bad):
+        b, k = bad[0]
+        raise ValueError(f"context_weights: image {b}: context row {k}: weight {float(w[b, k])!r} must be 0 or in [2^-20, 2^20]")
+    if context_segments is not None or token_segments is not None:
+        if context_lens is not None:
+            raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
+        cs, ts = host_segments(context_segments, token_segments, B, L, N)
+    else:
+        lens = host_lens(context_lens, B, L) or [L] * B
+        cs = np.where(np.arange(L)[None, :] < np.asarray(lens)[:, None], 0, 255).astype(np.uint8)
+        ts = np.full((B, N), 0xFFFFFFFF, np.uint32)
+    live = np.where(w > 0, cs, 255).astype(np.uint8)                      # a row of weight 0 is padding
+    bad = np.argwhere(~segments_allowed(live, ts).any(-1))
+    if len(bad):
+        b, t = bad[0]
+        raise ValueError(f"context_weights: image {b}: token {t} allows no context row with a weight above 0 (mask {int(ts[b, t]):#x})")
+    return cs, ts, w
+
+
 def segments_allowed(key_seg, query_mask):
     """numpy uint8 [B, L], uint32 [B, N] -> bool [B, N, L]: row k takes part in token t's softmax (the rule of pmhip_attention_segments)"""
     ks = key_seg.astype(np.int64)[:, None, :]
@@ -380,14 +416,30 @@ def attention_fallbacks(reset=False, device=None):
     return int(n.value)
 
 
-def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None):
+def key_bias(weights, use_exp2):
+    """weights f32 on the device, any shape -> the bias of ``attention(key_weights=)`` in the kernel's score unit, same shape
+    (pmhip_key_bias): 0 -> -inf, 1 -> exactly 0, otherwise log2(w), times ln 2 when the scores are nats (use_exp2 False).  One
+    asynchronous launch on the current stream."""
+    dev = _dev(weights)
+    if weights.dtype != torch.float32 or weights.numel() == 0:
+        raise ValueError(f"weights must be a non-empty float32 tensor, got {weights.dtype} {tuple(weights.shape)}")
+    out = torch.empty_like(weights)
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_key_bias(_p(weights), _p(out), weights.numel(), int(bool(use_exp2)), stream_ptr(dev)), "pmhip_key_bias")
+    return out
+
+
+def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None, key_weights=None):
     """q [B,H,Nq,dh], k [B,H,Nkp,dh], vt [B,H,dh,Nkp] -> [B*Nq, H*dh]  (dh 64: tuned MFMA kernel; else pmhip_attention_dh).
     kv_lens (None: every image attends to n_kv keys): int32 [B] on the device, image b attends to its first kv_lens[b] keys
     (clamped to [1, n_kv] by the kernel) -- pmhip_attention_lens.
     key_segments uint8 [B, n_kv] + query_segments int32 / uint32 [B, Nq] (bit masks), both on the device and never beside kv_lens:
     key j takes part in query i's softmax iff key_segments[b, j] < 32 and bit key_segments[b, j] of query_segments[b, i] is set; 255
-    marks padding, whose K rows and V^T columns never reach a result -- pmhip_attention_segments.  Every query must allow a key."""
-    dev = _dev(q, k, vt, kv_lens, key_segments, query_segments)
+    marks padding, whose K rows and V^T columns never reach a result -- pmhip_attention_segments.  Every query must allow a key.
+    key_weights f32 [B, n_kv] on the device, alone or with the pair of segment arrays, never beside kv_lens:
+    over the keys a query allows p = w exp(s) / sum w exp(s); weight 0 makes the key padding, weights 0 or in [2^-20, 2^20].  Alone,
+    the neutral arrays (every key segment 0, every query all ones) are built here -- pmhip_key_bias, pmhip_attention_weighted."""
+    dev = _dev(q, k, vt, kv_lens, key_segments, query_segments, key_weights)
     lib = _lib.load()
     B, H, Nq, dh = q.shape
     nkp = k.shape[2]
@@ -406,6 +458,20 @@ def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, q
                 not query_segments.is_contiguous():
             raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
                              f"{tuple(query_segments.shape)}")
+    if key_weights is not None:
+        if kv_lens is not None:
+            raise ValueError("key_weights and kv_lens exclude each other (a weight of 0 makes a key padding)")
+        if key_weights.dtype != torch.float32 or tuple(key_weights.shape) != (B, n_kv):
+            raise ValueError(f"key_weights must be a float32 tensor of shape ({B}, {n_kv}), got {key_weights.dtype} {tuple(key_weights.shape)}")
+        bias = key_bias(key_weights, use_exp2)
+        if key_segments is None:
+            key_segments = torch.zeros(B, n_kv, dtype=torch.uint8, device=dev)
+            query_segments = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.pmhip_attention_weighted(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * dh, B, H, dh, Nq, n_kv, nkp,
+                                               int(use_exp2), _p(key_segments), _p(query_segments), _p(bias), stream_ptr(dev)),
+                  "pmhip_attention_weighted")
+        return out
     with torch.cuda.device(dev):
         if key_segments is not None:
             check(lib.pmhip_attention_segments(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * dh, B, H, dh, Nq, n_kv, nkp,

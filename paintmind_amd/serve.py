@@ -222,7 +222,9 @@ class DecodeSession:
         if context is None:
             if text is None:
                 raise ValueError("a conditional session needs a text (or a context) for every request")
-            ctx, cs, ts = pipe._region_context([text], [regions], False)
+            ctx, cs, ts, weights = pipe._region_context_weighted([text], [regions], False)
+            if weights is not None:
+                raise ValueError("regions: a decode session serves no prompt weights ((prompt, mask, weight)): Pipeline.generate(regions=) does")
         else:
             for item in regions:
                 if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], torch.Tensor) and item[0].dim() == 2

@@ -21,10 +21,11 @@ class Layer(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ffnet = SwiGLUFFNFused(in_features=dim, hidden_features=mlp_dim)
 
-    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None):
+    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """self-attn, cross-attn (a 2nd self-attn when context is None), SwiGLU (transformer.py:44-49).
         context_lens: per-image context lengths for the cross-attention only (modules/attention.py).
-        context_segments / token_segments: regional prompts, for the cross-attention only (modules/attention.py)."""
+        context_segments / token_segments: regional prompts, for the cross-attention only (modules/attention.py).
+        context_weights: prompt weights, for the cross-attention only (modules/attention.py)."""
         B, N, D = x.shape
         T = compute_dtype_of(self)
         x = x.contiguous()
@@ -32,7 +33,8 @@ class Layer(nn.Module):
         x = self.attn2.run(_norm(x.reshape(B * N, D), self.norm2, T).reshape(B, N, D), context, residual=x,
                            context_lens=context_lens if context is not None else None,
                            context_segments=context_segments if context is not None else None,
-                           token_segments=token_segments if context is not None else None)
+                           token_segments=token_segments if context is not None else None,
+                           context_weights=context_weights if context is not None else None)
         return self.ffnet.run(_norm(x.reshape(B * N, D), self.norm3, T).reshape(B, N, D), residual=x)
 
 
@@ -50,11 +52,12 @@ class CondTransformer(nn.Module):
         self.to_logits = nn.Linear(dim, num_classes)
         _xavier_like_reference(self)
 
-    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None):
+    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """operator-level composition of transformer.py:80-93 (Pipeline uses the native engine instead).
         context_lens (extension; None = the reference's behaviour): image b's cross-attention sees rows [0, context_lens[b]) of
         its context only.  The context projection still covers every row: it is row-local, so padding stays in the padding.
-        context_segments [B, L] / token_segments [B, N] (extension, regional prompts): see ``CrossAttention.run``."""
+        context_segments [B, L] / token_segments [B, N] (extension, regional prompts): see ``CrossAttention.run``.
+        context_weights [B, L] (extension, prompt weights; beside the segments, beside context_lens, or alone): likewise."""
         if context_lens is not None:
             if context is None:
                 raise ValueError("context_lens needs a context (context None IS the unconditional branch)")
@@ -65,6 +68,12 @@ class CondTransformer(nn.Module):
             if context_lens is not None:
                 raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
             context_segments, token_segments = ops.host_segments(context_segments, token_segments, x.shape[0], context.shape[1], x.shape[1])
+        if context_weights is not None:
+            if context is None:
+                raise ValueError("context_weights need a context (context None IS the unconditional branch)")
+            context_segments, token_segments, context_weights = ops.host_weights(context_weights, x.shape[0], context.shape[1], x.shape[1],
+                                                                                 context_segments, token_segments, context_lens)
+            context_lens = None                                    # the neutral segments carry the lengths
         T = compute_dtype_of(self)
         B, N, E = x.shape
         dim = self.token_proj.out_features
@@ -75,7 +84,7 @@ class CondTransformer(nn.Module):
             if context is not None:
                 context = self.context_proj(context.float())
             for layer in self.layers:
-                h = layer(h, context, context_lens, context_segments, token_segments)
+                h = layer(h, context, context_lens, context_segments, token_segments, context_weights)
             return self.to_logits(self.norm(h))
         a = ops.convert_pad(x.contiguous().float().reshape(B * N, E), 64, T)
         pos = self.position_embedding.detach()[0].contiguous()
@@ -88,7 +97,7 @@ class CondTransformer(nn.Module):
                 c = ops.gemm(c, packing.pad_cols(self.context_proj.weight, c.shape[1], T))
             context = c.reshape(B, L, dim)
         for layer in self.layers:
-            h = layer(h, context, context_lens, context_segments, token_segments)
+            h = layer(h, context, context_lens, context_segments, token_segments, context_weights)
         y = _norm(h.reshape(B * N, dim), self.norm, T)
         logits = ops.gemm(y, packing.cast(self.to_logits.weight, T), bias=self.to_logits.bias.detach().float(),
                           out_dtype=torch.float32)

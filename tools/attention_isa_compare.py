@@ -2,11 +2,13 @@
 """Per-symbol ISA comparison of the three attention files between two trees.
 
     hipcc -S --cuda-device-only -O3 --offload-arch=gfx950 <file>.hip -o <dir>/<file>.s      in both trees, then
-    tools/attention_isa_compare.py <parent dir> <this dir> [--twin-suffix _seg_kernel]
+    tools/attention_isa_compare.py <parent dir> <this dir> [--twin-suffix _seg_kernel] [--twin-of-suffix _kernel]
 
 Per kernel symbol: the instruction lines with comments stripped and block labels renumbered, plus next_free_vgpr, next_free_sgpr,
 accum_offset, LDS and scratch sizes of the kernel descriptor.  Symbols of the second tree that the first does not have are listed
-beside their twin (the symbol without the suffix's middle part, e.g. attention_bf16_seg_kernel<..> beside attention_bf16_kernel<..>).
+beside their twin (the symbol without the suffix's middle part, e.g. attention_bf16_seg_kernel<..> beside attention_bf16_kernel<..>;
+--twin-of-suffix names what the suffix becomes: `--twin-suffix _seg_bias_kernel --twin-of-suffix _seg_kernel` lists the weighted forms
+of DESIGN.md 4w beside their segmented twins).
 Exit status 1 if any symbol of the first tree is missing from or differs in the second.
 """
 import re
@@ -52,6 +54,7 @@ def demangle(names):
 def main():
     a_dir, b_dir = sys.argv[1], sys.argv[2]
     suffix = sys.argv[sys.argv.index("--twin-suffix") + 1] if "--twin-suffix" in sys.argv else "_seg_kernel"
+    twin_suffix = sys.argv[sys.argv.index("--twin-of-suffix") + 1] if "--twin-of-suffix" in sys.argv else "_kernel"
     bad = same = 0
     for f in FILES:
         a, b = kernels(f"{a_dir}/{f}.s"), kernels(f"{b_dir}/{f}.s")
@@ -67,10 +70,12 @@ def main():
                       f"{a[name][1].count(chr(10)) + 1} -> {b[name][1].count(chr(10)) + 1} lines")
             else:
                 same += 1
-        short = lambda n: re.search(r"(\w+<[^>]*>)", pretty[n]).group(1)          # attention_bf16_seg_kernel<true, 2>
+        def short(n):                                                             # attention_bf16_seg_kernel<true, 2>
+            m = re.search(r"(\w+<[^>]*>)", pretty[n]) or re.search(r"(\w+)\(", pretty[n])      # (or the name of a kernel that is no template)
+            return m.group(1) if m else pretty[n]
         by_short = {short(n): n for n in b}
         for name in sorted(set(b) - set(a), key=short):
-            twin = by_short.get(short(name).replace(suffix, "_kernel"))
+            twin = by_short.get(short(name).replace(suffix, twin_suffix))
             d = dict(zip(FIELDS, b[name][0]))
             t = dict(zip(FIELDS, b[twin][0])) if twin else {}
             print(f"NEW       {short(name)}: " + ", ".join(f"{k} {d[k]} (twin {t.get(k, '?')})" for k in FIELDS) +

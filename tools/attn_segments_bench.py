@@ -3,7 +3,10 @@ B=64, H=12, Nq=1024, Nkv=231 = a global prompt and two regions of 77 rows, dh=64
 (exp2) and fp32.  A measurement for DESIGN.md section 4u, no gate.  Layout of the masks: rows [0,77) segment 0 (global), [77,154)
 segment 1, [154,231) segment 2; the left half of a 32 x 32 token grid attends to segments 0 and 1, the right half to 0 and 2.
 Behind them the picked forms of DESIGN.md section 4v (pmhip_attention_pick): each form with every image served, every second one and
-none -- the last is what a launch costs whose workgroups all return at once -- and the pair of launches of a half-regional batch."""
+none -- the last is what a launch costs whose workgroups all return at once -- and the pair of launches of a half-regional batch.
+Behind those the weighted form of DESIGN.md section 4w (pmhip_attention_weighted) under the same masks, with weights cycling through
+1/8, 1, 8 and 1.3: the call of ``ops.attention(key_weights=)``, which converts the weights first (pmhip_key_bias, one more launch), and
+that conversion alone."""
 import os
 import sys
 
@@ -45,6 +48,12 @@ for dtype, exp2 in ((torch.bfloat16, True), (torch.float32, False)):
     seg = timed(lambda: ops.attention(q, k, vt, NKV, use_exp2=exp2, key_segments=ks, query_segments=qm))
     print(f"{dtype} B={B} H={H} Nq={NQ} Nkv={NKV}: unmasked {plain:.1f} us, lens {per_image:.1f} us, segments {seg:.1f} us "
           f"({seg / per_image:.2f} x lens)")
+    if hasattr(ops, "key_bias"):
+        w = torch.tensor([0.125, 1.0, 8.0, 1.3])[torch.arange(NKV) % 4][None].expand(B, NKV).contiguous().to(dev)
+        weighted = timed(lambda: ops.attention(q, k, vt, NKV, use_exp2=exp2, key_segments=ks, query_segments=qm, key_weights=w))
+        convert = timed(lambda: ops.key_bias(w, exp2))
+        print(f"    weighted form (conversion included): {weighted:.1f} us ({weighted / seg:.2f} x segments, {weighted / per_image:.2f} x lens); "
+              f"the conversion alone: {convert:.1f} us")
     if hasattr(ops, "attention_pick"):
         out = torch.empty(B * NQ, H * 64, device=dev, dtype=dtype)
         picks = {"all": torch.zeros(B, dtype=torch.uint8, device=dev), "half": (torch.arange(B) % 2).to(torch.uint8).to(dev),
