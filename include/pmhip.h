@@ -263,8 +263,8 @@ int pmhip_attention_segments(int dtype, const void* Q, const void* K, const void
  *   - image b's rows do not depend on what else is in the batch; there is no kv_lens beside the arrays
  * Any dim_head the _dh entry serves.  dim_head 64 runs the tuned kernels, every half-tile on the exact path as in the segmented form
  * (pmhip_attention_fallbacks never counts these launches); the bf16 kernel runs 128 or 64 queries per workgroup, chosen from B,
- * heads and Nq only, never from the arrays, bit-identical per 16-query tile.  There is no picked variant.  key_seg, query_mask or
- * key_bias NULL is PMHIP_EINVAL. */
+ * heads and Nq only, never from the arrays, bit-identical per 16-query tile.  The picked variant is pmhip_attention_pick_weighted, below.  key_seg,
+ * query_mask or key_bias NULL is PMHIP_EINVAL. */
 int pmhip_attention_weighted(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                              int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
                              const uint32_t* query_mask, const float* key_bias, pmhip_stream stream);
@@ -288,6 +288,20 @@ int pmhip_key_bias(const float* weights, float* bias, int n, int use_exp2, pmhip
 int pmhip_attention_pick(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                          int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens, const uint8_t* key_seg,
                          const uint32_t* query_mask, const uint8_t* pick, int want, pmhip_stream stream);
+
+/* pmhip_attention_weighted for SOME images of the batch (prompt weights per slot; new entry within ABI 11, nothing existing
+ * changes meaning): the arguments of pmhip_attention_weighted, then pick and want as in
+ * pmhip_attention_pick.  The contract is that entry's: a workgroup of an image with pick[b] != want returns at once -- it reads
+ * nothing of that image's Q, K, V^T, segments or biases (NaN there reaches nothing) and leaves EVERY byte of that image's rows of
+ * `out` as it found it; an image with pick[b] == want gets, bit for bit, the rows pmhip_attention_weighted writes for it on the
+ * same inputs (same kernel text, same launch geometry, 128 or 64 queries per workgroup in bf16 chosen from B, heads and Nq only,
+ * never from `pick` or the arrays).  Three launches -- pmhip_attention_pick with kv_lens, pmhip_attention_pick with the key sets,
+ * this entry --, one per kind, fill one buffer.  These launches never count in pmhip_attention_fallbacks.  pick, key_seg,
+ * query_mask or key_bias NULL, or want outside 0..255: PMHIP_EINVAL. */
+int pmhip_attention_pick_weighted(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                                  int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
+                                  const uint32_t* query_mask, const float* key_bias, const uint8_t* pick, int want,
+                                  pmhip_stream stream);
 
 /* torch.nn.LayerNorm over the last dim, eps inside the sqrt (stage1/layers.py:49,51,89,128;
  * stage2/transformer.py:37,39,41,62).  x fp32 [M,D] -> out (`out_dtype`). */
@@ -998,6 +1012,39 @@ int pmhip_pipeline_step_slots_regions(pmhip_s2* s2, int64_t* ids, const float* c
 /* Steps pmhip_pipeline_step_slots_regions ran on this handle with the two-launch cross-attention (an active slot was regional;
  * the others ran the step of the entry above).  The pointer may be NULL. */
 int pmhip_s2_slots_region_steps(const pmhip_s2* h, int* steps);
+
+/* PROMPT WEIGHTS IN A SLOTS STEP (new entries within ABI 11): pmhip_pipeline_step_slots_regions with one more
+ * HOST array in front of `flags`:
+ *   ctx_w_host    f32    [B, L]     : the weight of context row k of slot b, 0 or in [2^-20, 2^20]
+ * and region_host read as a KIND per slot: 0 = the slot runs under its length, 1 = under its key sets, 2 = under its key sets AND
+ * its weights, exactly as pmhip_pipeline_sample_lens does for that image with ctx_seg_host, tok_seg_host and ctx_w_host (a weighted
+ * slot without regions brings the one-segment layout: segment 0 below its length, 255 behind, every token mask with bit 0 set).
+ * Idle slots count as 0.  The pass without a context and the pass against the negative context never see weights.  Every kind of
+ * slot computes the same bits whatever shares the batch.
+ * ctx_w_host NULL, or no ACTIVE slot of kind 2: the call runs exactly pmhip_pipeline_step_slots_regions -- the same validation
+ * (kind 2 without the weights array is PMHIP_EINVAL), the same launches, the same graph key, the same captured graph.
+ * Validated before anything is staged or launched (PMHIP_EINVAL, ids untouched), for ACTIVE slots: the kind in {0, 1, 2}; a
+ * kind-2 slot follows the rules of a regional one and the weight rules of the *_weights entries -- every weight finite and 0 or in
+ * [2^-20, 2^20] (the message names the slot and the row), every token allows a segment with a row of weight > 0 (the message names
+ * the slot and the token); slots of kind 0 and 1 keep their checks, their rows of ctx_w_host are not looked at and are staged as 1.
+ * ctx_w_host without the three arrays of the entry above is PMHIP_EINVAL.
+ * The weights travel as in the *_weights entries: pinned ring entry -> copy kernel -> "ctx.w" -> pmhip_key_bias in the handle's
+ * score unit -> "ctx.bias".  Every layer's cross-attention of the pass with the context is then THREE launches into the same buffer:
+ * pmhip_attention_pick with the lengths and want = 0, pmhip_attention_pick with the key sets and want = 1,
+ * pmhip_attention_pick_weighted with want = 2.  With PMHIP_SLOTS_GRAPH this form has one further graph key, and as the captured
+ * graph bakes in the device arrays, not their contents, one graph per (B, L, pass set, ...) serves every mix of the three kinds,
+ * every layout and every set of weights. */
+int pmhip_pipeline_step_slots_weights(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B,
+                                      const int32_t* ctx_lens_host, const pmhip_slot* slots_host,
+                                      const pmhip_slot_guide* guides_host, const float* choice_host /* [B] or NULL */,
+                                      const float* neg_context /* [B,Ln,context_dim] or NULL */, int Ln,
+                                      const int32_t* neg_lens_host /* [B] or NULL */, const float* top_p_host /* [B] or NULL */,
+                                      const int32_t* counts_host /* [B] or NULL */, const uint8_t* ctx_seg_host,
+                                      const uint32_t* tok_seg_host, const uint8_t* region_host, const float* ctx_w_host, int flags,
+                                      int64_t* pred_out, float* score_out, pmhip_stream stream);
+/* Steps pmhip_pipeline_step_slots_weights ran on this handle with the three-launch cross-attention (an active slot was of kind 2);
+ * such a step is NOT counted by pmhip_s2_slots_region_steps, which keeps counting the two-launch form.  The pointer may be NULL. */
+int pmhip_s2_slots_weight_steps(const pmhip_s2* h, int* steps);
 
 /* The PMHIP_* development switches are read from the environment when a handle is CREATED and stay with it (its workspace,
  * fold decisions and captured graphs depend on them); editing the environment of a live handle does nothing.  These return

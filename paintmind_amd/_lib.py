@@ -226,10 +226,15 @@ PROTOTYPES = {
     # regional prompts per slot: the picked forms of the per-image and the per-query cross-attention, and the
     # slots step that runs one launch of each into one buffer
     "pmhip_attention_pick": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "pmhip_attention_pick_weighted": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "pmhip_pipeline_step_slots_regions": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
                                                 vp, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(i32), C.POINTER(C.c_ubyte),
                                                 C.POINTER(u32), C.POINTER(C.c_ubyte), i32, vp, vp, vp]),
     "pmhip_s2_slots_region_steps": (i32, [vp, C.POINTER(i32)]),
+    "pmhip_pipeline_step_slots_weights": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(Slot), C.POINTER(SlotGuide), C.POINTER(f32),
+                                                vp, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(i32), C.POINTER(C.c_ubyte),
+                                                C.POINTER(u32), C.POINTER(C.c_ubyte), C.POINTER(f32), i32, vp, vp, vp]),
+    "pmhip_s2_slots_weight_steps": (i32, [vp, C.POINTER(i32)]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

@@ -123,6 +123,19 @@ __device__ __forceinline__ void zero_ragged_v(unsigned char* Vl, int kv0, int Nk
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
 #undef PM_ATTN_BIAS
+// the picked weighted form: the weighted form again with `pick` and `want` -- a workgroup whose image has
+// pick[b] != want returns at once, every other one runs attention_seg_bias_kernel's text
+#define PM_ATTN_KERNEL attention_seg_bias_pick_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_SEG 1
+#define PM_ATTN_BIAS 1
+#define PM_ATTN_PICK 1
+#include "attention_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_BIAS
+#undef PM_ATTN_PICK
 
 }  // namespace
 
@@ -172,4 +185,15 @@ void pm_attention_f32_pick(const void* Q, const void* K, const void* Vt, void* o
     auto k = use_exp2 ? attention_lens_pick_kernel<true, QF> : attention_lens_pick_kernel<false, QF>;
     hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
                        Nq, Nkv, Nkv_pad, nqb, lens, pk.pick, pk.want);
+}
+
+// The picked weighted form, a launcher of its own again: the grid and the workgroup of the weighted twin.
+void pm_attention_f32_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                                    int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
+                                    hipStream_t s) {
+    constexpr int QF = 2;
+    const int nqb = ceil_div(Nq, 4 * QF * 16);
+    auto k = use_exp2 ? attention_seg_bias_pick_kernel<true, QF> : attention_seg_bias_pick_kernel<false, QF>;
+    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
+                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias, pk.pick, pk.want);
 }

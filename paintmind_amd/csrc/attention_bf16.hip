@@ -161,6 +161,19 @@ __device__ __forceinline__ f32x4_t mma(const v4u_t& rows, const v4u_t& cols, con
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
 #undef PM_ATTN_BIAS
+// the picked weighted form: the weighted form again with `pick` and `want` -- a workgroup whose image has
+// pick[b] != want returns at once, every other one runs attention_bf16_seg_bias_kernel's text
+#define PM_ATTN_KERNEL attention_bf16_seg_bias_pick_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_SEG 1
+#define PM_ATTN_BIAS 1
+#define PM_ATTN_PICK 1
+#include "attention_bf16_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_BIAS
+#undef PM_ATTN_PICK
 
 #undef DSRX
 #undef LGKM4
@@ -195,6 +208,16 @@ static void launch_seg_bias_qf(const void* Q, const void* K, const void* Vt, voi
     auto k = use_exp2 ? attention_bf16_seg_bias_kernel<true, QF> : attention_bf16_seg_bias_kernel<false, QF>;
     hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
                        Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias);
+}
+
+// the picked weighted form: the geometry of the weighted twin
+template <int QF>
+static void launch_seg_bias_pick_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                                    int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk, hipStream_t s) {
+    const int nqb = ceil_div(Nq, 4 * QF * 16);
+    auto k = use_exp2 ? attention_bf16_seg_bias_pick_kernel<true, QF> : attention_bf16_seg_bias_pick_kernel<false, QF>;
+    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
+                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias, pk.pick, pk.want);
 }
 
 // the picked forms: exactly one of lens / seg, the geometry of the twin
@@ -264,4 +287,14 @@ void pm_attention_bf16_pick(const void* Q, const void* K, const void* Vt, void* 
     if (!seg && bh * ceil_div(Nq, 256) >= 512) launch_pick_qf<4>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
     else if (bh * ceil_div(Nq, 128) >= 512) launch_pick_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
     else launch_pick_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
+}
+
+// The picked weighted form: the rule of pm_attention_bf16_seg_bias, word for word -- B, heads and Nq decide between
+// 128 and 64 queries per workgroup, never `pick` or the arrays --, so a served image's bits are those of the weighted launch.
+void pm_attention_bf16_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                                     int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
+                                     hipStream_t s) {
+    if ((long long)B * heads * ceil_div(Nq, 128) >= 512)
+        launch_seg_bias_pick_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, pk, s);
+    else launch_seg_bias_pick_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, pk, s);
 }

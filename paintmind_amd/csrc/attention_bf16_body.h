@@ -1,4 +1,4 @@
-// The bf16 attention kernel of attention_bf16.hip, which includes this file SIX TIMES (no include guard on purpose):
+// The bf16 attention kernel of attention_bf16.hip, which includes this file SEVEN TIMES (no include guard on purpose):
 //   PM_ATTN_KERNEL = attention_bf16_kernel,      PM_ATTN_LENS_PARAM empty          one key count for the launch (Nkv)
 //   PM_ATTN_KERNEL = attention_bf16_lens_kernel, PM_ATTN_LENS_PARAM = ", lens"     PM_ATTN_LENS defined: the key count is per IMAGE --
 //       lens[b] (device int32 [B]), read once per workgroup into a scalar and clamped to [1, Nkv]; Nkv stays the launch-wide
@@ -18,7 +18,9 @@
 //       ", key_bias" (DESIGN.md section 4w).  key_bias[b, k] (device f32 [B, Nkv]) is log(weight) of a key in the kernel's score
 //       unit -- octaves when EXP2, nats otherwise --, added to the key's score in every half-tile BEFORE the maximum is taken, so
 //       the running max is a max over s + bias; -inf means excluded and makes the key padding (255) in seg_of, for the scores and
-//       for the V^T zeroing alike.  No picked variant.
+//       for the V^T zeroing alike.
+//   PM_ATTN_KERNEL = attention_bf16_seg_bias_pick_kernel: the weighted form again with PM_ATTN_PICK defined and ", pick, want" behind
+//       key_bias: the early return of the picked forms, then attention_bf16_seg_bias_kernel's text.
 // A compile-time variant by TEXT, not by a template parameter or an inlined body function: the first form is then the kernel the
 // library had before the second existed, token for token -- same symbol, same instruction stream, same registers (a shared
 // __device__ body, even force-inlined, was measured to move the schedule of every instantiation).

@@ -9,6 +9,8 @@
 // A SIXTH inclusion with PM_ATTN_BIAS beside PM_ATTN_SEG (attention_seg_bias_kernel; one more parameter key_bias, device f32 [B, Nkv])
 // is the weighted form of DESIGN.md 4w: key_bias[b, k] = log(weight) in the kernel's score unit is added to an allowed key's score
 // before the maximum is taken; -inf makes the key padding (255), for the scores and for the V^T zeroing alike.
+// A SEVENTH inclusion with PM_ATTN_PICK beside PM_ATTN_SEG and PM_ATTN_BIAS (attention_seg_bias_pick_kernel; pick, want behind key_bias)
+// is the picked weighted form of DESIGN.md 4x: the early return of the picked forms, then the sixth inclusion's text.
 template <bool EXP2, int QF>
 __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __restrict__ Q, const float* __restrict__ Kp,
                                                             const float* __restrict__ Vt, float* __restrict__ out,

@@ -9,7 +9,7 @@
 //                walk the keys in the same order, so K / V^T addresses are wave-uniform per quad position and come out of
 //                L1/L2 as broadcasts.  The score matrix is never materialised.
 //
-// The attention entry points of the C ABI (pmhip_attention, pmhip_attention_dh, pmhip_attention_lens, pmhip_attention_segments, pmhip_attention_pick) are at the end of this file:
+// The attention entry points of the C ABI (pmhip_attention, pmhip_attention_dh, pmhip_attention_lens, pmhip_attention_segments, pmhip_attention_weighted, pmhip_attention_pick, pmhip_attention_pick_weighted) are at the end of this file:
 // one argument check for the family, then the launcher of attention.hip, attention_bf16.hip or this file.
 #include "common.h"
 
@@ -100,6 +100,19 @@ __device__ __forceinline__ float quad_sum(float v) {
 #undef PM_ATTN_LENS_PARAM
 #undef PM_ATTN_SEG
 #undef PM_ATTN_BIAS
+// the picked weighted form: the weighted form again with `pick` and `want` -- a workgroup whose image has
+// pick[b] != want returns at once, every other one runs attention_dh_seg_bias_kernel's text
+#define PM_ATTN_KERNEL attention_dh_seg_bias_pick_kernel
+#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias, const unsigned char* __restrict__ pick, int want
+#define PM_ATTN_SEG 1
+#define PM_ATTN_BIAS 1
+#define PM_ATTN_PICK 1
+#include "attention_dh_body.h"
+#undef PM_ATTN_KERNEL
+#undef PM_ATTN_LENS_PARAM
+#undef PM_ATTN_SEG
+#undef PM_ATTN_BIAS
+#undef PM_ATTN_PICK
 
 // weights -> key_bias: 0 -> -inf (excluded), 1 -> exactly 0, otherwise log2(w), times ln 2 when the scores are nats
 __global__ __launch_bounds__(256) void key_bias_kernel(const float* __restrict__ w, float* __restrict__ bias, int n, int use_exp2) {
@@ -116,7 +129,13 @@ __global__ __launch_bounds__(256) void key_bias_kernel(const float* __restrict__
 template <typename T, int DPL>
 void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
                int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, const float* bias, hipStream_t s) {
-    if (bias) {                                        // the weighted form: seg beside it, never pk
+    if (bias && pk) {                                  // the picked weighted form: the geometry of the weighted twin
+        auto k = use_exp2 ? attention_dh_seg_bias_pick_kernel<T, DPL, true> : attention_dh_seg_bias_pick_kernel<T, DPL, false>;
+        hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
+                           Nkv, Nkp, seg->key_seg, seg->query_mask, bias, pk->pick, pk->want);
+        return;
+    }
+    if (bias) {                                        // the weighted form: seg beside it
         auto k = use_exp2 ? attention_dh_seg_bias_kernel<T, DPL, true> : attention_dh_seg_bias_kernel<T, DPL, false>;
         hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
                            Nkv, Nkp, seg->key_seg, seg->query_mask, bias);
@@ -215,10 +234,17 @@ void pm_attention_bf16_seg_bias(const void* Q, const void* K, const void* Vt, vo
                                 int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s);
 void pm_attention_bf16_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
                             int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s);
+void pm_attention_f32_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                                    int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
+                                    hipStream_t s);
+void pm_attention_bf16_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
+                                     int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
+                                     hipStream_t s);
 
 // Every attention entry point ends here: the arguments are checked once, then one launcher per kernel file.  lens = device
 // int32 [B], the per-image key counts, or NULL (one key count for the launch); seg = the per-query key sets (device arrays), or NULL;
-// pk = the picked forms (exactly one of lens / seg beside it), or NULL; bias = the weighted form (seg beside it, no pk), or NULL.
+// pk = the picked forms (exactly one of lens / seg beside it), or NULL; bias = the weighted form (seg beside it), or NULL; bias
+// and pk together = the picked weighted form.
 static int attention_any(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                          int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s,
                          const PmAttnSeg* seg = nullptr, const PmAttnPick* pk = nullptr, const float* bias = nullptr) {
@@ -239,6 +265,9 @@ static int attention_any(const char* who, int dtype, const void* Q, const void* 
     if (!tuned) {
         if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, bias, s));
         else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, bias, s));
+    } else if (bias && pk) {
+        if (dtype == PMHIP_F32) pm_attention_f32_seg_bias_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, *pk, s);
+        else pm_attention_bf16_seg_bias_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, *pk, s);
     } else if (bias) {
         if (dtype == PMHIP_F32) pm_attention_f32_seg_bias(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, s);
         else pm_attention_bf16_seg_bias(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, s);
@@ -314,4 +343,18 @@ extern "C" int pmhip_attention_pick(int dtype, const void* Q, const void* K, con
     const PmAttnPick pk{pick, want};
     return attention_any("attention_pick", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, kv_lens,
                          (hipStream_t)stream, key_seg ? &seg : nullptr, &pk);
+}
+
+extern "C" int pmhip_attention_pick_weighted(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
+                                             int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
+                                             const uint32_t* query_mask, const float* key_bias, const uint8_t* pick, int want,
+                                             pmhip_stream stream) {
+    PM_REQUIRE(pick, "attention_pick_weighted: pick is NULL (pmhip_attention_weighted is the entry that serves every image)");
+    PM_REQUIRE(key_seg && query_mask && key_bias,
+               "attention_pick_weighted: key_seg / query_mask / key_bias is NULL (pmhip_attention_pick is the entry without weights)");
+    PM_REQUIRE(want >= 0 && want <= 255, "attention_pick_weighted: want=%d is no value of a uint8 pick", want);
+    const PmAttnSeg seg{key_seg, query_mask};
+    const PmAttnPick pk{pick, want};
+    return attention_any("attention_pick_weighted", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
+                         (hipStream_t)stream, &seg, &pk, key_bias);
 }

@@ -8,6 +8,8 @@
 // A SIXTH inclusion with PM_ATTN_BIAS beside PM_ATTN_SEG (attention_dh_seg_bias_kernel; one more parameter key_bias, device f32
 // [B, Nkv]) is the weighted form of DESIGN.md 4w: an allowed key's score becomes s + key_bias[b, k] before it meets the running
 // maximum, and a key whose bias is -inf is skipped like padding.
+// A SEVENTH inclusion with PM_ATTN_PICK beside PM_ATTN_SEG and PM_ATTN_BIAS (attention_dh_seg_bias_pick_kernel; pick, want behind
+// key_bias) is the picked weighted form of DESIGN.md 4x: the early return of the picked forms, then the sixth inclusion's text.
 template <typename T, int DPL, bool EXP2>
 __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ Vt,
                                                           T* __restrict__ out, int ldo, int heads, int Nq, int Nkv, int Nkp PM_ATTN_LENS_PARAM) {

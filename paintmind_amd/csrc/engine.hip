@@ -200,11 +200,14 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     // and device uint32 [B, tokens], the segments every token attends to.  Never beside `lens`, except with `pick`.
     const uint8_t* key_seg = nullptr;
     const uint32_t* query_mask = nullptr;
-    // a slots step with regional and plain slots side by side, THIS call's or NULL: device uint8 [B], 1 = the image
-    // runs under its key sets, 0 = under its length.  Only then `lens` and the segments stand side by side: two picked launches.
+    // a slots step with slots of several kinds side by side, THIS call's or NULL: device uint8 [B], the kind of
+    // every image -- 0 = it runs under its length, 1 = under its key sets, 2 = under its key sets and its biases.  Only then `lens`
+    // and the segments stand side by side: two picked launches, and a third when `key_bias` is there as well.
     const uint8_t* pick = nullptr;
     // prompt weights, THIS call's or NULL: device f32 [B, L], log(weight) of every context row in the score unit of
-    // the handle's dtype (-inf = excluded).  Always beside key_seg / query_mask (the caller's or the neutral ones), never beside pick.
+    // the handle's dtype (-inf = excluded).  Always beside key_seg / query_mask (the caller's or the neutral ones).  Beside `pick` (a
+    // slots step with a weighted slot) the set carries lens, the segments, pick AND key_bias together, and only the
+    // images of kind 2 read their rows of it.
     const float* key_bias = nullptr;
 };
 
@@ -455,6 +458,10 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
                                             cross->lens, nullptr, nullptr, cross->pick, 0, s));
                 PM_TRY(pmhip_attention_pick(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
                                             nullptr, cross->key_seg, cross->query_mask, cross->pick, 1, s));
+                // ... and, in a step with a weighted slot, a third: the weighted ones under their key sets and biases
+                if (cross->key_bias)
+                    PM_TRY(pmhip_attention_pick_weighted(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L,
+                                                         cross->Lp, fast, cross->key_seg, cross->query_mask, cross->key_bias, cross->pick, 2, s));
             } else if (cross->key_bias)
                 PM_TRY(pmhip_attention_weighted(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
                                                 cross->key_seg, cross->query_mask, cross->key_bias, s));
@@ -803,6 +810,7 @@ struct pmhip_s2 {
     int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
     int slots_filter_tiles = 0, slots_filter_chain = 0;   // steps of pmhip_pipeline_step_slots_filter by the form of their sampling tail
     int slots_region_steps = 0;                           // steps of pmhip_pipeline_step_slots_regions that ran the two-launch cross-attention
+    int slots_weight_steps = 0;                           // steps of pmhip_pipeline_step_slots_weights that ran the three-launch cross-attention
     int slots_edit_steps = 0;                             // steps of pmhip_pipeline_step_slots_edit that re-masked by a count per slot
     int slots_ctx_B = 0, slots_ctx_L = -1;
     int slots_neg_B = 0, slots_neg_Ln = -1;
@@ -977,8 +985,8 @@ int check_segments(const char* who, const uint8_t* ctx_seg_host, const uint32_t*
 // copy kernel -> the handle's device array "ctx.seg" -> every layer's CrossKV of the context's set, from where the cross-attention
 // launch of layer_forward hands them to pmhip_attention_segments.  Called right behind s2_set_ctx_lens (which drops the segments of
 // an earlier call), always outside a graph: a captured graph bakes in the device array, never a layout of regions.
-// region_host (a slots step of pmhip_pipeline_step_slots_regions; NULL otherwise): the B flags ride in the same ring entry, behind the
-// row segments, into a device array of their own ("ctx.pick"), and the CrossKV keep the lengths s2_set_ctx_lens has just set.
+// region_host (a slots step of pmhip_pipeline_step_slots_regions / _weights; NULL otherwise): the B kinds ride in the same ring entry,
+// behind the row segments, into a device array of their own ("ctx.pick"), and the CrossKV keep the lengths s2_set_ctx_lens has just set.
 int s2_set_segments(pmhip_s2* h, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, int L, int B, hipStream_t s,
                     const uint8_t* region_host = nullptr) {
     if (!ctx_seg_host) return PMHIP_OK;
@@ -1054,7 +1062,9 @@ int check_weights(const char* who, const float* ctx_w_host, const uint8_t* ctx_s
 // The checked weights travel like the segments: pinned ring entry -> copy kernel -> the handle's device array "ctx.w" -> the conversion
 // kernel (pmhip_key_bias, in the score unit of the handle's dtype) -> the handle's device array "ctx.bias" -> every layer's CrossKV of
 // the context's set, from where the cross-attention launch of layer_forward hands it to pmhip_attention_weighted.  Called right behind
-// s2_set_segments, always outside a graph: a captured graph bakes in the bias array, never a weight.
+// s2_set_segments, always outside a graph: a captured graph bakes in the bias array, never a weight.  In a slots step with a weighted
+// slot (pmhip_pipeline_step_slots_weights) the set then carries lens, the segments, pick AND key_bias together, and the
+// third picked launch of layer_forward (pmhip_attention_pick_weighted, want = 2) is the one that reads the bias.
 int s2_set_weights(pmhip_s2* h, const float* ctx_w_host, int L, int B, hipStream_t s) {
     if (!ctx_w_host) return PMHIP_OK;
     const size_t n = (size_t)B * L, bytes = (n * 4 + 15) & ~(size_t)15;
@@ -1071,6 +1081,25 @@ int s2_set_weights(pmhip_s2* h, const float* ctx_w_host, int L, int B, hipStream
     PM_TRY(pmhip_key_bias(dw, dbias, (int)n, h->dtype == PMHIP_BF16, s));
     for (auto& ck : h->cross)
         if (ck.k) ck.key_bias = dbias;
+    return PMHIP_OK;
+}
+
+// One weighted slot's row of ctx_w_host (pmhip_pipeline_step_slots_weights), behind check_segments_of: the rules of
+// check_weights for that slot alone -- every weight 0 or in [2^-20, 2^20], every token allowing a segment with a row of weight > 0.
+int check_slot_weights(const char* who, int b, const float* ctx_w_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, int L,
+                       int tokens) {
+    uint32_t present = 0;                                     // segments with a row of weight > 0
+    for (int k = 0; k < L; ++k) {
+        const float w = ctx_w_host[(size_t)b * L + k];
+        PM_REQUIRE(std::isfinite(w) && (w == 0.f || (w >= 0x1p-20f && w <= 0x1p20f)),
+                   "%s: slot %d: context row %d: weight %g must be 0 or in [2^-20, 2^20]", who, b, k, (double)w);
+        const int sg = ctx_seg_host[(size_t)b * L + k];
+        if (sg < 32 && w > 0.f) present |= 1u << sg;
+    }
+    for (int t = 0; t < tokens; ++t)
+        PM_REQUIRE(tok_seg_host[(size_t)b * tokens + t] & present,
+                   "%s: slot %d: token %d allows no context row with a weight above 0 (mask 0x%08x, segments with such a row 0x%08x)", who, b, t,
+                   (unsigned)tok_seg_host[(size_t)b * tokens + t], (unsigned)present);
     return PMHIP_OK;
 }
 
@@ -2017,40 +2046,56 @@ extern "C" int pmhip_pipeline_generate_weights(pmhip_s2* s2, pmhip_vqgan* vq, in
 // counts_host (pmhip_pipeline_step_slots_edit; NULL from the six older entries): a re-masking count per slot,
 // -1 = the record's num_mask.  A step in which no active slot has a count >= 0 is the step without counts (launches, graph key and
 // graph); otherwise the counts are staged behind the masses and the re-masking launch is the form with a count per slot.
+// ctx_seg_host / tok_seg_host / region_host (pmhip_pipeline_step_slots_regions; NULL from the seven older entries; DESIGN.md section
+// 4v) and ctx_w_host (pmhip_pipeline_step_slots_weights; NULL from the eight older entries): region_host names
+// the kind of every slot -- 0 under its length, 1 under its key sets, 2 (with ctx_w_host only) under its key sets and its weights.
+// A step without an active slot of kind 1 or 2 is the step without the arrays; one without an active slot of kind 2 is the step of
+// the _regions entry (two picked cross-attention launches per layer, graph key suffix R); otherwise the weights are staged too and
+// the launches are three (suffix W).
 static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                            const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host, int flags,
                            int64_t* pred_out, float* score_out, pmhip_stream stream, bool kinds = false, const float* neg_context = nullptr,
                            int Ln = 0, const int32_t* neg_lens_host = nullptr, bool filters = false, const float* top_p_host = nullptr,
                            const int32_t* counts_host = nullptr, const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr,
-                           const uint8_t* region_host = nullptr) {
+                           const uint8_t* region_host = nullptr, const float* ctx_w_host = nullptr) {
     const bool keep_neg = kinds && (flags & PMHIP_SLOTS_KEEP_NEGATIVE) != 0;
     const bool neg_set = neg_context || keep_neg;             // this call has a negative set, given or kept
-    const char* who = (ctx_seg_host || tok_seg_host || region_host) ? "pipeline_step_slots_regions"
+    const char* who = ctx_w_host ? "pipeline_step_slots_weights" : (ctx_seg_host || tok_seg_host || region_host) ? "pipeline_step_slots_regions"
                       : counts_host ? "pipeline_step_slots_edit" : filters ? "pipeline_step_slots_filter"
                               : (neg_set || neg_lens_host) ? "pipeline_step_slots_negative" : choice_host ? "pipeline_step_slots_choice" : narrow;
     PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
     const bool have_context = context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0);
     // regional slots (pmhip_pipeline_step_slots_regions): the three arrays together or none, the rules of
     // check_segments for the ACTIVE slots that are flagged, the length check for every other slot
-    bool regions = false;                                     // an active slot is regional: the two-launch cross-attention
+    // weighted slots (pmhip_pipeline_step_slots_weights): region_host is a KIND per slot -- 0 under its length,
+    // 1 under its key sets, 2 under its key sets and its weights --, kind 2 only where ctx_w_host came; a kind-2 slot follows the
+    // rules of a regional one and the weight rules of check_weights
+    bool regions = false;                                     // an active slot is of kind 1 or 2: the picked cross-attention
+    bool weighted = false;                                    // an active slot is of kind 2: its third launch
     PM_REQUIRE((!ctx_seg_host == !tok_seg_host) && (!ctx_seg_host == !region_host),
                "%s: ctx_seg_host, tok_seg_host and region_host come together (one of them is NULL)", who);
     if (region_host) {
         for (int b = 0; b < B; ++b) {
             if (slots_host[b].step & PM_SLOT_IDLE) continue;
-            PM_REQUIRE(region_host[b] <= 1, "%s: slot %d: region_host=%d must be 0 or 1", who, b, (int)region_host[b]);
-            regions = regions || region_host[b] == 1;
+            if (ctx_w_host) PM_REQUIRE(region_host[b] <= 2, "%s: slot %d: region_host=%d must be 0, 1 or 2", who, b, (int)region_host[b]);
+            else PM_REQUIRE(region_host[b] <= 1, "%s: slot %d: region_host=%d must be 0 or 1 (2 needs ctx_w_host)", who, b, (int)region_host[b]);
+            regions = regions || region_host[b] >= 1;
+            weighted = weighted || region_host[b] == 2;
         }
+    } else {
+        PM_REQUIRE(!ctx_w_host, "%s: ctx_w_host given without ctx_seg_host, tok_seg_host and region_host", who);
     }
-    auto regional = [&](int b) { return regions && !(slots_host[b].step & PM_SLOT_IDLE) && region_host[b] == 1; };
+    auto regional = [&](int b) { return regions && !(slots_host[b].step & PM_SLOT_IDLE) && region_host[b] >= 1; };
+    auto weighted_slot = [&](int b) { return regional(b) && region_host[b] == 2; };
     if (!regions) {
         PM_TRY(check_ctx_lens(who, ctx_lens_host, have_context, L, B));
     } else {
         PM_REQUIRE(have_context && L > 0, "%s: regional slots given without a context", who);
         for (int b = 0; b < B; ++b) {
-            if (regional(b))
+            if (regional(b)) {
                 PM_TRY(check_segments_of(who, "slot", b, ctx_seg_host, tok_seg_host, L, s2->cfg.tokens));
-            else
+                if (weighted_slot(b)) PM_TRY(check_slot_weights(who, b, ctx_w_host, ctx_seg_host, tok_seg_host, L, s2->cfg.tokens));
+            } else
                 PM_REQUIRE(!ctx_lens_host || (ctx_lens_host[b] >= 1 && ctx_lens_host[b] <= L), "%s: image %d: context length %d must be in [1, L=%d]",
                            who, b, (int)ctx_lens_host[b], L);
         }
@@ -2133,19 +2178,22 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
         // and by no kernel -- one segment, every token attending to it.
         std::vector<int32_t> lens((size_t)B, L);
         std::vector<uint8_t> kseg((size_t)B * L, 0), flag((size_t)B, 0);
+        std::vector<float> wts(weighted ? (size_t)B * L : 0, 1.f);   // a slot of kind 0 or 1 is staged as 1; no kernel reads its rows
         std::vector<uint32_t> tseg((size_t)B * c.tokens, 1u);
         for (int b = 0; b < B; ++b) {
             if (!regional(b)) {
                 if (ctx_lens_host) lens[b] = ctx_lens_host[b];
                 continue;
             }
-            flag[b] = 1;
+            flag[b] = region_host[b];
+            if (weighted_slot(b)) std::copy(ctx_w_host + (size_t)b * L, ctx_w_host + (size_t)(b + 1) * L, wts.begin() + (size_t)b * L);
             memcpy(kseg.data() + (size_t)b * L, ctx_seg_host + (size_t)b * L, (size_t)L);
             memcpy(tseg.data() + (size_t)b * c.tokens, tok_seg_host + (size_t)b * c.tokens, (size_t)c.tokens * 4);
         }
         PM_TRY(s2_set_ctx_lens(s2, lens.data(), L, B, s));
         PM_TRY(s2_set_segments(s2, kseg.data(), tseg.data(), L, B, s, flag.data()));
-        ++s2->slots_region_steps;
+        if (weighted) PM_TRY(s2_set_weights(s2, wts.data(), L, B, s));
+        ++(weighted ? s2->slots_weight_steps : s2->slots_region_steps);
     }
     // the negative set: prepared (eager, outside any graph), kept, or -- a call that neither brings nor keeps one -- dropped
     if (keep_neg) {
@@ -2230,7 +2278,7 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     const char* passes = pass_neg ? (pass_uncond ? "slotsthreeB" : "slotsnegB") : two_pass ? "slotsguidedB" : "slotsB";
     const std::string neg_key = pass_neg ? "N" + std::to_string(Ln) + (neg_lens_host ? "n" : "") : "";
     GraphEntry& ge = s2->graphs[passes + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
-                                (regions ? "R" : ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "") + (edit ? "E" : "")];
+                                (weighted ? "W" : regions ? "R" : ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "") + (edit ? "E" : "")];
     PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
     PM_TRY(copy16_async(ids, gids, ids_bytes, s));
@@ -2309,6 +2357,25 @@ extern "C" int pmhip_pipeline_step_slots_regions(pmhip_s2* s2, int64_t* ids, con
 extern "C" int pmhip_s2_slots_region_steps(const pmhip_s2* h, int* steps) {
     PM_REQUIRE(h, "s2_slots_region_steps: null handle");
     if (steps) *steps = h->slots_region_steps;
+    return PMHIP_OK;
+}
+
+// ctx_w_host NULL, or no active slot of kind 2: exactly pmhip_pipeline_step_slots_regions
+extern "C" int pmhip_pipeline_step_slots_weights(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                                 const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
+                                                 const float* neg_context, int Ln, const int32_t* neg_lens_host, const float* top_p_host,
+                                                 const int32_t* counts_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
+                                                 const uint8_t* region_host, const float* ctx_w_host, int flags, int64_t* pred_out,
+                                                 float* score_out, pmhip_stream stream) {
+    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
+                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host, counts_host, ctx_seg_host, tok_seg_host,
+                           region_host, ctx_w_host);
+}
+
+// steps of that entry that ran the three-launch cross-attention (an active slot was weighted)
+extern "C" int pmhip_s2_slots_weight_steps(const pmhip_s2* h, int* steps) {
+    PM_REQUIRE(h, "s2_slots_weight_steps: null handle");
+    if (steps) *steps = h->slots_weight_steps;
     return PMHIP_OK;
 }
 

@@ -453,6 +453,13 @@ class S2Engine:
         check(self.lib.pmhip_s2_slots_region_steps(self.handle, C.byref(steps)), "pmhip_s2_slots_region_steps")
         return steps.value
 
+    def slots_weight_steps(self):
+        """the steps pmhip_pipeline_step_slots_weights ran on this handle with the three-launch cross-attention (an active slot was
+        weighted); they are not counted by ``slots_region_steps``"""
+        steps = C.c_int(0)
+        check(self.lib.pmhip_s2_slots_weight_steps(self.handle, C.byref(steps)), "pmhip_s2_slots_weight_steps")
+        return steps.value
+
     def slots_edit_steps(self):
         """the steps pmhip_pipeline_step_slots_edit ran on this handle with the re-masking form that takes a count per slot"""
         steps = C.c_int(0)
@@ -461,7 +468,7 @@ class S2Engine:
 
     def step_slots(self, ids, context, slots, use_graph=False, keep_context=False, want_aux=True, guides=None, context_lens=None,
                    choice=None, negative_context=None, negative_lens=None, keep_negative=False, top_p=None, counts=None,
-                   segments=None):
+                   segments=None, weights=None):
         """one MaskGIT step in which image b runs with slots[b] (a ctypes array of _lib.Slot, HOST records: seed, image_index,
         temperature, topk <= 8, num_mask, step; bit 31 of step = idle); ids int64 [B,N] is updated IN PLACE.  No image: the
         caller decodes the rows it wants.  keep_context: `context` only says whether there is one (None / not None) and its
@@ -489,6 +496,11 @@ class S2Engine:
         segment 0..31 of context row k or 255 for padding, tok_seg[b, t] the segments token t attends to --, every other slot under
         its context length; the native entry validates them (a context is required).  A step in which no active slot is flagged
         runs the launches and the graph of the `counts` route.
+        weights (None: the steps above; needs `segments`): f32 [B, L], a host array, which routes the step to
+        pmhip_pipeline_step_slots_weights: flags[b] is then a KIND -- 0 under the length, 1 under the key sets,
+        2 under the key sets and weights[b] (0 or in [2^-20, 2^20]; a weighted slot without regions brings the one-segment layout) --
+        and a step with an active slot of kind 2 runs three picked cross-attention launches per layer.  A step without such a slot
+        runs the launches and the graph of the `segments` route.
         -> (ids, pred [B,N], score [B,N])"""
         B = ids.shape[0]
         if len(slots) != B:
@@ -545,8 +557,19 @@ class S2Engine:
             if cs.shape != (B, L) or ts.shape != (B, self.tokens) or fl.shape != (B,):
                 raise ValueError(f"step_slots: segments {cs.shape}, {ts.shape}, {fl.shape}: expected ({B}, {L}), ({B}, {self.tokens}), ({B},)")
             segments = tuple(a.ctypes.data_as(C.POINTER(t)) for a, t in ((cs, C.c_ubyte), (ts, C.c_uint32), (fl, C.c_ubyte)))
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float32)
+            if w.shape != (B, L):
+                raise ValueError(f"step_slots: weights {w.shape}: expected ({B}, {L})")
+            weights = w.ctypes.data_as(C.POINTER(C.c_float))
         with torch.cuda.device(self.device):
-            if segments is not None:
+            if weights is not None:
+                none = (None, None, None)
+                check(self.lib.pmhip_pipeline_step_slots_weights(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
+                                                                 Ln, neg_lens, top_p, counts, *(segments or none), weights, flags,
+                                                                 _p(pred), _p(score), stream_ptr(self.device)),
+                      "pmhip_pipeline_step_slots_weights")
+            elif segments is not None:
                 check(self.lib.pmhip_pipeline_step_slots_regions(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
                                                                  Ln, neg_lens, top_p, counts, segments[0], segments[1], segments[2], flags,
                                                                  _p(pred), _p(score), stream_ptr(self.device)),

@@ -637,7 +637,7 @@ class Pipeline(nn.Module):
         return ids0.to(device, torch.long).clone(memory_format=torch.contiguous_format)
 
     def decode_session(self, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True, max_context_len=None,
-                       max_negative_len=None, filters=False, regions=False):
+                       max_negative_len=None, filters=False, regions=False, weights=False):
         """a DecodeSession over this pipeline (paintmind_amd/serve.py): `slots` images decode together, each with its own
         timesteps / temperature / top-k / seed / context length / guidance scale or schedule / negative prompt, and new requests
         are admitted into free slots between steps.  max_negative_len: the capacity of the negative contexts, like max_context_len
@@ -645,11 +645,14 @@ class Pipeline(nn.Module):
         1..n_embed (None: no filter) and it may carry a nucleus mass top_p, like ``generate``; False: the session and the limits
         (top-k <= 8, no top_p) of before.  regions=True (an option of either session): ``submit(regions=[(prompt,
         mask), ...])`` gives a request regional prompts, like ``generate(regions=)`` for one image; False: the session refuses them,
-        as before"""
+        as before.  weights=True (an option of either session, beside the other two): a request carries prompt
+        weights -- ``submit(text="a (red:1.4) barn")`` is read like ``generate(prompt_weights=True)``, ``submit(context=(ctx, w))``
+        takes them explicitly, a region may be ``(prompt, mask, weight)``; False: the session refuses them, as before"""
         from .serve import DecodeSession, FilterSession
         return (FilterSession if filters else DecodeSession)(self, slots=slots, conditional=conditional, use_graph=use_graph,
                                                              record_steps=record_steps, decode=decode, max_context_len=max_context_len,
-                                                             max_negative_len=max_negative_len, regions=bool(regions))
+                                                             max_negative_len=max_negative_len, regions=bool(regions),
+                                                             weights=bool(weights))
 
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
                      join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None,

@@ -489,14 +489,18 @@ def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, q
     return out
 
 
-def attention_pick(q, k, vt, n_kv, pick, want, out, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None):
+def attention_pick(q, k, vt, n_kv, pick, want, out, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None,
+                   key_weights=None):
     """``attention`` for SOME images of the batch, into a caller-supplied `out` (pmhip_attention_pick).
     pick uint8 [B] on the device names the kind of every image, `want` the kind this call serves: the rows of an image with
     pick[b] == want become, bit for bit, what ``attention`` with the same kv_lens / key_segments + query_segments writes for it,
     the rows of every other image stay as they are -- so two calls, one per kind, fill one buffer.  Exactly one of kv_lens and the
     pair key_segments + query_segments selects the form.  out: [B*Nq, H*dh] of q's dtype with unit column stride; its row stride is
-    the leading dimension (a window of a larger buffer will do).  -> out"""
-    dev = _dev(q, k, vt, pick, kv_lens, key_segments, query_segments)
+    the leading dimension (a window of a larger buffer will do).
+    key_weights f32 [B, n_kv] on the device, alone or with the pair of segment arrays, never beside kv_lens, as
+    in ``attention``: the served images get the rows of ``attention(key_weights=)`` -- pmhip_key_bias, pmhip_attention_pick_weighted.
+    The weights of a skipped image are read by pmhip_key_bias only; what it makes of them (NaN included) is read by nothing.  -> out"""
+    dev = _dev(q, k, vt, pick, kv_lens, key_segments, query_segments, key_weights)
     if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dim() == 2):
         raise ValueError("out must be a 2-D tensor on the operands' device")
     lib = _lib.load()
@@ -509,6 +513,14 @@ def attention_pick(q, k, vt, n_kv, pick, want, out, use_exp2=False, kv_lens=None
                          f"strides {tuple(out.stride())}")
     if (key_segments is None) != (query_segments is None):
         raise ValueError("key_segments and query_segments come together")
+    if key_weights is not None:
+        if kv_lens is not None:
+            raise ValueError("key_weights and kv_lens exclude each other (a weight of 0 makes a key padding)")
+        if key_weights.dtype != torch.float32 or tuple(key_weights.shape) != (B, n_kv):
+            raise ValueError(f"key_weights must be a float32 tensor of shape ({B}, {n_kv}), got {key_weights.dtype} {tuple(key_weights.shape)}")
+        if key_segments is None:
+            key_segments = torch.zeros(B, n_kv, dtype=torch.uint8, device=dev)
+            query_segments = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
     if (kv_lens is None) == (key_segments is None):
         raise ValueError("exactly one of kv_lens and the pair key_segments + query_segments selects the form")
     if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
@@ -521,6 +533,13 @@ def attention_pick(q, k, vt, n_kv, pick, want, out, use_exp2=False, kv_lens=None
                 not query_segments.is_contiguous():
             raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
                              f"{tuple(query_segments.shape)}")
+    if key_weights is not None:
+        bias = key_bias(key_weights, use_exp2)
+        with torch.cuda.device(dev):
+            check(lib.pmhip_attention_pick_weighted(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), out.stride(0), B, H, dh, Nq, n_kv, nkp,
+                                                    int(use_exp2), _p(key_segments), _p(query_segments), _p(bias), _p(pick), int(want),
+                                                    stream_ptr(dev)), "pmhip_attention_pick_weighted")
+        return out
     with torch.cuda.device(dev):
         check(lib.pmhip_attention_pick(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), out.stride(0), B, H, dh, Nq, n_kv, nkp, int(use_exp2),
                                        _p(kv_lens), _p(key_segments), _p(query_segments), _p(pick), int(want), stream_ptr(dev)),

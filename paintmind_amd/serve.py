@@ -87,10 +87,30 @@ Guidance or a schedule, a negative prompt, a choice temperature, the filters and
 context and the negative prompt's pass never see regions).  An edit request (``keep_given``, ``image=``) with ``regions=`` is
 refused -- there is no scalar edit with regions to be identical to -- and so is ``regions=`` in an unconditional session.
 
+Prompt weights are per request in a session opened with ``pipe.decode_session(..., weights=True)`` (an option
+like ``regions=``, composing with it and with ``filters=True``; without it the session is the one above, refusals included).
+``submit(text=...)`` is then read as ``Pipeline.generate(prompt_weights=True)`` reads it -- the session calls ``text_model([text],
+weighted=True)`` and, as a session always does, attends to the context in full; ``submit(context=(ctx [L, D], w [L]))`` takes the
+weights explicitly (a plain tensor stays what it was); with ``regions=True`` an item of ``regions=`` may be ``(prompt, mask, weight)``
+and beside ``text=`` the region prompts are read for emphasis too (``_region_context_weighted`` at B = 1).  ``negative_text`` is not
+read for emphasis.  A request is WEIGHTED iff any weight of its context is not exactly 1 (``weighted`` below states the rule; its
+``Request.weights`` is then the array, otherwise None): it runs as kind 2 of the native step (pmhip_pipeline_step_slots_weights: a
+kind per slot -- 0 under its length, 1 under its key sets, 2 under its key sets and its weights), under its own segments if it is
+regional and the one-segment layout otherwise; every other request keeps the kind and the cost it has today.  Every layer's
+cross-attention of the pass with the context is then three picked launches into one buffer, the third being the picked weighted
+form.  The contract: a weighted request in slot j of an S-slot session produces, bit for bit, the per-step predictions, the scores
+and the final ids of row j of ``generate_ids(context [S, capacity, D] with its rows in row j, context_segments / token_segments with
+its layout (or the one-segment layout: segment 0 below its total, 255 behind, token masks of 1) in row j, context_weights with its
+weights in row j, neutral rows -- one segment, weights of 1 -- elsewhere, B=S, ..., image_base=k - j, streams=1)``; the plain and the
+regional requests beside it still equal their ``context_lens=`` / segment rows.  A step passes the weights only while an occupied
+slot is weighted: a session without such a request runs the steps, launches and graphs it ran before.  An edit request with
+weights (the edit loop takes none), weights in an unconditional session and a weight outside 0 / [2^-20, 2^20] raise ValueError.
+
 On a CPU pipeline the session steps every occupied slot alone through the plain-torch step (B = 1, seed + step, like
 ``Pipeline.generate`` on the CPU): a request then equals ``pipe.generate([text], ..., seed=seed, guidance_scale=s,
 negative_text=n)`` -- in a FilterSession with ``topk=, top_p=`` as well -- and an edit request equals ``pipe.edit(img[None], ...,
-seed=seed)``; a regional request equals ``pipe.generate([text], regions=[regions], ..., seed=seed)``.
+seed=seed)``; a regional request equals ``pipe.generate([text], regions=[regions], ..., seed=seed)``; in a weights session a request with
+emphasis equals ``pipe.generate([text], prompt_weights=True, ..., seed=seed)``, ids and image exact.
 """
 import collections
 import math
@@ -104,6 +124,12 @@ from . import _lib, ops
 Finished = collections.namedtuple("Finished", ["handle", "image", "ids"])
 
 
+def weighted(weights):
+    """THE rule of a weights session: a request is weighted iff any weight of its context is not exactly 1.
+    Every other request is the request it would be in a session without the option, at the cost it has there."""
+    return weights is not None and bool((np.asarray(weights, np.float32) != 1).any())
+
+
 def _no_regions(regions):
     if regions is not None:
         raise ValueError("a decode session serves no regional prompts (regions=): Pipeline.generate(regions=) does")
@@ -113,7 +139,9 @@ class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
     def __init__(self, number, text, context, timesteps, temperature, topk, seed, image_index, temps, nmask, ids0, guidance_scale=None,
-                 ctemps=None, negative=None, scales=None, top_p=1.0, edit=False, orig=None, pixel_mask=None, segments=None):
+                 ctemps=None, negative=None, scales=None, top_p=1.0, edit=False, orig=None, pixel_mask=None, segments=None, weights=None):
+        # a weighted request (``weighted`` above): numpy float32 [L_r], the weight of every row of its context; None: a plain one
+        self.weights = weights
         # a regional request: (numpy uint8 [L_r], the segment of every row of its context; numpy uint32 [N], the segments of every token)
         self.segments = segments
         self.edit = edit                            # an edit request: nmask is edit_schedule's over its masked start ids, given ids stay
@@ -143,7 +171,8 @@ class DecodeSession:
     use_graph=None follows PMHIP_GENERATE_GRAPH like ``Pipeline.generate``."""
 
     def __init__(self, pipe, slots=64, conditional=True, use_graph=None, record_steps=False, decode=True, max_context_len=None,
-                 max_negative_len=None, regions=False):
+                 max_negative_len=None, regions=False, weights=False):
+        self.weights = bool(weights)        # prompt weights are served (DESIGN.md section 4x); False: refused, as before there was the option
         self.regions = bool(regions)        # submit(regions=) is served (DESIGN.md section 4v); False: refused, as before there was the option
         if slots < 1:
             raise ValueError("a decode session needs at least one slot")
@@ -197,7 +226,9 @@ class DecodeSession:
         from an image -- it is encoded and masked here, at submit -- and `preserve` ("tokens" | "pixels"): "pixels" puts the original
         pixels back outside the pixel mask, as in ``Pipeline.edit``.
         `regions`: refused -- unless the session was opened with ``regions=True``: then ONE image's list ``[(prompt, mask), ...]`` of
-        ``Pipeline.generate(regions=)``, `text` (or `context`) staying the global prompt (the module docstring has the rules)."""
+        ``Pipeline.generate(regions=)``, `text` (or `context`) staying the global prompt (the module docstring has the rules).
+        In a session opened with ``weights=True`` `text` (and the prompts of `regions`) may carry emphasis, ``a (red:1.4) barn``,
+        `context` may be a pair ``(context [L_r, D], weights [L_r])``, and an item of `regions` may be ``(prompt, mask, weight)``."""
         if not self.regions:
             _no_regions(regions)
         return self._submit(text, timesteps, temperature, topk, None, seed, image_index, context, ids0, guidance_scale, choice_temperature,
@@ -211,9 +242,11 @@ class DecodeSession:
             raise ValueError(f"a decode session serves topk in 1..8, got {topk}")
         return topk, 1.0
 
-    def _region_request(self, text, context, regions):
+    def _region_request(self, text, context, regions, weights=None):
         """submit(regions=) -> (the request's context [L_total, D]: global | region 1 | ..., (its segment row uint8 [L_total], its
-        token masks uint32 [N])), by the code of ``Pipeline.generate(regions=)`` at B = 1"""
+        token masks uint32 [N]), its weights float32 [L_total] or None), by the code of ``Pipeline.generate(regions=)`` at B = 1.
+        In a weights session the prompts are read for emphasis (``generate(prompt_weights=True)``), `weights` are those of a
+        ``context=`` pair (the global prompt's rows), and a region's third element multiplies its rows' weights."""
         from .generate import MAX_REGIONS, region_layout
         pipe = self.pipe
         regions = list(regions)
@@ -222,25 +255,48 @@ class DecodeSession:
         if context is None:
             if text is None:
                 raise ValueError("a conditional session needs a text (or a context) for every request")
-            ctx, cs, ts, weights = pipe._region_context_weighted([text], [regions], False)
-            if weights is not None:
+            ctx, cs, ts, weights = pipe._region_context_weighted([text], [regions], False, self.weights)
+            if weights is not None and not self.weights:
                 raise ValueError("regions: a decode session serves no prompt weights ((prompt, mask, weight)): Pipeline.generate(regions=) does")
+            weights = None if weights is None else weights[0]
         else:
+            sizes = (2, 3) if self.weights else (2,)
             for item in regions:
-                if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], torch.Tensor) and item[0].dim() == 2
+                if not (isinstance(item, (tuple, list)) and len(item) in sizes and isinstance(item[0], torch.Tensor) and item[0].dim() == 2
                         and item[0].shape[0] >= 1 and item[0].shape[1] == context.shape[-1]):
+                    raise ValueError("regions: beside context= every region is a (context [L_r, D], mask) pair of the context's width")
+                if len(item) == 3 and (isinstance(item[2], bool) or not isinstance(item[2], (int, float))):
                     raise ValueError("regions: beside context= every region is a (context [L_r, D], mask) pair of the context's width")
             if context.dim() != 2 or context.shape[0] < 1:
                 raise ValueError(f"a request's context is [L, D] with L >= 1, got {tuple(context.shape)}")
             ctx, cs, ts = region_layout([[context] + [item[0] for item in regions]], [[item[1] for item in regions]], pipe.image_size,
                                         pipe.patch_size)
-        return ctx[0], (cs[0], ts[0])
+            if self.weights:                            # the pair's weights on the global rows, a region's number on its rows
+                parts = [np.ones(context.shape[0], np.float32) if weights is None else np.asarray(weights, np.float32).reshape(-1)]
+                parts += [np.full(item[0].shape[0], item[2] if len(item) == 3 else 1.0, np.float32) for item in regions]
+                weights = np.concatenate(parts)
+        return ctx[0], (cs[0], ts[0]), weights
+
+    def _request_weights(self, weights, context, segments):
+        """a weights session's request: its weights as they came (the text model's, a ``context=`` pair's, the regions') -> numpy
+        float32 [L_r] checked by ``ops.host_weights`` at B = 1 under the request's own layout, or None when the request is not
+        weighted (``weighted``): it is then a plain request"""
+        if weights is None:
+            return None
+        w = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else np.asarray(weights)
+        L = context.shape[0]
+        if w.shape != (L,) or w.dtype.kind not in "fiu":
+            raise ValueError(f"a request's weights are numbers of shape ({L},), one per context row, got {w.dtype} {w.shape}")
+        cs, ts = (None, None) if segments is None else (segments[0][None], segments[1][None])
+        w = ops.host_weights(w[None], 1, L, self.pipe.num_tokens, cs, ts)[2][0]
+        return w if weighted(w) else None
 
     def _segment_arrays(self, capacity):
         """this step's (ctx_seg uint8 [S, capacity], tok_seg uint32 [S, N], flags uint8 [S]) for the native step, or None when no
-        occupied slot is regional (the step without).  A regional slot's rows are its layout, 255 behind its total; every other
+        occupied slot is regional or weighted (the step without).  The flag is the slot's kind: 0 plain, 1 regional, 2 weighted
+        (DESIGN.md section 4x).  A regional slot's rows are its layout, 255 behind its total; every other
         slot's rows are the one-segment layout (the native step does not look at them)."""
-        if not any(r is not None and r.segments is not None for r in self.occupied):
+        if not any(r is not None and (r.segments is not None or r.weights is not None) for r in self.occupied):
             return None
         cs = np.zeros((self.size, capacity), np.uint8)
         ts = np.ones((self.size, self.pipe.num_tokens), np.uint32)
@@ -253,7 +309,20 @@ class DecodeSession:
                 cs[j, :r.context.shape[0]] = r.segments[0]
                 ts[j] = r.segments[1]
                 flags[j] = 1
+            if r.weights is not None:                   # under its own segments if it is regional, the one-segment layout otherwise
+                flags[j] = 2
         return cs, ts, flags
+
+    def _weight_array(self, capacity):
+        """this step's weights float32 [S, capacity] for the native step, or None when no occupied slot is weighted (the step
+        without).  A weighted slot's row is its weights, 1 behind its total; every other slot's row is 1 (not looked at)."""
+        if not any(r is not None and r.weights is not None for r in self.occupied):
+            return None
+        w = np.ones((self.size, capacity), np.float32)
+        for j, r in enumerate(self.occupied):
+            if r is not None and r.weights is not None:
+                w[j, :r.weights.shape[0]] = r.weights
+        return w
 
     def _edit_start(self, ids0, keep_given, image, mask, token_mask, preserve):
         """the edit keywords of submit(), checked -> (ids0, edit, orig, pixel mask): an image is encoded (B = 1) and masked here, by
@@ -294,13 +363,33 @@ class DecodeSession:
                 negative_text, negative_context, keep_given=False, image=None, mask=None, token_mask=None, preserve="tokens", regions=None):
         """submit() behind its keywords; (topk, top_p) go through _filters, the session's own range of them"""
         topk, top_p = self._filters(topk, top_p)
-        segments = None
+        segments, weights = None, None
+        if isinstance(context, (tuple, list)):          # the pair (context [L_r, D], weights [L_r]) of a weights session
+            if not self.weights:
+                raise ValueError("a decode session serves no prompt weights (context=(context, weights)): open it with weights=True")
+            if not self.conditional:
+                raise ValueError("prompt weights need a text condition (an unconditional session IS the unconditional branch)")
+            if len(context) != 2 or not isinstance(context[0], torch.Tensor):
+                raise ValueError("context= is a tensor [L, D] or a pair (context [L, D], weights [L])")
+            context, weights = context
         if regions is not None:
             if not self.conditional:
                 raise ValueError("regions need a text condition (an unconditional session IS the unconditional branch)")
             if keep_given or image is not None:
                 raise ValueError("an edit request (keep_given, image=) takes no regions: Pipeline.edit has none to be identical to")
-            context, segments = self._region_request(text, context, regions)
+            context, segments, weights = self._region_request(text, context, regions, weights)
+        elif self.weights and self.conditional and context is None and text is not None:
+            # the text is read as generate(prompt_weights=True) reads it; the context is attended to in full, as a session always does
+            context, _, weights = self.pipe.text_model([text], weighted=True)
+            if context is None:
+                raise ValueError("the pipeline's text model gives no context: open the session with conditional=False")
+            context, weights = context[0], weights[0]
+        if weights is not None:
+            if context.dim() != 2 or context.shape[0] < 1:
+                raise ValueError(f"a request's context is [L, D] with L >= 1, got {tuple(context.shape)}")
+            weights = self._request_weights(weights, context, segments)
+            if weights is not None and (keep_given or image is not None):
+                raise ValueError("an edit request (keep_given, image=) takes no prompt weights: Pipeline.edit has none to be identical to")
         ids0, edit, orig, pixel_mask = self._edit_start(ids0, keep_given, image, mask, token_mask, preserve)
         timesteps = int(timesteps)
         if timesteps < 1:
@@ -361,7 +450,7 @@ class DecodeSession:
         if edit:                                    # m is counted once, here: the schedule over the region instead of the image
             nmask = edit_schedule(int((ids0 == self.pipe.mask_token_id).sum()), timesteps)
         r = Request(self._submitted, text, context, timesteps, temperature, topk, int(seed), int(image_index), temps, nmask, ids0, guidance_scale,
-                    ctemps, negative, scales, top_p, edit, orig, pixel_mask, segments)
+                    ctemps, negative, scales, top_p, edit, orig, pixel_mask, segments, weights)
         self._submitted += 1
         self.queue.append(r)
         return r
@@ -422,10 +511,13 @@ class DecodeSession:
             ctx = None if r.context is None else r.context[None]
             neg = None if r.negative is None else r.negative[None]
             # an edit request: the step with a count per image, as Pipeline.edit's CPU branch takes it
+            seg = None if r.segments is None else (r.segments[0][None], r.segments[1][None])
+            if r.weights is not None:                   # the three arrays generate(prompt_weights=True) hands its CPU loop
+                seg = ops.host_weights(r.weights[None], 1, r.context.shape[0], pipe.num_tokens, *(seg or ()))
             ids, img = pipe._sample_cpu(self._rows[j], 0 if r.edit else r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t,
                                         r.scales[t] if r.scales else r.guidance_scale, None, r.ctemps[t] if r.ctemps else 0.0,
                                         top_p=r.top_p, negative=neg, negative_lens=None, **({"counts": [r.nmask[t]]} if r.edit else {}),
-                                        **({"segments": (r.segments[0][None], r.segments[1][None])} if r.segments is not None else {}))
+                                        **({"segments": seg} if seg is not None else {}))
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
@@ -520,8 +612,12 @@ class DecodeSession:
             neg_lens = [min(n, neg.shape[1]) for n in self._neg_lens]
 
         # the regional slots' arrays -- None when no occupied slot is regional: the step without
-        segments = self._segment_arrays(ctx.shape[1]) if self.regions and self.conditional else None
+        segments = self._segment_arrays(ctx.shape[1]) if (self.regions or self.weights) and self.conditional else None
         seg_kw = {} if segments is None else {"segments": segments}
+        # the weighted slots' array -- None when no occupied slot is weighted: the step without
+        wts = self._weight_array(ctx.shape[1]) if self.weights and self.conditional else None
+        if wts is not None:
+            seg_kw["weights"] = wts
 
         def run(keep_context, keep_negative):
             return eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep_context, want_aux=want_aux,

@@ -6,7 +6,11 @@ Behind them the picked forms of DESIGN.md section 4v (pmhip_attention_pick): eac
 none -- the last is what a launch costs whose workgroups all return at once -- and the pair of launches of a half-regional batch.
 Behind those the weighted form of DESIGN.md section 4w (pmhip_attention_weighted) under the same masks, with weights cycling through
 1/8, 1, 8 and 1.3: the call of ``ops.attention(key_weights=)``, which converts the weights first (pmhip_key_bias, one more launch), and
-that conversion alone."""
+that conversion alone.
+Behind those the picked weighted form of DESIGN.md section 4x (pmhip_attention_pick_weighted, the bias converted once outside the
+timed call as the engine does per step): every image served, every second one and none; the three launches of a batch mixed in
+thirds (plain, regional, weighted); and the three launches with no weighted image, against the pair of 4v -- the difference is what
+the now-third empty launch costs per layer."""
 import os
 import sys
 
@@ -67,3 +71,20 @@ for dtype, exp2 in ((torch.bfloat16, True), (torch.float32, False)):
             ops.attention_pick(q, k, vt, NKV, picks["half"], 1, out, use_exp2=exp2, key_segments=ks, query_segments=qm)
         fmt = lambda d: ", ".join(f"{n} served {v:.1f} us" for n, v in d.items())
         print(f"    picked lens form: {fmt(lens_pick)}; picked segments form: {fmt(seg_pick)}; both launches, half and half: {timed(pair):.1f} us")
+    if "pmhip_attention_pick_weighted" in getattr(ops._lib, "PROTOTYPES", {}):
+        from paintmind_amd.ops import _p, check, pm_dtype, stream_ptr
+        lib, bias = ops._lib.load(), ops.key_bias(w, exp2)
+
+        def pick_weighted(p, want):
+            check(lib.pmhip_attention_pick_weighted(pm_dtype(dtype), _p(q), _p(k), _p(vt), _p(out), H * 64, B, H, 64, NQ, NKV, NKP, int(exp2), _p(ks),
+                                                    _p(qm), _p(bias), _p(p), want, stream_ptr(dev)), "pmhip_attention_pick_weighted")
+        w_pick = {n: timed(lambda: pick_weighted(p, 0)) for n, p in picks.items()}
+        thirds = (torch.arange(B) % 3).to(torch.uint8).to(dev)
+
+        def three(p):
+            ops.attention_pick(q, k, vt, NKV, p, 0, out, use_exp2=exp2, kv_lens=lens)
+            ops.attention_pick(q, k, vt, NKV, p, 1, out, use_exp2=exp2, key_segments=ks, query_segments=qm)
+            pick_weighted(p, 2)
+        mixed, three_half, two_half = timed(lambda: three(thirds)), timed(lambda: three(picks["half"])), timed(pair)
+        print(f"    picked weighted form: {fmt(w_pick)}; three launches, a third of each kind: {mixed:.1f} us; three launches, half plain and half "
+              f"regional: {three_half:.1f} us against the pair's {two_half:.1f} us (the empty third launch: {three_half - two_half:.1f} us)")

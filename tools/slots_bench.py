@@ -25,6 +25,12 @@
            one, all of them (two region prompts of 77 rows each over halves of the grid: a total of 231 rows, the capacity).
            --arms picks among none,half,all; a commit without the feature runs ``--arms none`` (point --root at it).
 
+  weights  prompt weights per request: milliseconds per session step, measured like ``regions`` -- S conditional
+           requests (T steps, a [77, D] context each, the capacity) admitted together, none weighted (a weights session's steps without
+           such a request: the steps of a session without the option), every second one, all of them (weights cycling through 1/8,
+           1, 8 and 1.3 over the rows).  --arms picks among none,half,all; a commit without the feature runs ``--arms none`` (point
+           --root at it: the option is then left out).
+
 The arms alternate inside one process, --rounds times; nothing is decoded (ids only).  --arms generate runs on a commit that has
 no sessions: point --root at such a checkout to time the scalar loop of another commit on the same box.
 """
@@ -39,7 +45,7 @@ import time
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), help="checkout whose paintmind_amd is timed")
-    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed", "guided", "negative", "regions"])
+    ap.add_argument("--mode", default="uniform", choices=["uniform", "mixed", "guided", "negative", "regions", "weights"])
     ap.add_argument("--arms", default="session,generate")
     ap.add_argument("--workload", default=None, help="default: bench-uncond-12L-d512; guided: bench-text-24L-d768")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
@@ -85,6 +91,11 @@ def main():
         if a.arms == "session,generate":
             a.arms = "none,half,all"
         emit(regions_session(a, dev), a.out)
+        return
+    if a.mode == "weights":
+        if a.arms == "session,generate":
+            a.arms = "none,half,all"
+        emit(weights_session(a, dev), a.out)
         return
     pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
     pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
@@ -323,6 +334,57 @@ def regions_session(a, dev):
     eng = pipe.engine()
     if hasattr(eng, "slots_region_steps"):
         out["slots_region_steps"] = eng.slots_region_steps()
+    return out
+
+
+def weights_session(a, dev):
+    """ms per session step (graph replay, nothing decoded), by how many of the S requests carry prompt weights"""
+    import inspect
+    import torch
+    import paintmind_amd as pm
+    from paintmind_amd.generate import Pipeline
+    pipe = Pipeline(pm.Config(pm.ver2cfg[a.workload]), stage1_pretrained=False).to(dev).eval()
+    pipe.set_compute_dtype(torch.bfloat16 if a.dtype == "bf16" else torch.float32)
+    S, T = a.slots, max(a.timesteps, 21)
+    D = pipe.engine().context_dim
+    ctx = torch.randn(S, 77, D, generator=torch.Generator().manual_seed(2))
+    w = torch.tensor([0.125, 1.0, 8.0, 1.3])[torch.arange(77) % 4].numpy()
+    share = {"none": lambda i: False, "half": lambda i: i % 2 == 1, "all": lambda i: True}
+    arms = a.arms.split(",")
+    has_option = "weights" in inspect.signature(Pipeline.decode_session).parameters
+
+    def run(arm, seed, timed):
+        kw = dict(weights=True) if has_option else {}
+        s = pipe.decode_session(slots=S, conditional=True, use_graph=True, decode=False, max_context_len=77, **kw)
+        for i in range(S):
+            s.submit(context=(ctx[i], w) if share[arm](i) else ctx[i], timesteps=T, temperature=1.0, topk=5, seed=seed + i)
+        ms = []
+        for step in range(T):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            s.step()
+            e1.record()
+            if timed and step > 0:
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+        assert s.idle()
+        return ms
+
+    for arm in arms:                                   # eager pass, capture pass
+        for k in range(2):
+            run(arm, k, False)
+    torch.cuda.synchronize(dev)
+    ms = {arm: [] for arm in arms}
+    for rnd in range(a.rounds):
+        for arm in arms:
+            ms[arm] += run(arm, 100 * rnd, True)
+    stat = lambda v: {"steps": len(v), "median": sorted(v)[len(v) // 2], "mean": sum(v) / len(v), "min": min(v)}
+    out = {"mode": "weights", "root": os.path.abspath(a.root), "workload": a.workload, "dtype": a.dtype, "slots": S, "timesteps": T,
+           "context_rows": 77, "option": has_option, "ms_per_step": {arm: stat(v) for arm, v in ms.items()}}
+    eng = pipe.engine()
+    if hasattr(eng, "slots_weight_steps"):
+        out["slots_weight_steps"] = eng.slots_weight_steps()
+    out["graphs"] = list(eng.graph_count())
     return out
 
 
