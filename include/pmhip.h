@@ -26,6 +26,7 @@
  *         ldo >= N, ldr >= N          pmhip_gemm / _ln / _softmax_stats (ldr only with a residual), pmhip_gemm_hilo / _stats / _center
  *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
  *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens
+ *         ldm >= Nkv                  pmhip_attention_maps
  *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus, pmhip_masked_ce
  *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
  *     N * ldw stay below 2^30 elements; beyond that another kernel may serve the call).
@@ -302,6 +303,38 @@ int pmhip_attention_pick_weighted(int dtype, const void* Q, const void* K, const
                                   int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
                                   const uint32_t* query_mask, const float* key_bias, const uint8_t* pick, int want,
                                   pmhip_stream stream);
+
+/* Cross-attention maps: the head-mean probabilities of one attention launch, materialised (new entry within ABI 11, nothing
+ * existing changes meaning).  The flash kernels above never hold a row of P; this entry recomputes it from the
+ * Q and K such a launch reads.  Q [B,H,Nq,dh] and K [B,H,Nkv_pad,dh] (`dtype`) have the layouts pmhip_gemm_heads(_dh) writes; Q is
+ * already scaled and carries log2(e) when use_exp2 != 0.  maps DEVICE f32 [B, Nq, ldm], ldm >= Nkv.  For every image b, query q and
+ * key k < Nkv:
+ *     v = scale * (1 / heads) * sum_h p_h[q,k]          maps[b,q,k] = accumulate ? maps[b,q,k] + v : v
+ * p_h is the softmax of the attention entry the nullable arrays select:
+ *     all NULL                           pmhip_attention_dh
+ *     kv_lens                            pmhip_attention_lens, with the same clamp to [1, Nkv]
+ *     key_seg + query_mask               pmhip_attention_segments
+ *     key_seg + query_mask + key_bias    pmhip_attention_weighted
+ * Any other combination is PMHIP_EINVAL.  Contract:
+ *   - excluded keys: a key that takes no part in a query's softmax -- behind the image's length, of a segment the query does not
+ *     attend to, of segment 255, with bias -inf -- is written as exactly 0.0f, or left as it is under `accumulate`; NaN in the K row
+ *     of such a key reaches nothing (it is masked by a select, never by arithmetic)
+ *   - row sums: over the keys that take part, a row of one launch sums to `scale` within f32 rounding ((Nkv + heads + 74) 2^-23
+ *     relative, plus the score error of the bound in tests/attnmap_ref.py)
+ *   - memory: columns [Nkv, ldm) of every row and every byte outside `maps` are untouched; nothing is read outside Nkv_pad or the
+ *     arrays (K rows at or behind Nkv are never read)
+ *   - a query with no allowed key yields a finite, unspecified row (zeros today), as in pmhip_attention_segments
+ *   - determinism: the sum over the heads runs in the fixed order h = 0 .. heads-1 inside one thread; there are no floating-point
+ *     atomics; every element of `maps` is written by exactly one thread, once per launch; two launches on the same inputs agree bit
+ *     for bit; image b's rows do not depend on what else is in the batch
+ *   - precision: P stays f32, also in bf16 mode.  The product's bf16 kernel rounds P to bf16 for its P.V MFMA; the maps report the f32
+ *     probabilities of the same bf16 Q and K, not those rounded values
+ * Any dim_head the _dh entry serves, any Nkv (two passes over the context; registers and LDS do not depend on it), heads <= 64.  bf16
+ * with dim_head 64 runs on MFMA (64 queries per workgroup, 16 per wave; Q and K 16-byte aligned); fp32 and every other dim_head run a
+ * plain vector-ALU kernel, 4 lanes per query. */
+int pmhip_attention_maps(int dtype, const void* Q, const void* K, float* maps, int ldm, int B, int heads, int dim_head, int Nq, int Nkv,
+                         int Nkv_pad, int use_exp2, const int32_t* kv_lens, const uint8_t* key_seg, const uint32_t* query_mask,
+                         const float* key_bias, float scale, int accumulate, pmhip_stream stream);
 
 /* torch.nn.LayerNorm over the last dim, eps inside the sqrt (stage1/layers.py:49,51,89,128;
  * stage2/transformer.py:37,39,41,62).  x fp32 [M,D] -> out (`out_dtype`). */
@@ -1124,6 +1157,20 @@ int pmhip_pipeline_generate_segments(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids
  * The other arguments are those of the entry each extends. */
 int pmhip_s2_forward_weights(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const uint8_t* ctx_seg_host,
                              const uint32_t* tok_seg_host, const float* ctx_w_host, float* logits_out, pmhip_stream stream);
+/* pmhip_s2_forward_weights / _lens with the cross-attention maps of chosen layers beside the logits (new entry within ABI 11, nothing
+ * existing changes meaning).  layer_bits: bit l set = layer l is chosen.  maps_out DEVICE f32 [B, tokens, L]:
+ * (1 / n) * the sum over the n chosen layers of that layer's head-mean probabilities (pmhip_attention_maps on the layer's scaled Q,
+ * its cached K and the call's lengths, key sets and key biases, issued directly behind the layer's cross-attention launch; the first
+ * chosen layer writes, the later ones accumulate, each with scale = 1 / n).  Rows of the context that take part in no softmax are 0.
+ *   - validation happens before anything is launched: the checks of pmhip_s2_forward_weights and _lens with the combination rules
+ *     of pmhip_pipeline_sample_weights (the weights beside the lengths, beside the segment arrays, or alone), plus: a context is
+ *     required, layer_bits != 0, no bit at or above depth, maps_out != NULL
+ *   - logits_out gets, bit for bit, the logits of the matching existing entry on the same arguments
+ *   - eager only: the entry adds no key to the handle's graph cache, and it clears the tap before it returns, on the error paths too:
+ *     a later call of any entry runs exactly what it ran before */
+int pmhip_s2_forward_maps(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                          const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const float* ctx_w_host, uint64_t layer_bits,
+                          float* logits_out, float* maps_out, pmhip_stream stream);
 int pmhip_pipeline_sample_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                   const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
                                   uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,

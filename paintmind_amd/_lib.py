@@ -235,6 +235,10 @@ PROTOTYPES = {
                                                 vp, i32, C.POINTER(i32), C.POINTER(f32), C.POINTER(i32), C.POINTER(C.c_ubyte),
                                                 C.POINTER(u32), C.POINTER(C.c_ubyte), C.POINTER(f32), i32, vp, vp, vp]),
     "pmhip_s2_slots_weight_steps": (i32, [vp, C.POINTER(i32)]),
+    # cross-attention maps: the operator, and the forward that taps chosen layers
+    "pmhip_attention_maps": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, i32, vp]),
+    "pmhip_s2_forward_maps": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(C.c_ubyte), C.POINTER(u32), C.POINTER(f32), u64, vp, vp,
+                                    vp]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

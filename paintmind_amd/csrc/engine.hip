@@ -209,6 +209,11 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     // slots step with a weighted slot) the set carries lens, the segments, pick AND key_bias together, and only the
     // images of kind 2 read their rows of it.
     const float* key_bias = nullptr;
+    // the maps tap (pmhip_s2_forward_maps only), THIS call's or NULL: device f32 [B, tokens, L].  A layer whose set carries
+    // it issues one pmhip_attention_maps directly behind its cross-attention launch, with this scale, writing or accumulating.
+    float* maps = nullptr;
+    float maps_scale = 1.f;
+    bool maps_accumulate = false;
 };
 
 // The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
@@ -473,6 +478,11 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
                                             cross->lens, s));
             else
                 PM_TRY(pmhip_attention_dh(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast, s));
+            // the maps tap: the head-mean probabilities of the launch above, from the same Q, K, lengths, sets and biases
+            if (cross->maps)
+                PM_TRY(pmhip_attention_maps(dtype, b.q, cross->k, cross->maps, cross->L, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
+                                            cross->key_seg ? nullptr : cross->lens, cross->key_seg, cross->query_mask, cross->key_bias,
+                                            cross->maps_scale, cross->maps_accumulate, s));
         } else {
             void* outs[3] = {b.q, b.k, b.vt};
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 3, kinds_qkv,
@@ -1401,8 +1411,16 @@ int run_graphs(pmhip_s2* s2, pmhip_vqgan* vq, GraphEntry& ge, size_t n_units, hi
 
 static int s2_forward_impl(const char* who, pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
                            float* logits_out, pmhip_stream stream, const uint8_t* ctx_seg_host = nullptr,
-                           const uint32_t* tok_seg_host = nullptr, const float* ctx_w_host = nullptr) {
+                           const uint32_t* tok_seg_host = nullptr, const float* ctx_w_host = nullptr, uint64_t layer_bits = 0,
+                           float* maps_out = nullptr) {
     PM_REQUIRE(h && tokens && logits_out && B > 0, "%s: bad arguments", who);
+    if (maps_out) {                                           // pmhip_s2_forward_maps: three checks of its own, before anything is launched
+        const int depth = h->cfg.tower.depth;
+        PM_REQUIRE(context && L > 0, "%s: the maps are those of the cross-attention: a context is required", who);
+        PM_REQUIRE(layer_bits != 0, "%s: layer_bits selects no layer", who);
+        PM_REQUIRE(depth >= 64 || (layer_bits >> depth) == 0, "%s: layer_bits 0x%llx selects a layer at or above depth=%d", who,
+                   (unsigned long long)layer_bits, depth);
+    }
     PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
     PM_TRY(check_segments(who, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, h));
     CtxWeights cw;
@@ -1416,6 +1434,21 @@ static int s2_forward_impl(const char* who, pmhip_s2* h, const float* tokens, co
     void* tp;
     PM_TRY(tok_buf(h, M, tp, s));
     PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
+    if (!maps_out) return s2_tower(h, tp, B, logits_out, s);
+    // the maps tap: the chosen layers' sets carry the pointer for this one eager tower, the first one writing, the
+    // later ones accumulating, each with scale 1 / n; cleared on every way out
+    struct Tap {
+        std::vector<CrossKV>& kv;
+        ~Tap() { for (auto& ck : kv) { ck.maps = nullptr; ck.maps_scale = 1.f; ck.maps_accumulate = false; } }
+    } tap{h->cross};
+    int n = 0;
+    for (size_t l = 0; l < h->cross.size() && l < 64; ++l) n += (int)((layer_bits >> l) & 1);
+    bool first = true;
+    for (size_t l = 0; l < h->cross.size() && l < 64; ++l)
+        if ((layer_bits >> l) & 1) {
+            h->cross[l].maps = maps_out; h->cross[l].maps_scale = 1.0f / (float)n; h->cross[l].maps_accumulate = !first;
+            first = false;
+        }
     return s2_tower(h, tp, B, logits_out, s);
 }
 
@@ -1451,6 +1484,15 @@ extern "C" int pmhip_s2_forward_weights(pmhip_s2* h, const float* tokens, const 
                                         const uint32_t* tok_seg_host, const float* ctx_w_host, float* logits_out, pmhip_stream stream) {
     const char* who = ctx_w_host ? "s2_forward_weights" : ctx_seg_host || tok_seg_host ? "s2_forward_segments" : "s2_forward";
     return s2_forward_impl(who, h, tokens, context, L, B, nullptr, logits_out, stream, ctx_seg_host, tok_seg_host, ctx_w_host);
+}
+
+// the logits of pmhip_s2_forward_weights / _lens on the same arguments, and the chosen layers' cross-attention maps beside them
+extern "C" int pmhip_s2_forward_maps(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                     const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const float* ctx_w_host, uint64_t layer_bits,
+                                     float* logits_out, float* maps_out, pmhip_stream stream) {
+    PM_REQUIRE(maps_out, "s2_forward_maps: maps_out is NULL (pmhip_s2_forward_weights is the entry without maps)");
+    return s2_forward_impl("s2_forward_maps", h, tokens, context, L, B, ctx_lens_host, logits_out, stream, ctx_seg_host, tok_seg_host, ctx_w_host,
+                           layer_bits, maps_out);
 }
 
 // The sample family's one builder: the argument list of pmhip_pipeline_sample_nucleus, the widest entry, -> the Step and the name

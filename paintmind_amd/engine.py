@@ -357,6 +357,34 @@ class S2Engine:
                   "pmhip_s2_forward_lens")
         return logits
 
+    def forward_maps(self, tokens, context, layers, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
+        """``forward`` with the cross-attention maps of the chosen layers beside the logits (pmhip_s2_forward_maps; DESIGN.md section
+        4y).  layers: the layer indices (an iterable of distinct ints in [0, depth)).  -> (logits, maps): the logits ``forward`` returns
+        on the same arguments, bit for bit, and maps f32 [B, tokens, L], the mean over the chosen layers of the head-mean
+        probabilities of each layer's cross-attention; context rows that take part in no softmax are exactly 0.  Always eager."""
+        if context is None:
+            raise ValueError("forward_maps: the maps are those of the cross-attention: a context is required")
+        depth = self.cfg.tower.depth
+        chosen = [int(l) for l in layers]
+        if not chosen or len(set(chosen)) != len(chosen) or min(chosen) < 0 or max(chosen) >= depth:
+            raise ValueError(f"forward_maps: layers {list(layers)!r} must be distinct indices in [0, {depth})")
+        bits = 0
+        for l in chosen:
+            bits |= 1 << l
+        tokens = tokens.to(self.device, torch.float32).contiguous()
+        B = tokens.shape[0]
+        context, L = self._ctx(context)
+        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L)
+        lens = self._lens(context_lens, context, B, L)
+        seg = wts[0] if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L) or (None, None)
+        logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
+        maps = torch.empty(B, self.tokens, L, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            check(self.lib.pmhip_s2_forward_maps(self.handle, _p(tokens), _p(context), L, B, lens, seg[0], seg[1],
+                                                 wts[1] if wts is not None else None, bits, _p(logits), _p(maps), stream_ptr(self.device)),
+                  "pmhip_s2_forward_maps")
+        return logits, maps
+
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
                want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None,
                top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None, context_weights=None):

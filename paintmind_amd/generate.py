@@ -453,6 +453,82 @@ class Pipeline(nn.Module):
         return self.engine().forward(token, text, context_lens=lens, **kw)
 
     @torch.no_grad()
+    def attention_maps(self, ids=None, text=None, layers=None, context_lens=None, mask_padding=False, context_segments=None,
+                       token_segments=None, context_weights=None, return_logits=False, img=None):
+        """CROSS-ATTENTION MAPS (extension): which tokens of the picture look at which rows of the prompt.
+
+        ``ids``: int64 [B, N] token ids, the mask id allowed (what a decode loop holds at some step); or ``img=`` [B, C, H, W]
+        instead, which is encoded first, as ``to_latent`` does.  ``text``: a list of prompts or a context tensor [B, L, D].
+        ``layers``: the layer indices to average over (None: all).  ``context_lens`` / ``mask_padding``, ``context_segments`` +
+        ``token_segments`` and ``context_weights``: as in ``tokens2logits`` / ``generate`` -- the maps are those of the very
+        softmax these select, and a context row that takes no part (padding, a denied segment, weight 0) is exactly 0.
+
+        -> f32 [B, L, g, g] on the pipeline's device: map [b, r] is where row r of image b's context is looked at -- the mean over
+        the chosen layers and over the heads of the cross-attention probabilities, so over r a token's values sum to 1.  With
+        ``return_logits`` (maps, logits [B, N, n_embed]), the logits being ``tokens2logits``' on the same arguments, bit for bit.
+        One eager forward: nothing is captured, and a later call of anything runs what it ran before."""
+        if (ids is None) == (img is None):
+            raise ValueError("attention_maps: give exactly one of ids and img")
+        if text is None:
+            raise ValueError("attention_maps: the maps are those of the cross-attention: a text condition is required")
+        if img is not None:
+            _, ids, _ = self.to_latent(img)
+        B = ids.shape[0]
+        ids = ids.reshape(B, self.num_tokens)
+        if isinstance(text, torch.Tensor):
+            context = text
+        elif mask_padding and context_lens is None:
+            context, context_lens = self.text_model(list(text), return_lens=True)
+        else:
+            context = self.text_model(list(text))
+        depth = len(self.transformer.layers)
+        chosen = list(range(depth)) if layers is None else [int(l) for l in layers]
+        if not chosen or len(set(chosen)) != len(chosen) or min(chosen) < 0 or max(chosen) >= depth:
+            raise ValueError(f"attention_maps: layers {layers!r} must be distinct indices in [0, {depth})")
+        lens = self._lens(context_lens, context, B)
+        segments = self._segments(context_segments, token_segments, context, lens, B, context_weights)
+        kw = _seg_kw(segments)
+        if context_weights is not None:
+            lens = None                                           # (the neutral segments carry them)
+        g = self.image_size // self.patch_size
+        if self._on_cpu():
+            logits, maps = self.transformer(self.ids2tokens(ids), context, lens, maps_layers=chosen, **kw)
+        else:
+            eng = self.engine()
+            token = self.ids2tokens(ids.to(eng.device))
+            logits, maps = eng.forward_maps(token, context.to(eng.device), chosen, context_lens=lens, **kw)
+        maps = maps.transpose(1, 2).reshape(B, context.shape[1], g, g).contiguous()
+        return (maps, logits) if return_logits else maps
+
+    @torch.no_grad()
+    def phrase_mask(self, img, text, phrase, threshold=0.5, layers=None, grow=0):
+        """An edit mask from a PHRASE of the prompt (extension): the tokens of ``img`` that look at the phrase.
+
+        ``text``: the prompts, ``phrase``: one phrase for all or one per prompt, each occurring exactly once in its prompt
+        (``T5TextEmbedder.phrase_rows``; other text towers raise NotImplementedError).  The rule, which is the contract:
+            score[b, t] = the sum over the phrase's context rows of ``attention_maps(img=img, ...)``, run under the non-pad lengths
+                          as ``mask_padding=True`` does
+            mask        = score >= threshold * max_t score[b],   0 < threshold <= 1
+        then dilated ``grow`` times by a 3 x 3 maximum.  The default threshold 0.5 is a default, not a measured optimum: look at
+        the maps and choose.  -> bool [B, g, g] on the pipeline's device: what ``edit(token_mask=)`` takes."""
+        if not (isinstance(threshold, (int, float)) and 0 < threshold <= 1):
+            raise ValueError(f"phrase_mask: threshold {threshold!r} must be in (0, 1]")
+        if not (isinstance(grow, int) and grow >= 0):
+            raise ValueError(f"phrase_mask: grow {grow!r} must be a non-negative integer")
+        if not hasattr(self.text_model, "phrase_rows"):
+            raise NotImplementedError(f"{type(self.text_model).__name__} serves no phrase rows (phrase_rows): T5TextEmbedder does")
+        prompts = [text] * img.shape[0] if isinstance(text, str) else list(text)
+        if len(prompts) != img.shape[0]:
+            raise ValueError(f"phrase_mask: {len(prompts)} prompts for a batch of {img.shape[0]}")
+        context, lens, rows = self.text_model.phrase_rows(prompts, phrase)
+        maps = self.attention_maps(img=img, text=context, layers=layers, context_lens=lens)      # [B, L, g, g]
+        score = (maps * rows.to(maps.device)[:, :, None, None].to(maps.dtype)).sum(1)             # [B, g, g]
+        mask = score >= threshold * score.amax(dim=(1, 2), keepdim=True)
+        for _ in range(grow):
+            mask = torch.nn.functional.max_pool2d(mask[:, None].float(), 3, stride=1, padding=1)[:, 0] > 0
+        return mask
+
+    @torch.no_grad()
     def ids2tokens(self, ids):
         """lookup in cat(RAW codebook, mask_token) (generate.py:148-157)."""
         table = torch.cat((self.vqgan.quantize.embedding.weight.data.float(), self.mask_token.data.float())).contiguous()

@@ -60,8 +60,11 @@ class CrossAttention(nn.Module):
         return self.run(x, context, residual=None, context_lens=context_lens, context_segments=context_segments,
                         token_segments=token_segments, context_weights=context_weights)
 
-    def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
+    def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
+            want_maps=False):
         """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x.
+        want_maps (extension, attention maps): -> (that, maps) with maps f32 [B, N, L], the mean over the heads
+        of this call's softmax probabilities -- exactly 0 where a row takes no part; it needs a context.
         context_lens (extension; None = the reference's behaviour, no mask): one length per image -- image b attends to rows
         [0, context_lens[b]) of its context only; the rows beyond never reach the result, NaN included.
         context_segments [B, L] + token_segments [B, N] (extension, regional prompts; never beside context_lens): row k of image
@@ -92,7 +95,11 @@ class CrossAttention(nn.Module):
                                                None if segments is None else segments[0], None if segments is None else segments[1],
                                                context_lens)
             segments, context_lens = (cs, ts), None               # (without segment arrays: the neutral ones, which carry the lengths)
+        if want_maps and context is None:
+            raise ValueError("want_maps: the maps are those of a cross-attention: a context is required")
         if not x.is_cuda:
+            if want_maps:
+                return self._run_cpu(x, context, residual, context_lens, segments, weights, want_maps=True)
             return self._run_cpu(x, context, residual, context_lens, segments, weights)
         B, N, D = x.shape
         dtype = x.dtype
@@ -113,18 +120,21 @@ class CrossAttention(nn.Module):
             n_kv = L
         kv_lens = None if context_lens is None else torch.tensor(context_lens, dtype=torch.int32, device=x.device)
         if segments is not None:
-            o = ops.attention(q, k, vt, n_kv, use_exp2=fast, key_segments=torch.from_numpy(segments[0]).to(x.device),
-                              query_segments=torch.from_numpy(segments[1].view(np.int32)).to(x.device),
-                              key_weights=None if weights is None else torch.from_numpy(weights).to(x.device))
+            form = dict(key_segments=torch.from_numpy(segments[0]).to(x.device),
+                        query_segments=torch.from_numpy(segments[1].view(np.int32)).to(x.device),
+                        key_weights=None if weights is None else torch.from_numpy(weights).to(x.device))
         else:
-            o = ops.attention(q, k, vt, n_kv, use_exp2=fast, kv_lens=kv_lens)
+            form = dict(kv_lens=kv_lens)
+        o = ops.attention(q, k, vt, n_kv, use_exp2=fast, **form)
         res = residual.reshape(B * N, D) if residual is not None else None
         out_dtype = torch.float32 if residual is not None else dtype
         out = ops.gemm(o, pk["wo"], bias=pk["bo"], residual=res, out_dtype=out_dtype)
+        if want_maps:
+            return out.reshape(B, N, D), ops.attention_maps(q, k, n_kv, use_exp2=fast, **form)
         return out.reshape(B, N, D)
 
 
-    def _run_cpu(self, x, context, residual, context_lens=None, segments=None, weights=None):
+    def _run_cpu(self, x, context, residual, context_lens=None, segments=None, weights=None, want_maps=False):
         """Parameters on the CPU: the same operator in plain torch (reference modules/attention.py:43-59; BASELINE config 1
         runs the model there).  q is scaled BEFORE the product (:52), no mask, softmax over the keys, head split 'b n (h d)'.
         context_lens (a checked list, or None): scores of the keys at or beyond an image's length become -inf (whatever they
@@ -132,9 +142,11 @@ class CrossAttention(nn.Module):
         segments (checked numpy arrays (uint8 [B, L], uint32 [B, N]), or None): the same per QUERY -- scores of the rows a token
         does not attend to become -inf, and the V rows of padding (segment 255) are zeroed.
         weights (checked numpy float32 [B, L] beside segments, or None): log w is added to the scores of the rows with w > 0; a row
-        with w == 0 is padding."""
+        with w == 0 is padding.
+        want_maps: -> (the result, p.mean(heads) f32 [B, N, L]): the probabilities of this very softmax, 0 where a row takes no part."""
         B, N, _ = x.shape
         c = x if context is None else context
+        L = c.shape[1]
         if context_lens is not None and len(set(context_lens)) == 1:
             c, context_lens = c[:, :context_lens[0]], None       # one length for the batch (B = 1 always): cut the padding off
         h, d = self.heads, self.dim_head
@@ -159,7 +171,10 @@ class CrossAttention(nn.Module):
         p = torch.softmax(s, dim=-1)
         o = (p @ v).permute(0, 2, 1, 3).reshape(B, N, h * d)
         out = F.linear(o, self.to_out[0].weight, self.to_out[0].bias)
-        return out if residual is None else out + residual
+        out = out if residual is None else out + residual
+        if want_maps:
+            return out, F.pad(p.mean(1).float(), (0, L - p.shape[-1]))       # (a context cut to one common length: zeros behind it)
+        return out
 
 
 def round_up64(v):

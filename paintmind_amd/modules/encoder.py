@@ -98,6 +98,54 @@ class T5TextEmbedder(nn.Module):
         context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
         return context, lens, weights
 
+    @torch.no_grad()
+    def phrase_rows(self, text, phrases):
+        """Which context rows are a phrase's tokens (``Pipeline.phrase_mask``).  Prompt b is split at the SINGLE
+        occurrence of phrases[b] into [before, phrase, after]; the three fragments are tokenised one by one WITHOUT special tokens,
+        exactly as ``_forward_weighted`` tokenises its fragments, the ids are concatenated, closed with the end-of-sequence id and
+        truncated or padded to max_length, and the context is ONE tower call on them.
+        -> (context (B, max_length, d_model), lens int32 [B] on the host, rows bool [B, max_length] on the host: the phrase's tokens).
+        A phrase that is empty, absent, occurs twice or is cut off by max_length raises ValueError naming the prompt."""
+        text = [text] if isinstance(text, str) else list(text)
+        phrases = [phrases] * len(text) if isinstance(phrases, str) else list(phrases)
+        if len(phrases) != len(text):
+            raise ValueError(f"phrase_rows: {len(phrases)} phrases for {len(text)} prompts")
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        eos = 1 if eos is None else int(eos)
+        pad = _pad_id(self.tokenizer)
+        B, L = len(text), self.max_length
+        ids = torch.full((B, L), pad, dtype=torch.long)
+        rows = torch.zeros(B, L, dtype=torch.bool)
+        lens = torch.zeros(B, dtype=torch.int32)
+
+        def pieces(frag):
+            if not frag:
+                return []
+            piece = self.tokenizer(frag, add_special_tokens=False)["input_ids"]
+            return [int(t) for t in (piece.reshape(-1).tolist() if hasattr(piece, "reshape") else piece)]
+
+        for b, (prompt, phrase) in enumerate(zip(text, phrases)):
+            if not isinstance(phrase, str) or not phrase.strip():
+                raise ValueError(f"phrase_rows: prompt {b} ({prompt!r}): the phrase is empty")
+            count = prompt.count(phrase)
+            if count == 0:
+                raise ValueError(f"phrase_rows: prompt {b} ({prompt!r}): the phrase {phrase!r} does not occur in it")
+            if count > 1:
+                raise ValueError(f"phrase_rows: prompt {b} ({prompt!r}): the phrase {phrase!r} occurs {count} times, not once")
+            before, after = prompt.split(phrase)
+            head, mid, tail = pieces(before), pieces(phrase), pieces(after)
+            if not mid:
+                raise ValueError(f"phrase_rows: prompt {b} ({prompt!r}): the phrase {phrase!r} has no tokens")
+            if len(head) + len(mid) > L - 1:
+                raise ValueError(f"phrase_rows: prompt {b} ({prompt!r}): the phrase {phrase!r} is cut off by max_length={L} "
+                                 f"(its tokens end at row {len(head) + len(mid)}, the last row is the end-of-sequence token's)")
+            row = (head + mid + tail)[:L - 1] + [eos]
+            ids[b, :len(row)] = torch.tensor(row, dtype=torch.long)
+            rows[b, len(head):len(head) + len(mid)] = True
+            lens[b] = len(row)
+        context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
+        return context, lens, rows
+
     def encode(self, text):
         return self(text)
 
@@ -150,6 +198,9 @@ class CLIPTextEmbedder(nn.Module):
         tokens = self.tokenize(text)
         context = self.encode_with_transformer(tokens.to(_module_device(self.model)))
         return (context, _count_tokens(tokens != 0)) if return_lens else context
+
+    def phrase_rows(self, text, phrases):
+        raise NotImplementedError("CLIPTextEmbedder serves no phrase rows (phrase_rows): T5TextEmbedder does")
 
     def encode_with_transformer(self, tokens):
         m = self.model
@@ -207,3 +258,6 @@ class SyntheticTextEmbedder(nn.Module):
             g = torch.Generator().manual_seed(self.seed * 1000003 + self.base_index + i)
             rows.append(torch.randn(self.max_length, self.context_dim, generator=g))
         return torch.stack(rows).to(self._anchor.device)
+
+    def phrase_rows(self, text, phrases):
+        raise NotImplementedError("SyntheticTextEmbedder has no tokenizer and serves no phrase rows (phrase_rows): T5TextEmbedder does")

@@ -547,6 +547,60 @@ def attention_pick(q, k, vt, n_kv, pick, want, out, use_exp2=False, kv_lens=None
     return out
 
 
+def attention_maps(q, k, n_kv, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None, key_weights=None, out=None,
+                   scale=1.0, accumulate=False):
+    """The head-mean probabilities of the softmax ``attention`` defines on the same arguments (pmhip_attention_maps; DESIGN.md
+    section 4y): q [B,H,Nq,dh], k [B,H,Nkp,dh] -> f32 [B, Nq, n_kv] with out[b, q, j] = scale / H * sum_h p_h[q, j], added to what
+    `out` holds when `accumulate`.  kv_lens, key_segments + query_segments and key_weights select the form exactly as in
+    ``attention`` (same checks, same neutral arrays for weights alone, the weights through ``key_bias``).  A key that takes part in
+    no softmax of a query is exactly 0 (left as it is under `accumulate`).  P stays f32 in bf16 mode.  out (None: a new tensor;
+    required under `accumulate`): f32 [B, Nq, n_kv] on the operands' device with unit stride in the last dimension, stride(1) >= n_kv
+    the leading dimension and stride(0) == Nq * stride(1) (a window of a wider buffer will do).  -> out"""
+    dev = _dev(q, k, kv_lens, key_segments, query_segments, key_weights)
+    lib = _lib.load()
+    B, H, Nq, dh = q.shape
+    nkp = k.shape[2]
+    if k.dtype != q.dtype or k.shape[0] != B or k.shape[1] != H or k.shape[3] != dh or nkp < n_kv:
+        raise ValueError(f"k must be a {q.dtype} [{B}, {H}, >= {n_kv}, {dh}] tensor, got {k.dtype} {tuple(k.shape)}")
+    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
+        raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
+    if (key_segments is None) != (query_segments is None):
+        raise ValueError("key_segments and query_segments come together")
+    if key_segments is not None:
+        if kv_lens is not None:
+            raise ValueError("key_segments / query_segments and kv_lens exclude each other (mark padding keys with segment 255)")
+        if key_segments.dtype != torch.uint8 or tuple(key_segments.shape) != (B, n_kv) or not key_segments.is_contiguous():
+            raise ValueError(f"key_segments must be a contiguous uint8 tensor of shape ({B}, {n_kv}), got {key_segments.dtype} "
+                             f"{tuple(key_segments.shape)}")
+        if query_segments.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(query_segments.shape) != (B, Nq) or \
+                not query_segments.is_contiguous():
+            raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
+                             f"{tuple(query_segments.shape)}")
+    bias = None
+    if key_weights is not None:
+        if kv_lens is not None:
+            raise ValueError("key_weights and kv_lens exclude each other (a weight of 0 makes a key padding)")
+        if key_weights.dtype != torch.float32 or tuple(key_weights.shape) != (B, n_kv):
+            raise ValueError(f"key_weights must be a float32 tensor of shape ({B}, {n_kv}), got {key_weights.dtype} {tuple(key_weights.shape)}")
+        bias = key_bias(key_weights, use_exp2)
+        if key_segments is None:
+            key_segments = torch.zeros(B, n_kv, dtype=torch.uint8, device=dev)
+            query_segments = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate adds to `out`: pass the tensor to add to")
+        out = torch.empty(B, Nq, n_kv, device=dev, dtype=torch.float32)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.float32 and
+            tuple(out.shape) == (B, Nq, n_kv) and out.stride(2) == 1 and out.stride(1) >= n_kv and out.stride(0) == Nq * out.stride(1)):
+        raise ValueError(f"out must be a float32 [{B}, {Nq}, {n_kv}] tensor on the operands' device with unit stride in the last dimension "
+                         f"and stride(0) == {Nq} * stride(1)")
+    with torch.cuda.device(dev):
+        check(lib.pmhip_attention_maps(pm_dtype(q.dtype), _p(q), _p(k), _p(out), out.stride(1), B, H, dh, Nq, n_kv, nkp, int(bool(use_exp2)),
+                                       _p(kv_lens), _p(key_segments), _p(query_segments), _p(bias), float(scale), int(bool(accumulate)),
+                                       stream_ptr(dev)), "pmhip_attention_maps")
+    return out
+
+
 def layernorm(x, gamma, beta, eps=1e-5, out_dtype=torch.float32):
     dev = _dev(x, gamma, beta)
     lib = _lib.load()

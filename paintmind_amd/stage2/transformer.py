@@ -21,8 +21,9 @@ class Layer(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ffnet = SwiGLUFFNFused(in_features=dim, hidden_features=mlp_dim)
 
-    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
+    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, want_maps=False):
         """self-attn, cross-attn (a 2nd self-attn when context is None), SwiGLU (transformer.py:44-49).
+        want_maps: -> (x, maps), maps f32 [B, N, L] the head-mean probabilities of the cross-attention (modules/attention.py).
         context_lens: per-image context lengths for the cross-attention only (modules/attention.py).
         context_segments / token_segments: regional prompts, for the cross-attention only (modules/attention.py).
         context_weights: prompt weights, for the cross-attention only (modules/attention.py)."""
@@ -30,12 +31,17 @@ class Layer(nn.Module):
         T = compute_dtype_of(self)
         x = x.contiguous()
         x = self.attn1.run(_norm(x.reshape(B * N, D), self.norm1, T).reshape(B, N, D), None, residual=x)
+        kw = dict(want_maps=True) if want_maps else {}
         x = self.attn2.run(_norm(x.reshape(B * N, D), self.norm2, T).reshape(B, N, D), context, residual=x,
                            context_lens=context_lens if context is not None else None,
                            context_segments=context_segments if context is not None else None,
                            token_segments=token_segments if context is not None else None,
-                           context_weights=context_weights if context is not None else None)
-        return self.ffnet.run(_norm(x.reshape(B * N, D), self.norm3, T).reshape(B, N, D), residual=x)
+                           context_weights=context_weights if context is not None else None, **kw)
+        maps = None
+        if want_maps:
+            x, maps = x
+        x = self.ffnet.run(_norm(x.reshape(B * N, D), self.norm3, T).reshape(B, N, D), residual=x)
+        return (x, maps) if want_maps else x
 
 
 class CondTransformer(nn.Module):
@@ -52,8 +58,27 @@ class CondTransformer(nn.Module):
         self.to_logits = nn.Linear(dim, num_classes)
         _xavier_like_reference(self)
 
-    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
+    def _layers(self, h, maps_layers, *args):
+        """the tower; maps_layers (None, or the checked layer indices): -> (h, the mean of those layers' cross-attention maps)"""
+        if maps_layers is None:
+            for layer in self.layers:
+                h = layer(h, *args)
+            return h
+        maps = None
+        for i, layer in enumerate(self.layers):
+            if i in maps_layers:
+                h, m = layer(h, *args, want_maps=True)
+                maps = m if maps is None else maps + m
+            else:
+                h = layer(h, *args)
+        return h, maps / len(maps_layers)
+
+    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
+                maps_layers=None):
         """operator-level composition of transformer.py:80-93 (Pipeline uses the native engine instead).
+        maps_layers (extension, attention maps; None = the call as without it): distinct layer indices ->
+        (logits, maps), the logits as without it and maps f32 [B, N, L], the mean over those layers of the head-mean probabilities
+        of each layer's cross-attention.  It needs a context.
         context_lens (extension; None = the reference's behaviour): image b's cross-attention sees rows [0, context_lens[b]) of
         its context only.  The context projection still covers every row: it is row-local, so padding stays in the padding.
         context_segments [B, L] / token_segments [B, N] (extension, regional prompts): see ``CrossAttention.run``.
@@ -74,6 +99,12 @@ class CondTransformer(nn.Module):
             context_segments, token_segments, context_weights = ops.host_weights(context_weights, x.shape[0], context.shape[1], x.shape[1],
                                                                                  context_segments, token_segments, context_lens)
             context_lens = None                                    # the neutral segments carry the lengths
+        if maps_layers is not None:
+            maps_layers = [int(l) for l in maps_layers]
+            if context is None:
+                raise ValueError("maps_layers: the maps are those of the cross-attention: a context is required")
+            if not maps_layers or len(set(maps_layers)) != len(maps_layers) or min(maps_layers) < 0 or max(maps_layers) >= len(self.layers):
+                raise ValueError(f"maps_layers {maps_layers!r} must be distinct indices in [0, {len(self.layers)})")
         T = compute_dtype_of(self)
         B, N, E = x.shape
         dim = self.token_proj.out_features
@@ -83,8 +114,9 @@ class CondTransformer(nn.Module):
             h = self.token_proj(x.float()) + self.position_embedding
             if context is not None:
                 context = self.context_proj(context.float())
-            for layer in self.layers:
-                h = layer(h, context, context_lens, context_segments, token_segments, context_weights)
+            h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights)
+            if maps_layers is not None:
+                return self.to_logits(self.norm(h[0])), h[1]
             return self.to_logits(self.norm(h))
         a = ops.convert_pad(x.contiguous().float().reshape(B * N, E), 64, T)
         pos = self.position_embedding.detach()[0].contiguous()
@@ -96,9 +128,11 @@ class CondTransformer(nn.Module):
             if isinstance(self.context_proj, nn.Linear):
                 c = ops.gemm(c, packing.pad_cols(self.context_proj.weight, c.shape[1], T))
             context = c.reshape(B, L, dim)
-        for layer in self.layers:
-            h = layer(h, context, context_lens, context_segments, token_segments, context_weights)
+        h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights)
+        maps = None
+        if maps_layers is not None:
+            h, maps = h
         y = _norm(h.reshape(B * N, dim), self.norm, T)
         logits = ops.gemm(y, packing.cast(self.to_logits.weight, T), bias=self.to_logits.bias.detach().float(),
                           out_dtype=torch.float32)
-        return logits.reshape(B, N, -1)
+        return (logits.reshape(B, N, -1), maps) if maps_layers is not None else logits.reshape(B, N, -1)
