@@ -72,128 +72,26 @@ __device__ __forceinline__ void zero_ragged_v(unsigned char* Vl, int kv0, int Nk
 }
 
 // QF = 16-query tiles per wave (2: 32 queries per wave, 128 per workgroup).
-// the kernel, in its two forms (attention_body.h)
-#define PM_ATTN_KERNEL attention_kernel
-#define PM_ATTN_LENS_PARAM
-#include "attention_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-// the per-image form: Nkv_b = clamp(lens[b], 1, Nkv)
-#define PM_ATTN_KERNEL attention_lens_kernel
-#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens
-#define PM_ATTN_LENS 1
-#include "attention_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_LENS
-// the per-query form: key k takes part in query q's softmax iff key_seg[b,k] < 32 and bit key_seg[b,k] of query_mask[b,q] is set
-#define PM_ATTN_KERNEL attention_seg_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
-#define PM_ATTN_SEG 1
-#include "attention_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-// the picked forms: the per-image and the per-query form again, each with `pick` (device uint8 [B]) and `want` --
-// a workgroup whose image has pick[b] != want returns at once, every other one runs its twin's text
-#define PM_ATTN_KERNEL attention_lens_pick_kernel
-#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_LENS 1
-#define PM_ATTN_PICK 1
-#include "attention_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_LENS
-#define PM_ATTN_KERNEL attention_seg_pick_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_SEG 1
-#include "attention_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_PICK
-// the weighted form: the per-query form plus key_bias (device f32 [B, Nkv]), log(weight) of every key in the
-// kernel's score unit; -inf = the key is padding
-#define PM_ATTN_KERNEL attention_seg_bias_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias
-#define PM_ATTN_SEG 1
-#define PM_ATTN_BIAS 1
-#include "attention_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_BIAS
-// the picked weighted form: the weighted form again with `pick` and `want` -- a workgroup whose image has
-// pick[b] != want returns at once, every other one runs attention_seg_bias_kernel's text
-#define PM_ATTN_KERNEL attention_seg_bias_pick_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_SEG 1
-#define PM_ATTN_BIAS 1
-#define PM_ATTN_PICK 1
-#include "attention_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_BIAS
-#undef PM_ATTN_PICK
+#define PM_ATTN_BODY "attention_body.h"
+#define PM_ATTN_NAME(sfx) attention##sfx##kernel
+#define PM_ATTN_INSTANTIATE
+#include "attention_forms.h"
 
 }  // namespace
 
-// fp32, dim_head = 64 leg of the attention entry points (attention_dh.hip): arguments already validated there;
-// lens = device int32 [B], the per-image key counts, or NULL; seg = the per-query key sets, or NULL (never both)
-void pm_attention_f32(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                      int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s) {
+// fp32, dim_head = 64 leg of attention_any (attention_dh.hip): arguments already validated there
+void pm_attention_f32(const PmAttnArgs& a) {
     constexpr int QF = 2;
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    if (seg) {
-        auto k = use_exp2 ? attention_seg_kernel<true, QF> : attention_seg_kernel<false, QF>;
-        hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
-                           Nq, Nkv, Nkv_pad, nqb, seg->key_seg, seg->query_mask);
-        return;
-    }
-    auto launch = [&](auto plain, auto per_image) {
-        pm_launch_lens(plain, per_image, dim3(nqb * B * heads), dim3(THREADS), s, lens, (const float*)Q, (const float*)K, (const float*)Vt,
-                       (float*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb);
-    };
-    if (use_exp2) launch(attention_kernel<true, QF>, attention_lens_kernel<true, QF>);
-    else launch(attention_kernel<false, QF>, attention_lens_kernel<false, QF>);
+    const int nqb = ceil_div(a.Nq, 4 * QF * 16);
+    const dim3 grid(nqb * a.B * a.heads), block(THREADS);
+#define PM_ATTN_LAUNCH(form, sfx, ...)                                                                                                  \
+    case PM_FORM_##form: {                                                                                                              \
+        auto k = a.use_exp2 ? PM_ATTN_NAME(sfx)<true, QF> : PM_ATTN_NAME(sfx)<false, QF>;                                                \
+        hipLaunchKernelGGL(k, grid, block, 0, a.stream, (const float*)a.Q, (const float*)a.K, (const float*)a.Vt, (float*)a.out, a.ldo, \
+                           a.heads, a.Nq, a.Nkv, a.Nkv_pad, nqb, ##__VA_ARGS__);                                                        \
+    } break;
+    switch (pm_attn_form(a)) { PM_ATTN_FORMS(PM_ATTN_LAUNCH) }
+#undef PM_ATTN_LAUNCH
 }
-
-// The weighted form, a launcher of its own so that the one above keeps its text: the grid and the workgroup of the
-// segmented twin.
-void pm_attention_f32_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                               int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s) {
-    constexpr int QF = 2;
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    auto k = use_exp2 ? attention_seg_bias_kernel<true, QF> : attention_seg_bias_kernel<false, QF>;
-    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
-                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias);
-}
-
-// The picked forms, a launcher of their own so that the one above keeps its text: exactly one of lens / seg is given,
-// the grid and the workgroup are those of the twin.
-void pm_attention_f32_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                           int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s) {
-    constexpr int QF = 2;
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    if (seg) {
-        auto k = use_exp2 ? attention_seg_pick_kernel<true, QF> : attention_seg_pick_kernel<false, QF>;
-        hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
-                           Nq, Nkv, Nkv_pad, nqb, seg->key_seg, seg->query_mask, pk.pick, pk.want);
-        return;
-    }
-    auto k = use_exp2 ? attention_lens_pick_kernel<true, QF> : attention_lens_pick_kernel<false, QF>;
-    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
-                       Nq, Nkv, Nkv_pad, nqb, lens, pk.pick, pk.want);
-}
-
-// The picked weighted form, a launcher of its own again: the grid and the workgroup of the weighted twin.
-void pm_attention_f32_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                                    int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
-                                    hipStream_t s) {
-    constexpr int QF = 2;
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    auto k = use_exp2 ? attention_seg_bias_pick_kernel<true, QF> : attention_seg_bias_pick_kernel<false, QF>;
-    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const float*)Q, (const float*)K, (const float*)Vt, (float*)out, ldo, heads,
-                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias, pk.pick, pk.want);
-}
+#undef PM_ATTN_BODY
+#undef PM_ATTN_NAME

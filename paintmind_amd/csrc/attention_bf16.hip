@@ -110,191 +110,56 @@ __device__ __forceinline__ f32x4_t mma(const v4u_t& rows, const v4u_t& cols, con
 // wave and per CU -- needs 13 % MORE cycles, 2.45e6 against 2.16e6 per launch, MFMA busy 0.49 against 0.55: the 8-wave barrier
 // per tile costs more than the DMA saves; two independent 4-wave workgroups cover each other's barrier waits.  The patch is
 // tools/ab_variants/attn_wv8.patch, the numbers profiles/r05_a_attention_gen4_ab.txt (5).)
-// the kernel, in its two forms (attention_bf16_body.h)
-#define PM_ATTN_KERNEL attention_bf16_kernel
-#define PM_ATTN_LENS_PARAM
-#include "attention_bf16_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-// the per-image form: Nkv_b = clamp(lens[b], 1, Nkv)
-#define PM_ATTN_KERNEL attention_bf16_lens_kernel
-#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens
-#define PM_ATTN_LENS 1
-#include "attention_bf16_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_LENS
-// the per-query form: key k takes part in query q's softmax iff key_seg[b,k] < 32 and bit key_seg[b,k] of query_mask[b,q] is set
-#define PM_ATTN_KERNEL attention_bf16_seg_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
-#define PM_ATTN_SEG 1
-#include "attention_bf16_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-// the picked forms: the per-image and the per-query form again, each with `pick` (device uint8 [B]) and `want` --
-// a workgroup whose image has pick[b] != want returns at once, every other one runs its twin's text
-#define PM_ATTN_KERNEL attention_bf16_lens_pick_kernel
-#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_LENS 1
-#define PM_ATTN_PICK 1
-#include "attention_bf16_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_LENS
-#define PM_ATTN_KERNEL attention_bf16_seg_pick_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_SEG 1
-#include "attention_bf16_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_PICK
-// the weighted form: the per-query form plus key_bias (device f32 [B, Nkv]), log(weight) of every key in the
-// kernel's score unit, added to an allowed key's score before the maximum is taken; -inf = the key is padding
-#define PM_ATTN_KERNEL attention_bf16_seg_bias_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias
-#define PM_ATTN_SEG 1
-#define PM_ATTN_BIAS 1
-#include "attention_bf16_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_BIAS
-// the picked weighted form: the weighted form again with `pick` and `want` -- a workgroup whose image has
-// pick[b] != want returns at once, every other one runs attention_bf16_seg_bias_kernel's text
-#define PM_ATTN_KERNEL attention_bf16_seg_bias_pick_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_SEG 1
-#define PM_ATTN_BIAS 1
-#define PM_ATTN_PICK 1
-#include "attention_bf16_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_BIAS
-#undef PM_ATTN_PICK
+#define PM_ATTN_BODY "attention_bf16_body.h"
+#define PM_ATTN_NAME(sfx) attention_bf16##sfx##kernel
+#define PM_ATTN_INSTANTIATE
+#include "attention_forms.h"
 
 #undef DSRX
 #undef LGKM4
 #undef LGKM2
 
+// The forms with a key set per query exist with 128 or 64 queries per workgroup only (QF <= 2): the 256-query form with the masks
+// does not fit in 256 VGPRs without more scratch than its twins, so it is not built.
 template <int QF>
-static void launch_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
-                      int use_exp2, const int* lens, hipStream_t s) {
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    auto launch = [&](auto plain, auto per_image) {
-        pm_launch_lens(plain, per_image, dim3(nqb * B * heads), dim3(THREADS), s, lens, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt,
-                       (bf16_t*)out, ldo, heads, Nq, Nkv, Nkv_pad, nqb);
-    };
-    if (use_exp2) launch(attention_bf16_kernel<true, QF>, attention_bf16_lens_kernel<true, QF>);
-    else launch(attention_bf16_kernel<false, QF>, attention_bf16_lens_kernel<false, QF>);
+static void launch_qf(const PmAttnArgs& a) {
+    const int nqb = ceil_div(a.Nq, 4 * QF * 16);
+    const dim3 grid(nqb * a.B * a.heads), block(THREADS);
+#define PM_ATTN_LAUNCH(form, sfx, ...)                                                                                                     \
+    case PM_FORM_##form: {                                                                                                                 \
+        auto k = a.use_exp2 ? PM_ATTN_NAME(sfx)<true, QF> : PM_ATTN_NAME(sfx)<false, QF>;                                                   \
+        hipLaunchKernelGGL(k, grid, block, 0, a.stream, (const bf16_t*)a.Q, (const bf16_t*)a.K, (const bf16_t*)a.Vt, (bf16_t*)a.out, a.ldo, \
+                           a.heads, a.Nq, a.Nkv, a.Nkv_pad, nqb, ##__VA_ARGS__);                                                           \
+    } break;
+    const PmAttnForm f = pm_attn_form(a);
+    if (!a.key_seg) switch (f) { PM_ATTN_FORMS_IMAGE(PM_ATTN_LAUNCH) default: break; }
+    else if constexpr (QF <= 2) switch (f) { PM_ATTN_FORMS_QUERY(PM_ATTN_LAUNCH) default: break; }
+#undef PM_ATTN_LAUNCH
 }
 
-template <int QF>
-static void launch_seg_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
-                          int use_exp2, const PmAttnSeg& seg, hipStream_t s) {
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    auto k = use_exp2 ? attention_bf16_seg_kernel<true, QF> : attention_bf16_seg_kernel<false, QF>;
-    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
-                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask);
-}
-
-// the weighted form: the geometry of the segmented twin
-template <int QF>
-static void launch_seg_bias_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
-                               int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s) {
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    auto k = use_exp2 ? attention_bf16_seg_bias_kernel<true, QF> : attention_bf16_seg_bias_kernel<false, QF>;
-    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
-                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias);
-}
-
-// the picked weighted form: the geometry of the weighted twin
-template <int QF>
-static void launch_seg_bias_pick_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                                    int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk, hipStream_t s) {
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    auto k = use_exp2 ? attention_bf16_seg_bias_pick_kernel<true, QF> : attention_bf16_seg_bias_pick_kernel<false, QF>;
-    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
-                       Nq, Nkv, Nkv_pad, nqb, seg.key_seg, seg.query_mask, key_bias, pk.pick, pk.want);
-}
-
-// the picked forms: exactly one of lens / seg, the geometry of the twin
-template <int QF>
-static void launch_pick_qf(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
-                           int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s) {
-    const int nqb = ceil_div(Nq, 4 * QF * 16);
-    if constexpr (QF <= 2) {
-        if (seg) {
-            auto k = use_exp2 ? attention_bf16_seg_pick_kernel<true, QF> : attention_bf16_seg_pick_kernel<false, QF>;
-            hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo,
-                               heads, Nq, Nkv, Nkv_pad, nqb, seg->key_seg, seg->query_mask, pk.pick, pk.want);
-            return;
-        }
-    }
-    auto k = use_exp2 ? attention_bf16_lens_pick_kernel<true, QF> : attention_bf16_lens_pick_kernel<false, QF>;
-    hipLaunchKernelGGL(k, dim3(nqb * B * heads), dim3(THREADS), 0, s, (const bf16_t*)Q, (const bf16_t*)K, (const bf16_t*)Vt, (bf16_t*)out, ldo, heads,
-                       Nq, Nkv, Nkv_pad, nqb, lens, pk.pick, pk.want);
+// The largest workgroup (64 * QF queries, QF <= max_qf) that still gives the chip two workgroups per CU (256 CUs on this part).  B,
+// heads and Nq decide, never lens, the key sets, the biases or pick: the forms are bit-identical per 16-query tile, so an image's
+// result depends neither on the choice nor on which images a launch serves.
+static int queries_qf(int B, int heads, int Nq, int max_qf) {
+#ifdef PM_ATTN_FORCE_QF              // tools/hwtests: one workgroup size for every launch (they launch the plain form only)
+    return PM_ATTN_FORCE_QF < max_qf ? PM_ATTN_FORCE_QF : max_qf;
+#else
+    constexpr int kFill = 512;
+    for (int qf = max_qf; qf > 1; qf /= 2)
+        if ((long long)B * heads * ceil_div(Nq, 64 * qf) >= kFill) return qf;
+    return 1;
+#endif
 }
 
 }  // namespace
 
-// bf16, dim_head = 64 leg of the attention entry points (attention_dh.hip): arguments already validated there; lens = device
-// int32 [B], the per-image key counts, or NULL.  The largest workgroup that still gives the chip two workgroups per CU (256 CUs on
-// this part: 512) is taken; the result of an image does not depend on the choice, and the choice looks at B, heads and Nq only --
-// never at `lens`.
-void pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                       int Nkv_pad, int use_exp2, const int* lens, hipStream_t s) {
-#ifdef PM_ATTN_FORCE_QF
-    constexpr int kFill = 0;
-    const int force = PM_ATTN_FORCE_QF;
-#else
-    constexpr int kFill = 512;
-    const int force = 0;
-#endif
-    const long long bh = (long long)B * heads;
-    if (force == 4 || (!force && bh * ceil_div(Nq, 256) >= kFill)) launch_qf<4>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
-    else if (force == 2 || (!force && bh * ceil_div(Nq, 128) >= kFill)) launch_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
-    else launch_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
+// bf16, dim_head = 64 leg of attention_any (attention_dh.hip): arguments already validated there
+void pm_attention_bf16(const PmAttnArgs& a) {
+    switch (queries_qf(a.B, a.heads, a.Nq, a.key_seg ? 2 : 4)) {
+        case 4: launch_qf<4>(a); break;
+        case 2: launch_qf<2>(a); break;
+        default: launch_qf<1>(a);
+    }
 }
-
-// The per-query form, a launcher of its own so that the one above keeps its signature (tools/hwtests build this file
-// under several names and call it through one function-pointer type).  128 or 64 queries per workgroup only: the 256-query form
-// with the masks does not fit in 256 VGPRs without more scratch than its twins, so it is not built.  Same rule otherwise -- B,
-// heads and Nq decide, never the masks -- and the forms are bit-identical per 16-query tile.
-void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                           int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s) {
-    if ((long long)B * heads * ceil_div(Nq, 128) >= 512) launch_seg_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
-    else launch_seg_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, s);
-}
-
-// The weighted form: the rule of pm_attention_bf16_seg, word for word -- B, heads and Nq decide between 128 and 64
-// queries per workgroup, never the arrays --, and the forms are bit-identical per 16-query tile.
-void pm_attention_bf16_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                                int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s) {
-    if ((long long)B * heads * ceil_div(Nq, 128) >= 512)
-        launch_seg_bias_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, s);
-    else launch_seg_bias_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, s);
-}
-
-// The picked forms: the rule of the twin, from B, heads and Nq only -- never from `pick` --, so an image's bits do not
-// depend on which images a launch serves.  lens: 256 / 128 / 64 queries per workgroup as pm_attention_bf16 (PM_ATTN_FORCE_QF builds
-// do not reach this launcher); seg: 128 / 64 as pm_attention_bf16_seg.
-void pm_attention_bf16_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                            int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s) {
-    const long long bh = (long long)B * heads;
-    if (!seg && bh * ceil_div(Nq, 256) >= 512) launch_pick_qf<4>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
-    else if (bh * ceil_div(Nq, 128) >= 512) launch_pick_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
-    else launch_pick_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, s);
-}
-
-// The picked weighted form: the rule of pm_attention_bf16_seg_bias, word for word -- B, heads and Nq decide between
-// 128 and 64 queries per workgroup, never `pick` or the arrays --, so a served image's bits are those of the weighted launch.
-void pm_attention_bf16_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                                     int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
-                                     hipStream_t s) {
-    if ((long long)B * heads * ceil_div(Nq, 128) >= 512)
-        launch_seg_bias_pick_qf<2>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, pk, s);
-    else launch_seg_bias_pick_qf<1>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, seg, key_bias, pk, s);
-}
+#undef PM_ATTN_BODY
+#undef PM_ATTN_NAME

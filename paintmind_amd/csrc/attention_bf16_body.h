@@ -1,33 +1,29 @@
-// The bf16 attention kernel of attention_bf16.hip, which includes this file SEVEN TIMES (no include guard on purpose):
-//   PM_ATTN_KERNEL = attention_bf16_kernel,      PM_ATTN_LENS_PARAM empty          one key count for the launch (Nkv)
-//   PM_ATTN_KERNEL = attention_bf16_lens_kernel, PM_ATTN_LENS_PARAM = ", lens"     PM_ATTN_LENS defined: the key count is per IMAGE --
-//       lens[b] (device int32 [B]), read once per workgroup into a scalar and clamped to [1, Nkv]; Nkv stays the launch-wide
-//       upper bound and Nkv_pad the layout, so every base and row stride is unchanged and every read stays inside Nkv_pad.
-//       Everything below the clamp -- tile counts, the ragged-tile K mask, the V^T zeroing, steady_end / all_steady -- uses the
-//       per-image value, so image b computes what it computes alone with Nkv = lens[b].
-//   PM_ATTN_KERNEL = attention_bf16_seg_kernel,  PM_ATTN_LENS_PARAM = ", key_seg, query_mask"   PM_ATTN_SEG defined: the key SET is per
-//       QUERY.  key_seg[b, k] (device uint8 [B, Nkv]) is the segment 0..31 of a key or 255 for padding,
-//       query_mask[b, q] (device uint32 [B, Nq]) the segments a query attends to.  Every half-tile takes the exact path: the mask
-//       sits where the ragged-tile mask sets scores to -inf, the V^T columns of padding keys are zeroed in every tile, and the
-//       running max of a query that has not met an allowed key yet stays "none" (negm 0, l 0) instead of -inf.
-//   PM_ATTN_KERNEL = attention_bf16_lens_pick_kernel / attention_bf16_seg_pick_kernel: the second and the third form again with
-//       PM_ATTN_PICK defined and two more parameters ", pick, want" (DESIGN.md section 4v).  pick (device uint8 [B]) names the kind
-//       of every image; a workgroup whose image has pick[b] != want returns at once and leaves the image's output rows as they
-//       are, every other workgroup runs its twin's text.  Two launches, one per kind, fill one output buffer.
-//   PM_ATTN_KERNEL = attention_bf16_seg_bias_kernel: the third form again with PM_ATTN_BIAS defined and one more parameter
-//       ", key_bias" (DESIGN.md section 4w).  key_bias[b, k] (device f32 [B, Nkv]) is log(weight) of a key in the kernel's score
-//       unit -- octaves when EXP2, nats otherwise --, added to the key's score in every half-tile BEFORE the maximum is taken, so
-//       the running max is a max over s + bias; -inf means excluded and makes the key padding (255) in seg_of, for the scores and
-//       for the V^T zeroing alike.
-//   PM_ATTN_KERNEL = attention_bf16_seg_bias_pick_kernel: the weighted form again with PM_ATTN_PICK defined and ", pick, want" behind
-//       key_bias: the early return of the picked forms, then attention_bf16_seg_bias_kernel's text.
-// A compile-time variant by TEXT, not by a template parameter or an inlined body function: the first form is then the kernel the
-// library had before the second existed, token for token -- same symbol, same instruction stream, same registers (a shared
-// __device__ body, even force-inlined, was measured to move the schedule of every instantiation).
+// The bf16 attention kernel of attention_bf16.hip, included once per form by attention_forms.h (no include guard on purpose; the
+// forms, their flags and their trailing parameters are described there, and so is why the body is text).  Particular to this kernel:
+//   PM_ATTN_LENS  everything below the clamp -- tile counts, the ragged-tile K mask, the V^T zeroing, steady_end / all_steady -- uses
+//                 the per-image value; every base and row stride is unchanged and every read stays inside Nkv_pad
+//   PM_ATTN_SEG   every half-tile takes the exact path: the mask sits where the ragged-tile mask sets scores to -inf, the V^T
+//                 columns of padding keys are zeroed in every tile, and the running max of a query that has not met an allowed key
+//                 yet stays "none" (negm 0, l 0) instead of -inf
+//   PM_ATTN_BIAS  the running max is a max over s + bias; a key whose bias is -inf is padding (255) in seg_of, for the scores and
+//                 for the V^T zeroing alike
 template <bool EXP2, int QF>
 __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kp,
                                                                     const bf16_t* __restrict__ Vt, bf16_t* __restrict__ out,
-                                                                    int ldo, int heads, int Nq, int Nkv, int Nkv_pad, int nqb PM_ATTN_LENS_PARAM) {
+                                                                    int ldo, int heads, int Nq, int Nkv, int Nkv_pad, int nqb
+#ifdef PM_ATTN_LENS
+                                                            , const int* __restrict__ lens
+#endif
+#ifdef PM_ATTN_SEG
+                                                            , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
+#endif
+#ifdef PM_ATTN_BIAS
+                                                            , const float* __restrict__ key_bias
+#endif
+#ifdef PM_ATTN_PICK
+                                                            , const unsigned char* __restrict__ pick, int want
+#endif
+                                                            ) {
     __shared__ __attribute__((aligned(16))) unsigned char lds[RING * STAGE_BYTES];   // K / V^T ring
 
     const int tid = threadIdx.x;

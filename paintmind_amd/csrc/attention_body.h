@@ -1,20 +1,26 @@
-// The fp32-verify attention kernel of attention.hip, which includes this file THREE TIMES (no include guard on purpose), exactly as
-// attention_bf16.hip includes attention_bf16_body.h -- see there: PM_ATTN_KERNEL names the kernel, PM_ATTN_LENS_PARAM is empty or
-// ", const int* lens", and with PM_ATTN_LENS the key count is lens[b], read once per workgroup and clamped to [1, Nkv].
-// A THIRD inclusion with PM_ATTN_SEG (attention_seg_kernel; parameters key_seg, query_mask) is the per-query key set of DESIGN.md 4u:
-// scores of denied keys become -inf in every half-tile, the V^T columns of padding keys (segment 255) are zeroed in every tile, the
-// running max is raised at every half-tile (no deferred rescale), and a query that has met no allowed key yet keeps negm = 0.
-// A FOURTH and a FIFTH inclusion with PM_ATTN_PICK beside PM_ATTN_LENS / PM_ATTN_SEG (attention_lens_pick_kernel, attention_seg_pick_kernel;
-// two more parameters pick, want) are the picked forms of DESIGN.md 4v: a workgroup whose image has pick[b] != want returns at once.
-// A SIXTH inclusion with PM_ATTN_BIAS beside PM_ATTN_SEG (attention_seg_bias_kernel; one more parameter key_bias, device f32 [B, Nkv])
-// is the weighted form of DESIGN.md 4w: key_bias[b, k] = log(weight) in the kernel's score unit is added to an allowed key's score
-// before the maximum is taken; -inf makes the key padding (255), for the scores and for the V^T zeroing alike.
-// A SEVENTH inclusion with PM_ATTN_PICK beside PM_ATTN_SEG and PM_ATTN_BIAS (attention_seg_bias_pick_kernel; pick, want behind key_bias)
-// is the picked weighted form of DESIGN.md 4x: the early return of the picked forms, then the sixth inclusion's text.
+// The fp32-verify attention kernel of attention.hip, included once per form by attention_forms.h (no include guard on purpose; the
+// forms, their flags and their trailing parameters are described there).  Particular to this kernel:
+//   PM_ATTN_SEG   scores of denied keys become -inf in every half-tile, the V^T columns of padding keys (segment 255) are zeroed in
+//                 every tile, the running max is raised at every half-tile (no deferred rescale), and a query that has met no allowed
+//                 key yet keeps negm = 0
+//   PM_ATTN_BIAS  a key whose bias is -inf is padding (255), for the scores and for the V^T zeroing alike
 template <bool EXP2, int QF>
 __global__ __launch_bounds__(THREADS, 2) void PM_ATTN_KERNEL(const float* __restrict__ Q, const float* __restrict__ Kp,
                                                             const float* __restrict__ Vt, float* __restrict__ out,
-                                                            int ldo, int heads, int Nq, int Nkv, int Nkv_pad, int nqb PM_ATTN_LENS_PARAM) {
+                                                            int ldo, int heads, int Nq, int Nkv, int Nkv_pad, int nqb
+#ifdef PM_ATTN_LENS
+                                                            , const int* __restrict__ lens
+#endif
+#ifdef PM_ATTN_SEG
+                                                            , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
+#endif
+#ifdef PM_ATTN_BIAS
+                                                            , const float* __restrict__ key_bias
+#endif
+#ifdef PM_ATTN_PICK
+                                                            , const unsigned char* __restrict__ pick, int want
+#endif
+                                                            ) {
     constexpr int TILE_BYTES = KT * ROWB;
     constexpr int STAGE_BYTES = 2 * TILE_BYTES;              // K tile + V^T tile
     constexpr float kDefer = EXP2 ? 8.0f : 0.0f;             // skip the O rescale while the row max grows < 2^8

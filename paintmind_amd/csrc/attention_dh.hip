@@ -49,70 +49,11 @@ __device__ __forceinline__ float quad_sum(float v) {
     return v;
 }
 
-// DPL = dims per lane = dh / 4.  The kernel, in its two forms (attention_dh_body.h)
-#define PM_ATTN_KERNEL attention_dh_kernel
-#define PM_ATTN_LENS_PARAM
-#include "attention_dh_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-// the per-image form: Nkv_b = clamp(lens[b], 1, Nkv)
-#define PM_ATTN_KERNEL attention_dh_lens_kernel
-#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens
-#define PM_ATTN_LENS 1
-#include "attention_dh_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_LENS
-// the per-query form: key k takes part in query q's softmax iff key_seg[b,k] < 32 and bit key_seg[b,k] of query_mask[b,q] is set
-#define PM_ATTN_KERNEL attention_dh_seg_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
-#define PM_ATTN_SEG 1
-#include "attention_dh_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-// the picked forms: the per-image and the per-query form again, each with `pick` (device uint8 [B]) and `want` --
-// a workgroup whose image has pick[b] != want returns at once, every other one runs its twin's text
-#define PM_ATTN_KERNEL attention_dh_lens_pick_kernel
-#define PM_ATTN_LENS_PARAM , const int* __restrict__ lens, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_LENS 1
-#define PM_ATTN_PICK 1
-#include "attention_dh_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_LENS
-#define PM_ATTN_KERNEL attention_dh_seg_pick_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_SEG 1
-#include "attention_dh_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_PICK
-// the weighted form: the per-query form plus key_bias (device f32 [B, Nkv]), log(weight) of every key in the
-// kernel's score unit; -inf = the key is skipped like padding
-#define PM_ATTN_KERNEL attention_dh_seg_bias_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias
-#define PM_ATTN_SEG 1
-#define PM_ATTN_BIAS 1
-#include "attention_dh_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_BIAS
-// the picked weighted form: the weighted form again with `pick` and `want` -- a workgroup whose image has
-// pick[b] != want returns at once, every other one runs attention_dh_seg_bias_kernel's text
-#define PM_ATTN_KERNEL attention_dh_seg_bias_pick_kernel
-#define PM_ATTN_LENS_PARAM , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask, const float* __restrict__ key_bias, const unsigned char* __restrict__ pick, int want
-#define PM_ATTN_SEG 1
-#define PM_ATTN_BIAS 1
-#define PM_ATTN_PICK 1
-#include "attention_dh_body.h"
-#undef PM_ATTN_KERNEL
-#undef PM_ATTN_LENS_PARAM
-#undef PM_ATTN_SEG
-#undef PM_ATTN_BIAS
-#undef PM_ATTN_PICK
+// DPL = dims per lane = dh / 4
+#define PM_ATTN_BODY "attention_dh_body.h"
+#define PM_ATTN_NAME(sfx) attention_dh##sfx##kernel
+#define PM_ATTN_INSTANTIATE
+#include "attention_forms.h"
 
 // weights -> key_bias: 0 -> -inf (excluded), 1 -> exactly 0, otherwise log2(w), times ln 2 when the scores are nats
 __global__ __launch_bounds__(256) void key_bias_kernel(const float* __restrict__ w, float* __restrict__ bias, int n, int use_exp2) {
@@ -127,53 +68,25 @@ __global__ __launch_bounds__(256) void key_bias_kernel(const float* __restrict__
 }
 
 template <typename T, int DPL>
-void launch_dh(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-               int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, const float* bias, hipStream_t s) {
-    if (bias && pk) {                                  // the picked weighted form: the geometry of the weighted twin
-        auto k = use_exp2 ? attention_dh_seg_bias_pick_kernel<T, DPL, true> : attention_dh_seg_bias_pick_kernel<T, DPL, false>;
-        hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
-                           Nkv, Nkp, seg->key_seg, seg->query_mask, bias, pk->pick, pk->want);
-        return;
-    }
-    if (bias) {                                        // the weighted form: seg beside it
-        auto k = use_exp2 ? attention_dh_seg_bias_kernel<T, DPL, true> : attention_dh_seg_bias_kernel<T, DPL, false>;
-        hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
-                           Nkv, Nkp, seg->key_seg, seg->query_mask, bias);
-        return;
-    }
-    if (pk) {                                          // the picked forms: exactly one of lens / seg, the geometry of the twin
-        const dim3 grid((Nq + 63) / 64, B * heads);
-        if (seg) {
-            auto k = use_exp2 ? attention_dh_seg_pick_kernel<T, DPL, true> : attention_dh_seg_pick_kernel<T, DPL, false>;
-            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq, Nkv, Nkp, seg->key_seg,
-                               seg->query_mask, pk->pick, pk->want);
-        } else {
-            auto k = use_exp2 ? attention_dh_lens_pick_kernel<T, DPL, true> : attention_dh_lens_pick_kernel<T, DPL, false>;
-            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq, Nkv, Nkp, lens, pk->pick,
-                               pk->want);
-        }
-        return;
-    }
-    if (seg) {
-        auto k = use_exp2 ? attention_dh_seg_kernel<T, DPL, true> : attention_dh_seg_kernel<T, DPL, false>;
-        hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B * heads), dim3(256), 0, s, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out, ldo, heads, Nq,
-                           Nkv, Nkp, seg->key_seg, seg->query_mask);
-        return;
-    }
-    auto launch = [&](auto plain, auto per_image) {
-        pm_launch_lens(plain, per_image, dim3((Nq + 63) / 64, B * heads), dim3(256), s, lens, (const T*)Q, (const T*)K, (const T*)Vt, (T*)out,
-                       ldo, heads, Nq, Nkv, Nkp);
-    };
-    if (use_exp2) launch(attention_dh_kernel<T, DPL, true>, attention_dh_lens_kernel<T, DPL, true>);
-    else launch(attention_dh_kernel<T, DPL, false>, attention_dh_lens_kernel<T, DPL, false>);
+void launch_dh(const PmAttnArgs& a) {
+    const dim3 grid((a.Nq + 63) / 64, a.B * a.heads), block(256);
+#define PM_ATTN_LAUNCH(form, sfx, ...)                                                                                                    \
+    case PM_FORM_##form: {                                                                                                                \
+        auto k = a.use_exp2 ? PM_ATTN_NAME(sfx)<T, DPL, true> : PM_ATTN_NAME(sfx)<T, DPL, false>;                                          \
+        hipLaunchKernelGGL(k, grid, block, 0, a.stream, (const T*)a.Q, (const T*)a.K, (const T*)a.Vt, (T*)a.out, a.ldo, a.heads, a.Nq, a.Nkv, \
+                           a.Nkv_pad, ##__VA_ARGS__);                                                                                     \
+    } break;
+    switch (pm_attn_form(a)) { PM_ATTN_FORMS(PM_ATTN_LAUNCH) }
+#undef PM_ATTN_LAUNCH
 }
+#undef PM_ATTN_BODY
+#undef PM_ATTN_NAME
 
 // the launcher of this file's kernels: dim_head != 64, already passed through check_dh
 template <typename T>
-int pm_attention_dh(int dh, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkp,
-                    int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick* pk, const float* bias, hipStream_t s) {
+int pm_attention_dh(int dh, const PmAttnArgs& a) {
     switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_dh<T, n>(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkp, use_exp2, lens, seg, pk, bias, s); break;
+#define PM_DH_CASE(n) case n: launch_dh<T, n>(a); break;
         PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
 #undef PM_DH_CASE
         default: PM_REQUIRE(false, "attention_dh: dim_head=%d not served", dh);
@@ -219,97 +132,76 @@ extern "C" int pmhip_gemm_heads_dh(int dtype, const void* A, int lda, const void
     return PMHIP_OK;
 }
 
-// the dim_head = 64 launchers (attention.hip, attention_bf16.hip)
-void pm_attention_f32(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                      int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, hipStream_t s);
-void pm_attention_bf16(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                       int Nkv_pad, int use_exp2, const int* lens, hipStream_t s);
-void pm_attention_bf16_seg(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                           int Nkv_pad, int use_exp2, const PmAttnSeg& seg, hipStream_t s);
-void pm_attention_f32_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                           int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s);
-void pm_attention_f32_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                               int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s);
-void pm_attention_bf16_seg_bias(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                                int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, hipStream_t s);
-void pm_attention_bf16_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                            int Nkv_pad, int use_exp2, const int* lens, const PmAttnSeg* seg, const PmAttnPick& pk, hipStream_t s);
-void pm_attention_f32_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                                    int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
-                                    hipStream_t s);
-void pm_attention_bf16_seg_bias_pick(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv,
-                                     int Nkv_pad, int use_exp2, const PmAttnSeg& seg, const float* key_bias, const PmAttnPick& pk,
-                                     hipStream_t s);
+int pm_attn_check(const char* who, const PmAttnArgs& a) {
+    PM_REQUIRE(!a.key_seg == !a.query_mask, "%s: key_seg and query_mask go together", who);
+    if (a.pick) PM_REQUIRE(!a.lens != !a.key_seg, "%s: exactly one of kv_lens and the pair key_seg + query_mask selects the form", who);
+    PM_REQUIRE(!(a.lens && a.key_seg), "%s: kv_lens and the pair key_seg + query_mask exclude each other (padding is segment 255)", who);
+    PM_REQUIRE(!a.key_bias || a.key_seg, "%s: key_bias needs key_seg and query_mask beside it", who);
+    if (a.pick) PM_REQUIRE(a.want >= 0 && a.want <= 255, "%s: want=%d is no value of a uint8 pick", who, a.want);
+    return PMHIP_OK;
+}
 
-// Every attention entry point ends here: the arguments are checked once, then one launcher per kernel file.  lens = device
-// int32 [B], the per-image key counts, or NULL (one key count for the launch); seg = the per-query key sets (device arrays), or NULL;
-// pk = the picked forms (exactly one of lens / seg beside it), or NULL; bias = the weighted form (seg beside it), or NULL; bias
-// and pk together = the picked weighted form.
-static int attention_any(const char* who, int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
-                         int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int* lens, hipStream_t s,
-                         const PmAttnSeg* seg = nullptr, const PmAttnPick* pk = nullptr, const float* bias = nullptr) {
+int attention_any(const char* who, int dtype, int dim_head, const PmAttnArgs& a) {
     const bool tuned = dim_head == 64;               // the MFMA kernels; otherwise this file's plain path
-    if (!tuned) PM_TRY(check_dh(who, heads, dim_head));
+    PM_TRY(pm_attn_check(who, a));
+    if (!tuned) PM_TRY(check_dh(who, a.heads, dim_head));
     PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "%s: bad dtype %d", who, dtype);
-    PM_REQUIRE(Q && K && Vt && out, "%s: null pointer", who);
-    PM_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0, "%s: empty problem", who);
+    PM_REQUIRE(a.Q && a.K && a.Vt && a.out, "%s: null pointer", who);
+    PM_REQUIRE(a.B > 0 && a.heads > 0 && a.Nq > 0 && a.Nkv > 0, "%s: empty problem", who);
     if (tuned) {
-        PM_REQUIRE(Nkv_pad % 64 == 0 && Nkv_pad >= Nkv, "%s: Nkv_pad=%d must be a multiple of 64 >= Nkv=%d", who, Nkv_pad, Nkv);
-        PM_REQUIRE(ldo % 4 == 0 && (dtype == PMHIP_F32 || ldo % 8 == 0), "%s: ldo must be a multiple of 4 (f32) / 8 (bf16: 16-byte row stores)", who);
+        PM_REQUIRE(a.Nkv_pad % 64 == 0 && a.Nkv_pad >= a.Nkv, "%s: Nkv_pad=%d must be a multiple of 64 >= Nkv=%d", who, a.Nkv_pad, a.Nkv);
+        PM_REQUIRE(a.ldo % 4 == 0 && (dtype == PMHIP_F32 || a.ldo % 8 == 0), "%s: ldo must be a multiple of 4 (f32) / 8 (bf16: 16-byte row stores)", who);
     } else {
-        PM_REQUIRE(Nkv_pad >= Nkv, "%s: Nkv_pad=%d must be >= Nkv=%d", who, Nkv_pad, Nkv);
+        PM_REQUIRE(a.Nkv_pad >= a.Nkv, "%s: Nkv_pad=%d must be >= Nkv=%d", who, a.Nkv_pad, a.Nkv);
     }
-    PM_REQUIRE(ldo >= heads * dim_head, "%s: ldo=%d is smaller than heads*dim_head=%d (rows of out would overlap)", who, ldo, heads * dim_head);
-    if (!tuned) PM_REQUIRE((long long)B * heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)B * heads);
-    PmTimer tm(FAM_ATTENTION, s);
-    if (!tuned) {
-        if (dtype == PMHIP_F32) PM_TRY(pm_attention_dh<float>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, bias, s));
-        else PM_TRY(pm_attention_dh<bf16_t>(dim_head, Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, pk, bias, s));
-    } else if (bias && pk) {
-        if (dtype == PMHIP_F32) pm_attention_f32_seg_bias_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, *pk, s);
-        else pm_attention_bf16_seg_bias_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, *pk, s);
-    } else if (bias) {
-        if (dtype == PMHIP_F32) pm_attention_f32_seg_bias(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, s);
-        else pm_attention_bf16_seg_bias(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, bias, s);
-    } else if (pk) {
-        if (dtype == PMHIP_F32) pm_attention_f32_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, *pk, s);
-        else pm_attention_bf16_pick(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, *pk, s);
-    } else if (dtype == PMHIP_F32) {
-        pm_attention_f32(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, seg, s);
-    } else {
-        if (seg) pm_attention_bf16_seg(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, *seg, s);
-        else pm_attention_bf16(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, lens, s);
-    }
+    PM_REQUIRE(a.ldo >= a.heads * dim_head, "%s: ldo=%d is smaller than heads*dim_head=%d (rows of out would overlap)", who, a.ldo, a.heads * dim_head);
+    if (!tuned) PM_REQUIRE((long long)a.B * a.heads <= 65535, "%s: B*heads=%lld exceeds the grid's y range", who, (long long)a.B * a.heads);
+    PmTimer tm(FAM_ATTENTION, a.stream);
+    if (!tuned) PM_TRY(dtype == PMHIP_F32 ? pm_attention_dh<float>(dim_head, a) : pm_attention_dh<bf16_t>(dim_head, a));
+    else if (dtype == PMHIP_F32) pm_attention_f32(a);
+    else pm_attention_bf16(a);
     PM_HIP(hipGetLastError());
     return PMHIP_OK;
 }
 
+// The C entry points: each checks the pointers that make it THIS entry, fills the record and calls attention_any.
+static PmAttnArgs attn_record(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
+                              int use_exp2, pmhip_stream stream) {
+    PmAttnArgs a{Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2};
+    a.stream = (hipStream_t)stream;
+    return a;
+}
+
 extern "C" int pmhip_attention(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq,
                                int Nkv, int Nkv_pad, int use_exp2, pmhip_stream stream) {
-    return attention_any("attention", dtype, Q, K, Vt, out, ldo, B, heads, 64, Nq, Nkv, Nkv_pad, use_exp2, nullptr, (hipStream_t)stream);
+    PmAttnArgs a = attn_record(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
+   
+    return attention_any("attention", dtype, 64, a);
 }
 
 extern "C" int pmhip_attention_dh(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                                   int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, pmhip_stream stream) {
-    return attention_any(dim_head == 64 ? "attention" : "attention_dh", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad,
-                         use_exp2, nullptr, (hipStream_t)stream);
+    PmAttnArgs a = attn_record(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
+   
+    return attention_any(dim_head == 64 ? "attention" : "attention_dh", dtype, dim_head, a);
 }
 
 extern "C" int pmhip_attention_lens(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                                     int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens,
                                     pmhip_stream stream) {
     PM_REQUIRE(kv_lens, "attention_lens: kv_lens is NULL (pmhip_attention_dh is the entry without per-image key counts)");
-    return attention_any("attention_lens", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, kv_lens,
-                         (hipStream_t)stream);
+    PmAttnArgs a = attn_record(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
+    a.lens = kv_lens;
+    return attention_any("attention_lens", dtype, dim_head, a);
 }
 
 extern "C" int pmhip_attention_segments(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
                                         int dim_head, int Nq, int Nkv, int Nkv_pad, int use_exp2, const uint8_t* key_seg,
                                         const uint32_t* query_mask, pmhip_stream stream) {
     PM_REQUIRE(key_seg && query_mask, "attention_segments: key_seg / query_mask is NULL (pmhip_attention_dh is the entry without key sets)");
-    const PmAttnSeg seg{key_seg, query_mask};
-    return attention_any("attention_segments", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
-                         (hipStream_t)stream, &seg);
+    PmAttnArgs a = attn_record(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
+    a.key_seg = key_seg; a.query_mask = query_mask;
+    return attention_any("attention_segments", dtype, dim_head, a);
 }
 
 extern "C" int pmhip_attention_weighted(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
@@ -317,9 +209,9 @@ extern "C" int pmhip_attention_weighted(int dtype, const void* Q, const void* K,
                                         const uint32_t* query_mask, const float* key_bias, pmhip_stream stream) {
     PM_REQUIRE(key_seg && query_mask && key_bias,
                "attention_weighted: key_seg / query_mask / key_bias is NULL (pmhip_attention_segments is the entry without weights)");
-    const PmAttnSeg seg{key_seg, query_mask};
-    return attention_any("attention_weighted", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
-                         (hipStream_t)stream, &seg, nullptr, key_bias);
+    PmAttnArgs a = attn_record(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
+    a.key_seg = key_seg; a.query_mask = query_mask; a.key_bias = key_bias;
+    return attention_any("attention_weighted", dtype, dim_head, a);
 }
 
 extern "C" int pmhip_key_bias(const float* weights, float* bias, int n, int use_exp2, pmhip_stream stream) {
@@ -336,13 +228,9 @@ extern "C" int pmhip_attention_pick(int dtype, const void* Q, const void* K, con
                                     const uint8_t* key_seg, const uint32_t* query_mask, const uint8_t* pick, int want,
                                     pmhip_stream stream) {
     PM_REQUIRE(pick, "attention_pick: pick is NULL (pmhip_attention_lens / pmhip_attention_segments are the entries that serve every image)");
-    PM_REQUIRE(!key_seg == !query_mask, "attention_pick: key_seg and query_mask go together");
-    PM_REQUIRE(!kv_lens != !key_seg, "attention_pick: exactly one of kv_lens and the pair key_seg + query_mask selects the form");
-    PM_REQUIRE(want >= 0 && want <= 255, "attention_pick: want=%d is no value of a uint8 pick", want);
-    const PmAttnSeg seg{key_seg, query_mask};
-    const PmAttnPick pk{pick, want};
-    return attention_any("attention_pick", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, kv_lens,
-                         (hipStream_t)stream, key_seg ? &seg : nullptr, &pk);
+    PmAttnArgs a = attn_record(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
+    a.lens = kv_lens; a.key_seg = key_seg; a.query_mask = query_mask; a.pick = pick; a.want = want;
+    return attention_any("attention_pick", dtype, dim_head, a);
 }
 
 extern "C" int pmhip_attention_pick_weighted(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads,
@@ -352,9 +240,7 @@ extern "C" int pmhip_attention_pick_weighted(int dtype, const void* Q, const voi
     PM_REQUIRE(pick, "attention_pick_weighted: pick is NULL (pmhip_attention_weighted is the entry that serves every image)");
     PM_REQUIRE(key_seg && query_mask && key_bias,
                "attention_pick_weighted: key_seg / query_mask / key_bias is NULL (pmhip_attention_pick is the entry without weights)");
-    PM_REQUIRE(want >= 0 && want <= 255, "attention_pick_weighted: want=%d is no value of a uint8 pick", want);
-    const PmAttnSeg seg{key_seg, query_mask};
-    const PmAttnPick pk{pick, want};
-    return attention_any("attention_pick_weighted", dtype, Q, K, Vt, out, ldo, B, heads, dim_head, Nq, Nkv, Nkv_pad, use_exp2, nullptr,
-                         (hipStream_t)stream, &seg, &pk, key_bias);
+    PmAttnArgs a = attn_record(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, stream);
+    a.key_seg = key_seg; a.query_mask = query_mask; a.key_bias = key_bias; a.pick = pick; a.want = want;
+    return attention_any("attention_pick_weighted", dtype, dim_head, a);
 }

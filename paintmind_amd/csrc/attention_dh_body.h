@@ -1,18 +1,25 @@
-// The plain-path attention kernel of attention_dh.hip (DPL = dims per lane = dh / 4), which includes this file THREE TIMES (no include
-// guard on purpose), exactly as attention_bf16.hip includes attention_bf16_body.h -- see there: PM_ATTN_KERNEL names the kernel,
-// PM_ATTN_LENS_PARAM is empty or ", const int* lens", and with PM_ATTN_LENS the loop bound is lens[b], clamped to [1, Nkv].
-// A THIRD inclusion with PM_ATTN_SEG (attention_dh_seg_kernel; parameters key_seg, query_mask) is the per-query key set of DESIGN.md
-// 4u: a key whose segment the query does not attend to (or padding, 255) is skipped -- its score and its V column are read by no update.
-// A FOURTH and a FIFTH inclusion with PM_ATTN_PICK beside PM_ATTN_LENS / PM_ATTN_SEG (attention_dh_lens_pick_kernel,
-// attention_dh_seg_pick_kernel; two more parameters pick, want) are the picked forms of DESIGN.md 4v.
-// A SIXTH inclusion with PM_ATTN_BIAS beside PM_ATTN_SEG (attention_dh_seg_bias_kernel; one more parameter key_bias, device f32
-// [B, Nkv]) is the weighted form of DESIGN.md 4w: an allowed key's score becomes s + key_bias[b, k] before it meets the running
-// maximum, and a key whose bias is -inf is skipped like padding.
-// A SEVENTH inclusion with PM_ATTN_PICK beside PM_ATTN_SEG and PM_ATTN_BIAS (attention_dh_seg_bias_pick_kernel; pick, want behind
-// key_bias) is the picked weighted form of DESIGN.md 4x: the early return of the picked forms, then the sixth inclusion's text.
+// The plain-path attention kernel of attention_dh.hip (DPL = dims per lane = dh / 4), included once per form by attention_forms.h (no
+// include guard on purpose; the forms, their flags and their trailing parameters are described there).  Particular to this kernel:
+//   PM_ATTN_SEG   a key whose segment the query does not attend to (or padding, 255) is skipped -- its score and its V column are
+//                 read by no update
+//   PM_ATTN_BIAS  an allowed key's score becomes s + key_bias[b, k] before it meets the running maximum, and a key whose bias is
+//                 -inf is skipped like padding
 template <typename T, int DPL, bool EXP2>
 __global__ __launch_bounds__(256) void PM_ATTN_KERNEL(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ Vt,
-                                                          T* __restrict__ out, int ldo, int heads, int Nq, int Nkv, int Nkp PM_ATTN_LENS_PARAM) {
+                                                          T* __restrict__ out, int ldo, int heads, int Nq, int Nkv, int Nkp
+#ifdef PM_ATTN_LENS
+                                                            , const int* __restrict__ lens
+#endif
+#ifdef PM_ATTN_SEG
+                                                            , const unsigned char* __restrict__ key_seg, const unsigned* __restrict__ query_mask
+#endif
+#ifdef PM_ATTN_BIAS
+                                                            , const float* __restrict__ key_bias
+#endif
+#ifdef PM_ATTN_PICK
+                                                            , const unsigned char* __restrict__ pick, int want
+#endif
+                                                            ) {
     constexpr int DH = DPL * 4;
     const int bh = blockIdx.y, b = bh / heads, h = bh % heads;
 #ifdef PM_ATTN_PICK

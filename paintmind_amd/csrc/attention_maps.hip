@@ -289,9 +289,9 @@ extern "C" int pmhip_attention_maps(int dtype, const void* Q, const void* K, flo
     PM_REQUIRE(Nkv_pad >= Nkv, "attention_maps: Nkv_pad=%d must be >= Nkv=%d", Nkv_pad, Nkv);
     PM_REQUIRE(ldm >= Nkv, "attention_maps: ldm=%d is smaller than Nkv=%d (rows of maps would overlap)", ldm, Nkv);
     PM_REQUIRE(B <= 65535, "attention_maps: B=%d exceeds the grid's y range", B);
-    PM_REQUIRE(!key_seg == !query_mask, "attention_maps: key_seg and query_mask go together");
-    PM_REQUIRE(!(kv_lens && key_seg), "attention_maps: kv_lens and the pair key_seg + query_mask exclude each other (padding is segment 255)");
-    PM_REQUIRE(!key_bias || key_seg, "attention_maps: key_bias needs key_seg and query_mask beside it");
+    PmAttnArgs a{};                                             // the optional arrays only: the rule of every attention entry
+    a.lens = kv_lens; a.key_seg = key_seg; a.query_mask = query_mask; a.key_bias = key_bias;
+    PM_TRY(pm_attn_check("attention_maps", a));
     PM_REQUIRE(std::isfinite(scale), "attention_maps: scale must be finite");
     hipStream_t s = (hipStream_t)stream;
     MapParams p{};

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/pmhip.h"
+#include "attention_forms.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
@@ -405,27 +406,32 @@ static inline int pm_dev_knob(const char* name, int dflt) {
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t dtype_size(int dtype) { return dtype == PMHIP_BF16 ? 2 : 4; }
 
-// The attention kernels come in two forms: `plain` takes one key count for the launch, `per_image` takes the same
-// arguments plus `lens` (device int32 [B]).  lens == NULL launches the plain form.
-template <typename Plain, typename PerImage, typename... Args>
-static inline void pm_launch_lens(Plain plain, PerImage per_image, dim3 grid, dim3 block, hipStream_t s, const int* lens, Args... args) {
-    if (lens) hipLaunchKernelGGL(per_image, grid, block, 0, s, args..., lens);
-    else hipLaunchKernelGGL(plain, grid, block, 0, s, args...);
+// One attention launch: operands, geometry, the optional arrays of the forms (attention_forms.h) and the stream.  The
+// pointers that are set select the form -- pm_attn_form --, and pm_attn_check is the one place that says which may stand together.
+struct PmAttnArgs {
+    const void *Q, *K, *Vt;
+    void* out;
+    int ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2;
+    const int* lens = nullptr;                   // device int32 [B], or NULL: one key count for the launch
+    const unsigned char* key_seg = nullptr;      // device uint8 [B, Nkv] and ...
+    const unsigned* query_mask = nullptr;        // ... device uint32 [B, Nq], or both NULL
+    const float* key_bias = nullptr;             // device f32 [B, Nkv], or NULL
+    const unsigned char* pick = nullptr;         // device uint8 [B], or NULL: the launch serves every image
+    int want = 0;
+    hipStream_t stream = nullptr;
+};
+inline PmAttnForm pm_attn_form(const PmAttnArgs& a) {
+    if (a.key_seg) return a.key_bias ? (a.pick ? PM_FORM_SEG_BIAS_PICK : PM_FORM_SEG_BIAS) : (a.pick ? PM_FORM_SEG_PICK : PM_FORM_SEG);
+    return a.lens ? (a.pick ? PM_FORM_LENS_PICK : PM_FORM_LENS) : PM_FORM_PLAIN;
 }
-
-// The third form: a key SET per query.  key_seg device uint8 [B, Nkv] (segment 0..31 of a key, 255 = padding),
-// query_mask device uint32 [B, Nq] (bit s: the query attends to segment s).  The launchers take a pointer to this, NULL for none.
-struct PmAttnSeg {
-    const unsigned char* key_seg;
-    const unsigned* query_mask;
-};
-
-// The picked forms: pick device uint8 [B], the kind of every image; a launch serves the images with pick[b] == want
-// and leaves the output rows of the others untouched.
-struct PmAttnPick {
-    const unsigned char* pick;
-    int want;
-};
+// key_seg and query_mask go together; lens and that pair exclude each other; key_bias needs the pair; pick needs exactly one of lens
+// and the pair, and want in [0, 255].  Looks at the optional arrays only (pmhip_attention_maps fills nothing else).
+int pm_attn_check(const char* who, const PmAttnArgs& a);
+// Every attention launch ends here (attention_dh.hip): the arguments are checked once, then one launcher per kernel file, each
+// already past the checks.  who = the entry point's name in error texts.
+int attention_any(const char* who, int dtype, int dim_head, const PmAttnArgs& a);
+void pm_attention_f32(const PmAttnArgs& a);      // attention.hip: fp32, dim_head = 64
+void pm_attention_bf16(const PmAttnArgs& a);     // attention_bf16.hip: bf16, dim_head = 64
 
 // Can a LayerNorm over K columns be folded into the GEMM out[M,N] = A[M,K] (row stride lda) . W[N,K]^T (row stride ldw)?  THE
 // predicate: the engine's decision (M = one image's rows: folded or not must not depend on the batch), the GEMM entry points'

@@ -455,34 +455,33 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
             void* outs[1] = {b.q};
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 1, kind_q,
                             outs, q_scale, s));
-            // the one launch that sees per-image context lengths (self-attention and the unconditional pass never do)
-            if (cross->pick) {
-                // two launches into one buffer: the plain images under their lengths, then the regional ones under
-                // their key sets; each launch leaves the other kind's rows as they are
-                PM_TRY(pmhip_attention_pick(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
-                                            cross->lens, nullptr, nullptr, cross->pick, 0, s));
-                PM_TRY(pmhip_attention_pick(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
-                                            nullptr, cross->key_seg, cross->query_mask, cross->pick, 1, s));
-                // ... and, in a step with a weighted slot, a third: the weighted ones under their key sets and biases
-                if (cross->key_bias)
-                    PM_TRY(pmhip_attention_pick_weighted(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L,
-                                                         cross->Lp, fast, cross->key_seg, cross->query_mask, cross->key_bias, cross->pick, 2, s));
-            } else if (cross->key_bias)
-                PM_TRY(pmhip_attention_weighted(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
-                                                cross->key_seg, cross->query_mask, cross->key_bias, s));
-            else if (cross->key_seg)
-                PM_TRY(pmhip_attention_segments(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
-                                                cross->key_seg, cross->query_mask, s));
-            else if (cross->lens)
-                PM_TRY(pmhip_attention_lens(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
-                                            cross->lens, s));
-            else
-                PM_TRY(pmhip_attention_dh(dtype, b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast, s));
+            // the one launch that sees per-image context lengths (self-attention and the unconditional pass never do): the set's
+            // arrays go into one record, which selects the form; key sets subsume the lengths (padding is segment 255)
+            PmAttnArgs a{b.q, cross->k, cross->vt, b.attn, inner, B, tc.heads, tokens, cross->L, cross->Lp, fast};
+            a.key_seg = cross->key_seg; a.query_mask = cross->query_mask; a.key_bias = cross->key_bias;
+            a.lens = a.key_seg ? nullptr : cross->lens;
+            a.stream = s;
+            if (!cross->pick) {
+                PM_TRY(attention_any("attention", dtype, dh, a));
+            } else {
+                // one launch per kind into one buffer, each leaving the other kinds' rows as they are: the plain
+                // images under their lengths, the regional ones under their key sets and, in a step with a weighted slot, the
+                // weighted ones under their key sets and biases
+                PmAttnArgs kind = a;
+                kind.pick = cross->pick;
+                kind.lens = cross->lens; kind.key_seg = nullptr; kind.query_mask = nullptr; kind.key_bias = nullptr; kind.want = 0;
+                PM_TRY(attention_any("attention_pick", dtype, dh, kind));
+                kind.lens = nullptr; kind.key_seg = a.key_seg; kind.query_mask = a.query_mask; kind.want = 1;
+                PM_TRY(attention_any("attention_pick", dtype, dh, kind));
+                if (a.key_bias) {
+                    kind.key_bias = a.key_bias; kind.want = 2;
+                    PM_TRY(attention_any("attention_pick_weighted", dtype, dh, kind));
+                }
+            }
             // the maps tap: the head-mean probabilities of the launch above, from the same Q, K, lengths, sets and biases
             if (cross->maps)
-                PM_TRY(pmhip_attention_maps(dtype, b.q, cross->k, cross->maps, cross->L, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast,
-                                            cross->key_seg ? nullptr : cross->lens, cross->key_seg, cross->query_mask, cross->key_bias,
-                                            cross->maps_scale, cross->maps_accumulate, s));
+                PM_TRY(pmhip_attention_maps(dtype, a.Q, a.K, cross->maps, cross->L, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast, a.lens,
+                                            a.key_seg, a.query_mask, a.key_bias, cross->maps_scale, cross->maps_accumulate, s));
         } else {
             void* outs[3] = {b.q, b.k, b.vt};
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 3, kinds_qkv,

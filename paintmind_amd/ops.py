@@ -429,6 +429,41 @@ def key_bias(weights, use_exp2):
     return out
 
 
+def _key_sets(B, Nq, n_kv, dev, use_exp2, kv_lens, key_segments, query_segments, key_weights, exactly_one=False):
+    """The optional arrays of ``attention``, ``attention_pick`` and ``attention_maps`` against (B, Nq, n_kv) -- the one place that
+    says which go together.  exactly_one (``attention_pick``): one of kv_lens and the pair of segment arrays must select the form.
+    For weights given alone the neutral arrays (every key segment 0, every query all ones) are built here.
+    -> (key_segments, query_segments, bias), each None where the form has none"""
+    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
+        raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
+    if (key_segments is None) != (query_segments is None):
+        raise ValueError("key_segments and query_segments come together")
+    if key_segments is not None:
+        if kv_lens is not None:
+            raise ValueError("exactly one of kv_lens and the pair key_segments + query_segments selects the form" if exactly_one else
+                             "key_segments / query_segments and kv_lens exclude each other (mark padding keys with segment 255)")
+        if key_segments.dtype != torch.uint8 or tuple(key_segments.shape) != (B, n_kv) or not key_segments.is_contiguous():
+            raise ValueError(f"key_segments must be a contiguous uint8 tensor of shape ({B}, {n_kv}), got {key_segments.dtype} "
+                             f"{tuple(key_segments.shape)}")
+        if query_segments.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(query_segments.shape) != (B, Nq) or \
+                not query_segments.is_contiguous():
+            raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
+                             f"{tuple(query_segments.shape)}")
+    bias = None
+    if key_weights is not None:
+        if kv_lens is not None:
+            raise ValueError("key_weights and kv_lens exclude each other (a weight of 0 makes a key padding)")
+        if key_weights.dtype != torch.float32 or tuple(key_weights.shape) != (B, n_kv):
+            raise ValueError(f"key_weights must be a float32 tensor of shape ({B}, {n_kv}), got {key_weights.dtype} {tuple(key_weights.shape)}")
+        bias = key_bias(key_weights, use_exp2)
+        if key_segments is None:
+            key_segments = torch.zeros(B, n_kv, dtype=torch.uint8, device=dev)
+            query_segments = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
+    if exactly_one and kv_lens is None and key_segments is None:
+        raise ValueError("exactly one of kv_lens and the pair key_segments + query_segments selects the form")
+    return key_segments, query_segments, bias
+
+
 def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, query_segments=None, key_weights=None):
     """q [B,H,Nq,dh], k [B,H,Nkp,dh], vt [B,H,dh,Nkp] -> [B*Nq, H*dh]  (dh 64: tuned MFMA kernel; else pmhip_attention_dh).
     kv_lens (None: every image attends to n_kv keys): int32 [B] on the device, image b attends to its first kv_lens[b] keys
@@ -444,36 +479,13 @@ def attention(q, k, vt, n_kv, use_exp2=False, kv_lens=None, key_segments=None, q
     B, H, Nq, dh = q.shape
     nkp = k.shape[2]
     out = torch.empty(B * Nq, H * dh, device=dev, dtype=q.dtype)
-    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
-        raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
-    if (key_segments is None) != (query_segments is None):
-        raise ValueError("key_segments and query_segments come together")
-    if key_segments is not None:
-        if kv_lens is not None:
-            raise ValueError("key_segments / query_segments and kv_lens exclude each other (mark padding keys with segment 255)")
-        if key_segments.dtype != torch.uint8 or tuple(key_segments.shape) != (B, n_kv) or not key_segments.is_contiguous():
-            raise ValueError(f"key_segments must be a contiguous uint8 tensor of shape ({B}, {n_kv}), got {key_segments.dtype} "
-                             f"{tuple(key_segments.shape)}")
-        if query_segments.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(query_segments.shape) != (B, Nq) or \
-                not query_segments.is_contiguous():
-            raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
-                             f"{tuple(query_segments.shape)}")
-    if key_weights is not None:
-        if kv_lens is not None:
-            raise ValueError("key_weights and kv_lens exclude each other (a weight of 0 makes a key padding)")
-        if key_weights.dtype != torch.float32 or tuple(key_weights.shape) != (B, n_kv):
-            raise ValueError(f"key_weights must be a float32 tensor of shape ({B}, {n_kv}), got {key_weights.dtype} {tuple(key_weights.shape)}")
-        bias = key_bias(key_weights, use_exp2)
-        if key_segments is None:
-            key_segments = torch.zeros(B, n_kv, dtype=torch.uint8, device=dev)
-            query_segments = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
+    key_segments, query_segments, bias = _key_sets(B, Nq, n_kv, dev, use_exp2, kv_lens, key_segments, query_segments, key_weights)
+    with torch.cuda.device(dev):
+        if bias is not None:
             check(lib.pmhip_attention_weighted(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * dh, B, H, dh, Nq, n_kv, nkp,
                                                int(use_exp2), _p(key_segments), _p(query_segments), _p(bias), stream_ptr(dev)),
                   "pmhip_attention_weighted")
-        return out
-    with torch.cuda.device(dev):
-        if key_segments is not None:
+        elif key_segments is not None:
             check(lib.pmhip_attention_segments(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), H * dh, B, H, dh, Nq, n_kv, nkp,
                                                int(use_exp2), _p(key_segments), _p(query_segments), stream_ptr(dev)),
                   "pmhip_attention_segments")
@@ -511,30 +523,9 @@ def attention_pick(q, k, vt, n_kv, pick, want, out, use_exp2=False, kv_lens=None
     if out.dtype != q.dtype or tuple(out.shape) != (B * Nq, H * dh) or out.stride(1) != 1 or out.stride(0) < H * dh:
         raise ValueError(f"out must be a {q.dtype} [{B * Nq}, {H * dh}] tensor with unit column stride, got {out.dtype} {tuple(out.shape)} "
                          f"strides {tuple(out.stride())}")
-    if (key_segments is None) != (query_segments is None):
-        raise ValueError("key_segments and query_segments come together")
-    if key_weights is not None:
-        if kv_lens is not None:
-            raise ValueError("key_weights and kv_lens exclude each other (a weight of 0 makes a key padding)")
-        if key_weights.dtype != torch.float32 or tuple(key_weights.shape) != (B, n_kv):
-            raise ValueError(f"key_weights must be a float32 tensor of shape ({B}, {n_kv}), got {key_weights.dtype} {tuple(key_weights.shape)}")
-        if key_segments is None:
-            key_segments = torch.zeros(B, n_kv, dtype=torch.uint8, device=dev)
-            query_segments = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
-    if (kv_lens is None) == (key_segments is None):
-        raise ValueError("exactly one of kv_lens and the pair key_segments + query_segments selects the form")
-    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
-        raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
-    if key_segments is not None:
-        if key_segments.dtype != torch.uint8 or tuple(key_segments.shape) != (B, n_kv) or not key_segments.is_contiguous():
-            raise ValueError(f"key_segments must be a contiguous uint8 tensor of shape ({B}, {n_kv}), got {key_segments.dtype} "
-                             f"{tuple(key_segments.shape)}")
-        if query_segments.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(query_segments.shape) != (B, Nq) or \
-                not query_segments.is_contiguous():
-            raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
-                             f"{tuple(query_segments.shape)}")
-    if key_weights is not None:
-        bias = key_bias(key_weights, use_exp2)
+    key_segments, query_segments, bias = _key_sets(B, Nq, n_kv, dev, use_exp2, kv_lens, key_segments, query_segments, key_weights,
+                                                   exactly_one=True)
+    if bias is not None:
         with torch.cuda.device(dev):
             check(lib.pmhip_attention_pick_weighted(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), out.stride(0), B, H, dh, Nq, n_kv, nkp,
                                                     int(use_exp2), _p(key_segments), _p(query_segments), _p(bias), _p(pick), int(want),
@@ -562,30 +553,7 @@ def attention_maps(q, k, n_kv, use_exp2=False, kv_lens=None, key_segments=None, 
     nkp = k.shape[2]
     if k.dtype != q.dtype or k.shape[0] != B or k.shape[1] != H or k.shape[3] != dh or nkp < n_kv:
         raise ValueError(f"k must be a {q.dtype} [{B}, {H}, >= {n_kv}, {dh}] tensor, got {k.dtype} {tuple(k.shape)}")
-    if kv_lens is not None and (kv_lens.dtype != torch.int32 or tuple(kv_lens.shape) != (B,)):
-        raise ValueError(f"kv_lens must be an int32 tensor of shape ({B},), got {kv_lens.dtype} {tuple(kv_lens.shape)}")
-    if (key_segments is None) != (query_segments is None):
-        raise ValueError("key_segments and query_segments come together")
-    if key_segments is not None:
-        if kv_lens is not None:
-            raise ValueError("key_segments / query_segments and kv_lens exclude each other (mark padding keys with segment 255)")
-        if key_segments.dtype != torch.uint8 or tuple(key_segments.shape) != (B, n_kv) or not key_segments.is_contiguous():
-            raise ValueError(f"key_segments must be a contiguous uint8 tensor of shape ({B}, {n_kv}), got {key_segments.dtype} "
-                             f"{tuple(key_segments.shape)}")
-        if query_segments.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or tuple(query_segments.shape) != (B, Nq) or \
-                not query_segments.is_contiguous():
-            raise ValueError(f"query_segments must be a contiguous int32 / uint32 tensor of shape ({B}, {Nq}), got {query_segments.dtype} "
-                             f"{tuple(query_segments.shape)}")
-    bias = None
-    if key_weights is not None:
-        if kv_lens is not None:
-            raise ValueError("key_weights and kv_lens exclude each other (a weight of 0 makes a key padding)")
-        if key_weights.dtype != torch.float32 or tuple(key_weights.shape) != (B, n_kv):
-            raise ValueError(f"key_weights must be a float32 tensor of shape ({B}, {n_kv}), got {key_weights.dtype} {tuple(key_weights.shape)}")
-        bias = key_bias(key_weights, use_exp2)
-        if key_segments is None:
-            key_segments = torch.zeros(B, n_kv, dtype=torch.uint8, device=dev)
-            query_segments = torch.full((B, Nq), -1, dtype=torch.int32, device=dev)
+    key_segments, query_segments, bias = _key_sets(B, Nq, n_kv, dev, use_exp2, kv_lens, key_segments, query_segments, key_weights)
     if out is None:
         if accumulate:
             raise ValueError("accumulate adds to `out`: pass the tensor to add to")

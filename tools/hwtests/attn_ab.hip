@@ -83,6 +83,14 @@ static void gen3_run(const void* Q, const void* K, const void* Vt, void* out, in
                      int use_exp2, const int*, hipStream_t s) {
     gen3::pm_attention_bf16(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, s);
 }
+// csrc/attention_bf16.hip's launcher takes a PmAttnArgs record; the variants here are called positionally through one type
+template <void (*Launch)(const PmAttnArgs&)>
+static void positional(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
+                       int use_exp2, const int* lens, hipStream_t s) {
+    PmAttnArgs a{Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2};
+    a.lens = lens; a.stream = s;
+    Launch(a);
+}
 struct V { const char* name; fn_t fn; bool exact; double us; };
 
 int main(int argc, char** argv) {
@@ -97,18 +105,18 @@ int main(int argc, char** argv) {
     void *q, *k, *v, *o, *oref;
     hipMalloc(&q, n * 2); hipMalloc(&k, n * 2); hipMalloc(&v, n * 2); hipMalloc(&o, n * 2); hipMalloc(&oref, n * 2);
     hipMemcpy(q, hq.data(), n * 2, hipMemcpyHostToDevice); hipMemcpy(k, hk.data(), n * 2, hipMemcpyHostToDevice); hipMemcpy(v, hv.data(), n * 2, hipMemcpyHostToDevice);
-    V vs[] = {{"gen3 (round 4)", gen3_run, true, 0}, {"gen4", gen4::pm_attention_bf16, true, 0},
-              {"gen4 256 queries / WG", g4_qf4::pm_attention_bf16, true, 0}, {"gen4 128 queries / WG", g4_qf2::pm_attention_bf16, true, 0},
-              {"gen4  64 queries / WG", g4_qf1::pm_attention_bf16, true, 0},
-              {"gen4 old K swizzle", g4_kswz0::pm_attention_bf16, true, 0},
-              {"gen4 3-stage ring", g4_ring3::pm_attention_bf16, true, 0},
-              {"gen4 no exp (mul)", g4_noexp::pm_attention_bf16, false, 0}, {"gen4 no fragment reads", g4_noreads::pm_attention_bf16, false, 0},
-              {"gen4 no DMA", g4_nodma::pm_attention_bf16, false, 0}, {"gen4 no barrier", g4_nobarrier::pm_attention_bf16, false, 0},
-              {"gen4 no reads/DMA/barrier", g4_nomove::pm_attention_bf16, false, 0}, {"gen4 MFMA + pack only", g4_skeleton::pm_attention_bf16, false, 0}};
+    V vs[] = {{"gen3 (round 4)", gen3_run, true, 0}, {"gen4", positional<gen4::pm_attention_bf16>, true, 0},
+              {"gen4 256 queries / WG", positional<g4_qf4::pm_attention_bf16>, true, 0}, {"gen4 128 queries / WG", positional<g4_qf2::pm_attention_bf16>, true, 0},
+              {"gen4  64 queries / WG", positional<g4_qf1::pm_attention_bf16>, true, 0},
+              {"gen4 old K swizzle", positional<g4_kswz0::pm_attention_bf16>, true, 0},
+              {"gen4 3-stage ring", positional<g4_ring3::pm_attention_bf16>, true, 0},
+              {"gen4 no exp (mul)", positional<g4_noexp::pm_attention_bf16>, false, 0}, {"gen4 no fragment reads", positional<g4_noreads::pm_attention_bf16>, false, 0},
+              {"gen4 no DMA", positional<g4_nodma::pm_attention_bf16>, false, 0}, {"gen4 no barrier", positional<g4_nobarrier::pm_attention_bf16>, false, 0},
+              {"gen4 no reads/DMA/barrier", positional<g4_nomove::pm_attention_bf16>, false, 0}, {"gen4 MFMA + pack only", positional<g4_skeleton::pm_attention_bf16>, false, 0}};
     // element-wise comparison of the exact variants (bf16 outputs)
     std::vector<unsigned short> ha(n), hb(n);
     gen3_run(q, k, v, oref, H * 64, B, H, N, N, N, 1, nullptr, 0);
-    gen4::pm_attention_bf16(q, k, v, o, H * 64, B, H, N, N, N, 1, nullptr, 0);
+    positional<gen4::pm_attention_bf16>(q, k, v, o, H * 64, B, H, N, N, N, 1, nullptr, 0);
     hipDeviceSynchronize();
     hipMemcpy(ha.data(), oref, n * 2, hipMemcpyDeviceToHost); hipMemcpy(hb.data(), o, n * 2, hipMemcpyDeviceToHost);
     double maxd = 0, maxv = 0; size_t ndiff = 0;
@@ -120,7 +128,7 @@ int main(int argc, char** argv) {
     }
     printf("gen4 vs gen3: %zu of %zu bf16 outputs differ, max abs diff %.3g (max |out| %.3g)\n", ndiff, n, maxd, maxv);
     {   // the workgroup size must not change a single bit (batch invariance of the model rests on it)
-        fn_t qfs[3] = {g4_qf4::pm_attention_bf16, g4_qf2::pm_attention_bf16, g4_qf1::pm_attention_bf16};
+        fn_t qfs[3] = {positional<g4_qf4::pm_attention_bf16>, positional<g4_qf2::pm_attention_bf16>, positional<g4_qf1::pm_attention_bf16>};
         const char* names[3] = {"256", "128", "64"};
         for (int i = 0; i < 3; ++i) {
             hipMemset(oref, 0xff, n * 2);

@@ -72,6 +72,14 @@ namespace a127 {
 #undef ABL
 
 typedef void (*fn_t)(const void*, const void*, const void*, void*, int, int, int, int, int, int, int, const int*, hipStream_t);
+// csrc/attention_bf16.hip's launcher takes a PmAttnArgs record; the variants here are called positionally through one type
+template <void (*Launch)(const PmAttnArgs&)>
+static void positional(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
+                       int use_exp2, const int* lens, hipStream_t s) {
+    PmAttnArgs a{Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2};
+    a.lens = lens; a.stream = s;
+    Launch(a);
+}
 struct V { const char* name; fn_t fn; };
 
 int main(int argc, char** argv) {
@@ -85,10 +93,10 @@ int main(int argc, char** argv) {
     void *q, *k, *v, *o;
     hipMalloc(&q, n * 2); hipMalloc(&k, n * 2); hipMalloc(&v, n * 2); hipMalloc(&o, n * 2);
     hipMemcpy(q, hq.data(), n * 2, hipMemcpyHostToDevice); hipMemcpy(k, hk.data(), n * 2, hipMemcpyHostToDevice); hipMemcpy(v, hv.data(), n * 2, hipMemcpyHostToDevice);
-    V vs[] = {{"full", a0::pm_attention_bf16}, {"no exp (mul)", a1::pm_attention_bf16}, {"no fragment reads", a2::pm_attention_bf16},
-              {"no DMA", a4::pm_attention_bf16}, {"no barrier", a8::pm_attention_bf16}, {"no max check", a16::pm_attention_bf16},
-              {"no output store", a32::pm_attention_bf16}, {"no Q load", a64::pm_attention_bf16}, {"no Q load, no store", a96::pm_attention_bf16},
-              {"no reads/DMA/barrier", a14::pm_attention_bf16}, {"MFMA + pack only", a31::pm_attention_bf16}, {"MFMA + pack, no Q/store", a127::pm_attention_bf16}};
+    V vs[] = {{"full", positional<a0::pm_attention_bf16>}, {"no exp (mul)", positional<a1::pm_attention_bf16>}, {"no fragment reads", positional<a2::pm_attention_bf16>},
+              {"no DMA", positional<a4::pm_attention_bf16>}, {"no barrier", positional<a8::pm_attention_bf16>}, {"no max check", positional<a16::pm_attention_bf16>},
+              {"no output store", positional<a32::pm_attention_bf16>}, {"no Q load", positional<a64::pm_attention_bf16>}, {"no Q load, no store", positional<a96::pm_attention_bf16>},
+              {"no reads/DMA/barrier", positional<a14::pm_attention_bf16>}, {"MFMA + pack only", positional<a31::pm_attention_bf16>}, {"MFMA + pack, no Q/store", positional<a127::pm_attention_bf16>}};
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int round = 0; round < 2; ++round)
         for (auto& x : vs) {

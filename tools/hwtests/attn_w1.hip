@@ -86,10 +86,12 @@ namespace g5b {
 #define NVAR 0
 #endif
 typedef int (*fn_t)(const void*, const void*, const void*, void*, int, int, int, int, int, int, int, hipStream_t);
-// the product's launcher takes per-image key counts (NULL here) and returns nothing; the shelved files keep the older form
+// the product's launcher takes a PmAttnArgs record (the plain form here) and returns nothing; the shelved files keep the older form
 static int g4_run(const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int Nq, int Nkv, int Nkv_pad,
                   int use_exp2, hipStream_t s) {
-    g4::pm_attention_bf16(Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2, nullptr, s);
+    PmAttnArgs a{Q, K, Vt, out, ldo, B, heads, Nq, Nkv, Nkv_pad, use_exp2};
+    a.stream = s;
+    g4::pm_attention_bf16(a);
     return 0;
 }
 struct V { const char* name; fn_t fn; double us; };
