@@ -25,7 +25,7 @@
  *         lda >= K, ldw >= K          every GEMM entry point (and both multiples of 8)
  *         ldo >= N, ldr >= N          pmhip_gemm / _ln / _softmax_stats (ldr only with a residual), pmhip_gemm_hilo / _stats / _center
  *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
- *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens
+ *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens / _control
  *         ldm >= Nkv                  pmhip_attention_maps
  *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus, pmhip_masked_ce
  *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
@@ -335,6 +335,43 @@ int pmhip_attention_pick_weighted(int dtype, const void* Q, const void* K, const
 int pmhip_attention_maps(int dtype, const void* Q, const void* K, float* maps, int ldm, int B, int heads, int dim_head, int Nq, int Nkv,
                          int Nkv_pad, int use_exp2, const int32_t* kv_lens, const uint8_t* key_seg, const uint32_t* query_mask,
                          const float* key_bias, float scale, int accumulate, pmhip_stream stream);
+
+/* Cross-attention control: the edited pass of a prompt-to-prompt pair attends with probabilities blended from the source pass's (new
+ * entry within ABI 11, nothing existing changes meaning).  The flash kernels above never hold a row of P, so
+ * no form of theirs can blend two passes; this entry recomputes both softmaxes.  B pairs.  Qs [B,H,Nq,dh] and Ks [B,H,Ls_pad,dh] are
+ * the source pass's, Qt, Kt [B,H,Lt_pad,dh] and Vt [B,H,dh,Lt_pad] the edited pass's (`dtype`), in the layouts pmhip_gemm_heads(_dh)
+ * writes; both Q are already scaled and carry log2(e) when use_exp2 != 0.  out (`dtype`) [B*Nq, ldo], ldo >= heads * dim_head.
+ *     row_map DEVICE int32 [B, Lt]: the source row of every target row, negative for none
+ *     blend   DEVICE f32   [B, Lt]: in [0, 1]            gain DEVICE f32 [B, Lt]: finite and >= 0
+ *     lens_s, lens_t DEVICE int32 [B] or NULL: the pair's key counts ns, nt, with the clamp of pmhip_attention_lens to [1, Ls] / [1, Lt];
+ *                   NULL: Ls / Lt
+ * For every pair b, head h, query q:
+ *     ps = softmax over k < ns of Qs_h Ks_h^T           pt = softmax over j < nt of Qt_h Kt_h^T
+ *     m = row_map[b,j];  has = 0 <= m < ns && blend[b,j] != 0
+ *     P[q,j] = gain[b,j] * (has ? (1 - blend[b,j]) * pt[q,j] + blend[b,j] * ps[q,m] : pt[q,j])                    j < nt
+ *     out[b*Nq + q, h*dh : (h+1)*dh] = sum_j P[q,j] * V_h[j,:]                  (no renormalisation, as in Hertz et al.)
+ * Contract:
+ *   - select, not arithmetic: a target key at or behind nt reaches nothing, NaN in its K row and V^T column included (the K row is
+ *     never read; the MFMA kernel reads a V^T column only inside the 8-byte group of 4 keys that straddles nt and drops it by a select); where `has` is
+ *     false no source score enters that key (a map entry at or behind ns is `none`); source rows at or behind ns are never read, so
+ *     NaN there reaches nothing.  K rows below ns / nt and V^T columns below nt must be finite
+ *   - the ranges of blend and gain are the caller's to validate (the model-level entry does): this operator cannot read device
+ *     memory on the host.  Values outside them yield finite or non-finite rows, never a read or a write outside the stated extents
+ *   - memory: nothing outside out's [B*Nq, heads*dim_head] extent under ldo is written; row_map, blend and gain are read in [B, Lt]
+ *   - determinism: no floating-point atomics; every element of out is written by exactly one thread, once per launch; two launches
+ *     on the same inputs agree bit for bit; pair b's rows do not depend on what else is in the batch
+ *   - blend == 0 and gain == 1 everywhere is the softmax of pmhip_attention_lens on the edited pass, computed by other kernels: equal
+ *     within the two entries' bounds (tests/control_ref.py), not bit for bit
+ *   - precision: bf16 with dim_head 64 rounds P -- after blend and gain -- to bf16 for its P.V MFMA, as the product kernel does, and
+ *     accumulates in f32; every other path keeps P in f32.  One rounding of out to `dtype`
+ * Any dim_head the _dh entry serves, heads <= 64, B * heads <= 65535, any Ls and Lt (two passes over both contexts; registers do not
+ * depend on them, and there is no LDS).  bf16 with dim_head 64 runs on MFMA (64 queries per workgroup, 16 per wave; Q and K 16-byte
+ * aligned, Vt and out 8-byte aligned, Lt_pad and ldo multiples of 4); fp32 and every other dim_head run a plain vector-ALU kernel, 4
+ * lanes per query.  A NULL operand or control array, or a shape outside the above: PMHIP_EINVAL before any launch. */
+int pmhip_attention_control(int dtype, const void* Qs, const void* Ks, const void* Qt, const void* Kt, const void* Vt, void* out, int ldo,
+                            int B, int heads, int dim_head, int Nq, int Ls, int Ls_pad, int Lt, int Lt_pad, int use_exp2,
+                            const int32_t* row_map, const float* blend, const float* gain, const int32_t* lens_s, const int32_t* lens_t,
+                            pmhip_stream stream);
 
 /* torch.nn.LayerNorm over the last dim, eps inside the sqrt (stage1/layers.py:49,51,89,128;
  * stage2/transformer.py:37,39,41,62).  x fp32 [M,D] -> out (`out_dtype`). */
@@ -1171,6 +1208,24 @@ int pmhip_s2_forward_weights(pmhip_s2* h, const float* tokens, const float* cont
 int pmhip_s2_forward_maps(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
                           const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const float* ctx_w_host, uint64_t layer_bits,
                           float* logits_out, float* maps_out, pmhip_stream stream);
+/* Prompt-to-prompt: ONE eager forward over B PAIRS of images (new entry within ABI 11, nothing existing changes meaning; DESIGN.md
+ * section 4za).  tokens [2B * tokens, embed_dim], context [2B, L, D], logits_out [2B * tokens, n_embed]: images [0, B) carry the
+ * source prompts, images [B, 2B) the edited ones.  ctx_lens_host [2B] or NULL.
+ *   cross_bits  bit l set: in layer l the cross-attention of the source half is the ordinary launch on its B images, and the edited
+ *               half runs pmhip_attention_control with Qs / Ks the source half's scaled Q and cached K, under
+ *               row_map_host int32 [B, L] (the source row of every edited row, negative: none), blend_host f32 [B, L] and
+ *               gain_host f32 [B, L] -- one row per pair
+ *   self_bits   bit l set (may be 0): in layer l the edited half's FIRST self-attention runs pmhip_attention_dh on the source half's Q
+ *               and K and its own V^T (self-attention injection; pointer arithmetic, no kernel of its own)
+ *   - validation happens before anything is launched: the checks of pmhip_s2_forward_lens, plus: a context is required,
+ *     cross_bits | self_bits != 0, no bit at or above depth, the three arrays required iff cross_bits != 0, every map entry < L, every
+ *     blend in [0, 1], every gain finite and >= 0
+ *   - the source half's logits are, bit for bit, those of pmhip_s2_forward_lens / pmhip_s2_forward on the source half alone
+ *   - eager only: the entry adds no key to the handle's graph cache, and it clears the control before it returns, on the error paths
+ *     too: a later call of any entry runs exactly what it ran before */
+int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                             uint64_t cross_bits, uint64_t self_bits, const int32_t* row_map_host, const float* blend_host,
+                             const float* gain_host, float* logits_out, pmhip_stream stream);
 int pmhip_pipeline_sample_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                   const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
                                   uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,

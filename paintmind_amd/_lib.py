@@ -239,6 +239,9 @@ PROTOTYPES = {
     "pmhip_attention_maps": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, f32, i32, vp]),
     "pmhip_s2_forward_maps": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(C.c_ubyte), C.POINTER(u32), C.POINTER(f32), u64, vp, vp,
                                     vp]),
+    # cross-attention control: the edited pass of a prompt-to-prompt pair, blended from the source pass
+    "pmhip_attention_control": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "pmhip_s2_forward_control": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), u64, u64, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), vp, vp]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

@@ -214,6 +214,14 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     float* maps = nullptr;
     float maps_scale = 1.f;
     bool maps_accumulate = false;
+    // cross-attention control (pmhip_s2_forward_control only), THIS call's or NULL: device int32 / f32 / f32 [B / 2, L].
+    // The batch is B / 2 pairs, the source images in front; a layer whose set carries the arrays runs the ordinary launch on the
+    // source half and pmhip_attention_control on the edited half.  ctl_self: the edited half's first self-attention of this layer
+    // takes the source half's Q and K.
+    const int32_t* ctl_map = nullptr;
+    const float* ctl_blend = nullptr;
+    const float* ctl_gain = nullptr;
+    bool ctl_self = false;
 };
 
 // The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
@@ -429,6 +437,16 @@ int ln_heads(int dtype, TowerBufs& b, const float* g, const float* be, const voi
     return pmhip_gemm_heads_dh(dtype, b.y, dim, W, dim, M, dim, heads, dh, tokens, Np, nparts, kinds, outs, q_scale, b.split, s);
 }
 
+// A controlled layer sees B / 2 pairs: images [0, B / 2) the source passes, [B / 2, B) the edited ones.  of(): where the
+// edited half of a per-image array starts.
+struct PairHalf {
+    int half; size_t es;
+    PairHalf(int dtype, int B) : half(B / 2), es(dtype_size(dtype)) {}
+    unsigned char* of(const void* base, size_t per_image) const {
+        return const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(base)) + (size_t)half * per_image * es;
+    }
+};
+
 // one pre-LN transformer block (stage1/layers.py:54-58; stage2/transformer.py:44-49)
 int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg& tc, TowerBufs& b, int B, int tokens,
                   bool stage2, const CrossKV* cross, hipStream_t s) {
@@ -445,7 +463,15 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
         PM_TRY(ln_heads(dtype, b, L.ln1_g, L.ln1_b, L.wqkv, L.wqkv_f, L.qkv_c, L.qkv_d, M, dim, tc.heads, dh, tokens, Np, 3, kinds_qkv, outs,
                         q_scale, s));
     }
-    PM_TRY(pmhip_attention_dh(dtype, b.q, b.k, b.vt, b.attn, inner, B, tc.heads, dh, tokens, tokens, Np, fast, s));
+    if (cross && cross->ctl_self) {
+        // self-attention injection: the edited half attends with the source half's Q and K and its own V^T -- pointers only
+        const PairHalf e(dtype, B);
+        PM_TRY(pmhip_attention_dh(dtype, b.q, b.k, b.vt, b.attn, inner, e.half, tc.heads, dh, tokens, tokens, Np, fast, s));
+        PM_TRY(pmhip_attention_dh(dtype, b.q, b.k, e.of(b.vt, (size_t)tc.heads * dh * Np), e.of(b.attn, (size_t)tokens * inner), inner, e.half,
+                                  tc.heads, dh, tokens, tokens, Np, fast, s));
+    } else {
+        PM_TRY(pmhip_attention_dh(dtype, b.q, b.k, b.vt, b.attn, inner, B, tc.heads, dh, tokens, tokens, Np, fast, s));
+    }
     PM_TRY(residual_gemm(dtype, b, b.attn, inner, L.wo, inner, L.bo, self, M, dim, inner, s, L.bo_mean));
 
     if (stage2) {
@@ -461,7 +487,17 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
             a.key_seg = cross->key_seg; a.query_mask = cross->query_mask; a.key_bias = cross->key_bias;
             a.lens = a.key_seg ? nullptr : cross->lens;
             a.stream = s;
-            if (!cross->pick) {
+            if (cross->ctl_map) {
+                // the source half as ever, on its own; the edited half blends the source half's probabilities into its own
+                const PairHalf e(dtype, B);
+                a.B = e.half;
+                PM_TRY(attention_any("attention", dtype, dh, a));
+                PM_TRY(pmhip_attention_control(dtype, b.q, cross->k, e.of(b.q, (size_t)tc.heads * tokens * dh),
+                                               e.of(cross->k, (size_t)tc.heads * cross->Lp * dh), e.of(cross->vt, (size_t)tc.heads * dh * cross->Lp),
+                                               e.of(b.attn, (size_t)tokens * inner), inner, e.half, tc.heads, dh, tokens, cross->L, cross->Lp, cross->L,
+                                               cross->Lp, fast, cross->ctl_map, cross->ctl_blend, cross->ctl_gain, cross->lens,
+                                               cross->lens ? cross->lens + e.half : nullptr, s));
+            } else if (!cross->pick) {
                 PM_TRY(attention_any("attention", dtype, dh, a));
             } else {
                 // one launch per kind into one buffer, each leaving the other kinds' rows as they are: the plain
@@ -815,6 +851,7 @@ struct pmhip_s2 {
     PinnedRing neg_lens_ring;       // ... and of its negative context (neg_lens_host): B int32 -> workspace "neg.lens"
     PinnedRing w_ring;              // prompt weights: B * L f32 -> workspace "ctx.w", from where pmhip_key_bias fills "ctx.bias"
     PinnedRing seg_ring;            // regional prompts: B * tokens uint32 token masks, then B * L uint8 row segments -> workspace "ctx.seg"
+    PinnedRing ctl_ring;            // cross-attention control: row_map | blend | gain, each B * L 4-byte values -> workspace "ctl.arrays"
     PinnedRing counts_ring;         // the edit loop's re-masking counts (nmask_img_host): T * B int32 -> workspace "gen.counts"
     int slots_one_pass = 0, slots_two_pass = 0, slots_three_pass = 0;
     int slots_filter_tiles = 0, slots_filter_chain = 0;   // steps of pmhip_pipeline_step_slots_filter by the form of their sampling tail
@@ -1492,6 +1529,66 @@ extern "C" int pmhip_s2_forward_maps(pmhip_s2* h, const float* tokens, const flo
     PM_REQUIRE(maps_out, "s2_forward_maps: maps_out is NULL (pmhip_s2_forward_weights is the entry without maps)");
     return s2_forward_impl("s2_forward_maps", h, tokens, context, L, B, ctx_lens_host, logits_out, stream, ctx_seg_host, tok_seg_host, ctx_w_host,
                            layer_bits, maps_out);
+}
+
+// One eager forward over B pairs: images [0, B) carry the source prompts, [B, 2B) the edited ones.  The layers of
+// cross_bits run the edited half's cross-attention under control, the layers of self_bits its first self-attention on the source
+// half's Q and K.  Everything is checked before anything is launched; the layers' sets carry the control for this one tower only.
+extern "C" int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                        uint64_t cross_bits, uint64_t self_bits, const int32_t* row_map_host, const float* blend_host,
+                                        const float* gain_host, float* logits_out, pmhip_stream stream) {
+    const char* who = "s2_forward_control";
+    PM_REQUIRE(h && tokens && logits_out && B > 0 && B <= (1 << 20), "%s: bad arguments", who);
+    const int depth = h->cfg.tower.depth, B2 = 2 * B;
+    PM_REQUIRE(context && L > 0, "%s: the control is that of the cross-attention: a context is required", who);
+    PM_REQUIRE((cross_bits | self_bits) != 0, "%s: cross_bits and self_bits select no layer", who);
+    PM_REQUIRE(depth >= 64 || ((cross_bits | self_bits) >> depth) == 0, "%s: cross_bits 0x%llx / self_bits 0x%llx select a layer at or above depth=%d",
+               who, (unsigned long long)cross_bits, (unsigned long long)self_bits, depth);
+    const int given = (row_map_host != nullptr) + (blend_host != nullptr) + (gain_host != nullptr);
+    PM_REQUIRE(given == (cross_bits ? 3 : 0), "%s: row_map_host, blend_host and gain_host are required with cross_bits and refused without", who);
+    PM_TRY(check_ctx_lens(who, ctx_lens_host, true, L, B2));
+    const size_t n = (size_t)B * L;
+    for (size_t i = 0; cross_bits && i < n; ++i) {
+        const int b = (int)(i / L), j = (int)(i % L);
+        PM_REQUIRE(row_map_host[i] < L, "%s: pair %d: row %d: source row %d must be below L=%d (negative: none)", who, b, j, (int)row_map_host[i], L);
+        PM_REQUIRE(blend_host[i] >= 0.f && blend_host[i] <= 1.f, "%s: pair %d: row %d: blend %g must be in [0, 1]", who, b, j, (double)blend_host[i]);
+        PM_REQUIRE(std::isfinite(gain_host[i]) && gain_host[i] >= 0.f, "%s: pair %d: row %d: gain %g must be finite and >= 0", who, b, j,
+                   (double)gain_host[i]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int M = B2 * h->cfg.tokens;
+    PM_TRY(s2_prepare_context(h, context, L, B2, s));
+    PM_TRY(s2_set_ctx_lens(h, ctx_lens_host, L, B2, s));
+    unsigned char* dctl = nullptr;
+    const size_t part = (n * 4 + 15) & ~(size_t)15;
+    if (cross_bits) {
+        WS(h->ws, "ctl.arrays", 3 * part, dctl);
+        std::vector<unsigned char> packed(3 * part, 0);
+        memcpy(packed.data(), row_map_host, n * 4);
+        memcpy(packed.data() + part, blend_host, n * 4);
+        memcpy(packed.data() + 2 * part, gain_host, n * 4);
+        PM_TRY(h->ctl_ring.reserve(3 * part));
+        PM_TRY(h->ctl_ring.acquire());
+        PM_TRY(h->ctl_ring.stage(dctl, 0, packed.data(), 3 * part, s));
+        PM_TRY(h->ctl_ring.commit(s));
+    }
+    void* tp;
+    PM_TRY(tok_buf(h, M, tp, s));
+    PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
+    struct Control {                                          // cleared on every way out
+        std::vector<CrossKV>& kv;
+        ~Control() { for (auto& ck : kv) { ck.ctl_map = nullptr; ck.ctl_blend = nullptr; ck.ctl_gain = nullptr; ck.ctl_self = false; } }
+    } control{h->cross};
+    for (size_t l = 0; l < h->cross.size() && l < 64; ++l) {
+        CrossKV& ck = h->cross[l];
+        if ((cross_bits >> l) & 1) {
+            ck.ctl_map = reinterpret_cast<const int32_t*>(dctl);
+            ck.ctl_blend = reinterpret_cast<const float*>(dctl + part);
+            ck.ctl_gain = reinterpret_cast<const float*>(dctl + 2 * part);
+        }
+        ck.ctl_self = ((self_bits >> l) & 1) != 0;
+    }
+    return s2_tower(h, tp, B2, logits_out, s);
 }
 
 // The sample family's one builder: the argument list of pmhip_pipeline_sample_nucleus, the widest entry, -> the Step and the name

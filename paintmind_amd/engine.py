@@ -385,6 +385,42 @@ class S2Engine:
                   "pmhip_s2_forward_maps")
         return logits, maps
 
+    def forward_control(self, tokens, context, row_map=None, blend=None, gain=None, cross_layers=(), self_layers=(), context_lens=None):
+        """One eager forward over B pairs (pmhip_s2_forward_control): tokens [2B, tokens, E] and context
+        [2B, L, D] with the source images in front, the edited ones behind.  In the layers of cross_layers the edited half's
+        cross-attention blends the source half's probabilities into its own under row_map / blend / gain ([B, L] each, one row per
+        pair: ``ops.host_control``); in the layers of self_layers its first self-attention takes the source half's Q and K.
+        -> logits [2B, tokens, n_embed]; the source half's are those of ``forward`` on the source half alone, bit for bit."""
+        if context is None:
+            raise ValueError("forward_control: the control is that of the cross-attention: a context is required")
+        depth = self.cfg.tower.depth
+        bits = []
+        for name, layers in (("cross_layers", cross_layers), ("self_layers", self_layers)):
+            chosen = [int(l) for l in layers]
+            if len(set(chosen)) != len(chosen) or (chosen and (min(chosen) < 0 or max(chosen) >= depth)):
+                raise ValueError(f"forward_control: {name} {list(layers)!r} must be distinct indices in [0, {depth})")
+            bits.append(sum(1 << l for l in chosen))
+        if not (bits[0] | bits[1]):
+            raise ValueError("forward_control: cross_layers and self_layers select no layer")
+        tokens = tokens.to(self.device, torch.float32).contiguous()
+        if tokens.shape[0] % 2:
+            raise ValueError(f"forward_control: {tokens.shape[0]} images are no pairs")
+        B = tokens.shape[0] // 2
+        context, L = self._ctx(context)
+        lens = self._lens(context_lens, context, 2 * B, L)
+        given = [x is not None for x in (row_map, blend, gain)]
+        if any(given) != bool(bits[0]) or any(given) != all(given):
+            raise ValueError("forward_control: row_map, blend and gain are required with cross_layers and refused without")
+        ctl = (None, None, None)
+        if bits[0]:
+            rm, bl, gn = ops.host_control(row_map, blend, gain, B, L)
+            ctl = tuple(np.ctypeslib.as_ctypes(x.reshape(-1)) for x in (rm, bl, gn))
+        logits = torch.empty(2 * B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            check(self.lib.pmhip_s2_forward_control(self.handle, _p(tokens), _p(context), L, B, lens, bits[0], bits[1], ctl[0], ctl[1], ctl[2],
+                                                    _p(logits), stream_ptr(self.device)), "pmhip_s2_forward_control")
+        return logits
+
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
                want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None,
                top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None, context_weights=None):

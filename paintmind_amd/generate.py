@@ -641,6 +641,10 @@ class Pipeline(nn.Module):
         if guidance_scale is not None:
             uncond = self.tokens2logits(tok, negative, negative_lens)
             logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(guidance_scale)))
+        return self._tail_cpu(ids, logits, nm, topk, temperature, noise, seed, choice_t, choice_noise, top_p, counts)
+
+    def _tail_cpu(self, ids, logits, nm, topk, temperature, noise, seed, choice_t=0.0, choice_noise=None, top_p=1.0, counts=None):
+        """the sampling tail of ``_sample_cpu`` behind the logits: the token draw, the decode, the merge and the re-masking"""
         val, ind = logits.topk(topk, dim=-1)
         if top_p < 1.0:
             val = val.masked_fill(~nucleus_keep(val, top_p), float("-inf"))
@@ -846,6 +850,175 @@ class Pipeline(nn.Module):
         if not join:
             return parts
         return self.join_lanes(parts)
+
+    @torch.no_grad()
+    def control_ids(self, context_src, context_edit, lens_src, lens_edit, row_map, blend, gain, B, timesteps, temperature, topk, seed,
+                    image_base=0, top_p=None, choice_temperature=None, guidance_scale=None, cross_steps=0.8, self_steps=0.0, layers=None,
+                    want_imgs=False, noise=None):
+        """Prompt-to-prompt (Hertz et al.): the eager decode loop over B PAIRS of images -- one from
+        context_src [B, L, D], one from context_edit [B, L, D], both from the all-mask state under the same seed -- in which the
+        edited image's cross-attention takes the source image's probabilities for the context rows row_map pairs.
+        -> (ids_src, ids_edit), each [B, N]; with want_imgs (ids_src, ids_edit, img_src, img_edit), the images decoded from the last
+        step's predictions at ALL positions, as ``generate`` decodes its images.
+        noise (None: drawn under `seed`): the token draw's uniforms, fp32 [T, B, N, n_embed], step t's for BOTH halves -- the same on the
+        CPU branch and on the GPU, which draw their own differently.
+
+        row_map, blend, gain [B, L]: per pair, the source row of every edited row (negative: none), how much of the source's
+        probability it takes (0..1) and a factor on the result (``prompt.align_rows`` builds the first two; ``ops.attention_control``
+        has the formula).  lens_src / lens_edit (None: every row): the per-image context lengths.
+        cross_steps / self_steps: the fractions of the loop under control -- steps s < ceil(cross_steps * T) run
+        ``S2Engine.forward_control`` with the cross-attention of `layers` (None: every layer) controlled, steps s < ceil(self_steps * T)
+        also with the self-attention of those layers injected; later steps run the plain forward on the 2B images.
+        The sampling tail runs once per half with the SAME seed, step and image_base: a pair shares its noise.  A scalar
+        guidance_scale adds the pass without a context over the 2B images; that pass is never controlled.
+        ids_src is ``generate_ids(context_src, ..., use_graph=False, streams=1)`` bit for bit; with cross_steps = self_steps = 0
+        ids_edit is that of context_edit.  Whether the edited image keeps the source's layout on a MaskGIT tower is unmeasured."""
+        if context_src is None or context_edit is None or tuple(context_src.shape) != tuple(context_edit.shape) or context_src.dim() != 3 \
+                or context_src.shape[0] != B:
+            raise ValueError(f"control_ids: context_src and context_edit must be two context tensors [{B}, L, D] of one shape")
+        if guidance_scale is not None and np.ndim(guidance_scale) > 0:
+            raise ValueError("control_ids: guidance_scale is one number (a schedule is not served)")
+        if (lens_src is None) != (lens_edit is None):
+            raise ValueError("control_ids: lens_src and lens_edit come together")
+        L, T = context_src.shape[1], int(timesteps)
+        context = torch.cat([context_src, context_edit])
+        lens = None if lens_src is None else ops.host_lens(lens_src, B, L, "lens_src") + ops.host_lens(lens_edit, B, L, "lens_edit")
+        opts = self._options(topk, top_p, guidance_scale, lens, choice_temperature, context, 2 * B)
+        rm, bl, gn = ops.host_control(row_map, blend, gain, B, L)
+        depth = len(self.transformer.layers)
+        layers = list(range(depth)) if layers is None else [int(l) for l in layers]
+        if not layers or len(set(layers)) != len(layers) or min(layers) < 0 or max(layers) >= depth:
+            raise ValueError(f"control_ids: layers {layers!r} must be distinct indices in [0, {depth})")
+        for name, f in (("cross_steps", cross_steps), ("self_steps", self_steps)):
+            if not 0.0 <= float(f) <= 1.0:
+                raise ValueError(f"control_ids: {name}={f} must be a fraction in [0, 1]")
+        n_cross, n_self = math.ceil(float(cross_steps) * T), math.ceil(float(self_steps) * T)
+        temps, nmask, ctemps = loop_schedule(T, temperature, self.num_tokens, opts.choice_temperature)
+        cpu = self._on_cpu()
+        dev = self.mask_token.device if cpu else self.engine().device
+        N = self.num_tokens
+        context = context.to(dev)
+        ids = torch.full((2 * B, N), self.mask_token_id, dtype=torch.long, device=dev)
+        imgs = [None, None]
+        if noise is not None and tuple(noise.shape) != (T, B, N, self.mask_token_id):
+            raise ValueError(f"control_ids: noise must be a tensor [{T}, {B}, {N}, {self.mask_token_id}], got {tuple(noise.shape)}")
+        for step in range(T):
+            last = want_imgs and step == T - 1
+            cross = layers if step < n_cross else []
+            inject = layers if step < n_self else []
+            ctl = dict(row_map=rm, blend=bl, gain=gn) if cross else {}
+            tok = self.ids2tokens(ids)
+            ct = ctemps[step] if ctemps else 0.0
+            if cpu:
+                if cross or inject:
+                    logits = self.transformer(tok, context, context_lens=opts.lens, control=dict(cross_layers=cross, self_layers=inject, **ctl))
+                else:
+                    logits = self.tokens2logits(tok, context, opts.lens)
+                if opts.guidance_scale is not None:
+                    uncond = self.tokens2logits(tok, None)
+                    logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(opts.guidance_scale)))
+                halves = [self._tail_cpu(ids[h * B:(h + 1) * B], logits[h * B:(h + 1) * B], nmask[step], opts.topk, temps[step],
+                                         None if noise is None else noise[step], None if seed is None else seed + step, ct, None, opts.top_p,
+                                         counts=None if last else [nmask[step]] * B)              # (counts: the same re-masking, no decode)
+                          for h in range(2)]
+                ids, imgs = torch.cat([h[0] for h in halves]), [h[1] for h in halves]
+                continue
+            eng = self.engine()
+            if cross or inject:
+                logits = eng.forward_control(tok, context, cross_layers=cross, self_layers=inject, context_lens=opts.lens, **ctl)
+            else:
+                logits = eng.forward(tok, context, context_lens=opts.lens)
+            if opts.guidance_scale is not None:
+                logits = ops.guidance_combine(logits, eng.forward(tok, None), opts.guidance_scale, out=logits)
+            for h in range(2):
+                rows = slice(h * B * N, (h + 1) * B * N)
+                pred, merged, score = ops.sample_rows(logits.reshape(2 * B * N, -1)[rows], ids.reshape(-1)[rows], self.mask_token_id, opts.topk,
+                                                   temps[step], seed=seed, step=step, row_base=image_base * N, top_p=opts.top_p,
+                                                   noise=None if noise is None else noise[step].to(dev, torch.float32).reshape(B * N, -1).contiguous())
+                ids[h * B:(h + 1) * B] = ops.remask(merged.reshape(B, N), score.reshape(B, N), nmask[step], self.mask_token_id,
+                                                    choice_temperature=ct, seed=seed, step=step, row_base=image_base * N)
+                if last:
+                    imgs[h] = self.vqgan.decode_from_indice(pred.reshape(B, N))
+        if want_imgs:
+            return ids[:B].clone(), ids[B:].clone(), imgs[0], imgs[1]
+        return ids[:B].clone(), ids[B:].clone()
+
+    @torch.no_grad()
+    def prompt_to_prompt(self, text, edit_text, mode="refine", reweight=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_base=0,
+                         top_p=None, choice_temperature=None, guidance_scale=None, cross_steps=0.8, self_steps=0.0, layers=None,
+                         return_ids=False, **refused):
+        """Change the prompt, keep the picture (Hertz et al., Prompt-to-Prompt): -> (img_src, img_edit), the
+        image of `text` and the image of `edit_text` from one seed, the second attending with the first's cross-attention for the
+        words the prompts share; ids with return_ids.  text / edit_text: a prompt each, or two lists of as many.
+
+        mode 'refine' (words added or removed) or 'replace' (a word swapped): ``prompt.align_rows``.  reweight {phrase: gain}: the
+        rows of that phrase of `edit_text` -- found as ``phrase_rows`` finds them, in every edited prompt that has it (once) -- are
+        scaled by gain (>= 0); edit_text == text
+        with a reweight is the paper's pure re-weighting.  Always under the non-pad lengths, as ``phrase_mask``.  The other
+        keywords are those of ``control_ids``.  Not served (ValueError): negative_text, regions, prompt_weights / context_weights,
+        the segment arrays, a guidance schedule, an unconditional pipeline.  Image quality on this tower is unmeasured."""
+        if refused:
+            raise ValueError(f"prompt_to_prompt does not serve {sorted(refused)} (negative prompts, regions, prompt weights and the segment "
+                             f"arrays stand beside no attention control)")
+        if guidance_scale is not None and np.ndim(guidance_scale) > 0:
+            raise ValueError("prompt_to_prompt: guidance_scale is one number (a schedule is not served)")
+        if getattr(self, "text_model", None) is None or text is None or edit_text is None:
+            raise ValueError("prompt_to_prompt needs a text condition (an unconditional pipeline has no cross-attention to control)")
+        if not hasattr(self.text_model, "fragment_ids"):
+            raise NotImplementedError(f"{type(self.text_model).__name__} serves no token ids (fragment_ids): T5TextEmbedder does")
+        from .prompt import align_rows
+        src = [text] if isinstance(text, str) else list(text)
+        tgt = [edit_text] if isinstance(edit_text, str) else list(edit_text)
+        if len(src) != len(tgt) or not src:
+            raise ValueError(f"prompt_to_prompt: {len(src)} prompts and {len(tgt)} edited prompts")
+        reweight = dict(reweight or {})
+        for phrase, g in reweight.items():
+            if not isinstance(phrase, str) or not phrase.strip() or not (math.isfinite(float(g)) and float(g) >= 0):
+                raise ValueError(f"prompt_to_prompt: reweight {phrase!r}: {g!r} must be a phrase and a finite gain >= 0")
+
+        def cut(prompt, strict):
+            """the prompt cut at the single occurrence of every phrase -> (fragments, the gain of each or None)"""
+            found = []
+            for phrase, g in reweight.items():
+                if prompt.count(phrase) == 0:
+                    continue                                     # (a phrase of another prompt of the batch)
+                if prompt.count(phrase) != 1:
+                    if strict:
+                        raise ValueError(f"prompt_to_prompt: the phrase {phrase!r} occurs {prompt.count(phrase)} times in {prompt!r}, not once")
+                    return [prompt], [None]
+                found.append((prompt.index(phrase), phrase, float(g)))
+            found.sort()
+            frags, gains, at = [], [], 0
+            for pos, phrase, g in found:
+                if pos < at:
+                    raise ValueError(f"prompt_to_prompt: the phrases of reweight overlap in {prompt!r}")
+                frags += [prompt[at:pos], phrase]
+                gains += [None, g]
+                at = pos + len(phrase)
+            return frags + [prompt[at:]], gains + [None]
+
+        B = len(src)
+        for phrase in reweight:
+            if not any(phrase in p for p in tgt):
+                raise ValueError(f"prompt_to_prompt: the phrase {phrase!r} of reweight occurs in no edited prompt")
+        cuts = [cut(p, False) for p in src] + [cut(p, True) for p in tgt]
+        context, lens, ids, spans = self.text_model.fragment_ids([c[0] for c in cuts])
+        L = context.shape[1]
+        lens = [int(n) for n in lens]
+        rm, bl, gn = np.full((B, L), -1, np.int32), np.zeros((B, L), np.float32), np.ones((B, L), np.float32)
+        for b in range(B):
+            m, w = align_rows(ids[b], ids[B + b], mode)
+            rm[b, :len(m)], bl[b, :len(w)] = m, w
+            for (lo, hi), g in zip(spans[B + b], cuts[B + b][1]):
+                if g is not None:
+                    if hi <= lo:
+                        raise ValueError(f"prompt_to_prompt: a phrase of reweight has no tokens below max_length in {tgt[b]!r}")
+                    gn[b, lo:hi] = g
+        context = context.to(self.mask_token.device, torch.float32)
+        out = self.control_ids(context[:B], context[B:], lens[:B], lens[B:], rm, bl, gn, B, timesteps, temperature, topk,
+                               _draw_seed() if seed is None else seed, image_base, top_p, choice_temperature, guidance_scale, cross_steps,
+                               self_steps, layers, want_imgs=not return_ids)
+        return out if return_ids else out[2:]
 
     def join_lanes(self, parts):
         """make the current stream wait for the lanes and concatenate their results"""

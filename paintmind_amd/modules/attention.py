@@ -61,7 +61,7 @@ class CrossAttention(nn.Module):
                         token_segments=token_segments, context_weights=context_weights)
 
     def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
-            want_maps=False):
+            want_maps=False, control=None, inject_self=False):
         """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x.
         want_maps (extension, attention maps): -> (that, maps) with maps f32 [B, N, L], the mean over the heads
         of this call's softmax probabilities -- exactly 0 where a row takes no part; it needs a context.
@@ -71,7 +71,19 @@ class CrossAttention(nn.Module):
         b's context belongs to segment context_segments[b, k] (0..31; -1 or 255 = padding, which never reaches the result), and
         token t attends to the rows whose segment is a set bit of token_segments[b, t].  Every token must allow a present segment.
         context_weights [B, L] (extension, prompt weights; beside the segment arrays, beside context_lens, or alone): over the rows
-        a token attends to, p = w exp(s) / sum w exp(s).  A weight of 0 makes the row padding; otherwise 2^-20 <= w <= 2^20."""
+        a token attends to, p = w exp(s) / sum w exp(s).  A weight of 0 makes the row padding; otherwise 2^-20 <= w <= 2^20.
+        control (extension, prompt-to-prompt): (row_map, blend, gain), each [B / 2, L] -- the batch is B / 2 pairs,
+        the source images in front; the edited half attends with P = gain (has ? (1 - blend) pt + blend ps[row_map] : pt), ps the source
+        half's probabilities (``ops.attention_control``).  It needs a context and stands beside context_lens only.
+        inject_self (the same extension, a self-attention): the edited half attends with the source half's Q and K and its own V."""
+        if control is not None:
+            if context is None or context_segments is not None or token_segments is not None or context_weights is not None or want_maps:
+                raise ValueError("control needs a context and stands beside context_lens only")
+            if x.shape[0] % 2:
+                raise ValueError(f"control: {x.shape[0]} images are no pairs")
+            control = ops.host_control(*control, x.shape[0] // 2, context.shape[1])
+        if inject_self and (context is not None or x.shape[0] % 2):
+            raise ValueError("inject_self is for the self-attention of a batch of pairs")
         if self.training and self.to_out[1].p > 0:
             raise RuntimeError("paintmind_amd attention is inference-only (dropout>0 in training mode)")
         if context_lens is not None:
@@ -98,6 +110,8 @@ class CrossAttention(nn.Module):
         if want_maps and context is None:
             raise ValueError("want_maps: the maps are those of a cross-attention: a context is required")
         if not x.is_cuda:
+            if control is not None or inject_self:
+                return self._run_cpu(x, context, residual, context_lens, control=control, inject_self=inject_self)
             if want_maps:
                 return self._run_cpu(x, context, residual, context_lens, segments, weights, want_maps=True)
             return self._run_cpu(x, context, residual, context_lens, segments, weights)
@@ -125,7 +139,20 @@ class CrossAttention(nn.Module):
                         key_weights=None if weights is None else torch.from_numpy(weights).to(x.device))
         else:
             form = dict(kv_lens=kv_lens)
-        o = ops.attention(q, k, vt, n_kv, use_exp2=fast, **form)
+        if control is not None or inject_self:
+            # a batch of pairs: the source half as ever, on its own; the edited half under control / on the source half's Q and K
+            h2 = B // 2
+            o = torch.empty(B * N, self.heads * self.dim_head, device=x.device, dtype=dtype)
+            o[:h2 * N] = ops.attention(q[:h2], k[:h2], vt[:h2], n_kv, use_exp2=fast, kv_lens=None if kv_lens is None else kv_lens[:h2])
+            if inject_self:
+                o[h2 * N:] = ops.attention(q[:h2], k[:h2], vt[h2:], n_kv, use_exp2=fast)
+            else:
+                rm, bl, gn = (torch.from_numpy(c).to(x.device) for c in control)
+                ops.attention_control(q[:h2], k[:h2], q[h2:], k[h2:], vt[h2:], n_kv, n_kv, rm, bl, gn, use_exp2=fast,
+                                      lens_src=None if kv_lens is None else kv_lens[:h2].contiguous(),
+                                      lens_tgt=None if kv_lens is None else kv_lens[h2:].contiguous(), out=o[h2 * N:])
+        else:
+            o = ops.attention(q, k, vt, n_kv, use_exp2=fast, **form)
         res = residual.reshape(B * N, D) if residual is not None else None
         out_dtype = torch.float32 if residual is not None else dtype
         out = ops.gemm(o, pk["wo"], bias=pk["bo"], residual=res, out_dtype=out_dtype)
@@ -134,7 +161,8 @@ class CrossAttention(nn.Module):
         return out.reshape(B, N, D)
 
 
-    def _run_cpu(self, x, context, residual, context_lens=None, segments=None, weights=None, want_maps=False):
+    def _run_cpu(self, x, context, residual, context_lens=None, segments=None, weights=None, want_maps=False, control=None,
+                 inject_self=False):
         """Parameters on the CPU: the same operator in plain torch (reference modules/attention.py:43-59; BASELINE config 1
         runs the model there).  q is scaled BEFORE the product (:52), no mask, softmax over the keys, head split 'b n (h d)'.
         context_lens (a checked list, or None): scores of the keys at or beyond an image's length become -inf (whatever they
@@ -143,16 +171,21 @@ class CrossAttention(nn.Module):
         does not attend to become -inf, and the V rows of padding (segment 255) are zeroed.
         weights (checked numpy float32 [B, L] beside segments, or None): log w is added to the scores of the rows with w > 0; a row
         with w == 0 is padding.
-        want_maps: -> (the result, p.mean(heads) f32 [B, N, L]): the probabilities of this very softmax, 0 where a row takes no part."""
+        want_maps: -> (the result, p.mean(heads) f32 [B, N, L]): the probabilities of this very softmax, 0 where a row takes no part.
+        control (checked numpy (int32, float32, float32) [B / 2, L], or None): the edited half's probabilities become
+        gain (has ? (1 - blend) pt + blend ps[row_map] : pt), ps the source half's, has = 0 <= row_map < the source length and
+        blend != 0; no renormalisation.  inject_self: the edited half's q and k are the source half's."""
         B, N, _ = x.shape
         c = x if context is None else context
         L = c.shape[1]
-        if context_lens is not None and len(set(context_lens)) == 1:
+        if context_lens is not None and len(set(context_lens)) == 1 and control is None:
             c, context_lens = c[:, :context_lens[0]], None       # one length for the batch (B = 1 always): cut the padding off
         h, d = self.heads, self.dim_head
         q = (F.linear(x, self.to_q.weight) * self.scale).reshape(B, N, h, d).permute(0, 2, 1, 3)
         k = F.linear(c, self.to_k.weight).reshape(B, c.shape[1], h, d).permute(0, 2, 1, 3)
         v = F.linear(c, self.to_v.weight).reshape(B, c.shape[1], h, d).permute(0, 2, 1, 3)
+        if inject_self:
+            q, k = torch.cat([q[:B // 2]] * 2), torch.cat([k[:B // 2]] * 2)
         s = q @ k.transpose(-1, -2)
         if context_lens is not None:
             pad = torch.arange(c.shape[1])[None, :] >= torch.tensor(context_lens)[:, None]           # [B, L]
@@ -169,6 +202,14 @@ class CrossAttention(nn.Module):
             s = s.masked_fill(off[:, None, None, :], float("-inf"))
             v = v.masked_fill(off[:, None, :, None], 0.0)
         p = torch.softmax(s, dim=-1)
+        if control is not None:
+            h2 = B // 2
+            rm, bl, gn = (torch.from_numpy(c) for c in control)
+            ns = torch.tensor(context_lens[:h2] if context_lens is not None else [L] * h2)
+            has = (rm >= 0) & (rm < ns[:, None]) & (bl != 0)                                            # [B / 2, L]
+            ps = torch.gather(p[:h2], -1, torch.where(has, rm, 0).long()[:, None, None, :].expand_as(p[h2:]))
+            bl, gn = bl.to(p.dtype)[:, None, None, :], gn.to(p.dtype)[:, None, None, :]
+            p = torch.cat([p[:h2], gn * torch.where(has[:, None, None, :], (1 - bl) * p[h2:] + bl * ps, p[h2:])])
         o = (p @ v).permute(0, 2, 1, 3).reshape(B, N, h * d)
         out = F.linear(o, self.to_out[0].weight, self.to_out[0].bias)
         out = out if residual is None else out + residual

@@ -146,6 +146,37 @@ class T5TextEmbedder(nn.Module):
         context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
         return context, lens, rows
 
+    @torch.no_grad()
+    def fragment_ids(self, fragments):
+        """Token ids without a second tower call (``Pipeline.prompt_to_prompt``).  fragments[b]: the strings
+        prompt b is cut into (their concatenation is the prompt).  They are tokenised one by one WITHOUT special tokens, exactly as
+        ``phrase_rows`` and ``_forward_weighted`` tokenise theirs, the ids are concatenated, closed with the end-of-sequence id and
+        truncated or padded to max_length, and the context is ONE tower call on them -- so a fragment that is a phrase sits in the rows
+        ``phrase_rows`` finds for it.
+        -> (context (B, max_length, d_model), lens int32 [B] on the host, ids: per prompt the list of its lens[b] token ids, spans: per
+        prompt the (first row, row behind the last) of every fragment, cut off at the end-of-sequence row)"""
+        eos = getattr(self.tokenizer, "eos_token_id", None)
+        eos = 1 if eos is None else int(eos)
+        pad = _pad_id(self.tokenizer)
+        B, L = len(fragments), self.max_length
+        ids = torch.full((B, L), pad, dtype=torch.long)
+        lens = torch.zeros(B, dtype=torch.int32)
+        rows, spans = [], []
+        for b, frags in enumerate(fragments):
+            row, span = [], []
+            for frag in frags:
+                piece = self.tokenizer(frag, add_special_tokens=False)["input_ids"] if frag else []
+                piece = [int(t) for t in (piece.reshape(-1).tolist() if hasattr(piece, "reshape") else piece)]
+                span.append((min(len(row), L - 1), min(len(row) + len(piece), L - 1)))
+                row += piece
+            row = row[:L - 1] + [eos]
+            ids[b, :len(row)] = torch.tensor(row, dtype=torch.long)
+            lens[b] = len(row)
+            rows.append(row)
+            spans.append(span)
+        context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
+        return context, lens, rows, spans
+
     def encode(self, text):
         return self(text)
 
@@ -201,6 +232,9 @@ class CLIPTextEmbedder(nn.Module):
 
     def phrase_rows(self, text, phrases):
         raise NotImplementedError("CLIPTextEmbedder serves no phrase rows (phrase_rows): T5TextEmbedder does")
+
+    def fragment_ids(self, fragments):
+        raise NotImplementedError("CLIPTextEmbedder serves no token ids (fragment_ids): T5TextEmbedder does")
 
     def encode_with_transformer(self, tokens):
         m = self.model
@@ -261,3 +295,6 @@ class SyntheticTextEmbedder(nn.Module):
 
     def phrase_rows(self, text, phrases):
         raise NotImplementedError("SyntheticTextEmbedder has no tokenizer and serves no phrase rows (phrase_rows): T5TextEmbedder does")
+
+    def fragment_ids(self, fragments):
+        raise NotImplementedError("SyntheticTextEmbedder has no tokenizer and serves no token ids (fragment_ids): T5TextEmbedder does")

@@ -66,6 +66,27 @@ def host_lens(lens, B, L, what="context_lens"):
     return out
 
 
+def host_control(row_map, blend, gain, B, L):
+    """cross-attention control: row_map [B, L] ints (the source row of every edited row, negative: none), blend
+    [B, L] in [0, 1] and gain [B, L] finite and >= 0, as lists, numpy arrays, CPU or device tensors -> contiguous numpy (int32,
+    float32, float32) on the host, brought there ONCE per call and checked before anything is launched"""
+    to_np = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+    rm, bl, gn = to_np(row_map), to_np(blend), to_np(gain)
+    if rm.shape != (B, L) or rm.dtype.kind not in "iu":
+        raise ValueError(f"row_map must be integers of shape ({B}, {L}), got {rm.dtype} {rm.shape}")
+    for name, x in (("blend", bl), ("gain", gn)):
+        if x.shape != (B, L) or x.dtype.kind not in "fiu":
+            raise ValueError(f"{name} must be numbers of shape ({B}, {L}), got {x.dtype} {x.shape}")
+    bl, gn = bl.astype(np.float32), gn.astype(np.float32)
+    if rm.size and rm.max() >= L:
+        raise ValueError(f"row_map: source row {int(rm.max())} must be below L={L} (negative: none)")
+    if not ((bl >= 0) & (bl <= 1)).all():
+        raise ValueError("blend must be in [0, 1]")
+    if not (np.isfinite(gn) & (gn >= 0)).all():
+        raise ValueError("gain must be finite and >= 0")
+    return np.ascontiguousarray(np.maximum(rm, -1).astype(np.int32)), np.ascontiguousarray(bl), np.ascontiguousarray(gn)
+
+
 def host_segments(context_segments, token_segments, B, L, N):
     """regional prompts: context_segments [B, L] ints (the segment 0..31 of every context row; -1 or 255 =
     padding) and token_segments [B, N] int bitmasks (bit s = the token attends to segment s), as lists, numpy arrays, CPU or device
@@ -566,6 +587,44 @@ def attention_maps(q, k, n_kv, use_exp2=False, kv_lens=None, key_segments=None, 
         check(lib.pmhip_attention_maps(pm_dtype(q.dtype), _p(q), _p(k), _p(out), out.stride(1), B, H, dh, Nq, n_kv, nkp, int(bool(use_exp2)),
                                        _p(kv_lens), _p(key_segments), _p(query_segments), _p(bias), float(scale), int(bool(accumulate)),
                                        stream_ptr(dev)), "pmhip_attention_maps")
+    return out
+
+
+def attention_control(qs, ks, qt, kt, vt, n_src, n_tgt, row_map, blend, gain, use_exp2=False, lens_src=None, lens_tgt=None, out=None):
+    """The edited pass of a prompt-to-prompt pair (pmhip_attention_control): qs [B,H,Nq,dh], ks [B,H,Lsp,dh] the
+    source pass, qt, kt [B,H,Ltp,dh], vt [B,H,dh,Ltp] the edited one -> [B*Nq, H*dh] with
+        P[q, j] = gain[b, j] * (has ? (1 - blend[b, j]) * pt[q, j] + blend[b, j] * ps[q, row_map[b, j]] : pt[q, j]),   out = P V
+    ps / pt the softmaxes of the two passes over their first lens_src[b] / lens_tgt[b] keys (None: n_src / n_tgt; clamped by the
+    kernel as in ``attention``), has = 0 <= row_map[b, j] < the source length and blend[b, j] != 0.  No renormalisation.
+    row_map int32, blend and gain float32, all contiguous [B, n_tgt] on the device; the ranges (blend in [0, 1], gain finite and
+    >= 0) are the caller's to keep.  out (None: a new tensor): [B*Nq, H*dh] of q's dtype with unit column stride; its row stride is
+    the leading dimension.  -> out"""
+    dev = _dev(qs, ks, qt, kt, vt, row_map, blend, gain, lens_src, lens_tgt)      # (every one of them on the device and contiguous)
+    lib = _lib.load()
+    B, H, Nq, dh = qt.shape
+    if tuple(qs.shape) != (B, H, Nq, dh) or qs.dtype != qt.dtype:
+        raise ValueError(f"qs must be a {qt.dtype} {(B, H, Nq, dh)} tensor like qt, got {qs.dtype} {tuple(qs.shape)}")
+    lsp, ltp = ks.shape[2], kt.shape[2]
+    for name, x, want in (("ks", ks, (B, H, lsp, dh)), ("kt", kt, (B, H, ltp, dh)), ("vt", vt, (B, H, dh, ltp))):
+        if x.dtype != qt.dtype or tuple(x.shape) != want:
+            raise ValueError(f"{name} must be a {qt.dtype} {want} tensor, got {x.dtype} {tuple(x.shape)}")
+    if lsp < n_src or ltp < n_tgt:
+        raise ValueError(f"n_src={n_src} / n_tgt={n_tgt} exceed the padded contexts {lsp} / {ltp}")
+    for name, x, dt in (("row_map", row_map, torch.int32), ("blend", blend, torch.float32), ("gain", gain, torch.float32)):
+        if x is None or x.dtype != dt or tuple(x.shape) != (B, n_tgt):
+            raise ValueError(f"{name} must be a {dt} tensor of shape ({B}, {n_tgt})")
+    for name, x in (("lens_src", lens_src), ("lens_tgt", lens_tgt)):
+        if x is not None and (x.dtype != torch.int32 or tuple(x.shape) != (B,)):
+            raise ValueError(f"{name} must be an int32 tensor of shape ({B},), got {x.dtype} {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(B * Nq, H * dh, device=dev, dtype=qt.dtype)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == qt.dtype and
+            tuple(out.shape) == (B * Nq, H * dh) and out.stride(1) == 1 and out.stride(0) >= H * dh):
+        raise ValueError(f"out must be a {qt.dtype} [{B * Nq}, {H * dh}] tensor on the operands' device with unit column stride")
+    with torch.cuda.device(dev):
+        check(lib.pmhip_attention_control(pm_dtype(qt.dtype), _p(qs), _p(ks), _p(qt), _p(kt), _p(vt), _p(out), out.stride(0), B, H, dh, Nq,
+                                          int(n_src), lsp, int(n_tgt), ltp, int(bool(use_exp2)), _p(row_map), _p(blend), _p(gain),
+                                          _p(lens_src), _p(lens_tgt), stream_ptr(dev)), "pmhip_attention_control")
     return out
 
 

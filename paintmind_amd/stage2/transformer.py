@@ -21,17 +21,23 @@ class Layer(nn.Module):
         self.norm3 = nn.LayerNorm(dim)
         self.ffnet = SwiGLUFFNFused(in_features=dim, hidden_features=mlp_dim)
 
-    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, want_maps=False):
+    def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, want_maps=False,
+                control=None, inject_self=False):
         """self-attn, cross-attn (a 2nd self-attn when context is None), SwiGLU (transformer.py:44-49).
         want_maps: -> (x, maps), maps f32 [B, N, L] the head-mean probabilities of the cross-attention (modules/attention.py).
         context_lens: per-image context lengths for the cross-attention only (modules/attention.py).
         context_segments / token_segments: regional prompts, for the cross-attention only (modules/attention.py).
-        context_weights: prompt weights, for the cross-attention only (modules/attention.py)."""
+        context_weights: prompt weights, for the cross-attention only (modules/attention.py).
+        control / inject_self: prompt-to-prompt on a batch of pairs, the cross-attention's control and the injection into the first
+        self-attention (modules/attention.py)."""
         B, N, D = x.shape
         T = compute_dtype_of(self)
         x = x.contiguous()
-        x = self.attn1.run(_norm(x.reshape(B * N, D), self.norm1, T).reshape(B, N, D), None, residual=x)
+        x = self.attn1.run(_norm(x.reshape(B * N, D), self.norm1, T).reshape(B, N, D), None, residual=x,
+                           **(dict(inject_self=True) if inject_self else {}))
         kw = dict(want_maps=True) if want_maps else {}
+        if control is not None:
+            kw["control"] = control
         x = self.attn2.run(_norm(x.reshape(B * N, D), self.norm2, T).reshape(B, N, D), context, residual=x,
                            context_lens=context_lens if context is not None else None,
                            context_segments=context_segments if context is not None else None,
@@ -58,8 +64,13 @@ class CondTransformer(nn.Module):
         self.to_logits = nn.Linear(dim, num_classes)
         _xavier_like_reference(self)
 
-    def _layers(self, h, maps_layers, *args):
-        """the tower; maps_layers (None, or the checked layer indices): -> (h, the mean of those layers' cross-attention maps)"""
+    def _layers(self, h, maps_layers, *args, control=None):
+        """the tower; maps_layers (None, or the checked layer indices): -> (h, the mean of those layers' cross-attention maps);
+        control (None, or per controlled layer its keywords): prompt-to-prompt, never beside maps_layers"""
+        if control is not None:
+            for i, layer in enumerate(self.layers):
+                h = layer(h, *args, **control.get(i, {}))
+            return h
         if maps_layers is None:
             for layer in self.layers:
                 h = layer(h, *args)
@@ -74,7 +85,7 @@ class CondTransformer(nn.Module):
         return h, maps / len(maps_layers)
 
     def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
-                maps_layers=None):
+                maps_layers=None, control=None):
         """operator-level composition of transformer.py:80-93 (Pipeline uses the native engine instead).
         maps_layers (extension, attention maps; None = the call as without it): distinct layer indices ->
         (logits, maps), the logits as without it and maps f32 [B, N, L], the mean over those layers of the head-mean probabilities
@@ -82,7 +93,23 @@ class CondTransformer(nn.Module):
         context_lens (extension; None = the reference's behaviour): image b's cross-attention sees rows [0, context_lens[b]) of
         its context only.  The context projection still covers every row: it is row-local, so padding stays in the padding.
         context_segments [B, L] / token_segments [B, N] (extension, regional prompts): see ``CrossAttention.run``.
-        context_weights [B, L] (extension, prompt weights; beside the segments, beside context_lens, or alone): likewise."""
+        context_weights [B, L] (extension, prompt weights; beside the segments, beside context_lens, or alone): likewise.
+        control (extension, prompt-to-prompt; None = the call as without it): a dict with row_map, blend, gain
+        ([B / 2, L]; required iff cross_layers), cross_layers and self_layers (distinct layer indices) over a batch of B / 2 pairs, the
+        source images in front -- ``S2Engine.forward_control`` as a composition of operators.  Beside context_lens only."""
+        if control is not None:
+            if context is None or context_segments is not None or token_segments is not None or context_weights is not None or \
+                    maps_layers is not None or x.shape[0] % 2:
+                raise ValueError("control needs a context and an even batch, and stands beside context_lens only")
+            cl, sl = [int(l) for l in control.get("cross_layers", ())], [int(l) for l in control.get("self_layers", ())]
+            for ls in (cl, sl):
+                if len(set(ls)) != len(ls) or (ls and (min(ls) < 0 or max(ls) >= len(self.layers))):
+                    raise ValueError(f"control: layers {ls!r} must be distinct indices in [0, {len(self.layers)})")
+            arrays = [control.get(k) for k in ("row_map", "blend", "gain")]
+            if not (cl or sl) or any(a is None for a in arrays) != (not cl) or any(a is None for a in arrays) != all(a is None for a in arrays):
+                raise ValueError("control: a layer must be chosen; row_map, blend and gain are required with cross_layers and refused without")
+            ctl = ops.host_control(*arrays, x.shape[0] // 2, context.shape[1]) if cl else None
+            control = {l: (dict(control=ctl) if l in cl else {}) | (dict(inject_self=True) if l in sl else {}) for l in set(cl) | set(sl)}
         if context_lens is not None:
             if context is None:
                 raise ValueError("context_lens needs a context (context None IS the unconditional branch)")
@@ -114,7 +141,7 @@ class CondTransformer(nn.Module):
             h = self.token_proj(x.float()) + self.position_embedding
             if context is not None:
                 context = self.context_proj(context.float())
-            h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights)
+            h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights, control=control)
             if maps_layers is not None:
                 return self.to_logits(self.norm(h[0])), h[1]
             return self.to_logits(self.norm(h))
@@ -128,7 +155,7 @@ class CondTransformer(nn.Module):
             if isinstance(self.context_proj, nn.Linear):
                 c = ops.gemm(c, packing.pad_cols(self.context_proj.weight, c.shape[1], T))
             context = c.reshape(B, L, dim)
-        h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights)
+        h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights, control=control)
         maps = None
         if maps_layers is not None:
             h, maps = h
