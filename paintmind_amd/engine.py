@@ -18,6 +18,27 @@ def _f32(t):
     return t.detach().float().contiguous()
 
 
+def _c_ints(vals):
+    """a host list of ints (or None) -> a ctypes int32 array (or None: NULL)"""
+    return None if vals is None else (C.c_int * len(vals))(*vals)
+
+
+def _key_args(keys, native_lens=True):
+    """a checked ``ops.Keys`` -> the ctypes arguments (ctx_lens_host int32 [B], ctx_seg_host uint8 [B * L], tok_seg_host uint32
+    [B * tokens], ctx_w_host float32 [B * L]), None where the entry takes NULL.  The neutral segments of weights without segment
+    arrays are not handed over: the native entry stages them itself from the lengths -- except one that takes no lengths
+    (native_lens False), which gets them from here when there are lengths."""
+    lens, cs, ts = keys.lens, keys.context_segments, keys.token_segments
+    if cs is None:
+        return _c_ints(lens), None, None, None
+    flat = lambda a: None if a is None else np.ctypeslib.as_ctypes(np.ascontiguousarray(a).reshape(-1))
+    if keys.neutral:
+        lens = keys.neutral_lens if native_lens else None
+        if native_lens or keys.neutral_lens is None:
+            cs = ts = None
+    return _c_ints(lens), flat(cs), flat(ts), flat(keys.weights)
+
+
 class _Keep:
     """keeps packed tensors alive for as long as the native handle points at them"""
 
@@ -295,93 +316,53 @@ class S2Engine:
             raise ValueError(f"context width {context.shape[-1]} != context_dim {self.context_dim}")
         return context, context.shape[1]
 
-    @staticmethod
-    def _lens(context_lens, context, B, L):
-        """context_lens (list / CPU tensor / device tensor / None) -> a ctypes int32 [B] for ctx_lens_host, or None; checked here
-        (1 <= len <= L, one per image) and again by the native entry"""
-        if context_lens is None:
-            return None
-        if context is None and L == 0:
-            raise ValueError("context_lens needs a context (context None IS the unconditional branch)")
-        vals = ops.host_lens(context_lens, B, L)
-        return (C.c_int * B)(*vals)
+    def _keys(self, B, L, context_lens=None, context_segments=None, token_segments=None, context_weights=None, keys=None):
+        """the four keywords of an entry point, or the record that stands for them -> the call's ``ops.Keys``: checked here, at the
+        door, unless it comes checked (and once more by the native entry).  L == 0: there is no context."""
+        return ops.host_keys(B, L, self.tokens, context_lens, context_segments, token_segments, context_weights, has_context=L > 0, keys=keys)
 
-    def _segments(self, context_segments, token_segments, context, context_lens, B, L):
-        """regional prompts: context_segments [B, L] (the segment 0..31 of every context row, -1 / 255 =
-        padding) and token_segments [B, tokens] (bit masks) -> (ctypes uint8 [B * L], ctypes uint32 [B * tokens]) for ctx_seg_host /
-        tok_seg_host, or None; checked here (``ops.host_segments``) and again by the native entry"""
-        if context_segments is None and token_segments is None:
-            return None
-        if context is None and L == 0:
-            raise ValueError("context_segments / token_segments need a context (context None IS the unconditional branch)")
-        if context_lens is not None:
-            raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
-        cs, ts = ops.host_segments(context_segments, token_segments, B, L, self.tokens)
-        return (np.ctypeslib.as_ctypes(cs.reshape(-1)), np.ctypeslib.as_ctypes(ts.reshape(-1)))
+    def _call(self, table, head, tail=()):
+        """the native call of an entry family: `table` is ordered (condition, entry name, trailing arguments); the first row whose
+        condition holds is called with head + its trailing arguments + tail -- an entry gets what it declares, no wider one stands in"""
+        for cond, name, extra in table:
+            if cond:
+                return check(getattr(self.lib, name)(*head, *extra, *tail), name)
 
-    def _weights(self, context_weights, context_segments, token_segments, context, context_lens, B, L, native_lens=True):
-        """prompt weights: context_weights [B, L] (None = the call as without them) -> (seg, w) with
-        seg = the pair of ``_segments`` or (None, None) and w a ctypes float32 [B * L] for ctx_w_host, or None; checked here
-        (``ops.host_weights``) and again by the native entry.  Without segment arrays the native entry stages the neutral ones from
-        ctx_lens_host; an entry without that argument (native_lens False) gets them from here when there are lengths."""
-        if context_weights is None:
-            return None
-        if context is None and L == 0:
-            raise ValueError("context_weights need a context (context None IS the unconditional branch)")
-        cs, ts, w = ops.host_weights(context_weights, B, L, self.tokens, context_segments, token_segments, context_lens)
-        given = context_segments is not None or (context_lens is not None and not native_lens)
-        seg = (np.ctypeslib.as_ctypes(cs.reshape(-1)), np.ctypeslib.as_ctypes(ts.reshape(-1))) if given else (None, None)
-        return seg, np.ctypeslib.as_ctypes(w.reshape(-1))
-
-    def forward(self, tokens, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
-        """context_segments / token_segments (None = the call as without them): regional prompts, see ``_segments``
-        (pmhip_s2_forward_segments).  context_weights (None = the call as without them): prompt weights, see ``_weights``
-        (pmhip_s2_forward_weights)."""
+    def forward(self, tokens, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, keys=None):
+        """context_segments / token_segments (None = the call as without them): regional prompts (pmhip_s2_forward_segments).
+        context_weights (None = the call as without them): prompt weights (pmhip_s2_forward_weights).  keys (instead of the four
+        keywords): the call's checked ``ops.Keys``."""
         tokens = tokens.to(self.device, torch.float32).contiguous()
         B = tokens.shape[0]
         context, L = self._ctx(context)
-        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L, native_lens=False)
-        lens = self._lens(context_lens, context, B, L)
-        seg = None if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L)
+        keys = self._keys(B, L, context_lens, context_segments, token_segments, context_weights, keys)
+        lens, cs, ts, w = _key_args(keys, native_lens=False)
         logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            if wts is not None:
-                check(self.lib.pmhip_s2_forward_weights(self.handle, _p(tokens), _p(context), L, B, wts[0][0], wts[0][1], wts[1], _p(logits),
-                                                        stream_ptr(self.device)), "pmhip_s2_forward_weights")
-                return logits
-            if seg is not None:
-                check(self.lib.pmhip_s2_forward_segments(self.handle, _p(tokens), _p(context), L, B, seg[0], seg[1], _p(logits),
-                                                         stream_ptr(self.device)), "pmhip_s2_forward_segments")
-                return logits
-            check(self.lib.pmhip_s2_forward_lens(self.handle, _p(tokens), _p(context), L, B, lens, _p(logits), stream_ptr(self.device)),
-                  "pmhip_s2_forward_lens")
+            self._call(((w is not None, "pmhip_s2_forward_weights", (cs, ts, w)),
+                        (cs is not None, "pmhip_s2_forward_segments", (cs, ts)),
+                        (True, "pmhip_s2_forward_lens", (lens,))),
+                       (self.handle, _p(tokens), _p(context), L, B), (_p(logits), stream_ptr(self.device)))
         return logits
 
-    def forward_maps(self, tokens, context, layers, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
+    def forward_maps(self, tokens, context, layers, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
+                     keys=None):
         """``forward`` with the cross-attention maps of the chosen layers beside the logits (pmhip_s2_forward_maps; DESIGN.md section
         4y).  layers: the layer indices (an iterable of distinct ints in [0, depth)).  -> (logits, maps): the logits ``forward`` returns
         on the same arguments, bit for bit, and maps f32 [B, tokens, L], the mean over the chosen layers of the head-mean
         probabilities of each layer's cross-attention; context rows that take part in no softmax are exactly 0.  Always eager."""
         if context is None:
             raise ValueError("forward_maps: the maps are those of the cross-attention: a context is required")
-        depth = self.cfg.tower.depth
-        chosen = [int(l) for l in layers]
-        if not chosen or len(set(chosen)) != len(chosen) or min(chosen) < 0 or max(chosen) >= depth:
-            raise ValueError(f"forward_maps: layers {list(layers)!r} must be distinct indices in [0, {depth})")
-        bits = 0
-        for l in chosen:
-            bits |= 1 << l
+        bits = sum(1 << l for l in ops.host_layers(layers, self.cfg.tower.depth, "forward_maps: layers"))
         tokens = tokens.to(self.device, torch.float32).contiguous()
         B = tokens.shape[0]
         context, L = self._ctx(context)
-        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L)
-        lens = self._lens(context_lens, context, B, L)
-        seg = wts[0] if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L) or (None, None)
+        lens, cs, ts, w = _key_args(self._keys(B, L, context_lens, context_segments, token_segments, context_weights, keys))
         logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
         maps = torch.empty(B, self.tokens, L, device=self.device, dtype=torch.float32)
         with torch.cuda.device(self.device):
-            check(self.lib.pmhip_s2_forward_maps(self.handle, _p(tokens), _p(context), L, B, lens, seg[0], seg[1],
-                                                 wts[1] if wts is not None else None, bits, _p(logits), _p(maps), stream_ptr(self.device)),
+            check(self.lib.pmhip_s2_forward_maps(self.handle, _p(tokens), _p(context), L, B, lens, cs, ts, w, bits, _p(logits), _p(maps),
+                                                 stream_ptr(self.device)),
                   "pmhip_s2_forward_maps")
         return logits, maps
 
@@ -396,10 +377,7 @@ class S2Engine:
         depth = self.cfg.tower.depth
         bits = []
         for name, layers in (("cross_layers", cross_layers), ("self_layers", self_layers)):
-            chosen = [int(l) for l in layers]
-            if len(set(chosen)) != len(chosen) or (chosen and (min(chosen) < 0 or max(chosen) >= depth)):
-                raise ValueError(f"forward_control: {name} {list(layers)!r} must be distinct indices in [0, {depth})")
-            bits.append(sum(1 << l for l in chosen))
+            bits.append(sum(1 << l for l in ops.host_layers(layers, depth, f"forward_control: {name}", allow_empty=True)))
         if not (bits[0] | bits[1]):
             raise ValueError("forward_control: cross_layers and self_layers select no layer")
         tokens = tokens.to(self.device, torch.float32).contiguous()
@@ -407,7 +385,7 @@ class S2Engine:
             raise ValueError(f"forward_control: {tokens.shape[0]} images are no pairs")
         B = tokens.shape[0] // 2
         context, L = self._ctx(context)
-        lens = self._lens(context_lens, context, 2 * B, L)
+        lens = _c_ints(self._keys(2 * B, L, context_lens).lens)
         given = [x is not None for x in (row_map, blend, gain)]
         if any(given) != bool(bits[0]) or any(given) != all(given):
             raise ValueError("forward_control: row_map, blend and gain are required with cross_layers and refused without")
@@ -423,12 +401,13 @@ class S2Engine:
 
     def sample(self, vq_engine, ids, context, topk, temperature, num_mask, noise=None, seed=0, step=0, image_base=0,
                want_img=True, want_aux=False, guidance_scale=None, context_lens=None, choice_temperature=None, choice_noise=None,
-               top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None, context_weights=None):
+               top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None, context_weights=None,
+               keys=None):
         """one MaskGIT step; ids int64 [B,N] is updated IN PLACE (pass a clone to keep the input).
-        context_weights (None = the calls below): prompt weights, see ``_weights``; only the pass with the context sees them
+        context_weights (None = the calls below): prompt weights; only the pass with the context sees them
         (pmhip_pipeline_sample_weights).
-        context_segments / token_segments (None = the calls below): regional prompts, see ``_segments``; only the pass with the
-        context sees them (pmhip_pipeline_sample_segments).
+        context_segments / token_segments (None = the calls below): regional prompts; only the pass with the context sees them
+        (pmhip_pipeline_sample_segments).  keys (instead of these and context_lens): the call's checked ``ops.Keys``.
         negative_context fp32 [B, Ln, context_dim] (None = the calls below, as without the keyword): the second tower of the guided
         step attends to it instead of running without a context (pmhip_pipeline_sample_negative); negative_lens: its per-image
         lengths, like context_lens.  Needs guidance_scale.
@@ -444,9 +423,7 @@ class S2Engine:
         ct = ops.choice_t(choice_temperature)
         nucleus = ops.nucleus_p(top_p)
         context, L = self._ctx(context)
-        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L)
-        lens = self._lens(context_lens, context, B, L)
-        seg = None if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L)
+        lens, cs, ts, w = _key_args(self._keys(B, L, context_lens, context_segments, token_segments, context_weights, keys))
         img = vq_engine._new_img(B) if want_img else None
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
@@ -456,37 +433,39 @@ class S2Engine:
             choice_noise = choice_noise.to(self.device, torch.float32).contiguous()
             if tuple(choice_noise.shape) != (B, self.tokens):
                 raise ValueError(f"choice_noise must be [B, {self.tokens}]")
-        neg, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
-        # always the widest entry: an absent option travels as the value with which the header promises the narrower entry's
-        # computation (NULL lengths, guided = 0, choice_t = 0, top_p = 1)
+        neg_ctx, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
+        neg = (_p(neg_ctx), Ln, neg_lens)                 # (neg_ctx lives until the native call has returned)
+        # the widest argument list of the entries before there was a negative context: an absent option travels as the value with which
+        # the header promises the narrower entry's computation (NULL lengths, guided = 0, choice_t = 0, top_p = 1)
         args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens,
                 int(topk), float(temperature), int(num_mask), _p(noise), int(seed), int(step), int(image_base), _p(img), _p(pred),
                 _p(score), int(guidance_scale is not None), float(guidance_scale or 0.0), ct, _p(choice_noise if ct else None), nucleus)
-        with torch.cuda.device(self.device):
-            if wts is not None:
-                check(self.lib.pmhip_pipeline_sample_weights(*args, _p(neg), Ln, neg_lens, wts[0][0], wts[0][1], wts[1], stream_ptr(self.device)),
-                      "pmhip_pipeline_sample_weights")
-            elif seg is not None:
-                check(self.lib.pmhip_pipeline_sample_segments(*args, _p(neg), Ln, neg_lens, seg[0], seg[1], stream_ptr(self.device)),
-                      "pmhip_pipeline_sample_segments")
-            elif neg is None:                     # without a negative context the native call is the one made before there was one
-                check(self.lib.pmhip_pipeline_sample_nucleus(*args, stream_ptr(self.device)), "pmhip_pipeline_sample_nucleus")
-            else:
-                check(self.lib.pmhip_pipeline_sample_negative(*args, _p(neg), Ln, neg_lens, stream_ptr(self.device)),
-                      "pmhip_pipeline_sample_negative")
+        with torch.cuda.device(self.device):      # without a negative context the native call is the one made before there was one
+            self._call(((w is not None, "pmhip_pipeline_sample_weights", neg + (cs, ts, w)),
+                        (cs is not None, "pmhip_pipeline_sample_segments", neg + (cs, ts)),
+                        (negative_context is not None, "pmhip_pipeline_sample_negative", neg),
+                        (True, "pmhip_pipeline_sample_nucleus", ())), args, (stream_ptr(self.device),))
         return ids, img, pred, score
 
-    def _negative(self, negative_context, negative_lens, B):
-        """(negative_context, negative_lens) -> (the context on the device or None, Ln, a ctypes int32 [B] or None)"""
+    def _negative(self, negative_context, negative_lens, B, keep=False):
+        """(negative_context, negative_lens) -> (the context on the device or None, Ln, a ctypes int32 [B] or None); the caller
+        holds the tensor while the native call reads it.  keep (``step_slots(keep_negative=)``): the negative K/V are kept, the
+        context only says how long it is -- None, Ln."""
         if negative_context is None:
+            if keep:
+                raise ValueError("step_slots: keep_negative needs the negative context it keeps (for its length)")
             if negative_lens is not None:
                 raise ValueError("negative_lens needs a negative context")
             return None, 0, None
-        neg, Ln = self._ctx(negative_context)
-        if neg.shape[0] != B:
-            raise ValueError(f"negative context for {neg.shape[0]} images, batch of {B}")
-        vals = ops.host_lens(negative_lens, B, Ln, "negative_lens")
-        return neg, Ln, None if vals is None else (C.c_int * B)(*vals)
+        if keep:
+            if negative_context.dim() != 3 or negative_context.shape[0] != B:
+                raise ValueError(f"step_slots: negative context {tuple(negative_context.shape)}, batch of {B}")
+            neg, Ln = None, negative_context.shape[1]
+        else:
+            neg, Ln = self._ctx(negative_context)
+            if neg.shape[0] != B:
+                raise ValueError(f"negative context for {neg.shape[0]} images, batch of {B}")
+        return neg, Ln, _c_ints(ops.host_lens(negative_lens, B, Ln, "negative_lens"))
 
     def slots_steps(self):
         """(one_pass, two_pass): the slots steps this handle ran, by tower passes (pmhip_s2_slots_steps) -- two passes exactly when
@@ -578,21 +557,13 @@ class S2Engine:
             context = None
         else:
             context, L = self._ctx(context)
-        lens = self._lens(context_lens, context, B, L)
+        lens = _c_ints(self._keys(B, L, context_lens).lens)
         pred = torch.empty(B, self.tokens, device=self.device, dtype=torch.int64) if want_aux else None
         score = torch.empty(B, self.tokens, device=self.device, dtype=torch.float32) if want_aux else None
-        flags = (_lib.SLOTS_GRAPH if use_graph else 0) | (_lib.SLOTS_KEEP_CONTEXT if keep_context else 0)
-        if keep_negative:
-            if negative_context is None:
-                raise ValueError("step_slots: keep_negative needs the negative context it keeps (for its length)")
-            if negative_context.dim() != 3 or negative_context.shape[0] != B:
-                raise ValueError(f"step_slots: negative context {tuple(negative_context.shape)}, batch of {B}")
-            neg, Ln = None, negative_context.shape[1]
-            vals = ops.host_lens(negative_lens, B, Ln, "negative_lens")
-            neg_lens = None if vals is None else (C.c_int * B)(*vals)
-            flags |= _lib.SLOTS_KEEP_NEGATIVE
-        else:
-            neg, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
+        flags = ((_lib.SLOTS_GRAPH if use_graph else 0) | (_lib.SLOTS_KEEP_CONTEXT if keep_context else 0) |
+                 (_lib.SLOTS_KEEP_NEGATIVE if keep_negative else 0))
+        neg_ctx, Ln, neg_lens = self._negative(negative_context, negative_lens, B, keep=keep_negative)
+        neg = (_p(neg_ctx), Ln, neg_lens)                 # (neg_ctx lives until the native call has returned)
         if choice is not None:
             if len(choice) != B:
                 raise ValueError(f"step_slots: {len(choice)} choice temperatures for a batch of {B}")
@@ -626,46 +597,31 @@ class S2Engine:
             if w.shape != (B, L):
                 raise ValueError(f"step_slots: weights {w.shape}: expected ({B}, {L})")
             weights = w.ctypes.data_as(C.POINTER(C.c_float))
+        none = (None, None, None)
         with torch.cuda.device(self.device):
-            if weights is not None:
-                none = (None, None, None)
-                check(self.lib.pmhip_pipeline_step_slots_weights(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
-                                                                 Ln, neg_lens, top_p, counts, *(segments or none), weights, flags,
-                                                                 _p(pred), _p(score), stream_ptr(self.device)),
-                      "pmhip_pipeline_step_slots_weights")
-            elif segments is not None:
-                check(self.lib.pmhip_pipeline_step_slots_regions(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
-                                                                 Ln, neg_lens, top_p, counts, segments[0], segments[1], segments[2], flags,
-                                                                 _p(pred), _p(score), stream_ptr(self.device)),
-                      "pmhip_pipeline_step_slots_regions")
-            elif counts is not None:
-                check(self.lib.pmhip_pipeline_step_slots_edit(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
-                                                              Ln, neg_lens, top_p, counts, flags, _p(pred), _p(score), stream_ptr(self.device)),
-                      "pmhip_pipeline_step_slots_edit")
-            elif top_p is not None:
-                check(self.lib.pmhip_pipeline_step_slots_filter(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
-                                                                Ln, neg_lens, top_p, flags, _p(pred), _p(score), stream_ptr(self.device)),
-                      "pmhip_pipeline_step_slots_filter")
-            elif neg is None and not keep_negative and not kinds:
-                check(self.lib.pmhip_pipeline_step_slots_choice(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, flags,
-                                                                _p(pred), _p(score), stream_ptr(self.device)), "pmhip_pipeline_step_slots_choice")
-            else:
-                check(self.lib.pmhip_pipeline_step_slots_negative(self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice, _p(neg),
-                                                                  Ln, neg_lens, flags, _p(pred), _p(score), stream_ptr(self.device)),
-                      "pmhip_pipeline_step_slots_negative")
+            self._call(((weights is not None, "pmhip_pipeline_step_slots_weights", neg + (top_p, counts) + (segments or none) + (weights,)),
+                        (segments is not None, "pmhip_pipeline_step_slots_regions", neg + (top_p, counts) + (segments or none)),
+                        (counts is not None, "pmhip_pipeline_step_slots_edit", neg + (top_p, counts)),
+                        (top_p is not None, "pmhip_pipeline_step_slots_filter", neg + (top_p,)),
+                        (negative_context is not None or kinds, "pmhip_pipeline_step_slots_negative", neg),
+                        (True, "pmhip_pipeline_step_slots_choice", ())),
+                       (self.handle, _p(ids), _p(context), L, B, lens, slots, guides, choice),
+                       (flags, _p(pred), _p(score), stream_ptr(self.device)))
         return ids, pred, score
 
     def generate(self, vq_engine, ids, context, temps, nmask, decode_flags, topk, seed=0, image_base=0, use_graph=False,
                  host=None, want_device_imgs=True, guidance_scale=None, concurrent_lanes=False, from_mask=False, context_lens=None,
                  choice_temps=None, top_p=None, negative_context=None, negative_lens=None, guidance_scales=None, nmask_img=None,
-                 context_segments=None, token_segments=None, context_weights=None):
+                 context_segments=None, token_segments=None, context_weights=None, keys=None):
         """T MaskGIT steps in one native call; returns imgs [n_decoded, B, C, H, W] (device) or None.
 
-        context_weights (None = the loops below): prompt weights, see ``_weights`` (pmhip_pipeline_generate_weights); the captured
-        loop reads their bias array from device memory: one graph serves every set of weights.
+        context_weights (None = the loops below): prompt weights (pmhip_pipeline_generate_weights); the captured loop reads their
+        bias array from device memory: one graph serves every set of weights.
 
-        context_segments / token_segments (None = the loops below): regional prompts, see ``_segments``
-        (pmhip_pipeline_generate_segments); the captured loop reads them from device memory: one graph serves every layout.
+        context_segments / token_segments (None = the loops below): regional prompts (pmhip_pipeline_generate_segments); the captured
+        loop reads them from device memory: one graph serves every layout.
+
+        keys (instead of these three and context_lens): the call's checked ``ops.Keys``.
 
         nmask_img (None = the loops below): the EDIT loop (pmhip_pipeline_generate_edit) -- T rows of B integers, step t re-masking
         nmask_img[t][b] positions of image b (0: none) instead of nmask[t] of every image; a decoded step then decodes the merged
@@ -699,13 +655,11 @@ class S2Engine:
             vals = [ops.choice_t(v, f"generate: step {i}: choice temperature") for i, v in enumerate(choice_temps)]
             choice_temps = (C.c_float * T)(*vals) if any(vals) else None
         context, L = self._ctx(context)
-        wts = self._weights(context_weights, context_segments, token_segments, context, context_lens, B, L)
-        lens = self._lens(context_lens, context, B, L)
-        seg = None if wts is not None else self._segments(context_segments, token_segments, context, context_lens, B, L)
-        if seg is not None and nmask_img is not None:
-            raise ValueError("generate: the edit loop takes no regional prompts")
-        if wts is not None and nmask_img is not None:
+        lens, cs, ts, w = _key_args(self._keys(B, L, context_lens, context_segments, token_segments, context_weights, keys))
+        if w is not None and nmask_img is not None:
             raise ValueError("generate: the edit loop takes no prompt weights")
+        if cs is not None and nmask_img is not None:
+            raise ValueError("generate: the edit loop takes no regional prompts")
         n_dec = int(sum(1 for f in decode_flags if f))
         imgs = None
         if n_dec and (want_device_imgs or host is None):
@@ -733,25 +687,21 @@ class S2Engine:
         dec_c = (C.c_ubyte * T)(*[1 if f else 0 for f in decode_flags])
         flags = ((_lib.GENERATE_GRAPH if use_graph else 0) | (_lib.GENERATE_CONCURRENT_LANES if concurrent_lanes else 0) |
                  (_lib.GENERATE_FROM_MASK if from_mask else 0))
-        neg, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
+        neg_ctx, Ln, neg_lens = self._negative(negative_context, negative_lens, B)
+        neg = (_p(neg_ctx), Ln, neg_lens)                 # (neg_ctx lives until the native call has returned)
         gscales = None
         if guidance_scales is not None:
             gscales = (C.c_float * T)(*ops.guidance_scales(guidance_scales, T, "generate: guidance_scales"))
         guided = guidance_scale is not None or gscales is not None
-        with torch.cuda.device(self.device):      # always the widest entry, absent options as the header's neutral values (see sample)
-            args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
-                    temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
-                    host_stride, copy_stream, int(guided), float(guidance_scale or 0.0), choice_temps, nucleus)
-            if wts is not None:
-                check(self.lib.pmhip_pipeline_generate_weights(*args, _p(neg), Ln, neg_lens, gscales, wts[0][0], wts[0][1], wts[1]),
-                      "pmhip_pipeline_generate_weights")
-            elif seg is not None:
-                check(self.lib.pmhip_pipeline_generate_segments(*args, _p(neg), Ln, neg_lens, gscales, seg[0], seg[1]),
-                      "pmhip_pipeline_generate_segments")
-            elif nmask_img is not None:
-                check(self.lib.pmhip_pipeline_generate_edit(*args, _p(neg), Ln, neg_lens, gscales), "pmhip_pipeline_generate_edit")
-            elif neg is None and gscales is None:
-                check(self.lib.pmhip_pipeline_generate_nucleus(*args), "pmhip_pipeline_generate_nucleus")
-            else:
-                check(self.lib.pmhip_pipeline_generate_negative(*args, _p(neg), Ln, neg_lens, gscales), "pmhip_pipeline_generate_negative")
+        # the widest argument list of the loops before there was a negative context, absent options as the header's neutral values
+        # (see sample); behind it what only the later entries read -- without any of it the call is the one made before they existed
+        args = (self.handle, vq_engine.handle if vq_engine is not None else C.c_void_p(0), _p(ids), _p(context), L, B, lens, T,
+                temps_c, nmask_c, dec_c, int(topk), int(seed), int(image_base), _p(imgs), flags, stream_ptr(self.device), host_ptr,
+                host_stride, copy_stream, int(guided), float(guidance_scale or 0.0), choice_temps, nucleus)
+        with torch.cuda.device(self.device):
+            self._call(((w is not None, "pmhip_pipeline_generate_weights", neg + (gscales, cs, ts, w)),
+                        (cs is not None, "pmhip_pipeline_generate_segments", neg + (gscales, cs, ts)),
+                        (nmask_img is not None, "pmhip_pipeline_generate_edit", neg + (gscales,)),
+                        (negative_context is not None or gscales is not None, "pmhip_pipeline_generate_negative", neg + (gscales,)),
+                        (True, "pmhip_pipeline_generate_nucleus", ())), args)
         return ids, imgs

@@ -127,20 +127,10 @@ def region_layout(contexts, masks, image_size, patch_size):
     return context, ctx_seg, tok_seg
 
 
-def _seg_kw(segments, lo=None, hi=None):
-    """the regional prompts' checked arrays (or None) as the keywords the engine and the modules take, of images [lo, hi); a third
-    array is the prompt weights that travel with them"""
-    if segments is None:
-        return {}
-    kw = dict(context_segments=segments[0][lo:hi], token_segments=segments[1][lo:hi])
-    if len(segments) == 3:
-        kw["context_weights"] = segments[2][lo:hi]
-    return kw
-
-
 class _Options(NamedTuple):
     """the sampler options of one public call, checked once (Pipeline._options): topk an integer (None resolved to n_embed), top_p a
-    float (1.0 = no nucleus filter), guidance_scale a number or None, lens the per-image context lengths as a host list or None,
+    float (1.0 = no nucleus filter), guidance_scale a number or None, lens the per-image context lengths as the caller gave them
+    (a host list or None; ``Pipeline._keys`` is their one reader: behind it the call's ``ops.Keys`` says what is attended to),
     choice_temperature the base value as a float (0.0 = the deterministic re-masking), negative the negative context [B, Ln, D] or
     None with negative_lens its per-image lengths as a host list or None, guidance_scales the loop's per-step scales as a list of
     floats or None (then guidance_scale is every step's)"""
@@ -154,11 +144,11 @@ class _Options(NamedTuple):
     guidance_scales: Optional[list] = None
 
     def lane(self, lo, hi):
-        """the options of the micro-batch of images [lo, hi): everything is per batch except the lengths and the negative context"""
-        if self.lens is None and self.negative is None:
+        """the options of the micro-batch of images [lo, hi): everything is per batch except the negative context (the call's
+        ``ops.Keys`` has a ``lane`` of its own)"""
+        if self.negative is None:
             return self
-        return self._replace(lens=None if self.lens is None else self.lens[lo:hi],
-                             negative=None if self.negative is None else self.negative[lo:hi].contiguous(),
+        return self._replace(negative=self.negative[lo:hi].contiguous(),
                              negative_lens=None if self.negative_lens is None else self.negative_lens[lo:hi])
 
     def step_scale(self, step):
@@ -371,15 +361,6 @@ class Pipeline(nn.Module):
         on the GPU branch alike.  An integer passes through unchecked: the step itself refuses what is out of 1..n_embed."""
         return self.mask_token_id if topk is None else topk
 
-    def _lens(self, context_lens, context, B):
-        """context_lens (a list, a CPU tensor or a device tensor; None passes through) -> a checked list of B ints on the host,
-        brought there ONCE per call: 1 <= len <= L, one per image"""
-        if context_lens is None:
-            return None
-        if context is None:
-            raise ValueError("context_lens needs a text condition (text=None IS the unconditional branch)")
-        return ops.host_lens(context_lens, B, context.shape[1])
-
     def _options(self, topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative=None, negative_lens=None,
                  timesteps=None):
         """the keywords of a public call -> its _Options, every value checked here and nowhere behind: the choice temperature and
@@ -393,11 +374,7 @@ class Pipeline(nn.Module):
         top_p = ops.nucleus_p(top_p)
         if guidance_scale is not None and context is None:
             raise ValueError("guidance_scale needs a text condition (text=None IS the unconditional branch)")
-        scales = None
-        if isinstance(guidance_scale, (list, tuple, np.ndarray, torch.Tensor)) and np.ndim(guidance_scale) > 0:
-            if timesteps is None:
-                raise ValueError("guidance_scale: one step takes one scale (a sequence is a loop's schedule)")
-            scales, guidance_scale = ops.guidance_scales(guidance_scale, timesteps), None
+        guidance_scale, scales = ops.guidance_parts(guidance_scale, timesteps)
         if negative_lens is not None and negative is None:
             raise ValueError("negative_context_lens needs a negative text")
         if negative is not None:
@@ -408,26 +385,19 @@ class Pipeline(nn.Module):
             if negative.dim() != 3 or negative.shape[0] != B or negative.shape[2] != context.shape[2]:
                 raise ValueError(f"negative_text must be a context tensor [{B}, Ln, {context.shape[2]}], got {tuple(negative.shape)}")
             negative_lens = ops.host_lens(negative_lens, B, negative.shape[1], "negative_context_lens")
-        return _Options(self._topk(topk), top_p, guidance_scale, self._lens(context_lens, context, B), base, negative, negative_lens,
-                        scales)
+        lens = self._host_keys(context, B, context_lens).lens
+        return _Options(self._topk(topk), top_p, guidance_scale, lens, base, negative, negative_lens, scales)
 
-    def _segments(self, context_segments, token_segments, context, context_lens, B, context_weights=None):
-        """context_segments [B, L] / token_segments [B, N] (lists, arrays or tensors; both None pass through) -> the two checked
-        host arrays of ``ops.host_segments`` (numpy uint8 [B, L], numpy uint32 [B, N]), brought to the host ONCE per call.  They
-        travel beside the call's ``_Options``, not in it: they need the context and exclude context_lens.
-        context_weights [B, L] (None: as above): -> the three checked host arrays of ``ops.host_weights``; without segment arrays
-        the first two are the neutral ones, which carry context_lens -- the caller drops the lengths from its ``_Options``."""
-        if context_weights is not None:
-            if context is None:
-                raise ValueError("context_weights need a text condition (text=None IS the unconditional branch)")
-            return ops.host_weights(context_weights, B, context.shape[1], self.num_tokens, context_segments, token_segments, context_lens)
-        if context_segments is None and token_segments is None:
-            return None
-        if context is None:
-            raise ValueError("context_segments / token_segments need a text condition (text=None IS the unconditional branch)")
-        if context_lens is not None:
-            raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
-        return ops.host_segments(context_segments, token_segments, B, context.shape[1], self.num_tokens)
+    def _host_keys(self, context, B, context_lens=None, context_segments=None, token_segments=None, context_weights=None, keys=None):
+        """``ops.host_keys`` (which has the rules) for a context [B, L, D] or None of this pipeline, in the words of its callers"""
+        return ops.host_keys(B, 0 if context is None else context.shape[1], self.num_tokens, context_lens, context_segments,
+                             token_segments, context_weights, has_context=context is not None, keys=keys,
+                             missing="a text condition (text=None IS the unconditional branch)")
+
+    def _keys(self, context, B, opts, context_segments=None, token_segments=None, context_weights=None):
+        """the ``ops.Keys`` of a call that has its ``_Options``: opts.lens -- read here and nowhere else -- with the segment and weight
+        arrays of the call beside them, brought to the host and checked ONCE per public call, here"""
+        return self._host_keys(context, B, opts.lens, context_segments, token_segments, context_weights)
 
     def tokens2logits(self, token, text=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None):
         """context_lens (extension; None = the reference's behaviour, every row of the context is attended to): one length per
@@ -443,14 +413,13 @@ class Pipeline(nn.Module):
         or alone): how much a context row counts -- over the rows a token attends to, p = w exp(s) / sum w exp(s).  1 is the row as
         without weights, an integer n the row repeated n times, 0 a padding row; otherwise 2^-20 <= w <= 2^20.  Every token must
         allow a row with a weight above 0.  ``generate(prompt_weights=True)`` reads them from ``(words:1.3)`` in the prompts."""
-        lens = self._lens(context_lens, text, token.shape[0])
-        segments = self._segments(context_segments, token_segments, text, lens, token.shape[0], context_weights)
-        kw = _seg_kw(segments)
-        if context_weights is not None:
-            lens = None                                           # (the neutral segments carry them)
+        return self._logits(token, text, self._host_keys(text, token.shape[0], context_lens, context_segments, token_segments, context_weights))
+
+    def _logits(self, token, text, keys=None):
+        """``tokens2logits`` behind its checks; keys None: every row of the context is attended to"""
         if self._on_cpu():
-            return self.transformer(token, text, lens, **kw)   # plain-torch operators of this package (no HIP engine on the CPU)
-        return self.engine().forward(token, text, context_lens=lens, **kw)
+            return self.transformer(token, text, keys=keys)   # plain-torch operators of this package (no HIP engine on the CPU)
+        return self.engine().forward(token, text, keys=keys)
 
     @torch.no_grad()
     def attention_maps(self, ids=None, text=None, layers=None, context_lens=None, mask_padding=False, context_segments=None,
@@ -482,21 +451,15 @@ class Pipeline(nn.Module):
         else:
             context = self.text_model(list(text))
         depth = len(self.transformer.layers)
-        chosen = list(range(depth)) if layers is None else [int(l) for l in layers]
-        if not chosen or len(set(chosen)) != len(chosen) or min(chosen) < 0 or max(chosen) >= depth:
-            raise ValueError(f"attention_maps: layers {layers!r} must be distinct indices in [0, {depth})")
-        lens = self._lens(context_lens, context, B)
-        segments = self._segments(context_segments, token_segments, context, lens, B, context_weights)
-        kw = _seg_kw(segments)
-        if context_weights is not None:
-            lens = None                                           # (the neutral segments carry them)
+        chosen = ops.host_layers(range(depth) if layers is None else layers, depth, "attention_maps: layers")
+        keys = self._host_keys(context, B, context_lens, context_segments, token_segments, context_weights)
         g = self.image_size // self.patch_size
         if self._on_cpu():
-            logits, maps = self.transformer(self.ids2tokens(ids), context, lens, maps_layers=chosen, **kw)
+            logits, maps = self.transformer(self.ids2tokens(ids), context, maps_layers=chosen, keys=keys)
         else:
             eng = self.engine()
             token = self.ids2tokens(ids.to(eng.device))
-            logits, maps = eng.forward_maps(token, context.to(eng.device), chosen, context_lens=lens, **kw)
+            logits, maps = eng.forward_maps(token, context.to(eng.device), chosen, keys=keys)
         maps = maps.transpose(1, 2).reshape(B, context.shape[1], g, g).contiguous()
         return (maps, logits) if return_logits else maps
 
@@ -585,27 +548,27 @@ class Pipeline(nn.Module):
         nm = num_token_masked(mask_ratio, self.num_tokens)
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, text, ids.shape[0], negative_text,
                              negative_context_lens)
-        segments = self._segments(context_segments, token_segments, text, opts.lens, ids.shape[0], context_weights)
-        if context_weights is not None:
-            opts = opts._replace(lens=None)
-        return self._step(ids, nm, text, opts, temperature, opts.choice_temperature, noise, seed, step, image_base, choice_noise, segments)
+        keys = self._keys(text, ids.shape[0], opts, context_segments, token_segments, context_weights)
+        return self._step(ids, nm, text, opts, temperature, opts.choice_temperature, noise, seed, step, image_base, choice_noise, keys)
 
     @torch.no_grad()
     def _step(self, ids, nm, text, opts, temperature, choice_t, noise=None, seed=None, step=0, image_base=0, choice_noise=None,
-              segments=None):
+              keys=None):
         """``sample`` behind its checks: one step that re-masks nm tokens, with the step's own temperature and choice temperature;
-        segments: the regional prompts' checked arrays (``_segments``) or None"""
+        keys: the call's ``ops.Keys`` (None: those of opts alone)"""
+        if keys is None:
+            keys = self._keys(text, ids.shape[0], opts)
         if self._on_cpu():
-            return self._sample_cpu(ids, nm, text, opts.topk, temperature, noise, seed, opts.guidance_scale, opts.lens, choice_t,
-                                    choice_noise, opts.top_p, opts.negative, opts.negative_lens, segments=segments)
+            return self._sample_cpu(ids, nm, text, opts.topk, temperature, noise, seed, opts.guidance_scale, keys, choice_t,
+                                    choice_noise, opts.top_p, opts.negative, opts.negative_lens)
         if seed is None:
             seed = _draw_seed()
         eng = self.engine()
         ids = ids.to(eng.device, torch.int64).clone().contiguous()
         ids, img, _, _ = eng.sample(self.vqgan.engine(), ids, text, opts.topk, temperature, nm, noise=noise, seed=seed, step=step,
-                                    image_base=image_base, want_img=True, guidance_scale=opts.guidance_scale, context_lens=opts.lens,
-                                    choice_temperature=choice_t, choice_noise=choice_noise, top_p=opts.top_p,
-                                    negative_context=opts.negative, negative_lens=opts.negative_lens, **_seg_kw(segments))
+                                    image_base=image_base, want_img=True, guidance_scale=opts.guidance_scale, choice_temperature=choice_t,
+                                    choice_noise=choice_noise, top_p=opts.top_p, negative_context=opts.negative,
+                                    negative_lens=opts.negative_lens, keys=keys)
         return ids, img
 
     def _sample_guided_composed(self, ids, nm, text, topk, temperature, noise, seed, step, image_base, scale, context_lens=None):
@@ -627,17 +590,18 @@ class Pipeline(nn.Module):
         ids = ops.remask(merged.reshape(B, N), score.reshape(B, N), nm, self.mask_token_id)
         return ids, img
 
-    def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, context_lens=None, choice_t=0.0,
-                    choice_noise=None, top_p=1.0, negative=None, negative_lens=None, counts=None, segments=None):
+    def _sample_cpu(self, ids, nm, text, topk, temperature, noise, seed, guidance_scale=None, keys=None, choice_t=0.0,
+                    choice_noise=None, top_p=1.0, negative=None, negative_lens=None, counts=None):
         """generate.py:159-181 in plain torch for a pipeline that lives on the CPU.  The noise is drawn from the torch CPU
         generator like the reference's (`seed` re-seeds a private generator; `noise` overrides it); ties in top-k / argmax
-        follow torch.  choice_t != 0: the re-masking sorts by choice_keys; its uniforms are `choice_noise`, or drawn behind the
+        follow torch.  keys: the checked ``ops.Keys`` of the forward with `text` (None: every row is attended to).
+        choice_t != 0: the re-masking sorts by choice_keys; its uniforms are `choice_noise`, or drawn behind the
         token noise from the same generator.  top_p < 1: of the top-k values only those nucleus_keep keeps.  negative: the second
         forward of a guided step takes this context (with negative_lens) instead of none.  counts (a list of B ints; None = the
         reference's step): the EDIT step -- image b re-masks counts[b] positions (0: none) instead of nm, and no image is decoded
         (``edit`` decodes the merged ids of its last step itself)."""
         tok = self.ids2tokens(ids)
-        logits = self.tokens2logits(tok, text, context_lens, *(segments or ()))
+        logits = self._logits(tok, text, keys)
         if guidance_scale is not None:
             uncond = self.tokens2logits(tok, negative, negative_lens)
             logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(guidance_scale)))
@@ -672,16 +636,18 @@ class Pipeline(nn.Module):
         return ids, img
 
     @torch.no_grad()
-    def _generate_cpu(self, context, B, timesteps, temperature, opts, save_interval, seed, return_ids, segments=None):
+    def _generate_cpu(self, context, B, timesteps, temperature, opts, save_interval, seed, return_ids, keys=None):
         """generate.py:183-198, with plain or guided steps (see `sample`), for a pipeline that lives on the CPU.  (On the GPU the
-        loop is the native one, graph-captured and lane-able.)"""
+        loop is the native one, graph-captured and lane-able.)  keys: the call's ``ops.Keys`` (None: those of opts alone)."""
+        if keys is None:
+            keys = self._keys(context, B, opts)
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
         ids = torch.full((B, self.num_tokens), self.mask_token_id, dtype=torch.long)
         imgs = []
         for step in range(timesteps):
             ids, img = self._sample_cpu(ids, nmask[step], context, opts.topk, temps[step], None, None if seed is None else seed + step,
-                                        opts.step_scale(step), opts.lens, ctemps[step] if ctemps else 0.0, None, opts.top_p, opts.negative,
-                                        opts.negative_lens, segments=segments)
+                                        opts.step_scale(step), keys, ctemps[step] if ctemps else 0.0, None, opts.top_p, opts.negative,
+                                        opts.negative_lens)
             if step % save_interval == 0:
                 imgs.append(img)
         return (imgs, ids) if return_ids else imgs
@@ -737,8 +703,11 @@ class Pipeline(nn.Module):
     def generate_ids(self, context, B, timesteps, temperature, topk, decode_flags, seed, image_base=0, use_graph=False, streams=1,
                      join=True, wait_current=True, host=None, guidance_scale=None, ids0=None, context_lens=None, choice_temperature=None,
                      top_p=None, negative_context=None, negative_lens=None, context_segments=None, token_segments=None,
-                     context_weights=None):
+                     context_weights=None, keys=None):
         """The decode loop on device tensors: returns (ids [B,N], imgs [n_decoded,B,C,H,W] or None).
+
+        keys (a caller that holds the call's ``_Options`` -- passed as `topk` -- holds its ``ops.Keys`` too, and passes it instead of
+        the lengths, segments and weights): nothing is checked again.
 
         context_weights [B, L] (None: the loop as without them): prompt weights, see ``tokens2logits``.  Every lane takes the rows of
         its micro-batch; the captured loop reads their bias array from device memory, so one graph serves every set of weights.
@@ -773,20 +742,20 @@ class Pipeline(nn.Module):
         so every lane takes it as it is; below 1 part of the key of a captured graph."""
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative_context, negative_lens,
                              timesteps)
-        segments = self._segments(context_segments, token_segments, context, opts.lens, B, context_weights)
-        if context_weights is not None:
-            opts = opts._replace(lens=None)
+        if keys is None:
+            keys = self._keys(context, B, opts, context_segments, token_segments, context_weights)
+        else:                                            # (refused beside any of the arrays it stands for, or for another shape)
+            keys = self._host_keys(context, B, context_lens, context_segments, token_segments, context_weights, keys)
         if ids0 is not None and tuple(ids0.shape) != (B, self.num_tokens):
             raise ValueError(f"generate_ids: ids0 has shape {tuple(ids0.shape)}, expected {(B, self.num_tokens)}")
         eng = self.engine()
         temps, nmask, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
 
-        def run(e, v, ids, c, o, lo=None, hi=None, **kw):  # the native loop of one engine pair: the whole batch, or one lane's images [lo, hi)
+        def run(e, v, ids, c, o, k, **kw):  # the native loop of one engine pair: the whole batch, or one lane's images with their o and k
             if o.negative is not None or o.guidance_scales is not None:
                 kw.update(negative_context=o.negative, negative_lens=o.negative_lens, guidance_scales=o.guidance_scales)
-            kw.update(_seg_kw(segments, lo, hi))
             return e.generate(v, ids, c, temps, nmask, decode_flags, o.topk, seed=seed, use_graph=use_graph, want_device_imgs=host is None,
-                              guidance_scale=o.guidance_scale, context_lens=o.lens, choice_temps=ctemps, top_p=o.top_p, **kw)
+                              guidance_scale=o.guidance_scale, choice_temps=ctemps, top_p=o.top_p, keys=k, **kw)
 
         if isinstance(streams, (list, tuple)):           # explicit micro-batch sizes, e.g. (32, 16, 16)
             sizes = [int(x) for x in streams]
@@ -807,7 +776,7 @@ class Pipeline(nn.Module):
             raise ValueError("generate_ids: ids0 needs streams=1")
         if streams == 1:
             ids = self._start_ids(B, ids0, eng.device)
-            return run(eng, self.vqgan.engine(), ids, context, opts, image_base=image_base, from_mask=ids0 is None,
+            return run(eng, self.vqgan.engine(), ids, context, opts, keys, image_base=image_base, from_mask=ids0 is None,
                        host=None if host is None else (host[0], 0, host[1][0]))
         from .dist import shard_range
         cur = torch.cuda.current_stream(eng.device)
@@ -822,7 +791,7 @@ class Pipeline(nn.Module):
             with torch.cuda.device(eng.device), torch.cuda.stream(st):
                 ids = torch.full((hi - lo, self.num_tokens), self.mask_token_id, dtype=torch.long, device=eng.device)
                 c = None if context is None else context[lo:hi].contiguous()
-                ids, imgs = run(e, v, ids, c, opts.lane(lo, hi), lo, hi, image_base=image_base + lo, concurrent_lanes=True,
+                ids, imgs = run(e, v, ids, c, opts.lane(lo, hi), keys.lane(lo, hi), image_base=image_base + lo, concurrent_lanes=True,
                                 from_mask=True,                  # lanes exist for ids0 None only (checked above)
                                 host=None if host is None else (host[0], lo, host[1][i]))
             return ids, imgs, st
@@ -882,13 +851,12 @@ class Pipeline(nn.Module):
             raise ValueError("control_ids: lens_src and lens_edit come together")
         L, T = context_src.shape[1], int(timesteps)
         context = torch.cat([context_src, context_edit])
-        lens = None if lens_src is None else ops.host_lens(lens_src, B, L, "lens_src") + ops.host_lens(lens_edit, B, L, "lens_edit")
-        opts = self._options(topk, top_p, guidance_scale, lens, choice_temperature, context, 2 * B)
+        lengths = None if lens_src is None else ops.host_lens(lens_src, B, L, "lens_src") + ops.host_lens(lens_edit, B, L, "lens_edit")
+        opts = self._options(topk, top_p, guidance_scale, lengths, choice_temperature, context, 2 * B)
+        keys = self._keys(context, 2 * B, opts)
         rm, bl, gn = ops.host_control(row_map, blend, gain, B, L)
         depth = len(self.transformer.layers)
-        layers = list(range(depth)) if layers is None else [int(l) for l in layers]
-        if not layers or len(set(layers)) != len(layers) or min(layers) < 0 or max(layers) >= depth:
-            raise ValueError(f"control_ids: layers {layers!r} must be distinct indices in [0, {depth})")
+        layers = ops.host_layers(range(depth) if layers is None else layers, depth, "control_ids: layers")
         for name, f in (("cross_steps", cross_steps), ("self_steps", self_steps)):
             if not 0.0 <= float(f) <= 1.0:
                 raise ValueError(f"control_ids: {name}={f} must be a fraction in [0, 1]")
@@ -911,11 +879,11 @@ class Pipeline(nn.Module):
             ct = ctemps[step] if ctemps else 0.0
             if cpu:
                 if cross or inject:
-                    logits = self.transformer(tok, context, context_lens=opts.lens, control=dict(cross_layers=cross, self_layers=inject, **ctl))
+                    logits = self.transformer(tok, context, keys=keys, control=dict(cross_layers=cross, self_layers=inject, **ctl))
                 else:
-                    logits = self.tokens2logits(tok, context, opts.lens)
+                    logits = self._logits(tok, context, keys)
                 if opts.guidance_scale is not None:
-                    uncond = self.tokens2logits(tok, None)
+                    uncond = self._logits(tok, None)
                     logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(opts.guidance_scale)))
                 halves = [self._tail_cpu(ids[h * B:(h + 1) * B], logits[h * B:(h + 1) * B], nmask[step], opts.topk, temps[step],
                                          None if noise is None else noise[step], None if seed is None else seed + step, ct, None, opts.top_p,
@@ -925,9 +893,9 @@ class Pipeline(nn.Module):
                 continue
             eng = self.engine()
             if cross or inject:
-                logits = eng.forward_control(tok, context, cross_layers=cross, self_layers=inject, context_lens=opts.lens, **ctl)
+                logits = eng.forward_control(tok, context, cross_layers=cross, self_layers=inject, context_lens=keys.lens, **ctl)
             else:
-                logits = eng.forward(tok, context, context_lens=opts.lens)
+                logits = eng.forward(tok, context, keys=keys)
             if opts.guidance_scale is not None:
                 logits = ops.guidance_combine(logits, eng.forward(tok, None), opts.guidance_scale, out=logits)
             for h in range(2):
@@ -1120,23 +1088,12 @@ class Pipeline(nn.Module):
             context, context_lens = self.text_model(text, return_lens=True)
         else:
             context = self.text_model(text)
-        negative = None
-        if negative_text is not None:
-            prompts = [negative_text] * B if isinstance(negative_text, str) else list(negative_text)
-            if len(prompts) != B:
-                raise ValueError(f"negative_text: {len(prompts)} prompts for a batch of {B}")
-            if mask_padding and negative_context_lens is None:
-                negative, negative_context_lens = self.text_model(prompts, return_lens=True)
-            else:
-                negative = self.text_model(prompts)
+        negative, negative_context_lens = self._negative_context(negative_text, B, mask_padding, negative_context_lens)
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative, negative_context_lens,
                              timesteps)
-        segments = self._segments(context_segments, token_segments, context, opts.lens, B, context_weights)
-        if context_weights is not None:
-            opts = opts._replace(lens=None)
+        keys = self._keys(context, B, opts, context_segments, token_segments, context_weights)
         if self._on_cpu():
-            return self._generate_cpu(context, B, timesteps, temperature, opts, save_interval, seed, return_ids, segments)
-        seg_kw = _seg_kw(segments)
+            return self._generate_cpu(context, B, timesteps, temperature, opts, save_interval, seed, return_ids, keys)
         eng = self.engine()
         if seed is None:
             seed = _draw_seed()
@@ -1160,7 +1117,7 @@ class Pipeline(nn.Module):
         n_dec = sum(flags)
         if keep_on_device or n_dec == 0:
             ids, imgs = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base,
-                                          use_graph=use_graph, streams=streams, **seg_kw)
+                                          use_graph=use_graph, streams=streams, keys=keys)
             out = [] if imgs is None else list(imgs)
             return (out, ids) if return_ids else out
         vq = self.vqgan.engine()
@@ -1174,7 +1131,7 @@ class Pipeline(nn.Module):
             cs.append(torch.cuda.Stream(device=eng.device))
         try:
             ids, _ = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base,
-                                       use_graph=use_graph, streams=streams, host=(host, cs), **seg_kw)
+                                       use_graph=use_graph, streams=streams, host=(host, cs), keys=keys)
         except BaseException:
             # a lane failed: whatever the other lanes queued may still be writing into `host`; drain it, and never hand
             # this buffer out again
@@ -1192,6 +1149,18 @@ class Pipeline(nn.Module):
                     pass
         out = list(host)                                     # views of one pinned buffer; it is reused once all of them are gone
         return (out, ids) if return_ids else out
+
+    def _negative_context(self, negative_text, B, mask_padding, negative_context_lens=None):
+        """a negative prompt -- one string for every image or a list of B -- through the text model -> (its context [B, Ln, D], its
+        lengths): with mask_padding the text model's own, unless the caller gave them; None: (None, the lengths as given)"""
+        if negative_text is None:
+            return None, negative_context_lens
+        prompts = [negative_text] * B if isinstance(negative_text, str) else list(negative_text)
+        if len(prompts) != B:
+            raise ValueError(f"negative_text: {len(prompts)} prompts for a batch of {B}")
+        if mask_padding and negative_context_lens is None:
+            return self.text_model(prompts, return_lens=True)
+        return self.text_model(prompts), negative_context_lens
 
     def _region_context(self, text, regions, mask_padding):
         """``generate(text, regions=)`` without prompt weights -> (context [B, Lmax, D], context_segments, token_segments); see
@@ -1312,13 +1281,28 @@ class Pipeline(nn.Module):
             raise ValueError(f"edit: mask must be [{B}, {H}, {W}], [{B}, 1, {H}, {W}] or [{H}, {W}], got {tuple(pm.shape)}")
         return None, (pm.to(img.device) != 0).expand(B, H, W).to(torch.uint8).contiguous()
 
-    def edit_ids(self, ids, counts, context, timesteps, temperature, opts, seed, image_base=0, use_graph=False):
+    def _masked_ids(self, ids, token_mask, pixel_mask):
+        """ids [B, N] and the masks of ``_edit_masks`` -> (ids with the mask id where a token is regenerated, counts [B]: how many per
+        image, on the device of the mask that counted them).  A pixel mask without a token mask marks a token iff any pixel of its patch is set: the mask operator
+        on the GPU, its rule in plain torch on the CPU."""
+        B = ids.shape[0]
+        if token_mask is None and not self._on_cpu():
+            return ops.mask_tokens(pixel_mask.to(ids.device), self.patch_size, ids, self.mask_token_id)
+        if token_mask is None:
+            p = self.patch_size
+            token_mask = pixel_mask.reshape(B, pixel_mask.shape[1] // p, p, pixel_mask.shape[2] // p, p).amax(dim=(2, 4)) != 0
+        tm = token_mask.reshape(B, -1)
+        return torch.where(tm.to(ids.device), torch.full_like(ids, self.mask_token_id), ids), tm.sum(1)       # (counted where the mask is)
+
+    def edit_ids(self, ids, counts, context, timesteps, temperature, opts, seed, image_base=0, use_graph=False, keys=None):
         """the EDIT loop on device tensors (pmhip_pipeline_generate_edit): ids int64 [B, N] with the mask id where a token is
         regenerated, counts = how many per image (a list of B ints), opts the call's ``_Options``.  Step t re-masks
         ``edit_schedule(counts[b], timesteps)[t]`` positions of image b; the last step is decoded, from the merged ids.
-        -> (final ids [B, N], image [B, C, H, W]); ``ids`` is left as it is."""
+        -> (final ids [B, N], image [B, C, H, W]); ``ids`` is left as it is.  keys: the call's ``ops.Keys`` (None: those of opts alone)."""
         eng = self.engine()
         B = ids.shape[0]
+        if keys is None:
+            keys = self._keys(context, B, opts)
         temps, _, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
         per_image = [edit_schedule(m, timesteps) for m in counts]
         table = [[per_image[b][t] for b in range(B)] for t in range(timesteps)]
@@ -1327,8 +1311,8 @@ class Pipeline(nn.Module):
             kw.update(negative_context=opts.negative, negative_lens=opts.negative_lens, guidance_scales=opts.guidance_scales)
         ids = self._start_ids(B, ids, eng.device)
         ids, imgs = eng.generate(self.vqgan.engine(), ids, context, temps, None, [False] * (timesteps - 1) + [True], opts.topk, seed=seed,
-                                 image_base=image_base, use_graph=use_graph, guidance_scale=opts.guidance_scale, context_lens=opts.lens,
-                                 choice_temps=ctemps, top_p=opts.top_p, nmask_img=table, **kw)
+                                 image_base=image_base, use_graph=use_graph, guidance_scale=opts.guidance_scale, choice_temps=ctemps,
+                                 top_p=opts.top_p, nmask_img=table, keys=keys, **kw)
         return ids, imgs[0]
 
     @torch.no_grad()
@@ -1357,38 +1341,28 @@ class Pipeline(nn.Module):
             raise ValueError(f"edit: preserve must be 'tokens' or 'pixels', got {preserve!r}")
         tm, pm = self._edit_masks(img, mask, token_mask)
         B = img.shape[0]
-        negative = negative_lens = None
         if exists(text):
             if mask_padding and context_lens is None:
                 context, context_lens = self.text_model(text, return_lens=True)
             else:
                 context = self.text_model(text)
-            if negative_text is not None:
-                prompts = [negative_text] * B if isinstance(negative_text, str) else list(negative_text)
-                if len(prompts) != B:
-                    raise ValueError(f"negative_text: {len(prompts)} prompts for a batch of {B}")
-                if mask_padding:
-                    negative, negative_lens = self.text_model(prompts, return_lens=True)
-                else:
-                    negative = self.text_model(prompts)
+        elif negative_text is not None:
+            raise ValueError("negative_text needs a text condition (text=None IS the unconditional branch)")
         else:
             context = None
-            if negative_text is not None:
-                raise ValueError("negative_text needs a text condition (text=None IS the unconditional branch)")
+        negative, negative_lens = self._negative_context(negative_text, B, mask_padding)
         opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative, negative_lens, timesteps)
         _, ids, _ = self.to_latent(img)
         ids = ids.reshape(B, self.num_tokens)
+        keys = self._keys(context, B, opts)
         if self._on_cpu():
-            if tm is None:
-                p = self.patch_size
-                tm = pm.reshape(B, pm.shape[1] // p, p, pm.shape[2] // p, p).amax(dim=(2, 4)) != 0
-            ids = torch.where(tm.reshape(B, -1), torch.full_like(ids, self.mask_token_id), ids)
-            counts = tm.reshape(B, -1).sum(1).tolist()
+            ids, counts = self._masked_ids(ids, tm, pm)
+            counts = counts.tolist()
             temps, _, ctemps = loop_schedule(timesteps, temperature, self.num_tokens, opts.choice_temperature)
             per_image = [edit_schedule(m, timesteps) for m in counts]
             for step in range(timesteps):
                 ids, _ = self._sample_cpu(ids, 0, context, opts.topk, temps[step], None, None if seed is None else seed + step,
-                                          opts.step_scale(step), opts.lens, ctemps[step] if ctemps else 0.0, None, opts.top_p,
+                                          opts.step_scale(step), keys, ctemps[step] if ctemps else 0.0, None, opts.top_p,
                                           opts.negative, opts.negative_lens, counts=[sched[step] for sched in per_image])
             out = self.vqgan.decode_from_indice(ids)
             if preserve == "pixels":
@@ -1398,18 +1372,14 @@ class Pipeline(nn.Module):
         if seed is None:
             seed = _draw_seed()
         ids = ids.to(eng.device, torch.long).clone(memory_format=torch.contiguous_format)
-        if tm is None:
-            ids, counts = ops.mask_tokens(pm.to(eng.device), self.patch_size, ids, self.mask_token_id)
-            counts = counts.tolist()                           # the one device-to-host copy of the call: B counts
-        else:
-            ids = torch.where(tm.reshape(B, -1).to(eng.device), torch.full_like(ids, self.mask_token_id), ids)
-            counts = tm.reshape(B, -1).sum(1).tolist()
+        ids, counts = self._masked_ids(ids, tm, pm)
+        counts = counts.tolist()                               # the one device-to-host copy of the call: B counts
         if context is not None:
             context = context.to(eng.device)
         if opts.negative is not None:
             opts = opts._replace(negative=opts.negative.to(eng.device))
         use_graph = os.environ.get("PMHIP_GENERATE_GRAPH", "1") != "0"
-        ids, out = self.edit_ids(ids, counts, context, timesteps, temperature, opts, seed, image_base=image_base, use_graph=use_graph)
+        ids, out = self.edit_ids(ids, counts, context, timesteps, temperature, opts, seed, image_base=image_base, use_graph=use_graph, keys=keys)
         if preserve == "pixels":
             out = ops.composite(out, img.to(eng.device, torch.float32).contiguous(), pm.to(eng.device), out=out)
         return (out, ids) if return_ids else out

@@ -61,7 +61,7 @@ class CrossAttention(nn.Module):
                         token_segments=token_segments, context_weights=context_weights)
 
     def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
-            want_maps=False, control=None, inject_self=False):
+            want_maps=False, control=None, inject_self=False, keys=None):
         """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x.
         want_maps (extension, attention maps): -> (that, maps) with maps f32 [B, N, L], the mean over the heads
         of this call's softmax probabilities -- exactly 0 where a row takes no part; it needs a context.
@@ -75,9 +75,19 @@ class CrossAttention(nn.Module):
         control (extension, prompt-to-prompt): (row_map, blend, gain), each [B / 2, L] -- the batch is B / 2 pairs,
         the source images in front; the edited half attends with P = gain (has ? (1 - blend) pt + blend ps[row_map] : pt), ps the source
         half's probabilities (``ops.attention_control``).  It needs a context and stands beside context_lens only.
-        inject_self (the same extension, a self-attention): the edited half attends with the source half's Q and K and its own V."""
+        inject_self (the same extension, a self-attention): the edited half attends with the source half's Q and K and its own V.
+        keys: the call's checked ``ops.Keys``, which is not checked again; the four arrays beside it are then its own (what
+        ``Layer.forward`` hands over) and are not looked at.  Without it the four arrays are checked here, whatever their types."""
+        shape = (x.shape[0], 0 if context is None else context.shape[1], x.shape[1])
+        if keys is not None:
+            keys = ops.host_keys(*shape, keys=keys)
+        else:
+            keys = ops.host_keys(*shape, context_lens, context_segments, token_segments, context_weights, has_context=context is not None,
+                                 missing="a context (self-attention takes no mask and no weights)")
+        context_lens, weights = keys.lens, keys.weights
+        segments = None if keys.context_segments is None else (keys.context_segments, keys.token_segments)
         if control is not None:
-            if context is None or context_segments is not None or token_segments is not None or context_weights is not None or want_maps:
+            if context is None or segments is not None or want_maps:
                 raise ValueError("control needs a context and stands beside context_lens only")
             if x.shape[0] % 2:
                 raise ValueError(f"control: {x.shape[0]} images are no pairs")
@@ -86,27 +96,6 @@ class CrossAttention(nn.Module):
             raise ValueError("inject_self is for the self-attention of a batch of pairs")
         if self.training and self.to_out[1].p > 0:
             raise RuntimeError("paintmind_amd attention is inference-only (dropout>0 in training mode)")
-        if context_lens is not None:
-            if context is None:
-                raise ValueError("context_lens needs a context (self-attention takes no key-padding mask)")
-            context_lens = ops.host_lens(context_lens, x.shape[0], context.shape[1])
-        segments = None
-        if context_segments is not None or token_segments is not None:
-            if context is None:
-                raise ValueError("context_segments / token_segments need a context (self-attention takes no mask)")
-            if context_lens is not None:
-                raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
-            segments = context_segments, token_segments
-            if not (isinstance(context_segments, np.ndarray) and context_segments.dtype == np.uint8):      # (checked already otherwise)
-                segments = ops.host_segments(context_segments, token_segments, x.shape[0], context.shape[1], x.shape[1])
-        weights = None
-        if context_weights is not None:
-            if context is None:
-                raise ValueError("context_weights need a context (self-attention takes no weights)")
-            cs, ts, weights = ops.host_weights(context_weights, x.shape[0], context.shape[1], x.shape[1],
-                                               None if segments is None else segments[0], None if segments is None else segments[1],
-                                               context_lens)
-            segments, context_lens = (cs, ts), None               # (without segment arrays: the neutral ones, which carry the lengths)
         if want_maps and context is None:
             raise ValueError("want_maps: the maps are those of a cross-attention: a context is required")
         if not x.is_cuda:

@@ -5,6 +5,7 @@ function asserts its operands live on a ROCm device; nothing falls back to ATen.
 """
 import ctypes as C
 import math
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -157,6 +158,75 @@ def host_weights(context_weights, B, L, N, context_segments=None, token_segments
         b, t = bad[0]
         raise ValueError(f"context_weights: image {b}: token {t} allows no context row with a weight above 0 (mask {int(ts[b, t]):#x})")
     return cs, ts, w
+
+
+def host_layers(layers, depth, what, allow_empty=False):
+    """a choice of tower layers (any iterable of ints) -> a list of distinct indices in [0, depth), checked; `what` names the
+    argument in the message; an empty choice is refused unless allow_empty"""
+    chosen = [int(l) for l in layers]
+    if (not chosen and not allow_empty) or len(set(chosen)) != len(chosen) or (chosen and (min(chosen) < 0 or max(chosen) >= depth)):
+        raise ValueError(f"{what} {chosen!r} must be distinct indices in [0, {depth})")
+    return chosen
+
+
+class Keys(NamedTuple):
+    """The KEY SETS of one call, checked (``host_keys``): which context rows a token attends to, and how much
+    each counts.  lens: a list of B ints or None; context_segments numpy uint8 [B, L] / token_segments numpy uint32 [B, N] or None;
+    weights numpy float32 [B, L] or None; shape: the (B, L, N) it was checked for.  Weights without segment arrays bring the neutral
+    segments (segment 0 below an image's length, 255 behind, every token mask all ones) and no lengths; `neutral` says so and
+    neutral_lens keeps the lengths they were built from (None: every row), for the native entries that stage them themselves.
+    A layer that receives a Keys does not check it again."""
+    lens: Optional[list] = None
+    context_segments: Optional[np.ndarray] = None
+    token_segments: Optional[np.ndarray] = None
+    weights: Optional[np.ndarray] = None
+    shape: tuple = (0, 0, 0)
+    neutral: bool = False
+    neutral_lens: Optional[list] = None
+
+    def lane(self, lo, hi):
+        """the record of the micro-batch of images [lo, hi): every array sliced"""
+        cut = lambda a: None if a is None else a[lo:hi]
+        return Keys(cut(self.lens), cut(self.context_segments), cut(self.token_segments), cut(self.weights),
+                    (len(range(self.shape[0])[lo:hi]),) + tuple(self.shape[1:]), self.neutral, cut(self.neutral_lens))
+
+    def cpu_args(self):
+        """the four arrays in the order ``Layer.forward`` and ``CrossAttention.run`` take them behind the context; ``Layer.forward``
+        hands them on beside the record"""
+        return self.lens, self.context_segments, self.token_segments, self.weights
+
+
+def host_keys(B, L, N, context_lens=None, context_segments=None, token_segments=None, context_weights=None, has_context=True, keys=None,
+              missing="a context (context None IS the unconditional branch)"):
+    """The four ways to say which context rows a token attends to -> the call's ``Keys``, brought to the host and checked ONCE
+    (``host_lens``, ``host_segments``, ``host_weights``).  The rules live here and nowhere else: the arrays need a context; segments
+    exclude lengths; weights fold the lengths into the neutral segments, after which there are no lengths.  All None: the empty
+    record.  keys (instead of the four): a record checked before -- it comes back as it is, no array is looked at; one checked for
+    another (B, L, N) is refused.  missing: what a caller without a context lacks, in that caller's words."""
+    none = context_lens is None and context_segments is None and token_segments is None and context_weights is None
+    if keys is not None:
+        if not none:
+            raise ValueError("keys stands for context_lens, context_segments, token_segments and context_weights: none of them beside it")
+        if keys.shape != (B, L, N):
+            raise ValueError(f"keys were checked for (B, L, N) = {keys.shape}, not for {(B, L, N)}")
+        return keys
+    if none:
+        return Keys(shape=(B, L, N))
+    if not has_context:
+        what = "context_lens needs" if context_lens is not None else "context_weights need" if context_weights is not None else \
+            "context_segments / token_segments need"
+        raise ValueError(f"{what} {missing}")
+    lens = host_lens(context_lens, B, L)
+    if context_weights is not None:
+        cs, ts, w = host_weights(context_weights, B, L, N, context_segments, token_segments, lens)
+        neutral = context_segments is None and token_segments is None
+        return Keys(None, cs, ts, w, (B, L, N), neutral, lens if neutral else None)
+    if context_segments is None and token_segments is None:
+        return Keys(lens, shape=(B, L, N))
+    if lens is not None:
+        raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
+    cs, ts = host_segments(context_segments, token_segments, B, L, N)
+    return Keys(None, cs, ts, None, (B, L, N))
 
 
 def segments_allowed(key_seg, query_mask):
@@ -746,6 +816,16 @@ def guidance_scales(value, timesteps, what="guidance_scale"):
         if not math.isfinite(v):
             raise ValueError(f"{what}: step {i}: the scale {v} must be finite")
     return out
+
+
+def guidance_parts(guidance_scale, timesteps):
+    """the ``guidance_scale`` keyword -> (scalar or None, schedule or None): a sequence is a loop's schedule, one scale per step
+    (``guidance_scales``), which a single step -- timesteps None -- refuses; anything else, a 0-d array or tensor included, is one scale, as it came"""
+    if isinstance(guidance_scale, (list, tuple, np.ndarray, torch.Tensor)) and np.ndim(guidance_scale) > 0:
+        if timesteps is None:
+            raise ValueError("guidance_scale: one step takes one scale (a sequence is a loop's schedule)")
+        return None, guidance_scales(guidance_scale, timesteps)
+    return guidance_scale, None
 
 
 def embed_rows(table, ids, kpad, out_dtype):

@@ -135,6 +135,42 @@ def _no_regions(regions):
         raise ValueError("a decode session serves no regional prompts (regions=): Pipeline.generate(regions=) does")
 
 
+class _SlotContexts:
+    """the contexts of a session's slots in one tensor [S, capacity, D] fp32, on the GPU: `capacity` rows when it is fixed, else as
+    many as the longest context admitted so far; a slot's rows behind its length are 0.  dirty: a slot's rows changed since the
+    cross K/V were prepared from the tensor."""
+
+    def __init__(self, slots, capacity=None):
+        self.slots, self.capacity = slots, capacity
+        self.tensor = None
+        self.dirty = True
+        self.lens = [1] * slots             # rows of every slot (a slot that holds none keeps a valid value)
+
+    def admit(self, slot, rows):
+        """slot `slot` holds `rows` [L_r, D] (on the device) from now on: grow to L_r rows if need be, fill, zero the tail"""
+        Lr, D = rows.shape
+        if self.tensor is None:
+            self.tensor = torch.zeros(self.slots, self.capacity or Lr, D, device=rows.device, dtype=torch.float32)
+        if D != self.tensor.shape[2]:
+            raise ValueError(f"every context of a session has the same width: {D} != {self.tensor.shape[2]}")
+        if Lr > self.tensor.shape[1]:               # no fixed capacity (submit checked the other case): it grows
+            grown = torch.zeros(self.slots, Lr, D, device=rows.device, dtype=torch.float32)
+            grown[:, :self.tensor.shape[1]] = self.tensor
+            self.tensor = grown
+        self.tensor[slot, :Lr] = rows
+        self.tensor[slot, Lr:] = 0
+        self.lens[slot] = Lr
+        self.dirty = True
+
+    def step_lens(self, uses):
+        """this step's length per slot -- or None when every slot of `uses` (one bool per slot) fills the capacity, which IS the step
+        without lengths"""
+        cap = self.tensor.shape[1]
+        if not any(u and n != cap for u, n in zip(uses, self.lens)):
+            return None
+        return [min(n, cap) for n in self.lens]
+
+
 class Request:
     """what submit() returns: the request's parameters, its schedule and where / when it ran"""
 
@@ -196,14 +232,14 @@ class DecodeSession:
         self._cpu = pipe._on_cpu()
         self._ids = None                    # GPU: [S, N] int64, one row per slot; CPU: one [1, N] tensor per slot
         self._rows = [None] * self.size
-        self._ctx = None                    # GPU, conditional: [S, capacity, context_dim] fp32, a slot's rows behind its length are 0
-        self._ctx_dirty = True              # a slot's context changed since the cross K/V were prepared
-        self._lens = [1] * self.size        # GPU, conditional: context rows of every slot (an idle slot keeps a valid value)
-        self._neg = None                    # GPU: [S, capacity_n, context_dim] fp32 once a request with a negative prompt was admitted
-        self._neg_dirty = True              # a slot's negative context changed since the negative K/V were prepared
-        self._neg_lens = [1] * self.size    # GPU: negative rows of every slot (a slot without a negative prompt keeps a valid value)
+        self._contexts = _SlotContexts(self.size, self.max_context_len)     # GPU, conditional: the contexts
+        self._negatives = _SlotContexts(self.size, self.max_negative_len)    # GPU: the negative contexts, once a request brought one
         self._records = (_lib.Slot * self.size)()
         self._guides = (_lib.SlotGuide * self.size)() if self.conditional else None
+
+    # the context tensor and its flag, as the session's own attributes (tests and tools poison padding rows through them)
+    _ctx = property(lambda self: self._contexts.tensor)
+    _ctx_dirty = property(lambda self: self._contexts.dirty, lambda self, dirty: setattr(self._contexts, "dirty", dirty))
 
     # -- requests -----------------------------------------------------------------------------------
     def submit(self, text=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_index=None, context=None, ids0=None,
@@ -347,14 +383,9 @@ class DecodeSession:
         tm, pm = pipe._edit_masks(img, mask, token_mask)
         with torch.no_grad():
             ids = pipe.to_latent(img)[1].reshape(1, pipe.num_tokens)
-        if tm is None and not self._cpu:
+        if not self._cpu:
             ids = ids.to(device, torch.long).clone(memory_format=torch.contiguous_format)
-            ids, _ = ops.mask_tokens(pm, pipe.patch_size, ids, pipe.mask_token_id)
-        else:
-            if tm is None:
-                p = pipe.patch_size
-                tm = pm.reshape(1, pm.shape[1] // p, p, pm.shape[2] // p, p).amax(dim=(2, 4)) != 0
-            ids = torch.where(tm.reshape(1, -1).to(ids.device), torch.full_like(ids, pipe.mask_token_id), ids)
+        ids, _ = pipe._masked_ids(ids, tm, pm)
         if preserve == "pixels":
             return ids[0], True, img[0], pm[0]
         return ids[0], True, None, None
@@ -398,10 +429,9 @@ class DecodeSession:
         if guidance_scale is not None:
             if not self.conditional:
                 raise ValueError("guidance_scale needs a text condition (an unconditional session IS the unconditional branch)")
-            if isinstance(guidance_scale, (list, tuple, torch.Tensor)) or (hasattr(guidance_scale, "ndim") and guidance_scale.ndim > 0):
-                scales = ops.guidance_scales(guidance_scale, timesteps)
-            else:
-                guidance_scale = float(guidance_scale)
+            scalar, scales = ops.guidance_parts(guidance_scale, timesteps)
+            if scales is None:
+                guidance_scale = float(scalar)
                 if not math.isfinite(guidance_scale):
                     raise ValueError("guidance_scale must be finite")
         negative = None
@@ -411,7 +441,7 @@ class DecodeSession:
             if guidance_scale is None:
                 raise ValueError("a negative prompt needs guidance_scale (the step moves away from it by that much)")
             if negative_context is None:
-                negative_context = self.pipe.text_model([negative_text])
+                negative_context = self.pipe._negative_context(negative_text, 1, False)[0]
                 if negative_context is None:
                     raise ValueError("the pipeline's text model gives no context for the negative prompt")
                 negative_context = negative_context[0]
@@ -511,13 +541,12 @@ class DecodeSession:
             ctx = None if r.context is None else r.context[None]
             neg = None if r.negative is None else r.negative[None]
             # an edit request: the step with a count per image, as Pipeline.edit's CPU branch takes it
-            seg = None if r.segments is None else (r.segments[0][None], r.segments[1][None])
-            if r.weights is not None:                   # the three arrays generate(prompt_weights=True) hands its CPU loop
-                seg = ops.host_weights(r.weights[None], 1, r.context.shape[0], pipe.num_tokens, *(seg or ()))
+            cs, ts = (None, None) if r.segments is None else (r.segments[0][None], r.segments[1][None])
+            keys = ops.host_keys(1, 0 if ctx is None else ctx.shape[1], pipe.num_tokens, None, cs, ts,
+                                 None if r.weights is None else r.weights[None], has_context=ctx is not None)
             ids, img = pipe._sample_cpu(self._rows[j], 0 if r.edit else r.nmask[t], ctx, r.topk, r.temps[t], None, r.seed + t,
-                                        r.scales[t] if r.scales else r.guidance_scale, None, r.ctemps[t] if r.ctemps else 0.0,
-                                        top_p=r.top_p, negative=neg, negative_lens=None, **({"counts": [r.nmask[t]]} if r.edit else {}),
-                                        **({"segments": seg} if seg is not None else {}))
+                                        r.scales[t] if r.scales else r.guidance_scale, keys, r.ctemps[t] if r.ctemps else 0.0,
+                                        top_p=r.top_p, negative=neg, negative_lens=None, **({"counts": [r.nmask[t]]} if r.edit else {}))
             self._rows[j] = ids
             r.done = t + 1
             if r.done == r.timesteps:
@@ -536,38 +565,14 @@ class DecodeSession:
         N, mask_id = pipe.num_tokens, pipe.mask_token_id
         if self._ids is None or self._ids.device != eng.device:
             self._ids = pipe._start_ids(self.size, None, eng.device)
-            self._ctx, self._ctx_dirty = None, True
-            self._neg, self._neg_dirty = None, True
+            self._contexts.tensor, self._contexts.dirty = None, True
+            self._negatives.tensor, self._negatives.dirty = None, True
         for r in admitted:
             self._ids[r.slot] = mask_id if r.ids0 is None else r.ids0[0].to(eng.device)
             if self.conditional:
-                c = r.context.to(eng.device)
-                Lr = c.shape[0]
-                if self._ctx is None:
-                    self._ctx = torch.zeros(self.size, self.max_context_len or Lr, c.shape[1], device=eng.device, dtype=torch.float32)
-                if c.shape[1] != self._ctx.shape[2]:
-                    raise ValueError(f"every context of a session has the same width: {c.shape[1]} != {self._ctx.shape[2]}")
-                if Lr > self._ctx.shape[1]:              # max_context_len None (submit checked the other case): the capacity grows
-                    grown = torch.zeros(self.size, Lr, c.shape[1], device=eng.device, dtype=torch.float32)
-                    grown[:, :self._ctx.shape[1]] = self._ctx
-                    self._ctx = grown
-                self._ctx[r.slot, :Lr] = c
-                self._ctx[r.slot, Lr:] = 0
-                self._lens[r.slot] = Lr
-                self._ctx_dirty = True
-            if r.negative is not None:                   # the same bookkeeping for the negative contexts
-                n = r.negative.to(eng.device)
-                Ln = n.shape[0]
-                if self._neg is None:
-                    self._neg = torch.zeros(self.size, self.max_negative_len or Ln, n.shape[1], device=eng.device, dtype=torch.float32)
-                if Ln > self._neg.shape[1]:
-                    grown = torch.zeros(self.size, Ln, n.shape[1], device=eng.device, dtype=torch.float32)
-                    grown[:, :self._neg.shape[1]] = self._neg
-                    self._neg = grown
-                self._neg[r.slot, :Ln] = n
-                self._neg[r.slot, Ln:] = 0
-                self._neg_lens[r.slot] = Ln
-                self._neg_dirty = True
+                self._contexts.admit(r.slot, r.context.to(eng.device))
+            if r.negative is not None:
+                self._negatives.admit(r.slot, r.negative.to(eng.device))
         if self.active == 0:
             return []
         retiring = []
@@ -596,33 +601,25 @@ class DecodeSession:
         if any(r is not None and r.edit for r in self.occupied):
             counts = [r.nmask[r.done] if r is not None and r.edit else -1 for r in self.occupied]
         want_aux = (any(not r.edit for r in retiring) and self.decode) or self.record_steps
-        ctx = self._ctx if self.conditional else None
-        keep = not self._ctx_dirty
+        ctx = self._contexts.tensor if self.conditional else None
+        keep = not self._contexts.dirty
         # one length per slot -- unless every occupied slot fills the capacity, which IS the step without lengths
-        lens = None
-        if self.conditional and any(r is not None and self._lens[j] != ctx.shape[1] for j, r in enumerate(self.occupied)):
-            lens = [min(n, ctx.shape[1]) for n in self._lens]
+        lens = self._contexts.step_lens([r is not None for r in self.occupied]) if self.conditional else None
 
         # the negative contexts: once a request brought one, every step hands the tensor over (or keeps its K/V), so that the set
         # outlives the steps in which no occupied slot uses it; lengths like the contexts', over the slots that have a negative prompt
-        neg, neg_lens = self._neg, None
-        keep_neg = neg is not None and not self._neg_dirty
-        if neg is not None and any(r is not None and r.negative is not None and self._neg_lens[j] != neg.shape[1]
-                                   for j, r in enumerate(self.occupied)):
-            neg_lens = [min(n, neg.shape[1]) for n in self._neg_lens]
+        neg = self._negatives.tensor
+        keep_neg = neg is not None and not self._negatives.dirty
+        neg_lens = None if neg is None else self._negatives.step_lens([r is not None and r.negative is not None for r in self.occupied])
 
-        # the regional slots' arrays -- None when no occupied slot is regional: the step without
+        # the regional and the weighted slots' arrays -- None when no occupied slot is regional / weighted: the step without
         segments = self._segment_arrays(ctx.shape[1]) if (self.regions or self.weights) and self.conditional else None
-        seg_kw = {} if segments is None else {"segments": segments}
-        # the weighted slots' array -- None when no occupied slot is weighted: the step without
         wts = self._weight_array(ctx.shape[1]) if self.weights and self.conditional else None
-        if wts is not None:
-            seg_kw["weights"] = wts
 
         def run(keep_context, keep_negative):
             return eng.step_slots(self._ids, ctx, self._records, use_graph=self.use_graph, keep_context=keep_context, want_aux=want_aux,
                                   guides=self._guides, context_lens=lens, choice=choice, negative_context=neg, negative_lens=neg_lens,
-                                  keep_negative=keep_negative, counts=counts, **seg_kw, **self._step_filters())
+                                  keep_negative=keep_negative, counts=counts, segments=segments, weights=wts, **self._step_filters())
         try:
             _, pred, score = run(keep, keep_neg)
         except _lib.PmhipError as e:
@@ -630,7 +627,7 @@ class DecodeSession:
             if not ((keep or keep_neg) and getattr(e, "code", None) == _lib.PMHIP_ESTATE):
                 raise
             _, pred, score = run(False, False)
-        self._ctx_dirty = self._neg_dirty = False
+        self._contexts.dirty = self._negatives.dirty = False
         for r in self.occupied:
             if r is not None:
                 r.done += 1

@@ -22,14 +22,18 @@ class Layer(nn.Module):
         self.ffnet = SwiGLUFFNFused(in_features=dim, hidden_features=mlp_dim)
 
     def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, want_maps=False,
-                control=None, inject_self=False):
+                control=None, inject_self=False, keys=None):
         """self-attn, cross-attn (a 2nd self-attn when context is None), SwiGLU (transformer.py:44-49).
         want_maps: -> (x, maps), maps f32 [B, N, L] the head-mean probabilities of the cross-attention (modules/attention.py).
         context_lens: per-image context lengths for the cross-attention only (modules/attention.py).
         context_segments / token_segments: regional prompts, for the cross-attention only (modules/attention.py).
         context_weights: prompt weights, for the cross-attention only (modules/attention.py).
         control / inject_self: prompt-to-prompt on a batch of pairs, the cross-attention's control and the injection into the first
-        self-attention (modules/attention.py)."""
+        self-attention (modules/attention.py).
+        keys (instead of the four arrays): the call's checked ``ops.Keys``; the cross-attention gets the record and, as keywords, the
+        record's own arrays."""
+        if keys is not None:
+            context_lens, context_segments, token_segments, context_weights = keys.cpu_args()
         B, N, D = x.shape
         T = compute_dtype_of(self)
         x = x.contiguous()
@@ -42,7 +46,8 @@ class Layer(nn.Module):
                            context_lens=context_lens if context is not None else None,
                            context_segments=context_segments if context is not None else None,
                            token_segments=token_segments if context is not None else None,
-                           context_weights=context_weights if context is not None else None, **kw)
+                           context_weights=context_weights if context is not None else None,
+                           keys=keys if context is not None else None, **kw)
         maps = None
         if want_maps:
             x, maps = x
@@ -64,28 +69,29 @@ class CondTransformer(nn.Module):
         self.to_logits = nn.Linear(dim, num_classes)
         _xavier_like_reference(self)
 
-    def _layers(self, h, maps_layers, *args, control=None):
-        """the tower; maps_layers (None, or the checked layer indices): -> (h, the mean of those layers' cross-attention maps);
+    def _layers(self, h, maps_layers, context, keys, control=None):
+        """the tower over the projected context and the call's checked ``ops.Keys``; maps_layers (None, or the checked layer
+        indices): -> (h, the mean of those layers' cross-attention maps);
         control (None, or per controlled layer its keywords): prompt-to-prompt, never beside maps_layers"""
         if control is not None:
             for i, layer in enumerate(self.layers):
-                h = layer(h, *args, **control.get(i, {}))
+                h = layer(h, context, keys=keys, **control.get(i, {}))
             return h
         if maps_layers is None:
             for layer in self.layers:
-                h = layer(h, *args)
+                h = layer(h, context, keys=keys)
             return h
         maps = None
         for i, layer in enumerate(self.layers):
             if i in maps_layers:
-                h, m = layer(h, *args, want_maps=True)
+                h, m = layer(h, context, keys=keys, want_maps=True)
                 maps = m if maps is None else maps + m
             else:
-                h = layer(h, *args)
+                h = layer(h, context, keys=keys)
         return h, maps / len(maps_layers)
 
     def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
-                maps_layers=None, control=None):
+                maps_layers=None, control=None, keys=None):
         """operator-level composition of transformer.py:80-93 (Pipeline uses the native engine instead).
         maps_layers (extension, attention maps; None = the call as without it): distinct layer indices ->
         (logits, maps), the logits as without it and maps f32 [B, N, L], the mean over those layers of the head-mean probabilities
@@ -96,42 +102,24 @@ class CondTransformer(nn.Module):
         context_weights [B, L] (extension, prompt weights; beside the segments, beside context_lens, or alone): likewise.
         control (extension, prompt-to-prompt; None = the call as without it): a dict with row_map, blend, gain
         ([B / 2, L]; required iff cross_layers), cross_layers and self_layers (distinct layer indices) over a batch of B / 2 pairs, the
-        source images in front -- ``S2Engine.forward_control`` as a composition of operators.  Beside context_lens only."""
+        source images in front -- ``S2Engine.forward_control`` as a composition of operators.  Beside context_lens only.
+        keys (instead of the four arrays): the call's checked ``ops.Keys``; it is not checked again."""
+        keys = ops.host_keys(x.shape[0], 0 if context is None else context.shape[1], x.shape[1], context_lens, context_segments,
+                             token_segments, context_weights, has_context=context is not None, keys=keys)
         if control is not None:
-            if context is None or context_segments is not None or token_segments is not None or context_weights is not None or \
-                    maps_layers is not None or x.shape[0] % 2:
+            if context is None or keys.context_segments is not None or maps_layers is not None or x.shape[0] % 2:
                 raise ValueError("control needs a context and an even batch, and stands beside context_lens only")
-            cl, sl = [int(l) for l in control.get("cross_layers", ())], [int(l) for l in control.get("self_layers", ())]
-            for ls in (cl, sl):
-                if len(set(ls)) != len(ls) or (ls and (min(ls) < 0 or max(ls) >= len(self.layers))):
-                    raise ValueError(f"control: layers {ls!r} must be distinct indices in [0, {len(self.layers)})")
+            cl, sl = (ops.host_layers(control.get(k, ()), len(self.layers), "control: layers", allow_empty=True)
+                      for k in ("cross_layers", "self_layers"))
             arrays = [control.get(k) for k in ("row_map", "blend", "gain")]
             if not (cl or sl) or any(a is None for a in arrays) != (not cl) or any(a is None for a in arrays) != all(a is None for a in arrays):
                 raise ValueError("control: a layer must be chosen; row_map, blend and gain are required with cross_layers and refused without")
             ctl = ops.host_control(*arrays, x.shape[0] // 2, context.shape[1]) if cl else None
             control = {l: (dict(control=ctl) if l in cl else {}) | (dict(inject_self=True) if l in sl else {}) for l in set(cl) | set(sl)}
-        if context_lens is not None:
-            if context is None:
-                raise ValueError("context_lens needs a context (context None IS the unconditional branch)")
-            context_lens = ops.host_lens(context_lens, x.shape[0], context.shape[1])
-        if context_segments is not None or token_segments is not None:
-            if context is None:
-                raise ValueError("context_segments / token_segments need a context (context None IS the unconditional branch)")
-            if context_lens is not None:
-                raise ValueError("context_segments and context_lens exclude each other (mark padding rows with segment 255)")
-            context_segments, token_segments = ops.host_segments(context_segments, token_segments, x.shape[0], context.shape[1], x.shape[1])
-        if context_weights is not None:
-            if context is None:
-                raise ValueError("context_weights need a context (context None IS the unconditional branch)")
-            context_segments, token_segments, context_weights = ops.host_weights(context_weights, x.shape[0], context.shape[1], x.shape[1],
-                                                                                 context_segments, token_segments, context_lens)
-            context_lens = None                                    # the neutral segments carry the lengths
         if maps_layers is not None:
-            maps_layers = [int(l) for l in maps_layers]
             if context is None:
                 raise ValueError("maps_layers: the maps are those of the cross-attention: a context is required")
-            if not maps_layers or len(set(maps_layers)) != len(maps_layers) or min(maps_layers) < 0 or max(maps_layers) >= len(self.layers):
-                raise ValueError(f"maps_layers {maps_layers!r} must be distinct indices in [0, {len(self.layers)})")
+            maps_layers = ops.host_layers(maps_layers, len(self.layers), "maps_layers")
         T = compute_dtype_of(self)
         B, N, E = x.shape
         dim = self.token_proj.out_features
@@ -141,7 +129,7 @@ class CondTransformer(nn.Module):
             h = self.token_proj(x.float()) + self.position_embedding
             if context is not None:
                 context = self.context_proj(context.float())
-            h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights, control=control)
+            h = self._layers(h, maps_layers, context, keys, control=control)
             if maps_layers is not None:
                 return self.to_logits(self.norm(h[0])), h[1]
             return self.to_logits(self.norm(h))
@@ -155,7 +143,7 @@ class CondTransformer(nn.Module):
             if isinstance(self.context_proj, nn.Linear):
                 c = ops.gemm(c, packing.pad_cols(self.context_proj.weight, c.shape[1], T))
             context = c.reshape(B, L, dim)
-        h = self._layers(h, maps_layers, context, context_lens, context_segments, token_segments, context_weights, control=control)
+        h = self._layers(h, maps_layers, context, keys, control=control)
         maps = None
         if maps_layers is not None:
             h, maps = h

@@ -289,7 +289,8 @@ def test_generate_with_regions_composes_with_guidance_and_a_negative_prompt(rows
             skw.update(negative_text=neg, negative_context_lens=lens)
         for step in range(3):
             opts = pipe._options(3, None, skw.get("guidance_scale"), None, None, context, 3, skw.get("negative_text"), skw.get("negative_context_lens"))
-            step_ids, img = pipe._step(step_ids, nmask[step], context, opts, temps[step], 0.0, seed=5 + step, segments=(ks, qm))
+            step_ids, img = pipe._step(step_ids, nmask[step], context, opts, temps[step], 0.0, seed=5 + step,
+                                       keys=ops.host_keys(3, context.shape[1], pipe.num_tokens, None, ks, qm))
             assert torch.equal(img, imgs[step]), (kw, step)
         assert torch.equal(step_ids, ids), kw
     plain = pipe.generate(texts, timesteps=3, topk=3, save_interval=1, seed=5, return_ids=True)[1]

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import paintmind_amd as pm
-from paintmind_amd import _lib
+from paintmind_amd import _lib, ops
 from paintmind_amd.generate import MAX_REGIONS, Pipeline, region_layout
 from paintmind_amd.serve import DecodeSession, FilterSession
 from util import load_golden, to_torch_sd
@@ -129,7 +129,7 @@ def test_context_tensors_instead_of_text(pipe):
     assert torch.equal(r.context, torch.cat([glob, reg])) and r.segments[0].tolist() == [0] * 20 + [1] * 30
     ctx, ks, qm = region_layout([[glob, reg]], [[tm]], pipe.image_size, pipe.patch_size)
     opts = pipe._options(3, None, None, None, None, ctx, 1, timesteps=2)
-    ids = pipe._generate_cpu(ctx, 1, 2, 1.0, opts, 1, 3, True, (ks, qm))[1]
+    ids = pipe._generate_cpu(ctx, 1, 2, 1.0, opts, 1, 3, True, ops.host_keys(1, ctx.shape[1], pipe.num_tokens, None, ks, qm))[1]
     assert torch.equal(session.drain()[0].ids, ids[0])
     with pytest.raises(ValueError, match=r"\(context \[L_r, D\], mask\) pair"):
         session.submit(context=glob, regions=[("d:30", tm)])

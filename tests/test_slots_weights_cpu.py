@@ -123,7 +123,7 @@ def test_a_weights_session_equals_generate_request_by_request(pipe):
     want = [pipe.generate([EMPH], prompt_weights=True, seed=11, **g), pipe.generate([PLAIN], seed=12, **g),
             pipe.generate(["the sky"], prompt_weights=True, regions=[[("(x:3) y", top, 0.5)]], seed=13, **g)]
     opts = pipe._options(4, None, None, None, None, ctx, 1, None, None, 3)
-    want.append(pipe._generate_cpu(ctx, 1, 3, 1.0, opts, 1, 14, True, ops.host_weights(w, 1, LMAX, pipe.num_tokens)))
+    want.append(pipe._generate_cpu(ctx, 1, 3, 1.0, opts, 1, 14, True, ops.host_keys(1, LMAX, pipe.num_tokens, context_weights=w)))
     for i, (imgs, ids) in enumerate(want):
         assert torch.equal(done[i].ids, ids[0]), i
         assert torch.equal(done[i].image, imgs[-1][0]), i

@@ -287,7 +287,7 @@ def test_regions_with_a_third_element(pipe):
     kw = dict(timesteps=3, topk=4, save_interval=1, seed=5, return_ids=True)
     _, ids_w = pipe.generate(texts, regions=[[("d", left, 0.25)], []], **kw)
     opts = pipe._options(4, None, None, None, None, ctx3, 2, None, None, 3)
-    _, ids_e = pipe._generate_cpu(ctx3, 2, 3, 1.0, opts, 1, 5, True, ops.host_weights(w3, 2, ctx3.shape[1], pipe.num_tokens, ks3, qm3))
+    _, ids_e = pipe._generate_cpu(ctx3, 2, 3, 1.0, opts, 1, 5, True, ops.host_keys(2, ctx3.shape[1], pipe.num_tokens, None, ks3, qm3, w3))
     assert torch.equal(ids_w, ids_e)
     _, ids_2 = pipe.generate(texts, regions=[[("d", left)], []], **kw)
     _, ids_1 = pipe.generate(texts, regions=[[("d", left, 1.0)], []], **kw)
@@ -335,7 +335,7 @@ def _explicit(pipe, context, weights, lens, kw):
     """the CPU loop on an explicit context with explicit weights (what generate builds from the prompts)"""
     B = context.shape[0]
     opts = pipe._options(kw["topk"], None, None, None, None, context, B, None, None, kw["timesteps"])
-    seg = None if weights is None else ops.host_weights(weights, B, context.shape[1], pipe.num_tokens, context_lens=lens)
+    seg = None if weights is None else ops.host_keys(B, context.shape[1], pipe.num_tokens, context_lens=lens, context_weights=weights)
     if weights is None and lens is not None:
         opts = opts._replace(lens=list(lens))
     return pipe._generate_cpu(context, B, kw["timesteps"], 1.0, opts, kw["save_interval"], kw["seed"], True, seg)

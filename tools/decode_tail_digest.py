@@ -6,6 +6,9 @@ One JSON line per case with a sha256 of every output tensor; inputs come from fi
 tolerance; this is for "bit for bit what another commit computes": run it on two built checkouts on one box and diff the files
 (profiles/decode_tail_digest_*.jsonl).  Only the public Python surface (ops, Pipeline) is used, so any commit that has the
 nucleus filter (and so wide top-k, choice temperatures, context lengths and per-request guidance) can be the other side.
+The last section -- regional prompts, prompt weights, a negative prompt under a schedule, edit, the attention maps and a session
+that mixes the request kinds -- needs a commit that has prompt weights in sessions and the maps
+(profiles/host_keys_digest_*.jsonl).
 """
 import argparse
 import hashlib
@@ -206,6 +209,50 @@ def main():
                 s.submit(context=ctx[i], timesteps=steps, temperature=temp, topk=topk, seed=100 + i, image_index=2 ** 33 + i, guidance_scale=scale)
             for f in sorted(s.drain(), key=lambda f: f.handle.number):
                 emit(f"session {tag} graph={int(graph)} request={f.handle.number}", ids=f.ids, image=f.image)
+        # the host request path: what says which context rows a token attends to (regional prompts, prompt weights alone and beside
+        # lengths), a negative prompt under a guidance schedule, edit, the attention maps, and a session that mixes the request kinds
+        krng = np.random.default_rng(17)
+        ks = np.array([[0, 0, 1, 1, 255], [0, 1, 2, 255, 255], [0, 0, 0, 0, 1]], np.uint8)
+        qm = (1 | (krng.integers(0, 4, (B, Nt)) << 1)).astype(np.uint32)
+        w = np.array([[1, 1.4, 0.5, 2, 1], [1, 1, 0.25, 1, 1], [3, 1, 1, 1, 0]], np.float32)
+        neg = ctx[1:4, :3].contiguous()
+        key_cases = [("segments", dict(context_segments=ks, token_segments=qm)), ("weights", dict(context_weights=w)),
+                     ("weights lens", dict(context_weights=w, context_lens=lens)),
+                     ("negative schedule", dict(negative_context=neg, negative_lens=[3, 1, 2], guidance_scale=[0.5, 1.0, 2.0, 3.0]))]
+        for name, kw in key_cases:
+            for graph, calls in ((False, 1), (True, 3)):
+                for call in range(calls):
+                    ids, imgs = pipe.generate_ids(full, B, T, 0.9, 5, flags, seed=1234, image_base=2 ** 33, use_graph=graph, streams=1, **kw)
+                    emit(f"generate_ids {tag} {name} graph={int(graph)} call={call}", ids=ids, imgs=imgs)
+            ids, imgs = pipe.generate_ids(full, B, T, 0.9, 5, flags, seed=1234, image_base=2 ** 33, use_graph=False, streams=2, **kw)
+            emit(f"generate_ids {tag} {name} lanes=2", ids=ids, imgs=imgs)
+        for name, kw in key_cases[:3] + [("lens", dict(context_lens=lens))]:
+            maps, logits = pipe.attention_maps(ids=t(start), text=full, return_logits=True, **kw)
+            emit(f"attention_maps {tag} {name}", maps=maps, logits=logits)
+        pixels = t((krng.random((2, pipe.image_size, pipe.image_size)) < 0.02).astype(np.uint8))
+        env = os.environ.get("PMHIP_GENERATE_GRAPH")
+        for graph, calls in ((False, 1), (True, 3)):
+            os.environ["PMHIP_GENERATE_GRAPH"] = str(int(graph))
+            for call in range(calls):
+                img, ids = pipe.edit(picture, mask=pixels, text=prompts[:2], timesteps=3, temperature=0.9, topk=5, seed=9, preserve="pixels",
+                                     guidance_scale=2.0, negative_text="d", mask_padding=True, return_ids=True)
+                emit(f"edit {tag} pixels graph={int(graph)} call={call}", ids=ids, img=img)
+        if env is None:
+            del os.environ["PMHIP_GENERATE_GRAPH"]
+        else:
+            os.environ["PMHIP_GENERATE_GRAPH"] = env
+        g = pipe.image_size // pipe.patch_size
+        corner = torch.zeros(g, g, dtype=torch.bool)
+        corner[:g // 2, :g // 2] = True
+        for graph in (False, True):
+            s = pipe.decode_session(slots=4, conditional=True, use_graph=graph, regions=True, weights=True)
+            s.submit(context=ctx[0], timesteps=3, temperature=1.0, topk=5, seed=300, image_index=2 ** 33)
+            s.submit(context=ctx[1, :3], regions=[(ctx[2, :2], corner)], timesteps=4, temperature=0.7, topk=3, seed=301, image_index=2 ** 33 + 1)
+            s.submit(context=(ctx[2, :4], w[0, :4]), timesteps=2, temperature=1.3, topk=8, seed=302, image_index=2 ** 33 + 2)
+            s.submit(context=ctx[3], negative_context=ctx[0, :2], guidance_scale=[2.0, 1.0, 0.5], timesteps=3, temperature=0.9, topk=5, seed=303,
+                     image_index=2 ** 33 + 3)
+            for f in sorted(s.drain(), key=lambda f: f.handle.number):
+                emit(f"session mixed {tag} graph={int(graph)} request={f.handle.number}", ids=f.ids, image=f.image)
     pipe.set_compute_dtype(torch.float32)
     if out:
         out.close()
