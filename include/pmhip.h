@@ -373,6 +373,49 @@ int pmhip_attention_control(int dtype, const void* Qs, const void* Ks, const voi
                             const int32_t* row_map, const float* blend, const float* gain, const int32_t* lens_s, const int32_t* lens_t,
                             pmhip_stream stream);
 
+/* Phrase score: where a prompt-to-prompt pair looks at a phrase, summed over the phrase's context rows and averaged over the heads
+ * (new entry within ABI 11, nothing existing changes meaning).  The operands, layouts, lengths and control
+ * arrays are those of pmhip_attention_control without Vt / out; row_map, blend and gain may be NULL, all three together: no control.
+ *     w_s DEVICE f32 [B, Ls], w_t DEVICE f32 [B, Lt]: the phrase's row weights, finite and >= 0, typically 0 / 1
+ *     score_s, score_t DEVICE f32 [B, Nq], contiguous
+ * For every pair b and query q, with ps, pt, has and P exactly as pmhip_attention_control defines them (P = pt without control):
+ *     vs = scale / heads * sum_h sum_{k < ns} w_s[b,k] * ps_h[q,k]        score_s[b,q] = accumulate ? score_s[b,q] + vs : vs
+ *     vt = scale / heads * sum_h sum_{j < nt} w_t[b,j] * P_h[q,j]         score_t[b,q] = accumulate ? score_t[b,q] + vt : vt
+ * Contract:
+ *   - select, not arithmetic: a key at or behind the pair's length reaches nothing -- its K row and its weight are never read, NaN
+ *     included; a map entry at or behind ns is `none`; a row of weight 0 takes part in the softmax and adds nothing.  K rows below
+ *     ns / nt must be finite; the ranges of the weights, blend and gain are the caller's to validate (the model-level entry does)
+ *   - memory: nothing outside the two [B, Nq] extents is written; w_s is read in [B, Ls], w_t and the control arrays in [B, Lt]
+ *   - determinism: the sums over the heads (h = 0 .. heads-1) and the keys run in a fixed order; no floating-point atomics; every
+ *     element is written by exactly one thread, once per launch; two launches on the same inputs agree bit for bit; pair b's rows
+ *     do not depend on what else is in the batch
+ *   - precision: P stays f32 in both dtypes -- the score reports the probabilities of the Q and K given, not the bf16-rounded
+ *     values pmhip_attention_control feeds its P.V MFMA.  The bound is in tests/blend_ref.py
+ * Shapes as pmhip_attention_control: any dim_head the _dh entry serves, heads <= 64, B * heads <= 65535, any Ls and Lt (two passes
+ * over both contexts per head; registers do not depend on them, and there is no LDS).  bf16 with dim_head 64 runs on MFMA (64 queries
+ * per workgroup, 16 per wave; Q and K 16-byte aligned); fp32 and every other dim_head run a plain vector-ALU kernel, 4 lanes per
+ * query.  A NULL operand, weight or score array, a partly given control triple, or a shape outside the above: PMHIP_EINVAL before any
+ * launch. */
+int pmhip_attention_phrase_score(int dtype, const void* Qs, const void* Ks, const void* Qt, const void* Kt, int B, int heads, int dim_head,
+                                 int Nq, int Ls, int Ls_pad, int Lt, int Lt_pad, int use_exp2, const int32_t* row_map, const float* blend,
+                                 const float* gain, const int32_t* lens_s, const int32_t* lens_t, const float* w_s, const float* w_t,
+                                 float* score_s, float* score_t, float scale, int accumulate, pmhip_stream stream);
+
+/* The blend region of a pair from its two phrase scores: the rule of Pipeline.phrase_mask on both halves,
+ * joined, then dilated.  score_s, score_t DEVICE f32 [B, g*g] (finite), mask_out DEVICE uint8 [B, g*g], 0 or 1:
+ *     m_x[b,t] = score_x[b,t] >= threshold * max_t' score_x[b,t']        (one f32 product, an f32 compare)
+ *     mask[b]  = dilate^grow (m_s[b] | m_t[b])                            a 3 x 3 maximum on the g x g grid, borders clipped
+ * 0 < threshold <= 1, grow >= 0, 1 <= g <= 64, else PMHIP_EINVAL.  One workgroup per pair, the grid in LDS.  A maximum has no order
+ * and the product is one rounding: given the same score bits the mask is exact.  An all-zero score row yields an all-true mask. */
+int pmhip_phrase_region(const float* score_s, const float* score_t, uint8_t* mask_out, int B, int g, float threshold, int grow,
+                        pmhip_stream stream);
+
+/* The token blend under a region: mask DEVICE uint8 [B, N]; pred, merged DEVICE int64 [B, N], score DEVICE f32
+ * [B, N], the _s arrays of the source half, the _t arrays of the edited half.  Where mask == 0 the three _t arrays take the _s arrays'
+ * values; where mask != 0 they are untouched.  The _s arrays and the mask are read only; nothing else is written. */
+int pmhip_blend_tokens(const uint8_t* mask, const int64_t* pred_s, const int64_t* merged_s, const float* score_s, int64_t* pred_t,
+                       int64_t* merged_t, float* score_t, int B, int N, pmhip_stream stream);
+
 /* torch.nn.LayerNorm over the last dim, eps inside the sqrt (stage1/layers.py:49,51,89,128;
  * stage2/transformer.py:37,39,41,62).  x fp32 [M,D] -> out (`out_dtype`). */
 int pmhip_layernorm(const float* x, const float* gamma, const float* beta, float eps, void* out,
@@ -1226,6 +1269,25 @@ int pmhip_s2_forward_maps(pmhip_s2* h, const float* tokens, const float* context
 int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
                              uint64_t cross_bits, uint64_t self_bits, const int32_t* row_map_host, const float* blend_host,
                              const float* gain_host, float* logits_out, pmhip_stream stream);
+/* pmhip_s2_forward_control with the PHRASE-SCORE tap (new entry within ABI 11, nothing existing changes meaning; DESIGN.md section
+ * 4zc): the arguments of pmhip_s2_forward_control, and
+ *   score_bits   bit l set: layer l issues one pmhip_attention_phrase_score directly behind its cross-attention launch, on that
+ *                layer's scaled Q and cached K of the two halves, under the call's lengths; with the control arrays if the layer is in
+ *                cross_bits, with NULL otherwise.  scale = 1 / popcount(score_bits); the first tapped layer writes unless
+ *                `accumulate` != 0, later tapped layers accumulate
+ *   w_src_host, w_edit_host  f32 [B, L]: the phrase's row weights of the source and of the edited prompt, one row per pair
+ *   scores       DEVICE f32 [2B, tokens], the source half in front
+ *   - cross_bits | self_bits == 0 is allowed here: the logits are then those of pmhip_s2_forward_lens / pmhip_s2_forward on the 2B
+ *     images, bit for bit.  In every other case they are those of pmhip_s2_forward_control on the same arguments, bit for bit
+ *   - validation happens before anything is launched: the checks of pmhip_s2_forward_control (but for the one above), plus:
+ *     score_bits != 0 with no bit at or above depth, the three pointers non-NULL, every weight finite and >= 0, every pair with a
+ *     positive weight below its length in at least one half
+ *   - the weights travel through the control staging ring, behind the control arrays
+ *   - eager only: no key is added to the graph cache, and the tap is cleared with the control on every way out */
+int pmhip_s2_forward_control_scores(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                    uint64_t cross_bits, uint64_t self_bits, const int32_t* row_map_host, const float* blend_host,
+                                    const float* gain_host, uint64_t score_bits, const float* w_src_host, const float* w_edit_host,
+                                    float* logits_out, float* scores, int accumulate, pmhip_stream stream);
 int pmhip_pipeline_sample_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                   const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
                                   uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,

@@ -242,6 +242,13 @@ PROTOTYPES = {
     # cross-attention control: the edited pass of a prompt-to-prompt pair, blended from the source pass
     "pmhip_attention_control": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "pmhip_s2_forward_control": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), u64, u64, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), vp, vp]),
+    # local blend: where a pair looks at a phrase, the region that follows, the token blend under it
+    "pmhip_attention_phrase_score": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                           f32, i32, vp]),
+    "pmhip_s2_forward_control_scores": (i32, [vp, vp, vp, i32, i32, C.POINTER(i32), u64, u64, C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), u64,
+                                              C.POINTER(f32), C.POINTER(f32), vp, vp, i32, vp]),
+    "pmhip_phrase_region": (i32, [vp, vp, vp, i32, i32, f32, i32, vp]),
+    "pmhip_blend_tokens": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

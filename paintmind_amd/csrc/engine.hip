@@ -222,6 +222,16 @@ struct CrossKV {            // cached cross-attention K / V^T of a static contex
     const float* ctl_blend = nullptr;
     const float* ctl_gain = nullptr;
     bool ctl_self = false;
+    // the phrase-score tap (pmhip_s2_forward_control_scores only), THIS call's or NULL: the phrase's row weights of the
+    // two halves, device f32 [B / 2, L] each, and the two halves of the score buffer, device f32 [B / 2, tokens] each.  A layer whose
+    // set carries them issues one pmhip_attention_phrase_score directly behind its cross-attention launch -- under the layer's control
+    // arrays where it has them --, with this scale, writing or accumulating.
+    const float* phr_w_src = nullptr;
+    const float* phr_w_edit = nullptr;
+    float* phr_src = nullptr;
+    float* phr_edit = nullptr;
+    float phr_scale = 1.f;
+    bool phr_accumulate = false;
 };
 
 // The bf16 hi/lo residual stream + folded LayerNorm is the DEFAULT of bf16 mode (PMHIP_HILO=0, read when a handle is created, restores
@@ -518,6 +528,16 @@ int layer_forward(int dtype, const pmhip_layer_weights& L, const pmhip_tower_cfg
             if (cross->maps)
                 PM_TRY(pmhip_attention_maps(dtype, a.Q, a.K, cross->maps, cross->L, B, tc.heads, dh, tokens, cross->L, cross->Lp, fast, a.lens,
                                             a.key_seg, a.query_mask, a.key_bias, cross->maps_scale, cross->maps_accumulate, s));
+            // the phrase-score tap: where the pair looks at the phrase, from the same Q, K, lengths and control arrays
+            if (cross->phr_src) {
+                const PairHalf e(dtype, B);
+                PM_TRY(pmhip_attention_phrase_score(dtype, b.q, cross->k, e.of(b.q, (size_t)tc.heads * tokens * dh),
+                                                    e.of(cross->k, (size_t)tc.heads * cross->Lp * dh), e.half, tc.heads, dh, tokens, cross->L,
+                                                    cross->Lp, cross->L, cross->Lp, fast, cross->ctl_map, cross->ctl_blend, cross->ctl_gain,
+                                                    cross->lens, cross->lens ? cross->lens + e.half : nullptr, cross->phr_w_src,
+                                                    cross->phr_w_edit, cross->phr_src, cross->phr_edit, cross->phr_scale, cross->phr_accumulate,
+                                                    s));
+            }
         } else {
             void* outs[3] = {b.q, b.k, b.vt};
             PM_TRY(ln_heads(dtype, b, L.lnx_g, L.lnx_b, L.wqkv2, L.wqkv2_f, L.qkv2_c, L.qkv2_d, M, dim, tc.heads, dh, tokens, Np, 3, kinds_qkv,
@@ -1534,16 +1554,23 @@ extern "C" int pmhip_s2_forward_maps(pmhip_s2* h, const float* tokens, const flo
 // One eager forward over B pairs: images [0, B) carry the source prompts, [B, 2B) the edited ones.  The layers of
 // cross_bits run the edited half's cross-attention under control, the layers of self_bits its first self-attention on the source
 // half's Q and K.  Everything is checked before anything is launched; the layers' sets carry the control for this one tower only.
-extern "C" int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
-                                        uint64_t cross_bits, uint64_t self_bits, const int32_t* row_map_host, const float* blend_host,
-                                        const float* gain_host, float* logits_out, pmhip_stream stream) {
-    const char* who = "s2_forward_control";
+static int s2_forward_control_impl(const char* who, pmhip_s2* h, const float* tokens, const float* context, int L, int B,
+                                   const int32_t* ctx_lens_host, uint64_t cross_bits, uint64_t self_bits, const int32_t* row_map_host,
+                                   const float* blend_host, const float* gain_host, float* logits_out, pmhip_stream stream,
+                                   bool with_scores = false, uint64_t score_bits = 0, const float* w_src_host = nullptr,
+                                   const float* w_edit_host = nullptr, float* scores = nullptr, int accumulate = 0) {
     PM_REQUIRE(h && tokens && logits_out && B > 0 && B <= (1 << 20), "%s: bad arguments", who);
     const int depth = h->cfg.tower.depth, B2 = 2 * B;
     PM_REQUIRE(context && L > 0, "%s: the control is that of the cross-attention: a context is required", who);
-    PM_REQUIRE((cross_bits | self_bits) != 0, "%s: cross_bits and self_bits select no layer", who);
+    if (with_scores)
+        PM_REQUIRE(score_bits != 0 && w_src_host && w_edit_host && scores,
+                   "%s: score_bits selects no layer, or w_src_host / w_edit_host / scores is NULL (pmhip_s2_forward_control is the entry without scores)", who);
+    else
+        PM_REQUIRE((cross_bits | self_bits) != 0, "%s: cross_bits and self_bits select no layer", who);
     PM_REQUIRE(depth >= 64 || ((cross_bits | self_bits) >> depth) == 0, "%s: cross_bits 0x%llx / self_bits 0x%llx select a layer at or above depth=%d",
                who, (unsigned long long)cross_bits, (unsigned long long)self_bits, depth);
+    PM_REQUIRE(depth >= 64 || (score_bits >> depth) == 0, "%s: score_bits 0x%llx selects a layer at or above depth=%d", who,
+               (unsigned long long)score_bits, depth);
     const int given = (row_map_host != nullptr) + (blend_host != nullptr) + (gain_host != nullptr);
     PM_REQUIRE(given == (cross_bits ? 3 : 0), "%s: row_map_host, blend_host and gain_host are required with cross_bits and refused without", who);
     PM_TRY(check_ctx_lens(who, ctx_lens_host, true, L, B2));
@@ -1555,21 +1582,44 @@ extern "C" int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const 
         PM_REQUIRE(std::isfinite(gain_host[i]) && gain_host[i] >= 0.f, "%s: pair %d: row %d: gain %g must be finite and >= 0", who, b, j,
                    (double)gain_host[i]);
     }
+    for (int b = 0; with_scores && b < B; ++b) {              // the phrase's rows: finite, >= 0, and something to look at in one half
+        bool any = false;
+        for (int half = 0; half < 2; ++half) {
+            const float* w = (half ? w_edit_host : w_src_host) + (size_t)b * L;
+            const int len = ctx_lens_host ? ctx_lens_host[half * B + b] : L;
+            for (int j = 0; j < L; ++j) {
+                PM_REQUIRE(std::isfinite(w[j]) && w[j] >= 0.f, "%s: pair %d: %s row %d: weight %g must be finite and >= 0", who, b,
+                           half ? "edited" : "source", j, (double)w[j]);
+                any |= j < len && w[j] > 0.f;
+            }
+        }
+        PM_REQUIRE(any, "%s: pair %d: no row of the phrase has a positive weight below its length in either half", who, b);
+    }
     hipStream_t s = (hipStream_t)stream;
     const int M = B2 * h->cfg.tokens;
     PM_TRY(s2_prepare_context(h, context, L, B2, s));
     PM_TRY(s2_set_ctx_lens(h, ctx_lens_host, L, B2, s));
     unsigned char* dctl = nullptr;
+    unsigned char* dw = nullptr;
     const size_t part = (n * 4 + 15) & ~(size_t)15;
-    if (cross_bits) {
-        WS(h->ws, "ctl.arrays", 3 * part, dctl);
-        std::vector<unsigned char> packed(3 * part, 0);
-        memcpy(packed.data(), row_map_host, n * 4);
-        memcpy(packed.data() + part, blend_host, n * 4);
-        memcpy(packed.data() + 2 * part, gain_host, n * 4);
-        PM_TRY(h->ctl_ring.reserve(3 * part));
+    if (cross_bits || with_scores) {                          // one trip through the control ring: row_map | blend | gain, then w_src | w_edit
+        const size_t ctl_bytes = cross_bits ? 3 * part : 0, w_bytes = with_scores ? 2 * part : 0;
+        if (cross_bits) WS(h->ws, "ctl.arrays", ctl_bytes, dctl);
+        if (with_scores) WS(h->ws, "ctl.weights", w_bytes, dw);
+        std::vector<unsigned char> packed(ctl_bytes + w_bytes, 0);
+        if (cross_bits) {
+            memcpy(packed.data(), row_map_host, n * 4);
+            memcpy(packed.data() + part, blend_host, n * 4);
+            memcpy(packed.data() + 2 * part, gain_host, n * 4);
+        }
+        if (with_scores) {
+            memcpy(packed.data() + ctl_bytes, w_src_host, n * 4);
+            memcpy(packed.data() + ctl_bytes + part, w_edit_host, n * 4);
+        }
+        PM_TRY(h->ctl_ring.reserve(ctl_bytes + w_bytes));
         PM_TRY(h->ctl_ring.acquire());
-        PM_TRY(h->ctl_ring.stage(dctl, 0, packed.data(), 3 * part, s));
+        if (cross_bits) PM_TRY(h->ctl_ring.stage(dctl, 0, packed.data(), ctl_bytes, s));
+        if (with_scores) PM_TRY(h->ctl_ring.stage(dw, ctl_bytes, packed.data() + ctl_bytes, w_bytes, s));
         PM_TRY(h->ctl_ring.commit(s));
     }
     void* tp;
@@ -1577,8 +1627,17 @@ extern "C" int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const 
     PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
     struct Control {                                          // cleared on every way out
         std::vector<CrossKV>& kv;
-        ~Control() { for (auto& ck : kv) { ck.ctl_map = nullptr; ck.ctl_blend = nullptr; ck.ctl_gain = nullptr; ck.ctl_self = false; } }
+        ~Control() {
+            for (auto& ck : kv) {
+                ck.ctl_map = nullptr; ck.ctl_blend = nullptr; ck.ctl_gain = nullptr; ck.ctl_self = false;
+                ck.phr_w_src = nullptr; ck.phr_w_edit = nullptr; ck.phr_src = nullptr; ck.phr_edit = nullptr;
+                ck.phr_scale = 1.f; ck.phr_accumulate = false;
+            }
+        }
     } control{h->cross};
+    int tapped = 0;
+    for (size_t l = 0; l < h->cross.size() && l < 64; ++l) tapped += (int)((score_bits >> l) & 1);
+    bool first = true;
     for (size_t l = 0; l < h->cross.size() && l < 64; ++l) {
         CrossKV& ck = h->cross[l];
         if ((cross_bits >> l) & 1) {
@@ -1587,8 +1646,34 @@ extern "C" int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const 
             ck.ctl_gain = reinterpret_cast<const float*>(dctl + 2 * part);
         }
         ck.ctl_self = ((self_bits >> l) & 1) != 0;
+        if (with_scores && ((score_bits >> l) & 1)) {
+            ck.phr_w_src = reinterpret_cast<const float*>(dw);
+            ck.phr_w_edit = reinterpret_cast<const float*>(dw + part);
+            ck.phr_src = scores; ck.phr_edit = scores + (size_t)B * h->cfg.tokens;
+            ck.phr_scale = 1.0f / (float)tapped; ck.phr_accumulate = !first || accumulate != 0;
+            first = false;
+        }
     }
     return s2_tower(h, tp, B2, logits_out, s);
+}
+
+extern "C" int pmhip_s2_forward_control(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
+                                        uint64_t cross_bits, uint64_t self_bits, const int32_t* row_map_host, const float* blend_host,
+                                        const float* gain_host, float* logits_out, pmhip_stream stream) {
+    return s2_forward_control_impl("s2_forward_control", h, tokens, context, L, B, ctx_lens_host, cross_bits, self_bits, row_map_host, blend_host,
+                                   gain_host, logits_out, stream);
+}
+
+// pmhip_s2_forward_control with the phrase-score tap: the layers of score_bits leave where the pair looks at the
+// phrase in `scores` [2B, tokens], the source half in front.  cross_bits | self_bits == 0 is allowed here: the logits are then those
+// of pmhip_s2_forward_lens.
+extern "C" int pmhip_s2_forward_control_scores(pmhip_s2* h, const float* tokens, const float* context, int L, int B,
+                                               const int32_t* ctx_lens_host, uint64_t cross_bits, uint64_t self_bits,
+                                               const int32_t* row_map_host, const float* blend_host, const float* gain_host,
+                                               uint64_t score_bits, const float* w_src_host, const float* w_edit_host, float* logits_out,
+                                               float* scores, int accumulate, pmhip_stream stream) {
+    return s2_forward_control_impl("s2_forward_control_scores", h, tokens, context, L, B, ctx_lens_host, cross_bits, self_bits, row_map_host,
+                                   blend_host, gain_host, logits_out, stream, true, score_bits, w_src_host, w_edit_host, scores, accumulate);
 }
 
 // The sample family's one builder: the argument list of pmhip_pipeline_sample_nucleus, the widest entry, -> the Step and the name

@@ -366,20 +366,31 @@ class S2Engine:
                   "pmhip_s2_forward_maps")
         return logits, maps
 
-    def forward_control(self, tokens, context, row_map=None, blend=None, gain=None, cross_layers=(), self_layers=(), context_lens=None):
+    def forward_control(self, tokens, context, row_map=None, blend=None, gain=None, cross_layers=(), self_layers=(), context_lens=None,
+                        score_layers=(), score_weights=None, scores=None):
         """One eager forward over B pairs (pmhip_s2_forward_control): tokens [2B, tokens, E] and context
         [2B, L, D] with the source images in front, the edited ones behind.  In the layers of cross_layers the edited half's
         cross-attention blends the source half's probabilities into its own under row_map / blend / gain ([B, L] each, one row per
         pair: ``ops.host_control``); in the layers of self_layers its first self-attention takes the source half's Q and K.
-        -> logits [2B, tokens, n_embed]; the source half's are those of ``forward`` on the source half alone, bit for bit."""
+        -> logits [2B, tokens, n_embed]; the source half's are those of ``forward`` on the source half alone, bit for bit.
+
+        score_layers (default (): the call as without the three keywords): the layers whose cross-attention is tapped for the PHRASE
+        SCORE (pmhip_s2_forward_control_scores) under score_weights = (w_src, w_edit), the phrase's row weights
+        [B, L] of the two prompts, finite and >= 0.  scores (None: a new buffer, written): f32 [2B, tokens] on the device, the source
+        half in front, which the call ACCUMULATES into -- mean over the tapped layers of ``ops.attention_phrase_score``, under the
+        control where the layer is controlled.  cross_layers and self_layers may then both be empty: the logits are ``forward``'s.
+        -> (logits, scores)"""
         if context is None:
             raise ValueError("forward_control: the control is that of the cross-attention: a context is required")
         depth = self.cfg.tower.depth
         bits = []
         for name, layers in (("cross_layers", cross_layers), ("self_layers", self_layers)):
             bits.append(sum(1 << l for l in ops.host_layers(layers, depth, f"forward_control: {name}", allow_empty=True)))
-        if not (bits[0] | bits[1]):
+        score_bits = sum(1 << l for l in ops.host_layers(score_layers, depth, "forward_control: score_layers", allow_empty=True))
+        if not (bits[0] | bits[1] | score_bits):
             raise ValueError("forward_control: cross_layers and self_layers select no layer")
+        if (score_weights is not None or scores is not None) and not score_bits:
+            raise ValueError("forward_control: score_weights and scores stand beside score_layers only")
         tokens = tokens.to(self.device, torch.float32).contiguous()
         if tokens.shape[0] % 2:
             raise ValueError(f"forward_control: {tokens.shape[0]} images are no pairs")
@@ -394,6 +405,20 @@ class S2Engine:
             rm, bl, gn = ops.host_control(row_map, blend, gain, B, L)
             ctl = tuple(np.ctypeslib.as_ctypes(x.reshape(-1)) for x in (rm, bl, gn))
         logits = torch.empty(2 * B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
+        if score_bits:
+            w_src, w_edit = ops.host_phrase_weights(score_weights, B, L)
+            accumulate = scores is not None
+            if scores is None:
+                scores = torch.empty(2 * B, self.tokens, device=self.device, dtype=torch.float32)
+            if not (isinstance(scores, torch.Tensor) and scores.device == self.device and scores.dtype == torch.float32 and
+                    tuple(scores.shape) == (2 * B, self.tokens) and scores.is_contiguous()):
+                raise ValueError(f"forward_control: scores must be a contiguous float32 [{2 * B}, {self.tokens}] tensor on {self.device}")
+            with torch.cuda.device(self.device):
+                check(self.lib.pmhip_s2_forward_control_scores(self.handle, _p(tokens), _p(context), L, B, lens, bits[0], bits[1], ctl[0], ctl[1],
+                                                               ctl[2], score_bits, np.ctypeslib.as_ctypes(w_src.reshape(-1)),
+                                                               np.ctypeslib.as_ctypes(w_edit.reshape(-1)), _p(logits), _p(scores),
+                                                               int(accumulate), stream_ptr(self.device)), "pmhip_s2_forward_control_scores")
+            return logits, scores
         with torch.cuda.device(self.device):
             check(self.lib.pmhip_s2_forward_control(self.handle, _p(tokens), _p(context), L, B, lens, bits[0], bits[1], ctl[0], ctl[1], ctl[2],
                                                     _p(logits), stream_ptr(self.device)), "pmhip_s2_forward_control")

@@ -609,6 +609,13 @@ class Pipeline(nn.Module):
 
     def _tail_cpu(self, ids, logits, nm, topk, temperature, noise, seed, choice_t=0.0, choice_noise=None, top_p=1.0, counts=None):
         """the sampling tail of ``_sample_cpu`` behind the logits: the token draw, the decode, the merge and the re-masking"""
+        pred, merged, scores, g = self._draw_cpu(ids, logits, topk, temperature, noise, seed, top_p)
+        img = None if counts is not None else self.vqgan.decode_from_indice(pred)   # decoded from the predictions at ALL positions (:165)
+        return self._remask_cpu(merged, scores, nm, g, choice_t, choice_noise, counts), img
+
+    def _draw_cpu(self, ids, logits, topk, temperature, noise, seed, top_p=1.0):
+        """the first half of ``_tail_cpu``: the token draw and the merge -> (pred, merged, score, the generator the draw used): what
+        ``ops.sample_rows`` leaves, before any re-masking (the local blend works on these)"""
         val, ind = logits.topk(topk, dim=-1)
         if top_p < 1.0:
             val = val.masked_fill(~nucleus_keep(val, top_p), float("-inf"))
@@ -618,11 +625,13 @@ class Pipeline(nn.Module):
             noise = torch.rand(logits.shape, generator=g)
         gumbel = -torch.log((-torch.log(noise.clamp(min=1e-20))).clamp(min=1e-20))
         pred = (filtered / max(temperature, 1e-10) + gumbel).argmax(dim=-1)
-        img = None if counts is not None else self.vqgan.decode_from_indice(pred)   # decoded from the predictions at ALL positions (:165)
         is_mask = ids == self.mask_token_id
-        ids = torch.where(is_mask, pred, ids)
+        merged = torch.where(is_mask, pred, ids)
         scores = 1 - logits.softmax(dim=-1).gather(2, pred[..., None])[..., 0]
-        scores = scores.masked_fill(~is_mask, -1e5)
+        return pred, merged, scores.masked_fill(~is_mask, -1e5), g
+
+    def _remask_cpu(self, ids, scores, nm, g, choice_t=0.0, choice_noise=None, counts=None):
+        """the second half of ``_tail_cpu``: the re-masking of the merged ids under their scores -> ids"""
         if choice_t:
             if choice_noise is None:
                 choice_noise = torch.rand(scores.shape, generator=g)
@@ -631,9 +640,24 @@ class Pipeline(nn.Module):
             for b, n in enumerate(counts):
                 if n > 0:
                     ids[b, scores[b].topk(n).indices] = self.mask_token_id
-            return ids, img
-        ids = ids.scatter(1, scores.topk(nm, dim=-1).indices, self.mask_token_id)
-        return ids, img
+            return ids
+        return ids.scatter(1, scores.topk(nm, dim=-1).indices, self.mask_token_id)
+
+    @staticmethod
+    def _region_cpu(score_src, score_edit, g, threshold, grow):
+        """``ops.phrase_region`` in plain torch: f32 [B, g*g] twice -> bool [B, g*g], the rule of ``phrase_mask`` on both halves, joined,
+        dilated `grow` times by a 3 x 3 maximum"""
+        B = score_src.shape[0]
+        mask = (score_src >= threshold * score_src.amax(dim=1, keepdim=True)) | (score_edit >= threshold * score_edit.amax(dim=1, keepdim=True))
+        mask = mask.reshape(B, g, g)
+        for _ in range(grow):
+            mask = torch.nn.functional.max_pool2d(mask[:, None].float(), 3, stride=1, padding=1)[:, 0] > 0
+        return mask.reshape(B, g * g)
+
+    @staticmethod
+    def _blend_cpu(mask, src, edit):
+        """``ops.blend_tokens`` in plain torch: (pred, merged, score) of the two halves -> the edited half's, the source's where not mask"""
+        return tuple(torch.where(mask, e, s_) for s_, e in zip(src, edit))
 
     @torch.no_grad()
     def _generate_cpu(self, context, B, timesteps, temperature, opts, save_interval, seed, return_ids, keys=None):
@@ -823,7 +847,8 @@ class Pipeline(nn.Module):
     @torch.no_grad()
     def control_ids(self, context_src, context_edit, lens_src, lens_edit, row_map, blend, gain, B, timesteps, temperature, topk, seed,
                     image_base=0, top_p=None, choice_temperature=None, guidance_scale=None, cross_steps=0.8, self_steps=0.0, layers=None,
-                    want_imgs=False, noise=None):
+                    want_imgs=False, noise=None, blend_rows=None, blend_mask=None, blend_threshold=0.3, blend_grow=1, blend_start=0.2,
+                    return_mask=False):
         """Prompt-to-prompt (Hertz et al.): the eager decode loop over B PAIRS of images -- one from
         context_src [B, L, D], one from context_edit [B, L, D], both from the all-mask state under the same seed -- in which the
         edited image's cross-attention takes the source image's probabilities for the context rows row_map pairs.
@@ -841,7 +866,25 @@ class Pipeline(nn.Module):
         The sampling tail runs once per half with the SAME seed, step and image_base: a pair shares its noise.  A scalar
         guidance_scale adds the pass without a context over the 2B images; that pass is never controlled.
         ids_src is ``generate_ids(context_src, ..., use_graph=False, streams=1)`` bit for bit; with cross_steps = self_steps = 0
-        ids_edit is that of context_edit.  Whether the edited image keeps the source's layout on a MaskGIT tower is unmeasured."""
+        ids_edit is that of context_edit.  Whether the edited image keeps the source's layout on a MaskGIT tower is unmeasured.
+
+        LOCAL BLEND (the paper's third control; without the keywords the call is the one above, bit for bit):
+        outside a region the edited image takes the source's TOKENS.  The region is either drawn -- blend_mask, bool [B, g, g], and
+        no scores are collected -- or follows from where the pair looks at a phrase: blend_rows = (w_src, w_edit), the phrase's row
+        weights [B, L] in the two prompts (finite, >= 0, typically 0 / 1; every pair with a positive weight below its length in one
+        half).  With blend_rows every step runs ``S2Engine.forward_control(score_layers=layers, ...)`` -- past cross_steps with no
+        layer controlled --, from the conditional pass only (guidance's second pass is never tapped), and the scores accumulate into
+        one [2B, N] buffer over layers and steps, in the stream's order.  A step s >= ceil(blend_start * T) then, between the token draw
+        of both halves and their re-masking: the region ``ops.phrase_region(scores so far, blend_threshold, blend_grow)``, and
+        ``ops.blend_tokens``.  Re-masking proceeds per half as ever; both halves share their noise, so outside the region they re-mask
+        the same way unless the region's own scores interfere.  The last step's image is decoded from the blended predictions.
+        return_mask appends the last region, bool [B, g, g].  blend_threshold 0.3, blend_grow 1 and blend_start 0.2 are the paper's
+        values, not optima measured on this tower.  Invariants:
+          - the source half never reads the edited half: ids_src stays ``generate_ids`` on the source alone, bit for bit
+          - at every blended step, before re-masking, the edited half's (pred, merged, score) equal the source half's at every token
+            outside the region, bit for bit
+          - blend_mask all true gives the ids of the call without a blend, bit for bit; all false makes ids_edit == ids_src
+          - the final IMAGE is not promised to be pixel-equal outside the region: the decoder mixes tokens."""
         if context_src is None or context_edit is None or tuple(context_src.shape) != tuple(context_edit.shape) or context_src.dim() != 3 \
                 or context_src.shape[0] != B:
             raise ValueError(f"control_ids: context_src and context_edit must be two context tensors [{B}, L, D] of one shape")
@@ -865,6 +908,31 @@ class Pipeline(nn.Module):
         cpu = self._on_cpu()
         dev = self.mask_token.device if cpu else self.engine().device
         N = self.num_tokens
+        g = self.image_size // self.patch_size
+        if blend_rows is not None and blend_mask is not None:
+            raise ValueError("control_ids: blend_rows and blend_mask exclude each other (the region follows from a phrase or is drawn)")
+        blending = blend_rows is not None or blend_mask is not None
+        if return_mask and not blending:
+            raise ValueError("control_ids: return_mask needs blend_rows or blend_mask")
+        region, scores, blend_from = None, None, T
+        if blending:
+            if not (isinstance(blend_threshold, (int, float)) and 0 < blend_threshold <= 1):
+                raise ValueError(f"control_ids: blend_threshold {blend_threshold!r} must be in (0, 1]")
+            if not (isinstance(blend_grow, int) and blend_grow >= 0):
+                raise ValueError(f"control_ids: blend_grow {blend_grow!r} must be a non-negative integer")
+            if not 0.0 <= float(blend_start) < 1.0:
+                raise ValueError(f"control_ids: blend_start={blend_start} must be a fraction in [0, 1) (the last step always blends)")
+            if g * g != N or g > 64:
+                raise ValueError(f"control_ids: the local blend needs a square token grid of at most 64 x 64, got {N} tokens")
+            blend_from = math.ceil(float(blend_start) * T)
+        if blend_rows is not None:
+            blend_rows = ops.host_phrase_weights(blend_rows, B, L)
+            ops.check_phrase_rows(*blend_rows, lengths, B, L)
+        if blend_mask is not None:
+            region = torch.as_tensor(blend_mask)
+            if region.dtype != torch.bool or tuple(region.shape) != (B, g, g):
+                raise ValueError(f"control_ids: blend_mask must be a bool tensor [{B}, {g}, {g}], got {region.dtype} {tuple(region.shape)}")
+            region = region.reshape(B, N).to(dev) if cpu else region.reshape(B, N).to(dev, torch.uint8).contiguous()
         context = context.to(dev)
         ids = torch.full((2 * B, N), self.mask_token_id, dtype=torch.long, device=dev)
         imgs = [None, None]
@@ -877,44 +945,60 @@ class Pipeline(nn.Module):
             ctl = dict(row_map=rm, blend=bl, gain=gn) if cross else {}
             tok = self.ids2tokens(ids)
             ct = ctemps[step] if ctemps else 0.0
+            tap = {} if blend_rows is None else dict(score_layers=layers, score_weights=blend_rows, scores=scores)
+            blend_now = blending and step >= blend_from
             if cpu:
-                if cross or inject:
-                    logits = self.transformer(tok, context, keys=keys, control=dict(cross_layers=cross, self_layers=inject, **ctl))
+                if cross or inject or tap:
+                    logits = self.transformer(tok, context, keys=keys, control=dict(cross_layers=cross, self_layers=inject, **ctl, **tap))
+                    if tap:
+                        logits, scores = logits
                 else:
                     logits = self._logits(tok, context, keys)
                 if opts.guidance_scale is not None:
                     uncond = self._logits(tok, None)
                     logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(opts.guidance_scale)))
-                halves = [self._tail_cpu(ids[h * B:(h + 1) * B], logits[h * B:(h + 1) * B], nmask[step], opts.topk, temps[step],
-                                         None if noise is None else noise[step], None if seed is None else seed + step, ct, None, opts.top_p,
-                                         counts=None if last else [nmask[step]] * B)              # (counts: the same re-masking, no decode)
-                          for h in range(2)]
-                ids, imgs = torch.cat([h[0] for h in halves]), [h[1] for h in halves]
+                draws = [self._draw_cpu(ids[h * B:(h + 1) * B], logits[h * B:(h + 1) * B], opts.topk, temps[step],
+                                        None if noise is None else noise[step], None if seed is None else seed + step, opts.top_p) for h in range(2)]
+                if blend_now:
+                    if blend_rows is not None:
+                        region = self._region_cpu(scores[:B], scores[B:], g, blend_threshold, blend_grow)
+                    draws[1] = self._blend_cpu(region, draws[0][:3], draws[1][:3]) + (draws[1][3],)
+                if last:
+                    imgs = [self.vqgan.decode_from_indice(d[0]) for d in draws]
+                ids = torch.cat([self._remask_cpu(d[1], d[2], nmask[step], d[3], ct, None, [nmask[step]] * B) for d in draws])
                 continue
             eng = self.engine()
-            if cross or inject:
+            if tap:
+                logits, scores = eng.forward_control(tok, context, cross_layers=cross, self_layers=inject, context_lens=keys.lens, **ctl, **tap)
+            elif cross or inject:
                 logits = eng.forward_control(tok, context, cross_layers=cross, self_layers=inject, context_lens=keys.lens, **ctl)
             else:
                 logits = eng.forward(tok, context, keys=keys)
             if opts.guidance_scale is not None:
                 logits = ops.guidance_combine(logits, eng.forward(tok, None), opts.guidance_scale, out=logits)
+            draws = []
             for h in range(2):
                 rows = slice(h * B * N, (h + 1) * B * N)
-                pred, merged, score = ops.sample_rows(logits.reshape(2 * B * N, -1)[rows], ids.reshape(-1)[rows], self.mask_token_id, opts.topk,
-                                                   temps[step], seed=seed, step=step, row_base=image_base * N, top_p=opts.top_p,
-                                                   noise=None if noise is None else noise[step].to(dev, torch.float32).reshape(B * N, -1).contiguous())
+                draws.append(ops.sample_rows(logits.reshape(2 * B * N, -1)[rows], ids.reshape(-1)[rows], self.mask_token_id, opts.topk,
+                                             temps[step], seed=seed, step=step, row_base=image_base * N, top_p=opts.top_p,
+                                             noise=None if noise is None else noise[step].to(dev, torch.float32).reshape(B * N, -1).contiguous()))
+            if blend_now:
+                if blend_rows is not None:
+                    region = ops.phrase_region(scores[:B], scores[B:], g, blend_threshold, blend_grow)
+                ops.blend_tokens(region, *draws[0], *draws[1])
+            for h, (pred, merged, score) in enumerate(draws):
                 ids[h * B:(h + 1) * B] = ops.remask(merged.reshape(B, N), score.reshape(B, N), nmask[step], self.mask_token_id,
                                                     choice_temperature=ct, seed=seed, step=step, row_base=image_base * N)
                 if last:
                     imgs[h] = self.vqgan.decode_from_indice(pred.reshape(B, N))
-        if want_imgs:
-            return ids[:B].clone(), ids[B:].clone(), imgs[0], imgs[1]
-        return ids[:B].clone(), ids[B:].clone()
+        out = (ids[:B].clone(), ids[B:].clone()) + ((imgs[0], imgs[1]) if want_imgs else ())
+        return out + ((region != 0).reshape(B, g, g),) if return_mask else out
 
     @torch.no_grad()
     def prompt_to_prompt(self, text, edit_text, mode="refine", reweight=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_base=0,
                          top_p=None, choice_temperature=None, guidance_scale=None, cross_steps=0.8, self_steps=0.0, layers=None,
-                         return_ids=False, **refused):
+                         return_ids=False, local_blend=None, blend_threshold=0.3, blend_grow=1, blend_start=0.2, blend_mask=None,
+                         return_mask=False, **refused):
         """Change the prompt, keep the picture (Hertz et al., Prompt-to-Prompt): -> (img_src, img_edit), the
         image of `text` and the image of `edit_text` from one seed, the second attending with the first's cross-attention for the
         words the prompts share; ids with return_ids.  text / edit_text: a prompt each, or two lists of as many.
@@ -924,7 +1008,14 @@ class Pipeline(nn.Module):
         scaled by gain (>= 0); edit_text == text
         with a reweight is the paper's pure re-weighting.  Always under the non-pad lengths, as ``phrase_mask``.  The other
         keywords are those of ``control_ids``.  Not served (ValueError): negative_text, regions, prompt_weights / context_weights,
-        the segment arrays, a guidance schedule, an unconditional pipeline.  Image quality on this tower is unmeasured."""
+        the segment arrays, a guidance schedule, an unconditional pipeline.  Image quality on this tower is unmeasured.
+
+        local_blend (the paper's third control; None = the call as without it): outside the region that looks
+        at a phrase the edited image keeps the source's tokens (``control_ids`` has the rule and its invariants).  "dog": the phrase,
+        in whichever prompt of a pair has it; ("cat", "dog"): the source prompt's phrase and the edited prompt's; or a list of B such
+        items.  Each phrase occurs once in its prompt; a phrase in neither prompt, or with no token below max_length, is a
+        ValueError.  blend_threshold / blend_grow / blend_start: the paper's 0.3 / 1 / 0.2, not optima measured on this tower.
+        blend_mask (bool [B, g, g], instead of local_blend): the region, drawn.  return_mask appends the last region, bool [B, g, g]."""
         if refused:
             raise ValueError(f"prompt_to_prompt does not serve {sorted(refused)} (negative prompts, regions, prompt weights and the segment "
                              f"arrays stand beside no attention control)")
@@ -944,32 +1035,58 @@ class Pipeline(nn.Module):
             if not isinstance(phrase, str) or not phrase.strip() or not (math.isfinite(float(g)) and float(g) >= 0):
                 raise ValueError(f"prompt_to_prompt: reweight {phrase!r}: {g!r} must be a phrase and a finite gain >= 0")
 
-        def cut(prompt, strict):
-            """the prompt cut at the single occurrence of every phrase -> (fragments, the gain of each or None)"""
-            found = []
+        def cut(prompt, strict, look=None):
+            """the prompt cut at the single occurrence of every phrase -> (fragments, the gain of each or None, whether each is the
+            local blend's phrase `look`)"""
+            found = {}
             for phrase, g in reweight.items():
                 if prompt.count(phrase) == 0:
                     continue                                     # (a phrase of another prompt of the batch)
                 if prompt.count(phrase) != 1:
                     if strict:
                         raise ValueError(f"prompt_to_prompt: the phrase {phrase!r} occurs {prompt.count(phrase)} times in {prompt!r}, not once")
-                    return [prompt], [None]
-                found.append((prompt.index(phrase), phrase, float(g)))
-            found.sort()
-            frags, gains, at = [], [], 0
-            for pos, phrase, g in found:
+                    found = {}
+                    break
+                found[phrase] = (prompt.index(phrase), phrase, float(g))
+            if look is not None:
+                if prompt.count(look) != 1:
+                    raise ValueError(f"prompt_to_prompt: the phrase {look!r} of local_blend occurs {prompt.count(look)} times in {prompt!r}, not once")
+                found.setdefault(look, (prompt.index(look), look, None))
+            frags, gains, looks, at = [], [], [], 0
+            for pos, phrase, g in sorted(found.values()):
                 if pos < at:
-                    raise ValueError(f"prompt_to_prompt: the phrases of reweight overlap in {prompt!r}")
+                    raise ValueError(f"prompt_to_prompt: the phrases of reweight and local_blend overlap in {prompt!r}")
                 frags += [prompt[at:pos], phrase]
                 gains += [None, g]
+                looks += [False, phrase == look]
                 at = pos + len(phrase)
-            return frags + [prompt[at:]], gains + [None]
+            return frags + [prompt[at:]], gains + [None], looks + [False]
 
         B = len(src)
+        looks = [(None, None)] * B
+        if local_blend is not None:
+            if blend_mask is not None:
+                raise ValueError("prompt_to_prompt: local_blend and blend_mask exclude each other (the region follows from a phrase or is drawn)")
+            if not isinstance(local_blend, (str, tuple, list)):
+                raise ValueError(f"prompt_to_prompt: local_blend {local_blend!r} must be a phrase, a pair of phrases or a list of {B} such items")
+            items = [local_blend] * B if isinstance(local_blend, (str, tuple)) else list(local_blend)
+            if len(items) != B:
+                raise ValueError(f"prompt_to_prompt: local_blend has {len(items)} items for {B} pairs")
+            looks = []
+            for b, item in enumerate(items):
+                if isinstance(item, str) and item.strip():
+                    pair = (item if item in src[b] else None, item if item in tgt[b] else None)
+                elif isinstance(item, tuple) and len(item) == 2 and all(isinstance(x, str) and x.strip() for x in item):
+                    pair = item
+                else:
+                    raise ValueError(f"prompt_to_prompt: local_blend {item!r} must be a phrase or a pair (source phrase, edited phrase)")
+                if pair == (None, None) or (pair[0] is not None and pair[0] not in src[b]) or (pair[1] is not None and pair[1] not in tgt[b]):
+                    raise ValueError(f"prompt_to_prompt: the phrase {item!r} of local_blend does not occur in {src[b]!r} / {tgt[b]!r}")
+                looks.append(pair)
         for phrase in reweight:
             if not any(phrase in p for p in tgt):
                 raise ValueError(f"prompt_to_prompt: the phrase {phrase!r} of reweight occurs in no edited prompt")
-        cuts = [cut(p, False) for p in src] + [cut(p, True) for p in tgt]
+        cuts = [cut(p, False, looks[b][0]) for b, p in enumerate(src)] + [cut(p, True, looks[b][1]) for b, p in enumerate(tgt)]
         context, lens, ids, spans = self.text_model.fragment_ids([c[0] for c in cuts])
         L = context.shape[1]
         lens = [int(n) for n in lens]
@@ -982,10 +1099,27 @@ class Pipeline(nn.Module):
                     if hi <= lo:
                         raise ValueError(f"prompt_to_prompt: a phrase of reweight has no tokens below max_length in {tgt[b]!r}")
                     gn[b, lo:hi] = g
+        blend = {}
+        if local_blend is not None:
+            rows = np.zeros((2, B, L), np.float32)
+            for half, prompts in enumerate((src, tgt)):
+                for b in range(B):
+                    for (lo, hi), look in zip(spans[half * B + b], cuts[half * B + b][2]):
+                        if look:
+                            if hi <= lo:
+                                raise ValueError(f"prompt_to_prompt: the phrase of local_blend has no tokens below max_length in {prompts[b]!r}")
+                            rows[half, b, lo:hi] = 1.0
+            blend = dict(blend_rows=(rows[0], rows[1]))
+        if blend_mask is not None:
+            blend = dict(blend_mask=blend_mask)
+        if blend:
+            blend.update(blend_threshold=blend_threshold, blend_grow=blend_grow, blend_start=blend_start, return_mask=return_mask)
+        elif return_mask:
+            raise ValueError("prompt_to_prompt: return_mask needs local_blend or blend_mask")
         context = context.to(self.mask_token.device, torch.float32)
         out = self.control_ids(context[:B], context[B:], lens[:B], lens[B:], rm, bl, gn, B, timesteps, temperature, topk,
                                _draw_seed() if seed is None else seed, image_base, top_p, choice_temperature, guidance_scale, cross_steps,
-                               self_steps, layers, want_imgs=not return_ids)
+                               self_steps, layers, want_imgs=not return_ids, **blend)
         return out if return_ids else out[2:]
 
     def join_lanes(self, parts):

@@ -61,7 +61,7 @@ class CrossAttention(nn.Module):
                         token_segments=token_segments, context_weights=context_weights)
 
     def run(self, x, context=None, residual=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None,
-            want_maps=False, control=None, inject_self=False, keys=None):
+            want_maps=False, control=None, inject_self=False, keys=None, score=None):
         """x [B,N,query_dim]; returns to_out(attn) (+ residual) as fp32/bf16 like x.
         want_maps (extension, attention maps): -> (that, maps) with maps f32 [B, N, L], the mean over the heads
         of this call's softmax probabilities -- exactly 0 where a row takes no part; it needs a context.
@@ -76,6 +76,11 @@ class CrossAttention(nn.Module):
         the source images in front; the edited half attends with P = gain (has ? (1 - blend) pt + blend ps[row_map] : pt), ps the source
         half's probabilities (``ops.attention_control``).  It needs a context and stands beside context_lens only.
         inject_self (the same extension, a self-attention): the edited half attends with the source half's Q and K and its own V.
+        score (extension, the local blend): (w_src, w_edit, scale, into) -- the phrase's row weights [B / 2, L]
+        of the two halves of a batch of pairs, checked (``ops.host_phrase_weights``), a scale, and None or the pair of f32 [B / 2, N]
+        tensors to add to -> (that, (score_src, score_edit)): scale times the head-mean of the phrase rows' probabilities, the source
+        half's own and the edited half's as it attends -- under `control` where given (``ops.attention_phrase_score``).  It needs a
+        context and stands beside context_lens only.
         keys: the call's checked ``ops.Keys``, which is not checked again; the four arrays beside it are then its own (what
         ``Layer.forward`` hands over) and are not looked at.  Without it the four arrays are checked here, whatever their types."""
         shape = (x.shape[0], 0 if context is None else context.shape[1], x.shape[1])
@@ -94,13 +99,15 @@ class CrossAttention(nn.Module):
             control = ops.host_control(*control, x.shape[0] // 2, context.shape[1])
         if inject_self and (context is not None or x.shape[0] % 2):
             raise ValueError("inject_self is for the self-attention of a batch of pairs")
+        if score is not None and (context is None or segments is not None or want_maps or x.shape[0] % 2):
+            raise ValueError("score needs a context and a batch of pairs, and stands beside context_lens only")
         if self.training and self.to_out[1].p > 0:
             raise RuntimeError("paintmind_amd attention is inference-only (dropout>0 in training mode)")
         if want_maps and context is None:
             raise ValueError("want_maps: the maps are those of a cross-attention: a context is required")
         if not x.is_cuda:
-            if control is not None or inject_self:
-                return self._run_cpu(x, context, residual, context_lens, control=control, inject_self=inject_self)
+            if control is not None or inject_self or score is not None:
+                return self._run_cpu(x, context, residual, context_lens, control=control, inject_self=inject_self, score=score)
             if want_maps:
                 return self._run_cpu(x, context, residual, context_lens, segments, weights, want_maps=True)
             return self._run_cpu(x, context, residual, context_lens, segments, weights)
@@ -147,11 +154,21 @@ class CrossAttention(nn.Module):
         out = ops.gemm(o, pk["wo"], bias=pk["bo"], residual=res, out_dtype=out_dtype)
         if want_maps:
             return out.reshape(B, N, D), ops.attention_maps(q, k, n_kv, use_exp2=fast, **form)
+        if score is not None:
+            h2 = B // 2
+            w_src, w_edit, scale, into = score
+            ctl = (None, None, None) if control is None else tuple(torch.from_numpy(c).to(x.device) for c in control)
+            got = ops.attention_phrase_score(q[:h2], k[:h2], q[h2:], k[h2:], n_kv, n_kv, torch.from_numpy(w_src).to(x.device),
+                                             torch.from_numpy(w_edit).to(x.device), *ctl, use_exp2=fast,
+                                             lens_src=None if kv_lens is None else kv_lens[:h2].contiguous(),
+                                             lens_tgt=None if kv_lens is None else kv_lens[h2:].contiguous(), out=into, scale=scale,
+                                             accumulate=into is not None)
+            return out.reshape(B, N, D), got
         return out.reshape(B, N, D)
 
 
     def _run_cpu(self, x, context, residual, context_lens=None, segments=None, weights=None, want_maps=False, control=None,
-                 inject_self=False):
+                 inject_self=False, score=None):
         """Parameters on the CPU: the same operator in plain torch (reference modules/attention.py:43-59; BASELINE config 1
         runs the model there).  q is scaled BEFORE the product (:52), no mask, softmax over the keys, head split 'b n (h d)'.
         context_lens (a checked list, or None): scores of the keys at or beyond an image's length become -inf (whatever they
@@ -163,11 +180,14 @@ class CrossAttention(nn.Module):
         want_maps: -> (the result, p.mean(heads) f32 [B, N, L]): the probabilities of this very softmax, 0 where a row takes no part.
         control (checked numpy (int32, float32, float32) [B / 2, L], or None): the edited half's probabilities become
         gain (has ? (1 - blend) pt + blend ps[row_map] : pt), ps the source half's, has = 0 <= row_map < the source length and
-        blend != 0; no renormalisation.  inject_self: the edited half's q and k are the source half's."""
+        blend != 0; no renormalisation.  inject_self: the edited half's q and k are the source half's.
+        score ((w_src, w_edit, scale, into), checked, or None): -> (the result, (score_src, score_edit)), f32 [B / 2, N] each: scale
+        times the mean over the heads of sum_k w[k] p[q, k], p the source half's probabilities and the edited half's as it attends
+        (behind `control`), added to `into` when given."""
         B, N, _ = x.shape
         c = x if context is None else context
         L = c.shape[1]
-        if context_lens is not None and len(set(context_lens)) == 1 and control is None:
+        if context_lens is not None and len(set(context_lens)) == 1 and control is None and score is None:
             c, context_lens = c[:, :context_lens[0]], None       # one length for the batch (B = 1 always): cut the padding off
         h, d = self.heads, self.dim_head
         q = (F.linear(x, self.to_q.weight) * self.scale).reshape(B, N, h, d).permute(0, 2, 1, 3)
@@ -202,6 +222,12 @@ class CrossAttention(nn.Module):
         o = (p @ v).permute(0, 2, 1, 3).reshape(B, N, h * d)
         out = F.linear(o, self.to_out[0].weight, self.to_out[0].bias)
         out = out if residual is None else out + residual
+        if score is not None:
+            h2 = B // 2
+            w_src, w_edit, scale, into = score
+            part = lambda ph, w: ((ph * torch.from_numpy(w).to(ph.dtype)[:, None, None, :]).sum(-1).mean(1) * scale).float()
+            got = part(p[:h2], w_src), part(p[h2:], w_edit)
+            return out, (got if into is None else (into[0] + got[0], into[1] + got[1]))
         if want_maps:
             return out, F.pad(p.mean(1).float(), (0, L - p.shape[-1]))       # (a context cut to one common length: zeros behind it)
         return out

@@ -88,6 +88,34 @@ def host_control(row_map, blend, gain, B, L):
     return np.ascontiguousarray(np.maximum(rm, -1).astype(np.int32)), np.ascontiguousarray(bl), np.ascontiguousarray(gn)
 
 
+def host_phrase_weights(score_weights, B, L):
+    """the local blend's phrase rows: (w_src, w_edit), each [B, L] numbers, finite and >= 0, as lists, numpy
+    arrays, CPU or device tensors -> two contiguous numpy float32 arrays on the host, brought there ONCE per call and checked before
+    anything is launched.  (That every pair has a positive weight below its length is the native entry's and the model's check: it
+    needs the lengths.)"""
+    if not (isinstance(score_weights, (tuple, list)) and len(score_weights) == 2):
+        raise ValueError("score_weights must be the pair (w_src, w_edit)")
+    out = []
+    for name, x in zip(("w_src", "w_edit"), score_weights):
+        w = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        if w.shape != (B, L) or w.dtype.kind not in "fiub":
+            raise ValueError(f"{name} must be numbers of shape ({B}, {L}), got {w.dtype} {w.shape}")
+        w = np.ascontiguousarray(w.astype(np.float32))
+        if not (np.isfinite(w) & (w >= 0)).all():
+            raise ValueError(f"{name} must be finite and >= 0")
+        out.append(w)
+    return out[0], out[1]
+
+
+def check_phrase_rows(w_src, w_edit, lens, B, L):
+    """every pair looks at something: a positive weight below its length in at least one half (lens: the 2B checked lengths, the
+    source half in front, or None: every row) -- the rule of pmhip_s2_forward_control_scores"""
+    for b in range(B):
+        ns, nt = (L, L) if lens is None else (lens[b], lens[B + b])
+        if not ((w_src[b, :ns] > 0).any() or (w_edit[b, :nt] > 0).any()):
+            raise ValueError(f"score_weights: pair {b}: no row of the phrase has a positive weight below its length in either half")
+
+
 def host_segments(context_segments, token_segments, B, L, N):
     """regional prompts: context_segments [B, L] ints (the segment 0..31 of every context row; -1 or 255 =
     padding) and token_segments [B, N] int bitmasks (bit s = the token attends to segment s), as lists, numpy arrays, CPU or device
@@ -696,6 +724,95 @@ def attention_control(qs, ks, qt, kt, vt, n_src, n_tgt, row_map, blend, gain, us
                                           int(n_src), lsp, int(n_tgt), ltp, int(bool(use_exp2)), _p(row_map), _p(blend), _p(gain),
                                           _p(lens_src), _p(lens_tgt), stream_ptr(dev)), "pmhip_attention_control")
     return out
+
+
+def attention_phrase_score(qs, ks, qt, kt, n_src, n_tgt, w_src, w_tgt, row_map=None, blend=None, gain=None, use_exp2=False, lens_src=None,
+                           lens_tgt=None, out=None, scale=1.0, accumulate=False):
+    """Where a prompt-to-prompt pair looks at a phrase (pmhip_attention_phrase_score): the operands, lengths
+    and control arrays of ``attention_control`` without vt -> (score_src, score_tgt), f32 [B, Nq] each, with
+        score_src[b, q] = scale / H * sum_h sum_k w_src[b, k] ps_h[q, k]        score_tgt[b, q] = scale / H * sum_h sum_j w_tgt[b, j] P_h[q, j]
+    ps and P those of ``attention_control``; row_map, blend and gain come together or not at all (None: P is the edited pass's own
+    softmax).  w_src f32 [B, n_src], w_tgt f32 [B, n_tgt]: the phrase's row weights, finite and >= 0 (the caller's to keep).  P stays
+    f32 in bf16 mode.  out (None: two new tensors; required under `accumulate`, which adds to what they hold): the pair
+    (score_src, score_tgt), contiguous f32 [B, Nq] on the operands' device.  -> out"""
+    dev = _dev(qs, ks, qt, kt, w_src, w_tgt, row_map, blend, gain, lens_src, lens_tgt)
+    lib = _lib.load()
+    B, H, Nq, dh = qt.shape
+    if tuple(qs.shape) != (B, H, Nq, dh) or qs.dtype != qt.dtype:
+        raise ValueError(f"qs must be a {qt.dtype} {(B, H, Nq, dh)} tensor like qt, got {qs.dtype} {tuple(qs.shape)}")
+    lsp, ltp = ks.shape[2], kt.shape[2]
+    for name, x, want in (("ks", ks, (B, H, lsp, dh)), ("kt", kt, (B, H, ltp, dh))):
+        if x.dtype != qt.dtype or tuple(x.shape) != want:
+            raise ValueError(f"{name} must be a {qt.dtype} {want} tensor, got {x.dtype} {tuple(x.shape)}")
+    if lsp < n_src or ltp < n_tgt:
+        raise ValueError(f"n_src={n_src} / n_tgt={n_tgt} exceed the padded contexts {lsp} / {ltp}")
+    if len({row_map is None, blend is None, gain is None}) != 1:
+        raise ValueError("row_map, blend and gain come together (all None: no control)")
+    for name, x, dt, n in (("row_map", row_map, torch.int32, n_tgt), ("blend", blend, torch.float32, n_tgt), ("gain", gain, torch.float32, n_tgt),
+                           ("w_src", w_src, torch.float32, n_src), ("w_tgt", w_tgt, torch.float32, n_tgt)):
+        if name.startswith("w_") and x is None:
+            raise ValueError(f"{name} must be a {dt} tensor of shape ({B}, {n})")
+        if x is not None and (x.dtype != dt or tuple(x.shape) != (B, n)):
+            raise ValueError(f"{name} must be a {dt} tensor of shape ({B}, {n}), got {x.dtype} {tuple(x.shape)}")
+    for name, x in (("lens_src", lens_src), ("lens_tgt", lens_tgt)):
+        if x is not None and (x.dtype != torch.int32 or tuple(x.shape) != (B,)):
+            raise ValueError(f"{name} must be an int32 tensor of shape ({B},), got {x.dtype} {tuple(x.shape)}")
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate adds to `out`: pass the pair of tensors to add to")
+        out = (torch.empty(B, Nq, device=dev, dtype=torch.float32), torch.empty(B, Nq, device=dev, dtype=torch.float32))
+    if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
+            isinstance(o, torch.Tensor) and o.is_cuda and o.device == dev and o.dtype == torch.float32 and tuple(o.shape) == (B, Nq) and
+            o.is_contiguous() for o in out)):
+        raise ValueError(f"out must be a pair of contiguous float32 [{B}, {Nq}] tensors on the operands' device")
+    with torch.cuda.device(dev):
+        check(lib.pmhip_attention_phrase_score(pm_dtype(qt.dtype), _p(qs), _p(ks), _p(qt), _p(kt), B, H, dh, Nq, int(n_src), lsp, int(n_tgt), ltp,
+                                               int(bool(use_exp2)), _p(row_map), _p(blend), _p(gain), _p(lens_src), _p(lens_tgt), _p(w_src),
+                                               _p(w_tgt), _p(out[0]), _p(out[1]), float(scale), int(bool(accumulate)), stream_ptr(dev)),
+              "pmhip_attention_phrase_score")
+    return out[0], out[1]
+
+
+def phrase_region(score_src, score_tgt, g, threshold, grow=0, out=None):
+    """The blend region of a pair from its two phrase scores (pmhip_phrase_region): score_src, score_tgt
+    contiguous f32 [B, g*g] on the device -> uint8 [B, g*g], 1 where score_x >= threshold * max score_x in either half, dilated
+    `grow` times by a 3 x 3 maximum on the g x g grid.  0 < threshold <= 1, grow >= 0, 1 <= g <= 64."""
+    dev = _dev(score_src, score_tgt)
+    B = score_src.shape[0]
+    for name, x in (("score_src", score_src), ("score_tgt", score_tgt)):
+        if x.dtype != torch.float32 or tuple(x.shape) != (B, g * g):
+            raise ValueError(f"{name} must be a float32 tensor of shape ({B}, {g * g}), got {x.dtype} {tuple(x.shape)}")
+    if not (isinstance(threshold, (int, float)) and 0 < threshold <= 1):
+        raise ValueError(f"phrase_region: threshold {threshold!r} must be in (0, 1]")
+    if not (isinstance(grow, int) and grow >= 0):
+        raise ValueError(f"phrase_region: grow {grow!r} must be a non-negative integer")
+    if out is None:
+        out = torch.empty(B, g * g, device=dev, dtype=torch.uint8)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (B, g * g) and
+            out.is_contiguous()):
+        raise ValueError(f"out must be a contiguous uint8 [{B}, {g * g}] tensor on the operands' device")
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_phrase_region(_p(score_src), _p(score_tgt), _p(out), B, int(g), float(threshold), int(grow), stream_ptr(dev)),
+              "pmhip_phrase_region")
+    return out
+
+
+def blend_tokens(mask, pred_src, merged_src, score_src, pred_tgt, merged_tgt, score_tgt):
+    """The token blend under a region (pmhip_blend_tokens), IN PLACE on the edited half: where mask == 0
+    (pred_tgt, merged_tgt, score_tgt) take the source half's values, elsewhere they stay.  mask uint8, pred / merged int64, score f32,
+    all contiguous with B * N elements on the device.  The source half is read only.  -> (pred_tgt, merged_tgt, score_tgt)"""
+    dev = _dev(mask, pred_src, merged_src, score_src, pred_tgt, merged_tgt, score_tgt)
+    n = mask.numel()
+    if mask.dtype != torch.uint8 or mask.dim() != 2 or n == 0:
+        raise ValueError(f"mask must be a non-empty uint8 tensor [B, N], got {mask.dtype} {tuple(mask.shape)}")
+    for name, x, dt in (("pred_src", pred_src, torch.int64), ("merged_src", merged_src, torch.int64), ("score_src", score_src, torch.float32),
+                        ("pred_tgt", pred_tgt, torch.int64), ("merged_tgt", merged_tgt, torch.int64), ("score_tgt", score_tgt, torch.float32)):
+        if x.dtype != dt or x.numel() != n:
+            raise ValueError(f"{name} must be a {dt} tensor of {n} elements, got {x.dtype} {tuple(x.shape)}")
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_blend_tokens(_p(mask), _p(pred_src), _p(merged_src), _p(score_src), _p(pred_tgt), _p(merged_tgt), _p(score_tgt),
+                                             mask.shape[0], mask.shape[1], stream_ptr(dev)), "pmhip_blend_tokens")
+    return pred_tgt, merged_tgt, score_tgt
 
 
 def layernorm(x, gamma, beta, eps=1e-5, out_dtype=torch.float32):

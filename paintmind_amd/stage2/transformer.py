@@ -22,7 +22,7 @@ class Layer(nn.Module):
         self.ffnet = SwiGLUFFNFused(in_features=dim, hidden_features=mlp_dim)
 
     def forward(self, x, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, want_maps=False,
-                control=None, inject_self=False, keys=None):
+                control=None, inject_self=False, keys=None, score=None):
         """self-attn, cross-attn (a 2nd self-attn when context is None), SwiGLU (transformer.py:44-49).
         want_maps: -> (x, maps), maps f32 [B, N, L] the head-mean probabilities of the cross-attention (modules/attention.py).
         context_lens: per-image context lengths for the cross-attention only (modules/attention.py).
@@ -30,6 +30,7 @@ class Layer(nn.Module):
         context_weights: prompt weights, for the cross-attention only (modules/attention.py).
         control / inject_self: prompt-to-prompt on a batch of pairs, the cross-attention's control and the injection into the first
         self-attention (modules/attention.py).
+        score: the local blend's phrase score of the cross-attention (modules/attention.py): -> (x, (score_src, score_edit)).
         keys (instead of the four arrays): the call's checked ``ops.Keys``; the cross-attention gets the record and, as keywords, the
         record's own arrays."""
         if keys is not None:
@@ -42,6 +43,8 @@ class Layer(nn.Module):
         kw = dict(want_maps=True) if want_maps else {}
         if control is not None:
             kw["control"] = control
+        if score is not None:
+            kw["score"] = score
         x = self.attn2.run(_norm(x.reshape(B * N, D), self.norm2, T).reshape(B, N, D), context, residual=x,
                            context_lens=context_lens if context is not None else None,
                            context_segments=context_segments if context is not None else None,
@@ -49,10 +52,10 @@ class Layer(nn.Module):
                            context_weights=context_weights if context is not None else None,
                            keys=keys if context is not None else None, **kw)
         maps = None
-        if want_maps:
+        if want_maps or score is not None:
             x, maps = x
         x = self.ffnet.run(_norm(x.reshape(B * N, D), self.norm3, T).reshape(B, N, D), residual=x)
-        return (x, maps) if want_maps else x
+        return (x, maps) if want_maps or score is not None else x
 
 
 class CondTransformer(nn.Module):
@@ -69,14 +72,20 @@ class CondTransformer(nn.Module):
         self.to_logits = nn.Linear(dim, num_classes)
         _xavier_like_reference(self)
 
-    def _layers(self, h, maps_layers, context, keys, control=None):
+    def _layers(self, h, maps_layers, context, keys, control=None, score=None):
         """the tower over the projected context and the call's checked ``ops.Keys``; maps_layers (None, or the checked layer
         indices): -> (h, the mean of those layers' cross-attention maps);
-        control (None, or per controlled layer its keywords): prompt-to-prompt, never beside maps_layers"""
+        control (None, or per controlled layer its keywords): prompt-to-prompt, never beside maps_layers;
+        score (None, or (the tapped layers, w_src, w_edit, the pair to add to or None)): beside control -> (h, (score_src, score_edit)),
+        the first tapped layer writing unless there is a pair to add to, the later ones accumulating, each with scale 1 / n"""
         if control is not None:
+            running = None if score is None else score[3]
             for i, layer in enumerate(self.layers):
-                h = layer(h, context, keys=keys, **control.get(i, {}))
-            return h
+                if score is not None and i in score[0]:
+                    h, running = layer(h, context, keys=keys, score=(score[1], score[2], 1.0 / len(score[0]), running), **control.get(i, {}))
+                else:
+                    h = layer(h, context, keys=keys, **control.get(i, {}))
+            return h if score is None else (h, running)
         if maps_layers is None:
             for layer in self.layers:
                 h = layer(h, context, keys=keys)
@@ -103,6 +112,10 @@ class CondTransformer(nn.Module):
         control (extension, prompt-to-prompt; None = the call as without it): a dict with row_map, blend, gain
         ([B / 2, L]; required iff cross_layers), cross_layers and self_layers (distinct layer indices) over a batch of B / 2 pairs, the
         source images in front -- ``S2Engine.forward_control`` as a composition of operators.  Beside context_lens only.
+        With score_layers (distinct layer indices) and score_weights = (w_src, w_edit) ([B / 2, L], finite and >= 0, every pair with a
+        positive weight below its length in one half) in the dict (extension, the local blend) -> (logits,
+        scores), scores f32 [B, N] with the source half in front: the mean over those layers of ``ops.attention_phrase_score``, added
+        to the dict's `scores` when given.  cross_layers and self_layers may then both be empty.
         keys (instead of the four arrays): the call's checked ``ops.Keys``; it is not checked again."""
         keys = ops.host_keys(x.shape[0], 0 if context is None else context.shape[1], x.shape[1], context_lens, context_segments,
                              token_segments, context_weights, has_context=context is not None, keys=keys)
@@ -112,8 +125,21 @@ class CondTransformer(nn.Module):
             cl, sl = (ops.host_layers(control.get(k, ()), len(self.layers), "control: layers", allow_empty=True)
                       for k in ("cross_layers", "self_layers"))
             arrays = [control.get(k) for k in ("row_map", "blend", "gain")]
-            if not (cl or sl) or any(a is None for a in arrays) != (not cl) or any(a is None for a in arrays) != all(a is None for a in arrays):
+            scl = ops.host_layers(control.get("score_layers", ()), len(self.layers), "control: score_layers", allow_empty=True)
+            if not (cl or sl or scl) or any(a is None for a in arrays) != (not cl) or any(a is None for a in arrays) != all(a is None for a in arrays):
                 raise ValueError("control: a layer must be chosen; row_map, blend and gain are required with cross_layers and refused without")
+            if not scl and (control.get("score_weights") is not None or control.get("scores") is not None):
+                raise ValueError("control: score_weights and scores stand beside score_layers only")
+            score = None
+            if scl:
+                h2, into = x.shape[0] // 2, control.get("scores")
+                scores_in = into
+                w_src, w_edit = ops.host_phrase_weights(control.get("score_weights"), h2, context.shape[1])
+                ops.check_phrase_rows(w_src, w_edit, keys.lens, h2, context.shape[1])
+                if into is not None and not (isinstance(into, torch.Tensor) and into.dtype == torch.float32 and into.device == x.device and
+                                             tuple(into.shape) == (x.shape[0], x.shape[1]) and into.is_contiguous()):
+                    raise ValueError(f"control: scores must be a contiguous float32 [{x.shape[0]}, {x.shape[1]}] tensor on the tokens' device")
+                score = (scl, w_src, w_edit, None if into is None else (into[:h2], into[h2:]))
             ctl = ops.host_control(*arrays, x.shape[0] // 2, context.shape[1]) if cl else None
             control = {l: (dict(control=ctl) if l in cl else {}) | (dict(inject_self=True) if l in sl else {}) for l in set(cl) | set(sl)}
         if maps_layers is not None:
@@ -129,9 +155,11 @@ class CondTransformer(nn.Module):
             h = self.token_proj(x.float()) + self.position_embedding
             if context is not None:
                 context = self.context_proj(context.float())
-            h = self._layers(h, maps_layers, context, keys, control=control)
+            h = self._layers(h, maps_layers, context, keys, control=control, score=score if control is not None else None)
             if maps_layers is not None:
                 return self.to_logits(self.norm(h[0])), h[1]
+            if control is not None and score is not None:
+                return self.to_logits(self.norm(h[0])), torch.cat(h[1])
             return self.to_logits(self.norm(h))
         a = ops.convert_pad(x.contiguous().float().reshape(B * N, E), 64, T)
         pos = self.position_embedding.detach()[0].contiguous()
@@ -143,11 +171,16 @@ class CondTransformer(nn.Module):
             if isinstance(self.context_proj, nn.Linear):
                 c = ops.gemm(c, packing.pad_cols(self.context_proj.weight, c.shape[1], T))
             context = c.reshape(B, L, dim)
-        h = self._layers(h, maps_layers, context, keys, control=control)
+        h = self._layers(h, maps_layers, context, keys, control=control, score=score if control is not None else None)
         maps = None
+        if control is not None and score is not None:
+            h, halves = h
+            halves = torch.cat(halves) if score[3] is None else scores_in    # (the operator added to the caller's buffer in place)
         if maps_layers is not None:
             h, maps = h
         y = _norm(h.reshape(B * N, dim), self.norm, T)
         logits = ops.gemm(y, packing.cast(self.to_logits.weight, T), bias=self.to_logits.bias.detach().float(),
                           out_dtype=torch.float32)
+        if control is not None and score is not None:
+            return logits.reshape(B, N, -1), halves
         return (logits.reshape(B, N, -1), maps) if maps_layers is not None else logits.reshape(B, N, -1)
