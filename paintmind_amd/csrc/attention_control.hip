@@ -7,7 +7,7 @@
 //   O[b, q, h * dh : (h + 1) * dh] = sum_j P[q, j] * V[j, :]                     (no renormalisation)
 //
 // The flash kernels never hold a row of P, so neither pass's probabilities exist anywhere; this file recomputes both, in the two-pass
-// structure of attention_maps.hip.  A workgroup owns one (pair, head) and 64 queries:
+// structure of attention_maps.hip and from the shared pieces of attention_probs.h (which holds THE definition of `has` and P).  A workgroup owns one (pair, head) and 64 queries:
 //   pass 1 : the maximum m and the sum l of every query row of BOTH softmaxes, (m, 1 / l) kept in registers
 //   pass 2 : walk the target keys, recompute Qt . Kt[j] and Qs . Ks[row_map[j]] (the Ks ROWS are gathered through row_map; no P is
 //            stored), blend, scale, accumulate P . V
@@ -24,55 +24,17 @@
 // bounds: Lt_pad is a multiple of 4) and zeroed by a select; where `has` is false the gathered row is row 0 of the pair's
 // own Ks in the MFMA kernel (any lane must feed the matrix core something) and nothing in the other, and its score is dropped by a
 // select; source rows at or behind ns are never read.
-#include "common.h"
-
-#include <cmath>
+#include "attention_probs.h"
 
 namespace {
 
 struct CtlParams {
     void* out;
     int ldo, heads, Nq, Ls, Lsp, Lt, Ltp;
-    const int* row_map;                 // [B, Lt]
-    const float* blend;                 // [B, Lt]
-    const float* gain;                  // [B, Lt]
+    PairControl ctl;
     const int* lens_s;                  // [B] or NULL
     const int* lens_t;                  // [B] or NULL
 };
-
-template <bool EXP2> __device__ __forceinline__ float ctl_exp(float x) { return EXP2 ? exp2f(x) : expf(x); }
-
-// workgroup-uniform: the pair's key count, with the clamp of pmhip_attention_lens
-__device__ __forceinline__ int ctl_len(const int* lens, int b, int L) {
-    if (!lens) return L;
-    const int n = __builtin_amdgcn_readfirstlane(lens[b]);
-    return n < 1 ? 1 : (n > L ? L : n);
-}
-
-// one more key of an online softmax: (m, l) <- (max(m, s), l exp(m - max) + exp(s - max))
-template <bool EXP2> __device__ __forceinline__ void ctl_online(float& m, float& l, float s) {
-    const float mn = fmaxf(m, s);
-    l = fmaf(l, ctl_exp<EXP2>(m - mn), ctl_exp<EXP2>(s - mn));
-    m = mn;
-}
-
-// target key j < nt of pair b: its gain, and whether (and from which source row, with which blend) the source takes part
-struct CtlKey {
-    float gain, blend;
-    int row;
-    bool has;
-};
-__device__ __forceinline__ CtlKey ctl_key(const CtlParams& p, int b, int j, int ns) {
-    const size_t at = (size_t)b * p.Lt + j;
-    CtlKey k;
-    k.gain = p.gain[at]; k.blend = p.blend[at]; k.row = p.row_map[at];
-    k.has = (k.row >= 0) & (k.row < ns) & (k.blend != 0.f);
-    return k;
-}
-__device__ __forceinline__ float ctl_mix(const CtlKey& k, float pt, float ps) {
-    const float mixed = fmaf(k.blend, ps, (1.f - k.blend) * pt);
-    return k.gain * (k.has ? mixed : pt);
-}
 
 template <bool EXP2>
 __global__ __launch_bounds__(256) void attention_control_mfma_kernel(const bf16_t* __restrict__ Qs, const bf16_t* __restrict__ Ks,
@@ -81,7 +43,7 @@ __global__ __launch_bounds__(256) void attention_control_mfma_kernel(const bf16_
     const int bh = blockIdx.y, b = bh / p.heads, h = bh % p.heads;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
     const int Nq = p.Nq;
-    const int ns = ctl_len(p.lens_s, b, p.Ls), nt = ctl_len(p.lens_t, b, p.Lt);
+    const int ns = prob_len(p.lens_s, b, p.Ls), nt = prob_len(p.lens_t, b, p.Lt);
     const int q0 = blockIdx.x * 64 + wave * 16;
     const int qi = q0 + col;                                    // this lane's query: every score and every output it holds
     const int qa = qi < Nq ? qi : Nq - 1;                       // (rows past the end: a copy, never stored)
@@ -94,32 +56,9 @@ __global__ __launch_bounds__(256) void attention_control_mfma_kernel(const bf16_
     }
     const bf16_t* ksb = Ks + (size_t)bh * p.Lsp * 64 + g * 8;
     const bf16_t* ktb = Kt + (size_t)bh * p.Ltp * 64 + g * 8;
-    // acc[r] = s[key row of lane (4 g + r)][query col]: `row` is the K row THIS lane feeds, as key (lane & 15) of the tile
-    auto scores = [&](const bf16_t* kb, int row, const uint4& f0, const uint4& f1) -> f32x4_t {
-        const uint4* kp = reinterpret_cast<const uint4*>(kb + (size_t)row * 64);
-        const uint4 k0 = kp[0], k1 = kp[4];
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-        Mma<bf16_t>::run(acc, k0, f0);
-        Mma<bf16_t>::run(acc, k1, f1);
-        return acc;
-    };
-    // pass 1: (m, 1 / l) of this lane's query over n keys; the four lanes of a query hold the key residues 4 g + r of every tile
-    auto stats = [&](const bf16_t* kb, int n, const uint4& f0, const uint4& f1, float& mx, float& inv) {
-        float m = -INFINITY, l = 0.f;
-        for (int k0 = 0; k0 < n; k0 += 16) {
-            const int kr = k0 + col < n ? k0 + col : n - 1;     // no row at or behind n is read
-            const f32x4_t s = scores(kb, kr, f0, f1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (k0 + 4 * g + r < n) ctl_online<EXP2>(m, l, s[r]);
-        }
-        mx = group4_max(m);
-        const float ll = group4_sum(m == -INFINITY ? 0.f : l * ctl_exp<EXP2>(m - mx));
-        inv = 1.f / ll;                                         // n >= 1: key 0 takes part in every query
-    };
     float ms, is, mt, it;
-    stats(ksb, ns, qs0, qs1, ms, is);
-    stats(ktb, nt, qt0, qt1, mt, it);
+    kq_stats<EXP2>(ksb, ns, qs0, qs1, col, g, ms, is);
+    kq_stats<EXP2>(ktb, nt, qt0, qt1, col, g, mt, it);
 
     f32x4_t o[4];                                               // o[db][r] = O[query col][16 db + 4 g + r]
 #pragma unroll
@@ -135,23 +74,17 @@ __global__ __launch_bounds__(256) void attention_control_mfma_kernel(const bf16_
             for (int r = 0; r < 4; ++r) pr[4 * t + r] = 0.f;
             if (jb >= nt) continue;                             // (workgroup-uniform)
             const int kj = jb + col;
-            const f32x4_t st = scores(ktb, kj < nt ? kj : nt - 1, qt0, qt1);
-            // the source rows of the tile's 16 keys, gathered: lane (col, g) feeds the row of key jb + col
-            bool feed = false; int srow = 0;
-            if (kj < nt) {
-                const CtlKey k = ctl_key(p, b, kj, ns);
-                feed = k.has; srow = k.has ? k.row : 0;
-            }
+            const f32x4_t st = kq_scores(ktb, kj < nt ? kj : nt - 1, qt0, qt1);
             f32x4_t ss = {0.f, 0.f, 0.f, 0.f};
-            if (__builtin_amdgcn_ballot_w64(feed) != 0) ss = scores(ksb, srow, qs0, qs1);       // (wave-uniform)
+            PM_KQ_GATHER(ss, p.ctl, p.Lt, b, kj, nt, ns, ksb, qs0, qs1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = jb + 4 * g + r;
                 if (j < nt) {
-                    const CtlKey k = ctl_key(p, b, j, ns);
-                    const float pt = ctl_exp<EXP2>(st[r] - mt) * it;
-                    const float ps = k.has ? ctl_exp<EXP2>(ss[r] - ms) * is : 0.f;
-                    pr[4 * t + r] = ctl_mix(k, pt, ps);
+                    const PairKey k = pair_key(p.ctl, p.Lt, b, j, ns);
+                    const float pt = prob_exp<EXP2>(st[r] - mt) * it;
+                    const float ps = k.has ? prob_exp<EXP2>(ss[r] - ms) * is : 0.f;
+                    pr[4 * t + r] = pair_mix(k, pt, ps);
                 }
             }
         }
@@ -180,12 +113,6 @@ __global__ __launch_bounds__(256) void attention_control_mfma_kernel(const bf16_
     }
 }
 
-__device__ __forceinline__ float ctl_quad_sum(float v) {
-    v += dpp_mov<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);      // quad_perm [2,3,0,1]
-    return v;
-}
-
 // DPL = dims per lane = dh / 4
 template <typename T, int DPL, bool EXP2>
 __global__ __launch_bounds__(256) void attention_control_valu_kernel(const T* __restrict__ Qs, const T* __restrict__ Ks,
@@ -194,7 +121,7 @@ __global__ __launch_bounds__(256) void attention_control_valu_kernel(const T* __
     constexpr int DH = DPL * 4;
     const int bh = blockIdx.y, b = bh / p.heads, h = bh % p.heads;
     const int Nq = p.Nq;
-    const int ns = ctl_len(p.lens_s, b, p.Ls), nt = ctl_len(p.lens_t, b, p.Lt);
+    const int ns = prob_len(p.lens_s, b, p.Ls), nt = prob_len(p.lens_t, b, p.Lt);
     const int qi = blockIdx.x * 64 + (threadIdx.x >> 2), part = threadIdx.x & 3;
     const int qr = qi < Nq ? qi : Nq - 1;                       // rows past the end compute a copy and do not store
     float qs[DPL], qt[DPL], o[DPL];
@@ -207,24 +134,17 @@ __global__ __launch_bounds__(256) void attention_control_valu_kernel(const T* __
     const T* ksb = Ks + (size_t)bh * p.Lsp * DH + part * DPL;
     const T* ktb = Kt + (size_t)bh * p.Ltp * DH + part * DPL;
     const T* vp = Vt + ((size_t)bh * DH + part * DPL) * p.Ltp;
-    auto score = [&](const T* kb, int row, const float (&q)[DPL]) -> float {  // every lane of the quad returns the score
-        const T* kp = kb + (size_t)row * DH;
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) s = fmaf(q[i], to_f32<T>(kp[i]), s);
-        return ctl_quad_sum(s);
-    };
-    float ms = -INFINITY, ls = 0.f, mt = -INFINITY, lt = 0.f;
-    for (int k = 0; k < ns; ++k) ctl_online<EXP2>(ms, ls, score(ksb, k, qs));
-    for (int j = 0; j < nt; ++j) ctl_online<EXP2>(mt, lt, score(ktb, j, qt));
+    float ms = -INFINITY, ls = 0.f, mt = -INFINITY, lt = 0.f;   // pass 1
+    for (int k = 0; k < ns; ++k) prob_online<EXP2>(ms, ls, quad_score<T, DPL>(ksb, k, qs));
+    for (int j = 0; j < nt; ++j) prob_online<EXP2>(mt, lt, quad_score<T, DPL>(ktb, j, qt));
     const float is = 1.f / ls, it = 1.f / lt;
 
     for (int j = 0; j < nt; ++j) {
-        const CtlKey k = ctl_key(p, b, j, ns);                  // (workgroup-uniform: the quads stay whole)
-        const float pt = ctl_exp<EXP2>(score(ktb, j, qt) - mt) * it;
+        const PairKey k = pair_key(p.ctl, p.Lt, b, j, ns);                  // (workgroup-uniform: the quads stay whole)
+        const float pt = prob_exp<EXP2>(quad_score<T, DPL>(ktb, j, qt) - mt) * it;
         float ps = 0.f;
-        if (k.has) ps = ctl_exp<EXP2>(score(ksb, k.row, qs) - ms) * is;
-        const float pj = ctl_mix(k, pt, ps);
+        if (k.has) ps = prob_exp<EXP2>(quad_score<T, DPL>(ksb, k.row, qs) - ms) * is;
+        const float pj = pair_mix(k, pt, ps);
 #pragma unroll
         for (int i = 0; i < DPL; ++i) o[i] = fmaf(pj, to_f32<T>(vp[(size_t)i * p.Ltp + j]), o[i]);
     }
@@ -235,24 +155,15 @@ __global__ __launch_bounds__(256) void attention_control_valu_kernel(const T* __
     }
 }
 
-template <typename T, int DPL>
-void launch_control_valu(const void* Qs, const void* Ks, const void* Qt, const void* Kt, const void* Vt, const CtlParams& p, int B,
-                         int use_exp2, hipStream_t s) {
-    auto k = use_exp2 ? attention_control_valu_kernel<T, DPL, true> : attention_control_valu_kernel<T, DPL, false>;
-    hipLaunchKernelGGL(k, dim3((p.Nq + 63) / 64, B * p.heads), dim3(256), 0, s, (const T*)Qs, (const T*)Ks, (const T*)Qt, (const T*)Kt,
-                       (const T*)Vt, p);
-}
-
 template <typename T>
 int control_valu(int dh, const void* Qs, const void* Ks, const void* Qt, const void* Kt, const void* Vt, const CtlParams& p, int B,
                  int use_exp2, hipStream_t s) {
-    switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_control_valu<T, n>(Qs, Ks, Qt, Kt, Vt, p, B, use_exp2, s); break;
-        PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
-#undef PM_DH_CASE
-        default: PM_REQUIRE(false, "attention_control: dim_head=%d not served", dh);
-    }
-    return PMHIP_OK;
+    return pm_dh_dispatch("attention_control", dh, [&](auto dpl) {
+        constexpr int DPL = decltype(dpl)::value;
+        auto k = use_exp2 ? attention_control_valu_kernel<T, DPL, true> : attention_control_valu_kernel<T, DPL, false>;
+        hipLaunchKernelGGL(k, dim3((p.Nq + 63) / 64, B * p.heads), dim3(256), 0, s, (const T*)Qs, (const T*)Ks, (const T*)Qt, (const T*)Kt,
+                           (const T*)Vt, p);
+    });
 }
 
 }  // namespace
@@ -261,24 +172,20 @@ extern "C" int pmhip_attention_control(int dtype, const void* Qs, const void* Ks
                                        int ldo, int B, int heads, int dim_head, int Nq, int Ls, int Ls_pad, int Lt, int Lt_pad,
                                        int use_exp2, const int32_t* row_map, const float* blend, const float* gain, const int32_t* lens_s,
                                        const int32_t* lens_t, pmhip_stream stream) {
-    PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "attention_control: bad dtype %d", dtype);
+    PM_TRY(pm_probs_check("attention_control", dtype, dim_head, heads, {{"Ls", Ls, Ls_pad}, {"Lt", Lt, Lt_pad}}));
     PM_REQUIRE(Qs && Ks && Qt && Kt && Vt && out, "attention_control: null pointer");
     PM_REQUIRE(row_map && blend && gain, "attention_control: row_map / blend / gain is NULL (pmhip_attention_lens is the entry without control)");
     PM_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Ls > 0 && Lt > 0, "attention_control: empty problem");
-    PM_REQUIRE(dim_head >= 16 && dim_head <= 128 && dim_head % 16 == 0, "attention_control: dim_head=%d must be a multiple of 16 in [16,128]", dim_head);
-    PM_REQUIRE(heads <= 64, "attention_control: heads=%d exceeds 64", heads);
-    PM_REQUIRE(Ls_pad >= Ls, "attention_control: Ls_pad=%d must be >= Ls=%d", Ls_pad, Ls);
-    PM_REQUIRE(Lt_pad >= Lt, "attention_control: Lt_pad=%d must be >= Lt=%d", Lt_pad, Lt);
     PM_REQUIRE(ldo >= heads * dim_head, "attention_control: ldo=%d is smaller than heads*dim_head=%d (rows of out would overlap)", ldo, heads * dim_head);
     PM_REQUIRE((long long)B * heads <= 65535, "attention_control: B*heads=%lld exceeds the grid's y range", (long long)B * heads);
     hipStream_t s = (hipStream_t)stream;
     CtlParams p{};
     p.out = out; p.ldo = ldo; p.heads = heads; p.Nq = Nq; p.Ls = Ls; p.Lsp = Ls_pad; p.Lt = Lt; p.Ltp = Lt_pad;
-    p.row_map = row_map; p.blend = blend; p.gain = gain; p.lens_s = lens_s; p.lens_t = lens_t;
+    p.ctl = {row_map, blend, gain}; p.lens_s = lens_s; p.lens_t = lens_t;
     const bool mfma = dtype == PMHIP_BF16 && dim_head == 64;
     if (mfma) {
-        PM_REQUIRE(((uintptr_t)Qs | (uintptr_t)Ks | (uintptr_t)Qt | (uintptr_t)Kt) % 16 == 0, "attention_control: Q and K must be 16-byte aligned");
-        PM_REQUIRE(((uintptr_t)Vt | (uintptr_t)out) % 8 == 0, "attention_control: Vt and out must be 8-byte aligned");
+        PM_REQUIRE(pm_aligned(16, {Qs, Ks, Qt, Kt}), "attention_control: Q and K must be 16-byte aligned");
+        PM_REQUIRE(pm_aligned(8, {Vt, out}), "attention_control: Vt and out must be 8-byte aligned");
         PM_REQUIRE(Lt_pad % 4 == 0, "attention_control: Lt_pad=%d must be a multiple of 4 (8-byte V^T loads)", Lt_pad);
         PM_REQUIRE(ldo % 4 == 0, "attention_control: ldo=%d must be a multiple of 4 (8-byte row stores)", ldo);
     }

@@ -43,12 +43,6 @@ __global__ __launch_bounds__(256) void head_split_kernel(SplitParams p) {
     }
 }
 
-__device__ __forceinline__ float quad_sum(float v) {
-    v += dpp_mov<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);      // quad_perm [2,3,0,1]
-    return v;
-}
-
 // DPL = dims per lane = dh / 4
 #define PM_ATTN_BODY "attention_dh_body.h"
 #define PM_ATTN_NAME(sfx) attention_dh##sfx##kernel
@@ -85,13 +79,7 @@ void launch_dh(const PmAttnArgs& a) {
 // the launcher of this file's kernels: dim_head != 64, already passed through check_dh
 template <typename T>
 int pm_attention_dh(int dh, const PmAttnArgs& a) {
-    switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_dh<T, n>(a); break;
-        PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
-#undef PM_DH_CASE
-        default: PM_REQUIRE(false, "attention_dh: dim_head=%d not served", dh);
-    }
-    return PMHIP_OK;
+    return pm_dh_dispatch("attention_dh", dh, [&](auto dpl) { launch_dh<T, decltype(dpl)::value>(a); });
 }
 
 int check_dh(const char* who, int heads, int dim_head) {
@@ -138,6 +126,14 @@ int pm_attn_check(const char* who, const PmAttnArgs& a) {
     PM_REQUIRE(!(a.lens && a.key_seg), "%s: kv_lens and the pair key_seg + query_mask exclude each other (padding is segment 255)", who);
     PM_REQUIRE(!a.key_bias || a.key_seg, "%s: key_bias needs key_seg and query_mask beside it", who);
     if (a.pick) PM_REQUIRE(a.want >= 0 && a.want <= 255, "%s: want=%d is no value of a uint8 pick", who, a.want);
+    return PMHIP_OK;
+}
+
+int pm_probs_check(const char* who, int dtype, int dim_head, int heads, std::initializer_list<PmContext> contexts) {
+    PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "%s: bad dtype %d", who, dtype);
+    PM_REQUIRE(dim_head >= 16 && dim_head <= 128 && dim_head % 16 == 0, "%s: dim_head=%d must be a multiple of 16 in [16,128]", who, dim_head);
+    PM_REQUIRE(heads <= 64, "%s: heads=%d exceeds 64", who, heads);
+    for (const PmContext& c : contexts) PM_REQUIRE(c.pad >= c.len, "%s: %s_pad=%d must be >= %s=%d", who, c.name, c.pad, c.name, c.len);
     return PMHIP_OK;
 }
 

@@ -18,9 +18,7 @@
 // A key that takes part in no softmax of a query (behind the image's length, a denied segment, segment 255, bias -inf) contributes
 // through a select, never through arithmetic: NaN in its K row reaches nothing, and its element is written as 0.0f (left alone
 // under `accumulate`).  K rows are read below Nkv only (tile tails re-read row Nkv - 1 and are masked).
-#include "common.h"
-
-#include <cmath>
+#include "attention_probs.h"
 
 namespace {
 
@@ -35,8 +33,6 @@ struct MapParams {
     int accumulate;
 };
 
-template <bool EXP2> __device__ __forceinline__ float map_exp(float x) { return EXP2 ? exp2f(x) : expf(x); }
-
 // this image's view of the forms: after it, a key takes part in query q's softmax iff seg(key) < 32 and bit seg(key) of mask(q) is set
 struct MapKeys {
     const unsigned char* segb;
@@ -45,11 +41,7 @@ struct MapKeys {
     __device__ __forceinline__ MapKeys(const MapParams& p, int b) {
         segb = p.key_seg ? p.key_seg + (size_t)b * p.Nkv : nullptr;
         biasb = p.key_bias ? p.key_bias + (size_t)b * p.Nkv : nullptr;
-        nb = p.Nkv;
-        if (p.lens) {                                           // workgroup-uniform, the clamp of pmhip_attention_lens
-            const int n = __builtin_amdgcn_readfirstlane(p.lens[b]);
-            nb = n < 1 ? 1 : (n > p.Nkv ? p.Nkv : n);
-        }
+        nb = prob_len(p.lens, b, p.Nkv);
     }
     // segment of `key` (255: excluded for every query) and its bias (0 without weights)
     __device__ __forceinline__ void of(int key, unsigned& sg, float& kb) const {
@@ -76,13 +68,6 @@ __device__ __forceinline__ void map_store(const MapParams& p, int b, int q, int 
     } else {
         *o = ok ? v : 0.f;
     }
-}
-
-// one more key of an online softmax: (m, l) <- (max(m, s), l exp(m - max) + exp(s - max))
-template <bool EXP2> __device__ __forceinline__ void map_online(float& m, float& l, float s) {
-    const float mn = fmaxf(m, s);
-    l = fmaf(l, map_exp<EXP2>(m - mn), map_exp<EXP2>(s - mn));
-    m = mn;
 }
 
 // reductions over the 16 lanes of a DPP row
@@ -138,12 +123,12 @@ __global__ __launch_bounds__(256) void attention_maps_mfma_kernel(const bf16_t* 
             const f32x4_t s = scores(h, k0 + col, f0, f1);
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (map_allowed(sg, qm[r])) map_online<EXP2>(m[r], l[r], s[r] + kb);
+                if (map_allowed(sg, qm[r])) prob_online<EXP2>(m[r], l[r], s[r] + kb);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                           // the 16 lanes of a row hold the 16 key residues of one query
             const float mm = row16_max(m[r]);
-            const float ll = row16_sum(m[r] == -INFINITY ? 0.f : l[r] * map_exp<EXP2>(m[r] - mm));
+            const float ll = row16_sum(m[r] == -INFINITY ? 0.f : l[r] * prob_exp<EXP2>(m[r] - mm));
             if (col == 0) map_stat[h * 64 + wave * 16 + 4 * g + r] = make_float2(mm, ll > 0.f ? 1.f / ll : 0.f);
         }
     }
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(256) void attention_maps_mfma_kernel(const bf16_t* 
                 const f32x4_t s = scores(h, c0 + 16 * t + col, f0, f1);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float pr = map_exp<EXP2>(s[r] + kb[t] - st[r].x) * st[r].y;
+                    const float pr = prob_exp<EXP2>(s[r] + kb[t] - st[r].x) * st[r].y;
                     sum[t][r] += map_allowed(sg[t], qm[r]) ? pr : 0.f;
                 }
             }
@@ -185,12 +170,6 @@ __global__ __launch_bounds__(256) void attention_maps_mfma_kernel(const bf16_t* 
             }
         }
     }
-}
-
-__device__ __forceinline__ float map_quad_sum(float v) {
-    v += dpp_mov<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);      // quad_perm [2,3,0,1]
-    return v;
 }
 
 // DPL = dims per lane = dh / 4
@@ -210,12 +189,8 @@ __global__ __launch_bounds__(256) void attention_maps_valu_kernel(const T* __res
 #pragma unroll
         for (int i = 0; i < DPL; ++i) q[i] = to_f32<T>(qp[i]);
     };
-    auto score = [&](int h, int j) -> float {                   // j < Nkv; every lane of the quad returns the score
-        const T* kp = K + (((size_t)b * heads + h) * p.Nkp + j) * DH + part * DPL;
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < DPL; ++i) s = fmaf(q[i], to_f32<T>(kp[i]), s);
-        return map_quad_sum(s);
+    auto score = [&](int h, int j) -> float {                   // j < Nkv
+        return quad_score<T, DPL>(K + (((size_t)b * heads + h) * p.Nkp + j) * DH + part * DPL, q);
     };
 
     for (int h = 0; h < heads; ++h) {
@@ -225,7 +200,7 @@ __global__ __launch_bounds__(256) void attention_maps_valu_kernel(const T* __res
             const float s = score(h, j);
             unsigned sg; float kb;
             keys.of(j, sg, kb);                                 // (wave-uniform address; the four lanes of a query agree)
-            if (map_allowed(sg, qm)) map_online<EXP2>(m, l, s + kb);
+            if (map_allowed(sg, qm)) prob_online<EXP2>(m, l, s + kb);
         }
         if (part == 0) map_stat[h * 64 + ql] = make_float2(m, l > 0.f ? 1.f / l : 0.f);
     }
@@ -243,7 +218,7 @@ __global__ __launch_bounds__(256) void attention_maps_valu_kernel(const T* __res
                 const float s = score(h, j);
                 unsigned sg; float kb;
                 keys.of(j, sg, kb);
-                const float pr = map_exp<EXP2>(s + kb - st.x) * st.y;
+                const float pr = prob_exp<EXP2>(s + kb - st.x) * st.y;
                 sum[jj & 3] += ((jj >> 2) == part && map_allowed(sg, qm)) ? pr : 0.f;
             }
         }
@@ -259,21 +234,13 @@ __global__ __launch_bounds__(256) void attention_maps_valu_kernel(const T* __res
     }
 }
 
-template <typename T, int DPL>
-void launch_maps_valu(const void* Q, const void* K, const MapParams& p, int B, int use_exp2, hipStream_t s) {
-    auto k = use_exp2 ? attention_maps_valu_kernel<T, DPL, true> : attention_maps_valu_kernel<T, DPL, false>;
-    hipLaunchKernelGGL(k, dim3((p.Nq + 63) / 64, B), dim3(256), (size_t)p.heads * 64 * sizeof(float2), s, (const T*)Q, (const T*)K, p);
-}
-
 template <typename T>
 int maps_valu(int dh, const void* Q, const void* K, const MapParams& p, int B, int use_exp2, hipStream_t s) {
-    switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_maps_valu<T, n>(Q, K, p, B, use_exp2, s); break;
-        PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
-#undef PM_DH_CASE
-        default: PM_REQUIRE(false, "attention_maps: dim_head=%d not served", dh);
-    }
-    return PMHIP_OK;
+    return pm_dh_dispatch("attention_maps", dh, [&](auto dpl) {
+        constexpr int DPL = decltype(dpl)::value;
+        auto k = use_exp2 ? attention_maps_valu_kernel<T, DPL, true> : attention_maps_valu_kernel<T, DPL, false>;
+        hipLaunchKernelGGL(k, dim3((p.Nq + 63) / 64, B), dim3(256), (size_t)p.heads * 64 * sizeof(float2), s, (const T*)Q, (const T*)K, p);
+    });
 }
 
 }  // namespace
@@ -281,12 +248,9 @@ int maps_valu(int dh, const void* Q, const void* K, const MapParams& p, int B, i
 extern "C" int pmhip_attention_maps(int dtype, const void* Q, const void* K, float* maps, int ldm, int B, int heads, int dim_head, int Nq,
                                     int Nkv, int Nkv_pad, int use_exp2, const int32_t* kv_lens, const uint8_t* key_seg,
                                     const uint32_t* query_mask, const float* key_bias, float scale, int accumulate, pmhip_stream stream) {
-    PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "attention_maps: bad dtype %d", dtype);
+    PM_TRY(pm_probs_check("attention_maps", dtype, dim_head, heads, {{"Nkv", Nkv, Nkv_pad}}));    // (heads: the row statistics live in LDS)
     PM_REQUIRE(Q && K && maps, "attention_maps: null pointer");
     PM_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Nkv > 0, "attention_maps: empty problem");
-    PM_REQUIRE(dim_head >= 16 && dim_head <= 128 && dim_head % 16 == 0, "attention_maps: dim_head=%d must be a multiple of 16 in [16,128]", dim_head);
-    PM_REQUIRE(heads <= 64, "attention_maps: heads=%d exceeds 64 (the per-head row statistics live in LDS)", heads);
-    PM_REQUIRE(Nkv_pad >= Nkv, "attention_maps: Nkv_pad=%d must be >= Nkv=%d", Nkv_pad, Nkv);
     PM_REQUIRE(ldm >= Nkv, "attention_maps: ldm=%d is smaller than Nkv=%d (rows of maps would overlap)", ldm, Nkv);
     PM_REQUIRE(B <= 65535, "attention_maps: B=%d exceeds the grid's y range", B);
     PmAttnArgs a{};                                             // the optional arrays only: the rule of every attention entry
@@ -300,7 +264,7 @@ extern "C" int pmhip_attention_maps(int dtype, const void* Q, const void* K, flo
     p.factor = scale * (1.0f / (float)heads); p.accumulate = accumulate != 0;
     PmTimer tm(FAM_ATTENTION, s);
     if (dtype == PMHIP_BF16 && dim_head == 64) {
-        PM_REQUIRE(((uintptr_t)Q | (uintptr_t)K) % 16 == 0, "attention_maps: Q and K must be 16-byte aligned");
+        PM_REQUIRE(pm_aligned(16, {Q, K}), "attention_maps: Q and K must be 16-byte aligned");
         auto k = use_exp2 ? attention_maps_mfma_kernel<true> : attention_maps_mfma_kernel<false>;
         hipLaunchKernelGGL(k, dim3((Nq + 63) / 64, B), dim3(256), (size_t)heads * 64 * sizeof(float2), s, (const bf16_t*)Q, (const bf16_t*)K, p);
     } else if (dtype == PMHIP_F32) {

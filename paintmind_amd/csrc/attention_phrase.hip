@@ -1,8 +1,8 @@
 // Local blend of a prompt-to-prompt pair: where the pair looks at a phrase, the region that follows from it, and the
 // token blend under that region.
 //
-// pmhip_attention_phrase_score.  Per pair b and query q, over the heads h, with ps, pt, has and P those of attention_control.hip
-// (P = pt when the control arrays are NULL):
+// pmhip_attention_phrase_score.  Per pair b and query q, over the heads h, with ps, pt, has and P those of the pair control
+// (attention_probs.h; P = pt when the control arrays are NULL):
 //
 //   score_s[b, q] (+)= scale / heads * sum_h sum_{k < ns} w_s[b, k] * ps_h[q, k]
 //   score_t[b, q] (+)= scale / heads * sum_h sum_{j < nt} w_t[b, j] * P_h[q, j]
@@ -11,8 +11,8 @@
 // pmhip_attention_control owns one head per workgroup.  This file recomputes both softmaxes in the two-pass structure of
 // attention_maps.hip -- a workgroup owns one pair and 64 queries and walks both contexts twice PER HEAD:
 //   pass 1 : the maximum m and the sum l of every query row of both softmaxes, (m, 1 / l) kept in registers
-//   pass 2 : walk the source keys (w_s . ps) and the target keys (w_t . P; the Ks rows gathered through row_map as the control kernel
-//            gathers them), adding into two registers that live across the loop over the heads h = 0 .. heads-1
+//   pass 2 : walk the source keys (w_s . ps) and the target keys (w_t . P; the Ks rows gathered through row_map by the control
+//            kernel's own PM_KQ_GATHER), adding into two registers that live across the loop over the heads h = 0 .. heads-1
 // so registers do not depend on the contexts, there is no LDS, the sum over heads and keys has a fixed order, every element of the
 // two outputs is written by exactly one thread once, and there are no atomics.  P stays f32 in both dtypes.
 //   attention_phrase_mfma_kernel  bf16, dim_head 64.  S^T = K Q^T by v_mfma_f32_16x16x32_bf16, operands straight from global memory in
@@ -27,9 +27,7 @@
 //
 // pmhip_phrase_region: the rule of Pipeline.phrase_mask on both halves, joined, then dilated; one workgroup per pair, the grid in LDS.
 // pmhip_blend_tokens: outside the region the edited half's (pred, merged, score) become the source half's.
-#include "common.h"
-
-#include <cmath>
+#include "attention_probs.h"
 
 namespace {
 
@@ -37,9 +35,7 @@ struct PhrParams {
     float* score_s;                     // [B, Nq]
     float* score_t;                     // [B, Nq]
     int heads, Nq, Ls, Lsp, Lt, Ltp;
-    const int* row_map;                 // [B, Lt], or all three NULL: no control
-    const float* blend;                 // [B, Lt]
-    const float* gain;                  // [B, Lt]
+    PairControl ctl;                    // or all three NULL: no control
     const int* lens_s;                  // [B] or NULL
     const int* lens_t;                  // [B] or NULL
     const float* w_s;                   // [B, Ls]
@@ -47,40 +43,6 @@ struct PhrParams {
     float factor;                       // scale / heads
     int accumulate;
 };
-
-template <bool EXP2> __device__ __forceinline__ float phr_exp(float x) { return EXP2 ? exp2f(x) : expf(x); }
-
-// workgroup-uniform: the pair's key count, with the clamp of pmhip_attention_lens
-__device__ __forceinline__ int phr_len(const int* lens, int b, int L) {
-    if (!lens) return L;
-    const int n = __builtin_amdgcn_readfirstlane(lens[b]);
-    return n < 1 ? 1 : (n > L ? L : n);
-}
-
-// one more key of an online softmax: (m, l) <- (max(m, s), l exp(m - max) + exp(s - max))
-template <bool EXP2> __device__ __forceinline__ void phr_online(float& m, float& l, float s) {
-    const float mn = fmaxf(m, s);
-    l = fmaf(l, phr_exp<EXP2>(m - mn), phr_exp<EXP2>(s - mn));
-    m = mn;
-}
-
-// target key j < nt of pair b under control: the arithmetic of attention_control.hip, term for term
-struct PhrKey {
-    float gain, blend;
-    int row;
-    bool has;
-};
-__device__ __forceinline__ PhrKey phr_key(const PhrParams& p, int b, int j, int ns) {
-    const size_t at = (size_t)b * p.Lt + j;
-    PhrKey k;
-    k.gain = p.gain[at]; k.blend = p.blend[at]; k.row = p.row_map[at];
-    k.has = (k.row >= 0) & (k.row < ns) & (k.blend != 0.f);
-    return k;
-}
-__device__ __forceinline__ float phr_mix(const PhrKey& k, float pt, float ps) {
-    const float mixed = fmaf(k.blend, ps, (1.f - k.blend) * pt);
-    return k.gain * (k.has ? mixed : pt);
-}
 
 __device__ __forceinline__ void phr_store(const PhrParams& p, int b, int q, float ss, float st) {
     const size_t at = (size_t)b * p.Nq + q;
@@ -98,35 +60,12 @@ __global__ __launch_bounds__(256) void attention_phrase_mfma_kernel(const bf16_t
     const int b = blockIdx.y;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 15, g = lane >> 4;
     const int Nq = p.Nq, heads = p.heads;
-    const int ns = phr_len(p.lens_s, b, p.Ls), nt = phr_len(p.lens_t, b, p.Lt);
-    const bool ctl = p.row_map != nullptr;                      // (uniform over the launch)
+    const int ns = prob_len(p.lens_s, b, p.Ls), nt = prob_len(p.lens_t, b, p.Lt);
+    const bool ctl = p.ctl.row_map != nullptr;                      // (uniform over the launch)
     const int qi = blockIdx.x * 64 + wave * 16 + col;           // this lane's query: every score it holds
     const int qa = qi < Nq ? qi : Nq - 1;                       // (rows past the end: a copy, never stored)
     const float* wsb = p.w_s + (size_t)b * p.Ls;
     const float* wtb = p.w_t + (size_t)b * p.Lt;
-    // acc[r] = s[key row of lane (4 g + r)][query col]: `row` is the K row THIS lane feeds, as key (lane & 15) of the tile
-    auto scores = [&](const bf16_t* kb, int row, const uint4& f0, const uint4& f1) -> f32x4_t {
-        const uint4* kp = reinterpret_cast<const uint4*>(kb + (size_t)row * 64);
-        const uint4 k0 = kp[0], k1 = kp[4];
-        f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-        Mma<bf16_t>::run(acc, k0, f0);
-        Mma<bf16_t>::run(acc, k1, f1);
-        return acc;
-    };
-    // pass 1: (m, 1 / l) of this lane's query over n keys; the four lanes of a query hold the key residues 4 g + r of every tile
-    auto stats = [&](const bf16_t* kb, int n, const uint4& f0, const uint4& f1, float& mx, float& inv) {
-        float m = -INFINITY, l = 0.f;
-        for (int k0 = 0; k0 < n; k0 += 16) {
-            const int kr = k0 + col < n ? k0 + col : n - 1;     // no row at or behind n is read
-            const f32x4_t s = scores(kb, kr, f0, f1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (k0 + 4 * g + r < n) phr_online<EXP2>(m, l, s[r]);
-        }
-        mx = group4_max(m);
-        const float ll = group4_sum(m == -INFINITY ? 0.f : l * phr_exp<EXP2>(m - mx));
-        inv = 1.f / ll;                                         // n >= 1: key 0 takes part in every query
-    };
     // the weights of this lane's four keys of the tile at k0 (0 by a select at or behind n) and whether any lane of the wave has one
     auto tile_weights = [&](const float* wb, int k0, int n, float (&w)[4]) -> bool {
         bool any = false;
@@ -152,16 +91,16 @@ __global__ __launch_bounds__(256) void attention_phrase_mfma_kernel(const bf16_t
         const bf16_t* ksb = Ks + bh * p.Lsp * 64 + g * 8;
         const bf16_t* ktb = Kt + bh * p.Ltp * 64 + g * 8;
         float ms, is, mt, it;
-        stats(ksb, ns, qs0, qs1, ms, is);
-        stats(ktb, nt, qt0, qt1, mt, it);
+        kq_stats<EXP2>(ksb, ns, qs0, qs1, col, g, ms, is);
+        kq_stats<EXP2>(ktb, nt, qt0, qt1, col, g, mt, it);
 
         for (int k0 = 0; k0 < ns; k0 += 16) {                   // w_s . ps
             float w[4];
             if (!tile_weights(wsb, k0, ns, w)) continue;
-            const f32x4_t s = scores(ksb, k0 + col < ns ? k0 + col : ns - 1, qs0, qs1);
+            const f32x4_t s = kq_scores(ksb, k0 + col < ns ? k0 + col : ns - 1, qs0, qs1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float pr = phr_exp<EXP2>(s[r] - ms) * is;
+                const float pr = prob_exp<EXP2>(s[r] - ms) * is;
                 acc_s += (k0 + 4 * g + r < ns) ? w[r] * pr : 0.f;
             }
         }
@@ -169,26 +108,18 @@ __global__ __launch_bounds__(256) void attention_phrase_mfma_kernel(const bf16_t
             float w[4];
             if (!tile_weights(wtb, j0, nt, w)) continue;
             const int kj = j0 + col;
-            const f32x4_t st = scores(ktb, kj < nt ? kj : nt - 1, qt0, qt1);
+            const f32x4_t st = kq_scores(ktb, kj < nt ? kj : nt - 1, qt0, qt1);
             f32x4_t ss = {0.f, 0.f, 0.f, 0.f};
-            if (ctl) {
-                // the source rows of the tile's 16 keys, gathered: lane (col, g) feeds the row of key j0 + col
-                bool feed = false; int srow = 0;
-                if (kj < nt) {
-                    const PhrKey k = phr_key(p, b, kj, ns);
-                    feed = k.has; srow = k.has ? k.row : 0;
-                }
-                if (__builtin_amdgcn_ballot_w64(feed) != 0) ss = scores(ksb, srow, qs0, qs1);       // (wave-uniform)
-            }
+            if (ctl) PM_KQ_GATHER(ss, p.ctl, p.Lt, b, kj, nt, ns, ksb, qs0, qs1);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = j0 + 4 * g + r;
                 if (j < nt) {
-                    float pj = phr_exp<EXP2>(st[r] - mt) * it;
+                    float pj = prob_exp<EXP2>(st[r] - mt) * it;
                     if (ctl) {
-                        const PhrKey k = phr_key(p, b, j, ns);
-                        const float ps = k.has ? phr_exp<EXP2>(ss[r] - ms) * is : 0.f;
-                        pj = phr_mix(k, pj, ps);
+                        const PairKey k = pair_key(p.ctl, p.Lt, b, j, ns);
+                        const float ps = k.has ? prob_exp<EXP2>(ss[r] - ms) * is : 0.f;
+                        pj = pair_mix(k, pj, ps);
                     }
                     acc_t += w[r] * pj;
                 }
@@ -200,12 +131,6 @@ __global__ __launch_bounds__(256) void attention_phrase_mfma_kernel(const bf16_t
     if (g == 0 && qi < Nq) phr_store(p, b, qi, acc_s, acc_t);
 }
 
-__device__ __forceinline__ float phr_quad_sum(float v) {
-    v += dpp_mov<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_mov<0x4E>(v);      // quad_perm [2,3,0,1]
-    return v;
-}
-
 // DPL = dims per lane = dh / 4
 template <typename T, int DPL, bool EXP2>
 __global__ __launch_bounds__(256) void attention_phrase_valu_kernel(const T* __restrict__ Qs, const T* __restrict__ Ks,
@@ -213,8 +138,8 @@ __global__ __launch_bounds__(256) void attention_phrase_valu_kernel(const T* __r
     constexpr int DH = DPL * 4;
     const int b = blockIdx.y;
     const int Nq = p.Nq, heads = p.heads;
-    const int ns = phr_len(p.lens_s, b, p.Ls), nt = phr_len(p.lens_t, b, p.Lt);
-    const bool ctl = p.row_map != nullptr;
+    const int ns = prob_len(p.lens_s, b, p.Ls), nt = prob_len(p.lens_t, b, p.Lt);
+    const bool ctl = p.ctl.row_map != nullptr;
     const int qi = blockIdx.x * 64 + (threadIdx.x >> 2), part = threadIdx.x & 3;
     const int qr = qi < Nq ? qi : Nq - 1;                       // rows past the end compute a copy and do not store
     const float* wsb = p.w_s + (size_t)b * p.Ls;
@@ -231,32 +156,25 @@ __global__ __launch_bounds__(256) void attention_phrase_valu_kernel(const T* __r
         }
         const T* ksb = Ks + bh * p.Lsp * DH + part * DPL;
         const T* ktb = Kt + bh * p.Ltp * DH + part * DPL;
-        auto score = [&](const T* kb, int row, const float (&q)[DPL]) -> float {  // every lane of the quad returns the score
-            const T* kp = kb + (size_t)row * DH;
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < DPL; ++i) s = fmaf(q[i], to_f32<T>(kp[i]), s);
-            return phr_quad_sum(s);
-        };
-        float ms = -INFINITY, ls = 0.f, mt = -INFINITY, lt = 0.f;
-        for (int k = 0; k < ns; ++k) phr_online<EXP2>(ms, ls, score(ksb, k, qs));
-        for (int j = 0; j < nt; ++j) phr_online<EXP2>(mt, lt, score(ktb, j, qt));
+        float ms = -INFINITY, ls = 0.f, mt = -INFINITY, lt = 0.f;                   // pass 1
+        for (int k = 0; k < ns; ++k) prob_online<EXP2>(ms, ls, quad_score<T, DPL>(ksb, k, qs));
+        for (int j = 0; j < nt; ++j) prob_online<EXP2>(mt, lt, quad_score<T, DPL>(ktb, j, qt));
         const float is = 1.f / ls, it = 1.f / lt;
 
         for (int k = 0; k < ns; ++k) {                          // w_s . ps
             const float w = wsb[k];                             // (workgroup-uniform: the quads stay whole)
             if (w == 0.f) continue;
-            acc_s += w * (phr_exp<EXP2>(score(ksb, k, qs) - ms) * is);
+            acc_s += w * (prob_exp<EXP2>(quad_score<T, DPL>(ksb, k, qs) - ms) * is);
         }
         for (int j = 0; j < nt; ++j) {                          // w_t . P
             const float w = wtb[j];
             if (w == 0.f) continue;
-            float pj = phr_exp<EXP2>(score(ktb, j, qt) - mt) * it;
+            float pj = prob_exp<EXP2>(quad_score<T, DPL>(ktb, j, qt) - mt) * it;
             if (ctl) {
-                const PhrKey k = phr_key(p, b, j, ns);
+                const PairKey k = pair_key(p.ctl, p.Lt, b, j, ns);
                 float ps = 0.f;
-                if (k.has) ps = phr_exp<EXP2>(score(ksb, k.row, qs) - ms) * is;
-                pj = phr_mix(k, pj, ps);
+                if (k.has) ps = prob_exp<EXP2>(quad_score<T, DPL>(ksb, k.row, qs) - ms) * is;
+                pj = pair_mix(k, pj, ps);
             }
             acc_t += w * pj;
         }
@@ -264,23 +182,14 @@ __global__ __launch_bounds__(256) void attention_phrase_valu_kernel(const T* __r
     if (part == 0 && qi < Nq) phr_store(p, b, qi, acc_s, acc_t);
 }
 
-template <typename T, int DPL>
-void launch_phrase_valu(const void* Qs, const void* Ks, const void* Qt, const void* Kt, const PhrParams& p, int B, int use_exp2,
-                        hipStream_t s) {
-    auto k = use_exp2 ? attention_phrase_valu_kernel<T, DPL, true> : attention_phrase_valu_kernel<T, DPL, false>;
-    hipLaunchKernelGGL(k, dim3((p.Nq + 63) / 64, B), dim3(256), 0, s, (const T*)Qs, (const T*)Ks, (const T*)Qt, (const T*)Kt, p);
-}
-
 template <typename T>
 int phrase_valu(int dh, const void* Qs, const void* Ks, const void* Qt, const void* Kt, const PhrParams& p, int B, int use_exp2,
                 hipStream_t s) {
-    switch (dh / 4) {
-#define PM_DH_CASE(n) case n: launch_phrase_valu<T, n>(Qs, Ks, Qt, Kt, p, B, use_exp2, s); break;
-        PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
-#undef PM_DH_CASE
-        default: PM_REQUIRE(false, "attention_phrase_score: dim_head=%d not served", dh);
-    }
-    return PMHIP_OK;
+    return pm_dh_dispatch("attention_phrase_score", dh, [&](auto dpl) {
+        constexpr int DPL = decltype(dpl)::value;
+        auto k = use_exp2 ? attention_phrase_valu_kernel<T, DPL, true> : attention_phrase_valu_kernel<T, DPL, false>;
+        hipLaunchKernelGGL(k, dim3((p.Nq + 63) / 64, B), dim3(256), 0, s, (const T*)Qs, (const T*)Ks, (const T*)Qt, (const T*)Kt, p);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------------------- region and blend
@@ -341,26 +250,22 @@ extern "C" int pmhip_attention_phrase_score(int dtype, const void* Qs, const voi
                                             const int32_t* row_map, const float* blend, const float* gain, const int32_t* lens_s,
                                             const int32_t* lens_t, const float* w_s, const float* w_t, float* score_s, float* score_t,
                                             float scale, int accumulate, pmhip_stream stream) {
-    PM_REQUIRE(dtype == PMHIP_F32 || dtype == PMHIP_BF16, "attention_phrase_score: bad dtype %d", dtype);
+    PM_TRY(pm_probs_check("attention_phrase_score", dtype, dim_head, heads, {{"Ls", Ls, Ls_pad}, {"Lt", Lt, Lt_pad}}));
     PM_REQUIRE(Qs && Ks && Qt && Kt, "attention_phrase_score: null pointer");
     PM_REQUIRE(w_s && w_t && score_s && score_t, "attention_phrase_score: w_s / w_t / score_s / score_t is NULL");
     PM_REQUIRE((row_map != nullptr) == (blend != nullptr) && (blend != nullptr) == (gain != nullptr),
                "attention_phrase_score: row_map, blend and gain come together (all NULL: no control)");
     PM_REQUIRE(B > 0 && heads > 0 && Nq > 0 && Ls > 0 && Lt > 0, "attention_phrase_score: empty problem");
-    PM_REQUIRE(dim_head >= 16 && dim_head <= 128 && dim_head % 16 == 0, "attention_phrase_score: dim_head=%d must be a multiple of 16 in [16,128]", dim_head);
-    PM_REQUIRE(heads <= 64, "attention_phrase_score: heads=%d exceeds 64", heads);
-    PM_REQUIRE(Ls_pad >= Ls, "attention_phrase_score: Ls_pad=%d must be >= Ls=%d", Ls_pad, Ls);
-    PM_REQUIRE(Lt_pad >= Lt, "attention_phrase_score: Lt_pad=%d must be >= Lt=%d", Lt_pad, Lt);
     PM_REQUIRE((long long)B * heads <= 65535, "attention_phrase_score: B*heads=%lld exceeds the range of pmhip_attention_control", (long long)B * heads);
     PM_REQUIRE(std::isfinite(scale), "attention_phrase_score: scale must be finite");
     hipStream_t s = (hipStream_t)stream;
     PhrParams p{};
     p.score_s = score_s; p.score_t = score_t; p.heads = heads; p.Nq = Nq; p.Ls = Ls; p.Lsp = Ls_pad; p.Lt = Lt; p.Ltp = Lt_pad;
-    p.row_map = row_map; p.blend = blend; p.gain = gain; p.lens_s = lens_s; p.lens_t = lens_t; p.w_s = w_s; p.w_t = w_t;
+    p.ctl = {row_map, blend, gain}; p.lens_s = lens_s; p.lens_t = lens_t; p.w_s = w_s; p.w_t = w_t;
     p.factor = scale * (1.0f / (float)heads); p.accumulate = accumulate != 0;
     const bool mfma = dtype == PMHIP_BF16 && dim_head == 64;
     if (mfma)
-        PM_REQUIRE(((uintptr_t)Qs | (uintptr_t)Ks | (uintptr_t)Qt | (uintptr_t)Kt) % 16 == 0, "attention_phrase_score: Q and K must be 16-byte aligned");
+        PM_REQUIRE(pm_aligned(16, {Qs, Ks, Qt, Kt}), "attention_phrase_score: Q and K must be 16-byte aligned");
     PmTimer tm(FAM_ATTENTION, s);
     if (mfma) {
         auto k = use_exp2 ? attention_phrase_mfma_kernel<true> : attention_phrase_mfma_kernel<false>;

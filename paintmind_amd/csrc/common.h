@@ -5,7 +5,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
+#include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pmhip.h"
@@ -318,6 +320,12 @@ __device__ __forceinline__ float group4_sum(float v) {
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
     return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
+// sum over the 4 lanes of a quad {4 i .. 4 i + 3}: two DPP steps
+__device__ __forceinline__ float quad_sum(float v) {
+    v += dpp_mov<0xB1>(v);      // quad_perm [1,0,3,2]
+    v += dpp_mov<0x4E>(v);      // quad_perm [2,3,0,1]
+    return v;
+}
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm fold: per-row (rstd, -rstd * mean) from the partial statistics a hi/lo producer left behind (per 64-column part:
@@ -432,6 +440,28 @@ int pm_attn_check(const char* who, const PmAttnArgs& a);
 int attention_any(const char* who, int dtype, int dim_head, const PmAttnArgs& a);
 void pm_attention_f32(const PmAttnArgs& a);      // attention.hip: fp32, dim_head = 64
 void pm_attention_bf16(const PmAttnArgs& a);     // attention_bf16.hip: bf16, dim_head = 64
+// The vector-ALU attention kernels are templates over DPL = dim_head / 4, the dims a lane owns: THE list of the values served.
+// f(std::integral_constant<int, DPL>) launches the caller's instantiation; any other dim_head is refused under the entry's name.
+template <typename F>
+int pm_dh_dispatch(const char* who, int dh, F&& f) {
+    switch (dh / 4) {
+#define PM_DH_CASE(n) case n: f(std::integral_constant<int, n>{}); break;
+        PM_DH_CASE(4) PM_DH_CASE(8) PM_DH_CASE(12) PM_DH_CASE(16) PM_DH_CASE(20) PM_DH_CASE(24) PM_DH_CASE(28) PM_DH_CASE(32)
+#undef PM_DH_CASE
+        default: PM_REQUIRE(false, "%s: dim_head=%d not served", who, dh);
+    }
+    return PMHIP_OK;
+}
+// What the entries that recompute probabilities (attention_maps.hip, attention_control.hip, attention_phrase.hip) ask of every call:
+// a dtype, dim_head a multiple of 16 in [16, 128], heads <= 64, and every context's padded length at least its length.
+struct PmContext { const char* name; int len, pad; };
+int pm_probs_check(const char* who, int dtype, int dim_head, int heads, std::initializer_list<PmContext> contexts);
+// every pointer a multiple of `bytes` (the 16-byte fragment loads of the MFMA routes)
+inline bool pm_aligned(size_t bytes, std::initializer_list<const void*> ptrs) {
+    uintptr_t all = 0;
+    for (const void* p : ptrs) all |= (uintptr_t)p;
+    return all % bytes == 0;
+}
 
 // Can a LayerNorm over K columns be folded into the GEMM out[M,N] = A[M,K] (row stride lda) . W[N,K]^T (row stride ldw)?  THE
 // predicate: the engine's decision (M = one image's rows: folded or not must not depend on the batch), the GEMM entry points'

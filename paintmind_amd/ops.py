@@ -688,6 +688,33 @@ def attention_maps(q, k, n_kv, use_exp2=False, kv_lens=None, key_segments=None, 
     return out
 
 
+def _pair_operands(qs, ks, qt, kt, vt, n_src, n_tgt, row_map, blend, gain, lens_src, lens_tgt, required):
+    """The operands of a prompt-to-prompt pair, checked once for ``attention_control`` and ``attention_phrase_score``: qs like qt
+    [B,H,Nq,dh], ks [B,H,Lsp,dh], kt [B,H,Ltp,dh] (and vt [B,H,dh,Ltp] unless None) of qt's dtype, n_src / n_tgt within the pads, the
+    control arrays row_map int32, blend and gain float32 [B, n_tgt] -- all three (`required`) or all three or none --, and the
+    lengths int32 [B] or None.  -> B, H, Nq, dh, Lsp, Ltp"""
+    B, H, Nq, dh = qt.shape
+    if tuple(qs.shape) != (B, H, Nq, dh) or qs.dtype != qt.dtype:
+        raise ValueError(f"qs must be a {qt.dtype} {(B, H, Nq, dh)} tensor like qt, got {qs.dtype} {tuple(qs.shape)}")
+    lsp, ltp = ks.shape[2], kt.shape[2]
+    for name, x, want in (("ks", ks, (B, H, lsp, dh)), ("kt", kt, (B, H, ltp, dh)), ("vt", vt, (B, H, dh, ltp))):
+        if x is not None and (x.dtype != qt.dtype or tuple(x.shape) != want):
+            raise ValueError(f"{name} must be a {qt.dtype} {want} tensor, got {x.dtype} {tuple(x.shape)}")
+    if lsp < n_src or ltp < n_tgt:
+        raise ValueError(f"n_src={n_src} / n_tgt={n_tgt} exceed the padded contexts {lsp} / {ltp}")
+    control = (("row_map", row_map, torch.int32), ("blend", blend, torch.float32), ("gain", gain, torch.float32))
+    if required or any(x is not None for _, x, _ in control):
+        if any(x is None for _, x, _ in control):
+            raise ValueError("row_map, blend and gain " + ("are required" if required else "come together (all None: no control)"))
+        for name, x, dt in control:
+            if x.dtype != dt or tuple(x.shape) != (B, n_tgt):
+                raise ValueError(f"{name} must be a {dt} tensor of shape ({B}, {n_tgt}), got {x.dtype} {tuple(x.shape)}")
+    for name, x in (("lens_src", lens_src), ("lens_tgt", lens_tgt)):
+        if x is not None and (x.dtype != torch.int32 or tuple(x.shape) != (B,)):
+            raise ValueError(f"{name} must be an int32 tensor of shape ({B},), got {x.dtype} {tuple(x.shape)}")
+    return B, H, Nq, dh, lsp, ltp
+
+
 def attention_control(qs, ks, qt, kt, vt, n_src, n_tgt, row_map, blend, gain, use_exp2=False, lens_src=None, lens_tgt=None, out=None):
     """The edited pass of a prompt-to-prompt pair (pmhip_attention_control): qs [B,H,Nq,dh], ks [B,H,Lsp,dh] the
     source pass, qt, kt [B,H,Ltp,dh], vt [B,H,dh,Ltp] the edited one -> [B*Nq, H*dh] with
@@ -699,21 +726,7 @@ def attention_control(qs, ks, qt, kt, vt, n_src, n_tgt, row_map, blend, gain, us
     the leading dimension.  -> out"""
     dev = _dev(qs, ks, qt, kt, vt, row_map, blend, gain, lens_src, lens_tgt)      # (every one of them on the device and contiguous)
     lib = _lib.load()
-    B, H, Nq, dh = qt.shape
-    if tuple(qs.shape) != (B, H, Nq, dh) or qs.dtype != qt.dtype:
-        raise ValueError(f"qs must be a {qt.dtype} {(B, H, Nq, dh)} tensor like qt, got {qs.dtype} {tuple(qs.shape)}")
-    lsp, ltp = ks.shape[2], kt.shape[2]
-    for name, x, want in (("ks", ks, (B, H, lsp, dh)), ("kt", kt, (B, H, ltp, dh)), ("vt", vt, (B, H, dh, ltp))):
-        if x.dtype != qt.dtype or tuple(x.shape) != want:
-            raise ValueError(f"{name} must be a {qt.dtype} {want} tensor, got {x.dtype} {tuple(x.shape)}")
-    if lsp < n_src or ltp < n_tgt:
-        raise ValueError(f"n_src={n_src} / n_tgt={n_tgt} exceed the padded contexts {lsp} / {ltp}")
-    for name, x, dt in (("row_map", row_map, torch.int32), ("blend", blend, torch.float32), ("gain", gain, torch.float32)):
-        if x is None or x.dtype != dt or tuple(x.shape) != (B, n_tgt):
-            raise ValueError(f"{name} must be a {dt} tensor of shape ({B}, {n_tgt})")
-    for name, x in (("lens_src", lens_src), ("lens_tgt", lens_tgt)):
-        if x is not None and (x.dtype != torch.int32 or tuple(x.shape) != (B,)):
-            raise ValueError(f"{name} must be an int32 tensor of shape ({B},), got {x.dtype} {tuple(x.shape)}")
+    B, H, Nq, dh, lsp, ltp = _pair_operands(qs, ks, qt, kt, vt, n_src, n_tgt, row_map, blend, gain, lens_src, lens_tgt, required=True)
     if out is None:
         out = torch.empty(B * Nq, H * dh, device=dev, dtype=qt.dtype)
     if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == dev and out.dtype == qt.dtype and
@@ -737,26 +750,10 @@ def attention_phrase_score(qs, ks, qt, kt, n_src, n_tgt, w_src, w_tgt, row_map=N
     (score_src, score_tgt), contiguous f32 [B, Nq] on the operands' device.  -> out"""
     dev = _dev(qs, ks, qt, kt, w_src, w_tgt, row_map, blend, gain, lens_src, lens_tgt)
     lib = _lib.load()
-    B, H, Nq, dh = qt.shape
-    if tuple(qs.shape) != (B, H, Nq, dh) or qs.dtype != qt.dtype:
-        raise ValueError(f"qs must be a {qt.dtype} {(B, H, Nq, dh)} tensor like qt, got {qs.dtype} {tuple(qs.shape)}")
-    lsp, ltp = ks.shape[2], kt.shape[2]
-    for name, x, want in (("ks", ks, (B, H, lsp, dh)), ("kt", kt, (B, H, ltp, dh))):
-        if x.dtype != qt.dtype or tuple(x.shape) != want:
-            raise ValueError(f"{name} must be a {qt.dtype} {want} tensor, got {x.dtype} {tuple(x.shape)}")
-    if lsp < n_src or ltp < n_tgt:
-        raise ValueError(f"n_src={n_src} / n_tgt={n_tgt} exceed the padded contexts {lsp} / {ltp}")
-    if len({row_map is None, blend is None, gain is None}) != 1:
-        raise ValueError("row_map, blend and gain come together (all None: no control)")
-    for name, x, dt, n in (("row_map", row_map, torch.int32, n_tgt), ("blend", blend, torch.float32, n_tgt), ("gain", gain, torch.float32, n_tgt),
-                           ("w_src", w_src, torch.float32, n_src), ("w_tgt", w_tgt, torch.float32, n_tgt)):
-        if name.startswith("w_") and x is None:
-            raise ValueError(f"{name} must be a {dt} tensor of shape ({B}, {n})")
-        if x is not None and (x.dtype != dt or tuple(x.shape) != (B, n)):
-            raise ValueError(f"{name} must be a {dt} tensor of shape ({B}, {n}), got {x.dtype} {tuple(x.shape)}")
-    for name, x in (("lens_src", lens_src), ("lens_tgt", lens_tgt)):
-        if x is not None and (x.dtype != torch.int32 or tuple(x.shape) != (B,)):
-            raise ValueError(f"{name} must be an int32 tensor of shape ({B},), got {x.dtype} {tuple(x.shape)}")
+    B, H, Nq, dh, lsp, ltp = _pair_operands(qs, ks, qt, kt, None, n_src, n_tgt, row_map, blend, gain, lens_src, lens_tgt, required=False)
+    for name, x, n in (("w_src", w_src, n_src), ("w_tgt", w_tgt, n_tgt)):
+        if x is None or x.dtype != torch.float32 or tuple(x.shape) != (B, n):
+            raise ValueError(f"{name} must be a float32 tensor of shape ({B}, {n})")
     if out is None:
         if accumulate:
             raise ValueError("accumulate adds to `out`: pass the pair of tensors to add to")

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
-"""Per-symbol ISA comparison of the three attention files between two trees.
+"""Per-symbol ISA comparison of attention kernel files between two trees.
 
     hipcc -S --cuda-device-only -O3 --offload-arch=gfx950 <file>.hip -o <dir>/<file>.s      in both trees, then
-    tools/attention_isa_compare.py <parent dir> <this dir> [--twin-suffix _seg_kernel] [--twin-of-suffix _kernel]
+    tools/attention_isa_compare.py <parent dir> <this dir> [--files a,b,...] [--twin-suffix _seg_kernel] [--twin-of-suffix _kernel]
+
+--files names the files to compare, without .hip (default: the three flash files attention, attention_bf16, attention_dh).
 
 Per kernel symbol: the instruction lines with comments stripped and block labels renumbered, plus next_free_vgpr, next_free_sgpr,
 accum_offset, LDS and scratch sizes of the kernel descriptor.  Symbols of the second tree that the first does not have are listed
@@ -55,8 +57,9 @@ def main():
     a_dir, b_dir = sys.argv[1], sys.argv[2]
     suffix = sys.argv[sys.argv.index("--twin-suffix") + 1] if "--twin-suffix" in sys.argv else "_seg_kernel"
     twin_suffix = sys.argv[sys.argv.index("--twin-of-suffix") + 1] if "--twin-of-suffix" in sys.argv else "_kernel"
+    files = sys.argv[sys.argv.index("--files") + 1].split(",") if "--files" in sys.argv else FILES
     bad = same = 0
-    for f in FILES:
+    for f in files:
         a, b = kernels(f"{a_dir}/{f}.s"), kernels(f"{b_dir}/{f}.s")
         pretty = demangle(sorted(set(a) | set(b)))
         print(f"== {f}.hip: {len(a)} symbols before, {len(b)} after")
