@@ -27,7 +27,7 @@
  *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
  *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens / _control
  *         ldm >= Nkv                  pmhip_attention_maps
- *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus, pmhip_masked_ce
+ *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus / _forced, pmhip_masked_ce
  *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
  *     N * ldw stay below 2^30 elements; beyond that another kernel may serve the call).
  *   - an output of [M, N] is written in exactly its M x N elements, however ragged M and N are against a kernel's tile; arrays
@@ -525,6 +525,21 @@ int pmhip_sample_rows(const float* logits, int ldl, const int64_t* ids_in, int64
 int pmhip_sample_rows_nucleus(const float* logits, int ldl, const int64_t* ids_in, int64_t mask_id, int topk, float top_p,
                               float temperature, const float* noise, uint64_t seed, uint32_t step, uint64_t row_base,
                               int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream);
+
+/* The FORCED step (a new entry within ABI 11): nothing is drawn.  target int64 [M] (device) gives every
+ * row its id, and the row is scored as a draw scores the id it produced:
+ *   pred_out[r] = target[r];  ids_out[r] = ids_in[r] == mask_id ? target[r] : ids_in[r];
+ *   score_out[r] = 1 - softmax(logits[r])[target[r]] where the position took the target, -1e5 where its id was given.
+ * One wave per row, one read of the row, the normaliser of pmhip_sample_rows' row kernel expression for expression: for a row
+ * whose target is the id a draw produced, the triple is bit-identical to that draw's wherever the draw ran on the row kernel
+ * (8 < topk <= 64, or V % 64 != 0), the selection kernel (topk > 64) or the nucleus kernel (top_p < 1).  The block-statistics
+ * kernel (topk <= 8, V % 64 == 0) rounds its confidence differently: there the scores agree to the last bits, not in them.
+ * A target outside [0, V) -- the mask id included -- is never used as an index (the range test sits in front of the load): the
+ * row is stored as an undrawn row, pred_out = ids_out = ids_in, score_out = -1e5.  The targets are device memory and are not
+ * read on the host.  pred_out and score_out may be NULL; ids_out may alias ids_in; logits, ids_in (unless aliased) and target
+ * are read only.  M > 0, 0 < V <= 16384, V % 4 == 0, ldl % 4 == 0, ldl >= V, else PMHIP_EINVAL naming the argument. */
+int pmhip_sample_rows_forced(const float* logits, int ldl, const int64_t* ids_in, const int64_t* target, int64_t mask_id,
+                             int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream);
 
 /* The same step for a caller that holds the SOFTMAX STATISTICS of the rows' 64-column blocks (round 5): block_stats [M][V/64][2] =
  * (max, sum_j 2^((x_j - max) log2 e)) per block, as pmhip_gemm_softmax_stats / pmhip_guidance_combine_stats leave them behind.

@@ -415,6 +415,49 @@ __global__ __launch_bounds__(THREADS) void sample_nucleus_kernel(
 #include "sample_select_draw.h"
 }
 
+// ---- the forced form (pmhip_sample_rows_forced): nothing is drawn -- the row's "prediction" is a GIVEN id,
+// target[row], and the kernel scores it as the draw would have scored it.  Same wave, same resident row, same normaliser as
+// sample_rows_kernel -- expression for expression, so for a target that a draw of the row, wide or nucleus kernel produced, the
+// stored triple has that draw's bits.  Behind the normaliser: one load of the target's logit, by the lane that stores, and
+// store_outcome with expf(v - mx) / se.  No top-k, no noise, no step values: no slots / params / period form.
+// A target outside [0, V) is never used as an index: the range test sits in front of the load, and the row is stored as an undrawn
+// row is (pred = merged = ids_in, score = -1e5).  The targets are device memory: the host cannot check them without a sync.
+template <int NV4>
+__global__ __launch_bounds__(THREADS) void sample_forced_kernel(
+    const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, const int64_t* __restrict__ target, int64_t mask_id,
+    int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+    if (row >= M) return;                                  // whole wave exits together
+    const float* lrow = logits + (size_t)row * ldl;
+
+    float4 x[NV4];
+#pragma unroll
+    for (int g = 0; g < NV4; ++g) {
+        const int col = (g * 64 + lane) * 4;
+        x[g] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        if (col < V) x[g] = *reinterpret_cast<const float4*>(lrow + col);
+    }
+    // ---- softmax normaliser of the UNfiltered row: sample_rows_kernel's expressions, in its order
+    float mx = -INFINITY;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g) mx = fmaxf(mx, fmaxf(fmaxf(x[g].x, x[g].y), fmaxf(x[g].z, x[g].w)));
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g)
+        se += (__expf(x[g].x - mx) + __expf(x[g].y - mx)) + (__expf(x[g].z - mx) + __expf(x[g].w - mx));
+    se = wave_sum(se);
+
+    if (lane == 0) {
+        const int64_t t = target[row];
+        const bool ok = t >= 0 && t < (int64_t)V;          // in front of the load: an id from outside indexes nothing
+        float v = -INFINITY;
+        if (ok) v = lrow[t];
+        store_outcome(row, ok, t, expf(v - mx) / se, ids_in, mask_id, pred_out, ids_out, score_out);
+    }
+}
+
 
 // ---- the step from block statistics -----------------------------------------------------------------------------------------
 // (KT_MAX = 8, the top-k this kernel serves, and K_LANES sit beside pm_sample_class in common.h)
@@ -820,6 +863,28 @@ extern "C" int pmhip_sample_rows_slots_filter(const float* logits, int ldl, cons
                                               int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream) {
     return pm_sample_rows(logits, ldl, block_stats, 0, ids_in, mask_id, nullptr, pred_out, ids_out, score_out, M, V,
                           PmStepSource::per_image(slots, tokens).with_filters(top_p_dev), stream);
+}
+
+// the forced step: target[row] in place of a draw, scored by the unfiltered softmax as a draw scores its id
+extern "C" int pmhip_sample_rows_forced(const float* logits, int ldl, const int64_t* ids_in, const int64_t* target, int64_t mask_id,
+                                        int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream) {
+    const char* who = "sample_rows_forced";
+    PM_REQUIRE(logits, "%s: logits is NULL", who);
+    PM_REQUIRE(ids_in, "%s: ids_in is NULL", who);
+    PM_REQUIRE(target, "%s: target is NULL", who);
+    PM_REQUIRE(ids_out, "%s: ids_out is NULL", who);
+    PM_REQUIRE(M > 0, "%s: M=%d must be positive", who, M);
+    PM_REQUIRE(V > 0 && V <= 16384 && V % 4 == 0, "%s: V=%d must be a positive multiple of 4, at most 16384", who, V);
+    PM_REQUIRE(ldl % 4 == 0 && ldl >= V, "%s: ldl=%d must be a multiple of 4, at least V=%d", who, ldl, V);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid(ceil_div(M, THREADS / 64)), block(THREADS);
+    PmTimer tm(FAM_SAMPLE, s);
+    pick<1, 4, 32, 64>(V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64, [&](auto NV4) {
+        hipLaunchKernelGGL((sample_forced_kernel<NV4()>), grid, block, 0, s, logits, ldl, ids_in, target, mask_id, pred_out, ids_out, score_out,
+                           M, V);
+    });
+    PM_HIP(hipGetLastError());
+    return PMHIP_OK;
 }
 
 int pm_check_top_p(const char* who, float p) {

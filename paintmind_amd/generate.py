@@ -630,6 +630,78 @@ class Pipeline(nn.Module):
         scores = 1 - logits.softmax(dim=-1).gather(2, pred[..., None])[..., 0]
         return pred, merged, scores.masked_fill(~is_mask, -1e5), g
 
+    def _forced_cpu(self, ids, logits, target, noise, seed):
+        """``ops.sample_rows_forced`` in plain torch: what ``_draw_cpu`` returns, with pred = target and score =
+        1 - softmax(logits)[target] (-1e5 at given ids).  It builds the generator ``_draw_cpu`` builds and, with noise None, draws and
+        DISCARDS the token draw's uniforms: the choice-temperature noise drawn behind them (``_remask_cpu``) is then the noise the
+        other half of a pair sees."""
+        g = None if seed is None else torch.Generator().manual_seed(int(seed) & (2 ** 63 - 1))
+        if noise is None:
+            torch.rand(logits.shape, generator=g)
+        pred = target.to(ids.device, torch.long)
+        is_mask = ids == self.mask_token_id
+        merged = torch.where(is_mask, pred, ids)
+        scores = 1 - logits.softmax(dim=-1).gather(2, pred[..., None])[..., 0]
+        return pred, merged, scores.masked_fill(~is_mask, -1e5), g
+
+    def _source_ids(self, source_ids, B, who):
+        """the tokens of a real image, checked on the host once: int64 [B, N], every value a code of the codebook (no mask id)"""
+        if not isinstance(source_ids, torch.Tensor) or source_ids.dtype != torch.int64 or tuple(source_ids.shape) != (B, self.num_tokens):
+            got = f"{source_ids.dtype} {tuple(source_ids.shape)}" if isinstance(source_ids, torch.Tensor) else type(source_ids).__name__
+            raise ValueError(f"{who}: source ids must be an int64 tensor [{B}, {self.num_tokens}], got {got}")
+        bad = ((source_ids < 0) | (source_ids >= self.mask_token_id)).nonzero()
+        if len(bad):
+            b, i = bad[0].tolist()
+            raise ValueError(f"{who}: source ids: image {b}, token {i}: {int(source_ids[b, i])} is no code in [0, {self.mask_token_id})")
+        return source_ids
+
+    @torch.no_grad()
+    def forced_ids(self, target_ids, context, B, timesteps, seed, image_base=0, choice_temperature=None, guidance_scale=None,
+                   context_lens=None, return_steps=False):
+        """The teacher-forced loop of ONE image batch: the eager MaskGIT loop from the all-mask state in which
+        every step's token draw is replaced by the KNOWN token, target_ids int64 [B, N] (``vqgan.encode``'s ids of a real image; every
+        value in [0, n_embed), else ValueError naming the first offender -- checked on the host, once).  Every step runs the tower on
+        the partially revealed image (a scalar guidance_scale adds the pass without a context), scores each revealed token by the
+        model's own confidence in it -- 1 - softmax(logits)[target] -- and re-masks by the usual schedule (``loop_schedule``; the
+        choice temperature's noise under `seed`, `image_base` as in ``generate_ids``): the image is revealed in the order the model
+        finds it plausible.  Nothing is drawn, so there is no temperature, top-k or top_p.
+        -> ids [B, N]: target_ids except at the nmask[T-1] positions per image still masked.  return_steps: (ids, revealed_at), int64
+        [B, N], the first step after which the position is unmasked (T: still masked at the end)."""
+        T, N = int(timesteps), self.num_tokens
+        cpu = self._on_cpu()
+        dev = self.mask_token.device if cpu else self.engine().device
+        target = self._source_ids(target_ids, B, "forced_ids").to(dev).contiguous()
+        if guidance_scale is not None and np.ndim(guidance_scale) > 0:
+            raise ValueError("forced_ids: guidance_scale is one number (a schedule is not served)")
+        opts = self._options(1, None, guidance_scale, context_lens, choice_temperature, context, B)
+        keys = self._keys(context, B, opts)
+        _, nmask, ctemps = loop_schedule(T, 1.0, N, opts.choice_temperature)
+        if context is not None:
+            context = context.to(dev)
+        ids = torch.full((B, N), self.mask_token_id, dtype=torch.long, device=dev)
+        revealed_at = torch.full((B, N), T, dtype=torch.long, device=dev)
+        for step in range(T):
+            tok = self.ids2tokens(ids)
+            ct = ctemps[step] if ctemps else 0.0
+            if cpu:
+                logits = self._logits(tok, context, keys)
+                if opts.guidance_scale is not None:
+                    uncond = self._logits(tok, None)
+                    logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(opts.guidance_scale)))
+                _, merged, score, g = self._forced_cpu(ids, logits, target, None, None if seed is None else seed + step)
+                ids = self._remask_cpu(merged, score, nmask[step], g, ct, None, [nmask[step]] * B)
+            else:
+                eng = self.engine()
+                logits = eng.forward(tok, context, keys=keys)
+                if opts.guidance_scale is not None:
+                    logits = ops.guidance_combine(logits, eng.forward(tok, None), opts.guidance_scale, out=logits)
+                _, merged, score = ops.sample_rows_forced(logits.reshape(B * N, -1), ids.reshape(-1), target.reshape(-1), self.mask_token_id)
+                ids = ops.remask(merged.reshape(B, N), score.reshape(B, N), nmask[step], self.mask_token_id, choice_temperature=ct, seed=seed,
+                                 step=step, row_base=image_base * N)
+            if return_steps:
+                revealed_at = torch.where((ids != self.mask_token_id) & (revealed_at == T), torch.full_like(revealed_at, step), revealed_at)
+        return (ids, revealed_at) if return_steps else ids
+
     def _remask_cpu(self, ids, scores, nm, g, choice_t=0.0, choice_noise=None, counts=None):
         """the second half of ``_tail_cpu``: the re-masking of the merged ids under their scores -> ids"""
         if choice_t:
@@ -848,7 +920,7 @@ class Pipeline(nn.Module):
     def control_ids(self, context_src, context_edit, lens_src, lens_edit, row_map, blend, gain, B, timesteps, temperature, topk, seed,
                     image_base=0, top_p=None, choice_temperature=None, guidance_scale=None, cross_steps=0.8, self_steps=0.0, layers=None,
                     want_imgs=False, noise=None, blend_rows=None, blend_mask=None, blend_threshold=0.3, blend_grow=1, blend_start=0.2,
-                    return_mask=False):
+                    return_mask=False, source_ids=None):
         """Prompt-to-prompt (Hertz et al.): the eager decode loop over B PAIRS of images -- one from
         context_src [B, L, D], one from context_edit [B, L, D], both from the all-mask state under the same seed -- in which the
         edited image's cross-attention takes the source image's probabilities for the context rows row_map pairs.
@@ -884,7 +956,15 @@ class Pipeline(nn.Module):
           - at every blended step, before re-masking, the edited half's (pred, merged, score) equal the source half's at every token
             outside the region, bit for bit
           - blend_mask all true gives the ids of the call without a blend, bit for bit; all false makes ids_edit == ids_src
-          - the final IMAGE is not promised to be pixel-equal outside the region: the decoder mixes tokens."""
+          - the final IMAGE is not promised to be pixel-equal outside the region: the decoder mixes tokens.
+
+        A REAL IMAGE AS THE SOURCE (source_ids None: the call above, launch for launch): source_ids int64
+        [B, N], the image's tokens (every value in [0, n_embed), checked on the host, once).  The source half's token draw at every step
+        is then the forced step on them -- ``ops.sample_rows_forced`` on the half's rows of the logits, ``_forced_cpu`` on the CPU --
+        and everything else is the loop as it stands: ids_src is ``forced_ids(source_ids, context_src, ...)`` bit for bit, whatever the
+        edited half does, and with want_imgs the source image is decoded from source_ids at all positions.  The pair then no longer
+        shares its TOKEN draw -- the edited half still draws under its noise; only the attention control and the blend tie the halves
+        together (the re-masking noise stays shared)."""
         if context_src is None or context_edit is None or tuple(context_src.shape) != tuple(context_edit.shape) or context_src.dim() != 3 \
                 or context_src.shape[0] != B:
             raise ValueError(f"control_ids: context_src and context_edit must be two context tensors [{B}, L, D] of one shape")
@@ -938,6 +1018,8 @@ class Pipeline(nn.Module):
         imgs = [None, None]
         if noise is not None and tuple(noise.shape) != (T, B, N, self.mask_token_id):
             raise ValueError(f"control_ids: noise must be a tensor [{T}, {B}, {N}, {self.mask_token_id}], got {tuple(noise.shape)}")
+        if source_ids is not None:
+            source_ids = self._source_ids(source_ids, B, "control_ids").to(dev).contiguous()
         for step in range(T):
             last = want_imgs and step == T - 1
             cross = layers if step < n_cross else []
@@ -958,7 +1040,10 @@ class Pipeline(nn.Module):
                     uncond = self._logits(tok, None)
                     logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(opts.guidance_scale)))
                 draws = [self._draw_cpu(ids[h * B:(h + 1) * B], logits[h * B:(h + 1) * B], opts.topk, temps[step],
-                                        None if noise is None else noise[step], None if seed is None else seed + step, opts.top_p) for h in range(2)]
+                                        None if noise is None else noise[step], None if seed is None else seed + step, opts.top_p)
+                         if h or source_ids is None else
+                         self._forced_cpu(ids[:B], logits[:B], source_ids, None if noise is None else noise[step], None if seed is None else seed + step)
+                         for h in range(2)]
                 if blend_now:
                     if blend_rows is not None:
                         region = self._region_cpu(scores[:B], scores[B:], g, blend_threshold, blend_grow)
@@ -979,6 +1064,10 @@ class Pipeline(nn.Module):
             draws = []
             for h in range(2):
                 rows = slice(h * B * N, (h + 1) * B * N)
+                if h == 0 and source_ids is not None:
+                    draws.append(ops.sample_rows_forced(logits.reshape(2 * B * N, -1)[rows], ids.reshape(-1)[rows], source_ids.reshape(-1),
+                                                        self.mask_token_id))
+                    continue
                 draws.append(ops.sample_rows(logits.reshape(2 * B * N, -1)[rows], ids.reshape(-1)[rows], self.mask_token_id, opts.topk,
                                              temps[step], seed=seed, step=step, row_base=image_base * N, top_p=opts.top_p,
                                              noise=None if noise is None else noise[step].to(dev, torch.float32).reshape(B * N, -1).contiguous()))
@@ -998,7 +1087,7 @@ class Pipeline(nn.Module):
     def prompt_to_prompt(self, text, edit_text, mode="refine", reweight=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_base=0,
                          top_p=None, choice_temperature=None, guidance_scale=None, cross_steps=0.8, self_steps=0.0, layers=None,
                          return_ids=False, local_blend=None, blend_threshold=0.3, blend_grow=1, blend_start=0.2, blend_mask=None,
-                         return_mask=False, **refused):
+                         return_mask=False, img=None, source_ids=None, **refused):
         """Change the prompt, keep the picture (Hertz et al., Prompt-to-Prompt): -> (img_src, img_edit), the
         image of `text` and the image of `edit_text` from one seed, the second attending with the first's cross-attention for the
         words the prompts share; ids with return_ids.  text / edit_text: a prompt each, or two lists of as many.
@@ -1015,7 +1104,13 @@ class Pipeline(nn.Module):
         in whichever prompt of a pair has it; ("cat", "dog"): the source prompt's phrase and the edited prompt's; or a list of B such
         items.  Each phrase occurs once in its prompt; a phrase in neither prompt, or with no token below max_length, is a
         ValueError.  blend_threshold / blend_grow / blend_start: the paper's 0.3 / 1 / 0.2, not optima measured on this tower.
-        blend_mask (bool [B, g, g], instead of local_blend): the region, drawn.  return_mask appends the last region, bool [B, g, g]."""
+        blend_mask (bool [B, g, g], instead of local_blend): the region, drawn.  return_mask appends the last region, bool [B, g, g].
+
+        img ([B, C, H, W] in [-1, 1], encoded as ``edit`` encodes its image) or source_ids (int64 [B, N], its tokens; not both): a
+        REAL image as the source.  `text` is then its caption, the source half is teacher-forced on its tokens
+        (``control_ids(source_ids=)``) and img_src is the VQGAN reconstruction of the input.  With local_blend on top the edited
+        image keeps the input's tokens outside the region; blend_start=0 is the natural setting for a real image (the default stays
+        the paper's).  The pair no longer shares its token draw: only the attention and the blend tie the halves together."""
         if refused:
             raise ValueError(f"prompt_to_prompt does not serve {sorted(refused)} (negative prompts, regions, prompt weights and the segment "
                              f"arrays stand beside no attention control)")
@@ -1063,6 +1158,19 @@ class Pipeline(nn.Module):
             return frags + [prompt[at:]], gains + [None], looks + [False]
 
         B = len(src)
+        if img is not None and source_ids is not None:
+            raise ValueError("prompt_to_prompt: img and source_ids exclude each other (the image, or its tokens)")
+        if img is not None:
+            if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[0] != B:
+                raise ValueError(f"prompt_to_prompt: img must be [{B}, C, H, W] (one image per prompt), got "
+                                 f"{tuple(img.shape) if isinstance(img, torch.Tensor) else type(img).__name__}")
+            if img.shape[2] != self.image_size or img.shape[3] != self.image_size:
+                raise ValueError(f"prompt_to_prompt: img must be {self.image_size} x {self.image_size}, got {img.shape[2]} x {img.shape[3]}")
+            source_ids = self.to_latent(img)[1].reshape(B, self.num_tokens).to(torch.long)
+        elif source_ids is not None:
+            if not isinstance(source_ids, torch.Tensor) or source_ids.dim() != 2 or source_ids.shape[0] != B:
+                raise ValueError(f"prompt_to_prompt: source_ids must be int64 [{B}, {self.num_tokens}] (one image per prompt), got "
+                                 f"{tuple(source_ids.shape) if isinstance(source_ids, torch.Tensor) else type(source_ids).__name__}")
         looks = [(None, None)] * B
         if local_blend is not None:
             if blend_mask is not None:
@@ -1119,7 +1227,7 @@ class Pipeline(nn.Module):
         context = context.to(self.mask_token.device, torch.float32)
         out = self.control_ids(context[:B], context[B:], lens[:B], lens[B:], rm, bl, gn, B, timesteps, temperature, topk,
                                _draw_seed() if seed is None else seed, image_base, top_p, choice_temperature, guidance_scale, cross_steps,
-                               self_steps, layers, want_imgs=not return_ids, **blend)
+                               self_steps, layers, want_imgs=not return_ids, **blend, **({} if source_ids is None else dict(source_ids=source_ids)))
         return out if return_ids else out[2:]
 
     def join_lanes(self, parts):

@@ -1027,6 +1027,31 @@ def sample_rows(logits, ids, mask_id, topk, temperature, noise=None, seed=0, ste
     return pred, ids_out, score
 
 
+def sample_rows_forced(logits, ids, target, mask_id, ids_out=None):
+    """The forced step (pmhip_sample_rows_forced): logits fp32 [M,V], ids int64 [M], target int64 [M] ->
+    (pred [M], merged ids [M], score [M]) with pred = target, merged = target where ids == mask_id, score = 1 - softmax(logits)[target]
+    there and -1e5 where the id was given: what ``sample_rows`` leaves for a row whose draw came out as `target`, bit for bit where
+    that draw ran on the row, selection or nucleus kernel.  A target outside [0, V) leaves its row undrawn (pred = merged = ids,
+    score = -1e5); the kernel tests the range in front of its load.  ids_out (None: a new tensor): where the merged ids go, `ids`
+    itself for the step in place."""
+    dev = _dev(logits, ids, target, ids_out)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"sample_rows_forced: logits must be fp32 [M, V], got {logits.dtype} {tuple(logits.shape)}")
+    M, V = logits.shape
+    for name, x in (("ids", ids), ("target", target), ("ids_out", ids_out)):
+        if x is not None and (x.dtype != torch.int64 or tuple(x.shape) != (M,)):
+            raise ValueError(f"sample_rows_forced: {name} must be int64 [{M}], got {x.dtype} {tuple(x.shape)}")
+    lib = _lib.load()
+    pred = torch.empty(M, device=dev, dtype=torch.int64)
+    if ids_out is None:
+        ids_out = torch.empty(M, device=dev, dtype=torch.int64)
+    score = torch.empty(M, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        check(lib.pmhip_sample_rows_forced(_p(logits), logits.stride(0), _p(ids), _p(target), int(mask_id), _p(pred), _p(ids_out), _p(score),
+                                           M, V, stream_ptr(dev)), "pmhip_sample_rows_forced")
+    return pred, ids_out, score
+
+
 def choice_t(value, what="choice_temperature"):
     """a step's choice temperature (None = 0) -> a float, checked as the native entries check it: finite, 0 <= t <= CHOICE_T_MAX"""
     t = 0.0 if value is None else float(value)
