@@ -27,7 +27,7 @@
  *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
  *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens / _control
  *         ldm >= Nkv                  pmhip_attention_maps
- *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus / _forced, pmhip_masked_ce
+ *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus / _forced, pmhip_masked_ce, pmhip_logit_divergence
  *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
  *     N * ldw stay below 2^30 elements; beyond that another kernel may serve the call).
  *   - an output of [M, N] is written in exactly its M x N elements, however ragged M and N are against a kernel's tile; arrays
@@ -540,6 +540,24 @@ int pmhip_sample_rows_nucleus(const float* logits, int ldl, const int64_t* ids_i
  * are read only.  M > 0, 0 < V <= 16384, V % 4 == 0, ldl % 4 == 0, ldl >= V, else PMHIP_EINVAL naming the argument. */
 int pmhip_sample_rows_forced(const float* logits, int ldl, const int64_t* ids_in, const int64_t* target, int64_t mask_id,
                              int64_t* pred_out, int64_t* ids_out, float* score_out, int M, int V, pmhip_stream stream);
+
+/* The DIVERGENCE between two rows of logits (a new entry within ABI 11).  a, b fp32 [M, V], both with the
+ * row stride ldl; they may be the same pointer.  Row r is SCORED iff ids is NULL or ids[r] == mask_id (ids int64 [M]: the
+ * masked-position rule of the samplers).  With p = softmax(a[r]) and q = softmax(b[r]), each over its own row,
+ *   kind 0 (tv)        d = 1/2 sum_i |p_i - q_i|                       in [0, 1]
+ *   kind 1 (jeffreys)  d = sum_i (p_i - q_i) (log p_i - log q_i)       >= 0, = KL(p || q) + KL(q || p)
+ * any other kind is refused.  A column that is -inf in both rows contributes nothing; a column that is -inf in exactly one row
+ * makes jeffreys +inf and is an ordinary column under tv; a NaN anywhere in a scored row gives NaN for that row and no other.
+ *                    accumulate == 0                        accumulate != 0
+ *   scored row       acc[r] = d;  count[r] = 1              acc[r] += d;  count[r] += 1
+ *   unscored row     acc[r] = 0;  count[r] = 0              neither is touched
+ * acc fp32 [M], count int32 [M] or NULL.  The logits of an unscored row are never loaded: a NaN there reaches nothing and the launch
+ * costs the scored rows' bytes.  Every element of a scored row is requested once; one writer per row, a fixed order of the sums,
+ * no atomics: two launches give the same bits.  a == b row-wise gives exactly 0.0f under both kinds, and swapping a and b gives
+ * the same bits (divergence.hip states the evaluation order that yields both).  a and b are read only and 16-byte aligned.
+ * M > 0, 0 < V <= 16384, V % 4 == 0, ldl % 4 == 0, ldl >= V, else PMHIP_EINVAL naming the argument. */
+int pmhip_logit_divergence(const float* a, const float* b, int ldl, const int64_t* ids, int64_t mask_id, int kind, float* acc,
+                           int32_t* count, int accumulate, int M, int V, pmhip_stream stream);
 
 /* The same step for a caller that holds the SOFTMAX STATISTICS of the rows' 64-column blocks (round 5): block_stats [M][V/64][2] =
  * (max, sum_j 2^((x_j - max) log2 e)) per block, as pmhip_gemm_softmax_stats / pmhip_guidance_combine_stats leave them behind.

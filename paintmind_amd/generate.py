@@ -97,6 +97,30 @@ def region_token_mask(mask, image_size, patch_size):
     return ((m != 0).reshape(g, patch_size, g, patch_size).to(torch.uint8).amax(dim=(1, 3)) != 0).reshape(-1)
 
 
+def diff_draws(B, N, mask_ratio, draws, seed):
+    """the masks of ``Pipeline.diff_mask``'s draws -> bool [draws, B, N] on the CPU.  Every image gets ONE
+    permutation, rank = argsort(argsort(torch.rand(B, N, generator=torch.Generator().manual_seed(seed)))), and with
+    k = ceil(mask_ratio * N) draw j masks the positions with (rank - (j * N) // draws) mod N < k: a window of k ranks that starts
+    where draw j's share of the permutation does.  0 < mask_ratio < 1, draws >= 1 and k >= ceil(N / draws) -- consecutive windows
+    start at most ceil(N / draws) apart, so under the last condition every position is masked in at least one draw -- else ValueError.
+    The CPU generator draws them: the CPU branch and the GPU see the same masks."""
+    if isinstance(draws, bool) or not isinstance(draws, int) or draws < 1:
+        raise ValueError(f"diff_draws: draws {draws!r} must be an integer >= 1")
+    if isinstance(mask_ratio, bool) or not isinstance(mask_ratio, (int, float)) or not 0 < mask_ratio < 1:
+        raise ValueError(f"diff_draws: mask_ratio {mask_ratio!r} must satisfy 0 < mask_ratio < 1")
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError(f"diff_draws: seed {seed!r} must be an integer")
+    if B < 1 or N < 1:
+        raise ValueError(f"diff_draws: B={B} and N={N} must be positive")
+    k = math.ceil(mask_ratio * N)
+    if k < math.ceil(N / draws):
+        raise ValueError(f"diff_draws: k = ceil(mask_ratio * N) = {k} must satisfy k >= ceil(N / draws) = {math.ceil(N / draws)}: with fewer "
+                         f"some position is masked in no draw (raise mask_ratio or draws)")
+    rank = torch.argsort(torch.argsort(torch.rand(B, N, generator=torch.Generator().manual_seed(seed)), dim=1), dim=1)
+    starts = torch.tensor([(j * N) // draws for j in range(draws)], dtype=rank.dtype)
+    return (rank[None] - starts[:, None, None]) % N < k
+
+
 MAX_REGIONS = 31           # segments 1..31 beside the global prompt's segment 0: one bit each of a token's 32-bit mask
 
 
@@ -490,6 +514,121 @@ class Pipeline(nn.Module):
         for _ in range(grow):
             mask = torch.nn.functional.max_pool2d(mask[:, None].float(), 3, stride=1, padding=1)[:, 0] > 0
         return mask
+
+    @staticmethod
+    def _divergence_cpu(la, lb, kind):
+        """``ops.logit_divergence`` on every row in plain torch, float32 with log_softmax: logits [..., V] twice -> f32 [...]"""
+        lp, lq = torch.log_softmax(la.float(), dim=-1), torch.log_softmax(lb.float(), dim=-1)
+        dp = lp.exp() - lq.exp()
+        if kind == "tv":
+            return 0.5 * dp.abs().sum(-1)
+        gone_p, gone_q = lp == float("-inf"), lq == float("-inf")
+        t = torch.where(gone_p & gone_q, torch.zeros_like(dp), dp * (lp - lq))         # -inf in both: nothing; in one: +inf
+        return torch.where(gone_p != gone_q, torch.full_like(dp, float("inf")), t).sum(-1)
+
+    def _diff_context(self, text, B, mask_padding, lens, who):
+        """one side of ``diff_mask``: a list of B prompts, one prompt for every image, or a context tensor [B, L, D] -> (context, lens)"""
+        if isinstance(text, torch.Tensor):
+            if text.dim() != 3 or text.shape[0] != B:
+                raise ValueError(f"diff_mask: {who} must be a context tensor [{B}, L, D], got {tuple(text.shape)}")
+            if mask_padding:
+                raise ValueError(f"diff_mask: mask_padding takes the lengths from the text model: {who} is a tensor, pass its lengths")
+            return text, lens
+        if getattr(self, "text_model", None) is None:
+            raise ValueError("diff_mask needs a text condition (an unconditional pipeline has no prompt to disagree about)")
+        if isinstance(text, str):
+            prompts = [text] * B
+        elif isinstance(text, (list, tuple)) and all(isinstance(p, str) for p in text):
+            prompts = list(text)
+        else:
+            raise ValueError(f"diff_mask: {who} must be a prompt, a list of {B} prompts or a context tensor, got {type(text).__name__}")
+        if len(prompts) != B:
+            raise ValueError(f"diff_mask: {who} has {len(prompts)} prompts for a batch of {B}")
+        if mask_padding and lens is None:
+            return self.text_model(prompts, return_lens=True)
+        return self.text_model(prompts), lens
+
+    @torch.no_grad()
+    def diff_mask(self, img, text, edit_text, mask_ratio=0.5, draws=4, seed=0, kind="tv", threshold=0.5, grow=1, mask_padding=False,
+                  context_lens=None, edit_context_lens=None, return_score=False, **refused):
+        """An edit mask from where TWO PROMPTS DISAGREE about ``img`` (extension; DiffEdit's idea on a
+        masked-token model): no phrase, no drawn mask.  ``text`` is the image's caption, ``edit_text`` what it should become: each a
+        list of B prompts, one prompt for every image, or a context tensor [B, L, D]; the two contexts must have one shape.  With
+        ``mask_padding`` the non-pad lengths come from the text model; ``context_lens`` / ``edit_context_lens`` give them per side.
+
+        The rule, which is the contract:
+            1. ids = to_latent(img)
+            2. for draw j of ``draws``: m = diff_draws(B, N, mask_ratio, draws, seed)[j]; the ids with the mask id where m is set go
+               through ONE forward of 2 B images -- the same masked ids twice, under the contexts cat[text, edit_text] -- and every
+               masked position t of image b adds  d(softmax(logits_text[b, t]), softmax(logits_edit[b, t]))  to acc[b, t] and 1 to
+               count[b, t]; d is ``kind``: "tv" = 1/2 sum |p - q| in [0, 1], "jeffreys" = KL(p||q) + KL(q||p)
+            3. score = acc / count                  (count >= 1 everywhere: ``diff_draws`` guarantees it)
+            4. mask  = score >= threshold * max_t score[b],   0 < threshold <= 1,   dilated ``grow`` times by a 3 x 3 maximum;
+               an image whose maximum score is exactly 0 -- the two prompts are the same text -- gets an EMPTY mask
+        On the GPU step 2's divergence is one HBM-bound kernel over the two halves of the logits (``ops.logit_divergence``) and step 4
+        the region kernel of the local blend (``ops.phrase_region``); on the CPU the same rule in plain torch.  The logits of a draw
+        take 2 B * N * n_embed * 4 bytes (B = 32 on the 8192-code tower: 2 GiB); a larger batch is the caller's to split.
+
+        The defaults 0.5 / 4 / 0.5 / 1 follow DiffEdit's spirit (half the image corrupted, a few draws, half the maximum, one
+        dilation); they are not optima measured on this tower, whose image quality is unmeasured.  Not served (ValueError):
+        guidance or a negative prompt in the divergence passes, the segment arrays, prompt weights.
+
+        -> bool [B, g, g] on the pipeline's device: what ``edit(token_mask=)`` and ``prompt_to_prompt(blend_mask=)`` take; with
+        ``return_score`` (mask, score f32 [B, g, g]).  Nothing is captured: a later call of anything runs what it ran before."""
+        if refused:
+            raise ValueError(f"diff_mask does not serve {sorted(refused)} (guidance, negative prompts, the segment arrays and prompt weights "
+                             f"take no part in the divergence passes)")
+        if not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and 0 < threshold <= 1):
+            raise ValueError(f"diff_mask: threshold {threshold!r} must be in (0, 1]")
+        if not (isinstance(grow, int) and not isinstance(grow, bool) and grow >= 0):
+            raise ValueError(f"diff_mask: grow {grow!r} must be a non-negative integer")
+        if kind not in ops.DIVERGENCE_KINDS:
+            raise ValueError(f"diff_mask: kind {kind!r} is neither 'tv' nor 'jeffreys'")
+        if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[2] != self.image_size or img.shape[3] != self.image_size:
+            raise ValueError(f"diff_mask: img must be [B, C, {self.image_size}, {self.image_size}], got "
+                             f"{tuple(img.shape) if isinstance(img, torch.Tensor) else type(img).__name__}")
+        if text is None or edit_text is None:
+            raise ValueError("diff_mask needs a text condition on both sides (the caption and what it should become)")
+        B, N, V = img.shape[0], self.num_tokens, self.mask_token_id
+        g = self.image_size // self.patch_size
+        masks = diff_draws(B, N, mask_ratio, draws, seed)
+        ctx_src, lens_src = self._diff_context(text, B, mask_padding, context_lens, "text")
+        ctx_edit, lens_edit = self._diff_context(edit_text, B, mask_padding, edit_context_lens, "edit_text")
+        if ctx_src.shape != ctx_edit.shape:
+            raise ValueError(f"diff_mask: the two contexts must have one shape, got {tuple(ctx_src.shape)} and {tuple(ctx_edit.shape)}")
+        L = ctx_src.shape[1]
+        lens = None
+        if lens_src is not None or lens_edit is not None:
+            lens = (ops.host_lens([L] * B if lens_src is None else lens_src, B, L, "context_lens") +
+                    ops.host_lens([L] * B if lens_edit is None else lens_edit, B, L, "edit_context_lens"))
+        ids = self.to_latent(img)[1].reshape(B, N)
+        if self._on_cpu():
+            context = torch.cat((ctx_src, ctx_edit)).float()
+            keys = self._host_keys(context, 2 * B, lens)
+            acc, count = torch.zeros(B, N), torch.zeros(B, N)
+            for m in masks:
+                masked = torch.where(m, torch.full_like(ids, V), ids)
+                logits = self._logits(self.ids2tokens(torch.cat((masked, masked))), context, keys)
+                acc += torch.where(m, self._divergence_cpu(logits[:B], logits[B:], kind), torch.zeros(B, N))
+                count += m
+            score = acc / count
+            mask = self._region_cpu(score, score, g, threshold, grow)
+        else:
+            eng = self.engine()
+            dev = eng.device
+            context = torch.cat((ctx_src.to(dev), ctx_edit.to(dev))).contiguous()
+            keys = self._host_keys(context, 2 * B, lens)
+            ids = ids.to(dev, torch.long)
+            acc, count = torch.zeros(B * N, device=dev, dtype=torch.float32), torch.zeros(B * N, device=dev, dtype=torch.int32)
+            for m in masks:
+                masked = torch.where(m.to(dev), torch.full_like(ids, V), ids).contiguous()
+                logits = eng.forward(self.ids2tokens(torch.cat((masked, masked))), context, keys=keys).reshape(2 * B * N, -1)
+                ops.logit_divergence(logits[:B * N], logits[B * N:], ids=masked.reshape(-1), mask_id=V, kind=kind, out=(acc, count),
+                                     accumulate=True)
+            score = (acc / count).reshape(B, N)
+            mask = ops.phrase_region(score, score, g, float(threshold), grow) != 0
+        mask = (mask & (score.amax(dim=1, keepdim=True) > 0)).reshape(B, g, g)      # (a maximum of 0: >= 0 would select everything)
+        return (mask, score.reshape(B, g, g)) if return_score else mask
 
     @torch.no_grad()
     def ids2tokens(self, ids):
@@ -1625,6 +1764,28 @@ class Pipeline(nn.Module):
         if preserve == "pixels":
             out = ops.composite(out, img.to(eng.device, torch.float32).contiguous(), pm.to(eng.device), out=out)
         return (out, ids) if return_ids else out
+
+    @torch.no_grad()
+    def diff_edit(self, img, text, edit_text, *, mask_ratio=0.5, draws=4, diff_seed=0, kind="tv", threshold=0.5, grow=1, return_mask=False,
+                  **edit_kwargs):
+        """MASK-FREE EDITING (extension): ``img`` with the caption ``text`` becomes ``edit_text`` where the two
+        prompts disagree about it, and stays as it is elsewhere.  The body is
+            mask = diff_mask(img, text, edit_text, mask_ratio, draws, diff_seed, kind, threshold, grow, mask_padding)
+            edit(img, token_mask=mask, text=edit_text, **edit_kwargs)
+        and the result is bit-identical to those two calls made by hand (``mask_padding``, if among ``edit_kwargs``, goes to both).
+        ``edit_kwargs``: ``edit``'s keywords (timesteps, seed, guidance_scale, ...; not mask / token_mask).  An image whose
+        mask is empty -- the prompts agree -- comes back as ``edit`` returns it: ``decode(encode(img))``.  -> what ``edit`` returns;
+        with ``return_mask`` that and the mask, bool [B, g, g].
+
+        The same mask serves the pair loop: ``prompt_to_prompt(text, edit_text, img=photo, blend_mask=pipe.diff_mask(photo, text,
+        edit_text))`` is prompt-to-prompt on a photograph with no phrase to point at."""
+        for k in ("mask", "token_mask"):
+            if k in edit_kwargs:
+                raise ValueError(f"diff_edit: {k} is not a keyword here (the mask follows from the prompts)")
+        mask = self.diff_mask(img, text, edit_text, mask_ratio=mask_ratio, draws=draws, seed=diff_seed, kind=kind, threshold=threshold,
+                              grow=grow, mask_padding=edit_kwargs.get("mask_padding", False))
+        out = self.edit(img, token_mask=mask, text=edit_text, **edit_kwargs)
+        return (out, mask) if return_mask else out
 
     @torch.no_grad()
     def inpaint(self, img, coord, text=None, timesteps=1, topk=1, temperature=0, seed=None, return_ids=False, choice_temperature=None,

@@ -1052,6 +1052,58 @@ def sample_rows_forced(logits, ids, target, mask_id, ids_out=None):
     return pred, ids_out, score
 
 
+DIVERGENCE_KINDS = {"tv": 0, "jeffreys": 1}
+
+
+def logit_divergence(a, b, ids=None, mask_id=None, kind="tv", out=None, accumulate=False):
+    """The divergence between two rows of logits (pmhip_logit_divergence): a, b fp32 [M, V] on the device, unit
+    column stride and one common row stride (a multiple of 4 elements; two halves of one tensor are served as they are, and a may be
+    b) -> (acc f32 [M], count int32 [M]).  Row r is scored iff ids is None or ids[r] == mask_id (ids int64 [M], contiguous; mask_id
+    comes with it).  kind "tv": 1/2 sum |p - q| in [0, 1]; "jeffreys": sum (p - q)(log p - log q) = KL(p||q) + KL(q||p); p, q the two
+    rows' softmax.  A scored row: acc = d, count = 1; an unscored one: 0 and 0, its logits never loaded.  Under `accumulate` a scored
+    row adds d and 1 to what `out` holds and an unscored row is left alone.  out (None: two new tensors; required under `accumulate`):
+    the pair (acc, count), contiguous f32 [M] and int32 [M] on the operands' device.  a == b gives exactly 0; swapping a and b gives
+    the same bits; two calls give the same bits.  Every argument fault is a ValueError in front of the launch.  -> out"""
+    for name, x in (("a", a), ("b", b)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+            raise ValueError(f"logit_divergence: {name} must be an fp32 [M, V] tensor, got "
+                             f"{(x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    dev = a.device
+    M, V = a.shape
+    if tuple(b.shape) != (M, V) or b.device != dev:
+        raise ValueError(f"logit_divergence: b must be an fp32 [{M}, {V}] tensor on a's device, got {tuple(b.shape)} on {b.device}")
+    if M == 0 or V == 0 or V % 4 or V > 16384:
+        raise ValueError(f"logit_divergence: M={M} must be positive and V={V} a multiple of 4 in (0, 16384]")
+    ldl = a.stride(0) if M > 1 else V
+    for name, x in (("a", a), ("b", b)):
+        if x.stride(1) != 1 or (M > 1 and x.stride(0) != ldl) or ldl < V or ldl % 4 or x.data_ptr() % 16:
+            raise ValueError(f"logit_divergence: {name} must have unit column stride, the common row stride (a multiple of 4, at least V={V}) and "
+                             f"16-byte alignment, got strides {tuple(x.stride())}")
+    if kind not in DIVERGENCE_KINDS:
+        raise ValueError(f"logit_divergence: kind {kind!r} is neither 'tv' nor 'jeffreys'")
+    if (ids is None) != (mask_id is None):
+        raise ValueError("logit_divergence: ids and mask_id come together (ids=None scores every row)")
+    if ids is not None:
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int64 and tuple(ids.shape) == (M,) and ids.is_contiguous() and ids.device == dev):
+            raise ValueError(f"logit_divergence: ids must be a contiguous int64 [{M}] tensor on the operands' device")
+        if isinstance(mask_id, bool) or not isinstance(mask_id, int):
+            raise ValueError(f"logit_divergence: mask_id {mask_id!r} must be an integer")
+    if out is None and accumulate:
+        raise ValueError("accumulate adds to `out`: pass the pair of tensors to add to")
+    if not a.is_cuda:                                          # (behind the argument checks: those hold without a device)
+        raise _lib.PmhipError("paintmind_amd runs only on a ROCm device (got a CPU tensor); there is no CPU fallback")
+    if out is None:
+        out = (torch.empty(M, device=dev, dtype=torch.float32), torch.empty(M, device=dev, dtype=torch.int32))
+    if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
+            isinstance(o, torch.Tensor) and o.is_cuda and o.device == dev and o.dtype == dt and tuple(o.shape) == (M,) and o.is_contiguous()
+            for o, dt in zip(out, (torch.float32, torch.int32)))):
+        raise ValueError(f"out must be a pair of contiguous tensors (float32 [{M}], int32 [{M}]) on the operands' device")
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_logit_divergence(_p(a), _p(b), int(ldl), _p(ids), int(mask_id or 0), DIVERGENCE_KINDS[kind], _p(out[0]), _p(out[1]),
+                                                 int(bool(accumulate)), M, V, stream_ptr(dev)), "pmhip_logit_divergence")
+    return out[0], out[1]
+
+
 def choice_t(value, what="choice_temperature"):
     """a step's choice temperature (None = 0) -> a float, checked as the native entries check it: finite, 0 <= t <= CHOICE_T_MAX"""
     t = 0.0 if value is None else float(value)
