@@ -27,7 +27,8 @@
  *         ldo >= Hp                   pmhip_gemm_swiglu / _ln
  *         ldo >= heads * dim_head     pmhip_attention / _dh / _lens / _control
  *         ldm >= Nkv                  pmhip_attention_maps
- *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus / _forced, pmhip_masked_ce, pmhip_logit_divergence
+ *         ldl >= V                    pmhip_sample_rows / _stats / _slots / _nucleus / _forced, pmhip_masked_ce, pmhip_logit_divergence,
+ *                                     pmhip_token_logprob
  *     A result does not depend on a leading dimension: the same values give the same bits at any ld (as long as M * lda and
  *     N * ldw stay below 2^30 elements; beyond that another kernel may serve the call).
  *   - an output of [M, N] is written in exactly its M x N elements, however ragged M and N are against a kernel's tile; arrays
@@ -558,6 +559,31 @@ int pmhip_sample_rows_forced(const float* logits, int ldl, const int64_t* ids_in
  * M > 0, 0 < V <= 16384, V % 4 == 0, ldl % 4 == 0, ldl >= V, else PMHIP_EINVAL naming the argument. */
 int pmhip_logit_divergence(const float* a, const float* b, int ldl, const int64_t* ids, int64_t mask_id, int kind, float* acc,
                            int32_t* count, int accumulate, int M, int V, pmhip_stream stream);
+
+/* The model's LIKELIHOOD of a given token (a new entry within ABI 11).  a (and b, or NULL) fp32 [M, V] with
+ * the row stride ldl; target, and ids when given, int64 [M] in device memory, never read on the host.  Row r is SCORED iff
+ * (ids is NULL or ids[r] == mask_id) and 0 <= target[r] < V.  The range test sits in front of any use of the target as an index: a
+ * target outside the range -- the mask id included -- makes the row an unscored row (the rule of pmhip_sample_rows_forced).
+ * The row that is scored: b NULL, x = a[r] (scale is ignored); b given, the guided logits x_i = b_i + scale * (a_i - b_i), formed at
+ * load by the expression of pmhip_guidance_combine (a = cond, b = uncond), bit for bit: the combined tensor is neither written nor
+ * re-read.  scale must be finite.  With t = target[r], m = max_i x_i and s = sum_i exp(x_i - m), a scored row yields
+ *   lp  = (x_t - m) - log s             natural log; <= 0 exactly; -inf for a target column at -inf
+ *   ent = log s + sum_i p_i (m - x_i)   the entropy of softmax(x); >= 0, exactly 0 for a row with one finite column; a -inf column adds 0
+ *   rk  = #{ i : x_i > x_t, or x_i == x_t and i < t }   the target's place in the samplers' order (value descending, column
+ *         ascending), exact: rk < k iff topk = k would have kept the token
+ * A NaN anywhere in a scored row gives NaN lp and ent for that row and no other; its rk is unspecified.
+ *                    accumulate == 0                                    accumulate != 0
+ *   scored row       logp[r] = lp; entropy[r] = ent; rank[r] = rk;      logp[r] += lp; entropy[r] += ent; rank[r] += rk;
+ *                    count[r] = 1                                       count[r] += 1
+ *   unscored row     all four = 0                                       none is touched
+ * logp fp32 [M]; entropy fp32 [M], rank int32 [M], count int32 [M], each or NULL.  The logits of an unscored row are never loaded:
+ * a NaN there reaches nothing and the launch costs the scored rows' bytes.  Every element of a scored row is requested once (the
+ * target's own logit a second time); one writer per row, a fixed order of the sums, no atomics: two launches give the same bits
+ * (logprob.hip states the evaluation order).  a, b, ids and target are read only; a and b are 16-byte aligned.
+ * M > 0, 0 < V <= 16384, V % 4 == 0, ldl % 4 == 0, ldl >= V, a / target / logp non-NULL, else PMHIP_EINVAL naming the argument, in
+ * front of any launch. */
+int pmhip_token_logprob(const float* a, const float* b, float scale, int ldl, const int64_t* ids, int64_t mask_id, const int64_t* target,
+                        float* logp, float* entropy, int32_t* rank, int32_t* count, int accumulate, int M, int V, pmhip_stream stream);
 
 /* The same step for a caller that holds the SOFTMAX STATISTICS of the rows' 64-column blocks (round 5): block_stats [M][V/64][2] =
  * (max, sum_j 2^((x_j - max) log2 e)) per block, as pmhip_gemm_softmax_stats / pmhip_guidance_combine_stats leave them behind.

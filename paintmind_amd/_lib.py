@@ -165,6 +165,7 @@ PROTOTYPES = {
     "pmhip_sample_rows_nucleus": (i32, [vp, i32, vp, i64, i32, f32, f32, vp, u64, u32, u64, vp, vp, vp, i32, i32, vp]),
     "pmhip_sample_rows_forced": (i32, [vp, i32, vp, vp, i64, vp, vp, vp, i32, i32, vp]),
     "pmhip_logit_divergence": (i32, [vp, vp, i32, vp, i64, i32, vp, vp, i32, i32, i32, vp]),
+    "pmhip_token_logprob": (i32, [vp, vp, f32, i32, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "pmhip_pipeline_sample_nucleus": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, f32, i32, vp, u64, u32, u64, vp, vp, vp, i32, f32,
                                             f32, vp, f32, vp]),
     "pmhip_pipeline_generate_nucleus": (i32, [vp, vp, vp, vp, i32, i32, C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(i32),

@@ -263,6 +263,21 @@ T5_TXT_DIM = {'t5-l': 1024, 't5-xl': 2048}      # no 't5-xxl' entry, as in the r
 LANES_MIN_WORK = 17_000_000
 
 
+class TokenScores(NamedTuple):
+    """``Pipeline.token_scores``: three f32 [B, g, g] maps of an image's tokens under a caption"""
+    logp: torch.Tensor        # mean over the draws that masked the token of log p(true id | the unmasked rest, text): <= 0
+    entropy: torch.Tensor     # ... of the entropy of the model's distribution at the token: >= 0
+    rank: torch.Tensor        # ... of the true id's place in the samplers' order: < k iff topk = k would have kept it
+
+
+def best_index(scores):
+    """the winner of ``Pipeline.best_of`` per prompt: scores f32 [B, n] -> int64 [B], the arg-max with ties to the lowest j; a NaN
+    never beats a number (a row of NaN only: 0)"""
+    s = torch.where(torch.isnan(scores), torch.full_like(scores, float("-inf")), scores)
+    cols = torch.arange(s.shape[1], device=s.device).expand_as(s)
+    return torch.where(s == s.amax(dim=1, keepdim=True), cols, torch.full_like(cols, s.shape[1])).amin(dim=1)
+
+
 class Pipeline(nn.Module):
     def __init__(self, config, stage1_pretrained=True, stage1_checkpoint_path=None, text_model=None):
         super().__init__()
@@ -526,24 +541,25 @@ class Pipeline(nn.Module):
         t = torch.where(gone_p & gone_q, torch.zeros_like(dp), dp * (lp - lq))         # -inf in both: nothing; in one: +inf
         return torch.where(gone_p != gone_q, torch.full_like(dp, float("inf")), t).sum(-1)
 
-    def _diff_context(self, text, B, mask_padding, lens, who):
-        """one side of ``diff_mask``: a list of B prompts, one prompt for every image, or a context tensor [B, L, D] -> (context, lens)"""
+    def _diff_context(self, text, B, mask_padding, lens, who, caller="diff_mask"):
+        """one side of ``diff_mask`` (or the caption of `caller`): a list of B prompts, one prompt for every image, or a context tensor
+        [B, L, D] -> (context, lens)"""
         if isinstance(text, torch.Tensor):
             if text.dim() != 3 or text.shape[0] != B:
-                raise ValueError(f"diff_mask: {who} must be a context tensor [{B}, L, D], got {tuple(text.shape)}")
+                raise ValueError(f"{caller}: {who} must be a context tensor [{B}, L, D], got {tuple(text.shape)}")
             if mask_padding:
-                raise ValueError(f"diff_mask: mask_padding takes the lengths from the text model: {who} is a tensor, pass its lengths")
+                raise ValueError(f"{caller}: mask_padding takes the lengths from the text model: {who} is a tensor, pass its lengths")
             return text, lens
         if getattr(self, "text_model", None) is None:
-            raise ValueError("diff_mask needs a text condition (an unconditional pipeline has no prompt to disagree about)")
+            raise ValueError(f"{caller} needs a text condition (an unconditional pipeline has no prompt to disagree about)")
         if isinstance(text, str):
             prompts = [text] * B
         elif isinstance(text, (list, tuple)) and all(isinstance(p, str) for p in text):
             prompts = list(text)
         else:
-            raise ValueError(f"diff_mask: {who} must be a prompt, a list of {B} prompts or a context tensor, got {type(text).__name__}")
+            raise ValueError(f"{caller}: {who} must be a prompt, a list of {B} prompts or a context tensor, got {type(text).__name__}")
         if len(prompts) != B:
-            raise ValueError(f"diff_mask: {who} has {len(prompts)} prompts for a batch of {B}")
+            raise ValueError(f"{caller}: {who} has {len(prompts)} prompts for a batch of {B}")
         if mask_padding and lens is None:
             return self.text_model(prompts, return_lens=True)
         return self.text_model(prompts), lens
@@ -629,6 +645,239 @@ class Pipeline(nn.Module):
             mask = ops.phrase_region(score, score, g, float(threshold), grow) != 0
         mask = (mask & (score.amax(dim=1, keepdim=True) > 0)).reshape(B, g, g)      # (a maximum of 0: >= 0 would select everything)
         return (mask, score.reshape(B, g, g)) if return_score else mask
+
+    # ------------------------------------------------------------------------------------------------ model likelihood (section 4zg)
+    @staticmethod
+    def _token_logprob_cpu(x, target):
+        """``ops.token_logprob`` on every row in plain torch, float32, by the kernel's expressions (torch's own sums, exp and log):
+        logits [..., V], target int64 [...] -> (logp, entropy f32, rank int64)"""
+        x = x.float()
+        t = target[..., None]
+        d = x - x.amax(dim=-1, keepdim=True)
+        e = d.exp()
+        s = e.sum(-1)
+        L = s.log()
+        ent = L + torch.where(e == 0, torch.zeros_like(e), e * -d).sum(-1) / s           # (a -inf column: 0 * inf through a select)
+        xt = x.gather(-1, t)
+        cols = torch.arange(x.shape[-1], device=x.device)
+        rank = ((x > xt) | ((x == xt) & (cols < t))).sum(-1)
+        return d.gather(-1, t)[..., 0] - L, ent, rank
+
+    def _score_args(self, who, img, ids, text, mask_padding, context_lens, guidance_scale, refused):
+        """what ``token_scores`` / ``score`` check: -> (ids int64 [B, N], context or None, lens or None, the scale or None)"""
+        if refused:
+            raise ValueError(f"{who} does not serve {sorted(refused)} (the segment arrays, prompt weights, negative prompts and a guidance "
+                             f"schedule take no part in the scoring passes)")
+        if (ids is None) == (img is None):
+            raise ValueError(f"{who}: give exactly one of img and ids")
+        N = self.num_tokens
+        if img is not None:
+            if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[2] != self.image_size or img.shape[3] != self.image_size:
+                raise ValueError(f"{who}: img must be [B, C, {self.image_size}, {self.image_size}], got "
+                                 f"{tuple(img.shape) if isinstance(img, torch.Tensor) else type(img).__name__}")
+            ids = self.to_latent(img)[1].reshape(img.shape[0], N)
+        else:
+            if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() < 2 or ids[0].numel() != N:
+                raise ValueError(f"{who}: ids must be an int64 tensor [B, {N}] or [B, g, g], got "
+                                 f"{(ids.dtype, tuple(ids.shape)) if isinstance(ids, torch.Tensor) else type(ids).__name__}")
+            ids = ids.reshape(ids.shape[0], N)
+            bad = ((ids < 0) | (ids > self.mask_token_id)).nonzero()
+            if len(bad):
+                b, i = bad[0].tolist()
+                raise ValueError(f"{who}: ids: image {b}, token {i}: {int(ids[b, i])} is neither a code nor the mask id {self.mask_token_id}")
+        B = ids.shape[0]
+        if guidance_scale is not None:
+            if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)) or not math.isfinite(guidance_scale):
+                raise ValueError(f"{who}: guidance_scale {guidance_scale!r} must be one finite number (a schedule belongs to a decode loop)")
+            if text is None:
+                raise ValueError(f"{who}: guidance_scale needs a text condition (text=None IS the unconditional branch)")
+        if text is None:
+            if mask_padding or context_lens is not None:
+                raise ValueError(f"{who}: mask_padding and context_lens need a text condition")
+            return ids, None, None, None
+        context, lens = self._diff_context(text, B, mask_padding, context_lens, "text", who)
+        return ids, context, lens, None if guidance_scale is None else float(guidance_scale)
+
+    def _token_scores(self, ids, context, lens, masks, scale):
+        """the rule of ``token_scores`` behind its checks: ids int64 [B, N], masks bool [draws, B, N] (CPU) -> (logp, entropy, rank) f32
+        [B, N] on the pipeline's device, each acc / count (NaN = 0 / 0 where the id is the mask id: such a position is never scored)"""
+        B, N, V = ids.shape[0], self.num_tokens, self.mask_token_id
+        if self._on_cpu():
+            ids = ids.cpu()
+            context = None if context is None else context.float()
+            keys, nokeys = self._host_keys(context, B, lens), self._host_keys(None, B)
+            acc = [torch.zeros(B, N) for _ in range(3)]
+            count = torch.zeros(B, N)
+            known = ids != V                                   # (a position that holds the mask id has no true id: never scored)
+            target = torch.where(known, ids, torch.zeros_like(ids))
+            for m in masks:
+                tok = self.ids2tokens(torch.where(m, torch.full_like(ids, V), ids))
+                x = self._logits(tok, context, keys)
+                if scale is not None:
+                    uncond = self._logits(tok, None, nokeys)
+                    x = torch.addcmul(uncond, x - uncond, torch.tensor(scale))
+                for a, v in zip(acc, self._token_logprob_cpu(x, target)):
+                    a += torch.where(m & known, v.float(), torch.zeros(B, N))
+                count += m & known
+            return tuple(a / count for a in acc)
+        eng = self.engine()
+        dev = eng.device
+        context = None if context is None else context.to(dev).contiguous()
+        keys, nokeys = self._host_keys(context, B, lens), self._host_keys(None, B)
+        ids = ids.to(dev, torch.long).contiguous()
+        out = (torch.zeros(B * N, device=dev), torch.zeros(B * N, device=dev), torch.zeros(B * N, device=dev, dtype=torch.int32),
+               torch.zeros(B * N, device=dev, dtype=torch.int32))
+        for m in masks:
+            masked = torch.where(m.to(dev), torch.full_like(ids, V), ids).contiguous()
+            tok = self.ids2tokens(masked)
+            x = eng.forward(tok, context, keys=keys).reshape(B * N, -1)
+            uncond = None if scale is None else eng.forward(tok, None, keys=nokeys).reshape(B * N, -1)
+            ops.token_logprob(x, ids.reshape(-1), uncond=uncond, scale=scale, ids=masked.reshape(-1), mask_id=V, out=out, accumulate=True)
+        count = out[3].float()
+        return tuple((a.float() / count).reshape(B, N) for a in out[:3])
+
+    @torch.no_grad()
+    def token_scores(self, img=None, text=None, *, ids=None, mask_ratio=0.5, draws=4, seed=0, guidance_scale=None, mask_padding=False,
+                     context_lens=None, **refused):
+        """HOW LIKELY the model finds every token of a picture under a caption (extension).  ``img`` [B, C, H, W]
+        is encoded as ``to_latent`` does, or ``ids=`` int64 [B, N] gives the codes; a position that holds the mask id (a decode loop
+        leaves some) has no true id: it stays masked in every draw, is never scored, and its map entries are NaN (0 / 0).  ``text``: a list of B
+        prompts, one prompt for every image, a context tensor [B, L, D], or None -- the unconditional branch.  With ``mask_padding``
+        the non-pad lengths come from the text model; ``context_lens`` gives them.
+
+        The rule, which is the contract:
+            1. ids are given, or ids = to_latent(img)
+            2. masks = diff_draws(B, N, mask_ratio, draws, seed): every position is masked in at least one draw
+            3. draw j: the ids with the mask id where masks[j] is set go through ONE forward under ``text``
+            4. with ``guidance_scale`` (one finite number; needs text) a second forward of the same ids runs without text, and the row
+               that is scored is uncond + guidance_scale * (cond - uncond): the logits a guided step samples from
+            5. every masked position t of image b, with its TRUE id i, adds  log softmax(x)[i],  the entropy of softmax(x)  and the
+               place of i in the samplers' order (value descending, column ascending)  to three accumulators, and 1 to count[b, t]
+            6. each map = acc / count (the rank as a float mean)
+        On the GPU step 5 is one HBM-bound kernel (``ops.token_logprob``) that forms step 4's row at load; on the CPU the same rule in
+        plain torch.  Not served (ValueError): the segment arrays, prompt weights, negative prompts, a guidance schedule.
+
+        -> TokenScores(logp, entropy, rank), f32 [B, g, g] on the pipeline's device.  Nothing is captured: a later call of anything
+        runs what it ran before."""
+        ids, context, lens, scale = self._score_args("token_scores", img, ids, text, mask_padding, context_lens, guidance_scale, refused)
+        B, g = ids.shape[0], self.image_size // self.patch_size
+        masks = diff_draws(B, self.num_tokens, mask_ratio, draws, seed)
+        return TokenScores(*(x.reshape(B, g, g) for x in self._token_scores(ids, context, lens, masks, scale)))
+
+    @torch.no_grad()
+    def score(self, img=None, text=None, *, ids=None, relative=False, mask_ratio=0.5, draws=4, seed=0, guidance_scale=None,
+              mask_padding=False, context_lens=None, **refused):
+        """The model's LIKELIHOOD of a picture under a caption (extension): the mean over the tokens of
+        ``token_scores(...).logp`` that hold a code (mask ids among ``ids=`` take no part) -> f32 [B], <= 0, higher = more plausible.  ``relative=True`` subtracts the same call with
+        ``text=None`` and the same masks: log p(tokens | text) - log p(tokens | no text), a text-to-image alignment score (it needs
+        text and refuses ``guidance_scale``, which mixes the two branches it compares).  Arguments as in ``token_scores``."""
+        ids, context, lens, scale = self._score_args("score", img, ids, text, mask_padding, context_lens, guidance_scale, refused)
+        if relative and (context is None or scale is not None):
+            raise ValueError("score: relative=True compares the text branch with the unconditional one: it needs text and takes no guidance_scale")
+        B = ids.shape[0]
+        masks = diff_draws(B, self.num_tokens, mask_ratio, draws, seed)
+        known = (ids != self.mask_token_id).to(self.mask_token.device)
+
+        def mean(logp):                                        # over the positions that hold a code (0 / 0 = NaN for an image with none)
+            return torch.where(known, logp, torch.zeros_like(logp)).sum(dim=1) / known.sum(dim=1)
+        value = mean(self._token_scores(ids, context, lens, masks, scale)[0])
+        if relative:
+            value = value - mean(self._token_scores(ids, None, None, masks, None)[0])
+        return value
+
+    @torch.no_grad()
+    def surprise_mask(self, img, text, threshold=0.5, grow=1, return_score=False, **token_scores_keywords):
+        """An edit mask from WHAT DOES NOT FIT THE CAPTION (extension): no phrase, no second prompt.
+            s    = -token_scores(img, text, ...).logp           the surprise of every token's true id under the caption
+            mask = s >= threshold * max_t s[b],  0 < threshold <= 1,  dilated ``grow`` times by a 3 x 3 maximum (``ops.phrase_region``);
+                   an image whose maximum is exactly 0 gets an EMPTY mask
+        -> bool [B, g, g] on the pipeline's device: what ``edit(token_mask=)`` and ``prompt_to_prompt(blend_mask=)`` take; with
+        ``return_score`` (mask, s f32 [B, g, g]).  The repair of what does not fit is the composition
+        ``edit(img, token_mask=surprise_mask(img, text), text=text)``.  The defaults are defaults, not optima measured on this tower."""
+        if not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and 0 < threshold <= 1):
+            raise ValueError(f"surprise_mask: threshold {threshold!r} must be in (0, 1]")
+        if not (isinstance(grow, int) and not isinstance(grow, bool) and grow >= 0):
+            raise ValueError(f"surprise_mask: grow {grow!r} must be a non-negative integer")
+        if "ids" in token_scores_keywords:
+            raise ValueError("surprise_mask: the mask is one of an image: pass img")
+        s = -self.token_scores(img, text, **token_scores_keywords).logp
+        B, g = s.shape[0], s.shape[1]
+        s = s.reshape(B, g * g).contiguous()
+        if self._on_cpu():
+            mask = self._region_cpu(s, s, g, threshold, grow)
+        else:
+            mask = ops.phrase_region(s, s, g, float(threshold), grow) != 0
+        mask = (mask & (s.amax(dim=1, keepdim=True) > 0)).reshape(B, g, g)          # (a maximum of 0: >= 0 would select everything)
+        return (mask, s.reshape(B, g, g)) if return_score else mask
+
+    @torch.no_grad()
+    def best_of(self, text, n, *, score_guidance=None, score_mask_ratio=0.5, score_draws=4, score_seed=0, return_all=False, timesteps=18,
+                temperature=1.0, topk=5, top_p=None, guidance_scale=None, choice_temperature=None, mask_padding=False, seed=None,
+                image_base=0, **refused):
+        """BEST OF n (extension): n candidates per prompt, the one the model itself finds most plausible is
+        kept.  ``text``: a list of B prompts.  Candidate j of prompt b is the image with the global index image_base + j * B + b: its ids
+        are, bit for bit, row b of the ``generate`` / ``generate_ids`` run with ``image_base = image_base + j * B`` and the same
+        ``seed`` (None: one seed is drawn for the call) -- that loop runs n times.  Then
+            scores[:, j] = score(ids=candidate ids, text=the prompts' context, guidance_scale=score_guidance,
+                                 mask_ratio=score_mask_ratio, draws=score_draws, seed=score_seed)
+        and the winner is the arg-max over j, ties to the lowest j; a NaN score never beats a number (``best_index``).  The ids a
+        loop returns still hold the mask id at the positions its last step re-masked (at least one): they take no part in the score,
+        and no image can be decoded from them -- ``generate``'s image is decoded from the last step's predictions at ALL positions.
+        So every candidate's LAST step is decoded inside its loop (one decode per candidate, none for the other steps) and the
+        winners' images are picked; they stay on the device.  ``timesteps, temperature, topk, top_p, guidance_scale,
+        choice_temperature, mask_padding, seed, image_base`` are ``generate``'s; regions, prompt weights, negative prompts and edits
+        are refused in this version.
+        (A pipeline on the CPU runs the same rule; its loop does not key the noise by the image index, so under a fixed seed its
+        candidates coincide.)
+
+        -> (imgs [B, C, H, W] on the pipeline's device, index int64 [B], scores f32 [B, n]); with ``return_all`` the candidates' ids
+        int64 [B, n, N] as a fourth."""
+        if refused:
+            raise ValueError(f"best_of does not serve {sorted(refused)} (regions, prompt weights, negative prompts and edits are refused "
+                             f"in this version)")
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"best_of: n {n!r} must be an integer >= 1")
+        if isinstance(text, str) or not isinstance(text, (list, tuple)) or not all(isinstance(p, str) for p in text) or not text:
+            raise ValueError("best_of: text must be a list of prompts")
+        if isinstance(image_base, bool) or not isinstance(image_base, int) or image_base < 0:
+            raise ValueError(f"best_of: image_base {image_base!r} must be a non-negative integer")
+        B = len(text)
+        diff_draws(B, self.num_tokens, score_mask_ratio, score_draws, score_seed)       # the scoring keywords, checked before any loop runs
+        if score_guidance is not None and (isinstance(score_guidance, bool) or not isinstance(score_guidance, (int, float))
+                                           or not math.isfinite(score_guidance)):
+            raise ValueError(f"best_of: score_guidance {score_guidance!r} must be one finite number")
+        if mask_padding:
+            context, lens = self.text_model(list(text), return_lens=True)
+        else:
+            context, lens = self.text_model(list(text)), None
+        if context is None:
+            raise ValueError("best_of needs a text condition (the score is that of the picture under its prompt)")
+        opts = self._options(topk, top_p, guidance_scale, lens, choice_temperature, context, B, timesteps=timesteps)
+        keys = self._keys(context, B, opts)
+        if seed is None:
+            seed = _draw_seed()
+        cpu = self._on_cpu()
+        if not cpu:
+            context = context.to(self.engine().device)
+            use_graph = os.environ.get("PMHIP_GENERATE_GRAPH", "1") != "0"
+        cands, scores, last = [], [], []
+        flags = [False] * (timesteps - 1) + [True]
+        for j in range(n):
+            if cpu:
+                imgs, ids = self._generate_cpu(context, B, timesteps, temperature, opts, 1, seed, True, keys)
+            else:
+                ids, imgs = self.generate_ids(context, B, timesteps, temperature, opts, flags, seed, image_base=image_base + j * B,
+                                              use_graph=use_graph, streams=1, keys=keys)
+            cands.append(ids)
+            last.append(imgs[-1])
+            scores.append(self.score(ids=ids, text=context, guidance_scale=score_guidance, mask_ratio=score_mask_ratio, draws=score_draws,
+                                     seed=score_seed, context_lens=lens))
+        scores = torch.stack(scores, dim=1)
+        cands = torch.stack(cands, dim=1)
+        index = best_index(scores)
+        last = torch.stack(last, dim=1)
+        imgs = last[torch.arange(B, device=last.device), index.to(last.device)]
+        return (imgs, index, scores, cands) if return_all else (imgs, index, scores)
 
     @torch.no_grad()
     def ids2tokens(self, ids):

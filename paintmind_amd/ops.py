@@ -1104,6 +1104,70 @@ def logit_divergence(a, b, ids=None, mask_id=None, kind="tv", out=None, accumula
     return out[0], out[1]
 
 
+def token_logprob(logits, target, uncond=None, scale=None, ids=None, mask_id=None, out=None, accumulate=False, entropy=True, rank=True):
+    """The model's likelihood of given tokens (pmhip_token_logprob): logits fp32 [M, V] on the device, unit
+    column stride and a row stride that is a multiple of 4 elements; target int64 [M] -> (logp f32 [M], entropy f32 [M] or None,
+    rank int32 [M] or None, count int32 [M]).  Row r is scored iff (ids is None or ids[r] == mask_id) and 0 <= target[r] < V (ids
+    int64 [M], contiguous; mask_id comes with it); the kernel tests the range in front of its load.  uncond (fp32 [M, V], logits' row
+    stride) with scale (a finite number; the two come together): the scored row is uncond + scale * (logits - uncond), formed at load
+    by ``guidance_combine``'s expression, bit for bit.  A scored row: logp = log softmax(x)[target] <= 0, entropy = that of softmax(x)
+    >= 0, rank = the target's place in the samplers' order (value descending, column ascending; rank < k iff topk = k keeps it),
+    count = 1; an unscored one: 0 everywhere, its logits never loaded.  Under `accumulate` a scored row adds to what `out` holds
+    and an unscored row is left alone.  entropy / rank False: that output is not computed into anything and comes back as None.
+    out (None: new tensors; required under `accumulate`): the 4-tuple in the order of the result, None where entropy / rank is off,
+    contiguous [M] tensors on the operands' device.  Two calls give the same bits.  Every argument fault is a ValueError in front of
+    the launch.  -> out"""
+    for name, x in (("logits", logits), ("uncond", uncond)):
+        if x is not None and (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32):
+            raise ValueError(f"token_logprob: {name} must be an fp32 [M, V] tensor, got "
+                             f"{(x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if logits is None:
+        raise ValueError("token_logprob: logits must be an fp32 [M, V] tensor, got None")
+    dev = logits.device
+    M, V = logits.shape
+    if M == 0 or V == 0 or V % 4 or V > 16384:
+        raise ValueError(f"token_logprob: M={M} must be positive and V={V} a multiple of 4 in (0, 16384]")
+    if (uncond is None) != (scale is None):
+        raise ValueError("token_logprob: uncond and scale come together (neither: the plain logits are scored)")
+    if uncond is not None:
+        if tuple(uncond.shape) != (M, V) or uncond.device != dev:
+            raise ValueError(f"token_logprob: uncond must be an fp32 [{M}, {V}] tensor on the logits' device, got {tuple(uncond.shape)} on {uncond.device}")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+            raise ValueError(f"token_logprob: scale {scale!r} must be a finite number")
+    ldl = logits.stride(0) if M > 1 else V
+    for name, x in (("logits", logits), ("uncond", uncond)):
+        if x is not None and (x.stride(1) != 1 or (M > 1 and x.stride(0) != ldl) or ldl < V or ldl % 4 or x.data_ptr() % 16):
+            raise ValueError(f"token_logprob: {name} must have unit column stride, the common row stride (a multiple of 4, at least V={V}) and "
+                             f"16-byte alignment, got strides {tuple(x.stride())}")
+    if not (isinstance(target, torch.Tensor) and target.dtype == torch.int64 and tuple(target.shape) == (M,) and target.is_contiguous()
+            and target.device == dev):
+        raise ValueError(f"token_logprob: target must be a contiguous int64 [{M}] tensor on the logits' device")
+    if (ids is None) != (mask_id is None):
+        raise ValueError("token_logprob: ids and mask_id come together (ids=None scores every row with a target in range)")
+    if ids is not None:
+        if not (isinstance(ids, torch.Tensor) and ids.dtype == torch.int64 and tuple(ids.shape) == (M,) and ids.is_contiguous() and ids.device == dev):
+            raise ValueError(f"token_logprob: ids must be a contiguous int64 [{M}] tensor on the logits' device")
+        if isinstance(mask_id, bool) or not isinstance(mask_id, int):
+            raise ValueError(f"token_logprob: mask_id {mask_id!r} must be an integer")
+    if out is None and accumulate:
+        raise ValueError("accumulate adds to `out`: pass the tensors to add to")
+    if not logits.is_cuda:                                     # (behind the argument checks: those hold without a device)
+        raise _lib.PmhipError("paintmind_amd runs only on a ROCm device (got a CPU tensor); there is no CPU fallback")
+    want = (torch.float32, torch.float32 if entropy else None, torch.int32 if rank else None, torch.int32)
+    if out is None:
+        out = tuple(None if dt is None else torch.empty(M, device=dev, dtype=dt) for dt in want)
+    if not (isinstance(out, (tuple, list)) and len(out) == 4 and all(
+            (o is None) if dt is None else (isinstance(o, torch.Tensor) and o.is_cuda and o.device == dev and o.dtype == dt
+                                            and tuple(o.shape) == (M,) and o.is_contiguous()) for o, dt in zip(out, want))):
+        raise ValueError(f"out must be (float32 [{M}], float32 [{M}] or None without entropy, int32 [{M}] or None without rank, int32 [{M}]): "
+                         f"contiguous tensors on the operands' device")
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_token_logprob(_p(logits), _p(uncond), float(scale or 0.0), int(ldl), _p(ids), int(mask_id or 0), _p(target),
+                                              _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3]), int(bool(accumulate)), M, V, stream_ptr(dev)),
+              "pmhip_token_logprob")
+    return tuple(out)
+
+
 def choice_t(value, what="choice_temperature"):
     """a step's choice temperature (None = 0) -> a float, checked as the native entries check it: finite, 0 <= t <= CHOICE_T_MAX"""
     t = 0.0 if value is None else float(value)
