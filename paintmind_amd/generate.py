@@ -21,6 +21,7 @@ from . import ops, packing
 from .config import ver2cfg
 from .engine import S2Engine
 from .stage2 import CondTransformer
+from .steps import HipSteps, TorchSteps
 
 
 def exists(x):
@@ -278,6 +279,27 @@ def best_index(scores):
     return torch.where(s == s.amax(dim=1, keepdim=True), cols, torch.full_like(cols, s.shape[1])).amin(dim=1)
 
 
+def _check_region(who, threshold, grow, bools=False, prefix=""):
+    """the two numbers of a region rule for caller `who`: a threshold in (0, 1] and a non-negative dilation count.  bools: True and
+    False pass as the numbers 1 and 0 (``phrase_mask`` and ``control_ids`` have always let them; the later callers refuse them)"""
+    if not (isinstance(threshold, (int, float)) and (bools or not isinstance(threshold, bool)) and 0 < threshold <= 1):
+        raise ValueError(f"{who}: {prefix}threshold {threshold!r} must be in (0, 1]")
+    if not (isinstance(grow, int) and (bools or not isinstance(grow, bool)) and grow >= 0):
+        raise ValueError(f"{who}: {prefix}grow {grow!r} must be a non-negative integer")
+
+
+def _no_schedule(who, guidance_scale):
+    """the eager pair and forced loops guide every step alike: anything with a dimension is refused"""
+    if guidance_scale is not None and np.ndim(guidance_scale) > 0:
+        raise ValueError(f"{who}: guidance_scale is one number (a schedule is not served)")
+
+
+def _finite_number(who, name, x, why=""):
+    """the scale of a scoring pass: None, or one finite int or float (no bool)"""
+    if x is not None and (isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x)):
+        raise ValueError(f"{who}: {name} {x!r} must be one finite number{why}")
+
+
 class Pipeline(nn.Module):
     def __init__(self, config, stage1_pretrained=True, stage1_checkpoint_path=None, text_model=None):
         super().__init__()
@@ -394,6 +416,23 @@ class Pipeline(nn.Module):
 
     def _on_cpu(self):
         return self.mask_token.device.type == "cpu"
+
+    def _steps(self):
+        """the step vocabulary of the eager flows (paintmind_amd/steps.py) for where this pipeline lives: their one device test"""
+        return TorchSteps(self) if self._on_cpu() else HipSteps(self)
+
+    def _check_img(self, who, img, B=None):
+        """an image batch [B, C, size, size] of this pipeline, for caller `who`; B: one image per prompt"""
+        size = self.image_size
+        if not isinstance(img, torch.Tensor) or img.dim() != 4 or B not in (None, img.shape[0]) or img.shape[2] != size or img.shape[3] != size:
+            raise ValueError(f"{who}: img must be [{'B' if B is None else B}, C, {size}, {size}]{'' if B is None else ' (one image per prompt)'}, got "
+                             f"{tuple(img.shape) if isinstance(img, torch.Tensor) else type(img).__name__}")
+
+    @staticmethod
+    def _score_mask(st, s, g, threshold, grow):
+        """a mask from ONE score f32 [B, g*g]: the region rule on it (``ops.phrase_region`` / ``_region_cpu`` through the vocabulary's
+        ``region``) -> bool [B, g*g]; an image whose maximum is exactly 0 gets an EMPTY mask (>= 0 would select everything)"""
+        return (st.region(s, s, g, threshold, grow) != 0) & (s.amax(dim=1, keepdim=True) > 0)
 
     def _topk(self, topk):
         """topk=None is 'no filter' (the plain MaskGIT / Muse sampler): every class is kept, topk = n_embed -- on the CPU and
@@ -513,10 +552,7 @@ class Pipeline(nn.Module):
             mask        = score >= threshold * max_t score[b],   0 < threshold <= 1
         then dilated ``grow`` times by a 3 x 3 maximum.  The default threshold 0.5 is a default, not a measured optimum: look at
         the maps and choose.  -> bool [B, g, g] on the pipeline's device: what ``edit(token_mask=)`` takes."""
-        if not (isinstance(threshold, (int, float)) and 0 < threshold <= 1):
-            raise ValueError(f"phrase_mask: threshold {threshold!r} must be in (0, 1]")
-        if not (isinstance(grow, int) and grow >= 0):
-            raise ValueError(f"phrase_mask: grow {grow!r} must be a non-negative integer")
+        _check_region("phrase_mask", threshold, grow, bools=True)
         if not hasattr(self.text_model, "phrase_rows"):
             raise NotImplementedError(f"{type(self.text_model).__name__} serves no phrase rows (phrase_rows): T5TextEmbedder does")
         prompts = [text] * img.shape[0] if isinstance(text, str) else list(text)
@@ -594,15 +630,10 @@ class Pipeline(nn.Module):
         if refused:
             raise ValueError(f"diff_mask does not serve {sorted(refused)} (guidance, negative prompts, the segment arrays and prompt weights "
                              f"take no part in the divergence passes)")
-        if not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and 0 < threshold <= 1):
-            raise ValueError(f"diff_mask: threshold {threshold!r} must be in (0, 1]")
-        if not (isinstance(grow, int) and not isinstance(grow, bool) and grow >= 0):
-            raise ValueError(f"diff_mask: grow {grow!r} must be a non-negative integer")
+        _check_region("diff_mask", threshold, grow)
         if kind not in ops.DIVERGENCE_KINDS:
             raise ValueError(f"diff_mask: kind {kind!r} is neither 'tv' nor 'jeffreys'")
-        if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[2] != self.image_size or img.shape[3] != self.image_size:
-            raise ValueError(f"diff_mask: img must be [B, C, {self.image_size}, {self.image_size}], got "
-                             f"{tuple(img.shape) if isinstance(img, torch.Tensor) else type(img).__name__}")
+        self._check_img("diff_mask", img)
         if text is None or edit_text is None:
             raise ValueError("diff_mask needs a text condition on both sides (the caption and what it should become)")
         B, N, V = img.shape[0], self.num_tokens, self.mask_token_id
@@ -617,33 +648,17 @@ class Pipeline(nn.Module):
         if lens_src is not None or lens_edit is not None:
             lens = (ops.host_lens([L] * B if lens_src is None else lens_src, B, L, "context_lens") +
                     ops.host_lens([L] * B if lens_edit is None else lens_edit, B, L, "edit_context_lens"))
-        ids = self.to_latent(img)[1].reshape(B, N)
-        if self._on_cpu():
-            context = torch.cat((ctx_src, ctx_edit)).float()
-            keys = self._host_keys(context, 2 * B, lens)
-            acc, count = torch.zeros(B, N), torch.zeros(B, N)
-            for m in masks:
-                masked = torch.where(m, torch.full_like(ids, V), ids)
-                logits = self._logits(self.ids2tokens(torch.cat((masked, masked))), context, keys)
-                acc += torch.where(m, self._divergence_cpu(logits[:B], logits[B:], kind), torch.zeros(B, N))
-                count += m
-            score = acc / count
-            mask = self._region_cpu(score, score, g, threshold, grow)
-        else:
-            eng = self.engine()
-            dev = eng.device
-            context = torch.cat((ctx_src.to(dev), ctx_edit.to(dev))).contiguous()
-            keys = self._host_keys(context, 2 * B, lens)
-            ids = ids.to(dev, torch.long)
-            acc, count = torch.zeros(B * N, device=dev, dtype=torch.float32), torch.zeros(B * N, device=dev, dtype=torch.int32)
-            for m in masks:
-                masked = torch.where(m.to(dev), torch.full_like(ids, V), ids).contiguous()
-                logits = eng.forward(self.ids2tokens(torch.cat((masked, masked))), context, keys=keys).reshape(2 * B * N, -1)
-                ops.logit_divergence(logits[:B * N], logits[B * N:], ids=masked.reshape(-1), mask_id=V, kind=kind, out=(acc, count),
-                                     accumulate=True)
-            score = (acc / count).reshape(B, N)
-            mask = ops.phrase_region(score, score, g, float(threshold), grow) != 0
-        mask = (mask & (score.amax(dim=1, keepdim=True) > 0)).reshape(B, g, g)      # (a maximum of 0: >= 0 would select everything)
+        st = self._steps()
+        ids = st.ids(self.to_latent(img)[1].reshape(B, N))
+        context = st.context(torch.cat((ctx_src.to(st.device), ctx_edit.to(st.device))).float())
+        keys = self._host_keys(context, 2 * B, lens)
+        acc = st.divergence_start(B, N)
+        for m in masks:
+            m = m.to(st.device)
+            masked = torch.where(m, torch.full_like(ids, V), ids)
+            st.divergence_add(acc, st.forward(self.ids2tokens(torch.cat((masked, masked))), context, keys), m, masked, kind)
+        score = st.divergence_finish(acc)
+        mask = self._score_mask(st, score, g, threshold, grow).reshape(B, g, g)
         return (mask, score.reshape(B, g, g)) if return_score else mask
 
     # ------------------------------------------------------------------------------------------------ model likelihood (section 4zg)
@@ -672,9 +687,7 @@ class Pipeline(nn.Module):
             raise ValueError(f"{who}: give exactly one of img and ids")
         N = self.num_tokens
         if img is not None:
-            if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[2] != self.image_size or img.shape[3] != self.image_size:
-                raise ValueError(f"{who}: img must be [B, C, {self.image_size}, {self.image_size}], got "
-                                 f"{tuple(img.shape) if isinstance(img, torch.Tensor) else type(img).__name__}")
+            self._check_img(who, img)
             ids = self.to_latent(img)[1].reshape(img.shape[0], N)
         else:
             if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.dim() < 2 or ids[0].numel() != N:
@@ -687,8 +700,7 @@ class Pipeline(nn.Module):
                 raise ValueError(f"{who}: ids: image {b}, token {i}: {int(ids[b, i])} is neither a code nor the mask id {self.mask_token_id}")
         B = ids.shape[0]
         if guidance_scale is not None:
-            if isinstance(guidance_scale, bool) or not isinstance(guidance_scale, (int, float)) or not math.isfinite(guidance_scale):
-                raise ValueError(f"{who}: guidance_scale {guidance_scale!r} must be one finite number (a schedule belongs to a decode loop)")
+            _finite_number(who, "guidance_scale", guidance_scale, " (a schedule belongs to a decode loop)")
             if text is None:
                 raise ValueError(f"{who}: guidance_scale needs a text condition (text=None IS the unconditional branch)")
         if text is None:
@@ -701,40 +713,18 @@ class Pipeline(nn.Module):
     def _token_scores(self, ids, context, lens, masks, scale):
         """the rule of ``token_scores`` behind its checks: ids int64 [B, N], masks bool [draws, B, N] (CPU) -> (logp, entropy, rank) f32
         [B, N] on the pipeline's device, each acc / count (NaN = 0 / 0 where the id is the mask id: such a position is never scored)"""
-        B, N, V = ids.shape[0], self.num_tokens, self.mask_token_id
-        if self._on_cpu():
-            ids = ids.cpu()
-            context = None if context is None else context.float()
-            keys, nokeys = self._host_keys(context, B, lens), self._host_keys(None, B)
-            acc = [torch.zeros(B, N) for _ in range(3)]
-            count = torch.zeros(B, N)
-            known = ids != V                                   # (a position that holds the mask id has no true id: never scored)
-            target = torch.where(known, ids, torch.zeros_like(ids))
-            for m in masks:
-                tok = self.ids2tokens(torch.where(m, torch.full_like(ids, V), ids))
-                x = self._logits(tok, context, keys)
-                if scale is not None:
-                    uncond = self._logits(tok, None, nokeys)
-                    x = torch.addcmul(uncond, x - uncond, torch.tensor(scale))
-                for a, v in zip(acc, self._token_logprob_cpu(x, target)):
-                    a += torch.where(m & known, v.float(), torch.zeros(B, N))
-                count += m & known
-            return tuple(a / count for a in acc)
-        eng = self.engine()
-        dev = eng.device
-        context = None if context is None else context.to(dev).contiguous()
+        B, V = ids.shape[0], self.mask_token_id
+        st = self._steps()
+        ids, context = st.ids(ids), st.context(None if context is None else context.float())
         keys, nokeys = self._host_keys(context, B, lens), self._host_keys(None, B)
-        ids = ids.to(dev, torch.long).contiguous()
-        out = (torch.zeros(B * N, device=dev), torch.zeros(B * N, device=dev), torch.zeros(B * N, device=dev, dtype=torch.int32),
-               torch.zeros(B * N, device=dev, dtype=torch.int32))
+        acc = st.logprob_start(ids)
         for m in masks:
-            masked = torch.where(m.to(dev), torch.full_like(ids, V), ids).contiguous()
+            m = m.to(st.device)
+            masked = torch.where(m, torch.full_like(ids, V), ids)
             tok = self.ids2tokens(masked)
-            x = eng.forward(tok, context, keys=keys).reshape(B * N, -1)
-            uncond = None if scale is None else eng.forward(tok, None, keys=nokeys).reshape(B * N, -1)
-            ops.token_logprob(x, ids.reshape(-1), uncond=uncond, scale=scale, ids=masked.reshape(-1), mask_id=V, out=out, accumulate=True)
-        count = out[3].float()
-        return tuple((a.float() / count).reshape(B, N) for a in out[:3])
+            x = st.forward(tok, context, keys)
+            st.logprob_add(acc, x, None if scale is None else st.forward(tok, None, nokeys), scale, m, masked)
+        return st.logprob_finish(acc)
 
     @torch.no_grad()
     def token_scores(self, img=None, text=None, *, ids=None, mask_ratio=0.5, draws=4, seed=0, guidance_scale=None, mask_padding=False,
@@ -794,20 +784,13 @@ class Pipeline(nn.Module):
         -> bool [B, g, g] on the pipeline's device: what ``edit(token_mask=)`` and ``prompt_to_prompt(blend_mask=)`` take; with
         ``return_score`` (mask, s f32 [B, g, g]).  The repair of what does not fit is the composition
         ``edit(img, token_mask=surprise_mask(img, text), text=text)``.  The defaults are defaults, not optima measured on this tower."""
-        if not (isinstance(threshold, (int, float)) and not isinstance(threshold, bool) and 0 < threshold <= 1):
-            raise ValueError(f"surprise_mask: threshold {threshold!r} must be in (0, 1]")
-        if not (isinstance(grow, int) and not isinstance(grow, bool) and grow >= 0):
-            raise ValueError(f"surprise_mask: grow {grow!r} must be a non-negative integer")
+        _check_region("surprise_mask", threshold, grow)
         if "ids" in token_scores_keywords:
             raise ValueError("surprise_mask: the mask is one of an image: pass img")
         s = -self.token_scores(img, text, **token_scores_keywords).logp
         B, g = s.shape[0], s.shape[1]
         s = s.reshape(B, g * g).contiguous()
-        if self._on_cpu():
-            mask = self._region_cpu(s, s, g, threshold, grow)
-        else:
-            mask = ops.phrase_region(s, s, g, float(threshold), grow) != 0
-        mask = (mask & (s.amax(dim=1, keepdim=True) > 0)).reshape(B, g, g)          # (a maximum of 0: >= 0 would select everything)
+        mask = self._score_mask(self._steps(), s, g, threshold, grow).reshape(B, g, g)
         return (mask, s.reshape(B, g, g)) if return_score else mask
 
     @torch.no_grad()
@@ -843,9 +826,7 @@ class Pipeline(nn.Module):
             raise ValueError(f"best_of: image_base {image_base!r} must be a non-negative integer")
         B = len(text)
         diff_draws(B, self.num_tokens, score_mask_ratio, score_draws, score_seed)       # the scoring keywords, checked before any loop runs
-        if score_guidance is not None and (isinstance(score_guidance, bool) or not isinstance(score_guidance, (int, float))
-                                           or not math.isfinite(score_guidance)):
-            raise ValueError(f"best_of: score_guidance {score_guidance!r} must be one finite number")
+        _finite_number("best_of", "score_guidance", score_guidance)
         if mask_padding:
             context, lens = self.text_model(list(text), return_lens=True)
         else:
@@ -1056,36 +1037,22 @@ class Pipeline(nn.Module):
         -> ids [B, N]: target_ids except at the nmask[T-1] positions per image still masked.  return_steps: (ids, revealed_at), int64
         [B, N], the first step after which the position is unmasked (T: still masked at the end)."""
         T, N = int(timesteps), self.num_tokens
-        cpu = self._on_cpu()
-        dev = self.mask_token.device if cpu else self.engine().device
-        target = self._source_ids(target_ids, B, "forced_ids").to(dev).contiguous()
-        if guidance_scale is not None and np.ndim(guidance_scale) > 0:
-            raise ValueError("forced_ids: guidance_scale is one number (a schedule is not served)")
+        st = self._steps()
+        target = st.ids(self._source_ids(target_ids, B, "forced_ids"))
+        _no_schedule("forced_ids", guidance_scale)
         opts = self._options(1, None, guidance_scale, context_lens, choice_temperature, context, B)
         keys = self._keys(context, B, opts)
         _, nmask, ctemps = loop_schedule(T, 1.0, N, opts.choice_temperature)
-        if context is not None:
-            context = context.to(dev)
-        ids = torch.full((B, N), self.mask_token_id, dtype=torch.long, device=dev)
-        revealed_at = torch.full((B, N), T, dtype=torch.long, device=dev)
+        context = st.context(context)
+        ids = torch.full((B, N), self.mask_token_id, dtype=torch.long, device=st.device)
+        revealed_at = torch.full((B, N), T, dtype=torch.long, device=st.device)
         for step in range(T):
             tok = self.ids2tokens(ids)
-            ct = ctemps[step] if ctemps else 0.0
-            if cpu:
-                logits = self._logits(tok, context, keys)
-                if opts.guidance_scale is not None:
-                    uncond = self._logits(tok, None)
-                    logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(opts.guidance_scale)))
-                _, merged, score, g = self._forced_cpu(ids, logits, target, None, None if seed is None else seed + step)
-                ids = self._remask_cpu(merged, score, nmask[step], g, ct, None, [nmask[step]] * B)
-            else:
-                eng = self.engine()
-                logits = eng.forward(tok, context, keys=keys)
-                if opts.guidance_scale is not None:
-                    logits = ops.guidance_combine(logits, eng.forward(tok, None), opts.guidance_scale, out=logits)
-                _, merged, score = ops.sample_rows_forced(logits.reshape(B * N, -1), ids.reshape(-1), target.reshape(-1), self.mask_token_id)
-                ids = ops.remask(merged.reshape(B, N), score.reshape(B, N), nmask[step], self.mask_token_id, choice_temperature=ct, seed=seed,
-                                 step=step, row_base=image_base * N)
+            logits = st.forward(tok, context, keys)
+            if opts.guidance_scale is not None:
+                logits = st.guide(logits, st.forward(tok, None, None), opts.guidance_scale)
+            draw = st.forced(ids, logits, target, None, seed, step)
+            ids = st.remask(draw, nmask[step], ctemps[step] if ctemps else 0.0, seed, step, image_base)
             if return_steps:
                 revealed_at = torch.where((ids != self.mask_token_id) & (revealed_at == T), torch.full_like(revealed_at, step), revealed_at)
         return (ids, revealed_at) if return_steps else ids
@@ -1356,8 +1323,7 @@ class Pipeline(nn.Module):
         if context_src is None or context_edit is None or tuple(context_src.shape) != tuple(context_edit.shape) or context_src.dim() != 3 \
                 or context_src.shape[0] != B:
             raise ValueError(f"control_ids: context_src and context_edit must be two context tensors [{B}, L, D] of one shape")
-        if guidance_scale is not None and np.ndim(guidance_scale) > 0:
-            raise ValueError("control_ids: guidance_scale is one number (a schedule is not served)")
+        _no_schedule("control_ids", guidance_scale)
         if (lens_src is None) != (lens_edit is None):
             raise ValueError("control_ids: lens_src and lens_edit come together")
         L, T = context_src.shape[1], int(timesteps)
@@ -1373,8 +1339,7 @@ class Pipeline(nn.Module):
                 raise ValueError(f"control_ids: {name}={f} must be a fraction in [0, 1]")
         n_cross, n_self = math.ceil(float(cross_steps) * T), math.ceil(float(self_steps) * T)
         temps, nmask, ctemps = loop_schedule(T, temperature, self.num_tokens, opts.choice_temperature)
-        cpu = self._on_cpu()
-        dev = self.mask_token.device if cpu else self.engine().device
+        st = self._steps()
         N = self.num_tokens
         g = self.image_size // self.patch_size
         if blend_rows is not None and blend_mask is not None:
@@ -1384,10 +1349,7 @@ class Pipeline(nn.Module):
             raise ValueError("control_ids: return_mask needs blend_rows or blend_mask")
         region, scores, blend_from = None, None, T
         if blending:
-            if not (isinstance(blend_threshold, (int, float)) and 0 < blend_threshold <= 1):
-                raise ValueError(f"control_ids: blend_threshold {blend_threshold!r} must be in (0, 1]")
-            if not (isinstance(blend_grow, int) and blend_grow >= 0):
-                raise ValueError(f"control_ids: blend_grow {blend_grow!r} must be a non-negative integer")
+            _check_region("control_ids", blend_threshold, blend_grow, bools=True, prefix="blend_")
             if not 0.0 <= float(blend_start) < 1.0:
                 raise ValueError(f"control_ids: blend_start={blend_start} must be a fraction in [0, 1) (the last step always blends)")
             if g * g != N or g > 64:
@@ -1400,74 +1362,37 @@ class Pipeline(nn.Module):
             region = torch.as_tensor(blend_mask)
             if region.dtype != torch.bool or tuple(region.shape) != (B, g, g):
                 raise ValueError(f"control_ids: blend_mask must be a bool tensor [{B}, {g}, {g}], got {region.dtype} {tuple(region.shape)}")
-            region = region.reshape(B, N).to(dev) if cpu else region.reshape(B, N).to(dev, torch.uint8).contiguous()
-        context = context.to(dev)
-        ids = torch.full((2 * B, N), self.mask_token_id, dtype=torch.long, device=dev)
+            region = st.drawn_region(region.reshape(B, N))
+        context = st.context(context)
+        ids = torch.full((2 * B, N), self.mask_token_id, dtype=torch.long, device=st.device)
         imgs = [None, None]
         if noise is not None and tuple(noise.shape) != (T, B, N, self.mask_token_id):
             raise ValueError(f"control_ids: noise must be a tensor [{T}, {B}, {N}, {self.mask_token_id}], got {tuple(noise.shape)}")
         if source_ids is not None:
-            source_ids = self._source_ids(source_ids, B, "control_ids").to(dev).contiguous()
+            source_ids = st.ids(self._source_ids(source_ids, B, "control_ids"))
         for step in range(T):
-            last = want_imgs and step == T - 1
             cross = layers if step < n_cross else []
             inject = layers if step < n_self else []
             ctl = dict(row_map=rm, blend=bl, gain=gn) if cross else {}
-            tok = self.ids2tokens(ids)
-            ct = ctemps[step] if ctemps else 0.0
             tap = {} if blend_rows is None else dict(score_layers=layers, score_weights=blend_rows, scores=scores)
-            blend_now = blending and step >= blend_from
-            if cpu:
-                if cross or inject or tap:
-                    logits = self.transformer(tok, context, keys=keys, control=dict(cross_layers=cross, self_layers=inject, **ctl, **tap))
-                    if tap:
-                        logits, scores = logits
-                else:
-                    logits = self._logits(tok, context, keys)
-                if opts.guidance_scale is not None:
-                    uncond = self._logits(tok, None)
-                    logits = torch.addcmul(uncond, logits - uncond, torch.tensor(float(opts.guidance_scale)))
-                draws = [self._draw_cpu(ids[h * B:(h + 1) * B], logits[h * B:(h + 1) * B], opts.topk, temps[step],
-                                        None if noise is None else noise[step], None if seed is None else seed + step, opts.top_p)
-                         if h or source_ids is None else
-                         self._forced_cpu(ids[:B], logits[:B], source_ids, None if noise is None else noise[step], None if seed is None else seed + step)
-                         for h in range(2)]
-                if blend_now:
-                    if blend_rows is not None:
-                        region = self._region_cpu(scores[:B], scores[B:], g, blend_threshold, blend_grow)
-                    draws[1] = self._blend_cpu(region, draws[0][:3], draws[1][:3]) + (draws[1][3],)
-                if last:
-                    imgs = [self.vqgan.decode_from_indice(d[0]) for d in draws]
-                ids = torch.cat([self._remask_cpu(d[1], d[2], nmask[step], d[3], ct, None, [nmask[step]] * B) for d in draws])
-                continue
-            eng = self.engine()
-            if tap:
-                logits, scores = eng.forward_control(tok, context, cross_layers=cross, self_layers=inject, context_lens=keys.lens, **ctl, **tap)
-            elif cross or inject:
-                logits = eng.forward_control(tok, context, cross_layers=cross, self_layers=inject, context_lens=keys.lens, **ctl)
+            tok = self.ids2tokens(ids)
+            if cross or inject or tap:
+                logits, scores = st.forward_control(tok, context, keys, cross, inject, ctl, tap)
             else:
-                logits = eng.forward(tok, context, keys=keys)
+                logits = st.forward(tok, context, keys)
             if opts.guidance_scale is not None:
-                logits = ops.guidance_combine(logits, eng.forward(tok, None), opts.guidance_scale, out=logits)
-            draws = []
-            for h in range(2):
-                rows = slice(h * B * N, (h + 1) * B * N)
-                if h == 0 and source_ids is not None:
-                    draws.append(ops.sample_rows_forced(logits.reshape(2 * B * N, -1)[rows], ids.reshape(-1)[rows], source_ids.reshape(-1),
-                                                        self.mask_token_id))
-                    continue
-                draws.append(ops.sample_rows(logits.reshape(2 * B * N, -1)[rows], ids.reshape(-1)[rows], self.mask_token_id, opts.topk,
-                                             temps[step], seed=seed, step=step, row_base=image_base * N, top_p=opts.top_p,
-                                             noise=None if noise is None else noise[step].to(dev, torch.float32).reshape(B * N, -1).contiguous()))
-            if blend_now:
+                logits = st.guide(logits, st.forward(tok, None, None), opts.guidance_scale)        # (that pass is never controlled or tapped)
+            u = None if noise is None else noise[step]
+            draws = [st.draw(ids[h * B:(h + 1) * B], logits[h * B:(h + 1) * B], opts, temps[step], u, seed, step, image_base)
+                     if h or source_ids is None else st.forced(ids[:B], logits[:B], source_ids, u, seed, step) for h in range(2)]
+            if blending and step >= blend_from:
                 if blend_rows is not None:
-                    region = ops.phrase_region(scores[:B], scores[B:], g, blend_threshold, blend_grow)
-                ops.blend_tokens(region, *draws[0], *draws[1])
-            for h, (pred, merged, score) in enumerate(draws):
-                ids[h * B:(h + 1) * B] = ops.remask(merged.reshape(B, N), score.reshape(B, N), nmask[step], self.mask_token_id,
-                                                    choice_temperature=ct, seed=seed, step=step, row_base=image_base * N)
-                if last:
-                    imgs[h] = self.vqgan.decode_from_indice(pred.reshape(B, N))
+                    region = st.region(scores[:B], scores[B:], g, blend_threshold, blend_grow)
+                draws[1] = st.blend(region, draws[0], draws[1])
+            for h, d in enumerate(draws):                    # per half: the re-masking, then on the last step the image from ALL predictions
+                ids[h * B:(h + 1) * B] = st.remask(d, nmask[step], ctemps[step] if ctemps else 0.0, seed, step, image_base)
+                if want_imgs and step == T - 1:
+                    imgs[h] = self.vqgan.decode_from_indice(d.pred.reshape(B, N))
         out = (ids[:B].clone(), ids[B:].clone()) + ((imgs[0], imgs[1]) if want_imgs else ())
         return out + ((region != 0).reshape(B, g, g),) if return_mask else out
 
@@ -1502,8 +1427,7 @@ class Pipeline(nn.Module):
         if refused:
             raise ValueError(f"prompt_to_prompt does not serve {sorted(refused)} (negative prompts, regions, prompt weights and the segment "
                              f"arrays stand beside no attention control)")
-        if guidance_scale is not None and np.ndim(guidance_scale) > 0:
-            raise ValueError("prompt_to_prompt: guidance_scale is one number (a schedule is not served)")
+        _no_schedule("prompt_to_prompt", guidance_scale)
         if getattr(self, "text_model", None) is None or text is None or edit_text is None:
             raise ValueError("prompt_to_prompt needs a text condition (an unconditional pipeline has no cross-attention to control)")
         if not hasattr(self.text_model, "fragment_ids"):
@@ -1549,11 +1473,7 @@ class Pipeline(nn.Module):
         if img is not None and source_ids is not None:
             raise ValueError("prompt_to_prompt: img and source_ids exclude each other (the image, or its tokens)")
         if img is not None:
-            if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[0] != B:
-                raise ValueError(f"prompt_to_prompt: img must be [{B}, C, H, W] (one image per prompt), got "
-                                 f"{tuple(img.shape) if isinstance(img, torch.Tensor) else type(img).__name__}")
-            if img.shape[2] != self.image_size or img.shape[3] != self.image_size:
-                raise ValueError(f"prompt_to_prompt: img must be {self.image_size} x {self.image_size}, got {img.shape[2]} x {img.shape[3]}")
+            self._check_img("prompt_to_prompt", img, B)
             source_ids = self.to_latent(img)[1].reshape(B, self.num_tokens).to(torch.long)
         elif source_ids is not None:
             if not isinstance(source_ids, torch.Tensor) or source_ids.dim() != 2 or source_ids.shape[0] != B:
