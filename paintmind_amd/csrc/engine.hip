@@ -1169,19 +1169,65 @@ int check_slot_weights(const char* who, int b, const float* ctx_w_host, const ui
     return PMHIP_OK;
 }
 
+// The two records every decode family's call carries (the native twins of ops.Keys and of its negative set).  Absent features sit
+// at their neutral values; an entry assigns the fields its own signature has.
+struct CtxKeys {                                              // what says which context rows a token attends to
+    const float* context = nullptr; int L = 0;                // [B, L, context_dim], or NULL: the unconditional branch
+    const int32_t* lens = nullptr;                            // host [B] (the *_lens entries)
+    const uint8_t* seg = nullptr; const uint32_t* tok = nullptr;   // host uint8 [B, L] and uint32 [B, tokens] (the *_segments entries)
+    const float* w = nullptr;                                 // host f32 [B, L] (the *_weights entries)
+    CtxKeys(const float* context_, int L_) : context(context_), L(L_) {}
+};
+struct NegSet {                                               // the negative context (the *_negative entries) with its host lengths [B]
+    const float* context = nullptr; int Ln = 0; const int32_t* lens = nullptr;
+};
+
 // The negative context of the *_negative entries, checked BEFORE anything is launched (who: the entry family).  It and a guidance
 // schedule need guidance and a context; Ln >= 1; 1 <= neg_len_b <= Ln; lengths need the negative context they are about.
-int check_negative(const char* who, const float* neg_context, int Ln, const int32_t* neg_lens_host, bool schedule, bool guided,
-                   bool have_context, int B) {
-    PM_REQUIRE(neg_context || !neg_lens_host, "%s: neg_lens_host given without a negative context", who);
-    if (!neg_context && !schedule) return PMHIP_OK;
+int check_negative(const char* who, const NegSet& neg, bool schedule, bool guided, bool have_context, int B) {
+    PM_REQUIRE(neg.context || !neg.lens, "%s: neg_lens_host given without a negative context", who);
+    if (!neg.context && !schedule) return PMHIP_OK;
     PM_REQUIRE(guided && have_context, "%s: a negative context or a guidance schedule needs guidance (guided != 0) and a context", who);
-    if (!neg_context) return PMHIP_OK;
-    PM_REQUIRE(Ln >= 1, "%s: negative context given with Ln=%d", who, Ln);
-    for (int b = 0; neg_lens_host && b < B; ++b)
-        PM_REQUIRE(neg_lens_host[b] >= 1 && neg_lens_host[b] <= Ln, "%s: image %d: negative context length %d must be in [1, Ln=%d]", who, b,
-                   (int)neg_lens_host[b], Ln);
+    if (!neg.context) return PMHIP_OK;
+    PM_REQUIRE(neg.Ln >= 1, "%s: negative context given with Ln=%d", who, neg.Ln);
+    for (int b = 0; neg.lens && b < B; ++b)
+        PM_REQUIRE(neg.lens[b] >= 1 && neg.lens[b] <= neg.Ln, "%s: image %d: negative context length %d must be in [1, Ln=%d]", who, b,
+                   (int)neg.lens[b], neg.Ln);
     return PMHIP_OK;
+}
+
+// The context sequence of every model-level entry but the slots step (which keeps contexts and stages neutral rows: slots_context),
+// in its two halves.  check_context: the three host checks of the key set, BEFORE anything is launched, yielding what is staged.
+// (The negative set's own check, check_negative, stands earlier in the sample and generate families' order and carries a name of
+// its own, so it stays a call of theirs.)
+int check_context(const char* who, const CtxKeys& k, int B, const pmhip_s2* h, CtxWeights& cw) {
+    PM_TRY(check_ctx_lens(who, k.lens, k.context != nullptr, k.L, B));
+    PM_TRY(check_segments(who, k.seg, k.tok, k.lens, k.context != nullptr, k.L, B, h));
+    return check_weights(who, k.w, k.seg, k.tok, k.lens, k.context != nullptr, k.L, B, h, cw);
+}
+
+// stage_context: the context's set prepared (or dropped, which drops the negative set of an earlier call too), its lengths, segments
+// and weights staged -- the context's set only: the other passes never see segments or weights -- and behind it the negative set of
+// a call that brings one.  Eager, outside any graph: once per call or loop.
+int stage_context(pmhip_s2* h, const CtxKeys& k, const CtxWeights& cw, const NegSet& neg, int B, hipStream_t s) {
+    PM_TRY(s2_prepare_context(h, k.context, k.L, B, s));
+    PM_TRY(s2_set_ctx_lens(h, cw.lens, k.L, B, s));
+    PM_TRY(s2_set_segments(h, cw.seg, cw.tok, k.L, B, s));
+    PM_TRY(s2_set_weights(h, cw.w, k.L, B, s));
+    if (neg.context) {
+        PM_TRY(s2_prepare_context(h, neg.context, neg.Ln, B, s, kCrossNegative));
+        PM_TRY(s2_set_ctx_lens(h, neg.lens, neg.Ln, B, s, kCrossNegative));
+    }
+    return PMHIP_OK;
+}
+
+// The name a call's messages carry, written once: the first arm whose feature is present names the call, widest feature first,
+// otherwise the fallback (the caller's narrow name) -- the shape of S2Engine._call in engine.py.
+struct NameArm { bool present; const char* name; };
+const char* call_name(std::initializer_list<NameArm> arms, const char* fallback) {
+    for (const NameArm& a : arms)
+        if (a.present) return a.name;
+    return fallback;
 }
 
 // token rows (T [M,64]) -> logits fp32 [M,V]  (transformer.py:81-82,87-91)
@@ -1465,28 +1511,38 @@ int run_graphs(pmhip_s2* s2, pmhip_vqgan* vq, GraphEntry& ge, size_t n_units, hi
 
 }  // namespace
 
-static int s2_forward_impl(const char* who, pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
-                           float* logits_out, pmhip_stream stream, const uint8_t* ctx_seg_host = nullptr,
-                           const uint32_t* tok_seg_host = nullptr, const float* ctx_w_host = nullptr, uint64_t layer_bits = 0,
-                           float* maps_out = nullptr) {
-    PM_REQUIRE(h && tokens && logits_out && B > 0, "%s: bad arguments", who);
+namespace {
+// One eager forward: the record the pmhip_s2_forward_* entries fill.  `who` is the entry's narrow name; maps_out / layer_bits are the
+// maps tap of pmhip_s2_forward_maps.
+struct ForwardCall {
+    const char* who; pmhip_s2* h; const float* tokens; CtxKeys keys; int B; float* logits_out; pmhip_stream stream;
+    uint64_t layer_bits = 0; float* maps_out = nullptr;
+    ForwardCall(const char* who_, pmhip_s2* h_, const float* tokens_, const float* context, int L, int B_, float* logits_out_, pmhip_stream stream_)
+        : who(who_), h(h_), tokens(tokens_), keys(context, L), B(B_), logits_out(logits_out_), stream(stream_) {}
+};
+}  // namespace
+
+static int s2_forward_impl(const ForwardCall& c) {
+    pmhip_s2* h = c.h;
+    const int B = c.B;
+    float* const maps_out = c.maps_out;
+    const uint64_t layer_bits = c.layer_bits;
+    const char* who = c.who;
+    PM_REQUIRE(h && c.tokens && c.logits_out && B > 0, "%s: bad arguments", who);
     if (maps_out) {                                           // pmhip_s2_forward_maps: three checks of its own, before anything is launched
         const int depth = h->cfg.tower.depth;
-        PM_REQUIRE(context && L > 0, "%s: the maps are those of the cross-attention: a context is required", who);
+        PM_REQUIRE(c.keys.context && c.keys.L > 0, "%s: the maps are those of the cross-attention: a context is required", who);
         PM_REQUIRE(layer_bits != 0, "%s: layer_bits selects no layer", who);
         PM_REQUIRE(depth >= 64 || (layer_bits >> depth) == 0, "%s: layer_bits 0x%llx selects a layer at or above depth=%d", who,
                    (unsigned long long)layer_bits, depth);
     }
-    PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
-    PM_TRY(check_segments(who, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, h));
     CtxWeights cw;
-    PM_TRY(check_weights(who, ctx_w_host, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, h, cw));
-    hipStream_t s = (hipStream_t)stream;
+    PM_TRY(check_context(who, c.keys, B, h, cw));
+    hipStream_t s = (hipStream_t)c.stream;
     const int M = B * h->cfg.tokens;
-    PM_TRY(s2_prepare_context(h, context, L, B, s));
-    PM_TRY(s2_set_ctx_lens(h, cw.lens, L, B, s));
-    PM_TRY(s2_set_segments(h, cw.seg, cw.tok, L, B, s));
-    PM_TRY(s2_set_weights(h, cw.w, L, B, s));
+    PM_TRY(stage_context(h, c.keys, cw, NegSet{}, B, s));
+    const float* tokens = c.tokens;
+    float* logits_out = c.logits_out;
     void* tp;
     PM_TRY(tok_buf(h, M, tp, s));
     PM_TRY(pmhip_convert_pad(tokens, h->cfg.embed_dim, tp, h->dtype, 64, M, s));
@@ -1510,12 +1566,14 @@ static int s2_forward_impl(const char* who, pmhip_s2* h, const float* tokens, co
 
 extern "C" int pmhip_s2_forward(pmhip_s2* h, const float* tokens, const float* context, int L, int B, float* logits_out,
                                 pmhip_stream stream) {
-    return s2_forward_impl("s2_forward", h, tokens, context, L, B, nullptr, logits_out, stream);
+    return s2_forward_impl(ForwardCall("s2_forward", h, tokens, context, L, B, logits_out, stream));
 }
 
 extern "C" int pmhip_s2_forward_lens(pmhip_s2* h, const float* tokens, const float* context, int L, int B,
                                      const int32_t* ctx_lens_host, float* logits_out, pmhip_stream stream) {
-    return s2_forward_impl("s2_forward_lens", h, tokens, context, L, B, ctx_lens_host, logits_out, stream);
+    ForwardCall c("s2_forward_lens", h, tokens, context, L, B, logits_out, stream);
+    c.keys.lens = ctx_lens_host;
+    return s2_forward_impl(c);
 }
 
 // the handle's graph cache: keys it holds, and how many of them hold captured graphs (the first call under a key runs eagerly)
@@ -1528,27 +1586,39 @@ extern "C" int pmhip_s2_graph_count(const pmhip_s2* h, int* entries, int* captur
     return PMHIP_OK;
 }
 
+// the two entries above pmhip_s2_forward that take no lengths report under the widest key array that came, otherwise as s2_forward
+static const char* s2_forward_name(const CtxKeys& k) {
+    return call_name({{k.w != nullptr, "s2_forward_weights"}, {k.seg || k.tok, "s2_forward_segments"}}, "s2_forward");
+}
+
 // ctx_seg_host == NULL and tok_seg_host == NULL: exactly pmhip_s2_forward
 extern "C" int pmhip_s2_forward_segments(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const uint8_t* ctx_seg_host,
                                          const uint32_t* tok_seg_host, float* logits_out, pmhip_stream stream) {
-    return s2_forward_impl(ctx_seg_host || tok_seg_host ? "s2_forward_segments" : "s2_forward", h, tokens, context, L, B, nullptr, logits_out,
-                           stream, ctx_seg_host, tok_seg_host);
+    ForwardCall c("s2_forward", h, tokens, context, L, B, logits_out, stream);
+    c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host;
+    c.who = s2_forward_name(c.keys);
+    return s2_forward_impl(c);
 }
 
 // ctx_w_host == NULL: exactly pmhip_s2_forward_segments
 extern "C" int pmhip_s2_forward_weights(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const uint8_t* ctx_seg_host,
                                         const uint32_t* tok_seg_host, const float* ctx_w_host, float* logits_out, pmhip_stream stream) {
-    const char* who = ctx_w_host ? "s2_forward_weights" : ctx_seg_host || tok_seg_host ? "s2_forward_segments" : "s2_forward";
-    return s2_forward_impl(who, h, tokens, context, L, B, nullptr, logits_out, stream, ctx_seg_host, tok_seg_host, ctx_w_host);
+    ForwardCall c("s2_forward", h, tokens, context, L, B, logits_out, stream);
+    c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host; c.keys.w = ctx_w_host;
+    c.who = s2_forward_name(c.keys);
+    return s2_forward_impl(c);
 }
 
 // the logits of pmhip_s2_forward_weights / _lens on the same arguments, and the chosen layers' cross-attention maps beside them
+// (its messages carry its own name whatever key arrays came)
 extern "C" int pmhip_s2_forward_maps(pmhip_s2* h, const float* tokens, const float* context, int L, int B, const int32_t* ctx_lens_host,
                                      const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const float* ctx_w_host, uint64_t layer_bits,
                                      float* logits_out, float* maps_out, pmhip_stream stream) {
     PM_REQUIRE(maps_out, "s2_forward_maps: maps_out is NULL (pmhip_s2_forward_weights is the entry without maps)");
-    return s2_forward_impl("s2_forward_maps", h, tokens, context, L, B, ctx_lens_host, logits_out, stream, ctx_seg_host, tok_seg_host, ctx_w_host,
-                           layer_bits, maps_out);
+    ForwardCall c("s2_forward_maps", h, tokens, context, L, B, logits_out, stream);
+    c.keys.lens = ctx_lens_host; c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host; c.keys.w = ctx_w_host;
+    c.layer_bits = layer_bits; c.maps_out = maps_out;
+    return s2_forward_impl(c);
 }
 
 // One eager forward over B pairs: images [0, B) carry the source prompts, [B, 2B) the edited ones.  The layers of
@@ -1676,66 +1746,86 @@ extern "C" int pmhip_s2_forward_control_scores(pmhip_s2* h, const float* tokens,
                                    blend_host, gain_host, logits_out, stream, true, score_bits, w_src_host, w_edit_host, scores, accumulate);
 }
 
-// The sample family's one builder: the argument list of pmhip_pipeline_sample_nucleus, the widest entry, -> the Step and the name
-// the messages carry.  A narrower entry passes the neutral values (include/pmhip.h) and `narrow`, the name its messages carry when
-// neither a nucleus mass nor a choice temperature is in play: its own, or the *_lens entry's for the two entries above that one.
-static int pipeline_sample_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
-                                const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
-                                uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out, float* score_out, int guided,
-                                float guidance_scale, float choice_t, const float* choice_noise, float top_p, pmhip_stream stream,
-                                const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
-                                const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr,
-                                const float* ctx_w_host = nullptr) {
-    PM_TRY(pm_check_top_p("pipeline_sample_nucleus", top_p));
-    const char* wide = top_p != 1.f ? "pipeline_sample_nucleus" : "pipeline_sample_choice";
-    PM_TRY(pm_check_choice_t(wide, choice_t));
-    PM_TRY(check_negative("pipeline_sample_negative", neg_context, Ln, neg_lens_host, false, guided != 0, context && L > 0, B));
-    const char* who = ctx_w_host ? "pipeline_sample_weights" : ctx_seg_host || tok_seg_host ? "pipeline_sample_segments"
-                      : neg_context ? "pipeline_sample_negative" : top_p != 1.f || choice_t != 0.f ? wide : narrow;
-    Step st{topk, temperature, num_mask, noise, seed, step, image_base, nullptr, false, guided ? &guidance_scale : nullptr};
-    if (choice_t != 0.f) { st.choice_t = choice_t; st.choice_noise = choice_noise; }     // 0: no given uniforms to ignore
-    st.top_p = top_p;
-    st.negative = neg_context != nullptr;
-    PM_REQUIRE(s2 && ids && B > 0, "%s: bad arguments", who);
-    PM_REQUIRE(!st.guidance || (context && L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
-    PM_TRY(check_ctx_lens(who, ctx_lens_host, context != nullptr, L, B));
-    PM_TRY(check_segments(who, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, s2));
+namespace {
+// The sample family's call record: the common head of its eight entries by the constructor, every optional feature at its neutral
+// value (include/pmhip.h) until an entry assigns it.  `narrow` is the name the entry's messages carry when no wider feature is
+// present: its own, or the *_lens entry's for the entries above that one.
+struct SampleCall {
+    const char* narrow; pmhip_s2* s2; pmhip_vqgan* vq; int64_t* ids; CtxKeys keys; int B;
+    int topk; float temperature; int num_mask; const float* noise; uint64_t seed; uint32_t step; uint64_t image_base;
+    float* img_out; int64_t* pred_out; float* score_out; pmhip_stream stream;
+    int guided = 0; float guidance_scale = 0.f;
+    float choice_t = 0.f; const float* choice_noise = nullptr;
+    float top_p = 1.f;
+    NegSet neg;
+    SampleCall(const char* narrow_, pmhip_s2* s2_, pmhip_vqgan* vq_, int64_t* ids_, const float* context, int L, int B_, int topk_,
+               float temperature_, int num_mask_, const float* noise_, uint64_t seed_, uint32_t step_, uint64_t image_base_, float* img_out_,
+               int64_t* pred_out_, float* score_out_, pmhip_stream stream_)
+        : narrow(narrow_), s2(s2_), vq(vq_), ids(ids_), keys(context, L), B(B_), topk(topk_), temperature(temperature_), num_mask(num_mask_),
+          noise(noise_), seed(seed_), step(step_), image_base(image_base_), img_out(img_out_), pred_out(pred_out_), score_out(score_out_),
+          stream(stream_) {}
+};
+}  // namespace
+
+// The sample family's one builder: the record -> the checks, the context, the Step.
+static int pipeline_sample_call(const SampleCall& c) {
+    // (pm_check_top_p always reports under the nucleus entry's name)
+    PM_TRY(pm_check_top_p("pipeline_sample_nucleus", c.top_p));
+    // (the choice temperature's check: the nucleus entry's name when a mass came, the choice entry's otherwise)
+    PM_TRY(pm_check_choice_t(call_name({{c.top_p != 1.f, "pipeline_sample_nucleus"}}, "pipeline_sample_choice"), c.choice_t));
+    // (check_negative always reports under the negative entry's name)
+    const bool schedule = false;                              // (a single step has no guidance schedule)
+    PM_TRY(check_negative("pipeline_sample_negative", c.neg, schedule, c.guided != 0, c.keys.context && c.keys.L > 0, c.B));
+    // (the entries above *_lens pass that entry's name as `narrow`: they report as *_lens when no wider feature is present)
+    const char* who = call_name({{c.keys.w != nullptr, "pipeline_sample_weights"},
+                                 {c.keys.seg || c.keys.tok, "pipeline_sample_segments"},
+                                 {c.neg.context != nullptr, "pipeline_sample_negative"},
+                                 {c.top_p != 1.f, "pipeline_sample_nucleus"},
+                                 {c.choice_t != 0.f, "pipeline_sample_choice"}}, c.narrow);
+    Step st;
+    st.topk = c.topk; st.temperature = c.temperature; st.num_mask = c.num_mask; st.noise = c.noise;
+    st.seed = c.seed; st.step = c.step; st.image_base = c.image_base;
+    st.guidance = c.guided ? &c.guidance_scale : nullptr;
+    if (c.choice_t != 0.f) { st.choice_t = c.choice_t; st.choice_noise = c.choice_noise; }     // 0: no given uniforms to ignore
+    st.top_p = c.top_p;
+    st.negative = c.neg.context != nullptr;
+    PM_REQUIRE(c.s2 && c.ids && c.B > 0, "%s: bad arguments", who);
+    PM_REQUIRE(!st.guidance || (c.keys.context && c.keys.L > 0), "%s: guidance needs a context (context NULL IS the unconditional branch)", who);
     CtxWeights cw;
-    PM_TRY(check_weights(who, ctx_w_host, ctx_seg_host, tok_seg_host, ctx_lens_host, context != nullptr, L, B, s2, cw));
-    hipStream_t s = (hipStream_t)stream;
-    PM_TRY(s2_prepare_context(s2, context, L, B, s));         // (drops the negative set of an earlier call)
-    PM_TRY(s2_set_ctx_lens(s2, cw.lens, L, B, s));
-    PM_TRY(s2_set_segments(s2, cw.seg, cw.tok, L, B, s));     // the context's set only: the other passes never see segments
-    PM_TRY(s2_set_weights(s2, cw.w, L, B, s));                // ... or weights
-    if (neg_context) {
-        PM_TRY(s2_prepare_context(s2, neg_context, Ln, B, s, kCrossNegative));
-        PM_TRY(s2_set_ctx_lens(s2, neg_lens_host, Ln, B, s, kCrossNegative));
-    }
-    return sample_step(s2, vq, ids, B, st, img_out, pred_out, score_out, s);
+    PM_TRY(check_context(who, c.keys, c.B, c.s2, cw));
+    hipStream_t s = (hipStream_t)c.stream;
+    PM_TRY(stage_context(c.s2, c.keys, cw, c.neg, c.B, s));
+    return sample_step(c.s2, c.vq, c.ids, c.B, st, c.img_out, c.pred_out, c.score_out, s);
 }
 
 extern "C" int pmhip_pipeline_sample(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                      int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                      uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                      float* score_out, pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample", s2, vq, ids, context, L, B, nullptr, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, 0, 0.f, 0.f, nullptr, 1.f, stream);
+    SampleCall c("pipeline_sample", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    return pipeline_sample_call(c);
 }
 
 extern "C" int pmhip_pipeline_sample_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                             int topk, float temperature, int num_mask, const float* noise, uint64_t seed,
                                             uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                             float* score_out, float guidance_scale, pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample_guided", s2, vq, ids, context, L, B, nullptr, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, 1, guidance_scale, 0.f, nullptr, 1.f, stream);
+    SampleCall c("pipeline_sample_guided", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    c.guided = 1; c.guidance_scale = guidance_scale;
+    return pipeline_sample_call(c);
 }
 
 extern "C" int pmhip_pipeline_sample_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                           const int32_t* ctx_lens_host, int topk, float temperature, int num_mask, const float* noise,
                                           uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                           float* score_out, int guided, float guidance_scale, pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, guided, guidance_scale, 0.f, nullptr, 1.f, stream);
+    SampleCall c("pipeline_sample_lens", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    return pipeline_sample_call(c);
 }
 
 // choice_t == 0: exactly pmhip_pipeline_sample_lens
@@ -1744,8 +1834,12 @@ extern "C" int pmhip_pipeline_sample_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64
                                             uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                             float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
                                             pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, 1.f, stream);
+    SampleCall c("pipeline_sample_lens", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.choice_t = choice_t; c.choice_noise = choice_noise;
+    return pipeline_sample_call(c);
 }
 
 // top_p == 1: exactly pmhip_pipeline_sample_choice
@@ -1754,8 +1848,13 @@ extern "C" int pmhip_pipeline_sample_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, int6
                                              uint64_t seed, uint32_t step, uint64_t image_base, float* img_out, int64_t* pred_out,
                                              float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
                                              float top_p, pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream);
+    SampleCall c("pipeline_sample_lens", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.choice_t = choice_t; c.choice_noise = choice_noise;
+    c.top_p = top_p;
+    return pipeline_sample_call(c);
 }
 
 // neg_context == NULL: exactly pmhip_pipeline_sample_nucleus
@@ -1765,9 +1864,14 @@ extern "C" int pmhip_pipeline_sample_negative(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
                                               float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                               pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream,
-                                neg_context, Ln, neg_lens_host);
+    SampleCall c("pipeline_sample_lens", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.choice_t = choice_t; c.choice_noise = choice_noise;
+    c.top_p = top_p;
+    c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    return pipeline_sample_call(c);
 }
 
 // ctx_seg_host == NULL and tok_seg_host == NULL: exactly pmhip_pipeline_sample_negative
@@ -1777,9 +1881,14 @@ extern "C" int pmhip_pipeline_sample_segments(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               float* score_out, int guided, float guidance_scale, float choice_t, const float* choice_noise,
                                               float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                               const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream,
-                                neg_context, Ln, neg_lens_host, ctx_seg_host, tok_seg_host);
+    SampleCall c("pipeline_sample_lens", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    c.keys.lens = ctx_lens_host; c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.choice_t = choice_t; c.choice_noise = choice_noise;
+    c.top_p = top_p;
+    c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    return pipeline_sample_call(c);
 }
 
 // ctx_w_host == NULL: exactly pmhip_pipeline_sample_segments
@@ -1790,9 +1899,14 @@ extern "C" int pmhip_pipeline_sample_weights(pmhip_s2* s2, pmhip_vqgan* vq, int6
                                              float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                              const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host, const float* ctx_w_host,
                                              pmhip_stream stream) {
-    return pipeline_sample_call("pipeline_sample_lens", s2, vq, ids, context, L, B, ctx_lens_host, topk, temperature, num_mask, noise, seed, step,
-                                image_base, img_out, pred_out, score_out, guided, guidance_scale, choice_t, choice_noise, top_p, stream,
-                                neg_context, Ln, neg_lens_host, ctx_seg_host, tok_seg_host, ctx_w_host);
+    SampleCall c("pipeline_sample_lens", s2, vq, ids, context, L, B, topk, temperature, num_mask, noise, seed, step, image_base, img_out, pred_out,
+                 score_out, stream);
+    c.keys.lens = ctx_lens_host; c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host; c.keys.w = ctx_w_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.choice_t = choice_t; c.choice_noise = choice_noise;
+    c.top_p = top_p;
+    c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    return pipeline_sample_call(c);
 }
 
 // process-wide: the runtime reads AMD_DIRECT_DISPATCH once when it starts, so does this
@@ -1803,29 +1917,32 @@ static bool direct_dispatch_off() {
 
 namespace {
 
-// the arguments of pmhip_pipeline_generate_nucleus, include/pmhip.h, as pipeline_generate_call (below) fills them in
+// The generate family's call record: the common head of its nine entries by the constructor, every optional feature at its
+// neutral value (include/pmhip.h) until an entry assigns it.  `narrow` is the name the entry's messages carry when no wider feature
+// is present: its own, or the *_lens entry's for the entries above that one.
 struct GenCall {
-    pmhip_s2* s2; pmhip_vqgan* vq; int64_t* ids; const float* context; int L, B, T;
+    const char* narrow; pmhip_s2* s2; pmhip_vqgan* vq; int64_t* ids; CtxKeys keys; int B, T;
     const float* temps_host; const int* nmask_host; const unsigned char* decode_host;
     int topk; uint64_t seed, image_base; float* imgs_out; int use_graph; pmhip_stream stream;
     float* imgs_host; size_t host_stride; pmhip_stream copy_stream;
-    const float* guidance = nullptr;
-    const int32_t* ctx_lens = nullptr;      // host [B] or NULL (pmhip_pipeline_generate_lens)
-    const char* who = "pipeline_generate";
+    int guided = 0; float guidance_scale = 0.f;   // one scale for the loop (ignored under a schedule)
     const float* ctemps = nullptr;          // host [T] or NULL: the steps' choice temperatures (pmhip_pipeline_generate_choice)
     float top_p = 1.f;                      // every step's nucleus mass (pmhip_pipeline_generate_nucleus); 1: no filter
     // pmhip_pipeline_generate_negative: the negative context [B, Ln, context_dim] with its host lengths [B] (or NULL), and the
-    // steps' guidance scales, host [T] (then `guidance` is NULL: the scalar is ignored)
-    const float* neg_context = nullptr; int Ln = 0; const int32_t* neg_lens = nullptr;
+    // steps' guidance scales, host [T] (then the scalar is ignored)
+    NegSet neg;
     const float* gscales = nullptr;
     // pmhip_pipeline_generate_edit: the re-masking counts per step and image, host [T][B], instead of nmask_host (then NULL); a
     // decoded step of such a loop decodes the merged ids
     const int32_t* nmask_img = nullptr;
-    // pmhip_pipeline_generate_segments: regional prompts, host uint8 [B, L] and uint32 [B, tokens], or both NULL
-    const uint8_t* ctx_seg = nullptr; const uint32_t* tok_seg = nullptr;
-    // pmhip_pipeline_generate_weights: prompt weights, host f32 [B, L], or NULL
-    const float* ctx_w = nullptr;
-    bool guided() const { return guidance || gscales; }
+    GenCall(const char* narrow_, pmhip_s2* s2_, pmhip_vqgan* vq_, int64_t* ids_, const float* context, int L, int B_, int T_,
+            const float* temps_host_, const int* nmask_host_, const unsigned char* decode_host_, int topk_, uint64_t seed_, uint64_t image_base_,
+            float* imgs_out_, int use_graph_, pmhip_stream stream_, float* imgs_host_, size_t host_stride_, pmhip_stream copy_stream_)
+        : narrow(narrow_), s2(s2_), vq(vq_), ids(ids_), keys(context, L), B(B_), T(T_), temps_host(temps_host_), nmask_host(nmask_host_),
+          decode_host(decode_host_), topk(topk_), seed(seed_), image_base(image_base_), imgs_out(imgs_out_), use_graph(use_graph_),
+          stream(stream_), imgs_host(imgs_host_), host_stride(host_stride_), copy_stream(copy_stream_) {}
+    const float* guidance() const { return guided && !gscales ? &guidance_scale : nullptr; }   // the loop's one scale, or NULL
+    bool any_guidance() const { return guidance() || gscales; }
     bool decodes(int t) const { return decode_host && decode_host[t]; }
 };
 
@@ -1890,67 +2007,99 @@ struct HostDelivery {
     }
 };
 
-int pipeline_generate(const GenCall& c) {
-    pmhip_s2* s2 = c.s2; pmhip_vqgan* vq = c.vq;
+// A call of the generate family beyond its record: the name its messages carry, the forms its checks found, and what the
+// preparation left in the workspace.  pipeline_generate fills it phase by phase: gen_checks, gen_prepare, then one of the two loops.
+struct GenLoop {
+    const GenCall& c;
+    const char* who;
+    const bool edit, sched, neg;
+    bool choice = false;                                      // a step has a choice temperature other than 0
+    CtxWeights cw;
+    hipStream_t s = nullptr, cs = nullptr;
+    bool graph = false, from_mask = false, share0 = false;
+    size_t img_elems = 0, n_ids = 0;
+    int n_dec = 0;
+    float* gimgs = nullptr;                                   // the handle-owned image buffer "gen.imgs", or NULL
+    PmGenParams* gparams = nullptr;                           // "gen.params" (stage_gen_params)
+    int32_t* gcounts = nullptr;                               // "gen.counts" (stage_gen_counts)
+    // the name: the widest feature present, otherwise the entry's narrow name
+    // (the edit entry's calls carry its own name wherever the negative entry's would stand)
+    // (the entries above *_lens pass that entry's name as `narrow`: they report as *_lens when no wider feature is present)
+    explicit GenLoop(const GenCall& c_)
+        : c(c_),
+          who(call_name({{c_.keys.w != nullptr, "pipeline_generate_weights"},
+                         {c_.keys.seg || c_.keys.tok, "pipeline_generate_segments"},
+                         {c_.nmask_img != nullptr, c_.narrow},
+                         {c_.neg.context || c_.gscales, "pipeline_generate_negative"},
+                         {c_.top_p != 1.f, "pipeline_generate_nucleus"},
+                         {c_.ctemps != nullptr, "pipeline_generate_choice"}}, c_.narrow)),
+          edit(c_.nmask_img != nullptr), sched(c_.gscales != nullptr), neg(c_.neg.context != nullptr) {}
+};
+
+// checks: every host check of the loop, in order, before anything is launched
+int gen_checks(GenLoop& g) {
+    const GenCall& c = g.c;
+    pmhip_s2* s2 = c.s2;
     const int B = c.B, T = c.T;
-    const bool edit = c.nmask_img != nullptr;
-    PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && (c.nmask_host || edit), "pipeline_generate: bad arguments");
-    if (edit) {                                               // checked before anything is launched
-        PM_REQUIRE(!(c.use_graph & PMHIP_GENERATE_FROM_MASK), "%s: an edit starts from the caller's ids, the from-mask flag is refused", c.who);
+    // (pm_check_top_p always reports under the nucleus entry's name)
+    PM_TRY(pm_check_top_p("pipeline_generate_nucleus", c.top_p));
+    // (check_negative and the schedule's checks report under the negative entry's name, except under the edit entry, which uses its own)
+    const char* neg_who = call_name({{g.edit, c.narrow}}, "pipeline_generate_negative");
+    PM_TRY(check_negative(neg_who, c.neg, g.sched, c.guided != 0, c.keys.context && c.keys.L > 0, B));
+    if (g.sched) {
+        PM_REQUIRE(T <= PM_MAX_STEPS, "%s: a guidance schedule serves at most %d steps, T=%d", neg_who, PM_MAX_STEPS, T);
+        for (int t = 0; t < T; ++t) PM_REQUIRE(std::isfinite(c.gscales[t]), "%s: step %d: the guidance scale must be finite", neg_who, t);
+    }
+    // (the loop's first check of its arguments says pipeline_generate, whichever entry was called)
+    PM_REQUIRE(s2 && c.ids && B > 0 && T > 0 && c.temps_host && (c.nmask_host || g.edit), "pipeline_generate: bad arguments");
+    if (g.edit) {
+        PM_REQUIRE(!(c.use_graph & PMHIP_GENERATE_FROM_MASK), "%s: an edit starts from the caller's ids, the from-mask flag is refused", g.who);
         for (int t = 0; t < T; ++t)
             for (int b = 0; b < B; ++b)
                 PM_REQUIRE(c.nmask_img[(size_t)t * B + b] >= 0 && c.nmask_img[(size_t)t * B + b] <= s2->cfg.tokens,
-                           "%s: step %d, image %d: the re-masking count %d must be in [0, %d]", c.who, t, b, c.nmask_img[(size_t)t * B + b],
+                           "%s: step %d, image %d: the re-masking count %d must be in [0, %d]", g.who, t, b, c.nmask_img[(size_t)t * B + b],
                            s2->cfg.tokens);
     }
-    PM_REQUIRE(!c.guided() || (c.context && c.L > 0), "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
-    PM_TRY(check_ctx_lens(c.who, c.ctx_lens, c.context != nullptr, c.L, B));
-    PM_TRY(check_segments(c.who, c.ctx_seg, c.tok_seg, c.ctx_lens, c.context != nullptr, c.L, B, s2));
-    CtxWeights cw;
-    PM_TRY(check_weights(c.who, c.ctx_w, c.ctx_seg, c.tok_seg, c.ctx_lens, c.context != nullptr, c.L, B, s2, cw));
-    const bool sched = c.gscales != nullptr, neg = c.neg_context != nullptr;
-    // the choice temperatures, checked before anything is launched; all zero IS the loop without them (same kernels, same graphs)
-    bool choice = false;
+    // (the guidance-needs-a-context message always says pipeline_generate_guided)
+    PM_REQUIRE(!c.any_guidance() || (c.keys.context && c.keys.L > 0),
+               "pipeline_generate_guided: guidance needs a context (context NULL IS the unconditional branch)");
+    PM_TRY(check_context(g.who, c.keys, B, s2, g.cw));
+    // the choice temperatures; all zero IS the loop without them (same kernels, same graphs)
     for (int t = 0; c.ctemps && t < T; ++t) {
-        PM_TRY(pm_check_choice_t(c.who, c.ctemps[t]));
-        choice = choice || c.ctemps[t] != 0.f;
+        PM_TRY(pm_check_choice_t(g.who, c.ctemps[t]));
+        g.choice = g.choice || c.ctemps[t] != 0.f;
     }
-    hipStream_t s = (hipStream_t)c.stream;
-    hipStream_t cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
-    PM_TRY(s2_prepare_context(s2, c.context, c.L, B, s));     // context projection + cross K/V: once per loop, eager
-    PM_TRY(s2_set_ctx_lens(s2, cw.lens, c.L, B, s));          // the lengths: device memory the (captured) cross-attention launches read
-    PM_TRY(s2_set_segments(s2, cw.seg, cw.tok, c.L, B, s));   // ... and the segments, likewise (the context's set only)
-    PM_TRY(s2_set_weights(s2, cw.w, c.L, B, s));              // ... and the weights' bias array
-    if (neg) {                                                // the negative set: one more preparation per loop, eager like the first
-        PM_TRY(s2_prepare_context(s2, c.neg_context, c.Ln, B, s, kCrossNegative));
-        PM_TRY(s2_set_ctx_lens(s2, c.neg_lens, c.Ln, B, s, kCrossNegative));
-    }
-    size_t img_elems = 0;
-    if (vq) img_elems = (size_t)B * vq->cfg.channels * vq->cfg.image_size * vq->cfg.image_size;
-    int n_dec = 0;
-    for (int t = 0; t < T; ++t) n_dec += c.decodes(t) ? 1 : 0;
-    PM_REQUIRE(n_dec == 0 || (vq && (c.imgs_out || c.imgs_host)), "pipeline_generate: decode requested without vqgan / an image destination");
-    PM_REQUIRE(!c.imgs_host || c.host_stride >= img_elems, "pipeline_generate: host_stride smaller than one image batch");
+    return PMHIP_OK;
+}
+
+// preparation: the contexts (once per loop, eager: the device memory the -- captured -- cross-attention launches read), the decode
+// plan, the loop's form, the events of a host delivery and the handle-owned image buffer
+int gen_prepare(GenLoop& g) {
+    const GenCall& c = g.c;
+    pmhip_s2* s2 = c.s2; pmhip_vqgan* vq = c.vq;
+    const int B = c.B, T = c.T;
+    hipStream_t s = g.s = (hipStream_t)c.stream;
+    g.cs = c.copy_stream ? (hipStream_t)c.copy_stream : s;
+    PM_TRY(stage_context(s2, c.keys, g.cw, c.neg, B, s));
+    if (vq) g.img_elems = (size_t)B * vq->cfg.channels * vq->cfg.image_size * vq->cfg.image_size;
+    for (int t = 0; t < T; ++t) g.n_dec += c.decodes(t) ? 1 : 0;
+    PM_REQUIRE(g.n_dec == 0 || (vq && (c.imgs_out || c.imgs_host)), "pipeline_generate: decode requested without vqgan / an image destination");
+    PM_REQUIRE(!c.imgs_host || c.host_stride >= g.img_elems, "pipeline_generate: host_stride smaller than one image batch");
     // AMD_DIRECT_DISPATCH=0 (the runtime mode without the busy-polling helper thread): hipGraph replay is broken there on ROCm 7.2
     // -- tools/hwtests/graph_dispatch_mode.hip, 39 of 40 replays of a chain of dependent kernels wrong with none of this library's
     // code involved -- so the loop stays eager in that mode whatever the caller asked for (same results, bit for bit)
     // pmhip_s2_switches reports the downgrade (bit 5) so that a caller can tell which mode ran
-    const bool graph = (c.use_graph & PMHIP_GENERATE_GRAPH) && !g_pm_timing_on.load() && T <= PM_MAX_STEPS && !direct_dispatch_off();
+    g.graph = (c.use_graph & PMHIP_GENERATE_GRAPH) && !g_pm_timing_on.load() && T <= PM_MAX_STEPS && !direct_dispatch_off();
     // PMHIP_GENERATE_FROM_MASK: the loop starts from the all-mask state -- the library writes that state itself, so the claim
     // cannot be false -- and, without a context, step 0 samples from the handle's shared step-0 logits instead of running the tower
     // (step0_tower_once).  Not while per-kernel timing is on: the timed pass accounts for the work of all T tower passes.
-    const bool from_mask = (c.use_graph & PMHIP_GENERATE_FROM_MASK) != 0;
-    const bool share0 = from_mask && !c.context && !c.guidance && !g_pm_timing_on.load();
-    const size_t n_ids = (size_t)B * s2->cfg.tokens;
-    if (share0 && s2->s0_valid) {
+    g.from_mask = (c.use_graph & PMHIP_GENERATE_FROM_MASK) != 0;
+    g.share0 = g.from_mask && !c.keys.context && !c.guidance() && !g_pm_timing_on.load();
+    g.n_ids = (size_t)B * s2->cfg.tokens;
+    if (g.share0 && s2->s0_valid) {
         ++s2->s0_hits;
         if (s != s2->s0_stream) PM_HIP(hipStreamWaitEvent(s, s2->s0_ready.h, 0));
     }
-    // the tower half of a step
-    auto tower = [&](const int64_t* from, const Step& st, hipStream_t on) -> int {
-        return st.shared0 ? step0_tower_once(s2, from, B, on) : step_tower(s2, from, B, st, on);
-    };
-
     if (c.imgs_host) {
         // PMHIP_BLOCKING_WAIT=1 (read when the handle is created): the lane's host thread SLEEPS in hipEventSynchronize while its
         // segment runs instead of spinning -- frees a core per lane on a host that is short of them, at 0.6 ms of wake-up latency
@@ -1958,121 +2107,164 @@ int pipeline_generate(const GenCall& c) {
         const unsigned evflags = hipEventDisableTiming | (s2->sw.blocking_wait ? hipEventBlockingSync : 0u);
         hipEvent_t e;
         PM_TRY(s2->host_copied.get(evflags, e));
-        if ((int)s2->img_ready.size() < n_dec) s2->img_ready.resize(n_dec);
-        for (int d = 0; d < n_dec; ++d) PM_TRY(s2->img_ready[d].get(evflags, e));
+        if ((int)s2->img_ready.size() < g.n_dec) s2->img_ready.resize(g.n_dec);
+        for (int d = 0; d < g.n_dec; ++d) PM_TRY(s2->img_ready[d].get(evflags, e));
     }
     // images are produced into a handle-owned buffer when a graph bakes the pointer in or when the caller only wants the
     // host copy; that buffer must not be overwritten while the previous call's last device-to-host copy still reads it
-    float* gimgs = nullptr;
-    if (n_dec && (graph || !c.imgs_out)) {
-        WS(s2->ws, "gen.imgs", (size_t)n_dec * img_elems * 4 + 16, gimgs);
+    if (g.n_dec && (g.graph || !c.imgs_out)) {
+        WS(s2->ws, "gen.imgs", (size_t)g.n_dec * g.img_elems * 4 + 16, g.gimgs);
         if (s2->host_copy_pending) { PM_HIP(hipStreamWaitEvent(s, s2->host_copied.h, 0)); s2->host_copy_pending = false; }
     }
-    HostDelivery out{c, s, cs, img_elems, n_dec, gimgs != nullptr};
+    return PMHIP_OK;
+}
 
-    // The device parameter block: what the kernels of a replayed loop read their per-call values from, and -- eager or replayed --
-    // where the combine launches of a loop with a guidance schedule read their scales (one kernel form for eager, capture and replay).
-    PmGenParams* gparams = nullptr;
-    auto stage_params = [&]() -> int {
-        WS(s2->ws, "gen.params", sizeof(PmGenParams), gparams);
-        PmGenParams hp;
-        hp.seed = c.seed;
-        hp.row_base = c.image_base * (uint64_t)s2->cfg.tokens;
-        for (int t = 0; t < T; ++t) {
-            hp.temps[t] = c.temps_host[t]; hp.nmask[t] = edit ? 0 : c.nmask_host[t]; hp.ctemps[t] = choice ? c.ctemps[t] : 0.f;
-            hp.gscales[t] = sched ? c.gscales[t] : 0.f;
-        }
-        // a loop stages what it always staged: without choice temperatures the block up to ctemps, without a guidance schedule the
-        // block up to gscales -- none of its kernels reads what lies behind
-        const size_t hp_bytes = sched ? sizeof hp : choice ? offsetof(PmGenParams, gscales) : offsetof(PmGenParams, ctemps);
-        PM_TRY(s2->params_ring.reserve(sizeof hp));
-        PM_TRY(s2->params_ring.acquire());
-        PM_TRY(s2->params_ring.stage(gparams, 0, &hp, hp_bytes, s));
-        PM_TRY(s2->params_ring.commit(s));
-        return PMHIP_OK;
-    };
-
-    // The edit loop's count table, T * B int32 at a fixed address: step t's re-masking launch -- eager, captured or replayed -- reads
-    // its B counts at gcounts + t * B, so a graph bakes in the address and never the counts.  Refreshed per call like the block above.
-    int32_t* gcounts = nullptr;
-    auto stage_counts = [&]() -> int {
-        const size_t bytes = ((size_t)T * B * 4 + 15) & ~(size_t)15;
-        WS(s2->ws, "gen.counts", bytes, gcounts);
-        std::vector<int32_t> padded(bytes / 4, 0);
-        std::copy(c.nmask_img, c.nmask_img + (size_t)T * B, padded.begin());
-        PM_TRY(s2->counts_ring.reserve(bytes));
-        PM_TRY(s2->counts_ring.acquire());
-        PM_TRY(s2->counts_ring.stage(gcounts, 0, padded.data(), bytes, s));
-        PM_TRY(s2->counts_ring.commit(s));
-        return PMHIP_OK;
-    };
-
-    if (!graph) {
-        int d = 0;
-        if (sched) PM_TRY(stage_params());
-        if (edit) PM_TRY(stage_counts());
-        if (from_mask) PM_TRY(fill_ids_async(c.ids, (int64_t)s2->cfg.n_embed, n_ids, s));
-        for (int t = 0; t < T; ++t) {
-            const bool dec = c.decodes(t);
-            float* img = !dec ? nullptr : (gimgs ? gimgs : c.imgs_out) + (size_t)d * img_elems;
-            Step st{c.topk, c.temps_host[t], edit ? 0 : c.nmask_host[t], nullptr, c.seed, (uint32_t)t, c.image_base, nullptr, share0 && t == 0,
-                    c.guidance};
-            if (edit) { st.counts = gcounts + (size_t)t * B; st.decode_merged = dec; }
-            if (choice) st.choice_t = c.ctemps[t];             // 0 (the last step of an annealed loop): the plain launch, the same keys
-            st.top_p = c.top_p;
-            st.negative = neg;
-            if (sched) st.guidance_dev = &gparams->gscales[t];
-            PM_TRY(tower(c.ids, st, s));
-            PM_TRY(step_tail(s2, vq, c.ids, B, st, img, nullptr, nullptr, s));
-            PM_TRY(out.flush());                               // the previous image, now that one more step is queued behind it
-            if (dec) PM_TRY(out.deliver(d++, img));
-        }
-        return out.flush();
+// staging: the device parameter block -- what the kernels of a replayed loop read their per-call values from, and, eager or
+// replayed, where the combine launches of a loop with a guidance schedule read their scales (one kernel form for eager, capture and
+// replay)
+int stage_gen_params(GenLoop& g) {
+    const GenCall& c = g.c;
+    pmhip_s2* s2 = c.s2;
+    hipStream_t s = g.s;
+    WS(s2->ws, "gen.params", sizeof(PmGenParams), g.gparams);
+    PmGenParams hp;
+    hp.seed = c.seed;
+    hp.row_base = c.image_base * (uint64_t)s2->cfg.tokens;
+    for (int t = 0; t < c.T; ++t) {
+        hp.temps[t] = c.temps_host[t]; hp.nmask[t] = g.edit ? 0 : c.nmask_host[t]; hp.ctemps[t] = g.choice ? c.ctemps[t] : 0.f;
+        hp.gscales[t] = g.sched ? c.gscales[t] : 0.f;
     }
+    // a loop stages what it always staged: without choice temperatures the block up to ctemps, without a guidance schedule the
+    // block up to gscales -- none of its kernels reads what lies behind
+    const size_t hp_bytes = g.sched ? sizeof hp : g.choice ? offsetof(PmGenParams, gscales) : offsetof(PmGenParams, ctemps);
+    PM_TRY(s2->params_ring.reserve(sizeof hp));
+    PM_TRY(s2->params_ring.acquire());
+    PM_TRY(s2->params_ring.stage(g.gparams, 0, &hp, hp_bytes, s));
+    return s2->params_ring.commit(s);
+}
 
-    // ---- hipGraph path.  The T-step loop is a chain of graphs, one per SEGMENT (the steps up to and including a decoded
-    // one), whose kernels read the per-call scalars (temperatures, mask counts, seed, row base) from a device parameter
-    // block and whose ids / image pointers are handle-owned buffers, so the same executable graphs serve every call with
-    // this structure; between two segments the finished image starts its way to the host.
-    const size_t ids_bytes = n_ids * 8;
-    int64_t* gids;
-    WS(s2->ws, "gen.ids", ids_bytes, gids);
-    PM_TRY(stage_params());
-    if (edit) PM_TRY(stage_counts());
-    if (from_mask) PM_TRY(fill_ids_async(gids, (int64_t)s2->cfg.n_embed, n_ids, s));
-    else PM_TRY(copy16_async(gids, c.ids, ids_bytes, s));
+// ... and the edit loop's count table, T * B int32 at a fixed address: step t's re-masking launch -- eager, captured or replayed --
+// reads its B counts at gcounts + t * B, so a graph bakes in the address and never the counts.  Refreshed per call like the block above.
+int stage_gen_counts(GenLoop& g) {
+    const GenCall& c = g.c;
+    pmhip_s2* s2 = c.s2;
+    hipStream_t s = g.s;
+    const size_t bytes = ((size_t)c.T * c.B * 4 + 15) & ~(size_t)15;
+    WS(s2->ws, "gen.counts", bytes, g.gcounts);
+    std::vector<int32_t> padded(bytes / 4, 0);
+    std::copy(c.nmask_img, c.nmask_img + (size_t)c.T * c.B, padded.begin());
+    PM_TRY(s2->counts_ring.reserve(bytes));
+    PM_TRY(s2->counts_ring.acquire());
+    PM_TRY(s2->counts_ring.stage(g.gcounts, 0, padded.data(), bytes, s));
+    return s2->counts_ring.commit(s);
+}
 
-    std::string key = "B" + std::to_string(B) + "T" + std::to_string(T) + "k" + std::to_string(c.topk) + "L" +
-                      std::to_string(c.context ? c.L : 0) + "v" + std::to_string(vq ? vq->uid : 0) + "f" +
-                      std::to_string(s2->sw.key() * 16 + (vq ? vq->sw.key() : 0));
-    if (c.guidance) {                                         // the scale is a kernel argument of the captured combine: one graph per value
+// The Step of loop step t, for both loops.  from_params: the per-call scalars (temperature, mask count, seed, row base, choice
+// temperature) come from the device parameter block -- the graph loop, whose graphs serve every call -- instead of from the call.
+Step gen_step(const GenLoop& g, int t, bool from_params) {
+    const GenCall& c = g.c;
+    Step st;
+    st.topk = c.topk;
+    st.step = (uint32_t)t;
+    st.shared0 = g.share0 && t == 0;
+    st.guidance = c.guidance();
+    if (from_params) {
+        st.gp = g.gparams;
+        st.choice_params = g.choice;
+    } else {
+        st.temperature = c.temps_host[t]; st.num_mask = g.edit ? 0 : c.nmask_host[t];
+        st.seed = c.seed; st.image_base = c.image_base;
+        if (g.choice) st.choice_t = c.ctemps[t];              // 0 (the last step of an annealed loop): the plain launch, the same keys
+    }
+    st.top_p = c.top_p;
+    st.negative = g.neg;
+    if (g.sched) st.guidance_dev = &g.gparams->gscales[t];
+    if (g.edit) { st.counts = g.gcounts + (size_t)t * c.B; st.decode_merged = c.decodes(t); }
+    return st;
+}
+
+// the tower half of a step
+int gen_tower(const GenLoop& g, const int64_t* from, const Step& st, hipStream_t on) {
+    return st.shared0 ? step0_tower_once(g.c.s2, from, g.c.B, on) : step_tower(g.c.s2, from, g.c.B, st, on);
+}
+
+// the eager loop: every step on the caller's ids, its scalars from the call
+int gen_eager_loop(GenLoop& g) {
+    const GenCall& c = g.c;
+    pmhip_s2* s2 = c.s2;
+    hipStream_t s = g.s;
+    HostDelivery out{c, s, g.cs, g.img_elems, g.n_dec, g.gimgs != nullptr};
+    int d = 0;
+    if (g.sched) PM_TRY(stage_gen_params(g));
+    if (g.edit) PM_TRY(stage_gen_counts(g));
+    if (g.from_mask) PM_TRY(fill_ids_async(c.ids, (int64_t)s2->cfg.n_embed, g.n_ids, s));
+    for (int t = 0; t < c.T; ++t) {
+        const bool dec = c.decodes(t);
+        float* img = !dec ? nullptr : (g.gimgs ? g.gimgs : c.imgs_out) + (size_t)d * g.img_elems;
+        const Step st = gen_step(g, t, false);
+        PM_TRY(gen_tower(g, c.ids, st, s));
+        PM_TRY(step_tail(s2, c.vq, c.ids, c.B, st, img, nullptr, nullptr, s));
+        PM_TRY(out.flush());                                   // the previous image, now that one more step is queued behind it
+        if (dec) PM_TRY(out.deliver(d++, img));
+    }
+    return out.flush();
+}
+
+// The graph cache key of a loop: everything that shapes its launches, nothing a launch reads from device memory.
+std::string gen_key(const GenLoop& g, bool overlap) {
+    const GenCall& c = g.c;
+    std::string key = "B" + std::to_string(c.B) + "T" + std::to_string(c.T) + "k" + std::to_string(c.topk) + "L" +
+                      std::to_string(c.keys.context ? c.keys.L : 0) + "v" + std::to_string(c.vq ? c.vq->uid : 0) + "f" +
+                      std::to_string(c.s2->sw.key() * 16 + (c.vq ? c.vq->sw.key() : 0));
+    if (c.guidance()) {                                       // the scale is a kernel argument of the captured combine: one graph per value
         unsigned bits;
-        memcpy(&bits, c.guidance, 4);
+        memcpy(&bits, c.guidance(), 4);
         key += "g" + std::to_string(bits);
-    } else if (sched) {                                       // the combine reads &gparams->gscales[t]: an address, so one graph serves every schedule
+    } else if (g.sched) {                                     // the combine reads &gparams->gscales[t]: an address, so one graph serves every schedule
         key += "gs";
     }
     // the second tower attends to the negative set: Ln shapes its cross-attention launches, lengths pick their per-image form
-    if (neg) key += "N" + std::to_string(c.Ln) + (c.neg_lens ? "l" : "");
+    if (g.neg) key += "N" + std::to_string(c.neg.Ln) + (c.neg.lens ? "l" : "");
     key += "d";
-    for (int t = 0; t < T; ++t) key += c.decodes(t) ? '1' : '0';
-    // (no deferred decode when the caller runs other lanes beside this one -- PMHIP_GENERATE_CONCURRENT_LANES: the chip is full
-    // then, and a third and fourth stream of kernels costs 5-17 % at 15-16 images per lane, profiles/r05_g_*)
-    const bool overlap = vq && n_dec > 0 && s2->sw.overlap_rows > 0 && (long long)B * s2->cfg.tokens <= s2->sw.overlap_rows &&
-                         !(c.use_graph & PMHIP_GENERATE_CONCURRENT_LANES);
-    const std::vector<Unit> units = plan_units(c, overlap);
+    for (int t = 0; t < c.T; ++t) key += c.decodes(t) ? '1' : '0';
     key += overlap ? "o1" : "o0";
-    if (from_mask) key += "m";                                // step 0 is captured without its tower: never shared with an unflagged loop
-    if (c.ctx_lens && !c.ctx_w) key += "n";                               // the per-image form of the cross-attention kernel; the lengths are not in the key
-    if (c.ctx_seg) key += "s";                                // the per-query form of the cross-attention kernel; the layout of regions is not in the key
-    if (c.ctx_w) key += "w";                                  // the weighted form of the cross-attention kernel; neither the weights nor the layout are in the key
-    if (edit) key += "e";                                     // the counts form of the re-masking kernel and the merged decode; the counts are not in the key
-    if (choice) key += "c";                                   // the choice form of the re-masking kernel; the temperatures are not in the key
+    if (g.from_mask) key += "m";                              // step 0 is captured without its tower: never shared with an unflagged loop
+    if (c.keys.lens && !c.keys.w) key += "n";                 // the per-image form of the cross-attention kernel; the lengths are not in the key
+    if (c.keys.seg) key += "s";                               // the per-query form of the cross-attention kernel; the layout of regions is not in the key
+    if (c.keys.w) key += "w";                                 // the weighted form of the cross-attention kernel; neither the weights nor the layout are in the key
+    if (g.edit) key += "e";                                   // the counts form of the re-masking kernel and the merged decode; the counts are not in the key
+    if (g.choice) key += "c";                                 // the choice form of the re-masking kernel; the temperatures are not in the key
     if (c.top_p < 1.f) {                                      // the nucleus kernel, the mass its argument in the captured graph: one graph per value
         unsigned bits;
         memcpy(&bits, &c.top_p, 4);
         key += "p" + std::to_string(bits);
     }
+    return key;
+}
+
+// The hipGraph loop.  The T-step loop is a chain of graphs, one per SEGMENT (the steps up to and including a decoded
+// one), whose kernels read the per-call scalars (temperatures, mask counts, seed, row base) from a device parameter
+// block and whose ids / image pointers are handle-owned buffers, so the same executable graphs serve every call with
+// this structure; between two segments the finished image starts its way to the host.
+int gen_graph_loop(GenLoop& g) {
+    const GenCall& c = g.c;
+    pmhip_s2* s2 = c.s2; pmhip_vqgan* vq = c.vq;
+    const int B = c.B;
+    hipStream_t s = g.s;
+    HostDelivery out{c, s, g.cs, g.img_elems, g.n_dec, g.gimgs != nullptr};
+    const size_t ids_bytes = g.n_ids * 8;
+    int64_t* gids;
+    WS(s2->ws, "gen.ids", ids_bytes, gids);
+    PM_TRY(stage_gen_params(g));
+    if (g.edit) PM_TRY(stage_gen_counts(g));
+    if (g.from_mask) PM_TRY(fill_ids_async(gids, (int64_t)s2->cfg.n_embed, g.n_ids, s));
+    else PM_TRY(copy16_async(gids, c.ids, ids_bytes, s));
+
+    // (no deferred decode when the caller runs other lanes beside this one -- PMHIP_GENERATE_CONCURRENT_LANES: the chip is full
+    // then, and a third and fourth stream of kernels costs 5-17 % at 15-16 images per lane, profiles/r05_g_*)
+    const bool overlap = vq && g.n_dec > 0 && s2->sw.overlap_rows > 0 && (long long)B * s2->cfg.tokens <= s2->sw.overlap_rows &&
+                         !(c.use_graph & PMHIP_GENERATE_CONCURRENT_LANES);
+    const std::vector<Unit> units = plan_units(c, overlap);
     hipStream_t side = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     if (overlap) {
@@ -2080,6 +2272,8 @@ int pipeline_generate(const GenCall& c) {
         PM_TRY(s2->ev_fork.get(hipEventDisableTiming, ev_fork));
         PM_TRY(s2->ev_join.get(hipEventDisableTiming, ev_join));
     }
+    float* const gimgs = g.gimgs;
+    const size_t img_elems = g.img_elems;
 
     auto run_unit = [&](hipStream_t on, size_t i) -> int {
         const Unit& u = units[i];
@@ -2097,20 +2291,15 @@ int pipeline_generate(const GenCall& c) {
             }
         }
         for (int t = u.t0; t < u.t1; ++t) {
-            Step st{c.topk, 0.f, 0, nullptr, 0, (uint32_t)t, 0, gparams, share0 && t == 0, c.guidance};
-            st.choice_params = choice;
-            st.top_p = c.top_p;
-            st.negative = neg;
-            if (sched) st.guidance_dev = &gparams->gscales[t];
-            if (edit) { st.counts = gcounts + (size_t)t * B; st.decode_merged = c.decodes(t); }
-            PM_TRY(tower(gids, st, on));
+            const Step st = gen_step(g, t, true);
+            PM_TRY(gen_tower(g, gids, st, on));
             if (need_join) { PM_HIP(hipStreamWaitEvent(on, ev_join, 0)); need_join = false; }   // before `s2.pred` is overwritten
             float* img = (u.decode_inline && c.decodes(t)) ? gimgs + (size_t)u.delivers * img_elems : nullptr;
             PM_TRY(step_tail(s2, vq, gids, B, st, img, nullptr, nullptr, on));
         }
         return PMHIP_OK;
     };
-    PM_TRY(run_graphs(s2, vq, s2->graphs[key], units.size(), s, run_unit, [&](size_t i) -> int {
+    PM_TRY(run_graphs(s2, vq, s2->graphs[gen_key(g, overlap)], units.size(), s, run_unit, [&](size_t i) -> int {
         PM_TRY(out.flush());
         if (units[i].delivers >= 0) PM_TRY(out.deliver(units[i].delivers, gimgs + (size_t)units[i].delivers * img_elems));
         return PMHIP_OK;
@@ -2119,48 +2308,24 @@ int pipeline_generate(const GenCall& c) {
     return out.flush();
 }
 
-}  // namespace
-
-// The generate family's one builder: the argument list of pmhip_pipeline_generate_nucleus, the widest entry, -> the GenCall and the
-// name its messages carry.  A narrower entry passes the neutral values (include/pmhip.h) and `narrow`, the name in use when neither
-// a nucleus mass nor choice temperatures are in play: its own, or the *_lens entry's for the two entries above that one.
-static int pipeline_generate_call(const char* narrow, pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
-                                  const int32_t* ctx_lens_host, int T, const float* temps_host, const int* nmask_host,
-                                  const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base, float* imgs_out,
-                                  int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride, pmhip_stream copy_stream,
-                                  int guided, float guidance_scale, const float* ctemps_host, float top_p,
-                                  const float* neg_context = nullptr, int Ln = 0, const int32_t* neg_lens_host = nullptr,
-                                  const float* gscales_host = nullptr, const int32_t* nmask_img_host = nullptr,
-                                  const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr,
-                                  const float* ctx_w_host = nullptr) {
-    PM_TRY(pm_check_top_p("pipeline_generate_nucleus", top_p));
-    const char* neg_who = nmask_img_host ? narrow : "pipeline_generate_negative";
-    PM_TRY(check_negative(neg_who, neg_context, Ln, neg_lens_host, gscales_host != nullptr, guided != 0, context && L > 0, B));
-    if (gscales_host) {
-        PM_REQUIRE(T <= PM_MAX_STEPS, "%s: a guidance schedule serves at most %d steps, T=%d", neg_who, PM_MAX_STEPS, T);
-        for (int t = 0; t < T; ++t) PM_REQUIRE(std::isfinite(gscales_host[t]), "%s: step %d: the guidance scale must be finite", neg_who, t);
-    }
-    GenCall c{s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base, imgs_out,
-              use_graph, stream, imgs_host, host_stride, copy_stream, guided && !gscales_host ? &guidance_scale : nullptr, ctx_lens_host,
-              nmask_img_host || neg_context || gscales_host ? neg_who : top_p != 1.f ? "pipeline_generate_nucleus" : ctemps_host ? "pipeline_generate_choice" : narrow,
-              ctemps_host, top_p};
-    c.neg_context = neg_context; c.Ln = Ln; c.neg_lens = neg_lens_host;
-    c.gscales = gscales_host;
-    c.nmask_img = nmask_img_host;
-    c.ctx_seg = ctx_seg_host; c.tok_seg = tok_seg_host;
-    if (ctx_seg_host || tok_seg_host) c.who = "pipeline_generate_segments";
-    c.ctx_w = ctx_w_host;
-    if (ctx_w_host) c.who = "pipeline_generate_weights";
-    return pipeline_generate(c);
+// The generate family's one builder: the record -> the checks, the preparation, one of the two loops.
+int pipeline_generate(const GenCall& c) {
+    GenLoop g(c);
+    PM_TRY(gen_checks(g));
+    PM_TRY(gen_prepare(g));
+    return g.graph ? gen_graph_loop(g) : gen_eager_loop(g);
 }
+
+}  // namespace
 
 extern "C" int pmhip_pipeline_generate(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
                                        int T, const float* temps_host, const int* nmask_host,
                                        const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                        float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
                                        size_t host_stride, pmhip_stream copy_stream) {
-    return pipeline_generate_call("pipeline_generate", s2, vq, ids, context, L, B, nullptr, T, temps_host, nmask_host, decode_host, topk, seed,
-                                  image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, 0, 0.f, nullptr, 1.f);
+    GenCall c("pipeline_generate", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    return pipeline_generate(c);
 }
 
 extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -2168,8 +2333,10 @@ extern "C" int pmhip_pipeline_generate_guided(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                               float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host,
                                               size_t host_stride, pmhip_stream copy_stream, float guidance_scale) {
-    return pipeline_generate_call("pipeline_generate", s2, vq, ids, context, L, B, nullptr, T, temps_host, nmask_host, decode_host, topk, seed,
-                                  image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, 1, guidance_scale, nullptr, 1.f);
+    GenCall c("pipeline_generate", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.guided = 1; c.guidance_scale = guidance_scale;
+    return pipeline_generate(c);
 }
 
 extern "C" int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -2177,9 +2344,11 @@ extern "C" int pmhip_pipeline_generate_lens(pmhip_s2* s2, pmhip_vqgan* vq, int64
                                             const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                             float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
                                             pmhip_stream copy_stream, int guided, float guidance_scale) {
-    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
-                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                  guidance_scale, nullptr, 1.f);
+    GenCall c("pipeline_generate_lens", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    return pipeline_generate(c);
 }
 
 extern "C" int pmhip_pipeline_generate_choice(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids, const float* context, int L, int B,
@@ -2187,9 +2356,12 @@ extern "C" int pmhip_pipeline_generate_choice(pmhip_s2* s2, pmhip_vqgan* vq, int
                                               const unsigned char* decode_host, int topk, uint64_t seed, uint64_t image_base,
                                               float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
                                               pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host) {
-    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
-                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                  guidance_scale, ctemps_host, 1.f);
+    GenCall c("pipeline_generate_lens", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.ctemps = ctemps_host;
+    return pipeline_generate(c);
 }
 
 // top_p == 1: exactly pmhip_pipeline_generate_choice
@@ -2199,9 +2371,13 @@ extern "C" int pmhip_pipeline_generate_nucleus(pmhip_s2* s2, pmhip_vqgan* vq, in
                                                float* imgs_out, int use_graph, pmhip_stream stream, float* imgs_host, size_t host_stride,
                                                pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
                                                float top_p) {
-    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
-                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                  guidance_scale, ctemps_host, top_p);
+    GenCall c("pipeline_generate_lens", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.ctemps = ctemps_host;
+    c.top_p = top_p;
+    return pipeline_generate(c);
 }
 
 // neg_context == NULL and gscales_host == NULL: exactly pmhip_pipeline_generate_nucleus
@@ -2212,9 +2388,15 @@ extern "C" int pmhip_pipeline_generate_negative(pmhip_s2* s2, pmhip_vqgan* vq, i
                                                 pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
                                                 float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                                 const float* gscales_host) {
-    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
-                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host);
+    GenCall c("pipeline_generate_lens", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.ctemps = ctemps_host;
+    c.top_p = top_p;
+    c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.gscales = gscales_host;
+    return pipeline_generate(c);
 }
 
 // ctx_seg_host == NULL and tok_seg_host == NULL: exactly pmhip_pipeline_generate_negative
@@ -2225,10 +2407,15 @@ extern "C" int pmhip_pipeline_generate_segments(pmhip_s2* s2, pmhip_vqgan* vq, i
                                                 pmhip_stream copy_stream, int guided, float guidance_scale, const float* ctemps_host,
                                                 float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                                 const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host) {
-    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
-                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host, nullptr, ctx_seg_host,
-                                  tok_seg_host);
+    GenCall c("pipeline_generate_lens", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.keys.lens = ctx_lens_host; c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.ctemps = ctemps_host;
+    c.top_p = top_p;
+    c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.gscales = gscales_host;
+    return pipeline_generate(c);
 }
 
 // ctx_w_host == NULL: exactly pmhip_pipeline_generate_segments
@@ -2240,135 +2427,175 @@ extern "C" int pmhip_pipeline_generate_weights(pmhip_s2* s2, pmhip_vqgan* vq, in
                                                float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                                const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
                                                const float* ctx_w_host) {
-    return pipeline_generate_call("pipeline_generate_lens", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nmask_host, decode_host,
-                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host, nullptr, ctx_seg_host,
-                                  tok_seg_host, ctx_w_host);
+    GenCall c("pipeline_generate_lens", s2, vq, ids, context, L, B, T, temps_host, nmask_host, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.keys.lens = ctx_lens_host; c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host; c.keys.w = ctx_w_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.ctemps = ctemps_host;
+    c.top_p = top_p;
+    c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.gscales = gscales_host;
+    return pipeline_generate(c);
 }
 
 // One MaskGIT step in which every image carries its own decode state (include/pmhip.h).  The host records are validated, staged
 // through the pinned ring into the workspace, and read from there by the sampling and re-masking kernels; with the graph flag the
 // step -- tower, sampling, re-masking: one linear chain -- is captured once per (B, context length) on handle-owned ids and
 // replayed, whatever the records say.
-// guides_host (pmhip_pipeline_step_slots_guided; NULL otherwise): per-image guidance.  The host decides "two tower passes or one"
-// per STEP -- two exactly when an active slot is guided -- and the two-pass chain (step_tower with the guide records + the same
-// tail) has a graph of its own; which rows the combination touches is decided on the device, from the staged records.
-// ctx_lens_host (pmhip_pipeline_step_slots_lens; NULL otherwise): per-image context lengths, staged by EVERY call -- also under
-// PMHIP_SLOTS_KEEP_CONTEXT, where the kept cross K/V serve whatever lengths this call brings.
-// The slots family's one builder: the argument list of pmhip_pipeline_step_slots_choice, the widest entry, -> the Step and the name
-// the messages carry: `narrow` (a narrower entry's own name, or the *_lens entry's for the widest) unless choice temperatures came.
-// neg_context / Ln / neg_lens_host (pmhip_pipeline_step_slots_negative, `kinds` set; NULL / 0 / NULL and PMHIP_SLOTS_KEEP_NEGATIVE
-// clear from the four narrower entries): guides_host[b].on then names what slot b is guided against -- 1 the pass without a
-// context, 2 the negative context's K/V -- and the host decides the passes per step: the conditional tower, the tower without a
-// context iff an active slot has on == 1, the tower against the negative set iff one has on == 2, each of the two followed by the
-// combine of its kind.  The negative set is prepared eagerly like the context's, or kept from the previous slots call.
-// filters / top_p_host (pmhip_pipeline_step_slots_filter; false / NULL from the five older entries): an active
-// slot may carry top-k up to n_embed and a nucleus mass.  The host decides the form of the sampling tail per STEP: the one
-// block-statistics launch of the older entries (their launches, graph key and graph) unless an active slot is of another class
-// (common.h pm_sample_class) -- then the launch per class, with the masses staged behind the choice temperatures.
-// counts_host (pmhip_pipeline_step_slots_edit; NULL from the six older entries): a re-masking count per slot,
-// -1 = the record's num_mask.  A step in which no active slot has a count >= 0 is the step without counts (launches, graph key and
-// graph); otherwise the counts are staged behind the masses and the re-masking launch is the form with a count per slot.
-// ctx_seg_host / tok_seg_host / region_host (pmhip_pipeline_step_slots_regions; NULL from the seven older entries; DESIGN.md section
-// 4v) and ctx_w_host (pmhip_pipeline_step_slots_weights; NULL from the eight older entries): region_host names
-// the kind of every slot -- 0 under its length, 1 under its key sets, 2 (with ctx_w_host only) under its key sets and its weights.
-// A step without an active slot of kind 1 or 2 is the step without the arrays; one without an active slot of kind 2 is the step of
-// the _regions entry (two picked cross-attention launches per layer, graph key suffix R); otherwise the weights are staged too and
-// the launches are three (suffix W).
-static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
-                           const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host, int flags,
-                           int64_t* pred_out, float* score_out, pmhip_stream stream, bool kinds = false, const float* neg_context = nullptr,
-                           int Ln = 0, const int32_t* neg_lens_host = nullptr, bool filters = false, const float* top_p_host = nullptr,
-                           const int32_t* counts_host = nullptr, const uint8_t* ctx_seg_host = nullptr, const uint32_t* tok_seg_host = nullptr,
-                           const uint8_t* region_host = nullptr, const float* ctx_w_host = nullptr) {
-    const bool keep_neg = kinds && (flags & PMHIP_SLOTS_KEEP_NEGATIVE) != 0;
-    const bool neg_set = neg_context || keep_neg;             // this call has a negative set, given or kept
-    const char* who = ctx_w_host ? "pipeline_step_slots_weights" : (ctx_seg_host || tok_seg_host || region_host) ? "pipeline_step_slots_regions"
-                      : counts_host ? "pipeline_step_slots_edit" : filters ? "pipeline_step_slots_filter"
-                              : (neg_set || neg_lens_host) ? "pipeline_step_slots_negative" : choice_host ? "pipeline_step_slots_choice" : narrow;
-    PM_REQUIRE(s2 && ids && slots_host && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
-    const bool have_context = context || ((flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0);
-    // regional slots (pmhip_pipeline_step_slots_regions; DESIGN.md section 4v): the three arrays together or none, the rules of
-    // check_segments for the ACTIVE slots that are flagged, the length check for every other slot
-    // weighted slots (pmhip_pipeline_step_slots_weights): region_host is a KIND per slot -- 0 under its length,
-    // 1 under its key sets, 2 under its key sets and its weights --, kind 2 only where ctx_w_host came; a kind-2 slot follows the
-    // rules of a regional one and the weight rules of check_weights
+// The host decides the step's FORM from the records of the active slots (SlotsPlan below): the tower passes, the form of the
+// cross-attention, of the sampling tail and of the re-masking launch.  Each form has a graph of its own, and a step in which no
+// active slot uses a feature is the step of the entry without it: its launches, its graph key and its graph.
+namespace {
+
+// The slots family's call record: the common head of its nine entries by the constructor, every optional feature at its neutral
+// value until an entry assigns it.  `narrow` is the name the entry's messages carry when no wider feature is present: its own, or
+// the *_lens entry's for the entries above that one.
+struct SlotsCall {
+    const char* narrow; pmhip_s2* s2; int64_t* ids;
+    // keys.lens (… _lens): staged by EVERY call -- also under PMHIP_SLOTS_KEEP_CONTEXT, where the kept cross K/V serve whatever
+    // lengths this call brings.  keys.seg / keys.tok with `region` (… _regions) and keys.w (… _weights; 4x):
+    // region names the kind of every slot -- 0 under its length, 1 under its key sets, 2 (with keys.w only) under its key sets and
+    // its weights.  An active slot of kind 1: two picked cross-attention launches per layer; of kind 2: the weights staged too, three.
+    CtxKeys keys; const uint8_t* region = nullptr;
+    int B; const pmhip_slot* slots; int flags;
+    int64_t* pred_out; float* score_out; pmhip_stream stream;
+    // per-image guidance (… _guided): two tower passes exactly when an active slot is guided; which rows the combination touches is
+    // decided on the device, from the staged records
+    const pmhip_slot_guide* guides = nullptr;
+    const float* choice = nullptr;                            // host [B]: choice temperatures (… _choice)
+    // (… _negative) kinds: guides[b].on names what slot b is guided against -- 1 the pass without a context, 2 the negative
+    // context's K/V -- and PMHIP_SLOTS_KEEP_NEGATIVE counts.  The passes per step: the conditional tower, the tower without a
+    // context iff an active slot has on == 1, the tower against the negative set iff one has on == 2, each of the two followed by
+    // the combine of its kind.  The negative set is prepared eagerly like the context's, or kept from the previous slots call.
+    bool kinds = false; NegSet neg;
+    // (… _filter) an active slot may carry top-k up to n_embed and a nucleus mass, host [B].  The sampling tail
+    // is the one block-statistics launch unless an active slot is of another class (common.h pm_sample_class): then the launch per class
+    bool filters = false; const float* top_p = nullptr;
+    // (… _edit) a re-masking count per slot, host [B], -1 = the record's num_mask; with an active slot at >= 0
+    // the re-masking launch is the form with a count per slot
+    const int32_t* counts = nullptr;
+    SlotsCall(const char* narrow_, pmhip_s2* s2_, int64_t* ids_, const float* context, int L, int B_, const pmhip_slot* slots_, int flags_,
+              int64_t* pred_out_, float* score_out_, pmhip_stream stream_)
+        : narrow(narrow_), s2(s2_), ids(ids_), keys(context, L), B(B_), slots(slots_), flags(flags_), pred_out(pred_out_), score_out(score_out_),
+          stream(stream_) {}
+    bool idle(int b) const { return (slots[b].step & PM_SLOT_IDLE) != 0; }
+};
+
+// What the host decides about a step from its records: the name its messages carry, which sets it has, and the step's form.
+struct SlotsPlan {
+    const char* who = nullptr;
+    bool keep_neg = false, neg_set = false;                   // the negative set is kept / this call has one, given or kept
     bool regions = false;                                     // an active slot is of kind 1 or 2: the picked cross-attention
     bool weighted = false;                                    // an active slot is of kind 2: its third launch
-    PM_REQUIRE((!ctx_seg_host == !tok_seg_host) && (!ctx_seg_host == !region_host),
-               "%s: ctx_seg_host, tok_seg_host and region_host come together (one of them is NULL)", who);
-    if (region_host) {
+    bool two_pass = false;                                    // an active slot is guided
+    bool pass_neg = false, pass_uncond = false;               // ... against the negative set / against no context
+    bool choice = false;                                      // an active slot has a choice temperature other than 0 (else: the step without)
+    bool chain = false;                                       // filters: an active slot is of another class than the block-statistics kernel's
+    bool edit = false;                                        // counts: an active slot brings a count of its own (>= 0)
+};
+
+bool slot_regional(const SlotsCall& c, const SlotsPlan& p, int b) { return p.regions && !c.idle(b) && c.region[b] >= 1; }
+bool slot_weighted(const SlotsCall& c, const SlotsPlan& p, int b) { return slot_regional(c, p, b) && c.region[b] == 2; }
+
+// plan: every check of the host records and the step's form, pure host code
+int slots_plan(const SlotsCall& c, SlotsPlan& p) {
+    pmhip_s2* s2 = c.s2;
+    const CtxKeys& k = c.keys;
+    const int B = c.B, L = k.L, Ln = c.neg.Ln;
+    p.keep_neg = c.kinds && (c.flags & PMHIP_SLOTS_KEEP_NEGATIVE) != 0;
+    p.neg_set = c.neg.context || p.keep_neg;
+    // (the entries above *_lens pass that entry's name as `narrow`: they report as *_lens when no wider feature is present)
+    const char* who = p.who = call_name({{k.w != nullptr, "pipeline_step_slots_weights"},
+                                         {k.seg || k.tok || c.region, "pipeline_step_slots_regions"},
+                                         {c.counts != nullptr, "pipeline_step_slots_edit"},
+                                         {c.filters, "pipeline_step_slots_filter"},
+                                         {p.neg_set || c.neg.lens, "pipeline_step_slots_negative"},
+                                         {c.choice != nullptr, "pipeline_step_slots_choice"}}, c.narrow);
+    PM_REQUIRE(s2 && c.ids && c.slots && B > 0, "%s: bad arguments (null handle, ids or slots, or B <= 0)", who);
+    const bool have_context = k.context || ((c.flags & PMHIP_SLOTS_KEEP_CONTEXT) && L > 0);
+    // regional slots (pmhip_pipeline_step_slots_regions; DESIGN.md section 4v): the three arrays together or none, the rules of
+    // check_segments for the ACTIVE slots that are flagged, the length check for every other slot
+    // weighted slots (pmhip_pipeline_step_slots_weights): region is a KIND per slot -- 0 under its length,
+    // 1 under its key sets, 2 under its key sets and its weights --, kind 2 only where the weights came; a kind-2 slot follows the
+    // rules of a regional one and the weight rules of check_weights
+    PM_REQUIRE((!k.seg == !k.tok) && (!k.seg == !c.region), "%s: ctx_seg_host, tok_seg_host and region_host come together (one of them is NULL)",
+               who);
+    if (c.region) {
         for (int b = 0; b < B; ++b) {
-            if (slots_host[b].step & PM_SLOT_IDLE) continue;
-            if (ctx_w_host) PM_REQUIRE(region_host[b] <= 2, "%s: slot %d: region_host=%d must be 0, 1 or 2", who, b, (int)region_host[b]);
-            else PM_REQUIRE(region_host[b] <= 1, "%s: slot %d: region_host=%d must be 0 or 1 (2 needs ctx_w_host)", who, b, (int)region_host[b]);
-            regions = regions || region_host[b] >= 1;
-            weighted = weighted || region_host[b] == 2;
+            if (c.idle(b)) continue;
+            if (k.w) PM_REQUIRE(c.region[b] <= 2, "%s: slot %d: region_host=%d must be 0, 1 or 2", who, b, (int)c.region[b]);
+            else PM_REQUIRE(c.region[b] <= 1, "%s: slot %d: region_host=%d must be 0 or 1 (2 needs ctx_w_host)", who, b, (int)c.region[b]);
+            p.regions = p.regions || c.region[b] >= 1;
+            p.weighted = p.weighted || c.region[b] == 2;
         }
     } else {
-        PM_REQUIRE(!ctx_w_host, "%s: ctx_w_host given without ctx_seg_host, tok_seg_host and region_host", who);
+        PM_REQUIRE(!k.w, "%s: ctx_w_host given without ctx_seg_host, tok_seg_host and region_host", who);
     }
-    auto regional = [&](int b) { return regions && !(slots_host[b].step & PM_SLOT_IDLE) && region_host[b] >= 1; };
-    auto weighted_slot = [&](int b) { return regional(b) && region_host[b] == 2; };
-    if (!regions) {
-        PM_TRY(check_ctx_lens(who, ctx_lens_host, have_context, L, B));
+    if (!p.regions) {
+        PM_TRY(check_ctx_lens(who, k.lens, have_context, L, B));
     } else {
         PM_REQUIRE(have_context && L > 0, "%s: regional slots given without a context", who);
         for (int b = 0; b < B; ++b) {
-            if (regional(b)) {
-                PM_TRY(check_segments_of(who, "slot", b, ctx_seg_host, tok_seg_host, L, s2->cfg.tokens));
-                if (weighted_slot(b)) PM_TRY(check_slot_weights(who, b, ctx_w_host, ctx_seg_host, tok_seg_host, L, s2->cfg.tokens));
+            if (slot_regional(c, p, b)) {
+                PM_TRY(check_segments_of(who, "slot", b, k.seg, k.tok, L, s2->cfg.tokens));
+                if (slot_weighted(c, p, b)) PM_TRY(check_slot_weights(who, b, k.w, k.seg, k.tok, L, s2->cfg.tokens));
             } else
-                PM_REQUIRE(!ctx_lens_host || (ctx_lens_host[b] >= 1 && ctx_lens_host[b] <= L), "%s: image %d: context length %d must be in [1, L=%d]",
-                           who, b, (int)ctx_lens_host[b], L);
+                PM_REQUIRE(!k.lens || (k.lens[b] >= 1 && k.lens[b] <= L), "%s: image %d: context length %d must be in [1, L=%d]", who, b,
+                           (int)k.lens[b], L);
         }
     }
-    const auto& c = s2->cfg;
-    PM_REQUIRE(c.n_embed % 64 == 0, "%s: n_embed=%d must be a multiple of 64", who, c.n_embed);
-    PM_REQUIRE(neg_set || !neg_lens_host, "%s: neg_lens_host given without a negative context", who);
-    PM_REQUIRE(!neg_set || Ln >= 1, "%s: negative context given with Ln=%d", who, Ln);
-    for (int b = 0; neg_lens_host && b < B; ++b)
-        PM_REQUIRE(neg_lens_host[b] >= 1 && neg_lens_host[b] <= Ln, "%s: slot %d: negative context length %d must be in [1, Ln=%d]", who, b,
-                   (int)neg_lens_host[b], Ln);
-    bool two_pass = false, choice = false;      // choice: an active slot has a choice temperature other than 0 (else: the step without)
-    bool pass_neg = false, pass_uncond = false;               // an active slot guided against the negative set / against no context
-    bool chain = false;                                       // filters: an active slot is of another class than the block-statistics kernel's
-    bool edit = false;                                        // counts_host: an active slot brings a count of its own (>= 0)
+    const auto& cfg = s2->cfg;
+    PM_REQUIRE(cfg.n_embed % 64 == 0, "%s: n_embed=%d must be a multiple of 64", who, cfg.n_embed);
+    PM_REQUIRE(p.neg_set || !c.neg.lens, "%s: neg_lens_host given without a negative context", who);
+    PM_REQUIRE(!p.neg_set || Ln >= 1, "%s: negative context given with Ln=%d", who, Ln);
+    for (int b = 0; c.neg.lens && b < B; ++b)
+        PM_REQUIRE(c.neg.lens[b] >= 1 && c.neg.lens[b] <= Ln, "%s: slot %d: negative context length %d must be in [1, Ln=%d]", who, b,
+                   (int)c.neg.lens[b], Ln);
     for (int b = 0; b < B; ++b) {
-        const pmhip_slot& sl = slots_host[b];
-        if (sl.step & PM_SLOT_IDLE) continue;
-        if (choice_host) {
-            PM_TRY(pm_check_choice_t(who, choice_host[b]));
-            choice = choice || choice_host[b] != 0.f;
+        const pmhip_slot& sl = c.slots[b];
+        if (c.idle(b)) continue;
+        if (c.choice) {
+            PM_TRY(pm_check_choice_t(who, c.choice[b]));
+            p.choice = p.choice || c.choice[b] != 0.f;
         }
-        if (filters) {
-            PM_REQUIRE(sl.topk >= 1 && sl.topk <= c.n_embed, "%s: slot %d: topk=%d must be in [1, n_embed=%d]", who, b, sl.topk, c.n_embed);
-            const float p = top_p_host ? top_p_host[b] : 1.f;
-            PM_TRY(pm_check_top_p((std::string(who) + ": slot " + std::to_string(b)).c_str(), p));
-            chain = chain || pm_sample_class(sl.topk, p < 1.f) != PM_CLASS_TILES;
+        if (c.filters) {
+            PM_REQUIRE(sl.topk >= 1 && sl.topk <= cfg.n_embed, "%s: slot %d: topk=%d must be in [1, n_embed=%d]", who, b, sl.topk, cfg.n_embed);
+            const float mass = c.top_p ? c.top_p[b] : 1.f;
+            PM_TRY(pm_check_top_p((std::string(who) + ": slot " + std::to_string(b)).c_str(), mass));
+            p.chain = p.chain || pm_sample_class(sl.topk, mass < 1.f) != PM_CLASS_TILES;
         } else {
             PM_REQUIRE(sl.topk >= 1 && sl.topk <= 8, "%s: slot %d: topk=%d must be in [1, 8]", who, b, sl.topk);
         }
-        if (counts_host) {
-            PM_REQUIRE(counts_host[b] >= -1 && counts_host[b] <= c.tokens, "%s: slot %d: count %d must be in [-1, tokens=%d]", who, b,
-                       (int)counts_host[b], c.tokens);
-            edit = edit || counts_host[b] >= 0;
+        if (c.counts) {
+            PM_REQUIRE(c.counts[b] >= -1 && c.counts[b] <= cfg.tokens, "%s: slot %d: count %d must be in [-1, tokens=%d]", who, b,
+                       (int)c.counts[b], cfg.tokens);
+            p.edit = p.edit || c.counts[b] >= 0;
         }
         // (a slot with a count of its own never reads the record's)
-        PM_REQUIRE(sl.num_mask >= 1 || (counts_host && counts_host[b] >= 0), "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
-        if (guides_host && guides_host[b].on) {
-            PM_REQUIRE(!kinds || guides_host[b].on <= 2, "%s: slot %d: on=%u must be 0, 1 or 2", who, b, guides_host[b].on);
-            PM_REQUIRE(std::isfinite(guides_host[b].scale), "%s: slot %d: the guidance scale must be finite", who, b);
-            PM_REQUIRE(L > 0 && (context || (flags & PMHIP_SLOTS_KEEP_CONTEXT)),
+        PM_REQUIRE(sl.num_mask >= 1 || (c.counts && c.counts[b] >= 0), "%s: slot %d: num_mask=%d must be >= 1", who, b, sl.num_mask);
+        if (c.guides && c.guides[b].on) {
+            PM_REQUIRE(!c.kinds || c.guides[b].on <= 2, "%s: slot %d: on=%u must be 0, 1 or 2", who, b, c.guides[b].on);
+            PM_REQUIRE(std::isfinite(c.guides[b].scale), "%s: slot %d: the guidance scale must be finite", who, b);
+            PM_REQUIRE(L > 0 && (k.context || (c.flags & PMHIP_SLOTS_KEEP_CONTEXT)),
                        "%s: slot %d: guidance needs a context (context NULL IS the unconditional branch)", who, b);
-            const bool against_neg = kinds && guides_host[b].on == 2;
-            PM_REQUIRE(!against_neg || neg_set, "%s: slot %d: on=2 needs a negative context, given or kept", who, b);
-            (against_neg ? pass_neg : pass_uncond) = true;
-            two_pass = true;
+            const bool against_neg = c.kinds && c.guides[b].on == 2;
+            PM_REQUIRE(!against_neg || p.neg_set, "%s: slot %d: on=2 needs a negative context, given or kept", who, b);
+            (against_neg ? p.pass_neg : p.pass_uncond) = true;
+            p.two_pass = true;
         }
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (keep_neg && (s2->slots_neg_Ln < 0 || s2->slots_neg_B != B || s2->slots_neg_Ln != Ln)) {
+    return PMHIP_OK;
+}
+
+// context: both sets prepared (eager, outside any graph) or kept, the key arrays staged -- the slots step's own variant of
+// stage_context: a kept set is refused unless a slots call prepared it at this shape, and under regional slots the rows of the other
+// slots are staged neutral.  Lc: the length the context's set was prepared at (0: without a context).
+int slots_context(const SlotsCall& c, const SlotsPlan& p, hipStream_t s, int& Lc) {
+    pmhip_s2* s2 = c.s2;
+    const CtxKeys& k = c.keys;
+    const int B = c.B, L = k.L, Ln = c.neg.Ln, tokens = s2->cfg.tokens;
+    const char* who = p.who;
+    if (p.keep_neg && (s2->slots_neg_Ln < 0 || s2->slots_neg_B != B || s2->slots_neg_Ln != Ln)) {
         pm_set_error("%s: keep-negative asked for B=%d Ln=%d, but %s", who, B, Ln,
                      s2->slots_neg_Ln < 0 ? "no slots call has prepared a negative context on this handle (or another entry point replaced it)"
                                           : "the prepared negative context has another B or Ln");
@@ -2377,8 +2604,8 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
     // a kept negative set outlives the preparation of a new context (which drops the handle's negative set: s2_prepare_context);
     // its K/V live in workspace buffers of their own, which only a negative preparation touches
     std::vector<CrossKV> kept_neg;
-    if (keep_neg) kept_neg = s2->cross_neg;
-    if (flags & PMHIP_SLOTS_KEEP_CONTEXT) {
+    if (p.keep_neg) kept_neg = s2->cross_neg;
+    if (c.flags & PMHIP_SLOTS_KEEP_CONTEXT) {
         if (s2->slots_ctx_L < 0 || s2->slots_ctx_B != B || s2->slots_ctx_L != L) {
             pm_set_error("%s: keep-context asked for B=%d L=%d, but %s", who, B, L,
                          s2->slots_ctx_L < 0 ? "no slots call has prepared a context on this handle (or another entry point replaced it)"
@@ -2386,155 +2613,198 @@ static int step_slots_call(const char* narrow, pmhip_s2* s2, int64_t* ids, const
             return PMHIP_ESTATE;
         }
     } else {
-        PM_TRY(s2_prepare_context(s2, context, L, B, s));     // eager, outside any graph
+        PM_TRY(s2_prepare_context(s2, k.context, L, B, s));
         s2->slots_ctx_B = B;
-        s2->slots_ctx_L = context ? L : 0;
+        s2->slots_ctx_L = k.context ? L : 0;
     }
-    const int Lc = s2->slots_ctx_L;
-    PM_REQUIRE(!ctx_lens_host || Lc > 0, "%s: ctx_lens_host given, but the kept context was prepared without one", who);
-    PM_REQUIRE(!regions || Lc > 0, "%s: regional slots given, but the kept context was prepared without one", who);
-    if (!regions) {
-        PM_TRY(s2_set_ctx_lens(s2, ctx_lens_host, L, B, s));
+    Lc = s2->slots_ctx_L;
+    PM_REQUIRE(!k.lens || Lc > 0, "%s: ctx_lens_host given, but the kept context was prepared without one", who);
+    PM_REQUIRE(!p.regions || Lc > 0, "%s: regional slots given, but the kept context was prepared without one", who);
+    if (!p.regions) {
+        PM_TRY(s2_set_ctx_lens(s2, k.lens, L, B, s));
     } else {
         // The lengths the want = 0 launch reads (L where none came; a regional or idle slot's is never read by a workgroup that
         // goes on), then the arrays with the rows of the slots that are not regional made neutral: they are not looked at here
         // and by no kernel -- one segment, every token attending to it.
         std::vector<int32_t> lens((size_t)B, L);
         std::vector<uint8_t> kseg((size_t)B * L, 0), flag((size_t)B, 0);
-        std::vector<float> wts(weighted ? (size_t)B * L : 0, 1.f);   // a slot of kind 0 or 1 is staged as 1; no kernel reads its rows
-        std::vector<uint32_t> tseg((size_t)B * c.tokens, 1u);
+        std::vector<float> wts(p.weighted ? (size_t)B * L : 0, 1.f);   // a slot of kind 0 or 1 is staged as 1; no kernel reads its rows
+        std::vector<uint32_t> tseg((size_t)B * tokens, 1u);
         for (int b = 0; b < B; ++b) {
-            if (!regional(b)) {
-                if (ctx_lens_host) lens[b] = ctx_lens_host[b];
+            if (!slot_regional(c, p, b)) {
+                if (k.lens) lens[b] = k.lens[b];
                 continue;
             }
-            flag[b] = region_host[b];
-            if (weighted_slot(b)) std::copy(ctx_w_host + (size_t)b * L, ctx_w_host + (size_t)(b + 1) * L, wts.begin() + (size_t)b * L);
-            memcpy(kseg.data() + (size_t)b * L, ctx_seg_host + (size_t)b * L, (size_t)L);
-            memcpy(tseg.data() + (size_t)b * c.tokens, tok_seg_host + (size_t)b * c.tokens, (size_t)c.tokens * 4);
+            flag[b] = c.region[b];
+            if (slot_weighted(c, p, b)) std::copy(k.w + (size_t)b * L, k.w + (size_t)(b + 1) * L, wts.begin() + (size_t)b * L);
+            memcpy(kseg.data() + (size_t)b * L, k.seg + (size_t)b * L, (size_t)L);
+            memcpy(tseg.data() + (size_t)b * tokens, k.tok + (size_t)b * tokens, (size_t)tokens * 4);
         }
         PM_TRY(s2_set_ctx_lens(s2, lens.data(), L, B, s));
         PM_TRY(s2_set_segments(s2, kseg.data(), tseg.data(), L, B, s, flag.data()));
-        if (weighted) PM_TRY(s2_set_weights(s2, wts.data(), L, B, s));
-        ++(weighted ? s2->slots_weight_steps : s2->slots_region_steps);
+        if (p.weighted) PM_TRY(s2_set_weights(s2, wts.data(), L, B, s));
     }
-    // the negative set: prepared (eager, outside any graph), kept, or -- a call that neither brings nor keeps one -- dropped
-    if (keep_neg) {
-        s2->cross_neg = kept_neg;                             // (neg_context is ignored, like context under PMHIP_SLOTS_KEEP_CONTEXT)
-    } else if (neg_context) {
+    // the negative set: prepared, kept, or -- a call that neither brings nor keeps one -- dropped
+    if (p.keep_neg) {
+        s2->cross_neg = kept_neg;                             // (neg.context is ignored, like the context under PMHIP_SLOTS_KEEP_CONTEXT)
+    } else if (c.neg.context) {
         const int ctx_B = s2->slots_ctx_B, ctx_L = s2->slots_ctx_L;
-        PM_TRY(s2_prepare_context(s2, neg_context, Ln, B, s, kCrossNegative));
+        PM_TRY(s2_prepare_context(s2, c.neg.context, Ln, B, s, kCrossNegative));
         s2->slots_ctx_B = ctx_B; s2->slots_ctx_L = ctx_L;     // (the preparation of either set forgets what slots calls prepared)
     } else {
         for (auto& ck : s2->cross_neg) ck = CrossKV{};
     }
     s2->slots_neg_B = B;
-    s2->slots_neg_Ln = neg_set ? Ln : -1;
-    if (neg_set) PM_TRY(s2_set_ctx_lens(s2, neg_lens_host, Ln, B, s, kCrossNegative));   // every call brings its own lengths (or NULL)
+    s2->slots_neg_Ln = p.neg_set ? Ln : -1;
+    if (p.neg_set) PM_TRY(s2_set_ctx_lens(s2, c.neg.lens, Ln, B, s, kCrossNegative));   // every call brings its own lengths (or NULL)
+    return PMHIP_OK;
+}
 
-    // the records: pinned ring entry -> device (the guide records sit behind the B slot records: 32 B bytes, a multiple of 16)
-    const size_t slot_bytes = sizeof(pmhip_slot) * (size_t)B, guide_bytes = sizeof(pmhip_slot_guide) * (size_t)B;
-    pmhip_slot* dslots;
+uint32_t word_of(float v) { uint32_t w; memcpy(&w, &v, 4); return w; }
+
+// records: one pinned ring entry -> the workspace, in five sections, each on a 16-byte boundary behind the one before it.  A section
+// has its place in the entry whether or not this step stages it (the layout is a contract with captured graphs).  The first two are
+// the caller's records as they came; the other three are 4-byte values per slot, padded to whole 16-byte words, an idle slot's (and
+// the padding) at the section's idle value.  The Step takes the device pointers; an unstaged section's is NULL.
+int slots_records(const SlotsCall& c, const SlotsPlan& p, hipStream_t s, Step& st) {
+    pmhip_s2* s2 = c.s2;
+    const size_t B = (size_t)c.B, words = (size_t)round_up(c.B, 4) * 4;
+    static_assert(sizeof(pmhip_slot) % 16 == 0, "the guide records sit right behind the slot records");
+    pmhip_slot* dslots = nullptr;
     pmhip_slot_guide* dguides = nullptr;
-    WS(s2->ws, "slots.dev", slot_bytes, dslots);
-    if (two_pass) WS(s2->ws, "slots.guides", guide_bytes, dguides);
-    // ... and behind those, on a 16-byte boundary, the B choice temperatures (padded to whole 16-byte words; an idle slot's is 0)
-    const size_t choice_at = (slot_bytes + guide_bytes + 15) & ~(size_t)15, choice_bytes = (size_t)round_up(B, 4) * 4;
-    float* dchoice = nullptr;
-    if (choice) WS(s2->ws, "slots.choice", choice_bytes, dchoice);
-    // ... and behind those (choice_bytes is whole 16-byte words) the B nucleus masses of a step whose tail is the launch per class,
-    // padded the same way; an idle slot's is 1
-    const size_t top_p_at = choice_at + choice_bytes, top_p_bytes = choice_bytes;
-    float* dtop_p = nullptr;
-    if (chain) WS(s2->ws, "slots.top_p", top_p_bytes, dtop_p);
-    // ... and behind those the B re-masking counts of a step in which an active slot brings its own, padded the
-    // same way; an idle slot's is 0
-    const size_t counts_at = top_p_at + top_p_bytes, counts_bytes = choice_bytes;
+    float *dchoice = nullptr, *dtop_p = nullptr;
     int32_t* dcounts = nullptr;
-    if (edit) WS(s2->ws, "slots.counts", counts_bytes, dcounts);
-    PM_TRY(s2->slots_ring.reserve(counts_at + counts_bytes));
+    struct Section { const char* ws; size_t bytes; bool staged; const void* host; bool padded; uint32_t idle; void** dev; size_t at; };
+    Section sections[5] = {
+        {"slots.dev", sizeof(pmhip_slot) * B, true, c.slots, false, 0, (void**)&dslots, 0},                  // the slot records
+        {"slots.guides", sizeof(pmhip_slot_guide) * B, p.two_pass, c.guides, false, 0, (void**)&dguides, 0},  // the guide records
+        {"slots.choice", words, p.choice, c.choice, true, word_of(0.f), (void**)&dchoice, 0},                 // choice temperatures; idle: 0
+        // the nucleus masses of a step whose tail is the launch per class; idle, or no masses given: 1
+        {"slots.top_p", words, p.chain, c.top_p, true, word_of(1.f), (void**)&dtop_p, 0},
+        // the re-masking counts of a step in which an active slot brings its own; idle: 0
+        {"slots.counts", words, p.edit, c.counts, true, 0, (void**)&dcounts, 0},
+    };
+    size_t end = 0;
+    for (Section& x : sections) {
+        x.at = (end + 15) & ~(size_t)15;
+        end = x.at + x.bytes;
+        if (x.staged) PM_TRY(s2->ws.get(x.ws, x.bytes, x.dev, s));
+    }
+    PM_TRY(s2->slots_ring.reserve(end));                      // the whole layout, whatever this step stages
     PM_TRY(s2->slots_ring.acquire());
-    PM_TRY(s2->slots_ring.stage(dslots, 0, slots_host, slot_bytes, s));
-    if (two_pass) PM_TRY(s2->slots_ring.stage(dguides, slot_bytes, guides_host, guide_bytes, s));
-    if (choice) {
-        std::vector<float> padded(choice_bytes / 4, 0.f);
-        for (int b = 0; b < B; ++b) padded[b] = (slots_host[b].step & PM_SLOT_IDLE) ? 0.f : choice_host[b];
-        PM_TRY(s2->slots_ring.stage(dchoice, choice_at, padded.data(), choice_bytes, s));
-    }
-    if (chain) {
-        std::vector<float> padded(top_p_bytes / 4, 1.f);
-        for (int b = 0; b < B; ++b) padded[b] = ((slots_host[b].step & PM_SLOT_IDLE) || !top_p_host) ? 1.f : top_p_host[b];
-        PM_TRY(s2->slots_ring.stage(dtop_p, top_p_at, padded.data(), top_p_bytes, s));
-    }
-    if (edit) {
-        std::vector<int32_t> padded(counts_bytes / 4, 0);
-        for (int b = 0; b < B; ++b) padded[b] = (slots_host[b].step & PM_SLOT_IDLE) ? 0 : counts_host[b];
-        PM_TRY(s2->slots_ring.stage(dcounts, counts_at, padded.data(), counts_bytes, s));
+    std::vector<uint32_t> padded;
+    for (const Section& x : sections) {
+        if (!x.staged) continue;
+        const void* src = x.host;
+        if (x.padded) {
+            padded.assign(x.bytes / 4, x.idle);
+            for (size_t b = 0; x.host && b < B; ++b)
+                if (!c.idle((int)b)) memcpy(&padded[b], static_cast<const unsigned char*>(x.host) + 4 * b, 4);
+            src = padded.data();
+        }
+        PM_TRY(s2->slots_ring.stage(*x.dev, x.at, src, x.bytes, s));
     }
     PM_TRY(s2->slots_ring.commit(s));
-    if (edit) ++s2->slots_edit_steps;
-    if (filters) ++(chain ? s2->slots_filter_chain : s2->slots_filter_tiles);
-    ++(pass_neg && pass_uncond ? s2->slots_three_pass : two_pass ? s2->slots_two_pass : s2->slots_one_pass);
-    Step st;
     st.slots = dslots;
     st.guides = dguides;
-    st.slots_neg = pass_neg;
-    st.slots_uncond = pass_uncond;
+    st.slots_neg = p.pass_neg;
+    st.slots_uncond = p.pass_uncond;
     st.choice_dev = dchoice;
-    st.filters = chain;                                       // every active slot of class T: the step of the entries without filters
+    st.filters = p.chain;                                     // every active slot of class T: the step of the entries without filters
     st.top_p_dev = dtop_p;
     st.counts = dcounts;                                      // NULL: the re-masking launch of the entries without counts
-    auto run_step = [&](int64_t* on_ids, int64_t* pred, float* score, hipStream_t on) -> int {
-        return sample_step(s2, nullptr, on_ids, B, st, nullptr, pred, score, on);
-    };
+    return PMHIP_OK;
+}
 
+// counters: a step is counted once it is staged, by each of its forms; a refused call counts nothing
+void slots_count(const SlotsCall& c, const SlotsPlan& p) {
+    pmhip_s2* s2 = c.s2;
+    if (p.regions) ++(p.weighted ? s2->slots_weight_steps : s2->slots_region_steps);
+    if (p.edit) ++s2->slots_edit_steps;
+    if (c.filters) ++(p.chain ? s2->slots_filter_chain : s2->slots_filter_tiles);
+    ++(p.pass_neg && p.pass_uncond ? s2->slots_three_pass : p.two_pass ? s2->slots_two_pass : s2->slots_one_pass);
+}
+
+// key: the graph cache key of a step.  It names the pass set; a step without a pass against the negative set keeps the key it had
+// before there was one, and one with it adds Ln and whether negative lengths came (the kernel form of that tower's cross-attention).
+// Behind it the form of the cross-attention (W three picked launches, R two, n per-image lengths), c the choice form of the
+// re-masking launch, F the sampling launch per class, E the re-masking launch with a count per slot.
+std::string slots_key(const SlotsCall& c, const SlotsPlan& p, int Lc) {
+    const char* passes = p.pass_neg ? (p.pass_uncond ? "slotsthreeB" : "slotsnegB") : p.two_pass ? "slotsguidedB" : "slotsB";
+    const std::string neg_key = p.pass_neg ? "N" + std::to_string(c.neg.Ln) + (c.neg.lens ? "n" : "") : "";
+    return passes + std::to_string(c.B) + "L" + std::to_string(Lc) + "f" + std::to_string(c.s2->sw.key()) +
+           (p.weighted ? "W" : p.regions ? "R" : c.keys.lens ? "n" : "") + (p.choice ? "c" : "") + neg_key + (p.chain ? "F" : "") +
+           (p.edit ? "E" : "");
+}
+
+// run: the step on the caller's ids, or -- with the graph flag -- captured once per key on handle-owned ids and replayed
+int slots_run(const SlotsCall& c, const SlotsPlan& p, const Step& st, int Lc, hipStream_t s) {
+    pmhip_s2* s2 = c.s2;
+    const int B = c.B;
     // ignored exactly when pipeline_generate ignores its graph request (same bits either way)
-    const bool graph = (flags & PMHIP_SLOTS_GRAPH) && !g_pm_timing_on.load() && !direct_dispatch_off();
-    if (!graph) return run_step(ids, pred_out, score_out, s);
+    const bool graph = (c.flags & PMHIP_SLOTS_GRAPH) && !g_pm_timing_on.load() && !direct_dispatch_off();
+    if (!graph) return sample_step(s2, nullptr, c.ids, B, st, nullptr, c.pred_out, c.score_out, s);
 
-    const size_t ids_bytes = (size_t)B * c.tokens * 8;
+    const size_t rows = (size_t)B * s2->cfg.tokens, ids_bytes = rows * 8;
     int64_t* gids;
     WS(s2->ws, "slots.ids", ids_bytes, gids);
-    PM_TRY(copy16_async(gids, ids, ids_bytes, s));
-    // the key names the pass set; a step without a pass against the negative set keeps the key it had before there was one, and
-    // one with it adds Ln and whether negative lengths came (the kernel form of that tower's cross-attention)
-    const char* passes = pass_neg ? (pass_uncond ? "slotsthreeB" : "slotsnegB") : two_pass ? "slotsguidedB" : "slotsB";
-    const std::string neg_key = pass_neg ? "N" + std::to_string(Ln) + (neg_lens_host ? "n" : "") : "";
-    GraphEntry& ge = s2->graphs[passes + std::to_string(B) + "L" + std::to_string(Lc) + "f" + std::to_string(s2->sw.key()) +
-                                (weighted ? "W" : regions ? "R" : ctx_lens_host ? "n" : "") + (choice ? "c" : "") + neg_key + (chain ? "F" : "") + (edit ? "E" : "")];
-    PM_TRY(run_graphs(s2, nullptr, ge, 1, s, [&](hipStream_t on, size_t) { return run_step(gids, nullptr, nullptr, on); },
+    PM_TRY(copy16_async(gids, c.ids, ids_bytes, s));
+    PM_TRY(run_graphs(s2, nullptr, s2->graphs[slots_key(c, p, Lc)], 1, s,
+                      [&](hipStream_t on, size_t) { return sample_step(s2, nullptr, gids, B, st, nullptr, nullptr, nullptr, on); },
                       [](size_t) { return PMHIP_OK; }));
-    PM_TRY(copy16_async(ids, gids, ids_bytes, s));
+    PM_TRY(copy16_async(c.ids, gids, ids_bytes, s));
     StepBufs b;
-    PM_TRY(pred_bufs(s2, (size_t)B * c.tokens, b, s));
-    return copy_aux(b, (size_t)B * c.tokens, pred_out, score_out, s);
+    PM_TRY(pred_bufs(s2, rows, b, s));
+    return copy_aux(b, rows, c.pred_out, c.score_out, s);
+}
+
+}  // namespace
+
+// The slots family's one builder: the record -> the step, phase by phase.
+static int step_slots_call(const SlotsCall& c) {
+    SlotsPlan p;
+    PM_TRY(slots_plan(c, p));
+    hipStream_t s = (hipStream_t)c.stream;
+    int Lc = 0;
+    PM_TRY(slots_context(c, p, s, Lc));
+    Step st;
+    PM_TRY(slots_records(c, p, s, st));
+    slots_count(c, p);
+    return slots_run(c, p, st, Lc, s);
 }
 
 extern "C" int pmhip_pipeline_step_slots(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
                                          int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots", s2, ids, context, L, B, nullptr, slots_host, nullptr, nullptr, flags, pred_out, score_out, stream);
+    SlotsCall c("pipeline_step_slots", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    return step_slots_call(c);
 }
 
 extern "C" int pmhip_pipeline_step_slots_guided(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const pmhip_slot* slots_host,
                                                 const pmhip_slot_guide* guides_host, int flags, int64_t* pred_out, float* score_out,
                                                 pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_guided", s2, ids, context, L, B, nullptr, slots_host, guides_host, nullptr, flags, pred_out,
-                           score_out, stream);
+    SlotsCall c("pipeline_step_slots_guided", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.guides = guides_host;
+    return step_slots_call(c);
 }
 
 extern "C" int pmhip_pipeline_step_slots_lens(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                                               const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, int flags,
                                               int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, nullptr, flags, pred_out,
-                           score_out, stream);
+    SlotsCall c("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guides = guides_host;
+    return step_slots_call(c);
 }
 
 // choice_host NULL, or 0 for every active slot: exactly pmhip_pipeline_step_slots_lens
 extern "C" int pmhip_pipeline_step_slots_choice(pmhip_s2* s2, int64_t* ids, const float* context, int L, int B, const int32_t* ctx_lens_host,
                                                 const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
                                                 int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
-                           score_out, stream);
+    SlotsCall c("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guides = guides_host;
+    c.choice = choice_host;
+    return step_slots_call(c);
 }
 
 // neg_context NULL, PMHIP_SLOTS_KEEP_NEGATIVE clear and no active slot with on == 2: exactly pmhip_pipeline_step_slots_choice
@@ -2542,8 +2812,12 @@ extern "C" int pmhip_pipeline_step_slots_negative(pmhip_s2* s2, int64_t* ids, co
                                                   const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
                                                   const float* neg_context, int Ln, const int32_t* neg_lens_host, int flags,
                                                   int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
-                           score_out, stream, true, neg_context, Ln, neg_lens_host);
+    SlotsCall c("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guides = guides_host;
+    c.choice = choice_host;
+    c.kinds = true; c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    return step_slots_call(c);
 }
 
 // top_p_host NULL and every active slot at topk <= 8: exactly pmhip_pipeline_step_slots_negative
@@ -2551,8 +2825,13 @@ extern "C" int pmhip_pipeline_step_slots_filter(pmhip_s2* s2, int64_t* ids, cons
                                                 const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
                                                 const float* neg_context, int Ln, const int32_t* neg_lens_host, const float* top_p_host,
                                                 int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
-                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host);
+    SlotsCall c("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guides = guides_host;
+    c.choice = choice_host;
+    c.kinds = true; c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.filters = true; c.top_p = top_p_host;
+    return step_slots_call(c);
 }
 
 // every active slot at -1 (or counts_host NULL): exactly pmhip_pipeline_step_slots_filter
@@ -2560,8 +2839,14 @@ extern "C" int pmhip_pipeline_step_slots_edit(pmhip_s2* s2, int64_t* ids, const 
                                               const pmhip_slot* slots_host, const pmhip_slot_guide* guides_host, const float* choice_host,
                                               const float* neg_context, int Ln, const int32_t* neg_lens_host, const float* top_p_host,
                                               const int32_t* counts_host, int flags, int64_t* pred_out, float* score_out, pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
-                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host, counts_host);
+    SlotsCall c("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guides = guides_host;
+    c.choice = choice_host;
+    c.kinds = true; c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.filters = true; c.top_p = top_p_host;
+    c.counts = counts_host;
+    return step_slots_call(c);
 }
 
 // no active slot with region_host == 1 (or the three arrays NULL): exactly pmhip_pipeline_step_slots_edit
@@ -2571,9 +2856,15 @@ extern "C" int pmhip_pipeline_step_slots_regions(pmhip_s2* s2, int64_t* ids, con
                                                  const int32_t* counts_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
                                                  const uint8_t* region_host, int flags, int64_t* pred_out, float* score_out,
                                                  pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
-                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host, counts_host, ctx_seg_host, tok_seg_host,
-                           region_host);
+    SlotsCall c("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guides = guides_host;
+    c.choice = choice_host;
+    c.kinds = true; c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.filters = true; c.top_p = top_p_host;
+    c.counts = counts_host;
+    c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host; c.region = region_host;
+    return step_slots_call(c);
 }
 
 // steps of that entry that ran the two-launch cross-attention (an active slot was regional)
@@ -2590,9 +2881,16 @@ extern "C" int pmhip_pipeline_step_slots_weights(pmhip_s2* s2, int64_t* ids, con
                                                  const int32_t* counts_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
                                                  const uint8_t* region_host, const float* ctx_w_host, int flags, int64_t* pred_out,
                                                  float* score_out, pmhip_stream stream) {
-    return step_slots_call("pipeline_step_slots_lens", s2, ids, context, L, B, ctx_lens_host, slots_host, guides_host, choice_host, flags, pred_out,
-                           score_out, stream, true, neg_context, Ln, neg_lens_host, true, top_p_host, counts_host, ctx_seg_host, tok_seg_host,
-                           region_host, ctx_w_host);
+    SlotsCall c("pipeline_step_slots_lens", s2, ids, context, L, B, slots_host, flags, pred_out, score_out, stream);
+    c.keys.lens = ctx_lens_host;
+    c.guides = guides_host;
+    c.choice = choice_host;
+    c.kinds = true; c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.filters = true; c.top_p = top_p_host;
+    c.counts = counts_host;
+    c.keys.seg = ctx_seg_host; c.keys.tok = tok_seg_host; c.region = region_host;
+    c.keys.w = ctx_w_host;
+    return step_slots_call(c);
 }
 
 // steps of that entry that ran the three-launch cross-attention (an active slot was weighted)
@@ -2658,7 +2956,14 @@ extern "C" int pmhip_pipeline_generate_edit(pmhip_s2* s2, pmhip_vqgan* vq, int64
                                             float top_p, const float* neg_context, int Ln, const int32_t* neg_lens_host,
                                             const float* gscales_host) {
     PM_REQUIRE(nmask_img_host, "pipeline_generate_edit: null count table");
-    return pipeline_generate_call("pipeline_generate_edit", s2, vq, ids, context, L, B, ctx_lens_host, T, temps_host, nullptr, decode_host,
-                                  topk, seed, image_base, imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream, guided,
-                                  guidance_scale, ctemps_host, top_p, neg_context, Ln, neg_lens_host, gscales_host, nmask_img_host);
+    GenCall c("pipeline_generate_edit", s2, vq, ids, context, L, B, T, temps_host, nullptr, decode_host, topk, seed, image_base,
+              imgs_out, use_graph, stream, imgs_host, host_stride, copy_stream);
+    c.keys.lens = ctx_lens_host;
+    c.guided = guided; c.guidance_scale = guidance_scale;
+    c.ctemps = ctemps_host;
+    c.top_p = top_p;
+    c.neg.context = neg_context; c.neg.Ln = Ln; c.neg.lens = neg_lens_host;
+    c.gscales = gscales_host;
+    c.nmask_img = nmask_img_host;
+    return pipeline_generate(c);
 }

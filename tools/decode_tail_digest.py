@@ -8,7 +8,8 @@ tolerance; this is for "bit for bit what another commit computes": run it on two
 nucleus filter (and so wide top-k, choice temperatures, context lengths and per-request guidance) can be the other side.
 The last section -- regional prompts, prompt weights, a negative prompt under a schedule, edit, the attention maps and a session
 that mixes the request kinds -- needs a commit that has prompt weights in sessions and the maps
-(profiles/host_keys_digest_*.jsonl).
+(profiles/host_keys_digest_*.jsonl).  Behind every session and every dtype section one more line gives (entries, captured) of
+the tiny pipeline's stage-2 graph cache (profiles/engine_records_digest_parent.jsonl).
 """
 import argparse
 import hashlib
@@ -41,6 +42,14 @@ def main():
 
     def emit(case, **tensors):
         line = json.dumps({"case": case, **{k: sha(v) for k, v in tensors.items()}})
+        print(line)
+        if out:
+            out.write(line + "\n")
+
+    def emit_graphs(case):
+        """(entries, captured) of the tiny pipeline's stage-2 graph cache: a changed graph key shows as a changed count even where
+        the ids agree"""
+        line = json.dumps({"case": case, "graph_count": list(pipe.engine().graph_count())})
         print(line)
         if out:
             out.write(line + "\n")
@@ -202,6 +211,7 @@ def main():
                          guidance_scale=scale, choice_temperature=choice)
             for f in sorted(s.drain(), key=lambda f: f.handle.number):
                 emit(f"session choice {tag} graph={int(graph)} request={f.handle.number}", ids=f.ids, image=f.image)
+            emit_graphs(f"session choice {tag} graph={int(graph)} graphs")
         # a decode session of four requests, two of them guided
         for graph in (False, True):
             s = pipe.decode_session(slots=4, conditional=True, use_graph=graph)
@@ -209,6 +219,7 @@ def main():
                 s.submit(context=ctx[i], timesteps=steps, temperature=temp, topk=topk, seed=100 + i, image_index=2 ** 33 + i, guidance_scale=scale)
             for f in sorted(s.drain(), key=lambda f: f.handle.number):
                 emit(f"session {tag} graph={int(graph)} request={f.handle.number}", ids=f.ids, image=f.image)
+            emit_graphs(f"session {tag} graph={int(graph)} graphs")
         # the host request path: what says which context rows a token attends to (regional prompts, prompt weights alone and beside
         # lengths), a negative prompt under a guidance schedule, edit, the attention maps, and a session that mixes the request kinds
         krng = np.random.default_rng(17)
@@ -253,6 +264,8 @@ def main():
                      image_index=2 ** 33 + 3)
             for f in sorted(s.drain(), key=lambda f: f.handle.number):
                 emit(f"session mixed {tag} graph={int(graph)} request={f.handle.number}", ids=f.ids, image=f.image)
+            emit_graphs(f"session mixed {tag} graph={int(graph)} graphs")
+        emit_graphs(f"section {tag} graphs")
     pipe.set_compute_dtype(torch.float32)
     if out:
         out.close()
