@@ -121,9 +121,10 @@ struct PmStepSource {
     PmStepSource with_top_p(float p) const { PmStepSource r = *this; r.top_p = p; return r; }
     // The re-masking count PER IMAGE (pm_remask only): a device int32 [B] beside a BATCH or PARAMS source --
     // image b re-masks counts[b] positions instead of num_mask / gp->nmask[step], 0 leaving its row untouched; the choice values keep
-    // coming from the source's kind.  NULL (the default): the kernels that ran before.  Appended: nothing above moves.
+    // coming from the source's kind.  NULL (the default): the source's own count.
     // Beside a SLOTS source the table is a count per SLOT: counts[b] < 0 the record's num_mask (with its clamp
-    // to 1), 0 the row untouched, > 0 exactly that many -- kernels of their own again, the step values from the record.
+    // to 1), 0 the row untouched, > 0 exactly that many; the step values from the record.  Every form is an instantiation of the one
+    // re-masking kernel (sample.hip remask_kernel<E, SLOTS, COUNTS, CHOICE>), and image_step there states each rule once.
     const int32_t* counts = nullptr;
     PmStepSource with_counts(const int32_t* dev) const { PmStepSource r = *this; r.counts = dev; return r; }
     // The sampler filters PER IMAGE (pm_sample_rows only, a SLOTS source): every slot's top-k in 1..V and its

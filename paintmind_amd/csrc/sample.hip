@@ -22,13 +22,19 @@
 //
 // remask: per image, the num_mask highest scores get the mask id (generate.py:175-179); bitonic sort
 // of 64-bit (score, reversed index) keys (remask_key) gives the exact (score desc, index asc) order; the keys stay in registers
-// (remask_reg_kernel, round 5; the all-LDS sort of rounds 1-4 is gone).
+// (remask_select, round 5; the all-LDS sort of rounds 1-4 is gone).  ONE kernel, remask_kernel<E, SLOTS, COUNTS, CHOICE>: the forms
+// differ in where an image's count and choice values come from (image_step) and in whether the keys are perturbed (remask_choice_keys).
 //
 // The sampling kernels differ in how they find the k candidates and (the tiles kernel) in how they round the confidence.  Everything
-// else is ONE piece of device code: where a row's step values come from (row_step: the kernel arguments, the PmGenParams block of a
-// replayed graph, or the pmhip_slot record of the row's image -- common.h PmStepSource), an element's noise and perturbed value
-// (perturbed), the draw among up to 64 candidates (draw_among) and the store of the row's outcome (store_outcome).  The host side
-// has one launcher per kernel family (pm_sample_rows, pm_remask): one copy of the checks, one place that picks the instantiation.
+// else is ONE piece of device code, each a function with its own signature: a wave's entry (wave_row, row_entry: the lane, the class
+// test, the logits row) and where the row's step values come from (row_step: the kernel arguments, the PmGenParams block of a
+// replayed graph, or the pmhip_slot record of the row's image -- common.h PmStepSource), the resident row and its normaliser
+// (resident_row), an element's noise and perturbed value (perturbed), the draw among up to 64 candidates (draw_among) and the store
+// of the row's outcome (store_outcome).  The host side has one launcher per kernel family (pm_sample_rows, pm_remask): one copy of
+// the checks, one place that picks the instantiation.
+// The one exception: the wide and the nucleus kernel still share their selection and their draw as two statement fragments,
+// sample_select_prologue.h and sample_select_draw.h (each says what it expects in scope).  As functions they compute the same, but
+// the register allocation of the 8192 and 16384 classes moves across an occupancy step (DESIGN.md section 4zj has the figures).
 //
 // Which of the four sampling kernels serves a row is pm_sample_class (common.h), a function of (top-k, top_p < 1).  A batch-scalar
 // launch asks it once; a per-image launch with filters is four launches, one per class, in which every
@@ -140,42 +146,76 @@ __device__ __forceinline__ bool slot_in_class(int cls, const RowStep& rs, int ro
     return !rs.idle && pm_sample_class(rs.topk, top_p < 1.f) == cls;
 }
 
-// its sibling for the re-masking kernel (one workgroup per image): how many positions image `img` masks; false: an idle slot
-template <bool SLOTS>
-__device__ __forceinline__ bool image_num_mask(int& num_mask, int img, const PmGenParams* __restrict__ gp, int step,
-                                               const pmhip_slot* __restrict__ slots) {
+// ---- the entry of a sampling kernel: one wave per row.  wave_row() is the row; a wave whose row is >= M leaves at once, all its
+// lanes together -- a test the kernel makes itself, in front of everything (a helper that made it, and handed the rest back through
+// a flag, left the compiler a merged path on which a row's step values are resolved and held before the row is known to exist).
+// row_entry then leaves the lane, the row's step values (row_step; `args` brings the kernel arguments), its nucleus mass (`top_p` as
+// given, or the slot's), its logits row -- row % period under PERIOD -- and `served`: false only in a per-image launch with filters
+// (CLS >= 0), for a live slot's row of another class.  The whole wave gets the same answer.  An idle slot's row comes back served
+// with rs.idle set: the kernel decides (the block-statistics kernel writes it, the others leave).
+__device__ __forceinline__ int wave_row() { return blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6); }
+
+struct RowEntry { int lane; RowStep rs; float top_p; int lr; const float* lrow; bool served; };
+
+template <bool SLOTS, bool PERIOD, int CLS = -1>
+__device__ __forceinline__ RowEntry row_entry(int row, RowStep args, float top_p, const float* logits, int ldl, const PmGenParams* gp,
+                                              int period, const pmhip_slot* slots, int tokens, const float* top_p_dev) {
+    RowEntry en;
+    en.lane = threadIdx.x & 63;
+    en.rs = row_step<SLOTS>(args, row, gp, slots, tokens);
+    en.top_p = top_p;
+    en.served = true;
+    if constexpr (SLOTS && CLS >= 0) en.served = slot_in_class(CLS, en.rs, row, tokens, top_p_dev, en.top_p) || en.rs.idle;
+    en.lr = PERIOD ? row % period : row;
+    en.lrow = logits + (size_t)en.lr * ldl;
+    return en;
+}
+
+// ---- the step values of one image for the re-masking kernel (one workgroup per image): how many positions it masks and, for the
+// CHOICE form, the choice temperature t and the image's Philox stream -- element i draws at counter
+// (base + i, 0xFFFFFFFF, step) under the seed.  `v` brings the kernel arguments.  false: the workgroup leaves its row untouched.
+// Every rule about the count is here and nowhere else:
+//   the arguments / gp / the slot record as the source      num_mask, gp->nmask[step] or the record's, clamped to [1, N]; an idle
+//                                                           slot leaves
+//   COUNTS beside BATCH or PARAMS    c = counts[img]: c <= 0 leaves, c > N is the whole row
+//   COUNTS beside SLOTS              an idle slot leaves whatever its count; c == 0 leaves; c < 0 is the
+//                                                           record's num_mask with the clamp to 1; c > 0 is exactly c (above N: the row)
+// The choice values never depend on COUNTS.  BATCH: the arguments, base = row_base + img * N; PARAMS: t = gp->ctemps[step], seed and
+// row base from the block; SLOTS: t = choice[img] (a device float [B] beside the records), seed, step and image_index * N from the
+// record, which is read once.
+struct ImageStep { int num_mask; float t; uint64_t seed; uint32_t step; uint64_t base; };
+
+template <bool SLOTS, bool COUNTS, bool CHOICE>
+__device__ __forceinline__ bool image_step(ImageStep& v, int img, int N, const PmGenParams* gp, const pmhip_slot* slots,
+                                           const int32_t* counts, const float* choice) {
+    int c = -1;                                            // the table's count; below 0: the source's own
+    if constexpr (COUNTS) {
+        c = counts[img];
+        if (SLOTS ? c == 0 : c <= 0) return false;
+    }
     if constexpr (SLOTS) {
         const pmhip_slot sl = slots[img];
         if (sl.step & PM_SLOT_IDLE) return false;
-        num_mask = sl.num_mask;
-    } else if (gp) num_mask = gp->nmask[step];
-    return true;
-}
-
-// and the values the CHOICE form of the re-masking kernel adds: the step's choice temperature t and the
-// Philox stream of the image -- element i draws at counter (base + i, 0xFFFFFFFF, step) under the seed.  BATCH: the kernel
-// arguments in `v`, base = row_base + img * N; PARAMS: t = gp->ctemps[step], seed and row base from the block; SLOTS: t =
-// choice[img] (a device float [B] beside the slot records), seed, step and image index from the slot.  false: an idle slot.
-struct ImageChoice { int num_mask; float t; uint64_t seed; uint32_t step; uint64_t base; };
-
-template <bool SLOTS>
-__device__ __forceinline__ bool image_choice(ImageChoice& v, int img, int N, const PmGenParams* __restrict__ gp,
-                                             const pmhip_slot* __restrict__ slots, const float* __restrict__ choice) {
-    if (!image_num_mask<SLOTS>(v.num_mask, img, gp, (int)v.step, slots)) return false;
-    if constexpr (SLOTS) {
-        const pmhip_slot sl = slots[img];
-        v.t = choice[img];
-        v.seed = sl.seed;
-        v.step = sl.step;
-        v.base = sl.image_index * (uint64_t)N;
+        v.num_mask = sl.num_mask;
+        if constexpr (CHOICE) {
+            v.t = choice[img];
+            v.seed = sl.seed;
+            v.step = sl.step;
+            v.base = sl.image_index * (uint64_t)N;
+        }
     } else {
         if (gp) {
-            v.t = gp->ctemps[v.step];
-            v.seed = gp->seed;
-            v.base = gp->row_base;
+            v.num_mask = gp->nmask[v.step];
+            if constexpr (CHOICE) {
+                v.t = gp->ctemps[v.step];
+                v.seed = gp->seed;
+                v.base = gp->row_base;
+            }
         }
         v.base += (uint64_t)img * (uint64_t)N;
     }
+    if (c > 0) v.num_mask = c;
+    v.num_mask = v.num_mask < 1 ? 1 : (v.num_mask > N ? N : v.num_mask);
     return true;
 }
 
@@ -229,7 +269,29 @@ __device__ __forceinline__ void store_outcome(int row, bool drawn, int64_t pred,
 // instantiation never looks at `period`.
 // SLOTS (a launch of class R for pmhip_sample_rows_slots_filter; no PERIOD form): the step values of row r come from slots[r /
 // tokens] (row_step), and only the rows whose slot is of this kernel's class are served (slot_in_class); everything below the
-// prologue is the code of the scalar form.
+// entry is the code of the scalar form.
+// resident_row: the row into registers (a column >= V reads as -inf) and the softmax normaliser of the UNfiltered row
+// (generate.py:170): max, sum of exp in lane order.  One copy of the expressions: the row, wide, nucleus and forced kernels give a
+// drawn id the same confidence bits because they all come through here.
+template <int NV4>
+__device__ __forceinline__ void resident_row(float4 (&x)[NV4], float& mx, float& se, const float* lrow, int lane, int V) {
+#pragma unroll
+    for (int g = 0; g < NV4; ++g) {
+        const int col = (g * 64 + lane) * 4;
+        x[g] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        if (col < V) x[g] = *reinterpret_cast<const float4*>(lrow + col);
+    }
+    mx = -INFINITY;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g) mx = fmaxf(mx, fmaxf(fmaxf(x[g].x, x[g].y), fmaxf(x[g].z, x[g].w)));
+    mx = wave_max(mx);
+    se = 0.f;
+#pragma unroll
+    for (int g = 0; g < NV4; ++g)
+        se += (__expf(x[g].x - mx) + __expf(x[g].y - mx)) + (__expf(x[g].z - mx) + __expf(x[g].w - mx));
+    se = wave_sum(se);
+}
+
 template <int NV4, bool PERIOD = false, bool SLOTS = false>
 __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
     const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, int64_t mask_id, int topk,
@@ -237,35 +299,17 @@ __global__ __launch_bounds__(THREADS) void sample_rows_kernel(
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V,
     const PmGenParams* __restrict__ gp, int period, const pmhip_slot* __restrict__ slots, int tokens,
     const float* __restrict__ top_p_dev) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+    const int row = wave_row();
     if (row >= M) return;                                  // whole wave exits together
-    const RowStep rs = row_step<SLOTS>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, slots, tokens);
-    if constexpr (SLOTS) {                                 // wave-uniform, like the kernel argument it replaces
-        float mass;
-        if (!slot_in_class(PM_CLASS_ROWS, rs, row, tokens, top_p_dev, mass)) return;
-        topk = rs.topk;
-    }
-    const int lr = PERIOD ? row % period : row;
-    const float* lrow = logits + (size_t)lr * ldl;
-
+    const RowEntry en = row_entry<SLOTS, PERIOD, PM_CLASS_ROWS>(row, RowStep{topk, temperature, seed, step, row_base, false}, 1.f, logits, ldl,
+                                                                gp, period, slots, tokens, top_p_dev);
+    if (!en.served || en.rs.idle) return;                  // (a per-image launch: the live rows of this class only)
+    const int lane = en.lane;
+    const RowStep& rs = en.rs;
+    topk = rs.topk;                                        // (a slot's: wave-uniform, like the kernel argument it replaces)
     float4 x[NV4];
-#pragma unroll
-    for (int g = 0; g < NV4; ++g) {
-        const int col = (g * 64 + lane) * 4;
-        x[g] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        if (col < V) x[g] = *reinterpret_cast<const float4*>(lrow + col);
-    }
-    // ---- softmax normaliser of the UNfiltered row (generate.py:170)
-    float mx = -INFINITY;
-#pragma unroll
-    for (int g = 0; g < NV4; ++g) mx = fmaxf(mx, fmaxf(fmaxf(x[g].x, x[g].y), fmaxf(x[g].z, x[g].w)));
-    mx = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int g = 0; g < NV4; ++g)
-        se += (__expf(x[g].x - mx) + __expf(x[g].y - mx)) + (__expf(x[g].z - mx) + __expf(x[g].w - mx));
-    se = wave_sum(se);
+    float mx, se;
+    resident_row<NV4>(x, mx, se, en.lrow, lane, V);
 
     // ---- top-k: k rounds of {per-lane best group, wave arg-max, winner removes its element}
     Cand mine{-INFINITY, 0x7fffffff};                      // candidate r is kept by lane r
@@ -426,34 +470,18 @@ template <int NV4>
 __global__ __launch_bounds__(THREADS) void sample_forced_kernel(
     const float* __restrict__ logits, int ldl, const int64_t* __restrict__ ids_in, const int64_t* __restrict__ target, int64_t mask_id,
     int64_t* __restrict__ pred_out, int64_t* __restrict__ ids_out, float* __restrict__ score_out, int M, int V) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
+    const int row = wave_row();
     if (row >= M) return;                                  // whole wave exits together
-    const float* lrow = logits + (size_t)row * ldl;
-
+    const RowEntry en = row_entry<false, false>(row, RowStep{}, 1.f, logits, ldl, nullptr, 0, nullptr, 0, nullptr);   // (no step values here)
     float4 x[NV4];
-#pragma unroll
-    for (int g = 0; g < NV4; ++g) {
-        const int col = (g * 64 + lane) * 4;
-        x[g] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        if (col < V) x[g] = *reinterpret_cast<const float4*>(lrow + col);
-    }
-    // ---- softmax normaliser of the UNfiltered row: sample_rows_kernel's expressions, in its order
-    float mx = -INFINITY;
-#pragma unroll
-    for (int g = 0; g < NV4; ++g) mx = fmaxf(mx, fmaxf(fmaxf(x[g].x, x[g].y), fmaxf(x[g].z, x[g].w)));
-    mx = wave_max(mx);
-    float se = 0.f;
-#pragma unroll
-    for (int g = 0; g < NV4; ++g)
-        se += (__expf(x[g].x - mx) + __expf(x[g].y - mx)) + (__expf(x[g].z - mx) + __expf(x[g].w - mx));
-    se = wave_sum(se);
+    float mx, se;
+    resident_row<NV4>(x, mx, se, en.lrow, en.lane, V);
 
-    if (lane == 0) {
+    if (en.lane == 0) {
         const int64_t t = target[row];
         const bool ok = t >= 0 && t < (int64_t)V;          // in front of the load: an id from outside indexes nothing
         float v = -INFINITY;
-        if (ok) v = lrow[t];
+        if (ok) v = en.lrow[t];
         store_outcome(row, ok, t, expf(v - mx) / se, ids_in, mask_id, pred_out, ids_out, score_out);
     }
 }
@@ -476,21 +504,19 @@ __global__ __launch_bounds__(THREADS) void sample_tiles_kernel(
     const PmGenParams* __restrict__ gp, const pmhip_slot* __restrict__ slots, int tokens, int period,
     const float* __restrict__ top_p_dev) {
     __shared__ float2 sh[DENSE ? THREADS / 64 : 1][DENSE ? NB2 * 64 : 1];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int row = blockIdx.x * (THREADS / 64) + wave;
+    const int row = wave_row(), wave = threadIdx.x >> 6;
     if (row >= M) return;                                  // whole wave exits together (no workgroup barrier below)
-    const RowStep rs = row_step<SLOTS>(RowStep{topk, temperature, seed, step, row_base, false}, row, gp, slots, tokens);
+    const RowEntry en = row_entry<SLOTS, PERIOD, FILTER ? (int)PM_CLASS_TILES : -1>(row, RowStep{topk, temperature, seed, step, row_base, false},
+                                                                                    1.f, logits, ldl, gp, period, slots, tokens, top_p_dev);
+    const int lane = en.lane, lr = en.lr;
+    const RowStep& rs = en.rs;
+    if (!en.served) return;                                // (FILTER: a live slot's row of another class)
     if (SLOTS && rs.idle) {                                // wave-uniform: nothing is drawn, the row keeps its id
         if (lane == 0) store_outcome(row, false, 0, 0.f, ids_in, mask_id, pred_out, ids_out, score_out);
         return;
     }
-    if constexpr (SLOTS && FILTER) {
-        float mass;
-        if (!slot_in_class(PM_CLASS_TILES, rs, row, tokens, top_p_dev, mass)) return;
-    }
     topk = rs.topk;
-    const int lr = PERIOD ? row % period : row;
-    const float* lrow = logits + (size_t)lr * ldl;
+    const float* lrow = en.lrow;
     const int nblk = V >> 6;
 
     float2 st[NB2];
@@ -591,144 +617,131 @@ __device__ __forceinline__ unsigned long long remask_key(float score, int i) {
     return ((unsigned long long)orderable(score) << 32) | (unsigned long long)(0xffffffffu - (uint32_t)i);
 }
 
-// The selection with the sort in registers (round 5).  Thread t keeps the E consecutive elements t*E .. t*E+E-1; a bitonic
-// compare-exchange with distance j is in-thread for j < E, a wave shuffle for j < 64*E and goes through LDS (two barriers) only
-// beyond that: 3 of the 55 stages at N = 1024 (the all-LDS sort of rounds 1-4 had one barrier per stage, 40 us per launch on B <= 64
-// workgroups -- latency, not work).
-// SLOTS (pmhip_remask_slots): num_mask = slots[image].num_mask; the workgroup of an idle slot leaves (before any barrier).
-// The network, the threshold and the store are remask_select.h: one copy for this kernel and the choice form below it.
-template <int E, bool SLOTS = false>
-__global__ __launch_bounds__(THREADS) void remask_reg_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
-                                                             int num_mask, int64_t mask_id, int N, const PmGenParams* __restrict__ gp,
-                                                             int step, const pmhip_slot* __restrict__ slots) {
-    constexpr int NP = THREADS * E;
-    __shared__ unsigned long long xs[NP];
-    if (!image_num_mask<SLOTS>(num_mask, blockIdx.x, gp, step, slots)) return;
-    const int tid = threadIdx.x, base = tid * E;
-    const float* sc = scores + (size_t)blockIdx.x * N;
-    unsigned long long key[E], mine[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = base + e;
-        key[e] = i < N ? remask_key(sc[i], i) : 0ull;
-        mine[e] = key[e];
-    }
-#include "remask_select.h"
-}
-
-// COUNTS (pmhip_remask_counts): num_mask = counts[image], a device int32 per image -- the third source of the
-// count beside the arguments / gp and the slot records, a kernel of its own so that theirs keep their arguments and their code.  The
-// workgroup of an image whose count is 0 leaves like an idle slot's (before any barrier), its row untouched: remask_select.h's
-// clamp to 1 is the other sources'.
-template <int E>
-__global__ __launch_bounds__(THREADS) void remask_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
-                                                                const int32_t* __restrict__ counts, int64_t mask_id, int N) {
-    constexpr int NP = THREADS * E;
-    __shared__ unsigned long long xs[NP];
-    const int num_mask = counts[blockIdx.x];
-    if (num_mask <= 0) return;
-    const int tid = threadIdx.x, base = tid * E;
-    const float* sc = scores + (size_t)blockIdx.x * N;
-    unsigned long long key[E], mine[E];
-#pragma unroll
-    for (int e = 0; e < E; ++e) {
-        const int i = base + e;
-        key[e] = i < N ? remask_key(sc[i], i) : 0ull;
-        mine[e] = key[e];
-    }
-#include "remask_select.h"
-}
-
-// The CHOICE form (pmhip_remask_choice, pmhip_remask_choice_slots): MaskGIT's perturbed confidence.  With the
-// image's choice temperature t (image_choice) an element with score s sorts by
+// ---- the keys of the CHOICE form: MaskGIT's perturbed confidence.  With the image's choice temperature t
+// (image_step) an element with score s sorts by
 //   s                                                           t == 0 (the plain key, bit for bit), or s < 0 (a given id: no draw)
 //   -fmaf(t, gumbel(u), logf(fmaxf(1 - s, 2^-24)))              otherwise
-// u: noise[img * N + i], or Philox at (base + i, 0xFFFFFFFF, step) -- a column word no class column has (V <= 16384), so the
-// stream never meets the token draw's.  t <= 1000 keeps every noisy key above the -1e5 of a given id; t is uniform over the
-// workgroup.  Everything behind the keys is remask_select.h, as in remask_reg_kernel.
-template <int E, bool SLOTS>
-__global__ __launch_bounds__(THREADS) void remask_choice_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores, int num_mask,
-                                                                int64_t mask_id, int N, const PmGenParams* __restrict__ gp, int step,
-                                                                const pmhip_slot* __restrict__ slots, float choice_t,
-                                                                const float* __restrict__ choice, const float* __restrict__ noise,
-                                                                uint64_t seed, uint64_t row_base) {
-    constexpr int NP = THREADS * E;
-    __shared__ unsigned long long xs[NP];
-    ImageChoice ic{num_mask, choice_t, seed, (uint32_t)step, row_base};
-    if (!image_choice<SLOTS>(ic, blockIdx.x, N, gp, slots, choice)) return;
-    num_mask = ic.num_mask;
-    const int tid = threadIdx.x, base = tid * E;
-    const float* sc = scores + (size_t)blockIdx.x * N;
-#include "remask_choice_keys.h"
-#include "remask_select.h"
-}
-
-// the counts form of the choice kernel: counts[image] positions, the choice values as in the scalar form (the arguments, or gp)
+// u: noise_row[i] (given uniforms, the image's row: BATCH sources only), or Philox at (st.base + i, 0xFFFFFFFF, step) -- a column
+// word no class column has (V <= 16384), so the stream never meets the token draw's.  t <= 1000 keeps every noisy key above the
+// -1e5 of a given id; t is uniform over the workgroup.
 template <int E>
-__global__ __launch_bounds__(THREADS) void remask_choice_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
-                                                                       const int32_t* __restrict__ counts, int64_t mask_id, int N,
-                                                                       const PmGenParams* __restrict__ gp, int step, float choice_t,
-                                                                       const float* __restrict__ noise, uint64_t seed, uint64_t row_base) {
-    constexpr int NP = THREADS * E;
-    __shared__ unsigned long long xs[NP];
-    const int num_mask = counts[blockIdx.x];
-    if (num_mask <= 0) return;
-    ImageChoice ic{num_mask, choice_t, seed, (uint32_t)step, row_base};
-    image_choice<false>(ic, blockIdx.x, N, gp, nullptr, nullptr);      // t, seed, step and the image's noise base; the count stays the table's
-    const int tid = threadIdx.x, base = tid * E;
-    const float* sc = scores + (size_t)blockIdx.x * N;
-#include "remask_choice_keys.h"
-#include "remask_select.h"
-}
-
-// SLOTS WITH A COUNT PER SLOT (pmhip_remask_slots_counts): the step values from the record as in the SLOTS
-// forms above, and beside the records a device int32 per slot, c = counts[image]:
-//   c < 0   the record's num_mask with remask_select.h's clamp to 1 -- remask_reg_kernel<E, true> on this row;
-//   c == 0  the workgroup leaves like an idle slot's (before any barrier), its row untouched;
-//   c > 0   exactly c positions (remask_counts_kernel on this row; above N: the row).
-// Kernels of their own, like the counts forms: the instantiations above keep their arguments and their code.
-template <int E>
-__global__ __launch_bounds__(THREADS) void remask_slots_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
-                                                                      const pmhip_slot* __restrict__ slots,
-                                                                      const int32_t* __restrict__ counts, int64_t mask_id, int N) {
-    constexpr int NP = THREADS * E;
-    __shared__ unsigned long long xs[NP];
-    int num_mask = 0;
-    if (!image_num_mask<true>(num_mask, blockIdx.x, nullptr, 0, slots)) return;
-    const int c = counts[blockIdx.x];
-    if (c == 0) return;
-    if (c > 0) num_mask = c;
-    const int tid = threadIdx.x, base = tid * E;
-    const float* sc = scores + (size_t)blockIdx.x * N;
-    unsigned long long key[E], mine[E];
-#pragma unroll
+__device__ __forceinline__ void remask_choice_keys(unsigned long long (&key)[E], unsigned long long* xs, const float* sc,
+                                                   const float* noise_row, int base, int N, const ImageStep& st) {
+    // one element at a time (a Philox and three logf each: unrolled E = 16 times they would not fit the registers), through the
+    // thread's own E words of xs, which nobody else touches before the first barrier
+#pragma unroll 1
     for (int e = 0; e < E; ++e) {
         const int i = base + e;
-        key[e] = i < N ? remask_key(sc[i], i) : 0ull;
-        mine[e] = key[e];
+        unsigned long long k = 0ull;
+        if (i < N) {
+            float s = sc[i];
+            if (st.t != 0.f && !(s < 0.f)) {
+                float u;
+                if (noise_row) {
+                    u = noise_row[i];
+                } else {
+                    const uint64_t grow = st.base + (uint64_t)i;
+                    const uint4 rnd = philox4x32_10(make_uint4((uint32_t)grow, (uint32_t)(grow >> 32), 0xFFFFFFFFu, st.step),
+                                                    make_uint2((uint32_t)st.seed, (uint32_t)(st.seed >> 32)));
+                    u = (float)(rnd.x >> 8) * (1.0f / 16777216.0f);
+                }
+                const float ph = 1.0f - s;
+                const float conf = logf(fmaxf(ph, 0x1p-24f));
+                s = -fmaf(st.t, gumbel_from_uniform(u), conf);
+            }
+            k = remask_key(s, i);
+        }
+        xs[i] = k;
     }
-#include "remask_select.h"
+#pragma unroll
+    for (int e = 0; e < E; ++e) key[e] = xs[base + e];
 }
 
-// its choice form (pmhip_remask_choice_slots_counts): t from choice[image], seed, step and image_index * N from the record
-// (image_choice<true>), Philox noise only; the count as above
+// ---- the selection with the sort in registers (round 5).  Thread t keeps the E consecutive elements base = t*E .. t*E+E-1 in
+// key[E] (sorted in place); mine[E] is a copy that stays.  A bitonic compare-exchange with distance j is in-thread for j < E, a
+// wave shuffle for j < 64*E and goes through LDS (xs[THREADS * E], two barriers) only beyond that: 3 of the 55 stages at N = 1024
+// (the all-LDS sort of rounds 1-4 had one barrier per stage, 40 us per launch on B <= 64 workgroups -- latency, not work).  Then the
+// threshold, the num_mask-th key (num_mask in [1, N]: image_step), and the store of mask_id into the image's ids row.
 template <int E>
-__global__ __launch_bounds__(THREADS) void remask_choice_slots_counts_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores,
-                                                                             const pmhip_slot* __restrict__ slots,
-                                                                             const float* __restrict__ choice,
-                                                                             const int32_t* __restrict__ counts, int64_t mask_id, int N) {
+__device__ __forceinline__ void remask_select(unsigned long long (&key)[E], const unsigned long long (&mine)[E], unsigned long long* xs,
+                                              int base, int num_mask, int N, int64_t* ids_row, int64_t mask_id) {
     constexpr int NP = THREADS * E;
-    __shared__ unsigned long long xs[NP];
-    ImageChoice ic{0, 0.f, 0ull, 0u, 0ull};
-    if (!image_choice<true>(ic, blockIdx.x, N, nullptr, slots, choice)) return;
-    const int c = counts[blockIdx.x];
-    if (c == 0) return;
-    const int num_mask = c > 0 ? c : ic.num_mask;
-    const float* noise = nullptr;
-    const int tid = threadIdx.x, base = tid * E;
-    const float* sc = scores + (size_t)blockIdx.x * N;
-#include "remask_choice_keys.h"
-#include "remask_select.h"
+#pragma unroll
+    for (int k = 2; k <= NP; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            if (j < E) {                                   // both elements in this thread
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    if ((e & j) == 0) {
+                        const bool desc = ((base + e) & k) == 0;
+                        const unsigned long long a = key[e], b = key[e | j];
+                        const bool swap = desc ? (a < b) : (a > b);
+                        key[e] = swap ? b : a;
+                        key[e | j] = swap ? a : b;
+                    }
+                }
+            } else {
+                unsigned long long other[E];
+                if (j < 64 * E) {                          // the partner thread is in this wave
+#pragma unroll
+                    for (int e = 0; e < E; ++e) other[e] = __shfl_xor(key[e], j / E, 64);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < E; ++e) xs[base + e] = key[e];
+                    __syncthreads();
+#pragma unroll
+                    for (int e = 0; e < E; ++e) other[e] = xs[(base + e) ^ j];
+                    __syncthreads();
+                }
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const int i = base + e;
+                    const bool want_max = ((i & j) == 0) == ((i & k) == 0);   // descending block: the lower index keeps the larger key
+                    const unsigned long long a = key[e], b = other[e];
+                    key[e] = want_max ? (a > b ? a : b) : (a < b ? a : b);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) xs[base + e] = key[e];
+    __syncthreads();
+    const unsigned long long thr = xs[num_mask - 1];
+    const int inside = N - base;                           // base + e < N as e < inside: one register for the E tests, not E indices
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+        if (e < inside && mine[e] >= thr) ids_row[base + e] = mask_id;
+}
+
+// ---- the re-masking kernel: one workgroup per image, every form of every entry (pmhip_remask*).  SLOTS, COUNTS and CHOICE say
+// where the image's count and choice values come from -- image_step resolves them, and every early exit is there, before the
+// first barrier; the forms differ in nothing else.  A form leaves the arguments it has no use for unread.
+template <int E, bool SLOTS, bool COUNTS, bool CHOICE>
+__global__ __launch_bounds__(THREADS) void remask_kernel(int64_t* __restrict__ ids, const float* __restrict__ scores, int num_mask,
+                                                         int64_t mask_id, int N, const PmGenParams* __restrict__ gp, int step,
+                                                         const pmhip_slot* __restrict__ slots, const int32_t* __restrict__ counts,
+                                                         float choice_t, const float* __restrict__ choice,
+                                                         const float* __restrict__ noise, uint64_t seed, uint64_t row_base) {
+    __shared__ unsigned long long xs[THREADS * E];
+    const int img = blockIdx.x;
+    ImageStep st{num_mask, choice_t, seed, (uint32_t)step, row_base};
+    if (!image_step<SLOTS, COUNTS, CHOICE>(st, img, N, gp, slots, counts, choice)) return;
+    const int base = threadIdx.x * E;
+    const float* sc = scores + (size_t)img * N;
+    unsigned long long key[E], mine[E];
+    if constexpr (CHOICE) {
+        remask_choice_keys<E>(key, xs, sc, SLOTS || !noise ? nullptr : noise + (size_t)img * N, base, N, st);
+    } else {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int i = base + e;
+            key[e] = i < N ? remask_key(sc[i], i) : 0ull;   // the plain key; an element beyond the row sorts below every real one
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) mine[e] = key[e];
+    remask_select<E>(key, mine, xs, base, st.num_mask, N, ids + (size_t)img * N, mask_id);
 }
 
 // a run-time size class or flag as a compile-time constant: f(std::integral_constant<int, V>) for the one V of Vs that equals v
@@ -736,6 +749,9 @@ template <int... Vs, typename F>
 void pick(int v, F&& f) {
     ((v == Vs ? f(std::integral_constant<int, Vs>{}) : (void)0), ...);
 }
+
+// the size class of the kernels with a resident row: NV4, the float4 groups a lane holds, for a row of V <= 16384 classes
+int nv4_class(int V) { return V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64; }
 
 }  // namespace
 
@@ -770,7 +786,7 @@ int pm_sample_rows(const float* logits, int ldl, const float* block_stats, int p
     // one launch of class `cls`; PER_IMAGE: the form that serves the rows of its class only (a filters source)
     auto launch = [&](int cls, auto PER_IMAGE) {
         constexpr bool PI = decltype(PER_IMAGE)::value == 1;
-        const int nv4 = V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64;
+        const int nv4 = nv4_class(V);
         if (cls == PM_CLASS_NUCLEUS) {
             pick<1, 4, 32, 64>(nv4, [&](auto NV4) {
                 pick<0, 1>(!PI && period != 0, [&](auto PER) {
@@ -879,7 +895,7 @@ extern "C" int pmhip_sample_rows_forced(const float* logits, int ldl, const int6
     hipStream_t s = (hipStream_t)stream;
     dim3 grid(ceil_div(M, THREADS / 64)), block(THREADS);
     PmTimer tm(FAM_SAMPLE, s);
-    pick<1, 4, 32, 64>(V <= 256 ? 1 : V <= 1024 ? 4 : V <= 8192 ? 32 : 64, [&](auto NV4) {
+    pick<1, 4, 32, 64>(nv4_class(V), [&](auto NV4) {
         hipLaunchKernelGGL((sample_forced_kernel<NV4()>), grid, block, 0, s, logits, ldl, ids_in, target, mask_id, pred_out, ids_out, score_out,
                            M, V);
     });
@@ -902,9 +918,8 @@ int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, 
     const bool slots = src.kind == PmStepSource::SLOTS;
     const bool counts = src.counts != nullptr;             // the count of image b from counts[b]; everything else from the source's kind
     const bool choice = src.choice_on();
-    const char* who = slots && counts ? (choice ? "remask_choice_slots_counts" : "remask_slots_counts")
-                      : counts        ? (choice ? "remask_choice_counts" : "remask_counts")
-                      : slots         ? (choice ? "remask_choice_slots" : "remask_slots") : (choice ? "remask_choice" : "remask");
+    char who[32];                                          // the entry's name, as the forms spell it
+    snprintf(who, sizeof who, "remask%s%s%s", choice ? "_choice" : "", slots ? "_slots" : "", counts ? "_counts" : "");
     PM_REQUIRE(ids && scores && (!slots || src.slots) && (src.kind != PmStepSource::PARAMS || src.gp), "%s: null pointer", who);
     PM_REQUIRE(B > 0 && N > 0 && N <= 4096, "%s: bad shape B=%d N=%d (N <= 4096)", who, B, N);
     int per_thread = 1;                                    // E: the power of two with THREADS * E >= N
@@ -912,29 +927,10 @@ int pm_remask(int64_t* ids, const float* scores, int64_t mask_id, int B, int N, 
     hipStream_t s = (hipStream_t)stream;
     PmTimer tm(FAM_SAMPLE, s);
     pick<1, 2, 4, 8, 16>(per_thread, [&](auto E) {
-        if (slots && counts) {                             // a count per slot beside the records
-            if (choice)
-                hipLaunchKernelGGL((remask_choice_slots_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.slots, src.choice_dev,
-                                   src.counts, mask_id, N);
-            else
-                hipLaunchKernelGGL((remask_slots_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.slots, src.counts, mask_id, N);
-            return;
-        }
-        if (counts) {
-            if (choice)
-                hipLaunchKernelGGL((remask_choice_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.counts, mask_id, N, src.gp,
-                                   (int)src.step, src.choice_t, src.choice_noise, src.seed, src.row_base);
-            else
-                hipLaunchKernelGGL((remask_counts_kernel<E()>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.counts, mask_id, N);
-            return;
-        }
-        pick<0, 1>(slots, [&](auto SLOTS) {
-            if (choice)
-                hipLaunchKernelGGL((remask_choice_kernel<E(), SLOTS() == 1>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.num_mask, mask_id,
-                                   N, src.gp, (int)src.step, src.slots, src.choice_t, src.choice_dev, src.choice_noise, src.seed, src.row_base);
-            else
-                hipLaunchKernelGGL((remask_reg_kernel<E(), SLOTS() == 1>), dim3(B), dim3(THREADS), 0, s, ids, scores, src.num_mask, mask_id, N,
-                                   src.gp, (int)src.step, src.slots);
+        pick<0, 1, 2, 3, 4, 5, 6, 7>((slots ? 4 : 0) | (counts ? 2 : 0) | (choice ? 1 : 0), [&](auto FORM) {
+            hipLaunchKernelGGL((remask_kernel<E(), (FORM() & 4) != 0, (FORM() & 2) != 0, (FORM() & 1) != 0>), dim3(B), dim3(THREADS), 0, s, ids,
+                               scores, src.num_mask, mask_id, N, src.gp, (int)src.step, src.slots, src.counts, src.choice_t, src.choice_dev,
+                               src.choice_noise, src.seed, src.row_base);
         });
     });
     PM_HIP(hipGetLastError());

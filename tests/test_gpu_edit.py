@@ -60,6 +60,27 @@ def test_remask_counts_equals_the_single_row_calls(N):
                        ops.remask_counts(ids.clone(), scores, cd, MASK_ID))
 
 
+@pytest.mark.parametrize("N", [16, 300])
+def test_remask_counts_above_n_is_the_row_and_a_negative_count_leaves_it(N):
+    """the two ends of the count rule the case above does not reach, in the two smallest classes (one and two elements per thread):
+    a count above N is pmhip_remask(_choice) on that row alone with that count -- the whole row -- and a negative one leaves the row
+    as a 0 does"""
+    counts = [N + 5, -3, N + 1]
+    ids_np, scores_np = scores_with_ties(3, N, seed=N + 1)
+    ids, scores = t(ids_np), t(scores_np)
+    cd = torch.tensor(counts, dtype=torch.int32, device=dev())
+    base = 3 * N
+    for kw in ({}, dict(choice_temperature=4.5, seed=11, step=2)):
+        got = ops.remask_counts(ids.clone(), scores, cd, MASK_ID, row_base=base, **kw)
+        for b, c in enumerate(counts):
+            want = ids[b:b + 1].clone()
+            if c > 0:
+                ops.remask(want, scores[b:b + 1].clone(), c, MASK_ID, row_base=base + b * N, **kw)
+                assert int((want == MASK_ID).sum()) == N, (N, b, c)
+            assert torch.equal(got[b:b + 1], want), (N, b, c, kw)
+        assert torch.equal(got[1], ids[1])                                         # a negative count: the row as it was
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # the pixel-side operators
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -267,6 +267,33 @@ def main():
             emit_graphs(f"session mixed {tag} graph={int(graph)} graphs")
         emit_graphs(f"section {tag} graphs")
     pipe.set_compute_dtype(torch.float32)
+
+    # ---- the sampler forms nothing above reaches (profiles/sampler_forms_digest_parent.jsonl): a count per image and per slot in
+    # every elements-per-thread class of the re-masking kernel (E = 1, 2, 4, 8, 16), and the forced step in every row class
+    for N in (16, 300, 1024, 2048, 4096):
+        rng = np.random.default_rng(5000 + N)
+        sc = (rng.integers(0, 8, (4, N)) / 8.0).astype(np.float32)
+        sc[rng.random((4, N)) < 0.3] = -1e5                       # given ids: never drawn for, last in the order
+        scores, ids = t(sc), t(rng.integers(0, 64, (4, N)).astype(np.int64))
+        noise = t(rng.random((4, N)).astype(np.float32))
+        counts = t(np.array([0, 1, N, N + 5], dtype=np.int32))
+        emit(f"remask_counts N={N}", ids=ops.remask_counts(ids.clone(), scores, counts, 64))
+        emit(f"remask_counts N={N} choice philox",
+             ids=ops.remask_counts(ids.clone(), scores, counts, 64, choice_temperature=4.5, seed=seed, step=2, row_base=base))
+        emit(f"remask_counts N={N} choice noise", ids=ops.remask_counts(ids.clone(), scores, counts, 64, choice_temperature=4.5, noise=noise))
+        slots = ops.pack_slots([(0x0123456789ABCDEF, 7, 0.0, 1, 0, 0), (77, 2 ** 33 + 5, 0.8, 8, N, 3),
+                                (0xFEDCBA9876543210, 4096, 1.3, 5, max(N // 2, 1), 17), None], dev)
+        counts = t(np.array([-1, 0, max(N // 3, 1), 3], dtype=np.int32))    # the record's (clamped to 1), none, its own, idle with a count
+        emit(f"remask_slots_counts N={N}", ids=ops.remask_slots_counts(ids.clone(), scores, slots, counts, 64))
+        choice = t(np.array([4.5, 2.0, 0.25, 1.5], dtype=np.float32))
+        emit(f"remask_slots_counts N={N} choice", ids=ops.remask_slots_counts(ids.clone(), scores, slots, counts, 64, choice=choice))
+    for V in (64, 1000, 8192, 16384):
+        rng = np.random.default_rng(7000 + V)
+        x, ids = t(logits_of(rng, 9, V, False)), t(ids_of(rng, 9, V))
+        target = rng.integers(0, V, 9).astype(np.int64)
+        target[4] = V                                             # outside [0, V): the row stays undrawn
+        pred, merged, score = ops.sample_rows_forced(x, ids, t(target), V)
+        emit(f"sample_rows_forced V={V}", pred=pred, ids=merged, score=score)
     if out:
         out.close()
 
