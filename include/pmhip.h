@@ -422,6 +422,41 @@ int pmhip_blend_tokens(const uint8_t* mask, const int64_t* pred_s, const int64_t
 int pmhip_layernorm(const float* x, const float* gamma, const float* beta, float eps, void* out,
                     int out_dtype, int M, int D, pmhip_stream stream);
 
+/* ---- the Flan-T5 encoder's own operators (new entries within ABI 11, nothing existing changes meaning).
+ * The tower is the text encoder of modules/encoder.py:18-42; its arithmetic is Hugging Face's modeling_t5.py. */
+
+/* T5LayerNorm: out[m,:] = weight * (x[m,:] * rsqrt(mean(x[m,:]^2) + eps)) -- no mean subtraction, no bias, statistics in f32.
+ * x f32 [M,D], weight f32 [D], out `out_dtype` (f32, or bf16 rounded once) [M,D].  D % 4 == 0 and 4 <= D <= 4096 (a row is held
+ * in registers and read once); any other D is PMHIP_EINVAL naming D.  An all-zero row gives zeros (eps > 0). */
+int pmhip_rmsnorm(const float* x, const float* weight, float eps, void* out, int out_dtype, int M, int D, pmhip_stream stream);
+
+/* T5's gated GELU (T5DenseGatedActDense with NewGELUActivation): out[m,j] = gelu_new(u[m,j]) * u[m,F+j] for j < F, with
+ * gelu_new(x) = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))).  u f32 [M, ldu >= 2F] -- the output of ONE GEMM against
+ * [wi_0; wi_1] --, out `out_dtype` [M, ldo >= F].  F % 4 == 0; ldu, ldo multiples of 4 (16-byte accesses).  Columns [F, ldo) of out
+ * are never written and columns [2F, ldu) of u never read.  Finite input gives finite output: where x^3 overflows the result is
+ * x * u[m,F+j] (x > 0) or -0 * u[m,F+j] (x < 0), never NaN. */
+int pmhip_geglu(const float* u, int ldu, void* out, int ldo, int out_dtype, int M, int F, pmhip_stream stream);
+
+/* Self-attention with T5's relative-position bias (T5Attention, encoder, bidirectional), dim_head 64.  Layouts are those
+ * pmhip_gemm_heads writes: Q [B,H,L,64] UNSCALED (T5 has no 1/sqrt(d): call pmhip_gemm_heads with q_scale = 1), K [B,H,L_pad,64],
+ * V^T [B,H,64,L_pad], all `dtype`; out `dtype` [B*L, ldo >= heads*64], head-major inside a row, written in exactly its
+ * B*L x heads*64 elements.
+ *   rel_bias  DEVICE f32 [heads][2L-1], natural-log units: query q and key k of head h get rel_bias[h][(k - q) + (L - 1)] added to
+ *             their score before the softmax.  T5's bucket depends on k - q only, so this table is all of the [H,L,L] bias, which
+ *             is never materialised.  NULL is PMHIP_EINVAL.
+ *   kv_lens   DEVICE int32 [B] or NULL: image b attends to the keys [0, n_b), n_b = min(max(kv_lens[b], 1), L) -- the clamp of
+ *             pmhip_attention_lens; NULL: n_b = L.
+ * Any L >= 1 is served (one wave per 16 queries walks the keys in blocks; L up to 2^20 by the entry's check).  L_pad >= L and a
+ * multiple of 4; ldo a multiple of 4; Q, K, V^T 16-byte aligned.
+ * bf16: Q K^T and P V on mfma_f32_16x16x32_bf16, the softmax in f32 with an exact running maximum that is subtracted before every
+ * exponential (unscaled T5 scores reach the hundreds), P rounded to bf16 once.  f32: the same flow on the exact-f32 matrix core
+ * (mfma_f32_16x16x4_f32), P not rounded.
+ * Contract (that of the sibling forms): no atomics; two launches give the same bits; image b's rows do not depend on the rest of
+ * the batch; K rows and V^T columns [L, L_pad) and behind n_b never reach a result, NaN included (the K rows are not read, the V^T
+ * elements are replaced by 0 as they are loaded). */
+int pmhip_attention_relbias(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int L,
+                            int L_pad, const float* rel_bias, const int32_t* kv_lens, pmhip_stream stream);
+
 /* Non-overlapping PxP patches of img[B,C,H,W] (fp32) as GEMM rows: out[B*(H/P)*(W/P), C*P*P],
  * column order (c, kh, kw) = the flattened Conv2d weight (stage1/layers.py:81-84,107). */
 int pmhip_patchify(const float* img, void* out, int out_dtype, int B, int C, int H, int W, int P,

@@ -252,6 +252,10 @@ PROTOTYPES = {
                                               C.POINTER(f32), C.POINTER(f32), vp, vp, i32, vp]),
     "pmhip_phrase_region": (i32, [vp, vp, vp, i32, i32, f32, i32, vp]),
     "pmhip_blend_tokens": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]),
+    # the Flan-T5 encoder's own operators: RMS norm, gated GELU, attention with the relative-position bias
+    "pmhip_rmsnorm": (i32, [vp, vp, f32, vp, i32, i32, i32, vp]),
+    "pmhip_geglu": (i32, [vp, i32, vp, i32, i32, i32, i32, vp]),
+    "pmhip_attention_relbias": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

@@ -1,5 +1,6 @@
 """Text-conditioning producers (reference modules/encoder.py:18-104): the frozen towers are third-party
-pretrained models that stay on stock PyTorch-ROCm; the hot path only consumes their (B,77,ctx) output.
+pretrained models that stay on stock PyTorch-ROCm; the hot path only consumes their (B,77,ctx) output.  The one exception is opt-in:
+``T5TextEmbedder(native=True)`` runs the Flan-T5 encoder's arithmetic on the HIP kernels (``modules/t5_native.py``).
 
 Both wrappers keep the reference's attribute names (`transformer` for the T5 encoder, `model` for the CLIP tower),
 because those names are the checkpoint-key contract: a Pipeline state_dict carries `text_model.transformer.*`
@@ -32,7 +33,13 @@ def _count_tokens(mask):
 class T5TextEmbedder(nn.Module):
     """Flan-T5 encoder (reference encoder.py:18-42): tokens padded / truncated to max_length -> last_hidden_state."""
 
-    def __init__(self, version="google/flan-t5-xl", device=None, max_length=77, freeze=True, tokenizer=None, transformer=None):
+    def __init__(self, version="google/flan-t5-xl", device=None, max_length=77, freeze=True, tokenizer=None, transformer=None,
+                 native=False, encoder_padding_mask=False):
+        """native: run the tower's arithmetic on the HIP kernels (``modules/t5_native.py``) when it lives on a
+        GPU -- on the CPU the Hugging Face tower runs, as everywhere in this package.  A tower the kernels do not serve is refused
+        here (ValueError naming the config field).  Off (the default): the Hugging Face tower, as before.
+        encoder_padding_mask: the tower is given the prompts' non-pad token counts, what Hugging Face users normally do
+        (``attention_mask=``).  Off (the default): the reference's behaviour -- padding attends and is attended to."""
         super().__init__()
         if tokenizer is None or transformer is None:
             from transformers import T5EncoderModel, T5Tokenizer   # needs local weights: there is no network here
@@ -41,10 +48,50 @@ class T5TextEmbedder(nn.Module):
         self.tokenizer = tokenizer
         self.transformer = transformer
         self.max_length = max_length
+        self.encoder_padding_mask = bool(encoder_padding_mask)
+        self._pm_dtype = torch.float32
+        self._native = None
+        if native:
+            self.use_native(True)
         if device is not None:
             self.to(device)
         if freeze:
             self.freeze()
+
+    def use_native(self, on=True):
+        """switch the HIP tower on or off; -> self"""
+        if on and self._native is None:
+            from .t5_native import NativeT5Encoder
+            self._native = NativeT5Encoder(self.transformer)       # refuses what the kernels do not serve
+        elif not on:
+            self._native = None
+        return self
+
+    @property
+    def native(self):
+        return self._native is not None
+
+    @property
+    def compute_dtype(self):
+        """of the native tower (the Hugging Face tower computes in its parameters' dtype): ``_pm_dtype`` (``Pipeline.set_compute_dtype``),
+        or bfloat16 inside ``torch.autocast('cuda', bfloat16)``"""
+        if torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16:
+            return torch.bfloat16
+        return self._pm_dtype
+
+    def _tower(self, tokens, lens):
+        """THE tower call of forward, _forward_weighted, phrase_rows and fragment_ids: tokens int64 [B, max_length] on the tower's
+        device, lens int32 [B] on the host (read only with encoder_padding_mask) -> last_hidden_state [B, max_length, d_model]"""
+        lens = lens if self.encoder_padding_mask else None
+        if self._native is not None and tokens.is_cuda:
+            if self._native.model is not self.transformer:          # the tower was replaced after use_native()
+                self._native = None
+                self.use_native(True)
+            return self._native(tokens, kv_lens=lens, dtype=self.compute_dtype)
+        if lens is None:
+            return self.transformer(input_ids=tokens).last_hidden_state
+        keep = torch.arange(tokens.shape[1])[None, :] < torch.as_tensor(lens).to(torch.long)[:, None]
+        return self.transformer(input_ids=tokens, attention_mask=keep.to(device=tokens.device, dtype=torch.long)).last_hidden_state
 
     def freeze(self):
         self.transformer = self.transformer.eval()
@@ -64,11 +111,10 @@ class T5TextEmbedder(nn.Module):
                              return_overflowing_tokens=False, padding="max_length", return_tensors="pt")
         ids = enc["input_ids"]
         tokens = ids.to(_module_device(self.transformer))
-        context = self.transformer(input_ids=tokens).last_hidden_state
-        if not return_lens:
-            return context
         mask = enc["attention_mask"] if "attention_mask" in enc else ids != _pad_id(self.tokenizer)
-        return context, _count_tokens(torch.as_tensor(mask))
+        lens = _count_tokens(torch.as_tensor(mask))
+        context = self._tower(tokens, lens)
+        return (context, lens) if return_lens else context
 
     def _forward_weighted(self, text):
         """Every prompt is parsed (``prompt.parse_weighted``), its fragments are tokenised one by one WITHOUT special tokens, the ids
@@ -95,7 +141,7 @@ class T5TextEmbedder(nn.Module):
             ids[b, :len(row)] = torch.tensor(row, dtype=torch.long)
             weights[b, :len(row)] = torch.tensor(wrow, dtype=torch.float32)
             lens[b] = len(row)
-        context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
+        context = self._tower(ids.to(_module_device(self.transformer)), lens)
         return context, lens, weights
 
     @torch.no_grad()
@@ -143,7 +189,7 @@ class T5TextEmbedder(nn.Module):
             ids[b, :len(row)] = torch.tensor(row, dtype=torch.long)
             rows[b, len(head):len(head) + len(mid)] = True
             lens[b] = len(row)
-        context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
+        context = self._tower(ids.to(_module_device(self.transformer)), lens)
         return context, lens, rows
 
     @torch.no_grad()
@@ -174,7 +220,7 @@ class T5TextEmbedder(nn.Module):
             lens[b] = len(row)
             rows.append(row)
             spans.append(span)
-        context = self.transformer(input_ids=ids.to(_module_device(self.transformer))).last_hidden_state
+        context = self._tower(ids.to(_module_device(self.transformer)), lens)
         return context, lens, rows, spans
 
     def encode(self, text):

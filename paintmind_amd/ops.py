@@ -269,14 +269,20 @@ def swiglu_hidden(hidden_features):
 
 
 # ------------------------------------------------------------------------------------------------
-def gemm(a, w, bias=None, residual=None, res_rows=0, out_dtype=None):
-    """a[M,K] @ w[N,K]^T (+bias) (+residual[m % res_rows])."""
-    dev = _dev(a, w, bias, residual)
+def gemm(a, w, bias=None, residual=None, res_rows=0, out_dtype=None, out=None):
+    """a[M,K] @ w[N,K]^T (+bias) (+residual[m % res_rows]).  out (optional): the contiguous [M,N] tensor to write; it may BE the f32
+    residual (res_rows covering all M rows): the stream updated in place, as pmhip_gemm allows."""
+    dev = _dev(a, w, bias, residual, out)
     lib = _lib.load()
     M, K = a.shape
     N = w.shape[0]
-    out_dtype = out_dtype or a.dtype
-    out = torch.empty(M, N, device=dev, dtype=out_dtype)
+    if out is None:
+        out_dtype = out_dtype or a.dtype
+        out = torch.empty(M, N, device=dev, dtype=out_dtype)
+    else:
+        if tuple(out.shape) != (M, N) or (out_dtype is not None and out.dtype != out_dtype):
+            raise ValueError(f"gemm: out must be [{M}, {N}] of the requested dtype, got {out.dtype} {tuple(out.shape)}")
+        out_dtype = out.dtype
     ldr = residual.shape[-1] if residual is not None else 0
     rr = res_rows or (residual.shape[0] if residual is not None else 0)
     with torch.cuda.device(dev):
@@ -820,6 +826,55 @@ def layernorm(x, gamma, beta, eps=1e-5, out_dtype=torch.float32):
     with torch.cuda.device(dev):
         check(lib.pmhip_layernorm(_p(x), _p(gamma), _p(beta), float(eps), _p(out), pm_dtype(out_dtype), M, D,
                                   stream_ptr(dev)), "pmhip_layernorm")
+    return out
+
+
+def rmsnorm(x, weight, eps=1e-6, out_dtype=torch.float32):
+    """T5LayerNorm (pmhip_rmsnorm): weight * (x * rsqrt(mean(x^2) + eps)); x f32 [M, D], D % 4 == 0, D <= 4096"""
+    dev = _dev(x, weight)
+    lib = _lib.load()
+    M, D = x.shape
+    out = torch.empty(M, D, device=dev, dtype=out_dtype)
+    with torch.cuda.device(dev):
+        check(lib.pmhip_rmsnorm(_p(x), _p(weight), float(eps), _p(out), pm_dtype(out_dtype), M, D, stream_ptr(dev)), "pmhip_rmsnorm")
+    return out
+
+
+def geglu(u, out_dtype=torch.float32):
+    """T5's gated GELU (pmhip_geglu): u f32 [M, 2F], the output of one GEMM against [wi_0; wi_1] -> gelu_new(u[:, :F]) * u[:, F:] as
+    `out_dtype` [M, F]"""
+    dev = _dev(u)
+    lib = _lib.load()
+    M, F2 = u.shape
+    F = F2 // 2
+    if F2 != 2 * F or u.dtype != torch.float32:
+        raise ValueError(f"geglu: u must be float32 [M, 2F], got {u.dtype} {tuple(u.shape)}")
+    out = torch.empty(M, F, device=dev, dtype=out_dtype)
+    with torch.cuda.device(dev):
+        check(lib.pmhip_geglu(_p(u), 2 * F, _p(out), F, pm_dtype(out_dtype), M, F, stream_ptr(dev)), "pmhip_geglu")
+    return out
+
+
+def attention_relbias(q, k, vt, rel_bias, kv_lens=None, out=None):
+    """Self-attention with T5's relative-position bias (pmhip_attention_relbias): q [B,H,L,64] UNSCALED, k [B,H,Lp,64], vt [B,H,64,Lp]
+    as gemm_heads writes them; rel_bias f32 [H, 2L-1] on the device, entry (k - q) + L - 1 is added to the score of query q and key k;
+    kv_lens int32 [B] on the device or None -> [B*L, H*64].  `out` may be a column slice of a wider matrix."""
+    dev = _dev(q, k, vt, rel_bias, kv_lens)
+    lib = _lib.load()
+    B, H, L, dh = q.shape
+    if dh != 64:
+        raise ValueError(f"attention_relbias: dim_head={dh} not served (64 only)")
+    if tuple(rel_bias.shape) != (H, 2 * L - 1) or rel_bias.dtype != torch.float32:
+        raise ValueError(f"attention_relbias: rel_bias must be float32 [{H}, {2 * L - 1}], got {rel_bias.dtype} {tuple(rel_bias.shape)}")
+    if kv_lens is not None and (kv_lens.dtype != torch.int32 or kv_lens.numel() != B):
+        raise ValueError(f"attention_relbias: kv_lens must be int32 [{B}]")
+    if out is None:
+        out = torch.empty(B * L, H * 64, device=dev, dtype=q.dtype)
+    if not out.is_cuda or out.dtype != q.dtype or tuple(out.shape) != (B * L, H * 64) or out.stride(1) != 1:
+        raise ValueError(f"attention_relbias: out must be {q.dtype} [{B * L}, {H * 64}] with unit column stride")
+    with torch.cuda.device(dev):
+        check(lib.pmhip_attention_relbias(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), out.stride(0), B, H, L, k.shape[2], _p(rel_bias),
+                                          _p(kv_lens), stream_ptr(dev)), "pmhip_attention_relbias")
     return out
 
 
