@@ -457,6 +457,44 @@ int pmhip_geglu(const float* u, int ldu, void* out, int ldo, int out_dtype, int 
 int pmhip_attention_relbias(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int L,
                             int L_pad, const float* rel_bias, const int32_t* kv_lens, pmhip_stream stream);
 
+/* ---- the OpenCLIP text tower's own operators (new entries within ABI 11, nothing existing changes meaning).
+ * The tower is the text encoder of modules/encoder.py:45-104; its arithmetic is open_clip's ResidualAttentionBlock around
+ * nn.MultiheadAttention. */
+
+/* Causal self-attention, dim_head 64: out[q] = softmax_k(Q[q] . K[k]) V[k] over the keys k in [0, q], per (image, head).  Layouts are
+ * those of pmhip_gemm_heads and pmhip_attention_relbias: Q [B,H,L,64] ALREADY SCALED, K [B,H,L_pad,64], V^T [B,H,64,L_pad], all
+ * `dtype`; out `dtype` [B*L, ldo >= heads*64], head-major inside a row, written in exactly its B*L x heads*64 elements.
+ * Any L in [1, 2^20]; L_pad >= L, a multiple of 4, at most 2^24; ldo a multiple of 4; Q, K, V^T 16-byte aligned, out 4-element
+ * aligned.
+ * One wave per 16 queries walks the keys [0, min(L, q0 + 16)) in blocks; blocks wholly above the diagonal are never visited.  The
+ * softmax is in f32 with an exact running maximum subtracted before every exponential.  bf16: Q K^T and, for the keys below the
+ * tile's first query, P V on mfma_f32_16x16x32_bf16 with P rounded to bf16 once (the denominator sums the unrounded P); f32: the
+ * same flow on mfma_f32_16x16x4_f32.  The 16 keys of the diagonal tile are applied on the vector ALU with P in f32, because the
+ * matrix core shares V^T among the queries of a tile.
+ * Contract: no atomics; two launches give the same bits; image b's rows do not depend on the rest of the batch; row q depends on no
+ * K row and no V^T column > q, NaN included, nor on the padding [L, L_pad). */
+int pmhip_attention_causal(int dtype, const void* Q, const void* K, const void* Vt, void* out, int ldo, int B, int heads, int L,
+                           int L_pad, pmhip_stream stream);
+
+/* Head split of a projection that is already computed: U f32 [M, ldu >= nparts*heads*64] is the output of ONE ordinary pmhip_gemm
+ * that added the projection's bias (nn.MultiheadAttention's in_proj_bias; pmhip_gemm_heads has no bias).  Part p is the columns
+ * [p*heads*64, (p+1)*heads*64) and is written as pmhip_gemm_heads writes a part of kind part_kinds_host[p], rounded to `dtype` once:
+ * Q -> [B,H,tokens,64] * q_scale ; K -> [B,H,tokens_pad,64] ; V -> transposed [B,H,64,tokens_pad].  M = B*tokens.  The f32 result
+ * is the single f32 product U * q_scale (K and V: U itself), the bf16 result that product rounded to nearest even.  The padding
+ * [tokens, tokens_pad) of K and V^T is left UNTOUCHED, and columns [nparts*heads*64, ldu) of U are never read.  part_kinds_host /
+ * part_outs_host: HOST arrays of nparts (1..3) kinds and 16-byte aligned device pointers.  ldu a multiple of 4, U 16-byte aligned. */
+int pmhip_split_heads(int dtype, const float* U, int ldu, int M, int heads, int tokens, int tokens_pad, int nparts,
+                      const int* part_kinds_host, void* const* part_outs_host, float q_scale, pmhip_stream stream);
+
+/* The GELUs of OpenCLIP's text towers on the f32 output of the c_fc GEMM (its bias already added): u f32 [M, ldu >= F] -> out
+ * `out_dtype` (f32, or bf16 rounded once) [M, ldo >= F].
+ *   kind 0   nn.GELU() (approximate='none'): 0.5 x (1 + erf(x / sqrt 2)), evaluated as 0.5 x erfc(-x sqrt(0.5)): no cancellation
+ *            at negative x
+ *   kind 1   open_clip's QuickGELU: x sigmoid(1.702 x), evaluated as x / (1 + exp(-1.702 x))
+ * Finite input gives finite output in both kinds (far out: x, or -0).  F % 4 == 0; ldu, ldo multiples of 4 (16-byte accesses);
+ * columns [F, ldo) of out are never written and columns [F, ldu) of u never read.  Any other kind is PMHIP_EINVAL. */
+int pmhip_gelu(const float* u, int ldu, void* out, int ldo, int out_dtype, int M, int F, int kind, pmhip_stream stream);
+
 /* Non-overlapping PxP patches of img[B,C,H,W] (fp32) as GEMM rows: out[B*(H/P)*(W/P), C*P*P],
  * column order (c, kh, kw) = the flattened Conv2d weight (stage1/layers.py:81-84,107). */
 int pmhip_patchify(const float* img, void* out, int out_dtype, int B, int C, int H, int W, int P,

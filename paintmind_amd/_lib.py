@@ -256,6 +256,10 @@ PROTOTYPES = {
     "pmhip_rmsnorm": (i32, [vp, vp, f32, vp, i32, i32, i32, vp]),
     "pmhip_geglu": (i32, [vp, i32, vp, i32, i32, i32, i32, vp]),
     "pmhip_attention_relbias": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    # the OpenCLIP text tower's own operators: causal attention, head split of a biased projection, the GELUs
+    "pmhip_attention_causal": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "pmhip_split_heads": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(vp), f32, vp]),
+    "pmhip_gelu": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

@@ -3,6 +3,7 @@
 // wave per 16 query rows of one (image, head), no LDS and no barrier.
 #include <math.h>
 
+#include "attn_wave16.h"
 #include "common.h"
 
 namespace {
@@ -86,41 +87,8 @@ __global__ __launch_bounds__(THREADS) void geglu_kernel(const float* __restrict_
 //   O^T tile dt: acc[r] = O[query c, dim 16 dt + 4 g + r] -> one 4-element store per tile.
 // Keys >= n (the image's count) get the score -inf; their K rows are never read (the row index is clamped to n - 1) and their V^T
 // elements are replaced by 0 on load (0 * NaN is NaN).  Queries >= L of the last tile repeat row L - 1 and are not stored.
+// pack_probs and load_vt live in attn_wave16.h: the causal kernel of clipops.hip uses them too.
 // ------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ uint4 pack_probs(const f32x4_t (&p)[Mma<T>::kElemsPerChunk / 4]);
-template <> __device__ __forceinline__ uint4 pack_probs<bf16_t>(const f32x4_t (&p)[2]) {
-    return make_uint4(pack_bf16x2(p[0][0], p[0][1]), pack_bf16x2(p[0][2], p[0][3]), pack_bf16x2(p[1][0], p[1][1]), pack_bf16x2(p[1][2], p[1][3]));
-}
-template <> __device__ __forceinline__ uint4 pack_probs<float>(const f32x4_t (&p)[1]) {
-    return make_uint4(__float_as_uint(p[0][0]), __float_as_uint(p[0][1]), __float_as_uint(p[0][2]), __float_as_uint(p[0][3]));
-}
-// the V^T operand chunk of dim row `vrow` for the block at k0: NT groups of 4 consecutive keys
-__device__ __forceinline__ uint4 load_vt(const bf16_t* vrow, int k0, int g, int n, bool full) {
-    uint32_t w[4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int key = k0 + 16 * t + 4 * g;
-        if (full) {
-            const uint2 x = *reinterpret_cast<const uint2*>(vrow + key);
-            w[2 * t] = x.x, w[2 * t + 1] = x.y;
-        } else {
-            uint32_t e[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) e[r] = key + r < n ? (uint32_t)vrow[key + r] : 0u;
-            w[2 * t] = e[0] | (e[1] << 16), w[2 * t + 1] = e[2] | (e[3] << 16);
-        }
-    }
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-__device__ __forceinline__ uint4 load_vt(const float* vrow, int k0, int g, int n, bool full) {
-    const int key = k0 + 4 * g;
-    if (full) return *reinterpret_cast<const uint4*>(vrow + key);
-    uint32_t e[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) e[r] = key + r < n ? __float_as_uint(vrow[key + r]) : 0u;
-    return make_uint4(e[0], e[1], e[2], e[3]);
-}
-
 template <typename T>
 __global__ __launch_bounds__(64) void attention_relbias_kernel(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ Vt,
                                                                T* __restrict__ out, int ldo, int heads, int L, int L_pad,

@@ -344,7 +344,7 @@ class Pipeline(nn.Module):
         self.vqgan.set_compute_dtype(dtype)
         for m in self.transformer.modules():
             m._pm_dtype = dtype
-        self.text_model._pm_dtype = dtype           # read by T5TextEmbedder(native=True) only: inert otherwise
+        self.text_model._pm_dtype = dtype           # read by T5TextEmbedder / CLIPTextEmbedder(native=True) only: inert otherwise
         self._pm_dtype = dtype
         return self
 

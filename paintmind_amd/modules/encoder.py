@@ -1,6 +1,7 @@
 """Text-conditioning producers (reference modules/encoder.py:18-104): the frozen towers are third-party
 pretrained models that stay on stock PyTorch-ROCm; the hot path only consumes their (B,77,ctx) output.  The one exception is opt-in:
-``T5TextEmbedder(native=True)`` runs the Flan-T5 encoder's arithmetic on the HIP kernels (``modules/t5_native.py``).
+``T5TextEmbedder(native=True)`` runs the Flan-T5 encoder's arithmetic on the HIP kernels (``modules/t5_native.py``), and
+``CLIPTextEmbedder(native=True)`` the OpenCLIP text tower's (``modules/clip_native.py``).
 
 Both wrappers keep the reference's attribute names (`transformer` for the T5 encoder, `model` for the CLIP tower),
 because those names are the checkpoint-key contract: a Pipeline state_dict carries `text_model.transformer.*`
@@ -236,7 +237,10 @@ class CLIPTextEmbedder(nn.Module):
     LAYERS = ("last", "penultimate")
 
     def __init__(self, arch=CLIP_ARCH, version=CLIP_VERSION, device=None, max_length=77, layer="last", precision='fp32',
-                 freeze=True, model=None, tokenizer=None):
+                 freeze=True, model=None, tokenizer=None, native=False):
+        """native: run the tower's arithmetic on the HIP kernels (``modules/clip_native.py``) when it lives on
+        a GPU -- on the CPU the stock tower runs, as everywhere in this package.  A tower the kernels do not serve is refused here
+        (ValueError naming what is wrong).  Off (the default): the stock tower, as before."""
         super().__init__()
         if layer not in self.LAYERS:
             raise ValueError(f"layer must be one of {self.LAYERS}, got {layer!r}")
@@ -255,10 +259,35 @@ class CLIPTextEmbedder(nn.Module):
         self.max_length = max_length
         self.layer = layer
         self.skip_last = {"last": 0, "penultimate": 1}[layer]
+        self._pm_dtype = torch.float32
+        self._native = None
+        if native:
+            self.use_native(True)
         if device is not None:
             self.to(device)
         if freeze:
             self.freeze()
+
+    def use_native(self, on=True):
+        """switch the HIP tower on or off; -> self"""
+        if on and self._native is None:
+            from .clip_native import NativeClipText
+            self._native = NativeClipText(self.model, self.skip_last)       # refuses what the kernels do not serve
+        elif not on:
+            self._native = None
+        return self
+
+    @property
+    def native(self):
+        return self._native is not None
+
+    @property
+    def compute_dtype(self):
+        """of the native tower (the stock tower computes in its parameters' dtype): ``_pm_dtype`` (``Pipeline.set_compute_dtype``), or
+        bfloat16 inside ``torch.autocast('cuda', bfloat16)``"""
+        if torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16:
+            return torch.bfloat16
+        return self._pm_dtype
 
     def freeze(self):
         self.model = self.model.eval()
@@ -283,6 +312,12 @@ class CLIPTextEmbedder(nn.Module):
         raise NotImplementedError("CLIPTextEmbedder serves no token ids (fragment_ids): T5TextEmbedder does")
 
     def encode_with_transformer(self, tokens):
+        """THE tower call: tokens int64 [B, n_ctx] on the tower's device -> [B, n_ctx, width]"""
+        if self._native is not None and tokens.is_cuda:
+            if self._native.model is not self.model:                # the tower was replaced after use_native()
+                self._native = None
+                self.use_native(True)
+            return self._native(tokens, dtype=self.compute_dtype)
         m = self.model
         x = m.token_embedding(tokens) + m.positional_embedding          # (B, n_ctx, width)
         blocks = list(m.transformer.resblocks)

@@ -878,6 +878,73 @@ def attention_relbias(q, k, vt, rel_bias, kv_lens=None, out=None):
     return out
 
 
+def attention_causal(q, k, vt, out=None):
+    """Causal self-attention (pmhip_attention_causal): q [B,H,L,64] ALREADY SCALED, k [B,H,Lp,64], vt [B,H,64,Lp] as gemm_heads /
+    split_heads write them; query q attends to the keys [0, q] -> [B*L, H*64].  `out` may be a column slice of a wider matrix."""
+    dev = _dev(q, k, vt)
+    lib = _lib.load()
+    B, H, L, dh = q.shape
+    if dh != 64:
+        raise ValueError(f"attention_causal: dim_head={dh} not served (64 only)")
+    if k.dtype != q.dtype or vt.dtype != q.dtype or tuple(k.shape) != (B, H, k.shape[2], 64) or tuple(vt.shape) != (B, H, 64, k.shape[2]):
+        raise ValueError(f"attention_causal: k / vt must be {q.dtype} [{B}, {H}, Lp, 64] / [{B}, {H}, 64, Lp], got {k.dtype} "
+                         f"{tuple(k.shape)} / {vt.dtype} {tuple(vt.shape)}")
+    if out is None:
+        out = torch.empty(B * L, H * 64, device=dev, dtype=q.dtype)
+    if not out.is_cuda or out.dtype != q.dtype or tuple(out.shape) != (B * L, H * 64) or out.stride(1) != 1:
+        raise ValueError(f"attention_causal: out must be {q.dtype} [{B * L}, {H * 64}] with unit column stride")
+    with torch.cuda.device(dev):
+        check(lib.pmhip_attention_causal(pm_dtype(q.dtype), _p(q), _p(k), _p(vt), _p(out), out.stride(0), B, H, L, k.shape[2],
+                                         stream_ptr(dev)), "pmhip_attention_causal")
+    return out
+
+
+def split_heads(u, heads, tokens, kinds, q_scale=1.0, dtype=torch.float32):
+    """Head split of a projection that already carries its bias (pmhip_split_heads): u f32 [M, len(kinds)*heads*64], the output of
+    one gemm(bias=) -> one `dtype` tensor per part, as gemm_heads returns them (Q [B,H,t,64] * q_scale, K [B,H,tp,64], V^T
+    [B,H,64,tp], tp = tokens rounded up to 64, the padding zero)."""
+    dev = _dev(u)
+    lib = _lib.load()
+    M, N = u.shape
+    if u.dtype != torch.float32 or N != len(kinds) * heads * 64 or M % tokens:
+        raise ValueError(f"split_heads: u must be float32 [B*{tokens}, {len(kinds)}*{heads}*64], got {u.dtype} {tuple(u.shape)}")
+    B = M // tokens
+    tp = round_up(tokens, 64)
+    outs = []
+    for kind in kinds:
+        if kind == PART_Q:
+            outs.append(torch.empty(B, heads, tokens, 64, device=dev, dtype=dtype))
+        elif kind == PART_K:
+            outs.append(torch.zeros(B, heads, tp, 64, device=dev, dtype=dtype))
+        else:
+            outs.append(torch.zeros(B, heads, 64, tp, device=dev, dtype=dtype))
+    kinds_c = (C.c_int * len(kinds))(*kinds)
+    outs_c = (C.c_void_p * len(kinds))(*[o.data_ptr() for o in outs])
+    with torch.cuda.device(dev):
+        check(lib.pmhip_split_heads(pm_dtype(dtype), _p(u), N, M, heads, tokens, tp, len(kinds), kinds_c, outs_c, float(q_scale),
+                                    stream_ptr(dev)), "pmhip_split_heads")
+    return outs
+
+
+GELU_KINDS = {"erf": 0, "quick": 1}
+
+
+def gelu(u, out_dtype=torch.float32, kind="erf"):
+    """pmhip_gelu on the f32 output of a GEMM that added its bias: kind "erf" is nn.GELU() (0.5 x erfc(-x / sqrt 2)), "quick" is
+    open_clip's QuickGELU (x / (1 + exp(-1.702 x))); u f32 [M, F], F % 4 == 0 -> `out_dtype` [M, F]"""
+    dev = _dev(u)
+    lib = _lib.load()
+    if kind not in GELU_KINDS:
+        raise ValueError(f"gelu: kind must be one of {sorted(GELU_KINDS)}, got {kind!r}")
+    if u.dim() != 2 or u.dtype != torch.float32:
+        raise ValueError(f"gelu: u must be float32 [M, F], got {u.dtype} {tuple(u.shape)}")
+    M, F = u.shape
+    out = torch.empty(M, F, device=dev, dtype=out_dtype)
+    with torch.cuda.device(dev):
+        check(lib.pmhip_gelu(_p(u), F, _p(out), F, pm_dtype(out_dtype), M, F, GELU_KINDS[kind], stream_ptr(dev)), "pmhip_gelu")
+    return out
+
+
 def patchify(img, patch, out_dtype=torch.float32):
     dev = _dev(img)
     lib = _lib.load()
