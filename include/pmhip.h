@@ -1436,6 +1436,34 @@ int pmhip_pipeline_generate_weights(pmhip_s2* s2, pmhip_vqgan* vq, int64_t* ids,
                                     const float* gscales_host, const uint8_t* ctx_seg_host, const uint32_t* tok_seg_host,
                                     const float* ctx_w_host);
 
+/* Canvases beyond the token grid (new entries within ABI 11, nothing existing changes meaning): overlapping
+ * model-sized windows over a larger canvas.  Both entries are gathers without atomics: two launches give the same bits.
+ *
+ * The canvas logits from the window logits.  win f32 [B * window_rows, V] with row stride ldw: canvas b's windows are the rows
+ * [b * window_rows, (b + 1) * window_rows), window w's token `local` at w * g^2 + local.  win_u (NULL: none) a second tensor of the
+ * same shape and stride with `scale` (finite): the element used is then fma(scale, c - u, u), the expression of
+ * pmhip_guidance_combine, formed at load.  cover int32 [Nc, K] and weight f32 [Nc, K] on the device, 1 <= K <= 16: for canvas token
+ * t the window rows that cover it.  out f32 [B * Nc, V] with row stride ldo:
+ *     out[b * Nc + t] = w_0 x_0, then fma(w_k, x_k, out), k ascending over the entries with 0 <= cover[t][k] < window_rows
+ *   - an entry outside [0, window_rows) is tested in front of its load and skipped: never an address, and the weight beside it is
+ *     never read into a result; a window row that no entry of a canvas row names never reaches that row, NaN included; a canvas row
+ *     without a valid entry is written as 0
+ *   - K = 1 with weight 1 is an exact copy; row offsets are 64-bit
+ *   - served: V % 4 == 0, ldw % 4 == 0, ldo % 4 == 0, both at least V, win / win_u / out 16-byte aligned; else PMHIP_EINVAL
+ *   - nothing outside the [B * Nc, V] extents of out is written; the inputs are left as they are */
+int pmhip_window_logits(const float* win, const float* win_u, float scale, int ldw, const int32_t* cover, const float* weight, int K,
+                        int window_rows, float* out, int ldo, int B, int Nc, int V, pmhip_stream stream);
+/* The canvas image from the decoded window images.  img f32 [B * ny * nx, C, S, S], canvas b's windows row-major in front of canvas
+ * b + 1's; ywin int32 [Hc, 4] / yw f32 [Hc, 4]: for every canvas row up to four (window index on the y axis, weight) pairs, ascending,
+ * padded with -1; xwin [Wc, 4] / xw [Wc, 4] likewise for the columns; yoff int32 [ny] / xoff int32 [nx]: the windows' offsets in
+ * pixels.  out f32 [B, C, Hc, Wc], contiguous:
+ *     out = sum over jy ascending (outside), jx ascending (inside) of rn(ay ax) * img[window (jy, jx)][c][y - yoff[jy]][x - xoff[jx]]
+ * the first product rounded, every later one a fused multiply-add; then the clamp of pmhip_unpatchify_clamp to [-1, 1] (a NaN stays
+ * a NaN).  An entry outside its axis' windows, or whose local coordinate falls outside [0, S), is tested in front of the load and
+ * skipped.  A pixel one window covers with weight 1 is that window's pixel, bit for bit (within [-1, 1]). */
+int pmhip_window_pixels(const float* img, const int32_t* ywin, const float* yw, const int32_t* xwin, const float* xw, const int32_t* yoff,
+                        const int32_t* xoff, float* out, int B, int C, int S, int ny, int nx, int Hc, int Wc, pmhip_stream stream);
+
 /* Per-kernel timing hook used by bench.py: when enabled, every kernel launch of the named family
  * is bracketed by hipEvents on its own stream and accumulated (count, total ms). */
 int pmhip_timing_enable(int on);

@@ -260,6 +260,9 @@ PROTOTYPES = {
     "pmhip_attention_causal": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "pmhip_split_heads": (i32, [i32, vp, i32, i32, i32, i32, i32, i32, C.POINTER(i32), C.POINTER(vp), f32, vp]),
     "pmhip_gelu": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    # canvases beyond the token grid: the fusion of window logits, the blend of decoded window pixels
+    "pmhip_window_logits": (i32, [vp, vp, f32, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, vp]),
+    "pmhip_window_pixels": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "pmhip_timing_enable": (i32, [i32]),
     "pmhip_timing_reset": (i32, []),
     "pmhip_timing_get": (i32, [C.c_char_p, C.POINTER(i32), C.POINTER(C.c_double)]),

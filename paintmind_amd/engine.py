@@ -328,16 +328,21 @@ class S2Engine:
             if cond:
                 return check(getattr(self.lib, name)(*head, *extra, *tail), name)
 
-    def forward(self, tokens, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, keys=None):
+    def forward(self, tokens, context=None, context_lens=None, context_segments=None, token_segments=None, context_weights=None, keys=None,
+                out=None):
         """context_segments / token_segments (None = the call as without them): regional prompts (pmhip_s2_forward_segments).
         context_weights (None = the call as without them): prompt weights (pmhip_s2_forward_weights).  keys (instead of the four
-        keywords): the call's checked ``ops.Keys``."""
+        keywords): the call's checked ``ops.Keys``.  out (None: a new tensor): where the logits go, a contiguous fp32 [B, tokens,
+        n_embed] tensor on the engine's device -- a slice of a larger buffer that several calls fill."""
         tokens = tokens.to(self.device, torch.float32).contiguous()
         B = tokens.shape[0]
         context, L = self._ctx(context)
         keys = self._keys(B, L, context_lens, context_segments, token_segments, context_weights, keys)
         lens, cs, ts, w = _key_args(keys, native_lens=False)
-        logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32)
+        logits = torch.empty(B, self.tokens, self.n_embed, device=self.device, dtype=torch.float32) if out is None else out
+        if (logits.dtype != torch.float32 or tuple(logits.shape) != (B, self.tokens, self.n_embed) or logits.device != tokens.device
+                or not logits.is_contiguous()):
+            raise ValueError(f"forward: out must be a contiguous fp32 [{B}, {self.tokens}, {self.n_embed}] tensor on {self.device}")
         with torch.cuda.device(self.device):
             self._call(((w is not None, "pmhip_s2_forward_weights", (cs, ts, w)),
                         (cs is not None, "pmhip_s2_forward_segments", (cs, ts)),

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, packing
+from .canvas import canvas_grid, canvas_layout
 from .config import ver2cfg
 from .engine import S2Engine
 from .stage2 import CondTransformer
@@ -121,6 +122,9 @@ def diff_draws(B, N, mask_ratio, draws, seed):
     starts = torch.tensor([(j * N) // draws for j in range(draws)], dtype=rank.dtype)
     return (rank[None] - starts[:, None, None]) % N < k
 
+
+# ``generate``'s keywords that ``generate_canvas`` refuses by name (a ValueError; any other unknown keyword is a TypeError)
+CANVAS_UNSERVED = ("regions", "prompt_weights", "context_weights", "context_segments", "token_segments", "context_lens", "negative_context_lens")
 
 MAX_REGIONS = 31           # segments 1..31 beside the global prompt's segment 0: one bit each of a token's 32-bit mask
 
@@ -1057,6 +1061,125 @@ class Pipeline(nn.Module):
             if return_steps:
                 revealed_at = torch.where((ids != self.mask_token_id) & (revealed_at == T), torch.full_like(revealed_at, step), revealed_at)
         return (ids, revealed_at) if return_steps else ids
+
+    # -- canvases beyond the token grid ---------------------------------------------------------------------
+    def canvas_layout(self, size, stride=None, fuse="uniform"):
+        """the ``canvas.CanvasLayout`` of a canvas of size = (H, W) pixels under this pipeline's windows; stride in tokens (None:
+        half a window)"""
+        g = self.image_size // self.patch_size
+        return canvas_layout(canvas_grid(size, self.patch_size), g, g // 2 if stride is None else stride, self.patch_size, fuse)
+
+    def _canvas_ids0(self, ids0, B, Nc):
+        """the start ids of a canvas call, checked on the host once: an integer tensor [B, Nc], every value a code or the mask id"""
+        if not isinstance(ids0, torch.Tensor) or ids0.dtype not in (torch.int64, torch.int32) or tuple(ids0.shape) != (B, Nc):
+            got = f"{ids0.dtype} {tuple(ids0.shape)}" if isinstance(ids0, torch.Tensor) else type(ids0).__name__
+            raise ValueError(f"canvas: ids0 must be an integer tensor [{B}, {Nc}], got {got}")
+        bad = ((ids0 < 0) | (ids0 > self.mask_token_id)).nonzero()
+        if len(bad):
+            b, i = bad[0].tolist()
+            raise ValueError(f"canvas: ids0: canvas {b}, token {i}: {int(ids0[b, i])} is outside [0, {self.mask_token_id}] (codes and the mask id)")
+        return ids0.to(torch.long)
+
+    @torch.no_grad()
+    def canvas_ids(self, context, B, layout, timesteps, temperature, topk, seed, image_base=0, guidance_scale=None, context_lens=None,
+                   choice_temperature=None, top_p=None, negative_context=None, negative_lens=None, ids0=None, window_batch=None):
+        """The decode loop of B CANVASES larger than the token grid on an explicit context -> (ids, merged),
+        int64 [B, Nc] each: the ids behind the last re-masking, and the last step's merged ids, every position filled.
+
+        layout (``canvas_layout``) lays overlapping model-sized windows over the canvas.  Every step gathers the windows' ids from
+        the canvas ids, runs the tower on the B * W windows -- every window of a canvas under that canvas's context, lengths and
+        negative context --, fuses the windows' logits into ONE row of logits per canvas token (``ops.window_logits``; a guided step
+        hands over both passes and the step's scale, so no combined window logits are written), and then takes one draw over the
+        B * Nc rows (the noise under row_base = image_base * Nc) and one re-masking over [B, Nc] with ``loop_schedule(T, temperature,
+        Nc, choice_temperature)``.  Overlapping windows therefore see the same token at every shared position at every step.
+
+        ids0 (None: all masked): int [B, Nc], a code or the mask id per position.  Positions that hold a code are kept: canvas b then
+        re-masks by ``edit_schedule`` over its own masked count, as ``edit`` does -- a given token is never re-masked and nothing
+        is left masked.  window_batch = n: the forward runs in chunks of at most n windows into one logits buffer; the engine may pick
+        another GEMM route per batch size, so results for different window_batch values are NOT promised to be bit-identical.
+        The other keywords: as in ``generate_ids``.  Eager; not served: the captured-graph loop, lanes, sessions, regions, weights."""
+        T, Nc, W = int(timesteps), layout.tokens, layout.n_windows
+        if layout.g * layout.g != self.num_tokens or layout.patch != self.patch_size:
+            raise ValueError(f"canvas_ids: the layout's windows ({layout.g} x {layout.g} tokens of {layout.patch} pixels) are not this pipeline's")
+        if window_batch is not None and (isinstance(window_batch, bool) or not isinstance(window_batch, int) or window_batch < 1):
+            raise ValueError(f"canvas_ids: window_batch {window_batch!r} must be a positive integer or None")
+        st = self._steps()
+        opts = self._options(topk, top_p, guidance_scale, context_lens, choice_temperature, context, B, negative_context, negative_lens, T)
+        per_window = lambda lens: None if lens is None else [n for n in lens for _ in range(W)]
+        context_w = st.context(None if context is None else context.repeat_interleave(W, 0))
+        negative_w = st.context(None if opts.negative is None else opts.negative.repeat_interleave(W, 0))
+        keys = self._host_keys(context_w, B * W, per_window(opts.lens))
+        negative_keys = None if negative_w is None else self._host_keys(negative_w, B * W, per_window(opts.negative_lens))
+        temps, nmask, ctemps = loop_schedule(T, temperature, Nc, opts.choice_temperature)
+        if ids0 is None:
+            ids, per_canvas = torch.full((B, Nc), self.mask_token_id, dtype=torch.long, device=st.device), None
+        else:
+            ids0 = self._canvas_ids0(ids0, B, Nc)
+            per_canvas = [edit_schedule(m, T) for m in (ids0 == self.mask_token_id).sum(1).tolist()]
+            ids = st.ids(ids0.clone())
+        if seed is None and not self._on_cpu():
+            seed = _draw_seed()
+        gather = st.ids(torch.from_numpy(np.array(layout.gather)))
+        merged = ids
+        for step in range(T):
+            tok = self.ids2tokens(ids[:, gather].reshape(B * W, self.num_tokens))
+            cond = st.forward_chunks(tok, context_w, keys, window_batch)
+            scale = opts.step_scale(step)
+            uncond = None if scale is None else st.forward_chunks(tok, negative_w, negative_keys, window_batch)
+            logits = st.window_logits(layout, cond, uncond, scale)
+            draw = st.canvas_draw(ids, logits, opts, temps[step], seed, step, image_base)
+            if step == T - 1:
+                merged = draw.merged.reshape(B, Nc).clone()    # (the re-masking works in place on the draw's merged ids)
+            ids = st.canvas_remask(draw, (B, Nc), nmask[step], None if per_canvas is None else [s[step] for s in per_canvas],
+                                   ctemps[step] if ctemps else 0.0, seed, step, image_base).reshape(B, Nc)
+        return ids, merged
+
+    @torch.no_grad()
+    def decode_canvas(self, ids, layout):
+        """canvas ids int64 [B, Nc] without a mask id -> the canvas image f32 [B, C, H, W]: the ids are gathered per window, every
+        window is decoded like an image of its own, and the windows' pixels are blended under the layout's separable tent weights
+        (``ops.window_pixels``): a pixel one window covers is that window's pixel"""
+        B, W = ids.shape[0], layout.n_windows
+        if tuple(ids.shape) != (B, layout.tokens):
+            raise ValueError(f"decode_canvas: ids must be [B, {layout.tokens}], got {tuple(ids.shape)}")
+        st = self._steps()
+        gather = st.ids(torch.from_numpy(np.array(layout.gather)))
+        imgs = self.vqgan.decode_from_indice(st.ids(ids)[:, gather].reshape(B * W, self.num_tokens))
+        return st.window_pixels(layout, imgs)
+
+    @torch.no_grad()
+    def generate_canvas(self, text, size, stride=None, timesteps=18, temperature=1.0, topk=5, seed=None, image_base=0, fuse="uniform",
+                        guidance_scale=None, negative_text=None, mask_padding=False, top_p=None, choice_temperature=None, ids0=None,
+                        window_batch=None, return_ids=False, **unserved):
+        """A picture LARGER than the model's square (extension): size = (H, W) pixels, multiples of the patch
+        size and at least the model's image on both axes, at most 4096 tokens -- a panorama, a 512 x 512, an image extended to three
+        times its width.  Overlapping model-sized windows, `stride` tokens apart (None: half a window), are laid over the canvas; the
+        tower runs on every window and the windows' LOGITS are fused per canvas token -- ``fuse`` "uniform": the mean over the windows
+        that cover it, "tent": weighted towards a window's centre --, so one draw and one re-masking are taken over the whole canvas
+        (``canvas_ids`` has the step).  The image is decoded per window from the last step's merged ids and the windows' pixels are
+        blended (``decode_canvas``).  -> img f32 [B, 3, H, W] on the pipeline's device; with return_ids (img, final ids [B, Gh * Gw]).
+
+        ids0 (None: everything is generated): int [B, Gh * Gw] with the mask id where a token is to be generated; the other
+        positions are kept as they are.  A 256-pixel image's ``vqgan.encode`` ids placed into a wide all-mask canvas are extended.
+        text, guidance_scale (a number or one per step), negative_text, mask_padding, topk, top_p, choice_temperature, temperature,
+        seed, image_base: as in ``generate``; canvas j of a batch is the call with image_base + j alone.  window_batch = n: at most n
+        windows per forward (memory); results for different values are not promised to be bit-identical (the engine may pick another
+        GEMM route per batch size).  Not served, a ValueError: regions, prompt weights, segment arrays, context lengths by hand."""
+        for name in sorted(unserved):
+            if name not in CANVAS_UNSERVED:                    # (a misspelt keyword is what it is anywhere else)
+                raise TypeError(f"generate_canvas() got an unexpected keyword argument {name!r}")
+            raise ValueError(f"generate_canvas: {name} is not served on a canvas (regions, prompt weights, segment arrays and context lengths "
+                             f"by hand are not parameters of generate_canvas)")
+        layout = self.canvas_layout(size, stride, fuse)
+        B = len(text)
+        context, context_lens = self.text_model(text, return_lens=True) if mask_padding else (self.text_model(text), None)
+        if negative_text is not None and context is None:
+            raise ValueError("negative_text needs a text condition (an unconditional pipeline has none)")
+        negative, negative_lens = self._negative_context(negative_text, B, mask_padding)
+        ids, merged = self.canvas_ids(context, B, layout, timesteps, temperature, topk, seed, image_base, guidance_scale, context_lens,
+                                      choice_temperature, top_p, negative, negative_lens, ids0, window_batch)
+        img = self.decode_canvas(merged, layout)
+        return (img, ids) if return_ids else img
 
     def _remask_cpu(self, ids, scores, nm, g, choice_t=0.0, choice_noise=None, counts=None):
         """the second half of ``_tail_cpu``: the re-masking of the merged ids under their scores -> ids"""

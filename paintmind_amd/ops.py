@@ -1290,6 +1290,131 @@ def token_logprob(logits, target, uncond=None, scale=None, ids=None, mask_id=Non
     return tuple(out)
 
 
+class CanvasTables(NamedTuple):
+    """the tables of a ``canvas.CanvasLayout`` on one device, as the two canvas operators take them"""
+    cover: torch.Tensor        # int32 [Nc, K]
+    weight: torch.Tensor       # f32 [Nc, K]
+    gather: torch.Tensor       # int64 [W, g^2]
+    ywin: torch.Tensor         # int32 [Hc, 4]
+    yw: torch.Tensor           # f32 [Hc, 4]
+    xwin: torch.Tensor         # int32 [Wc, 4]
+    xw: torch.Tensor           # f32 [Wc, 4]
+    yoff: torch.Tensor         # int32 [ny]
+    xoff: torch.Tensor         # int32 [nx]
+
+
+_canvas_tables = {}
+
+
+def canvas_tables(layout, device):
+    """``CanvasTables`` of `layout` on `device`: copied once per (layout, device) and kept as long as the layout lives"""
+    import weakref
+    key = (id(layout), str(device))
+    hit = _canvas_tables.get(key)
+    if hit is None or hit[0]() is not layout:
+        arrays = (layout.cover, layout.weight, layout.gather, *layout.pixel_y, *layout.pixel_x, layout.pixel_off_y, layout.pixel_off_x)
+        tables = CanvasTables(*(torch.from_numpy(np.array(a)).to(device).contiguous() for a in arrays))
+        _canvas_tables[key] = hit = (weakref.ref(layout, lambda _, k=key: _canvas_tables.pop(k, None)), tables)
+    return hit[1]
+
+
+def window_logits(win, cover, weight, window_rows, uncond=None, scale=None, out=None):
+    """The canvas logits from the window logits (pmhip_window_logits).  win fp32 [B * window_rows, V] on the
+    device, unit column stride, a row stride that is a multiple of 4 elements: canvas b's window rows are [b * window_rows, (b + 1) *
+    window_rows).  cover int32 [Nc, K] / weight fp32 [Nc, K] (1 <= K <= 16; ``canvas_tables``): the window rows that cover canvas
+    token t, ascending, padded with -1.  uncond (fp32, win's shape and strides) with scale (a finite number; the two come together):
+    the element used is uncond + scale * (win - uncond), formed at load by ``guidance_combine``'s expression, bit for bit.
+    -> out fp32 [B * Nc, V] (None: a new contiguous tensor; else unit column stride and a row stride that is a multiple of 4):
+    out[b * Nc + t] = w_0 x_0, then fma(w_k, x_k, .) over the entries in [0, window_rows), ascending.  An entry outside that range is
+    skipped in front of its load.  Deterministic: two calls give the same bits.  Every argument fault is a ValueError in front of the
+    launch."""
+    for name, x in (("win", win), ("uncond", uncond)):
+        if x is not None and (not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32):
+            raise ValueError(f"window_logits: {name} must be an fp32 [rows, V] tensor, got "
+                             f"{(x.dtype, tuple(x.shape)) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if win is None:
+        raise ValueError("window_logits: win must be an fp32 [rows, V] tensor, got None")
+    dev = win.device
+    M, V = win.shape
+    window_rows = int(window_rows)
+    if window_rows < 1 or M == 0 or M % window_rows:
+        raise ValueError(f"window_logits: the {M} rows of win must be a positive multiple of window_rows={window_rows}")
+    B = M // window_rows
+    if V == 0 or V % 4:
+        raise ValueError(f"window_logits: V={V} must be a positive multiple of 4")
+    if (uncond is None) != (scale is None):
+        raise ValueError("window_logits: uncond and scale come together (neither: the plain window logits are fused)")
+    if uncond is not None:
+        if tuple(uncond.shape) != (M, V) or uncond.device != dev:
+            raise ValueError(f"window_logits: uncond must be an fp32 [{M}, {V}] tensor on win's device, got {tuple(uncond.shape)} on {uncond.device}")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale):
+            raise ValueError(f"window_logits: scale {scale!r} must be a finite number")
+    ldw = win.stride(0) if M > 1 else V
+    for name, x in (("win", win), ("uncond", uncond)):
+        if x is not None and (x.stride(1) != 1 or (M > 1 and x.stride(0) != ldw) or ldw < V or ldw % 4 or x.data_ptr() % 16):
+            raise ValueError(f"window_logits: {name} must have unit column stride, the common row stride (a multiple of 4, at least V={V}) and "
+                             f"16-byte alignment, got strides {tuple(x.stride())}")
+    if not (isinstance(cover, torch.Tensor) and cover.dtype == torch.int32 and cover.dim() == 2 and cover.is_contiguous() and cover.device == dev
+            and 1 <= cover.shape[1] <= 16 and cover.shape[0] > 0):
+        raise ValueError("window_logits: cover must be a contiguous int32 [Nc, K] tensor on win's device, 1 <= K <= 16")
+    Nc, K = cover.shape
+    if not (isinstance(weight, torch.Tensor) and weight.dtype == torch.float32 and tuple(weight.shape) == (Nc, K) and weight.is_contiguous()
+            and weight.device == dev):
+        raise ValueError(f"window_logits: weight must be a contiguous fp32 [{Nc}, {K}] tensor on win's device")
+    if not win.is_cuda:                                        # (behind the argument checks: those hold without a device)
+        raise _lib.PmhipError("paintmind_amd runs only on a ROCm device (got a CPU tensor); there is no CPU fallback")
+    rows = B * Nc
+    if out is None:
+        out = torch.empty(rows, V, device=dev, dtype=torch.float32)
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (rows, V) and out.device == dev
+            and out.stride(1) == 1 and (rows == 1 or (out.stride(0) >= V and out.stride(0) % 4 == 0)) and out.data_ptr() % 16 == 0):
+        raise ValueError(f"window_logits: out must be an fp32 [{rows}, {V}] tensor on win's device with unit column stride, a row stride that is a "
+                         f"multiple of 4 and 16-byte alignment")
+    ldo = out.stride(0) if rows > 1 else V
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_window_logits(_p(win), _p(uncond), float(scale or 0.0), int(ldw), _p(cover), _p(weight), K, window_rows, _p(out),
+                                              int(ldo), B, Nc, V, stream_ptr(dev)), "pmhip_window_logits")
+    return out
+
+
+def window_pixels(img, tables, out=None):
+    """The canvas image from the decoded window images (pmhip_window_pixels).  img fp32 [B * W, C, S, S] on the
+    device, canvas b's W = ny * nx windows row-major in front of canvas b + 1's; tables: the layout's ``CanvasTables`` on that device
+    (``canvas_tables``).  -> out fp32 [B, C, Hc, Wc]: per pixel the sum over the windows that cover it of rn(ay ax) * pixel, rows
+    ascending outside and columns ascending inside, fused multiply-adds behind the first product, clamped to [-1, 1] like
+    ``unpatchify_clamp``.  A pixel one window covers is that window's pixel, bit for bit."""
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.dtype != torch.float32 or img.shape[2] != img.shape[3]:
+        raise ValueError(f"window_pixels: img must be an fp32 [B * W, C, S, S] tensor, got "
+                         f"{(img.dtype, tuple(img.shape)) if isinstance(img, torch.Tensor) else type(img).__name__}")
+    if not isinstance(tables, CanvasTables):
+        raise ValueError(f"window_pixels: tables must be the layout's CanvasTables (canvas_tables), got {type(tables).__name__}")
+    ny, nx, Hc, Wc = tables.yoff.shape[0], tables.xoff.shape[0], tables.ywin.shape[0], tables.xwin.shape[0]
+    for name, x, dt, shape in (("ywin", tables.ywin, torch.int32, (Hc, 4)), ("yw", tables.yw, torch.float32, (Hc, 4)),
+                               ("xwin", tables.xwin, torch.int32, (Wc, 4)), ("xw", tables.xw, torch.float32, (Wc, 4)),
+                               ("yoff", tables.yoff, torch.int32, (ny,)), ("xoff", tables.xoff, torch.int32, (nx,))):
+        if x.dtype != dt or tuple(x.shape) != shape or not x.is_contiguous() or x.device != img.device:
+            raise ValueError(f"window_pixels: tables.{name} must be a contiguous {dt} {list(shape)} tensor on img's device, got {x.dtype} "
+                             f"{tuple(x.shape)} on {x.device}")
+    n, Cc, S, _ = img.shape
+    if n == 0 or ny == 0 or nx == 0 or n % (ny * nx):
+        raise ValueError(f"window_pixels: {n} window images are no positive multiple of the layout's {ny} x {nx} windows")
+    B = n // (ny * nx)
+    if Hc < S or Wc < S:
+        raise ValueError(f"window_pixels: the canvas {Hc} x {Wc} is smaller than a window image ({S} x {S})")
+    if not img.is_contiguous():
+        raise ValueError("window_pixels: img must be contiguous")
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == (B, Cc, Hc, Wc)
+                                and out.is_contiguous() and out.device == img.device):
+        raise ValueError(f"window_pixels: out must be a contiguous fp32 [{B}, {Cc}, {Hc}, {Wc}] tensor on img's device")
+    dev = _dev(img)
+    if out is None:
+        out = torch.empty(B, Cc, Hc, Wc, device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        check(_lib.load().pmhip_window_pixels(_p(img), _p(tables.ywin), _p(tables.yw), _p(tables.xwin), _p(tables.xw), _p(tables.yoff),
+                                              _p(tables.xoff), _p(out), B, Cc, S, ny, nx, Hc, Wc, stream_ptr(dev)), "pmhip_window_pixels")
+    return out
+
+
 def choice_t(value, what="choice_temperature"):
     """a step's choice temperature (None = 0) -> a float, checked as the native entries check it: finite, 0 <= t <= CHOICE_T_MAX"""
     t = 0.0 if value is None else float(value)

@@ -4,8 +4,10 @@ a pipeline on the CPU (the plain-torch primitives ``Pipeline._*_cpu``, reached t
 ``HipSteps`` for a pipeline with an engine (``S2Engine`` and ``ops.*``).  ``Pipeline._steps`` picks one; a flow is written once
 against either.  What differs between the two stays in here: the generator against Philox (``Draw.rng``), a bool region against a
 uint8 one, a blend that returns against one in place, float accumulators against kernel-side ``accumulate=True``."""
+import functools
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import ops
@@ -17,6 +19,17 @@ class Draw(NamedTuple):
     merged: torch.Tensor
     score: torch.Tensor
     rng: Optional[torch.Generator]     # the generator the draw used, which the re-masking draws from next; None: no seed, or Philox
+
+
+@functools.lru_cache(maxsize=8)
+def _torch_tables(layout):
+    """a ``canvas.CanvasLayout``'s tables as CPU tensors, built once per layout (it hashes by identity): cover int64 [Nc, K], weight
+    f32 [Nc, K], and per pixel axis the dense f32 [windows, extent] weight of every window, 0 where it does not cover"""
+    def dense(table, n):
+        win, w = (torch.from_numpy(np.array(a)) for a in table)
+        return torch.stack([(w * (win == j)).sum(1) for j in range(n)])
+    return (torch.from_numpy(np.array(layout.cover)).long(), torch.from_numpy(np.array(layout.weight)),
+            dense(layout.pixel_y, len(layout.offsets_y)), dense(layout.pixel_x, len(layout.offsets_x)))
 
 
 class TorchSteps:
@@ -89,6 +102,61 @@ class TorchSteps:
 
     def logprob_finish(self, acc):
         return tuple(a / acc[0][3] for a in acc[0][:3])
+
+    # -- canvases beyond the token grid ---------------------------------------------------------------------
+    def forward_chunks(self, tok, context, keys, chunk):
+        """``forward`` over the windows of a canvas call, at most `chunk` windows at a time (None: all at once) -> one logits tensor"""
+        n = tok.shape[0]
+        if not chunk or chunk >= n:
+            return self.forward(tok, context, keys)
+        return torch.cat([self.forward(tok[lo:lo + chunk], None if context is None else context[lo:lo + chunk],
+                                       None if keys is None else keys.lane(lo, min(n, lo + chunk))) for lo in range(0, n, chunk)])
+
+    def window_logits(self, layout, cond, uncond, scale):
+        """``ops.window_logits`` in plain torch, the same order of operations: the window logits [B * W, g^2, V] (with uncond and scale:
+        guided at load) -> the canvas logits [B, Nc, V]; w_0 x_0, then + w_k x_k over the windows that cover a token, ascending"""
+        x = cond if uncond is None else self.guide(cond, uncond, scale)
+        x = x.reshape(-1, layout.window_rows, x.shape[-1])
+        cover, weight = _torch_tables(layout)[:2]
+        acc = weight[:, 0, None] * x[:, cover[:, 0]]
+        for k in range(1, layout.K):
+            on = cover[:, k] >= 0
+            acc = torch.where(on[None, :, None], acc + weight[:, k, None] * x[:, cover[:, k].clamp(min=0)], acc)
+        return acc
+
+    def window_pixels(self, layout, imgs):
+        """``ops.window_pixels`` in plain torch, the same order of operations: the decoded windows [B * W, C, S, S] -> [B, C, Hc, Wc]"""
+        (Hc, Wc), S = layout.size, layout.g * layout.patch
+        ny, nx = len(layout.offsets_y), len(layout.offsets_x)
+        imgs = imgs.reshape(-1, ny, nx, imgs.shape[1], S, S)
+        out = torch.zeros(imgs.shape[0], imgs.shape[3], Hc, Wc)
+        seen = torch.zeros(Hc, Wc, dtype=torch.bool)
+        wy, wx = _torch_tables(layout)[2:]
+        for jy, oy in enumerate(layout.pixel_off_y.tolist()):
+            for jx, ox in enumerate(layout.pixel_off_x.tolist()):
+                w = wy[jy, oy:oy + S, None] * wx[jx, None, ox:ox + S]
+                term, at = w * imgs[:, jy, jx], (slice(None), slice(None), slice(oy, oy + S), slice(ox, ox + S))
+                out[at] = torch.where(seen[oy:oy + S, ox:ox + S], out[at] + term, term)
+                seen[oy:oy + S, ox:ox + S] = True
+        return out.clamp(-1.0, 1.0)
+
+    def canvas_draw(self, ids, logits, opts, temperature, seed, step, image_base):
+        """one draw over the canvases [B, Nc].  Every canvas draws from a generator of its own, seeded seed + step + 2^32 (image_base
+        + j): canvas j of a batch is the call with image_base + j alone, and canvas 0 at image_base 0 draws what ``draw`` draws"""
+        if seed is None:
+            return self.draw(ids, logits, opts, temperature, None, None, step, image_base)
+        parts = [self.pipe._draw_cpu(ids[j:j + 1], logits[j:j + 1], opts.topk, temperature, None, seed + step + ((image_base + j) << 32), opts.top_p)
+                 for j in range(ids.shape[0])]
+        return Draw(*(torch.cat([p[i] for p in parts]) for i in range(3)), [p[3] for p in parts])
+
+    def canvas_remask(self, draw, shape, nm, counts, choice_t, seed, step, image_base):
+        """one re-masking over the canvases, shape = (B, Nc): nm positions each, or counts[b] (a list of B ints) where given"""
+        B = shape[0]
+        counts = [nm] * B if counts is None else counts
+        if not isinstance(draw.rng, list):
+            return self.pipe._remask_cpu(draw.merged, draw.score, nm, draw.rng, choice_t, None, counts)
+        return torch.cat([self.pipe._remask_cpu(draw.merged[j:j + 1], draw.score[j:j + 1], nm, draw.rng[j], choice_t, None, counts[j:j + 1])
+                          for j in range(B)])
 
 
 class HipSteps:
@@ -169,3 +237,40 @@ class HipSteps:
     def logprob_finish(self, acc):
         count = acc[0][3].float()
         return tuple((a.float() / count).reshape(acc[1].shape) for a in acc[0][:3])
+
+    # -- canvases beyond the token grid ---------------------------------------------------------------------
+    def forward_chunks(self, tok, context, keys, chunk):
+        """``forward`` over the windows of a canvas call, at most `chunk` windows at a time (None: all at once) into ONE logits buffer"""
+        n = tok.shape[0]
+        if not chunk or chunk >= n:
+            return self.forward(tok, context, keys)
+        out = torch.empty(n, self.eng.tokens, self.eng.n_embed, device=self.device, dtype=torch.float32)
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            self.eng.forward(tok[lo:hi], None if context is None else context[lo:hi], keys=None if keys is None else keys.lane(lo, hi),
+                             out=out[lo:hi])
+        return out
+
+    def window_logits(self, layout, cond, uncond, scale):
+        """the window logits [B * W, g^2, V] (with uncond and scale: guided at load, no combined window logits are written) -> the
+        canvas logits [B * Nc, V]"""
+        tables = ops.canvas_tables(layout, self.device)
+        V = cond.shape[-1]
+        return ops.window_logits(cond.reshape(-1, V), tables.cover, tables.weight, layout.window_rows,
+                                 uncond=None if uncond is None else uncond.reshape(-1, V), scale=None if uncond is None else float(scale))
+
+    def window_pixels(self, layout, imgs):
+        return ops.window_pixels(imgs.contiguous(), ops.canvas_tables(layout, self.device))
+
+    def canvas_draw(self, ids, logits, opts, temperature, seed, step, image_base):
+        """one draw over the B * Nc rows of the canvases [B, Nc]: Philox under row_base = image_base * Nc"""
+        return self.draw(ids, logits, opts, temperature, None, seed, step, image_base)
+
+    def canvas_remask(self, draw, shape, nm, counts, choice_t, seed, step, image_base):
+        """one re-masking over the canvases, shape = (B, Nc): nm positions each, or counts[b] (a list of B ints) where given"""
+        B, N = shape
+        merged, score = draw.merged.reshape(B, N), draw.score.reshape(B, N)
+        if counts is None:
+            return ops.remask(merged, score, nm, self.pipe.mask_token_id, choice_temperature=choice_t, seed=seed, step=step, row_base=image_base * N)
+        return ops.remask_counts(merged, score, torch.tensor(counts, dtype=torch.int32, device=self.device), self.pipe.mask_token_id,
+                                 choice_temperature=choice_t, seed=seed, step=step, row_base=image_base * N)
